@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define MCG_ABI_VERSION 13
+#define MCG_ABI_VERSION 14
 
 enum { MCG_OK = 0, MCG_ERR_ARG = 1, MCG_ERR_HIP = 2, MCG_ERR_UNSUPPORTED = 3, MCG_ERR_WORKSPACE = 4 };
 /* MCG_F16X3: the parity-grade fast mode.  Activations, biases and every non-GEMM kernel are exactly those of MCG_F32 (4-byte
@@ -148,6 +148,14 @@ int mcg_stem_forward(mcg_stream s, mcg_dtype dt, const float* img, const void* w
 int mcg_roi_align(mcg_stream s, mcg_dtype dt, const void* const feats[4], const int feat_h[4], const int feat_w[4],
                   const int strides[4], int C, const float* boxes, int num_boxes, int boxes_per_frame,
                   void* out, int32_t* levels_out);
+/* ABI 14: mcg_roi_align over window frames gathered from a pyramid STORE -- box row r reads pyramid row frame_of[r / boxes_per_frame]
+ * of feats [pyramid_frames][h][w][C] (frame_of: DEVICE int32 [num_boxes / boxes_per_frame]).  Replaces the same call site as
+ * mcg_roi_align, for a caller that holds each distinct video frame once although windows overlap (the reference's harness runs the whole
+ * model per window: tools/test_gaze360_gaze.py:72-111).  An entry outside [0, pyramid_frames) reads nothing (the address is clamped)
+ * and that box's output is NaN: a guard for callers, not a feature.  Bits equal mcg_roi_align's on the gathered rows. */
+int mcg_roi_align_indexed(mcg_stream s, mcg_dtype dt, const void* const feats[4], const int feat_h[4], const int feat_w[4],
+                          const int strides[4], int C, const float* boxes, int num_boxes, int boxes_per_frame,
+                          const int32_t* frame_of, int pyramid_frames, void* out, int32_t* levels_out);
 
 /* ---------------------------------------------------------------- decoder stage / gaze head / whole path
  * Weight tables are arrays of device pointers indexed by the enums below.  Matrices are
@@ -279,7 +287,7 @@ typedef struct mcg_engine mcg_engine;
  *     mcg_engine_set_option / mcg_engine_profile_* take the engine's mutex for the duration of the ENQUEUE (they never wait for
  *     the GPU): two host threads calling into the same engine are serialised silently, in lock order, and both calls are
  *     correct -- but they share the engine's fork / join events and the caller-provided workspace, so they must not pass the
- *     same workspace unless they also enqueue on the same stream.  mcg_decoder_forward touches no engine state beyond the
+ *     same workspace unless they also enqueue on the same stream.  mcg_decoder_forward(_indexed) touches no engine state beyond the
  *     (immutable) weight tables and does not take the mutex: it may run on another thread / stream beside the trunk of the
  *     next batch (mcgaze_amd/engine.py: PipelinedRunner) as long as its workspace and pyramid are its own.
  *     For concurrent forwards on one device use one engine per thread (weights may be shared: the engine copies only the
@@ -343,6 +351,19 @@ size_t mcg_trunk_workspace_bytes(const mcg_engine* e, int num_frames, int H, int
 size_t mcg_decoder_workspace_bytes(const mcg_engine* e, int num_frames);
 int mcg_decoder_forward(mcg_engine* e, mcg_stream s, const void* const pyramid[4], int num_frames, int clip_length, int H, int W,
                         const int* img_hw, float* gaze_out, float* boxes_out, float* scores_out, void* ws, size_t ws_bytes);
+/* ABI 14: mcg_decoder_forward over window frames gathered from a pyramid STORE: pyramid[i] holds pyramid_frames rows
+ * [pyramid_frames][(H/4) >> i][(W/4) >> i][256] (e.g. one row per distinct frame of overlapping windows, each written once by
+ * mcg_backbone_fpn_forward at a row offset), and window frame n (n < num_frames = windows * clip_length) reads row frame_of[n]
+ * (DEVICE int32 [num_frames]).  img_hw, when given, is indexed by pyramid ROW: [pyramid_frames][2].  Replaces, like mcg_decoder_forward,
+ * MultiClueGazeROIHead.simple_test (multiclue_gaze_roi_head.py:287-384) -- per window of the reference's sliding-window harness
+ * (tools/test_gaze360_gaze.py:72-111), whose trunk it no longer repeats for the frames windows share.  The gather is done by the
+ * RoIAlign reads and the query init; workspace = mcg_decoder_workspace_bytes(e, num_frames).  Outputs are bit for bit those of
+ * mcg_decoder_forward on a pyramid holding the gathered rows in window order.  An entry outside [0, pyramid_frames) is read as no row
+ * (clamped address) and gives that frame NaN boxes and features: a guard, callers range-check (mcgaze_amd/engine.py::HipEngine.decode).
+ * mcg_decoder_forward is this call with frame_of = NULL (row n for frame n, pyramid_frames = num_frames). */
+int mcg_decoder_forward_indexed(mcg_engine* e, mcg_stream s, const void* const pyramid[4], int pyramid_frames, const int32_t* frame_of,
+                                int num_frames, int clip_length, int H, int W, const int* img_hw, float* gaze_out, float* boxes_out,
+                                float* scores_out, void* ws, size_t ws_bytes);
 /* Whole path = mcg_backbone_fpn_forward + mcg_decoder_forward on one stream; ws >= mcg_engine_workspace_bytes. */
 int mcg_clip_forward(mcg_engine* e, mcg_stream s, const float* img, int num_frames, int clip_length, int H, int W,
                      const int* img_hw, int chunk_frames, float* gaze_out, float* boxes_out, float* scores_out,

@@ -502,8 +502,12 @@ __global__ __launch_bounds__(256) void gaze_tail_kernel(const T* __restrict__ fe
 // ------------------------------------------------------------------------------------------------
 // Query init (fixed_embedding_rpn_head.py:76-94): boxes = cxcywh->xyxy(E) * (w,h,w,h) per frame,
 // object features = E_feat broadcast to every frame.  img_hw (device, [N][2]) may be null = (H, W).
+// Indexed form (frame_of != NULL, mcg_decoder_forward_indexed): img_shape is a property of the FRAME, so window frame n reads
+// img_hw[frame_of[n]] of a table with one row per pyramid row; an index outside [0, pyramid_frames) reads no table row and gives the
+// frame NaN boxes (its RoIAlign output is NaN too, roi_align.hip).
 template <typename T>
 __global__ void init_queries_kernel(const float* __restrict__ init_boxes, const T* __restrict__ init_feats, const int* __restrict__ img_hw,
+                                    const int32_t* __restrict__ frame_of, int pyramid_frames,
                                     int H, int W, float* __restrict__ boxes, T* __restrict__ obj, int N) {
   const long long total = (long long)N * 3 * 256;
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
@@ -511,10 +515,17 @@ __global__ void init_queries_kernel(const float* __restrict__ init_boxes, const 
     const int n = (int)(i / (3 * 256));
     obj[i] = init_feats[q * 256 + d];
     if (d < 4) {
-      const float h = img_hw ? (float)img_hw[n * 2] : (float)H, w = img_hw ? (float)img_hw[n * 2 + 1] : (float)W;
+      int r = n;
+      bool bad_row = false;
+      if (frame_of) {
+        r = frame_of[n];
+        bad_row = r < 0 || r >= pyramid_frames;
+        if (bad_row) r = 0;
+      }
+      const float h = img_hw ? (float)img_hw[r * 2] : (float)H, w = img_hw ? (float)img_hw[r * 2 + 1] : (float)W;
       const float cx = init_boxes[q * 4], cy = init_boxes[q * 4 + 1], bw = init_boxes[q * 4 + 2], bh = init_boxes[q * 4 + 3];
       const float v = d == 0 ? (cx - 0.5f * bw) * w : d == 1 ? (cy - 0.5f * bh) * h : d == 2 ? (cx + 0.5f * bw) * w : (cy + 0.5f * bh) * h;
-      boxes[((long long)n * 3 + q) * 4 + d] = v;
+      boxes[((long long)n * 3 + q) * 4 + d] = bad_row ? __builtin_nanf("") : v;
     }
   }
 }
@@ -547,8 +558,8 @@ static StageWs stage_layout(mcg_dtype dt, int N, char* base) {
 extern "C" size_t mcg_stage_workspace_bytes(mcg_dtype dt, int num_frames) { return stage_layout(dt, num_frames, nullptr).total; }
 
 int launch_roi_align(hipStream_t s, mcg_dtype dt, const void* const feats[4], const int feat_h[4], const int feat_w[4],
-                     const int strides[4], int C, const float* boxes, int num_boxes, int boxes_per_frame, void* out,
-                     int32_t* levels_out);
+                     const int strides[4], int C, const float* boxes, int num_boxes, int boxes_per_frame, const int32_t* frame_of,
+                     int pyramid_frames, void* out, int32_t* levels_out);
 
 template <typename T>
 static void launch_attn(hipStream_t s, const void* qkv, void* out, int groups, int L, int temporal, int clip_len) {
@@ -740,13 +751,13 @@ int gaze_head_ctx(hipStream_t s, mcg_dtype dt, const void* const W[MCG_GW_COUNT]
 }
 
 // exported to engine.hip
-int launch_init_queries(hipStream_t s, mcg_dtype dt, const float* init_boxes, const void* init_feats, const int* img_hw, int H, int W,
-                        float* boxes, void* obj, int N) {
+int launch_init_queries(hipStream_t s, mcg_dtype dt, const float* init_boxes, const void* init_feats, const int* img_hw,
+                        const int32_t* frame_of, int pyramid_frames, int H, int W, float* boxes, void* obj, int N) {
   const long long total = (long long)N * 3 * 256;
   const int grid = (int)((total + 255) / 256 > 4096 ? 4096 : (total + 255) / 256);
-  if (dt == MCG_BF16) hipLaunchKernelGGL(init_queries_kernel<bf16_t>, dim3(grid), dim3(256), 0, s, init_boxes, (const bf16_t*)init_feats, img_hw, H, W, boxes, (bf16_t*)obj, N);
-  else if (dt == MCG_F16) hipLaunchKernelGGL(init_queries_kernel<f16_t>, dim3(grid), dim3(256), 0, s, init_boxes, (const f16_t*)init_feats, img_hw, H, W, boxes, (f16_t*)obj, N);
-  else hipLaunchKernelGGL(init_queries_kernel<float>, dim3(grid), dim3(256), 0, s, init_boxes, (const float*)init_feats, img_hw, H, W, boxes, (float*)obj, N);
+  if (dt == MCG_BF16) hipLaunchKernelGGL(init_queries_kernel<bf16_t>, dim3(grid), dim3(256), 0, s, init_boxes, (const bf16_t*)init_feats, img_hw, frame_of, pyramid_frames, H, W, boxes, (bf16_t*)obj, N);
+  else if (dt == MCG_F16) hipLaunchKernelGGL(init_queries_kernel<f16_t>, dim3(grid), dim3(256), 0, s, init_boxes, (const f16_t*)init_feats, img_hw, frame_of, pyramid_frames, H, W, boxes, (f16_t*)obj, N);
+  else hipLaunchKernelGGL(init_queries_kernel<float>, dim3(grid), dim3(256), 0, s, init_boxes, (const float*)init_feats, img_hw, frame_of, pyramid_frames, H, W, boxes, (float*)obj, N);
   MCG_CHECK_LAUNCH("init_queries");
   return MCG_OK;
 }

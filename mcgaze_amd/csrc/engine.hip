@@ -23,10 +23,10 @@
 #include <vector>
 
 int launch_roi_align(hipStream_t s, mcg_dtype dt, const void* const feats[4], const int feat_h[4], const int feat_w[4],
-                     const int strides[4], int C, const float* boxes, int num_boxes, int boxes_per_frame, void* out,
-                     int32_t* levels_out);
-int launch_init_queries(hipStream_t s, mcg_dtype dt, const float* init_boxes, const void* init_feats, const int* img_hw, int H, int W,
-                        float* boxes, void* obj, int N);
+                     const int strides[4], int C, const float* boxes, int num_boxes, int boxes_per_frame, const int32_t* frame_of,
+                     int pyramid_frames, void* out, int32_t* levels_out);
+int launch_init_queries(hipStream_t s, mcg_dtype dt, const float* init_boxes, const void* init_feats, const int* img_hw,
+                        const int32_t* frame_of, int pyramid_frames, int H, int W, float* boxes, void* obj, int N);
 
 struct mcg_engine {
   mcg_dtype dt;
@@ -729,22 +729,24 @@ extern "C" int mcg_bench_backbone_levels(const mcg_engine* e, void* ws, int N, i
   return MCG_OK;
 }
 
-extern "C" int mcg_decoder_forward(mcg_engine* e, mcg_stream s_, const void* const pyramid[4], int N, int clip_length, int H, int W,
-                                   const int* img_hw, float* gaze_out, float* boxes_out, float* scores_out, void* ws, size_t ws_bytes) {
-  hipStream_t s = (hipStream_t)s_;
+// The decoder over an existing pyramid; frame_of != NULL: window frame n reads pyramid row frame_of[n] of a store of pyramid_frames rows
+// (RoIAlign and the query init gather through the table, roi_align.hip / decoder.hip), img_hw is then indexed by pyramid row.
+static int decoder_forward(mcg_engine* e, hipStream_t s, const void* const pyramid[4], int pyramid_frames, const int32_t* frame_of, int N,
+                           int clip_length, int H, int W, const int* img_hw, float* gaze_out, float* boxes_out, float* scores_out, void* ws,
+                           size_t ws_bytes) {
   MCG_CHECK_ARG(e && pyramid && gaze_out && boxes_out && scores_out && ws, "mcg_decoder_forward: null pointer");
   MCG_TRY(check_shape(N, H, W));
   MCG_CHECK_ARG(clip_length > 0 && N % clip_length == 0, "num_frames=%d is not a multiple of clip_length=%d", N, clip_length);
   DecWs c = dec_layout(e->dt, N, (char*)ws);
   if (ws_bytes < c.total) { mcg_set_error("mcg_decoder_forward: workspace too small (%zu < %zu)", ws_bytes, c.total); return MCG_ERR_WORKSPACE; }
-  MCG_TRY(launch_init_queries(s, e->dt, e->init_boxes, e->init_feats, img_hw, H, W, c.boxes_a, c.obj_a, N));
+  MCG_TRY(launch_init_queries(s, e->dt, e->init_boxes, e->init_feats, img_hw, frame_of, pyramid_frames, H, W, c.boxes_a, c.obj_a, N));
   int fh[4], fw[4];
   const int strides[4] = {4, 8, 16, 32};
   for (int i = 0; i < 4; ++i) { fh[i] = (H / 4) >> i; fw[i] = (W / 4) >> i; }
   char* obj_in = c.obj_a; char* obj_out = c.obj_b;
   float* b_in = c.boxes_a; float* b_out = c.boxes_b;
   for (int st = 0; st < e->num_stages; ++st) {
-    MCG_TRY(launch_roi_align(s, e->dt, pyramid, fh, fw, strides, 256, b_in, N * 3, 3, c.roi, nullptr));
+    MCG_TRY(launch_roi_align(s, e->dt, pyramid, fh, fw, strides, 256, b_in, N * 3, 3, frame_of, pyramid_frames, c.roi, nullptr));
     float* bdst = (st == e->num_stages - 1) ? boxes_out : b_out;
     MCG_TRY(stage_forward_ctx(s, e->dt, &e->stage_w[(size_t)st * MCG_SW_COUNT], c.roi, obj_in, b_in, N, clip_length, obj_out, bdst,
                               c.cls, e->stds, c.stage_ws, c.stage_bytes, e->ctx));
@@ -753,6 +755,20 @@ extern "C" int mcg_decoder_forward(mcg_engine* e, mcg_stream s_, const void* con
   }
   MCG_TRY(gaze_head_ctx(s, e->dt, e->gaze_w, obj_in, N, gaze_out, c.gaze_ws, c.gaze_bytes, e->ctx, c.cls, scores_out));
   return MCG_OK;
+}
+
+extern "C" int mcg_decoder_forward(mcg_engine* e, mcg_stream s_, const void* const pyramid[4], int N, int clip_length, int H, int W,
+                                   const int* img_hw, float* gaze_out, float* boxes_out, float* scores_out, void* ws, size_t ws_bytes) {
+  return decoder_forward(e, (hipStream_t)s_, pyramid, N, nullptr, N, clip_length, H, W, img_hw, gaze_out, boxes_out, scores_out, ws, ws_bytes);
+}
+
+extern "C" int mcg_decoder_forward_indexed(mcg_engine* e, mcg_stream s_, const void* const pyramid[4], int pyramid_frames, const int32_t* frame_of,
+                                           int N, int clip_length, int H, int W, const int* img_hw, float* gaze_out, float* boxes_out,
+                                           float* scores_out, void* ws, size_t ws_bytes) {
+  MCG_CHECK_ARG(frame_of, "mcg_decoder_forward_indexed: null frame_of (mcg_decoder_forward is the plain path)");
+  MCG_CHECK_ARG(pyramid_frames > 0, "mcg_decoder_forward_indexed: empty pyramid store (pyramid_frames=%d)", pyramid_frames);
+  return decoder_forward(e, (hipStream_t)s_, pyramid, pyramid_frames, frame_of, N, clip_length, H, W, img_hw, gaze_out, boxes_out, scores_out,
+                         ws, ws_bytes);
 }
 
 extern "C" int mcg_clip_forward(mcg_engine* e, mcg_stream s_, const float* img, int N, int clip_length, int H, int W,

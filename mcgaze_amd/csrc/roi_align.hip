@@ -8,6 +8,13 @@
 //   otherwise y = max(y,0); y_low = int(y); if y_low >= H-1: y_low = y_high = H-1, y = y_low;
 //   value = bilinear; output = mean of the 4 samples.
 // Features are NHWC so one sample touches C contiguous channels; output is [box][49][C].
+//
+// Indexed form (frame_of != NULL, mcg_roi_align_indexed / mcg_decoder_forward_indexed): the features are a pyramid STORE of
+// pyramid_frames rows and box b of window frame n = b / boxes_per_frame reads row frame_of[n] -- the gather of a window's frames out of
+// a store that holds each distinct video frame once happens here, in the 49 x 4 sample reads of a box, instead of as a copy of whole
+// pyramid rows.  The index is uniform per workgroup (one box per workgroup): read once, as a scalar.  An index outside
+// [0, pyramid_frames) reads nothing: the address is clamped to row 0 and the box's output is NaN.  frame_of == NULL is the plain
+// path (row = n) with the same code and bits as before.
 #include "common.hpp"
 
 struct RoiLevels {
@@ -18,6 +25,7 @@ struct RoiLevels {
 
 template <typename T>
 __global__ __launch_bounds__(256) void roi_align_kernel(RoiLevels lv, int C, const float* __restrict__ boxes, int boxes_per_frame,
+                                                        const int32_t* __restrict__ frame_of, int pyramid_frames,
                                                         T* __restrict__ out, int32_t* __restrict__ levels_out, float finest_scale) {
   constexpr int EPC = Elem<T>::kPerChunk;
   constexpr int P = 7, S = 2, NS = P * S;
@@ -54,10 +62,24 @@ __global__ __launch_bounds__(256) void roi_align_kernel(RoiLevels lv, int C, con
     if (levels_out) levels_out[box] = level;
   }
   __syncthreads();
-  const int frame = box / boxes_per_frame;
+  int frame = box / boxes_per_frame;
+  bool bad_row = false;
+  if (frame_of) {
+    frame = __builtin_amdgcn_readfirstlane(frame_of[frame]);   // uniform per workgroup: one scalar load
+    bad_row = frame < 0 || frame >= pyramid_frames;
+    if (bad_row) frame = 0;                                     // never address outside the store
+  }
   const T* __restrict__ F = (const T*)lv.feat[level] + (long long)frame * H * W * C;
   const int groups = C / EPC, bins_per_pass = 256 / groups;
   const int cg = tid % groups, slot = tid / groups;
+  if (bad_row) {
+    float nan[EPC];
+#pragma unroll
+    for (int e = 0; e < EPC; ++e) nan[e] = __builtin_nanf("");
+    for (int bin = slot; bin < P * P; bin += bins_per_pass)
+      *(uint4*)(out + ((long long)box * (P * P) + bin) * C + cg * EPC) = f32_to_chunk(nan, (T*)nullptr);
+    return;
+  }
   for (int bin = slot; bin < P * P; bin += bins_per_pass) {
     const int ph = bin / P, pw = bin % P;
     float acc[EPC];
@@ -89,8 +111,8 @@ __global__ __launch_bounds__(256) void roi_align_kernel(RoiLevels lv, int C, con
 }
 
 int launch_roi_align(hipStream_t s, mcg_dtype dt, const void* const feats[4], const int feat_h[4], const int feat_w[4],
-                     const int strides[4], int C, const float* boxes, int num_boxes, int boxes_per_frame, void* out,
-                     int32_t* levels_out) {
+                     const int strides[4], int C, const float* boxes, int num_boxes, int boxes_per_frame, const int32_t* frame_of,
+                     int pyramid_frames, void* out, int32_t* levels_out) {
   RoiLevels lv;
   for (int i = 0; i < 4; ++i) {
     lv.feat[i] = feats[i]; lv.h[i] = feat_h[i]; lv.w[i] = feat_w[i];
@@ -99,11 +121,14 @@ int launch_roi_align(hipStream_t s, mcg_dtype dt, const void* const feats[4], co
   const int epc = mcg_is16(dt) ? 8 : 4;
   MCG_CHECK_ARG(C % epc == 0 && C / epc <= 256 && 256 % (C / epc) == 0, "roi_align: unsupported channel count %d", C);
   if (dt == MCG_BF16)
-    hipLaunchKernelGGL(roi_align_kernel<bf16_t>, dim3(num_boxes), dim3(256), 0, s, lv, C, boxes, boxes_per_frame, (bf16_t*)out, levels_out, 56.f);
+    hipLaunchKernelGGL(roi_align_kernel<bf16_t>, dim3(num_boxes), dim3(256), 0, s, lv, C, boxes, boxes_per_frame, frame_of, pyramid_frames,
+                       (bf16_t*)out, levels_out, 56.f);
   else if (dt == MCG_F16)
-    hipLaunchKernelGGL(roi_align_kernel<f16_t>, dim3(num_boxes), dim3(256), 0, s, lv, C, boxes, boxes_per_frame, (f16_t*)out, levels_out, 56.f);
+    hipLaunchKernelGGL(roi_align_kernel<f16_t>, dim3(num_boxes), dim3(256), 0, s, lv, C, boxes, boxes_per_frame, frame_of, pyramid_frames,
+                       (f16_t*)out, levels_out, 56.f);
   else
-    hipLaunchKernelGGL(roi_align_kernel<float>, dim3(num_boxes), dim3(256), 0, s, lv, C, boxes, boxes_per_frame, (float*)out, levels_out, 56.f);
+    hipLaunchKernelGGL(roi_align_kernel<float>, dim3(num_boxes), dim3(256), 0, s, lv, C, boxes, boxes_per_frame, frame_of, pyramid_frames,
+                       (float*)out, levels_out, 56.f);
   MCG_CHECK_LAUNCH("roi_align");
   return MCG_OK;
 }
@@ -114,5 +139,15 @@ extern "C" int mcg_roi_align(mcg_stream s, mcg_dtype dt, const void* const feats
   MCG_CHECK_ARG(feats && feat_h && feat_w && strides && boxes && out, "mcg_roi_align: null pointer");
   MCG_CHECK_ARG(num_boxes > 0 && boxes_per_frame > 0, "mcg_roi_align: empty box set");
   for (int i = 0; i < 4; ++i) MCG_CHECK_ARG(feats[i] && feat_h[i] > 0 && feat_w[i] > 0 && strides[i] > 0, "mcg_roi_align: bad level %d", i);
-  return launch_roi_align((hipStream_t)s, dt, feats, feat_h, feat_w, strides, C, boxes, num_boxes, boxes_per_frame, out, levels_out);
+  return launch_roi_align((hipStream_t)s, dt, feats, feat_h, feat_w, strides, C, boxes, num_boxes, boxes_per_frame, nullptr, 0, out, levels_out);
+}
+
+extern "C" int mcg_roi_align_indexed(mcg_stream s, mcg_dtype dt, const void* const feats[4], const int feat_h[4], const int feat_w[4],
+                                     const int strides[4], int C, const float* boxes, int num_boxes, int boxes_per_frame,
+                                     const int32_t* frame_of, int pyramid_frames, void* out, int32_t* levels_out) {
+  MCG_CHECK_ARG(feats && feat_h && feat_w && strides && boxes && out && frame_of, "mcg_roi_align_indexed: null pointer");
+  MCG_CHECK_ARG(num_boxes > 0 && boxes_per_frame > 0 && pyramid_frames > 0, "mcg_roi_align_indexed: empty box set or pyramid");
+  for (int i = 0; i < 4; ++i) MCG_CHECK_ARG(feats[i] && feat_h[i] > 0 && feat_w[i] > 0 && strides[i] > 0, "mcg_roi_align_indexed: bad level %d", i);
+  return launch_roi_align((hipStream_t)s, dt, feats, feat_h, feat_w, strides, C, boxes, num_boxes, boxes_per_frame, frame_of, pyramid_frames,
+                          out, levels_out);
 }

@@ -154,6 +154,46 @@ def roi_align(feats, boxes, strides=(4, 8, 16, 32)):
     return out, lv
 
 
+def roi_align_indexed(feats, boxes, frame_of, strides=(4, 8, 16, 32)):
+    """roi_align over window frames gathered from a pyramid store: box row r reads pyramid row frame_of[r // P].
+    feats: 4 NHWC levels [K,h,w,C]; boxes [N,P,4] f32; frame_of: N row indices (host, range-checked) -> ([N*P,49,C], levels).
+    mcg_roi_align_indexed."""
+    _require_gpu()
+    lib = L.load()
+    N, P = boxes.shape[:2]
+    K, Cc = feats[0].shape[0], feats[0].shape[-1]
+    table = torch.from_numpy(check_frame_table(frame_of, K, 1)).to(boxes.device)
+    if table.numel() != N:
+        raise L.McgError(f'frame_of holds {table.numel()} entries for {N} frames of boxes')
+    out = torch.empty(N * P, 49, Cc, dtype=feats[0].dtype, device=boxes.device)
+    lv = torch.empty(N * P, dtype=torch.int32, device=boxes.device)
+    fp = (C.c_void_p * 4)(*[f.data_ptr() for f in feats])
+    fh = (C.c_int * 4)(*[f.shape[1] for f in feats])
+    fw = (C.c_int * 4)(*[f.shape[2] for f in feats])
+    st = (C.c_int * 4)(*strides)
+    b = boxes.contiguous().float()
+    L.check(lib.mcg_roi_align_indexed(_stream(), _code(feats[0].dtype), fp, fh, fw, st, Cc, _ptr(b), N * P, P, _ptr(table), K, _ptr(out), _ptr(lv)),
+            'mcg_roi_align_indexed')
+    return out, lv
+
+
+def check_frame_table(frame_of, pyramid_frames, clip_length):
+    """Host-side check of a window-frame -> pyramid-row table: a sequence (or CPU tensor) of integers, a positive multiple of
+    clip_length long, every entry in [0, pyramid_frames).  -> int32 numpy array.  McgError otherwise (nothing reaches the device)."""
+    t = frame_of.numpy() if isinstance(frame_of, torch.Tensor) else frame_of
+    try:
+        a = np.asarray(t)
+    except Exception as ex:                          # ragged input
+        raise L.McgError(f'frame_of must be a flat sequence of row indices ({ex})')
+    if a.ndim != 1 or (a.size and not np.issubdtype(a.dtype, np.integer)):
+        raise L.McgError(f'frame_of must be a flat sequence of integer row indices (got {a.dtype} of shape {a.shape})')
+    if clip_length < 1 or a.size == 0 or a.size % clip_length:
+        raise L.McgError(f'frame_of holds {a.size} entries, not a positive multiple of clip_length={clip_length}')
+    if pyramid_frames < 1 or int(a.min()) < 0 or int(a.max()) >= pyramid_frames:
+        raise L.McgError(f'frame_of entries must lie in [0, {pyramid_frames}) (got {int(a.min())} .. {int(a.max())})')
+    return a.astype(np.int32)
+
+
 def _table(d, keys):
     return (C.c_void_p * len(keys))(*[d[k].data_ptr() for k in keys])
 
@@ -232,6 +272,7 @@ class HipEngine:
             L.check(self.lib.mcg_engine_create(C.byref(self._handle), C.byref(mw), self.code), 'mcg_engine_create')
         self._ws = None
         self._ws_key = None
+        self._dec_ws = None
 
     def set_option(self, name, value):
         """mcg_engine_set_option: 'trunk_streams', 'max_range_frames', 'tile', 'staged_gemm', 'conv3x3_c64', 'stem_fused',
@@ -299,17 +340,81 @@ class HipEngine:
         if not (img.is_cuda and img.device == self.device and img.dtype == torch.float32 and img.is_contiguous() and img.dim() == 4):
             raise L.McgError(f'img must be a contiguous float32 [N,3,H,W] tensor on {self.device} (got {img.dtype} {tuple(img.shape)} on {img.device})')
 
-    def backbone_fpn(self, img, chunk_frames=0):
-        """img [N,3,H,W] f32 on the device -> [P2..P5] NHWC in the engine dtype."""
+    def backbone_fpn(self, img, chunk_frames=0, out=None, row=0):
+        """img [N,3,H,W] f32 on the device -> [P2..P5] NHWC in the engine dtype.
+        out: four per-level tensors [K, H/4 >> i, W/4 >> i, 256] (engine dtype, contiguous) -- a pyramid STORE: the frames are written to
+        rows [row, row + N) of it (the trunk of a frame does not depend on its batch, so a row holds the bits a whole-batch call gives)
+        and ``out`` is returned."""
         self._check_img(img)
         N, _, H, W = img.shape
+        shapes = [((H // 4) >> i, (W // 4) >> i, 256) for i in range(4)]
+        if out is not None:
+            K = self._check_pyramid(out, shapes)
+            if not (0 <= row and row + N <= K):
+                raise L.McgError(f'backbone_fpn: rows [{row}, {row + N}) do not fit a pyramid store of {K} rows')
         with torch.cuda.device(self.device):
             ws = self._workspace(N, H, W, chunk_frames)
-            pyr = [torch.empty(N, (H // 4) >> i, (W // 4) >> i, 256, dtype=self.dtype, device=self.device) for i in range(4)]
-            tab = (C.c_void_p * 4)(*[p.data_ptr() for p in pyr])
+            if out is None:
+                pyr, row = [torch.empty((N,) + s, dtype=self.dtype, device=self.device) for s in shapes], 0
+            else:
+                pyr = out
+            es = pyr[0].element_size()
+            tab = (C.c_void_p * 4)(*[p.data_ptr() + row * s[0] * s[1] * s[2] * es for p, s in zip(pyr, shapes)])
             L.check(self.lib.mcg_backbone_fpn_forward(self._handle, _stream(self.device), _ptr(img), N, H, W, chunk_frames, tab, _ptr(ws), ws.numel()),
                     'mcg_backbone_fpn_forward')
         return pyr
+
+    def _check_pyramid(self, pyramid, shapes=None):
+        """-> rows K of a pyramid store (four contiguous [K,h,w,256] tensors of the engine dtype on its device, h, w halving per level)."""
+        if len(pyramid) != 4:
+            raise L.McgError(f'a pyramid is four levels (got {len(pyramid)})')
+        K = pyramid[0].shape[0]
+        if shapes is None:
+            h, w = pyramid[0].shape[1], pyramid[0].shape[2]
+            shapes = [(h >> i, w >> i, 256) for i in range(4)]
+        for i, (p, s) in enumerate(zip(pyramid, shapes)):
+            if not (p.dtype == self.dtype and p.device == self.device and p.is_contiguous() and tuple(p.shape) == (K,) + tuple(s)):
+                raise L.McgError(f'pyramid level {i} must be a contiguous {self.dtype} [{K},{s[0]},{s[1]},256] tensor on {self.device} '
+                                 f'(got {p.dtype} {tuple(p.shape)} on {p.device})')
+        return K
+
+    def decode(self, pyramid, frame_of, clip_length, img_hw=None, out=None):
+        """The decoder over window frames gathered from a pyramid STORE (mcg_decoder_forward_indexed): window frame n reads pyramid row
+        frame_of[n].  pyramid: four [K,h,w,256] tensors (backbone_fpn(..., out=)); frame_of: N = windows * clip_length row indices, a host
+        sequence (range-checked here, McgError) or an int32 tensor (a DEVICE table is the caller's responsibility: the kernels clamp
+        the address of an index outside [0, K) and write NaN for that frame); img_hw: img_shape (h, w) per pyramid ROW [K,2] or None.
+        Returns dict(gaze [4,N,3], boxes [N,3,4], scores [N,3]) like forward -- bit for bit forward's on the stacked window frames."""
+        K = pyramid[0].shape[0] if len(pyramid) else 0
+        H, W = (pyramid[0].shape[1] * 4, pyramid[0].shape[2] * 4) if len(pyramid) else (0, 0)
+        dev_table = isinstance(frame_of, torch.Tensor) and frame_of.device.type != 'cpu'
+        host = None if dev_table else check_frame_table(frame_of, K, clip_length)
+        self._check_pyramid(pyramid)
+        with torch.cuda.device(self.device):
+            if dev_table:
+                if not (frame_of.dtype == torch.int32 and frame_of.device == self.device and frame_of.dim() == 1):
+                    raise L.McgError(f'a device frame_of must be a 1-D int32 tensor on {self.device} (got {frame_of.dtype} {tuple(frame_of.shape)} on {frame_of.device})')
+                table = frame_of.contiguous()
+                if table.numel() == 0 or table.numel() % clip_length:
+                    raise L.McgError(f'frame_of holds {table.numel()} entries, not a positive multiple of clip_length={clip_length}')
+            else:
+                # pinned + non-blocking: a pageable upload would make the host wait for the work already queued (harness.py, upload)
+                table = torch.from_numpy(host).pin_memory().to(self.device, non_blocking=True)
+            N = table.numel()
+            if out is None:
+                out = dict(gaze=torch.empty(4, N, 3, dtype=torch.float32, device=self.device),
+                           boxes=torch.empty(N, 3, 4, dtype=torch.float32, device=self.device),
+                           scores=torch.empty(N, 3, dtype=torch.float32, device=self.device))
+            hw = self.img_hw_tensor(img_hw, K)
+            need = self.lib.mcg_decoder_workspace_bytes(self._handle, N)
+            if self._dec_ws is None or self._dec_ws.numel() < need:
+                self._dec_ws = None
+                self._dec_ws = _ws(need, self.device)
+            ws = self._dec_ws
+            tab = (C.c_void_p * 4)(*[p.data_ptr() for p in pyramid])
+            L.check(self.lib.mcg_decoder_forward_indexed(self._handle, _stream(self.device), tab, K, _ptr(table), N, clip_length, H, W, _ptr(hw),
+                                                         _ptr(out['gaze']), _ptr(out['boxes']), _ptr(out['scores']), _ptr(ws), ws.numel()),
+                    'mcg_decoder_forward_indexed')
+        return out
 
     def forward(self, img, clip_length, img_hw=None, chunk_frames=0, out=None):
         """img [N,3,H,W] f32 (device, contiguous), N = clips*clip_length.

@@ -21,7 +21,7 @@ import numpy as np
 import torch
 
 CLUES = ('face', 'eyes', 'head')
-last_run_stats = {}       # run_annotation's frame-cache counters of the last call (tools/dataset_throughput.py prints them)
+last_run_stats = {}       # run_annotation's frame-cache counters of the last call (tools/dataset_throughput.py prints them); trunk_frames of run_videos
 
 
 def plan_windows(video_length, clip_len=7, stride=4):
@@ -96,14 +96,18 @@ def result_file_name(config_path, json_path):
     return f'results_{config_path.rstrip(".py").split("/")[-1]}_{json_path.split("/")[-1]}'
 
 
-def _run_windows(engine, ids, plans, get_window, batch_clips, person_threshold):
+def _run_windows(engine, ids, plans, get_window, batch_clips, person_threshold, reuse_frames=False):
     """Core of run_videos / run_annotation, STREAMING: windows are visited in (video, window) order -- the reference's order, so the
     crop RNG draws inside ``get_window`` fall where upstream's do -- and dropped into per-(T, H, W) buckets; a bucket runs through
     the engine (batched semantics: N = B*T frames, clip_length = T) as soon as it holds ``batch_clips`` clips and its inputs are
     released; a video is merged and turned into its record as soon as its last window has come back.  Device memory is bounded by
     ``batch_clips`` clips per distinct window shape, not by the size of the dataset.
-    get_window(vi, wi) -> (frames [T,3,H,W] f32, img_hw [T,2] int or None, scale [T,4] f32 or None)."""
+    get_window(vi, wi) -> (frames [T,3,H,W] f32, img_hw [T,2] int or None, scale [T,4] f32 or None).
+    reuse_frames: frame t of window (a, b) of video vi IS frame a + t of the video: each distinct (video, frame) of a flush goes through the
+    trunk once, into one row of a pyramid store, and one indexed decoder call (engine.decode) reads the windows' frames from it -- the
+    same batch of windows as forward would run, so the same bits.  ``trunk`` counts the frames run through the trunk."""
     dev = engine.device
+    trunk = [0]
     buckets = {}                                       # (T, H, W) -> list of (vi, wi, frames, hw, scale)
     outputs = [[None] * len(p) for p in plans]
     pending = [len(p) for p in plans]
@@ -140,16 +144,43 @@ def _run_windows(engine, ids, plans, get_window, batch_clips, person_threshold):
                     records[vi] = video_record(ids[vi], *merge_video(plans[vi], outputs[vi], person_threshold))
                     outputs[vi] = None
 
+    def decode_distinct(items, T):
+        # rows of the pyramid store: the distinct (video, frame) of the batch, in order of first appearance; runs of consecutive frames
+        # of one window are taken as slices
+        row_of, parts, hws, table = {}, [], [], []
+        for vi, wi, x, hw, _ in items:
+            a = plans[vi][wi][0]
+            for t in range(T):
+                k = (vi, a + t)
+                if k not in row_of:
+                    row_of[k] = len(row_of)
+                    if parts and parts[-1][0] is x and parts[-1][2] == t:
+                        parts[-1][2] = t + 1
+                    else:
+                        parts.append([x, t, t + 1])
+                    if hw is not None:
+                        hws.append(np.asarray(hw, dtype=np.int32).reshape(-1, 2)[t])
+                table.append(row_of[k])
+        x = torch.cat([p[0][p[1]:p[2]] for p in parts]).to(dev, torch.float32).contiguous()
+        hw = None if items[0][3] is None else upload(torch.from_numpy(np.stack(hws)))
+        pyr = engine.backbone_fpn(x)
+        trunk[0] += x.shape[0]
+        return engine.decode(pyr, table, T, img_hw=hw)
+
     def flush(key):
         items = buckets.pop(key, [])
         if not items:
             return
         T = key[0]
         collect(2)
-        x = torch.cat([it[2] for it in items]).to(dev, torch.float32).contiguous()
         del keep[:max(0, len(keep) - 4)]
-        hw = None if items[0][3] is None else upload(torch.cat([torch.as_tensor(it[3], dtype=torch.int32).reshape(-1, 2) for it in items]))
-        out = engine.forward(x, T, img_hw=hw)
+        if reuse_frames:
+            out = decode_distinct(items, T)
+        else:
+            x = torch.cat([it[2] for it in items]).to(dev, torch.float32).contiguous()
+            hw = None if items[0][3] is None else upload(torch.cat([torch.as_tensor(it[3], dtype=torch.int32).reshape(-1, 2) for it in items]))
+            out = engine.forward(x, T, img_hw=hw)
+            trunk[0] += x.shape[0]
         boxes = out['boxes']
         if items[0][4] is not None:   # rescale=True: every frame's boxes by its own scale_factor (multiclue_gaze_roi_head.py:360-363)
             boxes = boxes / upload(torch.cat([torch.as_tensor(it[4], dtype=torch.float32) for it in items]))[:, None, :]
@@ -181,15 +212,21 @@ def _run_windows(engine, ids, plans, get_window, batch_clips, person_threshold):
     for key in sorted(buckets):
         flush(key)
     collect(0)
+    last_run_stats['trunk_frames'] = trunk[0]
     return records
 
 
-def run_videos(engine, videos, clip_len=7, stride=4, batch_clips=64, scale_factor=None, person_threshold=0.5):
+def run_videos(engine, videos, clip_len=7, stride=4, batch_clips=64, scale_factor=None, person_threshold=0.5, reuse_frames=False):
     """Push whole videos through the HIP engine.
 
     videos: list of dict(id=…, frames=Tensor[L,3,H,W] f32 already preprocessed (normalised, padded to /32)[, img_hw=[L,2] int: the
     per-frame img_shape inside the padded frame -- all videos or none]).
-    scale_factor (4 floats) divides the boxes like rescale=True does (multiclue_gaze_roi_head.py:360-363)."""
+    scale_factor (4 floats) divides the boxes like rescale=True does (multiclue_gaze_roi_head.py:360-363).
+    reuse_frames: overlapping windows share their frames' trunk.  Each batch runs every distinct (video, frame) of its windows through
+    backbone + FPN once, into a pyramid store, then one indexed decoder call over the batch's windows (engine.decode): about 4 / 7 of the
+    trunk work at (7, 4) on long videos, records == those of the default path (which runs engine.forward on every window's frames).
+    Frames shared by windows that land in different batches are computed in each: at most clip_len - stride per video per batch
+    boundary.  last_run_stats['trunk_frames'] holds the frames the trunk ran on, for both settings."""
     plans = [plan_windows(v['frames'].shape[0], clip_len, stride) for v in videos]
 
     def get_window(vi, wi):
@@ -198,7 +235,7 @@ def run_videos(engine, videos, clip_len=7, stride=4, batch_clips=64, scale_facto
         hw = videos[vi].get('img_hw')
         return videos[vi]['frames'][a:b], (None if hw is None else hw[a:b]), sc
 
-    return _run_windows(engine, [v['id'] for v in videos], plans, get_window, batch_clips, person_threshold)
+    return _run_windows(engine, [v['id'] for v in videos], plans, get_window, batch_clips, person_threshold, reuse_frames=reuse_frames)
 
 
 def run_annotation(engine, anno, root, pipeline, clip_len=7, stride=4, batch_clips=64, person_threshold=0.5, rng=None, workers=0, lookahead=None,

@@ -11,7 +11,7 @@ LIB_PATH = os.environ.get('MCGAZE_LIB') or os.path.join(_HERE, 'libmcgaze_hip.so
 
 MCG_OK = 0
 MCG_F32, MCG_BF16, MCG_F16X3, MCG_F16 = 0, 1, 2, 3
-ABI_VERSION = 13
+ABI_VERSION = 14
 RES_NONE, RES_ADD, RES_UPSAMPLE_ADD = 0, 1, 2
 FLAG_STAGED_GEMM, FLAG_NO_SPECIALISED, FLAG_NO_ATTN_BLOCK = 1, 2, 4
 
@@ -31,7 +31,7 @@ EXPORTS = ['mcg_abi_version', 'mcg_build_id', 'mcg_last_error', 'mcg_device_info
            'mcg_engine_workspace_bytes', 'mcg_trunk_workspace_bytes', 'mcg_decoder_workspace_bytes', 'mcg_backbone_fpn_forward',
            'mcg_decoder_forward', 'mcg_clip_forward', 'mcg_preprocess_frames', 'mcg_engine_set_option', 'mcg_engine_profile_start',
            'mcg_engine_profile_stop', 'mcg_bench_backbone_forward', 'mcg_bottleneck_x3', 'mcg_bench_backbone_levels', 'mcg_conv3x3_wino_x3',
-           'mcg_conv3x3_wino_x3_weight_bytes', 'mcg_engine_range_audit']
+           'mcg_conv3x3_wino_x3_weight_bytes', 'mcg_engine_range_audit', 'mcg_roi_align_indexed', 'mcg_decoder_forward_indexed']
 
 
 class ConvDesc(C.Structure):
@@ -92,6 +92,7 @@ def load():
     lib.mcg_stem_workspace_bytes.argtypes = [i, i, i, i]
     lib.mcg_stem_forward.argtypes = [vp, i, vp, vp, vp, vp, i, i, i, vp, sz, i]
     lib.mcg_roi_align.argtypes = [vp, i, C.POINTER(vp), C.POINTER(i), C.POINTER(i), C.POINTER(i), i, vp, i, i, vp, vp]
+    lib.mcg_roi_align_indexed.argtypes = [vp, i, C.POINTER(vp), C.POINTER(i), C.POINTER(i), C.POINTER(i), i, vp, i, i, vp, i, vp, vp]
     lib.mcg_stage_workspace_bytes.restype = sz
     lib.mcg_stage_workspace_bytes.argtypes = [i, i]
     lib.mcg_stage_forward.argtypes = [vp, i, C.POINTER(vp), vp, vp, vp, i, i, vp, vp, vp, C.POINTER(C.c_float), vp, sz, i]
@@ -108,6 +109,7 @@ def load():
     lib.mcg_decoder_workspace_bytes.restype = sz
     lib.mcg_decoder_workspace_bytes.argtypes = [vp, i]
     lib.mcg_decoder_forward.argtypes = [vp, vp, C.POINTER(vp), i, i, i, i, vp, vp, vp, vp, vp, sz]
+    lib.mcg_decoder_forward_indexed.argtypes = [vp, vp, C.POINTER(vp), i, vp, i, i, i, i, vp, vp, vp, vp, vp, sz]
     lib.mcg_backbone_fpn_forward.argtypes = [vp, vp, vp, i, i, i, i, C.POINTER(vp), vp, sz]
     lib.mcg_clip_forward.argtypes = [vp, vp, vp, i, i, i, i, vp, i, vp, vp, vp, vp, sz]
     lib.mcg_preprocess_frames.argtypes = [vp, vp, i, vp, i, i, C.POINTER(C.c_float), C.POINTER(C.c_float), i]
