@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define MCG_ABI_VERSION 14
+#define MCG_ABI_VERSION 15
 
 enum { MCG_OK = 0, MCG_ERR_ARG = 1, MCG_ERR_HIP = 2, MCG_ERR_UNSUPPORTED = 3, MCG_ERR_WORKSPACE = 4 };
 /* MCG_F16X3: the parity-grade fast mode.  Activations, biases and every non-GEMM kernel are exactly those of MCG_F32 (4-byte
@@ -324,6 +324,10 @@ void mcg_engine_destroy(mcg_engine* e);
  *                     workgroups --, 0 / 1 / 2 force the 8- / 4-wave tiles of wino_x3_kernel, 3 forces wino_x3w_kernel.  Every tile gives the same
  *                     bits; 0 is the run-time fallback for wino_x3w_kernel (its hand-issued register loads need a spill-free build, which
  *                     csrc/check_resources.py enforces at build time)
+ *   fpn_deferred      0/1 MCG_F16X3 (default 1): the FPN P2 output conv is left to the decoder and computed per 8 x 8-pixel block, only where the
+ *                     RoIAlign of some stage reads (mcg_backbone_fpn_forward_deferred / mcg_decoder_forward_deferred, mcg_clip_forward); bit-identical
+ *                     to the dense conv.  0 = every level dense in the trunk, launch for launch.  Off for other precisions, under range_audit
+ *                     (which audits whole P tensors) and for levels beyond 512 x 512 pixels.  Not to be changed between the two calls of a pair
  *   range_audit       0/1 DEBUG (MCG_F32 / MCG_F16X3; default 0): after every activation tensor the trunk writes, a counting kernel tallies the
  *                     values beyond the fp16 range (|x| > 65504: an f16x3 operand half would saturate there) and the non-finite ones;
  *                     read and reset with mcg_engine_range_audit.  Turning it on allocates the counters (the library's only allocation,
@@ -364,7 +368,21 @@ int mcg_decoder_forward(mcg_engine* e, mcg_stream s, const void* const pyramid[4
 int mcg_decoder_forward_indexed(mcg_engine* e, mcg_stream s, const void* const pyramid[4], int pyramid_frames, const int32_t* frame_of,
                                 int num_frames, int clip_length, int H, int W, const int* img_hw, float* gaze_out, float* boxes_out,
                                 float* scores_out, void* ws, size_t ws_bytes);
-/* Whole path = mcg_backbone_fpn_forward + mcg_decoder_forward on one stream; ws >= mcg_engine_workspace_bytes. */
+/* ABI 15: the same pair over a DEFERRED pyramid.  slot: caller-owned device memory of mcg_deferred_pyramid_bytes(e, N, H, W) bytes that
+ * carries one batch from the trunk to the decoder (double-buffer it to overlap batches, mcgaze_amd/engine.py: PipelinedRunner): P2..P5,
+ * and, when the engine defers P2 (option fpn_deferred), the P2 top-down inner map, a flag per 8 x 8 output block of P2 and one block list
+ * per stage.  The trunk then writes P3..P5 and the inner map; before each stage's RoIAlign the decoder flags the P2 blocks that stage's
+ * boxes read (the RoIAlign sample arithmetic itself, roi_sample.hpp) and computes those not yet computed (no host sync: graph-capturable).
+ * P2 pixels no box reads are never written.  Outputs are bit for bit those of mcg_backbone_fpn_forward + mcg_decoder_forward.
+ * mcg_deferred_pyramid_levels: where the slot's P2..P5 lie; *deferred (optional) = whether the engine defers P2 for this shape. */
+size_t mcg_deferred_pyramid_bytes(const mcg_engine* e, int num_frames, int H, int W);
+int mcg_deferred_pyramid_levels(const mcg_engine* e, void* slot, int num_frames, int H, int W, void* levels[4], int* deferred);
+int mcg_backbone_fpn_forward_deferred(mcg_engine* e, mcg_stream s, const float* img, int num_frames, int H, int W, int chunk_frames,
+                                      void* slot, size_t slot_bytes, void* ws, size_t ws_bytes);
+int mcg_decoder_forward_deferred(mcg_engine* e, mcg_stream s, void* slot, size_t slot_bytes, int num_frames, int clip_length, int H, int W,
+                                 const int* img_hw, float* gaze_out, float* boxes_out, float* scores_out, void* ws, size_t ws_bytes);
+/* Whole path = mcg_backbone_fpn_forward_deferred + mcg_decoder_forward_deferred on one stream (the slot inside ws);
+ * ws >= mcg_engine_workspace_bytes. */
 int mcg_clip_forward(mcg_engine* e, mcg_stream s, const float* img, int num_frames, int clip_length, int H, int W,
                      const int* img_hw, int chunk_frames, float* gaze_out, float* boxes_out, float* scores_out,
                      void* ws, size_t ws_bytes);

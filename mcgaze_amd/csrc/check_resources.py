@@ -16,6 +16,7 @@ import sys
 # kernel-name prefix (demangled template name as it appears in the mangled symbol) -> limits
 RULES = {
     'wino_x3w_kernel': dict(scratch=0, vgpr_spill=0, unit='engine'),   # unit: the translation unit that instantiates it -- the gate must SEE it there
+    'wino_x3w_blocks_kernel': dict(scratch=0, vgpr_spill=0, unit='engine'),   # the same loads, block-list tile (deferred FPN P2)
 }
 
 

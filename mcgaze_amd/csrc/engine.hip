@@ -27,6 +27,10 @@ int launch_roi_align(hipStream_t s, mcg_dtype dt, const void* const feats[4], co
                      int pyramid_frames, void* out, int32_t* levels_out);
 int launch_init_queries(hipStream_t s, mcg_dtype dt, const float* init_boxes, const void* init_feats, const int* img_hw,
                         const int32_t* frame_of, int pyramid_frames, int H, int W, float* boxes, void* obj, int N);
+bool roi_mark_supported(int H, int W);
+int launch_defer_clear(hipStream_t s, int* p, int n);
+int launch_roi_mark(hipStream_t s, const float* boxes, int num_boxes, int boxes_per_frame, int level, int H, int W, int stride, int* state,
+                    int* list, int* count);
 
 struct mcg_engine {
   mcg_dtype dt;
@@ -43,6 +47,8 @@ struct mcg_engine {
   int wino_tile = -1;          // tile of the F(2,3) kernel: -1 (default) by grid size (the one-wave-per-SIMD tile on grids >= 130 workgroups), 0 / 1 / 2 = the 8- and
                                // 4-wave tiles of wino_x3_kernel forced, 3 = wino_x3w_kernel forced.  Every tile gives the same bits; 0 is the run-time
                                // fallback for wino_x3w_kernel, whose hand-issued register loads depend on a spill-free build (csrc/check_resources.py)
+  int fpn_deferred = 1;        // f16x3: the FPN P2 output conv is deferred to the decoder and computed per 8 x 8 block where RoIAlign reads
+                               // (mcg_*_deferred, mcg_clip_forward); 0 = every level dense in the trunk.  Same bits either way
   // range audit (debug option, f32-storage engines): per activation tensor the trunk writes, how many values lie beyond the fp16 range
   // (|x| > 65504: an f16x3 operand half would saturate) and how many are not finite.  Counters live on the device; read by mcg_engine_range_audit.
   static constexpr int kAuditCap = 256;
@@ -210,6 +216,7 @@ extern "C" int mcg_engine_set_option(mcg_engine* e, const char* name, int value)
   else if (!strcmp(name, "bottleneck_fused")) e->bneck_fused = value != 0;
   else if (!strcmp(name, "bottleneck_blocked")) e->bneck_blocked = value != 0;
   else if (!strcmp(name, "winograd")) { MCG_CHECK_ARG(value >= 0 && value <= 2, "winograd must be 0, 1 or 2"); e->winograd = value; }
+  else if (!strcmp(name, "fpn_deferred")) e->fpn_deferred = value != 0;
   else if (!strcmp(name, "wino_tile")) { MCG_CHECK_ARG(value >= -1 && value <= 3, "wino_tile must be -1 (by grid size) .. 3"); e->wino_tile = value; }
   else if (!strcmp(name, "range_audit")) {
     MCG_CHECK_ARG(!mcg_is16(e->dt) || !value, "range_audit: f32-storage engines only (MCG_F32, MCG_F16X3)");
@@ -342,6 +349,13 @@ static TrunkWs trunk_layout(mcg_dtype dt, int n, int H, int W, char* base) {
   return t;
 }
 
+// Which Winograd form conv_call runs a conv in (0: none) -- by the layer's SHAPE only
+static int wino_kind(const mcg_engine* e, mcg_dtype dt, const mcg_conv_weights& cw, int n, int h, int w, int rm) {
+  return (dt == MCG_F16X3 && e->winograd && e->ctx.tile < 0 && cw.k == 3 && cw.stride == 1 && cw.pad == 1 && rm == MCG_RES_NONE)
+             ? ((cw.wf4 && e->winograd >= 2 && wino_x3_applicable(n, h, w, cw.cin, cw.cout, 4)) ? 4 : ((cw.wf && wino_x3_applicable(n, h, w, cw.cin, cw.cout, 2)) ? 2 : 0))
+             : 0;
+}
+
 static int conv_call(const mcg_engine* e, hipStream_t s, mcg_dtype dt, const mcg_conv_weights& cw, const void* x, int n, int h, int w, void* y,
                      int relu, const void* res, int res_mode, int hr, int wr) {
   mcg_conv_desc d;
@@ -384,9 +398,7 @@ static int conv_call(const mcg_engine* e, hipStream_t s, mcg_dtype dt, const mcg
     return MCG_OK;
   }
   // F(4,3) where the layer's shape allows it and the weights carry that copy, else F(2,3), else the direct kernel -- by SHAPE only
-  const int wg = (dt == MCG_F16X3 && e->winograd && e->ctx.tile < 0 && cw.k == 3 && cw.stride == 1 && cw.pad == 1 && rm == MCG_RES_NONE)
-                     ? ((cw.wf4 && e->winograd >= 2 && wino_x3_applicable(n, h, w, cw.cin, cw.cout, 4)) ? 4 : ((cw.wf && wino_x3_applicable(n, h, w, cw.cin, cw.cout, 2)) ? 2 : 0))
-                     : 0;
+  const int wg = wino_kind(e, dt, cw, n, h, w, rm);
   if (wg) {
     // f16x3: the 3x3 / stride 1 convs (FPN outputs, layer3's conv2) as a 1-D Winograd F(2,3) contraction (wino_x3.hpp); FLOPs and bytes
     // are booked as the DIRECT convolution's: the roofline keeps counting the reference's arithmetic
@@ -405,11 +417,13 @@ static int conv_call(const mcg_engine* e, hipStream_t s, mcg_dtype dt, const mcg
 }
 
 // Backbone + FPN over frames [f0, f0+n): writes pyramid level i at frame offset f0.
+// inner0 != NULL (deferred P2): the P2 top-down inner map goes to inner0 (frame offset f0) and the P2 output conv is left to the decoder
 static int trunk_chunk(mcg_engine* e, hipStream_t s, const float* img, int f0, int n, int H, int W, void* const pyr[4], char* wsbase,
-                       bool backbone_only = false) {
+                       bool backbone_only = false, char* inner0 = nullptr) {
   const mcg_dtype dt = e->dt;
   const size_t es = esize(dt);
   TrunkWs t = trunk_layout(dt, n, H, W, wsbase);
+  if (inner0) t.l[0] = inner0 + (size_t)f0 * (H / 4) * (W / 4) * 256 * es;
   MCG_TRY(stem_forward_ctx(s, dt, img + (size_t)f0 * 3 * H * W, e->stem.w, e->stem.bias, t.x0, n, H, W, t.stem_ws, t.stem_bytes, e->ctx));
   AuditCursor au{e, s, 0, e->audit_dev != nullptr && e->audit_names.empty()};
   char aname[64];
@@ -551,7 +565,7 @@ static int trunk_chunk(mcg_engine* e, hipStream_t s, const float* img, int f0, i
     snprintf(aname, sizeof(aname), "fpn.lateral%d (+ top-down)", i);
     audit_tensor(au, aname, t.l[i], (long long)n * hs[i] * wsz[i] * 256);
   }
-  for (int i = 0; i < 4; ++i) {
+  for (int i = inner0 ? 1 : 0; i < 4; ++i) {
     char* dst = (char*)pyr[i] + (size_t)f0 * hs[i] * wsz[i] * 256 * es;
     MCG_TRY(conv_call(e, s, dt, e->fpn_out[i], t.l[i], n, hs[i], wsz[i], dst, 0, nullptr, MCG_RES_NONE, 0, 0));
     snprintf(aname, sizeof(aname), "fpn.P%d", i + 2);
@@ -599,8 +613,44 @@ static DecWs dec_layout(mcg_dtype dt, int N, char* base) {
   c.total = off;
   return c;
 }
+static bool check_shape_ok(int N, int H, int W) { return N > 0 && H >= 32 && W >= 32 && H % 32 == 0 && W % 32 == 0; }
 static size_t pyramid_bytes(mcg_dtype dt, int N, int H, int W, int level) {
   return al256((size_t)N * ((H / 4) >> level) * ((W / 4) >> level) * 256 * esize(dt));
+}
+
+// Deferred pyramid slot (mcg_*_deferred): P2..P5 outputs, then -- when the engine defers P2 -- the P2 inner map the trunk leaves for the
+// decoder, one int per 8 x 8 output block of P2 (0 = not yet listed) followed by one list count per decoder stage, and one block list
+// per stage.  Without deferral the slot is the four pyramid levels and the pair runs the dense launches.
+struct DeferSlot {
+  void* p[4];
+  char* inner;
+  int *state, *count, *list;
+  int nblk;
+  bool deferred;
+  size_t total;
+};
+static bool fpn_deferred_on(const mcg_engine* e, int N, int H, int W) {
+  const mcg_conv_weights& cw = e->fpn_out[0];
+  const int h = H / 4, w = W / 4;
+  return e->fpn_deferred && e->dt == MCG_F16X3 && !e->audit_dev && e->num_stages > 0 && wino_kind(e, e->dt, cw, N, h, w, MCG_RES_NONE) == 2 &&
+         wino_x3_blocks_applicable(N, h, w, cw.cin, cw.cout) && roi_mark_supported(h, w);
+}
+static DeferSlot defer_layout(const mcg_engine* e, int N, int H, int W, char* base) {
+  DeferSlot d;
+  memset(&d, 0, sizeof(d));
+  size_t off = 0;
+  auto take = [&](size_t bytes) { char* p = base ? base + off : nullptr; off += al256(bytes); return p; };
+  for (int i = 0; i < 4; ++i) d.p[i] = take(pyramid_bytes(e->dt, N, H, W, i));
+  d.deferred = fpn_deferred_on(e, N, H, W);
+  if (d.deferred) {
+    d.inner = take((size_t)N * (H / 4) * (W / 4) * 256 * esize(e->dt));
+    d.nblk = N * wino_x3_blocks_per_frame(H / 4, W / 4);
+    d.state = (int*)take(sizeof(int) * ((size_t)d.nblk + e->num_stages));
+    d.count = d.state ? d.state + d.nblk : nullptr;
+    d.list = (int*)take(sizeof(int) * (size_t)d.nblk * e->num_stages);
+  }
+  d.total = off;
+  return d;
 }
 
 extern "C" size_t mcg_trunk_workspace_bytes(const mcg_engine* e, int N, int H, int W, int chunk) {
@@ -623,9 +673,11 @@ extern "C" size_t mcg_decoder_workspace_bytes(const mcg_engine* e, int N) {
 }
 extern "C" size_t mcg_engine_workspace_bytes(const mcg_engine* e, int N, int H, int W, int chunk) {
   if (!e || N <= 0) return 0;
-  size_t total = mcg_trunk_workspace_bytes(e, N, H, W, chunk) + mcg_decoder_workspace_bytes(e, N);
-  for (int i = 0; i < 4; ++i) total += pyramid_bytes(e->dt, N, H, W, i);
-  return total;
+  return mcg_trunk_workspace_bytes(e, N, H, W, chunk) + mcg_decoder_workspace_bytes(e, N) + defer_layout(e, N, H, W, nullptr).total;
+}
+extern "C" size_t mcg_deferred_pyramid_bytes(const mcg_engine* e, int N, int H, int W) {
+  if (!e || N <= 0 || check_shape_ok(N, H, W) == false) return 0;
+  return defer_layout(e, N, H, W, nullptr).total;
 }
 
 static int check_shape(int N, int H, int W) {
@@ -635,7 +687,7 @@ static int check_shape(int N, int H, int W) {
 }
 
 static int trunk_forward(mcg_engine* e, mcg_stream s_, const float* img, int N, int H, int W, int chunk,
-                         void* const pyramid[4], void* ws, size_t ws_bytes, bool backbone_only) {
+                         void* const pyramid[4], void* ws, size_t ws_bytes, bool backbone_only, char* inner0 = nullptr) {
   MCG_CHECK_ARG(e && img && (pyramid || backbone_only) && ws, "mcg_backbone_fpn_forward: null pointer");
   MCG_TRY(check_shape(N, H, W));
   std::lock_guard<std::mutex> lock(e->mu);
@@ -644,14 +696,14 @@ static int trunk_forward(mcg_engine* e, mcg_stream s_, const float* img, int N, 
   if (ws_bytes < need) { mcg_set_error("mcg_backbone_fpn_forward: workspace too small (%zu < %zu)", ws_bytes, need); return MCG_ERR_WORKSPACE; }
   hipStream_t s = (hipStream_t)s_;
   if (chunk < N) {  // sequential frame chunks in a small workspace
-    for (int f0 = 0; f0 < N; f0 += chunk) MCG_TRY(trunk_chunk(e, s, img, f0, (N - f0) < chunk ? (N - f0) : chunk, H, W, pyramid, (char*)ws, backbone_only));
+    for (int f0 = 0; f0 < N; f0 += chunk) MCG_TRY(trunk_chunk(e, s, img, f0, (N - f0) < chunk ? (N - f0) : chunk, H, W, pyramid, (char*)ws, backbone_only, inner0));
     return MCG_OK;
   }
   const int k = trunk_ranges(e, N);
   const int cap = range_frame_cap(e, H, W);
   const int per = (N + k - 1) / k < cap ? (N + k - 1) / k : cap;
   if (k == 1) {
-    for (int f0 = 0; f0 < N; f0 += per) MCG_TRY(trunk_chunk(e, s, img, f0, (N - f0) < per ? (N - f0) : per, H, W, pyramid, (char*)ws, backbone_only));
+    for (int f0 = 0; f0 < N; f0 += per) MCG_TRY(trunk_chunk(e, s, img, f0, (N - f0) < per ? (N - f0) : per, H, W, pyramid, (char*)ws, backbone_only, inner0));
     return MCG_OK;
   }
   // fork: the side streams start after everything already queued on the caller's stream (the input, the previous consumer of
@@ -665,7 +717,7 @@ static int trunk_forward(mcg_engine* e, mcg_stream s_, const float* img, int N, 
     if (hipStreamWaitEvent(e->cand[sides[i - 1]], e->ev_fork, 0) != hipSuccess) { mcg_set_error("mcg_backbone_fpn_forward: hipStreamWaitEvent failed"); return MCG_ERR_HIP; }
   for (int f0 = 0, i = 0; f0 < N && rc == MCG_OK; f0 += per, i = (i + 1) % k) {
     hipStream_t si = i == 0 ? s : e->cand[sides[i - 1]];
-    rc = trunk_chunk(e, si, img, f0, (N - f0) < per ? (N - f0) : per, H, W, pyramid, (char*)ws + (size_t)i * part_ws, backbone_only);
+    rc = trunk_chunk(e, si, img, f0, (N - f0) < per ? (N - f0) : per, H, W, pyramid, (char*)ws + (size_t)i * part_ws, backbone_only, inner0);
   }
   for (int i = 1; i < k; ++i) {  // joined even after a failed launch, so the caller's stream never runs ahead of a side stream
     hipStream_t si = e->cand[sides[i - 1]];
@@ -731,9 +783,11 @@ extern "C" int mcg_bench_backbone_levels(const mcg_engine* e, void* ws, int N, i
 
 // The decoder over an existing pyramid; frame_of != NULL: window frame n reads pyramid row frame_of[n] of a store of pyramid_frames rows
 // (RoIAlign and the query init gather through the table, roi_align.hip / decoder.hip), img_hw is then indexed by pyramid row.
+// d != NULL and deferred: pyramid[0] is computed here, block by block, from d->inner -- before each stage's RoIAlign, the blocks its boxes
+// read that no earlier stage listed (roi_mark_kernel, then wino_x3w_blocks_kernel: same bits as the dense conv).
 static int decoder_forward(mcg_engine* e, hipStream_t s, const void* const pyramid[4], int pyramid_frames, const int32_t* frame_of, int N,
                            int clip_length, int H, int W, const int* img_hw, float* gaze_out, float* boxes_out, float* scores_out, void* ws,
-                           size_t ws_bytes) {
+                           size_t ws_bytes, const DeferSlot* d = nullptr) {
   MCG_CHECK_ARG(e && pyramid && gaze_out && boxes_out && scores_out && ws, "mcg_decoder_forward: null pointer");
   MCG_TRY(check_shape(N, H, W));
   MCG_CHECK_ARG(clip_length > 0 && N % clip_length == 0, "num_frames=%d is not a multiple of clip_length=%d", N, clip_length);
@@ -745,7 +799,24 @@ static int decoder_forward(mcg_engine* e, hipStream_t s, const void* const pyram
   for (int i = 0; i < 4; ++i) { fh[i] = (H / 4) >> i; fw[i] = (W / 4) >> i; }
   char* obj_in = c.obj_a; char* obj_out = c.obj_b;
   float* b_in = c.boxes_a; float* b_out = c.boxes_b;
+  const bool defer = d && d->deferred;
+  if (defer) MCG_TRY(launch_defer_clear(s, d->state, d->nblk + e->num_stages));
   for (int st = 0; st < e->num_stages; ++st) {
+    if (defer) {
+      const mcg_conv_weights& cw = e->fpn_out[0];
+      MCG_TRY(launch_roi_mark(s, b_in, N * 3, 3, 0, fh[0], fw[0], strides[0], d->state, d->list + (size_t)st * d->nblk, d->count + st));
+      WinoParams wp;
+      memset(&wp, 0, sizeof(wp));
+      wp.x = (const float*)d->inner; wp.u = cw.wf; wp.bias = cw.bias; wp.y = (float*)d->p[0];
+      wp.H = fh[0]; wp.W = fw[0]; wp.frames = N; wp.Cin = cw.cin; wp.Cout = cw.cout; wp.relu = 0; wp.wscale = cw.wscale;
+      // booked once, at the dense conv's algorithmic FLOPs and bytes (the roofline counts the reference's arithmetic)
+      const double M = (double)N * fh[0] * fw[0];
+      ProfRec* rec = prof_begin(e->ctx, s, 73, (int)M, cw.cout, 9 * cw.cin, st == 0 ? 2.0 * M * 9.0 * cw.cin * cw.cout : 0.0,
+                                st == 0 ? 4.0 * (M * (cw.cin + cw.cout) + 9.0 * cw.cin * cw.cout) : 0.0);
+      const int wrc = launch_wino_x3_blocks(s, wp, d->list + (size_t)st * d->nblk, d->count + st, d->nblk);
+      prof_end(rec, s);
+      if (wrc) { mcg_set_error("wino_x3 block launch failed"); return MCG_ERR_HIP; }
+    }
     MCG_TRY(launch_roi_align(s, e->dt, pyramid, fh, fw, strides, 256, b_in, N * 3, 3, frame_of, pyramid_frames, c.roi, nullptr));
     float* bdst = (st == e->num_stages - 1) ? boxes_out : b_out;
     MCG_TRY(stage_forward_ctx(s, e->dt, &e->stage_w[(size_t)st * MCG_SW_COUNT], c.roi, obj_in, b_in, N, clip_length, obj_out, bdst,
@@ -771,6 +842,33 @@ extern "C" int mcg_decoder_forward_indexed(mcg_engine* e, mcg_stream s_, const v
                          ws, ws_bytes);
 }
 
+extern "C" int mcg_deferred_pyramid_levels(const mcg_engine* e, void* slot, int N, int H, int W, void* levels[4], int* deferred) {
+  MCG_CHECK_ARG(e && slot && levels, "mcg_deferred_pyramid_levels: null pointer");
+  MCG_TRY(check_shape(N, H, W));
+  const DeferSlot d = defer_layout(e, N, H, W, (char*)slot);
+  for (int i = 0; i < 4; ++i) levels[i] = d.p[i];
+  if (deferred) *deferred = d.deferred ? 1 : 0;
+  return MCG_OK;
+}
+
+extern "C" int mcg_backbone_fpn_forward_deferred(mcg_engine* e, mcg_stream s, const float* img, int N, int H, int W, int chunk, void* slot,
+                                                 size_t slot_bytes, void* ws, size_t ws_bytes) {
+  MCG_CHECK_ARG(e && slot, "mcg_backbone_fpn_forward_deferred: null pointer");
+  MCG_TRY(check_shape(N, H, W));
+  const DeferSlot d = defer_layout(e, N, H, W, (char*)slot);
+  if (slot_bytes < d.total) { mcg_set_error("mcg_backbone_fpn_forward_deferred: slot too small (%zu < %zu)", slot_bytes, d.total); return MCG_ERR_WORKSPACE; }
+  return trunk_forward(e, s, img, N, H, W, chunk, d.p, ws, ws_bytes, false, d.deferred ? d.inner : nullptr);
+}
+
+extern "C" int mcg_decoder_forward_deferred(mcg_engine* e, mcg_stream s, void* slot, size_t slot_bytes, int N, int clip_length, int H, int W,
+                                            const int* img_hw, float* gaze_out, float* boxes_out, float* scores_out, void* ws, size_t ws_bytes) {
+  MCG_CHECK_ARG(e && slot, "mcg_decoder_forward_deferred: null pointer");
+  MCG_TRY(check_shape(N, H, W));
+  const DeferSlot d = defer_layout(e, N, H, W, (char*)slot);
+  if (slot_bytes < d.total) { mcg_set_error("mcg_decoder_forward_deferred: slot too small (%zu < %zu)", slot_bytes, d.total); return MCG_ERR_WORKSPACE; }
+  return decoder_forward(e, (hipStream_t)s, d.p, N, nullptr, N, clip_length, H, W, img_hw, gaze_out, boxes_out, scores_out, ws, ws_bytes, &d);
+}
+
 extern "C" int mcg_clip_forward(mcg_engine* e, mcg_stream s_, const float* img, int N, int clip_length, int H, int W,
                                 const int* img_hw, int chunk, float* gaze_out, float* boxes_out, float* scores_out,
                                 void* ws, size_t ws_bytes) {
@@ -781,9 +879,9 @@ extern "C" int mcg_clip_forward(mcg_engine* e, mcg_stream s_, const float* img, 
   if (ws_bytes < need) { mcg_set_error("mcg_clip_forward: workspace too small (%zu < %zu)", ws_bytes, need); return MCG_ERR_WORKSPACE; }
   char* base = (char*)ws;
   const size_t trunk_bytes = mcg_trunk_workspace_bytes(e, N, H, W, chunk);
-  void* pyr[4];
-  size_t off = trunk_bytes;
-  for (int i = 0; i < 4; ++i) { pyr[i] = base + off; off += pyramid_bytes(e->dt, N, H, W, i); }
-  MCG_TRY(mcg_backbone_fpn_forward(e, s_, img, N, H, W, chunk, pyr, base, trunk_bytes));
-  return mcg_decoder_forward(e, s_, pyr, N, clip_length, H, W, img_hw, gaze_out, boxes_out, scores_out, base + off, ws_bytes - off);
+  const size_t slot_bytes = defer_layout(e, N, H, W, nullptr).total;
+  const size_t off = trunk_bytes + slot_bytes;
+  MCG_TRY(mcg_backbone_fpn_forward_deferred(e, s_, img, N, H, W, chunk, base + trunk_bytes, slot_bytes, base, trunk_bytes));
+  return mcg_decoder_forward_deferred(e, s_, base + trunk_bytes, slot_bytes, N, clip_length, H, W, img_hw, gaze_out, boxes_out, scores_out,
+                                      base + off, ws_bytes - off);
 }

@@ -16,6 +16,7 @@
 // [0, pyramid_frames) reads nothing: the address is clamped to row 0 and the box's output is NaN.  frame_of == NULL is the plain
 // path (row = n) with the same code and bits as before.
 #include "common.hpp"
+#include "roi_sample.hpp"
 
 struct RoiLevels {
   const void* feat[4];
@@ -34,29 +35,15 @@ __global__ __launch_bounds__(256) void roi_align_kernel(RoiLevels lv, int C, con
   __shared__ int s_valid[2][NS];
   const int box = blockIdx.x, tid = threadIdx.x;
   const float x1 = boxes[box * 4 + 0], y1 = boxes[box * 4 + 1], x2 = boxes[box * 4 + 2], y2 = boxes[box * 4 + 3];
-  // map_roi_levels (single_level_roi_extractor.py:51-54)
-  const float sc = sqrtf((x2 - x1) * (y2 - y1));
-  int level = (int)fminf(fmaxf(floorf(log2f(sc / finest_scale + 1e-6f)), 0.f), 3.f);
-  if (!(sc == sc)) level = 0;  // NaN guard
+  const int level = roi_level(x1, y1, x2, y2, finest_scale);
   const int H = lv.h[level], W = lv.w[level];
   const float ss = lv.scale[level];
   if (tid < 2 * NS) {
     const int axis = tid / NS, i = tid % NS;  // axis 0 = y, 1 = x
-    const float start = (axis == 0 ? y1 : x1) * ss - 0.5f, end = (axis == 0 ? y2 : x2) * ss - 0.5f;
-    const float bin = (end - start) / (float)P;
-    const int L = axis == 0 ? H : W;
-    float c = start + (float)(i / S) * bin + ((float)(i % S) + 0.5f) * bin / (float)S;
-    const int valid = !(c < -1.0f || c > (float)L);
-    c = fmaxf(c, 0.f);
-    int lo = (int)c, hi;
-    if (lo >= L - 1) {
-      lo = hi = L - 1;
-      c = (float)lo;
-    } else {
-      hi = lo + 1;
-    }
-    const float l = c - (float)lo;
-    s_lo[axis][i] = lo; s_hi[axis][i] = hi; s_l[axis][i] = l; s_h[axis][i] = 1.f - l; s_valid[axis][i] = valid && (c == c);
+    int lo, hi, valid;
+    float l;
+    roi_axis_sample<P, S>(axis == 0 ? y1 : x1, axis == 0 ? y2 : x2, ss, axis == 0 ? H : W, i, lo, hi, l, valid);
+    s_lo[axis][i] = lo; s_hi[axis][i] = hi; s_l[axis][i] = l; s_h[axis][i] = 1.f - l; s_valid[axis][i] = valid;
   }
   if (tid == 0) {
     if (levels_out) levels_out[box] = level;
@@ -108,6 +95,60 @@ __global__ __launch_bounds__(256) void roi_align_kernel(RoiLevels lv, int C, con
     for (int e = 0; e < EPC; ++e) acc[e] *= (1.0f / (float)(S * S));
     *(uint4*)(out + ((long long)box * (P * P) + bin) * C + cg * EPC) = f32_to_chunk(acc, (T*)nullptr);
   }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// Deferred pyramid level (engine.hip): before a stage's RoIAlign, flag the 8 x 8-pixel output blocks of the deferred
+// level that its boxes read and list those not yet listed.  One workgroup per box; a box routed to another level does nothing.  The
+// pixels a box reads are {lo, hi of every valid y sample} x {lo, hi of every valid x sample} (a sample pair is read iff both samples are
+// valid): the blocks are that product of block rows and columns.  state[b]: 0 = not listed, 1 = listed (by this or an earlier stage;
+// stream order computes a listed block before the RoIAlign that follows).  Vector atomics only.
+constexpr int kMarkMaxBlocks = 64;   // block rows / columns of the deferred level (512 pixels)
+__global__ __launch_bounds__(256) void roi_mark_kernel(const float* __restrict__ boxes, int boxes_per_frame, int level_deferred, int H, int W,
+                                                       float ss, int* __restrict__ state, int* __restrict__ list, int* __restrict__ count,
+                                                       float finest_scale) {
+  constexpr int P = 7, S = 2, NS = P * S;
+  __shared__ int s_hit[2][kMarkMaxBlocks];
+  const int box = blockIdx.x, tid = threadIdx.x;
+  const float x1 = boxes[box * 4 + 0], y1 = boxes[box * 4 + 1], x2 = boxes[box * 4 + 2], y2 = boxes[box * 4 + 3];
+  if (roi_level(x1, y1, x2, y2, finest_scale) != level_deferred) return;   // uniform per workgroup
+  const int by_n = (H + 7) / 8, bx_n = (W + 7) / 8;
+  if (tid < 2 * kMarkMaxBlocks) s_hit[tid / kMarkMaxBlocks][tid % kMarkMaxBlocks] = 0;
+  __syncthreads();
+  if (tid < 2 * NS) {
+    const int axis = tid / NS, i = tid % NS;
+    int lo, hi, valid;
+    float l;
+    roi_axis_sample<P, S>(axis == 0 ? y1 : x1, axis == 0 ? y2 : x2, ss, axis == 0 ? H : W, i, lo, hi, l, valid);
+    if (valid) { s_hit[axis][lo >> 3] = 1; s_hit[axis][hi >> 3] = 1; }
+  }
+  __syncthreads();
+  const int frame = box / boxes_per_frame;
+  for (int t = tid; t < by_n * bx_n; t += 256) {
+    const int by = t / bx_n, bx = t - by * bx_n;
+    if (s_hit[0][by] && s_hit[1][bx]) {
+      const int id = frame * (by_n * bx_n) + t;
+      if (atomicCAS(&state[id], 0, 1) == 0) list[atomicAdd(count, 1)] = id;
+    }
+  }
+}
+__global__ void defer_clear_kernel(int* __restrict__ p, int n) {
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) p[i] = 0;
+}
+bool roi_mark_supported(int H, int W) { return (H + 7) / 8 <= kMarkMaxBlocks && (W + 7) / 8 <= kMarkMaxBlocks; }
+int launch_defer_clear(hipStream_t s, int* p, int n) {
+  const int blocks = (n + 255) / 256 < 1024 ? (n + 255) / 256 : 1024;
+  hipLaunchKernelGGL(defer_clear_kernel, dim3(blocks > 0 ? blocks : 1), dim3(256), 0, s, p, n);
+  MCG_CHECK_LAUNCH("defer_clear");
+  return MCG_OK;
+}
+int launch_roi_mark(hipStream_t s, const float* boxes, int num_boxes, int boxes_per_frame, int level, int H, int W, int stride, int* state,
+                    int* list, int* count) {
+  MCG_CHECK_ARG(roi_mark_supported(H, W), "roi_mark: deferred level of %dx%d pixels exceeds %d blocks per axis", H, W, kMarkMaxBlocks);
+  hipLaunchKernelGGL(roi_mark_kernel, dim3(num_boxes), dim3(256), 0, s, boxes, boxes_per_frame, level, H, W, 1.0f / (float)stride, state, list,
+                     count, 56.f);
+  MCG_CHECK_LAUNCH("roi_mark");
+  return MCG_OK;
 }
 
 int launch_roi_align(hipStream_t s, mcg_dtype dt, const void* const feats[4], const int feat_h[4], const int feat_w[4],

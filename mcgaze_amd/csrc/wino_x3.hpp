@@ -70,6 +70,11 @@ struct WinoParams {
   int total_pairs, n_tiles;                // groups in all frames; channel tiles
   int tpf, gpf;                            // tiles per frame (0: tiles run over frame boundaries), groups per frame
   float wscale;          // the transformed sums are multiplied by this power of two before the bias (pre-scaled weights); 0 = 1
+  // block tile (wino_x3w_blocks_kernel): the outputs are 8 x 8-pixel blocks (8 rows x 4 pairs) named by a device list; block id =
+  // frame * bpf + by * bxn + bx
+  const int* blk_list;   // block ids to compute
+  const int* blk_count;  // DEVICE count of blk_list entries
+  int bxn, bpf;          // blocks per row, blocks per frame
 };
 
 // NB: 1 KiB pieces per window row.  Tile: RH x RT row tiles of 32 groups, CT column tiles of 32 channels; (G + 2) RH waves.
@@ -391,34 +396,56 @@ template <int IMM>
 __device__ __forceinline__ void buf_load16(u32x4v& dst, uint32_t voffset, const u32x4& srd, uint32_t soffset_uniform) {
   asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen offset:%4" : "=&v"(dst) : "v"(voffset), "s"(srd), "s"(soffset_uniform), "n"(IMM) : "memory");
 }
-template <int NB>
-__global__ __launch_bounds__(256, 1) void wino_x3w_kernel(const WinoParams p) {
+//
+// BLK (wino_x3w_blocks_kernel, the deferred FPN P2 conv -- DESIGN.md 3.1i): the same kernel whose four row tiles are four 8 x 8-pixel
+// BLOCKS (8 rows x 4 pairs = 32 pairs each) taken from a device list, so that a conv can compute only the blocks somebody reads.  The
+// window holds, per block, its 10 rows (one halo row above and below) of ONE 1 KiB piece (16 pixels from the block's first column - 1:
+// the block's 10 input columns), 40 pieces in all; the piece layout, swizzle, K order, transform and epilogue arithmetic are the raster
+// tile's, so a block's bits are those of the same pixels in wino_x3w_kernel (tests/test_gpu_fpn_deferred.py).
+template <int NB, bool BLK>
+__device__ __forceinline__ void wino_x3w_tile(const WinoParams& p, const int logical) {
   using namespace wnx;
   constexpr int G = 2, NV = 4, NW = 4, RT = 4, CT = 4, MT = 128, NT = 128;
   constexpr int ROWB = NB * 1024, WIN_CAP = 48 * 1024, USTAGE = ustage(2);
   constexpr int MAXP = WIN_CAP / 1024 / NW;            // window pieces per wave and slice (upper bound): 12, issued as two batches of 6
   constexpr int HB = MAXP / 2;
+  constexpr int BWR = 10;                               // BLK: window rows per block
+  static_assert(!BLK || (NB == 1 && RT * BWR <= NW * MAXP), "block tile: one piece per window row, every block's rows in the window");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* const s_win = smem;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int nu = wave;
-  const int logical = xcd_remap(blockIdx.x, gridDim.x);
   const int mt = logical / p.n_tiles, ntile = logical - mt * p.n_tiles;
-  int q0, q_end;
-  if (p.tpf > 0) {
-    const int f = mt / p.tpf, t = mt - f * p.tpf;
-    q0 = f * p.gpf + t * MT;
-    q_end = min(q0 + MT, (f + 1) * p.gpf);
+  int q0 = 0, q_end = 0;
+  int bf[RT], by0[RT], bxg[RT];                         // BLK: frame, first row, first pair of block rt
+  uint32_t bokm = 0;                                    // BLK: block rt exists
+  if constexpr (BLK) {
+    const int cnt = __builtin_amdgcn_readfirstlane(*p.blk_count);
+#pragma unroll
+    for (int rt = 0; rt < RT; ++rt) {
+      const int e = RT * mt + rt;
+      if (e < cnt) bokm |= 1u << rt;
+      const int id = __builtin_amdgcn_readfirstlane(p.blk_list[e < cnt ? e : RT * mt]);
+      const int f = id / p.bpf, r = id - f * p.bpf, by = r / p.bxn;
+      bf[rt] = f; by0[rt] = 8 * by; bxg[rt] = 4 * (r - by * p.bxn);
+    }
   } else {
-    q0 = mt * MT;
-    q_end = min(q0 + MT, p.total_pairs);
+    if (p.tpf > 0) {
+      const int f = mt / p.tpf, t = mt - f * p.tpf;
+      q0 = f * p.gpf + t * MT;
+      q_end = min(q0 + MT, (f + 1) * p.gpf);
+    } else {
+      q0 = mt * MT;
+      q_end = min(q0 + MT, p.total_pairs);
+    }
   }
+  auto pick = [&](const int (&a)[RT], int i) { return i == 0 ? a[0] : (i == 1 ? a[1] : (i == 2 ? a[2] : a[3])); };
   const int q_last = q_end - 1;
   const int H1 = p.H + 1;
   auto slot_of = [&](int q) { const int R = q / p.PW; return R + R / p.H + 1; };
-  const int sig_b = __builtin_amdgcn_readfirstlane(slot_of(q0) - 1);
-  const int NP = __builtin_amdgcn_readfirstlane((slot_of(q_last) - sig_b + 2) * NB);
+  const int sig_b = BLK ? 0 : __builtin_amdgcn_readfirstlane(slot_of(q0) - 1);
+  const int NP = BLK ? RT * BWR : __builtin_amdgcn_readfirstlane((slot_of(q_last) - sig_b + 2) * NB);
   const int NSL = p.Cin / KS, KT = 3 * NSL;
   const int n0 = ntile * NT;
   const u32x4 srd_x = make_srd(p.x);
@@ -426,31 +453,56 @@ __global__ __launch_bounds__(256, 1) void wino_x3w_kernel(const WinoParams p) {
   const uint32_t lds_win = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)s_win;
 
   // ---- window pieces of this wave: piece pi = wave + 4 n = block pi % NB (= wave % NB for every n: NB divides 4) of window row pi / NB
+  // (BLK: row pi % 10 of block pi / 10, whose piece starts at pixel pxo[n] - 1)
   uint32_t prow[MAXP];
+  int pxo[MAXP];
   uint32_t pokm = 0, prowokm = 0;
   static_for<MAXP>([&](auto nc) {
     constexpr int n = decltype(nc)::value;
-    const int pi = wave + NW * n, j = pi / NB;
-    const int sg = sig_b + j, f = sg / H1, r = sg - f * H1;
-    if (pi < NP) pokm |= 1u << n;
-    if (r != 0 && f < p.frames) prowokm |= 1u << n;
-    prow[n] = __builtin_amdgcn_readfirstlane((uint32_t)(((long long)(f * p.H + r - 1) * p.W) * p.Cin * 4));
+    const int pi = wave + NW * n;
+    if constexpr (BLK) {
+      const int rb = min(pi / BWR, RT - 1), y = pick(by0, rb) + pi - BWR * rb - 1, f = pick(bf, rb);
+      const bool rowok = y >= 0 && y < p.H;
+      if (pi < NP && ((bokm >> rb) & 1)) pokm |= 1u << n;
+      if (rowok) prowokm |= 1u << n;
+      prow[n] = __builtin_amdgcn_readfirstlane((uint32_t)(((long long)(f * p.H + (rowok ? y : 0)) * p.W) * p.Cin * 4));
+      pxo[n] = __builtin_amdgcn_readfirstlane(2 * pick(bxg, rb));
+    } else {
+      const int j = pi / NB;
+      const int sg = sig_b + j, f = sg / H1, r = sg - f * H1;
+      if (pi < NP) pokm |= 1u << n;
+      if (r != 0 && f < p.frames) prowokm |= 1u << n;
+      prow[n] = __builtin_amdgcn_readfirstlane((uint32_t)(((long long)(f * p.H + r - 1) * p.W) * p.Cin * 4));
+      pxo[n] = 0;
+    }
   });
   pokm = __builtin_amdgcn_readfirstlane(pokm);
   prowokm = __builtin_amdgcn_readfirstlane(prowokm);
   uint32_t w_voff;
+  int l_x;                                              // BLK: this lane's pixel relative to a piece's block column
   {
     const int l_ph = lane >> 5, l_i = (lane >> 2) & 7, l_cs = lane & 3, b = wave & (NB - 1);
     const int x = (8 * b + l_i) * G + l_ph - 1;
     const int c = l_cs ^ ((2 * b + (l_i >> 2)) & 3);
-    w_voff = (unsigned)x < (unsigned)p.W ? (uint32_t)((x * p.Cin + 4 * c) * 4) : MCG_OOB_OFFSET;
+    l_x = x;
+    w_voff = BLK ? (uint32_t)(4 * c * 4) : ((unsigned)x < (unsigned)p.W ? (uint32_t)((x * p.Cin + 4 * c) * 4) : MCG_OOB_OFFSET);
   }
+  auto piece_voff = [&](auto nc) -> uint32_t {
+    constexpr int n = decltype(nc)::value;
+    if (!(prowokm & (1u << n))) return MCG_OOB_OFFSET;
+    if constexpr (BLK) {
+      const int x = pxo[n] + l_x;
+      return (unsigned)x < (unsigned)p.W ? (uint32_t)(x * p.Cin * 4) + w_voff : MCG_OOB_OFFSET;
+    } else {
+      return w_voff;
+    }
+  };
   auto issue_window = [&](auto hc, int cs, uint32_t dst) {       // batch hc (0, 1) of slice cs
     constexpr int h0 = decltype(hc)::value * HB;
     static_for<HB>([&](auto nc) {
       constexpr int n = h0 + decltype(nc)::value;
       if (pokm & (1u << n)) {
-        const uint32_t v = (prowokm & (1u << n)) ? w_voff : MCG_OOB_OFFSET;
+        const uint32_t v = piece_voff(std::integral_constant<int, n>{});
         lds_dma16<0>(v, srd_x, prow[n] + (uint32_t)cs * (KS * 4), dst + (uint32_t)(wave + NW * n) * 1024u);
       }
     });
@@ -471,9 +523,16 @@ __global__ __launch_bounds__(256, 1) void wino_x3w_kernel(const WinoParams p) {
   const char* ap[RT][2][2];                               // window buffer 0, tap ky = 0
 #pragma unroll
   for (int rt = 0; rt < RT; ++rt) {
-    const int q = min(q0 + rt * 32 + pl, q_last);
-    const int R = q / p.PW, xg = q - R * p.PW;
-    const int jrow = (R + R / p.H + 1) - sig_b - 1;
+    int jrow, xg;
+    if constexpr (BLK) {                                  // pair pl of a block: row pl / 4, pair pl % 4 (the window starts at the block)
+      jrow = BWR * rt + (pl >> 2);
+      xg = pl & 3;
+    } else {
+      const int q = min(q0 + rt * 32 + pl, q_last);
+      const int R = q / p.PW;
+      xg = q - R * p.PW;
+      jrow = (R + R / p.H + 1) - sig_b - 1;
+    }
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
       const int wx = G * xg + (t == 0 ? toff0 : toff1);
@@ -561,7 +620,7 @@ __global__ __launch_bounds__(256, 1) void wino_x3w_kernel(const WinoParams p) {
           constexpr int n = (KY == 0 ? HB : 0) + (V - 8);
           const int csn = KY == 0 ? cs + 1 : cs + 2;
           if (csn < NSL && (pokm & (1u << n))) {
-            const uint32_t v = (prowokm & (1u << n)) ? w_voff : MCG_OOB_OFFSET;
+            const uint32_t v = piece_voff(std::integral_constant<int, n>{});
             lds_dma16<0>(v, srd_x, prow[n] + (uint32_t)csn * (KS * 4), lds_win + (KY == 0 ? (WB ^ 1) : WB) * WIN_CAP + (uint32_t)(wave + NW * n) * 1024u);
           }
         }
@@ -637,8 +696,18 @@ __global__ __launch_bounds__(256, 1) void wino_x3w_kernel(const WinoParams p) {
     __syncthreads();
     for (int item = tid; item < PP * CPR; item += 256) {
       const int prl = item / CPR, ch4 = (item - prl * CPR) * 4;
-      const int q = q0 + pass * PP + prl;
-      if (q >= q_end) continue;
+      int R, xo;
+      if constexpr (BLK) {
+        const int rt = 2 * pass + (prl >> 5), pl = prl & 31;
+        const int y = pick(by0, rt) + (pl >> 2);
+        xo = G * (pick(bxg, rt) + (pl & 3));
+        if (!((bokm >> rt) & 1) || y >= p.H || xo >= p.W) continue;
+        R = pick(bf, rt) * p.H + y;
+      } else {
+        const int q = q0 + pass * PP + prl;
+        if (q >= q_end) continue;
+        R = q / p.PW; xo = G * (q - R * p.PW);
+      }
       float4 bv = make_float4(0.f, 0.f, 0.f, 0.f);
       if (p.bias) bv = *(const float4*)(p.bias + n0 + ch4);
       float4 m[NV];
@@ -647,7 +716,6 @@ __global__ __launch_bounds__(256, 1) void wino_x3w_kernel(const WinoParams p) {
       float4 y[2];
       y[0] = make_float4(((m[0].x + m[1].x) + m[2].x) * wsc + bv.x, ((m[0].y + m[1].y) + m[2].y) * wsc + bv.y, ((m[0].z + m[1].z) + m[2].z) * wsc + bv.z, ((m[0].w + m[1].w) + m[2].w) * wsc + bv.w);
       y[1] = make_float4(((m[1].x - m[2].x) - m[3].x) * wsc + bv.x, ((m[1].y - m[2].y) - m[3].y) * wsc + bv.y, ((m[1].z - m[2].z) - m[3].z) * wsc + bv.z, ((m[1].w - m[2].w) - m[3].w) * wsc + bv.w);
-      const int R = q / p.PW, xo = G * (q - R * p.PW);
       float* yp = p.y + ((long long)R * p.W + xo) * p.Cout + n0 + ch4;
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
@@ -658,6 +726,22 @@ __global__ __launch_bounds__(256, 1) void wino_x3w_kernel(const WinoParams p) {
       }
     }
     __syncthreads();
+  }
+}
+template <int NB>
+__global__ __launch_bounds__(256, 1) void wino_x3w_kernel(const WinoParams p) {
+  wino_x3w_tile<NB, false>(p, xcd_remap(blockIdx.x, gridDim.x));
+}
+// The block tile over a device list: a fixed grid of one workgroup per CU walks the *blk_count entries, four blocks x one 128-channel
+// tile per unit (no host sync: the launch shape does not depend on the count).  With two channel tiles, units 2 m and 2 m + 1 (the same
+// four blocks) go to one XCD (workgroups are dealt round-robin over the 8 XCDs) so that the second reads the window from L2.
+__global__ __launch_bounds__(256, 1) void wino_x3w_blocks_kernel(const WinoParams p) {
+  const int units = __builtin_amdgcn_readfirstlane(((*p.blk_count + 3) >> 2) * p.n_tiles);
+  const int padded = p.n_tiles == 2 ? (units + 15) & ~15 : units;
+  for (int u = blockIdx.x; u < padded; u += gridDim.x) {
+    int logical = u;
+    if (p.n_tiles == 2) { const int x = u & 7, j = u >> 3; logical = (j & 1) + 2 * (x + 8 * (j >> 1)); }
+    if (logical < units) wino_x3w_tile<1, true>(p, logical);
   }
 }
 
@@ -729,6 +813,37 @@ static inline int launch_wino_x3_nb(hipStream_t s, const WinoParams& p, int g, i
   if (shape == 0) return launch_wino_x3_t<NB, 2, 2, 4, 2>(s, p, grid);
   if (shape == 1) return launch_wino_x3_t<NB, 2, 1, 2, 2>(s, p, grid);
   return launch_wino_x3_t<NB, 1, 1, 2, 2>(s, p, grid);
+}
+// Block tile (8 x 8-pixel blocks, F(2,3)): the shapes whose window fits (any W a block's 16-pixel piece serves) and whose operands fit the
+// buffer descriptors -- the same arithmetic as launch_wino_x3 on them.  blk_grid: workgroups of the persistent launch.
+static inline bool wino_x3_blocks_applicable(int frames, int H, int W, int Cin, int Cout) {
+  const long long px = (long long)frames * H * W;
+  return Cin % 32 == 0 && Cout % wnx::UNT == 0 && H >= 1 && W >= 2 && frames >= 1 && px * Cin * 4 < MCG_DMA_MAX_BYTES &&
+         px * Cout * 4 < MCG_DMA_MAX_BYTES && px < 0x7fffffffLL;
+}
+static inline int wino_x3_blocks_per_frame(int H, int W) { return ((H + 7) / 8) * ((W + 7) / 8); }
+static inline int launch_wino_x3_blocks(hipStream_t s, WinoParams p, const int* list, const int* count, int max_blocks) {
+  constexpr int kLds = 4 * 64 * 128 * 4;
+  static bool raised[MCG_MAX_DEVICES] = {false};
+  static int cus[MCG_MAX_DEVICES] = {0};
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MCG_MAX_DEVICES) dev = 0;
+  if (!raised[dev]) {
+    if (hipFuncSetAttribute((const void*)wino_x3w_blocks_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kLds) != hipSuccess) return 1;
+    int n = 0;
+    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
+    cus[dev] = n;
+    raised[dev] = true;
+  }
+  p.PW = (p.W + 1) / 2;
+  p.n_tiles = p.Cout / 128;
+  p.bxn = (p.W + 7) / 8;
+  p.bpf = wino_x3_blocks_per_frame(p.H, p.W);
+  p.blk_list = list; p.blk_count = count;
+  const int units = (max_blocks + 3) / 4 * p.n_tiles;
+  const int grid = units < cus[dev] ? units : cus[dev] / 16 * 16;
+  hipLaunchKernelGGL(wino_x3w_blocks_kernel, dim3(grid > 0 ? grid : 1), dim3(256), kLds, s, p);
+  return hipGetLastError() == hipSuccess ? 0 : 1;
 }
 // returns 0 on success; the caller has checked wino_x3_applicable(.., g).  shape: -1 = by grid size (the largest tile that still makes ~half
 // a chip's worth of workgroups), else forced (tests)

@@ -506,7 +506,8 @@ class PipelinedRunner:
     """Two-deep software pipeline over successive batches (throughput serving): the decoder of batch k
     (4 x [RoIAlign + stage] + gaze head: ~110 short, latency-bound launches) runs on a second HIP stream and
     overlaps the trunk of batch k+1, whose large contraction kernels leave CUs idle only at their tails.
-    Pyramids are double-buffered; trunks serialise on stream A, decoders on stream B, ordered by events.
+    Pyramid slots (mcg_deferred_pyramid_bytes: P2..P5, and the P2 inner map when the engine defers the P2 output conv to the decoder)
+    are double-buffered; trunks serialise on stream A, decoders on stream B, ordered by events.
     Every submitted batch is fully processed once ``flush()`` returns control to the caller's stream.  A loop that owns the runner
     should submit from ``runner.sa`` itself (``with torch.cuda.stream(runner.sa): ...``): the caller-stream -> trunk-stream hand-over
     of each submit is then no cross-queue dependency (2 ms per pipeline fill + drain when the queues are idle; bench.py does this)."""
@@ -516,8 +517,7 @@ class PipelinedRunner:
         dev, lib, h = engine.device, engine.lib, engine._handle
         # the decoder's short launches get the high-priority queue so they slot in between the trunk's long kernels
         self.sa, self.sb = pipeline_streams(dev, decoder_priority)
-        self.pyr = [[torch.empty(num_frames, (H // 4) >> i, (W // 4) >> i, 256, dtype=engine.dtype, device=dev) for i in range(4)] for _ in range(2)]
-        self.tabs = [(C.c_void_p * 4)(*[p.data_ptr() for p in lvl]) for lvl in self.pyr]
+        self.slots = [_ws(lib.mcg_deferred_pyramid_bytes(h, num_frames, H, W), dev) for _ in range(2)]
         self.trunk_ws = _ws(lib.mcg_trunk_workspace_bytes(h, num_frames, H, W, chunk_frames), dev)
         self.dec_ws = _ws(lib.mcg_decoder_workspace_bytes(h, num_frames), dev)
         self.trunk_done = [torch.cuda.Event() for _ in range(2)]
@@ -543,13 +543,14 @@ class PipelinedRunner:
         self.sa.wait_stream(cur)                       # input produced on the caller's stream
         if self.used[slot]:
             self.sa.wait_event(self.dec_done[slot])    # the decoder that read this pyramid slot has finished
-        L.check(lib.mcg_backbone_fpn_forward(e._handle, C.c_void_p(self.sa.cuda_stream), _ptr(img), self.N, self.H, self.W, self.chunk,
-                                             self.tabs[slot], _ptr(self.trunk_ws), self.trunk_ws.numel()), 'mcg_backbone_fpn_forward')
+        L.check(lib.mcg_backbone_fpn_forward_deferred(e._handle, C.c_void_p(self.sa.cuda_stream), _ptr(img), self.N, self.H, self.W, self.chunk,
+                                                      _ptr(self.slots[slot]), self.slots[slot].numel(), _ptr(self.trunk_ws), self.trunk_ws.numel()),
+                'mcg_backbone_fpn_forward_deferred')
         self.trunk_done[slot].record(self.sa)
         self.sb.wait_event(self.trunk_done[slot])
-        L.check(lib.mcg_decoder_forward(e._handle, C.c_void_p(self.sb.cuda_stream), self.tabs[slot], self.N, self.T, self.H, self.W,
-                                        _ptr(img_hw), _ptr(out['gaze']), _ptr(out['boxes']), _ptr(out['scores']),
-                                        _ptr(self.dec_ws), self.dec_ws.numel()), 'mcg_decoder_forward')
+        L.check(lib.mcg_decoder_forward_deferred(e._handle, C.c_void_p(self.sb.cuda_stream), _ptr(self.slots[slot]), self.slots[slot].numel(),
+                                                 self.N, self.T, self.H, self.W, _ptr(img_hw), _ptr(out['gaze']), _ptr(out['boxes']),
+                                                 _ptr(out['scores']), _ptr(self.dec_ws), self.dec_ws.numel()), 'mcg_decoder_forward_deferred')
         self.dec_done[slot].record(self.sb)
         self.used[slot] = True
         self.k += 1
