@@ -14,6 +14,7 @@
 #include "pw_single_x3.hpp"
 #include "wino_x3.hpp"
 
+#include <stdarg.h>
 #include <stdlib.h>
 #include <string.h>
 
@@ -311,9 +312,16 @@ __global__ void range_audit_kernel(const float* __restrict__ x, long long n, uns
 }
 // One audited tensor: slot idx of the chunk's sequence (the same for every chunk and frame range, so the counters add up over the batch)
 struct AuditCursor { mcg_engine* e; hipStream_t s; int idx; bool naming; };
-static void audit_tensor(AuditCursor& a, const char* name, const void* p, long long elements) {
+__attribute__((format(printf, 4, 5))) static void audit_tensor(AuditCursor& a, const void* p, long long elements, const char* fmt, ...) {
   if (!a.e->audit_dev || a.idx >= mcg_engine::kAuditCap) return;
-  if (a.naming) a.e->audit_names.push_back(name);
+  if (a.naming) {
+    char name[64];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(name, sizeof(name), fmt, ap);
+    va_end(ap);
+    a.e->audit_names.push_back(name);
+  }
   const long long per_thread = 16;
   long long blocks = (elements + 256 * per_thread - 1) / (256 * per_thread);
   if (blocks > 4096) blocks = 4096;
@@ -325,7 +333,7 @@ static void audit_tensor(AuditCursor& a, const char* name, const void* p, long l
 // ---------------------------------------------------------------- trunk workspace for one chunk of n frames
 struct TrunkWs {
   char *stem_ws, *x0, *xa, *xb, *o1, *o2, *ds, *c[4], *l[4];
-  size_t stem_bytes, total;
+  size_t stem_bytes, big, total;   // big: bytes of xa / xb / ds
 };
 static TrunkWs trunk_layout(mcg_dtype dt, int n, int H, int W, char* base) {
   const size_t es = esize(dt);
@@ -335,11 +343,11 @@ static TrunkWs trunk_layout(mcg_dtype dt, int n, int H, int W, char* base) {
   auto take = [&](size_t bytes) { char* p = base ? base + off : nullptr; off += al256(bytes); return p; };
   t.stem_bytes = mcg_stem_workspace_bytes(dt, n, H, W);
   t.stem_ws = take(t.stem_bytes);
-  const size_t big = (size_t)n * h2 * w2 * 256 * es;  // the largest activation: C2 = [n, H/4, W/4, 256]
+  t.big = (size_t)n * h2 * w2 * 256 * es;  // the largest activation: C2 = [n, H/4, W/4, 256]
   t.x0 = take((size_t)n * h2 * w2 * 64 * es);
-  t.xa = take(big); t.xb = take(big);
-  t.o1 = take(big / 2); t.o2 = take(big / 2);
-  t.ds = take(big);
+  t.xa = take(t.big); t.xb = take(t.big);
+  t.o1 = take(t.big / 2); t.o2 = take(t.big / 2);
+  t.ds = take(t.big);
   for (int i = 0; i < 4; ++i) {
     const size_t hi = (H / 4) >> i, wi = (W / 4) >> i;
     t.c[i] = take((size_t)n * hi * wi * (256u << i) * es);
@@ -355,65 +363,177 @@ static int wino_kind(const mcg_engine* e, mcg_dtype dt, const mcg_conv_weights& 
              ? ((cw.wf4 && e->winograd >= 2 && wino_x3_applicable(n, h, w, cw.cin, cw.cout, 4)) ? 4 : ((cw.wf && wino_x3_applicable(n, h, w, cw.cin, cw.cout, 2)) ? 2 : 0))
              : 0;
 }
-
-static int conv_call(const mcg_engine* e, hipStream_t s, mcg_dtype dt, const mcg_conv_weights& cw, const void* x, int n, int h, int w, void* y,
-                     int relu, const void* res, int res_mode, int hr, int wr) {
+// f16x3: a 3x3 / stride 1 conv as a 1-D Winograd F(g,3) contraction (wino_x3.hpp) on x [n, h, w, cin] -> y
+static WinoParams wino_params(const mcg_conv_weights& cw, int g, const void* x, int n, int h, int w, void* y, int relu) {
+  WinoParams wp;
+  memset(&wp, 0, sizeof(wp));
+  wp.x = (const float*)x; wp.u = g == 4 ? cw.wf4 : cw.wf; wp.bias = cw.bias; wp.y = (float*)y;
+  wp.H = h; wp.W = w; wp.frames = n; wp.Cin = cw.cin; wp.Cout = cw.cout; wp.relu = relu; wp.wscale = cw.wscale;
+  return wp;
+}
+// A Winograd launch of conv cw over M output pixels is booked as the DIRECT convolution's FLOPs and bytes: the roofline
+// keeps counting the reference's arithmetic.  book = false: 0 / 0 (a launch whose work an earlier record already counts)
+static ProfRec* prof_begin_wino(const McgCtx& ctx, hipStream_t s, const mcg_conv_weights& cw, long long M, bool book = true) {
+  return prof_begin(ctx, s, 73, (int)M, cw.cout, 9 * cw.cin, book ? 2.0 * M * 9.0 * cw.cin * cw.cout : 0.0,
+                    book ? 4.0 * ((double)M * (cw.cin + cw.cout) + 9.0 * cw.cin * cw.cout) : 0.0);
+}
+// Closes the profile record of a launch that returned rc: a failed launch is MCG_ERR_HIP ("<what> launch failed")
+static int launch_done(ProfRec* rec, hipStream_t s, int rc, const char* what) {
+  prof_end(rec, s);
+  if (rc) { mcg_set_error("%s launch failed", what); return MCG_ERR_HIP; }
+  return MCG_OK;
+}
+// The contraction kernel's descriptor of conv cw on x [n, h, w, cin] -> y, with an optional residual (res_mode; [n, hr, wr] for UPSAMPLE_ADD)
+static mcg_conv_desc conv_desc(mcg_dtype dt, const mcg_conv_weights& cw, const void* x, int n, int h, int w, void* y, int relu,
+                               const void* res, int res_mode, int hr, int wr) {
   mcg_conv_desc d;
   memset(&d, 0, sizeof(d));
   d.x = x; d.w = cw.w; d.bias = cw.bias; d.residual = res; d.y = y;
   d.N = n; d.H = h; d.W = w; d.Cin = cw.cin; d.Cout = cw.cout; d.KH = cw.k; d.KW = cw.k; d.stride = cw.stride; d.pad = cw.pad;
   d.relu = relu; d.residual_mode = res_mode; d.Hr = hr; d.Wr = wr;
   d.wscale = dt == MCG_F16X3 ? cw.wscale : 0.f;
+  return d;
+}
+static int conv_call(const mcg_engine* e, hipStream_t s, mcg_dtype dt, const mcg_conv_weights& cw, const void* x, int n, int h, int w, void* y,
+                     int relu, const void* res, int res_mode, int hr, int wr) {
   const long long M = (long long)n * h * w;
   const int rm = res ? res_mode : MCG_RES_NONE;
-  if (mcg_is16(dt) && e->pw_single && e->ctx.tile < 0 && !e->ctx.staged && cw.wf && cw.bias && cw.k == 1 && cw.stride == 1 && cw.pad == 0 &&
-      pw_single_applicable(cw.cin, cw.cout, rm, M, rm == MCG_RES_UPSAMPLE_ADD ? (long long)n * hr * wr : M) && M < 0x7fffffffll) {
+  const long long res_m = rm == MCG_RES_UPSAMPLE_ADD ? (long long)n * hr * wr : M;   // residual rows
+  const bool x3 = dt == MCG_F16X3;
+  // the HBM-bound 1x1 convs by the persistent register-resident-weight kernel: 16-bit pw_single.hpp, f16x3 pw_single_x3.hpp (256 -> 256 / 1024)
+  if ((x3 || mcg_is16(dt)) && e->pw_single && e->ctx.tile < 0 && cw.wf && cw.bias && cw.k == 1 && cw.stride == 1 && cw.pad == 0 && M < 0x7fffffffll &&
+      (x3 ? pw_single_x3_applicable(cw.cin, cw.cout, rm, M, res_m) : !e->ctx.staged && pw_single_applicable(cw.cin, cw.cout, rm, M, res_m))) {
     PwSingleParams pp;
     memset(&pp, 0, sizeof(pp));
     pp.a = x; pp.res = res; pp.wf = cw.wf; pp.bias = cw.bias; pp.y = y;
-    pp.M = (int)M; pp.relu = relu; pp.Ho = h; pp.Wo = w;
+    pp.M = (int)M; pp.relu = relu; pp.Ho = h; pp.Wo = w; pp.wscale = x3 ? cw.wscale : 0.f;
     if (rm == MCG_RES_UPSAMPLE_ADD) { pp.Hr = hr; pp.Wr = wr; pp.rscale_h = (float)hr / (float)h; pp.rscale_w = (float)wr / (float)w; }
-    const double res_rows = rm == MCG_RES_NONE ? 0.0 : (rm == MCG_RES_ADD ? (double)M : (double)n * hr * wr);
-    ProfRec* rec = prof_begin(e->ctx, s, 61, pp.M, cw.cout, cw.cin, 2.0 * M * cw.cin * cw.cout,
-                              2.0 * ((double)M * (cw.cin + cw.cout) + res_rows * cw.cout + (double)cw.cin * cw.cout));
-    const int prc = launch_pw_single(s, pp, cw.cin, cw.cout, rm == MCG_RES_NONE ? 0 : (rm == MCG_RES_ADD ? 1 : 2), dt == MCG_F16);
-    prof_end(rec, s);
-    if (prc) { mcg_set_error("pw_single launch failed"); return MCG_ERR_HIP; }
-    return MCG_OK;
+    ProfRec* rec = prof_begin(e->ctx, s, x3 ? 71 : 61, pp.M, cw.cout, cw.cin, 2.0 * M * cw.cin * cw.cout,
+                              (double)esize(dt) * ((double)M * (cw.cin + cw.cout) + (rm == MCG_RES_NONE ? 0.0 : (double)res_m) * cw.cout + (double)cw.cin * cw.cout));
+    const int rmode = rm == MCG_RES_NONE ? 0 : (rm == MCG_RES_ADD ? 1 : 2);
+    return launch_done(rec, s, x3 ? launch_pw_single_x3(s, pp, cw.cout, rmode) : launch_pw_single(s, pp, cw.cin, cw.cout, rmode, dt == MCG_F16),
+                       x3 ? "pw_single_x3" : "pw_single");
   }
-  if (dt == MCG_F16X3 && e->pw_single && e->ctx.tile < 0 && cw.wf && cw.bias && cw.k == 1 && cw.stride == 1 && cw.pad == 0 &&
-      pw_single_x3_applicable(cw.cin, cw.cout, rm, M, rm == MCG_RES_UPSAMPLE_ADD ? (long long)n * hr * wr : M) && M < 0x7fffffffll) {
-    // f16x3: the HBM-bound 256 -> 256 / 256 -> 1024 convs by the persistent streaming kernel (pw_single_x3.hpp)
-    PwSingleParams pp;
-    memset(&pp, 0, sizeof(pp));
-    pp.a = x; pp.res = res; pp.wf = cw.wf; pp.bias = cw.bias; pp.y = y;
-    pp.M = (int)M; pp.relu = relu; pp.Ho = h; pp.Wo = w; pp.wscale = cw.wscale;
-    if (rm == MCG_RES_UPSAMPLE_ADD) { pp.Hr = hr; pp.Wr = wr; pp.rscale_h = (float)hr / (float)h; pp.rscale_w = (float)wr / (float)w; }
-    const double res_rows = rm == MCG_RES_NONE ? 0.0 : (rm == MCG_RES_ADD ? (double)M : (double)n * hr * wr);
-    ProfRec* rec = prof_begin(e->ctx, s, 71, pp.M, cw.cout, cw.cin, 2.0 * M * cw.cin * cw.cout,
-                              4.0 * ((double)M * (cw.cin + cw.cout) + res_rows * cw.cout + (double)cw.cin * cw.cout));
-    const int prc = launch_pw_single_x3(s, pp, cw.cout, rm == MCG_RES_NONE ? 0 : (rm == MCG_RES_ADD ? 1 : 2));
-    prof_end(rec, s);
-    if (prc) { mcg_set_error("pw_single_x3 launch failed"); return MCG_ERR_HIP; }
-    return MCG_OK;
-  }
-  // F(4,3) where the layer's shape allows it and the weights carry that copy, else F(2,3), else the direct kernel -- by SHAPE only
+  // F(4,3) where the layer's shape allows it and the weights carry that copy, else F(2,3) (FPN outputs, layer3's conv2), else the direct kernel
   const int wg = wino_kind(e, dt, cw, n, h, w, rm);
   if (wg) {
-    // f16x3: the 3x3 / stride 1 convs (FPN outputs, layer3's conv2) as a 1-D Winograd F(2,3) contraction (wino_x3.hpp); FLOPs and bytes
-    // are booked as the DIRECT convolution's: the roofline keeps counting the reference's arithmetic
-    WinoParams wp;
-    memset(&wp, 0, sizeof(wp));
-    wp.x = (const float*)x; wp.u = wg == 4 ? cw.wf4 : cw.wf; wp.bias = cw.bias; wp.y = (float*)y;
-    wp.H = h; wp.W = w; wp.frames = n; wp.Cin = cw.cin; wp.Cout = cw.cout; wp.relu = relu; wp.wscale = cw.wscale;
-    ProfRec* rec = prof_begin(e->ctx, s, 73, (int)M, cw.cout, 9 * cw.cin, 2.0 * M * 9.0 * cw.cin * cw.cout,
-                              4.0 * ((double)M * (cw.cin + cw.cout) + 9.0 * cw.cin * cw.cout));
-    const int wrc = launch_wino_x3(s, wp, e->wino_tile, wg);
-    prof_end(rec, s);
-    if (wrc) { mcg_set_error("wino_x3 launch failed"); return MCG_ERR_HIP; }
-    return MCG_OK;
+    ProfRec* rec = prof_begin_wino(e->ctx, s, cw, M);
+    return launch_done(rec, s, launch_wino_x3(s, wino_params(cw, wg, x, n, h, w, y, relu), e->wino_tile, wg), "wino_x3");
   }
+  const mcg_conv_desc d = conv_desc(dt, cw, x, n, h, w, y, relu, res, res_mode, hr, wr);
   return conv2d_ctx(s, dt, &d, e->ctx);
+}
+
+// The trunk's walk over its bottleneck blocks: the current block's input and the buffers of its conv1 / conv2 outputs
+struct TrunkCursor {
+  const void* x;     // block input [n, h, w, *]
+  int h, w, ci;      // convs[ci] = the block's conv1
+  char *o1, *o2;     // conv1 / conv2 outputs; the fused tail writes the NEXT conv1 output into o2 and the two swap
+  bool o1_ready;     // o1 already holds this block's conv1 output (written by the previous block's pointwise-pair / fused-tail kernel)
+  bool x_blocked;    // x is in the fused tail's blocked layout (written by the previous block's fused tail for the next one's only)
+};
+// f16x3: the fused tail (bneck_x3.hpp: conv2 -> conv3 (+ downsample / + residual) -> the next block's conv1 as ONE kernel) of the block whose
+// conv1 is convs[ci] (block index b), if one was handed over and every shape matches
+static const mcg_fused_block* fused_tail_at(const mcg_engine* e, int ci, int b) {
+  if (!(e->dt == MCG_F16X3 && e->bneck_fused && e->ctx.tile < 0) || ci + 2 >= (int)e->convs.size()) return nullptr;
+  const mcg_fused_block* f = nullptr;
+  for (const mcg_fused_block& q : e->fused)
+    if (q.conv2_index == ci + 1) f = &q;
+  if (!f) return nullptr;
+  const bool ds = b == 0;
+  const mcg_conv_weights &d2 = e->convs[ci + 1], &d3 = e->convs[ci + 2];
+  const int kk = ds ? e->convs[ci + 3].cin : 0, ss = ds ? e->convs[ci + 3].stride : 1;
+  const int cn_i = ci + (ds ? 4 : 3);
+  const bool nx = f->cn == 0 || (cn_i < (int)e->convs.size() && e->convs[cn_i].k == 1 && e->convs[cn_i].stride == 1 && e->convs[cn_i].cout == f->cn && e->convs[cn_i].cin == f->c);
+  return (d2.k == 3 && d2.stride == 1 && d2.pad == 1 && d2.cin == f->cm && d2.cout == f->cm && d3.cout == f->c && f->nsrc == (ds ? 2 : 1) && nx &&
+          bneck_x3_applicable(f->cm, f->c, f->cn, f->nsrc, kk, ss)) ? f : nullptr;
+}
+// Block (l, b) from o1 by its fused tail fb into y (same size: conv2 has stride 1), and the next conv1 into o2
+static int fused_tail_step(const mcg_engine* e, hipStream_t s, const TrunkWs& t, AuditCursor& au, TrunkCursor& c, const mcg_fused_block* fb,
+                           int n, int l, int b, void* y) {
+  const bool has_ds = b == 0;
+  const int k2 = has_ds ? e->convs[c.ci + 3].cin : 0;
+  BneckParams bp;
+  memset(&bp, 0, sizeof(bp));
+  bp.x = (const float*)c.o1; bp.res = (const float*)c.x; bp.wstream = (const char*)fb->wstream; bp.bias = fb->bias;
+  bp.y = (float*)y; bp.z = (float*)c.o2; bp.H = c.h; bp.W = c.w;
+  // y goes to the NEXT block's fused tail only (as its residual; its conv1 is this kernel's z, cn > 0): both sides use the kernel's blocked
+  // layout -- whole-line stores and loads (bneck_x3.hpp) -- where the block grid fits the ping-pong buffer; not under range_audit,
+  // which reads tensors as [M][C]
+  const long long blk_bytes = (long long)n * ((c.h + bnx::TH - 1) / bnx::TH) * ((c.w + bnx::TW - 1) / bnx::TW) * bnx::NPIX * fb->c * (long long)esize(e->dt);
+  const mcg_fused_block* fnext = (b + 1 < e->blocks[l]) ? fused_tail_at(e, c.ci + (has_ds ? 4 : 3), b + 1) : nullptr;
+  bp.res_blocked = c.x_blocked ? 1 : 0;
+  bp.y_blocked = (e->bneck_blocked && !e->audit_dev && y != (void*)t.c[l] && fb->cn > 0 && fnext && fnext->nsrc == 1 && fnext->c == fb->c &&
+                  blk_bytes <= (long long)t.big) ? 1 : 0;
+  const double M = (double)n * c.h * c.w;
+  ProfRec* rec = prof_begin(e->ctx, s, 70, n * c.h * c.w, fb->c + fb->cn, 9 * fb->cm + fb->cm + k2 + fb->c,
+                            2.0 * M * (9.0 * fb->cm * fb->cm + (double)(fb->cm + k2) * fb->c + (double)fb->c * fb->cn),
+                            4.0 * (M * (fb->cm + (has_ds ? k2 : fb->c) + fb->c + fb->cn) + 9.0 * fb->cm * fb->cm + (double)(fb->cm + k2) * fb->c + (double)fb->c * fb->cn));
+  MCG_TRY(launch_done(rec, s, launch_bneck_x3(s, bp, n, fb->cm, fb->nsrc, fb->cn), "bneck_x3"));
+  audit_tensor(au, y, (long long)n * c.h * c.w * fb->c, "layer%d.%d.out (fused tail)", l + 1, b);
+  if (fb->cn > 0) {
+    audit_tensor(au, c.o2, (long long)n * c.h * c.w * fb->cn, "layer%d.%d.next_conv1 (fused tail)", l + 1, b);
+    std::swap(c.o1, c.o2);
+    c.o1_ready = true;
+  }
+  c.x_blocked = bp.y_blocked != 0;
+  return MCG_OK;
+}
+// pw_pair.hpp: conv3 (+ downsample / + residual) of block (l, b) and the NEXT block's conv1 -- the following block's, or the next layer's
+// first (1x1, stride 1 on this block's output) -- as one kernel: layer1 of the 16-bit engines, where both are HBM-bound.  -> that conv1's
+// weights, or NULL where the pair does not apply (M = output pixels)
+static const mcg_conv_weights* pw_pair_next(const mcg_engine* e, int ci, int l, int b, long long M) {
+  const bool has_ds = b == 0;
+  const mcg_conv_weights& c3 = e->convs[ci + 2];
+  const mcg_conv_weights* c3w = has_ds ? (e->c3_ds[l].w ? &e->c3_ds[l] : nullptr) : &c3;
+  const int ci_next = ci + (has_ds ? 4 : 3);
+  const mcg_conv_weights* c1n = ci_next < (int)e->convs.size() ? &e->convs[ci_next] : nullptr;
+  const int k2 = has_ds ? e->convs[ci + 3].cin : 0;
+  return (mcg_is16(e->dt) && e->pw_pair && l == 0 && c3w && c1n && c3w->wf && c1n->wf && c3w->bias && c1n->bias && c1n->k == 1 && c1n->stride == 1 &&
+          c1n->cin == c3.cout && pw_pair_applicable(c3.cin, k2, has_ds ? e->convs[ci + 3].stride : 1, c3.cout, c1n->cout, M) && M < 0x7fffffffll)
+             ? c1n : nullptr;
+}
+static int pw_pair_step(const mcg_engine* e, hipStream_t s, TrunkCursor& c, const mcg_conv_weights& c1n, int n, int l, int b, void* y, int ho, int wo) {
+  const bool has_ds = b == 0;
+  const mcg_conv_weights& c3 = e->convs[c.ci + 2];
+  const mcg_conv_weights& c3w = has_ds ? e->c3_ds[l] : c3;
+  PwPairParams pp;
+  memset(&pp, 0, sizeof(pp));
+  pp.a1 = c.o2; pp.K1 = c3.cin;
+  if (has_ds) { pp.a2 = c.x; pp.K2 = e->convs[c.ci + 3].cin; pp.stride2 = e->convs[c.ci + 3].stride; pp.H2 = c.h; pp.W2 = c.w; }
+  else pp.res = c.x;
+  pp.w3f = c3w.wf; pp.b3 = c3w.bias; pp.y = y;
+  pp.w1f = c1n.wf; pp.b1 = c1n.bias; pp.z = c.o1;
+  pp.M = n * ho * wo; pp.C = c3.cout; pp.C2 = c1n.cout; pp.Ho = ho; pp.Wo = wo;
+  // cfg 60: both contractions of the pair count (2 M (K C + C C2))
+  ProfRec* rec = prof_begin(e->ctx, s, 60, pp.M, pp.C + pp.C2, pp.K1 + pp.K2, 2.0 * pp.M * ((double)(pp.K1 + pp.K2) * pp.C + (double)pp.C * pp.C2),
+                            2.0 * ((double)pp.M * (pp.K1 + pp.K2 + (has_ds ? 0 : pp.C) + pp.C + pp.C2) + (double)(pp.K1 + pp.K2) * pp.C + (double)pp.C * pp.C2));
+  MCG_TRY(launch_done(rec, s, launch_pw_pair(s, pp, e->dt == MCG_F16), "pw_pair"));
+  c.o1_ready = true;
+  return MCG_OK;
+}
+// conv3 (+ downsample / + residual) of block (l, b) from o2 into y [n, ho, wo]
+static int conv3_step(const mcg_engine* e, hipStream_t s, const TrunkWs& t, AuditCursor& au, const TrunkCursor& c, int n, int l, int b, void* y,
+                      int ho, int wo) {
+  const mcg_conv_weights& c3 = e->convs[c.ci + 2];
+  if (b == 0 && e->c3_ds[l].w) {
+    // conv3 and the downsample conv as ONE K-concatenated GEMM: relu([o2 | x@stride] . [W3 | Wd]^T + b3 + bd);
+    // the downsample output never goes to HBM and conv3 reads no residual.
+    const mcg_conv_weights& ds = e->convs[c.ci + 3];
+    mcg_conv_desc d = conv_desc(e->dt, e->c3_ds[l], c.o2, n, ho, wo, y, 1, nullptr, MCG_RES_NONE, 0, 0);
+    d.Cin = c3.cin;   // o2's share of the weights' K = c3.cin + ds.cin
+    d.x2 = c.x; d.Cin2 = ds.cin; d.stride2 = ds.stride; d.H2 = c.h; d.W2 = c.w;
+    MCG_TRY(conv2d_ctx(s, e->dt, &d, e->ctx));
+  } else {
+    const void* identity = c.x;
+    if (b == 0) {
+      MCG_TRY(conv_call(e, s, e->dt, e->convs[c.ci + 3], c.x, n, c.h, c.w, t.ds, 0, nullptr, MCG_RES_NONE, 0, 0));
+      identity = t.ds;
+    }
+    MCG_TRY(conv_call(e, s, e->dt, c3, c.o2, n, ho, wo, y, 1, identity, MCG_RES_ADD, 0, 0));
+  }
+  audit_tensor(au, y, (long long)n * ho * wo * c3.cout, "layer%d.%d.out", l + 1, b);
+  return MCG_OK;
 }
 
 // Backbone + FPN over frames [f0, f0+n): writes pyramid level i at frame offset f0.
@@ -426,132 +546,30 @@ static int trunk_chunk(mcg_engine* e, hipStream_t s, const float* img, int f0, i
   if (inner0) t.l[0] = inner0 + (size_t)f0 * (H / 4) * (W / 4) * 256 * es;
   MCG_TRY(stem_forward_ctx(s, dt, img + (size_t)f0 * 3 * H * W, e->stem.w, e->stem.bias, t.x0, n, H, W, t.stem_ws, t.stem_bytes, e->ctx));
   AuditCursor au{e, s, 0, e->audit_dev != nullptr && e->audit_names.empty()};
-  char aname[64];
-  audit_tensor(au, "stem", t.x0, (long long)n * (H / 4) * (W / 4) * 64);
-  const void* x = t.x0;
-  int h = H / 4, w = W / 4, ci = 0;
-  bool x_blocked = false;  // x is in the fused tail's blocked layout (written by the previous block's fused tail for the next one's only)
-  bool o1_ready = false;   // o1 already holds this block's conv1 output (written by the previous block's pointwise-pair / fused-tail kernel)
-  char *o1 = t.o1, *o2 = t.o2;   // conv1 / conv2 outputs; the fused tail writes the NEXT conv1 output into o2 and the two swap
+  audit_tensor(au, t.x0, (long long)n * (H / 4) * (W / 4) * 64, "stem");
+  TrunkCursor c{t.x0, H / 4, W / 4, 0, t.o1, t.o2, false, false};
   for (int l = 0; l < 4; ++l) {
     for (int b = 0; b < e->blocks[l]; ++b) {
-      const mcg_conv_weights& c1 = e->convs[ci], &c2 = e->convs[ci + 1], &c3 = e->convs[ci + 2];
-      const bool has_ds = b == 0;
-      const int ho = (h + 2 * c2.pad - c2.k) / c2.stride + 1, wo = (w + 2 * c2.pad - c2.k) / c2.stride + 1;
-      void* y = (b == e->blocks[l] - 1) ? (void*)t.c[l] : (x == t.xa ? (void*)t.xb : (void*)t.xa);
-      if (!o1_ready) {
-        MCG_TRY(conv_call(e, s, dt, c1, x, n, h, w, o1, 1, nullptr, MCG_RES_NONE, 0, 0));
-        snprintf(aname, sizeof(aname), "layer%d.%d.conv1", l + 1, b);
-        audit_tensor(au, aname, o1, (long long)n * h * w * c1.cout);
+      const mcg_conv_weights &c1 = e->convs[c.ci], &c2 = e->convs[c.ci + 1];
+      const int ho = (c.h + 2 * c2.pad - c2.k) / c2.stride + 1, wo = (c.w + 2 * c2.pad - c2.k) / c2.stride + 1;
+      void* y = (b == e->blocks[l] - 1) ? (void*)t.c[l] : (c.x == t.xa ? (void*)t.xb : (void*)t.xa);
+      if (!c.o1_ready) {
+        MCG_TRY(conv_call(e, s, dt, c1, c.x, n, c.h, c.w, c.o1, 1, nullptr, MCG_RES_NONE, 0, 0));
+        audit_tensor(au, c.o1, (long long)n * c.h * c.w * c1.cout, "layer%d.%d.conv1", l + 1, b);
       }
-      o1_ready = false;
-      // f16x3: conv2 -> conv3 (+ downsample / + residual) -> the next block's conv1 as ONE kernel (bneck_x3.hpp)
-      // fused_at(conv index of a block's conv1, block index): that block's fused tail if one was handed over and every shape matches
-      auto fused_at = [&](int cj, int bj) -> const mcg_fused_block* {
-        if (!(dt == MCG_F16X3 && e->bneck_fused && e->ctx.tile < 0) || cj + 2 >= (int)e->convs.size()) return nullptr;
-        const mcg_fused_block* f = nullptr;
-        for (const mcg_fused_block& q : e->fused)
-          if (q.conv2_index == cj + 1) f = &q;
-        if (!f) return nullptr;
-        const bool ds = bj == 0;
-        const mcg_conv_weights &d2 = e->convs[cj + 1], &d3 = e->convs[cj + 2];
-        const int kk = ds ? e->convs[cj + 3].cin : 0, ss = ds ? e->convs[cj + 3].stride : 1;
-        const int cn_i = cj + (ds ? 4 : 3);
-        const bool nx = f->cn == 0 || (cn_i < (int)e->convs.size() && e->convs[cn_i].k == 1 && e->convs[cn_i].stride == 1 && e->convs[cn_i].cout == f->cn && e->convs[cn_i].cin == f->c);
-        return (d2.k == 3 && d2.stride == 1 && d2.pad == 1 && d2.cin == f->cm && d2.cout == f->cm && d3.cout == f->c && f->nsrc == (ds ? 2 : 1) && nx &&
-                bneck_x3_applicable(f->cm, f->c, f->cn, f->nsrc, kk, ss)) ? f : nullptr;
-      };
-      const mcg_fused_block* fb = fused_at(ci, b);
-      if (x_blocked && !(fb && fb->nsrc == 1)) { mcg_set_error("trunk: a blocked tensor reached a kernel that does not read that layout"); return MCG_ERR_UNSUPPORTED; }
+      c.o1_ready = false;
+      const mcg_fused_block* fb = fused_tail_at(e, c.ci, b);
+      if (c.x_blocked && !(fb && fb->nsrc == 1)) { mcg_set_error("trunk: a blocked tensor reached a kernel that does not read that layout"); return MCG_ERR_UNSUPPORTED; }
       if (fb) {
-        const int k2 = has_ds ? e->convs[ci + 3].cin : 0;
-        const int ci_nx = ci + (has_ds ? 4 : 3);
-        {
-          BneckParams bp;
-          memset(&bp, 0, sizeof(bp));
-          bp.x = (const float*)o1; bp.res = (const float*)x; bp.wstream = (const char*)fb->wstream; bp.bias = fb->bias;
-          bp.y = (float*)y; bp.z = (float*)o2; bp.H = h; bp.W = w;
-          // y goes to the NEXT block's fused tail only (as its residual; its conv1 is this kernel's z, cn > 0): both sides use the kernel's blocked
-          // layout -- whole-line stores and loads (bneck_x3.hpp) -- where the block grid fits the ping-pong buffer; not under range_audit,
-          // which reads tensors as [M][C]
-          const long long blk_bytes = (long long)n * ((h + bnx::TH - 1) / bnx::TH) * ((w + bnx::TW - 1) / bnx::TW) * bnx::NPIX * fb->c * (long long)es;
-          const mcg_fused_block* fnext = (b + 1 < e->blocks[l]) ? fused_at(ci_nx, b + 1) : nullptr;
-          bp.res_blocked = x_blocked ? 1 : 0;
-          bp.y_blocked = (e->bneck_blocked && !e->audit_dev && y != (void*)t.c[l] && fb->cn > 0 && fnext && fnext->nsrc == 1 && fnext->c == fb->c &&
-                          blk_bytes <= (long long)((size_t)n * (H / 4) * (W / 4) * 256 * es)) ? 1 : 0;
-          const double M = (double)n * h * w;
-          ProfRec* rec = prof_begin(e->ctx, s, 70, n * h * w, fb->c + fb->cn, 9 * fb->cm + fb->cm + k2 + fb->c,
-                                    2.0 * M * (9.0 * fb->cm * fb->cm + (double)(fb->cm + k2) * fb->c + (double)fb->c * fb->cn),
-                                    4.0 * (M * (fb->cm + (has_ds ? k2 : fb->c) + fb->c + fb->cn) + 9.0 * fb->cm * fb->cm + (double)(fb->cm + k2) * fb->c + (double)fb->c * fb->cn));
-          const int frc = launch_bneck_x3(s, bp, n, fb->cm, fb->nsrc, fb->cn);
-          prof_end(rec, s);
-          if (frc) { mcg_set_error("bneck_x3 launch failed"); return MCG_ERR_HIP; }
-          snprintf(aname, sizeof(aname), "layer%d.%d.out (fused tail)", l + 1, b);
-          audit_tensor(au, aname, y, (long long)n * h * w * fb->c);
-          if (fb->cn > 0) {
-            snprintf(aname, sizeof(aname), "layer%d.%d.next_conv1 (fused tail)", l + 1, b);
-            audit_tensor(au, aname, o2, (long long)n * h * w * fb->cn);
-          }
-          if (fb->cn > 0) { char* tmp = o1; o1 = o2; o2 = tmp; o1_ready = true; }
-          x = y; h = ho; w = wo;
-          x_blocked = bp.y_blocked != 0;
-          ci = ci_nx;
-          continue;
-        }
-      }
-      MCG_TRY(conv_call(e, s, dt, c2, o1, n, h, w, o2, 1, nullptr, MCG_RES_NONE, 0, 0));
-      snprintf(aname, sizeof(aname), "layer%d.%d.conv2", l + 1, b);
-      audit_tensor(au, aname, o2, (long long)n * ho * wo * c2.cout);
-      // conv3 (+ downsample / + residual) together with the NEXT block's conv1 (pw_pair.hpp): layer1 / layer2, where both are
-      // HBM-bound.  The next conv1 is the following block's, or the next layer's first (1x1, stride 1 on this block's output).
-      const int ci_next = ci + (has_ds ? 4 : 3);
-      const mcg_conv_weights* c3w = has_ds ? (e->c3_ds[l].w ? &e->c3_ds[l] : nullptr) : &c3;
-      const mcg_conv_weights* c1n = ci_next < (int)e->convs.size() ? &e->convs[ci_next] : nullptr;
-      const int k2 = has_ds ? e->convs[ci + 3].cin : 0;
-      if (mcg_is16(dt) && e->pw_pair && l == 0 && c3w && c1n && c3w->wf && c1n->wf && c3w->bias && c1n->bias && c1n->k == 1 && c1n->stride == 1 &&
-          c1n->cin == c3.cout && pw_pair_applicable(c3.cin, k2, has_ds ? e->convs[ci + 3].stride : 1, c3.cout, c1n->cout, (long long)n * ho * wo) && (long long)n * ho * wo < 0x7fffffffll) {
-        PwPairParams pp;
-        memset(&pp, 0, sizeof(pp));
-        pp.a1 = o2; pp.K1 = c3.cin;
-        if (has_ds) { pp.a2 = x; pp.K2 = k2; pp.stride2 = e->convs[ci + 3].stride; pp.H2 = h; pp.W2 = w; }
-        else pp.res = x;
-        pp.w3f = c3w->wf; pp.b3 = c3w->bias; pp.y = y;
-        pp.w1f = c1n->wf; pp.b1 = c1n->bias; pp.z = o1;
-        pp.M = n * ho * wo; pp.C = c3.cout; pp.C2 = c1n->cout; pp.Ho = ho; pp.Wo = wo;
-        // cfg 60: both contractions of the pair count (2 M (K C + C C2))
-        ProfRec* rec = prof_begin(e->ctx, s, 60, pp.M, pp.C + pp.C2, pp.K1 + pp.K2, 2.0 * pp.M * ((double)(pp.K1 + pp.K2) * pp.C + (double)pp.C * pp.C2),
-                                  2.0 * ((double)pp.M * (pp.K1 + pp.K2 + (has_ds ? 0 : pp.C) + pp.C + pp.C2) + (double)(pp.K1 + pp.K2) * pp.C + (double)pp.C * pp.C2));
-        const int prc = launch_pw_pair(s, pp, dt == MCG_F16);
-        prof_end(rec, s);
-        if (prc) { mcg_set_error("pw_pair launch failed"); return MCG_ERR_HIP; }
-        o1_ready = true;
-        x = y; h = ho; w = wo;
-        ci = ci_next;
-        continue;
-      }
-      if (has_ds && e->c3_ds[l].w) {
-        // conv3 and the downsample conv as ONE K-concatenated GEMM: relu([o2 | x@stride] . [W3 | Wd]^T + b3 + bd);
-        // the downsample output never goes to HBM and conv3 reads no residual.
-        const mcg_conv_weights& f = e->c3_ds[l];
-        mcg_conv_desc d;
-        memset(&d, 0, sizeof(d));
-        d.x = o2; d.w = f.w; d.bias = f.bias; d.y = y;
-        d.wscale = dt == MCG_F16X3 ? f.wscale : 0.f;
-        d.N = n; d.H = ho; d.W = wo; d.Cin = c3.cin; d.Cout = c3.cout; d.KH = 1; d.KW = 1; d.stride = 1; d.pad = 0; d.relu = 1;
-        d.x2 = x; d.Cin2 = e->convs[ci + 3].cin; d.stride2 = e->convs[ci + 3].stride; d.H2 = h; d.W2 = w;
-        MCG_TRY(conv2d_ctx(s, dt, &d, e->ctx));
+        MCG_TRY(fused_tail_step(e, s, t, au, c, fb, n, l, b, y));
       } else {
-        const void* identity = x;
-        if (has_ds) {
-          MCG_TRY(conv_call(e, s, dt, e->convs[ci + 3], x, n, h, w, t.ds, 0, nullptr, MCG_RES_NONE, 0, 0));
-          identity = t.ds;
-        }
-        MCG_TRY(conv_call(e, s, dt, c3, o2, n, ho, wo, y, 1, identity, MCG_RES_ADD, 0, 0));
+        MCG_TRY(conv_call(e, s, dt, c2, c.o1, n, c.h, c.w, c.o2, 1, nullptr, MCG_RES_NONE, 0, 0));
+        audit_tensor(au, c.o2, (long long)n * ho * wo * c2.cout, "layer%d.%d.conv2", l + 1, b);
+        const mcg_conv_weights* c1n = pw_pair_next(e, c.ci, l, b, (long long)n * ho * wo);
+        MCG_TRY(c1n ? pw_pair_step(e, s, c, *c1n, n, l, b, y, ho, wo) : conv3_step(e, s, t, au, c, n, l, b, y, ho, wo));
       }
-      snprintf(aname, sizeof(aname), "layer%d.%d.out", l + 1, b);
-      audit_tensor(au, aname, y, (long long)n * ho * wo * c3.cout);
-      x = y; h = ho; w = wo;
-      ci += has_ds ? 4 : 3;
+      c.x = y; c.h = ho; c.w = wo;
+      c.ci += b == 0 ? 4 : 3;
     }
   }
   if (backbone_only) return MCG_OK;  // mcg_bench_backbone_forward: C2..C5 only
@@ -562,14 +580,12 @@ static int trunk_chunk(mcg_engine* e, hipStream_t s, const float* img, int f0, i
     const void* res = i == 3 ? nullptr : t.l[i + 1];
     MCG_TRY(conv_call(e, s, dt, e->lateral[i], t.c[i], n, hs[i], wsz[i], t.l[i], 0, res, res ? MCG_RES_UPSAMPLE_ADD : MCG_RES_NONE,
                       i == 3 ? 0 : hs[i + 1], i == 3 ? 0 : wsz[i + 1]));
-    snprintf(aname, sizeof(aname), "fpn.lateral%d (+ top-down)", i);
-    audit_tensor(au, aname, t.l[i], (long long)n * hs[i] * wsz[i] * 256);
+    audit_tensor(au, t.l[i], (long long)n * hs[i] * wsz[i] * 256, "fpn.lateral%d (+ top-down)", i);
   }
   for (int i = inner0 ? 1 : 0; i < 4; ++i) {
     char* dst = (char*)pyr[i] + (size_t)f0 * hs[i] * wsz[i] * 256 * es;
     MCG_TRY(conv_call(e, s, dt, e->fpn_out[i], t.l[i], n, hs[i], wsz[i], dst, 0, nullptr, MCG_RES_NONE, 0, 0));
-    snprintf(aname, sizeof(aname), "fpn.P%d", i + 2);
-    audit_tensor(au, aname, dst, (long long)n * hs[i] * wsz[i] * 256);
+    audit_tensor(au, dst, (long long)n * hs[i] * wsz[i] * 256, "fpn.P%d", i + 2);
   }
   return MCG_OK;
 }
@@ -694,34 +710,27 @@ static int trunk_forward(mcg_engine* e, mcg_stream s_, const float* img, int N, 
   if (chunk <= 0 || chunk > N) chunk = N;
   const size_t need = mcg_trunk_workspace_bytes(e, N, H, W, chunk);
   if (ws_bytes < need) { mcg_set_error("mcg_backbone_fpn_forward: workspace too small (%zu < %zu)", ws_bytes, need); return MCG_ERR_WORKSPACE; }
-  hipStream_t s = (hipStream_t)s_;
-  if (chunk < N) {  // sequential frame chunks in a small workspace
-    for (int f0 = 0; f0 < N; f0 += chunk) MCG_TRY(trunk_chunk(e, s, img, f0, (N - f0) < chunk ? (N - f0) : chunk, H, W, pyramid, (char*)ws, backbone_only, inner0));
-    return MCG_OK;
-  }
-  const int k = trunk_ranges(e, N);
-  const int cap = range_frame_cap(e, H, W);
-  const int per = (N + k - 1) / k < cap ? (N + k - 1) / k : cap;
-  if (k == 1) {
-    for (int f0 = 0; f0 < N; f0 += per) MCG_TRY(trunk_chunk(e, s, img, f0, (N - f0) < per ? (N - f0) : per, H, W, pyramid, (char*)ws, backbone_only, inner0));
-    return MCG_OK;
-  }
+  // chunk < N: sequential frame chunks in a small workspace; else k concurrent frame ranges of at most the capped share
+  const int k = chunk < N ? 1 : trunk_ranges(e, N), cap = range_frame_cap(e, H, W);
+  const int per = chunk < N ? chunk : ((N + k - 1) / k < cap ? (N + k - 1) / k : cap);
   // fork: the side streams start after everything already queued on the caller's stream (the input, the previous consumer of
   // the pyramid buffers); join: the caller's stream continues after every range.  Range i owns stream i and workspace slot i;
   // a batch larger than k capped ranges takes several rounds on the same streams and slots (in order per stream).
-  const std::vector<int>& sides = side_streams_for(e, s);
-  const size_t part_ws = al256(trunk_layout(e->dt, per, H, W, nullptr).total);
-  if (hipEventRecord(e->ev_fork, s) != hipSuccess) { mcg_set_error("mcg_backbone_fpn_forward: hipEventRecord failed"); return MCG_ERR_HIP; }
-  int rc = MCG_OK;
-  for (int i = 1; i < k; ++i)
-    if (hipStreamWaitEvent(e->cand[sides[i - 1]], e->ev_fork, 0) != hipSuccess) { mcg_set_error("mcg_backbone_fpn_forward: hipStreamWaitEvent failed"); return MCG_ERR_HIP; }
-  for (int f0 = 0, i = 0; f0 < N && rc == MCG_OK; f0 += per, i = (i + 1) % k) {
-    hipStream_t si = i == 0 ? s : e->cand[sides[i - 1]];
-    rc = trunk_chunk(e, si, img, f0, (N - f0) < per ? (N - f0) : per, H, W, pyramid, (char*)ws + (size_t)i * part_ws, backbone_only, inner0);
+  const hipStream_t s = (hipStream_t)s_;
+  hipStream_t si[mcg_engine::kMaxSplit] = {s};
+  if (k > 1) {
+    const std::vector<int>& sides = side_streams_for(e, s);
+    for (int i = 1; i < k; ++i) si[i] = e->cand[sides[i - 1]];
+    if (hipEventRecord(e->ev_fork, s) != hipSuccess) { mcg_set_error("mcg_backbone_fpn_forward: hipEventRecord failed"); return MCG_ERR_HIP; }
+    for (int i = 1; i < k; ++i)
+      if (hipStreamWaitEvent(si[i], e->ev_fork, 0) != hipSuccess) { mcg_set_error("mcg_backbone_fpn_forward: hipStreamWaitEvent failed"); return MCG_ERR_HIP; }
   }
+  const size_t part_ws = k > 1 ? al256(trunk_layout(e->dt, per, H, W, nullptr).total) : 0;
+  int rc = MCG_OK;
+  for (int f0 = 0, i = 0; f0 < N && rc == MCG_OK; f0 += per, i = (i + 1) % k)
+    rc = trunk_chunk(e, si[i], img, f0, (N - f0) < per ? (N - f0) : per, H, W, pyramid, (char*)ws + (size_t)i * part_ws, backbone_only, inner0);
   for (int i = 1; i < k; ++i) {  // joined even after a failed launch, so the caller's stream never runs ahead of a side stream
-    hipStream_t si = e->cand[sides[i - 1]];
-    if (hipEventRecord(e->ev_join[i - 1], si) != hipSuccess || hipStreamWaitEvent(s, e->ev_join[i - 1], 0) != hipSuccess) {
+    if (hipEventRecord(e->ev_join[i - 1], si[i]) != hipSuccess || hipStreamWaitEvent(s, e->ev_join[i - 1], 0) != hipSuccess) {
       mcg_set_error("mcg_backbone_fpn_forward: join failed");
       rc = rc == MCG_OK ? MCG_ERR_HIP : rc;
     }
@@ -781,6 +790,16 @@ extern "C" int mcg_bench_backbone_levels(const mcg_engine* e, void* ws, int N, i
   return MCG_OK;
 }
 
+// Deferred P2 before stage st's RoIAlign: list the 8 x 8 blocks of P2 [N, h, w] that the stage's boxes read and no earlier stage listed
+// (roi_mark_kernel), then compute them from the inner map (wino_x3w_blocks_kernel: same bits as the dense conv).  Booked once, at stage 0
+static int defer_stage_forward(const mcg_engine* e, hipStream_t s, const DeferSlot& d, int st, const float* boxes, int N, int h, int w) {
+  const mcg_conv_weights& cw = e->fpn_out[0];
+  int* list = d.list + (size_t)st * d.nblk;
+  MCG_TRY(launch_roi_mark(s, boxes, N * 3, 3, 0, h, w, 4, d.state, list, d.count + st));
+  ProfRec* rec = prof_begin_wino(e->ctx, s, cw, (long long)N * h * w, st == 0);
+  return launch_done(rec, s, launch_wino_x3_blocks(s, wino_params(cw, 2, d.inner, N, h, w, d.p[0], 0), list, d.count + st, d.nblk), "wino_x3 block");
+}
+
 // The decoder over an existing pyramid; frame_of != NULL: window frame n reads pyramid row frame_of[n] of a store of pyramid_frames rows
 // (RoIAlign and the query init gather through the table, roi_align.hip / decoder.hip), img_hw is then indexed by pyramid row.
 // d != NULL and deferred: pyramid[0] is computed here, block by block, from d->inner -- before each stage's RoIAlign, the blocks its boxes
@@ -802,21 +821,7 @@ static int decoder_forward(mcg_engine* e, hipStream_t s, const void* const pyram
   const bool defer = d && d->deferred;
   if (defer) MCG_TRY(launch_defer_clear(s, d->state, d->nblk + e->num_stages));
   for (int st = 0; st < e->num_stages; ++st) {
-    if (defer) {
-      const mcg_conv_weights& cw = e->fpn_out[0];
-      MCG_TRY(launch_roi_mark(s, b_in, N * 3, 3, 0, fh[0], fw[0], strides[0], d->state, d->list + (size_t)st * d->nblk, d->count + st));
-      WinoParams wp;
-      memset(&wp, 0, sizeof(wp));
-      wp.x = (const float*)d->inner; wp.u = cw.wf; wp.bias = cw.bias; wp.y = (float*)d->p[0];
-      wp.H = fh[0]; wp.W = fw[0]; wp.frames = N; wp.Cin = cw.cin; wp.Cout = cw.cout; wp.relu = 0; wp.wscale = cw.wscale;
-      // booked once, at the dense conv's algorithmic FLOPs and bytes (the roofline counts the reference's arithmetic)
-      const double M = (double)N * fh[0] * fw[0];
-      ProfRec* rec = prof_begin(e->ctx, s, 73, (int)M, cw.cout, 9 * cw.cin, st == 0 ? 2.0 * M * 9.0 * cw.cin * cw.cout : 0.0,
-                                st == 0 ? 4.0 * (M * (cw.cin + cw.cout) + 9.0 * cw.cin * cw.cout) : 0.0);
-      const int wrc = launch_wino_x3_blocks(s, wp, d->list + (size_t)st * d->nblk, d->count + st, d->nblk);
-      prof_end(rec, s);
-      if (wrc) { mcg_set_error("wino_x3 block launch failed"); return MCG_ERR_HIP; }
-    }
+    if (defer) MCG_TRY(defer_stage_forward(e, s, *d, st, b_in, N, fh[0], fw[0]));
     MCG_TRY(launch_roi_align(s, e->dt, pyramid, fh, fw, strides, 256, b_in, N * 3, 3, frame_of, pyramid_frames, c.roi, nullptr));
     float* bdst = (st == e->num_stages - 1) ? boxes_out : b_out;
     MCG_TRY(stage_forward_ctx(s, e->dt, &e->stage_w[(size_t)st * MCG_SW_COUNT], c.roi, obj_in, b_in, N, clip_length, obj_out, bdst,
