@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define MCG_ABI_VERSION 15
+#define MCG_ABI_VERSION 16
 
 enum { MCG_OK = 0, MCG_ERR_ARG = 1, MCG_ERR_HIP = 2, MCG_ERR_UNSUPPORTED = 3, MCG_ERR_WORKSPACE = 4 };
 /* MCG_F16X3: the parity-grade fast mode.  Activations, biases and every non-GEMM kernel are exactly those of MCG_F32 (4-byte
@@ -216,6 +216,27 @@ int mcg_stage_forward(mcg_stream s, mcg_dtype dt, const void* const weights[MCG_
                       const void* obj_in, const float* boxes_in, int num_frames, int clip_length,
                       void* obj_out, float* boxes_out, float* cls_out, const float bbox_stds[4],
                       void* ws, size_t ws_bytes, int flags);
+/* ABI 16: clips of DIFFERENT lengths in one call (the mcg_*_ragged entry points).  The reference fixes one clip length per call
+ * (multiclue_gaze.py:77-78, :119: num_clips = frames / clip_length), but only ONE step of the path looks at where clips begin and end: the
+ * temporal attention pass of a stage (gaze_stqi_head.py:156-166, which regroups the tokens as [clip x clue][frames of the clip]); everything
+ * else is per frame or per token.  So a ragged call takes, in place of clip_length,
+ *   clip_start       DEVICE int32 [num_clips + 1]: frame indices, clip_start[0] = 0, strictly increasing, clip_start[num_clips] =
+ *                    num_frames; clip b holds frames [clip_start[b], clip_start[b + 1])
+ *   num_clips        HOST integer
+ *   max_clip_length  HOST integer: the length of the longest clip (exactly: it selects the attention path and bounds what a kernel reads)
+ * The two integers are host values so that the call reads nothing back: no sync, graph-capturable like every other call.  Every clip's
+ * results are bit for bit those of a call that holds this clip alone; they depend neither on its place in the batch nor on its
+ * neighbours' lengths (MCG_F16: as long as the SAME attention path runs -- the fused block when max_clip_length <= 10, else the launch
+ * sequence; the two differ by one fp16 ulp there, tests/test_gpu_kernels.py::test_mlp_chain_matches_unfused_bitwise -- so a short clip
+ * batched with one longer than 10 frames may differ in the last bit from the same clip run alone.  MCG_F32 / MCG_F16X3 / MCG_BF16: the two
+ * paths give the same bits).  The existing entry points are the clip_start = NULL case of the same code.
+ * The table is not read on the host.  Guard (like frame_of's): an entry outside [0, num_frames], a span that is not increasing or one
+ * longer than max_clip_length is clamped -- no kernel reads or writes outside rows [0, 3 num_frames) -- and that clip's attention output
+ * is NaN: for callers' bugs, not a feature; mcgaze_amd/engine.py::check_clip_lengths builds a valid table from a list of lengths. */
+int mcg_stage_forward_ragged(mcg_stream s, mcg_dtype dt, const void* const weights[MCG_SW_COUNT], const void* roi_feat,
+                             const void* obj_in, const float* boxes_in, int num_frames, const int* clip_start, int num_clips,
+                             int max_clip_length, void* obj_out, float* boxes_out, float* cls_out, const float bbox_stds[4],
+                             void* ws, size_t ws_bytes, int flags);
 
 /* GazeHead.forward (mask_heads/gaze_head.py:138-202): obj [N][3][256] dtype -> gaze [4][N][3] f32
  * unit vectors in the order fused, face, eyes, head. */
@@ -311,7 +332,7 @@ void mcg_engine_destroy(mcg_engine* e);
  *   tile              forces a contraction tile id (0 = heuristic), see mcg_conv_desc.tile
  *   staged_gemm, conv3x3_c64, stem_fused, decoder_chain   0/1 kernel-variant switches (defaults 0, 1, 1, 1)
  *   decoder_attn_block 0/1 f16x3: both attention passes of a decoder stage (in_proj, attention core, out_proj + residual + LayerNorm, twice) as ONE
- *                     launch per stage, one clip per workgroup (attn_block_x3.hpp; clips of at most 10 frames); bit-identical to the six launches (default 1)
+ *                     launch per stage, one clip per workgroup (attn_block_x3.hpp; calls whose longest clip has at most 10 frames); bit-identical to the six launches (default 1)
  *   pointwise_pair    0/1 conv3 (+ residual) of a block and conv1 of the next as one kernel in layer1 (bf16; default 1)
  *   pointwise_stream  0/1 HBM-bound 1x1 convs (layer2, layer3 conv3, P2 / P3 laterals) by the persistent register-resident-weight
  *                     kernel pw_single.hpp (bf16; default 1)
@@ -368,6 +389,12 @@ int mcg_decoder_forward(mcg_engine* e, mcg_stream s, const void* const pyramid[4
 int mcg_decoder_forward_indexed(mcg_engine* e, mcg_stream s, const void* const pyramid[4], int pyramid_frames, const int32_t* frame_of,
                                 int num_frames, int clip_length, int H, int W, const int* img_hw, float* gaze_out, float* boxes_out,
                                 float* scores_out, void* ws, size_t ws_bytes);
+/* ABI 16: the decoder over clips of different lengths (see mcg_stage_forward_ragged for clip_start / num_clips / max_clip_length and the
+ * guard; generalises multiclue_gaze.py:77-78,119 and gaze_stqi_head.py:156-166).  frame_of may be NULL: then pyramid_frames = num_frames
+ * and frame n reads row n (mcg_decoder_forward's case); else it is mcg_decoder_forward_indexed's table. */
+int mcg_decoder_forward_ragged(mcg_engine* e, mcg_stream s, const void* const pyramid[4], int pyramid_frames, const int32_t* frame_of,
+                               int num_frames, const int* clip_start, int num_clips, int max_clip_length, int H, int W, const int* img_hw,
+                               float* gaze_out, float* boxes_out, float* scores_out, void* ws, size_t ws_bytes);
 /* ABI 15: the same pair over a DEFERRED pyramid.  slot: caller-owned device memory of mcg_deferred_pyramid_bytes(e, N, H, W) bytes that
  * carries one batch from the trunk to the decoder (double-buffer it to overlap batches, mcgaze_amd/engine.py: PipelinedRunner): P2..P5,
  * and, when the engine defers P2 (option fpn_deferred), the P2 top-down inner map, a flag per 8 x 8 output block of P2 and one block list
@@ -381,11 +408,22 @@ int mcg_backbone_fpn_forward_deferred(mcg_engine* e, mcg_stream s, const float* 
                                       void* slot, size_t slot_bytes, void* ws, size_t ws_bytes);
 int mcg_decoder_forward_deferred(mcg_engine* e, mcg_stream s, void* slot, size_t slot_bytes, int num_frames, int clip_length, int H, int W,
                                  const int* img_hw, float* gaze_out, float* boxes_out, float* scores_out, void* ws, size_t ws_bytes);
+/* ABI 16: mcg_decoder_forward_deferred over clips of different lengths (mcg_stage_forward_ragged: the table, its contract and the guard;
+ * multiclue_gaze.py:77-78,119, gaze_stqi_head.py:156-166). */
+int mcg_decoder_forward_deferred_ragged(mcg_engine* e, mcg_stream s, void* slot, size_t slot_bytes, int num_frames, const int* clip_start,
+                                        int num_clips, int max_clip_length, int H, int W, const int* img_hw, float* gaze_out,
+                                        float* boxes_out, float* scores_out, void* ws, size_t ws_bytes);
 /* Whole path = mcg_backbone_fpn_forward_deferred + mcg_decoder_forward_deferred on one stream (the slot inside ws);
  * ws >= mcg_engine_workspace_bytes. */
 int mcg_clip_forward(mcg_engine* e, mcg_stream s, const float* img, int num_frames, int clip_length, int H, int W,
                      const int* img_hw, int chunk_frames, float* gaze_out, float* boxes_out, float* scores_out,
                      void* ws, size_t ws_bytes);
+/* ABI 16: the whole path over clips of different lengths -- e.g. one clip per person per segment, each as long as the person stays in
+ * view (MCGaze_demo/demo.ipynb, cell 4), in ONE call instead of one per clip (multiclue_gaze.py:77-78,119 take one clip_length;
+ * gaze_stqi_head.py:156-166 is the only step that groups by clip).  mcg_stage_forward_ragged states the table's contract and the guard. */
+int mcg_clip_forward_ragged(mcg_engine* e, mcg_stream s, const float* img, int num_frames, const int* clip_start, int num_clips,
+                            int max_clip_length, int H, int W, const int* img_hw, int chunk_frames, float* gaze_out, float* boxes_out,
+                            float* scores_out, void* ws, size_t ws_bytes);
 
 /* ---------------------------------------------------------------- test-time preprocessing
  * One launch replaces the per-frame CPU transforms the reference's test pipeline applies between image decode and the model

@@ -81,17 +81,35 @@ __device__ __forceinline__ void attend_row_head(const T* __restrict__ qp, KeyF k
   attend_row_head<T>(qp, key, val, L, scale, out, [](const T* base, int c) { return *(const uint4*)(base + c * Elem<T>::kPerChunk); });
 }
 
+// Clips of different lengths in one batch (gaze_stqi_head.py:156-166 groups the temporal pass by clip; multiclue_gaze.py:77-78,119 fix
+// ONE clip length per call): a device table clip_start[num_clips + 1] of frame indices, clip_start[0] = 0, strictly increasing,
+// clip_start[num_clips] = num_frames; clip b holds frames [clip_start[b], clip_start[b + 1]).  Workgroup-uniform: one scalar load pair.
+// Guard (like frame_of's, roi_align.hip): an entry that is out of range, not increasing, or a clip longer than max_len is CLAMPED so that
+// the span lies inside [0, num_frames) and holds 1 .. max_len frames, and bad tells the kernel to write NaN for that clip.
+struct ClipSpan { int first, len; bool bad; };
+__device__ __forceinline__ ClipSpan clip_span(const int32_t* __restrict__ clip_start, int b, int num_frames, int max_len) {
+  int a = clip_start[b], e = clip_start[b + 1];
+  const bool bad = a < 0 || e > num_frames || e <= a || e - a > max_len;
+  if (bad) {
+    a = min(max(a, 0), num_frames - 1);
+    e = min(max(e, a + 1), min(a + max_len, num_frames));
+  }
+  return ClipSpan{a, e - a, bad};
+}
+
 struct AttnBlockParams {
-  const void* x;        // [num_clips * 3T][256] bf16 token rows (attn_block_x3_kernel: f32)
-  void* y;              // [num_clips * 3T][256] bf16: rows after both passes (attn_block_x3_kernel: f32)
+  const void* x;        // [num_frames * 3][256] bf16 token rows (attn_block_x3_kernel: f32)
+  void* y;              // [num_frames * 3][256] bf16: rows after both passes (attn_block_x3_kernel: f32)
   const void* w_in;     // in_proj weight [768][256], MFMA-fragment-major (24 column tiles; attn_block_x3_kernel: the SPLIT fragment-major form)
   const float* b_in;    // [768]
   const void* w_out;    // out_proj weight [256][256], fragment-major
   const float* b_out;   // [256]
   const float* g;       // attention_norm gamma / beta [256]
   const float* b;
-  int num_clips, T;
+  int num_clips, T;     // T: frames per clip (clip_start == NULL), else the longest clip's (3 T <= 32 either way)
   float scale;          // 1 / sqrt(head_dim)
+  const int32_t* clip_start;   // NULL: num_clips clips of T frames; else the clip table above
+  int num_frames;              // read with clip_start only
 };
 
 template <typename T>   // bf16_t or f16_t
@@ -104,8 +122,14 @@ __global__ __launch_bounds__(256, 1) void attn_block_kernel(const AttnBlockParam
   T* s_qkv = (T*)s_big;
   float* s_t = (float*)s_big;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int rows = 3 * p.T;                                   // <= 32 (checked by the launcher)
-  const size_t m0 = (size_t)blockIdx.x * rows;
+  int T_b = p.T;
+  size_t m0 = (size_t)blockIdx.x * (3 * p.T);
+  bool bad = false;
+  if (p.clip_start) {                                         // ragged batch: this clip's span from the table
+    const ClipSpan cs = clip_span(p.clip_start, blockIdx.x, p.num_frames, p.T);
+    T_b = cs.len; m0 = (size_t)cs.first * 3; bad = cs.bad;
+  }
+  const int rows = 3 * T_b;                                   // <= 32 (checked by the launcher; clip_span clamps)
   auto swz = [](int row, int chunk) { return row * ROWB + ((chunk ^ (row & 31)) << 4); };
   for (int idx = tid; idx < ROWS * 32; idx += 256) {          // token rows -> LDS (padding rows are zero; never stored)
     const int r = idx >> 5, c = idx & 31;
@@ -158,7 +182,7 @@ __global__ __launch_bounds__(256, 1) void attn_block_kernel(const AttnBlockParam
     __syncthreads();
     // ---- attention core: thread = (query row, head) (attend_row_head); rows * 8 <= 256 pairs
     {
-      const int L = pass == 0 ? 3 : p.T;
+      const int L = pass == 0 ? 3 : T_b;
       const int i = tid >> 3, h = tid & 7;
       if (i < rows) {
         const int kbase = pass == 0 ? (i / 3) * 3 : i % 3, kstep = pass == 0 ? 1 : 3;
@@ -216,6 +240,7 @@ __global__ __launch_bounds__(256, 1) void attn_block_kernel(const AttnBlockParam
       uint2 o = make_uint2(H16<T>::pack2(v[0], v[1]), H16<T>::pack2(v[2], v[3]));
       if (r >= rows) o = make_uint2(0, 0);   // padding rows stay zero
       *(uint2*)(xout + swz(r, c0 >> 3) + (c0 & 7) * 2) = o;
+      if (bad) o = make_uint2(0xffffffffu, 0xffffffffu);   // a clip the table guard clamped: NaN (bf16 and fp16 alike)
       if (pass == 1 && r < rows) *(uint2*)((char*)p.y + (m0 + r) * ROWB + c0 * 2) = o;
     }
     __syncthreads();
@@ -223,7 +248,7 @@ __global__ __launch_bounds__(256, 1) void attn_block_kernel(const AttnBlockParam
   }
 }
 
-static inline bool attn_block_applicable(int T) { return T >= 1 && 3 * T <= 32; }
+static inline bool attn_block_applicable(int T) { return T >= 1 && 3 * T <= 32; }   // T: the longest clip of the call
 static inline int launch_attn_block(hipStream_t s, const AttnBlockParams& p, bool fp16 = false) {
   if (fp16) hipLaunchKernelGGL(attn_block_kernel<f16_t>, dim3(p.num_clips), dim3(256), 0, s, p);
   else hipLaunchKernelGGL(attn_block_kernel<bf16_t>, dim3(p.num_clips), dim3(256), 0, s, p);

@@ -44,8 +44,14 @@ __global__ __launch_bounds__(256, 1) void attn_block_x3_kernel(const AttnBlockPa
   float* const s_qkv = (float*)(smem + ROWS * ROWB);
   float* const s_t = s_qkv;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int rows = 3 * p.T;                                   // <= 32 (checked by the launcher)
-  const size_t m0 = (size_t)blockIdx.x * rows;
+  int T_b = p.T;
+  size_t m0 = (size_t)blockIdx.x * (3 * p.T);
+  bool bad = false;
+  if (p.clip_start) {                                         // ragged batch: this clip's span from the table (attn_block.hpp: clip_span)
+    const ClipSpan cs = clip_span(p.clip_start, blockIdx.x, p.num_frames, p.T);
+    T_b = cs.len; m0 = (size_t)cs.first * 3; bad = cs.bad;
+  }
+  const int rows = 3 * T_b;                                   // <= 32 (checked by the launcher; clip_span clamps)
   const float* const X = (const float*)p.x;
   for (int idx = tid; idx < ROWS * 64; idx += 256) {          // token rows -> LDS, split (padding rows are zero; never stored)
     const int r = idx >> 6, c = (idx & 63) * 4;
@@ -115,7 +121,7 @@ __global__ __launch_bounds__(256, 1) void attn_block_x3_kernel(const AttnBlockPa
     __syncthreads();   // qkv complete; every wave is done reading the input rows in s_x
     // ---- attention core: thread = (query row, head) (attend_row_head); rows * 8 <= 256 pairs; its output, split, becomes the next A operand
     {
-      const int L = pass == 0 ? 3 : p.T;
+      const int L = pass == 0 ? 3 : T_b;
       const int i = tid >> 3, h = tid & 7;
       __attribute__((aligned(16))) float o[32];
       if (i < rows) {
@@ -180,6 +186,11 @@ __global__ __launch_bounds__(256, 1) void attn_block_x3_kernel(const AttnBlockPa
       if (pass == 1 && r < rows) *(float4*)((float*)p.y + (m0 + r) * D + c0) = make_float4(v[0], v[1], v[2], v[3]);
     }
     __syncthreads();
+  }
+  if (bad) {   // a clip the table guard clamped: its rows become NaN.  A pass of its own behind the last barrier -- a select at the store above
+               // changes how the compiler contracts the LayerNorm's multiply-adds, and with it the bits of every VALID clip
+    const float nan = __builtin_nanf("");
+    for (int idx = threadIdx.x; idx < rows * 64; idx += 256) *(float4*)((float*)p.y + (m0 + (idx >> 6)) * D + (idx & 63) * 4) = make_float4(nan, nan, nan, nan);
   }
 }
 

@@ -19,16 +19,33 @@
 // The bf16 engine runs both attention passes of a stage in attn_block_kernel instead whenever a clip's 3 T rows fit one MFMA tile.
 //   spatial : group = frame,        tokens r = g*3 + i            (L = 3 clues)
 //   temporal: group = (clip, clue), tokens r = (b*T + i)*3 + c    (L = T frames)
+// Ragged batch (clip_start != NULL, temporal only): clip b spans frames [clip_start[b], clip_start[b + 1]) -- base and L come from the table
+// (attn_block.hpp: clip_span, one scalar load pair per workgroup; L is then the longest clip's length, the guard's cap).
 template <typename T>
-__global__ __launch_bounds__(256) void attn_core_kernel(const T* __restrict__ qkv, T* __restrict__ out, int L, int temporal, int clip_len, float scale) {
+__global__ __launch_bounds__(256) void attn_core_kernel(const T* __restrict__ qkv, T* __restrict__ out, int L, int temporal, int clip_len, float scale,
+                                                        const int32_t* __restrict__ clip_start, int num_frames) {
   const int g = blockIdx.x;
   long long base; int step;
-  if (temporal) { const int b = g / 3, c = g - b * 3; base = (long long)b * clip_len * 3 + c; step = 3; }
+  bool bad = false;
+  if (temporal) {
+    const int b = g / 3, c = g - b * 3;
+    step = 3;
+    if (clip_start) {
+      const ClipSpan cs = clip_span(clip_start, b, num_frames, L);
+      base = (long long)cs.first * 3 + c; L = cs.len; bad = cs.bad;
+    } else {
+      base = (long long)b * clip_len * 3 + c;
+    }
+  }
   else { base = (long long)g * 3; step = 1; }
   const int D = 256;
   for (int pair = threadIdx.x; pair < L * 8; pair += 256) {   // thread = (query token of the group, head)
     const int i = pair >> 3, h = pair & 7;
     const long long ri = base + (long long)i * step;
+    if (bad) {                                                // a clip the table guard clamped: NaN rows, nothing read
+      for (int d = 0; d < 32; ++d) Elem<T>::st(out + ri * D + h * 32 + d, __builtin_nanf(""));
+      continue;
+    }
     attend_row_head<T>(qkv + ri * (3 * D) + h * 32,
                        [&](int j) { return qkv + (base + (long long)j * step) * (3 * D) + D + h * 32; },
                        [&](int j) { return qkv + (base + (long long)j * step) * (3 * D) + 2 * D + h * 32; }, L, scale, out + ri * D + h * 32);
@@ -562,25 +579,50 @@ int launch_roi_align(hipStream_t s, mcg_dtype dt, const void* const feats[4], co
                      int pyramid_frames, void* out, int32_t* levels_out);
 
 template <typename T>
-static void launch_attn(hipStream_t s, const void* qkv, void* out, int groups, int L, int temporal, int clip_len) {
-  hipLaunchKernelGGL(attn_core_kernel<T>, dim3(groups), dim3(256), 0, s, (const T*)qkv, (T*)out, L, temporal, clip_len, 1.0f / sqrtf(32.f));
+static void launch_attn(hipStream_t s, const void* qkv, void* out, int groups, int L, int temporal, int clip_len, const int32_t* clip_start, int N) {
+  hipLaunchKernelGGL(attn_core_kernel<T>, dim3(groups), dim3(256), 0, s, (const T*)qkv, (T*)out, L, temporal, clip_len, 1.0f / sqrtf(32.f),
+                     temporal ? clip_start : nullptr, N);
+}
+
+// What the C-ABI accepts as a batch's split into clips (igemm.hpp: ClipTable).  The table itself lives on the device and is not read here
+// (no sync); the kernels clamp what it says (attn_block.hpp: clip_span).
+int check_clips(const char* what, int N, const ClipTable& ct) {
+  if (!ct.start) {
+    MCG_CHECK_ARG(N > 0 && ct.max_len > 0 && N % ct.max_len == 0, "%s: num_frames=%d is not a multiple of clip_length=%d", what, N, ct.max_len);
+    return MCG_OK;
+  }
+  MCG_CHECK_ARG(N > 0 && ct.num_clips > 0 && ct.max_len > 0, "%s: num_frames=%d, num_clips=%d, max_clip_length=%d must be positive", what, N,
+                ct.num_clips, ct.max_len);
+  // one clip holds max_clip_length frames, every other at least one and at most as many
+  MCG_CHECK_ARG((long long)ct.num_clips - 1 + ct.max_len <= N && (long long)ct.num_clips * ct.max_len >= N,
+                "%s: %d clips of at most %d frames (one of exactly that many) cannot hold num_frames=%d", what, ct.num_clips, ct.max_len, N);
+  return MCG_OK;
 }
 
 extern "C" int mcg_stage_forward(mcg_stream s, mcg_dtype dt, const void* const W[MCG_SW_COUNT], const void* roi_feat,
                                  const void* obj_in, const float* boxes_in, int N, int clip_length, void* obj_out,
                                  float* boxes_out, float* cls_out, const float stds[4], void* ws, size_t ws_bytes, int flags) {
-  return stage_forward_ctx((hipStream_t)s, dt, W, roi_feat, obj_in, boxes_in, N, clip_length, obj_out, boxes_out, cls_out, stds, ws, ws_bytes,
-                           McgCtx::from_flags(0, flags));
+  return stage_forward_ctx((hipStream_t)s, dt, W, roi_feat, obj_in, boxes_in, N, ClipTable::uniform(N, clip_length), obj_out, boxes_out, cls_out, stds, ws,
+                           ws_bytes, McgCtx::from_flags(0, flags));
+}
+extern "C" int mcg_stage_forward_ragged(mcg_stream s, mcg_dtype dt, const void* const W[MCG_SW_COUNT], const void* roi_feat,
+                                        const void* obj_in, const float* boxes_in, int N, const int* clip_start, int num_clips,
+                                        int max_clip_length, void* obj_out, float* boxes_out, float* cls_out, const float stds[4], void* ws,
+                                        size_t ws_bytes, int flags) {
+  MCG_CHECK_ARG(clip_start, "mcg_stage_forward_ragged: null clip_start (mcg_stage_forward is the equal-length path)");
+  return stage_forward_ctx((hipStream_t)s, dt, W, roi_feat, obj_in, boxes_in, N, ClipTable{clip_start, num_clips, max_clip_length}, obj_out, boxes_out,
+                           cls_out, stds, ws, ws_bytes, McgCtx::from_flags(0, flags));
 }
 int stage_forward_ctx(hipStream_t s, mcg_dtype dt, const void* const W[MCG_SW_COUNT], const void* roi_feat, const void* obj_in,
-                      const float* boxes_in, int N, int clip_length, void* obj_out, float* boxes_out, float* cls_out,
+                      const float* boxes_in, int N, const ClipTable& ct, void* obj_out, float* boxes_out, float* cls_out,
                       const float stds[4], void* ws, size_t ws_bytes, const McgCtx& ctx) {
   MCG_CHECK_ARG(W && roi_feat && obj_in && boxes_in && obj_out && boxes_out && cls_out && stds && ws, "mcg_stage_forward: null pointer");
-  MCG_CHECK_ARG(N > 0 && clip_length > 0 && N % clip_length == 0, "mcg_stage_forward: num_frames=%d is not a multiple of clip_length=%d", N, clip_length);
+  MCG_TRY(check_clips("mcg_stage_forward", N, ct));
+  const int clip_length = ct.max_len;   // the longest clip (every clip, without a table)
   for (int i = 0; i < MCG_SW_COUNT; ++i) MCG_CHECK_ARG(W[i], "mcg_stage_forward: weight table entry %d is null", i);
   StageWs w = stage_layout(dt, N, (char*)ws);
   if (ws_bytes < w.total) { mcg_set_error("mcg_stage_forward: workspace too small (%zu < %zu)", ws_bytes, w.total); return MCG_ERR_WORKSPACE; }
-  const int R = N * 3, B = N / clip_length;
+  const int R = N * 3, B = ct.num_clips;
   const float* f32w[MCG_SW_COUNT];
   for (int i = 0; i < MCG_SW_COUNT; ++i) f32w[i] = (const float*)W[i];
   const bool bf = mcg_is16(dt), h16 = dt == MCG_F16;   // bf: 2-byte storage (MCG_BF16 or MCG_F16: the same launch sequence); h16: fp16 instantiations
@@ -598,14 +640,14 @@ int stage_forward_ctx(hipStream_t s, mcg_dtype dt, const void* const W[MCG_SW_CO
     memset(&ap, 0, sizeof(ap));
     ap.x = obj_in; ap.y = w.x2; ap.w_in = W[MCG_SW_IN_PROJ_WF]; ap.b_in = f32w[MCG_SW_IN_PROJ_B];
     ap.w_out = W[MCG_SW_OUT_PROJ_WF]; ap.b_out = f32w[MCG_SW_OUT_PROJ_B]; ap.g = f32w[MCG_SW_ATTN_LN_G]; ap.b = f32w[MCG_SW_ATTN_LN_B];
-    ap.num_clips = B; ap.T = clip_length; ap.scale = 1.0f / sqrtf(32.f);
+    ap.num_clips = B; ap.T = clip_length; ap.scale = 1.0f / sqrtf(32.f); ap.clip_start = ct.start; ap.num_frames = N;
     if (chain_x3 ? launch_attn_block_x3(s, ap) : launch_attn_block(s, ap, h16)) { mcg_set_error("attn_block launch failed"); return MCG_ERR_HIP; }
   }
   for (int pass = 0; pass < 2 && !block_attn; ++pass) {
     MCG_TRY(launch_linear(s, dt, xin, 256, W[MCG_SW_IN_PROJ_W], f32w[MCG_SW_IN_PROJ_B], nullptr, 0, w.qkv, 768, R, 256, 768, 0, ctx));
-    if (h16) launch_attn<f16_t>(s, w.qkv, w.att, pass == 0 ? N : B * 3, pass == 0 ? 3 : clip_length, pass, clip_length);
-    else if (bf) launch_attn<bf16_t>(s, w.qkv, w.att, pass == 0 ? N : B * 3, pass == 0 ? 3 : clip_length, pass, clip_length);
-    else launch_attn<float>(s, w.qkv, w.att, pass == 0 ? N : B * 3, pass == 0 ? 3 : clip_length, pass, clip_length);
+    if (h16) launch_attn<f16_t>(s, w.qkv, w.att, pass == 0 ? N : B * 3, pass == 0 ? 3 : clip_length, pass, clip_length, ct.start, N);
+    else if (bf) launch_attn<bf16_t>(s, w.qkv, w.att, pass == 0 ? N : B * 3, pass == 0 ? 3 : clip_length, pass, clip_length, ct.start, N);
+    else launch_attn<float>(s, w.qkv, w.att, pass == 0 ? N : B * 3, pass == 0 ? 3 : clip_length, pass, clip_length, ct.start, N);
     MCG_CHECK_LAUNCH("attn_core");
     if (chain_attn || chain_x3) {  // out_proj + residual + LayerNorm as one launch
       ChainParams cp;

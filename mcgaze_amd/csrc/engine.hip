@@ -804,12 +804,13 @@ static int defer_stage_forward(const mcg_engine* e, hipStream_t s, const DeferSl
 // (RoIAlign and the query init gather through the table, roi_align.hip / decoder.hip), img_hw is then indexed by pyramid row.
 // d != NULL and deferred: pyramid[0] is computed here, block by block, from d->inner -- before each stage's RoIAlign, the blocks its boxes
 // read that no earlier stage listed (roi_mark_kernel, then wino_x3w_blocks_kernel: same bits as the dense conv).
+// ct: how the N frames split into clips (igemm.hpp: ClipTable) -- read by the stages' temporal attention pass only.
 static int decoder_forward(mcg_engine* e, hipStream_t s, const void* const pyramid[4], int pyramid_frames, const int32_t* frame_of, int N,
-                           int clip_length, int H, int W, const int* img_hw, float* gaze_out, float* boxes_out, float* scores_out, void* ws,
+                           const ClipTable& ct, int H, int W, const int* img_hw, float* gaze_out, float* boxes_out, float* scores_out, void* ws,
                            size_t ws_bytes, const DeferSlot* d = nullptr) {
   MCG_CHECK_ARG(e && pyramid && gaze_out && boxes_out && scores_out && ws, "mcg_decoder_forward: null pointer");
   MCG_TRY(check_shape(N, H, W));
-  MCG_CHECK_ARG(clip_length > 0 && N % clip_length == 0, "num_frames=%d is not a multiple of clip_length=%d", N, clip_length);
+  MCG_TRY(check_clips("mcg_decoder_forward", N, ct));
   DecWs c = dec_layout(e->dt, N, (char*)ws);
   if (ws_bytes < c.total) { mcg_set_error("mcg_decoder_forward: workspace too small (%zu < %zu)", ws_bytes, c.total); return MCG_ERR_WORKSPACE; }
   MCG_TRY(launch_init_queries(s, e->dt, e->init_boxes, e->init_feats, img_hw, frame_of, pyramid_frames, H, W, c.boxes_a, c.obj_a, N));
@@ -824,7 +825,7 @@ static int decoder_forward(mcg_engine* e, hipStream_t s, const void* const pyram
     if (defer) MCG_TRY(defer_stage_forward(e, s, *d, st, b_in, N, fh[0], fw[0]));
     MCG_TRY(launch_roi_align(s, e->dt, pyramid, fh, fw, strides, 256, b_in, N * 3, 3, frame_of, pyramid_frames, c.roi, nullptr));
     float* bdst = (st == e->num_stages - 1) ? boxes_out : b_out;
-    MCG_TRY(stage_forward_ctx(s, e->dt, &e->stage_w[(size_t)st * MCG_SW_COUNT], c.roi, obj_in, b_in, N, clip_length, obj_out, bdst,
+    MCG_TRY(stage_forward_ctx(s, e->dt, &e->stage_w[(size_t)st * MCG_SW_COUNT], c.roi, obj_in, b_in, N, ct, obj_out, bdst,
                               c.cls, e->stds, c.stage_ws, c.stage_bytes, e->ctx));
     char* t = obj_in; obj_in = obj_out; obj_out = t;
     if (st != e->num_stages - 1) { float* tb = b_in; b_in = b_out; b_out = tb; }
@@ -835,7 +836,8 @@ static int decoder_forward(mcg_engine* e, hipStream_t s, const void* const pyram
 
 extern "C" int mcg_decoder_forward(mcg_engine* e, mcg_stream s_, const void* const pyramid[4], int N, int clip_length, int H, int W,
                                    const int* img_hw, float* gaze_out, float* boxes_out, float* scores_out, void* ws, size_t ws_bytes) {
-  return decoder_forward(e, (hipStream_t)s_, pyramid, N, nullptr, N, clip_length, H, W, img_hw, gaze_out, boxes_out, scores_out, ws, ws_bytes);
+  return decoder_forward(e, (hipStream_t)s_, pyramid, N, nullptr, N, ClipTable::uniform(N, clip_length), H, W, img_hw, gaze_out, boxes_out, scores_out, ws,
+                         ws_bytes);
 }
 
 extern "C" int mcg_decoder_forward_indexed(mcg_engine* e, mcg_stream s_, const void* const pyramid[4], int pyramid_frames, const int32_t* frame_of,
@@ -843,8 +845,19 @@ extern "C" int mcg_decoder_forward_indexed(mcg_engine* e, mcg_stream s_, const v
                                            float* scores_out, void* ws, size_t ws_bytes) {
   MCG_CHECK_ARG(frame_of, "mcg_decoder_forward_indexed: null frame_of (mcg_decoder_forward is the plain path)");
   MCG_CHECK_ARG(pyramid_frames > 0, "mcg_decoder_forward_indexed: empty pyramid store (pyramid_frames=%d)", pyramid_frames);
-  return decoder_forward(e, (hipStream_t)s_, pyramid, pyramid_frames, frame_of, N, clip_length, H, W, img_hw, gaze_out, boxes_out, scores_out,
-                         ws, ws_bytes);
+  return decoder_forward(e, (hipStream_t)s_, pyramid, pyramid_frames, frame_of, N, ClipTable::uniform(N, clip_length), H, W, img_hw, gaze_out, boxes_out,
+                         scores_out, ws, ws_bytes);
+}
+
+extern "C" int mcg_decoder_forward_ragged(mcg_engine* e, mcg_stream s_, const void* const pyramid[4], int pyramid_frames, const int32_t* frame_of,
+                                          int N, const int* clip_start, int num_clips, int max_clip_length, int H, int W, const int* img_hw,
+                                          float* gaze_out, float* boxes_out, float* scores_out, void* ws, size_t ws_bytes) {
+  MCG_CHECK_ARG(clip_start, "mcg_decoder_forward_ragged: null clip_start (mcg_decoder_forward is the equal-length path)");
+  MCG_CHECK_ARG(pyramid_frames > 0, "mcg_decoder_forward_ragged: empty pyramid store (pyramid_frames=%d)", pyramid_frames);
+  MCG_CHECK_ARG(frame_of || pyramid_frames == N, "mcg_decoder_forward_ragged: without frame_of the pyramid holds one row per frame (%d rows, %d frames)",
+                pyramid_frames, N);
+  return decoder_forward(e, (hipStream_t)s_, pyramid, pyramid_frames, frame_of, N, ClipTable{clip_start, num_clips, max_clip_length}, H, W, img_hw,
+                         gaze_out, boxes_out, scores_out, ws, ws_bytes);
 }
 
 extern "C" int mcg_deferred_pyramid_levels(const mcg_engine* e, void* slot, int N, int H, int W, void* levels[4], int* deferred) {
@@ -865,21 +878,33 @@ extern "C" int mcg_backbone_fpn_forward_deferred(mcg_engine* e, mcg_stream s, co
   return trunk_forward(e, s, img, N, H, W, chunk, d.p, ws, ws_bytes, false, d.deferred ? d.inner : nullptr);
 }
 
-extern "C" int mcg_decoder_forward_deferred(mcg_engine* e, mcg_stream s, void* slot, size_t slot_bytes, int N, int clip_length, int H, int W,
-                                            const int* img_hw, float* gaze_out, float* boxes_out, float* scores_out, void* ws, size_t ws_bytes) {
+static int decoder_forward_deferred(mcg_engine* e, mcg_stream s, void* slot, size_t slot_bytes, int N, const ClipTable& ct, int H, int W,
+                                    const int* img_hw, float* gaze_out, float* boxes_out, float* scores_out, void* ws, size_t ws_bytes) {
   MCG_CHECK_ARG(e && slot, "mcg_decoder_forward_deferred: null pointer");
   MCG_TRY(check_shape(N, H, W));
   const DeferSlot d = defer_layout(e, N, H, W, (char*)slot);
   if (slot_bytes < d.total) { mcg_set_error("mcg_decoder_forward_deferred: slot too small (%zu < %zu)", slot_bytes, d.total); return MCG_ERR_WORKSPACE; }
-  return decoder_forward(e, (hipStream_t)s, d.p, N, nullptr, N, clip_length, H, W, img_hw, gaze_out, boxes_out, scores_out, ws, ws_bytes, &d);
+  return decoder_forward(e, (hipStream_t)s, d.p, N, nullptr, N, ct, H, W, img_hw, gaze_out, boxes_out, scores_out, ws, ws_bytes, &d);
 }
 
-extern "C" int mcg_clip_forward(mcg_engine* e, mcg_stream s_, const float* img, int N, int clip_length, int H, int W,
-                                const int* img_hw, int chunk, float* gaze_out, float* boxes_out, float* scores_out,
-                                void* ws, size_t ws_bytes) {
+extern "C" int mcg_decoder_forward_deferred(mcg_engine* e, mcg_stream s, void* slot, size_t slot_bytes, int N, int clip_length, int H, int W,
+                                            const int* img_hw, float* gaze_out, float* boxes_out, float* scores_out, void* ws, size_t ws_bytes) {
+  return decoder_forward_deferred(e, s, slot, slot_bytes, N, ClipTable::uniform(N, clip_length), H, W, img_hw, gaze_out, boxes_out, scores_out, ws, ws_bytes);
+}
+
+extern "C" int mcg_decoder_forward_deferred_ragged(mcg_engine* e, mcg_stream s, void* slot, size_t slot_bytes, int N, const int* clip_start,
+                                                   int num_clips, int max_clip_length, int H, int W, const int* img_hw, float* gaze_out,
+                                                   float* boxes_out, float* scores_out, void* ws, size_t ws_bytes) {
+  MCG_CHECK_ARG(clip_start, "mcg_decoder_forward_deferred_ragged: null clip_start (mcg_decoder_forward_deferred is the equal-length path)");
+  return decoder_forward_deferred(e, s, slot, slot_bytes, N, ClipTable{clip_start, num_clips, max_clip_length}, H, W, img_hw, gaze_out, boxes_out,
+                                  scores_out, ws, ws_bytes);
+}
+
+static int clip_forward(mcg_engine* e, mcg_stream s_, const float* img, int N, const ClipTable& ct, int H, int W, const int* img_hw, int chunk,
+                        float* gaze_out, float* boxes_out, float* scores_out, void* ws, size_t ws_bytes) {
   MCG_CHECK_ARG(e && img && gaze_out && boxes_out && scores_out && ws, "mcg_clip_forward: null pointer");
   MCG_TRY(check_shape(N, H, W));
-  MCG_CHECK_ARG(clip_length > 0 && N % clip_length == 0, "mcg_clip_forward: num_frames=%d is not a multiple of clip_length=%d", N, clip_length);
+  MCG_TRY(check_clips("mcg_clip_forward", N, ct));
   const size_t need = mcg_engine_workspace_bytes(e, N, H, W, chunk);
   if (ws_bytes < need) { mcg_set_error("mcg_clip_forward: workspace too small (%zu < %zu)", ws_bytes, need); return MCG_ERR_WORKSPACE; }
   char* base = (char*)ws;
@@ -887,6 +912,20 @@ extern "C" int mcg_clip_forward(mcg_engine* e, mcg_stream s_, const float* img, 
   const size_t slot_bytes = defer_layout(e, N, H, W, nullptr).total;
   const size_t off = trunk_bytes + slot_bytes;
   MCG_TRY(mcg_backbone_fpn_forward_deferred(e, s_, img, N, H, W, chunk, base + trunk_bytes, slot_bytes, base, trunk_bytes));
-  return mcg_decoder_forward_deferred(e, s_, base + trunk_bytes, slot_bytes, N, clip_length, H, W, img_hw, gaze_out, boxes_out, scores_out,
-                                      base + off, ws_bytes - off);
+  return decoder_forward_deferred(e, s_, base + trunk_bytes, slot_bytes, N, ct, H, W, img_hw, gaze_out, boxes_out, scores_out, base + off,
+                                  ws_bytes - off);
+}
+
+extern "C" int mcg_clip_forward(mcg_engine* e, mcg_stream s_, const float* img, int N, int clip_length, int H, int W,
+                                const int* img_hw, int chunk, float* gaze_out, float* boxes_out, float* scores_out,
+                                void* ws, size_t ws_bytes) {
+  return clip_forward(e, s_, img, N, ClipTable::uniform(N, clip_length), H, W, img_hw, chunk, gaze_out, boxes_out, scores_out, ws, ws_bytes);
+}
+
+extern "C" int mcg_clip_forward_ragged(mcg_engine* e, mcg_stream s_, const float* img, int N, const int* clip_start, int num_clips,
+                                       int max_clip_length, int H, int W, const int* img_hw, int chunk, float* gaze_out, float* boxes_out,
+                                       float* scores_out, void* ws, size_t ws_bytes) {
+  MCG_CHECK_ARG(clip_start, "mcg_clip_forward_ragged: null clip_start (mcg_clip_forward is the equal-length path)");
+  return clip_forward(e, s_, img, N, ClipTable{clip_start, num_clips, max_clip_length}, H, W, img_hw, chunk, gaze_out, boxes_out, scores_out, ws,
+                      ws_bytes);
 }

@@ -303,8 +303,15 @@ int launch_linear_splitk(hipStream_t s, mcg_dtype dt, const void* x, long long l
 int conv2d_ctx(hipStream_t s, mcg_dtype dt, const mcg_conv_desc* d, const McgCtx& ctx);
 int stem_forward_ctx(hipStream_t s, mcg_dtype dt, const float* img, const void* w_stem, const float* bias, void* y, int N, int H, int W,
                      void* ws, size_t ws_bytes, const McgCtx& ctx);
+// How the N frames of a batch split into clips (the only thing the temporal attention pass needs to know).  start == NULL: num_clips
+// clips of max_len frames each; else the device table of mcg_*_ragged (include/mcgaze_hip.h) with max_len = the longest clip's length.
+struct ClipTable {
+  const int32_t* start; int num_clips, max_len;
+  static ClipTable uniform(int N, int clip_length) { return ClipTable{nullptr, clip_length > 0 ? N / clip_length : 0, clip_length}; }
+};
+int check_clips(const char* what, int N, const ClipTable& ct);   // decoder.hip
 int stage_forward_ctx(hipStream_t s, mcg_dtype dt, const void* const W[MCG_SW_COUNT], const void* roi_feat, const void* obj_in,
-                      const float* boxes_in, int N, int clip_length, void* obj_out, float* boxes_out, float* cls_out,
+                      const float* boxes_in, int N, const ClipTable& ct, void* obj_out, float* boxes_out, float* cls_out,
                       const float stds[4], void* ws, size_t ws_bytes, const McgCtx& ctx);
 // cls_logits / scores_out (optional, [N][3]): the last stage's logits -> sigmoid scores, written by the gaze tail kernel
 int gaze_head_ctx(hipStream_t s, mcg_dtype dt, const void* const W[MCG_GW_COUNT], const void* obj, int N, float* gaze_out,

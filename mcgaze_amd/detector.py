@@ -316,6 +316,7 @@ class MultiClueGaze(nn.Module):
     Extension (the reference never batches clips at inference): pass
     ``clip_length=T`` to treat the N frames as N/T independent clips (the semantics of the
     reference's ``forward_train``); without it the N frames form ONE clip, as in the reference.
+    ``clip_length=[7, 3, 12]`` (a sequence of lengths summing to N): clips of different lengths in one call (HipEngine.forward).
     ``precision`` is an attribute of the model: 'f16x3' (DEFAULT: f32 activations, split-fp16 x 3 MFMA contraction -- meets the
     reference's fp32 results to < 1e-4 rad on (yaw, pitch), i.e. the engine to evaluate a checkpoint with), 'fp32' (f32 MFMA,
     the exact reference mode) or 'f16' / 'bf16' (16-bit throughput modes in fp16 / bf16; an explicit opt-in, its deviation from the fp32 reference is not
@@ -390,7 +391,7 @@ class MultiClueGaze(nn.Module):
         """mmdet/models/detectors/multiclue_gaze.py:105-131 + multiclue_gaze_roi_head.py:287-384."""
         N = img.size(0)
         assert len(img_metas) == N, f'{N} frames but {len(img_metas)} img_metas'
-        T = N if clip_length is None else int(clip_length)
+        T = N if clip_length is None else (int(clip_length) if np.isscalar(clip_length) else clip_length)   # a sequence: per-clip lengths
         eng = self.engine()
         x = img.to(device=eng.device, dtype=torch.float32).contiguous()
         hw = np.array([m['img_shape'][:2] for m in img_metas], dtype=np.int32)

@@ -194,13 +194,64 @@ def check_frame_table(frame_of, pyramid_frames, clip_length):
     return a.astype(np.int32)
 
 
+def check_clip_lengths(lengths, num_frames):
+    """Host-side check of a ragged batch's clip lengths: a non-empty flat sequence of positive integers summing to num_frames
+    (None: any sum).
+    -> int32 numpy array clip_start [len(lengths) + 1] (0, cumulative sums: the table the mcg_*_ragged entry points take).
+    McgError otherwise (nothing reaches the device)."""
+    t = lengths.numpy() if isinstance(lengths, torch.Tensor) else lengths
+    try:
+        a = np.asarray(t)
+    except Exception as ex:
+        raise L.McgError(f'clip lengths must be a flat sequence of integers ({ex})')
+    if a.ndim != 1 or a.size == 0 or not np.issubdtype(a.dtype, np.integer):
+        raise L.McgError(f'clip lengths must be a non-empty flat sequence of integers (got {a.dtype} of shape {a.shape})')
+    if int(a.min()) < 1:
+        raise L.McgError(f'every clip must hold at least one frame (got a length of {int(a.min())})')
+    total = int(a.astype(np.int64).sum())
+    if num_frames is not None and total != int(num_frames):
+        raise L.McgError(f'clip lengths sum to {total} frames, the batch holds {int(num_frames)}')
+    start = np.zeros(a.size + 1, dtype=np.int32)
+    np.cumsum(a, out=start[1:])
+    return start
+
+
+class ClipTable:
+    """The clip lengths of a ragged batch, checked and uploaded ONCE: what forward / decode / stage_forward build per call from a sequence
+    of lengths, for a caller who repeats a batch layout -- and the form to use under HIP-graph capture, where a per-call upload from a
+    temporary host buffer must not be recorded (GraphedForward builds one).  The upload is complete when the constructor returns."""
+
+    def __init__(self, lengths, device='cuda:0'):
+        self.start = check_clip_lengths(lengths, None)
+        self.num_frames, self.num_clips, self.max_len = int(self.start[-1]), self.start.size - 1, int(np.diff(self.start).max())
+        self.device = torch.device(device)
+        self.table = torch.from_numpy(self.start).to(self.device)
+
+
+def _clips(clip_length, num_frames, device):
+    """clip_length of forward / decode / stage_forward -> None for an int (one length for every clip: the mcg_* entry point), else
+    (device int32 clip_start, num_clips, max_clip_length): the three arguments of the mcg_*_ragged one.  A sequence of lengths is checked
+    (McgError before anything reaches the device) and uploaded pinned + non-blocking on the current stream: a pageable upload would make
+    the host wait for the work already queued (harness.py, upload)."""
+    if isinstance(clip_length, (int, np.integer)):
+        return None
+    if isinstance(clip_length, ClipTable):
+        ct = clip_length
+        if ct.num_frames != num_frames or ct.device != torch.device(device):
+            raise L.McgError(f'the ClipTable holds {ct.num_frames} frames on {ct.device}, the batch {num_frames} on {device}')
+        return ct.table, ct.num_clips, ct.max_len
+    start = check_clip_lengths(clip_length, num_frames)
+    return torch.from_numpy(start).pin_memory().to(device, non_blocking=True), start.size - 1, int(np.diff(start).max())
+
+
 def _table(d, keys):
     return (C.c_void_p * len(keys))(*[d[k].data_ptr() for k in keys])
 
 
 def stage_forward(stage_w, roi_feat, obj, boxes, clip_length, stds=(0.5, 0.5, 1.0, 1.0), split=False, flags=0):
     """One decoder stage.  roi_feat [R,49,256], obj [N,3,256], boxes [N,3,4] f32
-    -> (obj' [N,3,256], boxes' [N,3,4], cls logits [N,3]).  mcg_stage_forward."""
+    -> (obj' [N,3,256], boxes' [N,3,4], cls logits [N,3]).  mcg_stage_forward; clip_length: an int, or a sequence of per-clip lengths
+    summing to N (mcg_stage_forward_ragged)."""
     _require_gpu()
     lib = L.load()
     N = obj.shape[0]
@@ -210,6 +261,13 @@ def stage_forward(stage_w, roi_feat, obj, boxes, clip_length, stds=(0.5, 0.5, 1.
     boxes_out = torch.empty(N, 3, 4, dtype=torch.float32, device=obj.device)
     cls = torch.empty(N, 3, dtype=torch.float32, device=obj.device)
     sd = (C.c_float * 4)(*stds)
+    clips = _clips(clip_length, N, obj.device)
+    if clips is not None:
+        table, B, Tmax = clips
+        L.check(lib.mcg_stage_forward_ragged(_stream(), dt, _table(stage_w, L.STAGE_KEYS), _ptr(roi_feat.contiguous()), _ptr(obj.contiguous()),
+                                             _ptr(boxes.contiguous().float()), N, _ptr(table), B, Tmax, _ptr(obj_out), _ptr(boxes_out), _ptr(cls), sd,
+                                             _ptr(ws), ws.numel(), flags), 'mcg_stage_forward_ragged')
+        return obj_out, boxes_out, cls
     L.check(lib.mcg_stage_forward(_stream(), dt, _table(stage_w, L.STAGE_KEYS), _ptr(roi_feat.contiguous()), _ptr(obj.contiguous()),
                                   _ptr(boxes.contiguous().float()), N, clip_length, _ptr(obj_out), _ptr(boxes_out), _ptr(cls), sd,
                                   _ptr(ws), ws.numel(), flags), 'mcg_stage_forward')
@@ -384,18 +442,21 @@ class HipEngine:
         frame_of[n].  pyramid: four [K,h,w,256] tensors (backbone_fpn(..., out=)); frame_of: N = windows * clip_length row indices, a host
         sequence (range-checked here, McgError) or an int32 tensor (a DEVICE table is the caller's responsibility: the kernels clamp
         the address of an index outside [0, K) and write NaN for that frame); img_hw: img_shape (h, w) per pyramid ROW [K,2] or None.
+        clip_length: an int, or a sequence of per-clip lengths summing to N -- clips of different lengths (mcg_decoder_forward_ragged).
         Returns dict(gaze [4,N,3], boxes [N,3,4], scores [N,3]) like forward -- bit for bit forward's on the stacked window frames."""
         K = pyramid[0].shape[0] if len(pyramid) else 0
         H, W = (pyramid[0].shape[1] * 4, pyramid[0].shape[2] * 4) if len(pyramid) else (0, 0)
         dev_table = isinstance(frame_of, torch.Tensor) and frame_of.device.type != 'cpu'
-        host = None if dev_table else check_frame_table(frame_of, K, clip_length)
+        ragged = not isinstance(clip_length, (int, np.integer))
+        host = None if dev_table else check_frame_table(frame_of, K, 1 if ragged else clip_length)
+        clips = _clips(clip_length, frame_of.numel() if dev_table else host.size, self.device)
         self._check_pyramid(pyramid)
         with torch.cuda.device(self.device):
             if dev_table:
                 if not (frame_of.dtype == torch.int32 and frame_of.device == self.device and frame_of.dim() == 1):
                     raise L.McgError(f'a device frame_of must be a 1-D int32 tensor on {self.device} (got {frame_of.dtype} {tuple(frame_of.shape)} on {frame_of.device})')
                 table = frame_of.contiguous()
-                if table.numel() == 0 or table.numel() % clip_length:
+                if not ragged and (table.numel() == 0 or table.numel() % clip_length):
                     raise L.McgError(f'frame_of holds {table.numel()} entries, not a positive multiple of clip_length={clip_length}')
             else:
                 # pinned + non-blocking: a pageable upload would make the host wait for the work already queued (harness.py, upload)
@@ -412,6 +473,10 @@ class HipEngine:
                 self._dec_ws = _ws(need, self.device)
             ws = self._dec_ws
             tab = (C.c_void_p * 4)(*[p.data_ptr() for p in pyramid])
+            if ragged:
+                L.check(self.lib.mcg_decoder_forward_ragged(self._handle, _stream(self.device), tab, K, _ptr(table), N, _ptr(clips[0]), clips[1], clips[2], H, W, _ptr(hw), _ptr(out['gaze']), _ptr(out['boxes']),
+                                                            _ptr(out['scores']), _ptr(ws), ws.numel()), 'mcg_decoder_forward_ragged')
+                return out
             L.check(self.lib.mcg_decoder_forward_indexed(self._handle, _stream(self.device), tab, K, _ptr(table), N, clip_length, H, W, _ptr(hw),
                                                          _ptr(out['gaze']), _ptr(out['boxes']), _ptr(out['scores']), _ptr(ws), ws.numel()),
                     'mcg_decoder_forward_indexed')
@@ -419,9 +484,12 @@ class HipEngine:
 
     def forward(self, img, clip_length, img_hw=None, chunk_frames=0, out=None):
         """img [N,3,H,W] f32 (device, contiguous), N = clips*clip_length.
+        clip_length: an int (every clip that long: mcg_clip_forward), or a sequence of per-clip lengths summing to N -- clips of different
+        lengths, stacked in order (mcg_clip_forward_ragged; or a ClipTable built once); every clip's results are those of forward(img[a:b], b - a) bit for bit.
         Returns dict(gaze [4,N,3], boxes [N,3,4], scores [N,3]) -- f32 device tensors."""
         self._check_img(img)
         N, _, H, W = img.shape
+        clips = _clips(clip_length, N, self.device)
         with torch.cuda.device(self.device):
             ws = self._workspace(N, H, W, chunk_frames)
             if out is None:
@@ -429,6 +497,10 @@ class HipEngine:
                            boxes=torch.empty(N, 3, 4, dtype=torch.float32, device=self.device),
                            scores=torch.empty(N, 3, dtype=torch.float32, device=self.device))
             hw = self.img_hw_tensor(img_hw, N)
+            if clips is not None:
+                L.check(self.lib.mcg_clip_forward_ragged(self._handle, _stream(self.device), _ptr(img), N, _ptr(clips[0]), clips[1], clips[2], H, W, _ptr(hw), chunk_frames, _ptr(out['gaze']),
+                                                         _ptr(out['boxes']), _ptr(out['scores']), _ptr(ws), ws.numel()), 'mcg_clip_forward_ragged')
+                return out
             L.check(self.lib.mcg_clip_forward(self._handle, _stream(self.device), _ptr(img), N, clip_length, H, W, _ptr(hw), chunk_frames,
                                               _ptr(out['gaze']), _ptr(out['boxes']), _ptr(out['scores']), _ptr(ws), ws.numel()),
                     'mcg_clip_forward')
@@ -452,12 +524,15 @@ class GraphedForward:
     trunk, 4 x (RoIAlign + decoder stage), gaze head -- is captured ONCE into a HIP graph for a fixed (N, H, W, clip_length) and
     replayed: one graph launch per clip.  Inputs are copied into the graph's static buffer on the caller's stream; the
     returned tensors are the graph's static outputs (valid until the next call).  Results are bit-identical to engine.forward
-    (tests/test_gpu_forward.py::test_graphed_forward_is_bit_identical)."""
+    (tests/test_gpu_forward.py::test_graphed_forward_is_bit_identical).  clip_length may be a sequence of per-clip lengths: the clip table
+    is then uploaded once, before the capture (ClipTable), and the graph holds the ragged call."""
 
     def __init__(self, engine, num_frames, H, W, clip_length, with_img_hw=False):
         e = self.e = engine
-        self.N, self.T = num_frames, clip_length
         dev = e.device
+        if not isinstance(clip_length, (int, np.integer, ClipTable)):
+            clip_length = ClipTable(clip_length, dev)
+        self.N, self.T = num_frames, clip_length
         with torch.cuda.device(dev):
             self.img = torch.zeros(num_frames, 3, H, W, dtype=torch.float32, device=dev)
             self.hw = torch.zeros(num_frames, 2, dtype=torch.int32, device=dev) if with_img_hw else None
@@ -511,11 +586,16 @@ class PipelinedRunner:
     are double-buffered; trunks serialise on stream A, decoders on stream B, ordered by events.
     Every submitted batch is fully processed once ``flush()`` returns control to the caller's stream.  A loop that owns the runner
     should submit from ``runner.sa`` itself (``with torch.cuda.stream(runner.sa): ...``): the caller-stream -> trunk-stream hand-over
-    of each submit is then no cross-queue dependency (2 ms per pipeline fill + drain when the queues are idle; bench.py does this)."""
+    of each submit is then no cross-queue dependency (2 ms per pipeline fill + drain when the queues are idle; bench.py does this).
+    clip_length: an int, or a sequence of per-clip lengths / a ClipTable -- every batch then holds clips of those lengths (the table is
+    uploaded once, here; mcg_decoder_forward_deferred_ragged)."""
 
     def __init__(self, engine, num_frames, H, W, clip_length, chunk_frames=0, decoder_priority=-1):
         self.e, self.N, self.H, self.W, self.T, self.chunk = engine, num_frames, H, W, clip_length, chunk_frames
         dev, lib, h = engine.device, engine.lib, engine._handle
+        if not isinstance(clip_length, (int, np.integer, ClipTable)):
+            self.T = ClipTable(clip_length, dev)
+        self.clips = _clips(self.T, num_frames, dev)
         # the decoder's short launches get the high-priority queue so they slot in between the trunk's long kernels
         self.sa, self.sb = pipeline_streams(dev, decoder_priority)
         self.slots = [_ws(lib.mcg_deferred_pyramid_bytes(h, num_frames, H, W), dev) for _ in range(2)]
@@ -549,9 +629,15 @@ class PipelinedRunner:
                 'mcg_backbone_fpn_forward_deferred')
         self.trunk_done[slot].record(self.sa)
         self.sb.wait_event(self.trunk_done[slot])
-        L.check(lib.mcg_decoder_forward_deferred(e._handle, C.c_void_p(self.sb.cuda_stream), _ptr(self.slots[slot]), self.slots[slot].numel(),
-                                                 self.N, self.T, self.H, self.W, _ptr(img_hw), _ptr(out['gaze']), _ptr(out['boxes']),
-                                                 _ptr(out['scores']), _ptr(self.dec_ws), self.dec_ws.numel()), 'mcg_decoder_forward_deferred')
+        if self.clips is not None:
+            L.check(lib.mcg_decoder_forward_deferred_ragged(e._handle, C.c_void_p(self.sb.cuda_stream), _ptr(self.slots[slot]), self.slots[slot].numel(),
+                                                            self.N, _ptr(self.clips[0]), self.clips[1], self.clips[2], self.H, self.W, _ptr(img_hw),
+                                                            _ptr(out['gaze']), _ptr(out['boxes']), _ptr(out['scores']), _ptr(self.dec_ws),
+                                                            self.dec_ws.numel()), 'mcg_decoder_forward_deferred_ragged')
+        else:
+            L.check(lib.mcg_decoder_forward_deferred(e._handle, C.c_void_p(self.sb.cuda_stream), _ptr(self.slots[slot]), self.slots[slot].numel(),
+                                                     self.N, self.T, self.H, self.W, _ptr(img_hw), _ptr(out['gaze']), _ptr(out['boxes']),
+                                                     _ptr(out['scores']), _ptr(self.dec_ws), self.dec_ws.numel()), 'mcg_decoder_forward_deferred')
         self.dec_done[slot].record(self.sb)
         self.used[slot] = True
         self.k += 1

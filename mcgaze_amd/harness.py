@@ -96,7 +96,10 @@ def result_file_name(config_path, json_path):
     return f'results_{config_path.rstrip(".py").split("/")[-1]}_{json_path.split("/")[-1]}'
 
 
-def _run_windows(engine, ids, plans, get_window, batch_clips, person_threshold, reuse_frames=False):
+FUSED_ATTN_MAX_T = 10     # longest clip the fused attention block takes (3 T <= 32 token rows: one MFMA tile, csrc/attn_block.hpp)
+
+
+def _run_windows(engine, ids, plans, get_window, batch_clips, person_threshold, reuse_frames=False, mixed_lengths=False):
     """Core of run_videos / run_annotation, STREAMING: windows are visited in (video, window) order -- the reference's order, so the
     crop RNG draws inside ``get_window`` fall where upstream's do -- and dropped into per-(T, H, W) buckets; a bucket runs through
     the engine (batched semantics: N = B*T frames, clip_length = T) as soon as it holds ``batch_clips`` clips and its inputs are
@@ -105,7 +108,11 @@ def _run_windows(engine, ids, plans, get_window, batch_clips, person_threshold, 
     get_window(vi, wi) -> (frames [T,3,H,W] f32, img_hw [T,2] int or None, scale [T,4] f32 or None).
     reuse_frames: frame t of window (a, b) of video vi IS frame a + t of the video: each distinct (video, frame) of a flush goes through the
     trunk once, into one row of a pyramid store, and one indexed decoder call (engine.decode) reads the windows' frames from it -- the
-    same batch of windows as forward would run, so the same bits.  ``trunk`` counts the frames run through the trunk."""
+    same batch of windows as forward would run, so the same bits.  ``trunk`` counts the frames run through the trunk.
+    mixed_lengths: windows of DIFFERENT lengths share a bucket -- keyed (H, W, longest-clip class) with the classes T <= 10 and T > 10, so
+    that one long clip does not push a bucket of short windows off the fused attention block -- and a flush is one ragged forward / decode
+    (clip_length = the list of the windows' lengths): a video shorter than clip_len no longer runs alone.  A window's results do not
+    depend on its batch, so the records are those of the default bucketing."""
     dev = engine.device
     trunk = [0]
     buckets = {}                                       # (T, H, W) -> list of (vi, wi, frames, hw, scale)
@@ -114,7 +121,7 @@ def _run_windows(engine, ids, plans, get_window, batch_clips, person_threshold, 
     records = [None] * len(plans)
 
     keep = []                                          # pinned host tensors of the last flush: alive until their non-blocking copies ran
-    inflight = collections.deque()                     # batches whose results are on their way to the host: (items, T, pinned buffer, event)
+    inflight = collections.deque()                     # batches whose results are on their way to the host: (items (vi, wi, T), pinned buffer, event)
     spare = []                                         # pinned result buffers free for reuse
 
     def upload(t):
@@ -129,26 +136,32 @@ def _run_windows(engine, ids, plans, get_window, batch_clips, person_threshold, 
     def collect(leave):
         # results of finished batches -> per-window host arrays -> (once a video's last window is back) merge + record, all on the host:
         # the consumer never waits for a forward it has just queued (round 3 / 4 did, in video_record's .cpu(): host and device took turns)
-        while len(inflight) > leave or (inflight and (inflight[0][3] is None or inflight[0][3].query())):
-            items, T, buf, ev = inflight.popleft()
+        while len(inflight) > leave or (inflight and (inflight[0][2] is None or inflight[0][2].query())):
+            items, buf, ev = inflight.popleft()
             if ev is not None:
                 ev.synchronize()
-            res = buf[:len(items) * T].numpy().copy()  # [frames, 27] = det 3x5 | fused 3 | others 3x3; copied: the pinned buffer is reused
+            res = buf[:sum(T for _, _, T in items)].numpy().copy()  # [frames, 27] = det 3x5 | fused 3 | others 3x3; copied: the pinned buffer is reused
             if ev is not None:
                 spare.append(buf)
-            for bi, (vi, wi) in enumerate(items):
-                r = res[bi * T:(bi + 1) * T]
+            row = 0
+            for vi, wi, T in items:
+                r = res[row:row + T]
+                row += T
                 outputs[vi][wi] = (r[:, :15].reshape(T, 3, 5), r[:, 15:18], r[:, 18:].reshape(T, 3, 3))
                 pending[vi] -= 1
                 if pending[vi] == 0:                   # all windows of the video are back: merge, record, release
                     records[vi] = video_record(ids[vi], *merge_video(plans[vi], outputs[vi], person_threshold))
                     outputs[vi] = None
 
-    def decode_distinct(items, T):
+    def length_of(it):
+        a, b, _ = plans[it[0]][it[1]]
+        return b - a
+
+    def decode_distinct(items, Ts):
         # rows of the pyramid store: the distinct (video, frame) of the batch, in order of first appearance; runs of consecutive frames
         # of one window are taken as slices
         row_of, parts, hws, table = {}, [], [], []
-        for vi, wi, x, hw, _ in items:
+        for (vi, wi, x, hw, _), T in zip(items, Ts):
             a = plans[vi][wi][0]
             for t in range(T):
                 k = (vi, a + t)
@@ -165,47 +178,48 @@ def _run_windows(engine, ids, plans, get_window, batch_clips, person_threshold, 
         hw = None if items[0][3] is None else upload(torch.from_numpy(np.stack(hws)))
         pyr = engine.backbone_fpn(x)
         trunk[0] += x.shape[0]
-        return engine.decode(pyr, table, T, img_hw=hw)
+        return engine.decode(pyr, table, Ts if mixed_lengths else Ts[0], img_hw=hw)
 
     def flush(key):
         items = buckets.pop(key, [])
         if not items:
             return
-        T = key[0]
+        Ts = [length_of(it) for it in items]         # default bucketing: all equal (the key's T)
         collect(2)
         del keep[:max(0, len(keep) - 4)]
         if reuse_frames:
-            out = decode_distinct(items, T)
+            out = decode_distinct(items, Ts)
         else:
             x = torch.cat([it[2] for it in items]).to(dev, torch.float32).contiguous()
             hw = None if items[0][3] is None else upload(torch.cat([torch.as_tensor(it[3], dtype=torch.int32).reshape(-1, 2) for it in items]))
-            out = engine.forward(x, T, img_hw=hw)
+            out = engine.forward(x, Ts if mixed_lengths else Ts[0], img_hw=hw)
             trunk[0] += x.shape[0]
         boxes = out['boxes']
         if items[0][4] is not None:   # rescale=True: every frame's boxes by its own scale_factor (multiclue_gaze_roi_head.py:360-363)
             boxes = boxes / upload(torch.cat([torch.as_tensor(it[4], dtype=torch.float32) for it in items]))[:, None, :]
-        n = len(items) * T
+        n = sum(Ts)
         gaze = out['gaze']
         packed = torch.cat([boxes.reshape(n, 3, 4), out['scores'].reshape(n, 3, 1)], dim=-1).reshape(n, 15)
         packed = torch.cat([packed, gaze[0].reshape(n, 3), gaze[1:].permute(1, 0, 2).reshape(n, 9)], dim=1).to(torch.float32)
-        who = [(vi, wi) for vi, wi, _, _, _ in items]
+        who = [(it[0], it[1], T) for it, T in zip(items, Ts)]
         if dev.type != 'cuda':
-            inflight.append((who, T, packed, None))
+            inflight.append((who, packed, None))
             return
         buf = next((b for b in spare if b.shape[0] >= n), None)
         if buf is not None:
             spare.remove(buf)
         else:
-            buf = torch.empty(max(n, batch_clips * T), 27, dtype=torch.float32).pin_memory()
+            buf = torch.empty(max(n, batch_clips * max(Ts)), 27, dtype=torch.float32).pin_memory()
         buf[:n].copy_(packed, non_blocking=True)
         ev = torch.cuda.Event()
         ev.record(torch.cuda.current_stream(dev))
-        inflight.append((who, T, buf, ev))
+        inflight.append((who, buf, ev))
 
     for vi, plan in enumerate(plans):
         for wi in range(len(plan)):
             x, hw, sc = get_window(vi, wi)
-            key = (plan[wi][1] - plan[wi][0], x.shape[-2], x.shape[-1])
+            T = plan[wi][1] - plan[wi][0]
+            key = (x.shape[-2], x.shape[-1], int(T > FUSED_ATTN_MAX_T)) if mixed_lengths else (T, x.shape[-2], x.shape[-1])
             buckets.setdefault(key, []).append((vi, wi, x, hw, sc))
             if len(buckets[key]) >= batch_clips:
                 flush(key)
@@ -216,7 +230,8 @@ def _run_windows(engine, ids, plans, get_window, batch_clips, person_threshold, 
     return records
 
 
-def run_videos(engine, videos, clip_len=7, stride=4, batch_clips=64, scale_factor=None, person_threshold=0.5, reuse_frames=False):
+def run_videos(engine, videos, clip_len=7, stride=4, batch_clips=64, scale_factor=None, person_threshold=0.5, reuse_frames=False,
+               mixed_lengths=False):
     """Push whole videos through the HIP engine.
 
     videos: list of dict(id=…, frames=Tensor[L,3,H,W] f32 already preprocessed (normalised, padded to /32)[, img_hw=[L,2] int: the
@@ -226,7 +241,9 @@ def run_videos(engine, videos, clip_len=7, stride=4, batch_clips=64, scale_facto
     backbone + FPN once, into a pyramid store, then one indexed decoder call over the batch's windows (engine.decode): about 4 / 7 of the
     trunk work at (7, 4) on long videos, records == those of the default path (which runs engine.forward on every window's frames).
     Frames shared by windows that land in different batches are computed in each: at most clip_len - stride per video per batch
-    boundary.  last_run_stats['trunk_frames'] holds the frames the trunk ran on, for both settings."""
+    boundary.  last_run_stats['trunk_frames'] holds the frames the trunk ran on, for both settings.
+    mixed_lengths: windows of different lengths (videos shorter than clip_len) share batches -- one ragged engine call per flush
+    (_run_windows); the records are those of the default."""
     plans = [plan_windows(v['frames'].shape[0], clip_len, stride) for v in videos]
 
     def get_window(vi, wi):
@@ -235,11 +252,12 @@ def run_videos(engine, videos, clip_len=7, stride=4, batch_clips=64, scale_facto
         hw = videos[vi].get('img_hw')
         return videos[vi]['frames'][a:b], (None if hw is None else hw[a:b]), sc
 
-    return _run_windows(engine, [v['id'] for v in videos], plans, get_window, batch_clips, person_threshold, reuse_frames=reuse_frames)
+    return _run_windows(engine, [v['id'] for v in videos], plans, get_window, batch_clips, person_threshold, reuse_frames=reuse_frames,
+                        mixed_lengths=mixed_lengths)
 
 
 def run_annotation(engine, anno, root, pipeline, clip_len=7, stride=4, batch_clips=64, person_threshold=0.5, rng=None, workers=0, lookahead=None,
-                   processes=False, video_rng=None):
+                   processes=False, video_rng=None, mixed_lengths=False):
     """tools/test_gaze360_gaze.py:57-269 from the annotation file down: for every ``anno['videos']`` entry (``id``,
     ``file_names``) each window's frames are loaded and preprocessed ANEW through ``pipeline`` (a
     mcgaze_amd.pipeline.DevicePipeline built from cfg.data.test.pipeline) -- like the reference, which re-runs its test
@@ -254,7 +272,8 @@ def run_annotation(engine, anno, root, pipeline, clip_len=7, stride=4, batch_cli
     ``video_rng``: video id -> numpy RandomState.  With it every video draws its crops from its OWN generator (created when its first
     window is planned) instead of the shared ``rng``: the records then do not depend on which videos a process was given or in what
     order -- what a run sharded over several consumer processes needs to reproduce a single-process run record for record (the
-    reference's single global generator makes its results depend on the shard layout)."""
+    reference's single global generator makes its results depend on the shard layout).
+    ``mixed_lengths``: as in run_videos -- windows of different lengths in one ragged engine call per flush; same records."""
     import numpy as np
     import os
     from .pipeline import FrameCache
@@ -310,10 +329,73 @@ def run_annotation(engine, anno, root, pipeline, clip_len=7, stride=4, batch_cli
         return img, hw, np.stack([m['scale_factor'] for m in metas])
 
     try:
-        return _run_windows(engine, [v['id'] for v in videos], plans, get_window, batch_clips, person_threshold)
+        return _run_windows(engine, [v['id'] for v in videos], plans, get_window, batch_clips, person_threshold, mixed_lengths=mixed_lengths)
     finally:
         last_run_stats.update(decodes=cache.decodes, decode_waits=cache.waits, decode_wait_s=round(cache.wait_s, 3), decode_first_wait_s=round(cache.first_wait_s, 3))
         cache.close()
+
+
+def plan_track_chunks(track_length, max_len=100):
+    """-> list of (start, stop): how the reference's demo cuts one person's track into clips (MCGaze_demo/demo.ipynb, cell 4): frames are
+    gathered one by one and run as ONE clip as soon as more than max_len are held (``len(datas) > max_len``) or the track ends -- so
+    consecutive chunks of max_len + 1 frames, the last one shorter; an empty track gives no chunk."""
+    step = max_len + 1
+    return [(a, min(a + step, track_length)) for a in range(0, track_length, step)]
+
+
+def run_tracks(engine, tracks, max_len=100, batch_frames=448, scale_factor=None):
+    """The inference loop of the reference's demo (MCGaze_demo/demo.ipynb, cell 4) on preprocessed frames: one clip per (person, segment),
+    as long as the person stays in view, cut every max_len + 1 frames -- where the demo runs one forward per chunk, the chunks of ALL
+    tracks are batched here as clips of different lengths (engine.forward(x, [lengths])).
+
+    tracks: list of dict(id=..., frames=Tensor[L,3,H,W] f32 preprocessed head crops (normalised, padded to /32)[, img_hw=[L,2] int]), one per
+    (person, segment).  Chunks (plan_track_chunks) are visited in (track, chunk) order and batched per (H, W, longest-clip class) -- chunks
+    of at most 10 frames and longer ones in separate calls, so that short clips keep the fused attention block -- up to batch_frames
+    frames per call (a single chunk may exceed it and then runs alone).  No overlap merge: the demo has none; a track's outputs are its
+    chunks' outputs concatenated.  scale_factor (4 floats) divides the boxes like rescale=True (the demo's setting).
+    Returns one dict(id, det [L,3,5], fused [L,3], others [L,3,3]) per track, numpy f32 in merge_video's layout (det = box | score).
+    Head detection and cropping from full frames stay with the caller."""
+    dev = engine.device
+    plans = [plan_track_chunks(int(t['frames'].shape[0]), max_len) for t in tracks]
+    parts = [[None] * len(p) for p in plans]
+    buckets = {}                                       # (H, W, class) -> list of (ti, ci)
+
+    def flush(key):
+        items = buckets.pop(key, [])
+        if not items:
+            return
+        spans = [plans[ti][ci] for ti, ci in items]
+        Ts = [b - a for a, b in spans]
+        x = torch.cat([tracks[ti]['frames'][a:b] for (ti, _), (a, b) in zip(items, spans)]).to(dev, torch.float32).contiguous()
+        hw = None
+        if tracks[items[0][0]].get('img_hw') is not None:
+            hw = np.concatenate([np.asarray(tracks[ti]['img_hw'], dtype=np.int32).reshape(-1, 2)[a:b] for (ti, _), (a, b) in zip(items, spans)])
+        out = engine.forward(x, Ts, img_hw=hw)
+        boxes = out['boxes']
+        if scale_factor is not None:
+            boxes = boxes / torch.as_tensor(scale_factor, dtype=torch.float32, device=boxes.device)
+        det = _host(torch.cat([boxes, out['scores'][..., None]], dim=-1))
+        gaze = _host(out['gaze'])
+        row = 0
+        for (ti, ci), T in zip(items, Ts):
+            parts[ti][ci] = (det[row:row + T], gaze[0, row:row + T], gaze[1:, row:row + T].transpose(1, 0, 2))
+            row += T
+
+    for ti, plan in enumerate(plans):
+        fr = tracks[ti]['frames']
+        for ci, (a, b) in enumerate(plan):
+            key = (fr.shape[-2], fr.shape[-1], int(b - a > FUSED_ATTN_MAX_T))
+            held = sum(plans[t][c][1] - plans[t][c][0] for t, c in buckets.get(key, []))
+            if held and held + (b - a) > batch_frames:
+                flush(key)
+            buckets.setdefault(key, []).append((ti, ci))
+    for key in sorted(buckets):
+        flush(key)
+    out = []
+    for t, p in zip(tracks, parts):
+        cat = lambda k, shape: np.concatenate([c[k] for c in p]) if p else np.zeros(shape, np.float32)
+        out.append(dict(id=t['id'], det=cat(0, (0, 3, 5)), fused=cat(1, (0, 3)), others=cat(2, (0, 3, 3))))
+    return out
 
 
 def dump_results(records, config_path, json_path, out_dir='results'):

@@ -11,7 +11,7 @@ LIB_PATH = os.environ.get('MCGAZE_LIB') or os.path.join(_HERE, 'libmcgaze_hip.so
 
 MCG_OK = 0
 MCG_F32, MCG_BF16, MCG_F16X3, MCG_F16 = 0, 1, 2, 3
-ABI_VERSION = 15
+ABI_VERSION = 16
 RES_NONE, RES_ADD, RES_UPSAMPLE_ADD = 0, 1, 2
 FLAG_STAGED_GEMM, FLAG_NO_SPECIALISED, FLAG_NO_ATTN_BLOCK = 1, 2, 4
 
@@ -32,7 +32,8 @@ EXPORTS = ['mcg_abi_version', 'mcg_build_id', 'mcg_last_error', 'mcg_device_info
            'mcg_decoder_forward', 'mcg_clip_forward', 'mcg_preprocess_frames', 'mcg_engine_set_option', 'mcg_engine_profile_start',
            'mcg_engine_profile_stop', 'mcg_bench_backbone_forward', 'mcg_bottleneck_x3', 'mcg_bench_backbone_levels', 'mcg_conv3x3_wino_x3',
            'mcg_conv3x3_wino_x3_weight_bytes', 'mcg_engine_range_audit', 'mcg_roi_align_indexed', 'mcg_decoder_forward_indexed',
-           'mcg_deferred_pyramid_bytes', 'mcg_deferred_pyramid_levels', 'mcg_backbone_fpn_forward_deferred', 'mcg_decoder_forward_deferred']
+           'mcg_deferred_pyramid_bytes', 'mcg_deferred_pyramid_levels', 'mcg_backbone_fpn_forward_deferred', 'mcg_decoder_forward_deferred',
+           'mcg_stage_forward_ragged', 'mcg_decoder_forward_ragged', 'mcg_decoder_forward_deferred_ragged', 'mcg_clip_forward_ragged']
 
 
 class ConvDesc(C.Structure):
@@ -118,6 +119,11 @@ def load():
     lib.mcg_backbone_fpn_forward_deferred.argtypes = [vp, vp, vp, i, i, i, i, vp, sz, vp, sz]
     lib.mcg_decoder_forward_deferred.argtypes = [vp, vp, vp, sz, i, i, i, i, vp, vp, vp, vp, vp, sz]
     lib.mcg_clip_forward.argtypes = [vp, vp, vp, i, i, i, i, vp, i, vp, vp, vp, vp, sz]
+    # ragged forms: (clip_start (device), num_clips, max_clip_length) in place of clip_length
+    lib.mcg_stage_forward_ragged.argtypes = [vp, i, C.POINTER(vp), vp, vp, vp, i, vp, i, i, vp, vp, vp, C.POINTER(C.c_float), vp, sz, i]
+    lib.mcg_decoder_forward_ragged.argtypes = [vp, vp, C.POINTER(vp), i, vp, i, vp, i, i, i, i, vp, vp, vp, vp, vp, sz]
+    lib.mcg_decoder_forward_deferred_ragged.argtypes = [vp, vp, vp, sz, i, vp, i, i, i, i, vp, vp, vp, vp, vp, sz]
+    lib.mcg_clip_forward_ragged.argtypes = [vp, vp, vp, i, vp, i, i, i, i, vp, i, vp, vp, vp, vp, sz]
     lib.mcg_preprocess_frames.argtypes = [vp, vp, i, vp, i, i, C.POINTER(C.c_float), C.POINTER(C.c_float), i]
     lib.mcg_engine_set_option.argtypes = [vp, C.c_char_p, i]
     lib.mcg_engine_profile_start.argtypes = [vp, i]
