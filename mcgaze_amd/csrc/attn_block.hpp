@@ -249,8 +249,7 @@ __global__ __launch_bounds__(256, 1) void attn_block_kernel(const AttnBlockParam
 }
 
 static inline bool attn_block_applicable(int T) { return T >= 1 && 3 * T <= 32; }   // T: the longest clip of the call
-static inline int launch_attn_block(hipStream_t s, const AttnBlockParams& p, bool fp16 = false) {
-  if (fp16) hipLaunchKernelGGL(attn_block_kernel<f16_t>, dim3(p.num_clips), dim3(256), 0, s, p);
-  else hipLaunchKernelGGL(attn_block_kernel<bf16_t>, dim3(p.num_clips), dim3(256), 0, s, p);
+static inline int launch_attn_block(hipStream_t s, const AttnBlockParams& p, mcg_dtype dt) {
+  dispatch_elem16(dt, [&](auto e) { hipLaunchKernelGGL(attn_block_kernel<decltype(e)>, dim3(p.num_clips), dim3(256), 0, s, p); });
   return hipGetLastError() == hipSuccess ? 0 : 1;
 }

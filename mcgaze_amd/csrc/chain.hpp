@@ -121,8 +121,7 @@ __global__ __launch_bounds__(256, 1) void mlp_chain_kernel(const ChainParams p) 
   }
 }
 
-static inline int launch_mlp_chain(hipStream_t s, const ChainParams& p, bool fp16 = false) {
-  if (fp16) hipLaunchKernelGGL(mlp_chain_kernel<f16_t>, dim3((p.M + 31) / 32), dim3(256), 0, s, p);
-  else hipLaunchKernelGGL(mlp_chain_kernel<bf16_t>, dim3((p.M + 31) / 32), dim3(256), 0, s, p);
+static inline int launch_mlp_chain(hipStream_t s, const ChainParams& p, mcg_dtype dt) {
+  dispatch_elem16(dt, [&](auto e) { hipLaunchKernelGGL(mlp_chain_kernel<decltype(e)>, dim3((p.M + 31) / 32), dim3(256), 0, s, p); });
   return hipGetLastError() == hipSuccess ? 0 : 1;
 }

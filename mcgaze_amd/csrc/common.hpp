@@ -176,6 +176,11 @@ __device__ __forceinline__ int xcd_remap(int bid, int nb) {
 // ---------------------------------------------------------------- dtype helpers of the host launchers
 static inline bool mcg_is16(mcg_dtype dt) { return dt == MCG_BF16 || dt == MCG_F16; }   // 2-byte activation storage
 
+// The one place a launcher turns an mcg_dtype into the element type of a kernel template: f(e) with e a zero of the STORAGE type of dt, the
+// type tag (decltype(e): float for MCG_F32 and for MCG_F16X3, whose activations are f32).  dispatch_elem16: the 16-bit-only kernels.
+template <typename F> static inline auto dispatch_elem16(mcg_dtype dt, F&& f) { return dt == MCG_F16 ? f(f16_t{}) : f(bf16_t{}); }
+template <typename F> static inline auto dispatch_elem(mcg_dtype dt, F&& f) { return mcg_is16(dt) ? dispatch_elem16(dt, f) : f(float{}); }
+
 // ---------------------------------------------------------------- host side error plumbing
 void mcg_set_error(const char* fmt, ...);
 #define MCG_CHECK_ARG(cond, ...)        \

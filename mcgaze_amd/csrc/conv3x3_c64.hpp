@@ -132,14 +132,14 @@ __global__ __launch_bounds__(256) void conv3x3_c64_kernel(const bf16_t* __restri
 static inline bool conv3x3_c64_applicable(int KH, int KW, int stride, int pad, int Cin, int Cout, bool has_residual, bool has_x2) {
   return KH == 3 && KW == 3 && stride == 1 && pad == 1 && Cin == 64 && Cout == 64 && !has_residual && !has_x2;
 }
-static inline int launch_conv3x3_c64(hipStream_t s, const void* x, const void* w, const float* bias, void* y, int N, int H, int W, int relu, bool fp16 = false) {
+static inline int launch_conv3x3_c64(hipStream_t s, const void* x, const void* w, const float* bias, void* y, int N, int H, int W, int relu, mcg_dtype dt) {
   const int tiles_y = (H + c64::TH - 1) / c64::TH, tiles_x = (W + c64::TW - 1) / c64::TW;
   const long long total = (long long)tiles_y * tiles_x * N;
   if (total > 0x7fffffffLL) return 1;
   const int grid = (int)(total < 512 ? total : 512);
-  if (fp16) hipLaunchKernelGGL(conv3x3_c64_kernel<f16_t>, dim3(grid), dim3(256), 0, s, (const bf16_t*)x, (const bf16_t*)w, bias, (bf16_t*)y, H, W, tiles_x,
-                               tiles_y * tiles_x, (int)total, relu);
-  else hipLaunchKernelGGL(conv3x3_c64_kernel<bf16_t>, dim3(grid), dim3(256), 0, s, (const bf16_t*)x, (const bf16_t*)w, bias, (bf16_t*)y, H, W, tiles_x,
-                          tiles_y * tiles_x, (int)total, relu);
+  dispatch_elem16(dt, [&](auto e) {   // both instantiations take bf16_t-typed pointers (2-byte storage either way)
+    hipLaunchKernelGGL(conv3x3_c64_kernel<decltype(e)>, dim3(grid), dim3(256), 0, s, (const bf16_t*)x, (const bf16_t*)w, bias, (bf16_t*)y, H, W, tiles_x,
+                       tiles_y * tiles_x, (int)total, relu);
+  });
   return hipGetLastError() == hipSuccess ? 0 : 1;
 }

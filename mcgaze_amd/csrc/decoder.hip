@@ -119,9 +119,7 @@ __global__ __launch_bounds__(256) void ln_kernel(const LnParams p) {
 static int launch_ln(hipStream_t s, mcg_dtype dt, const LnParams& p) {
   MCG_CHECK_ARG(p.D % 64 == 0 && p.D <= 256 && p.M > 0, "layernorm: unsupported width %d", p.D);
   dim3 grid((p.M + 3) / 4);
-  if (dt == MCG_BF16) hipLaunchKernelGGL(ln_kernel<bf16_t>, grid, dim3(256), 0, s, p);
-  else if (dt == MCG_F16) hipLaunchKernelGGL(ln_kernel<f16_t>, grid, dim3(256), 0, s, p);
-  else hipLaunchKernelGGL(ln_kernel<float>, grid, dim3(256), 0, s, p);
+  dispatch_elem(dt, [&](auto e) { hipLaunchKernelGGL(ln_kernel<decltype(e)>, grid, dim3(256), 0, s, p); });
   MCG_CHECK_LAUNCH("layernorm");
   return MCG_OK;
 }
@@ -131,6 +129,13 @@ static LnParams ln_simple(const void* src, const float* g, const float* b, int r
   memset(&p, 0, sizeof(p));
   p.src = src; p.g1 = g; p.b1 = b; p.relu1 = relu; p.dst = dst; p.M = M; p.D = D;
   p.src_ld = D; p.res_ld = D; p.dst_ld = D; p.rows_per_group = 1 << 30; p.param_stride = 0;
+  return p;
+}
+// The epilogue of a split-K linear: sum the f32 slabs [slabs][M][256] + bias, LN1 (g1 null: none), + res, LN2 -> dst (deterministic, no atomics)
+static LnParams ln_splitk(const float* partial, int slabs, const float* bias, const float* g1, const float* b1, int relu1, const void* res,
+                          const float* g2, const float* b2, void* dst, int M) {
+  LnParams p = ln_simple(nullptr, g1, b1, relu1, dst, M, 256);
+  p.partial = partial; p.slabs = slabs; p.slab_stride = (long long)M * 256; p.bias = bias; p.res = res; p.g2 = g2; p.b2 = b2;
   return p;
 }
 
@@ -578,12 +583,6 @@ int launch_roi_align(hipStream_t s, mcg_dtype dt, const void* const feats[4], co
                      const int strides[4], int C, const float* boxes, int num_boxes, int boxes_per_frame, const int32_t* frame_of,
                      int pyramid_frames, void* out, int32_t* levels_out);
 
-template <typename T>
-static void launch_attn(hipStream_t s, const void* qkv, void* out, int groups, int L, int temporal, int clip_len, const int32_t* clip_start, int N) {
-  hipLaunchKernelGGL(attn_core_kernel<T>, dim3(groups), dim3(256), 0, s, (const T*)qkv, (T*)out, L, temporal, clip_len, 1.0f / sqrtf(32.f),
-                     temporal ? clip_start : nullptr, N);
-}
-
 // What the C-ABI accepts as a batch's split into clips (igemm.hpp: ClipTable).  The table itself lives on the device and is not read here
 // (no sync); the kernels clamp what it says (attn_block.hpp: clip_span).
 int check_clips(const char* what, int N, const ClipTable& ct) {
@@ -625,7 +624,7 @@ int stage_forward_ctx(hipStream_t s, mcg_dtype dt, const void* const W[MCG_SW_CO
   const int R = N * 3, B = ct.num_clips;
   const float* f32w[MCG_SW_COUNT];
   for (int i = 0; i < MCG_SW_COUNT; ++i) f32w[i] = (const float*)W[i];
-  const bool bf = mcg_is16(dt), h16 = dt == MCG_F16;   // bf: 2-byte storage (MCG_BF16 or MCG_F16: the same launch sequence); h16: fp16 instantiations
+  const bool bf = mcg_is16(dt);   // 2-byte storage (MCG_BF16 or MCG_F16: the same launch sequence, instantiated per number format)
   const size_t es = bf ? 2 : 4;
 
   // --- spatial then temporal self-attention with SHARED weights and LayerNorm (gaze_stqi_head.py:148-166)
@@ -641,13 +640,15 @@ int stage_forward_ctx(hipStream_t s, mcg_dtype dt, const void* const W[MCG_SW_CO
     ap.x = obj_in; ap.y = w.x2; ap.w_in = W[MCG_SW_IN_PROJ_WF]; ap.b_in = f32w[MCG_SW_IN_PROJ_B];
     ap.w_out = W[MCG_SW_OUT_PROJ_WF]; ap.b_out = f32w[MCG_SW_OUT_PROJ_B]; ap.g = f32w[MCG_SW_ATTN_LN_G]; ap.b = f32w[MCG_SW_ATTN_LN_B];
     ap.num_clips = B; ap.T = clip_length; ap.scale = 1.0f / sqrtf(32.f); ap.clip_start = ct.start; ap.num_frames = N;
-    if (chain_x3 ? launch_attn_block_x3(s, ap) : launch_attn_block(s, ap, h16)) { mcg_set_error("attn_block launch failed"); return MCG_ERR_HIP; }
+    if (chain_x3 ? launch_attn_block_x3(s, ap) : launch_attn_block(s, ap, dt)) { mcg_set_error("attn_block launch failed"); return MCG_ERR_HIP; }
   }
   for (int pass = 0; pass < 2 && !block_attn; ++pass) {
     MCG_TRY(launch_linear(s, dt, xin, 256, W[MCG_SW_IN_PROJ_W], f32w[MCG_SW_IN_PROJ_B], nullptr, 0, w.qkv, 768, R, 256, 768, 0, ctx));
-    if (h16) launch_attn<f16_t>(s, w.qkv, w.att, pass == 0 ? N : B * 3, pass == 0 ? 3 : clip_length, pass, clip_length, ct.start, N);
-    else if (bf) launch_attn<bf16_t>(s, w.qkv, w.att, pass == 0 ? N : B * 3, pass == 0 ? 3 : clip_length, pass, clip_length, ct.start, N);
-    else launch_attn<float>(s, w.qkv, w.att, pass == 0 ? N : B * 3, pass == 0 ? 3 : clip_length, pass, clip_length, ct.start, N);
+    dispatch_elem(dt, [&](auto e) {   // pass 0: over a frame's 3 tokens; pass 1: over a clue's tokens across its clip
+      using T = decltype(e);
+      hipLaunchKernelGGL(attn_core_kernel<T>, dim3(pass == 0 ? N : B * 3), dim3(256), 0, s, (const T*)w.qkv, (T*)w.att, pass == 0 ? 3 : clip_length, pass,
+                         clip_length, 1.0f / sqrtf(32.f), pass ? ct.start : nullptr, N);
+    });
     MCG_CHECK_LAUNCH("attn_core");
     if (chain_attn || chain_x3) {  // out_proj + residual + LayerNorm as one launch
       ChainParams cp;
@@ -655,7 +656,7 @@ int stage_forward_ctx(hipStream_t s, mcg_dtype dt, const void* const W[MCG_SW_CO
       cp.x = w.att; cp.M = R; cp.steps = 1;
       cp.st[0].W = W[MCG_SW_OUT_PROJ_WF]; cp.st[0].bias = f32w[MCG_SW_OUT_PROJ_B]; cp.st[0].res = xin;
       cp.st[0].g = f32w[MCG_SW_ATTN_LN_G]; cp.st[0].b = f32w[MCG_SW_ATTN_LN_B]; cp.st[0].dst = xout[pass]; cp.st[0].from_input = 1;
-      if (chain_x3 ? launch_mlp_chain_x3(s, cp) : launch_mlp_chain(s, cp, h16)) { mcg_set_error("mlp_chain launch failed"); return MCG_ERR_HIP; }
+      if (chain_x3 ? launch_mlp_chain_x3(s, cp) : launch_mlp_chain(s, cp, dt)) { mcg_set_error("mlp_chain launch failed"); return MCG_ERR_HIP; }
     } else {
       MCG_TRY(launch_linear(s, dt, w.att, 256, W[MCG_SW_OUT_PROJ_W], f32w[MCG_SW_OUT_PROJ_B], xin, 256, w.t, 256, R, 256, 256, 0, ctx));
       MCG_TRY(launch_ln(s, dt, ln_simple(w.t, f32w[MCG_SW_ATTN_LN_G], f32w[MCG_SW_ATTN_LN_B], 0, xout[pass], R, 256)));
@@ -670,40 +671,30 @@ int stage_forward_ctx(hipStream_t s, mcg_dtype dt, const void* const W[MCG_SW_CO
     memset(&pp, 0, sizeof(pp));
     pp.a = w.x2; pp.wf = W[MCG_SW_DYN_WF]; pp.bias = f32w[MCG_SW_DYN_B]; pp.y = w.params; pp.M = R; pp.Ho = 1; pp.Wo = 1;
     ProfRec* rec = prof_begin(ctx, s, chain_x3 ? 72 : 62, R, 32768, 256, 2.0 * R * 32768 * 256, (double)es * ((double)R * (256 + 32768) + 32768.0 * 256));
-    const int rc = chain_x3 ? launch_pw_dyn_x3(s, pp) : launch_pw_dyn(s, pp, h16);
+    const int rc = chain_x3 ? launch_pw_dyn_x3(s, pp) : launch_pw_dyn(s, pp, dt);
     prof_end(rec, s);
     if (rc) { mcg_set_error("%s (dynamic_layer) launch failed", chain_x3 ? "pw_single_x3" : "pw_single"); return MCG_ERR_HIP; }
   } else {
     MCG_TRY(launch_linear(s, dt, w.x2, 256, W[MCG_SW_DYN_W], f32w[MCG_SW_DYN_B], nullptr, 0, w.params, 32768, R, 256, 32768, 0, ctx));
   }
-  if (h16) hipLaunchKernelGGL(dynconv_kernel<f16_t>, dim3(R), dim3(256), 0, s, (const f16_t*)roi_feat, (const f16_t*)w.params, f32w[MCG_SW_NORM_IN_G], f32w[MCG_SW_NORM_IN_B], f32w[MCG_SW_NORM_OUT_G], f32w[MCG_SW_NORM_OUT_B], (f16_t*)w.feat2);
-  else if (bf) hipLaunchKernelGGL(dynconv_kernel<bf16_t>, dim3(R), dim3(256), 0, s, (const bf16_t*)roi_feat, (const bf16_t*)w.params, f32w[MCG_SW_NORM_IN_G], f32w[MCG_SW_NORM_IN_B], f32w[MCG_SW_NORM_OUT_G], f32w[MCG_SW_NORM_OUT_B], (bf16_t*)w.feat2);
-  else if (dt == MCG_F16X3) hipLaunchKernelGGL(dynconv_x3_kernel, dim3(R), dim3(256), 0, s, (const float*)roi_feat, (const float*)w.params, f32w[MCG_SW_NORM_IN_G], f32w[MCG_SW_NORM_IN_B], f32w[MCG_SW_NORM_OUT_G], f32w[MCG_SW_NORM_OUT_B], (float*)w.feat2);
-  else hipLaunchKernelGGL(dynconv_kernel<float>, dim3(R), dim3(256), 0, s, (const float*)roi_feat, (const float*)w.params, f32w[MCG_SW_NORM_IN_G], f32w[MCG_SW_NORM_IN_B], f32w[MCG_SW_NORM_OUT_G], f32w[MCG_SW_NORM_OUT_B], (float*)w.feat2);
+  auto dynconv = [&](auto kernel, auto e) {   // a kernel and (e) the element type of its three tensors
+    using T = decltype(e);
+    hipLaunchKernelGGL(kernel, dim3(R), dim3(256), 0, s, (const T*)roi_feat, (const T*)w.params, f32w[MCG_SW_NORM_IN_G], f32w[MCG_SW_NORM_IN_B],
+                       f32w[MCG_SW_NORM_OUT_G], f32w[MCG_SW_NORM_OUT_B], (T*)w.feat2);
+  };
+  if (dt == MCG_F16X3) dynconv(dynconv_x3_kernel, float{});
+  else dispatch_elem(dt, [&](auto e) { dynconv(dynconv_kernel<decltype(e)>, e); });
   MCG_CHECK_LAUNCH("dynconv");
   int slabs = 1;
   MCG_TRY(launch_linear_splitk(s, dt, w.feat2, 12544, W[MCG_SW_FC_W], w.partial, R, 12544, 256, kFcSlices, &slabs, ctx));
-  {
-    LnParams p;
-    memset(&p, 0, sizeof(p));
-    p.partial = w.partial; p.slabs = slabs; p.slab_stride = (long long)R * 256; p.bias = f32w[MCG_SW_FC_B];
-    p.g1 = f32w[MCG_SW_FC_LN_G]; p.b1 = f32w[MCG_SW_FC_LN_B]; p.relu1 = 1;
-    p.res = w.x2; p.g2 = f32w[MCG_SW_IIC_LN_G]; p.b2 = f32w[MCG_SW_IIC_LN_B]; p.relu2 = 0;
-    p.dst = w.x3; p.M = R; p.D = 256; p.src_ld = 256; p.res_ld = 256; p.dst_ld = 256; p.rows_per_group = 1 << 30;
-    MCG_TRY(launch_ln(s, dt, p));
-  }
+  MCG_TRY(launch_ln(s, dt, ln_splitk(w.partial, slabs, f32w[MCG_SW_FC_B], f32w[MCG_SW_FC_LN_G], f32w[MCG_SW_FC_LN_B], 1, w.x2, f32w[MCG_SW_IIC_LN_G], f32w[MCG_SW_IIC_LN_B], w.x3, R)));
   // --- FFN (mmcv FFN with add_identity, gaze_stqi_head.py:179-180)
   MCG_TRY(launch_linear(s, dt, w.x3, 256, W[MCG_SW_FFN1_W], f32w[MCG_SW_FFN1_B], nullptr, 0, w.h, 2048, R, 256, 2048, 1, ctx));
   {  // 2048 -> 256 at M = R rows is only a couple of dozen output tiles: split K so the whole chip works on it; the
      // LayerNorm kernel sums the slabs, adds bias and the residual, and normalises (deterministic, no atomics)
     int ffn_slabs = 1;
     MCG_TRY(launch_linear_splitk(s, dt, w.h, 2048, W[MCG_SW_FFN2_W], w.partial, R, 2048, 256, 8, &ffn_slabs, ctx));
-    LnParams p;
-    memset(&p, 0, sizeof(p));
-    p.partial = w.partial; p.slabs = ffn_slabs; p.slab_stride = (long long)R * 256; p.bias = f32w[MCG_SW_FFN2_B];
-    p.res = w.x3; p.g2 = f32w[MCG_SW_FFN_LN_G]; p.b2 = f32w[MCG_SW_FFN_LN_B];
-    p.dst = obj_out; p.M = R; p.D = 256; p.src_ld = 256; p.res_ld = 256; p.dst_ld = 256; p.rows_per_group = 1 << 30;
-    MCG_TRY(launch_ln(s, dt, p));
+    MCG_TRY(launch_ln(s, dt, ln_splitk(w.partial, ffn_slabs, f32w[MCG_SW_FFN2_B], nullptr, nullptr, 0, w.x3, f32w[MCG_SW_FFN_LN_G], f32w[MCG_SW_FFN_LN_B], obj_out, R)));
   }
   // --- towers (gaze_stqi_head.py:185-188)
   const void* rin = obj_out;
@@ -720,7 +711,7 @@ int stage_forward_ctx(hipStream_t s, mcg_dtype dt, const void* const W[MCG_SW_CO
       st.g = f32w[MCG_SW_REG_LN_G] + j * 256; st.b = f32w[MCG_SW_REG_LN_B] + j * 256;
       st.from_input = j == 0; st.relu = 1; st.dst = j == 2 ? w.r1 : nullptr;
     }
-    if (bf ? launch_mlp_chain(s, cp, h16) : launch_mlp_chain_x3(s, cp)) { mcg_set_error("mlp_chain launch failed"); return MCG_ERR_HIP; }
+    if (bf ? launch_mlp_chain(s, cp, dt) : launch_mlp_chain_x3(s, cp)) { mcg_set_error("mlp_chain launch failed"); return MCG_ERR_HIP; }
     rin = w.r1;
   } else {
     MCG_TRY(launch_linear(s, dt, obj_out, 256, W[MCG_SW_CLS_FC_W], nullptr, nullptr, 0, w.c1, 256, R, 256, 256, 0, ctx));
@@ -733,9 +724,11 @@ int stage_forward_ctx(hipStream_t s, mcg_dtype dt, const void* const W[MCG_SW_CO
     }
   }
   const float max_ratio = 4.135166556742356f;  // |log(16/1000)|, delta_xywh_bbox_coder.py:236
-  if (dt == MCG_BF16) hipLaunchKernelGGL(heads_kernel<bf16_t>, dim3((R + 3) / 4), dim3(256), 0, s, (const bf16_t*)w.clsf, (const bf16_t*)rin, f32w[MCG_SW_HEAD_CLS_W], f32w[MCG_SW_HEAD_CLS_B], f32w[MCG_SW_HEAD_REG_W], f32w[MCG_SW_HEAD_REG_B], boxes_in, boxes_out, cls_out, R, stds[0], stds[1], stds[2], stds[3], max_ratio);
-  else if (dt == MCG_F16) hipLaunchKernelGGL(heads_kernel<f16_t>, dim3((R + 3) / 4), dim3(256), 0, s, (const f16_t*)w.clsf, (const f16_t*)rin, f32w[MCG_SW_HEAD_CLS_W], f32w[MCG_SW_HEAD_CLS_B], f32w[MCG_SW_HEAD_REG_W], f32w[MCG_SW_HEAD_REG_B], boxes_in, boxes_out, cls_out, R, stds[0], stds[1], stds[2], stds[3], max_ratio);
-  else hipLaunchKernelGGL(heads_kernel<float>, dim3((R + 3) / 4), dim3(256), 0, s, (const float*)w.clsf, (const float*)rin, f32w[MCG_SW_HEAD_CLS_W], f32w[MCG_SW_HEAD_CLS_B], f32w[MCG_SW_HEAD_REG_W], f32w[MCG_SW_HEAD_REG_B], boxes_in, boxes_out, cls_out, R, stds[0], stds[1], stds[2], stds[3], max_ratio);
+  dispatch_elem(dt, [&](auto e) {
+    using T = decltype(e);
+    hipLaunchKernelGGL(heads_kernel<T>, dim3((R + 3) / 4), dim3(256), 0, s, (const T*)w.clsf, (const T*)rin, f32w[MCG_SW_HEAD_CLS_W], f32w[MCG_SW_HEAD_CLS_B],
+                       f32w[MCG_SW_HEAD_REG_W], f32w[MCG_SW_HEAD_REG_B], boxes_in, boxes_out, cls_out, R, stds[0], stds[1], stds[2], stds[3], max_ratio);
+  });
   MCG_CHECK_LAUNCH("heads");
   return MCG_OK;
 }
@@ -777,9 +770,11 @@ int gaze_head_ctx(hipStream_t s, mcg_dtype dt, const void* const W[MCG_GW_COUNT]
     q.rows_per_group = N; q.param_stride = 2 * 256;  // LN params are [6][2][256]
     MCG_TRY(launch_ln(s, dt, q));
   }
-  if (dt == MCG_BF16) hipLaunchKernelGGL(gaze_tail_kernel<bf16_t>, dim3((N + 3) / 4), dim3(256), 0, s, (const bf16_t*)h2, (const float*)W[MCG_GW_OUT_W], (const float*)W[MCG_GW_OUT_B], (const float*)W[MCG_GW_FUSE_W], (const float*)W[MCG_GW_FUSE_B], gaze_out, N, cls_logits, scores_out);
-  else if (dt == MCG_F16) hipLaunchKernelGGL(gaze_tail_kernel<f16_t>, dim3((N + 3) / 4), dim3(256), 0, s, (const f16_t*)h2, (const float*)W[MCG_GW_OUT_W], (const float*)W[MCG_GW_OUT_B], (const float*)W[MCG_GW_FUSE_W], (const float*)W[MCG_GW_FUSE_B], gaze_out, N, cls_logits, scores_out);
-  else hipLaunchKernelGGL(gaze_tail_kernel<float>, dim3((N + 3) / 4), dim3(256), 0, s, (const float*)h2, (const float*)W[MCG_GW_OUT_W], (const float*)W[MCG_GW_OUT_B], (const float*)W[MCG_GW_FUSE_W], (const float*)W[MCG_GW_FUSE_B], gaze_out, N, cls_logits, scores_out);
+  dispatch_elem(dt, [&](auto e) {
+    using T = decltype(e);
+    hipLaunchKernelGGL(gaze_tail_kernel<T>, dim3((N + 3) / 4), dim3(256), 0, s, (const T*)h2, (const float*)W[MCG_GW_OUT_W], (const float*)W[MCG_GW_OUT_B],
+                       (const float*)W[MCG_GW_FUSE_W], (const float*)W[MCG_GW_FUSE_B], gaze_out, N, cls_logits, scores_out);
+  });
   MCG_CHECK_LAUNCH("gaze_tail");
   return MCG_OK;
 }
@@ -789,9 +784,10 @@ int launch_init_queries(hipStream_t s, mcg_dtype dt, const float* init_boxes, co
                         const int32_t* frame_of, int pyramid_frames, int H, int W, float* boxes, void* obj, int N) {
   const long long total = (long long)N * 3 * 256;
   const int grid = (int)((total + 255) / 256 > 4096 ? 4096 : (total + 255) / 256);
-  if (dt == MCG_BF16) hipLaunchKernelGGL(init_queries_kernel<bf16_t>, dim3(grid), dim3(256), 0, s, init_boxes, (const bf16_t*)init_feats, img_hw, frame_of, pyramid_frames, H, W, boxes, (bf16_t*)obj, N);
-  else if (dt == MCG_F16) hipLaunchKernelGGL(init_queries_kernel<f16_t>, dim3(grid), dim3(256), 0, s, init_boxes, (const f16_t*)init_feats, img_hw, frame_of, pyramid_frames, H, W, boxes, (f16_t*)obj, N);
-  else hipLaunchKernelGGL(init_queries_kernel<float>, dim3(grid), dim3(256), 0, s, init_boxes, (const float*)init_feats, img_hw, frame_of, pyramid_frames, H, W, boxes, (float*)obj, N);
+  dispatch_elem(dt, [&](auto e) {
+    using T = decltype(e);
+    hipLaunchKernelGGL(init_queries_kernel<T>, dim3(grid), dim3(256), 0, s, init_boxes, (const T*)init_feats, img_hw, frame_of, pyramid_frames, H, W, boxes, (T*)obj, N);
+  });
   MCG_CHECK_LAUNCH("init_queries");
   return MCG_OK;
 }

@@ -411,7 +411,7 @@ static int conv_call(const mcg_engine* e, hipStream_t s, mcg_dtype dt, const mcg
     ProfRec* rec = prof_begin(e->ctx, s, x3 ? 71 : 61, pp.M, cw.cout, cw.cin, 2.0 * M * cw.cin * cw.cout,
                               (double)esize(dt) * ((double)M * (cw.cin + cw.cout) + (rm == MCG_RES_NONE ? 0.0 : (double)res_m) * cw.cout + (double)cw.cin * cw.cout));
     const int rmode = rm == MCG_RES_NONE ? 0 : (rm == MCG_RES_ADD ? 1 : 2);
-    return launch_done(rec, s, x3 ? launch_pw_single_x3(s, pp, cw.cout, rmode) : launch_pw_single(s, pp, cw.cin, cw.cout, rmode, dt == MCG_F16),
+    return launch_done(rec, s, x3 ? launch_pw_single_x3(s, pp, cw.cout, rmode) : launch_pw_single(s, pp, cw.cin, cw.cout, rmode, dt),
                        x3 ? "pw_single_x3" : "pw_single");
   }
   // F(4,3) where the layer's shape allows it and the weights carry that copy, else F(2,3) (FPN outputs, layer3's conv2), else the direct kernel
@@ -508,7 +508,7 @@ static int pw_pair_step(const mcg_engine* e, hipStream_t s, TrunkCursor& c, cons
   // cfg 60: both contractions of the pair count (2 M (K C + C C2))
   ProfRec* rec = prof_begin(e->ctx, s, 60, pp.M, pp.C + pp.C2, pp.K1 + pp.K2, 2.0 * pp.M * ((double)(pp.K1 + pp.K2) * pp.C + (double)pp.C * pp.C2),
                             2.0 * ((double)pp.M * (pp.K1 + pp.K2 + (has_ds ? 0 : pp.C) + pp.C + pp.C2) + (double)(pp.K1 + pp.K2) * pp.C + (double)pp.C * pp.C2));
-  MCG_TRY(launch_done(rec, s, launch_pw_pair(s, pp, e->dt == MCG_F16), "pw_pair"));
+  MCG_TRY(launch_done(rec, s, launch_pw_pair(s, pp, e->dt), "pw_pair"));
   c.o1_ready = true;
   return MCG_OK;
 }

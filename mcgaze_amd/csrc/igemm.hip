@@ -207,7 +207,7 @@ int launch_igemm(hipStream_t s, mcg_dtype dt, const IgemmParams& p_in, int group
   MCG_CHECK_ARG(p.M > 0 && p.Cout > 0 && groups > 0, "igemm: empty problem (M=%d Cout=%d groups=%d)", p.M, p.Cout, groups);
   MCG_CHECK_ARG(dt == MCG_F16X3 || p.wscale == 1.f, "igemm: wscale is an MCG_F16X3 operand (got %g)", (double)p.wscale);
   if (dt == MCG_F16X3) return launch_x3(s, p, groups, ctx);
-  return dt == MCG_BF16 ? launch_typed<bf16_t>(s, p, groups, ctx) : (dt == MCG_F16 ? launch_typed<f16_t>(s, p, groups, ctx) : launch_typed<float>(s, p, groups, ctx));
+  return dispatch_elem(dt, [&](auto e) { return launch_typed<decltype(e)>(s, p, groups, ctx); });
 }
 
 static IgemmParams linear_params(const void* x, long long lda, const void* w, int M, int K, int Cout) {
@@ -280,7 +280,7 @@ int conv2d_ctx(hipStream_t s, mcg_dtype dt, const mcg_conv_desc* d, const McgCtx
       conv3x3_c64_applicable(d->KH, d->KW, d->stride, d->pad, d->Cin, d->Cout, p.res_mode != MCG_RES_NONE, d->x2 != nullptr)) {
     // layer1's conv2: window staged once, nine taps by address (conv3x3_c64.hpp); bit-identical to the generic kernel
     ProfRec* rec = prof_begin(ctx, s, 40, p.M, 64, 576, 2.0 * p.M * 64 * 576, algo_bytes(p, 1, 2));
-    const int rc = launch_conv3x3_c64(s, d->x, d->w, d->bias, d->y, d->N, d->H, d->W, d->relu, dt == MCG_F16);
+    const int rc = launch_conv3x3_c64(s, d->x, d->w, d->bias, d->y, d->N, d->H, d->W, d->relu, dt);
     prof_end(rec, s);
     if (rc) { mcg_set_error("conv3x3_c64 launch failed"); return MCG_ERR_HIP; }
     return MCG_OK;
@@ -373,7 +373,7 @@ int stem_forward_ctx(hipStream_t s, mcg_dtype dt, const float* img, const void* 
     return MCG_ERR_WORKSPACE;
   }
   if (mcg_is16(dt) && ctx.stem_fused) {  // one kernel, no conv-map round trip (stem_fused.hpp); bit-identical to the path below
-    if (launch_stem_fused(s, img, w_stem, bias, y, N, H, W, dt == MCG_F16)) { mcg_set_error("stem_fused launch failed"); return MCG_ERR_HIP; }
+    if (launch_stem_fused(s, img, w_stem, bias, y, N, H, W, dt)) { mcg_set_error("stem_fused launch failed"); return MCG_ERR_HIP; }
     return MCG_OK;
   }
   if (dt == MCG_F16X3 && ctx.stem_fused) {  // the f16x3 form of the same kernel; bit-identical to the three launches below
@@ -385,9 +385,7 @@ int stem_forward_ctx(hipStream_t s, mcg_dtype dt, const float* img, const void* 
   char* packed = (char*)ws;
   char* conv = packed + (((size_t)N * Hp * Wp * 4 * es + 255) / 256) * 256;
   const long long npix = (long long)N * Hp * Wp;
-  if (dt == MCG_BF16) hipLaunchKernelGGL(stem_pack_kernel<bf16_t>, dim3(grid_for(npix, 256)), dim3(256), 0, s, img, (bf16_t*)packed, N, H, W, Hp, Wp);
-  else if (dt == MCG_F16) hipLaunchKernelGGL(stem_pack_kernel<f16_t>, dim3(grid_for(npix, 256)), dim3(256), 0, s, img, (f16_t*)packed, N, H, W, Hp, Wp);
-  else hipLaunchKernelGGL(stem_pack_kernel<float>, dim3(grid_for(npix, 256)), dim3(256), 0, s, img, (float*)packed, N, H, W, Hp, Wp);
+  dispatch_elem(dt, [&](auto e) { hipLaunchKernelGGL(stem_pack_kernel<decltype(e)>, dim3(grid_for(npix, 256)), dim3(256), 0, s, img, (decltype(e)*)packed, N, H, W, Hp, Wp); });
   MCG_CHECK_LAUNCH("stem_pack");
   IgemmParams p;
   memset(&p, 0, sizeof(p));
@@ -399,9 +397,10 @@ int stem_forward_ctx(hipStream_t s, mcg_dtype dt, const float* img, const void* 
   MCG_TRY(launch_igemm(s, dt, p, 1, ctx));
   const int Ho = (Hc + 2 - 3) / 2 + 1, Wo = (Wc + 2 - 3) / 2 + 1;
   const long long nchunks = (long long)N * Ho * Wo * (64 / (16 / (int)es));
-  if (dt == MCG_BF16) hipLaunchKernelGGL(maxpool3x3s2_kernel<bf16_t>, dim3(grid_for(nchunks, 256)), dim3(256), 0, s, (const bf16_t*)conv, (bf16_t*)y, N, Hc, Wc, 64, Ho, Wo);
-  else if (dt == MCG_F16) hipLaunchKernelGGL(maxpool3x3s2_kernel<f16_t>, dim3(grid_for(nchunks, 256)), dim3(256), 0, s, (const f16_t*)conv, (f16_t*)y, N, Hc, Wc, 64, Ho, Wo);
-  else hipLaunchKernelGGL(maxpool3x3s2_kernel<float>, dim3(grid_for(nchunks, 256)), dim3(256), 0, s, (const float*)conv, (float*)y, N, Hc, Wc, 64, Ho, Wo);
+  dispatch_elem(dt, [&](auto e) {
+    using T = decltype(e);
+    hipLaunchKernelGGL(maxpool3x3s2_kernel<T>, dim3(grid_for(nchunks, 256)), dim3(256), 0, s, (const T*)conv, (T*)y, N, Hc, Wc, 64, Ho, Wo);
+  });
   MCG_CHECK_LAUNCH("maxpool");
   return MCG_OK;
 }
@@ -442,18 +441,14 @@ __global__ void nhwc_to_nchw_kernel(const T* __restrict__ src, float* __restrict
 extern "C" int mcg_nchw_to_nhwc(mcg_stream s, mcg_dtype dt, const float* src, void* dst, int N, int C, int H, int W) {
   MCG_CHECK_ARG(src && dst && N > 0 && C > 0 && H > 0 && W > 0, "mcg_nchw_to_nhwc: bad argument");
   dim3 grid((H * W + 31) / 32, (C + 31) / 32, N);
-  if (dt == MCG_BF16) hipLaunchKernelGGL(nchw_to_nhwc_kernel<bf16_t>, grid, dim3(256), 0, (hipStream_t)s, src, (bf16_t*)dst, C, H * W);
-  else if (dt == MCG_F16) hipLaunchKernelGGL(nchw_to_nhwc_kernel<f16_t>, grid, dim3(256), 0, (hipStream_t)s, src, (f16_t*)dst, C, H * W);
-  else hipLaunchKernelGGL(nchw_to_nhwc_kernel<float>, grid, dim3(256), 0, (hipStream_t)s, src, (float*)dst, C, H * W);
+  dispatch_elem(dt, [&](auto e) { hipLaunchKernelGGL(nchw_to_nhwc_kernel<decltype(e)>, grid, dim3(256), 0, (hipStream_t)s, src, (decltype(e)*)dst, C, H * W); });
   MCG_CHECK_LAUNCH("nchw_to_nhwc");
   return MCG_OK;
 }
 extern "C" int mcg_nhwc_to_nchw(mcg_stream s, mcg_dtype dt, const void* src, float* dst, int N, int C, int H, int W) {
   MCG_CHECK_ARG(src && dst && N > 0 && C > 0 && H > 0 && W > 0, "mcg_nhwc_to_nchw: bad argument");
   dim3 grid((H * W + 31) / 32, (C + 31) / 32, N);
-  if (dt == MCG_BF16) hipLaunchKernelGGL(nhwc_to_nchw_kernel<bf16_t>, grid, dim3(256), 0, (hipStream_t)s, (const bf16_t*)src, dst, C, H * W);
-  else if (dt == MCG_F16) hipLaunchKernelGGL(nhwc_to_nchw_kernel<f16_t>, grid, dim3(256), 0, (hipStream_t)s, (const f16_t*)src, dst, C, H * W);
-  else hipLaunchKernelGGL(nhwc_to_nchw_kernel<float>, grid, dim3(256), 0, (hipStream_t)s, (const float*)src, dst, C, H * W);
+  dispatch_elem(dt, [&](auto e) { hipLaunchKernelGGL(nhwc_to_nchw_kernel<decltype(e)>, grid, dim3(256), 0, (hipStream_t)s, (const decltype(e)*)src, dst, C, H * W); });
   MCG_CHECK_LAUNCH("nhwc_to_nchw");
   return MCG_OK;
 }

@@ -251,6 +251,6 @@ static inline int launch_pw_pair_f(hipStream_t s, const PwPairParams& p) {
   else launch_pw_pair_t<F, 2, 2>(s, p);
   return hipGetLastError() == hipSuccess ? 0 : 1;
 }
-static inline int launch_pw_pair(hipStream_t s, const PwPairParams& p, bool fp16 = false) {
-  return fp16 ? launch_pw_pair_f<f16_t>(s, p) : launch_pw_pair_f<bf16_t>(s, p);
+static inline int launch_pw_pair(hipStream_t s, const PwPairParams& p, mcg_dtype dt) {
+  return dispatch_elem16(dt, [&](auto e) { return launch_pw_pair_f<decltype(e)>(s, p); });
 }

@@ -213,8 +213,8 @@ static inline int launch_pw_single_f(hipStream_t s, const PwSingleParams& p, int
 // 88 MB of output.  The generic kernel spends it in prologues and epilogues (4 K-tiles per 256x128 output tile: 55 us, 1.6 TB/s of
 // writes).  Here: 128 slices of 256 columns, each slice's weights resident in the registers of a few workgroups ("walkers") that
 // split the token tiles between them; the tokens (688 KB) stream out of L2.  Same arithmetic as every pw_single launch: bit-identical.
-static inline int launch_pw_single(hipStream_t s, const PwSingleParams& p, int K, int N, int res_mode, bool fp16 = false) {
-  return fp16 ? launch_pw_single_f<f16_t>(s, p, K, N, res_mode) : launch_pw_single_f<bf16_t>(s, p, K, N, res_mode);
+static inline int launch_pw_single(hipStream_t s, const PwSingleParams& p, int K, int N, int res_mode, mcg_dtype dt) {
+  return dispatch_elem16(dt, [&](auto e) { return launch_pw_single_f<decltype(e)>(s, p, K, N, res_mode); });
 }
 static inline bool pw_dyn_applicable(int M) { return M >= 256 && (long long)M * 512 < MCG_DMA_MAX_BYTES; }
 template <typename F>
@@ -236,6 +236,6 @@ static inline int launch_pw_dyn_f(hipStream_t s, PwSingleParams p) {
   hipLaunchKernelGGL((pw_single_kernel<F, KS, TPW, 0, NSPLIT>), dim3(walkers * NSPLIT), dim3(256), kLds, s, p);
   return hipGetLastError() == hipSuccess ? 0 : 1;
 }
-static inline int launch_pw_dyn(hipStream_t s, const PwSingleParams& p, bool fp16 = false) {
-  return fp16 ? launch_pw_dyn_f<f16_t>(s, p) : launch_pw_dyn_f<bf16_t>(s, p);
+static inline int launch_pw_dyn(hipStream_t s, const PwSingleParams& p, mcg_dtype dt) {
+  return dispatch_elem16(dt, [&](auto e) { return launch_pw_dyn_f<decltype(e)>(s, p); });
 }

@@ -161,15 +161,9 @@ int launch_roi_align(hipStream_t s, mcg_dtype dt, const void* const feats[4], co
   }
   const int epc = mcg_is16(dt) ? 8 : 4;
   MCG_CHECK_ARG(C % epc == 0 && C / epc <= 256 && 256 % (C / epc) == 0, "roi_align: unsupported channel count %d", C);
-  if (dt == MCG_BF16)
-    hipLaunchKernelGGL(roi_align_kernel<bf16_t>, dim3(num_boxes), dim3(256), 0, s, lv, C, boxes, boxes_per_frame, frame_of, pyramid_frames,
-                       (bf16_t*)out, levels_out, 56.f);
-  else if (dt == MCG_F16)
-    hipLaunchKernelGGL(roi_align_kernel<f16_t>, dim3(num_boxes), dim3(256), 0, s, lv, C, boxes, boxes_per_frame, frame_of, pyramid_frames,
-                       (f16_t*)out, levels_out, 56.f);
-  else
-    hipLaunchKernelGGL(roi_align_kernel<float>, dim3(num_boxes), dim3(256), 0, s, lv, C, boxes, boxes_per_frame, frame_of, pyramid_frames,
-                       (float*)out, levels_out, 56.f);
+  dispatch_elem(dt, [&](auto e) {
+    hipLaunchKernelGGL(roi_align_kernel<decltype(e)>, dim3(num_boxes), dim3(256), 0, s, lv, C, boxes, boxes_per_frame, frame_of, pyramid_frames, (decltype(e)*)out, levels_out, 56.f);
+  });
   MCG_CHECK_LAUNCH("roi_align");
   return MCG_OK;
 }

@@ -158,16 +158,16 @@ __global__ __launch_bounds__(256) void stem_fused_kernel(const float* __restrict
   }
 }
 
-static inline int launch_stem_fused(hipStream_t s, const float* img, const void* w_stem, const float* bias, void* y, int N, int H, int W, bool fp16 = false) {
+static inline int launch_stem_fused(hipStream_t s, const float* img, const void* w_stem, const float* bias, void* y, int N, int H, int W, mcg_dtype dt) {
   const int Hc = H / 2, Wc = W / 2, Ho = (Hc + 2 - 3) / 2 + 1, Wo = (Wc + 2 - 3) / 2 + 1;
   const int tiles_y = (Ho + stemf::PT - 1) / stemf::PT, tiles_x = (Wo + stemf::PT - 1) / stemf::PT;
   const long long total = (long long)tiles_y * tiles_x * N;
   if (total > 0x7fffffffLL) return 1;
   const int grid = (int)(total < 256 * 3 ? total : 256 * 3);  // persistent: 3 workgroups per CU (LDS-limited)
-  if (fp16) hipLaunchKernelGGL(stem_fused_kernel<f16_t>, dim3(grid), dim3(256), 0, s, img, (const bf16_t*)w_stem, bias, (bf16_t*)y, H, W, Hc, Wc, Ho, Wo, tiles_x,
-                               tiles_y * tiles_x, (int)total);
-  else hipLaunchKernelGGL(stem_fused_kernel<bf16_t>, dim3(grid), dim3(256), 0, s, img, (const bf16_t*)w_stem, bias, (bf16_t*)y, H, W, Hc, Wc, Ho, Wo, tiles_x,
-                          tiles_y * tiles_x, (int)total);
+  dispatch_elem16(dt, [&](auto e) {   // both instantiations take bf16_t-typed pointers (2-byte storage either way)
+    hipLaunchKernelGGL(stem_fused_kernel<decltype(e)>, dim3(grid), dim3(256), 0, s, img, (const bf16_t*)w_stem, bias, (bf16_t*)y, H, W, Hc, Wc, Ho, Wo,
+                       tiles_x, tiles_y * tiles_x, (int)total);
+  });
   return hipGetLastError() == hipSuccess ? 0 : 1;
 }
 

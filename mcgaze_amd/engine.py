@@ -139,32 +139,23 @@ def stem(img, w_stem, bias, dtype, flags=0, split=False):
 
 def roi_align(feats, boxes, strides=(4, 8, 16, 32)):
     """feats: 4 NHWC levels; boxes [N,P,4] f32 -> ([N*P,49,C], levels int32 [N*P]).  mcg_roi_align."""
-    _require_gpu()
-    lib = L.load()
-    N, P = boxes.shape[:2]
-    Cc = feats[0].shape[-1]
-    out = torch.empty(N * P, 49, Cc, dtype=feats[0].dtype, device=boxes.device)
-    lv = torch.empty(N * P, dtype=torch.int32, device=boxes.device)
-    fp = (C.c_void_p * 4)(*[f.data_ptr() for f in feats])
-    fh = (C.c_int * 4)(*[f.shape[1] for f in feats])
-    fw = (C.c_int * 4)(*[f.shape[2] for f in feats])
-    st = (C.c_int * 4)(*strides)
-    b = boxes.contiguous().float()
-    L.check(lib.mcg_roi_align(_stream(), _code(feats[0].dtype), fp, fh, fw, st, Cc, _ptr(b), N * P, P, _ptr(out), _ptr(lv)), 'mcg_roi_align')
-    return out, lv
+    return roi_align_indexed(feats, boxes, None, strides)
 
 
 def roi_align_indexed(feats, boxes, frame_of, strides=(4, 8, 16, 32)):
     """roi_align over window frames gathered from a pyramid store: box row r reads pyramid row frame_of[r // P].
     feats: 4 NHWC levels [K,h,w,C]; boxes [N,P,4] f32; frame_of: N row indices (host, range-checked) -> ([N*P,49,C], levels).
-    mcg_roi_align_indexed."""
+    mcg_roi_align_indexed.  frame_of None: frame n reads row n (roi_align)."""
     _require_gpu()
     lib = L.load()
     N, P = boxes.shape[:2]
     K, Cc = feats[0].shape[0], feats[0].shape[-1]
-    table = torch.from_numpy(check_frame_table(frame_of, K, 1)).to(boxes.device)
-    if table.numel() != N:
-        raise L.McgError(f'frame_of holds {table.numel()} entries for {N} frames of boxes')
+    name, gather = 'mcg_roi_align', ()
+    if frame_of is not None:
+        table = torch.from_numpy(check_frame_table(frame_of, K, 1)).to(boxes.device)
+        if table.numel() != N:
+            raise L.McgError(f'frame_of holds {table.numel()} entries for {N} frames of boxes')
+        name, gather = 'mcg_roi_align_indexed', (_ptr(table), K)
     out = torch.empty(N * P, 49, Cc, dtype=feats[0].dtype, device=boxes.device)
     lv = torch.empty(N * P, dtype=torch.int32, device=boxes.device)
     fp = (C.c_void_p * 4)(*[f.data_ptr() for f in feats])
@@ -172,21 +163,27 @@ def roi_align_indexed(feats, boxes, frame_of, strides=(4, 8, 16, 32)):
     fw = (C.c_int * 4)(*[f.shape[2] for f in feats])
     st = (C.c_int * 4)(*strides)
     b = boxes.contiguous().float()
-    L.check(lib.mcg_roi_align_indexed(_stream(), _code(feats[0].dtype), fp, fh, fw, st, Cc, _ptr(b), N * P, P, _ptr(table), K, _ptr(out), _ptr(lv)),
-            'mcg_roi_align_indexed')
+    L.check(getattr(lib, name)(_stream(), _code(feats[0].dtype), fp, fh, fw, st, Cc, _ptr(b), N * P, P, *gather, _ptr(out), _ptr(lv)), name)
     return out, lv
+
+
+def _flat_ints(seq, must, must_int, nonempty):
+    """A sequence (or CPU tensor) -> 1-D numpy array of integers; McgError(must ...) if it is no flat sequence, McgError(must_int ...) if
+    it is not one of integers (or is empty where nonempty)."""
+    t = seq.numpy() if isinstance(seq, torch.Tensor) else seq
+    try:
+        a = np.asarray(t)
+    except Exception as ex:                          # ragged input
+        raise L.McgError(f'{must} ({ex})')
+    if a.ndim != 1 or (nonempty and a.size == 0) or (a.size and not np.issubdtype(a.dtype, np.integer)):
+        raise L.McgError(f'{must_int} (got {a.dtype} of shape {a.shape})')
+    return a
 
 
 def check_frame_table(frame_of, pyramid_frames, clip_length):
     """Host-side check of a window-frame -> pyramid-row table: a sequence (or CPU tensor) of integers, a positive multiple of
     clip_length long, every entry in [0, pyramid_frames).  -> int32 numpy array.  McgError otherwise (nothing reaches the device)."""
-    t = frame_of.numpy() if isinstance(frame_of, torch.Tensor) else frame_of
-    try:
-        a = np.asarray(t)
-    except Exception as ex:                          # ragged input
-        raise L.McgError(f'frame_of must be a flat sequence of row indices ({ex})')
-    if a.ndim != 1 or (a.size and not np.issubdtype(a.dtype, np.integer)):
-        raise L.McgError(f'frame_of must be a flat sequence of integer row indices (got {a.dtype} of shape {a.shape})')
+    a = _flat_ints(frame_of, 'frame_of must be a flat sequence of row indices', 'frame_of must be a flat sequence of integer row indices', False)
     if clip_length < 1 or a.size == 0 or a.size % clip_length:
         raise L.McgError(f'frame_of holds {a.size} entries, not a positive multiple of clip_length={clip_length}')
     if pyramid_frames < 1 or int(a.min()) < 0 or int(a.max()) >= pyramid_frames:
@@ -199,13 +196,7 @@ def check_clip_lengths(lengths, num_frames):
     (None: any sum).
     -> int32 numpy array clip_start [len(lengths) + 1] (0, cumulative sums: the table the mcg_*_ragged entry points take).
     McgError otherwise (nothing reaches the device)."""
-    t = lengths.numpy() if isinstance(lengths, torch.Tensor) else lengths
-    try:
-        a = np.asarray(t)
-    except Exception as ex:
-        raise L.McgError(f'clip lengths must be a flat sequence of integers ({ex})')
-    if a.ndim != 1 or a.size == 0 or not np.issubdtype(a.dtype, np.integer):
-        raise L.McgError(f'clip lengths must be a non-empty flat sequence of integers (got {a.dtype} of shape {a.shape})')
+    a = _flat_ints(lengths, 'clip lengths must be a flat sequence of integers', 'clip lengths must be a non-empty flat sequence of integers', True)
     if int(a.min()) < 1:
         raise L.McgError(f'every clip must hold at least one frame (got a length of {int(a.min())})')
     total = int(a.astype(np.int64).sum())
@@ -228,20 +219,42 @@ class ClipTable:
         self.table = torch.from_numpy(self.start).to(self.device)
 
 
-def _clips(clip_length, num_frames, device):
-    """clip_length of forward / decode / stage_forward -> None for an int (one length for every clip: the mcg_* entry point), else
-    (device int32 clip_start, num_clips, max_clip_length): the three arguments of the mcg_*_ragged one.  A sequence of lengths is checked
-    (McgError before anything reaches the device) and uploaded pinned + non-blocking on the current stream: a pageable upload would make
-    the host wait for the work already queued (harness.py, upload)."""
-    if isinstance(clip_length, (int, np.integer)):
-        return None
-    if isinstance(clip_length, ClipTable):
-        ct = clip_length
-        if ct.num_frames != num_frames or ct.device != torch.device(device):
-            raise L.McgError(f'the ClipTable holds {ct.num_frames} frames on {ct.device}, the batch {num_frames} on {device}')
-        return ct.table, ct.num_clips, ct.max_len
-    start = check_clip_lengths(clip_length, num_frames)
-    return torch.from_numpy(start).pin_memory().to(device, non_blocking=True), start.size - 1, int(np.diff(start).max())
+def _upload_table(table, device):
+    """A small host table (numpy array or CPU tensor: clip starts, frame rows, img_shape, scale_factor) -> device tensor, pinned +
+    non-blocking on the current stream: a pageable upload would make the host wait for the work already queued (the host then idles for
+    the previous batch instead of preparing the next).  A CPU ``device`` (the oracle behind harness.run_videos) gets the tensor itself."""
+    t = torch.as_tensor(table)
+    return t.pin_memory().to(device, non_blocking=True) if torch.device(device).type == 'cuda' else t.to(device)
+
+
+def _outputs(N, device, alloc=torch.empty):
+    """The result dict of forward / decode over N frames: f32 device tensors."""
+    return dict(gaze=alloc(4, N, 3, dtype=torch.float32, device=device), boxes=alloc(N, 3, 4, dtype=torch.float32, device=device),
+                scores=alloc(N, 3, dtype=torch.float32, device=device))
+
+
+class _Clips:
+    """clip_length of forward / decode / stage_forward, as the C-ABI takes it.  An int (one length for every clip): ``args`` is that int,
+    for the mcg_* entry point.  A sequence of lengths or a ClipTable: ``args`` is (device int32 clip_start, num_clips, max_clip_length) for
+    the mcg_*_ragged one (which rejects a null table).  A sequence is checked (McgError before anything reaches the device) and uploaded
+    per call (_upload_table); ``pick(fixed, ragged)`` names the entry point that takes ``args`` in the clip position."""
+
+    def __init__(self, clip_length, num_frames, device):
+        self.ragged = not isinstance(clip_length, (int, np.integer))
+        if not self.ragged:
+            self.args = (clip_length,)
+        elif isinstance(clip_length, ClipTable):
+            ct = clip_length
+            if ct.num_frames != num_frames or ct.device != torch.device(device):
+                raise L.McgError(f'the ClipTable holds {ct.num_frames} frames on {ct.device}, the batch {num_frames} on {device}')
+            self.table, self.args = ct.table, (_ptr(ct.table), ct.num_clips, ct.max_len)
+        else:
+            start = check_clip_lengths(clip_length, num_frames)
+            self.table = _upload_table(start, device)           # held: args carries its address only
+            self.args = (_ptr(self.table), start.size - 1, int(np.diff(start).max()))
+
+    def pick(self, fixed, ragged):
+        return ragged if self.ragged else fixed
 
 
 def _table(d, keys):
@@ -261,16 +274,11 @@ def stage_forward(stage_w, roi_feat, obj, boxes, clip_length, stds=(0.5, 0.5, 1.
     boxes_out = torch.empty(N, 3, 4, dtype=torch.float32, device=obj.device)
     cls = torch.empty(N, 3, dtype=torch.float32, device=obj.device)
     sd = (C.c_float * 4)(*stds)
-    clips = _clips(clip_length, N, obj.device)
-    if clips is not None:
-        table, B, Tmax = clips
-        L.check(lib.mcg_stage_forward_ragged(_stream(), dt, _table(stage_w, L.STAGE_KEYS), _ptr(roi_feat.contiguous()), _ptr(obj.contiguous()),
-                                             _ptr(boxes.contiguous().float()), N, _ptr(table), B, Tmax, _ptr(obj_out), _ptr(boxes_out), _ptr(cls), sd,
-                                             _ptr(ws), ws.numel(), flags), 'mcg_stage_forward_ragged')
-        return obj_out, boxes_out, cls
-    L.check(lib.mcg_stage_forward(_stream(), dt, _table(stage_w, L.STAGE_KEYS), _ptr(roi_feat.contiguous()), _ptr(obj.contiguous()),
-                                  _ptr(boxes.contiguous().float()), N, clip_length, _ptr(obj_out), _ptr(boxes_out), _ptr(cls), sd,
-                                  _ptr(ws), ws.numel(), flags), 'mcg_stage_forward')
+    clips = _Clips(clip_length, N, obj.device)
+    name = clips.pick('mcg_stage_forward', 'mcg_stage_forward_ragged')
+    L.check(getattr(lib, name)(_stream(), dt, _table(stage_w, L.STAGE_KEYS), _ptr(roi_feat.contiguous()), _ptr(obj.contiguous()),
+                               _ptr(boxes.contiguous().float()), N, *clips.args, _ptr(obj_out), _ptr(boxes_out), _ptr(cls), sd, _ptr(ws), ws.numel(),
+                               flags), name)
     return obj_out, boxes_out, cls
 
 
@@ -329,7 +337,6 @@ class HipEngine:
         with torch.cuda.device(self.device):   # the engine's side streams and events belong to THIS device
             L.check(self.lib.mcg_engine_create(C.byref(self._handle), C.byref(mw), self.code), 'mcg_engine_create')
         self._ws = None
-        self._ws_key = None
         self._dec_ws = None
 
     def set_option(self, name, value):
@@ -385,15 +392,15 @@ class HipEngine:
             self.lib.mcg_engine_destroy(h)
             self._handle = None
 
+    def _grown(self, name, need):
+        """The engine's grow-only buffer ``name`` (_ws: whole forward; _dec_ws: decode), at least ``need`` bytes."""
+        if getattr(self, name) is None or getattr(self, name).numel() < need:
+            setattr(self, name, None)                  # release the old block before asking for the larger one
+            setattr(self, name, _ws(need, self.device))
+        return getattr(self, name)
+
     def _workspace(self, N, H, W, chunk):
-        key = (N, H, W, chunk)
-        need = self.lib.mcg_engine_workspace_bytes(self._handle, N, H, W, chunk)
-        if self._ws is None or self._ws.numel() < need or self._ws_key != key:
-            if self._ws is None or self._ws.numel() < need:
-                self._ws = None
-                self._ws = _ws(need, self.device)
-            self._ws_key = key
-        return self._ws
+        return self._grown('_ws', self.lib.mcg_engine_workspace_bytes(self._handle, N, H, W, chunk))
 
     def _check_img(self, img):
         if not (img.is_cuda and img.device == self.device and img.dtype == torch.float32 and img.is_contiguous() and img.dim() == 4):
@@ -449,7 +456,7 @@ class HipEngine:
         dev_table = isinstance(frame_of, torch.Tensor) and frame_of.device.type != 'cpu'
         ragged = not isinstance(clip_length, (int, np.integer))
         host = None if dev_table else check_frame_table(frame_of, K, 1 if ragged else clip_length)
-        clips = _clips(clip_length, frame_of.numel() if dev_table else host.size, self.device)
+        clips = _Clips(clip_length, frame_of.numel() if dev_table else host.size, self.device)
         self._check_pyramid(pyramid)
         with torch.cuda.device(self.device):
             if dev_table:
@@ -459,27 +466,15 @@ class HipEngine:
                 if not ragged and (table.numel() == 0 or table.numel() % clip_length):
                     raise L.McgError(f'frame_of holds {table.numel()} entries, not a positive multiple of clip_length={clip_length}')
             else:
-                # pinned + non-blocking: a pageable upload would make the host wait for the work already queued (harness.py, upload)
-                table = torch.from_numpy(host).pin_memory().to(self.device, non_blocking=True)
+                table = _upload_table(host, self.device)
             N = table.numel()
-            if out is None:
-                out = dict(gaze=torch.empty(4, N, 3, dtype=torch.float32, device=self.device),
-                           boxes=torch.empty(N, 3, 4, dtype=torch.float32, device=self.device),
-                           scores=torch.empty(N, 3, dtype=torch.float32, device=self.device))
+            out = _outputs(N, self.device) if out is None else out
             hw = self.img_hw_tensor(img_hw, K)
-            need = self.lib.mcg_decoder_workspace_bytes(self._handle, N)
-            if self._dec_ws is None or self._dec_ws.numel() < need:
-                self._dec_ws = None
-                self._dec_ws = _ws(need, self.device)
-            ws = self._dec_ws
+            ws = self._grown('_dec_ws', self.lib.mcg_decoder_workspace_bytes(self._handle, N))
             tab = (C.c_void_p * 4)(*[p.data_ptr() for p in pyramid])
-            if ragged:
-                L.check(self.lib.mcg_decoder_forward_ragged(self._handle, _stream(self.device), tab, K, _ptr(table), N, _ptr(clips[0]), clips[1], clips[2], H, W, _ptr(hw), _ptr(out['gaze']), _ptr(out['boxes']),
-                                                            _ptr(out['scores']), _ptr(ws), ws.numel()), 'mcg_decoder_forward_ragged')
-                return out
-            L.check(self.lib.mcg_decoder_forward_indexed(self._handle, _stream(self.device), tab, K, _ptr(table), N, clip_length, H, W, _ptr(hw),
-                                                         _ptr(out['gaze']), _ptr(out['boxes']), _ptr(out['scores']), _ptr(ws), ws.numel()),
-                    'mcg_decoder_forward_indexed')
+            name = clips.pick('mcg_decoder_forward_indexed', 'mcg_decoder_forward_ragged')
+            L.check(getattr(self.lib, name)(self._handle, _stream(self.device), tab, K, _ptr(table), N, *clips.args, H, W, _ptr(hw), _ptr(out['gaze']),
+                                            _ptr(out['boxes']), _ptr(out['scores']), _ptr(ws), ws.numel()), name)
         return out
 
     def forward(self, img, clip_length, img_hw=None, chunk_frames=0, out=None):
@@ -489,21 +484,14 @@ class HipEngine:
         Returns dict(gaze [4,N,3], boxes [N,3,4], scores [N,3]) -- f32 device tensors."""
         self._check_img(img)
         N, _, H, W = img.shape
-        clips = _clips(clip_length, N, self.device)
+        clips = _Clips(clip_length, N, self.device)
+        name = clips.pick('mcg_clip_forward', 'mcg_clip_forward_ragged')
         with torch.cuda.device(self.device):
             ws = self._workspace(N, H, W, chunk_frames)
-            if out is None:
-                out = dict(gaze=torch.empty(4, N, 3, dtype=torch.float32, device=self.device),
-                           boxes=torch.empty(N, 3, 4, dtype=torch.float32, device=self.device),
-                           scores=torch.empty(N, 3, dtype=torch.float32, device=self.device))
+            out = _outputs(N, self.device) if out is None else out
             hw = self.img_hw_tensor(img_hw, N)
-            if clips is not None:
-                L.check(self.lib.mcg_clip_forward_ragged(self._handle, _stream(self.device), _ptr(img), N, _ptr(clips[0]), clips[1], clips[2], H, W, _ptr(hw), chunk_frames, _ptr(out['gaze']),
-                                                         _ptr(out['boxes']), _ptr(out['scores']), _ptr(ws), ws.numel()), 'mcg_clip_forward_ragged')
-                return out
-            L.check(self.lib.mcg_clip_forward(self._handle, _stream(self.device), _ptr(img), N, clip_length, H, W, _ptr(hw), chunk_frames,
-                                              _ptr(out['gaze']), _ptr(out['boxes']), _ptr(out['scores']), _ptr(ws), ws.numel()),
-                    'mcg_clip_forward')
+            L.check(getattr(self.lib, name)(self._handle, _stream(self.device), _ptr(img), N, *clips.args, H, W, _ptr(hw), chunk_frames, _ptr(out['gaze']),
+                                            _ptr(out['boxes']), _ptr(out['scores']), _ptr(ws), ws.numel()), name)
         return out
 
     def img_hw_tensor(self, img_hw, N):
@@ -538,8 +526,7 @@ class GraphedForward:
             self.hw = torch.zeros(num_frames, 2, dtype=torch.int32, device=dev) if with_img_hw else None
             if self.hw is not None:
                 self.hw[:, 0], self.hw[:, 1] = H, W
-            self.out = dict(gaze=torch.zeros(4, num_frames, 3, device=dev), boxes=torch.zeros(num_frames, 3, 4, device=dev),
-                            scores=torch.zeros(num_frames, 3, device=dev))
+            self.out = _outputs(num_frames, dev, torch.zeros)
             side = torch.cuda.Stream(device=dev)
             side.wait_stream(torch.cuda.current_stream(dev))
             with torch.cuda.stream(side):          # eager warm-up on the capture stream: workspace allocation, side-stream probe
@@ -595,7 +582,7 @@ class PipelinedRunner:
         dev, lib, h = engine.device, engine.lib, engine._handle
         if not isinstance(clip_length, (int, np.integer, ClipTable)):
             self.T = ClipTable(clip_length, dev)
-        self.clips = _clips(self.T, num_frames, dev)
+        self.clips = _Clips(self.T, num_frames, dev)
         # the decoder's short launches get the high-priority queue so they slot in between the trunk's long kernels
         self.sa, self.sb = pipeline_streams(dev, decoder_priority)
         self.slots = [_ws(lib.mcg_deferred_pyramid_bytes(h, num_frames, H, W), dev) for _ in range(2)]
@@ -629,15 +616,10 @@ class PipelinedRunner:
                 'mcg_backbone_fpn_forward_deferred')
         self.trunk_done[slot].record(self.sa)
         self.sb.wait_event(self.trunk_done[slot])
-        if self.clips is not None:
-            L.check(lib.mcg_decoder_forward_deferred_ragged(e._handle, C.c_void_p(self.sb.cuda_stream), _ptr(self.slots[slot]), self.slots[slot].numel(),
-                                                            self.N, _ptr(self.clips[0]), self.clips[1], self.clips[2], self.H, self.W, _ptr(img_hw),
-                                                            _ptr(out['gaze']), _ptr(out['boxes']), _ptr(out['scores']), _ptr(self.dec_ws),
-                                                            self.dec_ws.numel()), 'mcg_decoder_forward_deferred_ragged')
-        else:
-            L.check(lib.mcg_decoder_forward_deferred(e._handle, C.c_void_p(self.sb.cuda_stream), _ptr(self.slots[slot]), self.slots[slot].numel(),
-                                                     self.N, self.T, self.H, self.W, _ptr(img_hw), _ptr(out['gaze']), _ptr(out['boxes']),
-                                                     _ptr(out['scores']), _ptr(self.dec_ws), self.dec_ws.numel()), 'mcg_decoder_forward_deferred')
+        name = self.clips.pick('mcg_decoder_forward_deferred', 'mcg_decoder_forward_deferred_ragged')
+        L.check(getattr(lib, name)(e._handle, C.c_void_p(self.sb.cuda_stream), _ptr(self.slots[slot]), self.slots[slot].numel(), self.N, *self.clips.args,
+                                   self.H, self.W, _ptr(img_hw), _ptr(out['gaze']), _ptr(out['boxes']), _ptr(out['scores']), _ptr(self.dec_ws),
+                                   self.dec_ws.numel()), name)
         self.dec_done[slot].record(self.sb)
         self.used[slot] = True
         self.k += 1

@@ -20,6 +20,8 @@ import os
 import numpy as np
 import torch
 
+from .engine import _upload_table
+
 CLUES = ('face', 'eyes', 'head')
 last_run_stats = {}       # run_annotation's frame-cache counters of the last call (tools/dataset_throughput.py prints them); trunk_frames of run_videos
 
@@ -45,33 +47,40 @@ def _host(t):
     return t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)
 
 
+def merge_window(det, fused, others, base, first, window, d, f, o, thr):
+    """One step of the overlap merge (tools/test_gaze360_gaze.py:129-206): window = (start, stop, overlap) of the plan with outputs
+    d [T,3,5], f [T,3], o [T,3,3] (torch tensors or numpy arrays, f32) into the per-frame buffers det / fused / others, whose row 0 is frame
+    ``base``; windows come in plan order, ``first`` marks the plan's first.  Host arithmetic in f32 -- sums and halvings, exactly rounded,
+    the same bits the reference's torch expressions give."""
+    start, stop, overlap = window
+    d, f, o = _host(d), _host(f), _host(o)
+    half = np.float32(2)
+    low = d[..., 4:] < thr
+    d = np.concatenate([np.where(low, np.float32(0), d[..., :4]), d[..., 4:]], axis=-1)      # boxes of low-score detections are zeroed (:140-150)
+    if first:
+        det[start - base:stop - base], fused[start - base:stop - base], others[start - base:stop - base] = d, f, o
+        return
+    # overlapping frames: the last `overlap` stored frames against the first `overlap` frames of this window
+    ov = slice(start - base, start + overlap - base)
+    old_d, cur_d = det[ov], d[:overlap]
+    bad = (old_d[..., 4:] < thr) | low[:overlap]
+    det[ov, :, :4] = np.where(bad, np.float32(0), (old_d[..., :4] + cur_d[..., :4]) / half)
+    det[ov, :, 4:] = (old_d[..., 4:] + cur_d[..., 4:]) / half
+    fused[ov] = (fused[ov] + f[:overlap]) / half
+    others[ov] = (others[ov] + o[:overlap]) / half
+    new = slice(start + overlap - base, stop - base)
+    det[new], fused[new], others[new] = d[overlap:], f[overlap:], o[overlap:]
+
+
 def merge_video(windows, clip_outputs, person_threshold=0.5):
     """windows from plan_windows; clip_outputs[i] = (det_bboxes [T,3,5], fused [T,3], others [T,3,3]) of window i (torch tensors or
-    numpy arrays, f32).  Returns per-frame numpy arrays (det_bboxes [L,3,5], fused [L,3], others [L,3,3]).
-    tools/test_gaze360_gaze.py:129-206.  Host arithmetic in f32 -- sums and halvings, exactly rounded, the same bits the reference's
-    torch expressions give; the windows of a video tile it from frame 0 with the last one flush to the end, so frame t of window
-    (start, stop) lands at row start + t."""
+    numpy arrays, f32).  Returns per-frame numpy arrays (det_bboxes [L,3,5], fused [L,3], others [L,3,3]): merge_window over the plan;
+    the windows of a video tile it from frame 0 with the last one flush to the end, so frame t of window (start, stop) lands at row
+    start + t."""
     L = windows[-1][1]
     det, fused, others = np.empty((L, 3, 5), np.float32), np.empty((L, 3), np.float32), np.empty((L, 3, 3), np.float32)
-    thr = np.float32(person_threshold)
-    half = np.float32(2)
-    for i, ((start, stop, overlap), (d, f, o)) in enumerate(zip(windows, clip_outputs)):
-        d, f, o = _host(d), _host(f), _host(o)
-        low = d[..., 4:] < thr
-        d = np.concatenate([np.where(low, np.float32(0), d[..., :4]), d[..., 4:]], axis=-1)      # boxes of low-score detections are zeroed (:140-150)
-        if i == 0:
-            det[:stop], fused[:stop], others[:stop] = d, f, o
-            continue
-        # overlapping frames: the last `overlap` stored frames against the first `overlap` frames of this window
-        ov = slice(start, start + overlap)
-        old_d, cur_d = det[ov], d[:overlap]
-        bad = (old_d[..., 4:] < thr) | low[:overlap]
-        det[ov, :, :4] = np.where(bad, np.float32(0), (old_d[..., :4] + cur_d[..., :4]) / half)
-        det[ov, :, 4:] = (old_d[..., 4:] + cur_d[..., 4:]) / half
-        fused[ov] = (fused[ov] + f[:overlap]) / half
-        others[ov] = (others[ov] + o[:overlap]) / half
-        new = slice(start + overlap, stop)
-        det[new], fused[new], others[new] = d[overlap:], f[overlap:], o[overlap:]
+    for i, (window, (d, f, o)) in enumerate(zip(windows, clip_outputs)):
+        merge_window(det, fused, others, 0, i == 0, window, d, f, o, np.float32(person_threshold))
     return det, fused, others
 
 
@@ -99,6 +108,20 @@ def result_file_name(config_path, json_path):
 FUSED_ATTN_MAX_T = 10     # longest clip the fused attention block takes (3 T <= 32 token rows: one MFMA tile, csrc/attn_block.hpp)
 
 
+def bucket_key(H, W, T, mixed):
+    """The batch a clip of T frames of H x W joins.  mixed (clips of different lengths in one ragged call): (H, W, longest-clip class), the
+    classes T <= 10 and T > 10, so that one long clip does not push a batch of short ones off the fused attention block; else (T, H, W)."""
+    return (H, W, int(T > FUSED_ATTN_MAX_T)) if mixed else (T, H, W)
+
+
+def clip_outputs(out, scale=None):
+    """Engine output dict(gaze [4,n,3], boxes [n,3,4], scores [n,3]) -> (det [n,3,5] = box | score, fused [n,3], others [n,3,3]) on its
+    device: merge_video's layout.  scale (broadcastable to the boxes): rescale=True, every frame's boxes divided by its scale_factor
+    (multiclue_gaze_roi_head.py:360-363)."""
+    boxes = out['boxes'] if scale is None else out['boxes'] / scale
+    return torch.cat([boxes, out['scores'][..., None]], dim=-1), out['gaze'][0], out['gaze'][1:].permute(1, 0, 2)
+
+
 def _run_windows(engine, ids, plans, get_window, batch_clips, person_threshold, reuse_frames=False, mixed_lengths=False):
     """Core of run_videos / run_annotation, STREAMING: windows are visited in (video, window) order -- the reference's order, so the
     crop RNG draws inside ``get_window`` fall where upstream's do -- and dropped into per-(T, H, W) buckets; a bucket runs through
@@ -120,18 +143,11 @@ def _run_windows(engine, ids, plans, get_window, batch_clips, person_threshold, 
     pending = [len(p) for p in plans]
     records = [None] * len(plans)
 
-    keep = []                                          # pinned host tensors of the last flush: alive until their non-blocking copies ran
     inflight = collections.deque()                     # batches whose results are on their way to the host: (items (vi, wi, T), pinned buffer, event)
     spare = []                                         # pinned result buffers free for reuse
 
-    def upload(t):
-        # small per-batch tables (img_shape, scale_factor): pinned + non-blocking, so that the host does not wait for the device queue to
-        # drain (a pageable .to() did: the host then idled for the previous batch's forward instead of preparing the next)
-        if dev.type != 'cuda':
-            return t.to(dev)
-        p = t.pin_memory()
-        keep.append(p)
-        return p.to(dev, non_blocking=True)
+    def upload(t):                                     # small per-batch tables (img_shape, scale_factor)
+        return _upload_table(t, dev)
 
     def collect(leave):
         # results of finished batches -> per-window host arrays -> (once a video's last window is back) merge + record, all on the host:
@@ -186,7 +202,6 @@ def _run_windows(engine, ids, plans, get_window, batch_clips, person_threshold, 
             return
         Ts = [length_of(it) for it in items]         # default bucketing: all equal (the key's T)
         collect(2)
-        del keep[:max(0, len(keep) - 4)]
         if reuse_frames:
             out = decode_distinct(items, Ts)
         else:
@@ -194,13 +209,12 @@ def _run_windows(engine, ids, plans, get_window, batch_clips, person_threshold, 
             hw = None if items[0][3] is None else upload(torch.cat([torch.as_tensor(it[3], dtype=torch.int32).reshape(-1, 2) for it in items]))
             out = engine.forward(x, Ts if mixed_lengths else Ts[0], img_hw=hw)
             trunk[0] += x.shape[0]
-        boxes = out['boxes']
-        if items[0][4] is not None:   # rescale=True: every frame's boxes by its own scale_factor (multiclue_gaze_roi_head.py:360-363)
-            boxes = boxes / upload(torch.cat([torch.as_tensor(it[4], dtype=torch.float32) for it in items]))[:, None, :]
+        scale = None      # rescale=True: every frame's boxes by its own scale_factor
+        if items[0][4] is not None:
+            scale = upload(torch.cat([torch.as_tensor(it[4], dtype=torch.float32) for it in items]))[:, None, :]
         n = sum(Ts)
-        gaze = out['gaze']
-        packed = torch.cat([boxes.reshape(n, 3, 4), out['scores'].reshape(n, 3, 1)], dim=-1).reshape(n, 15)
-        packed = torch.cat([packed, gaze[0].reshape(n, 3), gaze[1:].permute(1, 0, 2).reshape(n, 9)], dim=1).to(torch.float32)
+        det, fused, others = clip_outputs(out, scale)
+        packed = torch.cat([det.reshape(n, 15), fused.reshape(n, 3), others.reshape(n, 9)], dim=1).to(torch.float32)   # ONE copy to the host
         who = [(it[0], it[1], T) for it, T in zip(items, Ts)]
         if dev.type != 'cuda':
             inflight.append((who, packed, None))
@@ -219,7 +233,7 @@ def _run_windows(engine, ids, plans, get_window, batch_clips, person_threshold, 
         for wi in range(len(plan)):
             x, hw, sc = get_window(vi, wi)
             T = plan[wi][1] - plan[wi][0]
-            key = (x.shape[-2], x.shape[-1], int(T > FUSED_ATTN_MAX_T)) if mixed_lengths else (T, x.shape[-2], x.shape[-1])
+            key = bucket_key(x.shape[-2], x.shape[-1], T, mixed_lengths)
             buckets.setdefault(key, []).append((vi, wi, x, hw, sc))
             if len(buckets[key]) >= batch_clips:
                 flush(key)
@@ -274,8 +288,6 @@ def run_annotation(engine, anno, root, pipeline, clip_len=7, stride=4, batch_cli
     order -- what a run sharded over several consumer processes needs to reproduce a single-process run record for record (the
     reference's single global generator makes its results depend on the shard layout).
     ``mixed_lengths``: as in run_videos -- windows of different lengths in one ragged engine call per flush; same records."""
-    import numpy as np
-    import os
     from .pipeline import FrameCache
     rng = np.random if rng is None else rng
     videos = anno['videos']
@@ -371,20 +383,17 @@ def run_tracks(engine, tracks, max_len=100, batch_frames=448, scale_factor=None)
         if tracks[items[0][0]].get('img_hw') is not None:
             hw = np.concatenate([np.asarray(tracks[ti]['img_hw'], dtype=np.int32).reshape(-1, 2)[a:b] for (ti, _), (a, b) in zip(items, spans)])
         out = engine.forward(x, Ts, img_hw=hw)
-        boxes = out['boxes']
-        if scale_factor is not None:
-            boxes = boxes / torch.as_tensor(scale_factor, dtype=torch.float32, device=boxes.device)
-        det = _host(torch.cat([boxes, out['scores'][..., None]], dim=-1))
-        gaze = _host(out['gaze'])
+        scale = None if scale_factor is None else torch.as_tensor(scale_factor, dtype=torch.float32, device=out['boxes'].device)
+        det, fused, others = (_host(t) for t in clip_outputs(out, scale))
         row = 0
         for (ti, ci), T in zip(items, Ts):
-            parts[ti][ci] = (det[row:row + T], gaze[0, row:row + T], gaze[1:, row:row + T].transpose(1, 0, 2))
+            parts[ti][ci] = (det[row:row + T], fused[row:row + T], others[row:row + T])
             row += T
 
     for ti, plan in enumerate(plans):
         fr = tracks[ti]['frames']
         for ci, (a, b) in enumerate(plan):
-            key = (fr.shape[-2], fr.shape[-1], int(b - a > FUSED_ATTN_MAX_T))
+            key = bucket_key(fr.shape[-2], fr.shape[-1], b - a, True)
             held = sum(plans[t][c][1] - plans[t][c][0] for t, c in buckets.get(key, []))
             if held and held + (b - a) > batch_frames:
                 flush(key)

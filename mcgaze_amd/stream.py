@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 from . import lib as L
-from .harness import _host, plan_windows
+from .harness import _host, clip_outputs, merge_window, plan_windows
 
 
 class WindowPlanner:
@@ -72,8 +72,8 @@ class WindowPlanner:
 
 class StreamMerger:
     """``harness.merge_video`` one window at a time: windows must be added in plan order; ``pop(upto)`` returns the merged frames
-    [emitted, upto) -- which no later window may touch -- and forgets them.  The arithmetic is merge_video's (harness.py), step for
-    step, so the concatenated output of a stream equals merge_video over the whole plan bit for bit."""
+    [emitted, upto) -- which no later window may touch -- and forgets them.  Each step is harness.merge_window, the one merge_video
+    runs, so the concatenated output of a stream equals merge_video over the whole plan bit for bit."""
 
     def __init__(self, person_threshold=0.5):
         self.thr = np.float32(person_threshold)
@@ -96,28 +96,12 @@ class StreamMerger:
 
     def add(self, window, d, f, o):
         """window = (start, stop, overlap) from the plan; d [T,3,5], f [T,3], o [T,3,3] (f32)."""
-        start, stop, overlap = window
-        d, f, o = _host(d), _host(f), _host(o)
+        start, stop, _ = window
         if start < self.base:
             raise L.McgError(f'StreamMerger: window {window} reaches below frame {self.base}, which was already handed out')
         self._grow(stop)
-        det, fused, others, b = self.det, self.fused, self.others, self.base
-        thr, half = self.thr, np.float32(2)
-        low = d[..., 4:] < thr
-        d = np.concatenate([np.where(low, np.float32(0), d[..., :4]), d[..., 4:]], axis=-1)
-        if self.first:
-            det[start - b:stop - b], fused[start - b:stop - b], others[start - b:stop - b] = d, f, o
-            self.first = False
-        else:
-            ov = slice(start - b, start + overlap - b)
-            old_d, cur_d = det[ov], d[:overlap]
-            bad = (old_d[..., 4:] < thr) | low[:overlap]
-            det[ov, :, :4] = np.where(bad, np.float32(0), (old_d[..., :4] + cur_d[..., :4]) / half)
-            det[ov, :, 4:] = (old_d[..., 4:] + cur_d[..., 4:]) / half
-            fused[ov] = (fused[ov] + f[:overlap]) / half
-            others[ov] = (others[ov] + o[:overlap]) / half
-            new = slice(start + overlap - b, stop - b)
-            det[new], fused[new], others[new] = d[overlap:], f[overlap:], o[overlap:]
+        merge_window(self.det, self.fused, self.others, self.base, self.first, window, d, f, o, self.thr)
+        self.first = False
         self.end = max(self.end, stop)
 
     def pop(self, upto):
@@ -224,10 +208,7 @@ class GazeStream:
             T = part[0][1] - part[0][0]
             table = [self.ring.row(f) for a, b, _ in part for f in range(a, b)]
             out = self.e.decode(self.ring.levels, table, T, img_hw=self.ring.hw)
-            boxes = out['boxes'] if self.scale is None else out['boxes'] / self.scale
-            det = torch.cat([boxes, out['scores'][..., None]], dim=-1)
-            fused, others = out['gaze'][0], out['gaze'][1:].permute(1, 0, 2)
-            det, fused, others = det.cpu().numpy(), fused.cpu().numpy(), others.cpu().numpy()
+            det, fused, others = (t.cpu().numpy() for t in clip_outputs(out, self.scale))
             for k, w in enumerate(part):
                 self.merger.add(w, det[k * T:(k + 1) * T], fused[k * T:(k + 1) * T], others[k * T:(k + 1) * T])
 
