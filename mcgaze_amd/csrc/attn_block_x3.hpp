@@ -195,13 +195,7 @@ __global__ __launch_bounds__(256, 1) void attn_block_x3_kernel(const AttnBlockPa
 }
 
 static inline int launch_attn_block_x3(hipStream_t s, const AttnBlockParams& p) {
-  static bool attr_set[MCG_MAX_DEVICES] = {false};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MCG_MAX_DEVICES) dev = 0;
-  if (!attr_set[dev]) {
-    if (hipFuncSetAttribute((const void*)attn_block_x3_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, abx::LDS_BYTES) != hipSuccess) return 1;
-    attr_set[dev] = true;
-  }
+  if (kernel_ready<attn_block_x3_kernel>(abx::LDS_BYTES)) return 1;
   hipLaunchKernelGGL(attn_block_x3_kernel, dim3(p.num_clips), dim3(256), abx::LDS_BYTES, s, p);
   return hipGetLastError() == hipSuccess ? 0 : 1;
 }

@@ -465,15 +465,9 @@ static inline size_t bneck_x3_stream_bytes(int cm, int nsrc, int cn) {
 template <int CM, int NSRC, int CN, int LAYOUT>
 static inline int launch_bneck_x3_t(hipStream_t s, const BneckParams& p) {
   constexpr int kLds = bnx::WIN_BYTES + bnx::RING_BYTES + (CM + 4 * CM + CN + 4) * 4;
-  static int cus_of[MCG_MAX_DEVICES] = {0};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MCG_MAX_DEVICES) dev = 0;
-  if (!cus_of[dev]) {
-    hipDeviceProp_t prop;
-    if (hipFuncSetAttribute((const void*)bneck_x3_kernel<CM, NSRC, CN, LAYOUT>, hipFuncAttributeMaxDynamicSharedMemorySize, kLds) != hipSuccess) return 1;
-    cus_of[dev] = hipGetDeviceProperties(&prop, dev) == hipSuccess ? prop.multiProcessorCount : 256;
-  }
-  const int grid = p.total_tiles < cus_of[dev] ? p.total_tiles : cus_of[dev];
+  int cus;
+  if (kernel_ready<bneck_x3_kernel<CM, NSRC, CN, LAYOUT>>(kLds, &cus)) return 1;
+  const int grid = p.total_tiles < cus ? p.total_tiles : cus;
   hipLaunchKernelGGL((bneck_x3_kernel<CM, NSRC, CN, LAYOUT>), dim3(grid), dim3(bnx::NT), kLds, s, p);
   return hipGetLastError() == hipSuccess ? 0 : 1;
 }

@@ -4,6 +4,8 @@
 #include <stdint.h>
 #include <stdio.h>
 
+#include <atomic>
+
 #include "../../include/mcgaze_hip.h"
 
 typedef __attribute__((ext_vector_type(16))) float f32x16;
@@ -180,6 +182,40 @@ static inline bool mcg_is16(mcg_dtype dt) { return dt == MCG_BF16 || dt == MCG_F
 // type tag (decltype(e): float for MCG_F32 and for MCG_F16X3, whose activations are f32).  dispatch_elem16: the 16-bit-only kernels.
 template <typename F> static inline auto dispatch_elem16(mcg_dtype dt, F&& f) { return dt == MCG_F16 ? f(f16_t{}) : f(bf16_t{}); }
 template <typename F> static inline auto dispatch_elem(mcg_dtype dt, F&& f) { return mcg_is16(dt) ? dispatch_elem16(dt, f) : f(float{}); }
+
+// ---------------------------------------------------------------- launch preparation of the host launchers
+// Per-device launch state (a process may hold engines on several GPUs, and two threads may launch on one): devices beyond the table share
+// slot 0's entries.
+#define MCG_MAX_DEVICES 64
+static inline int mcg_device_slot() {
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MCG_MAX_DEVICES) dev = 0;
+  return dev;
+}
+// CU count of the current device, queried once per device (256 where the query fails): what the persistent grids are sized by
+inline int mcg_cu_count(int dev = mcg_device_slot()) {
+  static std::atomic<int> cus_of[MCG_MAX_DEVICES];
+  int n = cus_of[dev].load(std::memory_order_relaxed);
+  if (n == 0) {
+    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
+    cus_of[dev].store(n, std::memory_order_relaxed);
+  }
+  return n;
+}
+// What a launcher does before it launches Kernel with lds_bytes of dynamic LDS: raises the kernel's dynamic-LDS limit, once per (kernel,
+// device) -- the pair counts as ready only AFTER the raise has succeeded, so a second thread never launches in front of it -- and hands out
+// the CU count.  Returns non-zero where the raise fails: the launch would fail too, and the launcher reports it as a failed launch.
+template <auto Kernel>
+static inline int kernel_ready(int lds_bytes, int* cus = nullptr) {
+  static std::atomic<bool> ready[MCG_MAX_DEVICES];
+  const int dev = mcg_device_slot();
+  if (!ready[dev].load(std::memory_order_acquire)) {
+    if (hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes) != hipSuccess) return 1;
+    ready[dev].store(true, std::memory_order_release);
+  }
+  if (cus) *cus = mcg_cu_count(dev);
+  return 0;
+}
 
 // ---------------------------------------------------------------- host side error plumbing
 void mcg_set_error(const char* fmt, ...);

@@ -164,49 +164,41 @@ static inline bool pw_single_applicable(int K, int N, int res_mode, long long M,
   return shape && M >= 64 * 1024 && M * 2 * (K > N ? K : N) < MCG_DMA_MAX_BYTES && res_rows * 2 * N < MCG_DMA_MAX_BYTES;
 }
 template <typename F, int KS, int TPW, int RES, int NSPLIT>
-static inline void launch_pw_single_t(hipStream_t s, const PwSingleParams& p) {
+static inline int launch_pw_single_t(hipStream_t s, const PwSingleParams& p) {
   constexpr int K = 16 * KS, N = 128 * TPW, AB = 32 * 2 * K, YB = 32 * 2 * N, NYB = RES ? 2 : 1;
   constexpr int BB = TPW == 1 ? 0 : N * 4;
   constexpr int NAB = (2 * AB + NYB * YB + BB <= 80 * 1024) ? 2 : 1;
   constexpr int kLds = NYB * YB + NAB * AB + BB;
   static_assert(kLds <= 80 * 1024, "two workgroups per CU");
-  // per device (a process may hold engines on several GPUs): CU count, and the kernel's dynamic-LDS limit raised once
-  static int cus_of[MCG_MAX_DEVICES] = {0};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MCG_MAX_DEVICES) dev = 0;
-  if (!cus_of[dev]) {
-    hipDeviceProp_t prop;
-    (void)hipFuncSetAttribute((const void*)pw_single_kernel<F, KS, TPW, RES, NSPLIT>, hipFuncAttributeMaxDynamicSharedMemorySize, kLds);
-    cus_of[dev] = hipGetDeviceProperties(&prop, dev) == hipSuccess ? prop.multiProcessorCount : 256;
-  }
-  const int cus = cus_of[dev];
+  int cus;
+  if (kernel_ready<pw_single_kernel<F, KS, TPW, RES, NSPLIT>>(kLds, &cus)) return 1;
   const int ntiles = (p.M + 31) / 32, unit = 8 * NSPLIT;
   int wgs = 2 * cus / unit * unit;                              // two workgroups per CU, whole groups of NSPLIT slices x 8 XCDs
   const int need = (ntiles + 7) / 8 * unit;
   if (wgs < unit) wgs = unit;
   hipLaunchKernelGGL((pw_single_kernel<F, KS, TPW, RES, NSPLIT>), dim3(need < wgs ? need : wgs), dim3(256), kLds, s, p);
+  return hipGetLastError() == hipSuccess ? 0 : 1;
 }
 template <typename F>
 static inline int launch_pw_single_f(hipStream_t s, const PwSingleParams& p, int K, int N, int res_mode) {
   if (K == 256 && N == 256) {
-    if (res_mode == 0) launch_pw_single_t<F, 16, 2, 0, 1>(s, p);
-    else if (res_mode == 1) launch_pw_single_t<F, 16, 2, 1, 1>(s, p);
-    else launch_pw_single_t<F, 16, 2, 2, 1>(s, p);
-  } else if (K == 256 && N == 1024) {
-    if (res_mode == 0) launch_pw_single_t<F, 16, 2, 0, 4>(s, p);
-    else if (res_mode == 1) launch_pw_single_t<F, 16, 2, 1, 4>(s, p);
-    else launch_pw_single_t<F, 16, 2, 2, 4>(s, p);
-  } else if (K == 512 && N == 128) {
-    launch_pw_single_t<F, 32, 1, 0, 1>(s, p);
-  } else if (K == 512 && N == 256) {
-    if (res_mode == 0) launch_pw_single_t<F, 32, 1, 0, 2>(s, p);
-    else launch_pw_single_t<F, 32, 1, 2, 2>(s, p);
-  } else {
-    if (res_mode == 0) launch_pw_single_t<F, 8, 4, 0, 1>(s, p);
-    else if (res_mode == 1) launch_pw_single_t<F, 8, 4, 1, 1>(s, p);
-    else launch_pw_single_t<F, 8, 4, 2, 1>(s, p);
+    if (res_mode == 0) return launch_pw_single_t<F, 16, 2, 0, 1>(s, p);
+    if (res_mode == 1) return launch_pw_single_t<F, 16, 2, 1, 1>(s, p);
+    return launch_pw_single_t<F, 16, 2, 2, 1>(s, p);
   }
-  return hipGetLastError() == hipSuccess ? 0 : 1;
+  if (K == 256 && N == 1024) {
+    if (res_mode == 0) return launch_pw_single_t<F, 16, 2, 0, 4>(s, p);
+    if (res_mode == 1) return launch_pw_single_t<F, 16, 2, 1, 4>(s, p);
+    return launch_pw_single_t<F, 16, 2, 2, 4>(s, p);
+  }
+  if (K == 512 && N == 128) return launch_pw_single_t<F, 32, 1, 0, 1>(s, p);
+  if (K == 512 && N == 256) {
+    if (res_mode == 0) return launch_pw_single_t<F, 32, 1, 0, 2>(s, p);
+    return launch_pw_single_t<F, 32, 1, 2, 2>(s, p);
+  }
+  if (res_mode == 0) return launch_pw_single_t<F, 8, 4, 0, 1>(s, p);
+  if (res_mode == 1) return launch_pw_single_t<F, 8, 4, 1, 1>(s, p);
+  return launch_pw_single_t<F, 8, 4, 2, 1>(s, p);
 }
 
 // DynamicConv's `dynamic_layer` (transformer.py:1131-1134): y[M][32768] = x[M][256] . W^T + b with FEW rows (1344 tokens at 64 clips) and
@@ -220,16 +212,10 @@ static inline bool pw_dyn_applicable(int M) { return M >= 256 && (long long)M * 
 template <typename F>
 static inline int launch_pw_dyn_f(hipStream_t s, PwSingleParams p) {
   constexpr int KS = 16, TPW = 2, NSPLIT = 128, kLds = 32 * 512 + 2 * 32 * 512 + 256 * 4;   // y tile + two A tiles + biases
-  static int cus_of[MCG_MAX_DEVICES] = {0};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MCG_MAX_DEVICES) dev = 0;
-  if (!cus_of[dev]) {
-    hipDeviceProp_t prop;
-    (void)hipFuncSetAttribute((const void*)pw_single_kernel<F, KS, TPW, 0, NSPLIT>, hipFuncAttributeMaxDynamicSharedMemorySize, kLds);
-    cus_of[dev] = hipGetDeviceProperties(&prop, dev) == hipSuccess ? prop.multiProcessorCount : 256;
-  }
+  int cus;
+  if (kernel_ready<pw_single_kernel<F, KS, TPW, 0, NSPLIT>>(kLds, &cus)) return 1;
   const int ntiles = (p.M + 31) / 32;
-  int walkers = 2 * cus_of[dev] / NSPLIT;                       // two workgroups per CU (4 walkers per slice on 256 CUs; 2, 3, 6, 8 measured slower)
+  int walkers = 2 * cus / NSPLIT;                               // two workgroups per CU (4 walkers per slice on 256 CUs; 2, 3, 6, 8 measured slower)
   if (walkers < 1) walkers = 1;
   if (walkers > ntiles) walkers = ntiles;
   p.many_slices = 1;

@@ -129,33 +129,26 @@ static inline bool pw_single_x3_applicable(int K, int N, int res_mode, long long
   return K == 256 && (N == 256 || N == 1024) && M >= 64 * 1024 && M * 4 * (K > N ? K : N) < MCG_DMA_MAX_BYTES && res_rows * 4 * N < MCG_DMA_MAX_BYTES;
 }
 template <int KS, int RES, int NSPLIT>
-static inline void launch_pw_single_x3_t(hipStream_t s, const PwSingleParams& p) {
+static inline int launch_pw_single_x3_t(hipStream_t s, const PwSingleParams& p) {
   constexpr int kLds = (RES ? 2 : 1) * 32 * 512 + 32 * 64 * KS;
-  static int cus_of[MCG_MAX_DEVICES] = {0};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MCG_MAX_DEVICES) dev = 0;
-  if (!cus_of[dev]) {
-    hipDeviceProp_t prop;
-    (void)hipFuncSetAttribute((const void*)pw_single_x3_kernel<KS, RES, NSPLIT>, hipFuncAttributeMaxDynamicSharedMemorySize, kLds);
-    cus_of[dev] = hipGetDeviceProperties(&prop, dev) == hipSuccess ? prop.multiProcessorCount : 256;
-  }
+  int cus;
+  if (kernel_ready<pw_single_x3_kernel<KS, RES, NSPLIT>>(kLds, &cus)) return 1;
   const int ntiles = (p.M + 31) / 32, unit = 8 * NSPLIT;
-  int wgs = 2 * cus_of[dev] / unit * unit;                      // two workgroups per CU, whole groups of NSPLIT slices x 8 XCDs
+  int wgs = 2 * cus / unit * unit;                              // two workgroups per CU, whole groups of NSPLIT slices x 8 XCDs
   const int need = (ntiles + 7) / 8 * unit;
   if (wgs < unit) wgs = unit;
   hipLaunchKernelGGL((pw_single_x3_kernel<KS, RES, NSPLIT>), dim3(need < wgs ? need : wgs), dim3(256), kLds, s, p);
+  return hipGetLastError() == hipSuccess ? 0 : 1;
 }
 static inline int launch_pw_single_x3(hipStream_t s, const PwSingleParams& p, int N, int res_mode) {
   if (N == 256) {
-    if (res_mode == 0) launch_pw_single_x3_t<16, 0, 2>(s, p);
-    else if (res_mode == 1) launch_pw_single_x3_t<16, 1, 2>(s, p);
-    else launch_pw_single_x3_t<16, 2, 2>(s, p);
-  } else {
-    if (res_mode == 0) launch_pw_single_x3_t<16, 0, 8>(s, p);
-    else if (res_mode == 1) launch_pw_single_x3_t<16, 1, 8>(s, p);
-    else launch_pw_single_x3_t<16, 2, 8>(s, p);
+    if (res_mode == 0) return launch_pw_single_x3_t<16, 0, 2>(s, p);
+    if (res_mode == 1) return launch_pw_single_x3_t<16, 1, 2>(s, p);
+    return launch_pw_single_x3_t<16, 2, 2>(s, p);
   }
-  return hipGetLastError() == hipSuccess ? 0 : 1;
+  if (res_mode == 0) return launch_pw_single_x3_t<16, 0, 8>(s, p);
+  if (res_mode == 1) return launch_pw_single_x3_t<16, 1, 8>(s, p);
+  return launch_pw_single_x3_t<16, 2, 8>(s, p);
 }
 
 // DynamicConv's `dynamic_layer` for the f16x3 engine (transformer.py:1131-1134): y[M][32768] = x[M][256] . W^T + b on M = 1344 tokens,
@@ -163,16 +156,10 @@ static inline int launch_pw_single_x3(hipStream_t s, const PwSingleParams& p, in
 // the token tiles (pw_single.hpp's launch_pw_dyn).  Bit-identical to the x3 contraction kernel.
 static inline int launch_pw_dyn_x3(hipStream_t s, PwSingleParams p) {
   constexpr int KS = 16, NSPLIT = 256, kLds = 32 * 512 + 32 * 64 * KS;
-  static int cus_of[MCG_MAX_DEVICES] = {0};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MCG_MAX_DEVICES) dev = 0;
-  if (!cus_of[dev]) {
-    hipDeviceProp_t prop;
-    (void)hipFuncSetAttribute((const void*)pw_single_x3_kernel<KS, 0, NSPLIT>, hipFuncAttributeMaxDynamicSharedMemorySize, kLds);
-    cus_of[dev] = hipGetDeviceProperties(&prop, dev) == hipSuccess ? prop.multiProcessorCount : 256;
-  }
+  int cus;
+  if (kernel_ready<pw_single_x3_kernel<KS, 0, NSPLIT>>(kLds, &cus)) return 1;
   const int ntiles = (p.M + 31) / 32;
-  int walkers = 2 * cus_of[dev] / NSPLIT;                       // two workgroups per CU
+  int walkers = 2 * cus / NSPLIT;                               // two workgroups per CU
   if (walkers < 1) walkers = 1;
   if (walkers > ntiles) walkers = ntiles;
   p.many_slices = 1;

@@ -41,6 +41,8 @@
 //   * epilogue: the four positions of a pair live in four waves; they meet in LDS (two passes of 64 pairs x 128 channels x 4), the
 //     output transform + bias (+ ReLU) is applied on 16-byte channel chunks and both pixels of a pair are stored.
 // Batch invariance: a pair's arithmetic does not depend on the tile it falls into, so a clip's result is independent of the batch.
+// The tile range, the window's rows and piece layout, the A addresses, the input transform and the epilogue are functions of namespace
+// wnx, shared by this kernel and the one-wave tile (wino_x3w_tile) below; a kernel's own text is its K loop.
 //
 // G = 4 (round 4, second half): the same kernel with F(4,3) -- groups of FOUR output pixels, six positions (points 0, +-1, +-2, inf),
 //     V = B^T d with B^T = [4 0 -5 0 1 0; 0 -4 -4 1 1 0; 0 4 -4 -1 1 0; 0 -2 -1 2 1 0; 0 2 -1 -2 1 0; 0 4 0 -5 0 1]   (<= 4 terms: 1 mul + 3 fma)
@@ -59,6 +61,8 @@ constexpr int KS = 16;                              // input channels per K step
 constexpr int UNT = 128;                            // output channels per weight block of the packed operand (packing.py::wino_pack)
 constexpr int ustage(int g) { return (g + 2) * 4 * 2 * 1024; }   // one K step of one block: [nu G + 2][channel tile 4][high, low][64 lanes][16 B]
 constexpr int wcap(int g, int ct) { return (g == 4 && ct == 4) ? 32 * 1024 : 48 * 1024; }   // one window buffer (1 KiB pieces; a workgroup may use fewer)
+constexpr int W_LDS = 4 * 64 * 128 * 4;             // the one-wave tile: epilogue staging [nu][64 pairs][128 channels] f32 (its K loop uses the first
+                                                    // 96 KiB: two window buffers)
 }  // namespace wnx
 
 struct WinoParams {
@@ -76,6 +80,118 @@ struct WinoParams {
   const int* blk_count;  // DEVICE count of blk_list entries
   int bxn, bpf;          // blocks per row, blocks per frame
 };
+
+// What the tiles share, each piece stated once: wino_x3_kernel and wino_x3w_tile give the same bits because they run this text.
+namespace wnx {
+// Groups [q0, q_end) of row tile mt of MT groups: raster order over (frame, row, group), cut at frame boundaries where p.tpf > 0.
+__device__ __forceinline__ void tile_range(const WinoParams& p, int mt, int MT, int& q0, int& q_end) {
+  if (p.tpf > 0) {
+    const int f = mt / p.tpf, t = mt - f * p.tpf;
+    q0 = f * p.gpf + t * MT;
+    q_end = min(q0 + MT, (f + 1) * p.gpf);
+  } else {
+    q0 = mt * MT;
+    q_end = min(q0 + MT, p.total_pairs);
+  }
+}
+// window slot of the global output row R = f H + y of group q: R + f + 1 (slot f (H + 1) is the zero row in front of frame f)
+__device__ __forceinline__ int slot_of(const WinoParams& p, int q) { const int R = q / p.PW; return R + R / p.H + 1; }
+// byte offset of row y of frame f in x
+__device__ __forceinline__ uint32_t row_base(const WinoParams& p, int f, int y) { return (uint32_t)(((long long)(f * p.H + y) * p.W) * p.Cin * 4); }
+// the input row that window slot sg holds (not ok: the zero row in front of a frame, slots behind the last frame)
+struct WinRow { bool ok; uint32_t base; };
+__device__ __forceinline__ WinRow win_row(const WinoParams& p, int sg) {
+  const int H1 = p.H + 1, f = sg / H1, r = sg - f * H1;
+  return {r != 0 && f < p.frames, row_base(p, f, r - 1)};
+}
+// A window row is a sequence of blocks of 8 G pixels: phase ph = pixel % G, group index i = pixel / G: [ph][i (8)][64 B].  A 1 KiB piece
+// carries two phases of a block (G = 2: the whole block); lane l: phase 2 (piece % (G / 2)) + (l >> 5), group (l >> 2) & 7 of the block,
+// LDS chunk slot l & 3 (holds channel chunk slot ^ swizzle).  -> the pixel x (-1 and >= W: the zero columns) and the channel chunk c that
+// lane fetches of piece pc of a row, and their offset in the row
+template <int G>
+__device__ __forceinline__ void win_lane(int lane, int pc, int& x, int& c) {
+  const int l_ph = lane >> 5, l_i = (lane >> 2) & 7, l_cs = lane & 3;
+  const int b = pc / (G / 2), hph = pc - b * (G / 2);
+  x = (8 * b + l_i) * G + 2 * hph + l_ph - 1;
+  c = l_cs ^ ((2 * b + (l_i >> 2)) & 3);
+}
+__device__ __forceinline__ uint32_t win_voff(const WinoParams& p, int x, int c) {
+  return (unsigned)x < (unsigned)p.W ? (uint32_t)((x * p.Cin + 4 * c) * 4) : MCG_OOB_OFFSET;
+}
+// A operand: LDS address of 16-byte channel chunk `chunk` of pixel toff of group xg's G + 2 pixel footprint in window row jrow
+template <int G>
+__device__ __forceinline__ const char* a_addr(const char* win, int jrow, int rowb, int xg, int toff, int chunk) {
+  const int wx = G * xg + toff;
+  const int pp = wx / G, ph = wx - pp * G, swz = (pp >> 2) & 3;
+  const int off = jrow * rowb + (pp >> 3) * (G * 512) + ph * 512 + (pp & 7) * 64;
+  return win + off + ((chunk ^ swz) << 4);
+}
+// F(2,3) input transform of position nu: V = d[toff[0]] + sgn d[toff[1]] (pixel offsets in the pair's four-pixel footprint) ...
+__device__ __forceinline__ void f23_position(int nu, int (&toff)[2], float& sgn) {
+  toff[0] = nu == 0 ? 0 : 1; toff[1] = nu == 3 ? 3 : 2;
+  sgn = nu == 1 ? 1.f : -1.f;
+}
+// ... of one 16-byte chunk (four channels) ...
+__device__ __forceinline__ void f23_chunk(const uint4& d0, const uint4& d1, float sgn, float* v) {
+  const uint32_t e0[4] = {d0.x, d0.y, d0.z, d0.w};
+  const uint32_t e1[4] = {d1.x, d1.y, d1.z, d1.w};
+#pragma unroll
+  for (int e = 0; e < 4; ++e) v[e] = fmaf(sgn, __uint_as_float(e1[e]), __uint_as_float(e0[e]));
+}
+// ... and of a lane's eight channels d[term][chunk], split into the A fragment's high / low parts
+__device__ __forceinline__ void f23_fragment(const uint4 (&d)[2][2], float sgn, bf16x8& ah, bf16x8& al) {
+  float v[8];
+#pragma unroll
+  for (int c = 0; c < 2; ++c) f23_chunk(d[0][c], d[1][c], sgn, v + 4 * c);
+  const uint4 v0 = make_uint4(__float_as_uint(v[0]), __float_as_uint(v[1]), __float_as_uint(v[2]), __float_as_uint(v[3]));
+  const uint4 v1 = make_uint4(__float_as_uint(v[4]), __float_as_uint(v[5]), __float_as_uint(v[6]), __float_as_uint(v[7]));
+  split_f32x8(v0, v1, ah, al);
+}
+// Epilogue.  The G + 2 positions of a group live in different waves and meet in LDS: C[nu][PP groups][NT channels] takes one MFMA tile
+// (row tile rt, column tile ct of a pass) of position nu ...
+template <int PP, int NT>
+__device__ __forceinline__ void stage_acc(float* C, int nu, int rt, int ct, int lane, const f32x16& a) {
+#pragma unroll
+  for (int r = 0; r < 16; ++r) C[(nu * PP + rt * 32 + mfma32_row(r, lane)) * NT + ct * 32 + (lane & 31)] = a[r];
+}
+// ... and one item = group prl of the pass x channels ch4 .. ch4 + 3 reads its positions back, applies the output transform, the weight
+// scale, the bias (+ ReLU) and stores the group's pixels xo .. of global output row R that lie inside the row (valid: the group exists).
+template <int G, int PP, int NT>
+__device__ __forceinline__ void epilogue_item(const WinoParams& p, const float* C, int prl, int ch4, int n0, float wsc, int R, int xo, bool valid) {
+  constexpr int NV = G + 2;
+  if (!valid) return;
+  float4 bv = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (p.bias) bv = *(const float4*)(p.bias + n0 + ch4);
+  float4 m[NV];
+#pragma unroll
+  for (int v = 0; v < NV; ++v) m[v] = *(const float4*)(C + (v * PP + prl) * NT + ch4);
+  float4 y[G];
+  if constexpr (G == 2) {
+    y[0] = make_float4(((m[0].x + m[1].x) + m[2].x) * wsc + bv.x, ((m[0].y + m[1].y) + m[2].y) * wsc + bv.y, ((m[0].z + m[1].z) + m[2].z) * wsc + bv.z, ((m[0].w + m[1].w) + m[2].w) * wsc + bv.w);
+    y[1] = make_float4(((m[1].x - m[2].x) - m[3].x) * wsc + bv.x, ((m[1].y - m[2].y) - m[3].y) * wsc + bv.y, ((m[1].z - m[2].z) - m[3].z) * wsc + bv.z, ((m[1].w - m[2].w) - m[3].w) * wsc + bv.w);
+  } else {
+    // y0 = m0 + (m1 + m2) + (m3 + m4); y1 = (m1 - m2) + 2 (m3 - m4); y2 = (m1 + m2) + 4 (m3 + m4); y3 = (m1 - m2) + 8 (m3 - m4) + m5
+#define MCG_W4(F)                                                                                                            \
+    {                                                                                                                    \
+      const float s12 = m[1].F + m[2].F, d12 = m[1].F - m[2].F, s34 = m[3].F + m[4].F, d34 = m[3].F - m[4].F;            \
+      y[0].F = ((m[0].F + s12) + s34) * wsc + bv.F;                                                                      \
+      y[1].F = fmaf(2.f, d34, d12) * wsc + bv.F;                                                                         \
+      y[2].F = fmaf(4.f, s34, s12) * wsc + bv.F;                                                                         \
+      y[3].F = (fmaf(8.f, d34, d12) + m[5].F) * wsc + bv.F;                                                              \
+    }
+    MCG_W4(x) MCG_W4(y) MCG_W4(z) MCG_W4(w)
+#undef MCG_W4
+  }
+  float* yp = p.y + ((long long)R * p.W + xo) * p.Cout + n0 + ch4;
+#pragma unroll
+  for (int j = 0; j < G; ++j) {
+    if (xo + j >= p.W) break;
+    float4 o = y[j];
+    if (p.relu) { o.x = fmaxf(o.x, 0.f); o.y = fmaxf(o.y, 0.f); o.z = fmaxf(o.z, 0.f); o.w = fmaxf(o.w, 0.f); }
+    *(float4*)(yp + (long long)j * p.Cout) = o;
+  }
+}
+}  // namespace wnx
 
 // NB: 1 KiB pieces per window row.  Tile: RH x RT row tiles of 32 groups, CT column tiles of 32 channels; (G + 2) RH waves.
 template <int NB, int RH, int RT, int CT, int G>
@@ -97,20 +213,10 @@ __global__ __launch_bounds__(64 * (G + 2) * RH, 1) void wino_x3_kernel(const Win
   const int logical = xcd_remap(blockIdx.x, gridDim.x);
   const int mt = logical / p.n_tiles, ntile = logical - mt * p.n_tiles;
   int q0, q_end;
-  if (p.tpf > 0) {                                    // tiles cut at frame boundaries
-    const int f = mt / p.tpf, t = mt - f * p.tpf;
-    q0 = f * p.gpf + t * MT;
-    q_end = min(q0 + MT, (f + 1) * p.gpf);
-  } else {
-    q0 = mt * MT;
-    q_end = min(q0 + MT, p.total_pairs);
-  }
+  tile_range(p, mt, MT, q0, q_end);
   const int q_last = q_end - 1;
-  const int H1 = p.H + 1;
-  // window slot of global output row R = f H + y: R + f + 1 (slot f (H + 1) is the zero row in front of frame f)
-  auto slot_of = [&](int q) { const int R = q / p.PW; return R + R / p.H + 1; };
-  const int sig_b = __builtin_amdgcn_readfirstlane(slot_of(q0) - 1);
-  const int NP = __builtin_amdgcn_readfirstlane((slot_of(q_last) - sig_b + 2) * NB);   // window pieces per slice
+  const int sig_b = __builtin_amdgcn_readfirstlane(slot_of(p, q0) - 1);                   // the window's first slot: the halo row above the tile
+  const int NP = __builtin_amdgcn_readfirstlane((slot_of(p, q_last) - sig_b + 2) * NB);   // window pieces per slice
   const int NSL = p.Cin / KS, KT = 3 * NSL;
 
   const int n0 = ntile * NT;                                                    // first output channel of this workgroup
@@ -126,27 +232,22 @@ __global__ __launch_bounds__(64 * (G + 2) * RH, 1) void wino_x3_kernel(const Win
   static_for<MAXP>([&](auto nc) {
     constexpr int n = decltype(nc)::value;
     const int pi = wave + NW * n, j = pi / NB, b = pi - j * NB;
-    const int sg = sig_b + j, f = sg / H1, r = sg - f * H1;
+    const WinRow row = win_row(p, sig_b + j);
     pok[n] = pi < NP;
-    prowok[n] = __builtin_amdgcn_readfirstlane((r != 0 && f < p.frames) ? 1 : 0) != 0;
-    prow[n] = __builtin_amdgcn_readfirstlane((uint32_t)(((long long)(f * p.H + r - 1) * p.W) * p.Cin * 4));
+    prowok[n] = __builtin_amdgcn_readfirstlane(row.ok ? 1 : 0) != 0;
+    prow[n] = __builtin_amdgcn_readfirstlane(row.base);
     pblk[n] = b;
   });
-  // A window row is a sequence of blocks of 8 G pixels: phase ph = pixel % G, group index i = pixel / G: [ph][i (8)][64 B].  A 1 KiB piece
-  // carries two phases of a block (G = 2: the whole block); lane l: phase 2 (piece % (G / 2)) + (l >> 5), group (l >> 2) & 7 of the block,
-  // LDS chunk slot l & 3 (holds channel chunk slot ^ swizzle).
-  const int l_ph = lane >> 5, l_i = (lane >> 2) & 7, l_cs = lane & 3;
-  auto win_voff = [&](int pc) -> uint32_t {
-    const int b = pc / (G / 2), hph = pc - b * (G / 2);
-    const int x = (8 * b + l_i) * G + 2 * hph + l_ph - 1;
-    const int c = l_cs ^ ((2 * b + (l_i >> 2)) & 3);
-    return (unsigned)x < (unsigned)p.W ? (uint32_t)((x * p.Cin + 4 * c) * 4) : MCG_OOB_OFFSET;
+  auto piece_voff = [&](int pc) -> uint32_t {
+    int x, c;
+    win_lane<G>(lane, pc, x, c);
+    return win_voff(p, x, c);
   };
   auto issue_window = [&](int cs, uint32_t dst) {
     static_for<MAXP>([&](auto nc) {
       constexpr int n = decltype(nc)::value;
       if (pok[n]) {
-        const uint32_t v = prowok[n] ? win_voff(pblk[n]) : MCG_OOB_OFFSET;
+        const uint32_t v = prowok[n] ? piece_voff(pblk[n]) : MCG_OOB_OFFSET;
         lds_dma16<0>(v, srd_x, prow[n] + (uint32_t)cs * (KS * 4), dst + (uint32_t)(wave + NW * n) * 1024u);
       }
     });
@@ -166,8 +267,8 @@ __global__ __launch_bounds__(64 * (G + 2) * RH, 1) void wino_x3_kernel(const Win
   int toff[NTERM];
   float tco[NTERM];
   if constexpr (G == 2) {
-    toff[0] = nu == 0 ? 0 : 1; toff[1] = nu == 3 ? 3 : 2;
-    tco[0] = 1.f; tco[1] = nu == 1 ? 1.f : -1.f;            // V = a + sgn b
+    tco[0] = 1.f;
+    f23_position(nu, toff, tco[1]);
   } else {
     const int o4[6][4] = {{0, 2, 4, 4}, {1, 2, 3, 4}, {1, 2, 3, 4}, {1, 2, 3, 4}, {1, 2, 3, 4}, {1, 3, 5, 5}};
     const float c4[6][4] = {{4.f, -5.f, 1.f, 0.f}, {-4.f, -4.f, 1.f, 1.f}, {4.f, -4.f, -1.f, 1.f}, {-2.f, -1.f, 2.f, 1.f}, {2.f, -1.f, -2.f, 1.f}, {4.f, -5.f, 1.f, 0.f}};
@@ -185,16 +286,12 @@ __global__ __launch_bounds__(64 * (G + 2) * RH, 1) void wino_x3_kernel(const Win
 #pragma unroll
   for (int rt = 0; rt < RT; ++rt) {
     const int q = min(q0 + (RT * rh + rt) * 32 + pl, q_last);               // groups beyond the end repeat the last one; never stored
-    const int R = q / p.PW, xg = q - R * p.PW;
-    const int jrow = (R + R / p.H + 1) - sig_b - 1;                          // window row of tap ky = 0
+    const int xg = q - q / p.PW * p.PW;
+    const int jrow = slot_of(p, q) - sig_b - 1;                              // window row of tap ky = 0
 #pragma unroll
-    for (int t = 0; t < NTERM; ++t) {
-      const int wx = G * xg + toff[t];
-      const int pp = wx / G, ph = wx - pp * G, swz = (pp >> 2) & 3;
-      const int off = jrow * ROWB + (pp >> 3) * (G * 512) + ph * 512 + (pp & 7) * 64;
+    for (int t = 0; t < NTERM; ++t)
 #pragma unroll
-      for (int ch = 0; ch < 2; ++ch) ap[rt][t][ch] = s_win + off + (((2 * h + ch) ^ swz) << 4);
-    }
+      for (int ch = 0; ch < 2; ++ch) ap[rt][t][ch] = a_addr<G>(s_win, jrow, ROWB, xg, toff[t], 2 * h + ch);
   }
   const char* const bp = s_b + nu * (CT * 2 * 1024) + lane * 16;
 
@@ -218,25 +315,24 @@ __global__ __launch_bounds__(64 * (G + 2) * RH, 1) void wino_x3_kernel(const Win
   auto transform = [&](const Raw& r, bf16x8 (&ah)[RT], bf16x8 (&al)[RT]) {
 #pragma unroll
     for (int rt = 0; rt < RT; ++rt) {
-      float v[8];
+      if constexpr (G == 2) {
+        f23_fragment(r.d[rt], tco[1], ah[rt], al[rt]);
+      } else {                                                // F(4,3): four terms
+        float v[8];
 #pragma unroll
-      for (int c = 0; c < 2; ++c) {
-        const uint32_t e0[4] = {r.d[rt][0][c].x, r.d[rt][0][c].y, r.d[rt][0][c].z, r.d[rt][0][c].w};
-        const uint32_t e1[4] = {r.d[rt][1][c].x, r.d[rt][1][c].y, r.d[rt][1][c].z, r.d[rt][1][c].w};
-        if constexpr (G == 2) {
-#pragma unroll
-          for (int e = 0; e < 4; ++e) v[4 * c + e] = fmaf(tco[1], __uint_as_float(e1[e]), __uint_as_float(e0[e]));     // a + sgn b
-        } else {
+        for (int c = 0; c < 2; ++c) {
+          const uint32_t e0[4] = {r.d[rt][0][c].x, r.d[rt][0][c].y, r.d[rt][0][c].z, r.d[rt][0][c].w};
+          const uint32_t e1[4] = {r.d[rt][1][c].x, r.d[rt][1][c].y, r.d[rt][1][c].z, r.d[rt][1][c].w};
           const uint32_t e2[4] = {r.d[rt][2][c].x, r.d[rt][2][c].y, r.d[rt][2][c].z, r.d[rt][2][c].w};
           const uint32_t e3[4] = {r.d[rt][3][c].x, r.d[rt][3][c].y, r.d[rt][3][c].z, r.d[rt][3][c].w};
 #pragma unroll
           for (int e = 0; e < 4; ++e)
             v[4 * c + e] = fmaf(tco[3], __uint_as_float(e3[e]), fmaf(tco[2], __uint_as_float(e2[e]), fmaf(tco[1], __uint_as_float(e1[e]), tco[0] * __uint_as_float(e0[e]))));
         }
+        const uint4 v0 = make_uint4(__float_as_uint(v[0]), __float_as_uint(v[1]), __float_as_uint(v[2]), __float_as_uint(v[3]));
+        const uint4 v1 = make_uint4(__float_as_uint(v[4]), __float_as_uint(v[5]), __float_as_uint(v[6]), __float_as_uint(v[7]));
+        split_f32x8(v0, v1, ah[rt], al[rt]);
       }
-      const uint4 v0 = make_uint4(__float_as_uint(v[0]), __float_as_uint(v[1]), __float_as_uint(v[2]), __float_as_uint(v[3]));
-      const uint4 v1 = make_uint4(__float_as_uint(v[4]), __float_as_uint(v[5]), __float_as_uint(v[6]), __float_as_uint(v[7]));
-      split_f32x8(v0, v1, ah[rt], al[rt]);
     }
   };
 
@@ -330,47 +426,13 @@ __global__ __launch_bounds__(64 * (G + 2) * RH, 1) void wino_x3_kernel(const Win
 #pragma unroll
       for (int rt = 0; rt < RT; ++rt)
 #pragma unroll
-        for (int ct = 0; ct < CT; ++ct)
-#pragma unroll
-          for (int r = 0; r < 16; ++r)
-            C[(nu * PP + rt * 32 + mfma32_row(r, lane)) * NT + ct * 32 + (lane & 31)] = acc[rt][ct][r];
+        for (int ct = 0; ct < CT; ++ct) stage_acc<PP, NT>(C, nu, rt, ct, lane, acc[rt][ct]);
     }
     __syncthreads();
     for (int item = tid; item < PP * CPR; item += NTHREADS) {
       const int prl = item / CPR, ch4 = (item - prl * CPR) * 4;
-      const int q = q0 + pass * PP + prl;
-      if (q >= q_end) continue;
-      float4 bv = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (p.bias) bv = *(const float4*)(p.bias + n0 + ch4);
-      float4 m[NV];
-#pragma unroll
-      for (int v = 0; v < NV; ++v) m[v] = *(const float4*)(C + (v * PP + prl) * NT + ch4);
-      float4 y[G];
-      if constexpr (G == 2) {
-        y[0] = make_float4(((m[0].x + m[1].x) + m[2].x) * wsc + bv.x, ((m[0].y + m[1].y) + m[2].y) * wsc + bv.y, ((m[0].z + m[1].z) + m[2].z) * wsc + bv.z, ((m[0].w + m[1].w) + m[2].w) * wsc + bv.w);
-        y[1] = make_float4(((m[1].x - m[2].x) - m[3].x) * wsc + bv.x, ((m[1].y - m[2].y) - m[3].y) * wsc + bv.y, ((m[1].z - m[2].z) - m[3].z) * wsc + bv.z, ((m[1].w - m[2].w) - m[3].w) * wsc + bv.w);
-      } else {
-        // y0 = m0 + (m1 + m2) + (m3 + m4); y1 = (m1 - m2) + 2 (m3 - m4); y2 = (m1 + m2) + 4 (m3 + m4); y3 = (m1 - m2) + 8 (m3 - m4) + m5
-#define MCG_W4(F)                                                                                                            \
-        {                                                                                                                    \
-          const float s12 = m[1].F + m[2].F, d12 = m[1].F - m[2].F, s34 = m[3].F + m[4].F, d34 = m[3].F - m[4].F;            \
-          y[0].F = ((m[0].F + s12) + s34) * wsc + bv.F;                                                                      \
-          y[1].F = fmaf(2.f, d34, d12) * wsc + bv.F;                                                                         \
-          y[2].F = fmaf(4.f, s34, s12) * wsc + bv.F;                                                                         \
-          y[3].F = (fmaf(8.f, d34, d12) + m[5].F) * wsc + bv.F;                                                              \
-        }
-        MCG_W4(x) MCG_W4(y) MCG_W4(z) MCG_W4(w)
-#undef MCG_W4
-      }
-      const int R = q / p.PW, xo = G * (q - R * p.PW);
-      float* yp = p.y + ((long long)R * p.W + xo) * p.Cout + n0 + ch4;
-#pragma unroll
-      for (int j = 0; j < G; ++j) {
-        if (xo + j >= p.W) break;
-        float4 o = y[j];
-        if (p.relu) { o.x = fmaxf(o.x, 0.f); o.y = fmaxf(o.y, 0.f); o.z = fmaxf(o.z, 0.f); o.w = fmaxf(o.w, 0.f); }
-        *(float4*)(yp + (long long)j * p.Cout) = o;
-      }
+      const int q = q0 + pass * PP + prl, R = q / p.PW;
+      epilogue_item<G, PP, NT>(p, C, prl, ch4, n0, wsc, R, G * (q - R * p.PW), q < q_end);
     }
     __syncthreads();
   }
@@ -389,8 +451,8 @@ __global__ __launch_bounds__(64 * (G + 2) * RH, 1) void wino_x3_kernel(const Win
 //     instead of one per step; a slice's pieces are issued two to three steps before the barrier that publishes them;
 //   * LDS holds only the two window buffers (96 KiB) in the K loop; the epilogue's staging (two passes of 64 pairs x 128 channels x 4
 //     positions = 128 KiB) overlays them.
-// Per accumulator the arithmetic is the 8-wave kernel's -- K steps in the same order, lo.hi, hi.lo, hi.hi per step, the same output
-// transform -- so the two kernels give the same bits (test_conv3x3_wino_x3_tiles_are_bit_identical covers shape 3 = this kernel).
+// Per accumulator the arithmetic is the 8-wave kernel's -- K steps in the same order, lo.hi, hi.lo, hi.hi per step, the shared input and
+// output transforms -- so the two kernels give the same bits (test_conv3x3_wino_x3_tiles_are_bit_identical covers shape 3 = this kernel).
 typedef uint32_t u32x4v __attribute__((ext_vector_type(4)));
 template <int IMM>
 __device__ __forceinline__ void buf_load16(u32x4v& dst, uint32_t voffset, const u32x4& srd, uint32_t soffset_uniform) {
@@ -400,12 +462,12 @@ __device__ __forceinline__ void buf_load16(u32x4v& dst, uint32_t voffset, const 
 // BLK (wino_x3w_blocks_kernel, the deferred FPN P2 conv -- DESIGN.md 3.1i): the same kernel whose four row tiles are four 8 x 8-pixel
 // BLOCKS (8 rows x 4 pairs = 32 pairs each) taken from a device list, so that a conv can compute only the blocks somebody reads.  The
 // window holds, per block, its 10 rows (one halo row above and below) of ONE 1 KiB piece (16 pixels from the block's first column - 1:
-// the block's 10 input columns), 40 pieces in all; the piece layout, swizzle, K order, transform and epilogue arithmetic are the raster
-// tile's, so a block's bits are those of the same pixels in wino_x3w_kernel (tests/test_gpu_fpn_deferred.py).
+// the block's 10 input columns), 40 pieces in all; only where a row and a pair lie differs from the raster tile, so a block's bits are
+// those of the same pixels in wino_x3w_kernel (tests/test_gpu_fpn_deferred.py).
 template <int NB, bool BLK>
 __device__ __forceinline__ void wino_x3w_tile(const WinoParams& p, const int logical) {
   using namespace wnx;
-  constexpr int G = 2, NV = 4, NW = 4, RT = 4, CT = 4, MT = 128, NT = 128;
+  constexpr int G = 2, NW = 4, RT = 4, CT = 4, MT = 128, NT = 128;
   constexpr int ROWB = NB * 1024, WIN_CAP = 48 * 1024, USTAGE = ustage(2);
   constexpr int MAXP = WIN_CAP / 1024 / NW;            // window pieces per wave and slice (upper bound): 12, issued as two batches of 6
   constexpr int HB = MAXP / 2;
@@ -431,21 +493,12 @@ __device__ __forceinline__ void wino_x3w_tile(const WinoParams& p, const int log
       bf[rt] = f; by0[rt] = 8 * by; bxg[rt] = 4 * (r - by * p.bxn);
     }
   } else {
-    if (p.tpf > 0) {
-      const int f = mt / p.tpf, t = mt - f * p.tpf;
-      q0 = f * p.gpf + t * MT;
-      q_end = min(q0 + MT, (f + 1) * p.gpf);
-    } else {
-      q0 = mt * MT;
-      q_end = min(q0 + MT, p.total_pairs);
-    }
+    tile_range(p, mt, MT, q0, q_end);
   }
   auto pick = [&](const int (&a)[RT], int i) { return i == 0 ? a[0] : (i == 1 ? a[1] : (i == 2 ? a[2] : a[3])); };
   const int q_last = q_end - 1;
-  const int H1 = p.H + 1;
-  auto slot_of = [&](int q) { const int R = q / p.PW; return R + R / p.H + 1; };
-  const int sig_b = BLK ? 0 : __builtin_amdgcn_readfirstlane(slot_of(q0) - 1);
-  const int NP = BLK ? RT * BWR : __builtin_amdgcn_readfirstlane((slot_of(q_last) - sig_b + 2) * NB);
+  const int sig_b = BLK ? 0 : __builtin_amdgcn_readfirstlane(slot_of(p, q0) - 1);
+  const int NP = BLK ? RT * BWR : __builtin_amdgcn_readfirstlane((slot_of(p, q_last) - sig_b + 2) * NB);
   const int NSL = p.Cin / KS, KT = 3 * NSL;
   const int n0 = ntile * NT;
   const u32x4 srd_x = make_srd(p.x);
@@ -465,28 +518,23 @@ __device__ __forceinline__ void wino_x3w_tile(const WinoParams& p, const int log
       const bool rowok = y >= 0 && y < p.H;
       if (pi < NP && ((bokm >> rb) & 1)) pokm |= 1u << n;
       if (rowok) prowokm |= 1u << n;
-      prow[n] = __builtin_amdgcn_readfirstlane((uint32_t)(((long long)(f * p.H + (rowok ? y : 0)) * p.W) * p.Cin * 4));
+      prow[n] = __builtin_amdgcn_readfirstlane(row_base(p, f, rowok ? y : 0));
       pxo[n] = __builtin_amdgcn_readfirstlane(2 * pick(bxg, rb));
     } else {
-      const int j = pi / NB;
-      const int sg = sig_b + j, f = sg / H1, r = sg - f * H1;
+      const WinRow row = win_row(p, sig_b + pi / NB);
       if (pi < NP) pokm |= 1u << n;
-      if (r != 0 && f < p.frames) prowokm |= 1u << n;
-      prow[n] = __builtin_amdgcn_readfirstlane((uint32_t)(((long long)(f * p.H + r - 1) * p.W) * p.Cin * 4));
+      if (row.ok) prowokm |= 1u << n;
+      prow[n] = __builtin_amdgcn_readfirstlane(row.base);
       pxo[n] = 0;
     }
   });
   pokm = __builtin_amdgcn_readfirstlane(pokm);
   prowokm = __builtin_amdgcn_readfirstlane(prowokm);
-  uint32_t w_voff;
-  int l_x;                                              // BLK: this lane's pixel relative to a piece's block column
-  {
-    const int l_ph = lane >> 5, l_i = (lane >> 2) & 7, l_cs = lane & 3, b = wave & (NB - 1);
-    const int x = (8 * b + l_i) * G + l_ph - 1;
-    const int c = l_cs ^ ((2 * b + (l_i >> 2)) & 3);
-    l_x = x;
-    w_voff = BLK ? (uint32_t)(4 * c * 4) : ((unsigned)x < (unsigned)p.W ? (uint32_t)((x * p.Cin + 4 * c) * 4) : MCG_OOB_OFFSET);
-  }
+  // this lane's part of every piece of the wave (they all are piece wave % NB of their rows): its pixel (BLK: relative to the block's
+  // first column) and its offset in the row (BLK: of its channel chunk alone, the pixel depends on the piece's block)
+  int l_x, l_c;
+  win_lane<G>(lane, wave & (NB - 1), l_x, l_c);
+  const uint32_t w_voff = BLK ? (uint32_t)(4 * l_c * 4) : win_voff(p, l_x, l_c);
   auto piece_voff = [&](auto nc) -> uint32_t {
     constexpr int n = decltype(nc)::value;
     if (!(prowokm & (1u << n))) return MCG_OOB_OFFSET;
@@ -516,9 +564,10 @@ __device__ __forceinline__ void wino_x3w_tile(const WinoParams& p, const int log
     else buf_load16<(J & 3) * 1024>(bh[SLX][J >> 1], b_voff, srd_u, koff + (J >> 2) * 4096u);
   };
 
-  // ---- input transform of this wave's position: V = d[toff0] + sgn d[toff1]
-  const int toff0 = nu == 0 ? 0 : 1, toff1 = nu == 3 ? 3 : 2;
-  const float tsg = nu == 1 ? 1.f : -1.f;
+  // ---- input transform of this wave's position: V = d[toff[0]] + tsg d[toff[1]]
+  int toff[2];
+  float tsg;
+  f23_position(nu, toff, tsg);
   const int pl = lane & 31, h = lane >> 5;
   const char* ap[RT][2][2];                               // window buffer 0, tap ky = 0
 #pragma unroll
@@ -529,18 +578,13 @@ __device__ __forceinline__ void wino_x3w_tile(const WinoParams& p, const int log
       xg = pl & 3;
     } else {
       const int q = min(q0 + rt * 32 + pl, q_last);
-      const int R = q / p.PW;
-      xg = q - R * p.PW;
-      jrow = (R + R / p.H + 1) - sig_b - 1;
+      xg = q - q / p.PW * p.PW;
+      jrow = slot_of(p, q) - sig_b - 1;
     }
 #pragma unroll
-    for (int t = 0; t < 2; ++t) {
-      const int wx = G * xg + (t == 0 ? toff0 : toff1);
-      const int pp = wx / G, ph = wx - pp * G, swz = (pp >> 2) & 3;
-      const int off = jrow * ROWB + (pp >> 3) * (G * 512) + ph * 512 + (pp & 7) * 64;
+    for (int t = 0; t < 2; ++t)
 #pragma unroll
-      for (int ch = 0; ch < 2; ++ch) ap[rt][t][ch] = s_win + off + (((2 * h + ch) ^ swz) << 4);
-    }
+      for (int ch = 0; ch < 2; ++ch) ap[rt][t][ch] = a_addr<G>(s_win, jrow, ROWB, xg, toff[t], 2 * h + ch);
   }
 
   f32x16 acc[RT][CT];
@@ -559,22 +603,6 @@ __device__ __forceinline__ void wino_x3w_tile(const WinoParams& p, const int log
 #pragma unroll
       for (int t = 0; t < 2; ++t) { r.d[rt][t][0] = *(const uint4*)(ap[rt][t][0] + AOFF); r.d[rt][t][1] = *(const uint4*)(ap[rt][t][1] + AOFF); }
   };
-  auto transform = [&](const Raw& r, bf16x8 (&ah)[RT], bf16x8 (&al)[RT]) {
-#pragma unroll
-    for (int rt = 0; rt < RT; ++rt) {
-      float v[8];
-#pragma unroll
-      for (int c = 0; c < 2; ++c) {
-        const uint32_t e0[4] = {r.d[rt][0][c].x, r.d[rt][0][c].y, r.d[rt][0][c].z, r.d[rt][0][c].w};
-        const uint32_t e1[4] = {r.d[rt][1][c].x, r.d[rt][1][c].y, r.d[rt][1][c].z, r.d[rt][1][c].w};
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[4 * c + e] = fmaf(tsg, __uint_as_float(e1[e]), __uint_as_float(e0[e]));
-      }
-      const uint4 v0 = make_uint4(__float_as_uint(v[0]), __float_as_uint(v[1]), __float_as_uint(v[2]), __float_as_uint(v[3]));
-      const uint4 v1 = make_uint4(__float_as_uint(v[4]), __float_as_uint(v[5]), __float_as_uint(v[6]), __float_as_uint(v[7]));
-      split_f32x8(v0, v1, ah[rt], al[rt]);
-    }
-  };
 
   // ---- prologue: slice 0 (both batches), the weights of step 0, the first batch of slice 1
   issue_window(std::integral_constant<int, 0>{}, 0, lds_win);
@@ -587,7 +615,8 @@ __device__ __forceinline__ void wino_x3w_tile(const WinoParams& p, const int log
   {
     Raw r0;
     load_raw(std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{}, r0);
-    transform(r0, fh[0], fl[0]);
+#pragma unroll
+    for (int rt = 0; rt < RT; ++rt) f23_fragment(r0.d[rt], tsg, fh[0][rt], fl[0][rt]);
   }
   constexpr int NM1 = RT * CT;
   uint32_t nh[RT][4], nl[RT][4];                          // the next step's A fragments while they are being made
@@ -641,11 +670,8 @@ __device__ __forceinline__ void wino_x3w_tile(const WinoParams& p, const int log
         constexpr int Q = decltype(qc)::value, I = Q & 3, TERM3 = Q >> 2;
         constexpr int XR = Q >> 1, XC = Q & 1;               // transform unit: row tile XR, 16-byte chunk XC of the next step's A fragment
         {
-          const uint32_t e0[4] = {raw.d[XR][0][XC].x, raw.d[XR][0][XC].y, raw.d[XR][0][XC].z, raw.d[XR][0][XC].w};
-          const uint32_t e1[4] = {raw.d[XR][1][XC].x, raw.d[XR][1][XC].y, raw.d[XR][1][XC].z, raw.d[XR][1][XC].w};
           float v[4];
-#pragma unroll
-          for (int e = 0; e < 4; ++e) v[e] = fmaf(tsg, __uint_as_float(e1[e]), __uint_as_float(e0[e]));
+          f23_chunk(raw.d[XR][0][XC], raw.d[XR][1][XC], tsg, v);
           split_pair(v[0], v[1], nh[XR][2 * XC], nl[XR][2 * XC]);
           split_pair(v[2], v[3], nh[XR][2 * XC + 1], nl[XR][2 * XC + 1]);
         }
@@ -689,40 +715,17 @@ __device__ __forceinline__ void wino_x3w_tile(const WinoParams& p, const int log
 #pragma unroll
     for (int rt = 0; rt < 2; ++rt)
 #pragma unroll
-      for (int ct = 0; ct < CT; ++ct)
-#pragma unroll
-        for (int r = 0; r < 16; ++r)
-          C[(nu * PP + rt * 32 + mfma32_row(r, lane)) * NT + ct * 32 + (lane & 31)] = acc[2 * pass + rt][ct][r];
+      for (int ct = 0; ct < CT; ++ct) stage_acc<PP, NT>(C, nu, rt, ct, lane, acc[2 * pass + rt][ct]);
     __syncthreads();
     for (int item = tid; item < PP * CPR; item += 256) {
       const int prl = item / CPR, ch4 = (item - prl * CPR) * 4;
-      int R, xo;
-      if constexpr (BLK) {
+      if constexpr (BLK) {                                 // pair prl & 31 of block 2 pass + (prl >> 5): row pl / 4, pair pl % 4 of the block
         const int rt = 2 * pass + (prl >> 5), pl = prl & 31;
-        const int y = pick(by0, rt) + (pl >> 2);
-        xo = G * (pick(bxg, rt) + (pl & 3));
-        if (!((bokm >> rt) & 1) || y >= p.H || xo >= p.W) continue;
-        R = pick(bf, rt) * p.H + y;
+        const int y = pick(by0, rt) + (pl >> 2), xo = G * (pick(bxg, rt) + (pl & 3));
+        epilogue_item<G, PP, NT>(p, C, prl, ch4, n0, wsc, pick(bf, rt) * p.H + y, xo, ((bokm >> rt) & 1) && y < p.H && xo < p.W);
       } else {
-        const int q = q0 + pass * PP + prl;
-        if (q >= q_end) continue;
-        R = q / p.PW; xo = G * (q - R * p.PW);
-      }
-      float4 bv = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (p.bias) bv = *(const float4*)(p.bias + n0 + ch4);
-      float4 m[NV];
-#pragma unroll
-      for (int v = 0; v < NV; ++v) m[v] = *(const float4*)(C + (v * PP + prl) * NT + ch4);
-      float4 y[2];
-      y[0] = make_float4(((m[0].x + m[1].x) + m[2].x) * wsc + bv.x, ((m[0].y + m[1].y) + m[2].y) * wsc + bv.y, ((m[0].z + m[1].z) + m[2].z) * wsc + bv.z, ((m[0].w + m[1].w) + m[2].w) * wsc + bv.w);
-      y[1] = make_float4(((m[1].x - m[2].x) - m[3].x) * wsc + bv.x, ((m[1].y - m[2].y) - m[3].y) * wsc + bv.y, ((m[1].z - m[2].z) - m[3].z) * wsc + bv.z, ((m[1].w - m[2].w) - m[3].w) * wsc + bv.w);
-      float* yp = p.y + ((long long)R * p.W + xo) * p.Cout + n0 + ch4;
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        if (xo + j >= p.W) break;
-        float4 o = y[j];
-        if (p.relu) { o.x = fmaxf(o.x, 0.f); o.y = fmaxf(o.y, 0.f); o.z = fmaxf(o.z, 0.f); o.w = fmaxf(o.w, 0.f); }
-        *(float4*)(yp + (long long)j * p.Cout) = o;
+        const int q = q0 + pass * PP + prl, R = q / p.PW;
+        epilogue_item<G, PP, NT>(p, C, prl, ch4, n0, wsc, R, G * (q - R * p.PW), q < q_end);
       }
     }
     __syncthreads();
@@ -761,17 +764,21 @@ static inline int wino_x3_max_rows(int H, int W, int mt, int g, bool cross) {
   return rows + nz + 2;
 }
 static inline int wino_x3_nb_template(int pieces) { return pieces <= 1 ? 1 : (pieces <= 2 ? 2 : 4); }
-// 3x3 / stride 1 / pad 1, f16x3: channel counts the tiles divide, a window that fits its buffer, operands inside the 2 GiB descriptor.
+// What every tile needs of a conv: channel counts the tiles divide, operands inside the 2 GiB descriptor
+static inline bool wino_x3_operands_ok(int frames, int H, int W, int Cin, int Cout) {
+  const long long px = (long long)frames * H * W;
+  return Cin % 32 == 0 && Cout % wnx::UNT == 0 && H >= 1 && W >= 2 && frames >= 1 && px * Cin * 4 < MCG_DMA_MAX_BYTES &&
+         px * Cout * 4 < MCG_DMA_MAX_BYTES && px < 0x7fffffffLL;
+}
+// 3x3 / stride 1 / pad 1, f16x3: the above and a window that fits its buffer.
 // Decided by the LAYER's shape only (never by the batch): a layer either runs this arithmetic or the direct kernel's for every batch size.
 // -> 0 not applicable, 1 tiles may run over frame boundaries, 2 tiles must be cut at frame boundaries (the window buffer holds no zero row)
 static inline int wino_x3_mode(int frames, int H, int W, int Cin, int Cout, int g) {
-  if (Cin % 32 != 0 || Cout % wnx::UNT != 0 || H < 1 || W < 2 || frames < 1 || (g != 2 && g != 4)) return 0;
+  if (!wino_x3_operands_ok(frames, H, W, Cin, Cout) || (g != 2 && g != 4)) return 0;
   if (g == 4 && (W % 4 != 0 || W < 16)) return 0;       // F(4,3) only where a row is whole groups and wide enough to pay
   const int pcs = wino_x3_pieces(W, g);
   if (pcs > 4) return 0;
   const int nb = wino_x3_nb_template(pcs);
-  const long long px = (long long)frames * H * W;
-  if (!(px * Cin * 4 < MCG_DMA_MAX_BYTES && px * Cout * 4 < MCG_DMA_MAX_BYTES && px < 0x7fffffffLL)) return 0;
   const int mt = wino_x3_tile_groups(g, 0), cap = wnx::wcap(g, 4);
   if (wino_x3_max_rows(H, W, mt, g, true) * nb * 1024 <= cap) return 1;
   if (wino_x3_max_rows(H, W, mt, g, false) * nb * 1024 <= cap) return 2;
@@ -783,27 +790,14 @@ static inline size_t wino_x3_weight_bytes(int Cin, int Cout, int g = 2) { return
 template <int NB, int RH, int RT, int CT, int G>
 static inline int launch_wino_x3_t(hipStream_t s, const WinoParams& p, int grid) {
   constexpr int kLds = 2 * wnx::wcap(G, CT) + 2 * ((G + 2) * CT * 2 * 1024);
-  static bool raised[MCG_MAX_DEVICES] = {false};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MCG_MAX_DEVICES) dev = 0;
-  if (!raised[dev]) {
-    if (hipFuncSetAttribute((const void*)wino_x3_kernel<NB, RH, RT, CT, G>, hipFuncAttributeMaxDynamicSharedMemorySize, kLds) != hipSuccess) return 1;
-    raised[dev] = true;
-  }
+  if (kernel_ready<wino_x3_kernel<NB, RH, RT, CT, G>>(kLds)) return 1;
   hipLaunchKernelGGL((wino_x3_kernel<NB, RH, RT, CT, G>), dim3(grid), dim3(64 * (G + 2) * RH), kLds, s, p);
   return hipGetLastError() == hipSuccess ? 0 : 1;
 }
 template <int NB>
 static inline int launch_wino_x3w(hipStream_t s, const WinoParams& p, int grid) {
-  constexpr int kLds = 4 * 64 * 128 * 4;                 // epilogue staging (the K loop uses the first 96 KiB: two window buffers)
-  static bool raised[MCG_MAX_DEVICES] = {false};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MCG_MAX_DEVICES) dev = 0;
-  if (!raised[dev]) {
-    if (hipFuncSetAttribute((const void*)wino_x3w_kernel<NB>, hipFuncAttributeMaxDynamicSharedMemorySize, kLds) != hipSuccess) return 1;
-    raised[dev] = true;
-  }
-  hipLaunchKernelGGL((wino_x3w_kernel<NB>), dim3(grid), dim3(256), kLds, s, p);
+  if (kernel_ready<wino_x3w_kernel<NB>>(wnx::W_LDS)) return 1;
+  hipLaunchKernelGGL((wino_x3w_kernel<NB>), dim3(grid), dim3(256), wnx::W_LDS, s, p);
   return hipGetLastError() == hipSuccess ? 0 : 1;
 }
 template <int NB>
@@ -816,33 +810,19 @@ static inline int launch_wino_x3_nb(hipStream_t s, const WinoParams& p, int g, i
 }
 // Block tile (8 x 8-pixel blocks, F(2,3)): the shapes whose window fits (any W a block's 16-pixel piece serves) and whose operands fit the
 // buffer descriptors -- the same arithmetic as launch_wino_x3 on them.  blk_grid: workgroups of the persistent launch.
-static inline bool wino_x3_blocks_applicable(int frames, int H, int W, int Cin, int Cout) {
-  const long long px = (long long)frames * H * W;
-  return Cin % 32 == 0 && Cout % wnx::UNT == 0 && H >= 1 && W >= 2 && frames >= 1 && px * Cin * 4 < MCG_DMA_MAX_BYTES &&
-         px * Cout * 4 < MCG_DMA_MAX_BYTES && px < 0x7fffffffLL;
-}
+static inline bool wino_x3_blocks_applicable(int frames, int H, int W, int Cin, int Cout) { return wino_x3_operands_ok(frames, H, W, Cin, Cout); }
 static inline int wino_x3_blocks_per_frame(int H, int W) { return ((H + 7) / 8) * ((W + 7) / 8); }
 static inline int launch_wino_x3_blocks(hipStream_t s, WinoParams p, const int* list, const int* count, int max_blocks) {
-  constexpr int kLds = 4 * 64 * 128 * 4;
-  static bool raised[MCG_MAX_DEVICES] = {false};
-  static int cus[MCG_MAX_DEVICES] = {0};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MCG_MAX_DEVICES) dev = 0;
-  if (!raised[dev]) {
-    if (hipFuncSetAttribute((const void*)wino_x3w_blocks_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kLds) != hipSuccess) return 1;
-    int n = 0;
-    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-    cus[dev] = n;
-    raised[dev] = true;
-  }
+  int cus;
+  if (kernel_ready<wino_x3w_blocks_kernel>(wnx::W_LDS, &cus)) return 1;
   p.PW = (p.W + 1) / 2;
   p.n_tiles = p.Cout / 128;
   p.bxn = (p.W + 7) / 8;
   p.bpf = wino_x3_blocks_per_frame(p.H, p.W);
   p.blk_list = list; p.blk_count = count;
   const int units = (max_blocks + 3) / 4 * p.n_tiles;
-  const int grid = units < cus[dev] ? units : cus[dev] / 16 * 16;
-  hipLaunchKernelGGL(wino_x3w_blocks_kernel, dim3(grid > 0 ? grid : 1), dim3(256), kLds, s, p);
+  const int grid = units < cus ? units : cus / 16 * 16;
+  hipLaunchKernelGGL(wino_x3w_blocks_kernel, dim3(grid > 0 ? grid : 1), dim3(256), wnx::W_LDS, s, p);
   return hipGetLastError() == hipSuccess ? 0 : 1;
 }
 // returns 0 on success; the caller has checked wino_x3_applicable(.., g).  shape: -1 = by grid size (the largest tile that still makes ~half
