@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define MCG_ABI_VERSION 16
+#define MCG_ABI_VERSION 17
 
 enum { MCG_OK = 0, MCG_ERR_ARG = 1, MCG_ERR_HIP = 2, MCG_ERR_UNSUPPORTED = 3, MCG_ERR_WORKSPACE = 4 };
 /* MCG_F16X3: the parity-grade fast mode.  Activations, biases and every non-GEMM kernel are exactly those of MCG_F32 (4-byte
@@ -424,6 +424,17 @@ int mcg_clip_forward(mcg_engine* e, mcg_stream s, const float* img, int num_fram
 int mcg_clip_forward_ragged(mcg_engine* e, mcg_stream s, const float* img, int num_frames, const int* clip_start, int num_clips,
                             int max_clip_length, int H, int W, const int* img_hw, int chunk_frames, float* gaze_out, float* boxes_out,
                             float* scores_out, void* ws, size_t ws_bytes);
+/* ABI 17: a pyramid store SHARED by many live streams.  The reference's harness runs one sliding window of one video per call
+ * (tools/test_gaze360_gaze.py:72-111) and its demo one clip per tracked person (MCGaze_demo/demo.ipynb, cell 4); with S cameras or
+ * people that is S trunk calls of one new frame each per tick.  Batched across streams, one trunk call takes every stream's new frames --
+ * and their rows in the shared store are whatever rows are free, in no order (streams of different pace free rows out of order).
+ * Copies frame n of src (a contiguous NHWC pyramid of num_frames frames, as mcg_backbone_fpn_forward writes it) to row row_of[n] of dst
+ * (a store of store_rows frames per level), all four levels in one launch.  row_of: DEVICE int32[num_frames].  A row outside
+ * [0, store_rows) is skipped (nothing is written for that frame); two frames naming one row is the caller's error (host-checked in Python,
+ * mcgaze_amd/engine.py::check_row_table).  Level pointers 16-byte aligned; H, W multiples of 32; at most 65535 frames per call.
+ * No allocation, no host sync, graph-capturable. */
+int mcg_pyramid_scatter_rows(mcg_stream s, mcg_dtype dt, const void* const src[4], void* const dst[4],
+                             int num_frames, int store_rows, int H, int W, const int32_t* row_of);
 
 /* ---------------------------------------------------------------- test-time preprocessing
  * One launch replaces the per-frame CPU transforms the reference's test pipeline applies between image decode and the model

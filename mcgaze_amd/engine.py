@@ -191,6 +191,20 @@ def check_frame_table(frame_of, pyramid_frames, clip_length):
     return a.astype(np.int32)
 
 
+def check_row_table(rows, store_rows, num_frames):
+    """Host-side check of a frame -> store-row table (backbone_fpn_rows): a sequence (or CPU tensor) of num_frames integers, every entry in
+    [0, store_rows), no row named twice.  -> int32 numpy array.  McgError otherwise (nothing reaches the device)."""
+    a = _flat_ints(rows, 'rows must be a flat sequence of row indices', 'rows must be a flat sequence of integer row indices', False)
+    if a.size != int(num_frames):
+        raise L.McgError(f'rows holds {a.size} entries for {int(num_frames)} frames')
+    if a.size and (store_rows < 1 or int(a.min()) < 0 or int(a.max()) >= store_rows):
+        raise L.McgError(f'rows entries must lie in [0, {store_rows}) (got {int(a.min())} .. {int(a.max())})')
+    if a.size > 1 and len(set(a.tolist())) != a.size:
+        u, n = np.unique(a, return_counts=True)
+        raise L.McgError(f'rows names row {int(u[n.argmax()])} for {int(n.max())} frames: every frame needs a row of its own')
+    return a.astype(np.int32)
+
+
 def check_clip_lengths(lengths, num_frames):
     """Host-side check of a ragged batch's clip lengths: a non-empty flat sequence of positive integers summing to num_frames
     (None: any sum).
@@ -338,6 +352,7 @@ class HipEngine:
             L.check(self.lib.mcg_engine_create(C.byref(self._handle), C.byref(mw), self.code), 'mcg_engine_create')
         self._ws = None
         self._dec_ws = None
+        self._row_ws = None
 
     def set_option(self, name, value):
         """mcg_engine_set_option: 'trunk_streams', 'max_range_frames', 'tile', 'staged_gemm', 'conv3x3_c64', 'stem_fused',
@@ -429,6 +444,36 @@ class HipEngine:
             L.check(self.lib.mcg_backbone_fpn_forward(self._handle, _stream(self.device), _ptr(img), N, H, W, chunk_frames, tab, _ptr(ws), ws.numel()),
                     'mcg_backbone_fpn_forward')
         return pyr
+
+    def backbone_fpn_rows(self, img, store_levels, rows, chunk_frames=0):
+        """backbone_fpn into ARBITRARY rows of a pyramid store: frame n of img [N,3,H,W] is written to row rows[n] of store_levels (four
+        per-level tensors like backbone_fpn's ``out``).  rows: a host sequence of N distinct rows, checked here (check_row_table: McgError
+        before anything reaches the device).  The trunk runs into a scratch pyramid the engine owns (grown on demand, reused), then ONE
+        launch copies every frame to its row (mcg_pyramid_scatter_rows) on the same stream: a row holds the bits backbone_fpn(out=, row=)
+        writes.  Rows that are one ascending run (a single frame always is) need no copy: the trunk writes them in place, at the run's row
+        offset.  -> store_levels."""
+        K = store_levels[0].shape[0] if len(store_levels) else 0
+        table = check_row_table(rows, K, img.shape[0])
+        if table.size and bool((np.diff(table) == 1).all()):
+            return self.backbone_fpn(img, chunk_frames, out=store_levels, row=int(table[0]))
+        self._check_img(img)
+        N, _, H, W = img.shape
+        shapes = [((H // 4) >> i, (W // 4) >> i, 256) for i in range(4)]
+        self._check_pyramid(store_levels, shapes)
+        if N == 0:
+            return store_levels
+        with torch.cuda.device(self.device):
+            es = store_levels[0].element_size()
+            sizes = [N * s[0] * s[1] * s[2] * es for s in shapes]          # multiples of 512: every level of the scratch stays aligned
+            scratch = self._grown('_row_ws', sum(sizes))
+            src = (C.c_void_p * 4)(*[scratch.data_ptr() + sum(sizes[:i]) for i in range(4)])
+            dst = (C.c_void_p * 4)(*[p.data_ptr() for p in store_levels])
+            ws = self._workspace(N, H, W, chunk_frames)
+            L.check(self.lib.mcg_backbone_fpn_forward(self._handle, _stream(self.device), _ptr(img), N, H, W, chunk_frames, src, _ptr(ws), ws.numel()),
+                    'mcg_backbone_fpn_forward')
+            dev_rows = _upload_table(table, self.device)
+            L.check(self.lib.mcg_pyramid_scatter_rows(_stream(self.device), self.code, src, dst, N, K, H, W, _ptr(dev_rows)), 'mcg_pyramid_scatter_rows')
+        return store_levels
 
     def _check_pyramid(self, pyramid, shapes=None):
         """-> rows K of a pyramid store (four contiguous [K,h,w,256] tensors of the engine dtype on its device, h, w halving per level)."""

@@ -11,12 +11,17 @@ mcg_decoder_forward_indexed, the gather happens inside the RoIAlign read).
     already certain and below which frame no later window can reach.
   * ``StreamMerger``: the overlap merge of ``harness.merge_video`` applied window by window, handing out frames once they are final.
   * ``GazeStream``: push frames as they arrive, get back the per-frame results that became final; ``finish()`` returns the rest.
+  * ``PyramidStore`` / ``GazeStreamPool``: MANY streams at once (S cameras, or the reference demo's one clip per tracked person,
+    MCGaze_demo/demo.ipynb cell 4, each the sliding-window loop of tools/test_gaze360_gaze.py:72-111): one store shared by all streams,
+    rows handed out from a free list; per tick ONE trunk call over every stream's new frames, scattered into whichever rows are free
+    (``HipEngine.backbone_fpn_rows`` -> mcg_pyramid_scatter_rows), and ONE indexed, ragged decoder call over every stream's newly certain
+    windows.  Per stream the same planner, merger and bits as a lone ``GazeStream``.
 """
 import numpy as np
 import torch
 
 from . import lib as L
-from .harness import _host, clip_outputs, merge_window, plan_windows
+from .harness import _host, bucket_key, clip_outputs, merge_window, plan_windows
 
 
 class WindowPlanner:
@@ -240,3 +245,249 @@ class GazeStream:
         if wins:
             self._decode(wins)
         return self._emit(self.planner.frames)
+
+
+class PyramidStore:
+    """A pyramid store SHARED by many streams: ``rows`` frames per level, handed out from a free list in no particular order (streams of
+    different pace free their rows out of order, so a ring of one head would be pinned by its slowest stream).
+
+    ``alloc(n)`` -> n free rows (McgError when fewer are free: a live row is never handed out again before ``free`` returned it);
+    ``write(frames, rows)`` runs the trunk on the frames and writes frame i to rows[i] (``HipEngine.backbone_fpn_rows``).  ``hw`` holds
+    img_shape per row once any frame came with one (the decoder reads it by row), like ``PyramidRing.hw``."""
+
+    def __init__(self, engine, rows, H, W):
+        if rows < 1:
+            raise L.McgError(f'PyramidStore: rows must be positive (got {rows})')
+        self.e, self.rows, self.H, self.W = engine, int(rows), H, W
+        self.levels = [torch.empty(self.rows, (H // 4) >> i, (W // 4) >> i, 256, dtype=engine.dtype, device=engine.device) for i in range(4)]
+        self.hw = None
+        self._free = list(range(self.rows - 1, -1, -1))     # a stack: the lowest rows go out first
+        self._live = set()
+
+    def free_rows(self):
+        return len(self._free)
+
+    def alloc(self, n):
+        if n > len(self._free):
+            raise L.McgError(f'PyramidStore: {n} rows asked for, {len(self._free)} of {self.rows} are free')
+        rows = [self._free.pop() for _ in range(n)]
+        self._live.update(rows)
+        return rows
+
+    def free(self, rows):
+        for r in rows:
+            if r not in self._live:
+                raise L.McgError(f'PyramidStore: row {r} is freed but was not handed out')
+            self._live.remove(r)
+            self._free.append(r)
+
+    def write(self, frames, rows, img_hw=None):
+        """frames [n,3,H,W] f32 -> rows[i] of every level holds frame i's pyramid; img_hw [n,2] or None (every frame fills H x W)."""
+        n = frames.shape[0]
+        if tuple(frames.shape[1:]) != (3, self.H, self.W):
+            raise L.McgError(f'PyramidStore: frames must be [n,3,{self.H},{self.W}] (got {tuple(frames.shape)})')
+        rows = [int(r) for r in rows]
+        if len(rows) != n or any(r not in self._live for r in rows):
+            raise L.McgError(f'PyramidStore: write() takes one row from alloc() per frame (got {len(rows)} rows for {n} frames)')
+        self.e.backbone_fpn_rows(frames.to(self.e.device, torch.float32).contiguous(), self.levels, rows)
+        if img_hw is not None and self.hw is None:
+            self.hw = torch.empty(self.rows, 2, dtype=torch.int32, device=self.e.device)
+            self.hw[:, 0], self.hw[:, 1] = self.H, self.W       # = what the decoder assumes without a table
+        if self.hw is not None and n:
+            hw = (np.array([[self.H, self.W]] * n, dtype=np.int32) if img_hw is None else np.asarray(_host(img_hw), dtype=np.int32).reshape(n, 2))
+            self.hw[torch.as_tensor(rows, dtype=torch.int64).to(self.e.device)] = torch.from_numpy(hw).to(self.e.device)
+        return rows
+
+
+class _PoolStream:
+    """One stream of a GazeStreamPool: its plan, its merge, where its live frames lie in the store and the frames pushed but not run yet."""
+
+    def __init__(self, clip_len, stride, person_threshold):
+        self.planner = WindowPlanner(clip_len, stride)
+        self.merger = StreamMerger(person_threshold)
+        self.row_of = {}         # frame index -> store row, for the frames a later window may still read
+        self.queue = []          # (frames [n,3,H,W], img_hw [n,2] numpy or None) in push order
+        self.queued = 0
+        self.closed = False
+        self.admitted = False    # holds a reservation of clip_len + stride rows
+        self.emitted = 0
+        self.released = 0        # frames below this index gave their rows back
+
+    def take(self, m):
+        """The first m queued frames -> ([frames...], [img_hw or None per part])."""
+        parts, hws = [], []
+        while m:
+            x, hw = self.queue[0]
+            k = min(m, x.shape[0])
+            parts.append(x[:k])
+            hws.append(None if hw is None else hw[:k])
+            if k == x.shape[0]:
+                self.queue.pop(0)
+            else:
+                self.queue[0] = (x[k:], None if hw is None else hw[k:])
+            m -= k
+            self.queued -= k
+        return parts, hws
+
+
+class GazeStreamPool:
+    """Gaze on MANY live feeds at once -- S cameras, or S tracked people (one clip per person, like the reference demo): ``push`` queues a
+    stream's new frames, ``step`` runs every stream's queued frames through ONE trunk call into a shared ``PyramidStore`` and every
+    stream's newly certain windows through ONE indexed, ragged decoder call (per longest-clip class, ``harness.bucket_key``), where S
+    ``GazeStream`` objects make S calls of each.
+
+        pool = GazeStreamPool(engine, H, W)
+        sid = pool.open()
+        pool.push(sid, frames)            # queues only: no GPU work
+        for sid, r in pool.step().items():  # r = dict(first, det, fused, others): the frames of stream sid that became final
+            ...
+        pool.close(sid)                   # its last windows run in the next step(); then the stream is gone and its rows are free
+
+    Contract: for every stream the concatenation of what ``step`` returned for it equals, bit for bit, a lone ``GazeStream`` fed the same
+    frames in the same order -- so also ``harness.merge_video(plan_windows(L), [one engine.forward per window])`` -- however the other
+    streams' pushes, lengths and closes interleave with it.  It rests on the trunk giving a frame the same bits in any batch and on the
+    decoder giving a window the same bits whichever windows share its call.  The fp16 engine (precision 'f16') keeps the latter only below
+    256 tokens per call: give it ``max_decode_windows`` <= 12 at clip_len 7.
+
+    rows: rows of the shared store (default 64 * (clip_len + stride) + max_trunk_frames).  A stream that runs holds a reservation of
+    clip_len + stride rows, so it can always reach its next window; a ``step`` that finds fewer rows free than the queued frames need runs
+    what fits -- a part of a stream's queue, or none of a stream that cannot get its reservation yet -- and leaves the rest queued for the
+    next ``step`` (``pending()`` says whether anything is left).  It raises McgError only where the store cannot hold one stream's
+    reservation.  max_trunk_frames: the trunk call is split only above this many frames; max_decode_windows: windows per decoder call.
+    Driven from one thread.  Results: ``GazeStream.push``'s dicts, keyed by stream id; a closed stream gets an entry in the step that ends
+    it even when no frame was left."""
+
+    def __init__(self, engine_or_model, H, W, clip_len=7, stride=4, rows=None, scale_factor=None, person_threshold=0.5, max_decode_windows=None,
+                 max_trunk_frames=448):
+        e = engine_or_model
+        if not hasattr(e, 'decode') and hasattr(e, 'engine'):
+            e = e.engine()
+        self.e, self.H, self.W = e, H, W
+        self.T, self.s, self.thr = clip_len, stride, person_threshold
+        WindowPlanner(clip_len, stride)                     # rejects a bad (clip_len, stride) here, not at the first open()
+        if max_trunk_frames < 1 or (max_decode_windows is not None and max_decode_windows < 1):
+            raise L.McgError(f'GazeStreamPool: max_trunk_frames and max_decode_windows must be positive (got {max_trunk_frames}, {max_decode_windows})')
+        self.max_trunk, self.max_windows = int(max_trunk_frames), max_decode_windows
+        self.store = PyramidStore(e, 64 * (clip_len + stride) + self.max_trunk if rows is None else int(rows), H, W)
+        self.scale = None if scale_factor is None else torch.as_tensor(scale_factor, dtype=torch.float32, device=e.device).reshape(1, 1, 4)
+        self.streams = {}        # sid -> _PoolStream, in open order
+        self.next_sid = 0
+
+    def open(self):
+        sid = self.next_sid
+        self.next_sid += 1
+        self.streams[sid] = _PoolStream(self.T, self.s, self.thr)
+        return sid
+
+    def _stream(self, sid, what):
+        st = self.streams.get(sid)
+        if st is None:
+            raise L.McgError(f'GazeStreamPool.{what}: no open stream {sid!r}')
+        if st.closed:
+            raise L.McgError(f'GazeStreamPool.{what}: stream {sid!r} is closed')
+        return st
+
+    def push(self, sid, frames, img_hw=None):
+        """Queue frames [n,3,H,W] f32 (host or device, preprocessed like engine.forward's input) of stream sid; img_hw: [n,2] or None."""
+        st = self._stream(sid, 'push')
+        if frames.dim() != 4 or tuple(frames.shape[1:]) != (3, self.H, self.W):
+            raise L.McgError(f'GazeStreamPool.push: frames must be [n,3,{self.H},{self.W}] (got {tuple(frames.shape)})')
+        n = frames.shape[0]
+        if n:
+            st.queue.append((frames, None if img_hw is None else np.array(_host(img_hw), dtype=np.int32).reshape(n, 2)))
+            st.queued += n
+
+    def close(self, sid):
+        self._stream(sid, 'close').closed = True
+
+    def pending(self):
+        """Whether a step() has work left: queued frames, or a closed stream whose last windows have not run."""
+        return any(st.queued or st.closed for st in self.streams.values())
+
+    def _plan_step(self):
+        """-> {sid: frames of its queue that run now}.  Every admitted stream keeps clip_len + stride rows reserved (held + still free), so it
+        can always run up to its next window, whose decode releases rows again; rows beyond the reservations go to whoever asks first."""
+        R = self.T + self.s
+        spare = self.store.free_rows() - sum(max(0, R - len(st.row_of)) for st in self.streams.values() if st.admitted)
+        take = {}
+        for sid, st in self.streams.items():
+            if not st.queued:
+                continue
+            if not st.admitted:
+                if spare < R:
+                    continue
+                st.admitted, spare = True, spare - R
+            own = max(0, R - len(st.row_of))
+            m = min(st.queued, own + max(0, spare))
+            spare -= max(0, m - own)
+            if m:
+                take[sid] = m
+        if not take and not any(st.admitted for st in self.streams.values()) and any(st.queued for st in self.streams.values()):
+            raise L.McgError(f'GazeStreamPool: a store of {self.store.rows} rows cannot hold one stream (clip_len + stride = {R} live frames)')
+        return take
+
+    def _decode(self, items):
+        """items: [(stream, window)] -> one decoder call per longest-clip class and per max_decode_windows windows; merged per stream."""
+        classes = {}
+        for it in items:
+            classes.setdefault(bucket_key(self.H, self.W, it[1][1] - it[1][0], True), []).append(it)
+        for key in sorted(classes):
+            group = classes[key]
+            for i in range(0, len(group), self.max_windows or len(group)):
+                part = group[i:i + (self.max_windows or len(group))]
+                lengths = [w[1] - w[0] for _, w in part]
+                table = [st.row_of[f] for st, w in part for f in range(w[0], w[1])]
+                # windows of one length: the call a lone GazeStream makes; of different lengths: the ragged one
+                out = self.e.decode(self.store.levels, table, lengths[0] if len(set(lengths)) == 1 else lengths, img_hw=self.store.hw)
+                det, fused, others = (t.cpu().numpy() for t in clip_outputs(out, self.scale))
+                at = 0
+                for (st, w), T in zip(part, lengths):      # a stream's windows are in plan order within its class
+                    st.merger.add(w, det[at:at + T], fused[at:at + T], others[at:at + T])
+                    at += T
+
+    def step(self):
+        """Run what is queued -> {sid: dict(first, det, fused, others)} for every stream that had frames become final."""
+        take = self._plan_step()
+        # 1. one trunk call over every stream's frames, into whichever rows are free
+        parts, hws, rows = [], [], []
+        for sid, m in take.items():
+            st = self.streams[sid]
+            p, h = st.take(m)
+            r = self.store.alloc(m)
+            for k, row in enumerate(r):
+                st.row_of[st.planner.frames + k] = row
+            parts, hws, rows = parts + p, hws + h, rows + r
+        if rows:
+            x = [p.to(self.e.device, torch.float32) for p in parts]
+            x = x[0] if len(x) == 1 else torch.cat(x)
+            hw = None
+            if self.store.hw is not None or any(h is not None for h in hws):
+                hw = np.concatenate([np.array([[self.H, self.W]] * p.shape[0], dtype=np.int32) if h is None else h for p, h in zip(parts, hws)])
+            for i in range(0, len(rows), self.max_trunk):
+                self.store.write(x[i:i + self.max_trunk], rows[i:i + self.max_trunk], None if hw is None else hw[i:i + self.max_trunk])
+        # 2. one decoder call over every window that became certain
+        items, touched, ended = [], [], []
+        for sid, st in self.streams.items():
+            wins = st.planner.feed(take[sid]) if sid in take else []
+            if st.closed and not st.queued:
+                wins = wins + st.planner.finish()
+                ended.append(sid)
+            items += [(st, w) for w in wins]
+            if sid in take or st.planner.finished:
+                touched.append(sid)
+        if items:
+            self._decode(items)
+        # 3. + 4. per stream: hand out the frames that are final, give back the rows no later window reads
+        results = {}
+        for sid in touched:
+            st = self.streams[sid]
+            det, fused, others = st.merger.pop(st.planner.frames if st.planner.finished else st.planner.final_upto)
+            if det.shape[0] or st.planner.finished:
+                results[sid] = dict(first=st.emitted, det=det, fused=fused, others=others)
+            st.emitted += det.shape[0]
+            keep = st.planner.keep_from
+            self.store.free([st.row_of.pop(f) for f in range(st.released, keep)])
+            st.released = max(st.released, keep)
+        for sid in ended:
+            del self.streams[sid]
+        return results
