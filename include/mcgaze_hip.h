@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define MCG_ABI_VERSION 17
+#define MCG_ABI_VERSION 18
 
 enum { MCG_OK = 0, MCG_ERR_ARG = 1, MCG_ERR_HIP = 2, MCG_ERR_UNSUPPORTED = 3, MCG_ERR_WORKSPACE = 4 };
 /* MCG_F16X3: the parity-grade fast mode.  Activations, biases and every non-GEMM kernel are exactly those of MCG_F32 (4-byte
@@ -302,7 +302,7 @@ typedef struct {
 
 typedef struct mcg_engine mcg_engine;
 /* Threading and streams (what a host that drives the library from several threads may rely on)
- *   - The stand-alone operators (mcg_conv2d ... mcg_gaze_head, mcg_preprocess_frames) keep no state: any thread, any stream.
+ *   - The stand-alone operators (mcg_conv2d ... mcg_gaze_head, mcg_preprocess_frames, mcg_preprocess_head_crops) keep no state: any thread, any stream.
  *     mcg_last_error() is thread-local.
  *   - An ENGINE runs ONE forward at a time.  mcg_backbone_fpn_forward / mcg_clip_forward / mcg_bench_backbone_forward /
  *     mcg_engine_set_option / mcg_engine_profile_* take the engine's mutex for the duration of the ENQUEUE (they never wait for
@@ -454,6 +454,36 @@ typedef struct mcg_frame_desc {
 } mcg_frame_desc;
 int mcg_preprocess_frames(mcg_stream stream, const mcg_frame_desc* frames_dev, int num_frames, float* dst, int pad_h, int pad_w,
                           const float mean[3], const float stdinv[3], int to_rgb);
+/* ABI 18: head crops -- video frames and one head box per person per frame in, the model's `img` tensor and the decoder's per-frame tables
+ * out.  Replaces what the reference's demo does on the host for every (person, frame) before its Compose(cfg.data.test.pipeline[1:])
+ * (MCGaze_demo/demo.ipynb, cell 4): head_center = [int(y1 + y2) // 2, int(x1 + x2) // 2], l = int(max(y2 - y1, x2 - x1) * 0.8), the slice
+ * img[max(0, cy - l):min(cy + l, rows), max(0, cx - l):min(cx + l, cols)] -- then Resize(keep_ratio=True)'s size rule (transforms.py:216-242
+ * -> mmcv rescale_size: f = min(long / max(h, w), short / min(h, w)), int(side * f + 0.5)) and the `scale_factor` / `img_shape` metas
+ * (transforms.py:236-242).  Two launches: head_crop_plan_kernel (one thread per crop, double arithmetic, uncontracted) writes
+ * desc_out_dev, then the pixel kernel of mcg_preprocess_frames runs over it unchanged.  Crops may share an image: each frame is in device
+ * memory once however many heads it shows.
+ *   images_dev   DEVICE array of num_images (>= 1) frames: uint8, 3 interleaved channels, rows pitch bytes apart
+ *   boxes_dev    DEVICE f32 [n][4] x1 y1 x2 y2 in pixels of the crop's image (a detector's output as it is)
+ *   image_of_dev DEVICE int32 [n]: the image each crop is cut from
+ *   expand       the demo's 0.8 (finite);  scale_w, scale_h: Resize's img_scale
+ *   desc_out_dev DEVICE [n]: the window (crop_y, crop_x, crop_h, crop_w) and resized size (out_h, out_w) chosen per crop
+ *   img_hw_dev   DEVICE int32 [n][2] (out_h, out_w): what the forward and decoder entries take as img_hw
+ *   scale_factor_dev DEVICE f32 [n][4] (w, h, w, h) factors, (float)((double)new / (double)old): rescale=True divides the boxes by it
+ *   flags_dev    DEVICE int32 [n] or NULL.  0: the demo's window.  1: the demo's slice would be empty (a box of no extent, or one wholly
+ *                outside the frame) -- the window is ONE pixel, moved inside the frame.  2: a box that is not finite, an image_of outside
+ *                [0, num_images) or an image without pixels -- the crop reads pixel (0, 0) of image 0 as a 1 x 1 window.
+ *   dst          [n][3][pad_h][pad_w] f32; pad_h >= scale_h and pad_w >= scale_w (a non-square img_scale: both >= its long edge, keep_ratio
+ *                puts the long edge on the window's long side).  A resized side that would round to 0 is 1.
+ * Nothing is read outside an image for ANY box or index, and nothing is read on the host: no allocation, no host sync,
+ * graph-capturable; at most 65535 crops per call.  mean / stdinv / to_rgb as in mcg_preprocess_frames. */
+typedef struct mcg_image_desc {
+  const void* src;
+  int h, w, pitch;
+} mcg_image_desc;
+int mcg_preprocess_head_crops(mcg_stream s, const mcg_image_desc* images_dev, int num_images, const float* boxes_dev,
+                              const int32_t* image_of_dev, int n, double expand, int scale_w, int scale_h, mcg_frame_desc* desc_out_dev,
+                              int32_t* img_hw_dev, float* scale_factor_dev, int32_t* flags_dev, float* dst, int pad_h, int pad_w,
+                              const float mean[3], const float stdinv[3], int to_rgb);
 
 /* ---------------------------------------------------------------- measurement aids (bench.py)
  * While armed, every launch of the contraction kernel made by THIS engine is bracketed by a hipEvent pair on its launch stream.

@@ -360,13 +360,15 @@ def run_tracks(engine, tracks, max_len=100, batch_frames=448, scale_factor=None)
     as long as the person stays in view, cut every max_len + 1 frames -- where the demo runs one forward per chunk, the chunks of ALL
     tracks are batched here as clips of different lengths (engine.forward(x, [lengths])).
 
-    tracks: list of dict(id=..., frames=Tensor[L,3,H,W] f32 preprocessed head crops (normalised, padded to /32)[, img_hw=[L,2] int]), one per
-    (person, segment).  Chunks (plan_track_chunks) are visited in (track, chunk) order and batched per (H, W, longest-clip class) -- chunks
+    tracks: list of dict(id=..., frames=Tensor[L,3,H,W] f32 preprocessed head crops (normalised, padded to /32)[, img_hw=[L,2] int -- a host
+    array or a device tensor, sliced per chunk where it is][, scale_factor=[L,4] f32 per FRAME, host or device]), one per (person, segment).
+    Chunks (plan_track_chunks) are visited in (track, chunk) order and batched per (H, W, longest-clip class) -- chunks
     of at most 10 frames and longer ones in separate calls, so that short clips keep the fused attention block -- up to batch_frames
     frames per call (a single chunk may exceed it and then runs alone).  No overlap merge: the demo has none; a track's outputs are its
-    chunks' outputs concatenated.  scale_factor (4 floats) divides the boxes like rescale=True (the demo's setting).
+    chunks' outputs concatenated.  scale_factor divides the boxes like rescale=True (the demo's setting), on the device: the argument (4
+    floats) for every frame alike, a track's own table frame by frame (img_hw and scale_factor: all tracks or none).
     Returns one dict(id, det [L,3,5], fused [L,3], others [L,3,3]) per track, numpy f32 in merge_video's layout (det = box | score).
-    Head detection and cropping from full frames stay with the caller."""
+    Head detection stays with the caller; run_head_video cuts the crops from full frames and a detector's boxes."""
     dev = engine.device
     plans = [plan_track_chunks(int(t['frames'].shape[0]), max_len) for t in tracks]
     parts = [[None] * len(p) for p in plans]
@@ -379,11 +381,18 @@ def run_tracks(engine, tracks, max_len=100, batch_frames=448, scale_factor=None)
         spans = [plans[ti][ci] for ti, ci in items]
         Ts = [b - a for a, b in spans]
         x = torch.cat([tracks[ti]['frames'][a:b] for (ti, _), (a, b) in zip(items, spans)]).to(dev, torch.float32).contiguous()
+        first = tracks[items[0][0]]
         hw = None
-        if tracks[items[0][0]].get('img_hw') is not None:
+        if isinstance(first.get('img_hw'), torch.Tensor):
+            hw = torch.cat([tracks[ti]['img_hw'].reshape(-1, 2)[a:b] for (ti, _), (a, b) in zip(items, spans)])
+        elif first.get('img_hw') is not None:
             hw = np.concatenate([np.asarray(tracks[ti]['img_hw'], dtype=np.int32).reshape(-1, 2)[a:b] for (ti, _), (a, b) in zip(items, spans)])
         out = engine.forward(x, Ts, img_hw=hw)
-        scale = None if scale_factor is None else torch.as_tensor(scale_factor, dtype=torch.float32, device=out['boxes'].device)
+        bdev = out['boxes'].device
+        scale = None if scale_factor is None else torch.as_tensor(scale_factor, dtype=torch.float32, device=bdev)
+        if first.get('scale_factor') is not None:      # per frame: [n,1,4] against boxes [n,3,4]
+            scale = torch.cat([torch.as_tensor(tracks[ti]['scale_factor'], dtype=torch.float32).reshape(-1, 4)[a:b].to(bdev)
+                               for (ti, _), (a, b) in zip(items, spans)])[:, None, :]
         det, fused, others = (_host(t) for t in clip_outputs(out, scale))
         row = 0
         for (ti, ci), T in zip(items, Ts):
@@ -404,6 +413,122 @@ def run_tracks(engine, tracks, max_len=100, batch_frames=448, scale_factor=None)
     for t, p in zip(tracks, parts):
         cat = lambda k, shape: np.concatenate([c[k] for c in p]) if p else np.zeros(shape, np.float32)
         out.append(dict(id=t['id'], det=cat(0, (0, 3, 5)), fused=cat(1, (0, 3)), others=cat(2, (0, 3, 3))))
+    return out
+
+
+def read_head_labels(path, head_class=1):
+    """One label file of the demo's ``result/labels`` (the YOLO head detector's ``--save-txt`` output; MCGaze_demo/demo.ipynb, cell 1) ->
+    list of [x1, y1, x2, y2], one per line whose class is ``head_class``, in file order.  Lines are ``class x1 y1 x2 y2`` separated by
+    blanks; a field is an int where it reads as one and a float otherwise -- what the notebook's ``eval`` gives, without evaluating
+    anything.  Blank lines are skipped."""
+    def number(tok):
+        try:
+            return int(tok)
+        except ValueError:
+            return float(tok)
+
+    boxes = []
+    with open(path) as f:
+        for line in f:
+            tok = line.split()
+            if not tok:
+                continue
+            if len(tok) < 5:
+                raise ValueError(f'{path}: expected "class x1 y1 x2 y2", got {line.strip()!r}')
+            v = [number(t) for t in tok[:5]]
+            if v[0] == head_class:
+                boxes.append(v[1:5])
+    return boxes
+
+
+def segment_tracks(boxes_per_frame):
+    """Cell 1 of the demo (MCGaze_demo/demo.ipynb): boxes_per_frame[t] = the head boxes [x1, y1, x2, y2] of frame t, any order ->
+    list of dict(frame_id=[t, ...], boxes=[P][L][4]).  A new segment starts wherever the NUMBER of heads changes; inside a frame people
+    are ordered by x1 (a stable sort, like the notebook's), and person i of a segment is the i-th box of each of its frames -- the demo
+    has no other notion of identity.  Frames without a head belong to no segment and end the one before them (the notebook opens a
+    segment of zero people there, and fails on a video that starts with such a frame)."""
+    segments, cur, count = [], None, 0
+    for t, boxes in enumerate(boxes_per_frame):
+        boxes = sorted([list(b) for b in boxes], key=lambda b: b[0])
+        if len(boxes) != count:
+            cur = None
+            if boxes:
+                cur = dict(frame_id=[], boxes=[[] for _ in boxes])
+                segments.append(cur)
+            count = len(boxes)
+        if cur is not None:
+            cur['frame_id'].append(t)
+            for person, b in zip(cur['boxes'], boxes):
+                person.append(b)
+    return segments
+
+
+def head_arrows(head_boxes, gaze):
+    """Cell 5 of the demo: the arrow it draws per head, as end points.  head_boxes [L,4] x1 y1 x2 y2, gaze [L,>=2] (the fused gaze) ->
+    int64 [L,2,2]: (cx, cy) = (int(x1 + x2) // 2, int(y1 + y2) // 2) and (int(cx - l * g0), int(cy - l * g1)) with
+    l = int(max(y2 - y1, x2 - x1) * 1); the products are taken in double and int() truncates toward zero."""
+    b = np.asarray(head_boxes, dtype=np.float64).reshape(-1, 4)
+    g = np.asarray(gaze, dtype=np.float64).reshape(len(b), -1)
+    cx, cy = np.floor(np.trunc(b[:, 0] + b[:, 2]) / 2), np.floor(np.trunc(b[:, 1] + b[:, 3]) / 2)
+    l = np.trunc(np.maximum(b[:, 3] - b[:, 1], b[:, 2] - b[:, 0]) * 1)
+    tip = np.stack([np.trunc(cx - l * g[:, 0]), np.trunc(cy - l * g[:, 1])], axis=1)
+    return np.stack([np.stack([cx, cy], axis=1), tip], axis=1).astype(np.int64)
+
+
+def run_head_video(engine, pipeline, frames, boxes_per_frame, max_len=100, batch_frames=448, expand=0.8, rgb=False):
+    """Steps 3-4 of the demo from what its users hold -- the video's frames and one head box per person per frame -- to per-person gaze:
+    segment_tracks (cell 1), the head windows cut, resized and normalised on the device (pipeline.head_crops: cell 4's crop arithmetic and
+    ``cfg.data.test.pipeline[1:]``), run_tracks (cell 4's loop, batched), head_arrows (cell 5's end points).
+
+    frames: sequence of HxWx3 uint8 frames, numpy arrays (cv2's BGR; rgb=True: RGB) or tensors on the engine's device, indexed by frame
+    number; boxes_per_frame[t]: the head boxes of frame t.  pipeline: a DevicePipeline of the L2CS config's test pipeline.
+    The work goes in groups of about batch_frames crops -- whole chunks (plan_track_chunks), the people of a segment side by side, so that
+    a frame showing P heads is uploaded once per group and a long video never has all its crops resident: a chunk is one clip whichever
+    group it lands in, so the records do not depend on the grouping.  rescale=True as in the demo: every frame's boxes are divided by ITS
+    scale_factor, on the device; they are in pixels of the head window (``crop`` places it in the frame).
+    -> one dict per (segment, person), in that order: run_tracks' record (id = (segment, person), det, fused, others) plus frame_id [L],
+    head_box [L,4] f32 (as the device read it), crop [L,4] = y0, x0, h, w of the window, arrow int [L,2,2]."""
+    segments = segment_tracks(boxes_per_frame)
+    chunks = [(si, a, b, pi) for si, seg in enumerate(segments) for a, b in plan_track_chunks(len(seg['frame_id']), max_len)
+              for pi in range(len(seg['boxes']))]
+    pieces = {}                                        # (segment, person) -> list of (record, crop) in chunk order
+
+    def flush(group):
+        slot, images, boxes, image_of = {}, [], [], []
+        for si, a, b, pi in group:
+            for j in range(a, b):
+                t = segments[si]['frame_id'][j]
+                if t not in slot:
+                    slot[t] = len(images)
+                    images.append(frames[t])
+                image_of.append(slot[t])
+                boxes.append(segments[si]['boxes'][pi][j])
+        img, img_hw, scale, crop, _ = pipeline.head_crops(images, np.asarray(boxes, dtype=np.float32).reshape(-1, 4), np.asarray(image_of, dtype=np.int32),
+                                                          expand=expand, device=engine.device, rgb=rgb)
+        rows = np.concatenate([[0], np.cumsum([b - a for _, a, b, _ in group])])
+        tracks = [dict(id=k, frames=img[r0:r1], img_hw=img_hw[r0:r1], scale_factor=scale[r0:r1]) for k, (r0, r1) in enumerate(zip(rows[:-1], rows[1:]))]
+        records = run_tracks(engine, tracks, max_len=max_len, batch_frames=batch_frames)
+        crop = _host(crop)
+        for (si, a, b, pi), rec, r0, r1 in zip(group, records, rows[:-1], rows[1:]):
+            pieces.setdefault((si, pi), []).append((rec, crop[r0:r1]))
+
+    group, held = [], 0
+    for c in chunks:
+        if held and held + (c[2] - c[1]) > batch_frames:
+            flush(group)
+            group, held = [], 0
+        group.append(c)
+        held += c[2] - c[1]
+    if group:
+        flush(group)
+    out = []
+    for si, seg in enumerate(segments):
+        for pi, person in enumerate(seg['boxes']):
+            got = pieces[(si, pi)]
+            rec = {k: np.concatenate([r[k] for r, _ in got]) for k in ('det', 'fused', 'others')}
+            head_box = np.asarray(person, dtype=np.float32).reshape(-1, 4)
+            out.append(dict(id=(si, pi), **rec, frame_id=list(seg['frame_id']), head_box=head_box, crop=np.concatenate([c for _, c in got]),
+                            arrow=head_arrows(person, rec['fused'])))
     return out
 
 

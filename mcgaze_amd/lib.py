@@ -11,7 +11,7 @@ LIB_PATH = os.environ.get('MCGAZE_LIB') or os.path.join(_HERE, 'libmcgaze_hip.so
 
 MCG_OK = 0
 MCG_F32, MCG_BF16, MCG_F16X3, MCG_F16 = 0, 1, 2, 3
-ABI_VERSION = 17
+ABI_VERSION = 18
 RES_NONE, RES_ADD, RES_UPSAMPLE_ADD = 0, 1, 2
 FLAG_STAGED_GEMM, FLAG_NO_SPECIALISED, FLAG_NO_ATTN_BLOCK = 1, 2, 4
 
@@ -34,7 +34,7 @@ EXPORTS = ['mcg_abi_version', 'mcg_build_id', 'mcg_last_error', 'mcg_device_info
            'mcg_conv3x3_wino_x3_weight_bytes', 'mcg_engine_range_audit', 'mcg_roi_align_indexed', 'mcg_decoder_forward_indexed',
            'mcg_deferred_pyramid_bytes', 'mcg_deferred_pyramid_levels', 'mcg_backbone_fpn_forward_deferred', 'mcg_decoder_forward_deferred',
            'mcg_stage_forward_ragged', 'mcg_decoder_forward_ragged', 'mcg_decoder_forward_deferred_ragged', 'mcg_clip_forward_ragged',
-           'mcg_pyramid_scatter_rows']
+           'mcg_pyramid_scatter_rows', 'mcg_preprocess_head_crops']
 
 
 class ConvDesc(C.Structure):
@@ -65,6 +65,10 @@ class ModelWeights(C.Structure):
 class FrameDesc(C.Structure):
     _fields_ = [('src', C.c_void_p), ('src_h', C.c_int), ('src_w', C.c_int), ('src_pitch', C.c_int), ('crop_y', C.c_int),
                 ('crop_x', C.c_int), ('crop_h', C.c_int), ('crop_w', C.c_int), ('out_h', C.c_int), ('out_w', C.c_int)]
+
+
+class ImageDesc(C.Structure):
+    _fields_ = [('src', C.c_void_p), ('h', C.c_int), ('w', C.c_int), ('pitch', C.c_int)]
 
 
 class McgError(RuntimeError):
@@ -127,6 +131,7 @@ def load():
     lib.mcg_clip_forward_ragged.argtypes = [vp, vp, vp, i, vp, i, i, i, i, vp, i, vp, vp, vp, vp, sz]
     lib.mcg_pyramid_scatter_rows.argtypes = [vp, i, C.POINTER(vp), C.POINTER(vp), i, i, i, i, vp]
     lib.mcg_preprocess_frames.argtypes =[vp, vp, i, vp, i, i, C.POINTER(C.c_float), C.POINTER(C.c_float), i]
+    lib.mcg_preprocess_head_crops.argtypes = [vp, vp, i, vp, vp, i, C.c_double, i, i, vp, vp, vp, vp, vp, i, i, C.POINTER(C.c_float), C.POINTER(C.c_float), i]
     lib.mcg_engine_set_option.argtypes = [vp, C.c_char_p, i]
     lib.mcg_engine_profile_start.argtypes = [vp, i]
     lib.mcg_engine_profile_stop.argtypes = [vp, C.POINTER(i), C.POINTER(C.c_float), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(i), C.POINTER(i), i]

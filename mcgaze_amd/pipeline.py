@@ -13,6 +13,10 @@ device as they are, and the kernel writes the model's ``img`` tensor.  There is 
     img, img_metas = pipe(frames, device='cuda:0')            # frames: list of HxWx3 uint8 BGR arrays or file names
     model(img=[img], img_metas=[img_metas], return_loss=False, rescale=True, clip_length=7)
 
+Head crops (``DevicePipeline.head_crops``): the demo of the reference (MCGaze_demo/demo.ipynb, cell 4) cuts one window per person out of
+every video frame before this chain; there the WINDOW is chosen on the device as well (``mcg_preprocess_head_crops``), from frames and head
+boxes that may both live in device memory already.  ``head_crop_window`` is the same arithmetic on the host, for checks and for drawing.
+
 Randomness: the reference's ``CenterCrop(crop_type='relative_range')`` draws the crop size from the global numpy RNG at TEST
 time too (transforms.py:1126-1130), and ``RandomFlip(flip_ratio=0.0)`` consumes one more uniform
 (np.random.choice, transforms.py:463-497).  ``rng`` (default: the global ``np.random``) is drawn from in that order per frame,
@@ -518,6 +522,59 @@ _DESC = np.dtype([('src', np.uint64)] + [(f, np.int32) for f in ('src_h', 'src_w
 assert _DESC.itemsize == C.sizeof(L.FrameDesc) and all(_DESC.fields[n][1] == getattr(L.FrameDesc, n).offset for n in _DESC.names)
 
 
+_IMAGE = np.dtype([('src', np.uint64), ('h', np.int32), ('w', np.int32), ('pitch', np.int32)], align=True)   # lib.ImageDesc / mcg_image_desc
+assert _IMAGE.itemsize == C.sizeof(L.ImageDesc) and all(_IMAGE.fields[n][1] == getattr(L.ImageDesc, n).offset for n in _IMAGE.names)
+_DESC_WORDS = _DESC.itemsize // 4
+_CROP_WORD = _DESC.fields['crop_y'][1] // 4         # crop_y, crop_x, crop_h, crop_w are consecutive int32 words of a descriptor
+
+
+class _NoDraw:
+    """The generator behind head_crop_geometry's planning pass: RandomFlip(0.0)'s uniform decides nothing and is not drawn from the caller's."""
+
+    @staticmethod
+    def random_sample():
+        return 0.0
+
+
+_NO_DRAW = _NoDraw()
+
+
+def head_crop_windows(boxes, h, w, expand=0.8):
+    """The demo's head windows (MCGaze_demo/demo.ipynb, cell 4) for n boxes at once, in the doubles python computes them in:
+
+        head_center = [int(y1 + y2) // 2, int(x1 + x2) // 2];   l = int(max(y2 - y1, x2 - x1) * 0.8)
+        head_crop = img[max(0, cy - l):min(cy + l, rows), max(0, cx - l):min(cx + l, cols)]
+
+    boxes [n,4] x1 y1 x2 y2 (finite), h / w: frame size per box (scalars or [n]).  -> (windows int64 [n,4] = y0, x0, h, w; empty bool [n]):
+    a window the slice would leave empty (a box of no extent, or wholly outside the frame) is reported as ONE pixel moved inside the frame
+    and marked in ``empty`` -- what head_crop_plan_kernel (csrc/preprocess.hip) writes with flag 1; this is that kernel, line for line."""
+    b = np.asarray(boxes, dtype=np.float64).reshape(-1, 4)
+    if not np.isfinite(b).all():
+        raise ValueError('head boxes must be finite')
+    l = np.trunc(np.maximum(b[:, 3] - b[:, 1], b[:, 2] - b[:, 0]) * float(expand))
+
+    def span(a, c, size):
+        size = np.broadcast_to(np.asarray(size, dtype=np.float64), a.shape)
+        ctr = np.floor(np.trunc(a + c) / 2.0)        # int(a + c) // 2: truncate, then floor-divide (they differ below zero)
+        lo, hi = np.maximum(0.0, ctr - l), np.minimum(ctr + l, size)
+        return np.minimum(lo, size - 1), hi, ~(hi > lo)
+
+    y0, y1, ey = span(b[:, 1], b[:, 3], h)
+    x0, x1, ex = span(b[:, 0], b[:, 2], w)
+    empty = ey | ex
+    win = np.stack([y0, x0, np.where(empty, 1.0, y1 - y0), np.where(empty, 1.0, x1 - x0)], axis=1).astype(np.int64)
+    return win, empty
+
+
+def head_crop_window(box, h, w, expand=0.8):
+    """(y0, x0, crop_h, crop_w) of ONE head box [x1, y1, x2, y2] in an h x w frame: the window ``DevicePipeline.head_crops`` cuts (and
+    returns as ``crop``).  ValueError where the demo's slice is empty -- its cv2.resize would raise there."""
+    win, empty = head_crop_windows([box], h, w, expand)
+    if empty[0]:
+        raise ValueError(f'head box {[float(v) for v in box]} leaves an empty window in a {h} x {w} frame')
+    return tuple(int(v) for v in win[0])
+
+
 class DevicePipeline:
     """``Compose(cfg.data.test.pipeline)`` (mmdet/datasets/pipelines/compose.py:11-51) whose pixel work is one HIP launch."""
 
@@ -534,6 +591,7 @@ class DevicePipeline:
         # event of the pixel kernels that read the device twin (on the caller's stream)
         self._stages = [dict(pin=None, dev=None, copied=None, read=None) for _ in range(self.STAGES)]
         self._stage_i, self._copy_stream = 0, {}
+        self._image_tables = collections.OrderedDict()            # head_crops: (device, frame table bytes) -> that table on the device
 
     def plan(self, shape, rng=np.random, filename=None, ori_filename=None):
         p = FramePlan(shape, filename, ori_filename)
@@ -696,6 +754,153 @@ class DevicePipeline:
         st['read'] = torch.cuda.Event()
         st['read'].record(main)
         return out
+
+    IMAGE_TABLES = 16                                             # device-resident frame tables kept by head_crops (a decoder's buffer ring recurs)
+
+    def head_crop_geometry(self):
+        """-> (scale_w, scale_h, pad_h, pad_w, img_norm_cfg) of the chain a head crop goes through, which must be the demo's
+        ``cfg.data.test.pipeline[1:]``: Resize(keep_ratio=True), no flip, Normalize, Pad -- NotImplementedError for anything else."""
+        kinds = [type(t).__name__ for t in self.transforms]
+        if 'CenterCrop' in kinds:
+            raise NotImplementedError('head_crops: the window comes from the head box; a pipeline with a CenterCrop is not the demo\'s chain')
+        resize = next((t for t in self.transforms if isinstance(t, Resize)), None)
+        if resize is None or not resize.keep_ratio or resize.img_scale[0] != resize.img_scale[1]:
+            raise NotImplementedError('head_crops needs Resize(img_scale=(s, s), keep_ratio=True): a window clipped by the frame border may be '
+                                      'upright or lying, and keep_ratio puts the long edge of img_scale on its long side')
+        scale_w, scale_h = resize.img_scale
+        p = self.plan((scale_h, scale_w, 3), _NO_DRAW)            # the LARGEST resized crop through the planners: its pad_shape holds every crop
+        return int(scale_w), int(scale_h), int(p.pad_shape[0]), int(p.pad_shape[1]), p.img_norm_cfg
+
+    def head_crops(self, images, boxes, image_of, expand=0.8, device='cuda:0', stream=None, rgb=False):
+        """Video frames and head boxes -> the model's input, one head crop per box (MCGaze_demo/demo.ipynb, cell 4, then this chain): ONE
+        plan launch chooses every window on the device, the pixel kernel reads it (mcg_preprocess_head_crops).
+
+        images: list of HxWx3 uint8 frames in cv2's BGR order (rgb=True: RGB, the kernel swaps either way).  A numpy array is staged and
+        uploaded ONCE however many heads it shows; a CUDA uint8 tensor is read where it is (rows stride(0) bytes apart, pixels packed).
+        boxes [n,4] f32 x1 y1 x2 y2 in pixels of their frame; image_of [n] int: the frame of each box -- numpy arrays or device tensors.
+        Host tables are checked here (ValueError for an image_of out of range, a non-finite box or a window the demo's
+        slice leaves empty); device tables are not read back -- such rows come back flagged instead (1: empty window, cut as one pixel
+        inside the frame; 2: unusable box / index, pixel (0, 0) of frame 0), and a call on device frames and tables touches the host
+        nowhere: it can be captured in a graph once a first call has uploaded the frame table (kept per distinct set of frames).
+
+        -> (img [n,3,Hp,Wp] f32, img_hw [n,2] int32, scale_factor [n,4] f32, crop [n,4] int32 = y0, x0, h, w, flags [n] int32), all on
+        the device.  (Hp, Wp) is img_scale rounded up by Pad -- for every call, where mmcv's collate pads a chunk to ITS largest crop (the
+        same unless the frame border clips every crop of the chunk on one axis); img_hw is each crop's true resized size, the reference's
+        img_shape, and the decoder clips by it."""
+        lib = L.load()
+        dev = torch.device(device)
+        if dev.type != 'cuda':
+            raise L.McgError('DevicePipeline runs its pixel work on the GPU (mcg_preprocess_head_crops); there is no CPU path')
+        if dev.index is None:
+            dev = torch.device('cuda', torch.cuda.current_device())
+        scale_w, scale_h, pad_h, pad_w, norm = self.head_crop_geometry()
+        if not len(images):
+            raise ValueError('head_crops: no frames')
+        # frame table: host frames get their address once they are staged
+        table = np.zeros(len(images), dtype=_IMAGE)
+        host_at = {}                                              # index -> array to stage
+        for k, im in enumerate(images):
+            if isinstance(im, torch.Tensor):
+                if not (im.is_cuda and im.device == dev and im.dtype == torch.uint8 and im.ndim == 3 and im.shape[2] == 3 and im.numel() > 0
+                        and im.stride(2) == 1 and im.stride(1) == 3 and (im.shape[0] == 1 or im.stride(0) >= 3 * im.shape[1])):
+                    raise TypeError(f'frame {k}: device frames must be HxWx3 uint8 tensors on {dev} with packed pixels (stride (pitch, 3, 1)), '
+                                    f'got {im.dtype} {tuple(im.shape)} strides {tuple(im.stride())} on {im.device}')
+                table[k] = (im.data_ptr(), im.shape[0], im.shape[1], im.stride(0) if im.shape[0] > 1 else 3 * im.shape[1])
+            else:
+                a = np.ascontiguousarray(im)
+                if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3 or a.size == 0:
+                    raise TypeError(f'frame {k}: frames must be HxWx3 uint8 arrays, got {a.dtype} {a.shape}')
+                host_at[k] = a
+                table[k] = (0, a.shape[0], a.shape[1], 3 * a.shape[1])
+        on_device = [isinstance(t, torch.Tensor) and t.is_cuda for t in (boxes, image_of)]
+        if not on_device[0]:
+            boxes = np.ascontiguousarray(_host_array(boxes), dtype=np.float32).reshape(-1, 4)     # f32 is what the device reads: the checks see the same boxes
+        if not on_device[1]:
+            image_of = np.ascontiguousarray(_host_array(image_of)).reshape(-1)
+            if image_of.dtype.kind not in 'iu':
+                raise TypeError(f'image_of must hold integers, got {image_of.dtype}')
+            if len(image_of) and (image_of.min() < 0 or image_of.max() >= len(images)):
+                raise ValueError(f'image_of must lie in [0, {len(images)}), got [{image_of.min()}, {image_of.max()}]')
+            image_of = image_of.astype(np.int32)
+        n = int(boxes.shape[0])
+        if tuple(boxes.shape) != (n, 4) or tuple(image_of.shape) != (n,):
+            raise ValueError(f'head_crops: boxes {tuple(boxes.shape)} and image_of {tuple(image_of.shape)} must be [n,4] and [n]')
+        if n > 65535:
+            raise ValueError(f'head_crops: at most 65535 crops per call (got {n})')
+        if not any(on_device) and n:
+            _, empty = head_crop_windows(boxes, table['h'][image_of], table['w'][image_of], expand)
+            if empty.any():
+                k = int(np.flatnonzero(empty)[0])
+                raise ValueError(f'head box {k} {boxes[k].tolist()} leaves an empty window in frame {int(image_of[k])} '
+                                 f'({int(table["h"][image_of[k]])} x {int(table["w"][image_of[k]])})')
+        with torch.cuda.device(dev):
+            main = torch.cuda.current_stream(dev) if stream is None else torch.cuda.ExternalStream(stream, device=dev)
+            with torch.cuda.stream(main):
+                if on_device[0]:
+                    boxes = boxes.to(dev, torch.float32).contiguous()
+                if on_device[1]:
+                    image_of = image_of.to(dev, torch.int32).contiguous()
+                if n == 0:
+                    z = lambda *shape, dtype=torch.int32: torch.zeros(*shape, dtype=dtype, device=dev)
+                    return z(0, 3, pad_h, pad_w, dtype=torch.float32), z(0, 2), z(0, 4, dtype=torch.float32), z(0, 4), z(0)
+                # everything that comes from the host travels in ONE pinned staging buffer and one copy: pixels, frame table, host tables
+                parts = [(k, a.reshape(-1)) for k, a in host_at.items()]
+                tables = [t.view(np.uint8).reshape(-1) for t, d in zip((boxes, image_of), on_device) if not d]
+                if parts or tables:
+                    sizes = [(a.size + 255) // 256 * 256 for _, a in parts] + [(table.nbytes + 255) // 256 * 256] + [(t.size + 255) // 256 * 256 for t in tables]
+                    offs = np.cumsum([0] + sizes)
+                    total = int(offs[-1])
+                    st, cs = self._staging(total, dev, main)
+                    host, raw = st['pin'], st['dev']
+                    host_np = host.numpy()
+                    for (k, a), o in zip(parts, offs):
+                        host_np[int(o):int(o) + a.size] = a
+                        table['src'][k] = raw.data_ptr() + int(o)
+                    at = [raw.data_ptr() + int(o) for o in offs[len(parts):-1]]                  # frame table, then the host tables
+                    for t, o in zip([table.view(np.uint8).reshape(-1)] + tables, offs[len(parts):-1]):
+                        host_np[int(o):int(o) + t.size] = t
+                    if st['read'] is not None:
+                        cs.wait_event(st['read'])
+                    with torch.cuda.stream(cs):
+                        raw[:total].copy_(host[:total], non_blocking=True)
+                    st['copied'] = torch.cuda.Event()
+                    st['copied'].record(cs)
+                    main.wait_event(st['copied'])
+                    images_ptr, at = at[0], at[1:]
+                    boxes_ptr = boxes.data_ptr() if on_device[0] else at.pop(0)
+                    image_of_ptr = image_of.data_ptr() if on_device[1] else at.pop(0)
+                else:
+                    # nothing comes from the host but the frame table, and that only the first time these frames are seen
+                    st = None
+                    key = (dev.index, table.tobytes())
+                    tdev = self._image_tables.get(key)
+                    if tdev is None:
+                        tdev = self._image_tables[key] = torch.from_numpy(table.view(np.uint8).reshape(-1).copy()).to(dev)
+                        while len(self._image_tables) > self.IMAGE_TABLES:
+                            self._image_tables.popitem(last=False)
+                    else:
+                        self._image_tables.move_to_end(key)
+                    images_ptr, boxes_ptr, image_of_ptr = tdev.data_ptr(), boxes.data_ptr(), image_of.data_ptr()
+                img = torch.empty(n, 3, pad_h, pad_w, dtype=torch.float32, device=dev)
+                desc = torch.empty(n, _DESC_WORDS, dtype=torch.int32, device=dev)
+                img_hw = torch.empty(n, 2, dtype=torch.int32, device=dev)
+                scale_factor = torch.empty(n, 4, dtype=torch.float32, device=dev)
+                flags = torch.empty(n, dtype=torch.int32, device=dev)
+                mean = (C.c_float * 3)(*[float(v) for v in norm['mean']])
+                stdinv = (C.c_float * 3)(*[float(np.float32(1.0 / np.float64(v))) for v in norm['std']])
+                swap = int(bool(norm['to_rgb']) != bool(rgb))
+                vp = C.c_void_p
+                L.check(lib.mcg_preprocess_head_crops(vp(main.cuda_stream), vp(images_ptr), len(images), vp(boxes_ptr), vp(image_of_ptr), n, float(expand),
+                                                      scale_w, scale_h, vp(desc.data_ptr()), vp(img_hw.data_ptr()), vp(scale_factor.data_ptr()),
+                                                      vp(flags.data_ptr()), vp(img.data_ptr()), pad_h, pad_w, mean, stdinv, swap), 'mcg_preprocess_head_crops')
+                if st is not None:
+                    st['read'] = torch.cuda.Event()
+                    st['read'].record(main)
+        return img, img_hw, scale_factor, desc[:, _CROP_WORD:_CROP_WORD + 4], flags
+
+
+def _host_array(t):
+    return t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)
 
 
 def build_pipeline(transforms):

@@ -1,0 +1,69 @@
+#!/usr/bin/env python3
+"""Steps 3 - 4 of the reference's demo (MCGaze_demo/README.md; demo.ipynb, cells 1 - 5) without the drawing: a directory of video frames
+and the head detector's label files in, per-person per-frame gaze out.
+
+usage: demo_video.py FRAMES_DIR LABELS_DIR CONFIG CHECKPOINT --out gaze.json [--precision f16x3] [--device cuda:0] [--max-len 100]
+                     [--batch-frames 448] [--head-class 1] [--ext jpg]
+
+FRAMES_DIR holds 0.<ext>, 1.<ext>, ... (the demo's `frames/`), LABELS_DIR holds 0.txt, 1.txt, ... with lines `class x1 y1 x2 y2` in pixels
+(the demo's `result/labels/`); a frame without a label file shows no head.  CONFIG is the L2CS config, whose test pipeline the demo runs
+on every head crop.  The result file holds one entry per (segment, person) in the notebook's order -- a segment is a run of frames with
+the same number of heads, people are numbered left to right: `frame_id`, `head_box`, `crop` (y0, x0, h, w of the window cut from the
+frame), `gaze` (the fused gaze the notebook draws), `arrow` ((cx, cy) and the tip of the arrow of cell 5), and the per-clue boxes (in
+pixels of the head window, rescale=True), scores and gazes of harness.run_tracks (`det`, `others`)."""
+import argparse
+import json
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from mcgaze_amd import harness, init_detector  # noqa: E402
+from mcgaze_amd.pipeline import DevicePipeline, LoadImageFromFile  # noqa: E402
+
+
+class Frames:
+    """The demo's frames/ directory, decoded when a group of crops asks for them (RGB, as the decoder delivers them)."""
+
+    def __init__(self, root, n, ext):
+        self.root, self.n, self.ext = root, n, ext
+
+    def __len__(self):
+        return self.n
+
+    def __getitem__(self, t):
+        return LoadImageFromFile.load(os.path.join(self.root, f'{t}.{self.ext}'), rgb=True)
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
+    ap.add_argument('frames_dir')
+    ap.add_argument('labels_dir')
+    ap.add_argument('config')
+    ap.add_argument('checkpoint')
+    ap.add_argument('--out', required=True)
+    ap.add_argument('--precision', default='f16x3', choices=['f16x3', 'fp32', 'f16', 'bf16'])
+    ap.add_argument('--device', default='cuda:0')
+    ap.add_argument('--max-len', type=int, default=100)
+    ap.add_argument('--batch-frames', type=int, default=448)
+    ap.add_argument('--head-class', type=int, default=1)
+    ap.add_argument('--ext', default='jpg')
+    a = ap.parse_args(argv)
+    n = len([f for f in os.listdir(a.frames_dir) if f.endswith('.' + a.ext)])      # the notebook: vid_len = len(os.listdir(frames))
+    missing = [t for t in range(n) if not os.path.exists(os.path.join(a.frames_dir, f'{t}.{a.ext}'))]
+    if missing:
+        raise SystemExit(f'{a.frames_dir}: {n} .{a.ext} files but no {missing[0]}.{a.ext} -- frames are numbered from 0 without gaps')
+    labels = [os.path.join(a.labels_dir, f'{t}.txt') for t in range(n)]
+    per_frame = [harness.read_head_labels(p, a.head_class) if os.path.exists(p) else [] for p in labels]
+    model = init_detector(a.config, a.checkpoint, device=a.device, precision=a.precision)
+    pipe = DevicePipeline(model.cfg.data.test.pipeline)
+    res = harness.run_head_video(model.engine(), pipe, Frames(a.frames_dir, n, a.ext), per_frame, max_len=a.max_len, batch_frames=a.batch_frames, rgb=True)
+    out = [dict(segment=r['id'][0], person=r['id'][1], frame_id=r['frame_id'], head_box=r['head_box'].tolist(), crop=r['crop'].tolist(),
+                gaze=r['fused'].tolist(), arrow=r['arrow'].tolist(), det=r['det'].tolist(), others=r['others'].tolist()) for r in res]
+    with open(a.out, 'w') as f:
+        json.dump(dict(frames=n, tracks=out), f)
+    print(f'{n} frames, {len(out)} (segment, person) tracks, {sum(len(r["frame_id"]) for r in out)} head crops -> {a.out}')
+
+
+if __name__ == '__main__':
+    main()
