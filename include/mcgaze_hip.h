@@ -435,6 +435,25 @@ int mcg_clip_forward_ragged(mcg_engine* e, mcg_stream s, const float* img, int n
  * No allocation, no host sync, graph-capturable. */
 int mcg_pyramid_scatter_rows(mcg_stream s, mcg_dtype dt, const void* const src[4], void* const dst[4],
                              int num_frames, int store_rows, int H, int W, const int32_t* row_of);
+/* The overlap merge on the device (an addition to ABI 18: nothing that existed changes).  The reference's harness averages the frames two
+ * sliding windows share on the host, window after window (tools/test_gaze360_gaze.py:129-206), after rescale=True has divided every box by
+ * its frame's scale_factor (multiclue_gaze_roi_head.py:360-363).  Here the outputs of ONE decoder call -- any number of windows of any
+ * number of streams -- are folded into a store of per-frame result rows that stays in device memory.  The merge is sequential per frame
+ * and not associative (three windows on one frame give ((a + b) / 2 + c) / 2), so the table is per DESTINATION frame: the decoder-output
+ * frames that land on it, in plan order (mcgaze_amd/harness.py::merge_plan).
+ *   gaze [4][n][3], boxes [n][3][4], scores [n][3]   DEVICE f32: the decoder's outputs over n = num_frames frames
+ *   scale            NULL, DEVICE f32 [4] (scale_per_frame = 0) or [n][4] (scale_per_frame = 1): every box is divided by it, IEEE f32
+ *   plan             DEVICE int32 [num_dst][2 + max_src]: dst_row, cont, src[max_src] (-1 = none).  cont = 1: an earlier call wrote
+ *                    row dst_row and the fold starts from it; cont = 0: the first source starts it
+ *   store            DEVICE f32 [store_rows][27]: det[3][5] (x1 y1 x2 y2 score) | fused[3] | others[3][3], clues in the order face, eyes, head
+ * Per (destination frame, clue), for its sources in order: the box of a source whose score is < person_threshold is zeroed; the first
+ * state is the source itself; afterwards box = (old score < threshold or new score < threshold) ? 0 : (old + new) / 2 and score, fused
+ * and per-clue gaze = (old + new) / 2 -- f32, uncontracted: the bits of the host merge.  A dst_row outside [0, store_rows) skips that
+ * row and a source outside [0, n) skips that source: defined, never a stray access (the Python side rejects such a table first); two
+ * rows naming one dst_row is the caller's error.  num_dst and max_src are host integers; no allocation, no host sync, graph-capturable. */
+int mcg_merge_windows(mcg_stream s, const float* gaze, const float* boxes, const float* scores, int num_frames, const float* scale,
+                      int scale_per_frame, const int32_t* plan, int num_dst, int max_src, float* store, int store_rows,
+                      float person_threshold);
 
 /* ---------------------------------------------------------------- test-time preprocessing
  * One launch replaces the per-frame CPU transforms the reference's test pipeline applies between image decode and the model

@@ -84,6 +84,55 @@ def merge_video(windows, clip_outputs, person_threshold=0.5):
     return det, fused, others
 
 
+def merge_plan(windows, row_of, written, num_frames=None, store_rows=None):
+    """The table mcg_merge_windows takes for ONE decoder call: merge_window turned inside out.  merge_window applies windows one after the
+    other and its result is not associative (at clip_len 7, stride 4, L = 12 frames 5 and 6 become ((a + b) / 2 + c) / 2), so windows
+    cannot run in parallel -- but frames can: every destination frame gets the decoder-output frames that land on it, in plan order.
+
+    windows: [(stream key, (start, stop, overlap), first output row)] in call order -- frame start + t of the stream is row first + t of the
+    call's outputs; per stream the windows are in plan order.  row_of(key, frame) -> the store row of that frame.  written: the frames
+    that hold state from an EARLIER call, anything that answers ``(key, frame) in written``.
+    -> (int32 [num_dst, 2 + max_src]: dst_row, cont, src[max_src] padded with -1; max_src).  cont = 1 exactly when an earlier call wrote
+    that frame: the fold starts from the stored row.  max_src: the longest source list of the call (at least 1).
+    ValueError: windows of one stream out of plan order (starts and stops must rise, and the frames of a window that already hold state
+    must be its first ``overlap`` ones -- what merge_window averages), an output row outside [0, num_frames), a store row outside
+    [0, store_rows) or named by two frames (the last three only when the bound is given)."""
+    order, sources, last = [], {}, {}
+    for key, (start, stop, overlap), first in windows:
+        start, stop, first = int(start), int(stop), int(first)
+        if stop <= start:
+            raise ValueError(f'merge_plan: empty window ({start}, {stop}) of stream {key!r}')
+        if first < 0 or (num_frames is not None and first + stop - start > num_frames):
+            raise ValueError(f'merge_plan: window ({start}, {stop}) of stream {key!r} reads output rows {first}..{first + stop - start - 1}, '
+                             f'outside the call\'s {num_frames} frames')
+        prev = last.get(key)
+        if prev is not None and not (start > prev[0] and stop > prev[1]):
+            raise ValueError(f'merge_plan: window ({start}, {stop}) of stream {key!r} follows {prev}: windows must come in plan order')
+        held = [((key, f) in sources) or ((key, f) in written) for f in range(start, stop)]
+        k = sum(held)
+        if any(held[k:]) or (k != overlap and (k or prev is not None)):
+            raise ValueError(f'merge_plan: window ({start}, {stop}, {overlap}) of stream {key!r} is out of plan order: {k} of its frames hold '
+                             'state, and they must be its first `overlap` ones')
+        last[key] = (start, stop)
+        for t in range(stop - start):
+            kf = (key, start + t)
+            if kf not in sources:
+                sources[kf] = []
+                order.append(kf)
+            sources[kf].append(first + t)
+    max_src = max([len(s) for s in sources.values()] + [1])
+    table = np.full((len(order), 2 + max_src), -1, dtype=np.int32)
+    for i, kf in enumerate(order):
+        r = int(row_of(*kf))
+        if r < 0 or (store_rows is not None and r >= store_rows):
+            raise ValueError(f'merge_plan: frame {kf[1]} of stream {kf[0]!r} has store row {r}, outside the store of {store_rows} rows')
+        table[i, 0], table[i, 1] = r, int(kf in written)
+        table[i, 2:2 + len(sources[kf])] = sources[kf]
+    if len(set(table[:, 0].tolist())) != len(order):
+        raise ValueError('merge_plan: two frames share a store row')
+    return table, max_src
+
+
 def video_record(video_id, det, fused, others):
     """Result record of one video (tools/test_gaze360_gaze.py:210-260): python floats of the f32 values; a box is [x, y, w, h] with
     the differences taken in double (the reference subtracts python floats), or None where the four coordinates sum to zero."""
@@ -122,7 +171,7 @@ def clip_outputs(out, scale=None):
     return torch.cat([boxes, out['scores'][..., None]], dim=-1), out['gaze'][0], out['gaze'][1:].permute(1, 0, 2)
 
 
-def _run_windows(engine, ids, plans, get_window, batch_clips, person_threshold, reuse_frames=False, mixed_lengths=False):
+def _run_windows(engine, ids, plans, get_window, batch_clips, person_threshold, reuse_frames=False, mixed_lengths=False, merge='host'):
     """Core of run_videos / run_annotation, STREAMING: windows are visited in (video, window) order -- the reference's order, so the
     crop RNG draws inside ``get_window`` fall where upstream's do -- and dropped into per-(T, H, W) buckets; a bucket runs through
     the engine (batched semantics: N = B*T frames, clip_length = T) as soon as it holds ``batch_clips`` clips and its inputs are
@@ -135,8 +184,17 @@ def _run_windows(engine, ids, plans, get_window, batch_clips, person_threshold, 
     mixed_lengths: windows of DIFFERENT lengths share a bucket -- keyed (H, W, longest-clip class) with the classes T <= 10 and T > 10, so
     that one long clip does not push a bucket of short windows off the fused attention block -- and a flush is one ragged forward / decode
     (clip_length = the list of the windows' lengths): a video shorter than clip_len no longer runs alone.  A window's results do not
-    depend on its batch, so the records are those of the default bucketing."""
+    depend on its batch, so the records are those of the default bucketing.
+    merge='device': every flush is folded into a stream.DeviceMerger (one mcg_merge_windows launch per engine call; a video's windows share
+    one bucket, so they arrive in plan order) and a video's merged frames come to the host in ONE copy once its last window has run."""
+    if merge not in ('host', 'device'):
+        raise ValueError(f"merge is 'host' or 'device' (got {merge!r})")
     dev = engine.device
+    merger = None
+    if merge == 'device':
+        from .stream import DeviceMerger               # McgError on an engine without a HIP device: no CPU fallback
+        merger = DeviceMerger(dev, person_threshold, rows=2 * batch_clips * max([p[0][1] - p[0][0] for p in plans if p] + [1]))
+    merged = []                                        # merge='device': (vi, pinned [L, 27], event) of the videos on their way to the host
     trunk = [0]
     buckets = {}                                       # (T, H, W) -> list of (vi, wi, frames, hw, scale)
     outputs = [[None] * len(p) for p in plans]
@@ -213,6 +271,21 @@ def _run_windows(engine, ids, plans, get_window, batch_clips, person_threshold, 
         if items[0][4] is not None:
             scale = upload(torch.cat([torch.as_tensor(it[4], dtype=torch.float32) for it in items]))[:, None, :]
         n = sum(Ts)
+        if merger is not None:
+            rows = np.concatenate([[0], np.cumsum(Ts)]).tolist()
+            merger.add_call([(it[0], plans[it[0]][it[1]], r) for it, r in zip(items, rows)], out, scale)
+            for it in items:
+                vi = it[0]
+                pending[vi] -= 1
+                if pending[vi] == 0:                   # the video's last window is queued: its frames leave the store in one copy
+                    packed, _ = merger.pop_rows([(vi, plans[vi][-1][1])])
+                    merger.forget(vi)
+                    buf = torch.empty(packed.shape[0], 27, dtype=torch.float32).pin_memory()
+                    buf.copy_(packed, non_blocking=True)
+                    ev = torch.cuda.Event()
+                    ev.record(torch.cuda.current_stream(dev))
+                    merged.append((vi, buf, ev))
+            return
         det, fused, others = clip_outputs(out, scale)
         packed = torch.cat([det.reshape(n, 15), fused.reshape(n, 3), others.reshape(n, 9)], dim=1).to(torch.float32)   # ONE copy to the host
         who = [(it[0], it[1], T) for it, T in zip(items, Ts)]
@@ -240,12 +313,16 @@ def _run_windows(engine, ids, plans, get_window, batch_clips, person_threshold, 
     for key in sorted(buckets):
         flush(key)
     collect(0)
+    for vi, buf, ev in merged:
+        ev.synchronize()
+        r = buf.numpy()
+        records[vi] = video_record(ids[vi], r[:, :15].reshape(-1, 3, 5), r[:, 15:18], r[:, 18:].reshape(-1, 3, 3))
     last_run_stats['trunk_frames'] = trunk[0]
     return records
 
 
 def run_videos(engine, videos, clip_len=7, stride=4, batch_clips=64, scale_factor=None, person_threshold=0.5, reuse_frames=False,
-               mixed_lengths=False):
+               mixed_lengths=False, merge='host'):
     """Push whole videos through the HIP engine.
 
     videos: list of dict(id=…, frames=Tensor[L,3,H,W] f32 already preprocessed (normalised, padded to /32)[, img_hw=[L,2] int: the
@@ -257,7 +334,9 @@ def run_videos(engine, videos, clip_len=7, stride=4, batch_clips=64, scale_facto
     Frames shared by windows that land in different batches are computed in each: at most clip_len - stride per video per batch
     boundary.  last_run_stats['trunk_frames'] holds the frames the trunk ran on, for both settings.
     mixed_lengths: windows of different lengths (videos shorter than clip_len) share batches -- one ragged engine call per flush
-    (_run_windows); the records are those of the default."""
+    (_run_windows); the records are those of the default.
+    merge='device': the overlap merge runs on the device (mcg_merge_windows, one launch per engine call) and every video comes to the
+    host in one copy -- the same records; McgError on an engine without a HIP device."""
     plans = [plan_windows(v['frames'].shape[0], clip_len, stride) for v in videos]
 
     def get_window(vi, wi):
@@ -267,7 +346,7 @@ def run_videos(engine, videos, clip_len=7, stride=4, batch_clips=64, scale_facto
         return videos[vi]['frames'][a:b], (None if hw is None else hw[a:b]), sc
 
     return _run_windows(engine, [v['id'] for v in videos], plans, get_window, batch_clips, person_threshold, reuse_frames=reuse_frames,
-                        mixed_lengths=mixed_lengths)
+                        mixed_lengths=mixed_lengths, merge=merge)
 
 
 def run_annotation(engine, anno, root, pipeline, clip_len=7, stride=4, batch_clips=64, person_threshold=0.5, rng=None, workers=0, lookahead=None,
@@ -466,7 +545,17 @@ def segment_tracks(boxes_per_frame):
 def head_arrows(head_boxes, gaze):
     """Cell 5 of the demo: the arrow it draws per head, as end points.  head_boxes [L,4] x1 y1 x2 y2, gaze [L,>=2] (the fused gaze) ->
     int64 [L,2,2]: (cx, cy) = (int(x1 + x2) // 2, int(y1 + y2) // 2) and (int(cx - l * g0), int(cy - l * g1)) with
-    l = int(max(y2 - y1, x2 - x1) * 1); the products are taken in double and int() truncates toward zero."""
+    l = int(max(y2 - y1, x2 - x1) * 1); the products are taken in double and int() truncates toward zero.
+    gaze as a torch tensor (the ``fused`` of a results='device' stream): the same steps in torch, in double, on gaze's device -> an
+    int64 tensor there, nothing is copied to the host."""
+    if isinstance(gaze, torch.Tensor):
+        b = torch.as_tensor(np.asarray(head_boxes, dtype=np.float64) if not isinstance(head_boxes, torch.Tensor) else head_boxes)
+        b = b.to(gaze.device, torch.float64).reshape(-1, 4)
+        g = gaze.to(torch.float64).reshape(b.shape[0], -1)
+        cx, cy = torch.floor(torch.trunc(b[:, 0] + b[:, 2]) / 2), torch.floor(torch.trunc(b[:, 1] + b[:, 3]) / 2)
+        l = torch.trunc(torch.maximum(b[:, 3] - b[:, 1], b[:, 2] - b[:, 0]) * 1)
+        tip = torch.stack([torch.trunc(cx - l * g[:, 0]), torch.trunc(cy - l * g[:, 1])], dim=1)
+        return torch.stack([torch.stack([cx, cy], dim=1), tip], dim=1).to(torch.int64)
     b = np.asarray(head_boxes, dtype=np.float64).reshape(-1, 4)
     g = np.asarray(gaze, dtype=np.float64).reshape(len(b), -1)
     cx, cy = np.floor(np.trunc(b[:, 0] + b[:, 2]) / 2), np.floor(np.trunc(b[:, 1] + b[:, 3]) / 2)

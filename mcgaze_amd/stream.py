@@ -10,6 +10,8 @@ mcg_decoder_forward_indexed, the gather happens inside the RoIAlign read).
   * ``WindowPlanner``: pure host bookkeeping.  Fed a growing frame count, it says which windows of the FINAL ``plan_windows(L)`` are
     already certain and below which frame no later window can reach.
   * ``StreamMerger``: the overlap merge of ``harness.merge_video`` applied window by window, handing out frames once they are final.
+  * ``DeviceMerger``: the same merge on the device, for any number of streams -- one store of result rows in device memory, one plan
+    upload and one mcg_merge_windows launch per decoder call (``merge='device'`` of GazeStream / GazeStreamPool).
   * ``GazeStream``: push frames as they arrive, get back the per-frame results that became final; ``finish()`` returns the rest.
   * ``PyramidStore`` / ``GazeStreamPool``: MANY streams at once (S cameras, or the reference demo's one clip per tracked person,
     MCGaze_demo/demo.ipynb cell 4, each the sliding-window loop of tools/test_gaze360_gaze.py:72-111): one store shared by all streams,
@@ -21,7 +23,7 @@ import numpy as np
 import torch
 
 from . import lib as L
-from .harness import _host, bucket_key, clip_outputs, merge_window, plan_windows
+from .harness import _host, bucket_key, clip_outputs, merge_plan, merge_window, plan_windows
 
 
 class WindowPlanner:
@@ -119,6 +121,145 @@ class StreamMerger:
         return out
 
 
+class _Written:
+    """The frames of DeviceMerger's streams that held state before the current call: per stream the range [base, end)."""
+
+    def __init__(self, spans):
+        self.spans = spans
+
+    def __contains__(self, key_frame):
+        a, b = self.spans.get(key_frame[0], (0, 0))
+        return a <= key_frame[1] < b
+
+
+class DeviceMerger:
+    """The device counterpart of StreamMerger, for any number of streams: the merged frames live in ONE store tensor [rows, 27] on the
+    engine's device (a row = det 3x5 | fused 3 | others 3x3) and never visit the host.
+
+    ``add_call(windows, out, scale)`` folds the outputs of one decoder call -- however many windows of however many streams -- into the
+    store: one plan table (harness.merge_plan, uploaded pinned and non-blocking) and one mcg_merge_windows launch on the current stream.
+    ``pop([(key, upto)])`` hands out, per stream, the frames [handed out so far, upto) -- which no later window may touch -- with one
+    index_select over all of them, and gives their rows back for reuse.  Nothing here waits for the device unless ``host=True`` asks for
+    the popped frames as numpy arrays (one copy for all streams).  Per stream the windows must come in plan order; the concatenated
+    output of a stream equals harness.merge_video over its plan bit for bit (tests/test_gpu_device_merge.py).
+    Rows come from a free list; a store that runs out of rows is replaced by one twice as large (a device copy, no sync)."""
+
+    ROW = 27
+
+    class _Stream:
+        def __init__(self):
+            self.base, self.end, self.rows = 0, 0, {}      # frames handed out / written so far; frame -> store row of the live frames
+
+    def __init__(self, device, person_threshold=0.5, rows=256):
+        self.device = torch.device(device)
+        if self.device.type != 'cuda':
+            raise L.McgError(f'DeviceMerger: merging on the device needs a HIP device (got {self.device}); there is no CPU fallback path')
+        from .engine import _ptr, _stream, _upload_table
+        self._ptr, self._cur, self._upload = _ptr, _stream, _upload_table
+        self.lib = L.load()
+        self.thr = float(np.float32(person_threshold))
+        self.store = torch.empty(max(int(rows), 1), self.ROW, dtype=torch.float32, device=self.device)
+        self._free = list(range(self.store.shape[0] - 1, -1, -1))
+        self.streams = {}
+
+    def _alloc(self):
+        if not self._free:
+            old = self.store
+            self.store = torch.empty(2 * old.shape[0], self.ROW, dtype=torch.float32, device=self.device)
+            self.store[:old.shape[0]].copy_(old)
+            self._free = list(range(self.store.shape[0] - 1, old.shape[0] - 1, -1))
+        return self._free.pop()
+
+    def add_call(self, windows, out, scale=None):
+        """windows: [(key, (start, stop, overlap), first output row)] of ONE decoder call whose outputs are ``out`` (the engine's dict:
+        gaze [4,n,3], boxes [n,3,4], scores [n,3], f32 on the device); scale: None, 4 values for every frame alike, or [n,4] / [n,1,4] per
+        frame (a device tensor): rescale=True's division, done in the kernel."""
+        if not windows:
+            return
+        n = out['scores'].shape[0]
+        spans = {}
+        for key, (start, stop, _), _ in windows:
+            st = self.streams.setdefault(key, self._Stream())
+            if key not in spans:
+                spans[key] = (st.base, st.end)
+            if start < st.base:
+                raise L.McgError(f'DeviceMerger: window ({start}, {stop}) reaches below frame {st.base}, which was already handed out')
+        taken = []
+        try:
+            for key, (start, stop, _), _ in windows:
+                st = self.streams[key]
+                for f in range(start, stop):
+                    if f not in st.rows:
+                        st.rows[f] = self._alloc()
+                        taken.append((st, f))
+            table, max_src = merge_plan(windows, lambda key, f: self.streams[key].rows[f], _Written(spans), n, self.store.shape[0])
+        except ValueError:
+            for st, f in taken:                             # a rejected call leaves the merger as it was
+                self._free.append(st.rows.pop(f))
+            raise
+        per_frame = 0
+        if scale is not None:
+            scale = scale.to(self.device, torch.float32).contiguous()
+            if scale.numel() not in (4, 4 * n):
+                raise ValueError(f'DeviceMerger: scale must hold 4 or {n} x 4 values (got {tuple(scale.shape)})')
+            per_frame = int(scale.numel() != 4)
+        g, b, s = (out[k].to(torch.float32).contiguous() for k in ('gaze', 'boxes', 'scores'))
+        plan = self._upload(table, self.device)
+        L.check(self.lib.mcg_merge_windows(self._cur(self.device), self._ptr(g), self._ptr(b), self._ptr(s), n, self._ptr(scale), per_frame,
+                                           self._ptr(plan), table.shape[0], max_src, self._ptr(self.store), self.store.shape[0], self.thr),
+                'mcg_merge_windows')
+        for key, (_, stop, _), _ in windows:
+            st = self.streams[key]
+            st.end = max(st.end, stop)
+
+    def pop_rows(self, items):
+        """items: [(key, upto)] -> (rows [K,27], [k per item]): the frames [handed out, min(upto, written)) of every item's stream, item after
+        item, gathered into ONE fresh device tensor by one index_select; their store rows are free for reuse."""
+        rows, counts = [], []
+        for key, upto in items:
+            st = self.streams.get(key)
+            k = 0 if st is None else max(0, min(int(upto), st.end) - st.base)
+            if k:
+                rows += [st.rows.pop(f) for f in range(st.base, st.base + k)]
+                st.base += k
+            counts.append(k)
+        if not rows:
+            return torch.empty(0, self.ROW, dtype=torch.float32, device=self.device), counts
+        packed = self.store.index_select(0, self._upload(np.asarray(rows, dtype=np.int64), self.device))
+        self._free.extend(reversed(rows))                  # later launches on this stream run after the gather
+        return packed, counts
+
+    def pop(self, items, host=False):
+        """pop_rows as one (det [k,3,5], fused [k,3], others [k,3,3]) per item: views of the gathered tensor on the device, or (host=True)
+        numpy arrays after ONE copy to the host for all items together."""
+        packed, counts = self.pop_rows(items)
+        if host:
+            packed = packed.cpu().numpy()
+        res, at = [], 0
+        for k in counts:
+            r = packed[at:at + k]
+            res.append((r[:, :15].reshape(k, 3, 5), r[:, 15:18], r[:, 18:].reshape(k, 3, 3)))
+            at += k
+        if host:
+            res = [tuple(np.ascontiguousarray(x) for x in r) for r in res]
+        return res
+
+    def forget(self, key):
+        """The stream ended: its remaining rows (none after a pop up to its end) go back to the free list."""
+        st = self.streams.pop(key, None)
+        if st is not None:
+            self._free.extend(st.rows.values())
+
+
+def _check_switches(who, e, merge, results):
+    if merge not in ('host', 'device') or results not in ('host', 'device'):
+        raise ValueError(f"{who}: merge and results are 'host' or 'device' (got merge={merge!r}, results={results!r})")
+    if results == 'device' and merge != 'device':
+        raise ValueError(f"{who}: results='device' needs merge='device' (the host merge has its results on the host)")
+    if merge == 'device' and torch.device(e.device).type != 'cuda':
+        raise L.McgError(f"{who}: merge='device' needs an engine on a HIP device (got {e.device}); there is no CPU fallback path")
+
+
 class PyramidRing:
     """The per-level pyramid store of a stream, used as a ring of ``capacity`` rows: frame i lives in row i % capacity.
 
@@ -188,17 +329,24 @@ class GazeStream:
     (default clip_len + 64); a push larger than the free rows is run in steps.  scale_factor: 4 floats the boxes are divided by
     (rescale=True, multiclue_gaze_roi_head.py:360-363).
     Results: dicts of numpy arrays det [k,3,5] (boxes xyxy + score), fused [k,3], others [k,3,3] -- merge_video's layout -- plus
-    ``first``: the index of the first frame in the dict."""
+    ``first``: the index of the first frame in the dict.
+    merge='device': the windows are merged on the device (``DeviceMerger``: one mcg_merge_windows launch per decoder call) instead of on
+    the host after a blocking copy per decoder call -- the same bits.  results='host' then makes ONE copy to the host per push;
+    results='device' (needs merge='device') returns the same dicts with f32 tensors on the engine's device: their values are valid on
+    the engine's current stream, and push / finish never wait for the device."""
 
     def __init__(self, engine_or_model, H, W, clip_len=7, stride=4, capacity=None, scale_factor=None, person_threshold=0.5,
-                 max_decode_windows=None):
+                 max_decode_windows=None, merge='host', results='host'):
         e = engine_or_model
         if not hasattr(e, 'decode') and hasattr(e, 'engine'):
             e = e.engine()
         self.e = e
+        _check_switches('GazeStream', e, merge, results)
+        self.results = results
         self.T, self.s = clip_len, stride
         self.planner = WindowPlanner(clip_len, stride)
         self.merger = StreamMerger(person_threshold)
+        self.dmerger = DeviceMerger(e.device, person_threshold, rows=4 * clip_len) if merge == 'device' else None
         capacity = clip_len + 64 if capacity is None else int(capacity)
         if capacity <= clip_len:
             raise L.McgError(f'GazeStream: capacity must exceed clip_len ({capacity} <= {clip_len})')
@@ -213,12 +361,18 @@ class GazeStream:
             T = part[0][1] - part[0][0]
             table = [self.ring.row(f) for a, b, _ in part for f in range(a, b)]
             out = self.e.decode(self.ring.levels, table, T, img_hw=self.ring.hw)
+            if self.dmerger is not None:
+                self.dmerger.add_call([(0, w, k * T) for k, w in enumerate(part)], out, self.scale)
+                continue
             det, fused, others = (t.cpu().numpy() for t in clip_outputs(out, self.scale))
             for k, w in enumerate(part):
                 self.merger.add(w, det[k * T:(k + 1) * T], fused[k * T:(k + 1) * T], others[k * T:(k + 1) * T])
 
     def _emit(self, upto):
-        det, fused, others = self.merger.pop(upto)
+        if self.dmerger is not None:
+            det, fused, others = self.dmerger.pop([(0, upto)], host=self.results == 'host')[0]
+        else:
+            det, fused, others = self.merger.pop(upto)
         res = dict(first=self.emitted, det=det, fused=fused, others=others)
         self.emitted += det.shape[0]
         return res
@@ -355,13 +509,20 @@ class GazeStreamPool:
     next ``step`` (``pending()`` says whether anything is left).  It raises McgError only where the store cannot hold one stream's
     reservation.  max_trunk_frames: the trunk call is split only above this many frames; max_decode_windows: windows per decoder call.
     Driven from one thread.  Results: ``GazeStream.push``'s dicts, keyed by stream id; a closed stream gets an entry in the step that ends
-    it even when no frame was left."""
+    it even when no frame was left.
+    merge / results: as for ``GazeStream`` -- merge='device' folds every decoder call into ONE ``DeviceMerger`` shared by all streams (one
+    plan upload and one mcg_merge_windows launch per decoder call, where the host merge makes a blocking copy per call and one numpy
+    merge per window); results='host' then costs one copy per ``step`` for all streams together, results='device' none: ``step``
+    returns device tensors that are valid on the engine's current stream and never waits for the device."""
 
     def __init__(self, engine_or_model, H, W, clip_len=7, stride=4, rows=None, scale_factor=None, person_threshold=0.5, max_decode_windows=None,
-                 max_trunk_frames=448):
+                 max_trunk_frames=448, merge='host', results='host'):
         e = engine_or_model
         if not hasattr(e, 'decode') and hasattr(e, 'engine'):
             e = e.engine()
+        _check_switches('GazeStreamPool', e, merge, results)
+        self.results = results
+        self.dmerger = DeviceMerger(e.device, person_threshold, rows=16 * (clip_len + stride)) if merge == 'device' else None
         self.e, self.H, self.W = e, H, W
         self.T, self.s, self.thr = clip_len, stride, person_threshold
         WindowPlanner(clip_len, stride)                     # rejects a bad (clip_len, stride) here, not at the first open()
@@ -439,6 +600,10 @@ class GazeStreamPool:
                 table = [st.row_of[f] for st, w in part for f in range(w[0], w[1])]
                 # windows of one length: the call a lone GazeStream makes; of different lengths: the ragged one
                 out = self.e.decode(self.store.levels, table, lengths[0] if len(set(lengths)) == 1 else lengths, img_hw=self.store.hw)
+                if self.dmerger is not None:
+                    starts = np.concatenate([[0], np.cumsum(lengths)]).tolist()
+                    self.dmerger.add_call([(st, w, at) for (st, w), at in zip(part, starts)], out, self.scale)
+                    continue
                 det, fused, others = (t.cpu().numpy() for t in clip_outputs(out, self.scale))
                 at = 0
                 for (st, w), T in zip(part, lengths):      # a stream's windows are in plan order within its class
@@ -479,9 +644,12 @@ class GazeStreamPool:
             self._decode(items)
         # 3. + 4. per stream: hand out the frames that are final, give back the rows no later window reads
         results = {}
-        for sid in touched:
+        if self.dmerger is not None:                       # one gather (and, results='host', one copy) for all streams together
+            popped = self.dmerger.pop([(self.streams[sid], self.streams[sid].planner.frames if self.streams[sid].planner.finished
+                                        else self.streams[sid].planner.final_upto) for sid in touched], host=self.results == 'host')
+        for i, sid in enumerate(touched):
             st = self.streams[sid]
-            det, fused, others = st.merger.pop(st.planner.frames if st.planner.finished else st.planner.final_upto)
+            det, fused, others = popped[i] if self.dmerger is not None else st.merger.pop(st.planner.frames if st.planner.finished else st.planner.final_upto)
             if det.shape[0] or st.planner.finished:
                 results[sid] = dict(first=st.emitted, det=det, fused=fused, others=others)
             st.emitted += det.shape[0]
@@ -489,5 +657,7 @@ class GazeStreamPool:
             self.store.free([st.row_of.pop(f) for f in range(st.released, keep)])
             st.released = max(st.released, keep)
         for sid in ended:
+            if self.dmerger is not None:
+                self.dmerger.forget(self.streams[sid])
             del self.streams[sid]
         return results
