@@ -133,11 +133,70 @@ def merge_plan(windows, row_of, written, num_frames=None, store_rows=None):
     return table, max_src
 
 
-def video_record(video_id, det, fused, others):
+def check_smooth(who, smooth):
+    """The ``smooth=`` option: None, or smooth_filter's alpha as a number in (0, 1] -> None or the float."""
+    if smooth is None:
+        return None
+    if isinstance(smooth, bool) or not isinstance(smooth, (int, float, np.integer, np.floating)) or not 0 < float(smooth) <= 1:
+        raise ValueError(f'{who}: smooth is None or the filter\'s alpha, a number in (0, 1] (got {smooth!r})')
+    return float(smooth)
+
+
+def smooth_host(g, alpha, lead=False, trail=False):
+    """The temporal filter of tools/calculate_mae_gaze360.py:16-29 (smooth_filter) on the host, in the arithmetic mcg_smooth_gaze has
+    (include/mcgaze_hip.h states it): g [m, ..., 3] f32, consecutive frames of one stream -> the smoothed frames, same trailing shape.
+    lead / trail: g[0] / g[-1] is there only as a neighbour (the frame handed out before, the frame not handed out yet) and gets no output
+    row; without them g[0] is the stream's first frame and g[-1] its last.  A one-frame stream comes back as it is, not normalised.
+    Everything is f32 numpy, which contracts nothing; each of the norm's two fma is taken in float64 and rounded once."""
+    g = np.asarray(g, dtype=np.float32)
+    m, lo = g.shape[0], int(bool(lead))
+    hi = m - int(bool(trail))
+    if hi <= lo:
+        return g[:0].copy()
+    if m == 1:
+        return g.copy()
+    a, b = np.float32(alpha), np.float32(1.0 - float(alpha))
+    x, at = g[lo:hi], np.arange(lo, hi)
+    p, q = g[np.maximum(at - 1, 0)], g[np.minimum(at + 1, m - 1)]
+    shape = (-1,) + (1,) * (g.ndim - 1)
+    has_p, has_q = (at > 0).reshape(shape), (at < m - 1).reshape(shape)
+    with np.errstate(all='ignore'):
+        o = a * x
+        o = np.where(has_p & has_q, o + (b * (p + q)) / np.float32(2), o + b * np.where(has_p, p, q))
+        d = o.astype(np.float64)
+        n = (d[..., 1] * d[..., 1] + (o[..., 0] * o[..., 0]).astype(np.float64)).astype(np.float32)
+        n = np.sqrt((d[..., 2] * d[..., 2] + n.astype(np.float64)).astype(np.float32))
+        return o / n[..., None]
+
+
+def smooth_plan(frames, row_of, first=0, last=None, store_rows=None):
+    """The table mcg_smooth_gaze takes for the frames of ONE stream that are about to be handed out: int32 [k, 3] = (row of the frame
+    before, row of the frame, row of the frame after), in the order of ``frames``.  row_of(frame) -> its store row.  -1 stands for the
+    previous row of frame ``first`` (the stream's first frame) and for the next row of frame ``last`` (its last one, known only once the
+    stream has ended: None before).  ValueError: a row that is negative or (store_rows given) at or past store_rows."""
+    frames = [int(f) for f in frames]
+    table = np.full((len(frames), 3), -1, dtype=np.int32)
+    for i, f in enumerate(frames):
+        for j, g in enumerate((f - 1, f, f + 1)):
+            if (j == 0 and f == first) or (j == 2 and last is not None and f == last):
+                continue
+            r = int(row_of(g))
+            if r < 0 or (store_rows is not None and r >= store_rows):
+                raise ValueError(f'smooth_plan: frame {g} has store row {r}, outside the store of {store_rows} rows')
+            table[i, j] = r
+    return table
+
+
+def video_record(video_id, det, fused, others, smoothed=None):
     """Result record of one video (tools/test_gaze360_gaze.py:210-260): python floats of the f32 values; a box is [x, y, w, h] with
-    the differences taken in double (the reference subtracts python floats), or None where the four coordinates sum to zero."""
+    the differences taken in double (the reference subtracts python floats), or None where the four coordinates sum to zero.
+    smoothed = (fused [L,3], others [L,3,3]) after the temporal filter adds ``fusion_gazes_smooth`` and ``<clue>_gazes_smooth``."""
     det, fused, others = _host(det), _host(fused), _host(others)
     rec = dict(video_id=video_id, category_id=1, fusion_gazes=fused.tolist())
+    if smoothed is not None:
+        rec['fusion_gazes_smooth'] = _host(smoothed[0]).tolist()
+        for ci, c in enumerate(CLUES):
+            rec[f'{c}_gazes_smooth'] = _host(smoothed[1])[:, ci].tolist()
     m = det[..., :4].astype(np.float64)
     empty = (((m[..., 0] + m[..., 1]) + m[..., 2]) + m[..., 3] == 0).tolist()
     xywh = np.stack([m[..., 0], m[..., 1], m[..., 2] - m[..., 0], m[..., 3] - m[..., 1]], axis=-1).tolist()
@@ -171,7 +230,8 @@ def clip_outputs(out, scale=None):
     return torch.cat([boxes, out['scores'][..., None]], dim=-1), out['gaze'][0], out['gaze'][1:].permute(1, 0, 2)
 
 
-def _run_windows(engine, ids, plans, get_window, batch_clips, person_threshold, reuse_frames=False, mixed_lengths=False, merge='host'):
+def _run_windows(engine, ids, plans, get_window, batch_clips, person_threshold, reuse_frames=False, mixed_lengths=False, merge='host',
+                 smooth=None):
     """Core of run_videos / run_annotation, STREAMING: windows are visited in (video, window) order -- the reference's order, so the
     crop RNG draws inside ``get_window`` fall where upstream's do -- and dropped into per-(T, H, W) buckets; a bucket runs through
     the engine (batched semantics: N = B*T frames, clip_length = T) as soon as it holds ``batch_clips`` clips and its inputs are
@@ -186,14 +246,17 @@ def _run_windows(engine, ids, plans, get_window, batch_clips, person_threshold, 
     (clip_length = the list of the windows' lengths): a video shorter than clip_len no longer runs alone.  A window's results do not
     depend on its batch, so the records are those of the default bucketing.
     merge='device': every flush is folded into a stream.DeviceMerger (one mcg_merge_windows launch per engine call; a video's windows share
-    one bucket, so they arrive in plan order) and a video's merged frames come to the host in ONE copy once its last window has run."""
+    one bucket, so they arrive in plan order) and a video's merged frames come to the host in ONE copy once its last window has run.
+    smooth: None, or the alpha of the temporal filter (smooth_host; merge='device': mcg_smooth_gaze, one launch per video, its rows go
+    to the host in the same copy) -- every record then also holds the smoothed gazes (video_record)."""
     if merge not in ('host', 'device'):
         raise ValueError(f"merge is 'host' or 'device' (got {merge!r})")
+    smooth = check_smooth('run_videos', smooth)
     dev = engine.device
     merger = None
     if merge == 'device':
         from .stream import DeviceMerger               # McgError on an engine without a HIP device: no CPU fallback
-        merger = DeviceMerger(dev, person_threshold, rows=2 * batch_clips * max([p[0][1] - p[0][0] for p in plans if p] + [1]))
+        merger = DeviceMerger(dev, person_threshold, rows=2 * batch_clips * max([p[0][1] - p[0][0] for p in plans if p] + [1]), smooth=smooth)
     merged = []                                        # merge='device': (vi, pinned [L, 27], event) of the videos on their way to the host
     trunk = [0]
     buckets = {}                                       # (T, H, W) -> list of (vi, wi, frames, hw, scale)
@@ -224,7 +287,8 @@ def _run_windows(engine, ids, plans, get_window, batch_clips, person_threshold, 
                 outputs[vi][wi] = (r[:, :15].reshape(T, 3, 5), r[:, 15:18], r[:, 18:].reshape(T, 3, 3))
                 pending[vi] -= 1
                 if pending[vi] == 0:                   # all windows of the video are back: merge, record, release
-                    records[vi] = video_record(ids[vi], *merge_video(plans[vi], outputs[vi], person_threshold))
+                    whole = merge_video(plans[vi], outputs[vi], person_threshold)
+                    records[vi] = video_record(ids[vi], *whole, None if smooth is None else (smooth_host(whole[1], smooth), smooth_host(whole[2], smooth)))
                     outputs[vi] = None
 
     def length_of(it):
@@ -278,9 +342,13 @@ def _run_windows(engine, ids, plans, get_window, batch_clips, person_threshold, 
                 vi = it[0]
                 pending[vi] -= 1
                 if pending[vi] == 0:                   # the video's last window is queued: its frames leave the store in one copy
-                    packed, _ = merger.pop_rows([(vi, plans[vi][-1][1])])
+                    if smooth is None:
+                        packed, _ = merger.pop_rows([(vi, plans[vi][-1][1])])
+                    else:                              # the whole video at once: no frame waits for its successor
+                        packed, smoothed, _ = merger.pop_smooth_rows([(vi, plans[vi][-1][1])], ended=(vi,))
+                        packed = torch.cat([packed, smoothed], dim=1)
                     merger.forget(vi)
-                    buf = torch.empty(packed.shape[0], 27, dtype=torch.float32).pin_memory()
+                    buf = torch.empty(packed.shape[0], packed.shape[1], dtype=torch.float32).pin_memory()
                     buf.copy_(packed, non_blocking=True)
                     ev = torch.cuda.Event()
                     ev.record(torch.cuda.current_stream(dev))
@@ -316,13 +384,14 @@ def _run_windows(engine, ids, plans, get_window, batch_clips, person_threshold, 
     for vi, buf, ev in merged:
         ev.synchronize()
         r = buf.numpy()
-        records[vi] = video_record(ids[vi], r[:, :15].reshape(-1, 3, 5), r[:, 15:18], r[:, 18:].reshape(-1, 3, 3))
+        records[vi] = video_record(ids[vi], r[:, :15].reshape(-1, 3, 5), r[:, 15:18], r[:, 18:27].reshape(-1, 3, 3),
+                                   None if smooth is None else (r[:, 27:30], r[:, 30:39].reshape(-1, 3, 3)))
     last_run_stats['trunk_frames'] = trunk[0]
     return records
 
 
 def run_videos(engine, videos, clip_len=7, stride=4, batch_clips=64, scale_factor=None, person_threshold=0.5, reuse_frames=False,
-               mixed_lengths=False, merge='host'):
+               mixed_lengths=False, merge='host', smooth=None):
     """Push whole videos through the HIP engine.
 
     videos: list of dict(id=…, frames=Tensor[L,3,H,W] f32 already preprocessed (normalised, padded to /32)[, img_hw=[L,2] int: the
@@ -336,7 +405,10 @@ def run_videos(engine, videos, clip_len=7, stride=4, batch_clips=64, scale_facto
     mixed_lengths: windows of different lengths (videos shorter than clip_len) share batches -- one ragged engine call per flush
     (_run_windows); the records are those of the default.
     merge='device': the overlap merge runs on the device (mcg_merge_windows, one launch per engine call) and every video comes to the
-    host in one copy -- the same records; McgError on an engine without a HIP device."""
+    host in one copy -- the same records; McgError on an engine without a HIP device.
+    smooth: None, or the alpha in (0, 1] of the temporal filter the reference's metric runs over every video before the angular error
+    (tools/calculate_mae_gaze360.py:16-29, alpha 0.6 there): every record gains ``fusion_gazes_smooth`` and ``<clue>_gazes_smooth``, the
+    filtered gazes (mcg_smooth_gaze's arithmetic; on the device with merge='device'); everything else in it is unchanged."""
     plans = [plan_windows(v['frames'].shape[0], clip_len, stride) for v in videos]
 
     def get_window(vi, wi):
@@ -346,7 +418,7 @@ def run_videos(engine, videos, clip_len=7, stride=4, batch_clips=64, scale_facto
         return videos[vi]['frames'][a:b], (None if hw is None else hw[a:b]), sc
 
     return _run_windows(engine, [v['id'] for v in videos], plans, get_window, batch_clips, person_threshold, reuse_frames=reuse_frames,
-                        mixed_lengths=mixed_lengths, merge=merge)
+                        mixed_lengths=mixed_lengths, merge=merge, smooth=smooth)
 
 
 def run_annotation(engine, anno, root, pipeline, clip_len=7, stride=4, batch_clips=64, person_threshold=0.5, rng=None, workers=0, lookahead=None,
@@ -564,7 +636,7 @@ def head_arrows(head_boxes, gaze):
     return np.stack([np.stack([cx, cy], axis=1), tip], axis=1).astype(np.int64)
 
 
-def run_head_video(engine, pipeline, frames, boxes_per_frame, max_len=100, batch_frames=448, expand=0.8, rgb=False):
+def run_head_video(engine, pipeline, frames, boxes_per_frame, max_len=100, batch_frames=448, expand=0.8, rgb=False, smooth=None):
     """Steps 3-4 of the demo from what its users hold -- the video's frames and one head box per person per frame -- to per-person gaze:
     segment_tracks (cell 1), the head windows cut, resized and normalised on the device (pipeline.head_crops: cell 4's crop arithmetic and
     ``cfg.data.test.pipeline[1:]``), run_tracks (cell 4's loop, batched), head_arrows (cell 5's end points).
@@ -576,7 +648,11 @@ def run_head_video(engine, pipeline, frames, boxes_per_frame, max_len=100, batch
     group it lands in, so the records do not depend on the grouping.  rescale=True as in the demo: every frame's boxes are divided by ITS
     scale_factor, on the device; they are in pixels of the head window (``crop`` places it in the frame).
     -> one dict per (segment, person), in that order: run_tracks' record (id = (segment, person), det, fused, others) plus frame_id [L],
-    head_box [L,4] f32 (as the device read it), crop [L,4] = y0, x0, h, w of the window, arrow int [L,2,2]."""
+    head_box [L,4] f32 (as the device read it), crop [L,4] = y0, x0, h, w of the window, arrow int [L,2,2].
+    smooth: None, or the alpha in (0, 1] of the temporal filter (tools/calculate_mae_gaze360.py:16-29): every record gains ``fused_smooth``
+    [L,3], the fused gaze filtered over the person's whole track (smooth_host: the track is on the host by then), and ``arrow`` is drawn
+    from it instead of from ``fused``."""
+    smooth = check_smooth('run_head_video', smooth)
     segments = segment_tracks(boxes_per_frame)
     chunks = [(si, a, b, pi) for si, seg in enumerate(segments) for a, b in plan_track_chunks(len(seg['frame_id']), max_len)
               for pi in range(len(seg['boxes']))]
@@ -616,8 +692,10 @@ def run_head_video(engine, pipeline, frames, boxes_per_frame, max_len=100, batch
             got = pieces[(si, pi)]
             rec = {k: np.concatenate([r[k] for r, _ in got]) for k in ('det', 'fused', 'others')}
             head_box = np.asarray(person, dtype=np.float32).reshape(-1, 4)
+            if smooth is not None:
+                rec['fused_smooth'] = smooth_host(rec['fused'], smooth)
             out.append(dict(id=(si, pi), **rec, frame_id=list(seg['frame_id']), head_box=head_box, crop=np.concatenate([c for _, c in got]),
-                            arrow=head_arrows(person, rec['fused'])))
+                            arrow=head_arrows(person, rec['fused' if smooth is None else 'fused_smooth'])))
     return out
 
 

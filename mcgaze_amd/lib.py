@@ -34,7 +34,7 @@ EXPORTS = ['mcg_abi_version', 'mcg_build_id', 'mcg_last_error', 'mcg_device_info
            'mcg_conv3x3_wino_x3_weight_bytes', 'mcg_engine_range_audit', 'mcg_roi_align_indexed', 'mcg_decoder_forward_indexed',
            'mcg_deferred_pyramid_bytes', 'mcg_deferred_pyramid_levels', 'mcg_backbone_fpn_forward_deferred', 'mcg_decoder_forward_deferred',
            'mcg_stage_forward_ragged', 'mcg_decoder_forward_ragged', 'mcg_decoder_forward_deferred_ragged', 'mcg_clip_forward_ragged',
-           'mcg_pyramid_scatter_rows', 'mcg_preprocess_head_crops', 'mcg_merge_windows']
+           'mcg_pyramid_scatter_rows', 'mcg_preprocess_head_crops', 'mcg_merge_windows', 'mcg_smooth_gaze']
 
 
 class ConvDesc(C.Structure):
@@ -131,6 +131,7 @@ def load():
     lib.mcg_clip_forward_ragged.argtypes = [vp, vp, vp, i, vp, i, i, i, i, vp, i, vp, vp, vp, vp, sz]
     lib.mcg_pyramid_scatter_rows.argtypes = [vp, i, C.POINTER(vp), C.POINTER(vp), i, i, i, i, vp]
     lib.mcg_merge_windows.argtypes = [vp, vp, vp, vp, i, vp, i, vp, i, i, vp, i, C.c_float]
+    lib.mcg_smooth_gaze.argtypes = [vp, vp, i, vp, i, C.c_double, vp]
     lib.mcg_preprocess_frames.argtypes =[vp, vp, i, vp, i, i, C.POINTER(C.c_float), C.POINTER(C.c_float), i]
     lib.mcg_preprocess_head_crops.argtypes = [vp, vp, i, vp, vp, i, C.c_double, i, i, vp, vp, vp, vp, vp, i, i, C.POINTER(C.c_float), C.POINTER(C.c_float), i]
     lib.mcg_engine_set_option.argtypes = [vp, C.c_char_p, i]

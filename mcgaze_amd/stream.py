@@ -12,6 +12,9 @@ mcg_decoder_forward_indexed, the gather happens inside the RoIAlign read).
   * ``StreamMerger``: the overlap merge of ``harness.merge_video`` applied window by window, handing out frames once they are final.
   * ``DeviceMerger``: the same merge on the device, for any number of streams -- one store of result rows in device memory, one plan
     upload and one mcg_merge_windows launch per decoder call (``merge='device'`` of GazeStream / GazeStreamPool).
+  * ``StreamSmoother`` / ``DeviceMerger(smooth=alpha)``: the temporal filter the reference's metric runs over every video
+    (tools/calculate_mae_gaze360.py:16-29) as a stream goes -- a frame is handed out one frame late, once its successor is final -- on the
+    host, and on the device as one mcg_smooth_gaze launch per pop over all streams (``smooth=`` of GazeStream / GazeStreamPool).
   * ``GazeStream``: push frames as they arrive, get back the per-frame results that became final; ``finish()`` returns the rest.
   * ``PyramidStore`` / ``GazeStreamPool``: MANY streams at once (S cameras, or the reference demo's one clip per tracked person,
     MCGaze_demo/demo.ipynb cell 4, each the sliding-window loop of tools/test_gaze360_gaze.py:72-111): one store shared by all streams,
@@ -23,7 +26,7 @@ import numpy as np
 import torch
 
 from . import lib as L
-from .harness import _host, bucket_key, clip_outputs, merge_plan, merge_window, plan_windows
+from .harness import _host, bucket_key, check_smooth, clip_outputs, merge_plan, merge_window, plan_windows, smooth_host, smooth_plan
 
 
 class WindowPlanner:
@@ -121,6 +124,44 @@ class StreamMerger:
         return out
 
 
+class StreamSmoother:
+    """The temporal filter of the reference's metric (tools/calculate_mae_gaze360.py:16-29, smooth_filter) on a stream that is still
+    growing, for merge='host': ``push(det, fused, others)`` takes the frames that became final, in order, and returns
+    (det, fused, others, fused_smooth [k,3], others_smooth [k,3,3]) of the frames whose successor is known -- so it runs ONE frame behind
+    what it is fed; ``finish()`` returns the last frame.  det / fused / others pass through with their bits.  The arithmetic is
+    harness.smooth_host's -- mcg_smooth_gaze's -- and over a whole stream the concatenated output equals the filter over the whole
+    sequence bit for bit however the frames were chunked.  It keeps two frames: the last one handed out and the one held back."""
+
+    def __init__(self, alpha=0.6):
+        self.alpha = check_smooth('StreamSmoother', alpha)
+        self.prev = None         # gaze [4,3] (fused | others) of the last frame handed out
+        self.held = None         # (det [1,3,5], fused [1,3], others [1,3,3]) of the newest frame: its successor is not known yet
+        self.finished = False
+
+    def push(self, det, fused, others, ended=False):
+        if self.finished:
+            raise L.McgError('StreamSmoother: push() after finish()')
+        self.finished = bool(ended)
+        parts = [np.asarray(x, dtype=np.float32) for x in (det, fused, others)]
+        if self.held is not None:
+            parts = [np.concatenate([h, x]) for h, x in zip(self.held, parts)]
+        det, fused, others = parts
+        n = det.shape[0]
+        k = n if ended else max(0, n - 1)                  # the newest frame waits for its successor
+        g = np.concatenate([fused[:, None], others], axis=1)                       # [n,4,3]
+        lead = self.prev is not None
+        sm = smooth_host(np.concatenate([self.prev[None], g]) if lead else g, self.alpha, lead=lead, trail=k < n)
+        if k:
+            self.prev = g[k - 1]
+        self.held = None if k == n else tuple(x[k:].copy() for x in parts)
+        return det[:k].copy(), fused[:k].copy(), others[:k].copy(), np.ascontiguousarray(sm[:, 0]), np.ascontiguousarray(sm[:, 1:])
+
+    def finish(self):
+        """The stream ended -> the frame held back (no frame of an empty stream)."""
+        z = np.empty
+        return self.push(z((0, 3, 5), np.float32), z((0, 3), np.float32), z((0, 3, 3), np.float32), ended=True)
+
+
 class _Written:
     """The frames of DeviceMerger's streams that held state before the current call: per stream the range [base, end)."""
 
@@ -142,15 +183,24 @@ class DeviceMerger:
     index_select over all of them, and gives their rows back for reuse.  Nothing here waits for the device unless ``host=True`` asks for
     the popped frames as numpy arrays (one copy for all streams).  Per stream the windows must come in plan order; the concatenated
     output of a stream equals harness.merge_video over its plan bit for bit (tests/test_gpu_device_merge.py).
-    Rows come from a free list; a store that runs out of rows is replaced by one twice as large (a device copy, no sync)."""
+    Rows come from a free list; a store that runs out of rows is replaced by one twice as large (a device copy, no sync).
+
+    smooth=alpha: ``pop`` also returns the frames' gaze after the temporal filter of the reference's metric
+    (tools/calculate_mae_gaze360.py:16-29): (det, fused, others, fused_smooth [k,3], others_smooth [k,3,3]) per item, from ONE
+    mcg_smooth_gaze launch over all items (a host-built table, harness.smooth_plan) beside the index_select.  A frame needs its
+    successor, so it is handed out once the successor is final or the stream has ended (``ended``: the keys of such streams): ``pop``
+    then runs one frame behind what it returns without smoothing.  The row of the last frame handed out stays allocated, as the next
+    frame's predecessor, until that frame has been handed out, the stream has ended, or ``forget``.  det / fused / others keep their bits."""
 
     ROW = 27
+    SMOOTH_ROW = 12
 
     class _Stream:
         def __init__(self):
             self.base, self.end, self.rows = 0, 0, {}      # frames handed out / written so far; frame -> store row of the live frames
 
-    def __init__(self, device, person_threshold=0.5, rows=256):
+    def __init__(self, device, person_threshold=0.5, rows=256, smooth=None):
+        self.smooth = check_smooth('DeviceMerger', smooth)
         self.device = torch.device(device)
         if self.device.type != 'cuda':
             raise L.McgError(f'DeviceMerger: merging on the device needs a HIP device (got {self.device}); there is no CPU fallback path')
@@ -215,6 +265,8 @@ class DeviceMerger:
     def pop_rows(self, items):
         """items: [(key, upto)] -> (rows [K,27], [k per item]): the frames [handed out, min(upto, written)) of every item's stream, item after
         item, gathered into ONE fresh device tensor by one index_select; their store rows are free for reuse."""
+        if self.smooth is not None:
+            raise L.McgError('DeviceMerger.pop_rows: a smoothing merger hands frames out one frame late: pop() or pop_smooth_rows()')
         rows, counts = [], []
         for key, upto in items:
             st = self.streams.get(key)
@@ -229,16 +281,59 @@ class DeviceMerger:
         self._free.extend(reversed(rows))                  # later launches on this stream run after the gather
         return packed, counts
 
-    def pop(self, items, host=False):
+    def pop_smooth_rows(self, items, ended=()):
+        """pop_rows of a smoothing merger -> (rows [K,27], smoothed [K,12] = fused 3 | others 3x3, [k per item]): per item the frames
+        [handed out, min(upto, written)) but the last one -- all of them for a stream in ``ended`` -- gathered by one index_select and
+        filtered by one mcg_smooth_gaze launch.  Of the rows handed out, each stream's last stays allocated unless the stream has ended."""
+        if self.smooth is None:
+            raise L.McgError('DeviceMerger.pop_smooth_rows: this merger was made without smooth=')
+        rows, counts, plans, freed = [], [], [], []
+        for key, upto in items:
+            st = self.streams.get(key)
+            over = key in ended
+            final = 0 if st is None else min(int(upto), st.end)
+            k = 0 if st is None else max(0, final - st.base - (0 if over else 1))
+            if k:
+                frames = range(st.base, st.base + k)
+                plans.append(smooth_plan(frames, st.rows.__getitem__, 0, st.end - 1 if over else None, self.store.shape[0]))
+                rows += plans[-1][:, 1].tolist()
+                st.base += k
+            if st is not None:                             # the rows below the last frame handed out are no one's neighbour any more
+                keep = st.base - (0 if over and st.base == st.end else 1)
+                freed += [st.rows.pop(f) for f in sorted(f for f in st.rows if f < keep)]
+            counts.append(k)
+        if not rows:
+            self._free.extend(reversed(freed))
+            z = lambda w: torch.empty(0, w, dtype=torch.float32, device=self.device)
+            return z(self.ROW), z(self.SMOOTH_ROW), counts
+        packed = self.store.index_select(0, self._upload(np.asarray(rows, dtype=np.int64), self.device))
+        smoothed = torch.empty(len(rows), self.SMOOTH_ROW, dtype=torch.float32, device=self.device)
+        plan = self._upload(np.concatenate(plans), self.device)
+        L.check(self.lib.mcg_smooth_gaze(self._cur(self.device), self._ptr(self.store), self.store.shape[0], self._ptr(plan), len(rows),
+                                         self.smooth, self._ptr(smoothed)), 'mcg_smooth_gaze')
+        self._free.extend(reversed(freed))                 # later launches on this stream run after the gather and the filter
+        return packed, smoothed, counts
+
+    def pop(self, items, host=False, ended=()):
         """pop_rows as one (det [k,3,5], fused [k,3], others [k,3,3]) per item: views of the gathered tensor on the device, or (host=True)
-        numpy arrays after ONE copy to the host for all items together."""
-        packed, counts = self.pop_rows(items)
-        if host:
-            packed = packed.cpu().numpy()
+        numpy arrays after ONE copy to the host for all items together.  A smoothing merger (pop_smooth_rows; ``ended``: the keys whose
+        stream is over) adds fused_smooth [k,3] and others_smooth [k,3,3] to every item."""
+        if self.smooth is not None:
+            packed, smoothed, counts = self.pop_smooth_rows(items, ended)
+            if host:
+                packed = torch.cat([packed, smoothed], dim=1).cpu().numpy()
+                smoothed = packed[:, self.ROW:]
+        else:
+            packed, counts = self.pop_rows(items)
+            if host:
+                packed = packed.cpu().numpy()
         res, at = [], 0
         for k in counts:
             r = packed[at:at + k]
-            res.append((r[:, :15].reshape(k, 3, 5), r[:, 15:18], r[:, 18:].reshape(k, 3, 3)))
+            res.append((r[:, :15].reshape(k, 3, 5), r[:, 15:18], r[:, 18:27].reshape(k, 3, 3)))
+            if self.smooth is not None:
+                m = smoothed[at:at + k]
+                res[-1] += (m[:, :3], m[:, 3:].reshape(k, 3, 3))
             at += k
         if host:
             res = [tuple(np.ascontiguousarray(x) for x in r) for r in res]
@@ -333,20 +428,29 @@ class GazeStream:
     merge='device': the windows are merged on the device (``DeviceMerger``: one mcg_merge_windows launch per decoder call) instead of on
     the host after a blocking copy per decoder call -- the same bits.  results='host' then makes ONE copy to the host per push;
     results='device' (needs merge='device') returns the same dicts with f32 tensors on the engine's device: their values are valid on
-    the engine's current stream, and push / finish never wait for the device."""
+    the engine's current stream, and push / finish never wait for the device.
+    smooth: None, or the alpha in (0, 1] of the temporal filter the reference's published accuracy is measured with
+    (tools/calculate_mae_gaze360.py:16-29; 0.6 there).  The dicts gain ``fused_smooth`` [k,3] and ``others_smooth`` [k,3,3]: every gaze
+    vector mixed with the same vector of the frames before and after it and re-normalised (include/mcgaze_hip.h, mcg_smooth_gaze, states
+    the arithmetic; ``StreamSmoother`` on the host, one mcg_smooth_gaze launch per push with merge='device' -- the same bits).  A frame
+    needs its successor, so every frame is returned ONE frame later than without the option and ``finish`` returns the last; ``first``
+    and the lengths describe the frames a dict holds.  det / fused / others are the bits they are without it; a one-frame stream's
+    smoothed gaze is its gaze, not normalised (the reference's rule).  results='device' keeps its guarantee."""
 
     def __init__(self, engine_or_model, H, W, clip_len=7, stride=4, capacity=None, scale_factor=None, person_threshold=0.5,
-                 max_decode_windows=None, merge='host', results='host'):
+                 max_decode_windows=None, merge='host', results='host', smooth=None):
         e = engine_or_model
         if not hasattr(e, 'decode') and hasattr(e, 'engine'):
             e = e.engine()
         self.e = e
         _check_switches('GazeStream', e, merge, results)
+        smooth = check_smooth('GazeStream', smooth)
         self.results = results
         self.T, self.s = clip_len, stride
         self.planner = WindowPlanner(clip_len, stride)
         self.merger = StreamMerger(person_threshold)
-        self.dmerger = DeviceMerger(e.device, person_threshold, rows=4 * clip_len) if merge == 'device' else None
+        self.dmerger = DeviceMerger(e.device, person_threshold, rows=4 * clip_len, smooth=smooth) if merge == 'device' else None
+        self.smoother = StreamSmoother(smooth) if smooth is not None and merge == 'host' else None
         capacity = clip_len + 64 if capacity is None else int(capacity)
         if capacity <= clip_len:
             raise L.McgError(f'GazeStream: capacity must exceed clip_len ({capacity} <= {clip_len})')
@@ -369,12 +473,15 @@ class GazeStream:
                 self.merger.add(w, det[k * T:(k + 1) * T], fused[k * T:(k + 1) * T], others[k * T:(k + 1) * T])
 
     def _emit(self, upto):
+        over = self.planner.finished
         if self.dmerger is not None:
-            det, fused, others = self.dmerger.pop([(0, upto)], host=self.results == 'host')[0]
+            out = self.dmerger.pop([(0, upto)], host=self.results == 'host', ended=(0,) if over else ())[0]
         else:
-            det, fused, others = self.merger.pop(upto)
-        res = dict(first=self.emitted, det=det, fused=fused, others=others)
-        self.emitted += det.shape[0]
+            out = self.merger.pop(upto)
+            if self.smoother is not None:
+                out = self.smoother.push(*out, ended=over)
+        res = dict(first=self.emitted, **dict(zip(('det', 'fused', 'others', 'fused_smooth', 'others_smooth'), out)))
+        self.emitted += out[0].shape[0]
         return res
 
     def push(self, frames, img_hw=None):
@@ -456,9 +563,10 @@ class PyramidStore:
 class _PoolStream:
     """One stream of a GazeStreamPool: its plan, its merge, where its live frames lie in the store and the frames pushed but not run yet."""
 
-    def __init__(self, clip_len, stride, person_threshold):
+    def __init__(self, clip_len, stride, person_threshold, smooth=None):
         self.planner = WindowPlanner(clip_len, stride)
         self.merger = StreamMerger(person_threshold)
+        self.smoother = None if smooth is None else StreamSmoother(smooth)     # merge='host' only: the device merger filters its own rows
         self.row_of = {}         # frame index -> store row, for the frames a later window may still read
         self.queue = []          # (frames [n,3,H,W], img_hw [n,2] numpy or None) in push order
         self.queued = 0
@@ -513,16 +621,19 @@ class GazeStreamPool:
     merge / results: as for ``GazeStream`` -- merge='device' folds every decoder call into ONE ``DeviceMerger`` shared by all streams (one
     plan upload and one mcg_merge_windows launch per decoder call, where the host merge makes a blocking copy per call and one numpy
     merge per window); results='host' then costs one copy per ``step`` for all streams together, results='device' none: ``step``
-    returns device tensors that are valid on the engine's current stream and never waits for the device."""
+    returns device tensors that are valid on the engine's current stream and never waits for the device.
+    smooth: as for ``GazeStream`` -- every dict gains ``fused_smooth`` and ``others_smooth``, every stream's frames come one frame late and
+    the step that ends a stream returns its last; with merge='device' ONE mcg_smooth_gaze launch per ``step`` covers all streams."""
 
     def __init__(self, engine_or_model, H, W, clip_len=7, stride=4, rows=None, scale_factor=None, person_threshold=0.5, max_decode_windows=None,
-                 max_trunk_frames=448, merge='host', results='host'):
+                 max_trunk_frames=448, merge='host', results='host', smooth=None):
         e = engine_or_model
         if not hasattr(e, 'decode') and hasattr(e, 'engine'):
             e = e.engine()
         _check_switches('GazeStreamPool', e, merge, results)
+        self.smooth = check_smooth('GazeStreamPool', smooth)
         self.results = results
-        self.dmerger = DeviceMerger(e.device, person_threshold, rows=16 * (clip_len + stride)) if merge == 'device' else None
+        self.dmerger = DeviceMerger(e.device, person_threshold, rows=16 * (clip_len + stride), smooth=self.smooth) if merge == 'device' else None
         self.e, self.H, self.W = e, H, W
         self.T, self.s, self.thr = clip_len, stride, person_threshold
         WindowPlanner(clip_len, stride)                     # rejects a bad (clip_len, stride) here, not at the first open()
@@ -537,7 +648,7 @@ class GazeStreamPool:
     def open(self):
         sid = self.next_sid
         self.next_sid += 1
-        self.streams[sid] = _PoolStream(self.T, self.s, self.thr)
+        self.streams[sid] = _PoolStream(self.T, self.s, self.thr, None if self.dmerger is not None else self.smooth)
         return sid
 
     def _stream(self, sid, what):
@@ -646,13 +757,16 @@ class GazeStreamPool:
         results = {}
         if self.dmerger is not None:                       # one gather (and, results='host', one copy) for all streams together
             popped = self.dmerger.pop([(self.streams[sid], self.streams[sid].planner.frames if self.streams[sid].planner.finished
-                                        else self.streams[sid].planner.final_upto) for sid in touched], host=self.results == 'host')
+                                        else self.streams[sid].planner.final_upto) for sid in touched], host=self.results == 'host',
+                                      ended=[self.streams[sid] for sid in ended])
         for i, sid in enumerate(touched):
             st = self.streams[sid]
-            det, fused, others = popped[i] if self.dmerger is not None else st.merger.pop(st.planner.frames if st.planner.finished else st.planner.final_upto)
-            if det.shape[0] or st.planner.finished:
-                results[sid] = dict(first=st.emitted, det=det, fused=fused, others=others)
-            st.emitted += det.shape[0]
+            out = popped[i] if self.dmerger is not None else st.merger.pop(st.planner.frames if st.planner.finished else st.planner.final_upto)
+            if st.smoother is not None:
+                out = st.smoother.push(*out, ended=st.planner.finished)
+            if out[0].shape[0] or st.planner.finished:
+                results[sid] = dict(first=st.emitted, **dict(zip(('det', 'fused', 'others', 'fused_smooth', 'others_smooth'), out)))
+            st.emitted += out[0].shape[0]
             keep = st.planner.keep_from
             self.store.free([st.row_of.pop(f) for f in range(st.released, keep)])
             st.released = max(st.released, keep)

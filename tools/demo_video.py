@@ -3,14 +3,15 @@
 and the head detector's label files in, per-person per-frame gaze out.
 
 usage: demo_video.py FRAMES_DIR LABELS_DIR CONFIG CHECKPOINT --out gaze.json [--precision f16x3] [--device cuda:0] [--max-len 100]
-                     [--batch-frames 448] [--head-class 1] [--ext jpg]
+                     [--batch-frames 448] [--head-class 1] [--ext jpg] [--smooth ALPHA]
 
 FRAMES_DIR holds 0.<ext>, 1.<ext>, ... (the demo's `frames/`), LABELS_DIR holds 0.txt, 1.txt, ... with lines `class x1 y1 x2 y2` in pixels
 (the demo's `result/labels/`); a frame without a label file shows no head.  CONFIG is the L2CS config, whose test pipeline the demo runs
 on every head crop.  The result file holds one entry per (segment, person) in the notebook's order -- a segment is a run of frames with
 the same number of heads, people are numbered left to right: `frame_id`, `head_box`, `crop` (y0, x0, h, w of the window cut from the
 frame), `gaze` (the fused gaze the notebook draws), `arrow` ((cx, cy) and the tip of the arrow of cell 5), and the per-clue boxes (in
-pixels of the head window, rescale=True), scores and gazes of harness.run_tracks (`det`, `others`)."""
+pixels of the head window, rescale=True), scores and gazes of harness.run_tracks (`det`, `others`).  --smooth ALPHA (the reference's metric
+uses 0.6, tools/calculate_mae_gaze360.py:16-29) adds `gaze_smooth`, the fused gaze filtered over each track, and draws `arrow` from it."""
 import argparse
 import json
 import os
@@ -48,6 +49,7 @@ def main(argv=None):
     ap.add_argument('--batch-frames', type=int, default=448)
     ap.add_argument('--head-class', type=int, default=1)
     ap.add_argument('--ext', default='jpg')
+    ap.add_argument('--smooth', type=float, default=None, metavar='ALPHA', help='temporal filter of the reference\'s metric, alpha in (0, 1]')
     a = ap.parse_args(argv)
     n = len([f for f in os.listdir(a.frames_dir) if f.endswith('.' + a.ext)])      # the notebook: vid_len = len(os.listdir(frames))
     missing = [t for t in range(n) if not os.path.exists(os.path.join(a.frames_dir, f'{t}.{a.ext}'))]
@@ -57,9 +59,11 @@ def main(argv=None):
     per_frame = [harness.read_head_labels(p, a.head_class) if os.path.exists(p) else [] for p in labels]
     model = init_detector(a.config, a.checkpoint, device=a.device, precision=a.precision)
     pipe = DevicePipeline(model.cfg.data.test.pipeline)
-    res = harness.run_head_video(model.engine(), pipe, Frames(a.frames_dir, n, a.ext), per_frame, max_len=a.max_len, batch_frames=a.batch_frames, rgb=True)
+    res = harness.run_head_video(model.engine(), pipe, Frames(a.frames_dir, n, a.ext), per_frame, max_len=a.max_len, batch_frames=a.batch_frames, rgb=True,
+                                 smooth=a.smooth)
     out = [dict(segment=r['id'][0], person=r['id'][1], frame_id=r['frame_id'], head_box=r['head_box'].tolist(), crop=r['crop'].tolist(),
-                gaze=r['fused'].tolist(), arrow=r['arrow'].tolist(), det=r['det'].tolist(), others=r['others'].tolist()) for r in res]
+                gaze=r['fused'].tolist(), arrow=r['arrow'].tolist(), det=r['det'].tolist(), others=r['others'].tolist(),
+                **({} if a.smooth is None else dict(gaze_smooth=r['fused_smooth'].tolist()))) for r in res]
     with open(a.out, 'w') as f:
         json.dump(dict(frames=n, tracks=out), f)
     print(f'{n} frames, {len(out)} (segment, person) tracks, {sum(len(r["frame_id"]) for r in out)} head crops -> {a.out}')
