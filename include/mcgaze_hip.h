@@ -524,6 +524,49 @@ int mcg_preprocess_head_crops(mcg_stream s, const mcg_image_desc* images_dev, in
                               const int32_t* image_of_dev, int n, double expand, int scale_w, int scale_h, mcg_frame_desc* desc_out_dev,
                               int32_t* img_hw_dev, float* scale_factor_dev, int32_t* flags_dev, float* dst, int pad_h, int pad_w,
                               const float mean[3], const float stdinv[3], int to_rgb);
+/* NV12 surfaces in (additions to ABI 18; nothing above changes): the two pixel entries again, reading what a hardware video decoder
+ * delivers -- a full-resolution Y plane and a half-resolution plane of interleaved (U, V) pairs, each with its own pitch -- instead of
+ * packed BGR.  The colour conversion runs per TAP: each of the four source pixels an output pixel interpolates between is converted to
+ * three uint8 values (B, G, R) in 32-bit integers and handed to the unchanged fixed-point resize, normalisation and channel swap, so the
+ * result equals "convert the whole frame to BGR, then call the entry above" bit for bit, and no packed frame is ever written.  Tap (y, x) in
+ * frame coordinates reads Y[y][x], U = UV[y >> 1][2 * (x >> 1)], V = UV[y >> 1][2 * (x >> 1) + 1] (chroma is the NEAREST sample, not
+ * interpolated, as in cv2's COLOR_YUV2BGR_NV12), and with u = U - 128, v = V - 128, >> an arithmetic shift and sat8 a clamp to [0, 255]:
+ *   yy = max(0, Y - y_off) * cy
+ *   R = sat8((yy + cvr * v + (1 << 19)) >> 20);  G = sat8((yy + cvg * v + cug * u + (1 << 19)) >> 20);  B = sat8((yy + cub * u + (1 << 19)) >> 20)
+ * coef: HOST pointer to the six integers (20 fractional bits).  Limited-range BT.601, OpenCV's published constants restated (not linked;
+ * parity with cv2 is not pinned on any machine this was built on): {16, 1220542, 2116026, -409993, -852492, 1673527}.  Limited-range
+ * BT.709 (Kr = 0.2126, Kb = 0.0722, luma 255/219, chroma 255/224, each round(c * 2^20)): {16, 1220945, 2215014, -223607, -558796, 1879825}.
+ * The entries accept any coef whose sums stay inside an int: y_off in [0, 255] and |cy|, |cub|, |cug|, |cvg|, |cvr| < 2^22
+ * (255 * 2^22 + 2 * 128 * 2^22 + 2^19 < 2^31).
+ * h and w of every surface are EVEN; the UV plane is h / 2 rows of w bytes, rows pitch_uv apart.  With even sizes and a window inside the
+ * frame nothing is read outside either plane.  mcg_nv12_frame_desc holds the fields of mcg_frame_desc, src and src_pitch naming the Y plane,
+ * followed by the UV plane and its pitch; mcg_preprocess_head_crops_nv12 takes the arguments of mcg_preprocess_head_crops with the NV12 image table
+ * and descriptor output, writes the same img_hw / scale_factor / flags, and flags an image row whose h or w is odd 2 like one without
+ * pixels.  A flag-2 crop reads pixel (0, 0) of image 0 (Y[0] and UV[0..1] of it): whatever the other rows hold, images_dev[0] must be a
+ * valid surface with even h and w.  to_rgb as above: the converted taps are in BGR order.  No allocation, no host sync, graph-capturable; at most 65535 rows. */
+typedef struct mcg_yuv_coef {
+  int y_off, cy, cub, cug, cvg, cvr;
+} mcg_yuv_coef;
+typedef struct mcg_nv12_image_desc {
+  const void* y;
+  const void* uv;
+  int h, w, pitch_y, pitch_uv;
+} mcg_nv12_image_desc;
+typedef struct mcg_nv12_frame_desc {
+  const void* src;
+  int src_h, src_w, src_pitch;
+  int crop_y, crop_x, crop_h, crop_w;
+  int out_h, out_w;
+  const void* uv;
+  int uv_pitch;
+} mcg_nv12_frame_desc;
+int mcg_preprocess_frames_nv12(mcg_stream stream, const mcg_nv12_frame_desc* frames_dev, int num_frames, float* dst, int pad_h, int pad_w,
+                               const float mean[3], const float stdinv[3], int to_rgb, const mcg_yuv_coef* coef);
+int mcg_preprocess_head_crops_nv12(mcg_stream s, const mcg_nv12_image_desc* images_dev, int num_images, const float* boxes_dev,
+                                   const int32_t* image_of_dev, int n, double expand, int scale_w, int scale_h,
+                                   mcg_nv12_frame_desc* desc_out_dev, int32_t* img_hw_dev, float* scale_factor_dev, int32_t* flags_dev,
+                                   float* dst, int pad_h, int pad_w, const float mean[3], const float stdinv[3], int to_rgb,
+                                   const mcg_yuv_coef* coef);
 
 /* ---------------------------------------------------------------- measurement aids (bench.py)
  * While armed, every launch of the contraction kernel made by THIS engine is bracketed by a hipEvent pair on its launch stream.

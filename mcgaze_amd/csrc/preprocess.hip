@@ -18,6 +18,10 @@
 // that clips at the frame border) and mmcv's rescale_size behind Resize(keep_ratio=True) (transforms.py:216-242), and writes the
 // mcg_frame_desc rows preprocess_kernel reads -- so video frames and a detector's head boxes, both already in device memory, become the
 // model's input without a word going to the host.
+//
+// Both kernels are templates over the pixel SOURCE: packed 8-bit BGR (the entries above), or a video decoder's NV12 surface
+// (mcg_preprocess_frames_nv12, mcg_preprocess_head_crops_nv12), whose four taps are converted to BGR where they are read -- the frame is
+// never converted whole.
 #include "common.hpp"
 
 struct LinCoef {
@@ -40,10 +44,76 @@ __device__ __forceinline__ LinCoef lin_coef(int d, int dst, int src) {
   return c;
 }
 
-__global__ __launch_bounds__(256) void preprocess_kernel(const mcg_frame_desc* __restrict__ frames, float* __restrict__ dst, int pad_h,
-                                                         int pad_w, float m0, float m1, float m2, float s0, float s1, float s2, int to_rgb) {
+// Where the pixels come from.  A source names its descriptor types, reads ONE tap -- source pixel (sy, sx) of the crop window -- as three
+// uint8 values in cv2's order (B, G, R), and tells the plan kernel which image rows it can read and how to point a descriptor at one.
+// Everything after the taps (the two fixed-point passes, the normalisation, the channel swap) is the same code for every source.
+struct PackedSource {                                       // 3 interleaved 8-bit channels
+  using Frame = mcg_frame_desc;
+  using Image = mcg_image_desc;
+  struct Window {
+    const unsigned char* base;
+    size_t pitch;
+  };
+  __device__ __forceinline__ Window window(const Frame& fd) const {
+    return {(const unsigned char*)fd.src + (size_t)fd.crop_y * fd.src_pitch + (size_t)fd.crop_x * 3, (size_t)fd.src_pitch};
+  }
+  __device__ __forceinline__ void tap(const Window& w, int sy, int sx, int p[3]) const {
+    const unsigned char* q = w.base + (size_t)sy * w.pitch + sx * 3;
+    p[0] = q[0]; p[1] = q[1]; p[2] = q[2];
+  }
+  static __device__ __forceinline__ bool readable(const Image& im) { return im.h > 0 && im.w > 0; }
+  static __device__ __forceinline__ void point(Frame& d, const Image& im) {
+    d.src = im.src;
+    d.src_pitch = im.pitch;
+  }
+};
+
+// NV12: a Y plane and a half-resolution plane of interleaved (U, V) pairs.  The tap is converted where it is read, in 32-bit integers:
+// OpenCV's published COLOR_YUV2BGR_NV12 arithmetic restated (not linked; parity with cv2 is not pinned on any machine this was built on)
+//   yy = max(0, Y - y_off) * cy;  R = sat8((yy + cvr * v + 2^19) >> 20), G = sat8((yy + cvg * v + cug * u + 2^19) >> 20), B = sat8((yy + cub * u + 2^19) >> 20)
+// with u = U - 128, v = V - 128 and chroma taken from the NEAREST sample, UV[y >> 1][2 * (x >> 1)] -- (y, x) in FRAME coordinates, so an odd
+// crop origin lands on the right chroma phase.  Largest intermediate, BT.601: 239 * 1220542 + 127 * 2116026 + 2^19 = 560,969,128; BT.709:
+// 239 * 1220945 + 127 * 2215014 + 2^19 = 573,636,921; most negative -128 * 2215014 = -283,521,792: all far inside an int (the entry refuses
+// coefficients for which they could leave it).  h and w even and the window inside the frame: y >> 1 <= h / 2 - 1 and 2 * (x >> 1) + 1 <= w - 1.
+struct Nv12Source {
+  using Frame = mcg_nv12_frame_desc;
+  using Image = mcg_nv12_image_desc;
+  mcg_yuv_coef k;
+  struct Window {
+    const unsigned char *y, *uv;
+    size_t pitch_y, pitch_uv;
+    int y0, x0;
+  };
+  __device__ __forceinline__ Window window(const Frame& fd) const {
+    return {(const unsigned char*)fd.src, (const unsigned char*)fd.uv, (size_t)fd.src_pitch, (size_t)fd.uv_pitch, fd.crop_y, fd.crop_x};
+  }
+  static __device__ __forceinline__ int sat8(int v) { return min(max(v >> 20, 0), 255); }
+  __device__ __forceinline__ void tap(const Window& w, int sy, int sx, int p[3]) const {
+    const int y = w.y0 + sy, x = w.x0 + sx;
+    const unsigned char* c = w.uv + (size_t)(y >> 1) * w.pitch_uv + 2 * (x >> 1);
+    const int yy = max(0, (int)w.y[(size_t)y * w.pitch_y + x] - k.y_off) * k.cy + (1 << 19);
+    const int u = (int)c[0] - 128, v = (int)c[1] - 128;
+    p[0] = sat8(yy + k.cub * u);
+    p[1] = sat8(yy + k.cvg * v + k.cug * u);
+    p[2] = sat8(yy + k.cvr * v);
+  }
+  // an odd size has no whole chroma sample for its last row / column: such a row is not read (flag 2), like one without pixels.  (A flag-2
+  // crop reads pixel (0, 0) of image 0, i.e. Y[0] and UV[0..1]: image 0 has to be a surface with even sizes -- the header says so.)
+  static __device__ __forceinline__ bool readable(const Image& im) { return im.h > 0 && im.w > 0 && !((im.h | im.w) & 1); }
+  static __device__ __forceinline__ void point(Frame& d, const Image& im) {
+    d.src = im.y;
+    d.src_pitch = im.pitch_y;
+    d.uv = im.uv;
+    d.uv_pitch = im.pitch_uv;
+  }
+};
+
+template <class Source>
+__global__ __launch_bounds__(256) void preprocess_kernel(const typename Source::Frame* __restrict__ frames, float* __restrict__ dst, int pad_h,
+                                                         int pad_w, float m0, float m1, float m2, float s0, float s1, float s2, int to_rgb,
+                                                         const Source source) {
 #pragma clang fp contract(off)
-  const mcg_frame_desc fd = frames[blockIdx.y];
+  const typename Source::Frame fd = frames[blockIdx.y];
   const int idx = blockIdx.x * 256 + threadIdx.x;
   if (idx >= pad_h * pad_w) return;
   const int y = idx / pad_w, x = idx - y * pad_w;
@@ -54,33 +124,58 @@ __global__ __launch_bounds__(256) void preprocess_kernel(const mcg_frame_desc* _
     return;
   }
   const LinCoef cx = lin_coef(x, fd.out_w, fd.crop_w), cy = lin_coef(y, fd.out_h, fd.crop_h);
-  const unsigned char* base = (const unsigned char*)fd.src + (size_t)fd.crop_y * fd.src_pitch + (size_t)fd.crop_x * 3;
-  const unsigned char* r0 = base + (size_t)cy.s0 * fd.src_pitch;
-  const unsigned char* r1 = base + (size_t)cy.s1 * fd.src_pitch;
+  const typename Source::Window win = source.window(fd);
+  int p00[3], p01[3], p10[3], p11[3];
+  source.tap(win, cy.s0, cx.s0, p00);
+  source.tap(win, cy.s0, cx.s1, p01);
+  source.tap(win, cy.s1, cx.s0, p10);
+  source.tap(win, cy.s1, cx.s1, p11);
   int v[3];
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
-    const int h0 = (int)r0[cx.s0 * 3 + c] * cx.a0 + (int)r0[cx.s1 * 3 + c] * cx.a1;
-    const int h1 = (int)r1[cx.s0 * 3 + c] * cx.a0 + (int)r1[cx.s1 * 3 + c] * cx.a1;
+    const int h0 = p00[c] * cx.a0 + p01[c] * cx.a1;
+    const int h1 = p10[c] * cx.a0 + p11[c] * cx.a1;
     v[c] = (((cy.a0 * (h0 >> 4)) >> 16) + ((cy.a1 * (h1 >> 4)) >> 16) + 2) >> 2;
   }
-  const int c0 = to_rgb ? 2 : 0, c2 = to_rgb ? 0 : 2;  // source is BGR
+  const int c0 = to_rgb ? 2 : 0, c2 = to_rgb ? 0 : 2;  // taps are BGR
   out[0] = ((float)v[c0] - m0) * s0;
   out[plane] = ((float)v[1] - m1) * s1;
   out[2 * plane] = ((float)v[c2] - m2) * s2;
 }
 
-extern "C" int mcg_preprocess_frames(mcg_stream stream, const mcg_frame_desc* frames_dev, int num_frames, float* dst, int pad_h, int pad_w,
-                                     const float mean[3], const float stdinv[3], int to_rgb) {
-  MCG_CHECK_ARG(frames_dev && dst && mean && stdinv, "mcg_preprocess_frames: null pointer");
-  MCG_CHECK_ARG(num_frames >= 0 && pad_h > 0 && pad_w > 0, "mcg_preprocess_frames: bad sizes n=%d pad=%dx%d", num_frames, pad_h, pad_w);
-  MCG_CHECK_ARG(num_frames <= 65535, "mcg_preprocess_frames: at most 65535 frames per call (got %d)", num_frames);
+template <class Source>
+static int preprocess_frames(const char* what, const Source& source, mcg_stream stream, const typename Source::Frame* frames_dev, int num_frames,
+                             float* dst, int pad_h, int pad_w, const float mean[3], const float stdinv[3], int to_rgb) {
+  MCG_CHECK_ARG(frames_dev && dst && mean && stdinv, "%s: null pointer", what);
+  MCG_CHECK_ARG(num_frames >= 0 && pad_h > 0 && pad_w > 0, "%s: bad sizes n=%d pad=%dx%d", what, num_frames, pad_h, pad_w);
+  MCG_CHECK_ARG(num_frames <= 65535, "%s: at most 65535 frames per call (got %d)", what, num_frames);
   if (num_frames == 0) return MCG_OK;
   dim3 grid((pad_h * pad_w + 255) / 256, num_frames);
-  hipLaunchKernelGGL(preprocess_kernel, grid, dim3(256), 0, (hipStream_t)stream, frames_dev, dst, pad_h, pad_w, mean[0], mean[1], mean[2],
-                     stdinv[0], stdinv[1], stdinv[2], to_rgb);
-  MCG_CHECK_LAUNCH("mcg_preprocess_frames");
+  hipLaunchKernelGGL(preprocess_kernel<Source>, grid, dim3(256), 0, (hipStream_t)stream, frames_dev, dst, pad_h, pad_w, mean[0], mean[1], mean[2],
+                     stdinv[0], stdinv[1], stdinv[2], to_rgb, source);
+  MCG_CHECK_LAUNCH(what);
   return MCG_OK;
+}
+
+extern "C" int mcg_preprocess_frames(mcg_stream stream, const mcg_frame_desc* frames_dev, int num_frames, float* dst, int pad_h, int pad_w,
+                                     const float mean[3], const float stdinv[3], int to_rgb) {
+  return preprocess_frames("mcg_preprocess_frames", PackedSource{}, stream, frames_dev, num_frames, dst, pad_h, pad_w, mean, stdinv, to_rgb);
+}
+
+// 255 * 2^22 + 2 * 128 * 2^22 + 2^19 < 2^31: with these limits no sum of the conversion leaves an int
+static int check_yuv_coef(const char* what, const mcg_yuv_coef* k) {
+  MCG_CHECK_ARG(k, "%s: null coef", what);
+  constexpr int lim = 1 << 22;
+  const auto inside = [](int c) { return c > -lim && c < lim; };      // (not abs(): abs(INT_MIN) is not a positive number)
+  MCG_CHECK_ARG(k->y_off >= 0 && k->y_off <= 255 && inside(k->cy) && inside(k->cub) && inside(k->cug) && inside(k->cvg) && inside(k->cvr),
+                "%s: coef {%d, %d, %d, %d, %d, %d} outside y_off in [0, 255], |c| < 2^22", what, k->y_off, k->cy, k->cub, k->cug, k->cvg, k->cvr);
+  return MCG_OK;
+}
+
+extern "C" int mcg_preprocess_frames_nv12(mcg_stream stream, const mcg_nv12_frame_desc* frames_dev, int num_frames, float* dst, int pad_h,
+                                          int pad_w, const float mean[3], const float stdinv[3], int to_rgb, const mcg_yuv_coef* coef) {
+  if (int rc = check_yuv_coef("mcg_preprocess_frames_nv12", coef)) return rc;
+  return preprocess_frames("mcg_preprocess_frames_nv12", Nv12Source{*coef}, stream, frames_dev, num_frames, dst, pad_h, pad_w, mean, stdinv, to_rgb);
 }
 
 // MCGaze_demo/demo.ipynb, cell 4, per (person, frame) -- in double, uncontracted: python floats, and int(w * f + 0.5) must not fuse.
@@ -104,10 +199,11 @@ __device__ __forceinline__ Span head_span(double a, double b, double l, int size
   return s;
 }
 
-__global__ __launch_bounds__(256) void head_crop_plan_kernel(const mcg_image_desc* __restrict__ images, int num_images,
+template <class Source>
+__global__ __launch_bounds__(256) void head_crop_plan_kernel(const typename Source::Image* __restrict__ images, int num_images,
                                                              const float* __restrict__ boxes, const int32_t* __restrict__ image_of, int n,
                                                              double expand, int scale_long, int scale_short, int pad_h, int pad_w,
-                                                             mcg_frame_desc* __restrict__ desc, int32_t* __restrict__ img_hw,
+                                                             typename Source::Frame* __restrict__ desc, int32_t* __restrict__ img_hw,
                                                              float* __restrict__ scale_factor, int32_t* __restrict__ flags) {
 #pragma clang fp contract(off)
   const int k = blockIdx.x * 256 + threadIdx.x;
@@ -115,8 +211,8 @@ __global__ __launch_bounds__(256) void head_crop_plan_kernel(const mcg_image_des
   const double x1 = boxes[4 * k], y1 = boxes[4 * k + 1], x2 = boxes[4 * k + 2], y2 = boxes[4 * k + 3];   // f32 -> double: exact
   const int io = image_of[k];
   bool usable = io >= 0 && io < num_images && isfinite(x1) && isfinite(y1) && isfinite(x2) && isfinite(y2);
-  mcg_image_desc im = images[usable ? io : 0];
-  if (usable && (im.h <= 0 || im.w <= 0)) {               // an image row with no pixels names nothing to read either
+  typename Source::Image im = images[usable ? io : 0];
+  if (usable && !Source::readable(im)) {                  // an image row with no pixels names nothing to read either
     usable = false;
     im = images[0];
   }
@@ -136,9 +232,9 @@ __global__ __launch_bounds__(256) void head_crop_plan_kernel(const mcg_image_des
   const double f = fmin((double)scale_long / (double)max(h, w), (double)scale_short / (double)min(h, w));
   // at least one pixel (a 1 x 1000 sliver would round to zero columns, which cv2.resize refuses), at most the padded frame
   const int new_w = min(max((int)((double)w * f + 0.5), 1), pad_w), new_h = min(max((int)((double)h * f + 0.5), 1), pad_h);
-  mcg_frame_desc d;
-  d.src = im.src;
-  d.src_h = im.h; d.src_w = im.w; d.src_pitch = im.pitch;
+  typename Source::Frame d;
+  Source::point(d, im);
+  d.src_h = im.h; d.src_w = im.w;
   d.crop_y = ys.lo; d.crop_x = xs.lo; d.crop_h = h; d.crop_w = w;
   d.out_h = new_h; d.out_w = new_w;
   desc[k] = d;
@@ -149,24 +245,42 @@ __global__ __launch_bounds__(256) void head_crop_plan_kernel(const mcg_image_des
   if (flags) flags[k] = flag;
 }
 
+template <class Source>
+static int preprocess_head_crops(const char* what, const char* what_plan, const Source& source, mcg_stream stream, const typename Source::Image* images_dev, int num_images,
+                                 const float* boxes_dev, const int32_t* image_of_dev, int n, double expand, int scale_w, int scale_h,
+                                 typename Source::Frame* desc_out_dev, int32_t* img_hw_dev, float* scale_factor_dev, int32_t* flags_dev, float* dst,
+                                 int pad_h, int pad_w, const float mean[3], const float stdinv[3], int to_rgb) {
+  MCG_CHECK_ARG(images_dev && boxes_dev && image_of_dev && desc_out_dev && img_hw_dev && scale_factor_dev && dst && mean && stdinv,
+                "%s: null pointer", what);
+  MCG_CHECK_ARG(n >= 0 && num_images >= 1 && scale_w > 0 && scale_h > 0, "%s: bad sizes n=%d images=%d scale=%dx%d", what, n, num_images, scale_w,
+                scale_h);
+  MCG_CHECK_ARG(n <= 65535, "%s: at most 65535 crops per call (got %d)", what, n);
+  MCG_CHECK_ARG(expand == expand && expand - expand == 0.0, "%s: expand must be finite", what);
+  // keep_ratio puts the LONG edge of img_scale on the window's long side, whichever that is: a non-square scale needs room for it both ways
+  const int need_h = scale_w == scale_h ? scale_h : max(scale_w, scale_h), need_w = scale_w == scale_h ? scale_w : max(scale_w, scale_h);
+  MCG_CHECK_ARG(pad_h >= need_h && pad_w >= need_w, "%s: pad %dx%d cannot hold img_scale (%d, %d)", what, pad_h, pad_w, scale_w, scale_h);
+  if (n == 0) return MCG_OK;
+  hipLaunchKernelGGL(head_crop_plan_kernel<Source>, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, images_dev, num_images, boxes_dev,
+                     image_of_dev, n, expand, max(scale_w, scale_h), min(scale_w, scale_h), pad_h, pad_w, desc_out_dev, img_hw_dev,
+                     scale_factor_dev, flags_dev);
+  MCG_CHECK_LAUNCH(what_plan);
+  return preprocess_frames(what, source, stream, desc_out_dev, n, dst, pad_h, pad_w, mean, stdinv, to_rgb);
+}
+
 extern "C" int mcg_preprocess_head_crops(mcg_stream stream, const mcg_image_desc* images_dev, int num_images, const float* boxes_dev,
                                          const int32_t* image_of_dev, int n, double expand, int scale_w, int scale_h,
                                          mcg_frame_desc* desc_out_dev, int32_t* img_hw_dev, float* scale_factor_dev, int32_t* flags_dev,
                                          float* dst, int pad_h, int pad_w, const float mean[3], const float stdinv[3], int to_rgb) {
-  MCG_CHECK_ARG(images_dev && boxes_dev && image_of_dev && desc_out_dev && img_hw_dev && scale_factor_dev && dst && mean && stdinv,
-                "mcg_preprocess_head_crops: null pointer");
-  MCG_CHECK_ARG(n >= 0 && num_images >= 1 && scale_w > 0 && scale_h > 0, "mcg_preprocess_head_crops: bad sizes n=%d images=%d scale=%dx%d", n,
-                num_images, scale_w, scale_h);
-  MCG_CHECK_ARG(n <= 65535, "mcg_preprocess_head_crops: at most 65535 crops per call (got %d)", n);
-  MCG_CHECK_ARG(expand == expand && expand - expand == 0.0, "mcg_preprocess_head_crops: expand must be finite");
-  // keep_ratio puts the LONG edge of img_scale on the window's long side, whichever that is: a non-square scale needs room for it both ways
-  const int need_h = scale_w == scale_h ? scale_h : max(scale_w, scale_h), need_w = scale_w == scale_h ? scale_w : max(scale_w, scale_h);
-  MCG_CHECK_ARG(pad_h >= need_h && pad_w >= need_w, "mcg_preprocess_head_crops: pad %dx%d cannot hold img_scale (%d, %d)", pad_h, pad_w, scale_w,
-                scale_h);
-  if (n == 0) return MCG_OK;
-  hipLaunchKernelGGL(head_crop_plan_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, images_dev, num_images, boxes_dev,
-                     image_of_dev, n, expand, max(scale_w, scale_h), min(scale_w, scale_h), pad_h, pad_w, desc_out_dev, img_hw_dev,
-                     scale_factor_dev, flags_dev);
-  MCG_CHECK_LAUNCH("mcg_preprocess_head_crops (plan)");
-  return mcg_preprocess_frames(stream, desc_out_dev, n, dst, pad_h, pad_w, mean, stdinv, to_rgb);
+  return preprocess_head_crops("mcg_preprocess_head_crops", "mcg_preprocess_head_crops (plan)", PackedSource{}, stream, images_dev, num_images, boxes_dev, image_of_dev, n, expand, scale_w,
+                               scale_h, desc_out_dev, img_hw_dev, scale_factor_dev, flags_dev, dst, pad_h, pad_w, mean, stdinv, to_rgb);
+}
+
+extern "C" int mcg_preprocess_head_crops_nv12(mcg_stream stream, const mcg_nv12_image_desc* images_dev, int num_images, const float* boxes_dev,
+                                              const int32_t* image_of_dev, int n, double expand, int scale_w, int scale_h,
+                                              mcg_nv12_frame_desc* desc_out_dev, int32_t* img_hw_dev, float* scale_factor_dev,
+                                              int32_t* flags_dev, float* dst, int pad_h, int pad_w, const float mean[3], const float stdinv[3],
+                                              int to_rgb, const mcg_yuv_coef* coef) {
+  if (int rc = check_yuv_coef("mcg_preprocess_head_crops_nv12", coef)) return rc;
+  return preprocess_head_crops("mcg_preprocess_head_crops_nv12", "mcg_preprocess_head_crops_nv12 (plan)", Nv12Source{*coef}, stream, images_dev, num_images, boxes_dev, image_of_dev, n, expand,
+                               scale_w, scale_h, desc_out_dev, img_hw_dev, scale_factor_dev, flags_dev, dst, pad_h, pad_w, mean, stdinv, to_rgb);
 }

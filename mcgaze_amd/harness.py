@@ -636,13 +636,16 @@ def head_arrows(head_boxes, gaze):
     return np.stack([np.stack([cx, cy], axis=1), tip], axis=1).astype(np.int64)
 
 
-def run_head_video(engine, pipeline, frames, boxes_per_frame, max_len=100, batch_frames=448, expand=0.8, rgb=False, smooth=None):
+def run_head_video(engine, pipeline, frames, boxes_per_frame, max_len=100, batch_frames=448, expand=0.8, rgb=False, smooth=None, pixel_format='bgr',
+                   matrix='bt601'):
     """Steps 3-4 of the demo from what its users hold -- the video's frames and one head box per person per frame -- to per-person gaze:
     segment_tracks (cell 1), the head windows cut, resized and normalised on the device (pipeline.head_crops: cell 4's crop arithmetic and
     ``cfg.data.test.pipeline[1:]``), run_tracks (cell 4's loop, batched), head_arrows (cell 5's end points).
 
     frames: sequence of HxWx3 uint8 frames, numpy arrays (cv2's BGR; rgb=True: RGB) or tensors on the engine's device, indexed by frame
     number; boxes_per_frame[t]: the head boxes of frame t.  pipeline: a DevicePipeline of the L2CS config's test pipeline.
+    pixel_format='nv12': frames[t] is a decoder's NV12 surface instead -- a (y, uv) pair or one [3H/2, W] array, on the host or the device -- read
+    as it is, with the YUV -> RGB coefficients ``matrix`` names (pipeline.head_crops; rgb is ignored).
     The work goes in groups of about batch_frames crops -- whole chunks (plan_track_chunks), the people of a segment side by side, so that
     a frame showing P heads is uploaded once per group and a long video never has all its crops resident: a chunk is one clip whichever
     group it lands in, so the records do not depend on the grouping.  rescale=True as in the demo: every frame's boxes are divided by ITS
@@ -669,7 +672,7 @@ def run_head_video(engine, pipeline, frames, boxes_per_frame, max_len=100, batch
                 image_of.append(slot[t])
                 boxes.append(segments[si]['boxes'][pi][j])
         img, img_hw, scale, crop, _ = pipeline.head_crops(images, np.asarray(boxes, dtype=np.float32).reshape(-1, 4), np.asarray(image_of, dtype=np.int32),
-                                                          expand=expand, device=engine.device, rgb=rgb)
+                                                          expand=expand, device=engine.device, rgb=rgb, pixel_format=pixel_format, matrix=matrix)
         rows = np.concatenate([[0], np.cumsum([b - a for _, a, b, _ in group])])
         tracks = [dict(id=k, frames=img[r0:r1], img_hw=img_hw[r0:r1], scale_factor=scale[r0:r1]) for k, (r0, r1) in enumerate(zip(rows[:-1], rows[1:]))]
         records = run_tracks(engine, tracks, max_len=max_len, batch_frames=batch_frames)

@@ -34,7 +34,8 @@ EXPORTS = ['mcg_abi_version', 'mcg_build_id', 'mcg_last_error', 'mcg_device_info
            'mcg_conv3x3_wino_x3_weight_bytes', 'mcg_engine_range_audit', 'mcg_roi_align_indexed', 'mcg_decoder_forward_indexed',
            'mcg_deferred_pyramid_bytes', 'mcg_deferred_pyramid_levels', 'mcg_backbone_fpn_forward_deferred', 'mcg_decoder_forward_deferred',
            'mcg_stage_forward_ragged', 'mcg_decoder_forward_ragged', 'mcg_decoder_forward_deferred_ragged', 'mcg_clip_forward_ragged',
-           'mcg_pyramid_scatter_rows', 'mcg_preprocess_head_crops', 'mcg_merge_windows', 'mcg_smooth_gaze']
+           'mcg_pyramid_scatter_rows', 'mcg_preprocess_head_crops', 'mcg_merge_windows', 'mcg_smooth_gaze', 'mcg_preprocess_frames_nv12',
+           'mcg_preprocess_head_crops_nv12']
 
 
 class ConvDesc(C.Structure):
@@ -69,6 +70,18 @@ class FrameDesc(C.Structure):
 
 class ImageDesc(C.Structure):
     _fields_ = [('src', C.c_void_p), ('h', C.c_int), ('w', C.c_int), ('pitch', C.c_int)]
+
+
+class YuvCoef(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ('y_off', 'cy', 'cub', 'cug', 'cvg', 'cvr')]
+
+
+class Nv12ImageDesc(C.Structure):
+    _fields_ = [('y', C.c_void_p), ('uv', C.c_void_p), ('h', C.c_int), ('w', C.c_int), ('pitch_y', C.c_int), ('pitch_uv', C.c_int)]
+
+
+class Nv12FrameDesc(C.Structure):
+    _fields_ = FrameDesc._fields_ + [('uv', C.c_void_p), ('uv_pitch', C.c_int)]
 
 
 class McgError(RuntimeError):
@@ -134,6 +147,8 @@ def load():
     lib.mcg_smooth_gaze.argtypes = [vp, vp, i, vp, i, C.c_double, vp]
     lib.mcg_preprocess_frames.argtypes =[vp, vp, i, vp, i, i, C.POINTER(C.c_float), C.POINTER(C.c_float), i]
     lib.mcg_preprocess_head_crops.argtypes = [vp, vp, i, vp, vp, i, C.c_double, i, i, vp, vp, vp, vp, vp, i, i, C.POINTER(C.c_float), C.POINTER(C.c_float), i]
+    lib.mcg_preprocess_frames_nv12.argtypes = lib.mcg_preprocess_frames.argtypes + [C.POINTER(YuvCoef)]
+    lib.mcg_preprocess_head_crops_nv12.argtypes = lib.mcg_preprocess_head_crops.argtypes + [C.POINTER(YuvCoef)]
     lib.mcg_engine_set_option.argtypes = [vp, C.c_char_p, i]
     lib.mcg_engine_profile_start.argtypes = [vp, i]
     lib.mcg_engine_profile_stop.argtypes = [vp, C.POINTER(i), C.POINTER(C.c_float), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(i), C.POINTER(i), i]

@@ -16,6 +16,8 @@ device as they are, and the kernel writes the model's ``img`` tensor.  There is 
 Head crops (``DevicePipeline.head_crops``): the demo of the reference (MCGaze_demo/demo.ipynb, cell 4) cuts one window per person out of
 every video frame before this chain; there the WINDOW is chosen on the device as well (``mcg_preprocess_head_crops``), from frames and head
 boxes that may both live in device memory already.  ``head_crop_window`` is the same arithmetic on the host, for checks and for drawing.
+With ``pixel_format='nv12'`` the frames are a video decoder's NV12 surfaces, converted tap by tap inside the pixel kernel
+(``mcg_preprocess_head_crops_nv12``); ``nv12_to_bgr`` is that conversion on the host.
 
 Randomness: the reference's ``CenterCrop(crop_type='relative_range')`` draws the crop size from the global numpy RNG at TEST
 time too (transforms.py:1126-1130), and ``RandomFlip(flip_ratio=0.0)`` consumes one more uniform
@@ -525,7 +527,96 @@ assert _DESC.itemsize == C.sizeof(L.FrameDesc) and all(_DESC.fields[n][1] == get
 _IMAGE = np.dtype([('src', np.uint64), ('h', np.int32), ('w', np.int32), ('pitch', np.int32)], align=True)   # lib.ImageDesc / mcg_image_desc
 assert _IMAGE.itemsize == C.sizeof(L.ImageDesc) and all(_IMAGE.fields[n][1] == getattr(L.ImageDesc, n).offset for n in _IMAGE.names)
 _DESC_WORDS = _DESC.itemsize // 4
+# the NV12 records: lib.Nv12ImageDesc / mcg_nv12_image_desc, and mcg_nv12_frame_desc = the fields of _DESC, then the UV plane and its pitch
+_NV12_IMAGE = np.dtype([('y', np.uint64), ('uv', np.uint64), ('h', np.int32), ('w', np.int32), ('pitch_y', np.int32), ('pitch_uv', np.int32)], align=True)
+assert _NV12_IMAGE.itemsize == C.sizeof(L.Nv12ImageDesc) and all(_NV12_IMAGE.fields[n][1] == getattr(L.Nv12ImageDesc, n).offset for n in _NV12_IMAGE.names)
+_NV12_DESC = np.dtype([(n, _DESC.fields[n][0]) for n in _DESC.names] + [('uv', np.uint64), ('uv_pitch', np.int32)], align=True)
+assert _NV12_DESC.itemsize == C.sizeof(L.Nv12FrameDesc) and all(_NV12_DESC.fields[n][1] == getattr(L.Nv12FrameDesc, n).offset for n in _NV12_DESC.names)
+_NV12_DESC_WORDS = _NV12_DESC.itemsize // 4
 _CROP_WORD = _DESC.fields['crop_y'][1] // 4         # crop_y, crop_x, crop_h, crop_w are consecutive int32 words of a descriptor
+
+
+# YUV -> RGB coefficients at 20 fractional bits (include/mcgaze_hip.h, mcg_yuv_coef).  bt601: OpenCV's published limited-range constants
+# (its ITUR_BT_601_* set, 1.164 / 2.018 / -0.391 / -0.813 / 1.596 scaled by 2^20), restated, not linked: parity with cv2's COLOR_YUV2BGR_NV12
+# is not pinned on any machine this was built on.  bt709: limited range, round(c * 2**20) of the matrix with Kr = 0.2126, Kb = 0.0722,
+# luma scale 255/219 and chroma scale 255/224, worked out once in double: cy = 255/219, cub = 2 (1 - Kb) 255/224,
+# cug = -(Kb / Kg) 2 (1 - Kb) 255/224, cvg = -(Kr / Kg) 2 (1 - Kr) 255/224, cvr = 2 (1 - Kr) 255/224 with Kg = 1 - Kr - Kb.
+YUV_COEF = {
+    'bt601': dict(y_off=16, cy=1220542, cub=2116026, cug=-409993, cvg=-852492, cvr=1673527),
+    'bt709': dict(y_off=16, cy=1220945, cub=2215014, cug=-223607, cvg=-558796, cvr=1879825),
+}
+
+
+def _yuv_coef(matrix):
+    if matrix not in YUV_COEF:
+        raise ValueError(f'matrix must be one of {sorted(YUV_COEF)}, got {matrix!r}')
+    return YUV_COEF[matrix]
+
+
+def _nv12_planes(k, im, dev=None):
+    """One NV12 surface as head_crops takes it -> (y [H,W], uv [H/2,W] as a 2-d view, on_device): a (y, uv) pair with uv [H/2,W/2,2] or
+    [H/2,W], or a single [3H/2, W] surface (Y rows, then the UV rows).  TypeError for a wrong dtype, rank or device, ValueError for odd sizes
+    or a UV plane that does not belong to the Y plane."""
+    if isinstance(im, (tuple, list)):
+        if len(im) != 2:
+            raise TypeError(f'frame {k}: an NV12 frame is a (y, uv) pair or one [3H/2, W] surface, got a sequence of {len(im)}')
+        y, uv = im
+    else:
+        y, uv = im, None
+    on_device = isinstance(y, torch.Tensor)
+    if uv is not None and isinstance(uv, torch.Tensor) != on_device:
+        raise TypeError(f'frame {k}: the Y and UV planes must both be numpy arrays or both be device tensors')
+    if not on_device:
+        y = np.asarray(y)
+        uv = None if uv is None else np.asarray(uv)
+    u8 = torch.uint8 if on_device else np.uint8
+    for name, t in (('Y', y), ('UV', uv)):
+        if t is None:
+            continue
+        if t.dtype != u8 or t.ndim not in ((2,) if name == 'Y' else (2, 3)) or (t.numel() if on_device else t.size) == 0:
+            raise TypeError(f'frame {k}: the {name} plane must be a non-empty uint8 array of rank {"2" if name == "Y" else "2 or 3"}, got {t.dtype} {tuple(t.shape)}')
+        if on_device and not (t.is_cuda and t.device == dev):
+            raise TypeError(f'frame {k}: device planes must be uint8 tensors on {dev}, got one on {t.device}')
+    if uv is None:                                                # one surface: 3H/2 rows
+        rows, w = y.shape
+        if rows % 3 or w % 2:
+            raise ValueError(f'frame {k}: a {rows} x {w} surface is not [3H/2, W] with H and W even')
+        h = rows // 3 * 2
+        y, uv = y[:h], y[h:]
+    h, w = y.shape
+    if h % 2 or w % 2:
+        raise ValueError(f'frame {k}: NV12 frames have even sizes, got {h} x {w}')
+    if tuple(uv.shape) not in ((h // 2, w // 2, 2), (h // 2, w)):
+        raise ValueError(f'frame {k}: the UV plane of a {h} x {w} frame is [{h // 2}, {w // 2}, 2] or [{h // 2}, {w}], got {tuple(uv.shape)}')
+    if on_device:
+        # rows may lie further apart than w bytes (a decoder's pitch); inside a row the bytes are packed
+        packed = y.stride(1) == 1 and (uv.stride(1) == 1 if uv.ndim == 2 else (uv.stride(2) == 1 and (uv.shape[1] == 1 or uv.stride(1) == 2)))
+        if not (packed and y.stride(0) >= w and (uv.shape[0] == 1 or uv.stride(0) >= w)):
+            raise TypeError(f'frame {k}: device planes must have packed rows at least {w} bytes apart, got strides {tuple(y.stride())} and {tuple(uv.stride())}')
+        if uv.ndim == 3:
+            uv = uv.as_strided((h // 2, w), (uv.stride(0), 1))
+    else:
+        y, uv = np.ascontiguousarray(y), np.ascontiguousarray(uv).reshape(h // 2, w)
+    return y, uv, on_device
+
+
+def nv12_to_bgr(y, uv, matrix='bt601'):
+    """An NV12 frame -> HxWx3 uint8 BGR on the host, in the arithmetic the pixel kernel applies per tap (csrc/preprocess.hip, Nv12Source):
+    y [H,W] uint8, uv [H/2,W/2,2] or [H/2,W] uint8 interleaved (U, V), H and W even; matrix: a key of YUV_COEF.  Chroma is the nearest
+    sample, uv[y >> 1][x >> 1], and with u = U - 128, v = V - 128 in 32-bit integers (>> is an arithmetic shift):
+
+        yy = max(0, Y - y_off) * cy
+        R = sat8((yy + cvr * v + (1 << 19)) >> 20);  G = sat8((yy + cvg * v + cug * u + (1 << 19)) >> 20);  B = sat8((yy + cub * u + (1 << 19)) >> 20)
+
+    head_crops(pixel_format='nv12') on the planes equals head_crops on this frame bit for bit."""
+    k = _yuv_coef(matrix)
+    y, uv, _ = _nv12_planes(0, (np.asarray(y), np.asarray(uv)))
+    h, w = y.shape
+    c = uv.reshape(h // 2, w // 2, 2).astype(np.int32) - 128
+    u, v = (np.repeat(np.repeat(c[..., j], 2, axis=0), 2, axis=1) for j in (0, 1))
+    yy = np.maximum(0, y.astype(np.int32) - k['y_off']) * np.int32(k['cy']) + np.int32(1 << 19)
+    sat8 = lambda t: np.clip(t >> 20, 0, 255).astype(np.uint8)
+    return np.stack([sat8(yy + k['cub'] * u), sat8(yy + k['cvg'] * v + k['cug'] * u), sat8(yy + k['cvr'] * v)], axis=-1)
 
 
 class _NoDraw:
@@ -771,7 +862,7 @@ class DevicePipeline:
         p = self.plan((scale_h, scale_w, 3), _NO_DRAW)            # the LARGEST resized crop through the planners: its pad_shape holds every crop
         return int(scale_w), int(scale_h), int(p.pad_shape[0]), int(p.pad_shape[1]), p.img_norm_cfg
 
-    def head_crops(self, images, boxes, image_of, expand=0.8, device='cuda:0', stream=None, rgb=False):
+    def head_crops(self, images, boxes, image_of, expand=0.8, device='cuda:0', stream=None, rgb=False, pixel_format='bgr', matrix='bt601'):
         """Video frames and head boxes -> the model's input, one head crop per box (MCGaze_demo/demo.ipynb, cell 4, then this chain): ONE
         plan launch chooses every window on the device, the pixel kernel reads it (mcg_preprocess_head_crops).
 
@@ -786,9 +877,25 @@ class DevicePipeline:
         -> (img [n,3,Hp,Wp] f32, img_hw [n,2] int32, scale_factor [n,4] f32, crop [n,4] int32 = y0, x0, h, w, flags [n] int32), all on
         the device.  (Hp, Wp) is img_scale rounded up by Pad -- for every call, where mmcv's collate pads a chunk to ITS largest crop (the
         same unless the frame border clips every crop of the chunk on one axis); img_hw is each crop's true resized size, the reference's
-        img_shape, and the decoder clips by it."""
+        img_shape, and the decoder clips by it.
+
+        pixel_format='nv12': the frames are a video decoder's NV12 surfaces and are read as they are (mcg_preprocess_head_crops_nv12 converts
+        each tap it samples; no BGR frame is ever written).  Each image is a (y [H,W], uv [H/2,W/2,2] or [H/2,W]) pair or ONE [3H/2, W] surface
+        (the Y rows, then the UV rows), uint8, H and W even: numpy arrays are staged in the same single copy, CUDA tensors are read in place
+        (row strides are the pitches, at least W; bytes inside a row are packed).  matrix: 'bt601' (cv2's COLOR_YUV2BGR_NV12 constants) or
+        'bt709' (what HD decoders emit), both limited range -- ``YUV_COEF``.  rgb= is ignored: the output order is the config's to_rgb.  TypeError
+        / ValueError for a wrong dtype, rank, device or plane shape and for odd sizes, before anything is launched.  The result equals
+        head_crops on ``nv12_to_bgr`` of the same planes bit for bit; tables, flags and the no-host-touch property are as for BGR."""
         lib = L.load()
+        if pixel_format not in ('bgr', 'nv12'):
+            raise ValueError(f"pixel_format must be 'bgr' or 'nv12', got {pixel_format!r}")
+        coef = _yuv_coef(matrix)
+        nv12 = pixel_format == 'nv12'
         dev = torch.device(device)
+        if nv12:                                                  # the surfaces are checked whatever the device: a bad one is the caller's first error
+            if dev.type == 'cuda' and dev.index is None:
+                dev = torch.device('cuda', torch.cuda.current_device())
+            planes = [_nv12_planes(k, im, dev) for k, im in enumerate(images)]
         if dev.type != 'cuda':
             raise L.McgError('DevicePipeline runs its pixel work on the GPU (mcg_preprocess_head_crops); there is no CPU path')
         if dev.index is None:
@@ -797,10 +904,18 @@ class DevicePipeline:
         if not len(images):
             raise ValueError('head_crops: no frames')
         # frame table: host frames get their address once they are staged
-        table = np.zeros(len(images), dtype=_IMAGE)
-        host_at = {}                                              # index -> array to stage
+        table = np.zeros(len(images), dtype=_NV12_IMAGE if nv12 else _IMAGE)
+        host_at = {}                                              # index -> arrays to stage, one behind the other
         for k, im in enumerate(images):
-            if isinstance(im, torch.Tensor):
+            if nv12:
+                y, uv, there = planes[k]
+                h, w = y.shape
+                if there:
+                    table[k] = (y.data_ptr(), uv.data_ptr(), h, w, y.stride(0), uv.stride(0) if h > 2 else w)
+                else:
+                    host_at[k] = (y, uv)
+                    table[k] = (0, 0, h, w, w, w)
+            elif isinstance(im, torch.Tensor):
                 if not (im.is_cuda and im.device == dev and im.dtype == torch.uint8 and im.ndim == 3 and im.shape[2] == 3 and im.numel() > 0
                         and im.stride(2) == 1 and im.stride(1) == 3 and (im.shape[0] == 1 or im.stride(0) >= 3 * im.shape[1])):
                     raise TypeError(f'frame {k}: device frames must be HxWx3 uint8 tensors on {dev} with packed pixels (stride (pitch, 3, 1)), '
@@ -810,7 +925,7 @@ class DevicePipeline:
                 a = np.ascontiguousarray(im)
                 if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3 or a.size == 0:
                     raise TypeError(f'frame {k}: frames must be HxWx3 uint8 arrays, got {a.dtype} {a.shape}')
-                host_at[k] = a
+                host_at[k] = (a,)
                 table[k] = (0, a.shape[0], a.shape[1], 3 * a.shape[1])
         on_device = [isinstance(t, torch.Tensor) and t.is_cuda for t in (boxes, image_of)]
         if not on_device[0]:
@@ -844,18 +959,18 @@ class DevicePipeline:
                     z = lambda *shape, dtype=torch.int32: torch.zeros(*shape, dtype=dtype, device=dev)
                     return z(0, 3, pad_h, pad_w, dtype=torch.float32), z(0, 2), z(0, 4, dtype=torch.float32), z(0, 4), z(0)
                 # everything that comes from the host travels in ONE pinned staging buffer and one copy: pixels, frame table, host tables
-                parts = [(k, a.reshape(-1)) for k, a in host_at.items()]
+                parts = [(k, f, a.reshape(-1)) for k, arrays in host_at.items() for f, a in zip(('y', 'uv') if nv12 else ('src',), arrays)]
                 tables = [t.view(np.uint8).reshape(-1) for t, d in zip((boxes, image_of), on_device) if not d]
                 if parts or tables:
-                    sizes = [(a.size + 255) // 256 * 256 for _, a in parts] + [(table.nbytes + 255) // 256 * 256] + [(t.size + 255) // 256 * 256 for t in tables]
+                    sizes = [(a.size + 255) // 256 * 256 for _, _, a in parts] + [(table.nbytes + 255) // 256 * 256] + [(t.size + 255) // 256 * 256 for t in tables]
                     offs = np.cumsum([0] + sizes)
                     total = int(offs[-1])
                     st, cs = self._staging(total, dev, main)
                     host, raw = st['pin'], st['dev']
                     host_np = host.numpy()
-                    for (k, a), o in zip(parts, offs):
+                    for (k, f, a), o in zip(parts, offs):
                         host_np[int(o):int(o) + a.size] = a
-                        table['src'][k] = raw.data_ptr() + int(o)
+                        table[f][k] = raw.data_ptr() + int(o)
                     at = [raw.data_ptr() + int(o) for o in offs[len(parts):-1]]                  # frame table, then the host tables
                     for t, o in zip([table.view(np.uint8).reshape(-1)] + tables, offs[len(parts):-1]):
                         host_np[int(o):int(o) + t.size] = t
@@ -872,7 +987,7 @@ class DevicePipeline:
                 else:
                     # nothing comes from the host but the frame table, and that only the first time these frames are seen
                     st = None
-                    key = (dev.index, table.tobytes())
+                    key = (dev.index, table.tobytes()) + (('nv12',) if nv12 else ())
                     tdev = self._image_tables.get(key)
                     if tdev is None:
                         tdev = self._image_tables[key] = torch.from_numpy(table.view(np.uint8).reshape(-1).copy()).to(dev)
@@ -882,17 +997,18 @@ class DevicePipeline:
                         self._image_tables.move_to_end(key)
                     images_ptr, boxes_ptr, image_of_ptr = tdev.data_ptr(), boxes.data_ptr(), image_of.data_ptr()
                 img = torch.empty(n, 3, pad_h, pad_w, dtype=torch.float32, device=dev)
-                desc = torch.empty(n, _DESC_WORDS, dtype=torch.int32, device=dev)
+                desc = torch.empty(n, _NV12_DESC_WORDS if nv12 else _DESC_WORDS, dtype=torch.int32, device=dev)
                 img_hw = torch.empty(n, 2, dtype=torch.int32, device=dev)
                 scale_factor = torch.empty(n, 4, dtype=torch.float32, device=dev)
                 flags = torch.empty(n, dtype=torch.int32, device=dev)
                 mean = (C.c_float * 3)(*[float(v) for v in norm['mean']])
                 stdinv = (C.c_float * 3)(*[float(np.float32(1.0 / np.float64(v))) for v in norm['std']])
-                swap = int(bool(norm['to_rgb']) != bool(rgb))
+                swap = int(bool(norm['to_rgb']) != (bool(rgb) and not nv12))                     # converted NV12 taps are BGR
                 vp = C.c_void_p
-                L.check(lib.mcg_preprocess_head_crops(vp(main.cuda_stream), vp(images_ptr), len(images), vp(boxes_ptr), vp(image_of_ptr), n, float(expand),
-                                                      scale_w, scale_h, vp(desc.data_ptr()), vp(img_hw.data_ptr()), vp(scale_factor.data_ptr()),
-                                                      vp(flags.data_ptr()), vp(img.data_ptr()), pad_h, pad_w, mean, stdinv, swap), 'mcg_preprocess_head_crops')
+                entry, more = (lib.mcg_preprocess_head_crops_nv12, (C.byref(L.YuvCoef(**coef)),)) if nv12 else (lib.mcg_preprocess_head_crops, ())
+                L.check(entry(vp(main.cuda_stream), vp(images_ptr), len(images), vp(boxes_ptr), vp(image_of_ptr), n, float(expand),
+                              scale_w, scale_h, vp(desc.data_ptr()), vp(img_hw.data_ptr()), vp(scale_factor.data_ptr()),
+                              vp(flags.data_ptr()), vp(img.data_ptr()), pad_h, pad_w, mean, stdinv, swap, *more), entry.__name__)
                 if st is not None:
                     st['read'] = torch.cuda.Event()
                     st['read'].record(main)

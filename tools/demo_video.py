@@ -3,7 +3,7 @@
 and the head detector's label files in, per-person per-frame gaze out.
 
 usage: demo_video.py FRAMES_DIR LABELS_DIR CONFIG CHECKPOINT --out gaze.json [--precision f16x3] [--device cuda:0] [--max-len 100]
-                     [--batch-frames 448] [--head-class 1] [--ext jpg] [--smooth ALPHA]
+                     [--batch-frames 448] [--head-class 1] [--ext jpg] [--smooth ALPHA] [--nv12 WxH FILE] [--matrix bt601]
 
 FRAMES_DIR holds 0.<ext>, 1.<ext>, ... (the demo's `frames/`), LABELS_DIR holds 0.txt, 1.txt, ... with lines `class x1 y1 x2 y2` in pixels
 (the demo's `result/labels/`); a frame without a label file shows no head.  CONFIG is the L2CS config, whose test pipeline the demo runs
@@ -11,11 +11,16 @@ on every head crop.  The result file holds one entry per (segment, person) in th
 the same number of heads, people are numbered left to right: `frame_id`, `head_box`, `crop` (y0, x0, h, w of the window cut from the
 frame), `gaze` (the fused gaze the notebook draws), `arrow` ((cx, cy) and the tip of the arrow of cell 5), and the per-clue boxes (in
 pixels of the head window, rescale=True), scores and gazes of harness.run_tracks (`det`, `others`).  --smooth ALPHA (the reference's metric
-uses 0.6, tools/calculate_mae_gaze360.py:16-29) adds `gaze_smooth`, the fused gaze filtered over each track, and draws `arrow` from it."""
+uses 0.6, tools/calculate_mae_gaze360.py:16-29) adds `gaze_smooth`, the fused gaze filtered over each track, and draws `arrow` from it.
+--nv12 WxH FILE: the frames come from a raw NV12 video instead (`ffmpeg -i in.mp4 -pix_fmt nv12 -f rawvideo FILE`: per frame H rows of Y, then
+H/2 rows of interleaved U, V, W bytes each), read frame by frame with numpy and handed to the device as they are; FRAMES_DIR is then `-`.
+--matrix names the YUV -> RGB coefficients, bt601 or bt709 (limited range; HD video is usually bt709).  The records are the same."""
 import argparse
 import json
 import os
 import sys
+
+import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
@@ -36,6 +41,35 @@ class Frames:
         return LoadImageFromFile.load(os.path.join(self.root, f'{t}.{self.ext}'), rgb=True)
 
 
+class Nv12File:
+    """A raw NV12 video (`-pix_fmt nv12 -f rawvideo`): frame t is the (y [H,W], uv [H/2,W]) pair of views of its 3 H W / 2 bytes, read when a
+    group of crops asks for it.  Bytes behind the last whole frame are ignored."""
+
+    def __init__(self, path, w, h):
+        if w <= 0 or h <= 0 or w % 2 or h % 2:
+            raise ValueError(f'NV12 frames have even, positive sizes, got {w}x{h}')
+        self.path, self.w, self.h = path, w, h
+        self.frame_bytes = w * h * 3 // 2
+        self.n = os.path.getsize(path) // self.frame_bytes
+
+    def __len__(self):
+        return self.n
+
+    def __getitem__(self, t):
+        if not 0 <= t < self.n:
+            raise IndexError(t)
+        s = np.fromfile(self.path, dtype=np.uint8, count=self.frame_bytes, offset=t * self.frame_bytes).reshape(self.h * 3 // 2, self.w)
+        return s[:self.h], s[self.h:]
+
+
+def parse_size(text):
+    """'1920x1080' -> (1920, 1080)"""
+    w, _, h = text.lower().partition('x')
+    if not (w.isdigit() and h.isdigit()):
+        raise ValueError(f'expected WxH, got {text!r}')
+    return int(w), int(h)
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
     ap.add_argument('frames_dir')
@@ -50,17 +84,24 @@ def main(argv=None):
     ap.add_argument('--head-class', type=int, default=1)
     ap.add_argument('--ext', default='jpg')
     ap.add_argument('--smooth', type=float, default=None, metavar='ALPHA', help='temporal filter of the reference\'s metric, alpha in (0, 1]')
+    ap.add_argument('--nv12', nargs=2, default=None, metavar=('WxH', 'FILE'), help='read the frames from a raw NV12 video (FRAMES_DIR is then -)')
+    ap.add_argument('--matrix', default='bt601', choices=['bt601', 'bt709'], help='YUV -> RGB coefficients of --nv12')
     a = ap.parse_args(argv)
-    n = len([f for f in os.listdir(a.frames_dir) if f.endswith('.' + a.ext)])      # the notebook: vid_len = len(os.listdir(frames))
-    missing = [t for t in range(n) if not os.path.exists(os.path.join(a.frames_dir, f'{t}.{a.ext}'))]
-    if missing:
-        raise SystemExit(f'{a.frames_dir}: {n} .{a.ext} files but no {missing[0]}.{a.ext} -- frames are numbered from 0 without gaps')
+    if a.nv12 is not None:
+        frames = Nv12File(a.nv12[1], *parse_size(a.nv12[0]))
+        n = len(frames)
+    else:
+        n = len([f for f in os.listdir(a.frames_dir) if f.endswith('.' + a.ext)])      # the notebook: vid_len = len(os.listdir(frames))
+        missing = [t for t in range(n) if not os.path.exists(os.path.join(a.frames_dir, f'{t}.{a.ext}'))]
+        if missing:
+            raise SystemExit(f'{a.frames_dir}: {n} .{a.ext} files but no {missing[0]}.{a.ext} -- frames are numbered from 0 without gaps')
+        frames = Frames(a.frames_dir, n, a.ext)
     labels = [os.path.join(a.labels_dir, f'{t}.txt') for t in range(n)]
     per_frame = [harness.read_head_labels(p, a.head_class) if os.path.exists(p) else [] for p in labels]
     model = init_detector(a.config, a.checkpoint, device=a.device, precision=a.precision)
     pipe = DevicePipeline(model.cfg.data.test.pipeline)
-    res = harness.run_head_video(model.engine(), pipe, Frames(a.frames_dir, n, a.ext), per_frame, max_len=a.max_len, batch_frames=a.batch_frames, rgb=True,
-                                 smooth=a.smooth)
+    res = harness.run_head_video(model.engine(), pipe, frames, per_frame, max_len=a.max_len, batch_frames=a.batch_frames, rgb=True,
+                                 smooth=a.smooth, pixel_format='bgr' if a.nv12 is None else 'nv12', matrix=a.matrix)
     out = [dict(segment=r['id'][0], person=r['id'][1], frame_id=r['frame_id'], head_box=r['head_box'].tolist(), crop=r['crop'].tolist(),
                 gaze=r['fused'].tolist(), arrow=r['arrow'].tolist(), det=r['det'].tolist(), others=r['others'].tolist(),
                 **({} if a.smooth is None else dict(gaze_smooth=r['fused_smooth'].tolist()))) for r in res]
