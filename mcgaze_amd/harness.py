@@ -214,6 +214,7 @@ def result_file_name(config_path, json_path):
 
 
 FUSED_ATTN_MAX_T = 10     # longest clip the fused attention block takes (3 T <= 32 token rows: one MFMA tile, csrc/attn_block.hpp)
+ROW, SMOOTH_ROW = 27, 12  # columns of a result row (pack_rows): det 3x5 | fused 3 | others 3x3, and of what smooth= adds: fused_smooth 3 | others_smooth 3x3
 
 
 def bucket_key(H, W, T, mixed):
@@ -228,6 +229,23 @@ def clip_outputs(out, scale=None):
     (multiclue_gaze_roi_head.py:360-363)."""
     boxes = out['boxes'] if scale is None else out['boxes'] / scale
     return torch.cat([boxes, out['scores'][..., None]], dim=-1), out['gaze'][0], out['gaze'][1:].permute(1, 0, 2)
+
+
+def pack_rows(det, fused, others, fused_smooth=None, others_smooth=None):
+    """clip_outputs' / merge_video's (det [k,3,5], fused [k,3], others [k,3,3])[, the smoothed fused and others] -> ONE [k,27] or [k,39] array
+    of result rows: numpy arrays or torch tensors alike, one concatenation."""
+    parts = [det, fused, others] + ([] if fused_smooth is None else [fused_smooth, others_smooth])
+    parts = [p.reshape(det.shape[0], w) for p, w in zip(parts, (15, 3, 9, 3, 9))]
+    return torch.cat(parts, dim=1) if isinstance(det, torch.Tensor) else np.concatenate(parts, axis=1)
+
+
+def split_rows(r):
+    """pack_rows' inverse: [k,27] -> (det, fused, others), [k,39] -> the five parts, all views of r.  ValueError on any other width."""
+    if r.ndim != 2 or r.shape[1] not in (ROW, ROW + SMOOTH_ROW):
+        raise ValueError(f'split_rows: result rows have {ROW} or {ROW + SMOOTH_ROW} columns (got shape {tuple(r.shape)})')
+    k = r.shape[0]
+    out = (r[:, :15].reshape(k, 3, 5), r[:, 15:18], r[:, 18:27].reshape(k, 3, 3))
+    return out if r.shape[1] == ROW else out + (r[:, 27:30], r[:, 30:39].reshape(k, 3, 3))
 
 
 def _run_windows(engine, ids, plans, get_window, batch_clips, person_threshold, reuse_frames=False, mixed_lengths=False, merge='host',
@@ -277,14 +295,13 @@ def _run_windows(engine, ids, plans, get_window, batch_clips, person_threshold, 
             items, buf, ev = inflight.popleft()
             if ev is not None:
                 ev.synchronize()
-            res = buf[:sum(T for _, _, T in items)].numpy().copy()  # [frames, 27] = det 3x5 | fused 3 | others 3x3; copied: the pinned buffer is reused
+            res = buf[:sum(T for _, _, T in items)].numpy().copy()  # [frames, 27] result rows; copied: the pinned buffer is reused
             if ev is not None:
                 spare.append(buf)
-            row = 0
+            parts, row = split_rows(res), 0
             for vi, wi, T in items:
-                r = res[row:row + T]
+                outputs[vi][wi] = tuple(p[row:row + T] for p in parts)
                 row += T
-                outputs[vi][wi] = (r[:, :15].reshape(T, 3, 5), r[:, 15:18], r[:, 18:].reshape(T, 3, 3))
                 pending[vi] -= 1
                 if pending[vi] == 0:                   # all windows of the video are back: merge, record, release
                     whole = merge_video(plans[vi], outputs[vi], person_threshold)
@@ -342,10 +359,8 @@ def _run_windows(engine, ids, plans, get_window, batch_clips, person_threshold, 
                 vi = it[0]
                 pending[vi] -= 1
                 if pending[vi] == 0:                   # the video's last window is queued: its frames leave the store in one copy
-                    if smooth is None:
-                        packed, _ = merger.pop_rows([(vi, plans[vi][-1][1])])
-                    else:                              # the whole video at once: no frame waits for its successor
-                        packed, smoothed, _ = merger.pop_smooth_rows([(vi, plans[vi][-1][1])], ended=(vi,))
+                    packed, smoothed, _ = merger.pop_rows([(vi, plans[vi][-1][1])], ended=(vi,))   # ended: the whole video at once, no frame waits for its successor
+                    if smoothed is not None:
                         packed = torch.cat([packed, smoothed], dim=1)
                     merger.forget(vi)
                     buf = torch.empty(packed.shape[0], packed.shape[1], dtype=torch.float32).pin_memory()
@@ -354,8 +369,7 @@ def _run_windows(engine, ids, plans, get_window, batch_clips, person_threshold, 
                     ev.record(torch.cuda.current_stream(dev))
                     merged.append((vi, buf, ev))
             return
-        det, fused, others = clip_outputs(out, scale)
-        packed = torch.cat([det.reshape(n, 15), fused.reshape(n, 3), others.reshape(n, 9)], dim=1).to(torch.float32)   # ONE copy to the host
+        packed = pack_rows(*clip_outputs(out, scale)).to(torch.float32)   # ONE copy to the host
         who = [(it[0], it[1], T) for it, T in zip(items, Ts)]
         if dev.type != 'cuda':
             inflight.append((who, packed, None))
@@ -364,7 +378,7 @@ def _run_windows(engine, ids, plans, get_window, batch_clips, person_threshold, 
         if buf is not None:
             spare.remove(buf)
         else:
-            buf = torch.empty(max(n, batch_clips * max(Ts)), 27, dtype=torch.float32).pin_memory()
+            buf = torch.empty(max(n, batch_clips * max(Ts)), ROW, dtype=torch.float32).pin_memory()
         buf[:n].copy_(packed, non_blocking=True)
         ev = torch.cuda.Event()
         ev.record(torch.cuda.current_stream(dev))
@@ -383,9 +397,8 @@ def _run_windows(engine, ids, plans, get_window, batch_clips, person_threshold, 
     collect(0)
     for vi, buf, ev in merged:
         ev.synchronize()
-        r = buf.numpy()
-        records[vi] = video_record(ids[vi], r[:, :15].reshape(-1, 3, 5), r[:, 15:18], r[:, 18:27].reshape(-1, 3, 3),
-                                   None if smooth is None else (r[:, 27:30], r[:, 30:39].reshape(-1, 3, 3)))
+        r = split_rows(buf.numpy())
+        records[vi] = video_record(ids[vi], *r[:3], r[3:] or None)
     last_run_stats['trunk_frames'] = trunk[0]
     return records
 

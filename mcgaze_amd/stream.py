@@ -16,17 +16,22 @@ mcg_decoder_forward_indexed, the gather happens inside the RoIAlign read).
     (tools/calculate_mae_gaze360.py:16-29) as a stream goes -- a frame is handed out one frame late, once its successor is final -- on the
     host, and on the device as one mcg_smooth_gaze launch per pop over all streams (``smooth=`` of GazeStream / GazeStreamPool).
   * ``GazeStream``: push frames as they arrive, get back the per-frame results that became final; ``finish()`` returns the rest.
+    It owns a ``PyramidRing`` (the trunk writes in place, no scatter launch) and one ``_StreamState``.
   * ``PyramidStore`` / ``GazeStreamPool``: MANY streams at once (S cameras, or the reference demo's one clip per tracked person,
     MCGaze_demo/demo.ipynb cell 4, each the sliding-window loop of tools/test_gaze360_gaze.py:72-111): one store shared by all streams,
     rows handed out from a free list; per tick ONE trunk call over every stream's new frames, scattered into whichever rows are free
     (``HipEngine.backbone_fpn_rows`` -> mcg_pyramid_scatter_rows), and ONE indexed, ragged decoder call over every stream's newly certain
-    windows.  Per stream the same planner, merger and bits as a lone ``GazeStream``.
+    windows.  Per stream the same bits as a lone ``GazeStream``, by the same code: everything above the two stores is stated once --
+    ``_StreamState`` (a stream's planner, host merger and filter, frames handed out; a pool stream adds its queue and rows),
+    ``_decode_windows`` (windows -> decoder calls -> merge; a lone stream is the one-stream case) and ``_stream_setup`` (the arguments both
+    take) -- and the result-row layout is harness.pack_rows / split_rows.
 """
 import numpy as np
 import torch
 
 from . import lib as L
-from .harness import _host, bucket_key, check_smooth, clip_outputs, merge_plan, merge_window, plan_windows, smooth_host, smooth_plan
+from .harness import (ROW, SMOOTH_ROW, _host, bucket_key, check_smooth, clip_outputs, merge_plan, merge_window, plan_windows, smooth_host, smooth_plan,
+                      split_rows)
 
 
 class WindowPlanner:
@@ -192,8 +197,7 @@ class DeviceMerger:
     then runs one frame behind what it returns without smoothing.  The row of the last frame handed out stays allocated, as the next
     frame's predecessor, until that frame has been handed out, the stream has ended, or ``forget``.  det / fused / others keep their bits."""
 
-    ROW = 27
-    SMOOTH_ROW = 12
+    ROW, SMOOTH_ROW = ROW, SMOOTH_ROW
 
     class _Stream:
         def __init__(self):
@@ -262,78 +266,50 @@ class DeviceMerger:
             st = self.streams[key]
             st.end = max(st.end, stop)
 
-    def pop_rows(self, items):
-        """items: [(key, upto)] -> (rows [K,27], [k per item]): the frames [handed out, min(upto, written)) of every item's stream, item after
-        item, gathered into ONE fresh device tensor by one index_select; their store rows are free for reuse."""
-        if self.smooth is not None:
-            raise L.McgError('DeviceMerger.pop_rows: a smoothing merger hands frames out one frame late: pop() or pop_smooth_rows()')
-        rows, counts = [], []
-        for key, upto in items:
-            st = self.streams.get(key)
-            k = 0 if st is None else max(0, min(int(upto), st.end) - st.base)
-            if k:
-                rows += [st.rows.pop(f) for f in range(st.base, st.base + k)]
-                st.base += k
-            counts.append(k)
-        if not rows:
-            return torch.empty(0, self.ROW, dtype=torch.float32, device=self.device), counts
-        packed = self.store.index_select(0, self._upload(np.asarray(rows, dtype=np.int64), self.device))
-        self._free.extend(reversed(rows))                  # later launches on this stream run after the gather
-        return packed, counts
-
-    def pop_smooth_rows(self, items, ended=()):
-        """pop_rows of a smoothing merger -> (rows [K,27], smoothed [K,12] = fused 3 | others 3x3, [k per item]): per item the frames
-        [handed out, min(upto, written)) but the last one -- all of them for a stream in ``ended`` -- gathered by one index_select and
-        filtered by one mcg_smooth_gaze launch.  Of the rows handed out, each stream's last stays allocated unless the stream has ended."""
-        if self.smooth is None:
-            raise L.McgError('DeviceMerger.pop_smooth_rows: this merger was made without smooth=')
+    def pop_rows(self, items, ended=()):
+        """items: [(key, upto)] -> (rows [K,27], smoothed [K,12] = fused 3 | others 3x3 or None without smooth=, [k per item]): the frames
+        [handed out, min(upto, written)) of every item's stream -- but the last one, if the merger smooths and the stream is not in ``ended`` --
+        item after item, gathered into ONE fresh device tensor by one index_select and filtered by one mcg_smooth_gaze launch.  Their store
+        rows are free for reuse, except (smoothing) each stream's last, which stays allocated unless the stream has ended."""
+        smoothing = self.smooth is not None
         rows, counts, plans, freed = [], [], [], []
         for key, upto in items:
             st = self.streams.get(key)
             over = key in ended
-            final = 0 if st is None else min(int(upto), st.end)
-            k = 0 if st is None else max(0, final - st.base - (0 if over else 1))
+            k = 0 if st is None else max(0, min(int(upto), st.end) - st.base - int(smoothing and not over))
             if k:
                 frames = range(st.base, st.base + k)
-                plans.append(smooth_plan(frames, st.rows.__getitem__, 0, st.end - 1 if over else None, self.store.shape[0]))
-                rows += plans[-1][:, 1].tolist()
+                if smoothing:
+                    plans.append(smooth_plan(frames, st.rows.__getitem__, 0, st.end - 1 if over else None, self.store.shape[0]))
+                rows += [st.rows[f] for f in frames] if smoothing else [st.rows.pop(f) for f in frames]   # plain: released as handed out
                 st.base += k
-            if st is not None:                             # the rows below the last frame handed out are no one's neighbour any more
+            if smoothing and st is not None:               # the rows below the last frame handed out are no one's neighbour any more
                 keep = st.base - (0 if over and st.base == st.end else 1)
                 freed += [st.rows.pop(f) for f in sorted(f for f in st.rows if f < keep)]
             counts.append(k)
-        if not rows:
-            self._free.extend(reversed(freed))
-            z = lambda w: torch.empty(0, w, dtype=torch.float32, device=self.device)
-            return z(self.ROW), z(self.SMOOTH_ROW), counts
-        packed = self.store.index_select(0, self._upload(np.asarray(rows, dtype=np.int64), self.device))
-        smoothed = torch.empty(len(rows), self.SMOOTH_ROW, dtype=torch.float32, device=self.device)
-        plan = self._upload(np.concatenate(plans), self.device)
-        L.check(self.lib.mcg_smooth_gaze(self._cur(self.device), self._ptr(self.store), self.store.shape[0], self._ptr(plan), len(rows),
-                                         self.smooth, self._ptr(smoothed)), 'mcg_smooth_gaze')
-        self._free.extend(reversed(freed))                 # later launches on this stream run after the gather and the filter
+        new = lambda n, w: torch.empty(n, w, dtype=torch.float32, device=self.device)
+        packed = self.store.index_select(0, self._upload(np.asarray(rows, dtype=np.int64), self.device)) if rows else new(0, ROW)
+        smoothed = new(len(rows), SMOOTH_ROW) if smoothing else None
+        if rows and smoothing:
+            plan = self._upload(np.concatenate(plans), self.device)
+            L.check(self.lib.mcg_smooth_gaze(self._cur(self.device), self._ptr(self.store), self.store.shape[0], self._ptr(plan), len(rows),
+                                             self.smooth, self._ptr(smoothed)), 'mcg_smooth_gaze')
+        self._free.extend(reversed(freed if smoothing else rows))   # later launches on this stream run after the gather and the filter
         return packed, smoothed, counts
 
     def pop(self, items, host=False, ended=()):
         """pop_rows as one (det [k,3,5], fused [k,3], others [k,3,3]) per item: views of the gathered tensor on the device, or (host=True)
-        numpy arrays after ONE copy to the host for all items together.  A smoothing merger (pop_smooth_rows; ``ended``: the keys whose
-        stream is over) adds fused_smooth [k,3] and others_smooth [k,3,3] to every item."""
-        if self.smooth is not None:
-            packed, smoothed, counts = self.pop_smooth_rows(items, ended)
-            if host:
-                packed = torch.cat([packed, smoothed], dim=1).cpu().numpy()
-                smoothed = packed[:, self.ROW:]
-        else:
-            packed, counts = self.pop_rows(items)
-            if host:
-                packed = packed.cpu().numpy()
+        numpy arrays after ONE copy to the host for all items together.  A smoothing merger (``ended``: the keys whose stream is over)
+        adds fused_smooth [k,3] and others_smooth [k,3,3] to every item."""
+        packed, smoothed, counts = self.pop_rows(items, ended)
+        if host:
+            packed, smoothed = (packed if smoothed is None else torch.cat([packed, smoothed], dim=1)).cpu().numpy(), None
+        parts = split_rows(packed)                         # split once, then cut per item: views either way
+        if smoothed is not None:
+            parts += (smoothed[:, :3], smoothed[:, 3:].reshape(smoothed.shape[0], 3, 3))
         res, at = [], 0
         for k in counts:
-            r = packed[at:at + k]
-            res.append((r[:, :15].reshape(k, 3, 5), r[:, 15:18], r[:, 18:27].reshape(k, 3, 3)))
-            if self.smooth is not None:
-                m = smoothed[at:at + k]
-                res[-1] += (m[:, :3], m[:, 3:].reshape(k, 3, 3))
+            res.append(tuple(p[at:at + k] for p in parts))
             at += k
         if host:
             res = [tuple(np.ascontiguousarray(x) for x in r) for r in res]
@@ -346,13 +322,77 @@ class DeviceMerger:
             self._free.extend(st.rows.values())
 
 
-def _check_switches(who, e, merge, results):
+def _stream_setup(who, engine_or_model, clip_len, stride, scale_factor, person_threshold, merge, results, smooth, merger_rows):
+    """The arguments GazeStream and GazeStreamPool share, checked -> (engine, smooth, scale [1,1,4] on its device or None, the DeviceMerger
+    of ``merger_rows`` rows or None with merge='host')."""
+    e = engine_or_model
+    if not hasattr(e, 'decode') and hasattr(e, 'engine'):
+        e = e.engine()
     if merge not in ('host', 'device') or results not in ('host', 'device'):
         raise ValueError(f"{who}: merge and results are 'host' or 'device' (got merge={merge!r}, results={results!r})")
     if results == 'device' and merge != 'device':
         raise ValueError(f"{who}: results='device' needs merge='device' (the host merge has its results on the host)")
     if merge == 'device' and torch.device(e.device).type != 'cuda':
         raise L.McgError(f"{who}: merge='device' needs an engine on a HIP device (got {e.device}); there is no CPU fallback path")
+    smooth = check_smooth(who, smooth)
+    WindowPlanner(clip_len, stride)                         # rejects a bad (clip_len, stride) here, not at the first frame
+    scale = None if scale_factor is None else torch.as_tensor(scale_factor, dtype=torch.float32, device=e.device).reshape(1, 1, 4)
+    dmerger = DeviceMerger(e.device, person_threshold, rows=merger_rows, smooth=smooth) if merge == 'device' else None
+    return e, smooth, scale, dmerger
+
+
+class _StreamState:
+    """One stream above its pyramid rows, for a lone GazeStream and a stream of a GazeStreamPool alike: its plan, its host merge and host
+    filter (idle with merge='device': the DeviceMerger holds the stream's frames under this object as key) and the frames handed out."""
+
+    def __init__(self, clip_len, stride, person_threshold, smooth=None):
+        self.planner = WindowPlanner(clip_len, stride)
+        self.merger = StreamMerger(person_threshold)
+        self.smoother = None if smooth is None else StreamSmoother(smooth)     # merge='host' only: the device merger filters its own rows
+        self.emitted = 0
+
+    def upto(self):
+        """Frames below this index can be handed out: the final ones, which is all of them once the stream has ended."""
+        return self.planner.final_upto
+
+    def add_host(self, window, det, fused, others):
+        self.merger.add(window, det, fused, others)
+
+    def emit(self, popped=None):
+        """popped: this stream's tuple of DeviceMerger.pop, or None: the host merger's frames below upto(), through the host filter
+        -> dict(first, det, fused, others[, fused_smooth, others_smooth])."""
+        if popped is None:
+            popped = self.merger.pop(self.upto())
+            if self.smoother is not None:
+                popped = self.smoother.push(*popped, ended=self.planner.finished)
+        res = dict(first=self.emitted, **dict(zip(('det', 'fused', 'others', 'fused_smooth', 'others_smooth'), popped)))
+        self.emitted += popped[0].shape[0]
+        return res
+
+
+def _decode_windows(engine, levels, hw, H, W, items, row_of, scale, max_windows, dmerger):
+    """items: [(state, window)], frame f of a state in row row_of(state, f) of ``levels`` -> one decoder call per longest-clip class
+    (harness.bucket_key) and per max_windows windows, merged per stream: ONE dmerger.add_call keyed by the state, or (dmerger None) one
+    blocking copy and add_host per window.  Windows of one length: clip_length is that length; of different lengths: the ragged call.
+    A lone GazeStream brings what ONE feed() or finish() of its planner handed out -- regular windows and the flush-to-end last one,
+    all clip_len long, or the single short window of a stream of at most clip_len frames -- so: one class, the scalar clip_length."""
+    classes = {}
+    for it in items:
+        classes.setdefault(bucket_key(H, W, it[1][1] - it[1][0], True), []).append(it)
+    for key in sorted(classes):
+        group = classes[key]
+        for i in range(0, len(group), max_windows or len(group)):
+            part = group[i:i + (max_windows or len(group))]
+            lengths = [w[1] - w[0] for _, w in part]
+            starts = np.concatenate([[0], np.cumsum(lengths)]).tolist()
+            table = [row_of(st, f) for st, w in part for f in range(w[0], w[1])]
+            out = engine.decode(levels, table, lengths[0] if len(set(lengths)) == 1 else lengths, img_hw=hw)
+            if dmerger is not None:
+                dmerger.add_call([(st, w, at) for (st, w), at in zip(part, starts)], out, scale)
+                continue
+            det, fused, others = (t.cpu().numpy() for t in clip_outputs(out, scale))
+            for (st, w), a, b in zip(part, starts, starts[1:]):    # a stream's windows are in plan order within its class
+                st.add_host(w, det[a:b], fused[a:b], others[a:b])
 
 
 class PyramidRing:
@@ -439,73 +479,45 @@ class GazeStream:
 
     def __init__(self, engine_or_model, H, W, clip_len=7, stride=4, capacity=None, scale_factor=None, person_threshold=0.5,
                  max_decode_windows=None, merge='host', results='host', smooth=None):
-        e = engine_or_model
-        if not hasattr(e, 'decode') and hasattr(e, 'engine'):
-            e = e.engine()
-        self.e = e
-        _check_switches('GazeStream', e, merge, results)
-        smooth = check_smooth('GazeStream', smooth)
+        self.e, smooth, self.scale, self.dmerger = _stream_setup('GazeStream', engine_or_model, clip_len, stride, scale_factor, person_threshold,
+                                                                 merge, results, smooth, 4 * clip_len)
         self.results = results
         self.T, self.s = clip_len, stride
-        self.planner = WindowPlanner(clip_len, stride)
-        self.merger = StreamMerger(person_threshold)
-        self.dmerger = DeviceMerger(e.device, person_threshold, rows=4 * clip_len, smooth=smooth) if merge == 'device' else None
-        self.smoother = StreamSmoother(smooth) if smooth is not None and merge == 'host' else None
+        self.state = _StreamState(clip_len, stride, person_threshold, smooth if merge == 'host' else None)
         capacity = clip_len + 64 if capacity is None else int(capacity)
         if capacity <= clip_len:
             raise L.McgError(f'GazeStream: capacity must exceed clip_len ({capacity} <= {clip_len})')
-        self.ring = PyramidRing(e, capacity, H, W)
-        self.scale = None if scale_factor is None else torch.as_tensor(scale_factor, dtype=torch.float32, device=e.device).reshape(1, 1, 4)
+        self.ring = PyramidRing(self.e, capacity, H, W)
         self.max_windows = max_decode_windows
-        self.emitted = 0
 
     def _decode(self, windows):
-        for i in range(0, len(windows), self.max_windows or max(1, len(windows))):
-            part = windows[i:i + (self.max_windows or len(windows))]
-            T = part[0][1] - part[0][0]
-            table = [self.ring.row(f) for a, b, _ in part for f in range(a, b)]
-            out = self.e.decode(self.ring.levels, table, T, img_hw=self.ring.hw)
-            if self.dmerger is not None:
-                self.dmerger.add_call([(0, w, k * T) for k, w in enumerate(part)], out, self.scale)
-                continue
-            det, fused, others = (t.cpu().numpy() for t in clip_outputs(out, self.scale))
-            for k, w in enumerate(part):
-                self.merger.add(w, det[k * T:(k + 1) * T], fused[k * T:(k + 1) * T], others[k * T:(k + 1) * T])
+        _decode_windows(self.e, self.ring.levels, self.ring.hw, self.ring.H, self.ring.W, [(self.state, w) for w in windows],
+                        lambda st, f: self.ring.row(f), self.scale, self.max_windows, self.dmerger)
 
-    def _emit(self, upto):
-        over = self.planner.finished
-        if self.dmerger is not None:
-            out = self.dmerger.pop([(0, upto)], host=self.results == 'host', ended=(0,) if over else ())[0]
-        else:
-            out = self.merger.pop(upto)
-            if self.smoother is not None:
-                out = self.smoother.push(*out, ended=over)
-        res = dict(first=self.emitted, **dict(zip(('det', 'fused', 'others', 'fused_smooth', 'others_smooth'), out)))
-        self.emitted += out[0].shape[0]
-        return res
+    def _emit(self):
+        st = self.state
+        if self.dmerger is None:
+            return st.emit()
+        return st.emit(self.dmerger.pop([(st, st.upto())], host=self.results == 'host', ended=(st,) if st.planner.finished else ())[0])
 
     def push(self, frames, img_hw=None):
         """frames [n,3,H,W] f32 (preprocessed like engine.forward's input); img_hw: [n,2] img_shape per frame or None.
         -> the frames that became final (possibly none)."""
-        n, i = frames.shape[0], 0
+        n, i, planner = frames.shape[0], 0, self.state.planner
         while i < n:
             m = min(n - i, self.ring.free())
             if m <= 0:
                 raise L.McgError('GazeStream: the pyramid ring has no free row (capacity too small)')
             self.ring.append(frames[i:i + m], None if img_hw is None else np.asarray(_host(img_hw)).reshape(n, 2)[i:i + m])
-            wins = self.planner.feed(m)
-            if wins:
-                self._decode(wins)
-            self.ring.release(self.planner.keep_from)
+            self._decode(planner.feed(m))
+            self.ring.release(planner.keep_from)
             i += m
-        return self._emit(self.planner.final_upto)
+        return self._emit()
 
     def finish(self):
         """End of the stream: the windows that depend on its length, and every frame not returned yet."""
-        wins = self.planner.finish()
-        if wins:
-            self._decode(wins)
-        return self._emit(self.planner.frames)
+        self._decode(self.state.planner.finish())
+        return self._emit()
 
 
 class PyramidStore:
@@ -560,19 +572,16 @@ class PyramidStore:
         return rows
 
 
-class _PoolStream:
-    """One stream of a GazeStreamPool: its plan, its merge, where its live frames lie in the store and the frames pushed but not run yet."""
+class _PoolStream(_StreamState):
+    """One stream of a GazeStreamPool: a _StreamState plus where its live frames lie in the store and the frames pushed but not run yet."""
 
     def __init__(self, clip_len, stride, person_threshold, smooth=None):
-        self.planner = WindowPlanner(clip_len, stride)
-        self.merger = StreamMerger(person_threshold)
-        self.smoother = None if smooth is None else StreamSmoother(smooth)     # merge='host' only: the device merger filters its own rows
+        super().__init__(clip_len, stride, person_threshold, smooth)
         self.row_of = {}         # frame index -> store row, for the frames a later window may still read
         self.queue = []          # (frames [n,3,H,W], img_hw [n,2] numpy or None) in push order
         self.queued = 0
         self.closed = False
         self.admitted = False    # holds a reservation of clip_len + stride rows
-        self.emitted = 0
         self.released = 0        # frames below this index gave their rows back
 
     def take(self, m):
@@ -627,21 +636,15 @@ class GazeStreamPool:
 
     def __init__(self, engine_or_model, H, W, clip_len=7, stride=4, rows=None, scale_factor=None, person_threshold=0.5, max_decode_windows=None,
                  max_trunk_frames=448, merge='host', results='host', smooth=None):
-        e = engine_or_model
-        if not hasattr(e, 'decode') and hasattr(e, 'engine'):
-            e = e.engine()
-        _check_switches('GazeStreamPool', e, merge, results)
-        self.smooth = check_smooth('GazeStreamPool', smooth)
+        self.e, self.smooth, self.scale, self.dmerger = _stream_setup('GazeStreamPool', engine_or_model, clip_len, stride, scale_factor,
+                                                                      person_threshold, merge, results, smooth, 16 * (clip_len + stride))
         self.results = results
-        self.dmerger = DeviceMerger(e.device, person_threshold, rows=16 * (clip_len + stride), smooth=self.smooth) if merge == 'device' else None
-        self.e, self.H, self.W = e, H, W
+        self.H, self.W = H, W
         self.T, self.s, self.thr = clip_len, stride, person_threshold
-        WindowPlanner(clip_len, stride)                     # rejects a bad (clip_len, stride) here, not at the first open()
         if max_trunk_frames < 1 or (max_decode_windows is not None and max_decode_windows < 1):
             raise L.McgError(f'GazeStreamPool: max_trunk_frames and max_decode_windows must be positive (got {max_trunk_frames}, {max_decode_windows})')
         self.max_trunk, self.max_windows = int(max_trunk_frames), max_decode_windows
-        self.store = PyramidStore(e, 64 * (clip_len + stride) + self.max_trunk if rows is None else int(rows), H, W)
-        self.scale = None if scale_factor is None else torch.as_tensor(scale_factor, dtype=torch.float32, device=e.device).reshape(1, 1, 4)
+        self.store = PyramidStore(self.e, 64 * (clip_len + stride) + self.max_trunk if rows is None else int(rows), H, W)
         self.streams = {}        # sid -> _PoolStream, in open order
         self.next_sid = 0
 
@@ -698,29 +701,6 @@ class GazeStreamPool:
             raise L.McgError(f'GazeStreamPool: a store of {self.store.rows} rows cannot hold one stream (clip_len + stride = {R} live frames)')
         return take
 
-    def _decode(self, items):
-        """items: [(stream, window)] -> one decoder call per longest-clip class and per max_decode_windows windows; merged per stream."""
-        classes = {}
-        for it in items:
-            classes.setdefault(bucket_key(self.H, self.W, it[1][1] - it[1][0], True), []).append(it)
-        for key in sorted(classes):
-            group = classes[key]
-            for i in range(0, len(group), self.max_windows or len(group)):
-                part = group[i:i + (self.max_windows or len(group))]
-                lengths = [w[1] - w[0] for _, w in part]
-                table = [st.row_of[f] for st, w in part for f in range(w[0], w[1])]
-                # windows of one length: the call a lone GazeStream makes; of different lengths: the ragged one
-                out = self.e.decode(self.store.levels, table, lengths[0] if len(set(lengths)) == 1 else lengths, img_hw=self.store.hw)
-                if self.dmerger is not None:
-                    starts = np.concatenate([[0], np.cumsum(lengths)]).tolist()
-                    self.dmerger.add_call([(st, w, at) for (st, w), at in zip(part, starts)], out, self.scale)
-                    continue
-                det, fused, others = (t.cpu().numpy() for t in clip_outputs(out, self.scale))
-                at = 0
-                for (st, w), T in zip(part, lengths):      # a stream's windows are in plan order within its class
-                    st.merger.add(w, det[at:at + T], fused[at:at + T], others[at:at + T])
-                    at += T
-
     def step(self):
         """Run what is queued -> {sid: dict(first, det, fused, others)} for every stream that had frames become final."""
         take = self._plan_step()
@@ -742,36 +722,31 @@ class GazeStreamPool:
             for i in range(0, len(rows), self.max_trunk):
                 self.store.write(x[i:i + self.max_trunk], rows[i:i + self.max_trunk], None if hw is None else hw[i:i + self.max_trunk])
         # 2. one decoder call over every window that became certain
-        items, touched, ended = [], [], []
+        items, touched = [], []
         for sid, st in self.streams.items():
             wins = st.planner.feed(take[sid]) if sid in take else []
             if st.closed and not st.queued:
                 wins = wins + st.planner.finish()
-                ended.append(sid)
             items += [(st, w) for w in wins]
             if sid in take or st.planner.finished:
-                touched.append(sid)
-        if items:
-            self._decode(items)
+                touched.append((sid, st))
+        _decode_windows(self.e, self.store.levels, self.store.hw, self.H, self.W, items, lambda st, f: st.row_of[f], self.scale,
+                        self.max_windows, self.dmerger)
         # 3. + 4. per stream: hand out the frames that are final, give back the rows no later window reads
         results = {}
+        popped = [None] * len(touched)
         if self.dmerger is not None:                       # one gather (and, results='host', one copy) for all streams together
-            popped = self.dmerger.pop([(self.streams[sid], self.streams[sid].planner.frames if self.streams[sid].planner.finished
-                                        else self.streams[sid].planner.final_upto) for sid in touched], host=self.results == 'host',
-                                      ended=[self.streams[sid] for sid in ended])
-        for i, sid in enumerate(touched):
-            st = self.streams[sid]
-            out = popped[i] if self.dmerger is not None else st.merger.pop(st.planner.frames if st.planner.finished else st.planner.final_upto)
-            if st.smoother is not None:
-                out = st.smoother.push(*out, ended=st.planner.finished)
-            if out[0].shape[0] or st.planner.finished:
-                results[sid] = dict(first=st.emitted, **dict(zip(('det', 'fused', 'others', 'fused_smooth', 'others_smooth'), out)))
-            st.emitted += out[0].shape[0]
+            popped = self.dmerger.pop([(st, st.upto()) for _, st in touched], host=self.results == 'host',
+                                      ended=[st for _, st in touched if st.planner.finished])
+        for (sid, st), out in zip(touched, popped):
+            res = st.emit(out)
+            if res['det'].shape[0] or st.planner.finished:
+                results[sid] = res
             keep = st.planner.keep_from
             self.store.free([st.row_of.pop(f) for f in range(st.released, keep)])
             st.released = max(st.released, keep)
-        for sid in ended:
-            if self.dmerger is not None:
-                self.dmerger.forget(self.streams[sid])
-            del self.streams[sid]
+            if st.planner.finished:                        # the stream is gone; its frames left the device merger in the pop above
+                if self.dmerger is not None:
+                    self.dmerger.forget(st)
+                del self.streams[sid]
         return results
