@@ -126,6 +126,15 @@ def wino_pack(w, g=2):
     return v.contiguous().reshape(-1)
 
 
+def pack_stem(w_oihw, bias, dtype, split=False):
+    """Folded stem conv [64][3][7][7] OIHW + bias [64] -> (the weight operand of mcg_stem_forward, f32 bias), host tensors:
+    [64][7][8][4] (kw and channel zero-padded: one kernel row is one 32-element tap) in ``dtype``, or, split=True (MCG_F16X3), that
+    tensor split-packed over its flattened K = 224 as fp16 [64][448].  mcg_stem_forward takes no descale: the matrix is not pre-scaled."""
+    stem = torch.zeros(64, 7, 8, 4)
+    stem[:, :, :7, :3] = w_oihw.permute(0, 2, 3, 1)
+    return (split_pack(stem.reshape(64, -1)) if split else stem.to(dtype)), bias.float()
+
+
 def _slab(w64, chain):
     """f32 [64 out][64 k] -> one 16 KiB weight slab of bneck_x3.hpp: fp16 [2 channel tiles][4 K-steps][high, low][64 lanes][8], lane l
     holding row 32 ct + (l & 31) and, for e < 8, column 16 s + 8 (l >> 5) + e (chain = False: the 3x3 conv, whose B operand comes
@@ -236,9 +245,8 @@ class PackedWeights:
         # ... and F(4,3) copies for the FPN output convs (maps whose width is a multiple of 4 and >= 16: P2 / P3 of a 224 x 224 input)
         wf3x3_g4 = (lambda w: self._dev(wino_pack(ohwi(w), g=4))) if split else None
         w, b = fold_bn(sd, 'backbone.conv1.weight', 'backbone.bn1')
-        stem = torch.zeros(64, 7, 8, 4)
-        stem[:, :, :7, :3] = w.permute(0, 2, 3, 1)
-        self.stem = dict(w=cmat(stem), bias=vec(b), cin=32, cout=64, k=7, stride=2, pad=3, wscale=0.0)   # mcg_stem_forward takes no descale: unscaled
+        ws, bs = pack_stem(w, b, dtype, split)
+        self.stem = dict(w=self._dev(ws), bias=self._dev(bs), cin=32, cout=64, k=7, stride=2, pad=3, wscale=0.0)   # mcg_stem_forward takes no descale: unscaled
         self.convs = []
         self.fused = []  # f16x3: fused bottleneck tails (bneck_stream), dicts of wstream / bias / conv2_index / cm / c / cn / nsrc
         folded = []      # (w OIHW f32, b f32) of every entry of self.convs, for the fused tails
