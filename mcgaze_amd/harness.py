@@ -434,6 +434,18 @@ def run_videos(engine, videos, clip_len=7, stride=4, batch_clips=64, scale_facto
                         mixed_lengths=mixed_lengths, merge=merge, smooth=smooth)
 
 
+def expected_frame_bytes(path):
+    """What a decode-ring slot will really hold for a run that starts with the image file ``path``: twice its decoded size (frames of a dataset
+    vary), from the file's header alone (no decode) -- the /dev/shm check of the decode ring (pipeline.FrameCache) prices a slot at that instead
+    of the 3 MiB worst case (a 360 x 360 frame is 390 KB).  None where the header cannot be read."""
+    try:
+        from PIL import Image
+        with Image.open(path) as im:
+            return 2 * im.size[0] * im.size[1] * 3
+    except (OSError, ValueError):
+        return None
+
+
 def run_annotation(engine, anno, root, pipeline, clip_len=7, stride=4, batch_clips=64, person_threshold=0.5, rng=None, workers=0, lookahead=None,
                    processes=False, video_rng=None, mixed_lengths=False):
     """tools/test_gaze360_gaze.py:57-269 from the annotation file down: for every ``anno['videos']`` entry (``id``,
@@ -462,14 +474,8 @@ def run_annotation(engine, anno, root, pipeline, clip_len=7, stride=4, batch_cli
     group = max(1, min(batch_clips, 32))                                    # windows staged per preprocessing call
     frame_bytes = None
     if workers > 0 and processes and videos and videos[0]['file_names']:
-        # what a ring slot will really hold: the run's first frame, from its header (no decode) -- the /dev/shm check of the decode ring prices
-        # a slot at that instead of the 3 MiB worst case (a 360 x 360 frame is 390 KB)
-        try:
-            from PIL import Image
-            with Image.open(os.path.join(img_prefix, videos[0]['file_names'][0])) as im:
-                frame_bytes = 2 * im.size[0] * im.size[1] * 3        # x 2: frames of a dataset vary
-        except Exception:
-            frame_bytes = None
+        name = videos[0]['file_names'][0]
+        frame_bytes = expected_frame_bytes(os.path.join(root, name) if root is not None else name)
     cache = FrameCache(workers, capacity=((lookahead if workers > 0 else 0) + group + 2) * clip_len, processes=processes, frame_bytes=frame_bytes)   # in-line decoding never runs ahead: only the staged group (and the 3-frame overlap) is worth keeping
     state = dict(ahead=0)
 

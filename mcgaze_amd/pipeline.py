@@ -208,7 +208,6 @@ class FrameCache:
                               f'(room for {max(fit, 0)}); decoding in line instead of in helper processes')
                 processes, workers = False, 0                    # in line, not threads: decode threads LOSE to in-line decoding (class docstring)
         if workers > 0 and processes:
-            import tempfile
             fd, path = tempfile.mkstemp(prefix='mcg_ring_', dir=shm)
             os.unlink(path)
             import mmap
@@ -666,8 +665,134 @@ def head_crop_window(box, h, w, expand=0.8):
     return tuple(int(v) for v in win[0])
 
 
+def _layout(sizes, align=256):
+    """Byte ranges of the given sizes laid out one behind the other, each starting on a multiple of ``align`` -> (offsets, total)."""
+    offs = np.cumsum([0] + [(int(size) + align - 1) // align * align for size in sizes]).tolist()
+    return offs[:-1], offs[-1]
+
+
+def _device(device, entry=None):
+    """torch.device(device); a bare 'cuda' is the current device BY INDEX -- staging buffers and device frames are compared with it.  With
+    ``entry``, the library call about to be made, anything but a GPU is refused."""
+    dev = torch.device(device)
+    if entry is not None and dev.type != 'cuda':
+        raise L.McgError(f'DevicePipeline runs its pixel work on the GPU ({entry}); there is no CPU path')
+    return torch.device('cuda', torch.cuda.current_device()) if dev.type == 'cuda' and dev.index is None else dev
+
+
+def _caller_stream(stream, dev):
+    return torch.cuda.current_stream(dev) if stream is None else torch.cuda.ExternalStream(stream, device=dev)
+
+
+def _kernel_norm(norm, rgb, nv12=False):
+    """-> (mean, stdinv, swap) as the pixel kernels take them.  swap: the wanted order differs from the source's; converted NV12 taps are BGR."""
+    mean = (C.c_float * 3)(*[float(v) for v in norm['mean']])
+    stdinv = (C.c_float * 3)(*[float(np.float32(1.0 / np.float64(v))) for v in norm['std']])
+    return mean, stdinv, int(bool(norm['to_rgb']) != (bool(rgb) and not nv12))
+
+
+class _Stage:
+    """One upload stage: a pinned host buffer (``host``: its numpy view), its device twin (``base``: its address), the event of the copy between
+    them (on the copy stream) and the event of the pixel kernels that read the device twin (on the caller's stream).  ``send`` copies the first
+    nbytes across on the copy stream and lets the caller's stream wait for them; ``read_by`` marks the kernels launched on ``main`` as the readers."""
+    pin = dev = host = copied = read = cs = main = None
+
+    def send(self, nbytes):
+        if self.read is not None:
+            self.cs.wait_event(self.read)                         # the kernels that read this device buffer STAGES calls ago
+        with torch.cuda.stream(self.cs):
+            self.dev[:nbytes].copy_(self.pin[:nbytes], non_blocking=True)
+        self.copied = self.cs.record_event()
+        self.main.wait_event(self.copied)
+
+    def read_by(self, main):
+        self.read = main.record_event()
+
+
+class _StagingRing:
+    """The upload stages of a DevicePipeline, used in turn, and the copy stream of each device.  What the bytes are is the caller's business:
+    ``st = take(nbytes, dev, main)``, fill ``st.host`` (device addresses: ``st.base`` + offset), ``st.send(nbytes)``, launch, ``st.read_by(main)``."""
+
+    def __init__(self, stages):
+        self.stages, self.i, self.copy_stream = [_Stage() for _ in range(stages)], 0, {}
+
+    def take(self, nbytes, dev, main):
+        """The next upload stage, its buffers at least nbytes large: a pinned host buffer (a fresh ``pin_memory()`` per call costs
+        milliseconds once decode threads compete for the allocator) and a device buffer that only the copy stream writes and only the
+        pixel kernels read.  The upload runs on a stream of its own: on the caller's stream it would queue behind the forwards already
+        launched there and the PCIe transfer would take its turn with the compute instead of running under it.  STAGES of them, used in
+        turn, so that the host fills stage i while the copies and kernels of the stages before it are still queued."""
+        st = self.stages[self.i]
+        self.i = (self.i + 1) % len(self.stages)
+        if st.copied is not None:
+            st.copied.synchronize()                               # the pinned buffer is about to be overwritten
+        cs = self.copy_stream.get(dev)
+        if cs is None:
+            cs = self.copy_stream[dev] = torch.cuda.Stream(dev)
+        if st.pin is None or st.pin.numel() < nbytes or st.dev.device != dev:
+            size = max(int(nbytes * 1.25), 1 << 20)
+            st.pin = torch.empty(size, dtype=torch.uint8).pin_memory()
+            st.dev = torch.empty(size, dtype=torch.uint8, device=dev)
+            st.host, st.base = st.pin.numpy(), st.dev.data_ptr()
+            st.read = None
+            cs.wait_stream(main)                                  # the allocator may hand out memory that work queued on `main` still uses
+        st.cs, st.main = cs, main
+        return st
+
+
+def _head_crop_tables(images, dev, planes, boxes, image_of, expand):
+    """The host side of head_crops -> (table, parts, boxes, image_of, on_device, n).  table: one _IMAGE record per frame (_NV12_IMAGE with ``planes``,
+    the frames as _nv12_planes returns them); parts: (frame, field of its record, bytes) of every HOST frame -- it gets its address once it is staged.
+    Host box and index tables come back in the types the device reads (f32, int32) and are CHECKED here; device tables (on_device) are not read back."""
+    table, parts = np.zeros(len(images), dtype=_IMAGE if planes is None else _NV12_IMAGE), []
+    for k, im in enumerate(images):
+        if planes is not None:
+            y, uv, there = planes[k]
+            h, w = y.shape
+            if not there:
+                parts += [(k, 'y', y.reshape(-1)), (k, 'uv', uv.reshape(-1))]
+            table[k] = (y.data_ptr(), uv.data_ptr(), h, w, y.stride(0), uv.stride(0) if h > 2 else w) if there else (0, 0, h, w, w, w)
+        elif isinstance(im, torch.Tensor):
+            if not (im.is_cuda and im.device == dev and im.dtype == torch.uint8 and im.ndim == 3 and im.shape[2] == 3 and im.numel() > 0
+                    and im.stride(2) == 1 and im.stride(1) == 3 and (im.shape[0] == 1 or im.stride(0) >= 3 * im.shape[1])):
+                raise TypeError(f'frame {k}: device frames must be HxWx3 uint8 tensors on {dev} with packed pixels (stride (pitch, 3, 1)), '
+                                f'got {im.dtype} {tuple(im.shape)} strides {tuple(im.stride())} on {im.device}')
+            table[k] = (im.data_ptr(), im.shape[0], im.shape[1], im.stride(0) if im.shape[0] > 1 else 3 * im.shape[1])
+        else:
+            a = np.ascontiguousarray(im)
+            if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3 or a.size == 0:
+                raise TypeError(f'frame {k}: frames must be HxWx3 uint8 arrays, got {a.dtype} {a.shape}')
+            parts.append((k, 'src', a.reshape(-1)))
+            table[k] = (0, a.shape[0], a.shape[1], 3 * a.shape[1])
+    on_device = [isinstance(t, torch.Tensor) and t.is_cuda for t in (boxes, image_of)]
+    if not on_device[0]:
+        boxes = np.ascontiguousarray(_host_array(boxes), dtype=np.float32).reshape(-1, 4)     # f32 is what the device reads: the checks see the same boxes
+    if not on_device[1]:
+        image_of = np.ascontiguousarray(_host_array(image_of)).reshape(-1)
+        if image_of.dtype.kind not in 'iu':
+            raise TypeError(f'image_of must hold integers, got {image_of.dtype}')
+        if len(image_of) and (image_of.min() < 0 or image_of.max() >= len(images)):
+            raise ValueError(f'image_of must lie in [0, {len(images)}), got [{image_of.min()}, {image_of.max()}]')
+        image_of = image_of.astype(np.int32)
+    n = int(boxes.shape[0])
+    if tuple(boxes.shape) != (n, 4) or tuple(image_of.shape) != (n,):
+        raise ValueError(f'head_crops: boxes {tuple(boxes.shape)} and image_of {tuple(image_of.shape)} must be [n,4] and [n]')
+    if n > 65535:
+        raise ValueError(f'head_crops: at most 65535 crops per call (got {n})')
+    if not any(on_device) and n:
+        _, empty = head_crop_windows(boxes, table['h'][image_of], table['w'][image_of], expand)
+        if empty.any():
+            k = int(np.flatnonzero(empty)[0])
+            raise ValueError(f'head box {k} {boxes[k].tolist()} leaves an empty window in frame {int(image_of[k])} '
+                             f'({int(table["h"][image_of[k]])} x {int(table["w"][image_of[k]])})')
+    return table, parts, boxes, image_of, on_device, n
+
+
 class DevicePipeline:
     """``Compose(cfg.data.test.pipeline)`` (mmdet/datasets/pipelines/compose.py:11-51) whose pixel work is one HIP launch."""
+
+    STAGES = 4
+    IMAGE_TABLES = 16                                             # device-resident frame tables kept by head_crops (a decoder's buffer ring recurs)
 
     def __init__(self, transforms):
         self.transforms = [PIPELINES.build(dict(t)) if isinstance(t, dict) else t for t in transforms]
@@ -678,10 +803,7 @@ class DevicePipeline:
             raise ValueError(f'unsupported test pipeline {kinds}: need ... Normalize ... DefaultFormatBundle, Collect')
         self.collect = self.transforms[-1]
         self._planners = [t.plan for t in self.transforms if type(t) not in (LoadImageFromFile, ImageToTensor, Collect)]   # the rest plan nothing
-        # upload stages, used in turn: a pinned host buffer, its device twin, the event of the copy between them (on the copy stream) and the
-        # event of the pixel kernels that read the device twin (on the caller's stream)
-        self._stages = [dict(pin=None, dev=None, copied=None, read=None) for _ in range(self.STAGES)]
-        self._stage_i, self._copy_stream = 0, {}
+        self._ring = _StagingRing(self.STAGES)                    # run_many and head_crops upload through the same stages
         self._image_tables = collections.OrderedDict()            # head_crops: (device, frame table bytes) -> that table on the device
 
     def plan(self, shape, rng=np.random, filename=None, ori_filename=None):
@@ -700,62 +822,11 @@ class DevicePipeline:
         loader: path -> HxWx3 uint8 array (default LoadImageFromFile.load; a FrameCache decodes ahead on host threads)."""
         return self.run_many([frames], device, rng, img_prefix, stream, loader)[0]
 
-    STAGES = 4
-
-    def _staging(self, nbytes, dev, main):
-        """The next upload stage, its buffers at least nbytes large: a pinned host buffer (a fresh ``pin_memory()`` per call costs
-        milliseconds once decode threads compete for the allocator) and a device buffer that only the copy stream writes and only the
-        pixel kernels read.  The upload runs on a stream of its own: on the caller's stream it would queue behind the forwards already
-        launched there and the PCIe transfer would take its turn with the compute instead of running under it.  STAGES of them, used in
-        turn, so that the host fills stage i while the copies and kernels of the stages before it are still queued."""
-        st = self._stages[self._stage_i]
-        self._stage_i = (self._stage_i + 1) % self.STAGES
-        if st['copied'] is not None:
-            st['copied'].synchronize()                            # the pinned buffer is about to be overwritten
-        cs = self._copy_stream.get(dev)
-        if cs is None:
-            cs = self._copy_stream[dev] = torch.cuda.Stream(dev)
-        if st['pin'] is None or st['pin'].numel() < nbytes or st['dev'].device != dev:
-            size = max(int(nbytes * 1.25), 1 << 20)
-            st['pin'] = torch.empty(size, dtype=torch.uint8).pin_memory()
-            st['dev'] = torch.empty(size, dtype=torch.uint8, device=dev)
-            st['read'] = None
-            cs.wait_stream(main)                                  # the allocator may hand out memory that work queued on `main` still uses
-        return st, cs
-
-    def run_many(self, windows, device='cuda:0', rng=np.random, img_prefix=None, stream=None, loader=None):
-        """Several clip batches (windows) through ONE staging copy and one launch per distinct padded size: windows = list of lists
-        of frames (arrays or file names) -> list of (img, img_metas), each exactly what ``__call__`` returns for that window -- frames
-        are planned window by window, frame by frame, so the RNG draws fall where they do one window at a time; padding is per
-        window (mmcv's collate pads a clip to ITS largest frame)."""
-        lib = L.load()
-        dev = torch.device(device)
-        if dev.type != 'cuda':
-            raise L.McgError('DevicePipeline runs its pixel work on the GPU (mcg_preprocess_frames); there is no CPU path')
-        if dev.index is None:                                     # 'cuda': the current device, by index -- the staging buffers are compared with it
-            dev = torch.device('cuda', torch.cuda.current_device())
-        rgb_source = all(isinstance(f, str) for w in windows for f in w)      # our own decode: keep PIL's RGB order, the kernel swaps
-        if loader is not None:
-            load = loader
-            rgb_source = rgb_source and bool(getattr(loader, 'rgb', False))
-        else:
-            load = (lambda path: LoadImageFromFile.load(path, rgb=True)) if rgb_source else LoadImageFromFile.load
-        # arrays: the DISTINCT decoded frames of this call (a file named by several windows -- they overlap by three frames -- is staged and
-        # uploaded once); src[k]: the array the k-th (window, frame) reads; plans stay per (window, frame): every use draws its own crop
+    def _load_and_plan(self, windows, rngs, img_prefix, loader, load, rgb_source):
+        """-> (arrays, src, plans, bounds).  arrays: the DISTINCT decoded frames of this call (a file named by several windows -- they overlap
+        by three frames -- is staged and uploaded once); src[k]: the array the k-th (window, frame) reads; plans stay per (window, frame): every
+        use draws its own crop; window wi is rows bounds[wi]:bounds[wi + 1]."""
         arrays, src, plans, bounds, seen = [], [], [], [0], {}
-        rngs = rng if isinstance(rng, (list, tuple)) else [rng] * len(windows)   # one generator per window (harness: one per VIDEO), or one for all
-        if len(rngs) != len(windows):
-            raise ValueError(f'run_many: {len(rngs)} generators for {len(windows)} windows')
-        try:
-            return self._run_many_loaded(windows, rngs, img_prefix, loader, load, rgb_source, arrays, src, plans, bounds, seen, lib, dev, stream)
-        except BaseException:
-            # a TypeError for a non-uint8 frame, a decode error, a staging failure: the ring views handed out so far are not read any more --
-            # without this they stayed pinned and a caller that carried on met 'all cached frames are handed out' later (ADVICE r5)
-            if hasattr(loader, 'release'):
-                loader.release()
-            raise
-
-    def _run_many_loaded(self, windows, rngs, img_prefix, loader, load, rgb_source, arrays, src, plans, bounds, seen, lib, dev, stream):
         for frames, rng in zip(windows, rngs):
             for f in frames:
                 if isinstance(f, str):
@@ -777,76 +848,73 @@ class DevicePipeline:
                 src.append(k)
                 plans.append(self.plan(arr.shape, rng, *names))
             bounds.append(len(src))
-        out = [None] * len(windows)
-        n = len(src)
-        for wi in range(len(windows)):
-            if bounds[wi] == bounds[wi + 1]:
-                out[wi] = (torch.empty(0, 3, 0, 0, dtype=torch.float32, device=dev), [])
-        if n == 0:
-            return out
-        offs = np.cumsum([0] + [(a.size + 255) // 256 * 256 for a in arrays])
-        # the frame descriptors travel in the same pinned staging buffer, behind the pixels: one non-blocking copy for everything (a
-        # pageable .to() per descriptor table blocked the host until the stream had drained -- the engine's previous batch)
-        groups = {}                                           # padded size -> windows
-        for wi in range(len(windows)):
-            a, b = bounds[wi], bounds[wi + 1]
-            if b > a:
-                pad = (max(p.pad_shape[0] for p in plans[a:b]), max(p.pad_shape[1] for p in plans[a:b]))
-                groups.setdefault(pad, []).append(wi)
-        dsz = C.sizeof(L.FrameDesc)
-        desc_off, total = {}, int(offs[-1])
-        for pad, wis in groups.items():
-            desc_off[pad] = total
-            total += (sum(bounds[wi + 1] - bounds[wi] for wi in wis) * dsz + 255) // 256 * 256
-        with torch.cuda.device(dev):
-            main = torch.cuda.current_stream(dev) if stream is None else torch.cuda.ExternalStream(stream, device=dev)
-            st, cs = self._staging(total, dev, main)
-            host, raw = st['pin'], st['dev']
-            host_np = host.numpy()
-            for a, o in zip(arrays, offs):
-                host_np[int(o):int(o) + a.size] = a.reshape(-1)
-            if hasattr(loader, 'release'):
-                loader.release()                                  # ring views of a FrameCache: copied, their slots may go
-            # descriptors (mcg_frame_desc), built as one structured array per padded size
-            src_a = np.asarray(src, dtype=np.int64)
-            shp = np.asarray([a.shape[:2] for a in arrays], dtype=np.int32)
-            geo = np.asarray([p.crop + p.img_shape[:2] for p in plans], dtype=np.int32)          # crop y, x, h, w, out h, w
-            for pad, wis in groups.items():
-                idx = np.concatenate([np.arange(bounds[wi], bounds[wi + 1]) for wi in wis])
-                si = src_a[idx]
-                desc = np.zeros(len(idx), dtype=_DESC)
-                desc['src'] = raw.data_ptr() + offs[si]
-                desc['src_h'], desc['src_w'], desc['src_pitch'] = shp[si, 0], shp[si, 1], shp[si, 1] * 3
-                for j, f in enumerate(('crop_y', 'crop_x', 'crop_h', 'crop_w', 'out_h', 'out_w')):
-                    desc[f] = geo[idx, j]
-                host_np[desc_off[pad]:desc_off[pad] + len(idx) * dsz] = desc.view(np.uint8)
-            if st['read'] is not None:
-                cs.wait_event(st['read'])                         # the kernels that read this device buffer STAGES calls ago
-            with torch.cuda.stream(cs):
-                raw[:total].copy_(host[:total], non_blocking=True)
-            st['copied'] = torch.cuda.Event()
-            st['copied'].record(cs)
-            main.wait_event(st['copied'])
-        norm = plans[0].img_norm_cfg
-        mean = (C.c_float * 3)(*[float(v) for v in norm['mean']])
-        stdinv = (C.c_float * 3)(*[float(np.float32(1.0 / np.float64(v))) for v in norm['std']])
-        swap = int(bool(norm['to_rgb']) != rgb_source)        # channel swap the kernel performs: wanted order differs from the source's
-        s = main.cuda_stream
-        for (pad_h, pad_w), wis in groups.items():
-            n_idx = sum(bounds[wi + 1] - bounds[wi] for wi in wis)
-            img = torch.empty(n_idx, 3, pad_h, pad_w, dtype=torch.float32, device=dev)
-            L.check(lib.mcg_preprocess_frames(C.c_void_p(s), C.c_void_p(raw.data_ptr() + desc_off[(pad_h, pad_w)]), n_idx, C.c_void_p(img.data_ptr()), pad_h, pad_w,
-                                              mean, stdinv, swap), 'mcg_preprocess_frames')
-            at = 0
-            for wi in wis:
-                cnt = bounds[wi + 1] - bounds[wi]
-                out[wi] = (img[at:at + cnt], [self.collect.meta(p) for p in plans[bounds[wi]:bounds[wi + 1]]])
-                at += cnt
-        st['read'] = torch.cuda.Event()
-        st['read'].record(main)
-        return out
+        return arrays, src, plans, bounds
 
-    IMAGE_TABLES = 16                                             # device-resident frame tables kept by head_crops (a decoder's buffer ring recurs)
+    def run_many(self, windows, device='cuda:0', rng=np.random, img_prefix=None, stream=None, loader=None):
+        """Several clip batches (windows) through ONE staging copy and one launch per distinct padded size: windows = list of lists
+        of frames (arrays or file names) -> list of (img, img_metas), each exactly what ``__call__`` returns for that window -- frames
+        are planned window by window, frame by frame, so the RNG draws fall where they do one window at a time; padding is per
+        window (mmcv's collate pads a clip to ITS largest frame)."""
+        lib, release = L.load(), getattr(loader, 'release', lambda: None)
+        dev = _device(device, 'mcg_preprocess_frames')
+        rgb_source = all(isinstance(f, str) for w in windows for f in w)      # our own decode: keep PIL's RGB order, the kernel swaps
+        if loader is not None:
+            load = loader
+            rgb_source = rgb_source and bool(getattr(loader, 'rgb', False))
+        else:
+            load = (lambda path: LoadImageFromFile.load(path, rgb=True)) if rgb_source else LoadImageFromFile.load
+        rngs = rng if isinstance(rng, (list, tuple)) else [rng] * len(windows)   # one generator per window (harness: one per VIDEO), or one for all
+        if len(rngs) != len(windows):
+            raise ValueError(f'run_many: {len(rngs)} generators for {len(windows)} windows')
+        try:
+            arrays, src, plans, bounds = self._load_and_plan(windows, rngs, img_prefix, loader, load, rgb_source)
+            out = [None if bounds[wi + 1] > bounds[wi] else (torch.empty(0, 3, 0, 0, dtype=torch.float32, device=dev), []) for wi in range(len(windows))]
+            if not src:
+                return out
+            groups = {}                                           # padded size -> windows
+            for wi in range(len(windows)):
+                a, b = bounds[wi], bounds[wi + 1]
+                if b > a:
+                    pad = (max(p.pad_shape[0] for p in plans[a:b]), max(p.pad_shape[1] for p in plans[a:b]))
+                    groups.setdefault(pad, []).append(wi)
+            rows = {pad: np.concatenate([np.arange(bounds[wi], bounds[wi + 1]) for wi in wis]) for pad, wis in groups.items()}
+            # the frame descriptors travel in the same pinned staging buffer, behind the pixels: one non-blocking copy for everything (a
+            # pageable .to() per descriptor table blocked the host until the stream had drained -- the engine's previous batch)
+            dsz = C.sizeof(L.FrameDesc)
+            offs, total = _layout([a.size for a in arrays] + [len(idx) * dsz for idx in rows.values()])
+            desc_off = dict(zip(groups, offs[len(arrays):]))
+            with torch.cuda.device(dev):
+                main = _caller_stream(stream, dev)
+                st = self._ring.take(total, dev, main)
+                for a, o in zip(arrays, offs):
+                    st.host[o:o + a.size] = a.reshape(-1)
+                release()                                         # ring views of a FrameCache: copied, their slots may go
+                # descriptors (mcg_frame_desc), built as one structured array per padded size
+                addr = st.base + np.asarray(offs[:len(arrays)], dtype=np.int64)[src]
+                shp = np.asarray([a.shape[:2] for a in arrays], dtype=np.int32)[src]
+                geo = np.asarray([p.crop + p.img_shape[:2] for p in plans], dtype=np.int32)          # crop y, x, h, w, out h, w
+                for pad, idx in rows.items():
+                    desc = np.zeros(len(idx), dtype=_DESC)
+                    desc['src'], desc['src_h'], desc['src_w'], desc['src_pitch'] = addr[idx], shp[idx, 0], shp[idx, 1], shp[idx, 1] * 3
+                    for j, f in enumerate(('crop_y', 'crop_x', 'crop_h', 'crop_w', 'out_h', 'out_w')):
+                        desc[f] = geo[idx, j]
+                    st.host[desc_off[pad]:desc_off[pad] + len(idx) * dsz] = desc.view(np.uint8)
+                st.send(total)
+            mean, stdinv, swap = _kernel_norm(plans[0].img_norm_cfg, rgb_source)
+            for (pad_h, pad_w), wis in groups.items():
+                n = len(rows[pad_h, pad_w])
+                img = torch.empty(n, 3, pad_h, pad_w, dtype=torch.float32, device=dev)
+                L.check(lib.mcg_preprocess_frames(C.c_void_p(main.cuda_stream), C.c_void_p(st.base + desc_off[(pad_h, pad_w)]), n, C.c_void_p(img.data_ptr()),
+                                                  pad_h, pad_w, mean, stdinv, swap), 'mcg_preprocess_frames')
+                for wi, part in zip(wis, img.split([bounds[wi + 1] - bounds[wi] for wi in wis])):
+                    out[wi] = (part, [self.collect.meta(p) for p in plans[bounds[wi]:bounds[wi + 1]]])
+            st.read_by(main)
+            return out
+        except BaseException:
+            # a TypeError for a non-uint8 frame, a decode error, a staging failure: the ring views handed out so far are not read any more --
+            # without this they stayed pinned and a caller that carried on met 'all cached frames are handed out' later (ADVICE r5)
+            release()
+            raise
 
     def head_crop_geometry(self):
         """-> (scale_w, scale_h, pad_h, pad_w, img_norm_cfg) of the chain a head crop goes through, which must be the demo's
@@ -891,102 +959,39 @@ class DevicePipeline:
             raise ValueError(f"pixel_format must be 'bgr' or 'nv12', got {pixel_format!r}")
         coef = _yuv_coef(matrix)
         nv12 = pixel_format == 'nv12'
-        dev = torch.device(device)
-        if nv12:                                                  # the surfaces are checked whatever the device: a bad one is the caller's first error
-            if dev.type == 'cuda' and dev.index is None:
-                dev = torch.device('cuda', torch.cuda.current_device())
-            planes = [_nv12_planes(k, im, dev) for k, im in enumerate(images)]
-        if dev.type != 'cuda':
-            raise L.McgError('DevicePipeline runs its pixel work on the GPU (mcg_preprocess_head_crops); there is no CPU path')
-        if dev.index is None:
-            dev = torch.device('cuda', torch.cuda.current_device())
+        dev = _device(device)                                     # the surfaces are checked whatever the device: a bad one is the caller's first error
+        planes = [_nv12_planes(k, im, dev) for k, im in enumerate(images)] if nv12 else None
+        dev = _device(dev, 'mcg_preprocess_head_crops')
         scale_w, scale_h, pad_h, pad_w, norm = self.head_crop_geometry()
         if not len(images):
             raise ValueError('head_crops: no frames')
-        # frame table: host frames get their address once they are staged
-        table = np.zeros(len(images), dtype=_NV12_IMAGE if nv12 else _IMAGE)
-        host_at = {}                                              # index -> arrays to stage, one behind the other
-        for k, im in enumerate(images):
-            if nv12:
-                y, uv, there = planes[k]
-                h, w = y.shape
-                if there:
-                    table[k] = (y.data_ptr(), uv.data_ptr(), h, w, y.stride(0), uv.stride(0) if h > 2 else w)
-                else:
-                    host_at[k] = (y, uv)
-                    table[k] = (0, 0, h, w, w, w)
-            elif isinstance(im, torch.Tensor):
-                if not (im.is_cuda and im.device == dev and im.dtype == torch.uint8 and im.ndim == 3 and im.shape[2] == 3 and im.numel() > 0
-                        and im.stride(2) == 1 and im.stride(1) == 3 and (im.shape[0] == 1 or im.stride(0) >= 3 * im.shape[1])):
-                    raise TypeError(f'frame {k}: device frames must be HxWx3 uint8 tensors on {dev} with packed pixels (stride (pitch, 3, 1)), '
-                                    f'got {im.dtype} {tuple(im.shape)} strides {tuple(im.stride())} on {im.device}')
-                table[k] = (im.data_ptr(), im.shape[0], im.shape[1], im.stride(0) if im.shape[0] > 1 else 3 * im.shape[1])
-            else:
-                a = np.ascontiguousarray(im)
-                if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3 or a.size == 0:
-                    raise TypeError(f'frame {k}: frames must be HxWx3 uint8 arrays, got {a.dtype} {a.shape}')
-                host_at[k] = (a,)
-                table[k] = (0, a.shape[0], a.shape[1], 3 * a.shape[1])
-        on_device = [isinstance(t, torch.Tensor) and t.is_cuda for t in (boxes, image_of)]
-        if not on_device[0]:
-            boxes = np.ascontiguousarray(_host_array(boxes), dtype=np.float32).reshape(-1, 4)     # f32 is what the device reads: the checks see the same boxes
-        if not on_device[1]:
-            image_of = np.ascontiguousarray(_host_array(image_of)).reshape(-1)
-            if image_of.dtype.kind not in 'iu':
-                raise TypeError(f'image_of must hold integers, got {image_of.dtype}')
-            if len(image_of) and (image_of.min() < 0 or image_of.max() >= len(images)):
-                raise ValueError(f'image_of must lie in [0, {len(images)}), got [{image_of.min()}, {image_of.max()}]')
-            image_of = image_of.astype(np.int32)
-        n = int(boxes.shape[0])
-        if tuple(boxes.shape) != (n, 4) or tuple(image_of.shape) != (n,):
-            raise ValueError(f'head_crops: boxes {tuple(boxes.shape)} and image_of {tuple(image_of.shape)} must be [n,4] and [n]')
-        if n > 65535:
-            raise ValueError(f'head_crops: at most 65535 crops per call (got {n})')
-        if not any(on_device) and n:
-            _, empty = head_crop_windows(boxes, table['h'][image_of], table['w'][image_of], expand)
-            if empty.any():
-                k = int(np.flatnonzero(empty)[0])
-                raise ValueError(f'head box {k} {boxes[k].tolist()} leaves an empty window in frame {int(image_of[k])} '
-                                 f'({int(table["h"][image_of[k]])} x {int(table["w"][image_of[k]])})')
+        table, parts, boxes, image_of, on_device, n = _head_crop_tables(images, dev, planes, boxes, image_of, expand)
         with torch.cuda.device(dev):
-            main = torch.cuda.current_stream(dev) if stream is None else torch.cuda.ExternalStream(stream, device=dev)
+            main = _caller_stream(stream, dev)
             with torch.cuda.stream(main):
-                if on_device[0]:
-                    boxes = boxes.to(dev, torch.float32).contiguous()
-                if on_device[1]:
-                    image_of = image_of.to(dev, torch.int32).contiguous()
+                boxes = boxes.to(dev, torch.float32).contiguous() if on_device[0] else boxes
+                image_of = image_of.to(dev, torch.int32).contiguous() if on_device[1] else image_of
+                new = lambda *shape, dtype=torch.int32: torch.empty(*shape, dtype=dtype, device=dev)
                 if n == 0:
-                    z = lambda *shape, dtype=torch.int32: torch.zeros(*shape, dtype=dtype, device=dev)
-                    return z(0, 3, pad_h, pad_w, dtype=torch.float32), z(0, 2), z(0, 4, dtype=torch.float32), z(0, 4), z(0)
+                    return new(0, 3, pad_h, pad_w, dtype=torch.float32), new(0, 2), new(0, 4, dtype=torch.float32), new(0, 4), new(0)
                 # everything that comes from the host travels in ONE pinned staging buffer and one copy: pixels, frame table, host tables
-                parts = [(k, f, a.reshape(-1)) for k, arrays in host_at.items() for f, a in zip(('y', 'uv') if nv12 else ('src',), arrays)]
                 tables = [t.view(np.uint8).reshape(-1) for t, d in zip((boxes, image_of), on_device) if not d]
+                st = None
                 if parts or tables:
-                    sizes = [(a.size + 255) // 256 * 256 for _, _, a in parts] + [(table.nbytes + 255) // 256 * 256] + [(t.size + 255) // 256 * 256 for t in tables]
-                    offs = np.cumsum([0] + sizes)
-                    total = int(offs[-1])
-                    st, cs = self._staging(total, dev, main)
-                    host, raw = st['pin'], st['dev']
-                    host_np = host.numpy()
-                    for (k, f, a), o in zip(parts, offs):
-                        host_np[int(o):int(o) + a.size] = a
-                        table[f][k] = raw.data_ptr() + int(o)
-                    at = [raw.data_ptr() + int(o) for o in offs[len(parts):-1]]                  # frame table, then the host tables
-                    for t, o in zip([table.view(np.uint8).reshape(-1)] + tables, offs[len(parts):-1]):
-                        host_np[int(o):int(o) + t.size] = t
-                    if st['read'] is not None:
-                        cs.wait_event(st['read'])
-                    with torch.cuda.stream(cs):
-                        raw[:total].copy_(host[:total], non_blocking=True)
-                    st['copied'] = torch.cuda.Event()
-                    st['copied'].record(cs)
-                    main.wait_event(st['copied'])
-                    images_ptr, at = at[0], at[1:]
+                    blobs = [a for _, _, a in parts] + [table.view(np.uint8).reshape(-1)] + tables     # (the table's bytes are a VIEW: filled below, then copied)
+                    offs, total = _layout([b.size for b in blobs])
+                    st = self._ring.take(total, dev, main)
+                    for (k, f, _), o in zip(parts, offs):
+                        table[f][k] = st.base + o                 # a host frame's address: where its bytes land in the device twin
+                    for b, o in zip(blobs, offs):
+                        st.host[o:o + b.size] = b
+                    st.send(total)
+                    at = [st.base + o for o in offs[len(parts):]]                                # frame table, then the host tables
+                    images_ptr = at.pop(0)
                     boxes_ptr = boxes.data_ptr() if on_device[0] else at.pop(0)
                     image_of_ptr = image_of.data_ptr() if on_device[1] else at.pop(0)
                 else:
-                    # nothing comes from the host but the frame table, and that only the first time these frames are seen
-                    st = None
+                    # nothing comes from the host but the frame table, and that only the first time these frames are seen: no stage is taken
                     key = (dev.index, table.tobytes()) + (('nv12',) if nv12 else ())
                     tdev = self._image_tables.get(key)
                     if tdev is None:
@@ -996,22 +1001,15 @@ class DevicePipeline:
                     else:
                         self._image_tables.move_to_end(key)
                     images_ptr, boxes_ptr, image_of_ptr = tdev.data_ptr(), boxes.data_ptr(), image_of.data_ptr()
-                img = torch.empty(n, 3, pad_h, pad_w, dtype=torch.float32, device=dev)
-                desc = torch.empty(n, _NV12_DESC_WORDS if nv12 else _DESC_WORDS, dtype=torch.int32, device=dev)
-                img_hw = torch.empty(n, 2, dtype=torch.int32, device=dev)
-                scale_factor = torch.empty(n, 4, dtype=torch.float32, device=dev)
-                flags = torch.empty(n, dtype=torch.int32, device=dev)
-                mean = (C.c_float * 3)(*[float(v) for v in norm['mean']])
-                stdinv = (C.c_float * 3)(*[float(np.float32(1.0 / np.float64(v))) for v in norm['std']])
-                swap = int(bool(norm['to_rgb']) != (bool(rgb) and not nv12))                     # converted NV12 taps are BGR
+                img, scale_factor = new(n, 3, pad_h, pad_w, dtype=torch.float32), new(n, 4, dtype=torch.float32)
+                desc, img_hw, flags = new(n, _NV12_DESC_WORDS if nv12 else _DESC_WORDS), new(n, 2), new(n)
                 vp = C.c_void_p
                 entry, more = (lib.mcg_preprocess_head_crops_nv12, (C.byref(L.YuvCoef(**coef)),)) if nv12 else (lib.mcg_preprocess_head_crops, ())
                 L.check(entry(vp(main.cuda_stream), vp(images_ptr), len(images), vp(boxes_ptr), vp(image_of_ptr), n, float(expand),
                               scale_w, scale_h, vp(desc.data_ptr()), vp(img_hw.data_ptr()), vp(scale_factor.data_ptr()),
-                              vp(flags.data_ptr()), vp(img.data_ptr()), pad_h, pad_w, mean, stdinv, swap, *more), entry.__name__)
+                              vp(flags.data_ptr()), vp(img.data_ptr()), pad_h, pad_w, *_kernel_norm(norm, rgb, nv12), *more), entry.__name__)
                 if st is not None:
-                    st['read'] = torch.cuda.Event()
-                    st['read'].record(main)
+                    st.read_by(main)
         return img, img_hw, scale_factor, desc[:, _CROP_WORD:_CROP_WORD + 4], flags
 
 

@@ -158,6 +158,45 @@ def test_head_crops_capture_in_a_graph_and_follow_the_box_tensor(want64):
     check(out, oracle_crops(FRAMES, BOXES2, IMAGE_OF, 64, 64), 'replay on new boxes')
 
 
+def test_run_many_and_head_crops_take_turns_on_one_staging_ring():
+    """One DevicePipeline, 2 * STAGES + 1 calls on a side stream handed over as stream=, nothing synchronised between them: run_many and head_crops
+    (BGR frames, NV12 planes; all from the host) alternate, so run_many refills every stage and each head_crops call lands between two of its
+    uploads; the middle call stages a 640 x 600 frame, past the 1 MiB a stage starts with, so a stage is reallocated while earlier work is
+    queued.  After ONE synchronise every call's output equals the same call on a fresh pipeline of its own, bit for bit."""
+    rs = np.random.RandomState(11)
+    frame = lambda h, w: rs.randint(0, 256, (h, w, 3)).astype(np.uint8)
+    box = np.array([[2, 2, 7, 7], [1, 3, 6.5, 8]], dtype=np.float32)         # l = 4: rows [0, 8) and [1, 8) of any frame here
+    calls, n = [], 2 * P.DevicePipeline.STAGES + 1
+    for k in range(n):
+        h, w = 8 + 2 * rs.randint(0, 5), 8 + 2 * rs.randint(0, 5)              # 8 .. 16, even: NV12 sizes
+        if k % 2 == 0:
+            big = [frame(600, 640)] if k == n // 2 else []
+            windows = [[frame(h, w), frame(w, h)] + big, [frame(8, 16)]]        # padded to 64 x 64 and to 32 x 64: two launches
+            calls.append(lambda pipe, windows=windows, k=k, **kw: pipe.run_many(windows, device=DEV, rng=np.random.RandomState(k), **kw))
+        elif k % 4 == 1:
+            frames = [frame(h, w), frame(12, 8)]
+            calls.append(lambda pipe, frames=frames, **kw: pipe.head_crops(frames, box, [0, 1], device=DEV, **kw))
+        else:
+            planes = [(rs.randint(0, 256, (h, w)).astype(np.uint8), rs.randint(0, 256, (h // 2, w // 2, 2)).astype(np.uint8)) for _ in range(2)]
+            calls.append(lambda pipe, planes=planes, **kw: pipe.head_crops(planes, box, [1, 0], device=DEV, pixel_format='nv12', matrix='bt709', **kw))
+    assert sum(k % 2 == 0 for k in range(n)) == P.DevicePipeline.STAGES + 1 and n // 2 % 2 == 0     # run_many comes round to every stage; it makes the big call
+    assert 600 * 640 * 3 > 1 << 20                               # ... whose bytes no stage holds yet
+    pipe, side = P.DevicePipeline(chain(64)), torch.cuda.Stream(DEV)
+    got = [call(pipe, stream=side.cuda_stream) for call in calls]
+    torch.cuda.synchronize()
+    for k, (call, g) in enumerate(zip(calls, got)):
+        want = call(P.DevicePipeline(chain(64)))
+        torch.cuda.synchronize()
+        if k % 2:
+            same(g, want)
+            continue
+        assert len(g) == len(want) == 2
+        for (img, metas), (wimg, wmetas) in zip(g, want):
+            assert img.shape == wimg.shape and torch.equal(img.cpu(), wimg.cpu()), k
+            assert [sorted(m) for m in metas] == [sorted(m) for m in wmetas]
+            assert all(np.array_equal(m[key], wm[key]) for m, wm in zip(metas, wmetas) for key in ('ori_shape', 'img_shape', 'pad_shape', 'scale_factor')), k
+
+
 # ---------------------------------------------------------------- 4. flags
 def test_flags_mark_rows_without_a_window_and_leave_their_neighbours_alone(want64):
     pipe = P.DevicePipeline(chain(64))

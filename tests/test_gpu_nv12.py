@@ -160,17 +160,17 @@ def test_nv12_head_crops_capture_in_a_graph_and_reuse_the_frame_table(bgr_frames
     planes = [device_planes(k) for k in range(3)]
     boxes, image_of = torch.from_numpy(N.BOXES).to(DEV), torch.from_numpy(N.IMAGE_OF).to(DEV)
     want = pipe.head_crops(bgr_frames['bt709'], N.BOXES, N.IMAGE_OF, device=DEV)
-    stage_i = pipe._stage_i
+    stage_i = pipe._ring.i
     side = torch.cuda.Stream(DEV)
     side.wait_stream(torch.cuda.current_stream())
     with torch.cuda.stream(side):                              # eager warm-up: uploads the frame table of these surfaces, once
         pipe.head_crops(planes, boxes, image_of, device=DEV, pixel_format='nv12', matrix='bt709')
     torch.cuda.current_stream().wait_stream(side)
     torch.cuda.synchronize()
-    assert len(pipe._image_tables) == 1 and pipe._stage_i == stage_i      # one cached table; no staging buffer was taken
+    assert len(pipe._image_tables) == 1 and pipe._ring.i == stage_i      # one cached table; no staging buffer was taken
     table = next(iter(pipe._image_tables.values()))
     again = pipe.head_crops(planes, boxes, image_of, device=DEV, pixel_format='nv12', matrix='bt709')
-    assert len(pipe._image_tables) == 1 and next(iter(pipe._image_tables.values())) is table and pipe._stage_i == stage_i
+    assert len(pipe._image_tables) == 1 and next(iter(pipe._image_tables.values())) is table and pipe._ring.i == stage_i
     same(again, want, 'second call')
     graph = torch.cuda.CUDAGraph()
     with torch.cuda.graph(graph):

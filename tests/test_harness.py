@@ -137,6 +137,32 @@ def test_run_annotation_from_files_equals_window_by_window(tmp_path):
         assert rec == want and len(rec['fusion_gazes']) == len(v['file_names'])
 
 
+def test_expected_frame_bytes_reads_the_first_frames_header(tmp_path, monkeypatch):
+    """What run_annotation hands FrameCache as ``frame_bytes``: 2 * w * h * 3 of the run's first frame, None where there is no such file."""
+    from PIL import Image
+    w, h = 24, 10
+    Image.fromarray(np.zeros((h, w, 3), np.uint8)).save(str(tmp_path / 'a.png'))
+    assert harness.expected_frame_bytes(str(tmp_path / 'a.png')) == 2 * w * h * 3 == 1440
+    assert harness.expected_frame_bytes(str(tmp_path / 'absent.png')) is None
+    (tmp_path / 'text.png').write_text('no image')
+    assert harness.expected_frame_bytes(str(tmp_path / 'text.png')) is None
+    # ... and run_annotation finds that file under its ``root``: the cache is built with the first frame's price, not with None
+    from mcgaze_amd import pipeline as P
+
+    class Seen(Exception):
+        pass
+
+    def cache(*args, **kw):
+        raise Seen(kw['frame_bytes'])
+
+    monkeypatch.setattr(P, 'FrameCache', cache)
+    anno = dict(videos=[dict(id=0, file_names=['a.png'] * 7)])
+    for kw, want in ((dict(workers=2, processes=True), 1440), (dict(workers=2), None), (dict(), None)):
+        with pytest.raises(Seen) as seen:
+            harness.run_annotation(None, anno, str(tmp_path), None, **kw)
+        assert seen.value.args == (want,), kw
+
+
 def test_frame_cache_helper_processes(tmp_path):
     """pipeline.FrameCache(processes=True): frames decoded by the helper processes (mcgaze_amd/_decode_worker.py, shared-memory ring) are
     the in-line decoder's pixels; a frame larger than a ring slot is decoded in line; a missing file raises where the frame is asked
