@@ -568,6 +568,64 @@ int mcg_preprocess_head_crops_nv12(mcg_stream s, const mcg_nv12_image_desc* imag
                                    float* dst, int pad_h, int pad_w, const float mean[3], const float stdinv[3], int to_rgb,
                                    const mcg_yuv_coef* coef);
 
+/* ---------------------------------------------------------------- annotated frames out (additions to ABI 18; nothing above changes)
+ * The last step of the reference's demo (MCGaze_demo/demo.ipynb, cell 5): for every head on every frame
+ *   cv2.arrowedLine(frame, centre, tip, (230, 253, 11), thickness=max(5, int(l * 0.01)))
+ * drawn on the device, IN PLACE, into packed BGR frames (mcg_draw_gaze_arrows) or into a decoder's NV12 surfaces (mcg_draw_gaze_arrows_nv12):
+ * the image tables are those of the head-crop entries, and the planes they name are WRITTEN (the const of their pointers notwithstanding),
+ * honouring each plane's pitch.  Two launches: a plan kernel (one thread per row, double, uncontracted) writes one mcg_arrow_desc per row,
+ * then a gather kernel over (image, pixel tile) walks the rows of each tile in ascending order and stores the covered pixels.
+ * ARROW PLAN, per row, from a head box x1 y1 x2 y2 and a gaze g0 g1 (f32, widened to double; int() truncates, // floors):
+ *   cx = int(x1 + x2) // 2;  cy = int(y1 + y2) // 2;  l = int(max(y2 - y1, x2 - x1) * length);  tip = (int(cx - l * g0), int(cy - l * g1))
+ *   t = max(min_thickness, int(l * thickness_ratio))             -- mcgaze_amd/harness.py::head_arrows' steps; the demo: 1.0, 5, 0.01
+ * HEAD STROKES, as OpenCV's published arrowedLine computes them (tip_length, the demo's default 0.1), restated without atan2, cos or sin so
+ * that two libms cannot disagree: pt1 = (cx, cy), pt2 = tip, dx = pt1.x - pt2.x, dy = pt1.y - pt2.y, k = tip_length * 0.7071067811865476
+ * (the double nearest sqrt(0.5)); the strokes start at
+ *   (rint(pt2.x + k * (dx - dy)), rint(pt2.y + k * (dx + dy)))   and   (rint(pt2.x + k * (dx + dy)), rint(pt2.y + k * (dy - dx)))
+ * rint rounding half to even, every product and every sum rounded on its own (no FMA).  An arrow is three segments of thickness t: the
+ * shaft pt1 -> pt2 and the two strokes into pt2 -- seg[0], seg[1], seg[2] of the descriptor, each (from, to) x (x, y).
+ * This is OpenCV's rule restated, not linked: parity with cv2's own rasteriser (a polygon fill with its own end caps) is NOT claimed and is
+ * not pinned on any machine this was built on.
+ * COVERAGE: the pixel with integer centre p belongs to segment a -> b iff its squared distance to the segment is at most (t / 2)^2 -- a
+ * capsule; a segment of no length gives a disc.  Exactly, in 64-bit integers: d = b - a, L = d . d, u = (p - a) . d;
+ *   u <= 0: 4 |p - a|^2 <= t^2;   u >= L: 4 |p - b|^2 <= t^2;   otherwise 4 (|p - a|^2 L - u^2) <= t^2 L
+ * The bound under which this is exact: every end point coordinate in [-8191, 8191], frames of at most 8192 pixels a side, t <= 255 -- then
+ * every difference is below 2^14, L and |u| below 2^29 and the left side below 2^60.
+ * FLAGS (int32 per row, the head-crop convention).  0: drawn -- zero covered pixels is allowed (an arrow wholly outside its frame).
+ * 2: an unusable row, and NOTHING is written for it: a box or gaze that is not finite, an image_of outside [0, num_images), an image
+ * without pixels (NV12: with an odd size) or larger than (max_h, max_w), an end point or thickness beyond the bound.  Its descriptor is
+ * zero but for image = -1 and flag = 2.
+ * OVERLAP: where arrows overlap the HIGHEST ROW INDEX wins, whatever the launch geometry or the scheduling (each pixel is written once, by
+ * one thread, after it has seen every row).
+ * NV12: the Y plane gets the colour's Y at every covered pixel; the chroma pair UV[y >> 1][2 (x >> 1) .. + 1] gets the colour's (U, V) iff
+ * ANY of its four luma pixels is covered -- by several rows: the highest of them.  The colour is given as (Y, U, V)
+ * (mcgaze_amd/pipeline.py::bgr_to_yuv); read back through the conversion above, every covered pixel shows exactly that triple's BGR.
+ *   images_dev   DEVICE table as for the head-crop entries, num_images in 1 .. 65535
+ *   max_h, max_w the largest frame of the table, each 1 .. 8192: the raster grid is sized from them (a larger image is flagged, not drawn)
+ *   boxes_dev    DEVICE f32 [n][4];  image_of_dev DEVICE int32 [n]
+ *   gaze_dev     DEVICE f32, row k at gaze_dev + k * gaze_stride (floats, >= 2): g0, g1 -- e.g. the [n][3] fused gaze as it is
+ *   length, thickness_ratio, tip_length: finite;  min_thickness in 1 .. 255
+ *   color        HOST uint8[3] (B, G, R; NV12: Y, U, V), used for every row when colors_dev is NULL;  colors_dev DEVICE uint8 [n][3], one per row
+ *   plan_out_dev DEVICE [n] descriptors (written);  flags_dev DEVICE int32 [n] or NULL
+ * No byte outside [0, h) x [0, w) of any plane is touched, padding included, for ANY box, gaze or index.  No allocation, no host sync,
+ * graph-capturable; at most 65535 rows per call; n = 0 returns MCG_OK without a launch.  Every wave of the raster grid reads the plan in
+ * n / 64 slices: made for the tens of heads of video frames. */
+typedef struct mcg_arrow_desc {
+  int seg[3][2][2];         /* shaft, stroke, stroke: (from, to) x (x, y) */
+  int thickness;
+  int x0, y0, x1, y1;       /* bounding box of the covered pixels clipped to the frame, half open; may be empty */
+  int image, flag;
+  int reserved;
+} mcg_arrow_desc;
+int mcg_draw_gaze_arrows(mcg_stream s, const mcg_image_desc* images_dev, int num_images, int max_h, int max_w, const float* boxes_dev,
+                         const float* gaze_dev, int gaze_stride, const int32_t* image_of_dev, int n, double length, int min_thickness,
+                         double thickness_ratio, double tip_length, const unsigned char* color, const unsigned char* colors_dev,
+                         mcg_arrow_desc* plan_out_dev, int32_t* flags_dev);
+int mcg_draw_gaze_arrows_nv12(mcg_stream s, const mcg_nv12_image_desc* images_dev, int num_images, int max_h, int max_w, const float* boxes_dev,
+                              const float* gaze_dev, int gaze_stride, const int32_t* image_of_dev, int n, double length, int min_thickness,
+                              double thickness_ratio, double tip_length, const unsigned char* yuv, const unsigned char* yuvs_dev,
+                              mcg_arrow_desc* plan_out_dev, int32_t* flags_dev);
+
 /* ---------------------------------------------------------------- measurement aids (bench.py)
  * While armed, every launch of the contraction kernel made by THIS engine is bracketed by a hipEvent pair on its launch stream.
  * mcg_engine_profile_stop synchronises, returns per-launch duration (ms), algorithmic FLOPs, algorithmic HBM bytes (inputs and

@@ -21,6 +21,7 @@ import numpy as np
 import torch
 
 from .engine import _upload_table
+from .pipeline import ARROW_COLOR
 
 CLUES = ('face', 'eyes', 'head')
 last_run_stats = {}       # run_annotation's frame-cache counters of the last call (tools/dataset_throughput.py prints them); trunk_frames of run_videos
@@ -655,8 +656,11 @@ def head_arrows(head_boxes, gaze):
     return np.stack([np.stack([cx, cy], axis=1), tip], axis=1).astype(np.int64)
 
 
+DRAW_FRAMES = 16                                       # frames per drawing call of run_head_video(draw=...)
+
+
 def run_head_video(engine, pipeline, frames, boxes_per_frame, max_len=100, batch_frames=448, expand=0.8, rgb=False, smooth=None, pixel_format='bgr',
-                   matrix='bt601'):
+                   matrix='bt601', draw=None):
     """Steps 3-4 of the demo from what its users hold -- the video's frames and one head box per person per frame -- to per-person gaze:
     segment_tracks (cell 1), the head windows cut, resized and normalised on the device (pipeline.head_crops: cell 4's crop arithmetic and
     ``cfg.data.test.pipeline[1:]``), run_tracks (cell 4's loop, batched), head_arrows (cell 5's end points).
@@ -673,7 +677,13 @@ def run_head_video(engine, pipeline, frames, boxes_per_frame, max_len=100, batch
     head_box [L,4] f32 (as the device read it), crop [L,4] = y0, x0, h, w of the window, arrow int [L,2,2].
     smooth: None, or the alpha in (0, 1] of the temporal filter (tools/calculate_mae_gaze360.py:16-29): every record gains ``fused_smooth``
     [L,3], the fused gaze filtered over the person's whole track (smooth_host: the track is on the host by then), and ``arrow`` is drawn
-    from it instead of from ``fused``."""
+    from it instead of from ``fused``.
+    draw: None (the return value above, untouched), True, or a dict of pipeline.draw_arrows' options (color, length, min_thickness,
+    thickness_ratio, tip_length, copy): cell 5's arrows are drawn on the device once the records exist, DRAW_FRAMES frames per call, from the
+    gaze ``arrow`` comes from (``fused``, or ``fused_smooth`` with smooth=) -- the drawn shaft ends are ``arrow`` -- and the return value is
+    (records, annotated): annotated[t] is frame t on the device in draw_arrows' form, for every t of boxes_per_frame, a frame without a head
+    unchanged.  Device frames are drawn into clones (copy=False in the dict: in place).  ``color`` is B, G, R whatever rgb= says.  In a
+    frame the people of a segment are drawn left to right: where two arrows overlap, the person further right wins."""
     smooth = check_smooth('run_head_video', smooth)
     segments = segment_tracks(boxes_per_frame)
     chunks = [(si, a, b, pi) for si, seg in enumerate(segments) for a, b in plan_track_chunks(len(seg['frame_id']), max_len)
@@ -718,7 +728,28 @@ def run_head_video(engine, pipeline, frames, boxes_per_frame, max_len=100, batch
                 rec['fused_smooth'] = smooth_host(rec['fused'], smooth)
             out.append(dict(id=(si, pi), **rec, frame_id=list(seg['frame_id']), head_box=head_box, crop=np.concatenate([c for _, c in got]),
                             arrow=head_arrows(person, rec['fused' if smooth is None else 'fused_smooth'])))
-    return out
+    if draw is None:
+        return out
+    opts = {'copy': True, **({} if draw is True else dict(draw))}
+    if rgb and pixel_format == 'bgr':                  # the frames hold R, G, B: the colour goes in in their order
+        opts['color'] = np.asarray(ARROW_COLOR if opts.get('color') is None else opts['color'])[..., ::-1]
+    rows = [[] for _ in boxes_per_frame]               # frame -> (box, gaze) of its heads, in record order
+    for r in out:
+        g = r['fused' if smooth is None else 'fused_smooth']
+        for j, t in enumerate(r['frame_id']):
+            rows[t].append((r['head_box'][j], g[j, :2]))
+    if opts.get('color') is not None and np.ndim(opts['color']) == 2:
+        raise ValueError('run_head_video(draw=...): color is one (B, G, R) triple')
+    annotated = []
+    for t0 in range(0, len(rows), DRAW_FRAMES):
+        part = rows[t0:t0 + DRAW_FRAMES]
+        image_of = np.asarray([k for k, heads in enumerate(part) for _ in heads], dtype=np.int32)
+        boxes = np.asarray([b for heads in part for b, _ in heads], dtype=np.float32).reshape(-1, 4)
+        gaze = np.asarray([g for heads in part for _, g in heads], dtype=np.float32).reshape(-1, 2)
+        imgs, _ = pipeline.draw_arrows([frames[t] for t in range(t0, t0 + len(part))], boxes, gaze, image_of, pixel_format=pixel_format,
+                                       matrix=matrix, device=engine.device, **opts)
+        annotated += imgs
+    return out, annotated
 
 
 def dump_results(records, config_path, json_path, out_dir='results'):

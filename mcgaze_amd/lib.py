@@ -35,7 +35,7 @@ EXPORTS = ['mcg_abi_version', 'mcg_build_id', 'mcg_last_error', 'mcg_device_info
            'mcg_deferred_pyramid_bytes', 'mcg_deferred_pyramid_levels', 'mcg_backbone_fpn_forward_deferred', 'mcg_decoder_forward_deferred',
            'mcg_stage_forward_ragged', 'mcg_decoder_forward_ragged', 'mcg_decoder_forward_deferred_ragged', 'mcg_clip_forward_ragged',
            'mcg_pyramid_scatter_rows', 'mcg_preprocess_head_crops', 'mcg_merge_windows', 'mcg_smooth_gaze', 'mcg_preprocess_frames_nv12',
-           'mcg_preprocess_head_crops_nv12']
+           'mcg_preprocess_head_crops_nv12', 'mcg_draw_gaze_arrows', 'mcg_draw_gaze_arrows_nv12']
 
 
 class ConvDesc(C.Structure):
@@ -82,6 +82,11 @@ class Nv12ImageDesc(C.Structure):
 
 class Nv12FrameDesc(C.Structure):
     _fields_ = FrameDesc._fields_ + [('uv', C.c_void_p), ('uv_pitch', C.c_int)]
+
+
+class ArrowDesc(C.Structure):
+    _fields_ = [('seg', C.c_int * 2 * 2 * 3), ('thickness', C.c_int), ('x0', C.c_int), ('y0', C.c_int), ('x1', C.c_int), ('y1', C.c_int),
+                ('image', C.c_int), ('flag', C.c_int), ('reserved', C.c_int)]
 
 
 class McgError(RuntimeError):
@@ -149,6 +154,9 @@ def load():
     lib.mcg_preprocess_head_crops.argtypes = [vp, vp, i, vp, vp, i, C.c_double, i, i, vp, vp, vp, vp, vp, i, i, C.POINTER(C.c_float), C.POINTER(C.c_float), i]
     lib.mcg_preprocess_frames_nv12.argtypes = lib.mcg_preprocess_frames.argtypes + [C.POINTER(YuvCoef)]
     lib.mcg_preprocess_head_crops_nv12.argtypes = lib.mcg_preprocess_head_crops.argtypes + [C.POINTER(YuvCoef)]
+    u8p = C.POINTER(C.c_ubyte)
+    lib.mcg_draw_gaze_arrows.argtypes = [vp, vp, i, i, i, vp, vp, i, vp, i, C.c_double, i, C.c_double, C.c_double, u8p, vp, vp, vp]
+    lib.mcg_draw_gaze_arrows_nv12.argtypes = lib.mcg_draw_gaze_arrows.argtypes
     lib.mcg_engine_set_option.argtypes = [vp, C.c_char_p, i]
     lib.mcg_engine_profile_start.argtypes = [vp, i]
     lib.mcg_engine_profile_stop.argtypes = [vp, C.POINTER(i), C.POINTER(C.c_float), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(i), C.POINTER(i), i]

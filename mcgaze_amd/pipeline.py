@@ -618,6 +618,183 @@ def nv12_to_bgr(y, uv, matrix='bt601'):
     return np.stack([sat8(yy + k['cub'] * u), sat8(yy + k['cvg'] * v + k['cug'] * u), sat8(yy + k['cvr'] * v)], axis=-1)
 
 
+def _yuv_to_bgr(yuv, k):
+    """(Y, U, V) integer arrays [..., 3] -> BGR [..., 3] int32 by nv12_to_bgr's arithmetic."""
+    yuv = np.asarray(yuv, dtype=np.int32)
+    u, v = yuv[..., 1] - 128, yuv[..., 2] - 128
+    yy = np.maximum(0, yuv[..., 0] - k['y_off']) * np.int32(k['cy']) + np.int32(1 << 19)
+    sat8 = lambda t: np.clip(t >> 20, 0, 255)
+    return np.stack([sat8(yy + k['cub'] * u), sat8(yy + k['cvg'] * v + k['cug'] * u), sat8(yy + k['cvr'] * v)], axis=-1)
+
+
+def bgr_to_yuv(color, matrix='bt601'):
+    """The (Y, U, V) an NV12 surface is drawn with so that it SHOWS the BGR colour ``color`` -> uint8 [3].  No new constants: the matrix of
+    ``YUV_COEF[matrix]`` (B = cy y + cub u, G = cy y + cug u + cvg v, R = cy y + cvr v with y = Y - y_off, u = U - 128, v = V - 128, each
+    coefficient / 2^20) is inverted numerically and the result rounded; among the triples within 2 of it in every component (and inside
+    [0, 255]) the one whose conversion by nv12_to_bgr's integer arithmetic has the smallest maximum channel error against ``color`` is taken,
+    ties going to the smallest (Y, U, V) in lexicographic order.  Runs once per colour, on the host."""
+    k = _yuv_coef(matrix)
+    c = np.asarray(color)
+    if c.shape != (3,) or c.dtype.kind not in 'iu' or c.min() < 0 or c.max() > 255:
+        raise ValueError(f'a colour is three integers in [0, 255] (B, G, R), got {color!r}')
+    c = c.astype(np.int64)
+    m = np.array([[k['cy'], k['cub'], 0], [k['cy'], k['cug'], k['cvg']], [k['cy'], 0, k['cvr']]], dtype=np.float64) / float(1 << 20)
+    centre = np.rint(np.linalg.solve(m, c.astype(np.float64)) + np.array([k['y_off'], 128.0, 128.0])).astype(np.int64)
+    grid = np.stack(np.meshgrid(*[np.arange(v - 2, v + 3) for v in centre], indexing='ij'), axis=-1).reshape(-1, 3)     # lexicographic order
+    grid = grid[((grid >= 0) & (grid <= 255)).all(axis=1)]
+    if not len(grid):                                            # (cannot happen for a colour in [0, 255]^3: its YUV is inside the nominal range)
+        raise ValueError(f'no (Y, U, V) near {centre.tolist()} for colour {color!r}')
+    err = np.abs(_yuv_to_bgr(grid, k) - c).max(axis=1)
+    return grid[int(np.argmin(err))].astype(np.uint8)            # argmin: the FIRST of the smallest, i.e. the lexicographically smallest
+
+
+ARROW_COLOR = (230, 253, 11)                                     # the demo's, BGR (MCGaze_demo/demo.ipynb, cell 5)
+ARROW_COORD, ARROW_SIDE = 8191, 8192                             # the bound under which the coverage test is exact in 64-bit integers
+_ARROW = np.dtype([('seg', np.int32, (3, 2, 2)), ('thickness', np.int32)] + [(f, np.int32) for f in ('x0', 'y0', 'x1', 'y1', 'image', 'flag', 'reserved')])
+assert _ARROW.itemsize == C.sizeof(L.ArrowDesc) and all(_ARROW.fields[n][1] == getattr(L.ArrowDesc, n).offset for n in _ARROW.names)
+_ARROW_WORDS = _ARROW.itemsize // 4
+
+
+def _arrow_params(length=1.0, min_thickness=5, thickness_ratio=0.01, tip_length=0.1):
+    """The arrow parameters, validated (ValueError) -> (length, min_thickness, thickness_ratio, tip_length); the defaults are the demo's."""
+    length, thickness_ratio, tip_length = float(length), float(thickness_ratio), float(tip_length)
+    if not all(np.isfinite(v) for v in (length, thickness_ratio, tip_length)):
+        raise ValueError('length, thickness_ratio and tip_length must be finite')
+    if int(min_thickness) != min_thickness or not 1 <= int(min_thickness) <= 255:
+        raise ValueError(f'min_thickness must be an integer in 1 .. 255, got {min_thickness!r}')
+    return length, int(min_thickness), thickness_ratio, tip_length
+
+
+def arrow_segments(boxes, gaze, **params):
+    """The arrow plan on the host (include/mcgaze_hip.h, "annotated frames out"; arrow_plan_kernel line for line): boxes [n,4] x1 y1 x2 y2, gaze
+    [n,>=2], both read as f32 and widened to double; params: length, min_thickness, thickness_ratio, tip_length (the demo's by default).
+    -> (seg int64 [n,3,2,2]: shaft, stroke, stroke x (from, to) x (x, y); thickness int64 [n]; flags int32 [n]).  seg[:, 0] is
+    harness.head_arrows of the same input.  Flag 2 (and a zero row): a box or gaze that is not finite, an end point outside [-8191, 8191] or a
+    thickness above 255."""
+    length, min_thickness, ratio, tip_length = _arrow_params(**params)
+    b = np.asarray(boxes, dtype=np.float32).astype(np.float64).reshape(-1, 4)
+    g = np.asarray(gaze, dtype=np.float32).astype(np.float64)
+    g = g.reshape(len(b), -1)[:, :2] if g.size else np.zeros((len(b), 2 if not len(b) else 0))
+    if g.shape[1] != 2:
+        raise ValueError(f'gaze must be [n, >= 2], got {np.shape(gaze)}')
+    ok = np.isfinite(b).all(axis=1) & np.isfinite(g).all(axis=1)
+    b, g = np.where(ok[:, None], b, 0.0), np.where(ok[:, None], g, 0.0)
+    inside = lambda *vs: np.logical_and.reduce([np.abs(v) <= ARROW_COORD for v in vs])
+    # numpy rounds every elementwise product and sum on its own: nothing is contracted, as in the kernel
+    cx, cy = np.floor(np.trunc(b[:, 0] + b[:, 2]) / 2.0), np.floor(np.trunc(b[:, 1] + b[:, 3]) / 2.0)
+    l = np.trunc(np.maximum(b[:, 3] - b[:, 1], b[:, 2] - b[:, 0]) * length)
+    tx, ty = np.trunc(cx - l * g[:, 0]), np.trunc(cy - l * g[:, 1])
+    t = np.maximum(float(min_thickness), np.trunc(l * ratio))
+    ok &= inside(cx, cy, tx, ty) & (t <= 255.0)
+    cx, cy, tx, ty, t = (np.where(ok, v, 0.0) for v in (cx, cy, tx, ty, t))
+    dx, dy = cx - tx, cy - ty
+    k = tip_length * 0.7071067811865476
+    ax, ay = np.rint(tx + k * (dx - dy)), np.rint(ty + k * (dx + dy))          # np.rint rounds half to even
+    bx, by = np.rint(tx + k * (dx + dy)), np.rint(ty + k * (dy - dx))
+    ok &= inside(ax, ay, bx, by)
+    tip = np.stack([tx, ty], axis=1)
+    seg = np.stack([np.stack([np.stack([px, py], axis=1), tip], axis=1) for px, py in ((cx, cy), (ax, ay), (bx, by))], axis=1)
+    seg, t = np.where(ok[:, None, None, None], seg, 0.0), np.where(ok, t, 0.0)
+    return seg.astype(np.int64), t.astype(np.int64), np.where(ok, 0, 2).astype(np.int32)
+
+
+def segment_coverage(h, w, a, b, t, y0=0, x0=0):
+    """bool [h,w]: which pixels (integer centres (x0 + column, y0 + row)) belong to the segment a -> b (x, y each) of thickness t, i.e. lie
+    within t / 2 of it -- a capsule, a disc for a segment of no length -- exactly, in 64-bit integers (the kernel's test, include/mcgaze_hip.h)."""
+    py, px = np.mgrid[y0:y0 + h, x0:x0 + w].astype(np.int64)
+    ax, ay, bx, by, tt = int(a[0]), int(a[1]), int(b[0]), int(b[1]), int(t) * int(t)
+    dx, dy, qx, qy = bx - ax, by - ay, px - ax, py - ay
+    L, u = dx * dx + dy * dy, qx * dx + qy * dy
+    qq, rr = qx * qx + qy * qy, (px - bx) ** 2 + (py - by) ** 2
+    return np.where(u <= 0, 4 * qq <= tt, np.where(u >= L, 4 * rr <= tt, 4 * (qq * L - u * u) <= tt * L))
+
+
+def _arrow_colors(color, n, nv12, matrix):
+    """-> (one uint8 [3] or None, per-row uint8 [n,3] or None), as the entries take them: B, G, R, or with nv12 the (Y, U, V) of bgr_to_yuv."""
+    c = np.asarray(ARROW_COLOR if color is None else _host_array(color))
+    if c.dtype.kind not in 'iu' or c.shape not in ((3,), (n, 3)) or (c.size and (c.min() < 0 or c.max() > 255)):
+        raise ValueError(f'color must be one (B, G, R) triple or one per row, [{n}, 3], integers in [0, 255]; got {c.dtype} {c.shape}')
+    c = c.astype(np.uint8)
+    if nv12:
+        if c.ndim == 1:
+            c = bgr_to_yuv(c, matrix)
+        else:
+            uniq, inverse = np.unique(c, axis=0, return_inverse=True)
+            c = np.stack([bgr_to_yuv(v, matrix) for v in uniq]).reshape(-1, 3)[inverse.reshape(-1)] if n else c
+    return (c, None) if c.ndim == 1 else (None, np.ascontiguousarray(c))
+
+
+def _arrow_rows(boxes, gaze, image_of, sizes, strict, **params):
+    """Plan and flags of n rows on the host -> (seg, thickness, flags): arrow_segments plus what depends on the frames -- an image_of outside
+    ``sizes`` ([(h, w), ...]) and an image larger than 8192 a side are flag 2.  strict: ValueError instead, naming the first such row."""
+    seg, t, flags = arrow_segments(boxes, gaze, **params)
+    image_of = np.asarray(image_of).reshape(-1)
+    if image_of.dtype.kind not in 'iu':
+        raise TypeError(f'image_of must hold integers, got {image_of.dtype}')
+    if len(image_of) != len(flags):
+        raise ValueError(f'boxes {np.shape(boxes)}, gaze {np.shape(gaze)} and image_of {image_of.shape} must be [n,4], [n,>=2] and [n]')
+    hw = np.asarray(sizes, dtype=np.int64).reshape(-1, 2)
+    known = (image_of >= 0) & (image_of < len(hw))
+    bad = ~known
+    bad[known] = (hw[image_of[known]] > ARROW_SIDE).any(axis=1) | (hw[image_of[known]] <= 0).any(axis=1)
+    flags = np.where(bad, 2, flags).astype(np.int32)
+    if strict and flags.any():
+        k = int(np.flatnonzero(flags)[0])
+        raise ValueError(f'arrow {k} cannot be drawn: box {np.asarray(boxes).reshape(-1, 4)[k].tolist()}, gaze {np.asarray(gaze).reshape(len(flags), -1)[k, :2].tolist()}, '
+                         f'image_of {int(image_of[k])} of {len(hw)} -- not finite, outside the image table, or an end point beyond +-{ARROW_COORD} '
+                         f'/ a thickness beyond 255')
+    seg[flags != 0], t[flags != 0] = 0, 0
+    return seg, t, flags
+
+
+def draw_arrows_host(frames, boxes, gaze, image_of=None, color=None, pixel_format='bgr', matrix='bt601', strict=False, **params):
+    """The demo's arrows (MCGaze_demo/demo.ipynb, cell 5) drawn with numpy: what DevicePipeline.draw_arrows writes on the device, bit for bit
+    (include/mcgaze_hip.h, "annotated frames out": the plan, the capsule coverage in 64-bit integers, the highest row winning an overlap, the
+    NV12 chroma rule).  For checks and for users without a GPU.
+
+    frames: one HxWx3 uint8 frame or a list of them; pixel_format='nv12': one surface -- a (y, uv) tuple or a [3H/2, W] array -- or a list of
+    those.  boxes [n,4], gaze [n,>=2], image_of [n] (None: every row draws into frame 0), color: one (B, G, R) triple (None: the demo's
+    (230, 253, 11)) or one per row; params: length, min_thickness, thickness_ratio, tip_length.
+    -> (annotated COPIES in the form given -- NV12 frames as (y [H,W], uv [H/2,W]) pairs --, flags int32 [n]).  A row flagged 2 changes no
+    byte; strict=True raises ValueError for it instead (what draw_arrows does for host tables)."""
+    if pixel_format not in ('bgr', 'nv12'):
+        raise ValueError(f"pixel_format must be 'bgr' or 'nv12', got {pixel_format!r}")
+    nv12 = pixel_format == 'nv12'
+    _yuv_coef(matrix)
+    single = not isinstance(frames, list)
+    frames = [frames] if single else frames
+    if nv12:
+        out = [tuple(np.array(p) for p in _nv12_planes(k, f)[:2]) for k, f in enumerate(frames)]
+        sizes = [y.shape for y, _ in out]
+    else:
+        out = [np.array(f) for f in frames]
+        for k, a in enumerate(out):
+            if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3 or a.size == 0:
+                raise TypeError(f'frame {k}: frames must be HxWx3 uint8 arrays, got {a.dtype} {a.shape}')
+        sizes = [a.shape[:2] for a in out]
+    n = len(np.asarray(_host_array(boxes)).reshape(-1, 4))
+    image_of = np.zeros(n, dtype=np.int32) if image_of is None else _host_array(image_of)
+    seg, t, flags = _arrow_rows(_host_array(boxes), _host_array(gaze), image_of, sizes, strict, **params)
+    one, per_row = _arrow_colors(color, n, nv12, matrix)
+    for k in np.flatnonzero(flags == 0):                         # ascending: a later row overwrites an earlier one
+        h, w = sizes[int(image_of[k])]
+        r = (int(t[k]) + 1) // 2
+        x0, y0 = max(int(seg[k, :, :, 0].min()) - r, 0), max(int(seg[k, :, :, 1].min()) - r, 0)
+        x1, y1 = min(int(seg[k, :, :, 0].max()) + r + 1, w), min(int(seg[k, :, :, 1].max()) + r + 1, h)
+        if x1 <= x0 or y1 <= y0:
+            continue
+        mask = np.zeros((h, w), dtype=bool)
+        mask[y0:y1, x0:x1] = np.logical_or.reduce([segment_coverage(y1 - y0, x1 - x0, s[0], s[1], t[k], y0, x0) for s in seg[k]])
+        c = one if per_row is None else per_row[k]
+        if nv12:
+            y, uv = out[int(image_of[k])]
+            y[mask] = c[0]
+            uv.reshape(h // 2, w // 2, 2)[mask.reshape(h // 2, 2, w // 2, 2).any(axis=(1, 3))] = c[1:]
+        else:
+            out[int(image_of[k])][mask] = c
+    return (out[0] if single else out), flags
+
+
 class _NoDraw:
     """The generator behind head_crop_geometry's planning pass: RandomFlip(0.0)'s uniform decides nothing and is not drawn from the caller's."""
 
@@ -740,10 +917,10 @@ class _StagingRing:
         return st
 
 
-def _head_crop_tables(images, dev, planes, boxes, image_of, expand):
-    """The host side of head_crops -> (table, parts, boxes, image_of, on_device, n).  table: one _IMAGE record per frame (_NV12_IMAGE with ``planes``,
-    the frames as _nv12_planes returns them); parts: (frame, field of its record, bytes) of every HOST frame -- it gets its address once it is staged.
-    Host box and index tables come back in the types the device reads (f32, int32) and are CHECKED here; device tables (on_device) are not read back."""
+def _image_table(images, dev, planes):
+    """-> (table, parts).  table: one _IMAGE record per frame (_NV12_IMAGE with ``planes``, the frames as _nv12_planes returns them); parts: (frame,
+    field of its record, bytes) of every HOST frame -- it gets its address once it is staged.  head_crops reads the frames it names, draw_arrows
+    writes them."""
     table, parts = np.zeros(len(images), dtype=_IMAGE if planes is None else _NV12_IMAGE), []
     for k, im in enumerate(images):
         if planes is not None:
@@ -764,6 +941,13 @@ def _head_crop_tables(images, dev, planes, boxes, image_of, expand):
                 raise TypeError(f'frame {k}: frames must be HxWx3 uint8 arrays, got {a.dtype} {a.shape}')
             parts.append((k, 'src', a.reshape(-1)))
             table[k] = (0, a.shape[0], a.shape[1], 3 * a.shape[1])
+    return table, parts
+
+
+def _head_crop_tables(images, dev, planes, boxes, image_of, expand):
+    """The host side of head_crops -> (table, parts, boxes, image_of, on_device, n): _image_table's frame table, and the box and index tables.
+    Host tables come back in the types the device reads (f32, int32) and are CHECKED here; device tables (on_device) are not read back."""
+    table, parts = _image_table(images, dev, planes)
     on_device = [isinstance(t, torch.Tensor) and t.is_cuda for t in (boxes, image_of)]
     if not on_device[0]:
         boxes = np.ascontiguousarray(_host_array(boxes), dtype=np.float32).reshape(-1, 4)     # f32 is what the device reads: the checks see the same boxes
@@ -804,7 +988,20 @@ class DevicePipeline:
         self.collect = self.transforms[-1]
         self._planners = [t.plan for t in self.transforms if type(t) not in (LoadImageFromFile, ImageToTensor, Collect)]   # the rest plan nothing
         self._ring = _StagingRing(self.STAGES)                    # run_many and head_crops upload through the same stages
-        self._image_tables = collections.OrderedDict()            # head_crops: (device, frame table bytes) -> that table on the device
+        self._image_tables = collections.OrderedDict()            # head_crops, draw_arrows: (device, frame table bytes) -> that table on the device
+
+    def _cached_image_table(self, table, dev, nv12):
+        """The frame table ``table`` on the device: uploaded the first time these frames are seen, then found again (least recently used of
+        IMAGE_TABLES goes) -- what lets head_crops and draw_arrows on device frames and tables touch the host nowhere."""
+        key = (dev.index, table.tobytes()) + (('nv12',) if nv12 else ())
+        tdev = self._image_tables.get(key)
+        if tdev is None:
+            tdev = self._image_tables[key] = torch.from_numpy(table.view(np.uint8).reshape(-1).copy()).to(dev)
+            while len(self._image_tables) > self.IMAGE_TABLES:
+                self._image_tables.popitem(last=False)
+        else:
+            self._image_tables.move_to_end(key)
+        return tdev
 
     def plan(self, shape, rng=np.random, filename=None, ori_filename=None):
         p = FramePlan(shape, filename, ori_filename)
@@ -992,14 +1189,7 @@ class DevicePipeline:
                     image_of_ptr = image_of.data_ptr() if on_device[1] else at.pop(0)
                 else:
                     # nothing comes from the host but the frame table, and that only the first time these frames are seen: no stage is taken
-                    key = (dev.index, table.tobytes()) + (('nv12',) if nv12 else ())
-                    tdev = self._image_tables.get(key)
-                    if tdev is None:
-                        tdev = self._image_tables[key] = torch.from_numpy(table.view(np.uint8).reshape(-1).copy()).to(dev)
-                        while len(self._image_tables) > self.IMAGE_TABLES:
-                            self._image_tables.popitem(last=False)
-                    else:
-                        self._image_tables.move_to_end(key)
+                    tdev = self._cached_image_table(table, dev, nv12)
                     images_ptr, boxes_ptr, image_of_ptr = tdev.data_ptr(), boxes.data_ptr(), image_of.data_ptr()
                 img, scale_factor = new(n, 3, pad_h, pad_w, dtype=torch.float32), new(n, 4, dtype=torch.float32)
                 desc, img_hw, flags = new(n, _NV12_DESC_WORDS if nv12 else _DESC_WORDS), new(n, 2), new(n)
@@ -1011,6 +1201,133 @@ class DevicePipeline:
                 if st is not None:
                     st.read_by(main)
         return img, img_hw, scale_factor, desc[:, _CROP_WORD:_CROP_WORD + 4], flags
+
+    def draw_arrows(self, images, boxes, gaze, image_of, color=None, pixel_format='bgr', matrix='bt601', copy=False, device='cuda:0', stream=None,
+                    **params):
+        """The demo's last step (MCGaze_demo/demo.ipynb, cell 5) on the device: one arrow per head, from the head's centre along its gaze, drawn
+        into the frames (mcg_draw_gaze_arrows / mcg_draw_gaze_arrows_nv12: a plan launch and a raster launch) -- ``draw_arrows_host`` bit for bit.
+
+        images: as for head_crops -- HxWx3 uint8 frames, or with pixel_format='nv12' (y, uv) pairs / [3H/2, W] surfaces; numpy arrays or CUDA
+        tensors.  A CUDA frame is drawn IN PLACE (copy=True: into a packed clone) and handed back as it was given; a numpy frame goes up through the
+        staging ring into a fresh device tensor (NV12: one [3H/2, W] surface, handed back as its (y [H,W], uv [H/2,W]) views), which is drawn into.
+        boxes [n,4] x1 y1 x2 y2, gaze [n,>=2] (only g0, g1 are read), image_of [n]: numpy arrays or device tensors; an f32 device gaze with packed
+        rows -- the [n,3] ``fused`` of a results='device' stream -- is read where it is, its row stride taken from the tensor.
+        color: one (B, G, R) triple (None: the demo's (230, 253, 11)) or one per row, [n,3], on the host; for NV12 each is converted once by
+        ``bgr_to_yuv(color, matrix)``.  params: length, min_thickness, thickness_ratio, tip_length (the demo's 1.0, 5, 0.01, 0.1).
+        Where arrows overlap the highest row wins.  Host tables are checked before anything is launched (ValueError: an image_of out of range, a
+        box or gaze that is not finite, an end point beyond +-8191 or a thickness beyond 255; a frame larger than 8192 a side); device tables are
+        not read back -- such rows come back with flag 2 and write nothing.  TypeError / ValueError for frames as in head_crops.  With device
+        frames drawn in place, device tables and one colour the call touches the host nowhere once a first call has uploaded the frame table (the
+        cache head_crops keeps): it can be captured in a graph.
+        -> (images on the device, in order; flags [n] int32 on the device: 0 drawn -- possibly no pixel --, 2 unusable)."""
+        lib = L.load()
+        if pixel_format not in ('bgr', 'nv12'):
+            raise ValueError(f"pixel_format must be 'bgr' or 'nv12', got {pixel_format!r}")
+        _yuv_coef(matrix)
+        length, min_thickness, ratio, tip_length = _arrow_params(**params)
+        nv12 = pixel_format == 'nv12'
+        entry = lib.mcg_draw_gaze_arrows_nv12 if nv12 else lib.mcg_draw_gaze_arrows
+        dev = _device(device)
+        images = list(images)
+        planes = [_nv12_planes(k, im, dev) for k, im in enumerate(images)] if nv12 else None
+        dev = _device(dev, entry.__name__)
+        if not len(images):
+            raise ValueError('draw_arrows: no frames')
+        table, _ = _image_table(images, dev, planes)              # every frame is checked before the first clone or upload
+        on_device = [isinstance(t, torch.Tensor) and t.is_cuda for t in (boxes, gaze, image_of)]
+        if not on_device[0]:
+            boxes = np.ascontiguousarray(_host_array(boxes), dtype=np.float32).reshape(-1, 4)
+        n = int(boxes.shape[0])
+        if not on_device[1]:
+            gaze = np.ascontiguousarray(_host_array(gaze), dtype=np.float32)
+            gaze = np.zeros((0, 2), np.float32) if n == 0 and gaze.size == 0 else np.ascontiguousarray(gaze[:, :2]) if gaze.ndim == 2 else gaze
+        if not on_device[2]:
+            image_of = np.ascontiguousarray(_host_array(image_of)).reshape(-1)
+            if image_of.dtype.kind not in 'iu':
+                raise TypeError(f'image_of must hold integers, got {image_of.dtype}')
+            if len(image_of) and (image_of.min() < 0 or image_of.max() >= len(images)):
+                raise ValueError(f'image_of must lie in [0, {len(images)}), got [{image_of.min()}, {image_of.max()}]')
+            image_of = image_of.astype(np.int32)
+        if tuple(boxes.shape) != (n, 4) or gaze.ndim != 2 or gaze.shape[0] != n or gaze.shape[1] < 2 or tuple(image_of.shape) != (n,):
+            raise ValueError(f'draw_arrows: boxes {tuple(boxes.shape)}, gaze {tuple(gaze.shape)} and image_of {tuple(image_of.shape)} must be [n,4], [n,>=2] and [n]')
+        if n > 65535:
+            raise ValueError(f'draw_arrows: at most 65535 arrows per call (got {n})')
+        for name, t, there in (('box', boxes, on_device[0]), ('gaze', gaze, on_device[1])):
+            if not there and not np.isfinite(t).all():
+                raise ValueError(f'draw_arrows: {name} {int(np.flatnonzero(~np.isfinite(t).all(axis=1))[0])} is not finite')
+        one, per_row = _arrow_colors(color, n, nv12, matrix)
+        with torch.cuda.device(dev):
+            main = _caller_stream(stream, dev)
+            with torch.cuda.stream(main):
+                # where the arrows go: a device frame itself (or its clone), a fresh device tensor for every host frame
+                out = []
+                for k, im in enumerate(images):
+                    if nv12 and not planes[k][2]:
+                        h, w = planes[k][0].shape
+                        s = torch.empty(h * 3 // 2, w, dtype=torch.uint8, device=dev)
+                        out.append((s[:h], s[h:]))
+                    elif not nv12 and not isinstance(im, torch.Tensor):
+                        out.append(torch.empty(np.shape(im), dtype=torch.uint8, device=dev))
+                    elif copy:
+                        clone = lambda t: t.clone(memory_format=torch.contiguous_format)
+                        out.append(tuple(clone(t) for t in im) if isinstance(im, (tuple, list)) else clone(im))
+                    else:
+                        out.append(im)
+                in_place = all(o is im for o, im in zip(out, images))
+                if not in_place:                                  # the table of the tensors that are drawn into
+                    table, _ = _image_table(out, dev, [_nv12_planes(k, o, dev) for k, o in enumerate(out)] if nv12 else None)
+                if table['h'].max() > ARROW_SIDE or table['w'].max() > ARROW_SIDE:
+                    raise ValueError(f'draw_arrows: frames of at most {ARROW_SIDE} pixels a side, got {int(table["h"].max())} x {int(table["w"].max())}')
+                if not any(on_device[:2]) and n:
+                    _arrow_rows(boxes, gaze, image_of if not on_device[2] else np.zeros(n, np.int32),
+                                [(int(r['h']), int(r['w'])) for r in table], True, length=length, min_thickness=min_thickness,
+                                thickness_ratio=ratio, tip_length=tip_length)
+                boxes = boxes.to(dev, torch.float32).contiguous() if on_device[0] else boxes
+                image_of = image_of.to(dev, torch.int32).contiguous() if on_device[2] else image_of
+                if on_device[1]:
+                    if not (gaze.device == dev and gaze.dtype == torch.float32 and gaze.stride(1) == 1 and (n <= 1 or gaze.stride(0) >= 2)):
+                        gaze = gaze.to(dev, torch.float32).contiguous()
+                    gaze_stride = int(gaze.stride(0)) if n > 1 else int(gaze.shape[1])
+                else:
+                    gaze_stride = 2
+                # the bytes of the host frames (frame, the device tensor they belong in, bytes), in image order
+                if nv12:
+                    pixels = [(o[j], a.reshape(-1)) for o, p in zip(out, planes) if not p[2] for j, a in enumerate(p[:2])]
+                else:
+                    pixels = [(o, np.ascontiguousarray(im).reshape(-1)) for o, im in zip(out, images) if not isinstance(im, torch.Tensor)]
+                tables = [t.view(np.uint8).reshape(-1) for t, d in zip((boxes, gaze, image_of), on_device) if not d] + ([] if per_row is None else [per_row.reshape(-1)])
+                st = None
+                if pixels or tables or not in_place:
+                    # everything that comes from the host travels in ONE pinned staging buffer and one copy: pixels, frame table, host tables
+                    blobs = [a for _, a in pixels] + [table.view(np.uint8).reshape(-1)] + tables
+                    offs, total = _layout([b.size for b in blobs])
+                    st = self._ring.take(total, dev, main)
+                    for b, o in zip(blobs, offs):
+                        st.host[o:o + b.size] = b
+                    st.send(total)
+                    for (dst, a), o in zip(pixels, offs):          # out of the stage (the next calls reuse it) into the tensor handed back
+                        dst.copy_(st.dev[o:o + a.size].view(dst.shape))
+                    at = [st.base + o for o in offs[len(pixels):]]
+                    images_ptr = at.pop(0)
+                    boxes_ptr = boxes.data_ptr() if on_device[0] else at.pop(0)
+                    gaze_ptr = gaze.data_ptr() if on_device[1] else at.pop(0)
+                    image_of_ptr = image_of.data_ptr() if on_device[2] else at.pop(0)
+                    colors_ptr = None if per_row is None else at.pop(0)
+                else:
+                    # device frames drawn in place, device tables, one colour: only the frame table, and only the first time the frames are seen
+                    tdev = self._cached_image_table(table, dev, nv12)
+                    images_ptr, boxes_ptr, gaze_ptr, image_of_ptr, colors_ptr = tdev.data_ptr(), boxes.data_ptr(), gaze.data_ptr(), image_of.data_ptr(), None
+                flags = torch.empty(n, dtype=torch.int32, device=dev)
+                if n:
+                    plan = torch.empty(n, _ARROW_WORDS, dtype=torch.int32, device=dev)
+                    vp = C.c_void_p
+                    L.check(entry(vp(main.cuda_stream), vp(images_ptr), len(out), int(table['h'].max()), int(table['w'].max()), vp(boxes_ptr), vp(gaze_ptr),
+                                  gaze_stride, vp(image_of_ptr), n, length, min_thickness, ratio, tip_length,
+                                  None if one is None else (C.c_ubyte * 3)(*[int(v) for v in one]), vp(colors_ptr), vp(plan.data_ptr()),
+                                  vp(flags.data_ptr())), entry.__name__)
+                if st is not None:
+                    st.read_by(main)
+        return out, flags
 
 
 def _host_array(t):

@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
-"""Steps 3 - 4 of the reference's demo (MCGaze_demo/README.md; demo.ipynb, cells 1 - 5) without the drawing: a directory of video frames
-and the head detector's label files in, per-person per-frame gaze out.
+"""Steps 3 - 5 of the reference's demo (MCGaze_demo/README.md; demo.ipynb, cells 1 - 5): a directory of video frames and the head detector's
+label files in, per-person per-frame gaze out -- and, with --draw, the frames with cell 5's arrows drawn on the device.
 
 usage: demo_video.py FRAMES_DIR LABELS_DIR CONFIG CHECKPOINT --out gaze.json [--precision f16x3] [--device cuda:0] [--max-len 100]
-                     [--batch-frames 448] [--head-class 1] [--ext jpg] [--smooth ALPHA] [--nv12 WxH FILE] [--matrix bt601]
+                     [--batch-frames 448] [--head-class 1] [--ext jpg] [--smooth ALPHA] [--nv12 WxH FILE] [--matrix bt601] [--draw OUT]
+                     [--color B,G,R]
 
 FRAMES_DIR holds 0.<ext>, 1.<ext>, ... (the demo's `frames/`), LABELS_DIR holds 0.txt, 1.txt, ... with lines `class x1 y1 x2 y2` in pixels
 (the demo's `result/labels/`); a frame without a label file shows no head.  CONFIG is the L2CS config, whose test pipeline the demo runs
@@ -14,7 +15,11 @@ pixels of the head window, rescale=True), scores and gazes of harness.run_tracks
 uses 0.6, tools/calculate_mae_gaze360.py:16-29) adds `gaze_smooth`, the fused gaze filtered over each track, and draws `arrow` from it.
 --nv12 WxH FILE: the frames come from a raw NV12 video instead (`ffmpeg -i in.mp4 -pix_fmt nv12 -f rawvideo FILE`: per frame H rows of Y, then
 H/2 rows of interleaved U, V, W bytes each), read frame by frame with numpy and handed to the device as they are; FRAMES_DIR is then `-`.
---matrix names the YUV -> RGB coefficients, bt601 or bt709 (limited range; HD video is usually bt709).  The records are the same."""
+--matrix names the YUV -> RGB coefficients, bt601 or bt709 (limited range; HD video is usually bt709).  The records are the same.
+--draw OUT: the arrows of cell 5 are drawn into every frame on the device (harness.run_head_video(draw=...), from the gaze `arrow` comes
+from) and the annotated frames written into the directory OUT with numpy alone: 0.ppm, 1.ppm, ... (binary PPM, RGB), or with --nv12 ONE raw
+NV12 file OUT/annotated.nv12 (`ffmpeg -f rawvideo -pix_fmt nv12 -s WxH -i OUT/annotated.nv12 out.mp4` encodes it).  --color B,G,R sets
+the arrows' colour (default: the demo's 230,253,11)."""
 import argparse
 import json
 import os
@@ -70,6 +75,32 @@ def parse_size(text):
     return int(w), int(h)
 
 
+def parse_color(text):
+    """'230,253,11' -> (230, 253, 11)"""
+    v = text.split(',')
+    if len(v) != 3 or not all(t.strip().isdigit() and int(t) <= 255 for t in v):
+        raise ValueError(f'expected B,G,R with each in 0..255, got {text!r}')
+    return tuple(int(t) for t in v)
+
+
+def write_annotated(out_dir, annotated, nv12):
+    """The annotated frames of run_head_video(draw=...) -> files, with numpy alone.  Packed frames (RGB: the frames were loaded in the decoder's
+    order) become binary PPM files 0.ppm, 1.ppm, ...; NV12 surfaces are appended to ONE raw file, annotated.nv12 (H rows of Y, then H/2 rows
+    of U, V per frame -- what `ffmpeg -f rawvideo -pix_fmt nv12` reads)."""
+    os.makedirs(out_dir, exist_ok=True)
+    if nv12:
+        with open(os.path.join(out_dir, 'annotated.nv12'), 'wb') as f:
+            for y, uv in annotated:
+                f.write(np.ascontiguousarray(y.cpu().numpy()).tobytes())
+                f.write(np.ascontiguousarray(uv.cpu().numpy()).tobytes())
+        return
+    for t, im in enumerate(annotated):
+        rgb = np.ascontiguousarray(im.cpu().numpy())
+        with open(os.path.join(out_dir, f'{t}.ppm'), 'wb') as f:
+            f.write(b'P6\n%d %d\n255\n' % (rgb.shape[1], rgb.shape[0]))
+            f.write(rgb.tobytes())
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
     ap.add_argument('frames_dir')
@@ -86,7 +117,12 @@ def main(argv=None):
     ap.add_argument('--smooth', type=float, default=None, metavar='ALPHA', help='temporal filter of the reference\'s metric, alpha in (0, 1]')
     ap.add_argument('--nv12', nargs=2, default=None, metavar=('WxH', 'FILE'), help='read the frames from a raw NV12 video (FRAMES_DIR is then -)')
     ap.add_argument('--matrix', default='bt601', choices=['bt601', 'bt709'], help='YUV -> RGB coefficients of --nv12')
+    ap.add_argument('--draw', default=None, metavar='OUT', help='write the frames with the gaze arrows drawn into this directory')
+    ap.add_argument('--color', default=None, metavar='B,G,R', help='colour of the arrows of --draw')
     a = ap.parse_args(argv)
+    draw = None
+    if a.draw is not None:
+        draw = {} if a.color is None else dict(color=parse_color(a.color))
     if a.nv12 is not None:
         frames = Nv12File(a.nv12[1], *parse_size(a.nv12[0]))
         n = len(frames)
@@ -101,7 +137,10 @@ def main(argv=None):
     model = init_detector(a.config, a.checkpoint, device=a.device, precision=a.precision)
     pipe = DevicePipeline(model.cfg.data.test.pipeline)
     res = harness.run_head_video(model.engine(), pipe, frames, per_frame, max_len=a.max_len, batch_frames=a.batch_frames, rgb=True,
-                                 smooth=a.smooth, pixel_format='bgr' if a.nv12 is None else 'nv12', matrix=a.matrix)
+                                 smooth=a.smooth, pixel_format='bgr' if a.nv12 is None else 'nv12', matrix=a.matrix, draw=draw)
+    if draw is not None:
+        res, annotated = res
+        write_annotated(a.draw, annotated, a.nv12 is not None)
     out = [dict(segment=r['id'][0], person=r['id'][1], frame_id=r['frame_id'], head_box=r['head_box'].tolist(), crop=r['crop'].tolist(),
                 gaze=r['fused'].tolist(), arrow=r['arrow'].tolist(), det=r['det'].tolist(), others=r['others'].tolist(),
                 **({} if a.smooth is None else dict(gaze_smooth=r['fused_smooth'].tolist()))) for r in res]
