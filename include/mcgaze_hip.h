@@ -40,6 +40,12 @@ enum { MCG_OK = 0, MCG_ERR_ARG = 1, MCG_ERR_HIP = 2, MCG_ERR_UNSUPPORTED = 3, MC
  * element like f32) -- the f32 activations are split the same way in registers (round toward zero,
  * x - hi exact), and each product runs as three fp16 MFMAs (lo.hi + hi.lo + hi.hi) with f32 accumulation.  Operands beyond
  * +-65504 saturate per half (the reference's activations are orders of magnitude below); parts below 6e-8 flush to zero.
+ * The 22-bit figure is the TRUNK's: its matrices arrive pre-scaled by a power of two (mcg_conv_weights.wscale).  The DECODER's matrices
+ * (mcg_stage_forward, mcg_gaze_head) are NOT pre-scaled and take no descale factor, and DynamicConv's two products split data on both sides
+ * (theta = dynamic_layer's output, and the RoI features).  What a stage keeps, measured against float64 as a fraction of the output's
+ * scale (tests/test_gpu_decoder.py): theta and RoI features of magnitude 1: 2e-6; RoI features x 2^-6: 2e-6, x 2^-10:
+ * 7e-6 (the format's own figure: subnormal low halves are kept, not flushed); theta x 2^-6 / 2^-10 reached by scaling dynamic_layer's
+ * weights: 2e-5 / 2.5e-4, of which 2e-6 / 2e-5 is the DynamicConv products' and the rest the unscaled packing of dynamic_layer.weight.
  * Measured: 1e-5 rad on (yaw, pitch) against the reference (north_star: 1e-3), within a factor 2 of the MCG_F32 engine. */
 /* MCG_F16 (round 6, ABI 13): the 16-bit throughput mode in fp16 -- activations and weights stored as fp16 (11 significant bits instead of
  * bf16's 8; range +-65504), v_mfma_f32_32x32x16_f16, f32 accumulate, f32 LayerNorm / softmax / boxes.  Every layout, kernel and workspace size

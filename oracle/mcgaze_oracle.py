@@ -216,12 +216,31 @@ def _ln(sd, p, x):
     return F.layer_norm(x, (x.shape[-1],), sd[p + '.weight'], sd[p + '.bias'], 1e-5)
 
 
-def mha_self(sd, p, x, num_heads=8):
+def _linear(x, w, b=None, site=None):
+    """The default ``linear`` hook: F.linear, the site name unused."""
+    return F.linear(x, w, b)
+
+
+def _bmm(a, b, site=None):
+    """The default ``bmm`` hook: torch.bmm, the site name unused."""
+    return torch.bmm(a, b)
+
+
+# Contraction hooks.  ``stqi_stage``, ``dynamic_conv`` and ``mha_self`` take ``linear(x, w, b, site)`` and ``bmm(a, b, site)``: every
+# weight contraction of a stage goes through ``linear``, the two DynamicConv products (both operands are data) through ``bmm``, each
+# with the name of its site -- 'in_proj', 'out_proj', 'dynamic_layer', 'dyn_in', 'dyn_out', 'fc_layer', 'ffn1', 'ffn2', 'cls_fc', 'reg_fc'.
+# A test substitutes a model of a number format at the sites it stresses (tests/decoder_cases.py); the defaults are F.linear and
+# torch.bmm, and the functions run in float64 when the state dict and the inputs are double.  The attention core's q.k and a.v products
+# and the per-clue output heads are not contractions of the split format (attn_core_kernel, heads_kernel: plain f32) and carry no hook.
+SITES = ('in_proj', 'out_proj', 'dynamic_layer', 'dyn_in', 'dyn_out', 'fc_layer', 'ffn1', 'ffn2', 'cls_fc', 'reg_fc')
+
+
+def mha_self(sd, p, x, num_heads=8, linear=_linear, bmm=_bmm):
     """mmcv MultiheadAttention wrapper = identity + nn.MultiheadAttention(x,x,x)[0]
     (sequence-first; gaze_stqi_head.py:51,151,162).  x [L, Bt, d]."""
     L, Bt, d = x.shape
     hd = d // num_heads
-    qkv = F.linear(x, sd[p + '.attn.in_proj_weight'], sd[p + '.attn.in_proj_bias'])
+    qkv = linear(x, sd[p + '.attn.in_proj_weight'], sd[p + '.attn.in_proj_bias'], 'in_proj')
     q, k, v = qkv.split(d, dim=-1)
 
     def heads(t):  # [L,Bt,d] -> [Bt*h, L, hd]
@@ -230,50 +249,66 @@ def mha_self(sd, p, x, num_heads=8):
     q, k, v = heads(q) * (1.0 / math.sqrt(hd)), heads(k), heads(v)
     a = torch.softmax(torch.bmm(q, k.transpose(1, 2)), dim=-1)
     o = torch.bmm(a, v).transpose(0, 1).reshape(L, Bt, d)
-    o = F.linear(o, sd[p + '.attn.out_proj.weight'], sd[p + '.attn.out_proj.bias'])
+    o = linear(o, sd[p + '.attn.out_proj.weight'], sd[p + '.attn.out_proj.bias'], 'out_proj')
     return x + o
 
 
-def dynamic_conv(sd, p, x, roi, feat=64):
+def dynamic_conv(sd, p, x, roi, feat=64, linear=_linear, bmm=_bmm):
     """transformer.py:1116-1164. x [R,d]; roi [R,d,7,7] -> [R,d]."""
     R, d = x.shape
     f = roi.flatten(2).permute(0, 2, 1)  # [R,49,d]
-    theta = F.linear(x, sd[p + '.dynamic_layer.weight'], sd[p + '.dynamic_layer.bias'])
+    theta = linear(x, sd[p + '.dynamic_layer.weight'], sd[p + '.dynamic_layer.bias'], 'dynamic_layer')
     w_in = theta[:, :d * feat].view(R, d, feat)
     w_out = theta[:, -d * feat:].view(R, feat, d)
-    f = F.relu(_ln(sd, p + '.norm_in', torch.bmm(f, w_in)))
-    f = F.relu(_ln(sd, p + '.norm_out', torch.bmm(f, w_out)))
-    f = F.linear(f.flatten(1), sd[p + '.fc_layer.weight'], sd[p + '.fc_layer.bias'])
+    f = F.relu(_ln(sd, p + '.norm_in', bmm(f, w_in, 'dyn_in')))
+    f = F.relu(_ln(sd, p + '.norm_out', bmm(f, w_out, 'dyn_out')))
+    f = linear(f.flatten(1), sd[p + '.fc_layer.weight'], sd[p + '.fc_layer.bias'], 'fc_layer')
     return F.relu(_ln(sd, p + '.fc_norm', f))
 
 
-def stqi_stage(sd, s, roi_feat, obj, clip_length, return_intermediates=False):
-    """GazeSTQIHead.forward, gaze_stqi_head.py:119-202.
-    roi_feat [N*3,d,7,7]; obj [N,3,d] -> cls [N,3,1], delta [N,3,4], obj' [N,3,d]."""
-    p = f'roi_head.bbox_head.{s}'
-    N, P, d = obj.shape
-    T = clip_length
-    x = obj.permute(1, 0, 2)  # spatial: seq = 3 clues, batch = N frames (:148-151)
-    x = _ln(sd, p + '.attention_norm', mha_self(sd, p + '.attention', x)).permute(1, 0, 2)
-    sp = x
-    x = x.reshape(N // T, T, P, d).permute(1, 0, 2, 3).reshape(T, N * P // T, d)  # temporal (:156-166)
-    x = _ln(sd, p + '.attention_norm', mha_self(sd, p + '.attention', x))
-    x = x.reshape(T, N // T, P, d).permute(1, 0, 2, 3).reshape(N, P, d)
-    attn = x
+def spatial_attention(sd, p, obj, linear=_linear, bmm=_bmm):
+    """gaze_stqi_head.py:148-151: seq = a frame's 3 clues, batch = N frames.  obj [N,3,d] -> [N,3,d]."""
+    x = obj.permute(1, 0, 2)
+    return _ln(sd, p + '.attention_norm', mha_self(sd, p + '.attention', x, linear=linear, bmm=bmm)).permute(1, 0, 2)
+
+
+def temporal_attention(sd, p, x, T, linear=_linear, bmm=_bmm):
+    """gaze_stqi_head.py:156-166, same weights and LayerNorm: seq = a clip's T frames, batch = (clip, clue).  x [N,3,d] -> [N,3,d]."""
+    N, P, d = x.shape
+    x = x.reshape(N // T, T, P, d).permute(1, 0, 2, 3).reshape(T, N * P // T, d)
+    x = _ln(sd, p + '.attention_norm', mha_self(sd, p + '.attention', x, linear=linear, bmm=bmm))
+    return x.reshape(T, N // T, P, d).permute(1, 0, 2, 3).reshape(N, P, d)
+
+
+def stqi_after_attention(sd, p, roi_feat, x, linear=_linear, bmm=_bmm):
+    """gaze_stqi_head.py:168-202: DynamicConv, FFN, the towers and the per-clue heads on the attended queries x [N,3,d]
+    -> cls [N,3,1], delta [N,3,4], obj' [N,3,d], iic [N*3,d]."""
+    N, P, d = x.shape
     x = x.reshape(-1, d)
-    x = _ln(sd, p + '.instance_interactive_conv_norm', x + dynamic_conv(sd, p + '.instance_interactive_conv', x, roi_feat))
+    x = _ln(sd, p + '.instance_interactive_conv_norm',
+            x + dynamic_conv(sd, p + '.instance_interactive_conv', x, roi_feat, linear=linear, bmm=bmm))
     iic = x
-    h = F.linear(F.relu(F.linear(x, sd[p + '.ffn.layers.0.0.weight'], sd[p + '.ffn.layers.0.0.bias'])),
-                 sd[p + '.ffn.layers.1.weight'], sd[p + '.ffn.layers.1.bias'])
+    h = linear(F.relu(linear(x, sd[p + '.ffn.layers.0.0.weight'], sd[p + '.ffn.layers.0.0.bias'], 'ffn1')),
+               sd[p + '.ffn.layers.1.weight'], sd[p + '.ffn.layers.1.bias'], 'ffn2')
     x = _ln(sd, p + '.ffn_norm', x + h).view(N, P, d)  # mmcv FFN: add_identity (:179-180)
-    cls_f = F.relu(_ln(sd, p + '.cls_fcs.1', F.linear(x, sd[p + '.cls_fcs.0.weight'])))
+    cls_f = F.relu(_ln(sd, p + '.cls_fcs.1', linear(x, sd[p + '.cls_fcs.0.weight'], None, 'cls_fc')))
     reg_f = x
     for j in range(3):
-        reg_f = F.relu(_ln(sd, p + f'.reg_fcs.{3 * j + 1}', F.linear(reg_f, sd[p + f'.reg_fcs.{3 * j}.weight'])))
+        reg_f = F.relu(_ln(sd, p + f'.reg_fcs.{3 * j + 1}', linear(reg_f, sd[p + f'.reg_fcs.{3 * j}.weight'], None, 'reg_fc')))
     cls = torch.stack([F.linear(cls_f[:, c], sd[p + f'.{n}_fc_cls.weight'], sd[p + f'.{n}_fc_cls.bias'])
                        for c, n in enumerate(CLUES)], dim=1)
     delta = torch.stack([F.linear(reg_f[:, c], sd[p + f'.{n}_fc_reg.weight'], sd[p + f'.{n}_fc_reg.bias'])
                          for c, n in enumerate(CLUES)], dim=1)
+    return cls, delta, x, iic
+
+
+def stqi_stage(sd, s, roi_feat, obj, clip_length, return_intermediates=False, linear=_linear, bmm=_bmm):
+    """GazeSTQIHead.forward, gaze_stqi_head.py:119-202.
+    roi_feat [N*3,d,7,7]; obj [N,3,d] -> cls [N,3,1], delta [N,3,4], obj' [N,3,d]."""
+    p = f'roi_head.bbox_head.{s}'
+    sp = spatial_attention(sd, p, obj, linear, bmm)
+    attn = temporal_attention(sd, p, sp, clip_length, linear, bmm)
+    cls, delta, x, iic = stqi_after_attention(sd, p, roi_feat, attn, linear, bmm)
     if return_intermediates:
         return cls, delta, x, dict(spatial=sp, attn=attn, iic=iic)
     return cls, delta, x
