@@ -632,6 +632,59 @@ int mcg_draw_gaze_arrows_nv12(mcg_stream s, const mcg_nv12_image_desc* images_de
                               double thickness_ratio, double tip_length, const unsigned char* yuv, const unsigned char* yuvs_dev,
                               mcg_arrow_desc* plan_out_dev, int32_t* flags_dev);
 
+/* ---------------------------------------------------------------- head boxes from raw detector output (additions to ABI 18; nothing above changes)
+ * What a detector hands over is not head boxes: the demo's YOLOv5 head detector emits a raw [B][N][5 + nc] prediction (25 200 anchors per
+ * 640-pixel frame, nc = 2: person, head), and boxes only exist after non_max_suppression and scale_coords(...).round()
+ * (MCGaze_demo/yolo_head/detect.py:74,95; utils/general.py:291-312, 393-481).  mcg_detect_heads is that post-processing on a prediction in
+ * device memory: ONE launch, one workgroup per image, no allocation, no host sync, no state, graph-capturable.  The network itself stays
+ * outside this library.
+ * THE ARITHMETIC.  It is the reference function on a float32 prediction with classes=[only_class] (or None) and multi_label=False, then
+ * scale_coords(...).round().  Every operation is f32 and uncontracted (no FMA) unless it says double; thr = (float)conf_thres,
+ * it = (float)iou_thres.  Row a of image b is p = pred_dev + b * image_stride + a * row_stride (floats): x, y, w, h, objectness, nc classes.
+ *  1. p is a candidate iff p[4] > thr.  sc[c] = p[5 + c] * p[4];  conf = max over c of sc[c] and cls the LOWEST c that reaches it (a NaN
+ *     score makes conf NaN, as torch's max does).  The row is kept iff conf > thr and (only_class < 0 or cls == only_class).
+ *  2. x1 = p[0] - p[2] / 2, y1 = p[1] - p[3] / 2, x2 = p[0] + p[2] / 2, y2 = p[1] + p[3] / 2.  A row whose four box values or conf are not
+ *     all finite is DROPPED here -- a stated deviation: it is the reference's commented-out "finite constraint" (the IEEE result of a NaN
+ *     box differs between fmaxf and torch.clamp, and the head-crop entries would flag such a box anyway).
+ *  3. Candidate order: conf descending, ties by the LOWER anchor index (the reference leaves ties to its sort; -0 and +0 are one score).
+ *     If more than max_nms rows remain only the first max_nms in that order take part and the image's flag is 1: greedy NMS decides a row
+ *     from the rows before it only, so the result on the prefix is the full result restricted to it.
+ *  4. NMS offset o = agnostic ? 0 : (float)cls * 4096.0f, added to all four coordinates, each an f32 add (the reference's max_wh trick;
+ *     the rounding it introduces is part of the decision).
+ *  5. Greedy NMS walks that order; a row j is kept iff no earlier KEPT row i has iou(i, j) > it, with, on the offset boxes,
+ *       area = (x2 - x1) * (y2 - y1);  w = max(0, min(x2i, x2j) - max(x1i, x1j)), h likewise;  inter = w * h;
+ *       iou = inter / (area_i + area_j - inter)                    -- an IEEE division; 0 / 0 is NaN and suppresses nothing
+ *     This is torchvision's published nms rule restated, not linked: parity with its binary is not claimed or pinned, nor is the demo's
+ *     fp16 arithmetic (model.half()) -- the claim is the reference function on pred.float() with the CPU's arithmetic.
+ *  6. The first max_det kept rows are the image's detections, in that order.
+ *  7. Scale-back of the UN-offset box from the detector's letterboxed input (in_h, in_w) into the frame (h0, w0), in double:
+ *       gain = min(in_h / h0, in_w / w0);  pad_x = (in_w - w0 * gain) / 2;  pad_y = (in_h - h0 * gain) / 2
+ *     then g = (float)gain, px = (float)pad_x, py = (float)pad_y and per coordinate v = (v - px) / g (py for y; an IEEE division, not a
+ *     reciprocal multiply), clamped to [0, w0] (x) or [0, h0] (y): v < 0 ? 0 : v, then v > hi ? hi : v; then rintf, half to even.
+ *  8. Row k < counts[b] of image b: boxes = x1 y1 x2 y2, scores = conf, classes = cls, image_of = b.  Rows from counts[b] up are zero with
+ *     image_of = -1 -- what the head-crop and draw entries flag as an unusable row, so boxes as [B * max_det][4] and image_of as
+ *     [B * max_det] feed them with no read-back, inside one graph.
+ * FLAGS (int32 per image): 0; 1: more than max_nms candidates, the prefix was used; 2: h0 <= 0 or w0 <= 0 -- count 0, nothing is read or
+ * divided for that image.
+ *   pred_dev      DEVICE f32; row_stride >= 5 + num_classes, image_stride >= 0 (floats); fp16 predictions are widened by the caller (exact)
+ *   frame_hw_dev  DEVICE int32 [B][2]: h0, w0 of each image's frame;  in_h, in_w >= 1
+ *   conf_thres, iou_thres finite;  only_class: -1 for every class;  max_det in 1 .. 300;  max_nms in 1 .. num_anchors
+ *   boxes_dev [B][max_det][4] f32, scores_dev [B][max_det] f32, classes_dev, image_of_dev [B][max_det] int32, counts_dev [B] int32,
+ *   flags_dev [B] int32 or NULL: all written in full
+ *   ws_dev, ws_bytes: DEVICE scratch of at least mcg_detect_heads_workspace_bytes(num_images, num_anchors) bytes, 16-byte aligned (32 bytes
+ *   per anchor: keys, sorted offset boxes, anchors, marks); the workspace function returns 0 for sizes the entry refuses
+ * num_images in 0 .. 65535 (0: MCG_OK without a launch), num_anchors in 1 .. 2^24.  Argument errors (num_classes < 1, max_det or max_nms out of
+ * range, a small workspace, a threshold that is not finite, bad strides, a null pointer) return MCG_ERR_ARG before any launch.  The result
+ * does not depend on launch geometry or scheduling.  Ordering costs O(M^2) for M candidates on one compute unit: made for the hundreds a 0.25
+ * threshold leaves; at num_anchors candidates it stays correct and takes milliseconds. */
+size_t mcg_detect_heads_workspace_bytes(int num_images, int num_anchors);
+int mcg_detect_heads(mcg_stream s, const float* pred_dev, int num_images, int num_anchors, int num_classes, long long image_stride, int row_stride,
+                     int in_h, int in_w, const int32_t* frame_hw_dev /* [B][2] h0, w0 */, double conf_thres, double iou_thres,
+                     int only_class /* -1: every class */, int agnostic, int max_nms, int max_det,
+                     float* boxes_dev /* [B][max_det][4] */, float* scores_dev /* [B][max_det] */, int32_t* classes_dev /* [B][max_det] */,
+                     int32_t* image_of_dev /* [B][max_det] */, int32_t* counts_dev /* [B] */, int32_t* flags_dev /* [B] or NULL */,
+                     void* ws_dev, size_t ws_bytes);
+
 /* ---------------------------------------------------------------- measurement aids (bench.py)
  * While armed, every launch of the contraction kernel made by THIS engine is bracketed by a hipEvent pair on its launch stream.
  * mcg_engine_profile_stop synchronises, returns per-launch duration (ms), algorithmic FLOPs, algorithmic HBM bytes (inputs and

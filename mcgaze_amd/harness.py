@@ -657,10 +657,29 @@ def head_arrows(head_boxes, gaze):
 
 
 DRAW_FRAMES = 16                                       # frames per drawing call of run_head_video(draw=...)
+DETECT_FRAMES = 64                                     # frames per pipeline.detect_heads call of run_head_video(detections=...)
 
 
-def run_head_video(engine, pipeline, frames, boxes_per_frame, max_len=100, batch_frames=448, expand=0.8, rgb=False, smooth=None, pixel_format='bgr',
-                   matrix='bt601', draw=None):
+def head_boxes_per_frame(boxes, counts):
+    """The padded output of pipeline.detect_heads / detect_heads_host -> the ``boxes_per_frame`` lists segment_tracks and run_head_video take:
+    boxes [B, max_det, 4] and counts [B], numpy arrays or device tensors -> B lists of [x1, y1, x2, y2], best detection first.  This is the ONE
+    read-back of the offline route; a live route feeds ``boxes.view(-1, 4)`` and ``image_of.view(-1)`` to head_crops instead."""
+    boxes, counts = np.asarray(_host(boxes), dtype=np.float32), np.asarray(_host(counts)).reshape(-1)
+    if boxes.ndim != 3 or boxes.shape[2] != 4 or len(counts) != len(boxes) or (len(counts) and (counts.min() < 0 or counts.max() > boxes.shape[1])):
+        raise ValueError(f'head_boxes_per_frame: boxes [B, max_det, 4] and counts [B] in 0 .. max_det, got {boxes.shape} and {counts.shape}')
+    return [boxes[b, :int(n)].tolist() for b, n in enumerate(counts)]
+
+
+def _frame_hw(frame, pixel_format):
+    """(h, w) of one frame as run_head_video takes it."""
+    if pixel_format == 'nv12':
+        y = frame[0] if isinstance(frame, (tuple, list)) else frame
+        return (int(y.shape[0]), int(y.shape[1])) if isinstance(frame, (tuple, list)) else (int(y.shape[0]) // 3 * 2, int(y.shape[1]))
+    return int(frame.shape[0]), int(frame.shape[1])
+
+
+def run_head_video(engine, pipeline, frames, boxes_per_frame=None, max_len=100, batch_frames=448, expand=0.8, rgb=False, smooth=None, pixel_format='bgr',
+                   matrix='bt601', detections=None, draw=None):
     """Steps 3-4 of the demo from what its users hold -- the video's frames and one head box per person per frame -- to per-person gaze:
     segment_tracks (cell 1), the head windows cut, resized and normalised on the device (pipeline.head_crops: cell 4's crop arithmetic and
     ``cfg.data.test.pipeline[1:]``), run_tracks (cell 4's loop, batched), head_arrows (cell 5's end points).
@@ -683,8 +702,25 @@ def run_head_video(engine, pipeline, frames, boxes_per_frame, max_len=100, batch
     gaze ``arrow`` comes from (``fused``, or ``fused_smooth`` with smooth=) -- the drawn shaft ends are ``arrow`` -- and the return value is
     (records, annotated): annotated[t] is frame t on the device in draw_arrows' form, for every t of boxes_per_frame, a frame without a head
     unchanged.  Device frames are drawn into clones (copy=False in the dict: in place).  ``color`` is B, G, R whatever rgb= says.  In a
-    frame the people of a segment are drawn left to right: where two arrows overlap, the person further right wins."""
+    frame the people of a segment are drawn left to right: where two arrows overlap, the person further right wins.
+    detections: in place of boxes_per_frame (exactly one of the two is given) a dict(pred=..., in_shape=..., **options): the head detector's
+    raw prediction [T, N, 5 + nc] for the T frames, on the host or the device, the (h, w) of its letterboxed input, and options of
+    pipeline.detect_heads (conf_thres, iou_thres, only_class, agnostic, max_nms, max_det).  The boxes come from DETECT_FRAMES frames per
+    call of pipeline.detect_heads and one read-back (head_boxes_per_frame); the records are those of the same boxes given as lists."""
     smooth = check_smooth('run_head_video', smooth)
+    if (boxes_per_frame is None) == (detections is None):
+        raise ValueError('run_head_video: give exactly one of boxes_per_frame and detections')
+    if detections is not None:
+        opts = dict(detections)
+        if 'pred' not in opts or 'in_shape' not in opts:
+            raise ValueError('run_head_video(detections=...): a dict with pred and in_shape')
+        pred, in_shape = opts.pop('pred'), opts.pop('in_shape')
+        boxes_per_frame = []
+        for t0 in range(0, len(pred), DETECT_FRAMES):
+            part = pred[t0:t0 + DETECT_FRAMES]
+            hw = np.asarray([_frame_hw(frames[t], pixel_format) for t in range(t0, t0 + len(part))], dtype=np.int32).reshape(-1, 2)
+            got = pipeline.detect_heads(part, in_shape, hw, device=engine.device, **opts)
+            boxes_per_frame += head_boxes_per_frame(got[0], got[4])
     segments = segment_tracks(boxes_per_frame)
     chunks = [(si, a, b, pi) for si, seg in enumerate(segments) for a, b in plan_track_chunks(len(seg['frame_id']), max_len)
               for pi in range(len(seg['boxes']))]

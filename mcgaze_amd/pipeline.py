@@ -17,7 +17,9 @@ Head crops (``DevicePipeline.head_crops``): the demo of the reference (MCGaze_de
 every video frame before this chain; there the WINDOW is chosen on the device as well (``mcg_preprocess_head_crops``), from frames and head
 boxes that may both live in device memory already.  ``head_crop_window`` is the same arithmetic on the host, for checks and for drawing.
 With ``pixel_format='nv12'`` the frames are a video decoder's NV12 surfaces, converted tap by tap inside the pixel kernel
-(``mcg_preprocess_head_crops_nv12``); ``nv12_to_bgr`` is that conversion on the host.
+(``mcg_preprocess_head_crops_nv12``); ``nv12_to_bgr`` is that conversion on the host.  The head boxes themselves can come from the raw output
+of the demo's head detector without leaving the device (``DevicePipeline.detect_heads``, ``mcg_detect_heads``: confidence filter, NMS and
+scale-back); ``detect_heads_host`` is the same in numpy.
 
 Randomness: the reference's ``CenterCrop(crop_type='relative_range')`` draws the crop size from the global numpy RNG at TEST
 time too (transforms.py:1126-1130), and ``RandomFlip(flip_ratio=0.0)`` consumes one more uniform
@@ -795,6 +797,117 @@ def draw_arrows_host(frames, boxes, gaze, image_of=None, color=None, pixel_forma
     return (out[0] if single else out), flags
 
 
+# ---------------------------------------------------------------- head boxes from a detector's raw output (include/mcgaze_hip.h; csrc/detect.hip)
+DETECT_MAX_DET = 300                                             # the reference's max_det, and the bound of the entry
+
+
+def _detect_params(conf_thres=0.25, iou_thres=0.45, only_class=1, agnostic=False, max_nms=30000, max_det=300):
+    """The options of detect_heads_host / DevicePipeline.detect_heads, checked -> (conf_thres, iou_thres, only_class, agnostic, max_nms, max_det)."""
+    conf_thres, iou_thres = float(conf_thres), float(iou_thres)
+    if not (np.isfinite(conf_thres) and np.isfinite(iou_thres)):
+        raise ValueError(f'detect_heads: conf_thres and iou_thres must be finite, got {conf_thres}, {iou_thres}')
+    only_class = -1 if only_class is None else int(only_class)
+    if only_class < -1:
+        raise ValueError(f'detect_heads: only_class is a class index, or -1 / None for every class, got {only_class}')
+    if int(max_det) != max_det or not 1 <= max_det <= DETECT_MAX_DET:
+        raise ValueError(f'detect_heads: max_det in 1 .. {DETECT_MAX_DET}, got {max_det}')
+    if int(max_nms) != max_nms or max_nms < 1:
+        raise ValueError(f'detect_heads: max_nms must be at least 1, got {max_nms}')
+    return conf_thres, iou_thres, only_class, bool(agnostic), int(max_nms), int(max_det)
+
+
+def _detect_shapes(shape, in_shape, frame_hw):
+    """-> (B, N, nc, in_h, in_w, frame_hw [B,2] int32 or None for a device tensor, which is checked for its shape only)."""
+    if len(shape) != 3 or shape[2] < 6 or shape[1] < 1:
+        raise ValueError(f'detect_heads: pred must be [B, N, 5 + nc] with N >= 1 and nc >= 1, got {tuple(shape)}')
+    B, N, nc = int(shape[0]), int(shape[1]), int(shape[2]) - 5
+    in_h, in_w = (int(v) for v in in_shape)
+    if in_h < 1 or in_w < 1:
+        raise ValueError(f'detect_heads: in_shape is the detector\'s (h, w) input, got {tuple(in_shape)}')
+    if isinstance(frame_hw, torch.Tensor) and frame_hw.is_cuda:
+        if tuple(frame_hw.shape) != (B, 2) or frame_hw.dtype not in (torch.int32, torch.int64):
+            raise ValueError(f'detect_heads: a device frame_hw is an integer [{B}, 2] tensor, got {frame_hw.dtype} {tuple(frame_hw.shape)}')
+        return B, N, nc, in_h, in_w, None
+    hw = _host_array(frame_hw)
+    if hw.dtype.kind not in 'iu':
+        raise TypeError(f'detect_heads: frame_hw must hold integers, got {hw.dtype}')
+    if hw.shape == (2,):
+        hw = np.broadcast_to(hw, (B, 2))
+    if hw.shape != (B, 2):
+        raise ValueError(f'detect_heads: frame_hw is one (h, w) or [{B}, 2], got {hw.shape}')
+    return B, N, nc, in_h, in_w, np.ascontiguousarray(hw, dtype=np.int32)
+
+
+def detect_heads_host(pred, in_shape, frame_hw, conf_thres=0.25, iou_thres=0.45, only_class=1, agnostic=False, max_nms=30000, max_det=300):
+    """``mcg_detect_heads`` in numpy, bit for bit (the arithmetic: include/mcgaze_hip.h, "head boxes from raw detector output"): the demo's
+    head detector's post-processing -- non_max_suppression on a float32 prediction with classes=[only_class] and multi_label=False, then
+    scale_coords(...).round() (MCGaze_demo/yolo_head/utils/general.py:291-312, 393-481) -- for checks and for users without a GPU.
+
+    pred [B, N, 5 + nc] (x, y, w, h, objectness, classes; f32, or fp16 which is widened exactly); in_shape: the (h, w) of the detector's
+    letterboxed input; frame_hw: one (h, w) or [B, 2], the frames the boxes are scaled back into.  only_class: the head class of the
+    demo's detector is 1; -1 or None keeps every class.
+    -> (boxes [B, max_det, 4] f32, scores [B, max_det] f32, classes [B, max_det] int32, image_of [B, max_det] int32, counts [B] int32,
+    flags [B] int32): row k < counts[b] is a detection of image b (image_of = b), best first; the rows behind are zero with image_of = -1.
+    flags: 1 where more than max_nms candidates stood (the best max_nms took part), 2 for a frame without pixels (count 0)."""
+    conf_thres, iou_thres, only_class, agnostic, max_nms, max_det = _detect_params(conf_thres, iou_thres, only_class, agnostic, max_nms, max_det)
+    pred = _host_array(pred)
+    B, N, nc, in_h, in_w, hw = _detect_shapes(pred.shape, in_shape, _host_array(frame_hw))
+    if pred.dtype not in (np.float32, np.float16):
+        raise TypeError(f'detect_heads: pred must be float32 or float16, got {pred.dtype}')
+    pred = pred.astype(np.float32)
+    f32 = np.float32
+    with np.errstate(all='ignore'):
+        thr, it = f32(conf_thres), f32(iou_thres)
+    boxes, scores = np.zeros((B, max_det, 4), f32), np.zeros((B, max_det), f32)
+    classes, image_of = np.zeros((B, max_det), np.int32), np.full((B, max_det), -1, np.int32)
+    counts, flags = np.zeros(B, np.int32), np.zeros(B, np.int32)
+    for b in range(B):
+        h0, w0 = int(hw[b, 0]), int(hw[b, 1])
+        if h0 <= 0 or w0 <= 0:
+            flags[b] = 2
+            continue
+        p = pred[b]
+        with np.errstate(all='ignore'):
+            sc = p[:, 5:] * p[:, 4:5]
+            conf = sc.max(axis=1)                                # a NaN score makes conf NaN: the row is dropped below
+            cls = sc.argmax(axis=1)                              # the lowest class that reaches the maximum
+            half_w, half_h = p[:, 2] / f32(2), p[:, 3] / f32(2)
+            box = np.stack([p[:, 0] - half_w, p[:, 1] - half_h, p[:, 0] + half_w, p[:, 1] + half_h], axis=1)
+            keep = (p[:, 4] > thr) & (conf > thr) & np.isfinite(box).all(axis=1) & np.isfinite(conf)
+            if only_class >= 0:
+                keep &= cls == only_class
+            idx = np.flatnonzero(keep)
+            idx = idx[np.argsort(-(conf[idx] + f32(0)), kind='stable')]          # conf descending, ties by the lower anchor
+            if len(idx) > max_nms:
+                flags[b] = 1
+                idx = idx[:max_nms]
+            off = box[idx] + (f32(0) if agnostic else cls[idx].astype(f32) * f32(4096))[..., None]
+            x1, y1, x2, y2 = off.T
+            area = (x2 - x1) * (y2 - y1)
+            gone, kept = np.zeros(len(idx), bool), []
+            for i in range(len(idx)):
+                if gone[i]:
+                    continue
+                kept.append(i)
+                if len(kept) == max_det:
+                    break
+                r = slice(i + 1, None)
+                w = np.maximum(f32(0), np.minimum(x2[i], x2[r]) - np.maximum(x1[i], x1[r]))
+                h = np.maximum(f32(0), np.minimum(y2[i], y2[r]) - np.maximum(y1[i], y1[r]))
+                inter = w * h
+                gone[r] |= inter / (area[i] + area[r] - inter) > it                # NaN suppresses nothing
+            rows = idx[kept]
+            gain = min(in_h / h0, in_w / w0)
+            pad_x, pad_y = (in_w - w0 * gain) / 2, (in_h - h0 * gain) / 2
+            g, pad, hi = f32(gain), np.array([pad_x, pad_y, pad_x, pad_y], f32), np.array([w0, h0, w0, h0], f32)
+            v = (box[rows] - pad) / g
+            v = np.where(v < 0, f32(0), v)
+            v = np.where(v > hi, hi, v)
+            n = len(rows)
+            boxes[b, :n], scores[b, :n], classes[b, :n], image_of[b, :n], counts[b] = np.rint(v), conf[rows], cls[rows], b, n
+    return boxes, scores, classes, image_of, counts, flags
+
+
 class _NoDraw:
     """The generator behind head_crop_geometry's planning pass: RandomFlip(0.0)'s uniform decides nothing and is not drawn from the caller's."""
 
@@ -989,6 +1102,8 @@ class DevicePipeline:
         self._planners = [t.plan for t in self.transforms if type(t) not in (LoadImageFromFile, ImageToTensor, Collect)]   # the rest plan nothing
         self._ring = _StagingRing(self.STAGES)                    # run_many and head_crops upload through the same stages
         self._image_tables = collections.OrderedDict()            # head_crops, draw_arrows: (device, frame table bytes) -> that table on the device
+        self._frame_hw_tables = collections.OrderedDict()         # detect_heads: (device, host frame_hw bytes) -> that table on the device
+        self._detect_workspaces = collections.OrderedDict()       # detect_heads: (device, B, N) -> scratch of mcg_detect_heads
 
     def _cached_image_table(self, table, dev, nv12):
         """The frame table ``table`` on the device: uploaded the first time these frames are seen, then found again (least recently used of
@@ -1002,6 +1117,17 @@ class DevicePipeline:
         else:
             self._image_tables.move_to_end(key)
         return tdev
+
+    def _kept(self, cache, key, make):
+        """cache[key], made the first time it is asked for; the least recently used of IMAGE_TABLES entries goes."""
+        t = cache.get(key)
+        if t is None:
+            t = cache[key] = make()
+            while len(cache) > self.IMAGE_TABLES:
+                cache.popitem(last=False)
+        else:
+            cache.move_to_end(key)
+        return t
 
     def plan(self, shape, rng=np.random, filename=None, ori_filename=None):
         p = FramePlan(shape, filename, ori_filename)
@@ -1328,6 +1454,65 @@ class DevicePipeline:
                 if st is not None:
                     st.read_by(main)
         return out, flags
+
+    def detect_heads(self, pred, in_shape, frame_hw, conf_thres=0.25, iou_thres=0.45, only_class=1, agnostic=False, max_nms=30000, max_det=300,
+                     device='cuda:0', stream=None):
+        """Head boxes from the raw output of the demo's head detector, on the device (mcg_detect_heads: one launch, one workgroup per image) --
+        ``detect_heads_host`` bit for bit: the confidence filter, class-aware greedy NMS and the scale-back into the frame of
+        non_max_suppression + scale_coords(...).round() (MCGaze_demo/yolo_head/detect.py:74,95).
+
+        pred [B, N, 5 + nc]: a CUDA tensor is read where it is, its image and row strides taken from the tensor (fp16 is widened with
+        ``.float()``, which is exact; anything but unit-stride rows is made contiguous first); a numpy array goes up through the staging ring.
+        in_shape: the (h, w) of the detector's letterboxed input.  frame_hw: one (h, w), an [B, 2] array, or an integer [B, 2] device tensor
+        (h0, w0 per image), which is not read back.  The other arguments are detect_heads_host's; they and the shapes are checked before
+        anything is launched (TypeError / ValueError).
+        -> (boxes [B, max_det, 4] f32, scores [B, max_det] f32, classes, image_of [B, max_det] int32, counts [B] int32, flags [B] int32) on the
+        device.  Rows behind counts[b] are zero with image_of = -1, which head_crops and draw_arrows flag as unusable rows: ``boxes.view(-1, 4)``
+        and ``image_of.view(-1)`` feed them with no read-back.  The workspace is kept per (B, N) and the table of a host frame_hw per
+        content, so a call on a device prediction touches the host nowhere after the first and can be captured in a graph; calls that share a
+        (B, N) share the workspace and belong on one stream."""
+        lib = L.load()
+        params = _detect_params(conf_thres, iou_thres, only_class, agnostic, max_nms, max_det)
+        conf_thres, iou_thres, only_class, agnostic, max_nms, max_det = params
+        on_device = isinstance(pred, torch.Tensor) and pred.is_cuda
+        if not on_device:
+            pred = _host_array(pred)
+        if pred.dtype not in ((torch.float32, torch.float16) if on_device else (np.float32, np.float16)):
+            raise TypeError(f'detect_heads: pred must be float32 or float16, got {pred.dtype}')
+        B, N, nc, in_h, in_w, hw = _detect_shapes(tuple(pred.shape), in_shape, frame_hw)
+        dev = _device(pred.device if on_device else device, 'mcg_detect_heads')
+        with torch.cuda.device(dev):
+            main = _caller_stream(stream, dev)
+            with torch.cuda.stream(main):
+                new = lambda *shape, dtype=torch.int32: torch.empty(*shape, dtype=dtype, device=dev)
+                out = (new(B, max_det, 4, dtype=torch.float32), new(B, max_det, dtype=torch.float32), new(B, max_det), new(B, max_det), new(B), new(B))
+                if B == 0:
+                    return out
+                st = None
+                if on_device:
+                    pred = pred.float()
+                    if pred.stride(2) != 1 or pred.stride(1) < 5 + nc or pred.stride(0) < 0:
+                        pred = pred.contiguous()
+                    pred_ptr, image_stride, row_stride = pred.data_ptr(), int(pred.stride(0)), int(pred.stride(1))
+                else:
+                    flat = np.ascontiguousarray(pred, dtype=np.float32).reshape(-1).view(np.uint8)
+                    st = self._ring.take(flat.size, dev, main)
+                    st.host[:flat.size] = flat
+                    st.send(flat.size)
+                    pred_ptr, image_stride, row_stride = st.base, N * (5 + nc), 5 + nc
+                if hw is None:
+                    frame_hw = frame_hw.to(torch.int32).contiguous()
+                else:
+                    frame_hw = self._kept(self._frame_hw_tables, (dev.index, hw.tobytes()), lambda: torch.from_numpy(hw.copy()).to(dev))
+                ws = self._kept(self._detect_workspaces, (dev.index, B, N),
+                                lambda: torch.empty(int(lib.mcg_detect_heads_workspace_bytes(B, N)), dtype=torch.uint8, device=dev))
+                vp = C.c_void_p
+                L.check(lib.mcg_detect_heads(vp(main.cuda_stream), vp(pred_ptr), B, N, nc, image_stride, row_stride, in_h, in_w, vp(frame_hw.data_ptr()),
+                                             conf_thres, iou_thres, only_class, int(agnostic), min(max_nms, N), max_det, *(vp(t.data_ptr()) for t in out),
+                                             vp(ws.data_ptr()), ws.numel()), 'mcg_detect_heads')
+                if st is not None:
+                    st.read_by(main)
+        return out
 
 
 def _host_array(t):

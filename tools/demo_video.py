@@ -4,7 +4,7 @@ label files in, per-person per-frame gaze out -- and, with --draw, the frames wi
 
 usage: demo_video.py FRAMES_DIR LABELS_DIR CONFIG CHECKPOINT --out gaze.json [--precision f16x3] [--device cuda:0] [--max-len 100]
                      [--batch-frames 448] [--head-class 1] [--ext jpg] [--smooth ALPHA] [--nv12 WxH FILE] [--matrix bt601] [--draw OUT]
-                     [--color B,G,R]
+                     [--color B,G,R] [--predictions DIR --in-shape HxW [--conf-thres 0.25] [--iou-thres 0.45]]
 
 FRAMES_DIR holds 0.<ext>, 1.<ext>, ... (the demo's `frames/`), LABELS_DIR holds 0.txt, 1.txt, ... with lines `class x1 y1 x2 y2` in pixels
 (the demo's `result/labels/`); a frame without a label file shows no head.  CONFIG is the L2CS config, whose test pipeline the demo runs
@@ -19,7 +19,12 @@ H/2 rows of interleaved U, V, W bytes each), read frame by frame with numpy and 
 --draw OUT: the arrows of cell 5 are drawn into every frame on the device (harness.run_head_video(draw=...), from the gaze `arrow` comes
 from) and the annotated frames written into the directory OUT with numpy alone: 0.ppm, 1.ppm, ... (binary PPM, RGB), or with --nv12 ONE raw
 NV12 file OUT/annotated.nv12 (`ffmpeg -f rawvideo -pix_fmt nv12 -s WxH -i OUT/annotated.nv12 out.mp4` encodes it).  --color B,G,R sets
-the arrows' colour (default: the demo's 230,253,11)."""
+the arrows' colour (default: the demo's 230,253,11).
+--predictions DIR: instead of label files (LABELS_DIR is then `-`) DIR holds the head detector's RAW output, one `<t>.npy` per frame:
+the [N, 5 + nc] (or [1, N, 5 + nc]) prediction of frame t, as the YOLOv5 model returns it before non_max_suppression.  --in-shape HxW is
+the size of the letterboxed image the detector saw (e.g. 384x640 for 1080p frames).  The confidence filter, NMS and the scale-back into the
+frame run on the device (harness.run_head_video(detections=...), pipeline.detect_heads); --head-class, --conf-thres and --iou-thres are
+the detector's options."""
 import argparse
 import json
 import os
@@ -119,7 +124,13 @@ def main(argv=None):
     ap.add_argument('--matrix', default='bt601', choices=['bt601', 'bt709'], help='YUV -> RGB coefficients of --nv12')
     ap.add_argument('--draw', default=None, metavar='OUT', help='write the frames with the gaze arrows drawn into this directory')
     ap.add_argument('--color', default=None, metavar='B,G,R', help='colour of the arrows of --draw')
+    ap.add_argument('--predictions', default=None, metavar='DIR', help='raw detector output, <t>.npy per frame, instead of LABELS_DIR (then -)')
+    ap.add_argument('--in-shape', default=None, metavar='HxW', help='the letterboxed input of the detector behind --predictions')
+    ap.add_argument('--conf-thres', type=float, default=0.25)
+    ap.add_argument('--iou-thres', type=float, default=0.45)
     a = ap.parse_args(argv)
+    if (a.predictions is None) != (a.in_shape is None):
+        raise SystemExit('--predictions and --in-shape go together')
     draw = None
     if a.draw is not None:
         draw = {} if a.color is None else dict(color=parse_color(a.color))
@@ -132,12 +143,19 @@ def main(argv=None):
         if missing:
             raise SystemExit(f'{a.frames_dir}: {n} .{a.ext} files but no {missing[0]}.{a.ext} -- frames are numbered from 0 without gaps')
         frames = Frames(a.frames_dir, n, a.ext)
-    labels = [os.path.join(a.labels_dir, f'{t}.txt') for t in range(n)]
-    per_frame = [harness.read_head_labels(p, a.head_class) if os.path.exists(p) else [] for p in labels]
+    per_frame = detections = None
+    if a.predictions is not None:
+        in_h, _, in_w = a.in_shape.lower().partition('x')
+        raw = [np.load(os.path.join(a.predictions, f'{t}.npy')) for t in range(n)]
+        pred = np.stack([r.reshape(r.shape[-2], r.shape[-1]) for r in raw]) if n else np.zeros((0, 1, 6), np.float32)
+        detections = dict(pred=pred, in_shape=(int(in_h), int(in_w)), only_class=a.head_class, conf_thres=a.conf_thres, iou_thres=a.iou_thres)
+    else:
+        labels = [os.path.join(a.labels_dir, f'{t}.txt') for t in range(n)]
+        per_frame = [harness.read_head_labels(p, a.head_class) if os.path.exists(p) else [] for p in labels]
     model = init_detector(a.config, a.checkpoint, device=a.device, precision=a.precision)
     pipe = DevicePipeline(model.cfg.data.test.pipeline)
     res = harness.run_head_video(model.engine(), pipe, frames, per_frame, max_len=a.max_len, batch_frames=a.batch_frames, rgb=True,
-                                 smooth=a.smooth, pixel_format='bgr' if a.nv12 is None else 'nv12', matrix=a.matrix, draw=draw)
+                                 smooth=a.smooth, pixel_format='bgr' if a.nv12 is None else 'nv12', matrix=a.matrix, detections=detections, draw=draw)
     if draw is not None:
         res, annotated = res
         write_annotated(a.draw, annotated, a.nv12 is not None)
