@@ -1,7 +1,7 @@
-"""Decode worker of pipeline.FrameCache(processes=True).  Started as a plain child process (`python _decode_worker.py <ring fd> <slot
+"""Decode worker of frame_cache.FrameCache(processes=True).  Started as a plain child process (`python _decode_worker.py <ring fd> <slot
 bytes> <control fd> <k> <n> <records per queue> <slots> [<directory of the parent's PIL>]`, the two files being unlinked /dev/shm files inherited as descriptors, not through multiprocessing: no fork of a process that holds a HIP context, no
 re-import of the caller's main module, and this file imports neither torch, numpy nor the package).  It serves queue ``k`` of the
-mailbox pipeline._DecodeProcs lays out in the control file: a request record names a ring slot and a path; the file is decoded with
+mailbox frame_cache._DecodeProcs lays out in the control file: a request record names a ring slot and a path; the file is decoded with
 PIL, its RGB uint8 pixels go into the memory-mapped ring file (/dev/shm) at that slot, then h, w and LAST the state word of the slot
 are written (1 = done; 2 = the frame does not fit a slot, the consumer decodes it in line; 3 = failed, the message is in the slot).  The
 queue is polled (200 us naps while it is empty, 1 ms after 40 ms of idleness); the loop ends when the stop word is set or the parent
@@ -13,7 +13,7 @@ import struct
 import sys
 import time
 
-REC = 1024                             # pipeline._DecodeProcs.REC
+REC = 1024                             # frame_cache._DecodeProcs.REC
 
 
 def main():

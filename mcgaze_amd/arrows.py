@@ -1,0 +1,143 @@
+"""Gaze arrows on the host (include/mcgaze_hip.h, "annotated frames out"): the plan (``arrow_segments``), the capsule coverage
+(``segment_coverage``) and ``draw_arrows_host``, which draws in numpy what ``DevicePipeline.draw_arrows`` writes on the device, bit for bit."""
+import numpy as np
+
+from .nv12 import _nv12_planes, _pixel_format, bgr_to_yuv
+from .staging import _bgr_frame, _host_array
+
+ARROW_COLOR = (230, 253, 11)                                     # the demo's, BGR (MCGaze_demo/demo.ipynb, cell 5)
+ARROW_COORD, ARROW_SIDE = 8191, 8192                             # the bound under which the coverage test is exact in 64-bit integers
+
+
+def _arrow_params(length=1.0, min_thickness=5, thickness_ratio=0.01, tip_length=0.1):
+    """The arrow parameters, validated (ValueError) -> (length, min_thickness, thickness_ratio, tip_length); the defaults are the demo's."""
+    length, thickness_ratio, tip_length = float(length), float(thickness_ratio), float(tip_length)
+    if not all(np.isfinite(v) for v in (length, thickness_ratio, tip_length)):
+        raise ValueError('length, thickness_ratio and tip_length must be finite')
+    if int(min_thickness) != min_thickness or not 1 <= int(min_thickness) <= 255:
+        raise ValueError(f'min_thickness must be an integer in 1 .. 255, got {min_thickness!r}')
+    return length, int(min_thickness), thickness_ratio, tip_length
+
+
+def arrow_segments(boxes, gaze, **params):
+    """The arrow plan on the host (include/mcgaze_hip.h, "annotated frames out"; arrow_plan_kernel line for line): boxes [n,4] x1 y1 x2 y2, gaze
+    [n,>=2], both read as f32 and widened to double; params: length, min_thickness, thickness_ratio, tip_length (the demo's by default).
+    -> (seg int64 [n,3,2,2]: shaft, stroke, stroke x (from, to) x (x, y); thickness int64 [n]; flags int32 [n]).  seg[:, 0] is
+    harness.head_arrows of the same input.  Flag 2 (and a zero row): a box or gaze that is not finite, an end point outside [-8191, 8191] or a
+    thickness above 255."""
+    length, min_thickness, ratio, tip_length = _arrow_params(**params)
+    b = np.asarray(boxes, dtype=np.float32).astype(np.float64).reshape(-1, 4)
+    g = np.asarray(gaze, dtype=np.float32).astype(np.float64)
+    g = g.reshape(len(b), -1)[:, :2] if g.size else np.zeros((len(b), 2 if not len(b) else 0))
+    if g.shape[1] != 2:
+        raise ValueError(f'gaze must be [n, >= 2], got {np.shape(gaze)}')
+    ok = np.isfinite(b).all(axis=1) & np.isfinite(g).all(axis=1)
+    b, g = np.where(ok[:, None], b, 0.0), np.where(ok[:, None], g, 0.0)
+    inside = lambda *vs: np.logical_and.reduce([np.abs(v) <= ARROW_COORD for v in vs])
+    # numpy rounds every elementwise product and sum on its own: nothing is contracted, as in the kernel
+    cx, cy = np.floor(np.trunc(b[:, 0] + b[:, 2]) / 2.0), np.floor(np.trunc(b[:, 1] + b[:, 3]) / 2.0)
+    l = np.trunc(np.maximum(b[:, 3] - b[:, 1], b[:, 2] - b[:, 0]) * length)
+    tx, ty = np.trunc(cx - l * g[:, 0]), np.trunc(cy - l * g[:, 1])
+    t = np.maximum(float(min_thickness), np.trunc(l * ratio))
+    ok &= inside(cx, cy, tx, ty) & (t <= 255.0)
+    cx, cy, tx, ty, t = (np.where(ok, v, 0.0) for v in (cx, cy, tx, ty, t))
+    dx, dy = cx - tx, cy - ty
+    k = tip_length * 0.7071067811865476
+    ax, ay = np.rint(tx + k * (dx - dy)), np.rint(ty + k * (dx + dy))          # np.rint rounds half to even
+    bx, by = np.rint(tx + k * (dx + dy)), np.rint(ty + k * (dy - dx))
+    ok &= inside(ax, ay, bx, by)
+    tip = np.stack([tx, ty], axis=1)
+    seg = np.stack([np.stack([np.stack([px, py], axis=1), tip], axis=1) for px, py in ((cx, cy), (ax, ay), (bx, by))], axis=1)
+    seg, t = np.where(ok[:, None, None, None], seg, 0.0), np.where(ok, t, 0.0)
+    return seg.astype(np.int64), t.astype(np.int64), np.where(ok, 0, 2).astype(np.int32)
+
+
+def segment_coverage(h, w, a, b, t, y0=0, x0=0):
+    """bool [h,w]: which pixels (integer centres (x0 + column, y0 + row)) belong to the segment a -> b (x, y each) of thickness t, i.e. lie
+    within t / 2 of it -- a capsule, a disc for a segment of no length -- exactly, in 64-bit integers (the kernel's test, include/mcgaze_hip.h)."""
+    py, px = np.mgrid[y0:y0 + h, x0:x0 + w].astype(np.int64)
+    ax, ay, bx, by, tt = int(a[0]), int(a[1]), int(b[0]), int(b[1]), int(t) * int(t)
+    dx, dy, qx, qy = bx - ax, by - ay, px - ax, py - ay
+    L, u = dx * dx + dy * dy, qx * dx + qy * dy
+    qq, rr = qx * qx + qy * qy, (px - bx) ** 2 + (py - by) ** 2
+    return np.where(u <= 0, 4 * qq <= tt, np.where(u >= L, 4 * rr <= tt, 4 * (qq * L - u * u) <= tt * L))
+
+
+def _arrow_colors(color, n, nv12, matrix):
+    """-> (one uint8 [3] or None, per-row uint8 [n,3] or None), as the entries take them: B, G, R, or with nv12 the (Y, U, V) of bgr_to_yuv."""
+    c = np.asarray(ARROW_COLOR if color is None else _host_array(color))
+    if c.dtype.kind not in 'iu' or c.shape not in ((3,), (n, 3)) or (c.size and (c.min() < 0 or c.max() > 255)):
+        raise ValueError(f'color must be one (B, G, R) triple or one per row, [{n}, 3], integers in [0, 255]; got {c.dtype} {c.shape}')
+    c = c.astype(np.uint8)
+    if nv12:
+        if c.ndim == 1:
+            c = bgr_to_yuv(c, matrix)
+        else:
+            uniq, inverse = np.unique(c, axis=0, return_inverse=True)
+            c = np.stack([bgr_to_yuv(v, matrix) for v in uniq]).reshape(-1, 3)[inverse.reshape(-1)] if n else c
+    return (c, None) if c.ndim == 1 else (None, np.ascontiguousarray(c))
+
+
+def _arrow_rows(boxes, gaze, image_of, sizes, strict, **params):
+    """Plan and flags of n rows on the host -> (seg, thickness, flags): arrow_segments plus what depends on the frames -- an image_of outside
+    ``sizes`` ([(h, w), ...]) and an image larger than 8192 a side are flag 2.  strict: ValueError instead, naming the first such row."""
+    seg, t, flags = arrow_segments(boxes, gaze, **params)
+    image_of = np.asarray(image_of).reshape(-1)
+    if image_of.dtype.kind not in 'iu':
+        raise TypeError(f'image_of must hold integers, got {image_of.dtype}')
+    if len(image_of) != len(flags):
+        raise ValueError(f'boxes {np.shape(boxes)}, gaze {np.shape(gaze)} and image_of {image_of.shape} must be [n,4], [n,>=2] and [n]')
+    hw = np.asarray(sizes, dtype=np.int64).reshape(-1, 2)
+    known = (image_of >= 0) & (image_of < len(hw))
+    bad = ~known
+    bad[known] = (hw[image_of[known]] > ARROW_SIDE).any(axis=1) | (hw[image_of[known]] <= 0).any(axis=1)
+    flags = np.where(bad, 2, flags).astype(np.int32)
+    if strict and flags.any():
+        k = int(np.flatnonzero(flags)[0])
+        raise ValueError(f'arrow {k} cannot be drawn: box {np.asarray(boxes).reshape(-1, 4)[k].tolist()}, gaze {np.asarray(gaze).reshape(len(flags), -1)[k, :2].tolist()}, '
+                         f'image_of {int(image_of[k])} of {len(hw)} -- not finite, outside the image table, or an end point beyond +-{ARROW_COORD} '
+                         f'/ a thickness beyond 255')
+    seg[flags != 0], t[flags != 0] = 0, 0
+    return seg, t, flags
+
+
+def draw_arrows_host(frames, boxes, gaze, image_of=None, color=None, pixel_format='bgr', matrix='bt601', strict=False, **params):
+    """The demo's arrows (MCGaze_demo/demo.ipynb, cell 5) drawn with numpy: what DevicePipeline.draw_arrows writes on the device, bit for bit
+    (include/mcgaze_hip.h, "annotated frames out": the plan, the capsule coverage in 64-bit integers, the highest row winning an overlap, the
+    NV12 chroma rule).  For checks and for users without a GPU.
+
+    frames: one HxWx3 uint8 frame or a list of them; pixel_format='nv12': one surface -- a (y, uv) tuple or a [3H/2, W] array -- or a list of
+    those.  boxes [n,4], gaze [n,>=2], image_of [n] (None: every row draws into frame 0), color: one (B, G, R) triple (None: the demo's
+    (230, 253, 11)) or one per row; params: length, min_thickness, thickness_ratio, tip_length.
+    -> (annotated COPIES in the form given -- NV12 frames as (y [H,W], uv [H/2,W]) pairs --, flags int32 [n]).  A row flagged 2 changes no
+    byte; strict=True raises ValueError for it instead (what draw_arrows does for host tables)."""
+    nv12, _ = _pixel_format(pixel_format, matrix)
+    single = not isinstance(frames, list)
+    frames = [frames] if single else frames
+    if nv12:
+        out = [tuple(np.array(p) for p in _nv12_planes(k, f)[:2]) for k, f in enumerate(frames)]
+        sizes = [y.shape for y, _ in out]
+    else:
+        out = [_bgr_frame(k, np.array(f)) for k, f in enumerate(frames)]
+        sizes = [a.shape[:2] for a in out]
+    n = len(np.asarray(_host_array(boxes)).reshape(-1, 4))
+    image_of = np.zeros(n, dtype=np.int32) if image_of is None else _host_array(image_of)
+    seg, t, flags = _arrow_rows(_host_array(boxes), _host_array(gaze), image_of, sizes, strict, **params)
+    one, per_row = _arrow_colors(color, n, nv12, matrix)
+    for k in np.flatnonzero(flags == 0):                         # ascending: a later row overwrites an earlier one
+        h, w = sizes[int(image_of[k])]
+        r = (int(t[k]) + 1) // 2
+        x0, y0 = max(int(seg[k, :, :, 0].min()) - r, 0), max(int(seg[k, :, :, 1].min()) - r, 0)
+        x1, y1 = min(int(seg[k, :, :, 0].max()) + r + 1, w), min(int(seg[k, :, :, 1].max()) + r + 1, h)
+        if x1 <= x0 or y1 <= y0:
+            continue
+        mask = np.zeros((h, w), dtype=bool)
+        mask[y0:y1, x0:x1] = np.logical_or.reduce([segment_coverage(y1 - y0, x1 - x0, s[0], s[1], t[k], y0, x0) for s in seg[k]])
+        c = one if per_row is None else per_row[k]
+        if nv12:
+            y, uv = out[int(image_of[k])]
+            y[mask] = c[0]
+            uv.reshape(h // 2, w // 2, 2)[mask.reshape(h // 2, 2, w // 2, 2).any(axis=(1, 3))] = c[1:]
+        else:
+            out[int(image_of[k])][mask] = c
+    return (out[0] if single else out), flags

@@ -437,7 +437,7 @@ def run_videos(engine, videos, clip_len=7, stride=4, batch_clips=64, scale_facto
 
 def expected_frame_bytes(path):
     """What a decode-ring slot will really hold for a run that starts with the image file ``path``: twice its decoded size (frames of a dataset
-    vary), from the file's header alone (no decode) -- the /dev/shm check of the decode ring (pipeline.FrameCache) prices a slot at that instead
+    vary), from the file's header alone (no decode) -- the /dev/shm check of the decode ring (frame_cache.FrameCache) prices a slot at that instead
     of the 3 MiB worst case (a 360 x 360 frame is 390 KB).  None where the header cannot be read."""
     try:
         from PIL import Image
@@ -458,7 +458,7 @@ def run_annotation(engine, anno, root, pipeline, clip_len=7, stride=4, batch_cli
     Each file is decoded once while it stays cached (windows overlap by three frames); windows are preprocessed in groups (one
     pinned copy and one launch per padded size).  ``workers`` > 0 adds host threads that decode ``lookahead`` windows ahead of the
     consumer (the reference uses 7 loader threads per window, :88-95) -- measured slower than in-line decoding for small frames
-    (pipeline.FrameCache), hence 0 by default; ``processes=True`` makes them helper PROCESSES that decode into a shared-memory ring (no
+    (frame_cache.FrameCache), hence 0 by default; ``processes=True`` makes them helper PROCESSES that decode into a shared-memory ring (no
     interpreter lock in common with this loop).  The records do not depend on any of it.
     ``video_rng``: video id -> numpy RandomState.  With it every video draws its crops from its OWN generator (created when its first
     window is planned) instead of the shared ``rng``: the records then do not depend on which videos a process was given or in what

@@ -16,10 +16,7 @@ device as they are, and the kernel writes the model's ``img`` tensor.  There is 
 Head crops (``DevicePipeline.head_crops``): the demo of the reference (MCGaze_demo/demo.ipynb, cell 4) cuts one window per person out of
 every video frame before this chain; there the WINDOW is chosen on the device as well (``mcg_preprocess_head_crops``), from frames and head
 boxes that may both live in device memory already.  ``head_crop_window`` is the same arithmetic on the host, for checks and for drawing.
-With ``pixel_format='nv12'`` the frames are a video decoder's NV12 surfaces, converted tap by tap inside the pixel kernel
-(``mcg_preprocess_head_crops_nv12``); ``nv12_to_bgr`` is that conversion on the host.  The head boxes themselves can come from the raw output
-of the demo's head detector without leaving the device (``DevicePipeline.detect_heads``, ``mcg_detect_heads``: confidence filter, NMS and
-scale-back); ``detect_heads_host`` is the same in numpy.
+Re-exported from beside this module: decoded frames (frame_cache.py), NV12 (nv12.py), arrows (arrows.py), head boxes (head_detect.py), upload (staging.py).
 
 Randomness: the reference's ``CenterCrop(crop_type='relative_range')`` draws the crop size from the global numpy RNG at TEST
 time too (transforms.py:1126-1130), and ``RandomFlip(flip_ratio=0.0)`` consumes one more uniform
@@ -27,18 +24,20 @@ time too (transforms.py:1126-1130), and ``RandomFlip(flip_r
 so a seeded single-threaded run reproduces the reference's windows; ``crop_u=<float>`` pins the draw instead.
 """
 import collections
-import concurrent.futures
 import ctypes as C
 import os
-import struct
-import threading
-import time
 
 import numpy as np
 import torch
 
 from . import lib as L
+from .arrows import (ARROW_COLOR, ARROW_COORD, ARROW_SIDE, _arrow_colors, _arrow_params, _arrow_rows,  # noqa: F401
+                     arrow_segments, draw_arrows_host, segment_coverage)
+from .frame_cache import FrameCache, _DecodeProcs, decode_image  # noqa: F401
+from .head_detect import DETECT_MAX_DET, _detect_params, _detect_shapes, detect_heads_host  # noqa: F401
+from .nv12 import YUV_COEF, _nv12_planes, _pixel_format, _yuv_coef, _yuv_to_bgr, bgr_to_yuv, nv12_to_bgr  # noqa: F401
 from .registry import Registry
+from .staging import _Stage, _StagingRing, _bgr_frame, _host_array, _layout  # noqa: F401
 
 PIPELINES = Registry('pipeline')
 
@@ -66,282 +65,10 @@ class LoadImageFromFile:
         if to_float32 or color_type != 'color' or channel_order != 'bgr' or file_client_args.get('backend', 'disk') != 'disk':
             raise NotImplementedError('LoadImageFromFile: only uint8 colour BGR frames from disk feed the device pipeline')
 
-    @staticmethod
-    def load(filename, rgb=False):
-        """-> HxWx3 uint8, BGR like cv2.imread's (rgb=True: the decoder's RGB order as it is -- the pixel kernel swaps channels
-        either way, and the per-frame flip copy is saved)."""
-        from PIL import Image
-        with Image.open(filename) as im:
-            arr = np.asarray(im.convert('RGB'))
-        return arr if rgb else np.ascontiguousarray(arr[..., ::-1])
+    load = staticmethod(decode_image)
 
     def plan(self, p, rng):
         pass
-
-
-class _DecodeProcs:
-    """``n`` decode helper processes (mcgaze_amd/_decode_worker.py) driven through a MAILBOX in shared memory: a control file next to
-    the pixel ring holds one request queue per helper (fixed-size records: ring slot + path; ``head`` advanced by this side, ``tail`` by the
-    helper) and one status word per ring slot (0 = being decoded, 1 = done with h, w; 2 = does not fit a slot; 3 = failed, message in the
-    slot).  Nobody sleeps in a system call the other side has to wake: the helpers poll their queue (200 us naps when idle), the
-    consumer polls the status word of the frame it needs.  Round 4 measured the pipe protocol this replaces at 220 us per ``write`` on
-    the GPU box -- a virtual machine, where waking a task on another vCPU is an inter-processor interrupt through the hypervisor -- plus
-    one reader thread per helper competing for the interpreter lock.  A request goes to the helper with the shortest queue."""
-
-    REC = 1024                                                   # bytes per request record: int64 slot, int32 path length, path
-
-    def __init__(self, n, ring_fd, slot_bytes, slots, ring, shm_dir=None):
-        import mmap
-        import tempfile
-        import subprocess
-        import sys
-        self.n, self.slots, self.ring, self.slot_bytes = int(n), int(slots), ring, int(slot_bytes)
-        self.R = 1 << max(int(slots) + 2, 2).bit_length()        # records per queue: more than there are slots, so a queue never overflows
-        self.req_base = (64 + self.n * 128 + 4095) // 4096 * 4096
-        self.stat_base = self.req_base + self.n * self.R * self.REC
-        size = self.stat_base + self.slots * 16
-        fd, path = tempfile.mkstemp(prefix='mcg_ctl_', dir=shm_dir)
-        os.unlink(path)
-        os.ftruncate(fd, size)                                   # sparse: only the records in use ever get pages
-        self.map = mmap.mmap(fd, size)
-        self.stat = np.frombuffer(self.map, dtype=np.int32, count=self.slots * 4, offset=self.stat_base).reshape(self.slots, 4)
-        self.tails = np.frombuffer(self.map, dtype=np.int64, count=self.n * 16, offset=64).reshape(self.n, 16)[:, 8]
-        self.heads = np.zeros(self.n, dtype=np.int64)
-        worker = os.path.join(os.path.dirname(os.path.abspath(__file__)), '_decode_worker.py')
-        try:
-            # -E -s: the helper ignores PYTHON* variables and the user site (a stray sitecustomize must not slow or break seven start-ups), but it
-            # is TOLD where the parent's own PIL lives -- a Pillow reachable only through PYTHONPATH or `pip install --user` works (ADVICE r5)
-            import PIL
-            pil_dir = os.path.dirname(os.path.dirname(os.path.abspath(PIL.__file__)))
-            self.procs = [subprocess.Popen([sys.executable, '-E', '-s', worker, str(ring_fd), str(slot_bytes), str(fd), str(k), str(self.n), str(self.R), str(self.slots), pil_dir],
-                                           stdin=subprocess.DEVNULL, pass_fds=(ring_fd, fd)) for k in range(self.n)]
-        finally:
-            os.close(fd)
-
-    def submit(self, path, slot):
-        """Queue ``path`` for decoding into ring slot ``slot``.  False: the path does not fit a record (the caller decodes in line)."""
-        b = os.fsencode(path)
-        if len(b) > self.REC - 12:
-            return False
-        k = int(np.argmin(self.heads - self.tails))
-        h = int(self.heads[k])
-        struct.pack_into(f'<qi{len(b)}s', self.map, self.req_base + (k * self.R + h % self.R) * self.REC, slot, len(b), b)
-        self.stat[slot, 0] = 0
-        self.heads[k] = h + 1
-        struct.pack_into('<q', self.map, 64 + k * 128, h + 1)    # publish: the record and the status word are in place
-        return True
-
-    def wait(self, slot):
-        """-> (state, h, w) of ring slot ``slot`` once its helper is done with it."""
-        st = self.stat[slot]
-        spins = 0
-        while st[0] == 0:
-            spins += 1
-            if spins > 64:
-                time.sleep(5e-5)
-                if spins % 4096 == 0 and any(p.poll() is not None for p in self.procs):
-                    raise RuntimeError('decode worker exited')
-        if st[0] == 3:
-            raise RuntimeError('decode worker: ' + bytes(self.ring[slot * self.slot_bytes:slot * self.slot_bytes + int(st[3])]).decode('utf-8', 'replace'))
-        return int(st[0]), int(st[1]), int(st[2])
-
-    def close(self):
-        struct.pack_into('<q', self.map, 0, 1)                   # stop flag: the helpers leave their loop at the next poll
-        for p in self.procs:
-            try:
-                p.wait(timeout=5)
-            except Exception:
-                p.kill()
-                p.wait()                                         # reap it: no zombie behind a helper that had to be killed
-        self.stat = self.tails = self.ring = None
-        self.map = None
-
-
-class FrameCache:
-    """Decoded frames by path: each file is decoded once while it stays cached (LRU), optionally ahead of the consumer.
-
-    The reference harness decodes a frame again for every window it belongs to (windows overlap by three frames,
-    tools/test_gaze360_gaze.py:88-100).  Here a decode is shared by the windows that use the frame.  With ``workers`` > 0 a pool of
-    host threads decodes what ``prefetch`` names ahead of the consumer (the reference uses seven loader threads); measured on the
-    GPU box this LOSES to in-line decoding for small frames (a 360x360 JPEG decodes in 0.5 ms; the threads contend with the
-    consumer for the interpreter lock and the allocator), so the default is in-line.  ``processes=True`` (round 4) decodes in ``workers``
-    helper PROCESSES instead (``_decode_worker.py``, plain children started with subprocess: a process that holds a HIP context is
-    not forked -- measured: forked workers made every later host -> device copy of the parent 58 ms slow -- and the caller's main
-    module is not re-imported) that write the RGB pixels into a memory-mapped ring file in /dev/shm of ``capacity`` slots (``slot_bytes``
-    each; a larger frame is decoded in line); the consumer gets numpy views of the ring (valid while the frame stays cached: run_many
-    copies them into its pinned staging buffer at once).
-    A ring view is only as good as its slot: a frame handed out as a view is therefore PINNED -- never evicted -- until ``release()``
-    (run_many calls it once its staging copy is made); a call that needs more distinct frames at once than the cache has slots raises
-    instead of handing out a view whose slot a later decode overwrites.  A caller that uses the cache directly calls ``release()`` when it
-    is done with the views it holds.  ``processes=True`` needs (capacity + 1) * slot_bytes of /dev/shm at most (pages are touched as slots
-    are used: ``frame_bytes``, the decoded size the caller expects, prices a slot in the check; a node's ranks share the tmpfs,
-    LOCAL_WORLD_SIZE); when the tmpfs cannot back that (a container's default /dev/shm is 64 MB), the cache falls back to IN-LINE decoding
-    with a warning -- a tmpfs that runs out under a mapped write is a SIGBUS in a helper, not an exception.
-    Only the DECODE is shared: crop draws, geometry and the pixel kernel still run per window, in the caller's order -- results do
-    not depend on the cache, the worker count or the worker kind."""
-
-    def __init__(self, workers=0, capacity=512, loader=None, processes=False, slot_bytes=3 << 20, frame_bytes=None):
-        self.rgb = loader is None                   # our own decode keeps the decoder's RGB order (DevicePipeline.run_many swaps in the kernel)
-        self.loader = loader or (lambda path: LoadImageFromFile.load(path, rgb=True))
-        self.capacity = max(int(capacity), 1)
-        self.ring, self._map, self.procs, self.free, self.slot_bytes = None, None, None, [], int(slot_bytes)
-        self.pool = None
-        if workers > 0 and processes:
-            if loader is not None:
-                raise ValueError('FrameCache(processes=True) decodes with its own worker (PIL, RGB)')
-            import tempfile
-            # both shared files are ANONYMOUS: created in /dev/shm, unlinked at once, handed to the helpers as inherited descriptors -- nothing
-            # is left behind there however this process ends
-            shm = '/dev/shm' if os.path.isdir('/dev/shm') else None
-            # The ring file is sparse: a slot costs the pages its frame touches.  The check prices a slot at ``frame_bytes`` -- the decoded size
-            # the caller expects (harness: the first frame of the run, 390 KB for 360 x 360) -- or, unknown, at the whole slot; the tmpfs is
-            # shared by the ranks of a node, so each rank may count on its share only (LOCAL_WORLD_SIZE).  (ADVICE r5)
-            per_slot = min(int(frame_bytes), self.slot_bytes) if frame_bytes else self.slot_bytes
-            per_slot = (max(per_slot, 1) + 4095) // 4096 * 4096
-            ranks = max(int(os.environ.get('LOCAL_WORLD_SIZE', '1') or 1), 1)
-            try:
-                vfs = os.statvfs(shm or tempfile.gettempdir())
-                fit = int(vfs.f_bavail * vfs.f_frsize * 0.8 / ranks) // per_slot - 1     # slots the file system can back, with a margin
-            except OSError:
-                fit = self.capacity
-            if fit < self.capacity + 1:                          # (no half measures -- a ring smaller than one run_many call's frames would only move the failure)
-                import warnings
-                warnings.warn(f'FrameCache: {shm or tempfile.gettempdir()} cannot back {self.capacity + 1} ring slots of {per_slot} bytes for each of {ranks} rank(s) '
-                              f'(room for {max(fit, 0)}); decoding in line instead of in helper processes')
-                processes, workers = False, 0                    # in line, not threads: decode threads LOSE to in-line decoding (class docstring)
-        if workers > 0 and processes:
-            fd, path = tempfile.mkstemp(prefix='mcg_ring_', dir=shm)
-            os.unlink(path)
-            import mmap
-            try:
-                os.ftruncate(fd, (self.capacity + 1) * self.slot_bytes)           # sparse: a slot gets pages when a frame is written into it
-                self._map = mmap.mmap(fd, (self.capacity + 1) * self.slot_bytes)
-                self.ring = np.frombuffer(self._map, dtype=np.uint8)   # a plain ndarray: np.memmap's subclass machinery cost 5 us per slice
-                self.free = list(range(self.capacity + 1))
-                self.procs = _DecodeProcs(int(workers), fd, self.slot_bytes, self.capacity + 1, self.ring, shm)
-            finally:
-                os.close(fd)
-        elif workers > 0:
-            self.pool = concurrent.futures.ThreadPoolExecutor(max_workers=int(workers), thread_name_prefix='mcg-decode')
-        self.items = collections.OrderedDict()      # path -> Future (threads) / ring slot (processes) / array (in line), least recently used first
-        self.used = collections.OrderedDict()       # paths the consumer has already asked for, oldest use first: the eviction candidates
-        self.held = set()                           # paths handed out as ring views since the last release(): not evictable
-        self.lock = threading.Lock()
-        self.decodes = 0
-        self.waits, self.wait_s, self.first_wait_s = 0, 0.0, 0.0            # times the consumer found a frame not decoded yet, and how long it then waited
-
-    def _entry(self, path, wanted_now):
-        with self.lock:
-            e = self.items.get(path)
-            if wanted_now:
-                self.used[path] = True
-                self.used.move_to_end(path)
-            if e is not None:
-                self.items.move_to_end(path)
-                return e
-            if self.pool is None and self.procs is None and not wanted_now:
-                return None                         # in-line mode: prefetch is a no-op, the decode happens when the frame is asked for
-            if self.procs is not None:
-                while len(self.items) >= self.capacity:          # make room first: the new decode needs a ring slot
-                    self._evict()
-                slot = self.free.pop()
-                if self.procs.submit(path, slot):
-                    e = self.items[path] = slot
-                else:                                            # a path too long for a request record: decoded here
-                    self.free.append(slot)
-                    e = self.items[path] = self.loader(path)
-            else:
-                e = self.items[path] = self.pool.submit(self.loader, path) if self.pool is not None else self.loader(path)
-            self.decodes += 1
-            while len(self.items) > self.capacity:
-                self._evict()
-            return e
-
-    def _evict(self):
-        # A frame decoded AHEAD and not yet asked for is the one the consumer needs next: plain LRU threw exactly those out (they are the
-        # oldest entries once the cache is full -- every prefetch then cost a second, synchronous decode: round 3's "threads are slower").
-        # Victims are frames already consumed, oldest use first; an unconsumed one only when nothing else is left.
-        victim, kept = None, []
-        while self.used and victim is None:
-            p, _ = self.used.popitem(last=False)
-            if p in self.held:
-                kept.append(p)                                   # its view is still out: not a candidate (back in line below)
-            elif p in self.items:
-                victim = p
-        for p in reversed(kept):
-            self.used[p] = True
-            self.used.move_to_end(p, last=False)
-        if victim is None:
-            victim = next((p for p in self.items if p not in self.held), None)
-            if victim is None:
-                raise RuntimeError(f'FrameCache: all {len(self.items)} cached frames are handed out as views of the decode ring; raise capacity '
-                                   f'({self.capacity}) above the distinct frames of one run_many call, or release() between uses')
-        old = self.items.pop(victim)
-        if isinstance(old, int):                                 # ring slot: its writer must be done before the slot is handed out again
-            try:
-                self.procs.wait(old)
-            except RuntimeError:
-                pass
-            self.free.append(old)
-
-    def prefetch(self, paths):
-        """Start decoding ``paths`` ahead of their use (a no-op for in-line decoding)."""
-        if self.pool is not None or self.procs is not None:
-            for p in paths:
-                self._entry(p, False)
-
-    def _wait(self, e):
-        """The decode behind entry ``e`` (a Future of the thread pool or a ring slot of the helper processes), counting the times the
-        consumer had to wait for it."""
-        if isinstance(e, int):
-            if self.procs.stat[e, 0] != 0:
-                return self.procs.wait(e)
-            wait = lambda: self.procs.wait(e)
-        else:
-            if e.done():
-                return e.result()
-            wait = e.result
-        t0 = time.perf_counter()
-        r = wait()
-        dt = time.perf_counter() - t0
-        if self.waits == 0:
-            self.first_wait_s = dt                               # mostly the helpers' start-up (interpreter + PIL import)
-        self.waits += 1
-        self.wait_s += dt
-        return r
-
-    def __call__(self, path):
-        e = self.items.get(path)
-        if e is None:
-            e = self._entry(path, True)
-        else:                                                    # the common case (decoded ahead), without _entry's bookkeeping
-            self.used[path] = True
-            self.used.move_to_end(path)
-        if isinstance(e, int):                                   # decoded by a helper process into ring slot e
-            state, h, w = self._wait(e)
-            if state == 2:
-                return self.loader(path)                         # larger than a slot: decoded here
-            o = e * self.slot_bytes
-            with self.lock:
-                self.held.add(path)                              # a view of the ring: the slot stays until release()
-            return self.ring[o:o + h * w * 3].reshape(h, w, 3)
-        return self._wait(e) if isinstance(e, concurrent.futures.Future) else e
-
-    def release(self):
-        """The views handed out so far are no longer read (run_many: copied into the staging buffer): their slots may be evicted again."""
-        with self.lock:
-            self.held.clear()
-
-    def close(self):
-        if self.pool is not None:
-            self.pool.shutdown(wait=False, cancel_futures=True)
-        if self.procs is not None:
-            self.procs.close()
-            self.procs = None
-        self.items.clear()
-        self.used.clear()
-        self.ring = None                                         # (views handed out earlier keep the mapping alive; it goes with the last of them)
-        self._map = None
 
 
 @PIPELINES.register_module()
@@ -488,10 +215,7 @@ class DefaultFormatBundle:
         pass
 
     def plan(self, p, rng):
-        if p.pad_shape is None:
-            p.pad_shape = p.img_shape
-        if p.scale_factor is None:
-            p.scale_factor = 1.0
+        pass
 
 
 @PIPELINES.register_module()
@@ -535,377 +259,9 @@ _NV12_DESC = np.dtype([(n, _DESC.fields[n][0]) for n in _DESC.names] + [('uv', n
 assert _NV12_DESC.itemsize == C.sizeof(L.Nv12FrameDesc) and all(_NV12_DESC.fields[n][1] == getattr(L.Nv12FrameDesc, n).offset for n in _NV12_DESC.names)
 _NV12_DESC_WORDS = _NV12_DESC.itemsize // 4
 _CROP_WORD = _DESC.fields['crop_y'][1] // 4         # crop_y, crop_x, crop_h, crop_w are consecutive int32 words of a descriptor
-
-
-# YUV -> RGB coefficients at 20 fractional bits (include/mcgaze_hip.h, mcg_yuv_coef).  bt601: OpenCV's published limited-range constants
-# (its ITUR_BT_601_* set, 1.164 / 2.018 / -0.391 / -0.813 / 1.596 scaled by 2^20), restated, not linked: parity with cv2's COLOR_YUV2BGR_NV12
-# is not pinned on any machine this was built on.  bt709: limited range, round(c * 2**20) of the matrix with Kr = 0.2126, Kb = 0.0722,
-# luma scale 255/219 and chroma scale 255/224, worked out once in double: cy = 255/219, cub = 2 (1 - Kb) 255/224,
-# cug = -(Kb / Kg) 2 (1 - Kb) 255/224, cvg = -(Kr / Kg) 2 (1 - Kr) 255/224, cvr = 2 (1 - Kr) 255/224 with Kg = 1 - Kr - Kb.
-YUV_COEF = {
-    'bt601': dict(y_off=16, cy=1220542, cub=2116026, cug=-409993, cvg=-852492, cvr=1673527),
-    'bt709': dict(y_off=16, cy=1220945, cub=2215014, cug=-223607, cvg=-558796, cvr=1879825),
-}
-
-
-def _yuv_coef(matrix):
-    if matrix not in YUV_COEF:
-        raise ValueError(f'matrix must be one of {sorted(YUV_COEF)}, got {matrix!r}')
-    return YUV_COEF[matrix]
-
-
-def _nv12_planes(k, im, dev=None):
-    """One NV12 surface as head_crops takes it -> (y [H,W], uv [H/2,W] as a 2-d view, on_device): a (y, uv) pair with uv [H/2,W/2,2] or
-    [H/2,W], or a single [3H/2, W] surface (Y rows, then the UV rows).  TypeError for a wrong dtype, rank or device, ValueError for odd sizes
-    or a UV plane that does not belong to the Y plane."""
-    if isinstance(im, (tuple, list)):
-        if len(im) != 2:
-            raise TypeError(f'frame {k}: an NV12 frame is a (y, uv) pair or one [3H/2, W] surface, got a sequence of {len(im)}')
-        y, uv = im
-    else:
-        y, uv = im, None
-    on_device = isinstance(y, torch.Tensor)
-    if uv is not None and isinstance(uv, torch.Tensor) != on_device:
-        raise TypeError(f'frame {k}: the Y and UV planes must both be numpy arrays or both be device tensors')
-    if not on_device:
-        y = np.asarray(y)
-        uv = None if uv is None else np.asarray(uv)
-    u8 = torch.uint8 if on_device else np.uint8
-    for name, t in (('Y', y), ('UV', uv)):
-        if t is None:
-            continue
-        if t.dtype != u8 or t.ndim not in ((2,) if name == 'Y' else (2, 3)) or (t.numel() if on_device else t.size) == 0:
-            raise TypeError(f'frame {k}: the {name} plane must be a non-empty uint8 array of rank {"2" if name == "Y" else "2 or 3"}, got {t.dtype} {tuple(t.shape)}')
-        if on_device and not (t.is_cuda and t.device == dev):
-            raise TypeError(f'frame {k}: device planes must be uint8 tensors on {dev}, got one on {t.device}')
-    if uv is None:                                                # one surface: 3H/2 rows
-        rows, w = y.shape
-        if rows % 3 or w % 2:
-            raise ValueError(f'frame {k}: a {rows} x {w} surface is not [3H/2, W] with H and W even')
-        h = rows // 3 * 2
-        y, uv = y[:h], y[h:]
-    h, w = y.shape
-    if h % 2 or w % 2:
-        raise ValueError(f'frame {k}: NV12 frames have even sizes, got {h} x {w}')
-    if tuple(uv.shape) not in ((h // 2, w // 2, 2), (h // 2, w)):
-        raise ValueError(f'frame {k}: the UV plane of a {h} x {w} frame is [{h // 2}, {w // 2}, 2] or [{h // 2}, {w}], got {tuple(uv.shape)}')
-    if on_device:
-        # rows may lie further apart than w bytes (a decoder's pitch); inside a row the bytes are packed
-        packed = y.stride(1) == 1 and (uv.stride(1) == 1 if uv.ndim == 2 else (uv.stride(2) == 1 and (uv.shape[1] == 1 or uv.stride(1) == 2)))
-        if not (packed and y.stride(0) >= w and (uv.shape[0] == 1 or uv.stride(0) >= w)):
-            raise TypeError(f'frame {k}: device planes must have packed rows at least {w} bytes apart, got strides {tuple(y.stride())} and {tuple(uv.stride())}')
-        if uv.ndim == 3:
-            uv = uv.as_strided((h // 2, w), (uv.stride(0), 1))
-    else:
-        y, uv = np.ascontiguousarray(y), np.ascontiguousarray(uv).reshape(h // 2, w)
-    return y, uv, on_device
-
-
-def nv12_to_bgr(y, uv, matrix='bt601'):
-    """An NV12 frame -> HxWx3 uint8 BGR on the host, in the arithmetic the pixel kernel applies per tap (csrc/preprocess.hip, Nv12Source):
-    y [H,W] uint8, uv [H/2,W/2,2] or [H/2,W] uint8 interleaved (U, V), H and W even; matrix: a key of YUV_COEF.  Chroma is the nearest
-    sample, uv[y >> 1][x >> 1], and with u = U - 128, v = V - 128 in 32-bit integers (>> is an arithmetic shift):
-
-        yy = max(0, Y - y_off) * cy
-        R = sat8((yy + cvr * v + (1 << 19)) >> 20);  G = sat8((yy + cvg * v + cug * u + (1 << 19)) >> 20);  B = sat8((yy + cub * u + (1 << 19)) >> 20)
-
-    head_crops(pixel_format='nv12') on the planes equals head_crops on this frame bit for bit."""
-    k = _yuv_coef(matrix)
-    y, uv, _ = _nv12_planes(0, (np.asarray(y), np.asarray(uv)))
-    h, w = y.shape
-    c = uv.reshape(h // 2, w // 2, 2).astype(np.int32) - 128
-    u, v = (np.repeat(np.repeat(c[..., j], 2, axis=0), 2, axis=1) for j in (0, 1))
-    yy = np.maximum(0, y.astype(np.int32) - k['y_off']) * np.int32(k['cy']) + np.int32(1 << 19)
-    sat8 = lambda t: np.clip(t >> 20, 0, 255).astype(np.uint8)
-    return np.stack([sat8(yy + k['cub'] * u), sat8(yy + k['cvg'] * v + k['cug'] * u), sat8(yy + k['cvr'] * v)], axis=-1)
-
-
-def _yuv_to_bgr(yuv, k):
-    """(Y, U, V) integer arrays [..., 3] -> BGR [..., 3] int32 by nv12_to_bgr's arithmetic."""
-    yuv = np.asarray(yuv, dtype=np.int32)
-    u, v = yuv[..., 1] - 128, yuv[..., 2] - 128
-    yy = np.maximum(0, yuv[..., 0] - k['y_off']) * np.int32(k['cy']) + np.int32(1 << 19)
-    sat8 = lambda t: np.clip(t >> 20, 0, 255)
-    return np.stack([sat8(yy + k['cub'] * u), sat8(yy + k['cvg'] * v + k['cug'] * u), sat8(yy + k['cvr'] * v)], axis=-1)
-
-
-def bgr_to_yuv(color, matrix='bt601'):
-    """The (Y, U, V) an NV12 surface is drawn with so that it SHOWS the BGR colour ``color`` -> uint8 [3].  No new constants: the matrix of
-    ``YUV_COEF[matrix]`` (B = cy y + cub u, G = cy y + cug u + cvg v, R = cy y + cvr v with y = Y - y_off, u = U - 128, v = V - 128, each
-    coefficient / 2^20) is inverted numerically and the result rounded; among the triples within 2 of it in every component (and inside
-    [0, 255]) the one whose conversion by nv12_to_bgr's integer arithmetic has the smallest maximum channel error against ``color`` is taken,
-    ties going to the smallest (Y, U, V) in lexicographic order.  Runs once per colour, on the host."""
-    k = _yuv_coef(matrix)
-    c = np.asarray(color)
-    if c.shape != (3,) or c.dtype.kind not in 'iu' or c.min() < 0 or c.max() > 255:
-        raise ValueError(f'a colour is three integers in [0, 255] (B, G, R), got {color!r}')
-    c = c.astype(np.int64)
-    m = np.array([[k['cy'], k['cub'], 0], [k['cy'], k['cug'], k['cvg']], [k['cy'], 0, k['cvr']]], dtype=np.float64) / float(1 << 20)
-    centre = np.rint(np.linalg.solve(m, c.astype(np.float64)) + np.array([k['y_off'], 128.0, 128.0])).astype(np.int64)
-    grid = np.stack(np.meshgrid(*[np.arange(v - 2, v + 3) for v in centre], indexing='ij'), axis=-1).reshape(-1, 3)     # lexicographic order
-    grid = grid[((grid >= 0) & (grid <= 255)).all(axis=1)]
-    if not len(grid):                                            # (cannot happen for a colour in [0, 255]^3: its YUV is inside the nominal range)
-        raise ValueError(f'no (Y, U, V) near {centre.tolist()} for colour {color!r}')
-    err = np.abs(_yuv_to_bgr(grid, k) - c).max(axis=1)
-    return grid[int(np.argmin(err))].astype(np.uint8)            # argmin: the FIRST of the smallest, i.e. the lexicographically smallest
-
-
-ARROW_COLOR = (230, 253, 11)                                     # the demo's, BGR (MCGaze_demo/demo.ipynb, cell 5)
-ARROW_COORD, ARROW_SIDE = 8191, 8192                             # the bound under which the coverage test is exact in 64-bit integers
 _ARROW = np.dtype([('seg', np.int32, (3, 2, 2)), ('thickness', np.int32)] + [(f, np.int32) for f in ('x0', 'y0', 'x1', 'y1', 'image', 'flag', 'reserved')])
 assert _ARROW.itemsize == C.sizeof(L.ArrowDesc) and all(_ARROW.fields[n][1] == getattr(L.ArrowDesc, n).offset for n in _ARROW.names)
 _ARROW_WORDS = _ARROW.itemsize // 4
-
-
-def _arrow_params(length=1.0, min_thickness=5, thickness_ratio=0.01, tip_length=0.1):
-    """The arrow parameters, validated (ValueError) -> (length, min_thickness, thickness_ratio, tip_length); the defaults are the demo's."""
-    length, thickness_ratio, tip_length = float(length), float(thickness_ratio), float(tip_length)
-    if not all(np.isfinite(v) for v in (length, thickness_ratio, tip_length)):
-        raise ValueError('length, thickness_ratio and tip_length must be finite')
-    if int(min_thickness) != min_thickness or not 1 <= int(min_thickness) <= 255:
-        raise ValueError(f'min_thickness must be an integer in 1 .. 255, got {min_thickness!r}')
-    return length, int(min_thickness), thickness_ratio, tip_length
-
-
-def arrow_segments(boxes, gaze, **params):
-    """The arrow plan on the host (include/mcgaze_hip.h, "annotated frames out"; arrow_plan_kernel line for line): boxes [n,4] x1 y1 x2 y2, gaze
-    [n,>=2], both read as f32 and widened to double; params: length, min_thickness, thickness_ratio, tip_length (the demo's by default).
-    -> (seg int64 [n,3,2,2]: shaft, stroke, stroke x (from, to) x (x, y); thickness int64 [n]; flags int32 [n]).  seg[:, 0] is
-    harness.head_arrows of the same input.  Flag 2 (and a zero row): a box or gaze that is not finite, an end point outside [-8191, 8191] or a
-    thickness above 255."""
-    length, min_thickness, ratio, tip_length = _arrow_params(**params)
-    b = np.asarray(boxes, dtype=np.float32).astype(np.float64).reshape(-1, 4)
-    g = np.asarray(gaze, dtype=np.float32).astype(np.float64)
-    g = g.reshape(len(b), -1)[:, :2] if g.size else np.zeros((len(b), 2 if not len(b) else 0))
-    if g.shape[1] != 2:
-        raise ValueError(f'gaze must be [n, >= 2], got {np.shape(gaze)}')
-    ok = np.isfinite(b).all(axis=1) & np.isfinite(g).all(axis=1)
-    b, g = np.where(ok[:, None], b, 0.0), np.where(ok[:, None], g, 0.0)
-    inside = lambda *vs: np.logical_and.reduce([np.abs(v) <= ARROW_COORD for v in vs])
-    # numpy rounds every elementwise product and sum on its own: nothing is contracted, as in the kernel
-    cx, cy = np.floor(np.trunc(b[:, 0] + b[:, 2]) / 2.0), np.floor(np.trunc(b[:, 1] + b[:, 3]) / 2.0)
-    l = np.trunc(np.maximum(b[:, 3] - b[:, 1], b[:, 2] - b[:, 0]) * length)
-    tx, ty = np.trunc(cx - l * g[:, 0]), np.trunc(cy - l * g[:, 1])
-    t = np.maximum(float(min_thickness), np.trunc(l * ratio))
-    ok &= inside(cx, cy, tx, ty) & (t <= 255.0)
-    cx, cy, tx, ty, t = (np.where(ok, v, 0.0) for v in (cx, cy, tx, ty, t))
-    dx, dy = cx - tx, cy - ty
-    k = tip_length * 0.7071067811865476
-    ax, ay = np.rint(tx + k * (dx - dy)), np.rint(ty + k * (dx + dy))          # np.rint rounds half to even
-    bx, by = np.rint(tx + k * (dx + dy)), np.rint(ty + k * (dy - dx))
-    ok &= inside(ax, ay, bx, by)
-    tip = np.stack([tx, ty], axis=1)
-    seg = np.stack([np.stack([np.stack([px, py], axis=1), tip], axis=1) for px, py in ((cx, cy), (ax, ay), (bx, by))], axis=1)
-    seg, t = np.where(ok[:, None, None, None], seg, 0.0), np.where(ok, t, 0.0)
-    return seg.astype(np.int64), t.astype(np.int64), np.where(ok, 0, 2).astype(np.int32)
-
-
-def segment_coverage(h, w, a, b, t, y0=0, x0=0):
-    """bool [h,w]: which pixels (integer centres (x0 + column, y0 + row)) belong to the segment a -> b (x, y each) of thickness t, i.e. lie
-    within t / 2 of it -- a capsule, a disc for a segment of no length -- exactly, in 64-bit integers (the kernel's test, include/mcgaze_hip.h)."""
-    py, px = np.mgrid[y0:y0 + h, x0:x0 + w].astype(np.int64)
-    ax, ay, bx, by, tt = int(a[0]), int(a[1]), int(b[0]), int(b[1]), int(t) * int(t)
-    dx, dy, qx, qy = bx - ax, by - ay, px - ax, py - ay
-    L, u = dx * dx + dy * dy, qx * dx + qy * dy
-    qq, rr = qx * qx + qy * qy, (px - bx) ** 2 + (py - by) ** 2
-    return np.where(u <= 0, 4 * qq <= tt, np.where(u >= L, 4 * rr <= tt, 4 * (qq * L - u * u) <= tt * L))
-
-
-def _arrow_colors(color, n, nv12, matrix):
-    """-> (one uint8 [3] or None, per-row uint8 [n,3] or None), as the entries take them: B, G, R, or with nv12 the (Y, U, V) of bgr_to_yuv."""
-    c = np.asarray(ARROW_COLOR if color is None else _host_array(color))
-    if c.dtype.kind not in 'iu' or c.shape not in ((3,), (n, 3)) or (c.size and (c.min() < 0 or c.max() > 255)):
-        raise ValueError(f'color must be one (B, G, R) triple or one per row, [{n}, 3], integers in [0, 255]; got {c.dtype} {c.shape}')
-    c = c.astype(np.uint8)
-    if nv12:
-        if c.ndim == 1:
-            c = bgr_to_yuv(c, matrix)
-        else:
-            uniq, inverse = np.unique(c, axis=0, return_inverse=True)
-            c = np.stack([bgr_to_yuv(v, matrix) for v in uniq]).reshape(-1, 3)[inverse.reshape(-1)] if n else c
-    return (c, None) if c.ndim == 1 else (None, np.ascontiguousarray(c))
-
-
-def _arrow_rows(boxes, gaze, image_of, sizes, strict, **params):
-    """Plan and flags of n rows on the host -> (seg, thickness, flags): arrow_segments plus what depends on the frames -- an image_of outside
-    ``sizes`` ([(h, w), ...]) and an image larger than 8192 a side are flag 2.  strict: ValueError instead, naming the first such row."""
-    seg, t, flags = arrow_segments(boxes, gaze, **params)
-    image_of = np.asarray(image_of).reshape(-1)
-    if image_of.dtype.kind not in 'iu':
-        raise TypeError(f'image_of must hold integers, got {image_of.dtype}')
-    if len(image_of) != len(flags):
-        raise ValueError(f'boxes {np.shape(boxes)}, gaze {np.shape(gaze)} and image_of {image_of.shape} must be [n,4], [n,>=2] and [n]')
-    hw = np.asarray(sizes, dtype=np.int64).reshape(-1, 2)
-    known = (image_of >= 0) & (image_of < len(hw))
-    bad = ~known
-    bad[known] = (hw[image_of[known]] > ARROW_SIDE).any(axis=1) | (hw[image_of[known]] <= 0).any(axis=1)
-    flags = np.where(bad, 2, flags).astype(np.int32)
-    if strict and flags.any():
-        k = int(np.flatnonzero(flags)[0])
-        raise ValueError(f'arrow {k} cannot be drawn: box {np.asarray(boxes).reshape(-1, 4)[k].tolist()}, gaze {np.asarray(gaze).reshape(len(flags), -1)[k, :2].tolist()}, '
-                         f'image_of {int(image_of[k])} of {len(hw)} -- not finite, outside the image table, or an end point beyond +-{ARROW_COORD} '
-                         f'/ a thickness beyond 255')
-    seg[flags != 0], t[flags != 0] = 0, 0
-    return seg, t, flags
-
-
-def draw_arrows_host(frames, boxes, gaze, image_of=None, color=None, pixel_format='bgr', matrix='bt601', strict=False, **params):
-    """The demo's arrows (MCGaze_demo/demo.ipynb, cell 5) drawn with numpy: what DevicePipeline.draw_arrows writes on the device, bit for bit
-    (include/mcgaze_hip.h, "annotated frames out": the plan, the capsule coverage in 64-bit integers, the highest row winning an overlap, the
-    NV12 chroma rule).  For checks and for users without a GPU.
-
-    frames: one HxWx3 uint8 frame or a list of them; pixel_format='nv12': one surface -- a (y, uv) tuple or a [3H/2, W] array -- or a list of
-    those.  boxes [n,4], gaze [n,>=2], image_of [n] (None: every row draws into frame 0), color: one (B, G, R) triple (None: the demo's
-    (230, 253, 11)) or one per row; params: length, min_thickness, thickness_ratio, tip_length.
-    -> (annotated COPIES in the form given -- NV12 frames as (y [H,W], uv [H/2,W]) pairs --, flags int32 [n]).  A row flagged 2 changes no
-    byte; strict=True raises ValueError for it instead (what draw_arrows does for host tables)."""
-    if pixel_format not in ('bgr', 'nv12'):
-        raise ValueError(f"pixel_format must be 'bgr' or 'nv12', got {pixel_format!r}")
-    nv12 = pixel_format == 'nv12'
-    _yuv_coef(matrix)
-    single = not isinstance(frames, list)
-    frames = [frames] if single else frames
-    if nv12:
-        out = [tuple(np.array(p) for p in _nv12_planes(k, f)[:2]) for k, f in enumerate(frames)]
-        sizes = [y.shape for y, _ in out]
-    else:
-        out = [np.array(f) for f in frames]
-        for k, a in enumerate(out):
-            if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3 or a.size == 0:
-                raise TypeError(f'frame {k}: frames must be HxWx3 uint8 arrays, got {a.dtype} {a.shape}')
-        sizes = [a.shape[:2] for a in out]
-    n = len(np.asarray(_host_array(boxes)).reshape(-1, 4))
-    image_of = np.zeros(n, dtype=np.int32) if image_of is None else _host_array(image_of)
-    seg, t, flags = _arrow_rows(_host_array(boxes), _host_array(gaze), image_of, sizes, strict, **params)
-    one, per_row = _arrow_colors(color, n, nv12, matrix)
-    for k in np.flatnonzero(flags == 0):                         # ascending: a later row overwrites an earlier one
-        h, w = sizes[int(image_of[k])]
-        r = (int(t[k]) + 1) // 2
-        x0, y0 = max(int(seg[k, :, :, 0].min()) - r, 0), max(int(seg[k, :, :, 1].min()) - r, 0)
-        x1, y1 = min(int(seg[k, :, :, 0].max()) + r + 1, w), min(int(seg[k, :, :, 1].max()) + r + 1, h)
-        if x1 <= x0 or y1 <= y0:
-            continue
-        mask = np.zeros((h, w), dtype=bool)
-        mask[y0:y1, x0:x1] = np.logical_or.reduce([segment_coverage(y1 - y0, x1 - x0, s[0], s[1], t[k], y0, x0) for s in seg[k]])
-        c = one if per_row is None else per_row[k]
-        if nv12:
-            y, uv = out[int(image_of[k])]
-            y[mask] = c[0]
-            uv.reshape(h // 2, w // 2, 2)[mask.reshape(h // 2, 2, w // 2, 2).any(axis=(1, 3))] = c[1:]
-        else:
-            out[int(image_of[k])][mask] = c
-    return (out[0] if single else out), flags
-
-
-# ---------------------------------------------------------------- head boxes from a detector's raw output (include/mcgaze_hip.h; csrc/detect.hip)
-DETECT_MAX_DET = 300                                             # the reference's max_det, and the bound of the entry
-
-
-def _detect_params(conf_thres=0.25, iou_thres=0.45, only_class=1, agnostic=False, max_nms=30000, max_det=300):
-    """The options of detect_heads_host / DevicePipeline.detect_heads, checked -> (conf_thres, iou_thres, only_class, agnostic, max_nms, max_det)."""
-    conf_thres, iou_thres = float(conf_thres), float(iou_thres)
-    if not (np.isfinite(conf_thres) and np.isfinite(iou_thres)):
-        raise ValueError(f'detect_heads: conf_thres and iou_thres must be finite, got {conf_thres}, {iou_thres}')
-    only_class = -1 if only_class is None else int(only_class)
-    if only_class < -1:
-        raise ValueError(f'detect_heads: only_class is a class index, or -1 / None for every class, got {only_class}')
-    if int(max_det) != max_det or not 1 <= max_det <= DETECT_MAX_DET:
-        raise ValueError(f'detect_heads: max_det in 1 .. {DETECT_MAX_DET}, got {max_det}')
-    if int(max_nms) != max_nms or max_nms < 1:
-        raise ValueError(f'detect_heads: max_nms must be at least 1, got {max_nms}')
-    return conf_thres, iou_thres, only_class, bool(agnostic), int(max_nms), int(max_det)
-
-
-def _detect_shapes(shape, in_shape, frame_hw):
-    """-> (B, N, nc, in_h, in_w, frame_hw [B,2] int32 or None for a device tensor, which is checked for its shape only)."""
-    if len(shape) != 3 or shape[2] < 6 or shape[1] < 1:
-        raise ValueError(f'detect_heads: pred must be [B, N, 5 + nc] with N >= 1 and nc >= 1, got {tuple(shape)}')
-    B, N, nc = int(shape[0]), int(shape[1]), int(shape[2]) - 5
-    in_h, in_w = (int(v) for v in in_shape)
-    if in_h < 1 or in_w < 1:
-        raise ValueError(f'detect_heads: in_shape is the detector\'s (h, w) input, got {tuple(in_shape)}')
-    if isinstance(frame_hw, torch.Tensor) and frame_hw.is_cuda:
-        if tuple(frame_hw.shape) != (B, 2) or frame_hw.dtype not in (torch.int32, torch.int64):
-            raise ValueError(f'detect_heads: a device frame_hw is an integer [{B}, 2] tensor, got {frame_hw.dtype} {tuple(frame_hw.shape)}')
-        return B, N, nc, in_h, in_w, None
-    hw = _host_array(frame_hw)
-    if hw.dtype.kind not in 'iu':
-        raise TypeError(f'detect_heads: frame_hw must hold integers, got {hw.dtype}')
-    if hw.shape == (2,):
-        hw = np.broadcast_to(hw, (B, 2))
-    if hw.shape != (B, 2):
-        raise ValueError(f'detect_heads: frame_hw is one (h, w) or [{B}, 2], got {hw.shape}')
-    return B, N, nc, in_h, in_w, np.ascontiguousarray(hw, dtype=np.int32)
-
-
-def detect_heads_host(pred, in_shape, frame_hw, conf_thres=0.25, iou_thres=0.45, only_class=1, agnostic=False, max_nms=30000, max_det=300):
-    """``mcg_detect_heads`` in numpy, bit for bit (the arithmetic: include/mcgaze_hip.h, "head boxes from raw detector output"): the demo's
-    head detector's post-processing -- non_max_suppression on a float32 prediction with classes=[only_class] and multi_label=False, then
-    scale_coords(...).round() (MCGaze_demo/yolo_head/utils/general.py:291-312, 393-481) -- for checks and for users without a GPU.
-
-    pred [B, N, 5 + nc] (x, y, w, h, objectness, classes; f32, or fp16 which is widened exactly); in_shape: the (h, w) of the detector's
-    letterboxed input; frame_hw: one (h, w) or [B, 2], the frames the boxes are scaled back into.  only_class: the head class of the
-    demo's detector is 1; -1 or None keeps every class.
-    -> (boxes [B, max_det, 4] f32, scores [B, max_det] f32, classes [B, max_det] int32, image_of [B, max_det] int32, counts [B] int32,
-    flags [B] int32): row k < counts[b] is a detection of image b (image_of = b), best first; the rows behind are zero with image_of = -1.
-    flags: 1 where more than max_nms candidates stood (the best max_nms took part), 2 for a frame without pixels (count 0)."""
-    conf_thres, iou_thres, only_class, agnostic, max_nms, max_det = _detect_params(conf_thres, iou_thres, only_class, agnostic, max_nms, max_det)
-    pred = _host_array(pred)
-    B, N, nc, in_h, in_w, hw = _detect_shapes(pred.shape, in_shape, _host_array(frame_hw))
-    if pred.dtype not in (np.float32, np.float16):
-        raise TypeError(f'detect_heads: pred must be float32 or float16, got {pred.dtype}')
-    pred = pred.astype(np.float32)
-    f32 = np.float32
-    with np.errstate(all='ignore'):
-        thr, it = f32(conf_thres), f32(iou_thres)
-    boxes, scores = np.zeros((B, max_det, 4), f32), np.zeros((B, max_det), f32)
-    classes, image_of = np.zeros((B, max_det), np.int32), np.full((B, max_det), -1, np.int32)
-    counts, flags = np.zeros(B, np.int32), np.zeros(B, np.int32)
-    for b in range(B):
-        h0, w0 = int(hw[b, 0]), int(hw[b, 1])
-        if h0 <= 0 or w0 <= 0:
-            flags[b] = 2
-            continue
-        p = pred[b]
-        with np.errstate(all='ignore'):
-            sc = p[:, 5:] * p[:, 4:5]
-            conf = sc.max(axis=1)                                # a NaN score makes conf NaN: the row is dropped below
-            cls = sc.argmax(axis=1)                              # the lowest class that reaches the maximum
-            half_w, half_h = p[:, 2] / f32(2), p[:, 3] / f32(2)
-            box = np.stack([p[:, 0] - half_w, p[:, 1] - half_h, p[:, 0] + half_w, p[:, 1] + half_h], axis=1)
-            keep = (p[:, 4] > thr) & (conf > thr) & np.isfinite(box).all(axis=1) & np.isfinite(conf)
-            if only_class >= 0:
-                keep &= cls == only_class
-            idx = np.flatnonzero(keep)
-            idx = idx[np.argsort(-(conf[idx] + f32(0)), kind='stable')]          # conf descending, ties by the lower anchor
-            if len(idx) > max_nms:
-                flags[b] = 1
-                idx = idx[:max_nms]
-            off = box[idx] + (f32(0) if agnostic else cls[idx].astype(f32) * f32(4096))[..., None]
-            x1, y1, x2, y2 = off.T
-            area = (x2 - x1) * (y2 - y1)
-            gone, kept = np.zeros(len(idx), bool), []
-            for i in range(len(idx)):
-                if gone[i]:
-                    continue
-                kept.append(i)
-                if len(kept) == max_det:
-                    break
-                r = slice(i + 1, None)
-                w = np.maximum(f32(0), np.minimum(x2[i], x2[r]) - np.maximum(x1[i], x1[r]))
-                h = np.maximum(f32(0), np.minimum(y2[i], y2[r]) - np.maximum(y1[i], y1[r]))
-                inter = w * h
-                gone[r] |= inter / (area[i] + area[r] - inter) > it                # NaN suppresses nothing
-            rows = idx[kept]
-            gain = min(in_h / h0, in_w / w0)
-            pad_x, pad_y = (in_w - w0 * gain) / 2, (in_h - h0 * gain) / 2
-            g, pad, hi = f32(gain), np.array([pad_x, pad_y, pad_x, pad_y], f32), np.array([w0, h0, w0, h0], f32)
-            v = (box[rows] - pad) / g
-            v = np.where(v < 0, f32(0), v)
-            v = np.where(v > hi, hi, v)
-            n = len(rows)
-            boxes[b, :n], scores[b, :n], classes[b, :n], image_of[b, :n], counts[b] = np.rint(v), conf[rows], cls[rows], b, n
-    return boxes, scores, classes, image_of, counts, flags
 
 
 class _NoDraw:
@@ -955,12 +311,6 @@ def head_crop_window(box, h, w, expand=0.8):
     return tuple(int(v) for v in win[0])
 
 
-def _layout(sizes, align=256):
-    """Byte ranges of the given sizes laid out one behind the other, each starting on a multiple of ``align`` -> (offsets, total)."""
-    offs = np.cumsum([0] + [(int(size) + align - 1) // align * align for size in sizes]).tolist()
-    return offs[:-1], offs[-1]
-
-
 def _device(device, entry=None):
     """torch.device(device); a bare 'cuda' is the current device BY INDEX -- staging buffers and device frames are compared with it.  With
     ``entry``, the library call about to be made, anything but a GPU is refused."""
@@ -979,55 +329,6 @@ def _kernel_norm(norm, rgb, nv12=False):
     mean = (C.c_float * 3)(*[float(v) for v in norm['mean']])
     stdinv = (C.c_float * 3)(*[float(np.float32(1.0 / np.float64(v))) for v in norm['std']])
     return mean, stdinv, int(bool(norm['to_rgb']) != (bool(rgb) and not nv12))
-
-
-class _Stage:
-    """One upload stage: a pinned host buffer (``host``: its numpy view), its device twin (``base``: its address), the event of the copy between
-    them (on the copy stream) and the event of the pixel kernels that read the device twin (on the caller's stream).  ``send`` copies the first
-    nbytes across on the copy stream and lets the caller's stream wait for them; ``read_by`` marks the kernels launched on ``main`` as the readers."""
-    pin = dev = host = copied = read = cs = main = None
-
-    def send(self, nbytes):
-        if self.read is not None:
-            self.cs.wait_event(self.read)                         # the kernels that read this device buffer STAGES calls ago
-        with torch.cuda.stream(self.cs):
-            self.dev[:nbytes].copy_(self.pin[:nbytes], non_blocking=True)
-        self.copied = self.cs.record_event()
-        self.main.wait_event(self.copied)
-
-    def read_by(self, main):
-        self.read = main.record_event()
-
-
-class _StagingRing:
-    """The upload stages of a DevicePipeline, used in turn, and the copy stream of each device.  What the bytes are is the caller's business:
-    ``st = take(nbytes, dev, main)``, fill ``st.host`` (device addresses: ``st.base`` + offset), ``st.send(nbytes)``, launch, ``st.read_by(main)``."""
-
-    def __init__(self, stages):
-        self.stages, self.i, self.copy_stream = [_Stage() for _ in range(stages)], 0, {}
-
-    def take(self, nbytes, dev, main):
-        """The next upload stage, its buffers at least nbytes large: a pinned host buffer (a fresh ``pin_memory()`` per call costs
-        milliseconds once decode threads compete for the allocator) and a device buffer that only the copy stream writes and only the
-        pixel kernels read.  The upload runs on a stream of its own: on the caller's stream it would queue behind the forwards already
-        launched there and the PCIe transfer would take its turn with the compute instead of running under it.  STAGES of them, used in
-        turn, so that the host fills stage i while the copies and kernels of the stages before it are still queued."""
-        st = self.stages[self.i]
-        self.i = (self.i + 1) % len(self.stages)
-        if st.copied is not None:
-            st.copied.synchronize()                               # the pinned buffer is about to be overwritten
-        cs = self.copy_stream.get(dev)
-        if cs is None:
-            cs = self.copy_stream[dev] = torch.cuda.Stream(dev)
-        if st.pin is None or st.pin.numel() < nbytes or st.dev.device != dev:
-            size = max(int(nbytes * 1.25), 1 << 20)
-            st.pin = torch.empty(size, dtype=torch.uint8).pin_memory()
-            st.dev = torch.empty(size, dtype=torch.uint8, device=dev)
-            st.host, st.base = st.pin.numpy(), st.dev.data_ptr()
-            st.read = None
-            cs.wait_stream(main)                                  # the allocator may hand out memory that work queued on `main` still uses
-        st.cs, st.main = cs, main
-        return st
 
 
 def _image_table(images, dev, planes):
@@ -1049,40 +350,61 @@ def _image_table(images, dev, planes):
                                 f'got {im.dtype} {tuple(im.shape)} strides {tuple(im.stride())} on {im.device}')
             table[k] = (im.data_ptr(), im.shape[0], im.shape[1], im.stride(0) if im.shape[0] > 1 else 3 * im.shape[1])
         else:
-            a = np.ascontiguousarray(im)
-            if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3 or a.size == 0:
-                raise TypeError(f'frame {k}: frames must be HxWx3 uint8 arrays, got {a.dtype} {a.shape}')
+            a = _bgr_frame(k, np.ascontiguousarray(im))
             parts.append((k, 'src', a.reshape(-1)))
             table[k] = (0, a.shape[0], a.shape[1], 3 * a.shape[1])
     return table, parts
 
 
-def _head_crop_tables(images, dev, planes, boxes, image_of, expand):
-    """The host side of head_crops -> (table, parts, boxes, image_of, on_device, n): _image_table's frame table, and the box and index tables.
-    Host tables come back in the types the device reads (f32, int32) and are CHECKED here; device tables (on_device) are not read back."""
-    table, parts = _image_table(images, dev, planes)
-    on_device = [isinstance(t, torch.Tensor) and t.is_cuda for t in (boxes, image_of)]
-    if not on_device[0]:
+def _arrow_targets(images, planes, copy, dev):
+    """Where draw_arrows draws each frame -> (tensors, pixels, in_place): a device frame itself (copy: its packed clone), a fresh device tensor
+    for a host frame (NV12: one [3H/2, W] surface as its (y, uv) views).  pixels: (the tensor they belong in, bytes) of the host frames, in image
+    order; in_place: every frame is its own target."""
+    out, pixels = [], []
+    for k, im in enumerate(images):
+        if planes is not None and not planes[k][2]:
+            y, uv, _ = planes[k]
+            s = torch.empty(y.shape[0] * 3 // 2, y.shape[1], dtype=torch.uint8, device=dev)
+            out.append((s[:y.shape[0]], s[y.shape[0]:]))
+            pixels += [(out[-1][0], y.reshape(-1)), (out[-1][1], uv.reshape(-1))]
+        elif planes is None and not isinstance(im, torch.Tensor):
+            out.append(torch.empty(np.shape(im), dtype=torch.uint8, device=dev))
+            pixels.append((out[-1], np.ascontiguousarray(im).reshape(-1)))
+        elif copy:
+            clone = lambda t: t.clone(memory_format=torch.contiguous_format)
+            out.append(tuple(clone(t) for t in im) if isinstance(im, (tuple, list)) else clone(im))
+        else:
+            out.append(im)
+    return out, pixels, all(o is im for o, im in zip(out, images))
+
+
+def _row_tables(caller, rows, frames, boxes, image_of, gaze=None):
+    """The row tables of ``caller`` ('head_crops' cuts ``rows`` = 'crops', 'draw_arrows' draws 'arrows') over ``frames`` frames, as the device
+    reads them -> (boxes, image_of, gaze, n).  Each of boxes [n,4], image_of [n] and the optional gaze [n,>=2] is a CUDA tensor, which comes
+    back as it is and is not read back, or lives on the host and comes back CHECKED as a contiguous array: boxes f32 [n,4]; image_of int32
+    [n] (TypeError unless it holds integers, ValueError outside [0, frames)); gaze f32, cut to its first two columns.  ValueError where the shapes
+    do not belong together or n exceeds 65535."""
+    on_device = lambda t: isinstance(t, torch.Tensor) and t.is_cuda
+    if not on_device(boxes):
         boxes = np.ascontiguousarray(_host_array(boxes), dtype=np.float32).reshape(-1, 4)     # f32 is what the device reads: the checks see the same boxes
-    if not on_device[1]:
+    n = int(boxes.shape[0])
+    if gaze is not None and not on_device(gaze):
+        gaze = np.ascontiguousarray(_host_array(gaze), dtype=np.float32)
+        gaze = np.zeros((0, 2), np.float32) if n == 0 and gaze.size == 0 else np.ascontiguousarray(gaze[:, :2]) if gaze.ndim == 2 else gaze
+    if not on_device(image_of):
         image_of = np.ascontiguousarray(_host_array(image_of)).reshape(-1)
         if image_of.dtype.kind not in 'iu':
             raise TypeError(f'image_of must hold integers, got {image_of.dtype}')
-        if len(image_of) and (image_of.min() < 0 or image_of.max() >= len(images)):
-            raise ValueError(f'image_of must lie in [0, {len(images)}), got [{image_of.min()}, {image_of.max()}]')
+        if len(image_of) and (image_of.min() < 0 or image_of.max() >= frames):
+            raise ValueError(f'image_of must lie in [0, {frames}), got [{image_of.min()}, {image_of.max()}]')
         image_of = image_of.astype(np.int32)
-    n = int(boxes.shape[0])
-    if tuple(boxes.shape) != (n, 4) or tuple(image_of.shape) != (n,):
-        raise ValueError(f'head_crops: boxes {tuple(boxes.shape)} and image_of {tuple(image_of.shape)} must be [n,4] and [n]')
+    bad_gaze = gaze is not None and (gaze.ndim != 2 or gaze.shape[0] != n or gaze.shape[1] < 2)
+    if tuple(boxes.shape) != (n, 4) or bad_gaze or tuple(image_of.shape) != (n,):
+        got, want = ('', '') if gaze is None else (f', gaze {tuple(gaze.shape)}', ', [n,>=2]')
+        raise ValueError(f'{caller}: boxes {tuple(boxes.shape)}{got} and image_of {tuple(image_of.shape)} must be [n,4]{want} and [n]')
     if n > 65535:
-        raise ValueError(f'head_crops: at most 65535 crops per call (got {n})')
-    if not any(on_device) and n:
-        _, empty = head_crop_windows(boxes, table['h'][image_of], table['w'][image_of], expand)
-        if empty.any():
-            k = int(np.flatnonzero(empty)[0])
-            raise ValueError(f'head box {k} {boxes[k].tolist()} leaves an empty window in frame {int(image_of[k])} '
-                             f'({int(table["h"][image_of[k]])} x {int(table["w"][image_of[k]])})')
-    return table, parts, boxes, image_of, on_device, n
+        raise ValueError(f'{caller}: at most 65535 {rows} per call (got {n})')
+    return boxes, image_of, gaze, n
 
 
 class DevicePipeline:
@@ -1099,24 +421,11 @@ class DevicePipeline:
         if 'Normalize' not in kinds or not any(k in kinds for k in ('DefaultFormatBundle', 'ImageToTensor')) or kinds[-1] != 'Collect':
             raise ValueError(f'unsupported test pipeline {kinds}: need ... Normalize ... DefaultFormatBundle, Collect')
         self.collect = self.transforms[-1]
-        self._planners = [t.plan for t in self.transforms if type(t) not in (LoadImageFromFile, ImageToTensor, Collect)]   # the rest plan nothing
+        self._planners = [t.plan for t in self.transforms if type(t) not in (LoadImageFromFile, DefaultFormatBundle, ImageToTensor, Collect)]   # the rest plan nothing
         self._ring = _StagingRing(self.STAGES)                    # run_many and head_crops upload through the same stages
         self._image_tables = collections.OrderedDict()            # head_crops, draw_arrows: (device, frame table bytes) -> that table on the device
         self._frame_hw_tables = collections.OrderedDict()         # detect_heads: (device, host frame_hw bytes) -> that table on the device
         self._detect_workspaces = collections.OrderedDict()       # detect_heads: (device, B, N) -> scratch of mcg_detect_heads
-
-    def _cached_image_table(self, table, dev, nv12):
-        """The frame table ``table`` on the device: uploaded the first time these frames are seen, then found again (least recently used of
-        IMAGE_TABLES goes) -- what lets head_crops and draw_arrows on device frames and tables touch the host nowhere."""
-        key = (dev.index, table.tobytes()) + (('nv12',) if nv12 else ())
-        tdev = self._image_tables.get(key)
-        if tdev is None:
-            tdev = self._image_tables[key] = torch.from_numpy(table.view(np.uint8).reshape(-1).copy()).to(dev)
-            while len(self._image_tables) > self.IMAGE_TABLES:
-                self._image_tables.popitem(last=False)
-        else:
-            self._image_tables.move_to_end(key)
-        return tdev
 
     def _kept(self, cache, key, make):
         """cache[key], made the first time it is asked for; the least recently used of IMAGE_TABLES entries goes."""
@@ -1128,6 +437,12 @@ class DevicePipeline:
         else:
             cache.move_to_end(key)
         return t
+
+    def _device_image_table(self, table, dev, nv12):
+        """The frame table ``table`` on the device: uploaded the first time these frames are seen, then found again -- what lets head_crops
+        and draw_arrows on device frames and tables touch the host nowhere."""
+        return self._kept(self._image_tables, (dev.index, table.tobytes()) + (('nv12',) if nv12 else ()),
+                          lambda: torch.from_numpy(table.view(np.uint8).reshape(-1).copy()).to(dev))
 
     def plan(self, shape, rng=np.random, filename=None, ori_filename=None):
         p = FramePlan(shape, filename, ori_filename)
@@ -1201,33 +516,31 @@ class DevicePipeline:
                     pad = (max(p.pad_shape[0] for p in plans[a:b]), max(p.pad_shape[1] for p in plans[a:b]))
                     groups.setdefault(pad, []).append(wi)
             rows = {pad: np.concatenate([np.arange(bounds[wi], bounds[wi + 1]) for wi in wis]) for pad, wis in groups.items()}
-            # the frame descriptors travel in the same pinned staging buffer, behind the pixels: one non-blocking copy for everything (a
-            # pageable .to() per descriptor table blocked the host until the stream had drained -- the engine's previous batch)
-            dsz = C.sizeof(L.FrameDesc)
-            offs, total = _layout([a.size for a in arrays] + [len(idx) * dsz for idx in rows.values()])
-            desc_off = dict(zip(groups, offs[len(arrays):]))
-            with torch.cuda.device(dev):
-                main = _caller_stream(stream, dev)
-                st = self._ring.take(total, dev, main)
-                for a, o in zip(arrays, offs):
-                    st.host[o:o + a.size] = a.reshape(-1)
+            # the frame descriptors (mcg_frame_desc, one structured array per padded size) travel in the same pinned staging buffer, behind the
+            # pixels: one non-blocking copy for everything (a pageable .to() per descriptor table blocked the host until the stream had
+            # drained -- the engine's previous batch)
+            descs = {pad: np.zeros(len(idx), dtype=_DESC) for pad, idx in rows.items()}
+
+            def describe(at):
                 release()                                         # ring views of a FrameCache: copied, their slots may go
-                # descriptors (mcg_frame_desc), built as one structured array per padded size
-                addr = st.base + np.asarray(offs[:len(arrays)], dtype=np.int64)[src]
+                addr = np.asarray(at, dtype=np.int64)[src]
                 shp = np.asarray([a.shape[:2] for a in arrays], dtype=np.int32)[src]
                 geo = np.asarray([p.crop + p.img_shape[:2] for p in plans], dtype=np.int32)          # crop y, x, h, w, out h, w
                 for pad, idx in rows.items():
-                    desc = np.zeros(len(idx), dtype=_DESC)
+                    desc = descs[pad]
                     desc['src'], desc['src_h'], desc['src_w'], desc['src_pitch'] = addr[idx], shp[idx, 0], shp[idx, 1], shp[idx, 1] * 3
                     for j, f in enumerate(('crop_y', 'crop_x', 'crop_h', 'crop_w', 'out_h', 'out_w')):
                         desc[f] = geo[idx, j]
-                    st.host[desc_off[pad]:desc_off[pad] + len(idx) * dsz] = desc.view(np.uint8)
-                st.send(total)
+
+            with torch.cuda.device(dev):
+                main = _caller_stream(stream, dev)
+                st, _, desc_at = self._ring.upload([a.reshape(-1) for a in arrays], list(descs.values()), dev, main, describe)
+                desc_at = dict(zip(descs, desc_at))
             mean, stdinv, swap = _kernel_norm(plans[0].img_norm_cfg, rgb_source)
             for (pad_h, pad_w), wis in groups.items():
                 n = len(rows[pad_h, pad_w])
                 img = torch.empty(n, 3, pad_h, pad_w, dtype=torch.float32, device=dev)
-                L.check(lib.mcg_preprocess_frames(C.c_void_p(main.cuda_stream), C.c_void_p(st.base + desc_off[(pad_h, pad_w)]), n, C.c_void_p(img.data_ptr()),
+                L.check(lib.mcg_preprocess_frames(C.c_void_p(main.cuda_stream), C.c_void_p(desc_at[pad_h, pad_w]), n, C.c_void_p(img.data_ptr()),
                                                   pad_h, pad_w, mean, stdinv, swap), 'mcg_preprocess_frames')
                 for wi, part in zip(wis, img.split([bounds[wi + 1] - bounds[wi] for wi in wis])):
                     out[wi] = (part, [self.collect.meta(p) for p in plans[bounds[wi]:bounds[wi + 1]]])
@@ -1278,45 +591,40 @@ class DevicePipeline:
         / ValueError for a wrong dtype, rank, device or plane shape and for odd sizes, before anything is launched.  The result equals
         head_crops on ``nv12_to_bgr`` of the same planes bit for bit; tables, flags and the no-host-touch property are as for BGR."""
         lib = L.load()
-        if pixel_format not in ('bgr', 'nv12'):
-            raise ValueError(f"pixel_format must be 'bgr' or 'nv12', got {pixel_format!r}")
-        coef = _yuv_coef(matrix)
-        nv12 = pixel_format == 'nv12'
+        nv12, coef = _pixel_format(pixel_format, matrix)
         dev = _device(device)                                     # the surfaces are checked whatever the device: a bad one is the caller's first error
         planes = [_nv12_planes(k, im, dev) for k, im in enumerate(images)] if nv12 else None
         dev = _device(dev, 'mcg_preprocess_head_crops')
         scale_w, scale_h, pad_h, pad_w, norm = self.head_crop_geometry()
         if not len(images):
             raise ValueError('head_crops: no frames')
-        table, parts, boxes, image_of, on_device, n = _head_crop_tables(images, dev, planes, boxes, image_of, expand)
+        table, parts = _image_table(images, dev, planes)
+        boxes, image_of, _, n = _row_tables('head_crops', 'crops', len(images), boxes, image_of)
+        if isinstance(boxes, np.ndarray) and isinstance(image_of, np.ndarray) and n:
+            _, empty = head_crop_windows(boxes, table['h'][image_of], table['w'][image_of], expand)
+            if empty.any():
+                k = int(np.flatnonzero(empty)[0])
+                raise ValueError(f'head box {k} {boxes[k].tolist()} leaves an empty window in frame {int(image_of[k])} '
+                                 f'({int(table["h"][image_of[k]])} x {int(table["w"][image_of[k]])})')
         with torch.cuda.device(dev):
             main = _caller_stream(stream, dev)
             with torch.cuda.stream(main):
-                boxes = boxes.to(dev, torch.float32).contiguous() if on_device[0] else boxes
-                image_of = image_of.to(dev, torch.int32).contiguous() if on_device[1] else image_of
+                boxes = boxes if isinstance(boxes, np.ndarray) else boxes.to(dev, torch.float32).contiguous()
+                image_of = image_of if isinstance(image_of, np.ndarray) else image_of.to(dev, torch.int32).contiguous()
                 new = lambda *shape, dtype=torch.int32: torch.empty(*shape, dtype=dtype, device=dev)
                 if n == 0:
                     return new(0, 3, pad_h, pad_w, dtype=torch.float32), new(0, 2), new(0, 4, dtype=torch.float32), new(0, 4), new(0)
-                # everything that comes from the host travels in ONE pinned staging buffer and one copy: pixels, frame table, host tables
-                tables = [t.view(np.uint8).reshape(-1) for t, d in zip((boxes, image_of), on_device) if not d]
-                st = None
-                if parts or tables:
-                    blobs = [a for _, _, a in parts] + [table.view(np.uint8).reshape(-1)] + tables     # (the table's bytes are a VIEW: filled below, then copied)
-                    offs, total = _layout([b.size for b in blobs])
-                    st = self._ring.take(total, dev, main)
-                    for (k, f, _), o in zip(parts, offs):
-                        table[f][k] = st.base + o                 # a host frame's address: where its bytes land in the device twin
-                    for b, o in zip(blobs, offs):
-                        st.host[o:o + b.size] = b
-                    st.send(total)
-                    at = [st.base + o for o in offs[len(parts):]]                                # frame table, then the host tables
-                    images_ptr = at.pop(0)
-                    boxes_ptr = boxes.data_ptr() if on_device[0] else at.pop(0)
-                    image_of_ptr = image_of.data_ptr() if on_device[1] else at.pop(0)
-                else:
+                frame_table = table
+                if not parts and isinstance(boxes, torch.Tensor) and isinstance(image_of, torch.Tensor):
                     # nothing comes from the host but the frame table, and that only the first time these frames are seen: no stage is taken
-                    tdev = self._cached_image_table(table, dev, nv12)
-                    images_ptr, boxes_ptr, image_of_ptr = tdev.data_ptr(), boxes.data_ptr(), image_of.data_ptr()
+                    frame_table = self._device_image_table(table, dev, nv12)
+
+                def name_frames(at):                              # a host frame's address: where its bytes land in the device twin
+                    for (k, f, _), a in zip(parts, at):
+                        table[f][k] = a
+
+                # everything that comes from the host travels in ONE pinned staging buffer and one copy: pixels, frame table, host tables
+                st, _, (images_ptr, boxes_ptr, image_of_ptr) = self._ring.upload([a for _, _, a in parts], (frame_table, boxes, image_of), dev, main, name_frames)
                 img, scale_factor = new(n, 3, pad_h, pad_w, dtype=torch.float32), new(n, 4, dtype=torch.float32)
                 desc, img_hw, flags = new(n, _NV12_DESC_WORDS if nv12 else _DESC_WORDS), new(n, 2), new(n)
                 vp = C.c_void_p
@@ -1347,11 +655,8 @@ class DevicePipeline:
         cache head_crops keeps): it can be captured in a graph.
         -> (images on the device, in order; flags [n] int32 on the device: 0 drawn -- possibly no pixel --, 2 unusable)."""
         lib = L.load()
-        if pixel_format not in ('bgr', 'nv12'):
-            raise ValueError(f"pixel_format must be 'bgr' or 'nv12', got {pixel_format!r}")
-        _yuv_coef(matrix)
+        nv12, _ = _pixel_format(pixel_format, matrix)
         length, min_thickness, ratio, tip_length = _arrow_params(**params)
-        nv12 = pixel_format == 'nv12'
         entry = lib.mcg_draw_gaze_arrows_nv12 if nv12 else lib.mcg_draw_gaze_arrows
         dev = _device(device)
         images = list(images)
@@ -1360,94 +665,44 @@ class DevicePipeline:
         if not len(images):
             raise ValueError('draw_arrows: no frames')
         table, _ = _image_table(images, dev, planes)              # every frame is checked before the first clone or upload
-        on_device = [isinstance(t, torch.Tensor) and t.is_cuda for t in (boxes, gaze, image_of)]
-        if not on_device[0]:
-            boxes = np.ascontiguousarray(_host_array(boxes), dtype=np.float32).reshape(-1, 4)
-        n = int(boxes.shape[0])
-        if not on_device[1]:
-            gaze = np.ascontiguousarray(_host_array(gaze), dtype=np.float32)
-            gaze = np.zeros((0, 2), np.float32) if n == 0 and gaze.size == 0 else np.ascontiguousarray(gaze[:, :2]) if gaze.ndim == 2 else gaze
-        if not on_device[2]:
-            image_of = np.ascontiguousarray(_host_array(image_of)).reshape(-1)
-            if image_of.dtype.kind not in 'iu':
-                raise TypeError(f'image_of must hold integers, got {image_of.dtype}')
-            if len(image_of) and (image_of.min() < 0 or image_of.max() >= len(images)):
-                raise ValueError(f'image_of must lie in [0, {len(images)}), got [{image_of.min()}, {image_of.max()}]')
-            image_of = image_of.astype(np.int32)
-        if tuple(boxes.shape) != (n, 4) or gaze.ndim != 2 or gaze.shape[0] != n or gaze.shape[1] < 2 or tuple(image_of.shape) != (n,):
-            raise ValueError(f'draw_arrows: boxes {tuple(boxes.shape)}, gaze {tuple(gaze.shape)} and image_of {tuple(image_of.shape)} must be [n,4], [n,>=2] and [n]')
-        if n > 65535:
-            raise ValueError(f'draw_arrows: at most 65535 arrows per call (got {n})')
-        for name, t, there in (('box', boxes, on_device[0]), ('gaze', gaze, on_device[1])):
-            if not there and not np.isfinite(t).all():
+        boxes, image_of, gaze, n = _row_tables('draw_arrows', 'arrows', len(images), boxes, image_of, gaze)
+        for name, t in (('box', boxes), ('gaze', gaze)):
+            if isinstance(t, np.ndarray) and not np.isfinite(t).all():
                 raise ValueError(f'draw_arrows: {name} {int(np.flatnonzero(~np.isfinite(t).all(axis=1))[0])} is not finite')
         one, per_row = _arrow_colors(color, n, nv12, matrix)
         with torch.cuda.device(dev):
             main = _caller_stream(stream, dev)
             with torch.cuda.stream(main):
-                # where the arrows go: a device frame itself (or its clone), a fresh device tensor for every host frame
-                out = []
-                for k, im in enumerate(images):
-                    if nv12 and not planes[k][2]:
-                        h, w = planes[k][0].shape
-                        s = torch.empty(h * 3 // 2, w, dtype=torch.uint8, device=dev)
-                        out.append((s[:h], s[h:]))
-                    elif not nv12 and not isinstance(im, torch.Tensor):
-                        out.append(torch.empty(np.shape(im), dtype=torch.uint8, device=dev))
-                    elif copy:
-                        clone = lambda t: t.clone(memory_format=torch.contiguous_format)
-                        out.append(tuple(clone(t) for t in im) if isinstance(im, (tuple, list)) else clone(im))
-                    else:
-                        out.append(im)
-                in_place = all(o is im for o, im in zip(out, images))
+                out, pixels, in_place = _arrow_targets(images, planes, copy, dev)
                 if not in_place:                                  # the table of the tensors that are drawn into
                     table, _ = _image_table(out, dev, [_nv12_planes(k, o, dev) for k, o in enumerate(out)] if nv12 else None)
-                if table['h'].max() > ARROW_SIDE or table['w'].max() > ARROW_SIDE:
-                    raise ValueError(f'draw_arrows: frames of at most {ARROW_SIDE} pixels a side, got {int(table["h"].max())} x {int(table["w"].max())}')
-                if not any(on_device[:2]) and n:
-                    _arrow_rows(boxes, gaze, image_of if not on_device[2] else np.zeros(n, np.int32),
+                h_max, w_max = int(table['h'].max()), int(table['w'].max())
+                if h_max > ARROW_SIDE or w_max > ARROW_SIDE:
+                    raise ValueError(f'draw_arrows: frames of at most {ARROW_SIDE} pixels a side, got {h_max} x {w_max}')
+                if isinstance(boxes, np.ndarray) and isinstance(gaze, np.ndarray) and n:
+                    _arrow_rows(boxes, gaze, image_of if isinstance(image_of, np.ndarray) else np.zeros(n, np.int32),
                                 [(int(r['h']), int(r['w'])) for r in table], True, length=length, min_thickness=min_thickness,
                                 thickness_ratio=ratio, tip_length=tip_length)
-                boxes = boxes.to(dev, torch.float32).contiguous() if on_device[0] else boxes
-                image_of = image_of.to(dev, torch.int32).contiguous() if on_device[2] else image_of
-                if on_device[1]:
+                boxes = boxes if isinstance(boxes, np.ndarray) else boxes.to(dev, torch.float32).contiguous()
+                image_of = image_of if isinstance(image_of, np.ndarray) else image_of.to(dev, torch.int32).contiguous()
+                gaze_stride = 2
+                if isinstance(gaze, torch.Tensor):
                     if not (gaze.device == dev and gaze.dtype == torch.float32 and gaze.stride(1) == 1 and (n <= 1 or gaze.stride(0) >= 2)):
                         gaze = gaze.to(dev, torch.float32).contiguous()
                     gaze_stride = int(gaze.stride(0)) if n > 1 else int(gaze.shape[1])
-                else:
-                    gaze_stride = 2
-                # the bytes of the host frames (frame, the device tensor they belong in, bytes), in image order
-                if nv12:
-                    pixels = [(o[j], a.reshape(-1)) for o, p in zip(out, planes) if not p[2] for j, a in enumerate(p[:2])]
-                else:
-                    pixels = [(o, np.ascontiguousarray(im).reshape(-1)) for o, im in zip(out, images) if not isinstance(im, torch.Tensor)]
-                tables = [t.view(np.uint8).reshape(-1) for t, d in zip((boxes, gaze, image_of), on_device) if not d] + ([] if per_row is None else [per_row.reshape(-1)])
-                st = None
-                if pixels or tables or not in_place:
-                    # everything that comes from the host travels in ONE pinned staging buffer and one copy: pixels, frame table, host tables
-                    blobs = [a for _, a in pixels] + [table.view(np.uint8).reshape(-1)] + tables
-                    offs, total = _layout([b.size for b in blobs])
-                    st = self._ring.take(total, dev, main)
-                    for b, o in zip(blobs, offs):
-                        st.host[o:o + b.size] = b
-                    st.send(total)
-                    for (dst, a), o in zip(pixels, offs):          # out of the stage (the next calls reuse it) into the tensor handed back
-                        dst.copy_(st.dev[o:o + a.size].view(dst.shape))
-                    at = [st.base + o for o in offs[len(pixels):]]
-                    images_ptr = at.pop(0)
-                    boxes_ptr = boxes.data_ptr() if on_device[0] else at.pop(0)
-                    gaze_ptr = gaze.data_ptr() if on_device[1] else at.pop(0)
-                    image_of_ptr = image_of.data_ptr() if on_device[2] else at.pop(0)
-                    colors_ptr = None if per_row is None else at.pop(0)
-                else:
+                frame_table = table
+                if in_place and per_row is None and not (isinstance(boxes, np.ndarray) or isinstance(gaze, np.ndarray) or isinstance(image_of, np.ndarray)):
                     # device frames drawn in place, device tables, one colour: only the frame table, and only the first time the frames are seen
-                    tdev = self._cached_image_table(table, dev, nv12)
-                    images_ptr, boxes_ptr, gaze_ptr, image_of_ptr, colors_ptr = tdev.data_ptr(), boxes.data_ptr(), gaze.data_ptr(), image_of.data_ptr(), None
+                    frame_table = self._device_image_table(table, dev, nv12)
+                # everything that comes from the host travels in ONE pinned staging buffer and one copy: pixels, frame table, host tables
+                st, staged, (images_ptr, boxes_ptr, gaze_ptr, image_of_ptr, colors_ptr) = self._ring.upload([a for _, a in pixels], (frame_table, boxes, gaze, image_of, per_row), dev, main)
+                for (dst, _), src in zip(pixels, staged):         # out of the stage (the next calls reuse it) into the tensor handed back
+                    dst.copy_(src.view(dst.shape))
                 flags = torch.empty(n, dtype=torch.int32, device=dev)
                 if n:
                     plan = torch.empty(n, _ARROW_WORDS, dtype=torch.int32, device=dev)
                     vp = C.c_void_p
-                    L.check(entry(vp(main.cuda_stream), vp(images_ptr), len(out), int(table['h'].max()), int(table['w'].max()), vp(boxes_ptr), vp(gaze_ptr),
+                    L.check(entry(vp(main.cuda_stream), vp(images_ptr), len(out), h_max, w_max, vp(boxes_ptr), vp(gaze_ptr),
                                   gaze_stride, vp(image_of_ptr), n, length, min_thickness, ratio, tip_length,
                                   None if one is None else (C.c_ubyte * 3)(*[int(v) for v in one]), vp(colors_ptr), vp(plan.data_ptr()),
                                   vp(flags.data_ptr())), entry.__name__)
@@ -1488,18 +743,14 @@ class DevicePipeline:
                 out = (new(B, max_det, 4, dtype=torch.float32), new(B, max_det, dtype=torch.float32), new(B, max_det), new(B, max_det), new(B), new(B))
                 if B == 0:
                     return out
-                st = None
                 if on_device:
                     pred = pred.float()
                     if pred.stride(2) != 1 or pred.stride(1) < 5 + nc or pred.stride(0) < 0:
                         pred = pred.contiguous()
-                    pred_ptr, image_stride, row_stride = pred.data_ptr(), int(pred.stride(0)), int(pred.stride(1))
+                    image_stride, row_stride = int(pred.stride(0)), int(pred.stride(1))
                 else:
-                    flat = np.ascontiguousarray(pred, dtype=np.float32).reshape(-1).view(np.uint8)
-                    st = self._ring.take(flat.size, dev, main)
-                    st.host[:flat.size] = flat
-                    st.send(flat.size)
-                    pred_ptr, image_stride, row_stride = st.base, N * (5 + nc), 5 + nc
+                    pred, image_stride, row_stride = np.ascontiguousarray(pred, dtype=np.float32), N * (5 + nc), 5 + nc
+                st, _, (pred_ptr,) = self._ring.upload([], (pred,), dev, main)
                 if hw is None:
                     frame_hw = frame_hw.to(torch.int32).contiguous()
                 else:
@@ -1513,10 +764,6 @@ class DevicePipeline:
                 if st is not None:
                     st.read_by(main)
         return out
-
-
-def _host_array(t):
-    return t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)
 
 
 def build_pipeline(transforms):

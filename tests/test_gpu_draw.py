@@ -197,6 +197,30 @@ def test_flag_rows_from_device_tables_write_nothing(fmt, matrix):
         pipe.draw_arrows([], D.BOXES[:1], D.GAZE[:1], [0], device=DEV)
 
 
+@pytest.mark.parametrize('host_table,per_row', [('boxes', False), ('gaze', True), ('image_of', False), (None, True)],
+                         ids=['boxes', 'gaze+colours', 'image_of', 'colours'])
+@pytest.mark.parametrize('fmt', ['bgr', 'nv12'])
+def test_draw_arrows_with_one_table_on_the_host_and_the_rest_on_the_device(fmt, host_table, per_row):
+    """One host operand beside device ones (per-row colours are a host operand too): every operand must be read where it really is -- a host
+    table at its staged address, a device table at its own.  Device frames drawn in place come out as the all-host call's frames bit for bit,
+    and the call takes exactly one stage."""
+    pipe = P.DevicePipeline(chain(32))
+    kw = dict(device=DEV, pixel_format=fmt, matrix='bt709', color=D.COLORS if per_row else None)
+    want, want_flags = pipe.draw_arrows(host_frames(fmt), D.BOXES, D.GAZE, D.IMAGE_OF, **kw)
+    tables = dict(boxes=D.BOXES, gaze=D.GAZE, image_of=D.IMAGE_OF)
+    tables = {name: t if name == host_table else torch.from_numpy(t).to(DEV) for name, t in tables.items()}
+    views, _ = device_frames(fmt, 255)
+    before = pipe._ring.i
+    got, flags = pipe.draw_arrows(views, tables['boxes'], tables['gaze'], tables['image_of'], **kw)
+    assert pipe._ring.i == (before + 1) % pipe.STAGES
+    torch.cuda.synchronize()
+    assert torch.equal(flags.cpu(), want_flags.cpu()) and flags.tolist() == [0] * len(D.ROWS)
+    assert len(got) == len(want) and all(g is v for g, v in zip(got, views))
+    for k, (g, w) in enumerate(zip(got, want)):
+        for a, b in zip((g,) if fmt == 'bgr' else g, (w,) if fmt == 'bgr' else w):
+            assert a.shape == b.shape and torch.equal(a.cpu(), b.cpu()), (host_table, k)
+
+
 # ---------------------------------------------------------------- 2. the entries through ctypes
 def test_plan_descriptors_and_argument_checks():
     lib = L.load()

@@ -152,6 +152,30 @@ def test_an_odd_sized_row_of_a_device_image_table_is_flagged_and_not_read():
         assert rc != L.MCG_OK and b'2^22' in lib.mcg_last_error(), bad
 
 
+@pytest.mark.parametrize('frames_on', ['host', 'device'])
+@pytest.mark.parametrize('fmt', ['bgr', 'nv12'])
+@pytest.mark.parametrize('host_table', ['boxes', 'image_of'])
+def test_head_crops_with_one_table_on_the_host_and_the_other_on_the_device(bgr_frames, host_table, fmt, frames_on):
+    """One host operand beside a device one: every operand must be read where it really is -- the host table at its staged address, the
+    device table at its own.  The result is the all-host call's bit for bit, and the call takes exactly one stage."""
+    pipe = P.DevicePipeline(chain(32))
+    kw = dict(device=DEV, pixel_format=fmt, matrix='bt709')
+    host = bgr_frames['bt709'] if fmt == 'bgr' else N.FRAMES
+    want = pipe.head_crops(host, N.BOXES, N.IMAGE_OF, **kw)
+    if frames_on == 'host':
+        frames = host
+    else:
+        frames = [torch.from_numpy(f).to(DEV) for f in host] if fmt == 'bgr' else [device_planes(k) for k in range(len(N.FRAMES))]
+    boxes = N.BOXES if host_table == 'boxes' else torch.from_numpy(N.BOXES).to(DEV)
+    image_of = N.IMAGE_OF if host_table == 'image_of' else torch.from_numpy(N.IMAGE_OF).to(DEV)
+    before = pipe._ring.i
+    got = pipe.head_crops(frames, boxes, image_of, **kw)
+    assert pipe._ring.i == (before + 1) % pipe.STAGES
+    torch.cuda.synchronize()
+    assert got[4].tolist() == [0] * len(N.CASES) and got[3].cpu().tolist() == N.WINDOWS.tolist()
+    same(got, want, f'{host_table} on the host, frames on the {frames_on}')
+
+
 # ---------------------------------------------------------------- 2. nothing is read on the host
 def test_nv12_head_crops_capture_in_a_graph_and_reuse_the_frame_table(bgr_frames):
     """Device surfaces and device tables: the first call uploads the frame table (32 bytes per surface), the second finds it -- no pixel, no
