@@ -685,6 +685,62 @@ int mcg_detect_heads(mcg_stream s, const float* pred_dev, int num_images, int nu
                      int32_t* image_of_dev /* [B][max_det] */, int32_t* counts_dev /* [B] */, int32_t* flags_dev /* [B] or NULL */,
                      void* ws_dev, size_t ws_bytes);
 
+/* ---------------------------------------------------------------- the detector's input (additions to ABI 18; nothing above changes)
+ * What the demo's head detector reads is not a frame: LoadImages letterboxes it (MCGaze_demo/yolo_head/utils/datasets.py:185-189, 810-840),
+ * reverses the channels into planes (:188) and detect.py:64-65 turns the bytes into half or float in [0, 1].  mcg_letterbox_frames does all of
+ * that for a batch of frames in device memory in ONE launch; mcg_letterbox_frames_nv12 reads a decoder's NV12 surfaces through the per-tap
+ * conversion above.  cv2.resize and cv2.copyMakeBorder are restated, not linked: parity with cv2's binary is NOT claimed and is not pinned on
+ * any machine this was built on (the caveat the resize of mcg_preprocess_frames carries).
+ * GEOMETRY, on the host, in python floats (IEEE doubles; round() rounds half to even) -- mcgaze_amd/head_detect.py::letterbox_geometry is
+ * letterbox(img, new_shape, color=(114, 114, 114), auto, scaleFill=False, scaleup, stride) line for line:
+ *   r = min(new_h / h, new_w / w);  scaleup false: r = min(r, 1.0)
+ *   unpad_w = int(round(w * r));  unpad_h = int(round(h * r))
+ *   dw = new_w - unpad_w;  dh = new_h - unpad_h;  auto: dw %= stride, dh %= stride;  dw /= 2;  dh /= 2
+ *   top = int(round(dh - 0.1));  bottom = int(round(dh + 0.1));  left = int(round(dw - 0.1));  right = int(round(dw + 0.1))
+ *   out_h = top + unpad_h + bottom;  out_w = left + unpad_w + right
+ * An integer new_shape is a square.  scaleFill is not offered.  The entry takes the RESULT per frame: (unpad_h, unpad_w) as the out_h / out_w
+ * of the frame descriptor, and top, left.
+ * PIXELS.  dst is [num_frames][3][out_h][out_w].  Output pixel (y, x) of a frame lies inside its rectangle iff top <= y < top + unpad_h and
+ * left <= x < left + unpad_w.  Inside, it is the WHOLE frame (the descriptor's crop fields are not read) resized to (unpad_h, unpad_w) by the
+ * fixed-point bilinear of mcg_preprocess_frames: coefficients of column x - left for unpad_w <- w and of row y - top for unpad_h <- h
+ * (source coordinate (d + 0.5) * (src / dst) - 0.5 in double, cast to float, floor + fraction, clamped to the frame with a zero fraction at
+ * the borders, 11-bit coefficients rounded half to even), the horizontal pass in 32-bit integers, then
+ * uchar((((b0 * (S0 >> 4)) >> 16) + ((b1 * (S1 >> 4)) >> 16) + 2) >> 2).  Everywhere else it is 114.  Two facts that follow, and are not
+ * special cases of the code: where the frame already has the unpadded size the reference skips cv2.resize -- every fraction is then zero, one
+ * coefficient 2048, and the two passes reproduce the byte; and where cv2 turns an exact 2x INTER_LINEAR reduction into its area path,
+ * (a + b + c + d + 2) >> 2, the formula gives the same value because both coefficients are 1024.
+ * CHANNELS.  The taps are in the frame's order; plane c of dst is channel 2 - c of the tap when swap_rb (img[:, :, ::-1].transpose(2, 0, 1):
+ * RGB planes from BGR frames, and from NV12, whose converted taps are BGR), channel c otherwise (frames that already are RGB).
+ * VALUE, by out_type, of the byte v:
+ *   MCG_LETTERBOX_U8   v                                              -- LoadImages' own output
+ *   MCG_LETTERBOX_F32  (float)v / 255.0f, an IEEE division            -- img.float(); img /= 255.0  (detect.py:64-65)
+ *   MCG_LETTERBOX_F16  that float rounded to the nearest half, ties to even.  For all 256 bytes this is what img.half(); img /= 255.0 gives
+ *                      (torch divides halves in float and rounds once).  v * (1 / 255) is NOT the same value: it differs for 126 bytes.
+ * A descriptor whose rectangle is empty, reaches outside the output or whose frame has no pixels (NV12: an odd size) is not an error of the
+ * launch: the rectangle is clipped to the output, a frame that cannot be read gives 114 everywhere.  The table is in device memory and the
+ * entry does not read it back; mcgaze_amd checks the geometry on the host before it writes the table.  So for ANY table nothing is read
+ * outside [0, h) x [0, w) of a frame (rows pitch bytes apart) and nothing is written outside dst.
+ *   frames_dev  DEVICE array of num_frames descriptors: frame.src (.uv), frame.src_pitch (.uv_pitch), frame.src_h, frame.src_w,
+ *               frame.out_h = unpad_h, frame.out_w = unpad_w, then top, left
+ *   dst         DEVICE, aligned to its element; out_h, out_w >= 1 with out_h * out_w < 2^31
+ *   coef        HOST, as for mcg_preprocess_frames_nv12
+ * num_frames in 0 .. 65535 (0: MCG_OK without a launch).  A null pointer, a bad size, an unknown out_type, a misaligned dst or a coef outside
+ * its bounds return MCG_ERR_ARG before any launch.  One launch, one thread per output pixel (four adjacent pixels for u8 and two for f16 where
+ * out_w and dst allow 4-byte stores); no allocation, no host sync, no state, graph-capturable. */
+enum { MCG_LETTERBOX_U8 = 0, MCG_LETTERBOX_F16 = 1, MCG_LETTERBOX_F32 = 2 };
+typedef struct mcg_letterbox_desc {
+  mcg_frame_desc frame;
+  int top, left;
+} mcg_letterbox_desc;
+typedef struct mcg_nv12_letterbox_desc {
+  mcg_nv12_frame_desc frame;
+  int top, left;
+} mcg_nv12_letterbox_desc;
+int mcg_letterbox_frames(mcg_stream stream, const mcg_letterbox_desc* frames_dev, int num_frames, void* dst, int out_h, int out_w, int out_type,
+                         int swap_rb);
+int mcg_letterbox_frames_nv12(mcg_stream stream, const mcg_nv12_letterbox_desc* frames_dev, int num_frames, void* dst, int out_h, int out_w,
+                              int out_type, int swap_rb, const mcg_yuv_coef* coef);
+
 /* ---------------------------------------------------------------- measurement aids (bench.py)
  * While armed, every launch of the contraction kernel made by THIS engine is bracketed by a hipEvent pair on its launch stream.
  * mcg_engine_profile_stop synchronises, returns per-launch duration (ms), algorithmic FLOPs, algorithmic HBM bytes (inputs and

@@ -22,6 +22,11 @@
 // Both kernels are templates over the pixel SOURCE: packed 8-bit BGR (the entries above), or a video decoder's NV12 surface
 // (mcg_preprocess_frames_nv12, mcg_preprocess_head_crops_nv12), whose four taps are converted to BGR where they are read -- the frame is
 // never converted whole.
+//
+// The detector's input (mcg_letterbox_frames, mcg_letterbox_frames_nv12; at the end of this file): the same taps and the same resize, placed
+// inside a border of 114 and written as bytes, or as byte / 255 in float or half -- what the demo's head detector reads.
+#include <hip/hip_fp16.h>
+
 #include "common.hpp"
 
 struct LinCoef {
@@ -50,6 +55,7 @@ __device__ __forceinline__ LinCoef lin_coef(int d, int dst, int src) {
 struct PackedSource {                                       // 3 interleaved 8-bit channels
   using Frame = mcg_frame_desc;
   using Image = mcg_image_desc;
+  using Letterbox = mcg_letterbox_desc;
   struct Window {
     const unsigned char* base;
     size_t pitch;
@@ -78,6 +84,7 @@ struct PackedSource {                                       // 3 interleaved 8-b
 struct Nv12Source {
   using Frame = mcg_nv12_frame_desc;
   using Image = mcg_nv12_image_desc;
+  using Letterbox = mcg_nv12_letterbox_desc;
   mcg_yuv_coef k;
   struct Window {
     const unsigned char *y, *uv;
@@ -283,4 +290,122 @@ extern "C" int mcg_preprocess_head_crops_nv12(mcg_stream stream, const mcg_nv12_
   if (int rc = check_yuv_coef("mcg_preprocess_head_crops_nv12", coef)) return rc;
   return preprocess_head_crops("mcg_preprocess_head_crops_nv12", "mcg_preprocess_head_crops_nv12 (plan)", Nv12Source{*coef}, stream, images_dev, num_images, boxes_dev, image_of_dev, n, expand,
                                scale_w, scale_h, desc_out_dev, img_hw_dev, scale_factor_dev, flags_dev, dst, pad_h, pad_w, mean, stdinv, to_rgb);
+}
+
+// The detector's input (mcg_letterbox_frames, mcg_letterbox_frames_nv12): the header comment "the detector's input" states the arithmetic.
+// The taps, lin_coef and the two integer passes are preprocess_kernel's; what differs is the rectangle (anywhere inside the output, the
+// rest 114), the value written (the byte, or byte / 255 as float or half) and PX adjacent pixels of a row per thread, so that the 8- and
+// 16-bit outputs leave as 4-byte stores.  Nothing of a descriptor is trusted: the window is the whole frame whatever its crop fields say,
+// a frame that cannot be read is all border, and the rectangle is compared in 64 bits -- so no table makes a thread read outside a frame
+// (lin_coef clamps every tap to [0, src - 1]) or write outside dst (a thread owns output pixels, not source pixels).
+__device__ __forceinline__ bool whole_frame(const mcg_frame_desc& fd) { return fd.src_h > 0 && fd.src_w > 0; }
+__device__ __forceinline__ bool whole_frame(const mcg_nv12_frame_desc& fd) { return fd.src_h > 0 && fd.src_w > 0 && !((fd.src_h | fd.src_w) & 1); }
+
+// byte / 255: an IEEE f32 division (HIP's default; the test over all 256 bytes decides), then ONE rounding to half
+__device__ __forceinline__ float unit_value(int v) {
+#pragma clang fp contract(off)
+  return (float)v / 255.0f;
+}
+
+template <int PX>
+__device__ __forceinline__ void store_values(unsigned char* p, const int v[PX]) {
+  if constexpr (PX == 4) *reinterpret_cast<unsigned int*>(p) = (unsigned)v[0] | (unsigned)v[1] << 8 | (unsigned)v[2] << 16 | (unsigned)v[3] << 24;
+  else p[0] = (unsigned char)v[0];
+}
+template <int PX>
+__device__ __forceinline__ void store_values(__half* p, const int v[PX]) {
+  if constexpr (PX == 2) *reinterpret_cast<__half2*>(p) = __halves2half2(__float2half_rn(unit_value(v[0])), __float2half_rn(unit_value(v[1])));
+  else p[0] = __float2half_rn(unit_value(v[0]));
+}
+template <int PX>
+__device__ __forceinline__ void store_values(float* p, const int v[PX]) {
+  p[0] = unit_value(v[0]);
+}
+
+template <class Source, class T, int PX>
+__global__ __launch_bounds__(256) void letterbox_kernel(const typename Source::Letterbox* __restrict__ frames, T* __restrict__ dst, int out_h,
+                                                        int out_w, int swap_rb, const Source source) {
+#pragma clang fp contract(off)
+  const typename Source::Letterbox ld = frames[blockIdx.y];
+  typename Source::Frame fd = ld.frame;
+  fd.crop_y = 0; fd.crop_x = 0; fd.crop_h = fd.src_h; fd.crop_w = fd.src_w;      // the whole frame
+  const int groups = out_w / PX;                                                    // the entry picks a PX that divides out_w
+  const int idx = blockIdx.x * 256 + threadIdx.x;
+  if (idx >= out_h * groups) return;
+  const int y = idx / groups, x0 = (idx - y * groups) * PX;
+  const long long ry = (long long)y - ld.top;
+  const bool row_inside = whole_frame(fd) && fd.out_h > 0 && fd.out_w > 0 && ry >= 0 && ry < fd.out_h;
+  const typename Source::Window win = source.window(fd);
+  LinCoef cy = {0, 0, 0, 0};
+  if (row_inside) cy = lin_coef((int)ry, fd.out_h, fd.src_h);
+  int v[3][PX];
+#pragma unroll
+  for (int i = 0; i < PX; ++i) {
+    const long long rx = (long long)(x0 + i) - ld.left;
+    if (row_inside && rx >= 0 && rx < fd.out_w) {
+      const LinCoef cx = lin_coef((int)rx, fd.out_w, fd.src_w);
+      int p00[3], p01[3], p10[3], p11[3];
+      source.tap(win, cy.s0, cx.s0, p00);
+      source.tap(win, cy.s0, cx.s1, p01);
+      source.tap(win, cy.s1, cx.s0, p10);
+      source.tap(win, cy.s1, cx.s1, p11);
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        const int h0 = p00[c] * cx.a0 + p01[c] * cx.a1;
+        const int h1 = p10[c] * cx.a0 + p11[c] * cx.a1;
+        v[c][i] = (((cy.a0 * (h0 >> 4)) >> 16) + ((cy.a1 * (h1 >> 4)) >> 16) + 2) >> 2;
+      }
+    } else {
+      v[0][i] = v[1][i] = v[2][i] = 114;
+    }
+  }
+  const size_t plane = (size_t)out_h * out_w;
+  T* out = dst + (size_t)blockIdx.y * 3 * plane + (size_t)y * out_w + x0;
+  store_values<PX>(out, v[swap_rb ? 2 : 0]);
+  store_values<PX>(out + plane, v[1]);
+  store_values<PX>(out + 2 * plane, v[swap_rb ? 0 : 2]);
+}
+
+template <class Source, class T, int PX>
+static void letterbox_launch(const Source& source, mcg_stream stream, const void* frames_dev, int num_frames, void* dst, int out_h, int out_w, int swap_rb) {
+  dim3 grid((out_h * (out_w / PX) + 255) / 256, num_frames);
+  hipLaunchKernelGGL((letterbox_kernel<Source, T, PX>), grid, dim3(256), 0, (hipStream_t)stream,
+                     (const typename Source::Letterbox*)frames_dev, (T*)dst, out_h, out_w, swap_rb, source);
+}
+
+template <class Source>
+static int letterbox_frames(const char* what, const Source& source, mcg_stream stream, const void* frames_dev, int num_frames, void* dst, int out_h,
+                            int out_w, int out_type, int swap_rb) {
+  MCG_CHECK_ARG(frames_dev && dst, "%s: null pointer", what);
+  MCG_CHECK_ARG(num_frames >= 0 && out_h > 0 && out_w > 0 && (long long)out_h * out_w <= 0x7fffffffLL, "%s: bad sizes n=%d out=%dx%d", what,
+                num_frames, out_h, out_w);
+  MCG_CHECK_ARG(num_frames <= 65535, "%s: at most 65535 frames per call (got %d)", what, num_frames);
+  MCG_CHECK_ARG(out_type == MCG_LETTERBOX_U8 || out_type == MCG_LETTERBOX_F16 || out_type == MCG_LETTERBOX_F32, "%s: unknown out_type %d", what, out_type);
+  const size_t elem = out_type == MCG_LETTERBOX_U8 ? 1 : out_type == MCG_LETTERBOX_F16 ? 2 : 4;
+  MCG_CHECK_ARG((uintptr_t)dst % elem == 0, "%s: dst is not aligned to its %zu-byte elements", what, elem);
+  if (num_frames == 0) return MCG_OK;
+  // 4-byte stores need every row of every plane to start on 4 bytes: dst does and out_w is a multiple of the pixels per store
+  const bool wide = (uintptr_t)dst % 4 == 0;
+  if (out_type == MCG_LETTERBOX_U8) {
+    if (wide && out_w % 4 == 0) letterbox_launch<Source, unsigned char, 4>(source, stream, frames_dev, num_frames, dst, out_h, out_w, swap_rb);
+    else letterbox_launch<Source, unsigned char, 1>(source, stream, frames_dev, num_frames, dst, out_h, out_w, swap_rb);
+  } else if (out_type == MCG_LETTERBOX_F16) {
+    if (wide && out_w % 2 == 0) letterbox_launch<Source, __half, 2>(source, stream, frames_dev, num_frames, dst, out_h, out_w, swap_rb);
+    else letterbox_launch<Source, __half, 1>(source, stream, frames_dev, num_frames, dst, out_h, out_w, swap_rb);
+  } else {
+    letterbox_launch<Source, float, 1>(source, stream, frames_dev, num_frames, dst, out_h, out_w, swap_rb);
+  }
+  MCG_CHECK_LAUNCH(what);
+  return MCG_OK;
+}
+
+extern "C" int mcg_letterbox_frames(mcg_stream stream, const mcg_letterbox_desc* frames_dev, int num_frames, void* dst, int out_h, int out_w,
+                                    int out_type, int swap_rb) {
+  return letterbox_frames("mcg_letterbox_frames", PackedSource{}, stream, frames_dev, num_frames, dst, out_h, out_w, out_type, swap_rb);
+}
+
+extern "C" int mcg_letterbox_frames_nv12(mcg_stream stream, const mcg_nv12_letterbox_desc* frames_dev, int num_frames, void* dst, int out_h,
+                                         int out_w, int out_type, int swap_rb, const mcg_yuv_coef* coef) {
+  if (int rc = check_yuv_coef("mcg_letterbox_frames_nv12", coef)) return rc;
+  return letterbox_frames("mcg_letterbox_frames_nv12", Nv12Source{*coef}, stream, frames_dev, num_frames, dst, out_h, out_w, out_type, swap_rb);
 }

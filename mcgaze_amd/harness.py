@@ -21,7 +21,7 @@ import numpy as np
 import torch
 
 from .engine import _upload_table
-from .pipeline import ARROW_COLOR
+from .pipeline import ARROW_COLOR, letterbox_geometry
 
 CLUES = ('face', 'eyes', 'head')
 last_run_stats = {}       # run_annotation's frame-cache counters of the last call (tools/dataset_throughput.py prints them); trunk_frames of run_videos
@@ -670,6 +670,35 @@ def head_boxes_per_frame(boxes, counts):
     return [boxes[b, :int(n)].tolist() for b, n in enumerate(counts)]
 
 
+LETTERBOX_OPTIONS = ('new_shape', 'stride', 'auto', 'scaleup', 'dtype')      # of run_head_video(detections=dict(detector=...)): pipeline.letterbox's
+
+
+def _detector_groups(pipeline, frames, detector, letterbox, source):
+    """The head detector run over a video: yields (raw prediction, in_shape, [(h, w) per frame]) per group of up to DETECT_FRAMES consecutive frames
+    that share one letterboxed shape -- pipeline.letterbox (options ``letterbox``; ``source``: rgb, pixel_format, matrix, device), then
+    ``detector(img)``, which returns the [B, N, 5 + nc] prediction or a tuple / list that starts with it."""
+    geometry = {k: v for k, v in letterbox.items() if k != 'dtype'}
+
+    def run(group, hw):
+        img, _ = pipeline.letterbox(group, **letterbox, **source)
+        pred = detector(img)
+        return pred[0] if isinstance(pred, (tuple, list)) else pred, tuple(img.shape[2:]), hw
+
+    group, hw, shape = [], [], None
+    for t in range(len(frames)):
+        f = frames[t]                                             # fetched (decoded) once for the detector
+        size = _frame_hw(f, source['pixel_format'])
+        g = letterbox_geometry(*size, **geometry)
+        if group and ((g.out_h, g.out_w) != shape or len(group) == DETECT_FRAMES):
+            yield run(group, hw)
+            group, hw = [], []
+        group.append(f)
+        hw.append(size)
+        shape = (g.out_h, g.out_w)
+    if group:
+        yield run(group, hw)
+
+
 def _frame_hw(frame, pixel_format):
     """(h, w) of one frame as run_head_video takes it."""
     if pixel_format == 'nv12':
@@ -706,20 +735,31 @@ def run_head_video(engine, pipeline, frames, boxes_per_frame=None, max_len=100, 
     detections: in place of boxes_per_frame (exactly one of the two is given) a dict(pred=..., in_shape=..., **options): the head detector's
     raw prediction [T, N, 5 + nc] for the T frames, on the host or the device, the (h, w) of its letterboxed input, and options of
     pipeline.detect_heads (conf_thres, iou_thres, only_class, agnostic, max_nms, max_det).  The boxes come from DETECT_FRAMES frames per
-    call of pipeline.detect_heads and one read-back (head_boxes_per_frame); the records are those of the same boxes given as lists."""
+    call of pipeline.detect_heads and one read-back (head_boxes_per_frame); the records are those of the same boxes given as lists.
+    A second form runs the detector too: dict(detector=callable, new_shape=640, stride=32, dtype=torch.float16, auto=True, scaleup=True,
+    **options).  Per group of DETECT_FRAMES frames -- a group ends early where the letterboxed shape changes -- pipeline.letterbox makes the
+    detector's input from the frames (rgb, pixel_format and matrix as above), ``callable(img)`` returns the raw [B, N, 5 + nc] prediction
+    on the device (or a tuple / list whose first item it is), and pipeline.detect_heads reads it with in_shape = img.shape[2:].  pred or
+    in_shape together with detector is a ValueError."""
     smooth = check_smooth('run_head_video', smooth)
     if (boxes_per_frame is None) == (detections is None):
         raise ValueError('run_head_video: give exactly one of boxes_per_frame and detections')
     if detections is not None:
         opts = dict(detections)
-        if 'pred' not in opts or 'in_shape' not in opts:
-            raise ValueError('run_head_video(detections=...): a dict with pred and in_shape')
-        pred, in_shape = opts.pop('pred'), opts.pop('in_shape')
+        if 'detector' in opts:
+            if 'pred' in opts or 'in_shape' in opts:
+                raise ValueError('run_head_video(detections=...): either pred and in_shape, or a detector that makes them')
+            groups = _detector_groups(pipeline, frames, opts.pop('detector'), {k: opts.pop(k) for k in LETTERBOX_OPTIONS if k in opts},
+                                      dict(rgb=rgb, pixel_format=pixel_format, matrix=matrix, device=engine.device))
+        else:
+            if 'pred' not in opts or 'in_shape' not in opts:
+                raise ValueError('run_head_video(detections=...): a dict with pred and in_shape, or with detector')
+            pred, in_shape = opts.pop('pred'), opts.pop('in_shape')
+            groups = ((pred[t0:t0 + DETECT_FRAMES], in_shape, [_frame_hw(frames[t], pixel_format) for t in range(t0, min(t0 + DETECT_FRAMES, len(pred)))])
+                      for t0 in range(0, len(pred), DETECT_FRAMES))
         boxes_per_frame = []
-        for t0 in range(0, len(pred), DETECT_FRAMES):
-            part = pred[t0:t0 + DETECT_FRAMES]
-            hw = np.asarray([_frame_hw(frames[t], pixel_format) for t in range(t0, t0 + len(part))], dtype=np.int32).reshape(-1, 2)
-            got = pipeline.detect_heads(part, in_shape, hw, device=engine.device, **opts)
+        for part, in_shape, hw in groups:
+            got = pipeline.detect_heads(part, in_shape, np.asarray(hw, dtype=np.int32).reshape(-1, 2), device=engine.device, **opts)
             boxes_per_frame += head_boxes_per_frame(got[0], got[4])
     segments = segment_tracks(boxes_per_frame)
     chunks = [(si, a, b, pi) for si, seg in enumerate(segments) for a, b in plan_track_chunks(len(seg['frame_id']), max_len)

@@ -1,9 +1,14 @@
-"""Head boxes from the raw output of the demo's head detector: ``DevicePipeline.detect_heads`` (``mcg_detect_heads``: confidence filter, NMS and
-scale-back; csrc/detect.hip) never leaves the device; ``detect_heads_host`` is the same in numpy, and the option and shape checks they share."""
+"""Around the demo's head detector.  Its input: ``DevicePipeline.letterbox`` (``mcg_letterbox_frames``; csrc/preprocess.hip) turns frames into
+the letterboxed tensor the detector reads, ``letterbox_geometry`` is the reference's size rule and ``letterbox_host`` the same pixels in numpy.
+Its output: ``DevicePipeline.detect_heads`` (``mcg_detect_heads``: confidence filter, NMS and scale-back; csrc/detect.hip) never leaves the
+device; ``detect_heads_host`` is the same in numpy, and the option and shape checks they share."""
+import collections
+
 import numpy as np
 import torch
 
-from .staging import _host_array
+from .nv12 import _nv12_planes, _pixel_format, nv12_to_bgr
+from .staging import _bgr_frame, _host_array
 
 DETECT_MAX_DET = 300                                             # the reference's max_det, and the bound of the entry
 
@@ -113,3 +118,129 @@ def detect_heads_host(pred, in_shape, frame_hw, conf_thres=0.25, iou_thres=0.45,
             n = len(rows)
             boxes[b, :n], scores[b, :n], classes[b, :n], image_of[b, :n], counts[b] = np.rint(v), conf[rows], cls[rows], b, n
     return boxes, scores, classes, image_of, counts, flags
+
+
+# ---------------------------------------------------------------- the detector's input
+LETTERBOX_PAD = 114                                              # letterbox(color=(114, 114, 114))
+LETTERBOX_DTYPES = {torch.uint8: np.uint8, torch.float16: np.float16, torch.float32: np.float32}
+
+LetterboxGeometry = collections.namedtuple('LetterboxGeometry', 'unpad_h unpad_w top bottom left right out_h out_w ratio pad')
+
+
+def _letterbox_options(new_shape, stride):
+    """new_shape (an integer is a square) and stride, checked -> (new_h, new_w, stride)."""
+    shape = (new_shape, new_shape) if np.ndim(new_shape) == 0 else tuple(new_shape)
+    if len(shape) != 2 or any(int(v) != v or v < 1 for v in shape):
+        raise ValueError(f'letterbox: new_shape is a positive integer or (h, w), got {new_shape!r}')
+    if int(stride) != stride or stride < 1:
+        raise ValueError(f'letterbox: stride must be a positive integer, got {stride!r}')
+    return int(shape[0]), int(shape[1]), int(stride)
+
+
+def letterbox_geometry(h, w, new_shape=640, stride=32, auto=True, scaleup=True):
+    """The sizes of letterbox(img, new_shape, color=(114, 114, 114), auto, scaleFill=False, scaleup, stride)
+    (MCGaze_demo/yolo_head/utils/datasets.py:810-840) for an h x w frame, line for line in python floats:
+
+        r = min(new_h / h, new_w / w);  scaleup false: r = min(r, 1.0)
+        unpad_w, unpad_h = int(round(w * r)), int(round(h * r))
+        dw, dh = new_w - unpad_w, new_h - unpad_h;  auto: dw, dh = dw % stride, dh % stride;  dw /= 2;  dh /= 2
+        top, bottom = int(round(dh - 0.1)), int(round(dh + 0.1));  left, right = int(round(dw - 0.1)), int(round(dw + 0.1))
+
+    -> LetterboxGeometry(unpad_h, unpad_w, top, bottom, left, right, out_h, out_w, ratio, pad): the resized frame, the border on each side, the
+    output (top + unpad_h + bottom, left + unpad_w + right) and the reference's other two return values, ratio = (r, r) and pad = (dw, dh)
+    (halved, before rounding).  scaleFill is not offered.  ValueError for sizes that are not positive and for a frame so thin that a
+    resized side rounds to zero, which cv2.resize refuses."""
+    new_h, new_w, stride = _letterbox_options(new_shape, stride)
+    if int(h) != h or int(w) != w or h < 1 or w < 1:
+        raise ValueError(f'letterbox: a frame has a positive (h, w), got ({h!r}, {w!r})')
+    h, w = int(h), int(w)
+    r = min(new_h / h, new_w / w)
+    if not scaleup:
+        r = min(r, 1.0)
+    unpad_w, unpad_h = int(round(w * r)), int(round(h * r))
+    if unpad_w < 1 or unpad_h < 1:
+        raise ValueError(f'letterbox: a {h} x {w} frame in {new_h} x {new_w} would be resized to {unpad_h} x {unpad_w}')
+    dw, dh = new_w - unpad_w, new_h - unpad_h
+    if auto:
+        dw, dh = dw % stride, dh % stride
+    dw, dh = dw / 2, dh / 2
+    top, bottom = int(round(dh - 0.1)), int(round(dh + 0.1))
+    left, right = int(round(dw - 0.1)), int(round(dw + 0.1))
+    return LetterboxGeometry(unpad_h, unpad_w, top, bottom, left, right, top + unpad_h + bottom, left + unpad_w + right, (r, r), (dw, dh))
+
+
+def _letterbox_plan(sizes, new_shape, stride, auto, scaleup):
+    """letterbox_geometry of every (h, w) of ``sizes`` -> (geometries, out_h, out_w); ValueError, naming the shapes, unless they share one output."""
+    geoms = [letterbox_geometry(h, w, new_shape, stride, auto, scaleup) for h, w in sizes]
+    if not geoms:
+        raise ValueError('letterbox: no frames')
+    outs = [(g.out_h, g.out_w) for g in geoms]
+    if len(set(outs)) != 1:
+        raise ValueError(f'letterbox: the frames of one call must share one output shape, got {sorted(set(outs))} for frames {[tuple(s) for s in sizes]}')
+    return geoms, outs[0][0], outs[0][1]
+
+
+def _letterbox_dtype(dtype):
+    """torch.uint8 / float16 / float32, or the numpy type of the same name -> the torch dtype (TypeError for anything else)."""
+    for t, n in LETTERBOX_DTYPES.items():
+        if dtype is t or (not isinstance(dtype, torch.dtype) and np.dtype(dtype) == n):
+            return t
+    raise TypeError(f'letterbox: dtype is uint8, float16 or float32, got {dtype!r}')
+
+
+def _linear_coef(dst, src):
+    """Per destination index of a dst <- src resize: the two source indices and their 11-bit coefficients -- lin_coef of csrc/preprocess.hip
+    (OpenCV's published 8-bit INTER_LINEAR rule, restated): (d + 0.5) * (src / dst) - 0.5 in double, cast to float, floor + fraction, clamped
+    to the image with a zero fraction at the borders, coefficients rounded half to even."""
+    scale = 1.0 / (float(dst) / float(src))
+    f = ((np.arange(dst, dtype=np.float64) + 0.5) * scale - 0.5).astype(np.float32)
+    s = np.floor(f).astype(np.int64)
+    f = f - s.astype(np.float32)
+    edge = (s < 0) | (s >= src - 1)
+    f[edge] = 0
+    s = np.clip(s, 0, src - 1)
+    return s, np.minimum(s + 1, src - 1), np.rint((np.float32(1) - f) * np.float32(2048)).astype(np.int64), np.rint(f * np.float32(2048)).astype(np.int64)
+
+
+def _resize_linear(img, new_h, new_w):
+    """HxWx3 uint8 -> new_h x new_w x 3 uint8 by the two integer passes of the pixel kernels."""
+    x0, x1, ax0, ax1 = _linear_coef(new_w, img.shape[1])
+    y0, y1, ay0, ay1 = _linear_coef(new_h, img.shape[0])
+    src = img.astype(np.int64)
+    hor = src[:, x0] * ax0[None, :, None] + src[:, x1] * ax1[None, :, None]
+    out = (((ay0[:, None, None] * (hor[y0] >> 4)) >> 16) + ((ay1[:, None, None] * (hor[y1] >> 4)) >> 16) + 2) >> 2
+    return out.astype(np.uint8)
+
+
+def letterbox_host(frames, new_shape=640, stride=32, auto=True, scaleup=True, dtype=torch.float16, rgb=False, pixel_format='bgr', matrix='bt601'):
+    """``DevicePipeline.letterbox`` in numpy, bit for bit (the arithmetic: include/mcgaze_hip.h, "the detector's input"), for checks and for
+    users without a GPU: the demo's LoadImages (letterbox, then img[:, :, ::-1].transpose(2, 0, 1); utils/datasets.py:185-189) and the
+    conversion of detect.py:64-65, with cv2.resize and cv2.copyMakeBorder restated, not linked.
+
+    frames: HxWx3 uint8 arrays in cv2's BGR order (rgb=True: RGB, no swap), or with pixel_format='nv12' surfaces as head_crops takes them
+    ((y, uv) pairs or [3H/2, W] arrays, even sizes), converted by ``nv12_to_bgr(..., matrix)``; device tensors are read back.  The frames may
+    differ in size but must share one output shape (ValueError).  dtype: uint8 (the bytes), float32 (byte / 255) or float16 (that float
+    rounded to half: what ``img.half() / 255.0`` gives) -- a torch or numpy type.
+    -> (img [B, 3, out_h, out_w] numpy array, [LetterboxGeometry per frame])."""
+    nv12, _ = _pixel_format(pixel_format, matrix)
+    np_dtype = LETTERBOX_DTYPES[_letterbox_dtype(dtype)]
+    _letterbox_options(new_shape, stride)
+    images = []
+    for k, im in enumerate(frames):
+        if nv12:
+            host = lambda t: _host_array(t) if isinstance(t, torch.Tensor) else t
+            y, uv, _ = _nv12_planes(k, tuple(host(t) for t in im) if isinstance(im, (tuple, list)) else host(im))
+            images.append(nv12_to_bgr(y, uv, matrix))
+        else:
+            images.append(_bgr_frame(k, np.ascontiguousarray(_host_array(im))))
+    geoms, out_h, out_w = _letterbox_plan([im.shape[:2] for im in images], new_shape, stride, auto, scaleup)
+    out = np.full((len(images), out_h, out_w, 3), LETTERBOX_PAD, np.uint8)
+    for k, (im, g) in enumerate(zip(images, geoms)):
+        out[k, g.top:g.top + g.unpad_h, g.left:g.left + g.unpad_w] = _resize_linear(im, g.unpad_h, g.unpad_w)
+    if not (rgb and not nv12):
+        out = out[..., ::-1]
+    out = np.ascontiguousarray(out.transpose(0, 3, 1, 2))
+    if np_dtype is np.uint8:
+        return out, geoms
+    table = np.arange(256, dtype=np.float32) / np.float32(255)        # one IEEE f32 division per byte value, then one rounding to half
+    return table.astype(np_dtype)[out], geoms

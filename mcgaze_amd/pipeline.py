@@ -16,7 +16,8 @@ device as they are, and the kernel writes the model's ``img`` tensor.  There is 
 Head crops (``DevicePipeline.head_crops``): the demo of the reference (MCGaze_demo/demo.ipynb, cell 4) cuts one window per person out of
 every video frame before this chain; there the WINDOW is chosen on the device as well (``mcg_preprocess_head_crops``), from frames and head
 boxes that may both live in device memory already.  ``head_crop_window`` is the same arithmetic on the host, for checks and for drawing.
-Re-exported from beside this module: decoded frames (frame_cache.py), NV12 (nv12.py), arrows (arrows.py), head boxes (head_detect.py), upload (staging.py).
+``DevicePipeline.letterbox`` makes the head detector's input from the same frames and ``detect_heads`` head boxes from its raw output.
+Re-exported from beside this module: decoded frames (frame_cache.py), NV12 (nv12.py), arrows (arrows.py), the detector's two sides (head_detect.py), upload (staging.py).
 
 Randomness: the reference's ``CenterCrop(crop_type='relative_range')`` draws the crop size from the global numpy RNG at TEST
 time too (transforms.py:1126-1130), and ``RandomFlip(flip_ratio=0.0)`` consumes one more uniform
@@ -34,7 +35,8 @@ from . import lib as L
 from .arrows import (ARROW_COLOR, ARROW_COORD, ARROW_SIDE, _arrow_colors, _arrow_params, _arrow_rows,  # noqa: F401
                      arrow_segments, draw_arrows_host, segment_coverage)
 from .frame_cache import FrameCache, _DecodeProcs, decode_image  # noqa: F401
-from .head_detect import DETECT_MAX_DET, _detect_params, _detect_shapes, detect_heads_host  # noqa: F401
+from .head_detect import (DETECT_MAX_DET, LETTERBOX_PAD, LetterboxGeometry, _detect_params, _detect_shapes, _letterbox_dtype,  # noqa: F401
+                          _letterbox_plan, detect_heads_host, letterbox_geometry, letterbox_host)
 from .nv12 import YUV_COEF, _nv12_planes, _pixel_format, _yuv_coef, _yuv_to_bgr, bgr_to_yuv, nv12_to_bgr  # noqa: F401
 from .registry import Registry
 from .staging import _Stage, _StagingRing, _bgr_frame, _host_array, _layout  # noqa: F401
@@ -258,6 +260,11 @@ assert _NV12_IMAGE.itemsize == C.sizeof(L.Nv12ImageDesc) and all(_NV12_IMAGE.fie
 _NV12_DESC = np.dtype([(n, _DESC.fields[n][0]) for n in _DESC.names] + [('uv', np.uint64), ('uv_pitch', np.int32)], align=True)
 assert _NV12_DESC.itemsize == C.sizeof(L.Nv12FrameDesc) and all(_NV12_DESC.fields[n][1] == getattr(L.Nv12FrameDesc, n).offset for n in _NV12_DESC.names)
 _NV12_DESC_WORDS = _NV12_DESC.itemsize // 4
+# the letterbox records: lib.LetterboxDesc / mcg_letterbox_desc and its NV12 twin = a frame descriptor, then the rectangle's corner
+_LETTERBOX, _NV12_LETTERBOX = (np.dtype([('frame', d), ('top', np.int32), ('left', np.int32)], align=True) for d in (_DESC, _NV12_DESC))
+for _d, _c in ((_LETTERBOX, L.LetterboxDesc), (_NV12_LETTERBOX, L.Nv12LetterboxDesc)):
+    assert _d.itemsize == C.sizeof(_c) and all(_d.fields[n][1] == getattr(_c, n).offset for n in _d.names)
+_LETTERBOX_TYPES = {torch.uint8: L.LETTERBOX_U8, torch.float16: L.LETTERBOX_F16, torch.float32: L.LETTERBOX_F32}
 _CROP_WORD = _DESC.fields['crop_y'][1] // 4         # crop_y, crop_x, crop_h, crop_w are consecutive int32 words of a descriptor
 _ARROW = np.dtype([('seg', np.int32, (3, 2, 2)), ('thickness', np.int32)] + [(f, np.int32) for f in ('x0', 'y0', 'x1', 'y1', 'image', 'flag', 'reserved')])
 assert _ARROW.itemsize == C.sizeof(L.ArrowDesc) and all(_ARROW.fields[n][1] == getattr(L.ArrowDesc, n).offset for n in _ARROW.names)
@@ -423,7 +430,7 @@ class DevicePipeline:
         self.collect = self.transforms[-1]
         self._planners = [t.plan for t in self.transforms if type(t) not in (LoadImageFromFile, DefaultFormatBundle, ImageToTensor, Collect)]   # the rest plan nothing
         self._ring = _StagingRing(self.STAGES)                    # run_many and head_crops upload through the same stages
-        self._image_tables = collections.OrderedDict()            # head_crops, draw_arrows: (device, frame table bytes) -> that table on the device
+        self._image_tables = collections.OrderedDict()            # head_crops, draw_arrows, letterbox: (device, table bytes) -> that table on the device
         self._frame_hw_tables = collections.OrderedDict()         # detect_heads: (device, host frame_hw bytes) -> that table on the device
         self._detect_workspaces = collections.OrderedDict()       # detect_heads: (device, B, N) -> scratch of mcg_detect_heads
 
@@ -709,6 +716,60 @@ class DevicePipeline:
                 if st is not None:
                     st.read_by(main)
         return out, flags
+
+    def letterbox(self, frames, new_shape=640, stride=32, auto=True, scaleup=True, dtype=torch.float16, rgb=False, pixel_format='bgr', matrix='bt601',
+                  device='cuda:0', stream=None):
+        """Frames -> the input of the demo's head detector, on the device (mcg_letterbox_frames / mcg_letterbox_frames_nv12: one launch) --
+        ``letterbox_host`` bit for bit: LoadImages' letterbox with a border of 114, RGB planes, and the ``img.half() / 255.0`` of detect.py:64-65
+        (MCGaze_demo/yolo_head/utils/datasets.py:185-189, 810-840).
+
+        frames: what head_crops takes as ``images`` -- HxWx3 uint8 frames in cv2's BGR order (rgb=True: RGB), or with pixel_format='nv12' a
+        decoder's surfaces ((y, uv) pairs or [3H/2, W], even sizes; ``matrix`` names the coefficients, rgb is ignored).  A numpy frame goes up
+        through the staging ring, a CUDA tensor is read where it is, its row pitch taken from the tensor.  new_shape, stride, auto, scaleup:
+        ``letterbox_geometry``'s, worked out on the host from the shapes alone.  The frames of one call may differ in size but must share ONE
+        output shape (ValueError naming the shapes); that, the frames (TypeError / ValueError as in head_crops) and the options are checked
+        before anything is launched.  dtype: torch.uint8 (the bytes), float32 (byte / 255) or float16 (that float rounded to half).
+        -> (img [B, 3, out_h, out_w] on the device, [LetterboxGeometry per frame] on the host).  ``img.shape[2:]`` is detect_heads' in_shape.
+        The descriptor table of device frames is kept per content, so a call on device frames touches the host nowhere after the first and can
+        be captured in a graph."""
+        lib = L.load()
+        nv12, coef = _pixel_format(pixel_format, matrix)
+        out_dtype = _letterbox_dtype(dtype)
+        entry, more = (lib.mcg_letterbox_frames_nv12, (C.byref(L.YuvCoef(**coef)),)) if nv12 else (lib.mcg_letterbox_frames, ())
+        dev = _device(device)
+        frames = list(frames)
+        planes = [_nv12_planes(k, im, dev) for k, im in enumerate(frames)] if nv12 else None
+        dev = _device(dev, entry.__name__)
+        table, parts = _image_table(frames, dev, planes)
+        geoms, out_h, out_w = _letterbox_plan([(int(r['h']), int(r['w'])) for r in table], new_shape, stride, auto, scaleup)
+        desc = np.zeros(len(frames), dtype=_NV12_LETTERBOX if nv12 else _LETTERBOX)
+        fd = desc['frame']
+        fd['src'], fd['src_pitch'] = (table['y'], table['pitch_y']) if nv12 else (table['src'], table['pitch'])
+        if nv12:
+            fd['uv'], fd['uv_pitch'] = table['uv'], table['pitch_uv']
+        fd['src_h'] = fd['crop_h'] = table['h']
+        fd['src_w'] = fd['crop_w'] = table['w']
+        fd['out_h'], fd['out_w'] = [g.unpad_h for g in geoms], [g.unpad_w for g in geoms]
+        desc['top'], desc['left'] = [g.top for g in geoms], [g.left for g in geoms]
+        with torch.cuda.device(dev):
+            main = _caller_stream(stream, dev)
+            with torch.cuda.stream(main):
+                # device frames: only the descriptor table comes from the host, and only the first time these frames and sizes are seen
+                frame_table = desc if parts else self._kept(self._image_tables, (dev.index, desc.tobytes(), 'letterbox', nv12),
+                                                            lambda: torch.from_numpy(desc.view(np.uint8).reshape(-1).copy()).to(dev))
+
+                def name_frames(at):                              # a host frame's address: where its bytes land in the device twin
+                    for (k, f, _), a in zip(parts, at):
+                        fd['uv' if f == 'uv' else 'src'][k] = a
+
+                st, _, (desc_ptr,) = self._ring.upload([a for _, _, a in parts], (frame_table,), dev, main, name_frames)
+                img = torch.empty(len(frames), 3, out_h, out_w, dtype=out_dtype, device=dev)
+                vp = C.c_void_p
+                L.check(entry(vp(main.cuda_stream), vp(desc_ptr), len(frames), vp(img.data_ptr()), out_h, out_w, _LETTERBOX_TYPES[out_dtype],
+                              int(not (rgb and not nv12)), *more), entry.__name__)
+                if st is not None:
+                    st.read_by(main)
+        return img, geoms
 
     def detect_heads(self, pred, in_shape, frame_hw, conf_thres=0.25, iou_thres=0.45, only_class=1, agnostic=False, max_nms=30000, max_det=300,
                      device='cuda:0', stream=None):

@@ -5,6 +5,7 @@ label files in, per-person per-frame gaze out -- and, with --draw, the frames wi
 usage: demo_video.py FRAMES_DIR LABELS_DIR CONFIG CHECKPOINT --out gaze.json [--precision f16x3] [--device cuda:0] [--max-len 100]
                      [--batch-frames 448] [--head-class 1] [--ext jpg] [--smooth ALPHA] [--nv12 WxH FILE] [--matrix bt601] [--draw OUT]
                      [--color B,G,R] [--predictions DIR --in-shape HxW [--conf-thres 0.25] [--iou-thres 0.45]]
+                     [--detector MODULE:FACTORY [--img-size 640] [--half]]
 
 FRAMES_DIR holds 0.<ext>, 1.<ext>, ... (the demo's `frames/`), LABELS_DIR holds 0.txt, 1.txt, ... with lines `class x1 y1 x2 y2` in pixels
 (the demo's `result/labels/`); a frame without a label file shows no head.  CONFIG is the L2CS config, whose test pipeline the demo runs
@@ -24,13 +25,20 @@ the arrows' colour (default: the demo's 230,253,11).
 the [N, 5 + nc] (or [1, N, 5 + nc]) prediction of frame t, as the YOLOv5 model returns it before non_max_suppression.  --in-shape HxW is
 the size of the letterboxed image the detector saw (e.g. 384x640 for 1080p frames).  The confidence filter, NMS and the scale-back into the
 frame run on the device (harness.run_head_video(detections=...), pipeline.detect_heads); --head-class, --conf-thres and --iou-thres are
-the detector's options."""
+the detector's options.
+--detector MODULE:FACTORY: the detector itself runs (LABELS_DIR is then `-`, and --predictions is not given): MODULE is imported,
+`FACTORY()` returns a callable that takes the letterboxed batch [B, 3, h, w] on the device -- RGB planes in [0, 1], half with --half, else
+float -- and returns the raw [B, N, 5 + nc] prediction (or a tuple / list that starts with it).  The letterbox (--img-size, the demo's 640,
+stride 32), the filter, NMS and the scale-back run on the device (harness.run_head_video(detections=dict(detector=...)),
+pipeline.letterbox and pipeline.detect_heads); the network is the caller's."""
 import argparse
+import importlib
 import json
 import os
 import sys
 
 import numpy as np
+import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
@@ -106,6 +114,14 @@ def write_annotated(out_dir, annotated, nv12):
             f.write(rgb.tobytes())
 
 
+def load_detector(spec):
+    """'package.module:factory' -> factory()"""
+    module, _, factory = spec.partition(':')
+    if not module or not factory:
+        raise ValueError(f'expected MODULE:FACTORY, got {spec!r}')
+    return getattr(importlib.import_module(module), factory)()
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
     ap.add_argument('frames_dir')
@@ -128,9 +144,14 @@ def main(argv=None):
     ap.add_argument('--in-shape', default=None, metavar='HxW', help='the letterboxed input of the detector behind --predictions')
     ap.add_argument('--conf-thres', type=float, default=0.25)
     ap.add_argument('--iou-thres', type=float, default=0.45)
+    ap.add_argument('--detector', default=None, metavar='MODULE:FACTORY', help='run the head detector FACTORY() returns, instead of LABELS_DIR (then -)')
+    ap.add_argument('--img-size', type=int, default=640, help='the letterbox size of --detector')
+    ap.add_argument('--half', action='store_true', help='--detector reads half instead of float')
     a = ap.parse_args(argv)
     if (a.predictions is None) != (a.in_shape is None):
         raise SystemExit('--predictions and --in-shape go together')
+    if a.detector is not None and a.predictions is not None:
+        raise SystemExit('--detector takes the place of --predictions')
     draw = None
     if a.draw is not None:
         draw = {} if a.color is None else dict(color=parse_color(a.color))
@@ -144,7 +165,10 @@ def main(argv=None):
             raise SystemExit(f'{a.frames_dir}: {n} .{a.ext} files but no {missing[0]}.{a.ext} -- frames are numbered from 0 without gaps')
         frames = Frames(a.frames_dir, n, a.ext)
     per_frame = detections = None
-    if a.predictions is not None:
+    if a.detector is not None:
+        detections = dict(detector=load_detector(a.detector), new_shape=a.img_size, dtype=torch.float16 if a.half else torch.float32,
+                          only_class=a.head_class, conf_thres=a.conf_thres, iou_thres=a.iou_thres)
+    elif a.predictions is not None:
         in_h, _, in_w = a.in_shape.lower().partition('x')
         raw = [np.load(os.path.join(a.predictions, f'{t}.npy')) for t in range(n)]
         pred = np.stack([r.reshape(r.shape[-2], r.shape[-1]) for r in raw]) if n else np.zeros((0, 1, 6), np.float32)
