@@ -741,6 +741,60 @@ int mcg_letterbox_frames(mcg_stream stream, const mcg_letterbox_desc* frames_dev
 int mcg_letterbox_frames_nv12(mcg_stream stream, const mcg_nv12_letterbox_desc* frames_dev, int num_frames, void* dst, int out_h, int out_w,
                               int out_type, int swap_rb, const mcg_yuv_coef* coef);
 
+/* ---------------------------------------------------------------- head identities across frames (additions to ABI 18; nothing above changes)
+ * mcg_detect_heads gives the heads of each frame; which box of frame t is the person of which box of frame t - 1 the demo decides by the
+ * NUMBER of heads and their x1 order (harness.segment_tracks, cell 1), on the host.  mcg_track_heads is that decision on the device, by
+ * overlap: ONE launch, one workgroup per sequence, the frames of the call walked in order inside the kernel, no allocation, no host sync,
+ * graph-capturable.  The result is a pure function of (state, boxes, counts); it does not depend on launch geometry or scheduling.
+ * A SEQUENCE is one camera.  Its state is a mcg_track_header followed by `slots` mcg_track_slot records (1 <= slots <= 64); sequence q of a
+ * state lies mcg_track_state_bytes(1, slots) bytes behind sequence q - 1.  A slot is LIVE iff id > 0 and FREE iff id == 0; ids are handed
+ * out per sequence as 1, 2, 3, ...: a birth gets ++next_id.  All zero bytes are the empty state.  The reserved words are neither read nor
+ * written.
+ * THE ARITHMETIC, per sequence q and per frame t = 0 .. num_frames - 1 in order.  Every operation is f32 and uncontracted (no FMA);
+ * thr = (float)match_iou.  c = counts_dev[q * T + t], n = min(max(c, 0), D); detection d < n is the box
+ * boxes_dev + (q * T + t) * frame_stride + 4 * d (floats), x1 y1 x2 y2, in the order mcg_detect_heads emits them: best first.
+ *  1. Detection d is USABLE iff its four coordinates are finite.  Rows d >= n are never read.
+ *  2. For a live slot a and a usable detection b, with the operations of mcg_detect_heads' NMS:
+ *       area = (x2 - x1) * (y2 - y1) of each;  w = max(0, min(a.x2, b.x2) - max(a.x1, b.x1)), h likewise;  inter = w * h;
+ *       iou = inter / (area_a + area_b - inter) + 0.0f         -- an IEEE division; the + 0.0f makes -0 and +0 one value
+ *     The pair is a CANDIDATE iff iou > thr.  A NaN (0 / 0) never is.  A candidate's iou is >= 0.
+ *  3. Greedy match: while a candidate exists whose slot and detection are both unmatched, the one with the largest iou, ties by the LOWER
+ *     slot, then the LOWER detection, is matched.  A matched slot takes the detection's box and age = 0.
+ *  4. Every live slot left unmatched gets age += 1 and, if age > max_age, is freed: id = 0, age = 0, box zeroed.  A slot that coasts keeps
+ *     its last box: there is no motion model.
+ *  5. Births: the unmatched usable detections, in index order, each take the LOWEST free slot -- those freed in step 4 of this frame
+ *     included: id = ++next_id, age = 0, the detection's box.  A detection that finds no free slot is dropped.
+ *  6. Row s of frame (q, t) of the outputs, for a slot matched or born in this frame by detection d: slot_boxes = d's box,
+ *     image_of = q * T + t, det_of = d; for every other slot a zero box, image_of = -1, det_of = -1 -- the rows the head-crop and draw entries
+ *     flag as unusable, so slot_boxes as [Q * T * S][4] and image_of as [Q * T * S] feed them with no read-back when the frames of the
+ *     call are their images.  For every slot: track_id = its id after the frame (0: free), age = its age (-1: free).
+ *     flags (q, t): bit 1 a detection was dropped for want of a slot, bit 2 a row d < n was not usable, bit 4 c lay outside 0 .. D.
+ * After the call: header.frames_seen += num_frames.
+ *   boxes_dev   DEVICE f32 [Q][T][D][4]: frames frame_stride >= 4 * D floats apart, sequence q at q * T * frame_stride
+ *   counts_dev  DEVICE int32 [Q][T]
+ *   state_dev   DEVICE, 16-byte aligned, mcg_track_state_bytes(Q, slots) bytes: read and updated in place
+ *   slot_boxes_dev [Q][T][S][4] f32; image_of_dev, track_id_dev, age_dev, det_of_dev [Q][T][S] int32; flags_dev [Q][T] int32: written in full
+ * num_sequences in 0 .. 65535 (0: MCG_OK without a launch) with Q * T * S < 2^31.  slots outside 1 .. 64, max_det outside 1 .. 1024,
+ * num_frames < 1, max_age < 0, a match_iou that is not finite, a null pointer, a misaligned state or a frame_stride below 4 * D return
+ * MCG_ERR_ARG before any launch.  A match round costs one pass over the slots x detections pairs on one compute unit; there are at most
+ * min(slots, n) rounds per frame.  mcgaze_amd/head_detect.py::track_heads_host is the same on the host, bit for bit. */
+typedef struct mcg_track_header {
+  int32_t next_id;      /* ids handed out so far: the next birth gets next_id + 1 */
+  int32_t frames_seen;
+  int32_t reserved[2];
+} mcg_track_header;
+typedef struct mcg_track_slot {
+  float box[4];         /* x1 y1 x2 y2 of the last match; zero while free */
+  int32_t id;           /* 0: free */
+  int32_t age;          /* frames since the last match; 0 while free */
+  int32_t reserved[2];
+} mcg_track_slot;
+size_t mcg_track_state_bytes(int num_sequences, int slots);   /* 0 for sizes the entry refuses */
+int mcg_track_heads(mcg_stream s, const float* boxes_dev, long long frame_stride, const int32_t* counts_dev, int num_sequences, int num_frames,
+                    int max_det, int slots, double match_iou, int max_age, void* state_dev,
+                    float* slot_boxes_dev /* [Q][T][S][4] */, int32_t* image_of_dev /* [Q][T][S] */, int32_t* track_id_dev /* [Q][T][S] */,
+                    int32_t* age_dev /* [Q][T][S] */, int32_t* det_of_dev /* [Q][T][S] */, int32_t* flags_dev /* [Q][T] */);
+
 /* ---------------------------------------------------------------- measurement aids (bench.py)
  * While armed, every launch of the contraction kernel made by THIS engine is bracketed by a hipEvent pair on its launch stream.
  * mcg_engine_profile_stop synchronises, returns per-launch duration (ms), algorithmic FLOPs, algorithmic HBM bytes (inputs and

@@ -21,7 +21,7 @@ import numpy as np
 import torch
 
 from .engine import _upload_table
-from .pipeline import ARROW_COLOR, letterbox_geometry
+from .pipeline import ARROW_COLOR, _track_params, letterbox_geometry
 
 CLUES = ('face', 'eyes', 'head')
 last_run_stats = {}       # run_annotation's frame-cache counters of the last call (tools/dataset_throughput.py prints them); trunk_frames of run_videos
@@ -670,6 +670,66 @@ def head_boxes_per_frame(boxes, counts):
     return [boxes[b, :int(n)].tolist() for b, n in enumerate(counts)]
 
 
+def tracks_from_slots(slot_boxes, track_id, image_of):
+    """The slot tables of a whole video as pipeline.track_heads / track_heads_host give them -- slot_boxes [T, S, 4], track_id [T, S] and
+    image_of [T, S], numpy arrays or device tensors (chunks of frames concatenated; device tensors come back in ONE copy) -> the tracks in
+    segment_tracks' format, one person each: dict(id=track id, frame_id=[t, ...], boxes=[[[x1, y1, x2, y2], ...]]) in ascending id order.
+    frame_id holds the frames the track was matched (or born) in, image_of >= 0; a frame it coasted through is left out."""
+    if isinstance(slot_boxes, torch.Tensor) and slot_boxes.is_cuda and slot_boxes.ndim == 3 and slot_boxes.dtype == torch.float32:
+        dev = slot_boxes.device
+        words = torch.cat([slot_boxes.contiguous().view(torch.int32), track_id.to(dev, torch.int32)[..., None], image_of.to(dev, torch.int32)[..., None]],
+                          dim=2).cpu().numpy()
+        slot_boxes, track_id, image_of = np.ascontiguousarray(words[..., :4]).view(np.float32), words[..., 4], words[..., 5]
+    slot_boxes, track_id, image_of = np.asarray(_host(slot_boxes), dtype=np.float32), np.asarray(_host(track_id)), np.asarray(_host(image_of))
+    if slot_boxes.ndim != 3 or slot_boxes.shape[2] != 4 or track_id.shape != slot_boxes.shape[:2] or image_of.shape != slot_boxes.shape[:2]:
+        raise ValueError(f'tracks_from_slots: slot_boxes [T, S, 4], track_id [T, S] and image_of [T, S], got {slot_boxes.shape}, {track_id.shape} '
+                         f'and {image_of.shape}')
+    tracks = {}
+    for t, s in zip(*np.nonzero(image_of >= 0)):                  # row-major: frames in order
+        k = int(track_id[t, s])
+        tr = tracks.setdefault(k, dict(id=k, frame_id=[], boxes=[[]]))
+        tr['frame_id'].append(int(t))
+        tr['boxes'][0].append(slot_boxes[t, s].tolist())
+    return [tracks[k] for k in sorted(tracks)]
+
+
+class _HeadTracker:
+    """run_head_video(track=...): pipeline.track_heads over a video, DETECT_FRAMES frames at most per call, the state carried from call to call
+    and every table left on the device until ``tracks``."""
+
+    def __init__(self, pipeline, track, device):
+        self.options = {} if track is True else dict(track)
+        if track is False or set(self.options) - {'slots', 'match_iou', 'max_age'}:
+            raise ValueError(f'run_head_video: track is None, True or a dict of slots, match_iou and max_age, got {track!r}')
+        self.slots = _track_params(**self.options)[0]
+        self.pipeline, self.device, self.state, self.parts, self.frames = pipeline, device, None, [], 0
+
+    def feed(self, boxes, counts):
+        """The next frames: boxes [T, D, 4] and counts [T], on the host or the device."""
+        got = self.pipeline.track_heads(boxes, counts, state=self.state, device=self.device, **self.options)
+        self.state = got[6]
+        self.parts.append((got[0], got[2], got[1], got[5]))
+        self.frames += int(counts.shape[0])
+
+    def feed_lists(self, boxes_per_frame):
+        width = max([1] + [len(b) for b in boxes_per_frame])
+        table, counts = np.zeros((len(boxes_per_frame), width, 4), np.float32), np.asarray([len(b) for b in boxes_per_frame], dtype=np.int32)
+        for t, b in enumerate(boxes_per_frame):
+            table[t, :len(b)] = np.asarray(b, dtype=np.float32).reshape(-1, 4)
+        for t0 in range(0, len(table), DETECT_FRAMES):
+            self.feed(table[t0:t0 + DETECT_FRAMES], counts[t0:t0 + DETECT_FRAMES])
+
+    def tracks(self):
+        if not self.parts:
+            return []
+        slot_boxes, track_id, image_of, flags = (torch.cat([p[k] for p in self.parts]) for k in range(4))
+        full = np.flatnonzero(_host(flags) & 1)
+        if len(full):
+            raise ValueError(f'run_head_video(track=...): frame {int(full[0])} shows more heads than the tracker has free slots (slots={self.slots}); '
+                             'give track=dict(slots=...) more')
+        return tracks_from_slots(slot_boxes, track_id, image_of)
+
+
 LETTERBOX_OPTIONS = ('new_shape', 'stride', 'auto', 'scaleup', 'dtype')      # of run_head_video(detections=dict(detector=...)): pipeline.letterbox's
 
 
@@ -708,7 +768,7 @@ def _frame_hw(frame, pixel_format):
 
 
 def run_head_video(engine, pipeline, frames, boxes_per_frame=None, max_len=100, batch_frames=448, expand=0.8, rgb=False, smooth=None, pixel_format='bgr',
-                   matrix='bt601', detections=None, draw=None):
+                   matrix='bt601', detections=None, track=None, draw=None):
     """Steps 3-4 of the demo from what its users hold -- the video's frames and one head box per person per frame -- to per-person gaze:
     segment_tracks (cell 1), the head windows cut, resized and normalised on the device (pipeline.head_crops: cell 4's crop arithmetic and
     ``cfg.data.test.pipeline[1:]``), run_tracks (cell 4's loop, batched), head_arrows (cell 5's end points).
@@ -740,10 +800,18 @@ def run_head_video(engine, pipeline, frames, boxes_per_frame=None, max_len=100, 
     **options).  Per group of DETECT_FRAMES frames -- a group ends early where the letterboxed shape changes -- pipeline.letterbox makes the
     detector's input from the frames (rgb, pixel_format and matrix as above), ``callable(img)`` returns the raw [B, N, 5 + nc] prediction
     on the device (or a tuple / list whose first item it is), and pipeline.detect_heads reads it with in_shape = img.shape[2:].  pred or
-    in_shape together with detector is a ValueError."""
+    in_shape together with detector is a ValueError.
+    track: None (everything above), True, or a dict of pipeline.track_heads' options (slots, match_iou, max_age): identities come from the
+    tracker on the device (mcg_track_heads) instead of segment_tracks -- a person keeps ONE track while others enter, leave or cross, and
+    through up to max_age missed detections.  The tracker runs per DETECT_FRAMES frames with its state carried along: with detections= it
+    reads detect_heads' outputs where they are, and what is read back are the slot tables (tracks_from_slots) and the flags; boxes_per_frame
+    is padded to the largest count and uploaded.  -> one record per track in ascending id order, id = the track's id, frame_id = the frames
+    it was matched in (a frame it coasted through is left out); everything downstream is as above, and in a frame the tracks are drawn in
+    ascending id.  ValueError, naming the frame and ``slots``, where a frame shows more heads than there are free slots."""
     smooth = check_smooth('run_head_video', smooth)
     if (boxes_per_frame is None) == (detections is None):
         raise ValueError('run_head_video: give exactly one of boxes_per_frame and detections')
+    tracker = None if track is None else _HeadTracker(pipeline, track, engine.device)
     if detections is not None:
         opts = dict(detections)
         if 'detector' in opts:
@@ -760,8 +828,16 @@ def run_head_video(engine, pipeline, frames, boxes_per_frame=None, max_len=100, 
         boxes_per_frame = []
         for part, in_shape, hw in groups:
             got = pipeline.detect_heads(part, in_shape, np.asarray(hw, dtype=np.int32).reshape(-1, 2), device=engine.device, **opts)
-            boxes_per_frame += head_boxes_per_frame(got[0], got[4])
-    segments = segment_tracks(boxes_per_frame)
+            if tracker is None:
+                boxes_per_frame += head_boxes_per_frame(got[0], got[4])
+            else:
+                tracker.feed(got[0], got[4])
+    if tracker is None:
+        segments = segment_tracks(boxes_per_frame)
+    else:
+        if detections is None:
+            tracker.feed_lists(boxes_per_frame)
+        segments, boxes_per_frame = tracker.tracks(), range(tracker.frames)
     chunks = [(si, a, b, pi) for si, seg in enumerate(segments) for a, b in plan_track_chunks(len(seg['frame_id']), max_len)
               for pi in range(len(seg['boxes']))]
     pieces = {}                                        # (segment, person) -> list of (record, crop) in chunk order
@@ -802,7 +878,7 @@ def run_head_video(engine, pipeline, frames, boxes_per_frame=None, max_len=100, 
             head_box = np.asarray(person, dtype=np.float32).reshape(-1, 4)
             if smooth is not None:
                 rec['fused_smooth'] = smooth_host(rec['fused'], smooth)
-            out.append(dict(id=(si, pi), **rec, frame_id=list(seg['frame_id']), head_box=head_box, crop=np.concatenate([c for _, c in got]),
+            out.append(dict(id=(si, pi) if tracker is None else seg['id'], **rec, frame_id=list(seg['frame_id']), head_box=head_box, crop=np.concatenate([c for _, c in got]),
                             arrow=head_arrows(person, rec['fused' if smooth is None else 'fused_smooth'])))
     if draw is None:
         return out

@@ -1,7 +1,8 @@
 """Around the demo's head detector.  Its input: ``DevicePipeline.letterbox`` (``mcg_letterbox_frames``; csrc/preprocess.hip) turns frames into
 the letterboxed tensor the detector reads, ``letterbox_geometry`` is the reference's size rule and ``letterbox_host`` the same pixels in numpy.
 Its output: ``DevicePipeline.detect_heads`` (``mcg_detect_heads``: confidence filter, NMS and scale-back; csrc/detect.hip) never leaves the
-device; ``detect_heads_host`` is the same in numpy, and the option and shape checks they share."""
+device; ``detect_heads_host`` is the same in numpy, and the option and shape checks they share.  Behind it: ``DevicePipeline.track_heads``
+(``mcg_track_heads``; csrc/track.hip) gives the heads of consecutive frames one identity per person; ``track_heads_host`` is the same in numpy."""
 import collections
 
 import numpy as np
@@ -120,8 +121,128 @@ def detect_heads_host(pred, in_shape, frame_hw, conf_thres=0.25, iou_thres=0.45,
     return boxes, scores, classes, image_of, counts, flags
 
 
+# ---------------------------------------------------------------- identities across frames
+TRACK_MAX_SLOTS, TRACK_MAX_DET = 64, 1024                        # the bounds of mcg_track_heads
+TRACK_HEADER_WORDS, TRACK_SLOT_WORDS = 4, 8                      # mcg_track_header / mcg_track_slot in int32 words: next_id frames_seen - - | box[4] id age - -
+
+
+def track_state_words(slots):
+    """int32 words of one sequence's tracker state (mcg_track_state_bytes(1, slots) / 4): a state is an int32 [Q, words] array, zeros when empty."""
+    return TRACK_HEADER_WORDS + TRACK_SLOT_WORDS * int(slots)
+
+
+def _track_params(slots=16, match_iou=0.3, max_age=5):
+    """The options of track_heads_host / DevicePipeline.track_heads, checked -> (slots, match_iou, max_age)."""
+    if isinstance(slots, bool) or int(slots) != slots or not 1 <= slots <= TRACK_MAX_SLOTS:
+        raise ValueError(f'track_heads: slots in 1 .. {TRACK_MAX_SLOTS}, got {slots!r}')
+    match_iou = float(match_iou)
+    if not np.isfinite(match_iou):
+        raise ValueError(f'track_heads: match_iou must be finite, got {match_iou}')
+    if isinstance(max_age, bool) or int(max_age) != max_age or max_age < 0 or max_age > 0x7fffffff:
+        raise ValueError(f'track_heads: max_age is a number of frames, 0 or more, got {max_age!r}')
+    return int(slots), match_iou, int(max_age)
+
+
+def _track_shapes(boxes_shape, counts_shape, state_shape, slots):
+    """boxes [T, D, 4] (one sequence) or [Q, T, D, 4], counts [T] or [Q, T], state None or [Q, words] -> (Q, T, D, whether Q was given)."""
+    shape = tuple(int(v) for v in boxes_shape)
+    if len(shape) not in (3, 4) or shape[-1] != 4 or shape[-2] < 1 or shape[-2] > TRACK_MAX_DET or shape[-3] < 1:
+        raise ValueError(f'track_heads: boxes must be [T, D, 4] or [Q, T, D, 4] with T >= 1 and D in 1 .. {TRACK_MAX_DET}, got {shape}')
+    if tuple(int(v) for v in counts_shape) != shape[:-2]:
+        raise ValueError(f'track_heads: counts must be {list(shape[:-2])} for boxes {shape}, got {tuple(counts_shape)}')
+    Q = shape[0] if len(shape) == 4 else 1
+    if Q > 65535:
+        raise ValueError(f'track_heads: at most 65535 sequences per call, got {Q}')
+    if state_shape is not None and tuple(int(v) for v in state_shape) != (Q, track_state_words(slots)):
+        raise ValueError(f'track_heads: the state of {Q} sequences of {slots} slots is an int32 [{Q}, {track_state_words(slots)}] array, got {tuple(state_shape)}')
+    return Q, shape[-3], shape[-2], len(shape) == 4
+
+
+def track_heads_host(boxes, counts, state=None, slots=16, match_iou=0.3, max_age=5):
+    """``mcg_track_heads`` in numpy, bit for bit (the arithmetic: include/mcgaze_hip.h, "head identities across frames"), for checks and for
+    users without a GPU: which head box of frame t is the person of which box of frame t - 1, by greedy IoU matching against the ``slots``
+    tracks of a sequence (one camera).
+
+    boxes [T, D, 4] f32 (one sequence) or [Q, T, D, 4], counts [T] or [Q, T] integers: the first counts rows of a frame are its heads, best
+    first -- ``detect_heads_host``'s boxes and counts as they come.  state: None for the empty state, or what an earlier call returned (int32
+    [Q, track_state_words(slots)]; it is not written to).  A slot matched to a detection with IoU > match_iou keeps its id; an unmatched slot
+    coasts for max_age frames with its last box and is then freed; an unmatched detection opens the lowest free slot with the next id (1, 2, ...
+    per sequence).  ValueError for bad shapes and options, TypeError for boxes that are not float32 or counts that are not integers.
+    -> (slot_boxes [.., T, S, 4] f32, image_of [.., T, S] int32, track_id [.., T, S] int32, age [.., T, S] int32, det_of [.., T, S] int32,
+    flags [.., T] int32, state): row s of frame (q, t) is slot s -- for a slot matched or born in the frame the detection's box, image_of =
+    q * T + t and det_of = the detection; for every other slot zeros, -1, -1; track_id is the slot's id after the frame (0: free), age the frames
+    since its last match (-1: free).  flags: 1 a head was dropped for want of a slot, 2 a row was not finite (never matched or born), 4 a count
+    outside 0 .. D.  ``slot_boxes.reshape(-1, 4)`` and ``image_of.reshape(-1)`` are head_crops' tables when its images are the call's frames."""
+    slots, match_iou, max_age = _track_params(slots, match_iou, max_age)
+    boxes, counts = _host_array(boxes), _host_array(counts)
+    state = None if state is None else _host_array(state)
+    Q, T, D, given_q = _track_shapes(boxes.shape, counts.shape, None if state is None else state.shape, slots)
+    if boxes.dtype != np.float32:
+        raise TypeError(f'track_heads: boxes must be float32, got {boxes.dtype}')
+    if counts.dtype.kind not in 'iu':
+        raise TypeError(f'track_heads: counts must hold integers, got {counts.dtype}')
+    if state is not None and state.dtype != np.int32:
+        raise TypeError(f'track_heads: the state is an int32 array, got {state.dtype}')
+    S, f32, zero = slots, np.float32, np.float32(0)
+    boxes, counts = boxes.reshape(Q, T, D, 4), counts.reshape(Q, T)
+    state = np.zeros((Q, track_state_words(S)), np.int32) if state is None else np.array(state, dtype=np.int32, order='C')
+    thr = f32(match_iou)
+    slot_boxes = np.zeros((Q, T, S, 4), f32)
+    image_of, det_of = np.full((Q, T, S), -1, np.int32), np.full((Q, T, S), -1, np.int32)
+    track_id, age_out, flags = np.zeros((Q, T, S), np.int32), np.zeros((Q, T, S), np.int32), np.zeros((Q, T), np.int32)
+    for q in range(Q):
+        table = state[q, TRACK_HEADER_WORDS:].reshape(S, TRACK_SLOT_WORDS)
+        box, ids, age, next_id = table[:, :4].copy().view(f32), table[:, 4].copy(), table[:, 5].copy(), int(state[q, 0])
+        for t in range(T):
+            c = int(counts[q, t])
+            n = min(max(c, 0), D)
+            det = boxes[q, t, :n]
+            usable = np.isfinite(det).all(axis=1)
+            flag = (0 if usable.all() else 2) | (4 if c != n else 0)
+            slot_det, det_open = np.full(S, -1), usable.copy()
+            live = ids > 0
+            if n and live.any():
+                with np.errstate(all='ignore'):
+                    a, b = box[:, None, :], det[None, :, :]
+                    area_a, area_b = (a[..., 2] - a[..., 0]) * (a[..., 3] - a[..., 1]), (b[..., 2] - b[..., 0]) * (b[..., 3] - b[..., 1])
+                    dw = np.minimum(a[..., 2], b[..., 2]) - np.maximum(a[..., 0], b[..., 0])
+                    dh = np.minimum(a[..., 3], b[..., 3]) - np.maximum(a[..., 1], b[..., 1])
+                    inter = np.where(dw < 0, zero, dw) * np.where(dh < 0, zero, dh)
+                    iou = inter / (area_a + area_b - inter) + zero
+                    cand = (iou > thr) & live[:, None] & usable[None, :]                 # a NaN is no candidate; a candidate's iou is >= 0
+                while cand.any():
+                    held = np.where(cand, iou, f32(-1))
+                    s, d = np.argwhere(held == held.max())[0]                            # row-major: the lower slot, then the lower detection
+                    slot_det[s], det_open[d] = d, False
+                    cand[s, :] = False
+                    cand[:, d] = False
+            for s in range(S):
+                if slot_det[s] >= 0:
+                    box[s], age[s] = det[slot_det[s]], 0
+                elif ids[s] > 0:
+                    age[s] += 1
+                    if age[s] > max_age:
+                        box[s], ids[s], age[s] = 0, 0, 0
+            free = [s for s in range(S) if ids[s] == 0]
+            for d in np.flatnonzero(det_open):
+                if not free:
+                    flag |= 1
+                    break
+                s = free.pop(0)
+                next_id += 1
+                box[s], ids[s], age[s], slot_det[s] = det[d], next_id, 0, d
+            hit = slot_det >= 0
+            slot_boxes[q, t, hit] = det[slot_det[hit]]
+            image_of[q, t, hit], det_of[q, t] = q * T + t, slot_det
+            track_id[q, t], age_out[q, t], flags[q, t] = ids, np.where(ids != 0, age, -1), flag
+        table[:, :4], table[:, 4], table[:, 5] = box.view(np.int32), ids, age
+        state[q, 0], state[q, 1] = next_id, state[q, 1] + T
+    out = (slot_boxes, image_of, track_id, age_out, det_of, flags)
+    return (out if given_q else tuple(o[0] for o in out)) + (state,)
+
+
 # ---------------------------------------------------------------- the detector's input
-LETTERBOX_PAD = 114                                              # letterbox(color=(114, 114, 114))
+LETTERBOX_PAD = 114                                             # letterbox(color=(114, 114, 114))
 LETTERBOX_DTYPES = {torch.uint8: np.uint8, torch.float16: np.float16, torch.float32: np.float32}
 
 LetterboxGeometry = collections.namedtuple('LetterboxGeometry', 'unpad_h unpad_w top bottom left right out_h out_w ratio pad')

@@ -36,7 +36,8 @@ EXPORTS = ['mcg_abi_version', 'mcg_build_id', 'mcg_last_error', 'mcg_device_info
            'mcg_stage_forward_ragged', 'mcg_decoder_forward_ragged', 'mcg_decoder_forward_deferred_ragged', 'mcg_clip_forward_ragged',
            'mcg_pyramid_scatter_rows', 'mcg_preprocess_head_crops', 'mcg_merge_windows', 'mcg_smooth_gaze', 'mcg_preprocess_frames_nv12',
            'mcg_preprocess_head_crops_nv12', 'mcg_draw_gaze_arrows', 'mcg_draw_gaze_arrows_nv12',
-           'mcg_detect_heads_workspace_bytes', 'mcg_detect_heads', 'mcg_letterbox_frames', 'mcg_letterbox_frames_nv12']
+           'mcg_detect_heads_workspace_bytes', 'mcg_detect_heads', 'mcg_letterbox_frames', 'mcg_letterbox_frames_nv12',
+           'mcg_track_state_bytes', 'mcg_track_heads']
 LETTERBOX_U8, LETTERBOX_F16, LETTERBOX_F32 = 0, 1, 2             # enum order of include/mcgaze_hip.h
 
 
@@ -172,6 +173,9 @@ def load():
     lib.mcg_detect_heads.argtypes = [vp, vp, i, i, i, C.c_longlong, i, i, i, vp, C.c_double, C.c_double, i, i, i, i, vp, vp, vp, vp, vp, vp, vp, sz]
     lib.mcg_letterbox_frames.argtypes = [vp, vp, i, vp, i, i, i, i]
     lib.mcg_letterbox_frames_nv12.argtypes = lib.mcg_letterbox_frames.argtypes + [C.POINTER(YuvCoef)]
+    lib.mcg_track_state_bytes.restype = sz
+    lib.mcg_track_state_bytes.argtypes = [i, i]
+    lib.mcg_track_heads.argtypes = [vp, vp, C.c_longlong, vp, i, i, i, i, C.c_double, i, vp, vp, vp, vp, vp, vp, vp]
     lib.mcg_engine_set_option.argtypes = [vp, C.c_char_p, i]
     lib.mcg_engine_profile_start.argtypes = [vp, i]
     lib.mcg_engine_profile_stop.argtypes = [vp, C.POINTER(i), C.POINTER(C.c_float), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(i), C.POINTER(i), i]

@@ -16,7 +16,8 @@ device as they are, and the kernel writes the model's ``img`` tensor.  There is 
 Head crops (``DevicePipeline.head_crops``): the demo of the reference (MCGaze_demo/demo.ipynb, cell 4) cuts one window per person out of
 every video frame before this chain; there the WINDOW is chosen on the device as well (``mcg_preprocess_head_crops``), from frames and head
 boxes that may both live in device memory already.  ``head_crop_window`` is the same arithmetic on the host, for checks and for drawing.
-``DevicePipeline.letterbox`` makes the head detector's input from the same frames and ``detect_heads`` head boxes from its raw output.
+``DevicePipeline.letterbox`` makes the head detector's input from the same frames, ``detect_heads`` head boxes from its raw output and
+``track_heads`` one identity per person from the boxes of consecutive frames.
 Re-exported from beside this module: decoded frames (frame_cache.py), NV12 (nv12.py), arrows (arrows.py), the detector's two sides (head_detect.py), upload (staging.py).
 
 Randomness: the reference's ``CenterCrop(crop_type='relative_range')`` draws the crop size from the global numpy RNG at TEST
@@ -36,7 +37,8 @@ from .arrows import (ARROW_COLOR, ARROW_COORD, ARROW_SIDE, _arrow_colors, _arrow
                      arrow_segments, draw_arrows_host, segment_coverage)
 from .frame_cache import FrameCache, _DecodeProcs, decode_image  # noqa: F401
 from .head_detect import (DETECT_MAX_DET, LETTERBOX_PAD, LetterboxGeometry, _detect_params, _detect_shapes, _letterbox_dtype,  # noqa: F401
-                          _letterbox_plan, detect_heads_host, letterbox_geometry, letterbox_host)
+                          _letterbox_plan, _track_params, _track_shapes, detect_heads_host, letterbox_geometry, letterbox_host, track_heads_host,
+                          track_state_words)
 from .nv12 import YUV_COEF, _nv12_planes, _pixel_format, _yuv_coef, _yuv_to_bgr, bgr_to_yuv, nv12_to_bgr  # noqa: F401
 from .registry import Registry
 from .staging import _Stage, _StagingRing, _bgr_frame, _host_array, _layout  # noqa: F401
@@ -825,6 +827,65 @@ class DevicePipeline:
                 if st is not None:
                     st.read_by(main)
         return out
+
+    def track_heads(self, boxes, counts, state=None, slots=16, match_iou=0.3, max_age=5, device='cuda:0', stream=None):
+        """Which head of frame t is the person of which head of frame t - 1, on the device (mcg_track_heads: one launch, one workgroup per
+        sequence, the frames walked inside the kernel) -- ``track_heads_host`` bit for bit, whose arguments and seven results these are.
+
+        boxes [T, D, 4] f32 (one sequence, one camera) or [Q, T, D, 4] and counts [T] or [Q, T]: CUDA tensors are read where they are --
+        ``detect_heads``' boxes and counts as they come; the frame stride is taken from the tensor, any other view is made contiguous first --
+        and numpy arrays go up through the staging ring.  state: an int32 [Q, track_state_words(slots)] tensor on the device, which the call
+        UPDATES IN PLACE and hands back; None allocates a zeroed one (the empty state).  Shapes and options are checked before anything is
+        launched (TypeError / ValueError).
+        -> (slot_boxes [.., T, S, 4] f32, image_of, track_id, age, det_of [.., T, S] int32, flags [.., T] int32, state) on the device.
+        ``slot_boxes.view(-1, 4)`` and ``image_of.view(-1)`` feed head_crops and draw_arrows directly when their images are the frames of this
+        call: the rows of slots that saw no head in a frame have image_of = -1, which they flag as unusable rows (2) and skip.  With device
+        inputs and a given state the call touches the host nowhere and can be captured in a graph."""
+        lib = L.load()
+        slots, match_iou, max_age = _track_params(slots, match_iou, max_age)
+        on_device = isinstance(boxes, torch.Tensor) and boxes.is_cuda
+        if not on_device:
+            boxes = _host_array(boxes)
+        if boxes.dtype != (torch.float32 if on_device else np.float32):
+            raise TypeError(f'track_heads: boxes must be float32, got {boxes.dtype}')
+        counts_there = isinstance(counts, torch.Tensor) and counts.is_cuda
+        if not counts_there:
+            counts = _host_array(counts)
+            if counts.dtype.kind not in 'iu':
+                raise TypeError(f'track_heads: counts must hold integers, got {counts.dtype}')
+        elif counts.dtype not in (torch.int32, torch.int64):
+            raise TypeError(f'track_heads: counts must hold integers, got {counts.dtype}')
+        Q, T, D, given_q = _track_shapes(tuple(boxes.shape), tuple(counts.shape), None if state is None else tuple(state.shape), slots)
+        dev = _device(boxes.device if on_device else device, 'mcg_track_heads')
+        if state is not None and not (isinstance(state, torch.Tensor) and state.device == dev and state.dtype == torch.int32 and state.is_contiguous()):
+            raise TypeError(f'track_heads: the state is a contiguous int32 tensor on {dev} (it is updated in place)')
+        with torch.cuda.device(dev):
+            main = _caller_stream(stream, dev)
+            with torch.cuda.stream(main):
+                new = lambda *shape, dtype=torch.int32: torch.empty(*shape, dtype=dtype, device=dev)
+                lead = (Q, T) if given_q else (T,)
+                out = (new(*lead, slots, 4, dtype=torch.float32), new(*lead, slots), new(*lead, slots), new(*lead, slots), new(*lead, slots), new(*lead))
+                if state is None:
+                    state = torch.zeros(Q, track_state_words(slots), dtype=torch.int32, device=dev)
+                if Q == 0:
+                    return out + (state,)
+                frame_stride = 4 * D
+                if on_device:
+                    b = boxes if given_q else boxes[None]
+                    stride = b.stride(1) if T > 1 else b.stride(0) if Q > 1 else 4 * D
+                    if not (b.stride(3) == 1 and b.stride(2) == 4 and stride >= 4 * D and (Q == 1 or T == 1 or b.stride(0) == T * stride)):
+                        b, stride = b.contiguous(), 4 * D
+                    boxes, frame_stride = b, int(stride)
+                else:
+                    boxes = np.ascontiguousarray(boxes, dtype=np.float32)
+                counts = counts.to(dev, torch.int32).contiguous() if counts_there else np.ascontiguousarray(counts, dtype=np.int32)
+                st, _, (boxes_ptr, counts_ptr) = self._ring.upload([], (boxes, counts), dev, main)
+                vp = C.c_void_p
+                L.check(lib.mcg_track_heads(vp(main.cuda_stream), vp(boxes_ptr), frame_stride, vp(counts_ptr), Q, T, D, slots, match_iou, max_age,
+                                            vp(state.data_ptr()), *(vp(t.data_ptr()) for t in out)), 'mcg_track_heads')
+                if st is not None:
+                    st.read_by(main)
+        return out + (state,)
 
 
 def build_pipeline(transforms):

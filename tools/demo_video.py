@@ -4,6 +4,7 @@ label files in, per-person per-frame gaze out -- and, with --draw, the frames wi
 
 usage: demo_video.py FRAMES_DIR LABELS_DIR CONFIG CHECKPOINT --out gaze.json [--precision f16x3] [--device cuda:0] [--max-len 100]
                      [--batch-frames 448] [--head-class 1] [--ext jpg] [--smooth ALPHA] [--nv12 WxH FILE] [--matrix bt601] [--draw OUT]
+                     [--track [--slots 16] [--match-iou 0.3] [--max-age 5]]
                      [--color B,G,R] [--predictions DIR --in-shape HxW [--conf-thres 0.25] [--iou-thres 0.45]]
                      [--detector MODULE:FACTORY [--img-size 640] [--half]]
 
@@ -147,6 +148,10 @@ def main(argv=None):
     ap.add_argument('--detector', default=None, metavar='MODULE:FACTORY', help='run the head detector FACTORY() returns, instead of LABELS_DIR (then -)')
     ap.add_argument('--img-size', type=int, default=640, help='the letterbox size of --detector')
     ap.add_argument('--half', action='store_true', help='--detector reads half instead of float')
+    ap.add_argument('--track', action='store_true', help='identities from the tracker on the device instead of the head count and x1 order')
+    ap.add_argument('--slots', type=int, default=16, help='tracks held at once, of --track')
+    ap.add_argument('--match-iou', type=float, default=0.3, help='IoU above which a head continues a track, of --track')
+    ap.add_argument('--max-age', type=int, default=5, help='frames a track outlives its last detection, of --track')
     a = ap.parse_args(argv)
     if (a.predictions is None) != (a.in_shape is None):
         raise SystemExit('--predictions and --in-shape go together')
@@ -179,7 +184,8 @@ def main(argv=None):
     model = init_detector(a.config, a.checkpoint, device=a.device, precision=a.precision)
     pipe = DevicePipeline(model.cfg.data.test.pipeline)
     res = harness.run_head_video(model.engine(), pipe, frames, per_frame, max_len=a.max_len, batch_frames=a.batch_frames, rgb=True,
-                                 smooth=a.smooth, pixel_format='bgr' if a.nv12 is None else 'nv12', matrix=a.matrix, detections=detections, draw=draw)
+                                 smooth=a.smooth, pixel_format='bgr' if a.nv12 is None else 'nv12', matrix=a.matrix, detections=detections, draw=draw,
+                                 track=dict(slots=a.slots, match_iou=a.match_iou, max_age=a.max_age) if a.track else None)
     if draw is not None:
         res, annotated = res
         write_annotated(a.draw, annotated, a.nv12 is not None)
