@@ -232,7 +232,8 @@ def _bmm(a, b, site=None):
 # A test substitutes a model of a number format at the sites it stresses (tests/decoder_cases.py); the defaults are F.linear and
 # torch.bmm, and the functions run in float64 when the state dict and the inputs are double.  The attention core's q.k and a.v products
 # and the per-clue output heads are not contractions of the split format (attn_core_kernel, heads_kernel: plain f32) and carry no hook.
-SITES = ('in_proj', 'out_proj', 'dynamic_layer', 'dyn_in', 'dyn_out', 'fc_layer', 'ffn1', 'ffn2', 'cls_fc', 'reg_fc')
+# ``gaze_head`` takes ``linear`` alone: 'gaze_fc0' and 'gaze_fc1', the two MLP layers of its six branches.
+SITES = ('in_proj', 'out_proj', 'dynamic_layer', 'dyn_in', 'dyn_out', 'fc_layer', 'ffn1', 'ffn2', 'cls_fc', 'reg_fc', 'gaze_fc0', 'gaze_fc1')
 
 
 def mha_self(sd, p, x, num_heads=8, linear=_linear, bmm=_bmm):
@@ -314,13 +315,16 @@ def stqi_stage(sd, s, roi_feat, obj, clip_length, return_intermediates=False, li
     return cls, delta, x
 
 
-def gaze_head(sd, s, obj):
-    """GazeHead.forward, gaze_head.py:138-202. obj [N,3,d] -> 4 x [N,3] unit vectors."""
+def gaze_head(sd, s, obj, linear=_linear, return_raw=False):
+    """GazeHead.forward, gaze_head.py:138-202. obj [N,3,d] -> 4 x [N,3] unit vectors.  The two MLP layers of all six branches go through
+    ``linear`` as sites 'gaze_fc0' and 'gaze_fc1'; the per-clue output heads and the fusion are plain f32 in the kernel (gaze_tail_kernel)
+    and carry no hook.  ``return_raw``: -> (the dict, raw) with raw = dict(fused [N,3], gaze [3 clues][N,3], conf [3 clues][N,3]), the
+    vectors before normalisation and the confidences."""
     g = f'roi_head.gaze_head.{s}'
 
     def mlp(branch, x):
         for j in range(2):
-            x = F.relu(_ln(sd, g + f'.{branch}.{3 * j + 1}', F.linear(x, sd[g + f'.{branch}.{3 * j}.weight'])))
+            x = F.relu(_ln(sd, g + f'.{branch}.{3 * j + 1}', linear(x, sd[g + f'.{branch}.{3 * j}.weight'], None, f'gaze_fc{j}')))
         return x
 
     gz, conf = [], []
@@ -330,7 +334,8 @@ def gaze_head(sd, s, obj):
         conf.append(F.linear(mlp(f'gaze_{n}_confidence', f), sd[g + f'.fc_{n}_confidence.weight'], sd[g + f'.fc_{n}_confidence.bias']))
     fused = F.linear(torch.cat([c * z for c, z in zip(conf, gz)], dim=1), sd[g + '.fc_gaze.weight'], sd[g + '.fc_gaze.bias'])
     unit = lambda t: t / torch.norm(t, dim=-1, keepdim=True)  # no epsilon (:197-200)
-    return dict(gaze_score=unit(fused), face_gaze_score=unit(gz[0]), eyes_gaze_score=unit(gz[1]), head_gaze_score=unit(gz[2]))
+    out = dict(gaze_score=unit(fused), face_gaze_score=unit(gz[0]), eyes_gaze_score=unit(gz[1]), head_gaze_score=unit(gz[2]))
+    return (out, dict(fused=fused, gaze=gz, conf=conf)) if return_raw else out
 
 
 # --------------------------------------------------------------------------- whole path

@@ -78,7 +78,7 @@ def test_hook_defaults_change_no_bit(dtype):
         bmm = lambda a, b, site=None: (seen.append(site), torch.bmm(a, b))[1]
         again = orc.stqi_stage(sd, 3, roi, obj, 3, linear=lin, bmm=bmm)
     assert seen == ['in_proj', 'out_proj'] * 2 + ['dynamic_layer', 'dyn_in', 'dyn_out', 'fc_layer', 'ffn1', 'ffn2', 'cls_fc'] + ['reg_fc'] * 3
-    assert set(seen) == set(orc.SITES)
+    assert set(seen) == set(orc.SITES) - {'gaze_fc0', 'gaze_fc1'}               # the two sites of oracle.gaze_head: tests/test_gaze_cases_cpu.py
     assert all(torch.equal(a, b) for a, b in zip(again, want))
 
 
