@@ -795,6 +795,57 @@ int mcg_track_heads(mcg_stream s, const float* boxes_dev, long long frame_stride
                     float* slot_boxes_dev /* [Q][T][S][4] */, int32_t* image_of_dev /* [Q][T][S] */, int32_t* track_id_dev /* [Q][T][S] */,
                     int32_t* age_dev /* [Q][T][S] */, int32_t* det_of_dev /* [Q][T][S] */, int32_t* flags_dev /* [Q][T] */);
 
+/* ---------------------------------------------------------------- live: tracker slots as streams (additions to ABI 18; nothing above changes)
+ * mcg_track_heads decides on the device who is in which slot; the planning of a stream pool is a host function of how many frames each
+ * stream was given.  So a live chain makes every slot of every camera a stream that gets ONE crop per tick, person or not, and decides on
+ * the device, afterwards, which result rows belong to a person.  Two table kernels, one thread per row; no allocation, no host sync,
+ * graph-capturable; the results are pure functions of the inputs and do not depend on launch geometry.  A TICK is one frame per camera;
+ * ticks count from 0.  The identity RING keeps the last `ring_depth` ticks: tick t lives in ring row t % ring_depth.
+ *
+ * mcg_live_slots, after mcg_track_heads with one frame per camera: reads the tracker state of Q = num_cameras sequences of S = slots
+ * (mcg_track_header + mcg_track_slot, the layout above) and writes, for every (q, s), row = q * S + s:
+ *   a LIVE slot (id > 0, matched or coasting):  crop_boxes[row] = slot.box, image_of[row] = q      -- a coasting slot's box is its last match
+ *   a FREE slot:                                crop_boxes[row] = 0 0 0 0,  image_of[row] = -1     -- the row the head-crop entries flag 2
+ *   ring_id[tick % R][q][s] = the slot's id or 0;  ring_box[tick % R][q][s] = crop_boxes[row];  matched[q][s] = (id > 0 and age == 0)
+ * crop_boxes / image_of are the tables of mcg_preprocess_head_crops over the Q frames of the tick.
+ *   state_dev DEVICE, 16-byte aligned, mcg_track_state_bytes(Q, S) bytes, read only
+ *   crop_boxes_dev [Q][S][4] f32, image_of_dev [Q][S] int32, matched_dev [Q][S] int32, ring_id_dev [R][Q][S] int32, ring_box_dev [R][Q][S][4] f32
+ * num_cameras in 0 .. 65535 (0: MCG_OK without a launch); slots outside 1 .. 64, tick < 0, ring_depth outside 1 .. 65536, a null pointer
+ * or a misaligned state return MCG_ERR_ARG before any launch.
+ *
+ * mcg_live_gate: which result rows are a person.  The slots run in lockstep, so ONE host-built table serves all of them: entry e is five
+ * int32 (tick, lo, hi, prev, next) -- the tick of a frame, [lo, hi) the union of the ticks of every window that covered the frame in the
+ * overlap merge, prev / next the ticks the temporal filter read for it or -1.  Entries first_out .. first_out + num_out - 1 are the frames
+ * handed out, in order; the other entries are there as neighbours only.  `tick` is the newest tick mcg_live_slots wrote.
+ *   entry e is USABLE iff  tick - R < e.tick <= tick,  0 <= e.lo <= e.hi <= tick + 1,  e.hi - e.lo <= R,  e.lo > tick - R where hi > lo,
+ *                          e.prev >= -1 and e.next >= -1     -- so every t it names has its ring row: an index is never an address
+ *   id(e, q, s)    = e usable ? ring_id[e.tick % R][q][s] : 0
+ *   valid(e, q, s) = id != 0 and ring_id[t % R][q][s] == id for every t in [e.lo, e.hi)
+ *        -- a row is a person's only if every frame of every window merged into it was a crop of that person
+ * Per output row (i, q, s), e = first_out + i:
+ *   track_id = id(e);  valid = valid(e);  head_box = valid ? ring_box[e.tick % R][q][s] : 0 0 0 0;  image_of = valid ? i * Q + q : -1
+ *        -- image_of is the row table of the arrow entries over the num_out * Q frames handed out, frame (i, q) at i * Q + q: an invalid
+ *           row has no image and is skipped there (a zero box alone would still be drawn, as a dot at the origin)
+ *   with smoothing (fused_smooth_dev given):  a neighbour tick n in (e.prev, e.next) that is not -1 is GOOD iff some entry j has j.tick == n
+ *        (the first such j) and valid(j, q, s) and id(j, q, s) == id(e, q, s);
+ *        smooth_valid = valid and every neighbour that is not -1 is good;
+ *        where valid and not smooth_valid, row (i, q, s) of fused_smooth / others_smooth is REPLACED by the same row of fused / others;
+ *        every other row of them keeps its bits.  fused / others (and the detections) are never written: the masks say what they are.
+ *   table_dev DEVICE int32 [num_entries][5];  ring_id_dev, ring_box_dev as mcg_live_slots wrote them
+ *   fused_dev [num_out][Q][S][3], others_dev [num_out][Q][S][9] f32 (read), fused_smooth_dev, others_smooth_dev the same shapes (updated in
+ *   place): all four given, or all four NULL (no smoothing; smooth_valid_dev may then be NULL too)
+ *   track_id_dev, valid_dev, image_of_dev, smooth_valid_dev [num_out][Q][S] int32, head_box_dev [num_out][Q][S][4] f32: written in full
+ * num_out = 0 or num_cameras = 0 returns MCG_OK without a launch.  slots outside 1 .. 64, num_cameras outside 0 .. 65535, ring_depth
+ * outside 1 .. 65536, tick < 0, num_entries outside 0 .. 65536, first_out < 0, num_out < 0, first_out + num_out > num_entries,
+ * num_out * Q * S >= 2^31, a null pointer or smoothing pointers given in part return MCG_ERR_ARG before any launch.
+ * mcgaze_amd/live.py::live_slots_host and live_gate_host are the same on the host, bit for bit. */
+int mcg_live_slots(mcg_stream s, const void* state_dev, int num_cameras, int slots, int tick, int ring_depth, float* crop_boxes_dev,
+                   int32_t* image_of_dev, int32_t* ring_id_dev, float* ring_box_dev, int32_t* matched_dev);
+int mcg_live_gate(mcg_stream s, const int32_t* ring_id_dev, const float* ring_box_dev, int ring_depth, int num_cameras, int slots, int tick,
+                  const int32_t* table_dev, int num_entries, int first_out, int num_out, const float* fused_dev, const float* others_dev,
+                  float* fused_smooth_dev, float* others_smooth_dev, int32_t* track_id_dev, int32_t* valid_dev, float* head_box_dev,
+                  int32_t* image_of_dev, int32_t* smooth_valid_dev);
+
 /* ---------------------------------------------------------------- measurement aids (bench.py)
  * While armed, every launch of the contraction kernel made by THIS engine is bracketed by a hipEvent pair on its launch stream.
  * mcg_engine_profile_stop synchronises, returns per-launch duration (ms), algorithmic FLOPs, algorithmic HBM bytes (inputs and

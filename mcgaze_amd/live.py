@@ -1,0 +1,325 @@
+"""Live multi-person gaze with no host step: the tracker's slots as streams of a pool.
+
+``letterbox -> detector -> detect_heads -> track_heads -> head_crops`` leaves one crop per head in device memory, and ``GazeStreamPool``
+(merge='device', results='device', smooth=) turns streams of crops into gaze -- but who is in which slot is decided on the device
+(mcg_track_heads), while the pool's planning is a host function of how many frames each stream was given.  ``LiveGaze`` joins the two with
+a FIXED SCHEDULE: every slot of every camera is a stream that is always open and gets one crop per tick, whether or not a person is in the
+slot, and which result rows belong to a person is decided on the device, afterwards:
+
+  * mcg_live_slots (``live_slots_host``): the tracker state -> the crop table of the tick (a live slot's box, matched or coasting; a free
+    slot's unusable row), one row of an identity ring ``ring_id[tick % R]`` / ``ring_box[tick % R]``, and ``matched``;
+  * mcg_live_gate (``live_gate_host``): per returned frame and slot, ``track_id``, ``valid`` -- every frame of every window merged into the
+    row was a crop of that person --, the head box, the arrow table's ``image_of`` and, with smoothing, ``smooth_valid`` and the fall-back of
+    the smoothed gaze to the raw one next to an invalid neighbour.
+
+Nothing in a tick waits for the device or copies to the host.  The arithmetic of both kernels is stated in include/mcgaze_hip.h ("live:
+tracker slots as streams"); the host twins here are the same bit for bit.  ``live_gate_table`` is the host side of the gate: the spans of
+the windows a planner handed out, per returned frame."""
+import ctypes as C
+
+import numpy as np
+import torch
+
+from . import lib as L
+from .harness import _host, check_smooth
+from .head_detect import TRACK_HEADER_WORDS, TRACK_MAX_SLOTS, TRACK_SLOT_WORDS, _track_params, track_state_words
+from .stream import GazeStreamPool, WindowPlanner
+
+MAX_CAMERAS, MAX_RING, MAX_ENTRIES = 65535, 65536, 65536         # the bounds of mcg_live_slots / mcg_live_gate
+ENTRY = 5                                                        # tick, lo, hi, prev, next
+
+
+def ring_depth(clip_len):
+    """Rows of the identity ring a lockstep LiveGaze needs: 2 * clip_len + 2.  A frame f is handed out at tick f + clip_len (one later with
+    smoothing: f + clip_len + 1); the windows that cover it start above f - clip_len, and the gate also reads the span of its predecessor
+    f - 1, which starts at f - clip_len at the lowest.  So the ticks f - clip_len .. f + clip_len + 1 are live at once."""
+    return 2 * int(clip_len) + 2
+
+
+def _check_sizes(who, cameras, slots, depth=1, tick=0):
+    for name, v, lo, hi in (('cameras', cameras, 0, MAX_CAMERAS), ('slots', slots, 1, TRACK_MAX_SLOTS), ('ring depth', depth, 1, MAX_RING),
+                            ('tick', tick, 0, 0x7fffffff)):
+        if isinstance(v, bool) or int(v) != v or not lo <= v <= hi:
+            raise ValueError(f'{who}: {name} in {lo} .. {hi}, got {v!r}')
+
+
+def _check_ring(who, ring_id, ring_box):
+    if ring_id.ndim != 3 or ring_id.dtype != np.int32 or ring_box.dtype != np.float32 or ring_box.shape != ring_id.shape + (4,):
+        raise ValueError(f'{who}: the ring is ring_id int32 [R, Q, S] and ring_box float32 [R, Q, S, 4], got {ring_id.dtype} {ring_id.shape} and '
+                         f'{ring_box.dtype} {ring_box.shape}')
+    R, Q, S = ring_id.shape
+    _check_sizes(who, Q, S, R)
+    return R, Q, S
+
+
+def live_slots_host(state, tick, ring_id, ring_box):
+    """``mcg_live_slots`` in numpy, bit for bit.  state: int32 [Q, track_state_words(S)] as track_heads_host returns it, after the tick's
+    frame; ring_id int32 [R, Q, S] and ring_box float32 [R, Q, S, 4]: row tick % R is WRITTEN.
+    -> (crop_boxes float32 [Q * S, 4], image_of int32 [Q * S], matched int32 [Q, S]): head_crops' tables over the tick's Q frames -- a live
+    slot's box (a coasting slot keeps its last) with image_of = q, a free slot's zero box with image_of = -1 -- and which slots saw a
+    detection in this tick."""
+    state = np.asarray(_host(state))
+    R, Q, S = _check_ring('live_slots', ring_id, ring_box)
+    _check_sizes('live_slots', Q, S, R, tick)
+    if state.dtype != np.int32 or state.shape != (Q, track_state_words(S)):
+        raise ValueError(f'live_slots: the state of {Q} cameras of {S} slots is an int32 [{Q}, {track_state_words(S)}] array, got {state.dtype} {state.shape}')
+    table = np.ascontiguousarray(state[:, TRACK_HEADER_WORDS:]).reshape(Q, S, TRACK_SLOT_WORDS)
+    ids, age = table[..., 4], table[..., 5]
+    live = ids > 0
+    boxes = np.where(live[..., None], np.ascontiguousarray(table[..., :4]).view(np.float32), np.float32(0))
+    ring_id[tick % R], ring_box[tick % R] = np.where(live, ids, 0), boxes
+    image_of = np.where(live, np.arange(Q, dtype=np.int32)[:, None], -1).astype(np.int32)
+    return boxes.reshape(Q * S, 4).copy(), image_of.reshape(Q * S), (live & (age == 0)).astype(np.int32)
+
+
+def _span(windows, f):
+    """The union [lo, hi) of the windows (start, stop, ...) that cover frame f."""
+    over = [(w[0], w[1]) for w in windows if w[0] <= f < w[1]]
+    if not over:
+        raise L.McgError(f'live_gate_table: no window handed out covers frame {f}')
+    return min(a for a, _ in over), max(b for _, b in over)
+
+
+def live_gate_table(windows, first, k, smoothing=False, last=None):
+    """The table mcg_live_gate takes for the frames [first, first + k) a lockstep pool handed out -> (int32 [n, 5] = tick, lo, hi, prev, next
+    per entry; first_out: the entry of frame ``first``).  One frame per tick: a frame's index is its tick.  windows: the (start, stop,
+    overlap) tuples the planner handed out so far (WindowPlanner.feed / finish), the flush-to-end window of finish() included -- [lo, hi) is
+    the union of those that cover the frame.  smoothing: prev / next are the frames the filter read -- f - 1 unless f is 0, f + 1 unless f is
+    ``last`` (the stream's last frame, known once it has ended) -- and those frames get entries of their own, as neighbours."""
+    first, k = int(first), int(k)
+    if first < 0 or k < 0:
+        raise ValueError(f'live_gate_table: first and k must not be negative (got {first}, {k})')
+    if k == 0:
+        return np.zeros((0, ENTRY), np.int32), 0
+    lo_f = first - 1 if smoothing and first > 0 else first
+    hi_f = first + k + (1 if smoothing and first + k - 1 != last else 0)
+    table = np.full((hi_f - lo_f, ENTRY), -1, np.int32)
+    for i, f in enumerate(range(lo_f, hi_f)):
+        table[i, 0] = f
+        table[i, 1:3] = _span(windows, f)
+        if smoothing and first <= f < first + k:
+            table[i, 3], table[i, 4] = (f - 1 if f > 0 else -1), (-1 if f == last else f + 1)
+    return table, first - lo_f
+
+
+def check_gate_table(table, tick, depth):
+    """ValueError unless every tick the table names is still in a ring of ``depth`` rows whose newest is ``tick`` -- a span deeper than the ring
+    would read rows a later tick has overwritten.  -> the table as a contiguous int32 [n, 5] array."""
+    table = np.ascontiguousarray(table, dtype=np.int32)
+    if table.ndim != 2 or table.shape[1] != ENTRY or table.shape[0] > MAX_ENTRIES:
+        raise ValueError(f'live_gate: the table is int32 [n <= {MAX_ENTRIES}, {ENTRY}] = tick, lo, hi, prev, next; got {table.shape}')
+    if len(table):
+        t, lo, hi = table[:, 0].astype(np.int64), table[:, 1].astype(np.int64), table[:, 2].astype(np.int64)
+        if (t < 0).any() or (lo < 0).any() or (hi < lo).any() or (table[:, 3:] < -1).any() or (t > tick).any() or (hi > tick + 1).any():
+            raise ValueError(f'live_gate: an entry names a tick outside 0 .. {tick} or an empty span: {table.tolist()}')
+        oldest = min(int(t.min()), int(lo[hi > lo].min()) if (hi > lo).any() else int(t.min()))
+        if oldest <= tick - depth:
+            raise ValueError(f'live_gate: tick {oldest} has left the identity ring ({depth} rows, newest tick {tick}): a span deeper than the ring')
+    return table
+
+
+def live_gate_host(ring_id, ring_box, tick, table, first_out, num_out, fused=None, others=None, fused_smooth=None, others_smooth=None):
+    """``mcg_live_gate`` in numpy, bit for bit.  ring_id / ring_box: the identity ring (live_slots_host), whose newest row is ``tick``; table
+    int32 [n, 5] (live_gate_table), entries first_out .. first_out + num_out - 1 the frames handed out.  fused [k, Q, S, 3], others
+    [k, Q, S, 3, 3], fused_smooth, others_smooth: all four (smoothing) or none.
+    -> dict(track_id, valid, image_of int32 [k, Q, S], head_box float32 [k, Q, S, 4][, smooth_valid, fused_smooth, others_smooth -- copies,
+    the raw gaze where a row is valid next to a neighbour that is not]).  An entry that is not usable (a tick outside the ring) gives id 0,
+    invalid rows: defined, like the kernel."""
+    R, Q, S = _check_ring('live_gate', ring_id, ring_box)
+    _check_sizes('live_gate', Q, S, R, tick)
+    table = np.ascontiguousarray(table, dtype=np.int32).reshape(-1, ENTRY)
+    n, k = len(table), int(num_out)
+    if n > MAX_ENTRIES or first_out < 0 or k < 0 or first_out + k > n or k * Q * S >= 1 << 31:
+        raise ValueError(f'live_gate: the frames handed out must be entries of the table (first_out {first_out}, num_out {k}, {n} entries)')
+    smoothing = [x is not None for x in (fused, others, fused_smooth, others_smooth)]
+    if any(smoothing) != all(smoothing):
+        raise ValueError('live_gate: smoothing takes fused, others and both smoothed tables, or none')
+
+    def state(j):
+        t, lo, hi, prev, nxt = (int(v) for v in table[j])
+        old = tick - R
+        usable = old < t <= tick and 0 <= lo <= hi <= tick + 1 and (hi == lo or lo > old) and prev >= -1 and nxt >= -1
+        if not usable:
+            return np.zeros((Q, S), np.int32), np.zeros((Q, S), bool)
+        ids = ring_id[t % R]
+        valid = ids != 0
+        for u in range(lo, hi):
+            valid = valid & (ring_id[u % R] == ids)
+        return ids, valid
+
+    def neighbour(tk, ids):
+        for j in range(n):
+            if int(table[j, 0]) == tk:
+                idn, vn = state(j)
+                return vn & (idn == ids)
+        return np.zeros((Q, S), bool)
+
+    out = dict(track_id=np.zeros((k, Q, S), np.int32), valid=np.zeros((k, Q, S), np.int32), image_of=np.full((k, Q, S), -1, np.int32),
+               head_box=np.zeros((k, Q, S, 4), np.float32))
+    if all(smoothing):
+        out.update(smooth_valid=np.zeros((k, Q, S), np.int32), fused_smooth=np.array(fused_smooth, dtype=np.float32).reshape(k, Q, S, 3),
+                   others_smooth=np.array(others_smooth, dtype=np.float32).reshape(k, Q, S, 3, 3))
+        fused, others = np.asarray(fused, dtype=np.float32).reshape(k, Q, S, 3), np.asarray(others, dtype=np.float32).reshape(k, Q, S, 3, 3)
+    for i in range(k):
+        e = first_out + i
+        ids, valid = state(e)
+        out['track_id'][i], out['valid'][i] = ids, valid
+        out['image_of'][i] = np.where(valid, i * Q + np.arange(Q)[:, None], -1)
+        if valid.any():
+            out['head_box'][i] = np.where(valid[..., None], ring_box[int(table[e, 0]) % R], np.float32(0))
+        if all(smoothing):
+            ok = valid.copy()
+            for tk in (int(table[e, 3]), int(table[e, 4])):
+                if tk != -1:
+                    ok &= neighbour(tk, ids)
+            out['smooth_valid'][i] = ok
+            raw = valid & ~ok
+            out['fused_smooth'][i][raw], out['others_smooth'][i][raw] = fused[i][raw], others[i][raw]
+    return out
+
+
+def _clone_frame(f):
+    if isinstance(f, (tuple, list)):
+        return tuple(_clone_frame(p) for p in f)
+    return f.clone(memory_format=torch.contiguous_format) if isinstance(f, torch.Tensor) else np.array(f)
+
+
+class LiveGaze:
+    """Frames in, gaze for every tracked head a few ticks later, with no host step in between.
+
+        live = LiveGaze(engine_or_model, pipeline, cameras=Q, slots=S, smooth=0.6)
+        r = live.tick(frames, boxes, counts)     # frames: Q device frames; boxes [Q, D, 4], counts [Q] as detect_heads emits them
+        ...
+        r = live.finish()
+
+    ``tick`` runs, on the current stream of the engine's device: track_heads (the state is kept here), mcg_live_slots, head_crops, one push
+    per (camera, slot) stream of an internal GazeStreamPool(merge='device', results='device', smooth=smooth) whose Q * S streams were opened
+    at construction, pool.step(), mcg_live_gate and, with draw=True, pipeline.draw_arrows on copies of the frames of the returned ticks
+    (the gated boxes, ``fused_smooth`` if smoothing, else ``fused``).  It returns device tensors stacked over the k frames that became final
+    (k may be 0): first (a host int: the tick of row 0), track_id, valid [k, Q, S] int32, head_box [k, Q, S, 4], det [k, Q, S, 3, 5] (boxes
+    in the crop's resized pixels), fused [k, Q, S, 3], others [k, Q, S, 3, 3], image_of [k, Q, S] (draw_arrows' table over the k * Q returned
+    frames; -1 on invalid rows), with smoothing fused_smooth, others_smooth, smooth_valid, the tick's own ``flags`` [Q] (the tracker's) and
+    ``matched`` [Q, S], and with draw ``frames``: k lists of Q annotated frames.  ``finish`` returns the rest (no flags / matched).
+    Neither waits for the device or copies to the host.
+
+    What the rows mean: windows are aligned to the tick count, so a row is ``valid`` -- every frame of every window merged into it was a
+    crop of the person ``track_id`` -- from the first multiple of ``stride`` at or after the person's birth tick, plus clip_len - stride, and
+    symmetrically before the slot is freed; a slot that coasts (up to max_age missed detections) keeps its last box and stays valid; a
+    slot handed to another person yields invalid rows around the hand-over.  det / fused / others are never altered: of an invalid row
+    they are what the network made of a mixture or of an empty slot's crop (pixel (0, 0) of frame 0).  Where a row is valid but a
+    neighbour the filter read is not, fused_smooth / others_smooth are the raw gaze (smooth_valid 0).  All S slots of every camera go
+    through the network every tick.  The fp16 engine (precision 'f16') needs max_decode_windows <= 12 at clip_len 7, as for any pool."""
+
+    def __init__(self, engine_or_model, pipeline, cameras, slots=16, clip_len=7, stride=4, expand=0.8, match_iou=0.3, max_age=5, smooth=None,
+                 pixel_format='bgr', draw=False, matrix='bt601', rgb=False, person_threshold=0.5, max_decode_windows=None):
+        self.S, self.match_iou, self.max_age = _track_params(slots, match_iou, max_age)
+        _check_sizes('LiveGaze', cameras, self.S)
+        if cameras < 1:
+            raise ValueError(f'LiveGaze: at least one camera (got {cameras})')
+        self.Q, self.T, self.s = int(cameras), int(clip_len), int(stride)
+        self.smooth = check_smooth('LiveGaze', smooth)
+        self.pipe, self.expand, self.draw = pipeline, float(expand), bool(draw)
+        self.frame_options = dict(pixel_format=pixel_format, matrix=matrix)
+        self.rgb = bool(rgb)
+        _, _, pad_h, pad_w, _ = pipeline.head_crop_geometry()
+        n = self.Q * self.S
+        self.pool = GazeStreamPool(engine_or_model, pad_h, pad_w, clip_len, stride, rows=n * (clip_len + stride + 1), person_threshold=person_threshold,
+                                   max_decode_windows=max_decode_windows, max_trunk_frames=max(448, n), merge='device', results='device', smooth=self.smooth)
+        self.sids = [self.pool.open() for _ in range(n)]
+        self.dev = torch.device(self.pool.e.device)
+        self.lib = L.load()
+        self.R = ring_depth(clip_len)
+        new = lambda *shape, dtype=torch.int32: torch.zeros(*shape, dtype=dtype, device=self.dev)
+        self.ring_id, self.ring_box = new(self.R, self.Q, self.S), new(self.R, self.Q, self.S, 4, dtype=torch.float32)
+        self.crop_boxes, self.image_of = new(n, 4, dtype=torch.float32), new(n)
+        self.state = new(self.Q, track_state_words(self.S))
+        self.planner = WindowPlanner(clip_len, stride)           # fed like every stream of the pool: the windows they were handed
+        self.windows, self.kept = [], {}
+        self.ticks = self.emitted = 0
+        self.finished = False
+
+    def _stream(self):
+        return C.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream)
+
+    def tick(self, frames, boxes, counts):
+        """One frame per camera and its detections -> the frames that became final (see the class)."""
+        if self.finished:
+            raise L.McgError('LiveGaze: tick() after finish()')
+        frames = list(frames)
+        if len(frames) != self.Q or boxes.ndim != 3 or (boxes.shape[0], boxes.shape[2]) != (self.Q, 4) or tuple(counts.shape) != (self.Q,):
+            raise ValueError(f'LiveGaze.tick: {self.Q} frames, boxes [{self.Q}, D, 4] and counts [{self.Q}] (got {len(frames)} frames, '
+                             f'{tuple(boxes.shape)}, {tuple(counts.shape)})')
+        vp, n = C.c_void_p, self.Q * self.S
+        with torch.cuda.device(self.dev):
+            out = self.pipe.track_heads(boxes[:, None], counts[:, None], state=self.state, slots=self.S, match_iou=self.match_iou, max_age=self.max_age,
+                                        device=self.dev)
+            matched = torch.empty(self.Q, self.S, dtype=torch.int32, device=self.dev)
+            L.check(self.lib.mcg_live_slots(self._stream(), vp(self.state.data_ptr()), self.Q, self.S, self.ticks, self.R, vp(self.crop_boxes.data_ptr()),
+                                            vp(self.image_of.data_ptr()), vp(self.ring_id.data_ptr()), vp(self.ring_box.data_ptr()),
+                                            vp(matched.data_ptr())), 'mcg_live_slots')
+            img, img_hw, _, _, _ = self.pipe.head_crops(frames, self.crop_boxes, self.image_of, expand=self.expand, device=self.dev, rgb=self.rgb,
+                                                        **self.frame_options)
+            for j, sid in enumerate(self.sids):
+                self.pool.push(sid, img[j:j + 1], img_hw[j:j + 1])
+            res = self.pool.step()
+            if self.draw:                                         # the caller's buffers may be a decoder's, rewritten before the tick is returned
+                self.kept[self.ticks] = [_clone_frame(f) for f in frames]
+            self.ticks += 1
+            self.windows += self.planner.feed(1)
+            return self._emit(res, flags=out[5].reshape(self.Q), matched=matched)
+
+    def finish(self):
+        """The cameras ended: the windows that depend on the length, and every frame not returned yet."""
+        if self.finished:
+            raise L.McgError('LiveGaze: finish() called twice')
+        with torch.cuda.device(self.dev):
+            for sid in self.sids:
+                self.pool.close(sid)
+            res = self.pool.step()
+            self.finished = True
+            self.windows += self.planner.finish()
+            return self._emit(res)
+
+    def _emit(self, res, **more):
+        Q, S, smoothing = self.Q, self.S, self.smooth is not None
+        upto = self.planner.final_upto
+        k = max(0, upto - self.emitted - int(smoothing and not self.finished))
+        got = [res.get(sid) for sid in self.sids]
+        shapes = {(r['first'], int(r['det'].shape[0])) for r in got if r is not None}
+        if (shapes - {(self.emitted, k)}) or (k and any(r is None for r in got)):
+            raise L.McgError(f'LiveGaze: the streams left lockstep -- frames [{self.emitted}, {self.emitted + k}) were due from each of {Q * S} '
+                             f'streams, {sum(r is not None for r in got)} returned (first, k) = {sorted(shapes)}')
+        names = ('det', 'fused', 'others') + (('fused_smooth', 'others_smooth') if smoothing else ())
+        tail = dict(det=(3, 5), fused=(3,), others=(3, 3), fused_smooth=(3,), others_smooth=(3, 3))
+        if k:
+            parts = {name: torch.stack([r[name] for r in got], dim=1).reshape((k, Q, S) + tail[name]) for name in names}
+        else:
+            parts = {name: torch.empty((0, Q, S) + tail[name], dtype=torch.float32, device=self.dev) for name in names}
+        new = lambda *shape, dtype=torch.int32: torch.empty(*shape, dtype=dtype, device=self.dev)
+        gate = dict(track_id=new(k, Q, S), valid=new(k, Q, S), head_box=new(k, Q, S, 4, dtype=torch.float32), image_of=new(k, Q, S))
+        if smoothing:
+            gate['smooth_valid'] = new(k, Q, S)
+        out = dict(first=self.emitted, **gate, **parts, **more)
+        if k:
+            from .engine import _upload_table
+            table, first_out = live_gate_table(self.windows, self.emitted, k, smoothing, self.ticks - 1 if self.finished else None)
+            table = check_gate_table(table, self.ticks - 1, self.R)
+            plan = _upload_table(table, self.dev)
+            p = lambda name: C.c_void_p(out[name].data_ptr()) if name in out else C.c_void_p(0)
+            raw = ('fused', 'others') if smoothing else ('', '')
+            L.check(self.lib.mcg_live_gate(self._stream(), C.c_void_p(self.ring_id.data_ptr()), C.c_void_p(self.ring_box.data_ptr()),
+                                           self.R, Q, S, self.ticks - 1, C.c_void_p(plan.data_ptr()), len(table), first_out, k, p(raw[0]), p(raw[1]),
+                                           p('fused_smooth'), p('others_smooth'), p('track_id'), p('valid'), p('head_box'), p('image_of'),
+                                           p('smooth_valid')), 'mcg_live_gate')
+            self.windows = [w for w in self.windows if w[1] > self.emitted + k - 1]     # the next call's first neighbour is the last frame of this
+        if self.draw:
+            images = [f for t in range(self.emitted, self.emitted + k) for f in self.kept.pop(t)]
+            if k:
+                gaze = out['fused_smooth' if smoothing else 'fused']
+                # copy=True: the frame table of fresh tensors then travels pinned through the staging ring, not as a pageable upload
+                drawn, _ = self.pipe.draw_arrows(images, out['head_box'].view(-1, 4), gaze.view(-1, 3), out['image_of'].view(-1), copy=True,
+                                                 device=self.dev, **self.frame_options)
+                images = list(drawn)
+            out['frames'] = [images[i * Q:(i + 1) * Q] for i in range(k)]
+        self.emitted += k
+        return out

@@ -34,6 +34,11 @@ from .harness import (ROW, SMOOTH_ROW, _host, bucket_key, check_smooth, clip_out
                       split_rows)
 
 
+def _on_device(t):
+    """Whether t is a tensor in device memory (an img_hw table that must not be read back)."""
+    return isinstance(t, torch.Tensor) and t.is_cuda
+
+
 class WindowPlanner:
     """Which windows of ``plan_windows(L, clip_len, stride)`` are known while L is still growing.
 
@@ -555,7 +560,8 @@ class PyramidStore:
             self._free.append(r)
 
     def write(self, frames, rows, img_hw=None):
-        """frames [n,3,H,W] f32 -> rows[i] of every level holds frame i's pyramid; img_hw [n,2] or None (every frame fills H x W)."""
+        """frames [n,3,H,W] f32 -> rows[i] of every level holds frame i's pyramid; img_hw [n,2] (host, or a device tensor, which stays on the
+        device) or None (every frame fills H x W)."""
         n = frames.shape[0]
         if tuple(frames.shape[1:]) != (3, self.H, self.W):
             raise L.McgError(f'PyramidStore: frames must be [n,3,{self.H},{self.W}] (got {tuple(frames.shape)})')
@@ -566,7 +572,11 @@ class PyramidStore:
         if img_hw is not None and self.hw is None:
             self.hw = torch.empty(self.rows, 2, dtype=torch.int32, device=self.e.device)
             self.hw[:, 0], self.hw[:, 1] = self.H, self.W       # = what the decoder assumes without a table
-        if self.hw is not None and n:
+        if self.hw is not None and n and _on_device(img_hw):
+            # a table that is on the device stays there: one indexed copy, the row indices uploaded pinned -- nothing waits (live.LiveGaze)
+            from .engine import _upload_table
+            self.hw.index_copy_(0, _upload_table(np.asarray(rows, dtype=np.int64), self.e.device), img_hw.to(self.e.device, torch.int32).reshape(n, 2))
+        elif self.hw is not None and n:
             hw = (np.array([[self.H, self.W]] * n, dtype=np.int32) if img_hw is None else np.asarray(_host(img_hw), dtype=np.int32).reshape(n, 2))
             self.hw[torch.as_tensor(rows, dtype=torch.int64).to(self.e.device)] = torch.from_numpy(hw).to(self.e.device)
         return rows
@@ -663,13 +673,18 @@ class GazeStreamPool:
         return st
 
     def push(self, sid, frames, img_hw=None):
-        """Queue frames [n,3,H,W] f32 (host or device, preprocessed like engine.forward's input) of stream sid; img_hw: [n,2] or None."""
+        """Queue frames [n,3,H,W] f32 (host or device, preprocessed like engine.forward's input) of stream sid; img_hw: [n,2] or None.  An
+        img_hw that is a device tensor (head_crops' as it comes) is not read back: it reaches the store's table by an indexed copy."""
         st = self._stream(sid, 'push')
         if frames.dim() != 4 or tuple(frames.shape[1:]) != (3, self.H, self.W):
             raise L.McgError(f'GazeStreamPool.push: frames must be [n,3,{self.H},{self.W}] (got {tuple(frames.shape)})')
         n = frames.shape[0]
         if n:
-            st.queue.append((frames, None if img_hw is None else np.array(_host(img_hw), dtype=np.int32).reshape(n, 2)))
+            if _on_device(img_hw):                         # kept where it is, and not read back: step() copies it into the store's table
+                hw = img_hw.to(torch.int32).reshape(n, 2)
+            else:
+                hw = None if img_hw is None else np.array(_host(img_hw), dtype=np.int32).reshape(n, 2)
+            st.queue.append((frames, hw))
             st.queued += n
 
     def close(self, sid):
@@ -718,7 +733,13 @@ class GazeStreamPool:
             x = x[0] if len(x) == 1 else torch.cat(x)
             hw = None
             if self.store.hw is not None or any(h is not None for h in hws):
-                hw = np.concatenate([np.array([[self.H, self.W]] * p.shape[0], dtype=np.int32) if h is None else h for p, h in zip(parts, hws)])
+                full = lambda p: np.array([[self.H, self.W]] * p.shape[0], dtype=np.int32)
+                if any(_on_device(h) for h in hws):           # device tables stay on the device; host ones join them (pinned, non-blocking)
+                    from .engine import _upload_table
+                    hw = [h.to(self.e.device) if _on_device(h) else _upload_table(full(p) if h is None else h, self.e.device) for p, h in zip(parts, hws)]
+                    hw = hw[0] if len(hw) == 1 else torch.cat(hw)
+                else:
+                    hw = np.concatenate([full(p) if h is None else h for p, h in zip(parts, hws)])
             for i in range(0, len(rows), self.max_trunk):
                 self.store.write(x[i:i + self.max_trunk], rows[i:i + self.max_trunk], None if hw is None else hw[i:i + self.max_trunk])
         # 2. one decoder call over every window that became certain
