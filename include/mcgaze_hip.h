@@ -846,6 +846,63 @@ int mcg_live_gate(mcg_stream s, const int32_t* ring_id_dev, const float* ring_bo
                   float* fused_smooth_dev, float* others_smooth_dev, int32_t* track_id_dev, int32_t* valid_dev, float* head_box_dev,
                   int32_t* image_of_dev, int32_t* smooth_valid_dev);
 
+/* ---------------------------------------------------------------- live: occupied slots compacted into lanes (additions to ABI 18; nothing above changes)
+ * The fixed schedule above sends all Q * S slots through the network every tick.  A slot table is sized for the worst case per camera; the
+ * people present at once over all cameras are far fewer.  So a pool gets a fixed number P = `lanes` of streams, and which live slot holds
+ * which LANE is decided on the device, each tick.  A person keeps the lane for as long as they keep the slot, so a lane is a contiguous
+ * stream of one person's crops, and the ring-of-ids gate decides validity as above, over P ring columns.  Host work per tick is the same
+ * whoever is in the picture; no allocation, no host sync, graph-capturable; the results are pure functions of the inputs and do not depend
+ * on launch geometry or scheduling.  COLUMN = q * S + s names a slot.
+ *
+ * mcg_live_lanes, after mcg_track_heads with one frame per camera: ONE launch of ONE workgroup.
+ *   lane_state_dev DEVICE int32 [P][2] = (id, column) per lane, read and updated in place.  A lane is FREE iff id == 0: all zero bytes are
+ *   "every lane free".  id(c) below is the id of the tracker slot at column c after the tick's frame; the slot is live iff id(c) > 0.
+ *   1. RELEASE.  Lane p = (id, column) stays HELD iff id > 0, 0 <= column < Q * S, id(column) == id, and no lane below p is held with the
+ *      same column (a state no call leaves behind; the lowest lane keeps the slot).  Every other lane becomes free: a freed slot, a slot
+ *      handed to another person, a column out of range.  The column is range-checked before it is used as an index.
+ *   2. ASSIGN.  The WAITING slots are the live slots no held lane names, in ascending column order; the free lanes are taken in ascending
+ *      lane order, those released in step 1 included.  The k-th waiting slot takes the k-th free lane: lane = (id(c), c).  Waiting slots
+ *      beyond the number of free lanes get no lane in this tick and wait again in the next, by the same rule.  Ranks come from ballots and
+ *      prefix sums over ascending indices, so the order does not depend on timing.
+ *   3. OUTPUTS, lane p, ring row r = tick % R:
+ *        held by (id, c):  lane_state[p] = id, c;  crop_boxes[p] = box of slot c (matched or coasting);  image_of[p] = c / S;
+ *                          ring_id[r][p] = id;  ring_col[r][p] = c;  ring_box[r][p] = crop_boxes[p];  matched[p] = (age of slot c == 0)
+ *        free:             lane_state[p] = 0, 0;  crop_boxes[p] = 0 0 0 0;  image_of[p] = -1  -- the row the head-crop entries flag 2;
+ *                          ring_id[r][p] = 0;  ring_col[r][p] = -1;  ring_box[r][p] = 0 0 0 0;  matched[p] = 0
+ *      lane_of[q][s] = the lane that holds slot (q, s), or -1: the slot is free, or live and left out.
+ *      overflow[0] = max(0, waiting slots - free lanes): the live slots left without a lane in this tick.
+ *   state_dev DEVICE, 16-byte aligned, mcg_track_state_bytes(Q, S) bytes, read only
+ *   crop_boxes_dev [P][4] f32, image_of_dev [P], matched_dev [P] int32, ring_id_dev, ring_col_dev [R][P] int32, ring_box_dev [R][P][4] f32,
+ *   lane_of_dev [Q][S] int32, overflow_dev [1] int32: written in full (of the rings, row tick % R)
+ * num_cameras in 0 .. 65535 with Q * S <= 4096 (0 cameras: MCG_OK without a launch); lanes outside 1 .. 1024, slots outside 1 .. 64,
+ * tick < 0, ring_depth outside 1 .. 65536, a null pointer or a misaligned state return MCG_ERR_ARG before any launch.  Every index into
+ * global memory is a thread index below a checked bound, or a column that was range-checked.
+ *
+ * mcg_live_gate_lanes: mcg_live_gate over lanes, with the same table (tick, lo, hi, prev, next), the same USABLE rule and `tick`.
+ * Ids are per camera, so a lane's identity is the pair (ring_id, ring_col):
+ *   id(e, p)    = e usable ? ring_id[e.tick % R][p] : 0;   col(e, p) = e usable ? ring_col[e.tick % R][p] : -1
+ *   valid(e, p) = id != 0 and ring_id[t % R][p] == id and ring_col[t % R][p] == col for every t in [e.lo, e.hi)
+ * Per output row (i, p), e = first_out + i:
+ *   track_id = id(e);  valid = valid(e);  head_box = valid ? ring_box[e.tick % R][p] : 0 0 0 0
+ *   where valid and 0 <= col < Q * S:  camera = col / S, slot = col % S, image_of = i * Q + camera;  everywhere else all three are -1
+ *   with smoothing: a neighbour tick n is GOOD iff the first entry j with j.tick == n has valid(j, p), id(j, p) == id(e, p) and
+ *        col(j, p) == col(e, p);  smooth_valid and the replacement of rows of fused_smooth / others_smooth are those of mcg_live_gate.
+ *   ring_col_dev [R][P] as mcg_live_lanes wrote it;  fused_dev [num_out][P][3], others_dev [num_out][P][9] and the smoothed tables: all
+ *   four or none;  track_id_dev, valid_dev, camera_dev, slot_dev, image_of_dev, smooth_valid_dev [num_out][P] int32, head_box_dev
+ *   [num_out][P][4] f32: written in full
+ * num_out = 0 or num_cameras = 0 returns MCG_OK without a launch.  lanes outside 1 .. 1024, slots outside 1 .. 64, num_cameras outside
+ * 0 .. 65535, Q * S > 4096, ring_depth outside 1 .. 65536, tick < 0, num_entries outside 0 .. 65536, first_out < 0, num_out < 0,
+ * first_out + num_out > num_entries, num_out * P >= 2^31, a null pointer or smoothing pointers given in part return MCG_ERR_ARG before any
+ * launch.  mcgaze_amd/live.py::live_lanes_host and live_gate_lanes_host are the same on the host, bit for bit. */
+int mcg_live_lanes(mcg_stream s, const void* state_dev, int num_cameras, int slots, int lanes, int tick, int ring_depth,
+                   int32_t* lane_state_dev, float* crop_boxes_dev, int32_t* image_of_dev, int32_t* ring_id_dev, float* ring_box_dev,
+                   int32_t* ring_col_dev, int32_t* lane_of_dev, int32_t* matched_dev, int32_t* overflow_dev);
+int mcg_live_gate_lanes(mcg_stream s, const int32_t* ring_id_dev, const float* ring_box_dev, const int32_t* ring_col_dev, int ring_depth,
+                        int num_cameras, int slots, int lanes, int tick, const int32_t* table_dev, int num_entries, int first_out, int num_out,
+                        const float* fused_dev, const float* others_dev, float* fused_smooth_dev, float* others_smooth_dev,
+                        int32_t* track_id_dev, int32_t* valid_dev, int32_t* camera_dev, int32_t* slot_dev, float* head_box_dev,
+                        int32_t* image_of_dev, int32_t* smooth_valid_dev);
+
 /* ---------------------------------------------------------------- measurement aids (bench.py)
  * While armed, every launch of the contraction kernel made by THIS engine is bracketed by a hipEvent pair on its launch stream.
  * mcg_engine_profile_stop synchronises, returns per-launch duration (ms), algorithmic FLOPs, algorithmic HBM bytes (inputs and

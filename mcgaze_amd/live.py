@@ -14,7 +14,12 @@ slot, and which result rows belong to a person is decided on the device, afterwa
 
 Nothing in a tick waits for the device or copies to the host.  The arithmetic of both kernels is stated in include/mcgaze_hip.h ("live:
 tracker slots as streams"); the host twins here are the same bit for bit.  ``live_gate_table`` is the host side of the gate: the spans of
-the windows a planner handed out, per returned frame."""
+the windows a planner handed out, per returned frame.
+
+``LiveGaze(lanes=P)`` compacts the occupied slots into P streams instead ("live: occupied slots compacted into lanes" in the header):
+mcg_live_lanes (``live_lanes_host``) keeps a lane table (id, column) on the device, releases the lanes whose slot lost its person and hands
+the free lanes to the waiting slots in a fixed order; mcg_live_gate_lanes (``live_gate_lanes_host``) is the gate over the lanes' ring, with
+the same host-built table.  Trunk and decoder work per tick is then P frames, not Q * S."""
 import ctypes as C
 
 import numpy as np
@@ -26,6 +31,7 @@ from .head_detect import TRACK_HEADER_WORDS, TRACK_MAX_SLOTS, TRACK_SLOT_WORDS, 
 from .stream import GazeStreamPool, WindowPlanner
 
 MAX_CAMERAS, MAX_RING, MAX_ENTRIES = 65535, 65536, 65536         # the bounds of mcg_live_slots / mcg_live_gate
+MAX_LANES, MAX_COLUMNS = 1024, 4096                              # the bounds of mcg_live_lanes: lanes, cameras x slots
 ENTRY = 5                                                        # tick, lo, hi, prev, next
 
 
@@ -178,6 +184,129 @@ def live_gate_host(ring_id, ring_box, tick, table, first_out, num_out, fused=Non
     return out
 
 
+def _check_lanes(who, lanes, cameras, slots):
+    if isinstance(lanes, bool) or not isinstance(lanes, (int, np.integer)) or not 1 <= lanes <= MAX_LANES:
+        raise ValueError(f'{who}: lanes is an int in 1 .. {MAX_LANES}, got {lanes!r}')
+    if cameras * slots > MAX_COLUMNS:
+        raise ValueError(f'{who}: with lanes, cameras x slots must not exceed {MAX_COLUMNS} (got {cameras} x {slots})')
+    return int(lanes)
+
+
+def _check_lane_ring(who, ring_id, ring_box, ring_col):
+    if ring_id.ndim != 2 or ring_id.dtype != np.int32 or ring_col.dtype != np.int32 or ring_col.shape != ring_id.shape or \
+            ring_box.dtype != np.float32 or ring_box.shape != ring_id.shape + (4,):
+        raise ValueError(f'{who}: the ring is ring_id, ring_col int32 [R, P] and ring_box float32 [R, P, 4], got {ring_id.dtype} {ring_id.shape}, '
+                         f'{ring_col.dtype} {ring_col.shape} and {ring_box.dtype} {ring_box.shape}')
+    return ring_id.shape
+
+
+def live_lanes_host(state, tick, lane_state, ring_id, ring_box, ring_col):
+    """``mcg_live_lanes`` in numpy, bit for bit.  state: int32 [Q, track_state_words(S)] after the tick's frame; lane_state int32 [P, 2] =
+    (id, column) per lane, UPDATED in place (all zero: every lane free); ring_id, ring_col int32 [R, P] and ring_box float32 [R, P, 4]: row
+    tick % R is WRITTEN.  Release: a lane stays held iff id > 0, its column lies in 0 .. Q * S - 1, the slot there still has that id and no
+    lower lane holds the same column.  Assign: the live slots no held lane names, in ascending column order, take the free lanes in
+    ascending lane order; the rest wait.
+    -> (crop_boxes float32 [P, 4], image_of int32 [P] -- head_crops' tables over the tick's Q frames: a held lane's slot box and camera, a
+    free lane's zero box and -1 --, lane_of int32 [Q, S] (-1: the slot is free, or live and left out), matched int32 [P], overflow int32 [1]:
+    the live slots left without a lane)."""
+    state = np.asarray(_host(state))
+    R, P = _check_lane_ring('live_lanes', ring_id, ring_box, ring_col)
+    if state.ndim != 2 or state.dtype != np.int32 or state.shape[1] < TRACK_HEADER_WORDS + TRACK_SLOT_WORDS or \
+            (state.shape[1] - TRACK_HEADER_WORDS) % TRACK_SLOT_WORDS:
+        raise ValueError(f'live_lanes: the state of Q cameras of S slots is an int32 [Q, {TRACK_HEADER_WORDS} + {TRACK_SLOT_WORDS} * S] array, got '
+                         f'{state.dtype} {state.shape}')
+    Q, S = state.shape[0], (state.shape[1] - TRACK_HEADER_WORDS) // TRACK_SLOT_WORDS
+    _check_sizes('live_lanes', Q, S, R, tick)
+    _check_lanes('live_lanes', P, Q, S)
+    if lane_state.dtype != np.int32 or lane_state.shape != (P, 2):
+        raise ValueError(f'live_lanes: the lane state of {P} lanes is an int32 [{P}, 2] array, got {lane_state.dtype} {lane_state.shape}')
+    table = np.ascontiguousarray(state[:, TRACK_HEADER_WORDS:]).reshape(Q * S, TRACK_SLOT_WORDS)
+    ids, age, box = table[:, 4], table[:, 5], np.ascontiguousarray(table[:, :4]).view(np.float32)
+    lane_of = np.full(Q * S, -1, np.int32)
+    for p in range(P):                                           # 1. release
+        i, c = int(lane_state[p, 0]), int(lane_state[p, 1])
+        if i > 0 and 0 <= c < Q * S and ids[c] == i and lane_of[c] == -1:
+            lane_of[c] = p
+        else:
+            lane_state[p] = 0
+    free = [p for p in range(P) if lane_state[p, 0] == 0]
+    waiting = [c for c in range(Q * S) if ids[c] > 0 and lane_of[c] == -1]
+    for p, c in zip(free, waiting):                              # 2. assign
+        lane_state[p], lane_of[c] = (ids[c], c), p
+    held = lane_state[:, 0] != 0                                 # 3. outputs
+    col = lane_state[:, 1]
+    crop_boxes = np.where(held[:, None], box[col], np.float32(0))
+    row = tick % R
+    ring_id[row], ring_box[row], ring_col[row] = lane_state[:, 0], crop_boxes, np.where(held, col, -1)
+    image_of = np.where(held, col // S, -1).astype(np.int32)
+    matched = (held & (age[col] == 0)).astype(np.int32)
+    return crop_boxes, image_of, lane_of.reshape(Q, S), matched, np.array([max(0, len(waiting) - len(free))], np.int32)
+
+
+def live_gate_lanes_host(ring_id, ring_box, ring_col, cameras, slots, tick, table, first_out, num_out, fused=None, others=None, fused_smooth=None,
+                         others_smooth=None):
+    """``mcg_live_gate_lanes`` in numpy, bit for bit: live_gate_host over the P columns of the lane ring (live_lanes_host), a lane's identity
+    being the pair (ring_id, ring_col) -- ids are per camera.  table, first_out, num_out as for live_gate_host; fused [k, P, 3], others
+    [k, P, 3, 3], fused_smooth, others_smooth: all four (smoothing) or none.
+    -> dict(track_id, valid, camera, slot, image_of int32 [k, P], head_box float32 [k, P, 4][, smooth_valid, fused_smooth, others_smooth]).
+    camera / slot name the slot the lane held at the frame's tick and image_of is i * Q + camera, all three -1 on invalid rows."""
+    R, P = _check_lane_ring('live_gate_lanes', ring_id, ring_box, ring_col)
+    Q, S = int(cameras), int(slots)
+    _check_sizes('live_gate_lanes', Q, S, R, tick)
+    _check_lanes('live_gate_lanes', P, Q, S)
+    table = np.ascontiguousarray(table, dtype=np.int32).reshape(-1, ENTRY)
+    n, k = len(table), int(num_out)
+    if n > MAX_ENTRIES or first_out < 0 or k < 0 or first_out + k > n or k * P >= 1 << 31:
+        raise ValueError(f'live_gate_lanes: the frames handed out must be entries of the table (first_out {first_out}, num_out {k}, {n} entries)')
+    smoothing = [x is not None for x in (fused, others, fused_smooth, others_smooth)]
+    if any(smoothing) != all(smoothing):
+        raise ValueError('live_gate_lanes: smoothing takes fused, others and both smoothed tables, or none')
+
+    def state(j):
+        t, lo, hi, prev, nxt = (int(v) for v in table[j])
+        old = tick - R
+        usable = old < t <= tick and 0 <= lo <= hi <= tick + 1 and (hi == lo or lo > old) and prev >= -1 and nxt >= -1
+        if not usable:
+            return np.zeros(P, np.int32), np.full(P, -1, np.int32), np.zeros(P, bool)
+        ids, col = ring_id[t % R], ring_col[t % R]
+        valid = ids != 0
+        for u in range(lo, hi):
+            valid = valid & (ring_id[u % R] == ids) & (ring_col[u % R] == col)
+        return ids, col, valid
+
+    def neighbour(tk, ids, col):
+        for j in range(n):
+            if int(table[j, 0]) == tk:
+                idn, cn, vn = state(j)
+                return vn & (idn == ids) & (cn == col)
+        return np.zeros(P, bool)
+
+    new = lambda fill=0: np.full((k, P), fill, np.int32)
+    out = dict(track_id=new(), valid=new(), camera=new(-1), slot=new(-1), image_of=new(-1), head_box=np.zeros((k, P, 4), np.float32))
+    if all(smoothing):
+        out.update(smooth_valid=new(), fused_smooth=np.array(fused_smooth, dtype=np.float32).reshape(k, P, 3),
+                   others_smooth=np.array(others_smooth, dtype=np.float32).reshape(k, P, 3, 3))
+        fused, others = np.asarray(fused, dtype=np.float32).reshape(k, P, 3), np.asarray(others, dtype=np.float32).reshape(k, P, 3, 3)
+    for i in range(k):
+        e = first_out + i
+        ids, col, valid = state(e)
+        named = valid & (col >= 0) & (col < Q * S)
+        out['track_id'][i], out['valid'][i] = ids, valid
+        out['camera'][i], out['slot'][i] = np.where(named, col // S, -1), np.where(named, col % S, -1)
+        out['image_of'][i] = np.where(named, i * Q + col // S, -1)
+        if valid.any():
+            out['head_box'][i] = np.where(valid[:, None], ring_box[int(table[e, 0]) % R], np.float32(0))
+        if all(smoothing):
+            ok = valid.copy()
+            for tk in (int(table[e, 3]), int(table[e, 4])):
+                if tk != -1:
+                    ok &= neighbour(tk, ids, col)
+            out['smooth_valid'][i] = ok
+            raw = valid & ~ok
+            out['fused_smooth'][i][raw], out['others_smooth'][i][raw] = fused[i][raw], others[i][raw]
+    return out
+
+
 def _clone_frame(f):
     if isinstance(f, (tuple, list)):
         return tuple(_clone_frame(p) for p in f)
@@ -208,21 +337,38 @@ class LiveGaze:
     slot handed to another person yields invalid rows around the hand-over.  det / fused / others are never altered: of an invalid row
     they are what the network made of a mixture or of an empty slot's crop (pixel (0, 0) of frame 0).  Where a row is valid but a
     neighbour the filter read is not, fused_smooth / others_smooth are the raw gaze (smooth_valid 0).  All S slots of every camera go
-    through the network every tick.  The fp16 engine (precision 'f16') needs max_decode_windows <= 12 at clip_len 7, as for any pool."""
+    through the network every tick.  The fp16 engine (precision 'f16') needs max_decode_windows <= 12 at clip_len 7, as for any pool.
+
+    LANES.  ``lanes=None`` is everything above.  ``lanes=P`` (an int in 1 .. 1024, with cameras * slots <= 4096) gives the pool P streams
+    instead of Q * S: mcg_live_lanes decides on the device, every tick, which live slot holds which lane -- a person keeps the lane for as
+    long as they keep the slot; the live slots that hold none take the free lanes in ascending (camera, slot) / ascending lane order --, and
+    head_crops, the trunk and the decoder run over P rows a tick.  P should be the most people expected at once over ALL cameras; a slot
+    table is sized for the worst case per camera, P for the scene.  A tick then runs track_heads, mcg_live_lanes, head_crops over P rows,
+    P pushes, pool.step(), mcg_live_gate_lanes and the drawing, still with no wait for the device and no copy to the host, and with host
+    work that does not depend on who is in the picture.  The results are per LANE: track_id, valid, camera, slot, image_of [k, P] int32
+    (camera / slot: the slot the lane held at the frame's tick, -1 on invalid rows; image_of = i * Q + camera), head_box [k, P, 4], det
+    [k, P, 3, 5], fused [k, P, 3], others [k, P, 3, 3] and the smoothed tables likewise; every tick also returns flags [Q], matched [P],
+    lane_of [Q, S] (the lane of each slot, -1 if the slot is free or was left out) and overflow [1] (the live slots left without a lane in
+    this tick).  A row means what it means above with the LANE GRANT tick in place of the birth tick: a person is valid from the first
+    multiple of ``stride`` at or after the tick they got a lane, plus clip_len - stride, and symmetrically before the slot is freed; a lane
+    handed from one person to another (it can happen within one tick) yields invalid rows around the hand-over; a person left out by
+    overflow has no rows until a lane frees, and is a candidate again every tick.  ``ring_depth`` is unchanged."""
 
     def __init__(self, engine_or_model, pipeline, cameras, slots=16, clip_len=7, stride=4, expand=0.8, match_iou=0.3, max_age=5, smooth=None,
-                 pixel_format='bgr', draw=False, matrix='bt601', rgb=False, person_threshold=0.5, max_decode_windows=None):
+                 pixel_format='bgr', draw=False, matrix='bt601', rgb=False, person_threshold=0.5, max_decode_windows=None, lanes=None):
         self.S, self.match_iou, self.max_age = _track_params(slots, match_iou, max_age)
         _check_sizes('LiveGaze', cameras, self.S)
         if cameras < 1:
             raise ValueError(f'LiveGaze: at least one camera (got {cameras})')
+        self.P = None if lanes is None else _check_lanes('LiveGaze', lanes, int(cameras), self.S)
         self.Q, self.T, self.s = int(cameras), int(clip_len), int(stride)
         self.smooth = check_smooth('LiveGaze', smooth)
         self.pipe, self.expand, self.draw = pipeline, float(expand), bool(draw)
         self.frame_options = dict(pixel_format=pixel_format, matrix=matrix)
         self.rgb = bool(rgb)
         _, _, pad_h, pad_w, _ = pipeline.head_crop_geometry()
-        n = self.Q * self.S
+        n = self.Q * self.S if self.P is None else self.P       # the pool's streams: every slot, or the lanes
+        self.lead = (self.Q, self.S) if self.P is None else (self.P,)
         self.pool = GazeStreamPool(engine_or_model, pad_h, pad_w, clip_len, stride, rows=n * (clip_len + stride + 1), person_threshold=person_threshold,
                                    max_decode_windows=max_decode_windows, max_trunk_frames=max(448, n), merge='device', results='device', smooth=self.smooth)
         self.sids = [self.pool.open() for _ in range(n)]
@@ -230,7 +376,9 @@ class LiveGaze:
         self.lib = L.load()
         self.R = ring_depth(clip_len)
         new = lambda *shape, dtype=torch.int32: torch.zeros(*shape, dtype=dtype, device=self.dev)
-        self.ring_id, self.ring_box = new(self.R, self.Q, self.S), new(self.R, self.Q, self.S, 4, dtype=torch.float32)
+        self.ring_id, self.ring_box = new(self.R, *self.lead), new(self.R, *self.lead, 4, dtype=torch.float32)
+        if self.P is not None:
+            self.ring_col, self.lane_state = new(self.R, self.P), new(self.P, 2)
         self.crop_boxes, self.image_of = new(n, 4, dtype=torch.float32), new(n)
         self.state = new(self.Q, track_state_words(self.S))
         self.planner = WindowPlanner(clip_len, stride)           # fed like every stream of the pool: the windows they were handed
@@ -249,14 +397,24 @@ class LiveGaze:
         if len(frames) != self.Q or boxes.ndim != 3 or (boxes.shape[0], boxes.shape[2]) != (self.Q, 4) or tuple(counts.shape) != (self.Q,):
             raise ValueError(f'LiveGaze.tick: {self.Q} frames, boxes [{self.Q}, D, 4] and counts [{self.Q}] (got {len(frames)} frames, '
                              f'{tuple(boxes.shape)}, {tuple(counts.shape)})')
-        vp, n = C.c_void_p, self.Q * self.S
+        vp = C.c_void_p
         with torch.cuda.device(self.dev):
             out = self.pipe.track_heads(boxes[:, None], counts[:, None], state=self.state, slots=self.S, match_iou=self.match_iou, max_age=self.max_age,
                                         device=self.dev)
-            matched = torch.empty(self.Q, self.S, dtype=torch.int32, device=self.dev)
-            L.check(self.lib.mcg_live_slots(self._stream(), vp(self.state.data_ptr()), self.Q, self.S, self.ticks, self.R, vp(self.crop_boxes.data_ptr()),
-                                            vp(self.image_of.data_ptr()), vp(self.ring_id.data_ptr()), vp(self.ring_box.data_ptr()),
-                                            vp(matched.data_ptr())), 'mcg_live_slots')
+            matched = torch.empty(*self.lead, dtype=torch.int32, device=self.dev)
+            more = dict(flags=out[5].reshape(self.Q), matched=matched)
+            if self.P is None:
+                L.check(self.lib.mcg_live_slots(self._stream(), vp(self.state.data_ptr()), self.Q, self.S, self.ticks, self.R, vp(self.crop_boxes.data_ptr()),
+                                                vp(self.image_of.data_ptr()), vp(self.ring_id.data_ptr()), vp(self.ring_box.data_ptr()),
+                                                vp(matched.data_ptr())), 'mcg_live_slots')
+            else:
+                more.update(lane_of=torch.empty(self.Q, self.S, dtype=torch.int32, device=self.dev),
+                            overflow=torch.empty(1, dtype=torch.int32, device=self.dev))
+                L.check(self.lib.mcg_live_lanes(self._stream(), vp(self.state.data_ptr()), self.Q, self.S, self.P, self.ticks, self.R,
+                                                vp(self.lane_state.data_ptr()), vp(self.crop_boxes.data_ptr()), vp(self.image_of.data_ptr()),
+                                                vp(self.ring_id.data_ptr()), vp(self.ring_box.data_ptr()), vp(self.ring_col.data_ptr()),
+                                                vp(more['lane_of'].data_ptr()), vp(matched.data_ptr()), vp(more['overflow'].data_ptr())),
+                        'mcg_live_lanes')
             img, img_hw, _, _, _ = self.pipe.head_crops(frames, self.crop_boxes, self.image_of, expand=self.expand, device=self.dev, rgb=self.rgb,
                                                         **self.frame_options)
             for j, sid in enumerate(self.sids):
@@ -266,7 +424,7 @@ class LiveGaze:
                 self.kept[self.ticks] = [_clone_frame(f) for f in frames]
             self.ticks += 1
             self.windows += self.planner.feed(1)
-            return self._emit(res, flags=out[5].reshape(self.Q), matched=matched)
+            return self._emit(res, **more)
 
     def finish(self):
         """The cameras ended: the windows that depend on the length, and every frame not returned yet."""
@@ -281,24 +439,26 @@ class LiveGaze:
             return self._emit(res)
 
     def _emit(self, res, **more):
-        Q, S, smoothing = self.Q, self.S, self.smooth is not None
+        Q, S, lead, smoothing = self.Q, self.S, self.lead, self.smooth is not None
         upto = self.planner.final_upto
         k = max(0, upto - self.emitted - int(smoothing and not self.finished))
         got = [res.get(sid) for sid in self.sids]
         shapes = {(r['first'], int(r['det'].shape[0])) for r in got if r is not None}
         if (shapes - {(self.emitted, k)}) or (k and any(r is None for r in got)):
-            raise L.McgError(f'LiveGaze: the streams left lockstep -- frames [{self.emitted}, {self.emitted + k}) were due from each of {Q * S} '
+            raise L.McgError(f'LiveGaze: the streams left lockstep -- frames [{self.emitted}, {self.emitted + k}) were due from each of {len(self.sids)} '
                              f'streams, {sum(r is not None for r in got)} returned (first, k) = {sorted(shapes)}')
         names = ('det', 'fused', 'others') + (('fused_smooth', 'others_smooth') if smoothing else ())
         tail = dict(det=(3, 5), fused=(3,), others=(3, 3), fused_smooth=(3,), others_smooth=(3, 3))
         if k:
-            parts = {name: torch.stack([r[name] for r in got], dim=1).reshape((k, Q, S) + tail[name]) for name in names}
+            parts = {name: torch.stack([r[name] for r in got], dim=1).reshape((k,) + lead + tail[name]) for name in names}
         else:
-            parts = {name: torch.empty((0, Q, S) + tail[name], dtype=torch.float32, device=self.dev) for name in names}
+            parts = {name: torch.empty((0,) + lead + tail[name], dtype=torch.float32, device=self.dev) for name in names}
         new = lambda *shape, dtype=torch.int32: torch.empty(*shape, dtype=dtype, device=self.dev)
-        gate = dict(track_id=new(k, Q, S), valid=new(k, Q, S), head_box=new(k, Q, S, 4, dtype=torch.float32), image_of=new(k, Q, S))
+        gate = dict(track_id=new(k, *lead), valid=new(k, *lead), head_box=new(k, *lead, 4, dtype=torch.float32), image_of=new(k, *lead))
+        if self.P is not None:
+            gate.update(camera=new(k, self.P), slot=new(k, self.P))
         if smoothing:
-            gate['smooth_valid'] = new(k, Q, S)
+            gate['smooth_valid'] = new(k, *lead)
         out = dict(first=self.emitted, **gate, **parts, **more)
         if k:
             from .engine import _upload_table
@@ -307,10 +467,17 @@ class LiveGaze:
             plan = _upload_table(table, self.dev)
             p = lambda name: C.c_void_p(out[name].data_ptr()) if name in out else C.c_void_p(0)
             raw = ('fused', 'others') if smoothing else ('', '')
-            L.check(self.lib.mcg_live_gate(self._stream(), C.c_void_p(self.ring_id.data_ptr()), C.c_void_p(self.ring_box.data_ptr()),
-                                           self.R, Q, S, self.ticks - 1, C.c_void_p(plan.data_ptr()), len(table), first_out, k, p(raw[0]), p(raw[1]),
-                                           p('fused_smooth'), p('others_smooth'), p('track_id'), p('valid'), p('head_box'), p('image_of'),
-                                           p('smooth_valid')), 'mcg_live_gate')
+            if self.P is None:
+                L.check(self.lib.mcg_live_gate(self._stream(), C.c_void_p(self.ring_id.data_ptr()), C.c_void_p(self.ring_box.data_ptr()),
+                                               self.R, Q, S, self.ticks - 1, C.c_void_p(plan.data_ptr()), len(table), first_out, k, p(raw[0]), p(raw[1]),
+                                               p('fused_smooth'), p('others_smooth'), p('track_id'), p('valid'), p('head_box'), p('image_of'),
+                                               p('smooth_valid')), 'mcg_live_gate')
+            else:
+                L.check(self.lib.mcg_live_gate_lanes(self._stream(), C.c_void_p(self.ring_id.data_ptr()), C.c_void_p(self.ring_box.data_ptr()),
+                                                     C.c_void_p(self.ring_col.data_ptr()), self.R, Q, S, self.P, self.ticks - 1,
+                                                     C.c_void_p(plan.data_ptr()), len(table), first_out, k, p(raw[0]), p(raw[1]), p('fused_smooth'),
+                                                     p('others_smooth'), p('track_id'), p('valid'), p('camera'), p('slot'), p('head_box'),
+                                                     p('image_of'), p('smooth_valid')), 'mcg_live_gate_lanes')
             self.windows = [w for w in self.windows if w[1] > self.emitted + k - 1]     # the next call's first neighbour is the last frame of this
         if self.draw:
             images = [f for t in range(self.emitted, self.emitted + k) for f in self.kept.pop(t)]

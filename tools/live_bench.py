@@ -1,19 +1,21 @@
 #!/usr/bin/env python3
-"""Live multi-person gaze: the fixed-schedule route (live.LiveGaze) against the read-back route, ms per tick at steady state.  Prints ONE JSON
-line; --out also writes the note profiles/live_<build id>.md holds.
+"""Live multi-person gaze: the fixed-schedule route (live.LiveGaze), the lanes route (live.LiveGaze(lanes=P)) and the read-back route, ms
+per tick at steady state.  Prints ONE JSON line; --out also writes the note profiles/live_lanes_<build id>.md holds.
 
 usage: live_bench.py [--cases 1x8x3,4x16x6,8x8x3] [--precisions f16x3,f16] [--steps 20] [--warmup 16] [--rounds 3] [--smooth 0.6] [--out FILE]
 
 Workload: per case Q x S x people, Q cameras of 720 x 1280 BGR frames in device memory with `people` heads each, wandering a few pixels a tick
 and listed as detect_heads leaves them (boxes [Q, max_det, 4], counts [Q] on the device); crops are 448 x 448 (the L2CS chain), clip 7 /
-stride 4, synthetic weights.  Two routes, alternated --rounds times, each round = --warmup untimed ticks (windows are being decoded and
+stride 4, synthetic weights.  Three routes, alternated --rounds times, each round = --warmup untimed ticks (windows are being decoded and
 frames returned by then), then --steps ticks bracketed by synchronize:
   fixed:     LiveGaze.tick -- every one of the Q x S slots is a pool stream and gets a crop every tick; nothing is read back.
              Trunk frames per tick: Q x S.
+  lanes:     LiveGaze(lanes=P).tick -- the occupied slots compacted on the device into P pool streams, P = the people present over all
+             cameras rounded up to a multiple of 8 (--lane-multiple); nothing is read back.  Trunk frames per tick: P.
   readback:  written here only: track_heads, then track_id, det_of and the slot boxes are copied to the host (ONE wait for the device per
              tick, in front of the trunk), head_crops cuts the matched heads only, and pool streams are opened, pushed and closed per track.
              Trunk frames per tick: Q x people.
-Both pools run merge='device', results='device' and the same smoothing.  The ratio is that of this comparison only."""
+All pools run merge='device', results='device' and the same smoothing.  The ratios are those of this comparison only."""
 import argparse
 import json
 import os
@@ -96,6 +98,7 @@ def main():
     ap.add_argument('--warmup', type=int, default=16)
     ap.add_argument('--rounds', type=int, default=3)
     ap.add_argument('--smooth', type=float, default=0.6)
+    ap.add_argument('--lane-multiple', type=int, default=8)
     ap.add_argument('--out')
     a = ap.parse_args()
     rs = np.random.RandomState(11)
@@ -111,7 +114,9 @@ def main():
             boxes, counts = torch.from_numpy(host_boxes).to(DEV), torch.from_numpy(host_counts).to(DEV)
             frames = [torch.randint(0, 256, (FRAME_H, FRAME_W, 3), dtype=torch.uint8, device=DEV) for _ in range(Q)]
             pipe = P.DevicePipeline(CHAIN)
-            routes = dict(fixed=LiveGaze(engine, pipe, cameras=Q, slots=S, clip_len=CLIP, stride=STRIDE, smooth=a.smooth, max_decode_windows=max_windows),
+            lanes = -(-Q * people // a.lane_multiple) * a.lane_multiple
+            options = dict(cameras=Q, slots=S, clip_len=CLIP, stride=STRIDE, smooth=a.smooth, max_decode_windows=max_windows)
+            routes = dict(fixed=LiveGaze(engine, pipe, **options), lanes=LiveGaze(engine, pipe, lanes=lanes, **options),
                           readback=ReadBack(engine, pipe, Q, S, a.smooth, max_windows))
             at = {k: 0 for k in routes}
 
@@ -127,10 +132,11 @@ def main():
                         step(name)
                     ms[name].append(timed(lambda: step(name), a.steps))
             med = {k: float(np.median(v)) for k, v in ms.items()}
-            results.append(dict(precision=precision, cameras=Q, slots=S, people=people,
-                                trunk_frames_per_tick=dict(fixed=Q * S, readback=routes['readback'].trunk_frames / at['readback']),
+            results.append(dict(precision=precision, cameras=Q, slots=S, people=people, lanes=lanes,
+                                trunk_frames_per_tick=dict(fixed=Q * S, lanes=lanes, readback=routes['readback'].trunk_frames / at['readback']),
                                 ms={k: [round(v, 3) for v in ms[k]] for k in ms}, median_ms={k: round(v, 3) for k, v in med.items()},
-                                fixed_over_readback=round(med['fixed'] / med['readback'], 3), faster=min(med, key=med.get)))
+                                fixed_over_readback=round(med['fixed'] / med['readback'], 3), lanes_over_fixed=round(med['lanes'] / med['fixed'], 3),
+                                lanes_over_readback=round(med['lanes'] / med['readback'], 3), fastest=min(med, key=med.get)))
             del routes
             torch.cuda.empty_cache()
     line = dict(tool='live_bench', build_id=lib.build_id(), device=torch.cuda.get_device_name(0), arch=torch.cuda.get_device_properties(0).gcnArchName,
@@ -138,12 +144,13 @@ def main():
                 cases=results)
     print(json.dumps(line))
     if a.out:
-        rows = ['| precision | Q x S, people | trunk frames / tick: fixed, read-back | fixed ms / tick (rounds) | read-back ms / tick (rounds) | fixed / read-back | faster |',
-                '|---|---|---|---|---|---|---|']
+        rows = ['| precision | Q x S, people | trunk frames / tick: fixed, lanes, read-back | fixed ms / tick (rounds) | lanes ms / tick (rounds) | '
+                'read-back ms / tick (rounds) | lanes / fixed | lanes / read-back | fixed / read-back | fastest |', '|---|---|---|---|---|---|---|---|---|---|']
+        cell = lambda r, k: f"{r['median_ms'][k]} ({', '.join(str(v) for v in r['ms'][k])})"
         for r in results:
             rows.append(f"| {r['precision']} | {r['cameras']} x {r['slots']}, {r['people']} | {r['trunk_frames_per_tick']['fixed']}, "
-                        f"{r['trunk_frames_per_tick']['readback']:.1f} | {r['median_ms']['fixed']} ({', '.join(str(v) for v in r['ms']['fixed'])}) | "
-                        f"{r['median_ms']['readback']} ({', '.join(str(v) for v in r['ms']['readback'])}) | {r['fixed_over_readback']} | {r['faster']} |")
+                        f"{r['trunk_frames_per_tick']['lanes']}, {r['trunk_frames_per_tick']['readback']:.1f} | {cell(r, 'fixed')} | {cell(r, 'lanes')} | "
+                        f"{cell(r, 'readback')} | {r['lanes_over_fixed']} | {r['lanes_over_readback']} | {r['fixed_over_readback']} | {r['fastest']} |")
         with open(a.out, 'a') as f:
             f.write(f"\n## Run on {line['device']} ({line['arch']}), build {line['build_id']}\n\n{a.steps} ticks a round after {a.warmup} untimed, "
                     f"{a.rounds} rounds alternated, medians; smooth = {a.smooth}.\n\n" + '\n'.join(rows) + '\n')
