@@ -5,6 +5,9 @@
 // live_gate_host are the same on the host.  Two table kernels, tiny and latency-bound: one thread per row, integer compares and copies.
 // A tick enters an address only as t % R after the entry that names it was found usable (every tick it names lies in the ring); q and s
 // come from the thread index, below the host-checked Q and S.
+// The GATE is stated once, over a ring of `cols` columns: live_gate_kernel serves mcg_live_gate (the slot ring: one column per (camera,
+// slot), a column's identity is its own index) and mcg_live_gate_lanes (the lane ring: the identity is read from ring_col), and every
+// argument bound of the four entries is stated once, in live_check and live_gate.
 #include "common.hpp"
 
 #define MCG_LIVE_THREADS 256
@@ -48,8 +51,8 @@ __device__ __forceinline__ live_entry live_load(const int32_t* __restrict__ tabl
 }
 
 // id and valid of entry e for the ring column `col` (a slot, or a lane); 64-bit compares: tick - R may pass below INT_MIN for no valid input
-// only.  ring_col is null for the slot ring; for the lane ring it is the second half of a lane's identity (ids are per camera) and has to
-// hold over the span as the id does.
+// only.  The column is the second half of a row's identity (ids are per camera) and has to hold over the span as the id does: the lane
+// ring reads it from ring_col; in the slot ring (ring_col null) it is `col` itself, and the compares on it are trivially true.
 __device__ __forceinline__ bool live_state(const live_entry& e, const int32_t* __restrict__ ring_id, const int32_t* __restrict__ ring_col, int R,
                                            size_t cols, size_t col, int tick, int* id_out, int* column_out) {
   const long long old = (long long)tick - R;                       // ticks at or below it have left the ring
@@ -61,7 +64,7 @@ __device__ __forceinline__ bool live_state(const live_entry& e, const int32_t* _
     return false;
   }
   const size_t own = (size_t)(e.tick % R) * cols + col;
-  const int id = ring_id[own], column = ring_col != nullptr ? ring_col[own] : -1;
+  const int id = ring_id[own], column = ring_col != nullptr ? ring_col[own] : (int)col;    // col < cols <= 65535 * 64
   *id_out = id;
   *column_out = column;
   bool valid = id != 0;
@@ -107,29 +110,36 @@ __device__ __forceinline__ void live_gate_smooth(const live_entry& e, bool valid
   }
 }
 
-__global__ __launch_bounds__(MCG_LIVE_THREADS) void live_gate_kernel(const int32_t* __restrict__ ring_id, const float* __restrict__ ring_box, int R,
-                                                                     int Q, int S, int tick, const int32_t* __restrict__ table, int num_entries,
-                                                                     int first_out, int num_out, const float* __restrict__ fused,
-                                                                     const float* __restrict__ others, float* __restrict__ fused_smooth,
-                                                                     float* __restrict__ others_smooth, int32_t* __restrict__ track_id,
-                                                                     int32_t* __restrict__ valid_out, float* __restrict__ head_box,
-                                                                     int32_t* __restrict__ image_of, int32_t* __restrict__ smooth_valid) {
-  const size_t cols = (size_t)Q * S;
-  const size_t row = (size_t)blockIdx.x * MCG_LIVE_THREADS + threadIdx.x;   // < num_out * Q * S < 2^31
+// The gate over a ring of `num_cols` columns: Q * S of them without ring_col (mcg_live_gate), P lanes with it (mcg_live_gate_lanes).
+// camera / slot_out: null, or where to write the slot the row names.
+__global__ __launch_bounds__(MCG_LIVE_THREADS) void live_gate_kernel(const int32_t* __restrict__ ring_id, const float* __restrict__ ring_box,
+                                                                     const int32_t* __restrict__ ring_col, int R, int num_cols, int Q, int S, int tick,
+                                                                     const int32_t* __restrict__ table, int num_entries, int first_out, int num_out,
+                                                                     const float* __restrict__ fused, const float* __restrict__ others,
+                                                                     float* __restrict__ fused_smooth, float* __restrict__ others_smooth,
+                                                                     int32_t* __restrict__ track_id, int32_t* __restrict__ valid_out,
+                                                                     int32_t* __restrict__ camera, int32_t* __restrict__ slot_out,
+                                                                     float* __restrict__ head_box, int32_t* __restrict__ image_of,
+                                                                     int32_t* __restrict__ smooth_valid) {
+  const size_t cols = (size_t)num_cols;
+  const size_t row = (size_t)blockIdx.x * MCG_LIVE_THREADS + threadIdx.x;   // < num_out * cols < 2^31
   if (row >= (size_t)num_out * cols) return;
   const int i = (int)(row / cols);
   const size_t col = row - (size_t)i * cols;
-  const int q = (int)(col / S);
   const live_entry e = live_load(table, first_out + i);            // first_out + i < num_entries
   int id, column;
-  const bool valid = live_state(e, ring_id, nullptr, R, cols, col, tick, &id, &column);
+  const bool valid = live_state(e, ring_id, ring_col, R, cols, col, tick, &id, &column);
+  const bool named = valid && column >= 0 && column < Q * S;       // the column is a value here, never an address; a slot ring names every valid row
+  const int q = named ? column / S : -1;
   track_id[row] = id;
   valid_out[row] = valid ? 1 : 0;
-  image_of[row] = valid ? i * Q + q : -1;
+  if (camera != nullptr) camera[row] = q;
+  if (slot_out != nullptr) slot_out[row] = named ? column - q * S : -1;
+  image_of[row] = named ? i * Q + q : -1;                          // < num_out * Q: below 2^31 for either ring
   const size_t at = valid ? (size_t)(e.tick % R) * cols + col : 0;
 #pragma unroll
   for (int c = 0; c < 4; ++c) head_box[4 * row + c] = valid ? ring_box[4 * at + c] : 0.0f;
-  live_gate_smooth(e, valid, id, column, row, table, num_entries, ring_id, nullptr, R, cols, col, tick, fused, others, fused_smooth, others_smooth,
+  live_gate_smooth(e, valid, id, column, row, table, num_entries, ring_id, ring_col, R, cols, col, tick, fused, others, fused_smooth, others_smooth,
                    smooth_valid);
 }
 
@@ -248,43 +258,25 @@ __global__ __launch_bounds__(MCG_LIVE_THREADS) void live_lanes_kernel(const unsi
   if (tid == 0) overflow[0] = waiting > num_free ? waiting - num_free : 0;
 }
 
-__global__ __launch_bounds__(MCG_LIVE_THREADS) void live_gate_lanes_kernel(const int32_t* __restrict__ ring_id, const float* __restrict__ ring_box,
-                                                                           const int32_t* __restrict__ ring_col, int R, int Q, int S, int P, int tick,
-                                                                           const int32_t* __restrict__ table, int num_entries, int first_out,
-                                                                           int num_out, const float* __restrict__ fused,
-                                                                           const float* __restrict__ others, float* __restrict__ fused_smooth,
-                                                                           float* __restrict__ others_smooth, int32_t* __restrict__ track_id,
-                                                                           int32_t* __restrict__ valid_out, int32_t* __restrict__ camera,
-                                                                           int32_t* __restrict__ slot_out, float* __restrict__ head_box,
-                                                                           int32_t* __restrict__ image_of, int32_t* __restrict__ smooth_valid) {
-  const size_t cols = (size_t)P;
-  const size_t row = (size_t)blockIdx.x * MCG_LIVE_THREADS + threadIdx.x;   // < num_out * P < 2^31
-  if (row >= (size_t)num_out * cols) return;
-  const int i = (int)(row / cols);
-  const size_t p = row - (size_t)i * cols;
-  const live_entry e = live_load(table, first_out + i);            // first_out + i < num_entries
-  int id, column;
-  const bool valid = live_state(e, ring_id, ring_col, R, cols, p, tick, &id, &column);
-  const bool named = valid && column >= 0 && column < Q * S;       // the column is a value here, never an address
-  const int q = named ? column / S : -1;
-  track_id[row] = id;
-  valid_out[row] = valid ? 1 : 0;
-  camera[row] = q;
-  slot_out[row] = named ? column - q * S : -1;
-  image_of[row] = named ? i * Q + q : -1;                          // < 65536 * 4096
-  const size_t at = valid ? (size_t)(e.tick % R) * cols + p : 0;
-#pragma unroll
-  for (int c = 0; c < 4; ++c) head_box[4 * row + c] = valid ? ring_box[4 * at + c] : 0.0f;
-  live_gate_smooth(e, valid, id, column, row, table, num_entries, ring_id, ring_col, R, cols, p, tick, fused, others, fused_smooth, others_smooth,
-                   smooth_valid);
+// ---------------------------------------------------------------- the entries
+// The bounds the four entries share, each stated once, in the order the entries always checked them; `who` opens every message.
+// lanes: null for the entries of the fixed schedule.
+static int live_check(const char* who, int num_cameras, int slots, const int* lanes, int tick, int ring_depth) {
+  MCG_CHECK_ARG(num_cameras >= 0 && num_cameras <= MCG_LIVE_MAX_CAMERAS, "%s: 0 .. 65535 cameras per call (got %d)", who, num_cameras);
+  MCG_CHECK_ARG(slots >= 1 && slots <= MCG_LIVE_MAX_SLOTS, "%s: slots in 1 .. 64 (got %d)", who, slots);
+  if (lanes != nullptr) {
+    MCG_CHECK_ARG((long long)num_cameras * slots <= MCG_LIVE_MAX_COLUMNS, "%s: cameras x slots must not exceed 4096 (got %d x %d)", who, num_cameras,
+                  slots);
+    MCG_CHECK_ARG(*lanes >= 1 && *lanes <= MCG_LIVE_MAX_LANES, "%s: lanes in 1 .. 1024 (got %d)", who, *lanes);
+  }
+  MCG_CHECK_ARG(tick >= 0, "%s: tick must not be negative (got %d)", who, tick);
+  MCG_CHECK_ARG(ring_depth >= 1 && ring_depth <= MCG_LIVE_MAX_RING, "%s: ring_depth in 1 .. 65536 (got %d)", who, ring_depth);
+  return MCG_OK;
 }
 
 extern "C" int mcg_live_slots(mcg_stream s, const void* state_dev, int num_cameras, int slots, int tick, int ring_depth, float* crop_boxes_dev,
                               int32_t* image_of_dev, int32_t* ring_id_dev, float* ring_box_dev, int32_t* matched_dev) {
-  MCG_CHECK_ARG(num_cameras >= 0 && num_cameras <= MCG_LIVE_MAX_CAMERAS, "mcg_live_slots: 0 .. 65535 cameras per call (got %d)", num_cameras);
-  MCG_CHECK_ARG(slots >= 1 && slots <= MCG_LIVE_MAX_SLOTS, "mcg_live_slots: slots in 1 .. 64 (got %d)", slots);
-  MCG_CHECK_ARG(tick >= 0, "mcg_live_slots: tick must not be negative (got %d)", tick);
-  MCG_CHECK_ARG(ring_depth >= 1 && ring_depth <= MCG_LIVE_MAX_RING, "mcg_live_slots: ring_depth in 1 .. 65536 (got %d)", ring_depth);
+  MCG_TRY(live_check("mcg_live_slots", num_cameras, slots, nullptr, tick, ring_depth));
   if (num_cameras == 0) return MCG_OK;
   MCG_CHECK_ARG(state_dev && crop_boxes_dev && image_of_dev && ring_id_dev && ring_box_dev && matched_dev, "mcg_live_slots: null pointer");
   MCG_CHECK_ARG(((uintptr_t)state_dev & 15) == 0, "mcg_live_slots: the state must be 16-byte aligned");
@@ -296,41 +288,10 @@ extern "C" int mcg_live_slots(mcg_stream s, const void* state_dev, int num_camer
   return MCG_OK;
 }
 
-extern "C" int mcg_live_gate(mcg_stream s, const int32_t* ring_id_dev, const float* ring_box_dev, int ring_depth, int num_cameras, int slots,
-                             int tick, const int32_t* table_dev, int num_entries, int first_out, int num_out, const float* fused_dev,
-                             const float* others_dev, float* fused_smooth_dev, float* others_smooth_dev, int32_t* track_id_dev,
-                             int32_t* valid_dev, float* head_box_dev, int32_t* image_of_dev, int32_t* smooth_valid_dev) {
-  MCG_CHECK_ARG(num_cameras >= 0 && num_cameras <= MCG_LIVE_MAX_CAMERAS, "mcg_live_gate: 0 .. 65535 cameras per call (got %d)", num_cameras);
-  MCG_CHECK_ARG(slots >= 1 && slots <= MCG_LIVE_MAX_SLOTS, "mcg_live_gate: slots in 1 .. 64 (got %d)", slots);
-  MCG_CHECK_ARG(tick >= 0, "mcg_live_gate: tick must not be negative (got %d)", tick);
-  MCG_CHECK_ARG(ring_depth >= 1 && ring_depth <= MCG_LIVE_MAX_RING, "mcg_live_gate: ring_depth in 1 .. 65536 (got %d)", ring_depth);
-  MCG_CHECK_ARG(num_entries >= 0 && num_entries <= MCG_LIVE_MAX_ENTRIES, "mcg_live_gate: 0 .. 65536 table entries (got %d)", num_entries);
-  MCG_CHECK_ARG(first_out >= 0 && num_out >= 0 && (long long)first_out + num_out <= num_entries,
-                "mcg_live_gate: the frames handed out must be entries of the table (first_out %d, num_out %d, %d entries)", first_out, num_out,
-                num_entries);
-  MCG_CHECK_ARG((long long)num_out * num_cameras * slots < (1ll << 31), "mcg_live_gate: frames x cameras x slots must stay below 2^31");
-  if (num_out == 0 || num_cameras == 0) return MCG_OK;
-  MCG_CHECK_ARG(ring_id_dev && ring_box_dev && table_dev && track_id_dev && valid_dev && head_box_dev && image_of_dev, "mcg_live_gate: null pointer");
-  const int given = (fused_dev != nullptr) + (others_dev != nullptr) + (fused_smooth_dev != nullptr) + (others_smooth_dev != nullptr);
-  MCG_CHECK_ARG(given == 0 || (given == 4 && smooth_valid_dev), "mcg_live_gate: smoothing takes fused, others, both smoothed tables and smooth_valid, or none");
-  const long long rows = (long long)num_out * num_cameras * slots;
-  hipLaunchKernelGGL(live_gate_kernel, dim3((unsigned)((rows + MCG_LIVE_THREADS - 1) / MCG_LIVE_THREADS)), dim3(MCG_LIVE_THREADS), 0, (hipStream_t)s,
-                     ring_id_dev, ring_box_dev, ring_depth, num_cameras, slots, tick, table_dev, num_entries, first_out, num_out, fused_dev,
-                     others_dev, fused_smooth_dev, others_smooth_dev, track_id_dev, valid_dev, head_box_dev, image_of_dev, smooth_valid_dev);
-  MCG_CHECK_LAUNCH("mcg_live_gate");
-  return MCG_OK;
-}
-
 extern "C" int mcg_live_lanes(mcg_stream s, const void* state_dev, int num_cameras, int slots, int lanes, int tick, int ring_depth,
                               int32_t* lane_state_dev, float* crop_boxes_dev, int32_t* image_of_dev, int32_t* ring_id_dev, float* ring_box_dev,
                               int32_t* ring_col_dev, int32_t* lane_of_dev, int32_t* matched_dev, int32_t* overflow_dev) {
-  MCG_CHECK_ARG(num_cameras >= 0 && num_cameras <= MCG_LIVE_MAX_CAMERAS, "mcg_live_lanes: 0 .. 65535 cameras per call (got %d)", num_cameras);
-  MCG_CHECK_ARG(slots >= 1 && slots <= MCG_LIVE_MAX_SLOTS, "mcg_live_lanes: slots in 1 .. 64 (got %d)", slots);
-  MCG_CHECK_ARG((long long)num_cameras * slots <= MCG_LIVE_MAX_COLUMNS, "mcg_live_lanes: cameras x slots must not exceed 4096 (got %d x %d)",
-                num_cameras, slots);
-  MCG_CHECK_ARG(lanes >= 1 && lanes <= MCG_LIVE_MAX_LANES, "mcg_live_lanes: lanes in 1 .. 1024 (got %d)", lanes);
-  MCG_CHECK_ARG(tick >= 0, "mcg_live_lanes: tick must not be negative (got %d)", tick);
-  MCG_CHECK_ARG(ring_depth >= 1 && ring_depth <= MCG_LIVE_MAX_RING, "mcg_live_lanes: ring_depth in 1 .. 65536 (got %d)", ring_depth);
+  MCG_TRY(live_check("mcg_live_lanes", num_cameras, slots, &lanes, tick, ring_depth));
   if (num_cameras == 0) return MCG_OK;
   MCG_CHECK_ARG(state_dev && lane_state_dev && crop_boxes_dev && image_of_dev && ring_id_dev && ring_box_dev && ring_col_dev && lane_of_dev &&
                     matched_dev && overflow_dev,
@@ -343,35 +304,46 @@ extern "C" int mcg_live_lanes(mcg_stream s, const void* state_dev, int num_camer
   return MCG_OK;
 }
 
+// Both gates: the bounds of the table and the launch.  lanes null: the slot ring of Q * S columns, no ring_col, no camera / slot outputs;
+// otherwise the lane ring of *lanes columns, and all three are required.
+static int live_gate(const char* who, mcg_stream s, const int32_t* ring_id, const float* ring_box, const int32_t* ring_col, int ring_depth,
+                     int num_cameras, int slots, const int* lanes, int tick, const int32_t* table, int num_entries, int first_out, int num_out,
+                     const float* fused, const float* others, float* fused_smooth, float* others_smooth, int32_t* track_id, int32_t* valid,
+                     int32_t* camera, int32_t* slot, float* head_box, int32_t* image_of, int32_t* smooth_valid) {
+  MCG_TRY(live_check(who, num_cameras, slots, lanes, tick, ring_depth));
+  MCG_CHECK_ARG(num_entries >= 0 && num_entries <= MCG_LIVE_MAX_ENTRIES, "%s: 0 .. 65536 table entries (got %d)", who, num_entries);
+  MCG_CHECK_ARG(first_out >= 0 && num_out >= 0 && (long long)first_out + num_out <= num_entries,
+                "%s: the frames handed out must be entries of the table (first_out %d, num_out %d, %d entries)", who, first_out, num_out, num_entries);
+  const int cols = lanes != nullptr ? *lanes : num_cameras * slots;          // <= 65535 * 64
+  const long long rows = (long long)num_out * cols;
+  MCG_CHECK_ARG(rows < (1ll << 31), "%s: frames x %s must stay below 2^31", who, lanes != nullptr ? "lanes" : "cameras x slots");
+  if (num_out == 0 || num_cameras == 0) return MCG_OK;
+  MCG_CHECK_ARG(ring_id && ring_box && table && track_id && valid && head_box && image_of && (lanes == nullptr || (ring_col && camera && slot)),
+                "%s: null pointer", who);
+  const int given = (fused != nullptr) + (others != nullptr) + (fused_smooth != nullptr) + (others_smooth != nullptr);
+  MCG_CHECK_ARG(given == 0 || (given == 4 && smooth_valid), "%s: smoothing takes fused, others, both smoothed tables and smooth_valid, or none", who);
+  hipLaunchKernelGGL(live_gate_kernel, dim3((unsigned)((rows + MCG_LIVE_THREADS - 1) / MCG_LIVE_THREADS)), dim3(MCG_LIVE_THREADS), 0, (hipStream_t)s,
+                     ring_id, ring_box, ring_col, ring_depth, cols, num_cameras, slots, tick, table, num_entries, first_out, num_out, fused, others,
+                     fused_smooth, others_smooth, track_id, valid, camera, slot, head_box, image_of, smooth_valid);
+  MCG_CHECK_LAUNCH(who);
+  return MCG_OK;
+}
+
+extern "C" int mcg_live_gate(mcg_stream s, const int32_t* ring_id_dev, const float* ring_box_dev, int ring_depth, int num_cameras, int slots,
+                             int tick, const int32_t* table_dev, int num_entries, int first_out, int num_out, const float* fused_dev,
+                             const float* others_dev, float* fused_smooth_dev, float* others_smooth_dev, int32_t* track_id_dev,
+                             int32_t* valid_dev, float* head_box_dev, int32_t* image_of_dev, int32_t* smooth_valid_dev) {
+  return live_gate("mcg_live_gate", s, ring_id_dev, ring_box_dev, nullptr, ring_depth, num_cameras, slots, nullptr, tick, table_dev, num_entries,
+                   first_out, num_out, fused_dev, others_dev, fused_smooth_dev, others_smooth_dev, track_id_dev, valid_dev, nullptr, nullptr,
+                   head_box_dev, image_of_dev, smooth_valid_dev);
+}
+
 extern "C" int mcg_live_gate_lanes(mcg_stream s, const int32_t* ring_id_dev, const float* ring_box_dev, const int32_t* ring_col_dev, int ring_depth,
                                    int num_cameras, int slots, int lanes, int tick, const int32_t* table_dev, int num_entries, int first_out,
                                    int num_out, const float* fused_dev, const float* others_dev, float* fused_smooth_dev, float* others_smooth_dev,
                                    int32_t* track_id_dev, int32_t* valid_dev, int32_t* camera_dev, int32_t* slot_dev, float* head_box_dev,
                                    int32_t* image_of_dev, int32_t* smooth_valid_dev) {
-  MCG_CHECK_ARG(num_cameras >= 0 && num_cameras <= MCG_LIVE_MAX_CAMERAS, "mcg_live_gate_lanes: 0 .. 65535 cameras per call (got %d)", num_cameras);
-  MCG_CHECK_ARG(slots >= 1 && slots <= MCG_LIVE_MAX_SLOTS, "mcg_live_gate_lanes: slots in 1 .. 64 (got %d)", slots);
-  MCG_CHECK_ARG((long long)num_cameras * slots <= MCG_LIVE_MAX_COLUMNS, "mcg_live_gate_lanes: cameras x slots must not exceed 4096 (got %d x %d)",
-                num_cameras, slots);
-  MCG_CHECK_ARG(lanes >= 1 && lanes <= MCG_LIVE_MAX_LANES, "mcg_live_gate_lanes: lanes in 1 .. 1024 (got %d)", lanes);
-  MCG_CHECK_ARG(tick >= 0, "mcg_live_gate_lanes: tick must not be negative (got %d)", tick);
-  MCG_CHECK_ARG(ring_depth >= 1 && ring_depth <= MCG_LIVE_MAX_RING, "mcg_live_gate_lanes: ring_depth in 1 .. 65536 (got %d)", ring_depth);
-  MCG_CHECK_ARG(num_entries >= 0 && num_entries <= MCG_LIVE_MAX_ENTRIES, "mcg_live_gate_lanes: 0 .. 65536 table entries (got %d)", num_entries);
-  MCG_CHECK_ARG(first_out >= 0 && num_out >= 0 && (long long)first_out + num_out <= num_entries,
-                "mcg_live_gate_lanes: the frames handed out must be entries of the table (first_out %d, num_out %d, %d entries)", first_out, num_out,
-                num_entries);
-  MCG_CHECK_ARG((long long)num_out * lanes < (1ll << 31), "mcg_live_gate_lanes: frames x lanes must stay below 2^31");
-  if (num_out == 0 || num_cameras == 0) return MCG_OK;
-  MCG_CHECK_ARG(ring_id_dev && ring_box_dev && ring_col_dev && table_dev && track_id_dev && valid_dev && camera_dev && slot_dev && head_box_dev &&
-                    image_of_dev,
-                "mcg_live_gate_lanes: null pointer");
-  const int given = (fused_dev != nullptr) + (others_dev != nullptr) + (fused_smooth_dev != nullptr) + (others_smooth_dev != nullptr);
-  MCG_CHECK_ARG(given == 0 || (given == 4 && smooth_valid_dev),
-                "mcg_live_gate_lanes: smoothing takes fused, others, both smoothed tables and smooth_valid, or none");
-  const long long rows = (long long)num_out * lanes;
-  hipLaunchKernelGGL(live_gate_lanes_kernel, dim3((unsigned)((rows + MCG_LIVE_THREADS - 1) / MCG_LIVE_THREADS)), dim3(MCG_LIVE_THREADS), 0,
-                     (hipStream_t)s, ring_id_dev, ring_box_dev, ring_col_dev, ring_depth, num_cameras, slots, lanes, tick, table_dev, num_entries,
-                     first_out, num_out, fused_dev, others_dev, fused_smooth_dev, others_smooth_dev, track_id_dev, valid_dev, camera_dev, slot_dev,
-                     head_box_dev, image_of_dev, smooth_valid_dev);
-  MCG_CHECK_LAUNCH("mcg_live_gate_lanes");
-  return MCG_OK;
+  return live_gate("mcg_live_gate_lanes", s, ring_id_dev, ring_box_dev, ring_col_dev, ring_depth, num_cameras, slots, &lanes, tick, table_dev,
+                   num_entries, first_out, num_out, fused_dev, others_dev, fused_smooth_dev, others_smooth_dev, track_id_dev, valid_dev, camera_dev,
+                   slot_dev, head_box_dev, image_of_dev, smooth_valid_dev);
 }

@@ -19,13 +19,18 @@ the windows a planner handed out, per returned frame.
 ``LiveGaze(lanes=P)`` compacts the occupied slots into P streams instead ("live: occupied slots compacted into lanes" in the header):
 mcg_live_lanes (``live_lanes_host``) keeps a lane table (id, column) on the device, releases the lanes whose slot lost its person and hands
 the free lanes to the waiting slots in a fixed order; mcg_live_gate_lanes (``live_gate_lanes_host``) is the gate over the lanes' ring, with
-the same host-built table.  Trunk and decoder work per tick is then P frames, not Q * S."""
+the same host-built table.  Trunk and decoder work per tick is then P frames, not Q * S.
+
+The gate is stated ONCE, in ``_gate``, over a ring of columns: the slot ring is the lane ring with one column per (camera, slot) whose
+identity is its own index, so ``live_gate_host`` and ``live_gate_lanes_host`` share the "usable" rule of an entry, the neighbour rule of
+smoothing and the argument checks (live.hip does the same with one kernel)."""
 import ctypes as C
 
 import numpy as np
 import torch
 
 from . import lib as L
+from .engine import _upload_table
 from .harness import _host, check_smooth
 from .head_detect import TRACK_HEADER_WORDS, TRACK_MAX_SLOTS, TRACK_SLOT_WORDS, _track_params, track_state_words
 from .stream import GazeStreamPool, WindowPlanner
@@ -49,13 +54,15 @@ def _check_sizes(who, cameras, slots, depth=1, tick=0):
             raise ValueError(f'{who}: {name} in {lo} .. {hi}, got {v!r}')
 
 
-def _check_ring(who, ring_id, ring_box):
-    if ring_id.ndim != 3 or ring_id.dtype != np.int32 or ring_box.dtype != np.float32 or ring_box.shape != ring_id.shape + (4,):
-        raise ValueError(f'{who}: the ring is ring_id int32 [R, Q, S] and ring_box float32 [R, Q, S, 4], got {ring_id.dtype} {ring_id.shape} and '
-                         f'{ring_box.dtype} {ring_box.shape}')
-    R, Q, S = ring_id.shape
-    _check_sizes(who, Q, S, R)
-    return R, Q, S
+def _check_ring(who, ring_id, ring_box, ring_col=None):
+    """-> ring_id.shape: (R, Q, S) of the slot ring, or (R, P) of the lane ring (the one with a ring_col)."""
+    cols = ring_col is not None
+    if ring_id.ndim != (2 if cols else 3) or ring_id.dtype != np.int32 or ring_box.dtype != np.float32 or ring_box.shape != ring_id.shape + (4,) or \
+            (cols and (ring_col.dtype != np.int32 or ring_col.shape != ring_id.shape)):
+        lead = '[R, P]' if cols else '[R, Q, S]'
+        raise ValueError(f'{who}: the ring is ring_id{", ring_col" * cols} int32 {lead} and ring_box float32 {lead[:-1]}, 4], got ' +
+                         ', '.join(f'{x.dtype} {x.shape}' for x in (ring_id, ring_col, ring_box) if x is not None))
+    return ring_id.shape
 
 
 def live_slots_host(state, tick, ring_id, ring_box):
@@ -124,6 +131,66 @@ def check_gate_table(table, tick, depth):
     return table
 
 
+def _gate(who, ring_id, ring_col, ring_box, Q, S, tick, table, first_out, num_out, fused, others, fused_smooth, others_smooth):
+    """The gate of both entries, stated once, over a ring of C columns: ring_id [R, C], ring_box [R, C, 4] and ring_col [R, C], or None for
+    the slot ring, where C = Q * S and a column's identity is its own index.  -> the dict of live_gate_lanes_host, over [k, C]."""
+    R, C = ring_id.shape
+    _check_sizes(who, Q, S, R, tick)
+    table = np.ascontiguousarray(table, dtype=np.int32).reshape(-1, ENTRY)
+    n, k = len(table), int(num_out)
+    if n > MAX_ENTRIES or first_out < 0 or k < 0 or first_out + k > n or k * C >= 1 << 31:
+        raise ValueError(f'{who}: the frames handed out must be entries of the table (first_out {first_out}, num_out {k}, {n} entries)')
+    smoothing = [x is not None for x in (fused, others, fused_smooth, others_smooth)]
+    if any(smoothing) != all(smoothing):
+        raise ValueError(f'{who}: smoothing takes fused, others and both smoothed tables, or none')
+    own = np.arange(C, dtype=np.int32)
+    column = lambda t: own if ring_col is None else ring_col[t % R]
+
+    def state(j):
+        t, lo, hi, prev, nxt = (int(v) for v in table[j])
+        old = tick - R
+        usable = old < t <= tick and 0 <= lo <= hi <= tick + 1 and (hi == lo or lo > old) and prev >= -1 and nxt >= -1
+        if not usable:
+            return np.zeros(C, np.int32), np.full(C, -1, np.int32), np.zeros(C, bool)
+        ids, col = ring_id[t % R], column(t)
+        valid = ids != 0
+        for u in range(lo, hi):
+            valid = valid & (ring_id[u % R] == ids) & (column(u) == col)
+        return ids, col, valid
+
+    def neighbour(tk, ids, col):
+        for j in range(n):
+            if int(table[j, 0]) == tk:
+                idn, cn, vn = state(j)
+                return vn & (idn == ids) & (cn == col)
+        return np.zeros(C, bool)
+
+    new = lambda fill=0: np.full((k, C), fill, np.int32)
+    out = dict(track_id=new(), valid=new(), camera=new(-1), slot=new(-1), image_of=new(-1), head_box=np.zeros((k, C, 4), np.float32))
+    if all(smoothing):
+        out.update(smooth_valid=new(), fused_smooth=np.array(fused_smooth, dtype=np.float32).reshape(k, C, 3),
+                   others_smooth=np.array(others_smooth, dtype=np.float32).reshape(k, C, 3, 3))
+        fused, others = np.asarray(fused, dtype=np.float32).reshape(k, C, 3), np.asarray(others, dtype=np.float32).reshape(k, C, 3, 3)
+    for i in range(k):
+        e = first_out + i
+        ids, col, valid = state(e)
+        named = valid & (col >= 0) & (col < Q * S)                # every valid row of a slot ring
+        out['track_id'][i], out['valid'][i] = ids, valid
+        out['camera'][i], out['slot'][i] = np.where(named, col // S, -1), np.where(named, col % S, -1)
+        out['image_of'][i] = np.where(named, i * Q + col // S, -1)
+        if valid.any():
+            out['head_box'][i] = np.where(valid[:, None], ring_box[int(table[e, 0]) % R], np.float32(0))
+        if all(smoothing):
+            ok = valid.copy()
+            for tk in (int(table[e, 3]), int(table[e, 4])):
+                if tk != -1:
+                    ok &= neighbour(tk, ids, col)
+            out['smooth_valid'][i] = ok
+            raw = valid & ~ok
+            out['fused_smooth'][i][raw], out['others_smooth'][i][raw] = fused[i][raw], others[i][raw]
+    return out
+
+
 def live_gate_host(ring_id, ring_box, tick, table, first_out, num_out, fused=None, others=None, fused_smooth=None, others_smooth=None):
     """``mcg_live_gate`` in numpy, bit for bit.  ring_id / ring_box: the identity ring (live_slots_host), whose newest row is ``tick``; table
     int32 [n, 5] (live_gate_table), entries first_out .. first_out + num_out - 1 the frames handed out.  fused [k, Q, S, 3], others
@@ -132,56 +199,9 @@ def live_gate_host(ring_id, ring_box, tick, table, first_out, num_out, fused=Non
     the raw gaze where a row is valid next to a neighbour that is not]).  An entry that is not usable (a tick outside the ring) gives id 0,
     invalid rows: defined, like the kernel."""
     R, Q, S = _check_ring('live_gate', ring_id, ring_box)
-    _check_sizes('live_gate', Q, S, R, tick)
-    table = np.ascontiguousarray(table, dtype=np.int32).reshape(-1, ENTRY)
-    n, k = len(table), int(num_out)
-    if n > MAX_ENTRIES or first_out < 0 or k < 0 or first_out + k > n or k * Q * S >= 1 << 31:
-        raise ValueError(f'live_gate: the frames handed out must be entries of the table (first_out {first_out}, num_out {k}, {n} entries)')
-    smoothing = [x is not None for x in (fused, others, fused_smooth, others_smooth)]
-    if any(smoothing) != all(smoothing):
-        raise ValueError('live_gate: smoothing takes fused, others and both smoothed tables, or none')
-
-    def state(j):
-        t, lo, hi, prev, nxt = (int(v) for v in table[j])
-        old = tick - R
-        usable = old < t <= tick and 0 <= lo <= hi <= tick + 1 and (hi == lo or lo > old) and prev >= -1 and nxt >= -1
-        if not usable:
-            return np.zeros((Q, S), np.int32), np.zeros((Q, S), bool)
-        ids = ring_id[t % R]
-        valid = ids != 0
-        for u in range(lo, hi):
-            valid = valid & (ring_id[u % R] == ids)
-        return ids, valid
-
-    def neighbour(tk, ids):
-        for j in range(n):
-            if int(table[j, 0]) == tk:
-                idn, vn = state(j)
-                return vn & (idn == ids)
-        return np.zeros((Q, S), bool)
-
-    out = dict(track_id=np.zeros((k, Q, S), np.int32), valid=np.zeros((k, Q, S), np.int32), image_of=np.full((k, Q, S), -1, np.int32),
-               head_box=np.zeros((k, Q, S, 4), np.float32))
-    if all(smoothing):
-        out.update(smooth_valid=np.zeros((k, Q, S), np.int32), fused_smooth=np.array(fused_smooth, dtype=np.float32).reshape(k, Q, S, 3),
-                   others_smooth=np.array(others_smooth, dtype=np.float32).reshape(k, Q, S, 3, 3))
-        fused, others = np.asarray(fused, dtype=np.float32).reshape(k, Q, S, 3), np.asarray(others, dtype=np.float32).reshape(k, Q, S, 3, 3)
-    for i in range(k):
-        e = first_out + i
-        ids, valid = state(e)
-        out['track_id'][i], out['valid'][i] = ids, valid
-        out['image_of'][i] = np.where(valid, i * Q + np.arange(Q)[:, None], -1)
-        if valid.any():
-            out['head_box'][i] = np.where(valid[..., None], ring_box[int(table[e, 0]) % R], np.float32(0))
-        if all(smoothing):
-            ok = valid.copy()
-            for tk in (int(table[e, 3]), int(table[e, 4])):
-                if tk != -1:
-                    ok &= neighbour(tk, ids)
-            out['smooth_valid'][i] = ok
-            raw = valid & ~ok
-            out['fused_smooth'][i][raw], out['others_smooth'][i][raw] = fused[i][raw], others[i][raw]
-    return out
+    out = _gate('live_gate', ring_id.reshape(R, Q * S), None, ring_box.reshape(R, Q * S, 4), Q, S, tick, table, first_out, num_out, fused, others,
+                fused_smooth, others_smooth)
+    return {name: v.reshape((len(v), Q, S) + v.shape[2:]) for name, v in out.items() if name not in ('camera', 'slot')}
 
 
 def _check_lanes(who, lanes, cameras, slots):
@@ -190,14 +210,6 @@ def _check_lanes(who, lanes, cameras, slots):
     if cameras * slots > MAX_COLUMNS:
         raise ValueError(f'{who}: with lanes, cameras x slots must not exceed {MAX_COLUMNS} (got {cameras} x {slots})')
     return int(lanes)
-
-
-def _check_lane_ring(who, ring_id, ring_box, ring_col):
-    if ring_id.ndim != 2 or ring_id.dtype != np.int32 or ring_col.dtype != np.int32 or ring_col.shape != ring_id.shape or \
-            ring_box.dtype != np.float32 or ring_box.shape != ring_id.shape + (4,):
-        raise ValueError(f'{who}: the ring is ring_id, ring_col int32 [R, P] and ring_box float32 [R, P, 4], got {ring_id.dtype} {ring_id.shape}, '
-                         f'{ring_col.dtype} {ring_col.shape} and {ring_box.dtype} {ring_box.shape}')
-    return ring_id.shape
 
 
 def live_lanes_host(state, tick, lane_state, ring_id, ring_box, ring_col):
@@ -210,7 +222,7 @@ def live_lanes_host(state, tick, lane_state, ring_id, ring_box, ring_col):
     free lane's zero box and -1 --, lane_of int32 [Q, S] (-1: the slot is free, or live and left out), matched int32 [P], overflow int32 [1]:
     the live slots left without a lane)."""
     state = np.asarray(_host(state))
-    R, P = _check_lane_ring('live_lanes', ring_id, ring_box, ring_col)
+    R, P = _check_ring('live_lanes', ring_id, ring_box, ring_col)
     if state.ndim != 2 or state.dtype != np.int32 or state.shape[1] < TRACK_HEADER_WORDS + TRACK_SLOT_WORDS or \
             (state.shape[1] - TRACK_HEADER_WORDS) % TRACK_SLOT_WORDS:
         raise ValueError(f'live_lanes: the state of Q cameras of S slots is an int32 [Q, {TRACK_HEADER_WORDS} + {TRACK_SLOT_WORDS} * S] array, got '
@@ -250,61 +262,10 @@ def live_gate_lanes_host(ring_id, ring_box, ring_col, cameras, slots, tick, tabl
     [k, P, 3, 3], fused_smooth, others_smooth: all four (smoothing) or none.
     -> dict(track_id, valid, camera, slot, image_of int32 [k, P], head_box float32 [k, P, 4][, smooth_valid, fused_smooth, others_smooth]).
     camera / slot name the slot the lane held at the frame's tick and image_of is i * Q + camera, all three -1 on invalid rows."""
-    R, P = _check_lane_ring('live_gate_lanes', ring_id, ring_box, ring_col)
-    Q, S = int(cameras), int(slots)
-    _check_sizes('live_gate_lanes', Q, S, R, tick)
-    _check_lanes('live_gate_lanes', P, Q, S)
-    table = np.ascontiguousarray(table, dtype=np.int32).reshape(-1, ENTRY)
-    n, k = len(table), int(num_out)
-    if n > MAX_ENTRIES or first_out < 0 or k < 0 or first_out + k > n or k * P >= 1 << 31:
-        raise ValueError(f'live_gate_lanes: the frames handed out must be entries of the table (first_out {first_out}, num_out {k}, {n} entries)')
-    smoothing = [x is not None for x in (fused, others, fused_smooth, others_smooth)]
-    if any(smoothing) != all(smoothing):
-        raise ValueError('live_gate_lanes: smoothing takes fused, others and both smoothed tables, or none')
-
-    def state(j):
-        t, lo, hi, prev, nxt = (int(v) for v in table[j])
-        old = tick - R
-        usable = old < t <= tick and 0 <= lo <= hi <= tick + 1 and (hi == lo or lo > old) and prev >= -1 and nxt >= -1
-        if not usable:
-            return np.zeros(P, np.int32), np.full(P, -1, np.int32), np.zeros(P, bool)
-        ids, col = ring_id[t % R], ring_col[t % R]
-        valid = ids != 0
-        for u in range(lo, hi):
-            valid = valid & (ring_id[u % R] == ids) & (ring_col[u % R] == col)
-        return ids, col, valid
-
-    def neighbour(tk, ids, col):
-        for j in range(n):
-            if int(table[j, 0]) == tk:
-                idn, cn, vn = state(j)
-                return vn & (idn == ids) & (cn == col)
-        return np.zeros(P, bool)
-
-    new = lambda fill=0: np.full((k, P), fill, np.int32)
-    out = dict(track_id=new(), valid=new(), camera=new(-1), slot=new(-1), image_of=new(-1), head_box=np.zeros((k, P, 4), np.float32))
-    if all(smoothing):
-        out.update(smooth_valid=new(), fused_smooth=np.array(fused_smooth, dtype=np.float32).reshape(k, P, 3),
-                   others_smooth=np.array(others_smooth, dtype=np.float32).reshape(k, P, 3, 3))
-        fused, others = np.asarray(fused, dtype=np.float32).reshape(k, P, 3), np.asarray(others, dtype=np.float32).reshape(k, P, 3, 3)
-    for i in range(k):
-        e = first_out + i
-        ids, col, valid = state(e)
-        named = valid & (col >= 0) & (col < Q * S)
-        out['track_id'][i], out['valid'][i] = ids, valid
-        out['camera'][i], out['slot'][i] = np.where(named, col // S, -1), np.where(named, col % S, -1)
-        out['image_of'][i] = np.where(named, i * Q + col // S, -1)
-        if valid.any():
-            out['head_box'][i] = np.where(valid[:, None], ring_box[int(table[e, 0]) % R], np.float32(0))
-        if all(smoothing):
-            ok = valid.copy()
-            for tk in (int(table[e, 3]), int(table[e, 4])):
-                if tk != -1:
-                    ok &= neighbour(tk, ids, col)
-            out['smooth_valid'][i] = ok
-            raw = valid & ~ok
-            out['fused_smooth'][i][raw], out['others_smooth'][i][raw] = fused[i][raw], others[i][raw]
-    return out
+    _, P = _check_ring('live_gate_lanes', ring_id, ring_box, ring_col)
+    _check_lanes('live_gate_lanes', P, int(cameras), int(slots))
+    return _gate('live_gate_lanes', ring_id, ring_col, ring_box, int(cameras), int(slots), tick, table, first_out, num_out, fused, others, fused_smooth,
+                 others_smooth)
 
 
 def _clone_frame(f):
@@ -367,8 +328,9 @@ class LiveGaze:
         self.frame_options = dict(pixel_format=pixel_format, matrix=matrix)
         self.rgb = bool(rgb)
         _, _, pad_h, pad_w, _ = pipeline.head_crop_geometry()
-        n = self.Q * self.S if self.P is None else self.P       # the pool's streams: every slot, or the lanes
-        self.lead = (self.Q, self.S) if self.P is None else (self.P,)
+        # the pool's streams, and what the gate says of a row besides: every slot, or the lanes and the slot each held
+        self.lead, self.extra = ((self.Q, self.S), ()) if self.P is None else ((self.P,), ('camera', 'slot'))
+        n = int(np.prod(self.lead))
         self.pool = GazeStreamPool(engine_or_model, pad_h, pad_w, clip_len, stride, rows=n * (clip_len + stride + 1), person_threshold=person_threshold,
                                    max_decode_windows=max_decode_windows, max_trunk_frames=max(448, n), merge='device', results='device', smooth=self.smooth)
         self.sids = [self.pool.open() for _ in range(n)]
@@ -386,8 +348,34 @@ class LiveGaze:
         self.ticks = self.emitted = 0
         self.finished = False
 
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream)
+    def _call(self, name, *args):
+        """One entry of the library on the current stream: a tensor goes as its address, None as a null pointer, an int as it is."""
+        ptr = lambda a: C.c_void_p(a.data_ptr()) if isinstance(a, torch.Tensor) else C.c_void_p(0) if a is None else a
+        L.check(getattr(self.lib, name)(C.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream), *map(ptr, args)), name)
+
+    def _assign(self):
+        """The tick's crop table (crop_boxes, image_of) and ring row from the tracker state -> what the tick returns of it."""
+        new = lambda *shape: torch.empty(*shape, dtype=torch.int32, device=self.dev)
+        matched = new(*self.lead)
+        if self.P is None:
+            self._call('mcg_live_slots', self.state, self.Q, self.S, self.ticks, self.R, self.crop_boxes, self.image_of, self.ring_id, self.ring_box,
+                       matched)
+            return dict(matched=matched)
+        lane_of, overflow = new(self.Q, self.S), new(1)
+        self._call('mcg_live_lanes', self.state, self.Q, self.S, self.P, self.ticks, self.R, self.lane_state, self.crop_boxes, self.image_of,
+                   self.ring_id, self.ring_box, self.ring_col, lane_of, matched, overflow)
+        return dict(matched=matched, lane_of=lane_of, overflow=overflow)
+
+    def _gate(self, plan, num_entries, first_out, k, out):
+        """The gate over the k frames handed out, into the tables of ``out``."""
+        smooth = [out[name] if self.smooth is not None else None for name in ('fused', 'others', 'fused_smooth', 'others_smooth')]
+        table = [self.ticks - 1, plan, num_entries, first_out, k, *smooth, out['track_id'], out['valid']]
+        tail = [out['head_box'], out['image_of'], out.get('smooth_valid')]
+        if self.P is None:
+            self._call('mcg_live_gate', self.ring_id, self.ring_box, self.R, self.Q, self.S, *table, *tail)
+        else:
+            self._call('mcg_live_gate_lanes', self.ring_id, self.ring_box, self.ring_col, self.R, self.Q, self.S, self.P, *table, out['camera'],
+                       out['slot'], *tail)
 
     def tick(self, frames, boxes, counts):
         """One frame per camera and its detections -> the frames that became final (see the class)."""
@@ -397,24 +385,10 @@ class LiveGaze:
         if len(frames) != self.Q or boxes.ndim != 3 or (boxes.shape[0], boxes.shape[2]) != (self.Q, 4) or tuple(counts.shape) != (self.Q,):
             raise ValueError(f'LiveGaze.tick: {self.Q} frames, boxes [{self.Q}, D, 4] and counts [{self.Q}] (got {len(frames)} frames, '
                              f'{tuple(boxes.shape)}, {tuple(counts.shape)})')
-        vp = C.c_void_p
         with torch.cuda.device(self.dev):
             out = self.pipe.track_heads(boxes[:, None], counts[:, None], state=self.state, slots=self.S, match_iou=self.match_iou, max_age=self.max_age,
                                         device=self.dev)
-            matched = torch.empty(*self.lead, dtype=torch.int32, device=self.dev)
-            more = dict(flags=out[5].reshape(self.Q), matched=matched)
-            if self.P is None:
-                L.check(self.lib.mcg_live_slots(self._stream(), vp(self.state.data_ptr()), self.Q, self.S, self.ticks, self.R, vp(self.crop_boxes.data_ptr()),
-                                                vp(self.image_of.data_ptr()), vp(self.ring_id.data_ptr()), vp(self.ring_box.data_ptr()),
-                                                vp(matched.data_ptr())), 'mcg_live_slots')
-            else:
-                more.update(lane_of=torch.empty(self.Q, self.S, dtype=torch.int32, device=self.dev),
-                            overflow=torch.empty(1, dtype=torch.int32, device=self.dev))
-                L.check(self.lib.mcg_live_lanes(self._stream(), vp(self.state.data_ptr()), self.Q, self.S, self.P, self.ticks, self.R,
-                                                vp(self.lane_state.data_ptr()), vp(self.crop_boxes.data_ptr()), vp(self.image_of.data_ptr()),
-                                                vp(self.ring_id.data_ptr()), vp(self.ring_box.data_ptr()), vp(self.ring_col.data_ptr()),
-                                                vp(more['lane_of'].data_ptr()), vp(matched.data_ptr()), vp(more['overflow'].data_ptr())),
-                        'mcg_live_lanes')
+            more = dict(flags=out[5].reshape(self.Q), **self._assign())
             img, img_hw, _, _, _ = self.pipe.head_crops(frames, self.crop_boxes, self.image_of, expand=self.expand, device=self.dev, rgb=self.rgb,
                                                         **self.frame_options)
             for j, sid in enumerate(self.sids):
@@ -439,7 +413,7 @@ class LiveGaze:
             return self._emit(res)
 
     def _emit(self, res, **more):
-        Q, S, lead, smoothing = self.Q, self.S, self.lead, self.smooth is not None
+        Q, lead, smoothing = self.Q, self.lead, self.smooth is not None
         upto = self.planner.final_upto
         k = max(0, upto - self.emitted - int(smoothing and not self.finished))
         got = [res.get(sid) for sid in self.sids]
@@ -455,29 +429,12 @@ class LiveGaze:
             parts = {name: torch.empty((0,) + lead + tail[name], dtype=torch.float32, device=self.dev) for name in names}
         new = lambda *shape, dtype=torch.int32: torch.empty(*shape, dtype=dtype, device=self.dev)
         gate = dict(track_id=new(k, *lead), valid=new(k, *lead), head_box=new(k, *lead, 4, dtype=torch.float32), image_of=new(k, *lead))
-        if self.P is not None:
-            gate.update(camera=new(k, self.P), slot=new(k, self.P))
-        if smoothing:
-            gate['smooth_valid'] = new(k, *lead)
+        gate.update({name: new(k, *lead) for name in self.extra + (('smooth_valid',) if smoothing else ())})
         out = dict(first=self.emitted, **gate, **parts, **more)
         if k:
-            from .engine import _upload_table
             table, first_out = live_gate_table(self.windows, self.emitted, k, smoothing, self.ticks - 1 if self.finished else None)
             table = check_gate_table(table, self.ticks - 1, self.R)
-            plan = _upload_table(table, self.dev)
-            p = lambda name: C.c_void_p(out[name].data_ptr()) if name in out else C.c_void_p(0)
-            raw = ('fused', 'others') if smoothing else ('', '')
-            if self.P is None:
-                L.check(self.lib.mcg_live_gate(self._stream(), C.c_void_p(self.ring_id.data_ptr()), C.c_void_p(self.ring_box.data_ptr()),
-                                               self.R, Q, S, self.ticks - 1, C.c_void_p(plan.data_ptr()), len(table), first_out, k, p(raw[0]), p(raw[1]),
-                                               p('fused_smooth'), p('others_smooth'), p('track_id'), p('valid'), p('head_box'), p('image_of'),
-                                               p('smooth_valid')), 'mcg_live_gate')
-            else:
-                L.check(self.lib.mcg_live_gate_lanes(self._stream(), C.c_void_p(self.ring_id.data_ptr()), C.c_void_p(self.ring_box.data_ptr()),
-                                                     C.c_void_p(self.ring_col.data_ptr()), self.R, Q, S, self.P, self.ticks - 1,
-                                                     C.c_void_p(plan.data_ptr()), len(table), first_out, k, p(raw[0]), p(raw[1]), p('fused_smooth'),
-                                                     p('others_smooth'), p('track_id'), p('valid'), p('camera'), p('slot'), p('head_box'),
-                                                     p('image_of'), p('smooth_valid')), 'mcg_live_gate_lanes')
+            self._gate(_upload_table(table, self.dev), len(table), first_out, k, out)
             self.windows = [w for w in self.windows if w[1] > self.emitted + k - 1]     # the next call's first neighbour is the last frame of this
         if self.draw:
             images = [f for t in range(self.emitted, self.emitted + k) for f in self.kept.pop(t)]

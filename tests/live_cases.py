@@ -8,7 +8,8 @@ Camera 1:  empty until tick 6, then D, detected up to tick 24 (it coasts 25 and 
 The variant scene ('other'): C enters at the same tick and position, B never existed, and camera 1 shows one other head from tick 2 on.
 
 ``run_host`` is the whole chain on the host with the schedule LiveGaze has: track_heads_host, live_slots_host, the spans of a WindowPlanner,
-live_gate_host -- one frame per tick, a frame handed out once it is final (one frame later with smoothing), the rest at the end."""
+live_gate_host -- one frame per tick, a frame handed out once it is final (one frame later with smoothing), the rest at the end; with
+``lanes``, the same schedule over live_lanes_host and live_gate_lanes_host (tests/live_lanes_cases.py holds the scene made for it)."""
 import numpy as np
 
 from mcgaze_amd import live
@@ -58,26 +59,42 @@ def scene(variant='main'):
     return boxes, counts
 
 
-def fake_gaze(k, first):
-    """Stand-ins for a pool's gaze rows of frames first .. first + k - 1, each value naming its (frame, camera, slot, component), and their
-    'smoothed' twins (negated): the gate copies rows, it computes nothing on them."""
-    f, q, s = np.meshgrid(np.arange(first, first + k), np.arange(Q), np.arange(S), indexing='ij')
-    base = (f * 1000 + q * 100 + s * 10).astype(np.float32)
+def fake_gaze(k, first, lanes=None):
+    """Stand-ins for a pool's gaze rows of frames first .. first + k - 1, each value naming its (frame, camera, slot, component) -- with
+    lanes, its (frame, lane, component) --, and their 'smoothed' twins (negated): the gate copies rows, it computes nothing on them."""
+    if lanes is None:
+        f, q, s = np.meshgrid(np.arange(first, first + k), np.arange(Q), np.arange(S), indexing='ij')
+        base = (f * 1000 + q * 100 + s * 10).astype(np.float32)
+    else:
+        f, p = np.meshgrid(np.arange(first, first + k), np.arange(lanes), indexing='ij')
+        base = (f * 10000 + p * 10).astype(np.float32)
     fused = base[..., None] + np.arange(3, dtype=np.float32)
     others = base[..., None, None] + np.arange(3, 12, dtype=np.float32).reshape(3, 3)
     return fused, others, -fused, -others
 
 
-def run_host(boxes, counts, smooth=False, gaze=fake_gaze):
-    """-> dict(ticks=[per tick: crop_boxes, image_of, ring_id row, ring_box row, matched, flags], emitted=[(tick it was returned at, first, k)],
-    windows, tables=[(table, first_out)], and the gate's outputs concatenated over the frames: track_id, valid, image_of, head_box[,
-    smooth_valid, fused_smooth, others_smooth]).  gaze(k, first) -> (fused, others, fused_smooth, others_smooth) of the returned frames."""
+def run_host(boxes, counts, smooth=False, gaze=fake_gaze, lanes=None):
+    """The fixed schedule, or with ``lanes`` the lanes of LiveGaze(lanes=lanes).
+    -> dict(ticks=[per tick: crop_boxes, image_of, ring_id row, ring_box row, matched, flags, track_id; with lanes also lane_state, lane_of,
+    overflow and the ring_col row], emitted=[(tick it was returned at, first, k)], windows, tables=[(table, first_out)], and the gate's
+    outputs concatenated over the frames: track_id, valid, image_of, head_box[, camera, slot][, smooth_valid, fused_smooth,
+    others_smooth]).  gaze(k, first, lanes) -> (fused, others, fused_smooth, others_smooth) of the returned frames."""
     R = live.ring_depth(CLIP)
-    ring_id, ring_box = np.zeros((R, Q, S), np.int32), np.zeros((R, Q, S, 4), np.float32)
+    lead = (Q, S) if lanes is None else (lanes,)
+    ring_id, ring_box = np.zeros((R,) + lead, np.int32), np.zeros((R,) + lead + (4,), np.float32)
+    ring_col, lane_state = np.zeros((R,) + lead, np.int32), np.zeros(lead + (2,), np.int32)      # with lanes only
     state = np.zeros((Q, track_state_words(S)), np.int32)
     planner, windows, emitted = WindowPlanner(CLIP, STRIDE), [], 0
     out = dict(ticks=[], emitted=[], tables=[], windows=[])
     parts = []
+
+    def assign(t):
+        if lanes is None:
+            crop_boxes, image_of, matched = live.live_slots_host(state, t, ring_id, ring_box)
+            return dict(crop_boxes=crop_boxes, image_of=image_of, matched=matched)
+        crop_boxes, image_of, lane_of, matched, overflow = live.live_lanes_host(state, t, lane_state, ring_id, ring_box, ring_col)
+        return dict(crop_boxes=crop_boxes, image_of=image_of, matched=matched, lane_state=lane_state.copy(), lane_of=lane_of, overflow=overflow,
+                    ring_col=ring_col[t % R].copy())
 
     def emit(tick, ended):
         nonlocal emitted
@@ -85,8 +102,11 @@ def run_host(boxes, counts, smooth=False, gaze=fake_gaze):
         if k:
             table, first_out = live.live_gate_table(windows, emitted, k, smooth, tick if ended else None)
             table = live.check_gate_table(table, tick, R)
-            g = gaze(k, emitted) if smooth else (None,) * 4
-            parts.append(live.live_gate_host(ring_id, ring_box, tick, table, first_out, k, *g))
+            g = gaze(k, emitted, lanes) if smooth else (None,) * 4
+            if lanes is None:
+                parts.append(live.live_gate_host(ring_id, ring_box, tick, table, first_out, k, *g))
+            else:
+                parts.append(live.live_gate_lanes_host(ring_id, ring_box, ring_col, Q, S, tick, table, first_out, k, *g))
             out['tables'].append((table, first_out))
         out['emitted'].append((tick, emitted, k))
         emitted += k
@@ -94,9 +114,8 @@ def run_host(boxes, counts, smooth=False, gaze=fake_gaze):
     for t in range(len(boxes)):
         res = track_heads_host(boxes[t][:, None], counts[t][:, None], state=state, **OPTIONS)
         state = res[6]
-        crop_boxes, image_of, matched = live.live_slots_host(state, t, ring_id, ring_box)
-        out['ticks'].append(dict(crop_boxes=crop_boxes, image_of=image_of, ring_id=ring_id[t % R].copy(), ring_box=ring_box[t % R].copy(),
-                                 matched=matched, flags=res[5].reshape(Q), track_id=res[2].reshape(Q, S)))
+        out['ticks'].append(dict(assign(t), ring_id=ring_id[t % R].copy(), ring_box=ring_box[t % R].copy(), flags=res[5].reshape(Q),
+                                 track_id=res[2].reshape(Q, S)))
         windows += planner.feed(1)
         emit(t, False)
     windows += planner.finish()
@@ -105,3 +124,18 @@ def run_host(boxes, counts, smooth=False, gaze=fake_gaze):
     for name in parts[0]:
         out[name] = np.concatenate([p[name] for p in parts])
     return out
+
+
+def ring_at(run, tick):
+    """The identity ring of a fixed-schedule run_host as it stood after ``tick``, from the rows its ticks recorded."""
+    R = live.ring_depth(CLIP)
+    ring_id, ring_box = np.zeros((R, Q, S), np.int32), np.zeros((R, Q, S, 4), np.float32)
+    for t in range(max(0, tick - R + 1), tick + 1):
+        ring_id[t % R], ring_box[t % R] = run['ticks'][t]['ring_id'], run['ticks'][t]['ring_box']
+    return ring_id, ring_box
+
+
+def as_lane_ring(ring_id, ring_box):
+    """A slot ring as the lane ring it is: P = Q * S lanes, lane p naming column p wherever a person is.  -> (ring_id, ring_box, ring_col)."""
+    ids = ring_id.reshape(len(ring_id), Q * S)
+    return ids, ring_box.reshape(len(ring_id), Q * S, 4), np.where(ids != 0, np.arange(Q * S, dtype=np.int32), -1).astype(np.int32)

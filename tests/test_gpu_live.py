@@ -9,88 +9,36 @@ import numpy as np
 import pytest
 import torch
 
-from mcgaze_amd import live, synth
-from mcgaze_amd import pipeline as P
+from mcgaze_amd import live
 from mcgaze_amd.arrows import draw_arrows_host
 from mcgaze_amd.stream import GazeStream, GazeStreamPool
 from tests import live_cases as LC
-from tests.test_gpu_nv12 import chain
+from tests.live_gpu_common import ALPHA, CAMS, DEV, GAZE, call, dev, make_engine, make_frames, make_pipe, run_live, same
 
 pytestmark = pytest.mark.gpu
 
-DEV = 'cuda:0'
-ALPHA = 0.6
-H, W = LC.FRAME_HW
-GAZE = ('det', 'fused', 'others')
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
-
-
-def make_frames(seed):
-    """[TICKS, 96, 128, 3] uint8: one frame per tick of one camera."""
-    return np.random.default_rng(seed).integers(0, 256, (LC.TICKS, H, W, 3), dtype=np.uint8)
-
-
-CAM0, CAM1, CAM1_OTHER = make_frames(1), make_frames(2), make_frames(3)
+CAM0, CAM1 = CAMS
+CAMS_OTHER = (CAM0, make_frames(3))
 
 
 @pytest.fixture(scope='module')
 def engine():
-    from mcgaze_amd.engine import HipEngine
-    return HipEngine(synth.make_state_dict(0), precision='f16x3')
+    return make_engine()
 
 
 @pytest.fixture(scope='module')
 def pipe():
-    return P.DevicePipeline(chain(64))
-
-
-def run_live(engine, pipe, variant, cam1, smooth=ALPHA, draw=False):
-    """The scene through LiveGaze -> dict of host arrays: the results concatenated over all returned frames, ``ticks`` (what each tick left in
-    the object's tables), ``calls`` ((first, k) of every call) and, with draw, ``frames`` [(frame index, [Q annotated frames])]."""
-    boxes, counts = LC.scene(variant)
-    lg = live.LiveGaze(engine, pipe, cameras=LC.Q, clip_len=LC.CLIP, stride=LC.STRIDE, smooth=smooth, draw=draw, **LC.OPTIONS)
-    bufs = [torch.empty(H, W, 3, dtype=torch.uint8, device=DEV) for _ in range(LC.Q)]      # a camera's buffer, rewritten every tick
-    ticks, results = [], []
-    for t in range(LC.TICKS):
-        bufs[0].copy_(dev(CAM0[t]))
-        bufs[1].copy_(dev(cam1[t]))
-        r = lg.tick(bufs, dev(boxes[t]), dev(counts[t]))
-        row = t % lg.R
-        ticks.append(dict(crop_boxes=lg.crop_boxes.clone(), image_of=lg.image_of.clone(), ring_id=lg.ring_id[row].clone(),
-                          ring_box=lg.ring_box[row].clone(), matched=r['matched'], flags=r['flags']))
-        results.append(r)
-    results.append(lg.finish())
-    torch.cuda.synchronize()
-    out = dict(calls=[(r['first'], int(r['valid'].shape[0])) for r in results],
-               ticks=[{k: v.cpu().numpy() for k, v in rec.items()} for rec in ticks])
-    names = ('track_id', 'valid', 'head_box', 'image_of') + GAZE + (('smooth_valid', 'fused_smooth', 'others_smooth') if smooth else ())
-    for name in names:
-        out[name] = torch.cat([r[name] for r in results]).cpu().numpy()
-    if draw:
-        out['frames'] = [(r['first'] + i, [f.cpu().numpy() for f in fr]) for r in results for i, fr in enumerate(r['frames'])]
-    return out
+    return make_pipe()
 
 
 @pytest.fixture(scope='module')
 def main_run(engine, pipe):
-    return run_live(engine, pipe, 'main', CAM1)
+    return run_live(engine, pipe, 'main')
 
 
 @pytest.fixture(scope='module')
 def twin():
     return LC.run_host(*LC.scene(), smooth=True)
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.int32)
-
-
-def same(a, b, what):
-    assert a.dtype == b.dtype and a.shape == b.shape, (what, a.dtype, a.shape, b.dtype, b.shape)
-    assert np.array_equal(bits(a), bits(b)), what
 
 
 def slot_crops(pipe, twin, where):
@@ -124,6 +72,39 @@ def test_kernels_equal_the_host_twins(main_run, twin):
     same(main_run['others_smooth'][raw], main_run['others'][raw], 'others_smooth where only valid')
 
 
+def test_a_slot_ring_is_a_lane_ring_whose_column_is_its_own_index(twin):
+    """mcg_live_gate and mcg_live_gate_lanes, called directly, over the twin's ring as it stood at its last tick() that returned a frame
+    and at finish(): the slot ring handed to the lanes entry as P = Q * S lanes, lane p naming column p.  Every output both entries have
+    is the same bit for bit (and the twin's); camera / slot are p // S and p % S on the valid rows and -1 elsewhere."""
+    cols = LC.Q * LC.S
+    calls = [c for c in twin['emitted'] if c[2]]
+    assert calls[-2:] == [(27, 19, 1), (27, 20, 8)]
+    new = lambda *shape, dtype=torch.int32: torch.full(shape, 77, dtype=dtype, device=DEV)
+    for (tick, first, k), (table, first_out) in zip(calls[-2:], twin['tables'][-2:]):
+        ring_id, ring_box = LC.ring_at(twin, tick)
+        lane_id, lane_box, lane_col = LC.as_lane_ring(ring_id, ring_box)
+        fused, others, fused_s, others_s = LC.fake_gaze(k, first)
+        got = {}
+        for name, ring, lead in (('mcg_live_gate', (dev(ring_id), dev(ring_box), live.ring_depth(LC.CLIP), LC.Q, LC.S), (k, LC.Q, LC.S)),
+                                 ('mcg_live_gate_lanes', (dev(lane_id), dev(lane_box), dev(lane_col), live.ring_depth(LC.CLIP), LC.Q, LC.S, cols),
+                                  (k, cols))):
+            o = dict(fused_smooth=dev(fused_s), others_smooth=dev(others_s), head_box=new(*lead, 4, dtype=torch.float32))
+            o.update({n: new(*lead) for n in ('track_id', 'valid', 'camera', 'slot', 'image_of', 'smooth_valid')})
+            extra = (o['camera'], o['slot']) if name == 'mcg_live_gate_lanes' else ()
+            call(name, *ring, tick, dev(table), len(table), first_out, k, dev(fused), dev(others), o['fused_smooth'], o['others_smooth'], o['track_id'],
+                 o['valid'], *extra, o['head_box'], o['image_of'], o['smooth_valid'])
+            torch.cuda.synchronize()
+            got[name] = {n: v.cpu().numpy() for n, v in o.items()}
+        slots, lanes = got['mcg_live_gate'], got['mcg_live_gate_lanes']
+        for name in ('track_id', 'valid', 'image_of', 'head_box', 'smooth_valid', 'fused_smooth', 'others_smooth'):
+            same(slots[name], twin[name][first:first + k], name)
+            same(lanes[name], slots[name].reshape(lanes[name].shape), name + ' over lanes')
+        valid, p = lanes['valid'] == 1, np.arange(cols, dtype=np.int32)[None]
+        assert valid.sum() >= 2 and not valid.all()
+        same(lanes['camera'], np.where(valid, p // LC.S, -1).astype(np.int32), 'camera')
+        same(lanes['slot'], np.where(valid, p % LC.S, -1).astype(np.int32), 'slot')
+
+
 # ---------------------------------------------------------------- 2. the pool's contract, through LiveGaze
 @pytest.mark.parametrize('where', [LC.SLOT_A, LC.SLOT_BC], ids=['A', 'B_then_C'])
 def test_a_slot_is_a_lone_stream_of_its_crops(engine, pipe, main_run, twin, where):
@@ -143,7 +124,7 @@ def test_a_slot_is_a_lone_stream_of_its_crops(engine, pipe, main_run, twin, wher
 
 # ---------------------------------------------------------------- 3. independence: the point of the gate
 def test_a_persons_valid_rows_do_not_depend_on_the_others(engine, pipe, main_run):
-    other = run_live(engine, pipe, 'other', CAM1_OTHER)
+    other = run_live(engine, pipe, 'other', CAMS_OTHER)
     q, s = LC.SLOT_BC
     assert other['track_id'][14:, q, s].tolist() == [2] * 14 and main_run['track_id'][14:, q, s].tolist() == [3] * 14     # C, under another id
     both = (main_run['valid'][:, q, s] == 1) & (other['valid'][:, q, s] == 1)
@@ -211,7 +192,7 @@ def test_a_device_img_hw_gives_the_pools_outputs(engine, pipe, twin):
 
 # ---------------------------------------------------------------- 6. drawing
 def test_drawn_frames_equal_the_host_drawing(engine, pipe):
-    run = run_live(engine, pipe, 'main', CAM1, smooth=None, draw=True)
+    run = run_live(engine, pipe, 'main', smooth=None, draw=True)
     host = LC.run_host(*LC.scene())
     same(run['valid'], host['valid'], 'valid')
     same(run['image_of'], host['image_of'], 'image_of')

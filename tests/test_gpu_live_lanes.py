@@ -10,75 +10,26 @@ import numpy as np
 import pytest
 import torch
 
-from mcgaze_amd import live, synth
-from mcgaze_amd import pipeline as P
+from mcgaze_amd import live
 from mcgaze_amd.arrows import draw_arrows_host
 from mcgaze_amd.stream import GazeStream
 from tests import live_cases as LC
 from tests import live_lanes_cases as LL
-from tests.test_gpu_nv12 import chain
+from tests.live_gpu_common import ALPHA, CAMS, DEV, GAZE, dev, make_engine, make_pipe, run_live, same
 
 pytestmark = pytest.mark.gpu
 
-DEV = 'cuda:0'
-ALPHA = 0.6
-H, W = LC.FRAME_HW
-GAZE = ('det', 'fused', 'others')
 TICK_TABLES = ('lane_state', 'crop_boxes', 'image_of', 'lane_of', 'overflow', 'matched', 'ring_id', 'ring_box', 'ring_col', 'flags')
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
-
-
-def make_frames(seed):
-    """[TICKS, 96, 128, 3] uint8: one frame per tick of one camera."""
-    return np.random.default_rng(seed).integers(0, 256, (LC.TICKS, H, W, 3), dtype=np.uint8)
-
-
-CAMS = (make_frames(1), make_frames(2))
 
 
 @pytest.fixture(scope='module')
 def engine():
-    from mcgaze_amd.engine import HipEngine
-    return HipEngine(synth.make_state_dict(0), precision='f16x3')
+    return make_engine()
 
 
 @pytest.fixture(scope='module')
 def pipe():
-    return P.DevicePipeline(chain(64))
-
-
-def run_live(engine, pipe, variant, lanes, smooth=ALPHA, draw=False):
-    """A scene through LiveGaze(lanes=lanes) (None: the fixed schedule) -> dict of host arrays: the results concatenated over all returned
-    frames, ``calls`` ((first, k) of every call), with lanes ``ticks`` (what each tick left in the object's tables and returned) and, with
-    draw, ``frames`` [(frame index, [Q annotated frames])]."""
-    boxes, counts = LL.scene(variant)
-    lg = live.LiveGaze(engine, pipe, cameras=LC.Q, clip_len=LC.CLIP, stride=LC.STRIDE, smooth=smooth, draw=draw, lanes=lanes, **LC.OPTIONS)
-    bufs = [torch.empty(H, W, 3, dtype=torch.uint8, device=DEV) for _ in range(LC.Q)]      # a camera's buffer, rewritten every tick
-    ticks, results = [], []
-    for t in range(LC.TICKS):
-        for q in range(LC.Q):
-            bufs[q].copy_(dev(CAMS[q][t]))
-        r = lg.tick(bufs, dev(boxes[t]), dev(counts[t]))
-        if lanes is not None:
-            row = t % lg.R
-            ticks.append(dict(lane_state=lg.lane_state.clone(), crop_boxes=lg.crop_boxes.clone(), image_of=lg.image_of.clone(),
-                              ring_id=lg.ring_id[row].clone(), ring_box=lg.ring_box[row].clone(), ring_col=lg.ring_col[row].clone(),
-                              lane_of=r['lane_of'], overflow=r['overflow'], matched=r['matched'], flags=r['flags']))
-        results.append(r)
-    results.append(lg.finish())
-    torch.cuda.synchronize()
-    out = dict(calls=[(r['first'], int(r['valid'].shape[0])) for r in results],
-               ticks=[{k: v.cpu().numpy() for k, v in rec.items()} for rec in ticks])
-    names = ('track_id', 'valid', 'head_box', 'image_of') + GAZE + (('smooth_valid', 'fused_smooth', 'others_smooth') if smooth else ()) + \
-        (('camera', 'slot') if lanes is not None else ())
-    for name in names:
-        out[name] = torch.cat([r[name] for r in results]).cpu().numpy()
-    if draw:
-        out['frames'] = [(r['first'] + i, [f.cpu().numpy() for f in fr]) for r in results for i, fr in enumerate(r['frames'])]
-    return out
+    return make_pipe()
 
 
 @pytest.fixture(scope='module')
@@ -88,7 +39,7 @@ def runs(engine, pipe):
 
     def get(variant, lanes):
         if (variant, lanes) not in made:
-            made[variant, lanes] = run_live(engine, pipe, variant, lanes)
+            made[variant, lanes] = run_live(engine, pipe, variant, lanes=lanes)
         return made[variant, lanes]
     return get
 
@@ -99,18 +50,9 @@ def twins():
 
     def get(variant, lanes, smooth=True):
         if (variant, lanes, smooth) not in made:
-            made[variant, lanes, smooth] = LL.run_host_lanes(*LL.scene(variant), lanes, smooth=smooth)
+            made[variant, lanes, smooth] = LC.run_host(*LL.scene(variant), smooth=smooth, lanes=lanes)
         return made[variant, lanes, smooth]
     return get
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.int32)
-
-
-def same(a, b, what):
-    assert a.dtype == b.dtype and a.shape == b.shape, (what, a.dtype, a.shape, b.dtype, b.shape)
-    assert np.array_equal(bits(a), bits(b)), what
 
 
 # ---------------------------------------------------------------- 1. the kernels against their twins
@@ -253,7 +195,7 @@ def test_a_tick_never_waits_for_the_device(engine, pipe, monkeypatch):
 
 # ---------------------------------------------------------------- 6. drawing
 def test_drawn_frames_equal_the_host_drawing(engine, pipe, twins):
-    run = run_live(engine, pipe, 'main', 6, smooth=None, draw=True)
+    run = run_live(engine, pipe, 'main', lanes=6, smooth=None, draw=True)
     host = twins('main', 6, smooth=False)
     same(run['valid'], host['valid'], 'valid')
     same(run['image_of'], host['image_of'], 'image_of')

@@ -117,6 +117,27 @@ def test_smoothing_falls_back_next_to_an_invalid_neighbour(smoothed):
     assert first_out == 1 and table[1].tolist() == [20, 16, 27, 19, 21] and table[-1].tolist() == [27, 21, 28, 26, -1]
 
 
+def test_a_slot_ring_is_a_lane_ring_whose_column_is_its_own_index(smoothed):
+    """What the one gate rests on.  At every call that returned frames, the slot ring handed to live_gate_lanes_host as P = Q * S lanes,
+    lane p naming column p where a person is and -1 elsewhere, gives the outputs of live_gate_host bit for bit, and camera / slot are
+    p // S and p % S on the valid rows, -1 elsewhere."""
+    cols = LC.Q * LC.S
+    bits = lambda a: np.ascontiguousarray(a).view(np.int32)
+    calls = [c for c in smoothed['emitted'] if c[2]]
+    assert len(calls) == len(smoothed['tables']) == 21 and sum(k for _, _, k in calls) == 28
+    for (tick, first, k), (table, first_out) in zip(calls, smoothed['tables']):
+        ring_id, ring_box, ring_col = LC.as_lane_ring(*LC.ring_at(smoothed, tick))
+        gaze = [g.reshape((k, cols) + g.shape[3:]) for g in LC.fake_gaze(k, first)]
+        got = live.live_gate_lanes_host(ring_id, ring_box, ring_col, LC.Q, LC.S, tick, table, first_out, k, *gaze)
+        for name in ('track_id', 'valid', 'image_of', 'head_box', 'smooth_valid', 'fused_smooth', 'others_smooth'):
+            want = smoothed[name][first:first + k]
+            want = want.reshape((k, cols) + want.shape[3:])
+            assert got[name].dtype == want.dtype and got[name].shape == want.shape and np.array_equal(bits(got[name]), bits(want)), (name, first)
+        valid, p = got['valid'] == 1, np.arange(cols)[None]
+        assert np.array_equal(got['camera'], np.where(valid, p // LC.S, -1)) and np.array_equal(got['slot'], np.where(valid, p % LC.S, -1)), first
+        assert got['camera'].dtype == got['slot'].dtype == np.int32
+
+
 def test_a_span_deeper_than_the_ring_raises():
     R = live.ring_depth(CLIP)
     ok = np.array([[20, 20 - R + 8, 28, -1, -1]], np.int32)

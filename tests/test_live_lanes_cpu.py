@@ -18,22 +18,22 @@ CLIP, STRIDE = LL.CLIP, LL.STRIDE
 
 @pytest.fixture(scope='module')
 def main6():
-    return LL.run_host_lanes(*LL.scene('main'), 6)
+    return LC.run_host(*LL.scene('main'), lanes=6)
 
 
 @pytest.fixture(scope='module')
 def main4():
-    return LL.run_host_lanes(*LL.scene('main'), 4)
+    return LC.run_host(*LL.scene('main'), lanes=4)
 
 
 @pytest.fixture(scope='module')
 def queue():
-    return LL.run_host_lanes(*LL.scene('queue'), LL.QUEUE_LANES)
+    return LC.run_host(*LL.scene('queue'), lanes=LL.QUEUE_LANES)
 
 
 @pytest.fixture(scope='module')
 def queue_smoothed():
-    return LL.run_host_lanes(*LL.scene('queue'), LL.QUEUE_LANES, smooth=True)
+    return LC.run_host(*LL.scene('queue'), smooth=True, lanes=LL.QUEUE_LANES)
 
 
 def lanes_at(run, t):
@@ -167,7 +167,7 @@ def test_smoothing_falls_back_next_to_an_invalid_neighbour(queue_smoothed):
     sv, v = queue_smoothed['smooth_valid'], queue_smoothed['valid']
     # A's frame 7 is valid but its successor 8 is not; C's frame 15 is valid but its predecessor 14 is not
     assert sv[:, 0].tolist() == [1] * 7 + [0] * 9 + [1] * 12 and sv[:, 1].tolist() == [1] * 28
-    fused, others, fused_s, others_s = LL.fake_gaze(28, 0, LL.QUEUE_LANES)
+    fused, others, fused_s, others_s = LC.fake_gaze(28, 0, LL.QUEUE_LANES)
     raw = (v == 1) & (sv == 0)
     assert np.argwhere(raw).tolist() == [[7, 0], [15, 0]]
     assert np.array_equal(queue_smoothed['fused_smooth'][raw], fused[raw]) and np.array_equal(queue_smoothed['others_smooth'][raw], others[raw])
