@@ -12,13 +12,14 @@ __device__ __forceinline__ int roi_level(float x1, float y1, float x2, float y2,
 }
 
 // Sample i (0 .. 2 P - 1: bin i / 2, sample i % 2) along one axis of a box [a1, a2] (image coordinates) on a level of L pixels and
-// scale ss: the two taps lo / hi, the weight l of hi, and whether the sample reads anything (y < -1 or y > L adds 0).
+// scale ss: the two taps lo / hi, the weight l of hi, and whether the sample reads anything (y < -1 or y > L adds 0, and so does a
+// NaN y: the comparisons below are ordered, so NaN is outside -- it has to be caught BEFORE the clamp, which turns NaN into 0).
 template <int P, int S>
 __device__ __forceinline__ void roi_axis_sample(float a1, float a2, float ss, int L, int i, int& lo_out, int& hi_out, float& l_out, int& valid_out) {
   const float start = a1 * ss - 0.5f, end = a2 * ss - 0.5f;
   const float bin = (end - start) / (float)P;
   float c = start + (float)(i / S) * bin + ((float)(i % S) + 0.5f) * bin / (float)S;
-  const int valid = !(c < -1.0f || c > (float)L);
+  const int valid = c >= -1.0f && c <= (float)L;
   c = fmaxf(c, 0.f);
   int lo = (int)c, hi;
   if (lo >= L - 1) {
@@ -27,5 +28,5 @@ __device__ __forceinline__ void roi_axis_sample(float a1, float a2, float ss, in
   } else {
     hi = lo + 1;
   }
-  lo_out = lo; hi_out = hi; l_out = c - (float)lo; valid_out = valid && (c == c);
+  lo_out = lo; hi_out = hi; l_out = c - (float)lo; valid_out = valid;
 }

@@ -165,13 +165,15 @@ def check_exactness_wino(x, w, b, g, what):
 
 
 # ------------------------------------------------------------------------------------------------ expected values, ties, comparison
-def expected(ref_int, dtype):
+def expected(ref_int, dtype, frac_bits=0):
     """The value a kernel must store for the int64 reference: the integer itself (f32, f16x3), or ONE round-to-nearest-even of it
-    (bf16, fp16) -- applied after bias, residual and ReLU."""
-    assert int(ref_int.abs().max()) < LIMIT
-    want = ref_int.float()
+    (bf16, fp16) -- applied after bias, residual and ReLU.  frac_bits: the reference is the dyadic fraction ref_int / 2^frac_bits
+    (tests/roi_exact_cases.py); a power-of-two scale moves exponents only, and a non-zero value of at least 2^-frac_bits is a normal
+    number of every storage type as long as frac_bits <= 14."""
+    assert int(ref_int.abs().max()) < LIMIT and 0 <= frac_bits <= 14
+    want = ref_int.float() * 2.0 ** -frac_bits
     if dtype in SIG_BITS:
-        assert dtype != torch.float16 or int(ref_int.abs().max()) <= 65504, 'fp16 overflow'
+        assert dtype != torch.float16 or int(ref_int.abs().max()) <= 65504 << frac_bits, 'fp16 overflow'
         want = want.to(dtype)
     return want
 
@@ -195,10 +197,10 @@ def count_inexact(ref_int, dtype=torch.float16):
     return int((a % _ulp(a, SIG_BITS[dtype]) != 0).sum())
 
 
-def truncated(ref_int, dtype):
+def truncated(ref_int, dtype, frac_bits=0):
     """MUTANT of ``expected``: round toward zero instead of to nearest even."""
     a = ref_int.abs()
-    return (ref_int.sign() * (a - a % _ulp(a, SIG_BITS[dtype]))).float().to(dtype)
+    return ((ref_int.sign() * (a - a % _ulp(a, SIG_BITS[dtype]))).float() * 2.0 ** -frac_bits).to(dtype)
 
 
 def assert_exact(got, want, what):

@@ -587,6 +587,8 @@ def test_fused_stem_is_bit_identical_to_the_three_kernel_path(eng, sd, shape):
 
 @pytest.mark.parametrize('dtype', DTYPES)
 def test_roi_align_all_levels(eng, dtype):
+    """Random features and generic boxes on all four levels, within 1e-5 (f32) / 1e-2 (16-bit) of the tensor's scale; the test of the
+    16-bit rounding (and of every edge, bit for bit) is tests/test_gpu_roi_exact.py."""
     g = torch.Generator().manual_seed(5)
     N = 3
     feats = [torch.randn(N, 256, 64 >> i, 96 >> i, generator=g) for i in range(4)]  # a 256x384 frame
