@@ -355,6 +355,10 @@ void mcg_engine_destroy(mcg_engine* e);
  *                     RoIAlign of some stage reads (mcg_backbone_fpn_forward_deferred / mcg_decoder_forward_deferred, mcg_clip_forward); bit-identical
  *                     to the dense conv.  0 = every level dense in the trunk, launch for launch.  Off for other precisions, under range_audit
  *                     (which audits whole P tensors) and for levels beyond 512 x 512 pixels.  Not to be changed between the two calls of a pair
+ *   fpn_lateral_deferred 0/1 (default 1), honoured only where fpn_deferred holds: the P2 lateral conv (+ nearest-upsampled P3 term) is left to the
+ *                     decoder as well and computed only for the 8 x 8 blocks the deferred output conv reads -- the listed blocks and their
+ *                     neighbours inside the frame.  The trunk then writes C2 and the P3 inner map into the slot.  Bit-identical; 0 = the dense
+ *                     lateral in the trunk, launch for launch.  Not to be changed between the two calls of a pair
  *   range_audit       0/1 DEBUG (MCG_F32 / MCG_F16X3; default 0): after every activation tensor the trunk writes, a counting kernel tallies the
  *                     values beyond the fp16 range (|x| > 65504: an f16x3 operand half would saturate there) and the non-finite ones;
  *                     read and reset with mcg_engine_range_audit.  Turning it on allocates the counters (the library's only allocation,
@@ -407,9 +411,20 @@ int mcg_decoder_forward_ragged(mcg_engine* e, mcg_stream s, const void* const py
  * per stage.  The trunk then writes P3..P5 and the inner map; before each stage's RoIAlign the decoder flags the P2 blocks that stage's
  * boxes read (the RoIAlign sample arithmetic itself, roi_sample.hpp) and computes those not yet computed (no host sync: graph-capturable).
  * P2 pixels no box reads are never written.  Outputs are bit for bit those of mcg_backbone_fpn_forward + mcg_decoder_forward.
- * mcg_deferred_pyramid_levels: where the slot's P2..P5 lie; *deferred (optional) = whether the engine defers P2 for this shape. */
+ * With the P2 lateral deferred too (option fpn_lateral_deferred) the slot also holds C2, the P3 inner map, a flag per 8 x 8 INNER block and
+ * one inner-block list per stage: the trunk writes C2 and the P3 inner map there, and the decoder computes, before a stage's output blocks,
+ * the inner blocks they read (themselves and their in-frame neighbours) that no earlier stage computed.  Inner pixels nobody reads are
+ * never written.
+ * mcg_deferred_pyramid_levels: where the slot's P2..P5 lie; *deferred (optional) = whether the engine defers P2 for this shape.
+ * mcg_deferred_pyramid_state (test / measurement aid): where the slot's P2 inner map [N][H/4][W/4][256] lies (NULL: P2 not deferred) and,
+ * where *lateral_deferred is 1, the inner-block flags [*blocks], counts [stages] and lists [stages][*blocks] (else NULL); any output
+ * pointer may be NULL.  mcg_inner_block_neighbours: the host twin of the inner-block rule -- the blocks (id itself included, at most nine)
+ * whose inner pixels output block id of a [.][H][W] map reads; returns how many were written to out. */
 size_t mcg_deferred_pyramid_bytes(const mcg_engine* e, int num_frames, int H, int W);
 int mcg_deferred_pyramid_levels(const mcg_engine* e, void* slot, int num_frames, int H, int W, void* levels[4], int* deferred);
+int mcg_deferred_pyramid_state(const mcg_engine* e, void* slot, int num_frames, int H, int W, void** inner, int** flags, int** counts,
+                               int** lists, int* blocks, int* lateral_deferred);
+int mcg_inner_block_neighbours(int id, int H, int W, int out[9]);
 int mcg_backbone_fpn_forward_deferred(mcg_engine* e, mcg_stream s, const float* img, int num_frames, int H, int W, int chunk_frames,
                                       void* slot, size_t slot_bytes, void* ws, size_t ws_bytes);
 int mcg_decoder_forward_deferred(mcg_engine* e, mcg_stream s, void* slot, size_t slot_bytes, int num_frames, int clip_length, int H, int W,

@@ -32,6 +32,7 @@ bool roi_mark_supported(int H, int W);
 int launch_defer_clear(hipStream_t s, int* p, int n);
 int launch_roi_mark(hipStream_t s, const float* boxes, int num_boxes, int boxes_per_frame, int level, int H, int W, int stride, int* state,
                     int* list, int* count);
+int launch_inner_mark(hipStream_t s, const int* out_list, const int* out_count, int H, int W, int nblk, int* state, int* list, int* count);
 
 struct mcg_engine {
   mcg_dtype dt;
@@ -50,6 +51,8 @@ struct mcg_engine {
                                // fallback for wino_x3w_kernel, whose hand-issued register loads depend on a spill-free build (csrc/check_resources.py)
   int fpn_deferred = 1;        // f16x3: the FPN P2 output conv is deferred to the decoder and computed per 8 x 8 block where RoIAlign reads
                                // (mcg_*_deferred, mcg_clip_forward); 0 = every level dense in the trunk.  Same bits either way
+  int fpn_lateral_deferred = 1; // with fpn_deferred: the P2 lateral (+ top-down add) is left to the decoder too and computed for the listed blocks
+                               // and their neighbours only (pw_single_x3_blocks_kernel); 0 = the dense lateral in the trunk.  Same bits either way
   // range audit (debug option, f32-storage engines): per activation tensor the trunk writes, how many values lie beyond the fp16 range
   // (|x| > 65504: an f16x3 operand half would saturate) and how many are not finite.  Counters live on the device; read by mcg_engine_range_audit.
   static constexpr int kAuditCap = 256;
@@ -218,6 +221,7 @@ extern "C" int mcg_engine_set_option(mcg_engine* e, const char* name, int value)
   else if (!strcmp(name, "bottleneck_blocked")) e->bneck_blocked = value != 0;
   else if (!strcmp(name, "winograd")) { MCG_CHECK_ARG(value >= 0 && value <= 2, "winograd must be 0, 1 or 2"); e->winograd = value; }
   else if (!strcmp(name, "fpn_deferred")) e->fpn_deferred = value != 0;
+  else if (!strcmp(name, "fpn_lateral_deferred")) e->fpn_lateral_deferred = value != 0;
   else if (!strcmp(name, "wino_tile")) { MCG_CHECK_ARG(value >= -1 && value <= 3, "wino_tile must be -1 (by grid size) .. 3"); e->wino_tile = value; }
   else if (!strcmp(name, "range_audit")) {
     MCG_CHECK_ARG(!mcg_is16(e->dt) || !value, "range_audit: f32-storage engines only (MCG_F32, MCG_F16X3)");
@@ -537,13 +541,22 @@ static int conv3_step(const mcg_engine* e, hipStream_t s, const TrunkWs& t, Audi
 }
 
 // Backbone + FPN over frames [f0, f0+n): writes pyramid level i at frame offset f0.
-// inner0 != NULL (deferred P2): the P2 top-down inner map goes to inner0 (frame offset f0) and the P2 output conv is left to the decoder
+// tk.inner != NULL (deferred P2): the P2 top-down inner map goes to tk.inner (frame offset f0) and the P2 output conv is left to the decoder.
+// tk.c2 != NULL (deferred P2 lateral): C2 and the P3 inner map are written straight to tk.c2 / tk.l1 (frame offset f0) -- in place of the
+// workspace, no copy -- and the P2 lateral is left to the decoder as well; every reader follows t.c[0] / t.l[1]
+struct TrunkKeep { char *inner, *c2, *l1; };
 static int trunk_chunk(mcg_engine* e, hipStream_t s, const float* img, int f0, int n, int H, int W, void* const pyr[4], char* wsbase,
-                       bool backbone_only = false, char* inner0 = nullptr) {
+                       bool backbone_only = false, const TrunkKeep tk = TrunkKeep{nullptr, nullptr, nullptr}) {
   const mcg_dtype dt = e->dt;
   const size_t es = esize(dt);
   TrunkWs t = trunk_layout(dt, n, H, W, wsbase);
+  char* const inner0 = tk.inner;
   if (inner0) t.l[0] = inner0 + (size_t)f0 * (H / 4) * (W / 4) * 256 * es;
+  const bool lateral_deferred = inner0 && tk.c2 && tk.l1;
+  if (lateral_deferred) {
+    t.c[0] = tk.c2 + (size_t)f0 * (H / 4) * (W / 4) * 256 * es;
+    t.l[1] = tk.l1 + (size_t)f0 * (H / 8) * (W / 8) * 256 * es;
+  }
   MCG_TRY(stem_forward_ctx(s, dt, img + (size_t)f0 * 3 * H * W, e->stem.w, e->stem.bias, t.x0, n, H, W, t.stem_ws, t.stem_bytes, e->ctx));
   AuditCursor au{e, s, 0, e->audit_dev != nullptr && e->audit_names.empty()};
   audit_tensor(au, t.x0, (long long)n * (H / 4) * (W / 4) * 64, "stem");
@@ -576,7 +589,7 @@ static int trunk_chunk(mcg_engine* e, hipStream_t s, const float* img, int f0, i
   // FPN (fpn.py:157-180): laterals top-down with the nearest-upsample add fused into the epilogue
   int hs[4], wsz[4];
   for (int i = 0; i < 4; ++i) { hs[i] = (H / 4) >> i; wsz[i] = (W / 4) >> i; }
-  for (int i = 3; i >= 0; --i) {
+  for (int i = 3; i >= (lateral_deferred ? 1 : 0); --i) {
     const void* res = i == 3 ? nullptr : t.l[i + 1];
     MCG_TRY(conv_call(e, s, dt, e->lateral[i], t.c[i], n, hs[i], wsz[i], t.l[i], 0, res, res ? MCG_RES_UPSAMPLE_ADD : MCG_RES_NONE,
                       i == 3 ? 0 : hs[i + 1], i == 3 ? 0 : wsz[i + 1]));
@@ -637,12 +650,19 @@ static size_t pyramid_bytes(mcg_dtype dt, int N, int H, int W, int level) {
 // Deferred pyramid slot (mcg_*_deferred): P2..P5 outputs, then -- when the engine defers P2 -- the P2 inner map the trunk leaves for the
 // decoder, one int per 8 x 8 output block of P2 (0 = not yet listed) followed by one list count per decoder stage, and one block list
 // per stage.  Without deferral the slot is the four pyramid levels and the pair runs the dense launches.
+// When the P2 lateral is deferred as well (option fpn_lateral_deferred), the slot also carries what that lateral reads -- C2 and the P3
+// inner map, written there by the trunk: the next batch's trunk overwrites its workspace while this batch's decoder runs -- and a second
+// set of flags, counts and lists for the INNER blocks (the listed output blocks and their neighbours).  The inner flags and counts follow
+// the output ones, so one clear covers both.
 struct DeferSlot {
   void* p[4];
   char* inner;
   int *state, *count, *list;
   int nblk;
   bool deferred;
+  bool lateral;                      // the P2 lateral is deferred too
+  char *c2, *l1;                     // C2 [N, H/4, W/4, 256], P3 inner map [N, H/8, W/8, 256]
+  int *istate, *icount, *ilist;      // inner blocks: flag per block, count per stage, list per stage
   size_t total;
 };
 static bool fpn_deferred_on(const mcg_engine* e, int N, int H, int W) {
@@ -650,6 +670,14 @@ static bool fpn_deferred_on(const mcg_engine* e, int N, int H, int W) {
   const int h = H / 4, w = W / 4;
   return e->fpn_deferred && e->dt == MCG_F16X3 && !e->audit_dev && e->num_stages > 0 && wino_kind(e, e->dt, cw, N, h, w, MCG_RES_NONE) == 2 &&
          wino_x3_blocks_applicable(N, h, w, cw.cin, cw.cout) && roi_mark_supported(h, w);
+}
+// The P2 lateral goes to the decoder too: only where P2 is deferred, for a lateral the list kernel serves (the streaming kernel's weights)
+static bool fpn_lateral_deferred_on(const mcg_engine* e, int N, int H, int W) {
+  const mcg_conv_weights& cw = e->lateral[0];
+  const int h = H / 4, w = W / 4;
+  return e->fpn_lateral_deferred && fpn_deferred_on(e, N, H, W) && e->pw_single && e->ctx.tile < 0 && cw.wf && cw.bias && cw.k == 1 && cw.stride == 1 &&
+         cw.pad == 0 && h % 2 == 0 && w % 2 == 0 &&
+         pw_single_x3_blocks_applicable(cw.cin, cw.cout, h, w, (long long)N * h * w, (long long)N * (h / 2) * (w / 2));
 }
 static DeferSlot defer_layout(const mcg_engine* e, int N, int H, int W, char* base) {
   DeferSlot d;
@@ -661,9 +689,18 @@ static DeferSlot defer_layout(const mcg_engine* e, int N, int H, int W, char* ba
   if (d.deferred) {
     d.inner = take((size_t)N * (H / 4) * (W / 4) * 256 * esize(e->dt));
     d.nblk = N * wino_x3_blocks_per_frame(H / 4, W / 4);
-    d.state = (int*)take(sizeof(int) * ((size_t)d.nblk + e->num_stages));
+    d.lateral = fpn_lateral_deferred_on(e, N, H, W);
+    const size_t per = (size_t)d.nblk + e->num_stages;
+    d.state = (int*)take(sizeof(int) * per * (d.lateral ? 2 : 1));
     d.count = d.state ? d.state + d.nblk : nullptr;
     d.list = (int*)take(sizeof(int) * (size_t)d.nblk * e->num_stages);
+    if (d.lateral) {
+      d.istate = d.state ? d.state + per : nullptr;
+      d.icount = d.istate ? d.istate + d.nblk : nullptr;
+      d.ilist = (int*)take(sizeof(int) * (size_t)d.nblk * e->num_stages);
+      d.c2 = take((size_t)N * (H / 4) * (W / 4) * 256 * esize(e->dt));
+      d.l1 = take((size_t)N * (H / 8) * (W / 8) * 256 * esize(e->dt));
+    }
   }
   d.total = off;
   return d;
@@ -703,7 +740,7 @@ static int check_shape(int N, int H, int W) {
 }
 
 static int trunk_forward(mcg_engine* e, mcg_stream s_, const float* img, int N, int H, int W, int chunk,
-                         void* const pyramid[4], void* ws, size_t ws_bytes, bool backbone_only, char* inner0 = nullptr) {
+                         void* const pyramid[4], void* ws, size_t ws_bytes, bool backbone_only, const TrunkKeep tk = TrunkKeep{nullptr, nullptr, nullptr}) {
   MCG_CHECK_ARG(e && img && (pyramid || backbone_only) && ws, "mcg_backbone_fpn_forward: null pointer");
   MCG_TRY(check_shape(N, H, W));
   std::lock_guard<std::mutex> lock(e->mu);
@@ -728,7 +765,7 @@ static int trunk_forward(mcg_engine* e, mcg_stream s_, const float* img, int N, 
   const size_t part_ws = k > 1 ? al256(trunk_layout(e->dt, per, H, W, nullptr).total) : 0;
   int rc = MCG_OK;
   for (int f0 = 0, i = 0; f0 < N && rc == MCG_OK; f0 += per, i = (i + 1) % k)
-    rc = trunk_chunk(e, si[i], img, f0, (N - f0) < per ? (N - f0) : per, H, W, pyramid, (char*)ws + (size_t)i * part_ws, backbone_only, inner0);
+    rc = trunk_chunk(e, si[i], img, f0, (N - f0) < per ? (N - f0) : per, H, W, pyramid, (char*)ws + (size_t)i * part_ws, backbone_only, tk);
   for (int i = 1; i < k; ++i) {  // joined even after a failed launch, so the caller's stream never runs ahead of a side stream
     if (hipEventRecord(e->ev_join[i - 1], si[i]) != hipSuccess || hipStreamWaitEvent(s, e->ev_join[i - 1], 0) != hipSuccess) {
       mcg_set_error("mcg_backbone_fpn_forward: join failed");
@@ -791,11 +828,28 @@ extern "C" int mcg_bench_backbone_levels(const mcg_engine* e, void* ws, int N, i
 }
 
 // Deferred P2 before stage st's RoIAlign: list the 8 x 8 blocks of P2 [N, h, w] that the stage's boxes read and no earlier stage listed
-// (roi_mark_kernel), then compute them from the inner map (wino_x3w_blocks_kernel: same bits as the dense conv).  Booked once, at stage 0
+// (roi_mark_kernel), then compute them from the inner map (wino_x3w_blocks_kernel: same bits as the dense conv).  Booked once, at stage 0.
+// d.lateral: the inner map is computed here as well, between the two -- the listed blocks and their in-frame neighbours that no earlier
+// stage computed (inner_mark_kernel), by the streaming lateral's per-pixel code over that list (pw_single_x3_blocks_kernel)
 static int defer_stage_forward(const mcg_engine* e, hipStream_t s, const DeferSlot& d, int st, const float* boxes, int N, int h, int w) {
   const mcg_conv_weights& cw = e->fpn_out[0];
   int* list = d.list + (size_t)st * d.nblk;
   MCG_TRY(launch_roi_mark(s, boxes, N * 3, 3, 0, h, w, 4, d.state, list, d.count + st));
+  if (d.lateral) {
+    const mcg_conv_weights& lw = e->lateral[0];
+    int* ilist = d.ilist + (size_t)st * d.nblk;
+    MCG_TRY(launch_inner_mark(s, list, d.count + st, h, w, d.nblk, d.istate, ilist, d.icount + st));
+    const long long M = (long long)N * h * w, res_m = (long long)N * (h / 2) * (w / 2);
+    PwSingleParams pp;
+    memset(&pp, 0, sizeof(pp));
+    pp.a = d.c2; pp.res = d.l1; pp.wf = lw.wf; pp.bias = lw.bias; pp.y = d.inner;
+    pp.M = (int)M; pp.relu = 0; pp.Ho = h; pp.Wo = w; pp.wscale = lw.wscale;
+    pp.Hr = h / 2; pp.Wr = w / 2; pp.rscale_h = (float)pp.Hr / (float)h; pp.rscale_w = (float)pp.Wr / (float)w;
+    const bool book = st == 0;   // the dense lateral's FLOPs and bytes, once
+    ProfRec* lrec = prof_begin(e->ctx, s, 71, pp.M, lw.cout, lw.cin, book ? 2.0 * M * lw.cin * lw.cout : 0.0,
+                               book ? 4.0 * ((double)M * (lw.cin + lw.cout) + (double)res_m * lw.cout + (double)lw.cin * lw.cout) : 0.0);
+    MCG_TRY(launch_done(lrec, s, launch_pw_single_x3_blocks(s, pp, ilist, d.icount + st, d.nblk), "pw_single_x3 block"));
+  }
   ProfRec* rec = prof_begin_wino(e->ctx, s, cw, (long long)N * h * w, st == 0);
   return launch_done(rec, s, launch_wino_x3_blocks(s, wino_params(cw, 2, d.inner, N, h, w, d.p[0], 0), list, d.count + st, d.nblk), "wino_x3 block");
 }
@@ -820,7 +874,7 @@ static int decoder_forward(mcg_engine* e, hipStream_t s, const void* const pyram
   char* obj_in = c.obj_a; char* obj_out = c.obj_b;
   float* b_in = c.boxes_a; float* b_out = c.boxes_b;
   const bool defer = d && d->deferred;
-  if (defer) MCG_TRY(launch_defer_clear(s, d->state, d->nblk + e->num_stages));
+  if (defer) MCG_TRY(launch_defer_clear(s, d->state, (d->nblk + e->num_stages) * (d->lateral ? 2 : 1)));
   for (int st = 0; st < e->num_stages; ++st) {
     if (defer) MCG_TRY(defer_stage_forward(e, s, *d, st, b_in, N, fh[0], fw[0]));
     MCG_TRY(launch_roi_align(s, e->dt, pyramid, fh, fw, strides, 256, b_in, N * 3, 3, frame_of, pyramid_frames, c.roi, nullptr));
@@ -875,7 +929,25 @@ extern "C" int mcg_backbone_fpn_forward_deferred(mcg_engine* e, mcg_stream s, co
   MCG_TRY(check_shape(N, H, W));
   const DeferSlot d = defer_layout(e, N, H, W, (char*)slot);
   if (slot_bytes < d.total) { mcg_set_error("mcg_backbone_fpn_forward_deferred: slot too small (%zu < %zu)", slot_bytes, d.total); return MCG_ERR_WORKSPACE; }
-  return trunk_forward(e, s, img, N, H, W, chunk, d.p, ws, ws_bytes, false, d.deferred ? d.inner : nullptr);
+  return trunk_forward(e, s, img, N, H, W, chunk, d.p, ws, ws_bytes, false,
+                       TrunkKeep{d.deferred ? d.inner : nullptr, d.lateral ? d.c2 : nullptr, d.lateral ? d.l1 : nullptr});
+}
+
+// Test / measurement aid: where a deferred slot keeps the P2 inner map and the inner-block bookkeeping of the deferred lateral
+// (flags [blocks], counts [stages], lists [stages][blocks]); *lateral_deferred = whether the engine defers the P2 lateral for this shape
+// (else the bookkeeping pointers are NULL; inner is NULL where P2 is not deferred at all)
+extern "C" int mcg_deferred_pyramid_state(const mcg_engine* e, void* slot, int N, int H, int W, void** inner, int** flags, int** counts, int** lists,
+                                          int* blocks, int* lateral_deferred) {
+  MCG_CHECK_ARG(e && slot, "mcg_deferred_pyramid_state: null pointer");
+  MCG_TRY(check_shape(N, H, W));
+  const DeferSlot d = defer_layout(e, N, H, W, (char*)slot);
+  if (inner) *inner = d.inner;
+  if (flags) *flags = d.istate;
+  if (counts) *counts = d.icount;
+  if (lists) *lists = d.ilist;
+  if (blocks) *blocks = d.nblk;
+  if (lateral_deferred) *lateral_deferred = d.lateral ? 1 : 0;
+  return MCG_OK;
 }
 
 static int decoder_forward_deferred(mcg_engine* e, mcg_stream s, void* slot, size_t slot_bytes, int N, const ClipTable& ct, int H, int W,

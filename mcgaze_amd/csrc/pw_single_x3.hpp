@@ -13,8 +13,20 @@
 #pragma once
 #include "pw_single.hpp"
 
-template <int KS, int RES, int NSPLIT>
-__global__ __launch_bounds__(256, 2) void pw_single_x3_kernel(const PwSingleParams p) {
+// A device list of 8 x 8-pixel blocks of the output map [frames][Ho][Wo] (Ho, Wo multiples of 8): block id = (frame * (Ho / 8) + block row)
+// * (Wo / 8) + block column, the numbering of wino_x3w_blocks_kernel.  LISTED form of the kernel below
+struct PwBlockList {
+  const int* list;
+  const int* count;         // entries of list (device)
+  int bxn, bpf, nblk;       // blocks per row, per frame, in the map
+};
+
+// LISTED: the tiles are not 32 consecutive pixels of [0, M) but the two halves (4 rows x 8 pixels) of the *bl.count listed blocks: tile t =
+// rows 4 (t & 1) .. + 3 of block bl.list[t >> 1], tile row r = its pixel (r >> 3, r & 7).  Everything a pixel's value depends on -- its A
+// row, its residual row, the K order, the three-term order, the epilogue -- is the dense form's: which tile or workgroup computes a pixel
+// does not enter its bits.  Pixels of unlisted blocks are neither read nor written.
+template <int KS, int RES, int NSPLIT, bool LISTED>
+__device__ __forceinline__ void pw_single_x3_body(const PwSingleParams& p, const PwBlockList& bl) {
   constexpr int PX = 32, K = 16 * KS, N = 128, NF = N * NSPLIT, AROWB = 4 * K, YROWB = 4 * N, GROWB = 4 * NF, ACH = AROWB / 16, YCH = YROWB / 16;
   constexpr int ABYTES = PX * AROWB, YBYTES = PX * YROWB;
   constexpr int NYB = RES ? 2 : 1;
@@ -27,6 +39,11 @@ __global__ __launch_bounds__(256, 2) void pw_single_x3_kernel(const PwSinglePara
   const int bid = blockIdx.x, nwalkers = gridDim.x / NSPLIT;
   // ids 8 apart sit on the same XCD; many_slices (dynamic_layer: 256 slices): workgroup id = walker * NSPLIT + slice
   const int nsp = p.many_slices ? bid % NSPLIT : (bid >> 3) % NSPLIT, walker = p.many_slices ? bid / NSPLIT : (bid / (8 * NSPLIT)) * 8 + (bid & 7);
+  int listed_tiles = 0;
+  if constexpr (LISTED) {
+    listed_tiles = 2 * __builtin_amdgcn_readfirstlane(*bl.count);
+    if (walker >= listed_tiles) return;                // uniform per workgroup, before the weights are read
+  }
   const float wsc = p.wscale > 0.f ? p.wscale : 1.f;   // exact power of two: the weights were packed pre-scaled by its inverse
   float4 breg[4];
 #pragma unroll
@@ -47,20 +64,29 @@ __global__ __launch_bounds__(256, 2) void pw_single_x3_kernel(const PwSinglePara
   const uint32_t lds_base = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
   constexpr int A_LPR = ACH < 64 ? ACH : 64, Y_LPR = YCH < 64 ? YCH : 64;
   constexpr int A_RPP = 64 / A_LPR, Y_RPP = 64 / Y_LPR;
-  const int ntiles = (p.M + PX - 1) / PX;
-  auto issue_a = [&](int tile) {
-    const int rows_left = p.M - tile * PX;
-    const uint32_t so = (uint32_t)tile * ABYTES;
+  const int ntiles = LISTED ? listed_tiles : (p.M + PX - 1) / PX;
+  // LISTED: pixel index of a tile's first pixel (uniform; -1 for an id outside the map: nothing read, nothing written), and of its row r
+  auto tile_origin = [&](int tile) {
+    const int blk = __builtin_amdgcn_readfirstlane(bl.list[tile >> 1]);
+    if (blk < 0 || blk >= bl.nblk) return -1;
+    const int f = blk / bl.bpf, rem = blk - f * bl.bpf, by = rem / bl.bxn, bx = rem - by * bl.bxn;
+    return (f * p.Ho + by * 8 + (tile & 1) * 4) * p.Wo + bx * 8;
+  };
+  auto listed_pixel = [&](int org, int r) { return org + (r >> 3) * p.Wo + (r & 7); };
+  auto issue_a = [&](int tile, int org) {
+    const int rows_left = LISTED ? (org >= 0 ? PX : 0) : p.M - tile * PX;
+    const uint32_t so = LISTED ? 0u : (uint32_t)tile * ABYTES;
     static_for<A_PIECES>([&](auto jc) {
       constexpr int J = decltype(jc)::value;
       const int row = (wave * A_PIECES + J) * A_RPP + lane / A_LPR, pos = lane % A_LPR;
-      const uint32_t vo = row < rows_left ? (uint32_t)(row * AROWB + ((pos ^ (row & (ACH >= 32 ? 31 : 15))) << 4)) : MCG_OOB_OFFSET;
+      const uint32_t grow = LISTED ? (uint32_t)listed_pixel(org, row) : (uint32_t)row;   // M * AROWB fits the descriptor window (launcher)
+      const uint32_t vo = row < rows_left ? grow * AROWB + (uint32_t)((pos ^ (row & (ACH >= 32 ? 31 : 15))) << 4) : MCG_OOB_OFFSET;
       lds_dma16<AOFF + J * 1024>(vo, srd_a, so, lds_base + wave * (A_PIECES * 1024));
     });
   };
   const int HoWo = p.Ho * p.Wo;
-  auto issue_res = [&](int tile, int buf) {
-    const int rows_left = p.M - tile * PX;
+  auto issue_res = [&](int tile, int buf, int org) {
+    const int rows_left = LISTED ? (org >= 0 ? PX : 0) : p.M - tile * PX;
     static_for<Y_PIECES>([&](auto jc) {
       constexpr int J = decltype(jc)::value;
       const int row = (wave * Y_PIECES + J) * Y_RPP + lane / Y_LPR, pos = lane % Y_LPR;
@@ -70,7 +96,7 @@ __global__ __launch_bounds__(256, 2) void pw_single_x3_kernel(const PwSinglePara
         so = (uint32_t)tile * (PX * GROWB) + nsp * YROWB;
         if (row < rows_left) vo = (uint32_t)(row * GROWB + (chunk << 4));
       } else if (row < rows_left) {   // nearest-upsample gather (torch: src = min(floor(dst * in / out), in - 1))
-        const int m = tile * PX + row;
+        const int m = LISTED ? listed_pixel(org, row) : tile * PX + row;
         const int f = m / HoWo, rem = m - f * HoWo, ho = rem / p.Wo, wo = rem - ho * p.Wo;
         const int sh = min((int)floorf(ho * p.rscale_h), p.Hr - 1), sw = min((int)floorf(wo * p.rscale_w), p.Wr - 1);
         vo = (uint32_t)((((long long)f * p.Hr + sh) * p.Wr + sw) * GROWB + nsp * YROWB + (chunk << 4));
@@ -78,9 +104,11 @@ __global__ __launch_bounds__(256, 2) void pw_single_x3_kernel(const PwSinglePara
       lds_dma16<J * 1024>(vo, srd_r, so, lds_base + buf * YBYTES + wave * (Y_PIECES * 1024));
     });
   };
+  int org = 0, org_next = 0;
   if (walker < ntiles) {
-    if (RES) issue_res(walker, 0);
-    issue_a(walker);
+    if constexpr (LISTED) org = tile_origin(walker);
+    if (RES) issue_res(walker, 0, org);
+    issue_a(walker, org);
   }
   int it = 0;
   for (int tile = walker; tile < ntiles; tile += nwalkers, ++it) {
@@ -90,7 +118,8 @@ __global__ __launch_bounds__(256, 2) void pw_single_x3_kernel(const PwSinglePara
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");           // this wave's pieces of the tile have landed (and its earlier stores left)
     __syncthreads();                                           // everyone's pieces landed; the other y buffer is free
     const bool more = tile + nwalkers < ntiles;
-    if (more && RES) issue_res(tile + nwalkers, (it + 1) & 1);
+    if constexpr (LISTED) { if (more) org_next = tile_origin(tile + nwalkers); }
+    if (more && RES) issue_res(tile + nwalkers, (it + 1) & 1, org_next);
     f32x16 acc;
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[r] = 0.f;
@@ -103,7 +132,7 @@ __global__ __launch_bounds__(256, 2) void pw_single_x3_kernel(const PwSinglePara
       acc = x3_mfma(__builtin_bit_cast(bf16x8, w[ks][0]), xh, acc);
     }
     __syncthreads();                                           // the A tile has been consumed by every wave (and, RES == 0: the previous y tile is stored)
-    if (more) issue_a(tile + nwalkers);                        // single A tile (two would not leave room for two workgroups per CU): refilled under the epilogue
+    if (more) issue_a(tile + nwalkers, org_next);                        // single A tile (two would not leave room for two workgroups per CU): refilled under the epilogue
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       const int c0 = wave * 32 + 8 * q + 4 * half;
@@ -119,9 +148,24 @@ __global__ __launch_bounds__(256, 2) void pw_single_x3_kernel(const PwSinglePara
     __syncthreads();                                           // y tile complete
     for (int idx = tid; idx < PX * YCH; idx += 256) {
       const int r = idx / YCH, c = idx - r * YCH;
-      if (m0 + r < p.M) *(uint4*)((float*)p.y + (m0 + r) * NF + nsp * N + c * 4) = *(const uint4*)(s_y + y_off(r, c));
+      if constexpr (LISTED) {
+        if (org >= 0) *(uint4*)((float*)p.y + (long long)listed_pixel(org, r) * NF + nsp * N + c * 4) = *(const uint4*)(s_y + y_off(r, c));
+      } else {
+        if (m0 + r < p.M) *(uint4*)((float*)p.y + (m0 + r) * NF + nsp * N + c * 4) = *(const uint4*)(s_y + y_off(r, c));
+      }
     }
+    if constexpr (LISTED) org = org_next;
   }
+}
+template <int KS, int RES, int NSPLIT>
+__global__ __launch_bounds__(256, 2) void pw_single_x3_kernel(const PwSingleParams p) {
+  pw_single_x3_body<KS, RES, NSPLIT, false>(p, PwBlockList{});
+}
+// The P2 lateral + nearest-upsampled top-down term over a device list of 8 x 8 blocks (deferred FPN P2 lateral): a fixed
+// persistent grid, no host read of the count.  Bit for bit pw_single_x3_kernel<KS, 2, NSPLIT> on the listed pixels
+template <int KS, int NSPLIT>
+__global__ __launch_bounds__(256, 2) void pw_single_x3_blocks_kernel(const PwSingleParams p, const PwBlockList bl) {
+  pw_single_x3_body<KS, 2, NSPLIT, true>(p, bl);
 }
 
 // (K, N) of the f16x3 trunk served here: 256 -> 256 (P2 lateral) and 256 -> 1024 (layer3's conv3)
@@ -149,6 +193,25 @@ static inline int launch_pw_single_x3(hipStream_t s, const PwSingleParams& p, in
   if (res_mode == 0) return launch_pw_single_x3_t<16, 0, 8>(s, p);
   if (res_mode == 1) return launch_pw_single_x3_t<16, 1, 8>(s, p);
   return launch_pw_single_x3_t<16, 2, 8>(s, p);
+}
+
+// The list form serves the P2 lateral (256 -> 256 + upsampled residual) on maps of whole 8 x 8 blocks whose operands fit the descriptors
+static inline bool pw_single_x3_blocks_applicable(int K, int N, int Ho, int Wo, long long M, long long res_rows) {
+  return K == 256 && N == 256 && Ho > 0 && Wo > 0 && Ho % 8 == 0 && Wo % 8 == 0 && M * 4 * K < MCG_DMA_MAX_BYTES && res_rows * 4 * N < MCG_DMA_MAX_BYTES;
+}
+// p as for launch_pw_single_x3(.., 256, 2) (M = frames * Ho * Wo); list / count: the blocks to compute; max_blocks = blocks of the map
+static inline int launch_pw_single_x3_blocks(hipStream_t s, const PwSingleParams& p, const int* list, const int* count, int max_blocks) {
+  constexpr int KS = 16, NSPLIT = 2, kLds = 2 * 32 * 512 + 32 * 64 * KS;
+  int cus;
+  if (kernel_ready<pw_single_x3_blocks_kernel<KS, NSPLIT>>(kLds, &cus)) return 1;
+  PwBlockList bl;
+  bl.list = list; bl.count = count; bl.bxn = p.Wo / 8; bl.bpf = (p.Ho / 8) * (p.Wo / 8); bl.nblk = max_blocks;
+  const int unit = 8 * NSPLIT;
+  int wgs = 2 * cus / unit * unit;                              // two workgroups per CU, whole groups of NSPLIT slices x 8 XCDs
+  const int need = (2 * max_blocks + 7) / 8 * unit;             // two tiles per block
+  if (wgs < unit) wgs = unit;
+  hipLaunchKernelGGL((pw_single_x3_blocks_kernel<KS, NSPLIT>), dim3(need < wgs ? need : wgs), dim3(256), kLds, s, p, bl);
+  return hipGetLastError() == hipSuccess ? 0 : 1;
 }
 
 // DynamicConv's `dynamic_layer` for the f16x3 engine (transformer.py:1131-1134): y[M][32768] = x[M][256] . W^T + b on M = 1344 tokens,

@@ -132,6 +132,42 @@ __global__ __launch_bounds__(256) void roi_mark_kernel(const float* __restrict__
     }
   }
 }
+// Deferred P2 lateral (engine option fpn_lateral_deferred): the 3 x 3 conv of an 8 x 8 output block reads a 10 x 10 window of the inner map,
+// so the inner blocks a stage needs are its newly listed output blocks and their neighbours inside the SAME frame (up to nine; beyond the
+// image border the conv pads with zeros and reads nothing).  One thread per (listed block, neighbour): whoever flips the neighbour's flag
+// 0 -> 1 appends it to the stage's inner list -- a flag flip is the only way onto a list, so no block is listed twice, in this stage or a
+// later one.  The grid is fixed by the map's size; the list length is read on the device.  Vector atomics only.
+__host__ __device__ inline int inner_neighbour(int id, int k, int by_n, int bx_n) {   // k = 0 .. 8 -> block id, or -1 outside the frame
+  const int bpf = by_n * bx_n, f = id / bpf, rem = id - f * bpf, by = rem / bx_n + k / 3 - 1, bx = rem % bx_n + k % 3 - 1;
+  return (by < 0 || by >= by_n || bx < 0 || bx >= bx_n) ? -1 : f * bpf + by * bx_n + bx;
+}
+__global__ __launch_bounds__(256) void inner_mark_kernel(const int* __restrict__ out_list, const int* __restrict__ out_count, int by_n, int bx_n,
+                                                         int nblk, int* __restrict__ state, int* __restrict__ list, int* __restrict__ count) {
+  const int n = min(*out_count, nblk) * 9;
+  for (int t = blockIdx.x * blockDim.x + threadIdx.x; t < n; t += gridDim.x * blockDim.x) {
+    const int src = out_list[t / 9];
+    if (src < 0 || src >= nblk) continue;
+    const int id = inner_neighbour(src, t % 9, by_n, bx_n);
+    if (id >= 0 && atomicCAS(&state[id], 0, 1) == 0) list[atomicAdd(count, 1)] = id;
+  }
+}
+int launch_inner_mark(hipStream_t s, const int* out_list, const int* out_count, int H, int W, int nblk, int* state, int* list, int* count) {
+  const long long threads = (long long)nblk * 9;
+  const int blocks = (int)((threads + 255) / 256 < 1024 ? (threads + 255) / 256 : 1024);
+  hipLaunchKernelGGL(inner_mark_kernel, dim3(blocks > 0 ? blocks : 1), dim3(256), 0, s, out_list, out_count, (H + 7) / 8, (W + 7) / 8, nblk, state,
+                     list, count);
+  MCG_CHECK_LAUNCH("inner_mark");
+  return MCG_OK;
+}
+// Host twin of inner_mark_kernel's rule (tests): the neighbours of block id inside its frame, id itself included; returns how many
+extern "C" int mcg_inner_block_neighbours(int id, int H, int W, int out[9]) {
+  int n = 0;
+  for (int k = 0; k < 9; ++k) {
+    const int v = inner_neighbour(id, k, (H + 7) / 8, (W + 7) / 8);
+    if (v >= 0) out[n++] = v;
+  }
+  return n;
+}
 __global__ void defer_clear_kernel(int* __restrict__ p, int n) {
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) p[i] = 0;
 }

@@ -37,7 +37,8 @@ EXPORTS = ['mcg_abi_version', 'mcg_build_id', 'mcg_last_error', 'mcg_device_info
            'mcg_pyramid_scatter_rows', 'mcg_preprocess_head_crops', 'mcg_merge_windows', 'mcg_smooth_gaze', 'mcg_preprocess_frames_nv12',
            'mcg_preprocess_head_crops_nv12', 'mcg_draw_gaze_arrows', 'mcg_draw_gaze_arrows_nv12',
            'mcg_detect_heads_workspace_bytes', 'mcg_detect_heads', 'mcg_letterbox_frames', 'mcg_letterbox_frames_nv12',
-           'mcg_track_state_bytes', 'mcg_track_heads', 'mcg_live_slots', 'mcg_live_gate', 'mcg_live_lanes', 'mcg_live_gate_lanes']
+           'mcg_track_state_bytes', 'mcg_track_heads', 'mcg_live_slots', 'mcg_live_gate', 'mcg_live_lanes', 'mcg_live_gate_lanes',
+           'mcg_deferred_pyramid_state', 'mcg_inner_block_neighbours']
 LETTERBOX_U8, LETTERBOX_F16, LETTERBOX_F32 = 0, 1, 2             # enum order of include/mcgaze_hip.h
 
 
@@ -150,6 +151,8 @@ def load():
     lib.mcg_deferred_pyramid_bytes.restype = sz
     lib.mcg_deferred_pyramid_bytes.argtypes = [vp, i, i, i]
     lib.mcg_deferred_pyramid_levels.argtypes = [vp, vp, i, i, i, C.POINTER(vp), C.POINTER(i)]
+    lib.mcg_deferred_pyramid_state.argtypes = [vp, vp, i, i, i, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(i), C.POINTER(i)]
+    lib.mcg_inner_block_neighbours.argtypes = [i, i, i, C.POINTER(i)]
     lib.mcg_backbone_fpn_forward_deferred.argtypes = [vp, vp, vp, i, i, i, i, vp, sz, vp, sz]
     lib.mcg_decoder_forward_deferred.argtypes = [vp, vp, vp, sz, i, i, i, i, vp, vp, vp, vp, vp, sz]
     lib.mcg_clip_forward.argtypes = [vp, vp, vp, i, i, i, i, vp, i, vp, vp, vp, vp, sz]
