@@ -802,13 +802,50 @@ typedef struct mcg_track_slot {
   float box[4];         /* x1 y1 x2 y2 of the last match; zero while free */
   int32_t id;           /* 0: free */
   int32_t age;          /* frames since the last match; 0 while free */
-  int32_t reserved[2];
+  int32_t reserved[2];  /* mcg_track_heads: neither read nor written; mcg_track_heads_motion: the bits of vx, vy (f32) */
 } mcg_track_slot;
 size_t mcg_track_state_bytes(int num_sequences, int slots);   /* 0 for sizes the entry refuses */
 int mcg_track_heads(mcg_stream s, const float* boxes_dev, long long frame_stride, const int32_t* counts_dev, int num_sequences, int num_frames,
                     int max_det, int slots, double match_iou, int max_age, void* state_dev,
                     float* slot_boxes_dev /* [Q][T][S][4] */, int32_t* image_of_dev /* [Q][T][S] */, int32_t* track_id_dev /* [Q][T][S] */,
                     int32_t* age_dev /* [Q][T][S] */, int32_t* det_of_dev /* [Q][T][S] */, int32_t* flags_dev /* [Q][T] */);
+
+/* ---------------------------------------------------------------- head identities with a constant-velocity motion model (additions to ABI 18;
+ * nothing above changes)
+ * mcg_track_heads_motion is mcg_track_heads with one thing more: a slot carries the velocity (vx, vy) of its box's centre, in pixels a frame,
+ * and its box is moved by it before every frame's match.  A head that is missed for a few frames is then looked for where it has gone, and
+ * the box of a coasting slot -- which mcg_live_slots / mcg_live_lanes cut the crop at -- follows the person.  The velocity is two f32 kept,
+ * as bits, in reserved[0] (vx) and reserved[1] (vy) of the slot's mcg_track_slot: the state layout, mcg_track_state_bytes and every reader
+ * of the state are as they were, and all zero bytes are still the empty state.  mcg_track_heads neither reads nor writes those words, so a
+ * state may pass between the two entries; the plain entry leaves the velocities as it found them.  The launch shape (ONE launch, one
+ * workgroup per sequence, no allocation, no host sync, graph-capturable), the limits, the argument checks and the six outputs are those of
+ * mcg_track_heads; velocity_gain and coast_decay must each lie in [0, 1] (a NaN does not), else MCG_ERR_ARG before any launch.
+ * THE ARITHMETIC, in terms of the numbered steps above.  Every operation is f32 and uncontracted; g = (float)velocity_gain,
+ * k = (float)coast_decay.  Per sequence and per frame, in order:
+ *  0. PREDICT.  For every live slot whose (vx, vy) is not (0, 0) -- compared as values: a -0 is a zero --:
+ *       p = (x1 + vx, y1 + vy, x2 + vx, y2 + vy);  if the four are finite the slot's box is now p; otherwise the slot keeps its box and
+ *       its velocity becomes (0, 0).  A slot with zero velocity is not touched at all (no + 0.0f): its box keeps its bits, negative zeros
+ *       included.
+ *  1 - 3 run exactly as they stand, on the predicted boxes.
+ *  4. A MATCHED slot with predicted box p and detection d:
+ *       rx = ((d.x1 + d.x2) - (p.x1 + p.x2)) * 0.5f, ry likewise in y;  vx = vx + g * rx, vy = vy + g * ry -- the product is rounded, then
+ *       the sum;  if either is not finite, both become 0.  The slot takes d's box and age = 0, as above.
+ *     An UNMATCHED live slot gets age += 1.  If age > max_age it is freed as above and its velocity becomes (0, 0).  Otherwise it KEEPS THE
+ *     PREDICTED BOX -- the coasting box moves -- and its velocity becomes (vx * k, vy * k).
+ *  5. Births as above, with velocity (0, 0): a slot freed in step 4 and born again in the same frame does not inherit a velocity.
+ *  6. The six outputs as above.  state_boxes_dev, where not NULL, row s of frame (q, t): the slot's box after the frame -- the detection's
+ *     for a slot matched or born, the predicted box for a coasting slot, zeros for a free one.
+ * Consequences: with velocity_gain == 0 on a state whose velocity words are zero, every output and the state are mcg_track_heads', bit for
+ * bit (no velocity ever leaves zero, and a slot at rest is not touched).  The result is a pure function of (state, boxes, counts, the
+ * parameters): T frames in one call are T calls of one frame, and the velocity goes through the state words exactly.  The box SIZE has no
+ * dynamics: a prediction moves the box and keeps its width and height.
+ * velocity_gain = 0.5, coast_decay = 1.0 are what the Python layer defaults to: conventional alpha-beta values, not tuned on data.
+ * mcgaze_amd/head_detect.py::track_heads_host(motion=...) is the same on the host, bit for bit. */
+int mcg_track_heads_motion(mcg_stream s, const float* boxes_dev, long long frame_stride, const int32_t* counts_dev, int num_sequences,
+                           int num_frames, int max_det, int slots, double match_iou, int max_age, double velocity_gain, double coast_decay,
+                           void* state_dev, float* slot_boxes_dev /* [Q][T][S][4] */, int32_t* image_of_dev /* [Q][T][S] */,
+                           int32_t* track_id_dev /* [Q][T][S] */, int32_t* age_dev /* [Q][T][S] */, int32_t* det_of_dev /* [Q][T][S] */,
+                           int32_t* flags_dev /* [Q][T] */, float* state_boxes_dev /* [Q][T][S][4] or NULL */);
 
 /* ---------------------------------------------------------------- live: tracker slots as streams (additions to ABI 18; nothing above changes)
  * mcg_track_heads decides on the device who is in which slot; the planning of a stream pool is a host function of how many frames each
@@ -819,7 +856,8 @@ int mcg_track_heads(mcg_stream s, const float* boxes_dev, long long frame_stride
  *
  * mcg_live_slots, after mcg_track_heads with one frame per camera: reads the tracker state of Q = num_cameras sequences of S = slots
  * (mcg_track_header + mcg_track_slot, the layout above) and writes, for every (q, s), row = q * S + s:
- *   a LIVE slot (id > 0, matched or coasting):  crop_boxes[row] = slot.box, image_of[row] = q      -- a coasting slot's box is its last match
+ *   a LIVE slot (id > 0, matched or coasting):  crop_boxes[row] = slot.box, image_of[row] = q      -- a coasting slot's box is its last match,
+ *                                                                                                     or what mcg_track_heads_motion predicted
  *   a FREE slot:                                crop_boxes[row] = 0 0 0 0,  image_of[row] = -1     -- the row the head-crop entries flag 2
  *   ring_id[tick % R][q][s] = the slot's id or 0;  ring_box[tick % R][q][s] = crop_boxes[row];  matched[q][s] = (id > 0 and age == 0)
  * crop_boxes / image_of are the tables of mcg_preprocess_head_crops over the Q frames of the tick.

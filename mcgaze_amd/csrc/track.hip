@@ -17,6 +17,13 @@
 //            ballot of free slots
 //   output   thread s writes row s of the frame
 // No decision depends on which thread made it.
+//
+// mcg_track_heads_motion is the same kernel with MOTION = true ("head identities with a constant-velocity motion model" in the header):
+// a slot carries a centre velocity, two f32 in the reserved words of its record and 512 bytes of LDS here.  Thread s moves slot s by its
+// velocity while the frame's detections are loaded -- the barrier that ends the load makes the predicted box visible to the four waves of the
+// match, so the frame has no barrier more --, and the age step, still wave 0 / lane = slot, corrects the velocity of a matched slot by the
+// distance between the detection's centre and the predicted one, decays that of a coasting slot, which keeps the predicted box, and zeroes
+// that of a freed one; a birth starts at rest.  The plain instantiation holds none of it and is what mcg_track_heads launches.
 #include "common.hpp"
 
 #pragma clang fp contract(off)
@@ -38,18 +45,22 @@ __device__ __forceinline__ int track_kth_bit(unsigned long long m, int k) {
   return __builtin_ctzll(m);
 }
 
+// MOTION: gain and decay are g and k of the header; state_boxes may be null.  Without MOTION the three are not read.
+template <bool MOTION>
 __global__ __launch_bounds__(MCG_TRK_THREADS) void track_heads_kernel(const float* __restrict__ boxes, long long frame_stride,
                                                                       const int32_t* __restrict__ counts, int T, int D, int S, float thr, int max_age,
                                                                       unsigned char* state, size_t seq_bytes, float* __restrict__ slot_boxes,
                                                                       int32_t* __restrict__ image_of, int32_t* __restrict__ track_id,
                                                                       int32_t* __restrict__ age_out, int32_t* __restrict__ det_of,
-                                                                      int32_t* __restrict__ flags) {
+                                                                      int32_t* __restrict__ flags, float gain, float decay,
+                                                                      float* __restrict__ state_boxes) {
   __shared__ float s_det[MCG_TRK_MAX_DET][4];
   __shared__ int s_det_slot[MCG_TRK_MAX_DET];                     // -2 not usable, -1 open, else the slot it went to
   __shared__ float s_box[MCG_TRK_MAX_SLOTS][4];
   __shared__ int s_id[MCG_TRK_MAX_SLOTS], s_age[MCG_TRK_MAX_SLOTS], s_slot_det[MCG_TRK_MAX_SLOTS];
   __shared__ unsigned long long s_best[3];
   __shared__ int s_flag, s_next_id;
+  __shared__ float s_vel[MOTION ? MCG_TRK_MAX_SLOTS : 1][2];      // the slot's centre velocity, pixels a frame
   const int q = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   mcg_track_header* hdr = (mcg_track_header*)(state + (size_t)q * seq_bytes);
   mcg_track_slot* slots = (mcg_track_slot*)(hdr + 1);
@@ -59,6 +70,10 @@ __global__ __launch_bounds__(MCG_TRK_THREADS) void track_heads_kernel(const floa
     for (int c = 0; c < 4; ++c) s_box[tid][c] = slots[tid].box[c];
     s_id[tid] = slots[tid].id;
     s_age[tid] = slots[tid].age;
+    if constexpr (MOTION) {
+      s_vel[tid][0] = __int_as_float(slots[tid].reserved[0]);
+      s_vel[tid][1] = __int_as_float(slots[tid].reserved[1]);
+    }
   }
   if (tid == 0) {
     s_best[0] = 0ull; s_best[1] = 0ull; s_best[2] = 0ull;
@@ -83,6 +98,19 @@ __global__ __launch_bounds__(MCG_TRK_THREADS) void track_heads_kernel(const floa
     }
     if (bad) atomicOr(&s_flag, 2);
     if (tid < S) s_slot_det[tid] = -1;
+    if constexpr (MOTION) {                                       // predict: s_box[tid] is read and written by thread tid only until the barrier
+      if (tid < S && s_id[tid] > 0) {
+        const float vx = s_vel[tid][0], vy = s_vel[tid][1];
+        if (!(vx == 0.0f && vy == 0.0f)) {                        // a slot at rest is not touched: no + 0.0f
+          const float px1 = s_box[tid][0] + vx, py1 = s_box[tid][1] + vy, px2 = s_box[tid][2] + vx, py2 = s_box[tid][3] + vy;
+          if (isfinite(px1) && isfinite(py1) && isfinite(px2) && isfinite(py2)) {
+            s_box[tid][0] = px1; s_box[tid][1] = py1; s_box[tid][2] = px2; s_box[tid][3] = py2;
+          } else {
+            s_vel[tid][0] = 0.0f; s_vel[tid][1] = 0.0f;
+          }
+        }
+      }
+    }
     __syncthreads();
     // ---------------------------------------------------------------- match
     {
@@ -135,6 +163,15 @@ __global__ __launch_bounds__(MCG_TRK_THREADS) void track_heads_kernel(const floa
       if (lane < S) {
         const int d = s_slot_det[lane];
         if (d >= 0) {
+          if constexpr (MOTION) {                                 // the detection's centre against the predicted one, before the box is taken
+            const float rx = ((s_det[d][0] + s_det[d][2]) - (s_box[lane][0] + s_box[lane][2])) * 0.5f;
+            const float ry = ((s_det[d][1] + s_det[d][3]) - (s_box[lane][1] + s_box[lane][3])) * 0.5f;
+            const float gx = gain * rx, gy = gain * ry;
+            const float vx = s_vel[lane][0] + gx, vy = s_vel[lane][1] + gy;
+            const bool ok = isfinite(vx) && isfinite(vy);
+            s_vel[lane][0] = ok ? vx : 0.0f;
+            s_vel[lane][1] = ok ? vy : 0.0f;
+          }
 #pragma unroll
           for (int c4 = 0; c4 < 4; ++c4) s_box[lane][c4] = s_det[d][c4];
           s_age[lane] = 0;
@@ -146,8 +183,10 @@ __global__ __launch_bounds__(MCG_TRK_THREADS) void track_heads_kernel(const floa
             s_age[lane] = 0;
 #pragma unroll
             for (int c4 = 0; c4 < 4; ++c4) s_box[lane][c4] = 0.0f;
+            if constexpr (MOTION) { s_vel[lane][0] = 0.0f; s_vel[lane][1] = 0.0f; }
           } else {
-            s_age[lane] = a;
+            s_age[lane] = a;                                      // with MOTION the box it keeps is the predicted one
+            if constexpr (MOTION) { s_vel[lane][0] = s_vel[lane][0] * decay; s_vel[lane][1] = s_vel[lane][1] * decay; }
           }
         }
       }
@@ -166,6 +205,7 @@ __global__ __launch_bounds__(MCG_TRK_THREADS) void track_heads_kernel(const floa
           s_id[sl] = first_id + 1 + rank;
           s_age[sl] = 0;
           s_slot_det[sl] = d;
+          if constexpr (MOTION) { s_vel[sl][0] = 0.0f; s_vel[sl][1] = 0.0f; }   // at rest, also in a slot freed in this frame
         }
         seen += __popcll(m);
       }
@@ -185,6 +225,12 @@ __global__ __launch_bounds__(MCG_TRK_THREADS) void track_heads_kernel(const floa
       det_of[o] = d;                                              // -1 unless matched or born
       track_id[o] = id;
       age_out[o] = id != 0 ? s_age[tid] : -1;
+      if constexpr (MOTION) {
+        if (state_boxes) {
+#pragma unroll
+          for (int c4 = 0; c4 < 4; ++c4) state_boxes[4 * o + c4] = id > 0 ? s_box[tid][c4] : 0.0f;
+        }
+      }
     }
     if (tid == 0) {
       flags[frame] = s_flag | (c != n ? 4 : 0);
@@ -198,6 +244,10 @@ __global__ __launch_bounds__(MCG_TRK_THREADS) void track_heads_kernel(const floa
     for (int c = 0; c < 4; ++c) slots[tid].box[c] = s_box[tid][c];
     slots[tid].id = s_id[tid];
     slots[tid].age = s_age[tid];
+    if constexpr (MOTION) {
+      slots[tid].reserved[0] = __float_as_int(s_vel[tid][0]);
+      slots[tid].reserved[1] = __float_as_int(s_vel[tid][1]);
+    }
   }
   if (tid == 0) {
     hdr->next_id = s_next_id;
@@ -210,24 +260,46 @@ extern "C" size_t mcg_track_state_bytes(int num_sequences, int slots) {
   return (size_t)num_sequences * track_sequence_bytes(slots);
 }
 
+// The one launch under both entries: `who` names the entry in the messages.
+template <bool MOTION>
+static int track_launch(const char* who, mcg_stream s, const float* boxes_dev, long long frame_stride, const int32_t* counts_dev, int num_sequences,
+                        int num_frames, int max_det, int slots, double match_iou, int max_age, float gain, float decay, void* state_dev,
+                        float* slot_boxes_dev, int32_t* image_of_dev, int32_t* track_id_dev, int32_t* age_dev, int32_t* det_of_dev, int32_t* flags_dev,
+                        float* state_boxes_dev) {
+  MCG_CHECK_ARG(num_sequences >= 0 && num_sequences <= MCG_TRK_MAX_SEQUENCES, "%s: 0 .. 65535 sequences per call (got %d)", who, num_sequences);
+  MCG_CHECK_ARG(slots >= 1 && slots <= MCG_TRK_MAX_SLOTS, "%s: slots in 1 .. 64 (got %d)", who, slots);
+  MCG_CHECK_ARG(max_det >= 1 && max_det <= MCG_TRK_MAX_DET, "%s: max_det in 1 .. 1024 (got %d)", who, max_det);
+  MCG_CHECK_ARG(num_frames >= 1, "%s: num_frames must be at least 1 (got %d)", who, num_frames);
+  MCG_CHECK_ARG((long long)num_sequences * num_frames * slots < (1ll << 31), "%s: sequences x frames x slots must stay below 2^31", who);
+  MCG_CHECK_ARG(max_age >= 0, "%s: max_age must not be negative (got %d)", who, max_age);
+  MCG_CHECK_ARG(match_iou - match_iou == 0.0, "%s: match_iou must be finite", who);
+  MCG_CHECK_ARG(frame_stride >= 4ll * max_det, "%s: bad frame_stride %lld (a frame holds %d boxes of 4 floats)", who, frame_stride, max_det);
+  if (num_sequences == 0) return MCG_OK;
+  MCG_CHECK_ARG(boxes_dev && counts_dev && state_dev && slot_boxes_dev && image_of_dev && track_id_dev && age_dev && det_of_dev && flags_dev,
+                "%s: null pointer", who);
+  MCG_CHECK_ARG(((uintptr_t)state_dev & 15) == 0, "%s: the state must be 16-byte aligned", who);
+  hipLaunchKernelGGL(track_heads_kernel<MOTION>, dim3(num_sequences), dim3(MCG_TRK_THREADS), 0, (hipStream_t)s, boxes_dev, frame_stride, counts_dev,
+                     num_frames, max_det, slots, (float)match_iou, max_age, (unsigned char*)state_dev, track_sequence_bytes(slots), slot_boxes_dev,
+                     image_of_dev, track_id_dev, age_dev, det_of_dev, flags_dev, gain, decay, state_boxes_dev);
+  MCG_CHECK_LAUNCH(who);
+  return MCG_OK;
+}
+
 extern "C" int mcg_track_heads(mcg_stream s, const float* boxes_dev, long long frame_stride, const int32_t* counts_dev, int num_sequences,
                                int num_frames, int max_det, int slots, double match_iou, int max_age, void* state_dev, float* slot_boxes_dev,
                                int32_t* image_of_dev, int32_t* track_id_dev, int32_t* age_dev, int32_t* det_of_dev, int32_t* flags_dev) {
-  MCG_CHECK_ARG(num_sequences >= 0 && num_sequences <= MCG_TRK_MAX_SEQUENCES, "mcg_track_heads: 0 .. 65535 sequences per call (got %d)", num_sequences);
-  MCG_CHECK_ARG(slots >= 1 && slots <= MCG_TRK_MAX_SLOTS, "mcg_track_heads: slots in 1 .. 64 (got %d)", slots);
-  MCG_CHECK_ARG(max_det >= 1 && max_det <= MCG_TRK_MAX_DET, "mcg_track_heads: max_det in 1 .. 1024 (got %d)", max_det);
-  MCG_CHECK_ARG(num_frames >= 1, "mcg_track_heads: num_frames must be at least 1 (got %d)", num_frames);
-  MCG_CHECK_ARG((long long)num_sequences * num_frames * slots < (1ll << 31), "mcg_track_heads: sequences x frames x slots must stay below 2^31");
-  MCG_CHECK_ARG(max_age >= 0, "mcg_track_heads: max_age must not be negative (got %d)", max_age);
-  MCG_CHECK_ARG(match_iou - match_iou == 0.0, "mcg_track_heads: match_iou must be finite");
-  MCG_CHECK_ARG(frame_stride >= 4ll * max_det, "mcg_track_heads: bad frame_stride %lld (a frame holds %d boxes of 4 floats)", frame_stride, max_det);
-  if (num_sequences == 0) return MCG_OK;
-  MCG_CHECK_ARG(boxes_dev && counts_dev && state_dev && slot_boxes_dev && image_of_dev && track_id_dev && age_dev && det_of_dev && flags_dev,
-                "mcg_track_heads: null pointer");
-  MCG_CHECK_ARG(((uintptr_t)state_dev & 15) == 0, "mcg_track_heads: the state must be 16-byte aligned");
-  hipLaunchKernelGGL(track_heads_kernel, dim3(num_sequences), dim3(MCG_TRK_THREADS), 0, (hipStream_t)s, boxes_dev, frame_stride, counts_dev, num_frames,
-                     max_det, slots, (float)match_iou, max_age, (unsigned char*)state_dev, track_sequence_bytes(slots), slot_boxes_dev, image_of_dev,
-                     track_id_dev, age_dev, det_of_dev, flags_dev);
-  MCG_CHECK_LAUNCH("mcg_track_heads");
-  return MCG_OK;
+  return track_launch<false>("mcg_track_heads", s, boxes_dev, frame_stride, counts_dev, num_sequences, num_frames, max_det, slots, match_iou, max_age,
+                             0.0f, 0.0f, state_dev, slot_boxes_dev, image_of_dev, track_id_dev, age_dev, det_of_dev, flags_dev, nullptr);
+}
+
+extern "C" int mcg_track_heads_motion(mcg_stream s, const float* boxes_dev, long long frame_stride, const int32_t* counts_dev, int num_sequences,
+                                      int num_frames, int max_det, int slots, double match_iou, int max_age, double velocity_gain,
+                                      double coast_decay, void* state_dev, float* slot_boxes_dev, int32_t* image_of_dev, int32_t* track_id_dev,
+                                      int32_t* age_dev, int32_t* det_of_dev, int32_t* flags_dev, float* state_boxes_dev) {
+  const char* who = "mcg_track_heads_motion";
+  MCG_CHECK_ARG(velocity_gain >= 0.0 && velocity_gain <= 1.0, "%s: velocity_gain must lie in 0 .. 1 (got %g)", who, velocity_gain);   // not for a NaN
+  MCG_CHECK_ARG(coast_decay >= 0.0 && coast_decay <= 1.0, "%s: coast_decay must lie in 0 .. 1 (got %g)", who, coast_decay);
+  return track_launch<true>(who, s, boxes_dev, frame_stride, counts_dev, num_sequences, num_frames, max_det, slots, match_iou, max_age,
+                            (float)velocity_gain, (float)coast_decay, state_dev, slot_boxes_dev, image_of_dev, track_id_dev, age_dev, det_of_dev,
+                            flags_dev, state_boxes_dev);
 }

@@ -21,7 +21,7 @@ import numpy as np
 import torch
 
 from .engine import _upload_table
-from .pipeline import ARROW_COLOR, _track_params, letterbox_geometry
+from .pipeline import ARROW_COLOR, _track_motion, _track_params, letterbox_geometry
 
 CLUES = ('face', 'eyes', 'head')
 last_run_stats = {}       # run_annotation's frame-cache counters of the last call (tools/dataset_throughput.py prints them); trunk_frames of run_videos
@@ -699,9 +699,10 @@ class _HeadTracker:
 
     def __init__(self, pipeline, track, device):
         self.options = {} if track is True else dict(track)
-        if track is False or set(self.options) - {'slots', 'match_iou', 'max_age'}:
-            raise ValueError(f'run_head_video: track is None, True or a dict of slots, match_iou and max_age, got {track!r}')
-        self.slots = _track_params(**self.options)[0]
+        if track is False or set(self.options) - {'slots', 'match_iou', 'max_age', 'motion'}:
+            raise ValueError(f'run_head_video: track is None, True or a dict of slots, match_iou, max_age and motion, got {track!r}')
+        self.slots = _track_params(**{k: v for k, v in self.options.items() if k != 'motion'})[0]
+        _track_motion(self.options.get('motion'), 'run_head_video(track=...)')
         self.pipeline, self.device, self.state, self.parts, self.frames = pipeline, device, None, [], 0
 
     def feed(self, boxes, counts):
@@ -801,9 +802,10 @@ def run_head_video(engine, pipeline, frames, boxes_per_frame=None, max_len=100, 
     detector's input from the frames (rgb, pixel_format and matrix as above), ``callable(img)`` returns the raw [B, N, 5 + nc] prediction
     on the device (or a tuple / list whose first item it is), and pipeline.detect_heads reads it with in_shape = img.shape[2:].  pred or
     in_shape together with detector is a ValueError.
-    track: None (everything above), True, or a dict of pipeline.track_heads' options (slots, match_iou, max_age): identities come from the
+    track: None (everything above), True, or a dict of pipeline.track_heads' options (slots, match_iou, max_age, motion): identities come from the
     tracker on the device (mcg_track_heads) instead of segment_tracks -- a person keeps ONE track while others enter, leave or cross, and
-    through up to max_age missed detections.  The tracker runs per DETECT_FRAMES frames with its state carried along: with detections= it
+    through up to max_age missed detections (motion=True or dict(gain=, decay=): looked for where their velocity takes them, the
+    constant-velocity model of mcg_track_heads_motion).  The tracker runs per DETECT_FRAMES frames with its state carried along: with detections= it
     reads detect_heads' outputs where they are, and what is read back are the slot tables (tracks_from_slots) and the flags; boxes_per_frame
     is padded to the largest count and uploaded.  -> one record per track in ascending id order, id = the track's id, frame_id = the frames
     it was matched in (a frame it coasted through is left out); everything downstream is as above, and in a frame the tracks are drawn in

@@ -123,7 +123,8 @@ def detect_heads_host(pred, in_shape, frame_hw, conf_thres=0.25, iou_thres=0.45,
 
 # ---------------------------------------------------------------- identities across frames
 TRACK_MAX_SLOTS, TRACK_MAX_DET = 64, 1024                        # the bounds of mcg_track_heads
-TRACK_HEADER_WORDS, TRACK_SLOT_WORDS = 4, 8                      # mcg_track_header / mcg_track_slot in int32 words: next_id frames_seen - - | box[4] id age - -
+TRACK_HEADER_WORDS, TRACK_SLOT_WORDS = 4, 8                      # mcg_track_header / mcg_track_slot in int32 words: next_id frames_seen - - | box[4] id age vx vy
+TRACK_MOTION_DEFAULTS = dict(gain=0.5, decay=1.0)                # conventional alpha-beta values; not tuned on data
 
 
 def track_state_words(slots):
@@ -143,6 +144,22 @@ def _track_params(slots=16, match_iou=0.3, max_age=5):
     return int(slots), match_iou, int(max_age)
 
 
+def _track_motion(motion, who='track_heads'):
+    """motion= of track_heads_host / DevicePipeline.track_heads, checked -> None (the plain tracker) or (gain, decay) of mcg_track_heads_motion.
+    None, True (gain 0.5, decay 1.0: conventional alpha-beta values, not tuned on data) or a dict of gain and decay, each in [0, 1]."""
+    if motion is None:
+        return None
+    if motion is True:
+        motion = {}
+    if not isinstance(motion, dict) or set(motion) - set(TRACK_MOTION_DEFAULTS):
+        raise ValueError(f'{who}: motion is None, True or a dict of gain and decay, got {motion!r}')
+    values = {**TRACK_MOTION_DEFAULTS, **motion}
+    for name, v in values.items():
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not 0.0 <= float(v) <= 1.0:   # not for a NaN
+            raise ValueError(f'{who}: motion {name} must lie in 0 .. 1, got {v!r}')
+    return float(values['gain']), float(values['decay'])
+
+
 def _track_shapes(boxes_shape, counts_shape, state_shape, slots):
     """boxes [T, D, 4] (one sequence) or [Q, T, D, 4], counts [T] or [Q, T], state None or [Q, words] -> (Q, T, D, whether Q was given)."""
     shape = tuple(int(v) for v in boxes_shape)
@@ -158,7 +175,7 @@ def _track_shapes(boxes_shape, counts_shape, state_shape, slots):
     return Q, shape[-3], shape[-2], len(shape) == 4
 
 
-def track_heads_host(boxes, counts, state=None, slots=16, match_iou=0.3, max_age=5):
+def track_heads_host(boxes, counts, state=None, slots=16, match_iou=0.3, max_age=5, motion=None):
     """``mcg_track_heads`` in numpy, bit for bit (the arithmetic: include/mcgaze_hip.h, "head identities across frames"), for checks and for
     users without a GPU: which head box of frame t is the person of which box of frame t - 1, by greedy IoU matching against the ``slots``
     tracks of a sequence (one camera).
@@ -172,8 +189,17 @@ def track_heads_host(boxes, counts, state=None, slots=16, match_iou=0.3, max_age
     flags [.., T] int32, state): row s of frame (q, t) is slot s -- for a slot matched or born in the frame the detection's box, image_of =
     q * T + t and det_of = the detection; for every other slot zeros, -1, -1; track_id is the slot's id after the frame (0: free), age the frames
     since its last match (-1: free).  flags: 1 a head was dropped for want of a slot, 2 a row was not finite (never matched or born), 4 a count
-    outside 0 .. D.  ``slot_boxes.reshape(-1, 4)`` and ``image_of.reshape(-1)`` are head_crops' tables when its images are the call's frames."""
+    outside 0 .. D.  ``slot_boxes.reshape(-1, 4)`` and ``image_of.reshape(-1)`` are head_crops' tables when its images are the call's frames.
+
+    motion: None is everything above.  True or dict(gain=0.5, decay=1.0) is ``mcg_track_heads_motion`` instead, bit for bit (the header's
+    "head identities with a constant-velocity motion model"): a slot carries the velocity of its box's centre in the last two words of its
+    record, its box is moved by it before every match, a match corrects the velocity by ``gain`` times the distance between the detection's
+    centre and the predicted one, and a coasting slot keeps the PREDICTED box with its velocity times ``decay``.  Both lie in [0, 1]; the
+    defaults are conventional alpha-beta values, not tuned on data.  An eighth result follows the state: state_boxes [.., T, S, 4] f32, each
+    slot's box after the frame (a coasting slot's predicted box; zeros for a free slot).  gain=0 on a state without velocities gives the
+    plain tracker's seven results."""
     slots, match_iou, max_age = _track_params(slots, match_iou, max_age)
+    motion = _track_motion(motion)
     boxes, counts = _host_array(boxes), _host_array(counts)
     state = None if state is None else _host_array(state)
     Q, T, D, given_q = _track_shapes(boxes.shape, counts.shape, None if state is None else state.shape, slots)
@@ -187,12 +213,14 @@ def track_heads_host(boxes, counts, state=None, slots=16, match_iou=0.3, max_age
     boxes, counts = boxes.reshape(Q, T, D, 4), counts.reshape(Q, T)
     state = np.zeros((Q, track_state_words(S)), np.int32) if state is None else np.array(state, dtype=np.int32, order='C')
     thr = f32(match_iou)
-    slot_boxes = np.zeros((Q, T, S, 4), f32)
+    gain, decay = (None, None) if motion is None else (f32(motion[0]), f32(motion[1]))
+    slot_boxes, state_boxes = np.zeros((Q, T, S, 4), f32), np.zeros((Q, T, S, 4), f32)
     image_of, det_of = np.full((Q, T, S), -1, np.int32), np.full((Q, T, S), -1, np.int32)
     track_id, age_out, flags = np.zeros((Q, T, S), np.int32), np.zeros((Q, T, S), np.int32), np.zeros((Q, T), np.int32)
     for q in range(Q):
         table = state[q, TRACK_HEADER_WORDS:].reshape(S, TRACK_SLOT_WORDS)
         box, ids, age, next_id = table[:, :4].copy().view(f32), table[:, 4].copy(), table[:, 5].copy(), int(state[q, 0])
+        vel = table[:, 6:8].copy().view(f32)
         for t in range(T):
             c = int(counts[q, t])
             n = min(max(c, 0), D)
@@ -201,6 +229,14 @@ def track_heads_host(boxes, counts, state=None, slots=16, match_iou=0.3, max_age
             flag = (0 if usable.all() else 2) | (4 if c != n else 0)
             slot_det, det_open = np.full(S, -1), usable.copy()
             live = ids > 0
+            if motion is not None:                                                       # step 0: a slot at rest is not touched
+                with np.errstate(all='ignore'):
+                    for s in np.flatnonzero(live & ~((vel[:, 0] == 0) & (vel[:, 1] == 0))):
+                        p = box[s] + vel[s][[0, 1, 0, 1]]
+                        if np.isfinite(p).all():
+                            box[s] = p
+                        else:
+                            vel[s] = 0
             if n and live.any():
                 with np.errstate(all='ignore'):
                     a, b = box[:, None, :], det[None, :, :]
@@ -218,11 +254,21 @@ def track_heads_host(boxes, counts, state=None, slots=16, match_iou=0.3, max_age
                     cand[:, d] = False
             for s in range(S):
                 if slot_det[s] >= 0:
+                    if motion is not None:
+                        with np.errstate(all='ignore'):
+                            d = det[slot_det[s]]
+                            r = ((d[:2] + d[2:]) - (box[s, :2] + box[s, 2:])) * f32(0.5)
+                            v = vel[s] + gain * r                                        # the product is rounded, then the sum
+                        vel[s] = v if np.isfinite(v).all() else 0
                     box[s], age[s] = det[slot_det[s]], 0
                 elif ids[s] > 0:
                     age[s] += 1
                     if age[s] > max_age:
                         box[s], ids[s], age[s] = 0, 0, 0
+                        if motion is not None:
+                            vel[s] = 0
+                    elif motion is not None:                                             # it keeps the predicted box
+                        vel[s] = vel[s] * decay
             free = [s for s in range(S) if ids[s] == 0]
             for d in np.flatnonzero(det_open):
                 if not free:
@@ -231,14 +277,21 @@ def track_heads_host(boxes, counts, state=None, slots=16, match_iou=0.3, max_age
                 s = free.pop(0)
                 next_id += 1
                 box[s], ids[s], age[s], slot_det[s] = det[d], next_id, 0, d
+                if motion is not None:
+                    vel[s] = 0
             hit = slot_det >= 0
             slot_boxes[q, t, hit] = det[slot_det[hit]]
             image_of[q, t, hit], det_of[q, t] = q * T + t, slot_det
             track_id[q, t], age_out[q, t], flags[q, t] = ids, np.where(ids != 0, age, -1), flag
+            state_boxes[q, t] = np.where((ids > 0)[:, None], box, zero)
         table[:, :4], table[:, 4], table[:, 5] = box.view(np.int32), ids, age
+        if motion is not None:
+            table[:, 6:8] = vel.view(np.int32)
         state[q, 0], state[q, 1] = next_id, state[q, 1] + T
     out = (slot_boxes, image_of, track_id, age_out, det_of, flags)
-    return (out if given_q else tuple(o[0] for o in out)) + (state,)
+    if motion is None:
+        return (out if given_q else tuple(o[0] for o in out)) + (state,)
+    return (out if given_q else tuple(o[0] for o in out)) + (state, state_boxes if given_q else state_boxes[0])
 
 
 # ---------------------------------------------------------------- the detector's input

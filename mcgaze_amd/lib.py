@@ -37,7 +37,7 @@ EXPORTS = ['mcg_abi_version', 'mcg_build_id', 'mcg_last_error', 'mcg_device_info
            'mcg_pyramid_scatter_rows', 'mcg_preprocess_head_crops', 'mcg_merge_windows', 'mcg_smooth_gaze', 'mcg_preprocess_frames_nv12',
            'mcg_preprocess_head_crops_nv12', 'mcg_draw_gaze_arrows', 'mcg_draw_gaze_arrows_nv12',
            'mcg_detect_heads_workspace_bytes', 'mcg_detect_heads', 'mcg_letterbox_frames', 'mcg_letterbox_frames_nv12',
-           'mcg_track_state_bytes', 'mcg_track_heads', 'mcg_live_slots', 'mcg_live_gate', 'mcg_live_lanes', 'mcg_live_gate_lanes',
+           'mcg_track_state_bytes', 'mcg_track_heads', 'mcg_track_heads_motion', 'mcg_live_slots', 'mcg_live_gate', 'mcg_live_lanes', 'mcg_live_gate_lanes',
            'mcg_deferred_pyramid_state', 'mcg_inner_block_neighbours']
 LETTERBOX_U8, LETTERBOX_F16, LETTERBOX_F32 = 0, 1, 2             # enum order of include/mcgaze_hip.h
 
@@ -179,6 +179,7 @@ def load():
     lib.mcg_track_state_bytes.restype = sz
     lib.mcg_track_state_bytes.argtypes = [i, i]
     lib.mcg_track_heads.argtypes = [vp, vp, C.c_longlong, vp, i, i, i, i, C.c_double, i, vp, vp, vp, vp, vp, vp, vp]
+    lib.mcg_track_heads_motion.argtypes = [vp, vp, C.c_longlong, vp, i, i, i, i, C.c_double, i, C.c_double, C.c_double, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.mcg_live_slots.argtypes = [vp, vp, i, i, i, i, vp, vp, vp, vp, vp]
     lib.mcg_live_gate.argtypes = [vp, vp, vp, i, i, i, i, vp, i, i, i, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.mcg_live_lanes.argtypes = [vp, vp, i, i, i, i, i, vp, vp, vp, vp, vp, vp, vp, vp, vp]

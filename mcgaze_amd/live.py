@@ -32,7 +32,7 @@ import torch
 from . import lib as L
 from .engine import _upload_table
 from .harness import _host, check_smooth
-from .head_detect import TRACK_HEADER_WORDS, TRACK_MAX_SLOTS, TRACK_SLOT_WORDS, _track_params, track_state_words
+from .head_detect import TRACK_HEADER_WORDS, TRACK_MAX_SLOTS, TRACK_SLOT_WORDS, _track_motion, _track_params, track_state_words
 from .stream import GazeStreamPool, WindowPlanner
 
 MAX_CAMERAS, MAX_RING, MAX_ENTRIES = 65535, 65536, 65536         # the bounds of mcg_live_slots / mcg_live_gate
@@ -313,11 +313,19 @@ class LiveGaze:
     this tick).  A row means what it means above with the LANE GRANT tick in place of the birth tick: a person is valid from the first
     multiple of ``stride`` at or after the tick they got a lane, plus clip_len - stride, and symmetrically before the slot is freed; a lane
     handed from one person to another (it can happen within one tick) yields invalid rows around the hand-over; a person left out by
-    overflow has no rows until a lane frees, and is a candidate again every tick.  ``ring_depth`` is unchanged."""
+    overflow has no rows until a lane frees, and is a candidate again every tick.  ``ring_depth`` is unchanged.
+
+    MOTION.  ``motion=None`` is everything above.  ``motion=True`` or ``dict(gain=0.5, decay=1.0)`` (pipeline.track_heads' option: conventional
+    alpha-beta values, not tuned on data) runs the tracker with its constant-velocity model (mcg_track_heads_motion): a head that is missed
+    for a few ticks is looked for where its velocity takes it, so it keeps its id, slot and lane where the plain tracker would have given
+    birth to a new person, and the box a coasting slot's crop is cut at is the PREDICTED one -- mcg_live_slots / mcg_live_lanes read it from
+    the state as before."""
 
     def __init__(self, engine_or_model, pipeline, cameras, slots=16, clip_len=7, stride=4, expand=0.8, match_iou=0.3, max_age=5, smooth=None,
-                 pixel_format='bgr', draw=False, matrix='bt601', rgb=False, person_threshold=0.5, max_decode_windows=None, lanes=None):
+                 pixel_format='bgr', draw=False, matrix='bt601', rgb=False, person_threshold=0.5, max_decode_windows=None, lanes=None, motion=None):
         self.S, self.match_iou, self.max_age = _track_params(slots, match_iou, max_age)
+        _track_motion(motion, 'LiveGaze')
+        self.motion = motion
         _check_sizes('LiveGaze', cameras, self.S)
         if cameras < 1:
             raise ValueError(f'LiveGaze: at least one camera (got {cameras})')
@@ -387,7 +395,7 @@ class LiveGaze:
                              f'{tuple(boxes.shape)}, {tuple(counts.shape)})')
         with torch.cuda.device(self.dev):
             out = self.pipe.track_heads(boxes[:, None], counts[:, None], state=self.state, slots=self.S, match_iou=self.match_iou, max_age=self.max_age,
-                                        device=self.dev)
+                                        device=self.dev, motion=self.motion)
             more = dict(flags=out[5].reshape(self.Q), **self._assign())
             img, img_hw, _, _, _ = self.pipe.head_crops(frames, self.crop_boxes, self.image_of, expand=self.expand, device=self.dev, rgb=self.rgb,
                                                         **self.frame_options)

@@ -37,7 +37,7 @@ from .arrows import (ARROW_COLOR, ARROW_COORD, ARROW_SIDE, _arrow_colors, _arrow
                      arrow_segments, draw_arrows_host, segment_coverage)
 from .frame_cache import FrameCache, _DecodeProcs, decode_image  # noqa: F401
 from .head_detect import (DETECT_MAX_DET, LETTERBOX_PAD, LetterboxGeometry, _detect_params, _detect_shapes, _letterbox_dtype,  # noqa: F401
-                          _letterbox_plan, _track_params, _track_shapes, detect_heads_host, letterbox_geometry, letterbox_host, track_heads_host,
+                          _letterbox_plan, _track_motion, _track_params, _track_shapes, detect_heads_host, letterbox_geometry, letterbox_host, track_heads_host,
                           track_state_words)
 from .nv12 import YUV_COEF, _nv12_planes, _pixel_format, _yuv_coef, _yuv_to_bgr, bgr_to_yuv, nv12_to_bgr  # noqa: F401
 from .registry import Registry
@@ -828,7 +828,7 @@ class DevicePipeline:
                     st.read_by(main)
         return out
 
-    def track_heads(self, boxes, counts, state=None, slots=16, match_iou=0.3, max_age=5, device='cuda:0', stream=None):
+    def track_heads(self, boxes, counts, state=None, slots=16, match_iou=0.3, max_age=5, device='cuda:0', stream=None, motion=None):
         """Which head of frame t is the person of which head of frame t - 1, on the device (mcg_track_heads: one launch, one workgroup per
         sequence, the frames walked inside the kernel) -- ``track_heads_host`` bit for bit, whose arguments and seven results these are.
 
@@ -840,9 +840,13 @@ class DevicePipeline:
         -> (slot_boxes [.., T, S, 4] f32, image_of, track_id, age, det_of [.., T, S] int32, flags [.., T] int32, state) on the device.
         ``slot_boxes.view(-1, 4)`` and ``image_of.view(-1)`` feed head_crops and draw_arrows directly when their images are the frames of this
         call: the rows of slots that saw no head in a frame have image_of = -1, which they flag as unusable rows (2) and skip.  With device
-        inputs and a given state the call touches the host nowhere and can be captured in a graph."""
+        inputs and a given state the call touches the host nowhere and can be captured in a graph.
+        motion: None, True or dict(gain=0.5, decay=1.0) as for ``track_heads_host``: the constant-velocity motion model
+        (mcg_track_heads_motion, the same launch), with state_boxes [.., T, S, 4] f32 -- every slot's box after the frame, a coasting slot's
+        predicted one -- as an eighth result behind the state."""
         lib = L.load()
         slots, match_iou, max_age = _track_params(slots, match_iou, max_age)
+        motion = _track_motion(motion)
         on_device = isinstance(boxes, torch.Tensor) and boxes.is_cuda
         if not on_device:
             boxes = _host_array(boxes)
@@ -865,10 +869,11 @@ class DevicePipeline:
                 new = lambda *shape, dtype=torch.int32: torch.empty(*shape, dtype=dtype, device=dev)
                 lead = (Q, T) if given_q else (T,)
                 out = (new(*lead, slots, 4, dtype=torch.float32), new(*lead, slots), new(*lead, slots), new(*lead, slots), new(*lead, slots), new(*lead))
+                more = () if motion is None else (new(*lead, slots, 4, dtype=torch.float32),)     # state_boxes
                 if state is None:
                     state = torch.zeros(Q, track_state_words(slots), dtype=torch.int32, device=dev)
                 if Q == 0:
-                    return out + (state,)
+                    return out + (state,) + more
                 frame_stride = 4 * D
                 if on_device:
                     b = boxes if given_q else boxes[None]
@@ -881,11 +886,15 @@ class DevicePipeline:
                 counts = counts.to(dev, torch.int32).contiguous() if counts_there else np.ascontiguousarray(counts, dtype=np.int32)
                 st, _, (boxes_ptr, counts_ptr) = self._ring.upload([], (boxes, counts), dev, main)
                 vp = C.c_void_p
-                L.check(lib.mcg_track_heads(vp(main.cuda_stream), vp(boxes_ptr), frame_stride, vp(counts_ptr), Q, T, D, slots, match_iou, max_age,
-                                            vp(state.data_ptr()), *(vp(t.data_ptr()) for t in out)), 'mcg_track_heads')
+                head = (vp(main.cuda_stream), vp(boxes_ptr), frame_stride, vp(counts_ptr), Q, T, D, slots, match_iou, max_age)
+                tail = (vp(state.data_ptr()), *(vp(t.data_ptr()) for t in out + more))
+                if motion is None:
+                    L.check(lib.mcg_track_heads(*head, *tail), 'mcg_track_heads')
+                else:
+                    L.check(lib.mcg_track_heads_motion(*head, *motion, *tail), 'mcg_track_heads_motion')
                 if st is not None:
                     st.read_by(main)
-        return out + (state,)
+        return out + (state,) + more
 
 
 def build_pipeline(transforms):

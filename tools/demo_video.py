@@ -4,7 +4,7 @@ label files in, per-person per-frame gaze out -- and, with --draw, the frames wi
 
 usage: demo_video.py FRAMES_DIR LABELS_DIR CONFIG CHECKPOINT --out gaze.json [--precision f16x3] [--device cuda:0] [--max-len 100]
                      [--batch-frames 448] [--head-class 1] [--ext jpg] [--smooth ALPHA] [--nv12 WxH FILE] [--matrix bt601] [--draw OUT]
-                     [--track [--slots 16] [--match-iou 0.3] [--max-age 5]]
+                     [--track [--slots 16] [--match-iou 0.3] [--max-age 5]] [--track-motion [GAIN[,DECAY]]]
                      [--color B,G,R] [--predictions DIR --in-shape HxW [--conf-thres 0.25] [--iou-thres 0.45]]
                      [--detector MODULE:FACTORY [--img-size 640] [--half]]
 
@@ -152,7 +152,19 @@ def main(argv=None):
     ap.add_argument('--slots', type=int, default=16, help='tracks held at once, of --track')
     ap.add_argument('--match-iou', type=float, default=0.3, help='IoU above which a head continues a track, of --track')
     ap.add_argument('--max-age', type=int, default=5, help='frames a track outlives its last detection, of --track')
+    ap.add_argument('--track-motion', nargs='?', const='', default=None, metavar='GAIN[,DECAY]',
+                    help='--track with the constant-velocity motion model: a head missed for a few frames is looked for where it was going '
+                         '(default 0.5,1.0: conventional alpha-beta values, not tuned on data)')
     a = ap.parse_args(argv)
+    track = dict(slots=a.slots, match_iou=a.match_iou, max_age=a.max_age) if a.track or a.track_motion is not None else None
+    if a.track_motion is not None:
+        try:
+            values = [float(v) for v in a.track_motion.split(',')] if a.track_motion else []
+        except ValueError:
+            values = None
+        if values is None or len(values) > 2:
+            raise SystemExit(f'--track-motion takes GAIN or GAIN,DECAY, got {a.track_motion!r}')
+        track['motion'] = dict(zip(('gain', 'decay'), values))
     if (a.predictions is None) != (a.in_shape is None):
         raise SystemExit('--predictions and --in-shape go together')
     if a.detector is not None and a.predictions is not None:
@@ -185,7 +197,7 @@ def main(argv=None):
     pipe = DevicePipeline(model.cfg.data.test.pipeline)
     res = harness.run_head_video(model.engine(), pipe, frames, per_frame, max_len=a.max_len, batch_frames=a.batch_frames, rgb=True,
                                  smooth=a.smooth, pixel_format='bgr' if a.nv12 is None else 'nv12', matrix=a.matrix, detections=detections, draw=draw,
-                                 track=dict(slots=a.slots, match_iou=a.match_iou, max_age=a.max_age) if a.track else None)
+                                 track=track)
     if draw is not None:
         res, annotated = res
         write_annotated(a.draw, annotated, a.nv12 is not None)

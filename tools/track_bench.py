@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Head identities across frames on the device, measured against the only route there was before it.  Prints ONE JSON line.
 
-usage: track_bench.py [--cases 1x1x4,8x1x16,1x64x16] [--max-det 300] [--slots 16] [--steps 20] [--warmup 3] [--rounds 3]
+usage: track_bench.py [--cases 1x1x4,8x1x16,1x64x16] [--max-det 300] [--slots 16] [--steps 20] [--warmup 3] [--rounds 3] [--motion]
 
 Workload: per case Q x T x heads, Q sequences of T frames with `heads` people each, drifting a few pixels a frame and listed in a random order,
 as detect_heads leaves them in device memory: boxes [Q, T, max_det, 4] and counts [Q, T].  The state carries over from call to call, so after
@@ -10,7 +10,10 @@ calls, then --steps calls bracketed by synchronize:
   device:  DevicePipeline.track_heads (mcg_track_heads: one launch, one workgroup per sequence, nothing read back);
   host:    what a caller could do before -- read boxes and counts back, run track_heads_host, upload the tables.  HOST-BOUND: a read-back that
            waits for the device, python loops and an upload, so its time is not the arithmetic's and the ratio is that of this comparison only.
-Reported per case and way: ms per call of every round and the median; the two ways' tables are compared once."""
+--motion adds a third way, alternated with the others in the same run:
+  motion:  DevicePipeline.track_heads(motion=True) (mcg_track_heads_motion: the same launch with the constant-velocity model), on a state of its
+           own, its tables compared once with track_heads_host(motion=True).  The plain entry is its yardstick.
+Reported per case and way: ms per call of every round and the median; the ways' tables are compared once."""
 import argparse
 import json
 import os
@@ -61,6 +64,7 @@ def main():
     ap.add_argument('--steps', type=int, default=20)
     ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--rounds', type=int, default=3)
+    ap.add_argument('--motion', action='store_true', help='also time mcg_track_heads_motion (gain 0.5, decay 1) beside the plain entry')
     a = ap.parse_args()
     dev = 'cuda:0'
     rs = np.random.RandomState(7)
@@ -72,6 +76,7 @@ def main():
         host_boxes, host_counts = walkers(rs, Q, T, heads, a.max_det)
         boxes, counts = torch.from_numpy(host_boxes).to(dev), torch.from_numpy(host_counts).to(dev)
         states = dict(device=torch.zeros(Q, P.track_state_words(a.slots), dtype=torch.int32, device=dev), host=None)
+        states['motion'] = torch.zeros_like(states['device'])
 
         def device():
             return pipe.track_heads(boxes, counts, state=states['device'], **opts)
@@ -81,11 +86,20 @@ def main():
             states['host'] = out[6]
             return tuple(torch.from_numpy(t).to(dev) for t in out)
 
+        def motion():
+            return pipe.track_heads(boxes, counts, state=states['motion'], motion=True, **opts)
+
         got, old = device(), host()
         torch.cuda.synchronize()
         equal = all(bool(torch.equal(g, o)) for g, o in zip(got, old))
         matched = int((got[1] >= 0).sum())
         ways = dict(device=device, host=host)
+        if a.motion:
+            moved = motion()
+            torch.cuda.synchronize()
+            twin = P.track_heads_host(host_boxes, host_counts, motion=True, **opts)
+            equal = equal and all(np.array_equal(g.cpu().numpy().view(np.int32), np.ascontiguousarray(o).view(np.int32)) for g, o in zip(moved, twin))
+            ways['motion'] = motion
         ms = {k: [] for k in ways}
         for _ in range(a.rounds):
             for k, fn in ways.items():
