@@ -956,6 +956,53 @@ int mcg_live_gate_lanes(mcg_stream s, const int32_t* ring_id_dev, const float* r
                         int32_t* track_id_dev, int32_t* valid_dev, int32_t* camera_dev, int32_t* slot_dev, float* head_box_dev,
                         int32_t* image_of_dev, int32_t* smooth_valid_dev);
 
+/* ---------------------------------------------------------------- gaze targets (additions to ABI 18; nothing above changes)
+ * What each head looks at: another head of its picture (and whether that head looks back), a rectangle marked in the picture, the lens, or
+ * nothing.  The reference stops at the arrow (MCGaze_demo/demo.ipynb, cell 5: from the head's centre towards centre - l * gaze[:2]);
+ * mcg_gaze_targets follows THAT ray until it meets something.  Targets are decided in the IMAGE PLANE: no camera intrinsics, no depth.
+ * Two launches (one thread per row; then `mutual`, which needs every target), no allocation, no host sync, graph-capturable.
+ * Everything is double and uncontracted (no FMA), every product, quotient and sum rounded on its own; inputs are read as f32 and widened,
+ * as the arrow plan does.  min / max below never see a NaN.
+ * INPUTS.  Rows: boxes [n][4] x1 y1 x2 y2, gaze (gx, gy, gz) at gaze_dev + i * gaze_stride, image_of [n]: rows with equal image_of are in
+ * one picture.  Regions: regions [m][4] rectangles and region_image [m].  Region j APPLIES to row i iff region_image[j] < 0 (every
+ * picture), or region_period == 0 and region_image[j] == image_of[i], or region_period > 0 and region_image[j] == image_of[i] %
+ * region_period (LiveGaze numbers the pictures of a call i * Q + camera: region_period = Q gives regions per camera).
+ * UNUSABLE.  A row is unusable (flag 2) iff one of its four box values or three gaze values is not finite, or x2 < x1, or y2 < y1, or
+ * image_of < 0.  It gets kind 0, target -1 and zeros elsewhere; it looks at nothing and nothing looks at it.  A region that is not finite
+ * or inverted is never hit and flags nothing.  Every other row has flag 0.
+ * CAMERA.  A usable row has kind 3 iff gz < 0 and gz * gz >= camera_cos2 * ((gx * gx + gy * gy) + gz * gz): -z is towards the lens
+ * (mcgaze_amd/metric.py::vector_to_yaw_pitch), camera_cos2 = cos(angle)^2 of the cone's half angle; a camera_cos2 above 1 never holds.
+ * This test comes before everything below.
+ * RAY.  o = ((x1 + x2) * 0.5, (y1 + y2) * 0.5), d = (-gx, -gy): the arrow's direction from the box's REAL centre -- not the arrow's own
+ * start, which the plan above truncates to whole pixels.  If both components of d compare equal to zero the kind is 0.
+ * CANDIDATES.  Every OTHER usable row of the same picture, its box grown on each side by e = expand * max(x2 - x1, y2 - y1):
+ * [x1 - e, x2 + e] x [y1 - e, y2 + e]; and every usable region that applies, as it is.
+ * SLAB TEST of a rectangle [lo_x, hi_x] x [lo_y, hi_y].  An axis a with d_a == 0 (+0 or -0) passes iff lo_a <= o_a <= hi_a and gives no
+ * bound.  Otherwise t1 = (lo_a - o_a) / d_a, t2 = (hi_a - o_a) / d_a; near = max over such axes of min(t1, t2), far = min over them of
+ * max(t1, t2) (one axis: its own pair).  A hit iff every axis passes, near <= far and far >= 0; the entry is t = near if near > 0 else +0
+ * -- 0 when o lies inside.  A hit whose t is not finite is a miss.
+ * CHOICE.  The smallest t wins; on equal t a head comes before a region, then the lower index.  Kind 1 (head: target = its row index) or 2
+ * (region: target = its index), else kind 0.
+ * OUTPUTS, per row: kind int32 (0 none, 1 head, 2 region, 3 camera), target int32 (-1 unless kind is 1 or 2), t f32 -- the double rounded
+ * once --, hit [n][2] f32 = o + t * d per component (product and sum each rounded in double, then once to f32), mutual int32, flags int32.
+ * t and hit are 0 unless kind is 1 or 2.  mutual[i] = 1 iff kind[i] == 1 and, with r = target[i], kind[r] == 1 and target[r] == i.
+ * The result is a function of the inputs alone, whatever the launch geometry.
+ *   boxes_dev, image_of_dev, regions_dev, region_image_dev   DEVICE f32 [n][4], int32 [n], f32 [m][4], int32 [m]; the region tables may be
+ *                NULL iff m == 0
+ *   gaze_dev     DEVICE f32, row i at gaze_dev + i * gaze_stride (floats, >= 3) -- the [n][3] fused gaze as it is
+ *   expand       finite, >= 0 (Python default 0.25);  camera_cos2 not NaN (Python: cos(10 degrees)^2; 2.0 switches the test off).  Both
+ *                defaults are CONVENTIONS, not tuned on data.
+ *   kind_dev .. flags_dev   DEVICE, written: int32 [n], int32 [n], f32 [n], f32 [n][2], int32 [n], int32 [n]
+ * 0 <= n <= 65536, 0 <= m <= 4096, region_period >= 0; n == 0 returns MCG_OK without a launch.  A wrong count, stride or parameter or a
+ * null pointer returns MCG_ERR_ARG before any launch; the CONTENTS of the device tables never are an error, are never read back, and
+ * whatever they hold nothing outside the given arrays is read or written.  Heads are searched in tiles of 256 rows and a tile whose
+ * image_of range holds no picture a workgroup asks about is skipped: tables whose pictures come in ascending row order (LiveGaze's
+ * [k, Q, S]) cost one picture per row.  mcgaze_amd/attention.py::gaze_targets_host is the same on the host, bit for bit.
+ * Out of scope: dwell-time accumulation, camera intrinsics or depth, polygonal regions, arrows coloured or cut at the hit point. */
+int mcg_gaze_targets(mcg_stream s, const float* boxes_dev, const float* gaze_dev, int gaze_stride, const int32_t* image_of_dev, int n,
+                     const float* regions_dev, const int32_t* region_image_dev, int m, int region_period, double expand, double camera_cos2,
+                     int32_t* kind_dev, int32_t* target_dev, float* t_dev, float* hit_dev, int32_t* mutual_dev, int32_t* flags_dev);
+
 /* ---------------------------------------------------------------- measurement aids (bench.py)
  * While armed, every launch of the contraction kernel made by THIS engine is bracketed by a hipEvent pair on its launch stream.
  * mcg_engine_profile_stop synchronises, returns per-launch duration (ms), algorithmic FLOPs, algorithmic HBM bytes (inputs and

@@ -1,0 +1,234 @@
+// Gaze targets on the device: what every head looks at -- another head of its picture, a marked region, the lens, or nothing.  The ray is the
+// demo's arrow (MCGaze_demo/demo.ipynb, cell 5: from the head's centre towards centre - l * gaze[:2]) followed until it meets something.  The
+// arithmetic is stated once, in include/mcgaze_hip.h ("gaze targets"); mcgaze_amd/attention.py::gaze_targets_host is the same on the host.
+//
+// Two launches.  gaze_targets_kernel: one thread per SOURCE row, 256-thread workgroups, everything in double and uncontracted like
+// arrow_plan_kernel.  Candidate rows go through LDS in tiles of 256 (the grown box and image_of; -1 for a row that cannot be looked at) and
+// while a tile is staged the workgroup takes the min and max image_of of its usable rows: a tile whose range cannot contain a picture of any
+// searching row of the workgroup is skipped in a workgroup-uniform branch, which is what makes the [k, Q, S] tables of live gaze (pictures in
+// ascending row order) cost one picture per row, not n.  Regions are staged the same way, keyed by region_image.  A thread walks the
+// candidates in ASCENDING index, heads before regions, and replaces its best only on a strictly smaller t: the winner is a function of the
+// inputs alone -- a skipped tile holds no candidate of the workgroup, so the launch geometry cannot show.  gaze_mutual_kernel needs every
+// target and is a second launch.  No atomics in global memory, no scratch; LDS: 256 x (4 doubles + 1 int) and a few words.
+#include <climits>
+
+#include "common.hpp"
+
+#define MCG_ATTEND_ROWS 65536
+#define MCG_ATTEND_REGIONS 4096
+#define MCG_ATTEND_THREADS 256   // the tile of candidates is one per thread
+
+// The slab test of one candidate rectangle against the ray o + t d, t >= 0 (d not both zero).  -> the entry t, or -1 for a miss.
+__device__ __forceinline__ double slab_entry(double ox, double oy, double dx, double dy, double lox, double loy, double hix, double hiy) {
+#pragma clang fp contract(off)
+  double near = -HUGE_VAL, far = HUGE_VAL;
+  bool pass = true;
+  if (dx == 0.0) {
+    pass = lox <= ox && ox <= hix;
+  } else {
+    const double t1 = (lox - ox) / dx, t2 = (hix - ox) / dx;
+    near = t1 < t2 ? t1 : t2;
+    far = t1 < t2 ? t2 : t1;
+  }
+  if (dy == 0.0) {
+    pass = pass && loy <= oy && oy <= hiy;
+  } else {
+    const double t1 = (loy - oy) / dy, t2 = (hiy - oy) / dy;
+    const double lo = t1 < t2 ? t1 : t2, hi = t1 < t2 ? t2 : t1;
+    near = lo > near ? lo : near;
+    far = hi < far ? hi : far;
+  }
+  const double t = near > 0.0 ? near : 0.0;
+  return (pass && near <= far && far >= 0.0 && isfinite(t)) ? t : -1.0;
+}
+
+__global__ __launch_bounds__(MCG_ATTEND_THREADS) void gaze_targets_kernel(const float* __restrict__ boxes, const float* __restrict__ gaze,
+                                                                          int gaze_stride, const int32_t* __restrict__ image_of, int n,
+                                                                          const float* __restrict__ regions,
+                                                                          const int32_t* __restrict__ region_image, int m, int region_period,
+                                                                          double expand, double camera_cos2, int32_t* __restrict__ kind,
+                                                                          int32_t* __restrict__ target, float* __restrict__ t_out,
+                                                                          float* __restrict__ hit, int32_t* __restrict__ flags) {
+#pragma clang fp contract(off)
+  __shared__ double c_lox[MCG_ATTEND_THREADS], c_loy[MCG_ATTEND_THREADS], c_hix[MCG_ATTEND_THREADS], c_hiy[MCG_ATTEND_THREADS];
+  __shared__ int c_key[MCG_ATTEND_THREADS];                      // a head's image_of / a region's region_image; INT_MIN: no candidate
+  __shared__ int src_lo, src_hi, srk_lo, srk_hi, tile_lo, tile_hi, tile_any;
+  const int tid = threadIdx.x;
+  const int i = blockIdx.x * MCG_ATTEND_THREADS + tid;
+  if (tid == 0) {
+    src_lo = srk_lo = INT_MAX;
+    src_hi = srk_hi = INT_MIN;
+  }
+  // ---- this thread's own row
+  int io = -1, my_kind = 0, my_flag = 2;
+  double ox = 0.0, oy = 0.0, dx = 0.0, dy = 0.0;
+  bool searching = false;
+  if (i < n) {
+    const double x1 = boxes[4 * (size_t)i], y1 = boxes[4 * (size_t)i + 1], x2 = boxes[4 * (size_t)i + 2], y2 = boxes[4 * (size_t)i + 3];
+    const float* g = gaze + (size_t)i * gaze_stride;
+    const double gx = g[0], gy = g[1], gz = g[2];                // f32 -> double: exact
+    io = image_of[i];
+    const bool usable = isfinite(x1) && isfinite(y1) && isfinite(x2) && isfinite(y2) && isfinite(gx) && isfinite(gy) && isfinite(gz) && !(x2 < x1) &&
+                        !(y2 < y1) && io >= 0;
+    if (usable) {
+      my_flag = 0;
+      if (gz < 0.0 && gz * gz >= camera_cos2 * ((gx * gx + gy * gy) + gz * gz)) {
+        my_kind = 3;
+      } else {
+        ox = (x1 + x2) * 0.5;
+        oy = (y1 + y2) * 0.5;
+        dx = -gx;
+        dy = -gy;
+        searching = !(dx == 0.0 && dy == 0.0);
+      }
+    } else {
+      io = -1;
+    }
+  }
+  const int my_rkey = region_period > 0 && io >= 0 ? io % region_period : io;
+  __syncthreads();
+  if (searching) {                                               // the pictures this workgroup asks about (LDS atomics: order-free results)
+    atomicMin(&src_lo, io);
+    atomicMax(&src_hi, io);
+    atomicMin(&srk_lo, my_rkey);
+    atomicMax(&srk_hi, my_rkey);
+  }
+  __syncthreads();
+  const int wg_lo = src_lo, wg_hi = src_hi, wgr_lo = srk_lo, wgr_hi = srk_hi;
+  double best = HUGE_VAL;
+  int best_target = -1;
+  if (wg_lo <= wg_hi) {                                          // uniform: somebody searches
+    // ---- heads, in tiles of 256 rows
+    for (int base = 0; base < n; base += MCG_ATTEND_THREADS) {
+      __syncthreads();                                           // the tile before has been read
+      if (tid == 0) {
+        tile_lo = INT_MAX;
+        tile_hi = INT_MIN;
+      }
+      const int j = base + tid;
+      int key = INT_MIN;
+      if (j < n) {
+        const double x1 = boxes[4 * (size_t)j], y1 = boxes[4 * (size_t)j + 1], x2 = boxes[4 * (size_t)j + 2], y2 = boxes[4 * (size_t)j + 3];
+        const float* g = gaze + (size_t)j * gaze_stride;
+        const double gx = g[0], gy = g[1], gz = g[2];
+        const int jo = image_of[j];
+        if (isfinite(x1) && isfinite(y1) && isfinite(x2) && isfinite(y2) && isfinite(gx) && isfinite(gy) && isfinite(gz) && !(x2 < x1) && !(y2 < y1) &&
+            jo >= 0) {
+          const double w = x2 - x1, h = y2 - y1;
+          const double e = expand * (w > h ? w : h);
+          c_lox[tid] = x1 - e;
+          c_loy[tid] = y1 - e;
+          c_hix[tid] = x2 + e;
+          c_hiy[tid] = y2 + e;
+          key = jo;
+        }
+      }
+      c_key[tid] = key;
+      __syncthreads();
+      if (key != INT_MIN) {
+        atomicMin(&tile_lo, key);
+        atomicMax(&tile_hi, key);
+      }
+      __syncthreads();
+      if (tile_hi < wg_lo || tile_lo > wg_hi) continue;          // uniform: no row of this tile is in a picture this workgroup asks about
+      if (searching) {
+        const int count = min(MCG_ATTEND_THREADS, n - base);
+        for (int c = 0; c < count; ++c) {
+          if (c_key[c] != io || base + c == i) continue;
+          const double t = slab_entry(ox, oy, dx, dy, c_lox[c], c_loy[c], c_hix[c], c_hiy[c]);
+          if (t >= 0.0 && t < best) {
+            best = t;
+            best_target = base + c;
+            my_kind = 1;
+          }
+        }
+      }
+    }
+    // ---- regions, the same way; a head wins an equal t, so a region replaces only on a strictly smaller one
+    for (int base = 0; base < m; base += MCG_ATTEND_THREADS) {
+      __syncthreads();
+      if (tid == 0) {
+        tile_lo = INT_MAX;
+        tile_hi = INT_MIN;
+        tile_any = 0;
+      }
+      const int j = base + tid;
+      int key = INT_MIN;
+      if (j < m) {
+        const double x1 = regions[4 * (size_t)j], y1 = regions[4 * (size_t)j + 1], x2 = regions[4 * (size_t)j + 2], y2 = regions[4 * (size_t)j + 3];
+        if (isfinite(x1) && isfinite(y1) && isfinite(x2) && isfinite(y2) && !(x2 < x1) && !(y2 < y1)) {
+          c_lox[tid] = x1;
+          c_loy[tid] = y1;
+          c_hix[tid] = x2;
+          c_hiy[tid] = y2;
+          key = region_image[j] < 0 ? -1 : region_image[j];
+        }
+      }
+      c_key[tid] = key;
+      __syncthreads();
+      if (key == -1) {
+        tile_any = 1;                                            // (every writer stores the same value)
+      } else if (key != INT_MIN) {
+        atomicMin(&tile_lo, key);
+        atomicMax(&tile_hi, key);
+      }
+      __syncthreads();
+      if (!tile_any && (tile_hi < wgr_lo || tile_lo > wgr_hi)) continue;   // uniform
+      if (searching) {
+        const int count = min(MCG_ATTEND_THREADS, m - base);
+        for (int c = 0; c < count; ++c) {
+          const int rk = c_key[c];
+          if (rk == INT_MIN || (rk != -1 && rk != my_rkey)) continue;
+          const double t = slab_entry(ox, oy, dx, dy, c_lox[c], c_loy[c], c_hix[c], c_hiy[c]);
+          if (t >= 0.0 && t < best) {
+            best = t;
+            best_target = base + c;
+            my_kind = 2;
+          }
+        }
+      }
+    }
+  }
+  if (i >= n) return;
+  const bool found = my_kind == 1 || my_kind == 2;
+  kind[i] = my_kind;
+  target[i] = found ? best_target : -1;
+  t_out[i] = found ? (float)best : 0.0f;
+  hit[2 * (size_t)i] = found ? (float)(ox + best * dx) : 0.0f;
+  hit[2 * (size_t)i + 1] = found ? (float)(oy + best * dy) : 0.0f;
+  flags[i] = my_flag;
+}
+
+__global__ __launch_bounds__(MCG_ATTEND_THREADS) void gaze_mutual_kernel(const int32_t* __restrict__ kind, const int32_t* __restrict__ target, int n,
+                                                                         int32_t* __restrict__ mutual) {
+  const int i = blockIdx.x * MCG_ATTEND_THREADS + threadIdx.x;
+  if (i >= n) return;
+  int v = 0;
+  if (kind[i] == 1) {
+    const int r = target[i];
+    if (r >= 0 && r < n) v = kind[r] == 1 && target[r] == i;     // (r is a row index the first launch wrote: always in range)
+  }
+  mutual[i] = v;
+}
+
+extern "C" int mcg_gaze_targets(mcg_stream stream, const float* boxes_dev, const float* gaze_dev, int gaze_stride, const int32_t* image_of_dev, int n,
+                                const float* regions_dev, const int32_t* region_image_dev, int m, int region_period, double expand, double camera_cos2,
+                                int32_t* kind_dev, int32_t* target_dev, float* t_dev, float* hit_dev, int32_t* mutual_dev, int32_t* flags_dev) {
+  const char* what = "mcg_gaze_targets";
+  MCG_CHECK_ARG(n >= 0 && n <= MCG_ATTEND_ROWS, "%s: 0 .. %d rows per call (got %d)", what, MCG_ATTEND_ROWS, n);
+  MCG_CHECK_ARG(m >= 0 && m <= MCG_ATTEND_REGIONS, "%s: 0 .. %d regions per call (got %d)", what, MCG_ATTEND_REGIONS, m);
+  MCG_CHECK_ARG(gaze_stride >= 3 && region_period >= 0, "%s: bad sizes gaze_stride=%d region_period=%d", what, gaze_stride, region_period);
+  MCG_CHECK_ARG(expand >= 0.0 && expand - expand == 0.0 && camera_cos2 == camera_cos2, "%s: expand must be finite and not negative, camera_cos2 a number",
+                what);
+  MCG_CHECK_ARG(n == 0 || (boxes_dev && gaze_dev && image_of_dev && kind_dev && target_dev && t_dev && hit_dev && mutual_dev && flags_dev),
+                "%s: null pointer", what);
+  MCG_CHECK_ARG(m == 0 || (regions_dev && region_image_dev), "%s: null region table with m=%d", what, m);
+  if (n == 0) return MCG_OK;
+  const dim3 grid((n + MCG_ATTEND_THREADS - 1) / MCG_ATTEND_THREADS), block(MCG_ATTEND_THREADS);
+  hipLaunchKernelGGL(gaze_targets_kernel, grid, block, 0, (hipStream_t)stream, boxes_dev, gaze_dev, gaze_stride, image_of_dev, n, regions_dev,
+                     region_image_dev, m, region_period, expand, camera_cos2, kind_dev, target_dev, t_dev, hit_dev, flags_dev);
+  MCG_CHECK_LAUNCH(what);
+  hipLaunchKernelGGL(gaze_mutual_kernel, grid, block, 0, (hipStream_t)stream, kind_dev, target_dev, n, mutual_dev);
+  MCG_CHECK_LAUNCH("mcg_gaze_targets (mutual)");
+  return MCG_OK;
+}

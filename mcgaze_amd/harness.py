@@ -20,6 +20,7 @@ import os
 import numpy as np
 import torch
 
+from .attention import _attention_options
 from .engine import _upload_table
 from .pipeline import ARROW_COLOR, _track_motion, _track_params, letterbox_geometry
 
@@ -658,6 +659,7 @@ def head_arrows(head_boxes, gaze):
 
 DRAW_FRAMES = 16                                       # frames per drawing call of run_head_video(draw=...)
 DETECT_FRAMES = 64                                     # frames per pipeline.detect_heads call of run_head_video(detections=...)
+ATTENTION_FRAMES = 64                                  # frames per pipeline.gaze_targets call of run_head_video(attention=...)
 
 
 def head_boxes_per_frame(boxes, counts):
@@ -768,8 +770,36 @@ def _frame_hw(frame, pixel_format):
     return int(frame.shape[0]), int(frame.shape[1])
 
 
+def _add_targets(records, pipeline, device, num_frames, gaze_key, regions, region_image, options):
+    """run_head_video(attention=...): the gaze targets of every record and frame, ATTENTION_FRAMES frames per pipeline.gaze_targets call (host
+    tables up through the staging ring, the result tables read back), written into the records."""
+    rows = [[] for _ in range(num_frames)]                        # frame -> (record, index in it) of its heads, in record order
+    for r, rec in enumerate(records):
+        L_ = len(rec['frame_id'])
+        rec.update(target_kind=np.zeros(L_, np.int32), target_id=[None] * L_, target_region=np.full(L_, -1, np.int32),
+                   target_hit=np.zeros((L_, 2), np.float32), mutual=np.zeros(L_, np.int32))
+        for j, t in enumerate(rec['frame_id']):
+            rows[t].append((r, j))
+    for t0 in range(0, num_frames, ATTENTION_FRAMES):
+        part = [(k, r, j) for k, heads in enumerate(rows[t0:t0 + ATTENTION_FRAMES]) for r, j in heads]
+        if not part:
+            continue
+        boxes = np.asarray([records[r]['head_box'][j] for _, r, j in part], dtype=np.float32).reshape(-1, 4)
+        gaze = np.asarray([records[r][gaze_key][j, :3] for _, r, j in part], dtype=np.float32).reshape(-1, 3)
+        got = pipeline.gaze_targets(boxes, gaze, np.asarray([k for k, _, _ in part], dtype=np.int32), regions=regions, region_image=region_image,
+                                    device=device, **options)
+        kind, target, _, hit, mutual, _ = (np.asarray(_host(g)) for g in got)
+        for i, (_, r, j) in enumerate(part):
+            rec, k = records[r], int(kind[i])
+            rec['target_kind'][j], rec['mutual'][j], rec['target_hit'][j] = k, mutual[i], hit[i]
+            if k == 1:
+                rec['target_id'][j] = records[part[int(target[i])][1]]['id']
+            elif k == 2:
+                rec['target_region'][j] = target[i]
+
+
 def run_head_video(engine, pipeline, frames, boxes_per_frame=None, max_len=100, batch_frames=448, expand=0.8, rgb=False, smooth=None, pixel_format='bgr',
-                   matrix='bt601', detections=None, track=None, draw=None):
+                   matrix='bt601', detections=None, track=None, attention=None, draw=None):
     """Steps 3-4 of the demo from what its users hold -- the video's frames and one head box per person per frame -- to per-person gaze:
     segment_tracks (cell 1), the head windows cut, resized and normalised on the device (pipeline.head_crops: cell 4's crop arithmetic and
     ``cfg.data.test.pipeline[1:]``), run_tracks (cell 4's loop, batched), head_arrows (cell 5's end points).
@@ -809,8 +839,16 @@ def run_head_video(engine, pipeline, frames, boxes_per_frame=None, max_len=100, 
     reads detect_heads' outputs where they are, and what is read back are the slot tables (tracks_from_slots) and the flags; boxes_per_frame
     is padded to the largest count and uploaded.  -> one record per track in ascending id order, id = the track's id, frame_id = the frames
     it was matched in (a frame it coasted through is left out); everything downstream is as above, and in a frame the tracks are drawn in
-    ascending id.  ValueError, naming the frame and ``slots``, where a frame shows more heads than there are free slots."""
+    ascending id.  ValueError, naming the frame and ``slots``, where a frame shows more heads than there are free slots.
+    attention: None (everything above), True, or dict(regions=[[x1, y1, x2, y2], ...], expand=0.25, camera_angle=10.0): what every person looks
+    at in every frame (pipeline.gaze_targets, mcg_gaze_targets), worked out once the records exist, ATTENTION_FRAMES frames per call, from
+    the boxes and the gaze ``arrow`` comes from.  Every record gains, per frame: target_kind int32 [L] (attention.KIND_NONE / KIND_HEAD /
+    KIND_REGION / KIND_CAMERA), target_id (a list: the ``id`` of the record of the person looked at, else None), target_region int32 [L] (the
+    index into regions, else -1), target_hit f32 [L,2] (where the ray from the head's centre enters the target, in frame pixels) and mutual
+    int32 [L] (the two look at each other).  The regions apply to every frame.  Decided in the image plane; expand and camera_angle are
+    conventions, not tuned on data."""
     smooth = check_smooth('run_head_video', smooth)
+    attention = _attention_options('run_head_video', attention)
     if (boxes_per_frame is None) == (detections is None):
         raise ValueError('run_head_video: give exactly one of boxes_per_frame and detections')
     tracker = None if track is None else _HeadTracker(pipeline, track, engine.device)
@@ -882,6 +920,8 @@ def run_head_video(engine, pipeline, frames, boxes_per_frame=None, max_len=100, 
                 rec['fused_smooth'] = smooth_host(rec['fused'], smooth)
             out.append(dict(id=(si, pi) if tracker is None else seg['id'], **rec, frame_id=list(seg['frame_id']), head_box=head_box, crop=np.concatenate([c for _, c in got]),
                             arrow=head_arrows(person, rec['fused' if smooth is None else 'fused_smooth'])))
+    if attention is not None:
+        _add_targets(out, pipeline, engine.device, len(boxes_per_frame), 'fused' if smooth is None else 'fused_smooth', *attention)
     if draw is None:
         return out
     opts = {'copy': True, **({} if draw is True else dict(draw))}

@@ -30,6 +30,7 @@ import numpy as np
 import torch
 
 from . import lib as L
+from .attention import KIND_HEAD, _attention_options
 from .engine import _upload_table
 from .harness import _host, check_smooth
 from .head_detect import TRACK_HEADER_WORDS, TRACK_MAX_SLOTS, TRACK_SLOT_WORDS, _track_motion, _track_params, track_state_words
@@ -319,10 +320,21 @@ class LiveGaze:
     alpha-beta values, not tuned on data) runs the tracker with its constant-velocity model (mcg_track_heads_motion): a head that is missed
     for a few ticks is looked for where its velocity takes it, so it keeps its id, slot and lane where the plain tracker would have given
     birth to a new person, and the box a coasting slot's crop is cut at is the PREDICTED one -- mcg_live_slots / mcg_live_lanes read it from
-    the state as before."""
+    the state as before.
+
+    ATTENTION.  ``attention=None`` is everything above.  ``attention=True`` or ``dict(regions=, expand=0.25, camera_angle=10.0)`` adds what
+    every returned row looks at (pipeline.gaze_targets, mcg_gaze_targets: one call per tick that returns frames, over the gated head_box, the
+    gaze that ``draw`` uses and the gate's image_of, so an invalid row looks at nothing and nothing looks at it): target_kind (0 none, 1 head,
+    2 region, 3 camera), target (the slot of the person looked at -- with lanes their lane --, or the region's index, else -1), target_id (that
+    person's track_id, else 0), target_t, target_hit [.., 2] (where the ray from the head's centre enters the target, in frame pixels) and
+    mutual (the two look at each other), shaped like track_id.  regions: a list of Q tables [m_q, 4] of rectangles x1 y1 x2 y2 in frame
+    pixels, one per camera (None: none there), uploaded once; a region's index counts through the cameras' tables in order.  Targets are
+    decided in the image plane, and expand / camera_angle are conventions, not tuned on data.  Still no wait for the device, no copy to the
+    host."""
 
     def __init__(self, engine_or_model, pipeline, cameras, slots=16, clip_len=7, stride=4, expand=0.8, match_iou=0.3, max_age=5, smooth=None,
-                 pixel_format='bgr', draw=False, matrix='bt601', rgb=False, person_threshold=0.5, max_decode_windows=None, lanes=None, motion=None):
+                 pixel_format='bgr', draw=False, matrix='bt601', rgb=False, person_threshold=0.5, max_decode_windows=None, lanes=None, motion=None,
+                 attention=None):
         self.S, self.match_iou, self.max_age = _track_params(slots, match_iou, max_age)
         _track_motion(motion, 'LiveGaze')
         self.motion = motion
@@ -332,6 +344,7 @@ class LiveGaze:
         self.P = None if lanes is None else _check_lanes('LiveGaze', lanes, int(cameras), self.S)
         self.Q, self.T, self.s = int(cameras), int(clip_len), int(stride)
         self.smooth = check_smooth('LiveGaze', smooth)
+        attention = _attention_options('LiveGaze', attention, self.Q)
         self.pipe, self.expand, self.draw = pipeline, float(expand), bool(draw)
         self.frame_options = dict(pixel_format=pixel_format, matrix=matrix)
         self.rgb = bool(rgb)
@@ -355,6 +368,10 @@ class LiveGaze:
         self.windows, self.kept = [], {}
         self.ticks = self.emitted = 0
         self.finished = False
+        self.attention = None
+        if attention is not None:                                # the regions go up once: region_image = camera, matched through region_period = Q
+            regions, region_image, options = attention
+            self.attention = dict(options, regions=torch.from_numpy(regions).to(self.dev), region_image=torch.from_numpy(region_image).to(self.dev))
 
     def _call(self, name, *args):
         """One entry of the library on the current stream: a tensor goes as its address, None as a null pointer, an int as it is."""
@@ -384,6 +401,24 @@ class LiveGaze:
         else:
             self._call('mcg_live_gate_lanes', self.ring_id, self.ring_box, self.ring_col, self.R, self.Q, self.S, self.P, *table, out['camera'],
                        out['slot'], *tail)
+
+    def _targets(self, out, k):
+        """attention=: what every gated row looks at, over the k * Q pictures handed out -> the tables _emit adds."""
+        lead = self.lead
+        if k:
+            gaze = out['fused_smooth' if self.smooth is not None else 'fused']
+            kind, target, t, hit, mutual, _ = self.pipe.gaze_targets(out['head_box'].view(-1, 4), gaze.view(-1, 3), out['image_of'].view(-1),
+                                                                     region_period=self.Q, device=self.dev, **self.attention)
+            head = kind == KIND_HEAD
+            # a head's target is a flat row of [k, Q, S] / [k, P]: its id is gathered there, and what is handed back is the index within
+            # the picture's rows -- the slot (the same camera, since the same picture) or the lane
+            target_id = torch.where(head, out['track_id'].view(-1)[target.clamp(min=0).long()], torch.zeros_like(kind))
+            target = torch.where(head, target % lead[-1], target)
+        else:
+            new = lambda *shape, dtype=torch.int32: torch.empty(*shape, dtype=dtype, device=self.dev)
+            kind, target, target_id, mutual, t, hit = new(0), new(0), new(0), new(0), new(0, dtype=torch.float32), new(0, 2, dtype=torch.float32)
+        return dict(target_kind=kind.view(k, *lead), target=target.view(k, *lead), target_id=target_id.view(k, *lead), target_t=t.view(k, *lead),
+                    target_hit=hit.view(k, *lead, 2), mutual=mutual.view(k, *lead))
 
     def tick(self, frames, boxes, counts):
         """One frame per camera and its detections -> the frames that became final (see the class)."""
@@ -444,6 +479,8 @@ class LiveGaze:
             table = check_gate_table(table, self.ticks - 1, self.R)
             self._gate(_upload_table(table, self.dev), len(table), first_out, k, out)
             self.windows = [w for w in self.windows if w[1] > self.emitted + k - 1]     # the next call's first neighbour is the last frame of this
+        if self.attention is not None:
+            out.update(self._targets(out, k))
         if self.draw:
             images = [f for t in range(self.emitted, self.emitted + k) for f in self.kept.pop(t)]
             if k:

@@ -18,7 +18,7 @@ every video frame before this chain; there the WINDOW is chosen on the device as
 boxes that may both live in device memory already.  ``head_crop_window`` is the same arithmetic on the host, for checks and for drawing.
 ``DevicePipeline.letterbox`` makes the head detector's input from the same frames, ``detect_heads`` head boxes from its raw output and
 ``track_heads`` one identity per person from the boxes of consecutive frames.
-Re-exported from beside this module: decoded frames (frame_cache.py), NV12 (nv12.py), arrows (arrows.py), the detector's two sides (head_detect.py), upload (staging.py).
+Re-exported from beside this module: decoded frames (frame_cache.py), NV12 (nv12.py), arrows (arrows.py), gaze targets (attention.py), the detector's two sides (head_detect.py), upload (staging.py).
 
 Randomness: the reference's ``CenterCrop(crop_type='relative_range')`` draws the crop size from the global numpy RNG at TEST
 time too (transforms.py:1126-1130), and ``RandomFlip(flip_ratio=0.0)`` consumes one more uniform
@@ -35,6 +35,8 @@ import torch
 from . import lib as L
 from .arrows import (ARROW_COLOR, ARROW_COORD, ARROW_SIDE, _arrow_colors, _arrow_params, _arrow_rows,  # noqa: F401
                      arrow_segments, draw_arrows_host, segment_coverage)
+from .attention import _check_counts, _region_tables, _target_params, gaze_targets_host  # noqa: F401
+from .attention import _row_tables as _target_rows
 from .frame_cache import FrameCache, _DecodeProcs, decode_image  # noqa: F401
 from .head_detect import (DETECT_MAX_DET, LETTERBOX_PAD, LetterboxGeometry, _detect_params, _detect_shapes, _letterbox_dtype,  # noqa: F401
                           _letterbox_plan, _track_motion, _track_params, _track_shapes, detect_heads_host, letterbox_geometry, letterbox_host, track_heads_host,
@@ -718,6 +720,74 @@ class DevicePipeline:
                 if st is not None:
                     st.read_by(main)
         return out, flags
+
+    def gaze_targets(self, boxes, gaze, image_of, regions=None, region_image=None, region_period=0, expand=0.25, camera_angle=10.0, device='cuda:0',
+                     stream=None):
+        """What every head looks at, on the device (mcg_gaze_targets: one launch over the rows, one for ``mutual``) -- ``gaze_targets_host`` bit
+        for bit, whose arguments and six results these are: the arrow's ray from the head's centre followed to the nearest other head of the
+        same picture (its box grown by ``expand`` of its longer side), the nearest marked rectangle, or the lens (a gaze within
+        ``camera_angle`` degrees of -z).  Decided in the image plane; the defaults are conventions, not tuned on data.
+
+        boxes [n,4], gaze [n,>=3], image_of [n] (None: one picture): CUDA tensors are read where they are -- an f32 gaze with packed rows, the
+        [n,3] ``fused`` of a results='device' stream or a wider table, has its row stride taken from the tensor; other views are made contiguous
+        -- and numpy tables go up through the staging ring (a host table next to a device one is moved with torch).  regions [m,4] and
+        region_image [m] (None: -1, every picture) likewise; region_period as in the header.  Options and shapes are checked on the host
+        before anything is launched (TypeError / ValueError); device tables are not read back: a row that cannot be used comes back with
+        flag 2.  With device tables the call touches the host nowhere and can be captured in a graph.
+        -> (kind, target [n] int32, t [n] f32, hit [n,2] f32, mutual, flags [n] int32) on the device."""
+        lib = L.load()
+        who = 'gaze_targets'
+        expand, cos2, period = _target_params(expand, camera_angle, region_period, who)
+        dev = _device(device, 'mcg_gaze_targets')
+        on_device = lambda t: isinstance(t, torch.Tensor) and t.is_cuda
+        rows_there = any(on_device(t) for t in (boxes, gaze, image_of))
+        regions_there = any(on_device(t) for t in (regions, region_image))
+        if not rows_there:
+            boxes, gaze, image_of = _target_rows(who, boxes, gaze, image_of)
+        if not regions_there:
+            regions, region_image = _region_tables(who, regions, region_image)
+        with torch.cuda.device(dev):
+            main = _caller_stream(stream, dev)
+            with torch.cuda.stream(main):
+                there = lambda t, dtype: (t if isinstance(t, torch.Tensor) else torch.as_tensor(np.asarray(t))).to(dev, dtype)
+                gaze_stride = 3
+                if rows_there:
+                    boxes, gaze = there(boxes, torch.float32).contiguous(), there(gaze, torch.float32)
+                    n = int(boxes.shape[0])
+                    if boxes.ndim != 2 or boxes.shape[1] != 4 or gaze.ndim != 2 or gaze.shape[0] != n or gaze.shape[1] < 3:
+                        raise ValueError(f'{who}: boxes {tuple(boxes.shape)} and gaze {tuple(gaze.shape)} must be [n,4] and [n,>=3]')
+                    if not (gaze.stride(1) == 1 and (n <= 1 or gaze.stride(0) >= 3)):
+                        gaze = gaze.contiguous()
+                    gaze_stride = int(gaze.stride(0)) if n > 1 else int(gaze.shape[1])
+                    image_of = torch.zeros(n, dtype=torch.int32, device=dev) if image_of is None else there(image_of, torch.int32).contiguous()
+                    if tuple(image_of.shape) != (n,):
+                        raise ValueError(f'{who}: image_of must be [{n}], one per row; got {tuple(image_of.shape)}')
+                n = int(boxes.shape[0])
+                if regions_there:
+                    if regions is None:
+                        raise ValueError(f'{who}: region_image without regions')
+                    regions = there(regions, torch.float32).contiguous()
+                    if regions.ndim != 2 or regions.shape[1] != 4:
+                        raise ValueError(f'{who}: regions must be [m, 4] x1 y1 x2 y2, got {tuple(regions.shape)}')
+                    m = int(regions.shape[0])
+                    region_image = torch.full((m,), -1, dtype=torch.int32, device=dev) if region_image is None else \
+                        there(region_image, torch.int32).contiguous()
+                    if tuple(region_image.shape) != (m,):
+                        raise ValueError(f'{who}: region_image must be [{m}], one per region; got {tuple(region_image.shape)}')
+                m = int(regions.shape[0])
+                _check_counts(who, n, m)
+                new = lambda *shape, dtype=torch.int32: torch.empty(*shape, dtype=dtype, device=dev)
+                out = (new(n), new(n), new(n, dtype=torch.float32), new(n, 2, dtype=torch.float32), new(n), new(n))
+                if n == 0:
+                    return out
+                st, _, (boxes_ptr, gaze_ptr, image_of_ptr, regions_ptr, region_image_ptr) = self._ring.upload(
+                    [], (boxes, gaze, image_of, regions if m else None, region_image if m else None), dev, main)
+                vp = C.c_void_p
+                L.check(lib.mcg_gaze_targets(vp(main.cuda_stream), vp(boxes_ptr), vp(gaze_ptr), gaze_stride, vp(image_of_ptr), n, vp(regions_ptr),
+                                             vp(region_image_ptr), m, period, expand, cos2, *(vp(t.data_ptr()) for t in out)), 'mcg_gaze_targets')
+                if st is not None:
+                    st.read_by(main)
+        return out
 
     def letterbox(self, frames, new_shape=640, stride=32, auto=True, scaleup=True, dtype=torch.float16, rgb=False, pixel_format='bgr', matrix='bt601',
                   device='cuda:0', stream=None):

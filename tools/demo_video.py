@@ -6,7 +6,7 @@ usage: demo_video.py FRAMES_DIR LABELS_DIR CONFIG CHECKPOINT --out gaze.json [--
                      [--batch-frames 448] [--head-class 1] [--ext jpg] [--smooth ALPHA] [--nv12 WxH FILE] [--matrix bt601] [--draw OUT]
                      [--track [--slots 16] [--match-iou 0.3] [--max-age 5]] [--track-motion [GAIN[,DECAY]]]
                      [--color B,G,R] [--predictions DIR --in-shape HxW [--conf-thres 0.25] [--iou-thres 0.45]]
-                     [--detector MODULE:FACTORY [--img-size 640] [--half]]
+                     [--detector MODULE:FACTORY [--img-size 640] [--half]] [--attention [--regions FILE.json]]
 
 FRAMES_DIR holds 0.<ext>, 1.<ext>, ... (the demo's `frames/`), LABELS_DIR holds 0.txt, 1.txt, ... with lines `class x1 y1 x2 y2` in pixels
 (the demo's `result/labels/`); a frame without a label file shows no head.  CONFIG is the L2CS config, whose test pipeline the demo runs
@@ -31,7 +31,12 @@ the detector's options.
 `FACTORY()` returns a callable that takes the letterboxed batch [B, 3, h, w] on the device -- RGB planes in [0, 1], half with --half, else
 float -- and returns the raw [B, N, 5 + nc] prediction (or a tuple / list that starts with it).  The letterbox (--img-size, the demo's 640,
 stride 32), the filter, NMS and the scale-back run on the device (harness.run_head_video(detections=dict(detector=...)),
-pipeline.letterbox and pipeline.detect_heads); the network is the caller's."""
+pipeline.letterbox and pipeline.detect_heads); the network is the caller's.
+--attention: what every person looks at in every frame (harness.run_head_video(attention=...), pipeline.gaze_targets on the device): each
+entry gains per frame `target_kind` (0 none, 1 another person, 2 a region, 3 the camera), `target_id` (the [segment, person] looked at, or
+null), `target_region`, `target_hit` (where the gaze ray enters the target, in frame pixels) and `mutual`.  --regions FILE.json: a JSON list
+of rectangles [[x1, y1, x2, y2], ...] in frame pixels -- a screen, a shelf, a door.  Decided in the image plane, with conventional,
+untuned defaults (a looked-at head box grown by 0.25 of its longer side, a 10 degree cone for the camera)."""
 import argparse
 import importlib
 import json
@@ -155,7 +160,17 @@ def main(argv=None):
     ap.add_argument('--track-motion', nargs='?', const='', default=None, metavar='GAIN[,DECAY]',
                     help='--track with the constant-velocity motion model: a head missed for a few frames is looked for where it was going '
                          '(default 0.5,1.0: conventional alpha-beta values, not tuned on data)')
+    ap.add_argument('--attention', action='store_true', help='add what every person looks at: another person, a region of --regions, the camera')
+    ap.add_argument('--regions', default=None, metavar='FILE.json', help='rectangles [[x1, y1, x2, y2], ...] in frame pixels, of --attention')
     a = ap.parse_args(argv)
+    if a.regions is not None and not a.attention:
+        raise SystemExit('--regions belongs to --attention')
+    attention = None
+    if a.attention:
+        attention = {}
+        if a.regions is not None:
+            with open(a.regions) as f:
+                attention['regions'] = json.load(f)
     track = dict(slots=a.slots, match_iou=a.match_iou, max_age=a.max_age) if a.track or a.track_motion is not None else None
     if a.track_motion is not None:
         try:
@@ -197,13 +212,16 @@ def main(argv=None):
     pipe = DevicePipeline(model.cfg.data.test.pipeline)
     res = harness.run_head_video(model.engine(), pipe, frames, per_frame, max_len=a.max_len, batch_frames=a.batch_frames, rgb=True,
                                  smooth=a.smooth, pixel_format='bgr' if a.nv12 is None else 'nv12', matrix=a.matrix, detections=detections, draw=draw,
-                                 track=track)
+                                 track=track, attention=attention)
     if draw is not None:
         res, annotated = res
         write_annotated(a.draw, annotated, a.nv12 is not None)
     out = [dict(segment=r['id'][0], person=r['id'][1], frame_id=r['frame_id'], head_box=r['head_box'].tolist(), crop=r['crop'].tolist(),
                 gaze=r['fused'].tolist(), arrow=r['arrow'].tolist(), det=r['det'].tolist(), others=r['others'].tolist(),
-                **({} if a.smooth is None else dict(gaze_smooth=r['fused_smooth'].tolist()))) for r in res]
+                **({} if a.smooth is None else dict(gaze_smooth=r['fused_smooth'].tolist())),
+                **({} if attention is None else dict(target_kind=r['target_kind'].tolist(), target_id=[None if v is None else list(v) for v in r['target_id']],
+                                                     target_region=r['target_region'].tolist(), target_hit=r['target_hit'].tolist(),
+                                                     mutual=r['mutual'].tolist()))) for r in res]
     with open(a.out, 'w') as f:
         json.dump(dict(frames=n, tracks=out), f)
     print(f'{n} frames, {len(out)} (segment, person) tracks, {sum(len(r["frame_id"]) for r in out)} head crops -> {a.out}')
