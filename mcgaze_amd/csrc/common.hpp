@@ -113,6 +113,23 @@ __device__ __forceinline__ uint4 relu_chunk(const uint4& c, bf16_t*) {
 }
 
 __device__ __forceinline__ uint4 relu_chunk(const uint4& c, f16_t*) { return relu_chunk(c, (bf16_t*)nullptr); }   // fp16 is sign-magnitude too
+// four f32 -> four bf16 (round to nearest even) with ReLU applied on the stored bf16 as a packed signed max (relu_chunk's form:
+// the bits the contraction kernel's epilogue produces)
+typedef short s16x4_hw __attribute__((ext_vector_type(4)));
+template <typename F>   // bf16_t or f16_t: both are sign-magnitude, the packed signed max clears exactly the negative values
+__device__ __forceinline__ uint2 relu_pack4(const float (&v)[4]) {
+  const uint2 o = make_uint2(H16<F>::pack2(v[0], v[1]), H16<F>::pack2(v[2], v[3]));
+  const s16x4_hw z4 = {0, 0, 0, 0};
+  return __builtin_bit_cast(uint2, __builtin_elementwise_max(__builtin_bit_cast(s16x4_hw, o), z4));
+}
+
+// Nearest-upsample source: the row of [frames][Hr][Wr] that F.interpolate(mode='nearest') reads for output pixel m of [frames][Ho][Wo]
+// (HoWo = Ho * Wo).  torch's rule per axis: src = min(floor(dst * scale), in - 1) with scale = in / out in f32 (rscale_h, rscale_w)
+__device__ __forceinline__ long long nearest_src_row(int m, int HoWo, int Wo, int Hr, int Wr, float rscale_h, float rscale_w) {
+  const int f = m / HoWo, rem = m - f * HoWo, ho = rem / Wo, wo = rem - ho * Wo;
+  const int sh = min((int)floorf(ho * rscale_h), Hr - 1), sw = min((int)floorf(wo * rscale_w), Wr - 1);
+  return ((long long)f * Hr + sh) * Wr + sw;
+}
 
 // One 32x32 MFMA "chunk pair" step: each lane holds 16 bytes of A (row lane&31) and 16 bytes of B
 // (column lane&31) taken from K-chunk 2j + (lane>>5).  bf16: one v_mfma_f32_32x32x16_bf16.

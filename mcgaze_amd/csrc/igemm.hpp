@@ -238,11 +238,7 @@ __global__ __launch_bounds__(256) void igemm_kernel(const IgemmParams p) {
         }
         if (p.res_mode != MCG_RES_NONE) {
           long long rrow = m;
-          if (p.res_mode == MCG_RES_UPSAMPLE_ADD) {
-            const int f = m / HoWo, rem = m - f * HoWo, ho = rem / p.Wo, wo = rem - ho * p.Wo;
-            const int sh = min((int)floorf(ho * p.rscale_h), p.Hr - 1), sw = min((int)floorf(wo * p.rscale_w), p.Wr - 1);
-            rrow = ((long long)f * p.Hr + sh) * p.Wr + sw;
-          }
+          if (p.res_mode == MCG_RES_UPSAMPLE_ADD) rrow = nearest_src_row(m, HoWo, p.Wo, p.Hr, p.Wr, p.rscale_h, p.rscale_w);
           float rv[EPC];
           const uint4 rc = *(const uint4*)(R + rrow * p.res_row_stride + n);
           chunk_to_f32(rc, rv, (T*)nullptr);

@@ -182,11 +182,7 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, MINW) void igemm_dma_kernel
       rpre[q] = make_uint4(0, 0, 0, 0);
       if (has_res && m < p.M && n < p.Cout) {
         long long rrow = m;
-        if (p.res_mode == MCG_RES_UPSAMPLE_ADD) {
-          const int f = m / HoWo, rem = m - f * HoWo, ho = rem / p.Wo, wo = rem - ho * p.Wo;
-          const int sh = min((int)floorf(ho * p.rscale_h), p.Hr - 1), sw = min((int)floorf(wo * p.rscale_w), p.Wr - 1);
-          rrow = ((long long)f * p.Hr + sh) * p.Wr + sw;
-        }
+        if (p.res_mode == MCG_RES_UPSAMPLE_ADD) rrow = nearest_src_row(m, HoWo, p.Wo, p.Hr, p.Wr, p.rscale_h, p.rscale_w);
         rpre[q] = *(const uint4*)(R + rrow * p.res_row_stride + n);
       }
     }

@@ -19,16 +19,6 @@
 #pragma once
 #include "igemm_dma.hpp"
 
-// four f32 -> four bf16 (round to nearest even) with ReLU applied on the stored bf16 as a packed signed max (relu_chunk's form:
-// the bits the contraction kernel's epilogue produces)
-typedef short s16x4_hw __attribute__((ext_vector_type(4)));
-template <typename F>   // bf16_t or f16_t: both are sign-magnitude, the packed signed max clears exactly the negative values
-__device__ __forceinline__ uint2 relu_pack4(const float (&v)[4]) {
-  const uint2 o = make_uint2(H16<F>::pack2(v[0], v[1]), H16<F>::pack2(v[2], v[3]));
-  const s16x4_hw z4 = {0, 0, 0, 0};
-  return __builtin_bit_cast(uint2, __builtin_elementwise_max(__builtin_bit_cast(s16x4_hw, o), z4));
-}
-
 struct PwPairParams {
   const void* a1; int K1;                          // [M][K1] bf16, rows contiguous (conv2's output)
   const void* a2; int K2, stride2, H2, W2;         // optional second source (block 0: the downsample conv's input), NHWC [frames][H2][W2][K2]

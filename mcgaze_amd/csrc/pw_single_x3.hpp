@@ -25,20 +25,25 @@ struct PwBlockList {
 // rows 4 (t & 1) .. + 3 of block bl.list[t >> 1], tile row r = its pixel (r >> 3, r & 7).  Everything a pixel's value depends on -- its A
 // row, its residual row, the K order, the three-term order, the epilogue -- is the dense form's: which tile or workgroup computes a pixel
 // does not enter its bits.  Pixels of unlisted blocks are neither read nor written.
+template <int KS, int RES> using PwX3Layout = pwx::Layout<4, KS, 1, RES, 1>;   // one A tile: two would not leave room for two workgroups per CU
+// rows of a listed tile whose first pixel is org (tile_origin below; -1: the tile has no rows), in a map Wo pixels wide
+struct PwListedRows {
+  int org, Wo;
+  __device__ __forceinline__ int rows() const { return org >= 0 ? 32 : 0; }
+  __device__ __forceinline__ long long base() const { return 0; }
+  __device__ __forceinline__ int rel(int r) const { return org + (r >> 3) * Wo + (r & 7); }
+  __device__ __forceinline__ int pixel(int r) const { return rel(r); }
+  __device__ __forceinline__ bool has(int) const { return org >= 0; }
+};
 template <int KS, int RES, int NSPLIT, bool LISTED>
 __device__ __forceinline__ void pw_single_x3_body(const PwSingleParams& p, const PwBlockList& bl) {
-  constexpr int PX = 32, K = 16 * KS, N = 128, NF = N * NSPLIT, AROWB = 4 * K, YROWB = 4 * N, GROWB = 4 * NF, ACH = AROWB / 16, YCH = YROWB / 16;
-  constexpr int ABYTES = PX * AROWB, YBYTES = PX * YROWB;
-  constexpr int NYB = RES ? 2 : 1;
-  constexpr int AOFF = NYB * YBYTES;
-  constexpr int A_PIECES = ABYTES / 1024 / 4, Y_PIECES = YBYTES / 1024 / 4;
-  static_assert(ACH <= 64 && YCH <= 64 && A_PIECES >= 1 && Y_PIECES >= 1 && AOFF + ABYTES <= 80 * 1024, "tile geometry");
+  using L = PwX3Layout<KS, RES>;
+  constexpr int N = L::N, YBYTES = L::YBYTES;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63, px = lane & 31, half = lane >> 5;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int bid = blockIdx.x, nwalkers = gridDim.x / NSPLIT;
-  // ids 8 apart sit on the same XCD; many_slices (dynamic_layer: 256 slices): workgroup id = walker * NSPLIT + slice
-  const int nsp = p.many_slices ? bid % NSPLIT : (bid >> 3) % NSPLIT, walker = p.many_slices ? bid / NSPLIT : (bid / (8 * NSPLIT)) * 8 + (bid & 7);
+  const pwx::Place at = pwx::place<NSPLIT>(p.many_slices);   // dynamic_layer: 256 slices
+  const int nsp = at.nsp, walker = at.walker, nwalkers = at.nwalkers;
   int listed_tiles = 0;
   if constexpr (LISTED) {
     listed_tiles = 2 * __builtin_amdgcn_readfirstlane(*bl.count);
@@ -48,8 +53,6 @@ __device__ __forceinline__ void pw_single_x3_body(const PwSingleParams& p, const
   float4 breg[4];
 #pragma unroll
   for (int q = 0; q < 4; ++q) breg[q] = *(const float4*)(p.bias + nsp * N + wave * 32 + 8 * q + 4 * half);
-  auto a_off = [](int r, int chunk) { return r * AROWB + ((chunk ^ (r & (ACH >= 32 ? 31 : 15))) << 4); };
-  auto y_off = [](int r, int chunk) { return r * YROWB + ((chunk ^ (r & (YCH >= 32 ? 31 : 15))) << 4); };
   // weights of this wave's 32 channels, once per workgroup: split fragment-major [tile][K-step][high, low][lane][8] (packing.frag_major_split)
   uint4 w[KS][2];
   {
@@ -62,48 +65,19 @@ __device__ __forceinline__ void pw_single_x3_body(const PwSingleParams& p, const
   }
   const u32x4 srd_a = make_srd(p.a), srd_r = make_srd(RES ? p.res : p.a);
   const uint32_t lds_base = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
-  constexpr int A_LPR = ACH < 64 ? ACH : 64, Y_LPR = YCH < 64 ? YCH : 64;
-  constexpr int A_RPP = 64 / A_LPR, Y_RPP = 64 / Y_LPR;
-  const int ntiles = LISTED ? listed_tiles : (p.M + PX - 1) / PX;
-  // LISTED: pixel index of a tile's first pixel (uniform; -1 for an id outside the map: nothing read, nothing written), and of its row r
+  const int ntiles = LISTED ? listed_tiles : (p.M + L::PX - 1) / L::PX;
+  // LISTED: pixel index of a tile's first pixel (uniform; -1 for an id outside the map: nothing read, nothing written)
   auto tile_origin = [&](int tile) {
     const int blk = __builtin_amdgcn_readfirstlane(bl.list[tile >> 1]);
     if (blk < 0 || blk >= bl.nblk) return -1;
     const int f = blk / bl.bpf, rem = blk - f * bl.bpf, by = rem / bl.bxn, bx = rem - by * bl.bxn;
     return (f * p.Ho + by * 8 + (tile & 1) * 4) * p.Wo + bx * 8;
   };
-  auto listed_pixel = [&](int org, int r) { return org + (r >> 3) * p.Wo + (r & 7); };
-  auto issue_a = [&](int tile, int org) {
-    const int rows_left = LISTED ? (org >= 0 ? PX : 0) : p.M - tile * PX;
-    const uint32_t so = LISTED ? 0u : (uint32_t)tile * ABYTES;
-    static_for<A_PIECES>([&](auto jc) {
-      constexpr int J = decltype(jc)::value;
-      const int row = (wave * A_PIECES + J) * A_RPP + lane / A_LPR, pos = lane % A_LPR;
-      const uint32_t grow = LISTED ? (uint32_t)listed_pixel(org, row) : (uint32_t)row;   // M * AROWB fits the descriptor window (launcher)
-      const uint32_t vo = row < rows_left ? grow * AROWB + (uint32_t)((pos ^ (row & (ACH >= 32 ? 31 : 15))) << 4) : MCG_OOB_OFFSET;
-      lds_dma16<AOFF + J * 1024>(vo, srd_a, so, lds_base + wave * (A_PIECES * 1024));
-    });
+  auto rows = [&](int tile, int org) {
+    if constexpr (LISTED) return PwListedRows{org, p.Wo}; else return pwx::DenseRows{tile, p.M};
   };
-  const int HoWo = p.Ho * p.Wo;
-  auto issue_res = [&](int tile, int buf, int org) {
-    const int rows_left = LISTED ? (org >= 0 ? PX : 0) : p.M - tile * PX;
-    static_for<Y_PIECES>([&](auto jc) {
-      constexpr int J = decltype(jc)::value;
-      const int row = (wave * Y_PIECES + J) * Y_RPP + lane / Y_LPR, pos = lane % Y_LPR;
-      const int chunk = pos ^ (row & (YCH >= 32 ? 31 : 15));
-      uint32_t vo = MCG_OOB_OFFSET, so = 0;
-      if (RES == 1) {
-        so = (uint32_t)tile * (PX * GROWB) + nsp * YROWB;
-        if (row < rows_left) vo = (uint32_t)(row * GROWB + (chunk << 4));
-      } else if (row < rows_left) {   // nearest-upsample gather (torch: src = min(floor(dst * in / out), in - 1))
-        const int m = LISTED ? listed_pixel(org, row) : tile * PX + row;
-        const int f = m / HoWo, rem = m - f * HoWo, ho = rem / p.Wo, wo = rem - ho * p.Wo;
-        const int sh = min((int)floorf(ho * p.rscale_h), p.Hr - 1), sw = min((int)floorf(wo * p.rscale_w), p.Wr - 1);
-        vo = (uint32_t)((((long long)f * p.Hr + sh) * p.Wr + sw) * GROWB + nsp * YROWB + (chunk << 4));
-      }
-      lds_dma16<J * 1024>(vo, srd_r, so, lds_base + buf * YBYTES + wave * (Y_PIECES * 1024));
-    });
-  };
+  auto issue_a = [&](int tile, int org) { pwx::issue_a<L>(rows(tile, org), 0, srd_a, lds_base, wave, lane); };
+  auto issue_res = [&](int tile, int buf, int org) { pwx::issue_res<L, RES, NSPLIT>(rows(tile, org), buf, p, nsp, srd_r, lds_base, wave, lane); };
   int org = 0, org_next = 0;
   if (walker < ntiles) {
     if constexpr (LISTED) org = tile_origin(walker);
@@ -112,9 +86,8 @@ __device__ __forceinline__ void pw_single_x3_body(const PwSingleParams& p, const
   }
   int it = 0;
   for (int tile = walker; tile < ntiles; tile += nwalkers, ++it) {
-    const long long m0 = (long long)tile * PX;
     char* s_y = smem + (RES ? (it & 1) * YBYTES : 0);
-    const char* s_a = smem + AOFF;
+    const char* s_a = smem + L::AOFF;
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");           // this wave's pieces of the tile have landed (and its earlier stores left)
     __syncthreads();                                           // everyone's pieces landed; the other y buffer is free
     const bool more = tile + nwalkers < ntiles;
@@ -126,17 +99,17 @@ __device__ __forceinline__ void pw_single_x3_body(const PwSingleParams& p, const
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
       bf16x8 xh, xl;
-      split_f32x8(*(const uint4*)(s_a + a_off(px, 4 * ks + 2 * half)), *(const uint4*)(s_a + a_off(px, 4 * ks + 2 * half + 1)), xh, xl);
+      split_f32x8(*(const uint4*)(s_a + L::a_off(px, 4 * ks + 2 * half)), *(const uint4*)(s_a + L::a_off(px, 4 * ks + 2 * half + 1)), xh, xl);
       acc = x3_mfma(__builtin_bit_cast(bf16x8, w[ks][0]), xl, acc);   // activation low x weight high first: the contraction kernel's order
       acc = x3_mfma(__builtin_bit_cast(bf16x8, w[ks][1]), xh, acc);
       acc = x3_mfma(__builtin_bit_cast(bf16x8, w[ks][0]), xh, acc);
     }
     __syncthreads();                                           // the A tile has been consumed by every wave (and, RES == 0: the previous y tile is stored)
-    if (more) issue_a(tile + nwalkers, org_next);                        // single A tile (two would not leave room for two workgroups per CU): refilled under the epilogue
+    if (more) issue_a(tile + nwalkers, org_next);              // single A tile: refilled under the epilogue
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       const int c0 = wave * 32 + 8 * q + 4 * half;
-      char* slot = s_y + y_off(px, c0 >> 2);
+      char* slot = s_y + L::y_off(px, c0 >> 2);
       float4 v = make_float4(acc[4 * q] * wsc + breg[q].x, acc[4 * q + 1] * wsc + breg[q].y, acc[4 * q + 2] * wsc + breg[q].z, acc[4 * q + 3] * wsc + breg[q].w);
       if (RES) {
         const float4 rr = *(const float4*)slot;
@@ -146,14 +119,7 @@ __device__ __forceinline__ void pw_single_x3_body(const PwSingleParams& p, const
       *(float4*)slot = v;
     }
     __syncthreads();                                           // y tile complete
-    for (int idx = tid; idx < PX * YCH; idx += 256) {
-      const int r = idx / YCH, c = idx - r * YCH;
-      if constexpr (LISTED) {
-        if (org >= 0) *(uint4*)((float*)p.y + (long long)listed_pixel(org, r) * NF + nsp * N + c * 4) = *(const uint4*)(s_y + y_off(r, c));
-      } else {
-        if (m0 + r < p.M) *(uint4*)((float*)p.y + (m0 + r) * NF + nsp * N + c * 4) = *(const uint4*)(s_y + y_off(r, c));
-      }
-    }
+    pwx::store_tile<L, NSPLIT>(rows(tile, org), s_y, p.y, nsp, tid);
     if constexpr (LISTED) org = org_next;
   }
 }
@@ -174,25 +140,13 @@ static inline bool pw_single_x3_applicable(int K, int N, int res_mode, long long
 }
 template <int KS, int RES, int NSPLIT>
 static inline int launch_pw_single_x3_t(hipStream_t s, const PwSingleParams& p) {
-  constexpr int kLds = (RES ? 2 : 1) * 32 * 512 + 32 * 64 * KS;
-  int cus;
-  if (kernel_ready<pw_single_x3_kernel<KS, RES, NSPLIT>>(kLds, &cus)) return 1;
-  const int ntiles = (p.M + 31) / 32, unit = 8 * NSPLIT;
-  int wgs = 2 * cus / unit * unit;                              // two workgroups per CU, whole groups of NSPLIT slices x 8 XCDs
-  const int need = (ntiles + 7) / 8 * unit;
-  if (wgs < unit) wgs = unit;
-  hipLaunchKernelGGL((pw_single_x3_kernel<KS, RES, NSPLIT>), dim3(need < wgs ? need : wgs), dim3(256), kLds, s, p);
-  return hipGetLastError() == hipSuccess ? 0 : 1;
+  return pwx::launch<pw_single_x3_kernel<KS, RES, NSPLIT>, PwX3Layout<KS, RES>, NSPLIT>(s, (p.M + 31) / 32, p.many_slices, p);
 }
 static inline int launch_pw_single_x3(hipStream_t s, const PwSingleParams& p, int N, int res_mode) {
-  if (N == 256) {
-    if (res_mode == 0) return launch_pw_single_x3_t<16, 0, 2>(s, p);
-    if (res_mode == 1) return launch_pw_single_x3_t<16, 1, 2>(s, p);
-    return launch_pw_single_x3_t<16, 2, 2>(s, p);
-  }
-  if (res_mode == 0) return launch_pw_single_x3_t<16, 0, 8>(s, p);
-  if (res_mode == 1) return launch_pw_single_x3_t<16, 1, 8>(s, p);
-  return launch_pw_single_x3_t<16, 2, 8>(s, p);
+  return pwx::dispatch_res(res_mode, [&](auto rc) {
+    constexpr int RES = decltype(rc)::value;
+    return N == 256 ? launch_pw_single_x3_t<16, RES, 2>(s, p) : launch_pw_single_x3_t<16, RES, 8>(s, p);
+  });
 }
 
 // The list form serves the P2 lateral (256 -> 256 + upsampled residual) on maps of whole 8 x 8 blocks whose operands fit the descriptors
@@ -201,31 +155,15 @@ static inline bool pw_single_x3_blocks_applicable(int K, int N, int Ho, int Wo, 
 }
 // p as for launch_pw_single_x3(.., 256, 2) (M = frames * Ho * Wo); list / count: the blocks to compute; max_blocks = blocks of the map
 static inline int launch_pw_single_x3_blocks(hipStream_t s, const PwSingleParams& p, const int* list, const int* count, int max_blocks) {
-  constexpr int KS = 16, NSPLIT = 2, kLds = 2 * 32 * 512 + 32 * 64 * KS;
-  int cus;
-  if (kernel_ready<pw_single_x3_blocks_kernel<KS, NSPLIT>>(kLds, &cus)) return 1;
   PwBlockList bl;
   bl.list = list; bl.count = count; bl.bxn = p.Wo / 8; bl.bpf = (p.Ho / 8) * (p.Wo / 8); bl.nblk = max_blocks;
-  const int unit = 8 * NSPLIT;
-  int wgs = 2 * cus / unit * unit;                              // two workgroups per CU, whole groups of NSPLIT slices x 8 XCDs
-  const int need = (2 * max_blocks + 7) / 8 * unit;             // two tiles per block
-  if (wgs < unit) wgs = unit;
-  hipLaunchKernelGGL((pw_single_x3_blocks_kernel<KS, NSPLIT>), dim3(need < wgs ? need : wgs), dim3(256), kLds, s, p, bl);
-  return hipGetLastError() == hipSuccess ? 0 : 1;
+  return pwx::launch<pw_single_x3_blocks_kernel<16, 2>, PwX3Layout<16, 2>, 2>(s, 2 * max_blocks, 0, p, bl);   // two tiles per block
 }
 
 // DynamicConv's `dynamic_layer` for the f16x3 engine (transformer.py:1131-1134): y[M][32768] = x[M][256] . W^T + b on M = 1344 tokens,
 // 176 MB of f32 output: 256 slices of 128 columns, each slice's split weights resident in the registers of two workgroups that share
 // the token tiles (pw_single.hpp's launch_pw_dyn).  Bit-identical to the x3 contraction kernel.
 static inline int launch_pw_dyn_x3(hipStream_t s, PwSingleParams p) {
-  constexpr int KS = 16, NSPLIT = 256, kLds = 32 * 512 + 32 * 64 * KS;
-  int cus;
-  if (kernel_ready<pw_single_x3_kernel<KS, 0, NSPLIT>>(kLds, &cus)) return 1;
-  const int ntiles = (p.M + 31) / 32;
-  int walkers = 2 * cus / NSPLIT;                               // two workgroups per CU
-  if (walkers < 1) walkers = 1;
-  if (walkers > ntiles) walkers = ntiles;
   p.many_slices = 1;
-  hipLaunchKernelGGL((pw_single_x3_kernel<KS, 0, NSPLIT>), dim3(walkers * NSPLIT), dim3(256), kLds, s, p);
-  return hipGetLastError() == hipSuccess ? 0 : 1;
+  return launch_pw_single_x3_t<16, 0, 256>(s, p);
 }
