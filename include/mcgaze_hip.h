@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define MCG_ABI_VERSION 18
+#define MCG_ABI_VERSION 19
 
 enum { MCG_OK = 0, MCG_ERR_ARG = 1, MCG_ERR_HIP = 2, MCG_ERR_UNSUPPORTED = 3, MCG_ERR_WORKSPACE = 4 };
 /* MCG_F16X3: the parity-grade fast mode.  Activations, biases and every non-GEMM kernel are exactly those of MCG_F32 (4-byte
@@ -136,6 +136,38 @@ int mcg_bottleneck_x3(mcg_stream s, const float* x, const float* src2, const voi
 size_t mcg_conv3x3_wino_x3_weight_bytes(int Cin, int Cout, int g);
 int mcg_conv3x3_wino_x3(mcg_stream s, const float* x, const void* u, const float* bias, float* y, int frames, int H, int W,
                         int Cin, int Cout, int relu, int tile, float wscale, int g);
+
+/* The streaming 1x1 kernels as stand-alone operators (ABI 19; pw_single.hpp, pw_single_x3.hpp, pw_pair.hpp): the engine takes them from
+ * 64 Ki rows on and the decoder from 256 tokens on; these entries run the same launchers at ANY M >= 1, for tests and measurements.  They
+ * never fall back to another kernel: what the launchers do not dispatch is MCG_ERR_UNSUPPORTED.
+ *
+ * mcg_pointwise_stream: y [M][N] = [relu](a [M][K] . W^T + bias (+ res)), f32 accumulate, bias / residual / ReLU in f32, ONE store.
+ *   dt MCG_BF16 / MCG_F16: a, res, y 16-bit; wf = the fragment-major copy of W [N][K] (packing.py::frag_major; mcg_conv_weights.wf);
+ *     (K, N) = (512, 128) without a residual; (512, 256) with res_mode NONE or UPSAMPLE_ADD; (256, 256), (256, 1024), (128, 512) with
+ *     every res_mode.
+ *   dt MCG_F16X3: a, res, y f32; wf = frag_major_split of W pre-scaled by a power of two (packing.py::pow2_prescale), wscale its inverse
+ *     (0 = 1, unscaled); (K, N) = (256, 256), (256, 1024) with every res_mode.
+ *   res_mode MCG_RES_ADD: res [M][N].  MCG_RES_UPSAMPLE_ADD: M = frames * Ho * Wo and res [frames][Hr][Wr][N], gathered by
+ *     F.interpolate(mode='nearest')'s rule, per axis src = min(floor(dst * f32(in / out)), in - 1).  MCG_RES_NONE: res NULL; Ho .. Wr unread.
+ *   block_list / block_count (device; both or neither): MCG_F16X3, K = N = 256, UPSAMPLE_ADD, Ho and Wo multiples of 8 only -- the LIST form:
+ *     block_list holds *block_count ids of 8 x 8-pixel blocks, id = (frame * (Ho / 8) + block row) * (Wo / 8) + block column, in any order;
+ *     the pixels of the listed blocks are written, bit for bit as the dense form writes them, every other pixel of y is left alone and an id
+ *     outside [0, M / 64) is skipped (nothing read, nothing written).  block_list must hold at least *block_count entries.
+ *   Operands must fit the 2 GiB window of a DMA descriptor (M * max(K, N) and the residual's rows * N elements).
+ * mcg_pointwise_dyn: DynamicConv's dynamic_layer, y [M][32768] = a [M][256] . W^T + bias, by the decoder's two forms (128 slices of 256
+ *   columns for bf16 / fp16, 256 slices of 128 for MCG_F16X3); wf / wscale as above (the decoder itself hands MCG_SW_DYN_WF over unscaled).
+ * mcg_pointwise_pair: y [M][256] = relu([a1 | a2] . W3^T + b3 (+ res)) rounded ONCE to the 16-bit type, and z [M][C2] = relu(y . W1^T + b1)
+ *   from that ROUNDED y, rounded once (pw_pair.hpp; bf16 / fp16).  a1 [M][64]; a2 [M][64] with K2 = 64, or NULL with K2 = 0; res [M][256] or
+ *   NULL, only without a second source; w3f = frag_major of W3 [256][64 + K2], w1f of W1 [C2][256]; C2 = 64 or 128.
+ * grid_cap: 0 = the product's persistent grid.  Else a host-side limit on it, so that a small problem walks several tiles per workgroup:
+ *   mcg_pointwise_stream: at most grid_cap groups of 8 * (N / channels per workgroup) workgroups (8 walkers per channel slice and group);
+ *   mcg_pointwise_dyn: at most grid_cap walkers per channel slice; mcg_pointwise_pair: at most grid_cap workgroups.  No kernel reads it. */
+int mcg_pointwise_stream(mcg_stream s, mcg_dtype dt, const void* a, const void* wf, const float* bias, const void* res, void* y,
+                         int M, int K, int N, int relu, int res_mode, int Ho, int Wo, int Hr, int Wr, float wscale,
+                         const int* block_list, const int* block_count, int grid_cap);
+int mcg_pointwise_dyn(mcg_stream s, mcg_dtype dt, const void* a, const void* wf, const float* bias, void* y, int M, float wscale, int grid_cap);
+int mcg_pointwise_pair(mcg_stream s, mcg_dtype dt, const void* a1, const void* a2, const void* res, const void* w3f, const float* b3,
+                       void* y, const void* w1f, const float* b1, void* z, int M, int K2, int C2, int grid_cap);
 
 /* Stem: conv 7x7 s2 p3 (3->64) + BN + ReLU then max-pool 3x3 s2 p1 (resnet.py:636-639).
  * img is the reference's NCHW f32 frame tensor.  w_stem is the packed stem weight

@@ -612,6 +612,26 @@ extern "C" int mcg_stage_forward_ragged(mcg_stream s, mcg_dtype dt, const void* 
   return stage_forward_ctx((hipStream_t)s, dt, W, roi_feat, obj_in, boxes_in, N, ClipTable{clip_start, num_clips, max_clip_length}, obj_out, boxes_out,
                            cls_out, stds, ws, ws_bytes, McgCtx::from_flags(0, flags));
 }
+// `dynamic_layer`'s streaming kernels as a stand-alone operator, through this unit's own launchers (launch_pw_dyn / launch_pw_dyn_x3) at any M >= 1
+extern "C" int mcg_pointwise_dyn(mcg_stream s, mcg_dtype dt, const void* a, const void* wf, const float* bias, void* y, int M, float wscale,
+                                 int grid_cap) {
+  MCG_CHECK_ARG(a && wf && bias && y, "mcg_pointwise_dyn: null pointer");
+  MCG_CHECK_ARG(M > 0 && grid_cap >= 0, "mcg_pointwise_dyn: M must be positive and grid_cap >= 0 (M=%d grid_cap=%d)", M, grid_cap);
+  const bool x3 = dt == MCG_F16X3;
+  if (!(x3 || mcg_is16(dt)) || (long long)M * MCG_ELEM_BYTES(dt) * 256 >= MCG_DMA_MAX_BYTES) {   // the A rows travel through a DMA descriptor
+    mcg_set_error("mcg_pointwise_dyn: unsupported (dtype %d, M=%d): bf16 / fp16 / f16x3, M rows of 256 inputs below 2 GiB", (int)dt, M);
+    return MCG_ERR_UNSUPPORTED;
+  }
+  PwSingleParams pp;
+  memset(&pp, 0, sizeof(pp));
+  pp.a = a; pp.wf = wf; pp.bias = bias; pp.y = y; pp.M = M; pp.Ho = 1; pp.Wo = 1; pp.wscale = x3 ? wscale : 0.f;
+  if (x3 ? launch_pw_dyn_x3((hipStream_t)s, pp, grid_cap) : launch_pw_dyn((hipStream_t)s, pp, dt, grid_cap)) {
+    mcg_set_error("mcg_pointwise_dyn: launch failed");
+    return MCG_ERR_HIP;
+  }
+  return MCG_OK;
+}
+
 int stage_forward_ctx(hipStream_t s, mcg_dtype dt, const void* const W[MCG_SW_COUNT], const void* roi_feat, const void* obj_in,
                       const float* boxes_in, int N, const ClipTable& ct, void* obj_out, float* boxes_out, float* cls_out,
                       const float stds[4], void* ws, size_t ws_bytes, const McgCtx& ctx) {

@@ -806,6 +806,58 @@ extern "C" int mcg_conv3x3_wino_x3(mcg_stream s, const float* x, const void* u, 
   return MCG_OK;
 }
 
+// The streaming 1x1 kernels as stand-alone operators: the launchers' own dispatch tables at any M >= 1, never another kernel
+extern "C" int mcg_pointwise_stream(mcg_stream s, mcg_dtype dt, const void* a, const void* wf, const float* bias, const void* res, void* y,
+                                    int M, int K, int N, int relu, int res_mode, int Ho, int Wo, int Hr, int Wr, float wscale,
+                                    const int* block_list, const int* block_count, int grid_cap) {
+  MCG_CHECK_ARG(a && wf && bias && y, "mcg_pointwise_stream: null pointer");
+  MCG_CHECK_ARG(M > 0 && grid_cap >= 0, "mcg_pointwise_stream: M must be positive and grid_cap >= 0 (M=%d grid_cap=%d)", M, grid_cap);
+  MCG_CHECK_ARG(res_mode >= MCG_RES_NONE && res_mode <= MCG_RES_UPSAMPLE_ADD && (res != nullptr) == (res_mode != MCG_RES_NONE),
+                "mcg_pointwise_stream: res_mode %d needs %s residual", res_mode, res_mode == MCG_RES_NONE ? "no" : "a");
+  MCG_CHECK_ARG((block_list != nullptr) == (block_count != nullptr), "mcg_pointwise_stream: block_list and block_count come together");
+  const bool x3 = dt == MCG_F16X3, up = res_mode == MCG_RES_UPSAMPLE_ADD;
+  if (up) MCG_CHECK_ARG(Ho > 0 && Wo > 0 && Hr > 0 && Wr > 0 && M % ((long long)Ho * Wo) == 0,
+                        "mcg_pointwise_stream: upsample residual: M = frames * Ho * Wo (M=%d, %dx%d from %dx%d)", M, Ho, Wo, Hr, Wr);
+  const long long res_rows = up ? M / ((long long)Ho * Wo) * Hr * Wr : M;
+  bool ok = x3 ? pw_single_x3_dispatched(K, N, M, res_rows) : mcg_is16(dt) && pw_single_dispatched(K, N, res_mode, M, res_rows);
+  if (block_list) ok = x3 && up && pw_single_x3_blocks_applicable(K, N, Ho, Wo, M, res_rows);
+  if (!ok) {
+    mcg_set_error("mcg_pointwise_stream: unsupported (dtype %d, %d -> %d channels, res_mode %d, M=%d%s): see include/mcgaze_hip.h for the table", (int)dt, K, N,
+                  res_mode, M, block_list ? ", block list" : "");
+    return MCG_ERR_UNSUPPORTED;
+  }
+  PwSingleParams pp;
+  memset(&pp, 0, sizeof(pp));
+  pp.a = a; pp.res = res; pp.wf = wf; pp.bias = bias; pp.y = y;
+  pp.M = M; pp.relu = relu; pp.Ho = up ? Ho : 1; pp.Wo = up ? Wo : 1; pp.wscale = x3 ? wscale : 0.f;
+  if (up) { pp.Hr = Hr; pp.Wr = Wr; pp.rscale_h = (float)Hr / (float)Ho; pp.rscale_w = (float)Wr / (float)Wo; }
+  const int rc = block_list ? launch_pw_single_x3_blocks((hipStream_t)s, pp, block_list, block_count, M / 64, grid_cap)
+                 : x3       ? launch_pw_single_x3((hipStream_t)s, pp, N, res_mode, grid_cap)
+                            : launch_pw_single((hipStream_t)s, pp, K, N, res_mode, dt, grid_cap);
+  if (rc) { mcg_set_error("mcg_pointwise_stream: launch failed"); return MCG_ERR_HIP; }
+  return MCG_OK;
+}
+
+extern "C" int mcg_pointwise_pair(mcg_stream s, mcg_dtype dt, const void* a1, const void* a2, const void* res, const void* w3f, const float* b3,
+                                  void* y, const void* w1f, const float* b1, void* z, int M, int K2, int C2, int grid_cap) {
+  MCG_CHECK_ARG(a1 && w3f && b3 && y && w1f && b1 && z, "mcg_pointwise_pair: null pointer");
+  MCG_CHECK_ARG(M > 0 && grid_cap >= 0, "mcg_pointwise_pair: M must be positive and grid_cap >= 0 (M=%d grid_cap=%d)", M, grid_cap);
+  MCG_CHECK_ARG((a2 != nullptr) == (K2 != 0), "mcg_pointwise_pair: a second source comes with K2 = 64, none with K2 = 0");
+  // the two-source form has ONE y tile (pw_pair.hpp): a residual's next tile would land in the tile being read
+  if (!mcg_is16(dt) || !pw_pair_applicable(64, K2, 1, 256, C2, M) || (K2 != 0 && res)) {
+    mcg_set_error("mcg_pointwise_pair: unsupported (dtype %d, K2=%d, C2=%d, M=%d%s): bf16 / fp16, K2 0 or 64, C2 64 or 128, a residual only without a second source",
+                  (int)dt, K2, C2, M, res ? ", residual" : "");
+    return MCG_ERR_UNSUPPORTED;
+  }
+  PwPairParams pp;
+  memset(&pp, 0, sizeof(pp));
+  pp.a1 = a1; pp.K1 = 64; pp.a2 = a2; pp.K2 = K2; pp.stride2 = 1; pp.res = res;
+  pp.w3f = w3f; pp.b3 = b3; pp.y = y; pp.w1f = w1f; pp.b1 = b1; pp.z = z;
+  pp.M = M; pp.C = 256; pp.C2 = C2; pp.Ho = 1; pp.Wo = M; pp.H2 = 1; pp.W2 = M;
+  if (launch_pw_pair((hipStream_t)s, pp, dt, grid_cap)) { mcg_set_error("mcg_pointwise_pair: launch failed"); return MCG_ERR_HIP; }
+  return MCG_OK;
+}
+
 extern "C" int mcg_backbone_fpn_forward(mcg_engine* e, mcg_stream s, const float* img, int N, int H, int W, int chunk,
                                         void* const pyramid[4], void* ws, size_t ws_bytes) {
   return trunk_forward(e, s, img, N, H, W, chunk, pyramid, ws, ws_bytes, false);

@@ -216,23 +216,24 @@ __global__ __launch_bounds__(256, 2) void pw_pair_kernel(const PwPairParams p) {
 static inline bool pw_pair_applicable(int K1, int K2, int stride2, int C, int C2, long long M) {
   return K1 == 64 && (K2 == 0 || (K2 == 64 && stride2 == 1)) && C == 256 && (C2 == 64 || C2 == 128) && M * 512 < MCG_DMA_MAX_BYTES;
 }
+// cap (0 = none): a host-side limit on the workgroups, for the stand-alone entry point (mcg_pointwise_pair); the engine passes 0
 template <typename F, int NSRC, int C2T>
-static inline int launch_pw_pair_t(hipStream_t s, const PwPairParams& p) {
+static inline int launch_pw_pair_t(hipStream_t s, const PwPairParams& p, int cap) {
   constexpr int kLds = (NSRC == 1 ? 2 * 64 * 512 + 64 * 128 : 64 * 512 + 2 * 2 * 64 * 128) + (256 + 128) * 4;
   int cus;
   if (kernel_ready<pw_pair_kernel<F, NSRC, C2T>>(kLds, &cus)) return 1;
   const int ntiles = (p.M + 63) / 64;
-  const int wgs = 2 * cus;                                     // two workgroups per CU (2 x 80 KiB of LDS fit exactly)
+  const int wgs = cap > 0 && cap < 2 * cus ? cap : 2 * cus;    // two workgroups per CU (2 x 80 KiB of LDS fit exactly)
   hipLaunchKernelGGL((pw_pair_kernel<F, NSRC, C2T>), dim3(ntiles < wgs ? ntiles : wgs), dim3(256), kLds, s, p);
   return hipGetLastError() == hipSuccess ? 0 : 1;
 }
 template <typename F>
-static inline int launch_pw_pair_f(hipStream_t s, const PwPairParams& p) {
-  if (p.K2 == 0 && p.C2 == 64) return launch_pw_pair_t<F, 1, 1>(s, p);
-  if (p.K2 == 0) return launch_pw_pair_t<F, 1, 2>(s, p);
-  if (p.C2 == 64) return launch_pw_pair_t<F, 2, 1>(s, p);
-  return launch_pw_pair_t<F, 2, 2>(s, p);
+static inline int launch_pw_pair_f(hipStream_t s, const PwPairParams& p, int cap) {
+  if (p.K2 == 0 && p.C2 == 64) return launch_pw_pair_t<F, 1, 1>(s, p, cap);
+  if (p.K2 == 0) return launch_pw_pair_t<F, 1, 2>(s, p, cap);
+  if (p.C2 == 64) return launch_pw_pair_t<F, 2, 1>(s, p, cap);
+  return launch_pw_pair_t<F, 2, 2>(s, p, cap);
 }
-static inline int launch_pw_pair(hipStream_t s, const PwPairParams& p, mcg_dtype dt) {
-  return dispatch_elem16(dt, [&](auto e) { return launch_pw_pair_f<decltype(e)>(s, p); });
+static inline int launch_pw_pair(hipStream_t s, const PwPairParams& p, mcg_dtype dt, int cap = 0) {
+  return dispatch_elem16(dt, [&](auto e) { return launch_pw_pair_f<decltype(e)>(s, p, cap); });
 }

@@ -123,24 +123,29 @@ __device__ __forceinline__ void store_tile(const Rows& t, const char* s_y, void*
   }
 }
 
-// Persistent grids.  Sliced: two workgroups per CU in whole groups of NSPLIT slices x 8 XCDs, no more groups than there are tiles
-static inline int sliced_grid(int cus, int ntiles, int nsplit) {
+// Persistent grids.  Sliced: two workgroups per CU in whole groups of NSPLIT slices x 8 XCDs, no more groups than there are tiles.
+// cap (here and below; 0 = none): a host-side limit for the stand-alone entry points (mcg_pointwise_*), which walk many tiles per workgroup
+// on a small problem with it; the engine and the decoder pass 0.  Sliced: at most cap groups
+static inline int sliced_grid(int cus, int ntiles, int nsplit, int cap = 0) {
   const int unit = 8 * nsplit, need = (ntiles + 7) / 8 * unit;
   int wgs = 2 * cus / unit * unit;
   if (wgs < unit) wgs = unit;
-  return need < wgs ? need : wgs;
+  if (need < wgs) wgs = need;
+  return cap > 0 && (long long)cap * unit < wgs ? cap * unit : wgs;
 }
-// many_slices: walkers per slice, two workgroups per CU (dynamic_layer's 128 slices: 4 walkers per slice on 256 CUs; 2, 3, 6, 8 measured slower)
-static inline int slice_walkers(int cus, int ntiles, int nsplit) {
-  const int walkers = 2 * cus / nsplit < 1 ? 1 : 2 * cus / nsplit;
-  return walkers > ntiles ? ntiles : walkers;
+// many_slices: walkers per slice, two workgroups per CU (dynamic_layer's 128 slices: 4 walkers per slice on 256 CUs; 2, 3, 6, 8 measured
+// slower); at most cap walkers
+static inline int slice_walkers(int cus, int ntiles, int nsplit, int cap = 0) {
+  int walkers = 2 * cus / nsplit < 1 ? 1 : 2 * cus / nsplit;
+  if (walkers > ntiles) walkers = ntiles;
+  return cap > 0 && cap < walkers ? cap : walkers;
 }
 // Kernel with layout L over ntiles tiles: dynamic LDS from the layout, the grid by the form the kernel will read in p.many_slices
 template <auto Kernel, typename L, int NSPLIT, typename... Args>
-static inline int launch(hipStream_t s, int ntiles, int many_slices, const Args&... args) {
+static inline int launch(hipStream_t s, int ntiles, int many_slices, int cap, const Args&... args) {
   int cus;
   if (kernel_ready<Kernel>(L::kLds, &cus)) return 1;
-  const int wgs = many_slices ? slice_walkers(cus, ntiles, NSPLIT) * NSPLIT : sliced_grid(cus, ntiles, NSPLIT);
+  const int wgs = many_slices ? slice_walkers(cus, ntiles, NSPLIT, cap) * NSPLIT : sliced_grid(cus, ntiles, NSPLIT, cap);
   hipLaunchKernelGGL(Kernel, dim3(wgs), dim3(256), L::kLds, s, args...);
   return hipGetLastError() == hipSuccess ? 0 : 1;
 }
@@ -240,29 +245,34 @@ __global__ __launch_bounds__(256, 2) void pw_single_kernel(const PwSingleParams 
   }
 }
 
-// (K, N) pairs of the R-50 trunk whose weights -- or a 128 / 256-channel slice of them -- fit the registers of one workgroup (128 KB)
-static inline bool pw_single_applicable(int K, int N, int res_mode, long long M, long long res_rows) {
+// (K, N) pairs of the R-50 trunk whose weights -- or a 128 / 256-channel slice of them -- fit the registers of one workgroup (128 KB):
+// what launch_pw_single_f dispatches, for any M >= 1 whose operands fit the DMA descriptors (mcg_pointwise_stream) ...
+static inline bool pw_single_dispatched(int K, int N, int res_mode, long long M, long long res_rows) {
   const bool shape = (K == 256 && N == 256) || (K == 512 && N == 128 && res_mode == 0) || (K == 128 && N == 512) ||
                      (K == 256 && N == 1024) || (K == 512 && N == 256 && res_mode != 1);
-  return shape && M >= 64 * 1024 && M * 2 * (K > N ? K : N) < MCG_DMA_MAX_BYTES && res_rows * 2 * N < MCG_DMA_MAX_BYTES;
+  return shape && M * 2 * (K > N ? K : N) < MCG_DMA_MAX_BYTES && res_rows * 2 * N < MCG_DMA_MAX_BYTES;
+}
+// ... and where the engine takes it: from 64 Ki rows on
+static inline bool pw_single_applicable(int K, int N, int res_mode, long long M, long long res_rows) {
+  return M >= 64 * 1024 && pw_single_dispatched(K, N, res_mode, M, res_rows);
 }
 template <typename F, int KS, int TPW, int RES, int NSPLIT>
-static inline int launch_pw_single_t(hipStream_t s, const PwSingleParams& p) {
-  return pwx::launch<pw_single_kernel<F, KS, TPW, RES, NSPLIT>, PwLayout<KS, TPW, RES>, NSPLIT>(s, (p.M + 31) / 32, p.many_slices, p);
+static inline int launch_pw_single_t(hipStream_t s, const PwSingleParams& p, int cap = 0) {
+  return pwx::launch<pw_single_kernel<F, KS, TPW, RES, NSPLIT>, PwLayout<KS, TPW, RES>, NSPLIT>(s, (p.M + 31) / 32, p.many_slices, cap, p);
 }
 template <typename F>
-static inline int launch_pw_single_f(hipStream_t s, const PwSingleParams& p, int K, int N, int res_mode) {
-  if (K == 512 && N == 128) return launch_pw_single_t<F, 32, 1, 0, 1>(s, p);
-  if (K == 512 && N == 256) return res_mode == 0 ? launch_pw_single_t<F, 32, 1, 0, 2>(s, p) : launch_pw_single_t<F, 32, 1, 2, 2>(s, p);
+static inline int launch_pw_single_f(hipStream_t s, const PwSingleParams& p, int K, int N, int res_mode, int cap) {
+  if (K == 512 && N == 128) return launch_pw_single_t<F, 32, 1, 0, 1>(s, p, cap);
+  if (K == 512 && N == 256) return res_mode == 0 ? launch_pw_single_t<F, 32, 1, 0, 2>(s, p, cap) : launch_pw_single_t<F, 32, 1, 2, 2>(s, p, cap);
   return pwx::dispatch_res(res_mode, [&](auto rc) {
     constexpr int RES = decltype(rc)::value;
-    if (K == 256 && N == 256) return launch_pw_single_t<F, 16, 2, RES, 1>(s, p);
-    if (K == 256 && N == 1024) return launch_pw_single_t<F, 16, 2, RES, 4>(s, p);
-    return launch_pw_single_t<F, 8, 4, RES, 1>(s, p);
+    if (K == 256 && N == 256) return launch_pw_single_t<F, 16, 2, RES, 1>(s, p, cap);
+    if (K == 256 && N == 1024) return launch_pw_single_t<F, 16, 2, RES, 4>(s, p, cap);
+    return launch_pw_single_t<F, 8, 4, RES, 1>(s, p, cap);
   });
 }
-static inline int launch_pw_single(hipStream_t s, const PwSingleParams& p, int K, int N, int res_mode, mcg_dtype dt) {
-  return dispatch_elem16(dt, [&](auto e) { return launch_pw_single_f<decltype(e)>(s, p, K, N, res_mode); });
+static inline int launch_pw_single(hipStream_t s, const PwSingleParams& p, int K, int N, int res_mode, mcg_dtype dt, int cap = 0) {
+  return dispatch_elem16(dt, [&](auto e) { return launch_pw_single_f<decltype(e)>(s, p, K, N, res_mode, cap); });
 }
 
 // DynamicConv's `dynamic_layer` (transformer.py:1131-1134): y[M][32768] = x[M][256] . W^T + b with FEW rows (1344 tokens at 64 clips) and
@@ -270,8 +280,8 @@ static inline int launch_pw_single(hipStream_t s, const PwSingleParams& p, int K
 // writes).  Here: 128 slices of 256 columns, each slice's weights resident in the registers of a few workgroups ("walkers") that
 // split the token tiles between them; the tokens (688 KB) stream out of L2.  Same arithmetic as every pw_single launch: bit-identical.
 static inline bool pw_dyn_applicable(int M) { return M >= 256 && (long long)M * 512 < MCG_DMA_MAX_BYTES; }
-static inline int launch_pw_dyn(hipStream_t s, const PwSingleParams& p, mcg_dtype dt) {
+static inline int launch_pw_dyn(hipStream_t s, const PwSingleParams& p, mcg_dtype dt, int cap = 0) {
   PwSingleParams q = p;
   q.many_slices = 1;
-  return dispatch_elem16(dt, [&](auto e) { return launch_pw_single_t<decltype(e), 16, 2, 0, 128>(s, q); });
+  return dispatch_elem16(dt, [&](auto e) { return launch_pw_single_t<decltype(e), 16, 2, 0, 128>(s, q, cap); });
 }

@@ -135,17 +135,22 @@ __global__ __launch_bounds__(256, 2) void pw_single_x3_blocks_kernel(const PwSin
 }
 
 // (K, N) of the f16x3 trunk served here: 256 -> 256 (P2 lateral) and 256 -> 1024 (layer3's conv3)
+// what launch_pw_single_x3 dispatches, for any M >= 1 whose operands fit the DMA descriptors (mcg_pointwise_stream) ...
+static inline bool pw_single_x3_dispatched(int K, int N, long long M, long long res_rows) {
+  return K == 256 && (N == 256 || N == 1024) && M * 4 * (K > N ? K : N) < MCG_DMA_MAX_BYTES && res_rows * 4 * N < MCG_DMA_MAX_BYTES;
+}
+// ... and where the engine takes it: from 64 Ki rows on
 static inline bool pw_single_x3_applicable(int K, int N, int res_mode, long long M, long long res_rows) {
-  return K == 256 && (N == 256 || N == 1024) && M >= 64 * 1024 && M * 4 * (K > N ? K : N) < MCG_DMA_MAX_BYTES && res_rows * 4 * N < MCG_DMA_MAX_BYTES;
+  return M >= 64 * 1024 && pw_single_x3_dispatched(K, N, M, res_rows);
 }
 template <int KS, int RES, int NSPLIT>
-static inline int launch_pw_single_x3_t(hipStream_t s, const PwSingleParams& p) {
-  return pwx::launch<pw_single_x3_kernel<KS, RES, NSPLIT>, PwX3Layout<KS, RES>, NSPLIT>(s, (p.M + 31) / 32, p.many_slices, p);
+static inline int launch_pw_single_x3_t(hipStream_t s, const PwSingleParams& p, int cap = 0) {
+  return pwx::launch<pw_single_x3_kernel<KS, RES, NSPLIT>, PwX3Layout<KS, RES>, NSPLIT>(s, (p.M + 31) / 32, p.many_slices, cap, p);
 }
-static inline int launch_pw_single_x3(hipStream_t s, const PwSingleParams& p, int N, int res_mode) {
+static inline int launch_pw_single_x3(hipStream_t s, const PwSingleParams& p, int N, int res_mode, int cap = 0) {
   return pwx::dispatch_res(res_mode, [&](auto rc) {
     constexpr int RES = decltype(rc)::value;
-    return N == 256 ? launch_pw_single_x3_t<16, RES, 2>(s, p) : launch_pw_single_x3_t<16, RES, 8>(s, p);
+    return N == 256 ? launch_pw_single_x3_t<16, RES, 2>(s, p, cap) : launch_pw_single_x3_t<16, RES, 8>(s, p, cap);
   });
 }
 
@@ -154,16 +159,16 @@ static inline bool pw_single_x3_blocks_applicable(int K, int N, int Ho, int Wo, 
   return K == 256 && N == 256 && Ho > 0 && Wo > 0 && Ho % 8 == 0 && Wo % 8 == 0 && M * 4 * K < MCG_DMA_MAX_BYTES && res_rows * 4 * N < MCG_DMA_MAX_BYTES;
 }
 // p as for launch_pw_single_x3(.., 256, 2) (M = frames * Ho * Wo); list / count: the blocks to compute; max_blocks = blocks of the map
-static inline int launch_pw_single_x3_blocks(hipStream_t s, const PwSingleParams& p, const int* list, const int* count, int max_blocks) {
+static inline int launch_pw_single_x3_blocks(hipStream_t s, const PwSingleParams& p, const int* list, const int* count, int max_blocks, int cap = 0) {
   PwBlockList bl;
   bl.list = list; bl.count = count; bl.bxn = p.Wo / 8; bl.bpf = (p.Ho / 8) * (p.Wo / 8); bl.nblk = max_blocks;
-  return pwx::launch<pw_single_x3_blocks_kernel<16, 2>, PwX3Layout<16, 2>, 2>(s, 2 * max_blocks, 0, p, bl);   // two tiles per block
+  return pwx::launch<pw_single_x3_blocks_kernel<16, 2>, PwX3Layout<16, 2>, 2>(s, 2 * max_blocks, 0, cap, p, bl);   // two tiles per block
 }
 
 // DynamicConv's `dynamic_layer` for the f16x3 engine (transformer.py:1131-1134): y[M][32768] = x[M][256] . W^T + b on M = 1344 tokens,
 // 176 MB of f32 output: 256 slices of 128 columns, each slice's split weights resident in the registers of two workgroups that share
 // the token tiles (pw_single.hpp's launch_pw_dyn).  Bit-identical to the x3 contraction kernel.
-static inline int launch_pw_dyn_x3(hipStream_t s, PwSingleParams p) {
+static inline int launch_pw_dyn_x3(hipStream_t s, PwSingleParams p, int cap = 0) {
   p.many_slices = 1;
-  return launch_pw_single_x3_t<16, 0, 256>(s, p);
+  return launch_pw_single_x3_t<16, 0, 256>(s, p, cap);
 }

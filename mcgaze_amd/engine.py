@@ -92,6 +92,69 @@ def conv2d(x, w, bias=None, stride=1, pad=0, relu=False, residual=None, residual
     return y
 
 
+def pointwise_weights(w, dtype, split=False, device='cuda'):
+    """W [N, K] -> (wf, wscale): the weight operand of the streaming 1x1 kernels (pointwise_stream / pointwise_pair).  16-bit ``dtype``:
+    packing.frag_major; split=True (MCG_F16X3): packing.frag_major_split of the pow2_prescale'd matrix and the descale factor."""
+    from .packing import frag_major, frag_major_split, pow2_prescale
+    if split:
+        ws, wscale = pow2_prescale(w.cpu())
+        return frag_major_split(ws).to(device), wscale
+    return frag_major(w.cpu().to(dtype)).contiguous().to(device), 0.0
+
+
+def _rows_out(out, M, N, dtype, device):
+    """The output [M, N]: fresh, or the first M rows of a caller's buffer (which may hold more rows: the tests' guard rows)."""
+    if out is None:
+        return torch.empty(M, N, dtype=dtype, device=device)
+    assert out.is_contiguous() and out.dtype == dtype and out.shape[0] >= M and tuple(out.shape[1:]) == (N,), (tuple(out.shape), M, N)
+    return out
+
+
+def pointwise_stream(a, wf, bias, N, relu=False, residual=None, residual_mode=L.RES_NONE, out_hw=None, split=False, wscale=0.0,
+                     many_slices=False, blocks=None, grid_cap=0, out=None):
+    """The streaming 1x1 kernels at any M (mcg_pointwise_stream; many_slices=True: dynamic_layer's forms, mcg_pointwise_dyn, N = 32768):
+    a [M, K] (16-bit, or f32 with split=True), wf / wscale from pointwise_weights, bias f32 [N] -> y [M, N].  residual [M, N] (RES_ADD) or
+    [frames, Hr, Wr, N] with out_hw = (Ho, Wo) and M = frames * Ho * Wo (RES_UPSAMPLE_ADD).  blocks: a sequence of 8 x 8 block ids -- the
+    list form, which writes the listed blocks only (give ``out``).  grid_cap: include/mcgaze_hip.h.  out: a buffer of at least M rows."""
+    _require_gpu()
+    lib = L.load()
+    M, K = a.shape
+    code = L.MCG_F16X3 if split else _code(a.dtype)
+    y = _rows_out(out, M, N, a.dtype, a.device)
+    a = a.contiguous()
+    if many_slices:
+        assert residual is None and blocks is None and N == 32768 and K == 256
+        L.check(lib.mcg_pointwise_dyn(_stream(), code, _ptr(a), _ptr(wf), _ptr(bias), _ptr(y), M, wscale, grid_cap), 'mcg_pointwise_dyn')
+        return y
+    mode = residual_mode if residual is not None else L.RES_NONE
+    Ho, Wo = out_hw if out_hw is not None else (1, M)
+    Hr, Wr = (residual.shape[1], residual.shape[2]) if mode == L.RES_UPSAMPLE_ADD else (Ho, Wo)
+    blist = bcount = None
+    if blocks is not None:
+        ids = _flat_ints(blocks, 'blocks must be a flat sequence', 'blocks must be integers', False)
+        blist = torch.zeros(max(len(ids), 1), dtype=torch.int32, device=a.device)
+        blist[:len(ids)] = torch.from_numpy(ids.astype(np.int32)).to(a.device)
+        bcount = torch.tensor([len(ids)], dtype=torch.int32, device=a.device)
+    L.check(lib.mcg_pointwise_stream(_stream(), code, _ptr(a), _ptr(wf), _ptr(bias), _ptr(residual.contiguous() if residual is not None else None),
+                                     _ptr(y), M, K, N, int(relu), mode, Ho, Wo, Hr, Wr, wscale, _ptr(blist), _ptr(bcount), grid_cap),
+            'mcg_pointwise_stream')
+    return y
+
+
+def pointwise_pair(a1, w3f, b3, w1f, b1, C2, a2=None, residual=None, grid_cap=0, out=None):
+    """pw_pair.hpp's kernel at any M (mcg_pointwise_pair): a1 [M, 64], a2 [M, 64] or None, residual [M, 256] or None (16-bit), w3f / w1f
+    from pointwise_weights (W3 [256, 64 (+ 64)], W1 [C2, 256]) -> (y [M, 256], z [M, C2]).  out: (y, z) buffers of at least M rows."""
+    _require_gpu()
+    lib = L.load()
+    M = a1.shape[0]
+    y = _rows_out(out[0] if out else None, M, 256, a1.dtype, a1.device)
+    z = _rows_out(out[1] if out else None, M, C2, a1.dtype, a1.device)
+    cont = lambda t: t.contiguous() if t is not None else None
+    L.check(lib.mcg_pointwise_pair(_stream(), _code(a1.dtype), _ptr(a1.contiguous()), _ptr(cont(a2)), _ptr(cont(residual)), _ptr(w3f), _ptr(b3),
+                                   _ptr(y), _ptr(w1f), _ptr(b1), _ptr(z), M, a2.shape[1] if a2 is not None else 0, C2, grid_cap), 'mcg_pointwise_pair')
+    return y, z
+
+
 def conv3x3_wino(x, w, bias=None, relu=False, tile=0, g=2):
     """3x3 / stride 1 / pad 1 conv by the 1-D Winograd F(2,3) kernel of the MCG_F16X3 engine (mcg_conv3x3_wino_x3, wino_x3.hpp):
     x NHWC f32, w OHWI f32 [Cout,3,3,Cin] (packed here by packing.wino_pack), bias f32 -> NHWC f32.  tile: 0 = by grid size, 1..4 forced

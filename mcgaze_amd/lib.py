@@ -11,7 +11,7 @@ LIB_PATH = os.environ.get('MCGAZE_LIB') or os.path.join(_HERE, 'libmcgaze_hip.so
 
 MCG_OK = 0
 MCG_F32, MCG_BF16, MCG_F16X3, MCG_F16 = 0, 1, 2, 3
-ABI_VERSION = 18
+ABI_VERSION = 19
 RES_NONE, RES_ADD, RES_UPSAMPLE_ADD = 0, 1, 2
 FLAG_STAGED_GEMM, FLAG_NO_SPECIALISED, FLAG_NO_ATTN_BLOCK = 1, 2, 4
 
@@ -38,7 +38,8 @@ EXPORTS = ['mcg_abi_version', 'mcg_build_id', 'mcg_last_error', 'mcg_device_info
            'mcg_preprocess_head_crops_nv12', 'mcg_draw_gaze_arrows', 'mcg_draw_gaze_arrows_nv12',
            'mcg_detect_heads_workspace_bytes', 'mcg_detect_heads', 'mcg_letterbox_frames', 'mcg_letterbox_frames_nv12',
            'mcg_track_state_bytes', 'mcg_track_heads', 'mcg_track_heads_motion', 'mcg_live_slots', 'mcg_live_gate', 'mcg_live_lanes', 'mcg_live_gate_lanes',
-           'mcg_deferred_pyramid_state', 'mcg_inner_block_neighbours', 'mcg_gaze_targets']
+           'mcg_deferred_pyramid_state', 'mcg_inner_block_neighbours', 'mcg_gaze_targets',
+           'mcg_pointwise_stream', 'mcg_pointwise_dyn', 'mcg_pointwise_pair']
 LETTERBOX_U8, LETTERBOX_F16, LETTERBOX_F32 = 0, 1, 2             # enum order of include/mcgaze_hip.h
 
 
@@ -193,6 +194,9 @@ def load():
     lib.mcg_bottleneck_x3.argtypes = [vp, vp, vp, vp, vp, vp, vp, i, i, i, i, i, i, vp]
     lib.mcg_conv3x3_wino_x3.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, i, i, i, C.c_float, i]
     lib.mcg_conv3x3_wino_x3_weight_bytes.restype = sz
+    lib.mcg_pointwise_stream.argtypes = [vp, i, vp, vp, vp, vp, vp, i, i, i, i, i, i, i, i, i, C.c_float, vp, vp, i]
+    lib.mcg_pointwise_dyn.argtypes = [vp, i, vp, vp, vp, vp, i, C.c_float, i]
+    lib.mcg_pointwise_pair.argtypes = [vp, i, vp, vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, i]
     lib.mcg_engine_range_audit.argtypes = [vp, C.POINTER(C.c_ulonglong), C.POINTER(C.c_char_p), i, C.POINTER(i)]
     lib.mcg_conv3x3_wino_x3_weight_bytes.argtypes = [i, i, i]
     for name in EXPORTS:

@@ -54,10 +54,23 @@ def _conv(x, w, stride=1, pad=0):
     return _integral(F.conv2d(x.double(), w.double(), stride=stride, padding=pad), 'conv')
 
 
-def upsample_nearest(r, size):
-    """F.interpolate(r, size=size, mode='nearest') in integer arithmetic: source index = floor(dst * in / out)."""
-    ih = (torch.arange(size[0]) * r.shape[2]) // size[0]
-    iw = (torch.arange(size[1]) * r.shape[3]) // size[1]
+def nearest_index(out, inn):
+    """The source index F.interpolate(mode='nearest') reads for each of ``out`` destinations of an axis of ``inn`` sources, by torch's own
+    rule on f32 tensors: min(floor(dst * scale), in - 1) with scale = in / out divided in f32 and the product rounded to f32
+    (include/mcgaze_hip.h; common.hpp: nearest_src_row).  It is NOT floor(dst * in / out) in integers: for out <= 64 the two part at (out,
+    in, dst) = (44, 26, 22), (46, 14, 23), (46, 28, 23), (58, 30, 29), where the rounded scale falls below in / out."""
+    scale = torch.tensor(float(inn), dtype=torch.float32) / torch.tensor(float(out), dtype=torch.float32)
+    return torch.floor(torch.arange(out, dtype=torch.float32) * scale).to(torch.int64).clamp_max(inn - 1)
+
+
+def nearest_index_integer(out, inn):
+    """MUTANT of ``nearest_index``: floor(dst * in / out) in integer arithmetic."""
+    return (torch.arange(out) * inn) // out
+
+
+def upsample_nearest(r, size, index=nearest_index):
+    """F.interpolate(r, size=size, mode='nearest') on integers: the gather by torch's index rule (``nearest_index``)."""
+    ih, iw = index(size[0], r.shape[2]), index(size[1], r.shape[3])
     return r[:, :, ih][:, :, :, iw]
 
 
