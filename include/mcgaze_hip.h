@@ -1030,10 +1030,73 @@ int mcg_live_gate_lanes(mcg_stream s, const int32_t* ring_id_dev, const float* r
  * whatever they hold nothing outside the given arrays is read or written.  Heads are searched in tiles of 256 rows and a tile whose
  * image_of range holds no picture a workgroup asks about is skipped: tables whose pictures come in ascending row order (LiveGaze's
  * [k, Q, S]) cost one picture per row.  mcgaze_amd/attention.py::gaze_targets_host is the same on the host, bit for bit.
- * Out of scope: dwell-time accumulation, camera intrinsics or depth, polygonal regions, arrows coloured or cut at the hit point. */
+ * Out of scope: camera intrinsics or depth, polygonal regions, arrows coloured or cut at the hit point.  (How long a target is looked at: "gaze
+ * dwell" below.) */
 int mcg_gaze_targets(mcg_stream s, const float* boxes_dev, const float* gaze_dev, int gaze_stride, const int32_t* image_of_dev, int n,
                      const float* regions_dev, const int32_t* region_image_dev, int m, int region_period, double expand, double camera_cos2,
                      int32_t* kind_dev, int32_t* target_dev, float* t_dev, float* hit_dev, int32_t* mutual_dev, int32_t* flags_dev);
+
+/* ---------------------------------------------------------------- gaze dwell (additions to ABI 19; nothing above changes)
+ * How long each person looks at what: the per-frame targets of mcg_gaze_targets, which flicker, become debounced EPISODES -- a target, a
+ * start, a length, an end and why it ended -- and every region collects its person-frames.  mcg_gaze_dwell walks F frames of R COLUMNS (a
+ * column is a tracker slot or a lane) in frame order, one thread per column, with a 16-word state record per column that the caller keeps
+ * between calls: the caller reads nothing back per tick and keeps no state per person.  A second launch compacts the episodes that ended
+ * into an event table.  No allocation, no host sync, graph-capturable; the result is a function of the inputs alone.
+ * ARITHMETIC.  Everything is int32.  Every sum below (`+=`, and n = frame0 + f) is computed UNSIGNED, modulo 2^32, and stored back as
+ * int32; the two comparisons `gap > exit` and `cand_frames >= enter` compare the stored int32 values, signed.  So whatever the tables
+ * and the state hold nothing overflows, and nothing outside the given arrays is read or written.
+ * INPUTS, each [F][R] int32; frame f has the number n = frame0 + f.
+ *   person   > 0: the id of the person with a usable result in that column and frame; <= 0: nobody
+ *   tag      the second half of the identity (ids are per camera: LiveGaze's lanes pass the ring column); NULL: all zero
+ *   kind, ident, mutual   what the person looks at: kind in mcg_gaze_targets' values, ident the identity of the target -- the Python
+ *            layer passes the looked-at person's track id for a head (stable over frames where the slot is not) and the region's index
+ *            for a region --, mutual as mcg_gaze_targets writes it
+ *   enter >= 1: the consecutive frames an observation must repeat before it becomes the current target;  exit >= 0: the consecutive
+ *   frames the current target may go unobserved before its episode ends.  (Python defaults 3 and 2: CONVENTIONS, not tuned on data.)
+ * OBSERVATION, normalised: a kind outside 1 .. 3 gives (k, i) = (0, 0); kind 3 gives (3, 0); otherwise (kind, ident).  m = 1 iff k == 1
+ * and mutual != 0, else 0.
+ * STATE, per column 16 int32 words, read and updated in place; all zero is the empty state:
+ *   0 person  1 tag  2 cur_kind  3 cur_ident  4 cur_start  5 cur_frames  6 cur_mutual  7 gap
+ *   8 cand_kind  9 cand_ident  10 cand_start  11 cand_frames  12 cand_mutual  13 seen  14, 15 reserved, written 0
+ * An episode that is still open is (words 0 .. 6) of a record whose cur_kind != 0: the kernel does not flush it, the layout is public.
+ * PER FRAME AND COLUMN, in this order.  END(reason) records (person, tag, cur_kind, cur_ident, cur_start, cur_frames, cur_mutual, reason)
+ * of the state as it stands, as this row of `ended`.
+ *   A. OWNER.  p = person > 0 ? person : 0;  g = p ? tag : 0.  If state.person != 0 and (state.person, state.tag) != (p, g): when
+ *      cur_kind != 0, END(2: the owner left); then all 16 words become zero.  If p == 0 the step is done: the row of `dwell` is zero
+ *      (the row of `ended` holds the END of the line before, if there was one).  Otherwise (state.person, state.tag) = (p, g).
+ *   B. seen += 1.  If k == 2 and 0 <= i < M: region_frames[i] += 1 -- RAW person-frames, before any debouncing; an integer atomic, so
+ *      the sum does not depend on the order; the index is range-checked before it is used.
+ *   C. CURRENT.  If cur_kind != 0: if (k, i) == (cur_kind, cur_ident): cur_frames += 1 + gap (the bridged frames count), gap = 0,
+ *      cur_mutual += m, and the five cand_ words become zero.  Otherwise gap += 1, and if gap > exit: END(1: looked away) -- cur_frames
+ *      as it stands, the trailing gap not counted --, then the five cur_ words and gap become zero.
+ *   D. CANDIDATE, unless C found the observation to be the current target.  If k == 0 the five cand_ words become zero.  Else if
+ *      (k, i) == (cand_kind, cand_ident): cand_frames += 1, cand_mutual += m.  Else the candidate becomes (k, i) with cand_start = n,
+ *      cand_frames = 1, cand_mutual = m.  Then, if cand_frames >= enter: when cur_kind != 0, END(3: replaced); the five cur_ words take
+ *      the five cand_ words, gap = 0, the five cand_ words become zero.
+ *   E. OUTPUTS.  dwell [F][R][4] = (cur_kind, cur_ident, cur_start, cur_frames) after the step (zero where p == 0);
+ *      ended [F][R][8] = the END of this step, else all zero.  A reason is never 0, so an END row is never all zero.
+ * AT MOST ONE END happens per row and frame: A zeroes the record, so C and D find cur_kind == 0 behind an END(2); C clears cur_kind
+ * with its END(1), so D's END(3), which needs cur_kind != 0, cannot follow it.
+ * EVENTS.  With events_dev given a second launch (one workgroup) compacts the non-zero rows of `ended` into events [E][10] = (frame
+ * number n, column, the 8 words), in ascending (frame, column) order -- ranks from ballots and prefix sums over ascending rows, never from
+ * timing.  num_events[0] = the number of non-zero rows of this call; rows beyond E are dropped and still counted, so the caller sees the
+ * overflow; rows of `events` behind the count are left as they were.  events_dev == NULL (then E must be 0) skips the launch and
+ * writes no count.
+ *   person_dev .. mutual_dev   DEVICE int32 [F][R], read only; tag_dev may be NULL
+ *   state_dev    DEVICE int32 [R][16], 16-byte aligned, updated in place
+ *   region_frames_dev   DEVICE int32 [M], accumulated in place; NULL iff M == 0
+ *   dwell_dev, ended_dev   DEVICE int32 [F][R][4] and [F][R][8], 16-byte aligned, written in full
+ *   events_dev, num_events_dev   DEVICE int32 [E][10] (8-byte aligned) and [1]; both or neither
+ * 1 <= R <= 4096, F >= 0 with F * R <= 65536 (F == 0 returns MCG_OK without a launch and writes nothing), 0 <= M <= 4096,
+ * 0 <= E <= 65536, frame0 >= 0, 1 <= enter <= 65536, 0 <= exit <= 65536.  A wrong count or parameter, a null pointer or a misaligned
+ * table returns MCG_ERR_ARG before any launch; the CONTENTS of the tables and of the state never are an error.
+ * mcgaze_amd/attention.py::gaze_dwell_host is the same on the host, bit for bit.
+ * Out of scope: dwell per polygonal region, camera intrinsics or depth, re-identifying a person who comes back after the tracker's
+ * max_age (a new id is a new owner). */
+int mcg_gaze_dwell(mcg_stream s, const int32_t* person_dev, const int32_t* tag_dev, const int32_t* kind_dev, const int32_t* ident_dev,
+                   const int32_t* mutual_dev, int num_frames, int columns, int frame0, int enter, int exit_frames, int32_t* state_dev,
+                   int32_t* region_frames_dev, int num_regions, int32_t* dwell_dev, int32_t* ended_dev, int32_t* events_dev, int max_events,
+                   int32_t* num_events_dev);
 
 /* ---------------------------------------------------------------- measurement aids (bench.py)
  * While armed, every launch of the contraction kernel made by THIS engine is bracketed by a hipEvent pair on its launch stream.

@@ -2,7 +2,12 @@
 rectangle, the lens or nothing.  ``gaze_targets_host`` is in numpy what ``DevicePipeline.gaze_targets`` (mcg_gaze_targets) writes on the
 device, bit for bit; it serves checks and users without a GPU.  The ray is the demo's arrow (MCGaze_demo/demo.ipynb, cell 5) followed until
 it meets something, in the image plane: no camera intrinsics, no depth.  The defaults (expand 0.25, a 10 degree cone for "the camera") are
-conventions, not tuned on data."""
+conventions, not tuned on data.
+
+Gaze dwell (include/mcgaze_hip.h, "gaze dwell"): how LONG each person looks at what.  ``gaze_dwell_host`` is in numpy what
+``DevicePipeline.gaze_dwell`` (mcg_gaze_dwell) writes on the device, bit for bit: the per-frame targets of the columns (tracker slots or
+lanes) become debounced episodes with a start, a length, an end and a reason, and every region collects its person-frames.  The defaults
+(enter 3, exit 2) are conventions, not tuned on data."""
 import math
 
 import numpy as np
@@ -186,3 +191,178 @@ def gaze_targets_host(boxes, gaze, image_of=None, regions=None, region_image=Non
     mutual[heads] = (kind[back] == KIND_HEAD) & (target[back] == heads)
     with np.errstate(over='ignore'):
         return kind, target, t_out.astype(np.float32), hit.astype(np.float32), mutual, flags
+
+
+# ---------------------------------------------------------------- gaze dwell (include/mcgaze_hip.h, "gaze dwell")
+DWELL_ENTER, DWELL_EXIT = 3, 2                                   # conventions, not tuned on data
+END_LOOKED_AWAY, END_OWNER_LEFT, END_REPLACED, END_VIDEO_ENDED = 1, 2, 3, 4      # 4 is given on the host only (run_head_video), never by the kernel
+END_NAMES = ('', 'looked_away', 'owner_left', 'replaced', 'video_ended')
+STATE_WORDS = ('person', 'tag', 'cur_kind', 'cur_ident', 'cur_start', 'cur_frames', 'cur_mutual', 'gap', 'cand_kind', 'cand_ident', 'cand_start',
+               'cand_frames', 'cand_mutual', 'seen', 'reserved0', 'reserved1')      # the 16 words of a column's state record, in order
+STATE_INDEX = {name: k for k, name in enumerate(STATE_WORDS)}
+DWELL_FIELDS = ('kind', 'ident', 'start', 'frames')              # the 4 words of a row of ``dwell``
+ENDED_FIELDS = ('person', 'tag', 'kind', 'ident', 'start', 'frames', 'mutual_frames', 'reason')      # the 8 words of a row of ``ended``
+EVENT_FIELDS = ('frame', 'column') + ENDED_FIELDS                # the 10 words of a row of ``events``
+MAX_COLUMNS, MAX_EVENTS, MAX_DWELL_FRAMES = 4096, 65536, 65536  # the bounds of mcg_gaze_dwell (rows and regions: MAX_ROWS, MAX_REGIONS)
+
+
+def _dwell_params(enter=DWELL_ENTER, exit=DWELL_EXIT, frame0=0, who='gaze_dwell'):
+    """The options, validated (ValueError) -> (enter, exit, frame0) as the entry takes them."""
+    for name, v, lo, hi in (('enter', enter, 1, MAX_DWELL_FRAMES), ('exit', exit, 0, MAX_DWELL_FRAMES), ('frame0', frame0, 0, 2 ** 31 - 1)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= v <= hi:
+            raise ValueError(f'{who}: {name} must be an int in {lo} .. {hi}, got {v!r}')
+    return int(enter), int(exit), int(frame0)
+
+
+def _dwell_options(who, dwell, attention):
+    """The ``dwell=`` option of LiveGaze and run_head_video, validated (ValueError) -> None (off) or dict(enter=, exit=).  dwell: None, True
+    or dict(enter=, exit=); it needs ``attention`` (the targets it accumulates)."""
+    if dwell is None:
+        return None
+    if dwell is not True and not isinstance(dwell, dict):
+        raise ValueError(f'{who}: dwell is None, True or a dict of enter and exit; got {dwell!r}')
+    if attention is None:
+        raise ValueError(f'{who}: dwell accumulates the targets of attention=...; give attention as well')
+    opts = {} if dwell is True else dict(dwell)
+    if set(opts) - {'enter', 'exit'}:
+        raise ValueError(f'{who}: dwell takes enter and exit; got {sorted(opts)}')
+    enter, exit, _ = _dwell_params(opts.get('enter', DWELL_ENTER), opts.get('exit', DWELL_EXIT), 0, f'{who}(dwell=...)')
+    return dict(enter=enter, exit=exit)
+
+
+def _dwell_counts(who, F, R, m, max_events):
+    """The counts of one call, checked (ValueError) -> max_events (None: F * R, every row can end an episode)."""
+    if not 1 <= R <= MAX_COLUMNS:
+        raise ValueError(f'{who}: 1 .. {MAX_COLUMNS} columns per call (got {R})')
+    if F * R > MAX_ROWS:
+        raise ValueError(f'{who}: frames x columns must not exceed {MAX_ROWS} per call (got {F} x {R})')
+    if m > MAX_REGIONS:
+        raise ValueError(f'{who}: at most {MAX_REGIONS} regions per call (got {m})')
+    if max_events is None:
+        return F * R
+    if isinstance(max_events, bool) or not isinstance(max_events, (int, np.integer)) or not 0 <= max_events <= MAX_EVENTS:
+        raise ValueError(f'{who}: max_events is None or an int in 0 .. {MAX_EVENTS}, got {max_events!r}')
+    return int(max_events)
+
+
+def _dwell_tables(who, person, kind, ident, mutual, tag):
+    """Host tables -> five int32 [F, R] arrays (tag None: zeros), checked (TypeError / ValueError)."""
+    out, shape = [], None
+    for name, t in (('person', person), ('kind', kind), ('ident', ident), ('mutual', mutual), ('tag', tag)):
+        if t is None and name == 'tag':
+            out.append(np.zeros(shape, np.int32))
+            continue
+        a = np.asarray(_host_array(t))
+        if a.dtype.kind not in 'iub':
+            raise TypeError(f'{who}: {name} must hold integers, got {a.dtype}')
+        if a.ndim != 2 or (shape is not None and a.shape != shape):
+            raise ValueError(f'{who}: person, kind, ident, mutual and tag are [F, R] tables of one shape; {name} is {a.shape}' +
+                             (f', person {shape}' if shape is not None else ''))
+        shape = a.shape
+        out.append(np.ascontiguousarray(a.astype(np.int32)))
+    return out
+
+
+def _dwell_events(ended, frame0, E):
+    """The rows of ended [F, R, 8] that are not all zero, in ascending (frame, column) -> (events [E, 10], num_events [1])."""
+    F, R = ended.shape[:2]
+    f, c = np.nonzero(ended.any(axis=2))                          # row-major: ascending (frame, column)
+    events = np.zeros((E, 10), np.int32)
+    keep = min(E, len(f))
+    events[:keep, 0] = ((frame0 + f[:keep].astype(np.int64)) & 0xffffffff).astype(np.uint32).view(np.int32)
+    events[:keep, 1] = c[:keep]
+    events[:keep, 2:] = ended[f[:keep], c[:keep]]
+    return events, np.asarray([len(f)], np.int32)
+
+
+def gaze_dwell_host(person, kind, ident, mutual, tag=None, state=None, frame0=0, enter=DWELL_ENTER, exit=DWELL_EXIT, region_frames=None,
+                    max_events=None):
+    """``mcg_gaze_dwell`` in numpy, bit for bit (include/mcgaze_hip.h, "gaze dwell"): the per-frame targets of F frames of R columns (a column
+    is a tracker slot or a lane) become debounced episodes, walked in frame order.
+
+    person [F, R]: > 0 the id of the person with a usable result there, <= 0 nobody; tag [F, R]: the second half of the identity (None:
+    zeros); kind, ident, mutual [F, R]: what the person looks at -- kind in gaze_targets' values, ident the looked-at person's track id for a
+    head and the region's index for a region.  state: int32 [R, 16] (STATE_WORDS), None: the empty state, all zero; it is NOT changed, the
+    updated copy is returned.  frame0: the number of frame 0.  enter: the consecutive frames an observation must repeat to become the
+    current target; exit: the consecutive frames the current target may go unobserved before its episode ends (the defaults, 3 and 2, are
+    conventions, not tuned on data).  region_frames: int32 [M] totals to add to (None: no regions).  max_events: the rows of the event table
+    (None: F * R).
+    -> (dwell int32 [F, R, 4] = DWELL_FIELDS after every frame, ended int32 [F, R, 8] = ENDED_FIELDS of the episode that ended there, else
+    zero, events int32 [max_events, 10] = EVENT_FIELDS in ascending (frame, column), rows behind the count zero, num_events int32 [1]: the
+    episodes that ended in this call, those beyond max_events included, state int32 [R, 16], region_frames int32 [M])."""
+    who = 'gaze_dwell_host'
+    enter, exit, frame0 = _dwell_params(enter, exit, frame0, who)
+    P, K, I, MU, T = _dwell_tables(who, person, kind, ident, mutual, tag)
+    F, R = P.shape
+    rf = np.zeros(0, np.int32) if region_frames is None else np.array(_host_array(region_frames), dtype=np.int32).reshape(-1)
+    E = _dwell_counts(who, F, R, len(rf), max_events)
+    M = len(rf)
+    if state is None:
+        s = np.zeros((R, 16), np.int32)
+    else:
+        s = np.asarray(_host_array(state))
+        if s.shape != (R, 16) or s.dtype.kind not in 'iu':
+            raise ValueError(f'{who}: the state is an integer [{R}, 16] table, got {s.dtype} {s.shape}')
+        s = np.array(s, dtype=np.int32)
+    u, rfu = s.view(np.uint32), rf.view(np.uint32)               # every sum is unsigned, modulo 2^32; every comparison reads the int32
+    dwell, ended = np.zeros((F, R, 4), np.int32), np.zeros((F, R, 8), np.int32)
+    one = np.uint32(1)
+    for f in range(F):
+        n = np.asarray([(frame0 + f) & 0xffffffff], np.uint32).view(np.int32)[0]
+        p = np.where(P[f] > 0, P[f], 0)
+        g = np.where(p != 0, T[f], 0)
+        k = np.where((K[f] >= 1) & (K[f] <= 3), K[f], 0)
+        i = np.where((k == 1) | (k == 2), I[f], 0)
+        m = ((k == 1) & (MU[f] != 0)).astype(np.uint32)
+        e = ended[f]
+
+        def end(rows, reason):
+            e[rows, :7] = s[rows, :7]                             # person, tag, cur_kind, cur_ident, cur_start, cur_frames, cur_mutual
+            e[rows, 7] = reason
+
+        # A. owner
+        left = (s[:, 0] != 0) & ((s[:, 0] != p) | (s[:, 1] != g))
+        end(left & (s[:, 2] != 0), END_OWNER_LEFT)
+        s[left] = 0
+        live = p != 0
+        s[live, 0], s[live, 1] = p[live], g[live]
+        # B. raw person-frames
+        u[live, 13] += one
+        hit = live & (k == 2) & (i >= 0) & (i < M)
+        np.add.at(rfu, i[hit], one)
+        # C. the current target
+        has = live & (s[:, 2] != 0)
+        same = has & (k == s[:, 2]) & (i == s[:, 3])
+        u[same, 5] += one + u[same, 7]
+        s[same, 7] = 0
+        u[same, 6] += m[same]
+        s[same, 8:13] = 0
+        other = has & ~same
+        u[other, 7] += one
+        away = other & (s[:, 7] > exit)
+        end(away, END_LOOKED_AWAY)
+        s[away, 2:8] = 0
+        # D. the candidate
+        d = live & ~same
+        s[d & (k == 0), 8:13] = 0
+        cont = d & (k != 0) & (k == s[:, 8]) & (i == s[:, 9])
+        fresh = d & (k != 0) & ~cont
+        u[cont, 11] += one
+        u[cont, 12] += m[cont]
+        s[fresh, 8], s[fresh, 9], s[fresh, 10], s[fresh, 11], u[fresh, 12] = k[fresh], i[fresh], n, 1, m[fresh]
+        prom = d & (s[:, 11] >= enter)
+        end(prom & (s[:, 2] != 0), END_REPLACED)
+        s[prom, 2:7] = s[prom, 8:13]
+        s[prom, 7] = 0
+        s[prom, 8:13] = 0
+        # E. outputs
+        dwell[f] = np.where(live[:, None], s[:, 2:6], 0)
+    events, num = _dwell_events(ended, frame0, E)
+    return dwell, ended, events, num, s, rf
+
+
+def open_episodes(state):
+    """The episodes still open in a state [R, 16] -> (columns, rows [len, 7] = the first seven ENDED_FIELDS), in ascending column."""
+    s = np.asarray(_host_array(state)).reshape(-1, 16)
+    cols = np.flatnonzero((s[:, 0] != 0) & (s[:, 2] != 0))
+    return cols, s[cols, :7]

@@ -20,6 +20,9 @@ RULES = {
     # no hand-issued loads, but a double-precision row walk that is meant to live in registers: scratch would be a cost nobody looks for
     'gaze_targets_kernel': dict(scratch=0, vgpr_spill=0, unit='attend'),
     'gaze_mutual_kernel': dict(scratch=0, vgpr_spill=0, unit='attend'),
+    # the 16 state words of a column are meant to stay in registers across the frame loop
+    'gaze_dwell_kernel': dict(scratch=0, vgpr_spill=0, unit='dwell'),
+    'gaze_dwell_events_kernel': dict(scratch=0, vgpr_spill=0, unit='dwell'),
 }
 
 

@@ -20,7 +20,7 @@ import os
 import numpy as np
 import torch
 
-from .attention import _attention_options
+from .attention import END_VIDEO_ENDED, KIND_HEAD, KIND_REGION, MAX_COLUMNS, MAX_ROWS, _attention_options, _dwell_options, open_episodes
 from .engine import _upload_table
 from .pipeline import ARROW_COLOR, _track_motion, _track_params, letterbox_geometry
 
@@ -798,8 +798,64 @@ def _add_targets(records, pipeline, device, num_frames, gaze_key, regions, regio
                 rec['target_region'][j] = target[i]
 
 
+def _dwell_episodes(events, state, columns, id_of):
+    """The episodes of every column, in the order they began: the rows of an event table [n, 10] (attention.EVENT_FIELDS, ascending frames),
+    then the one still open in the column's state [columns, 16], with reason END_VIDEO_ENDED.  id_of(ident): the ``id`` of the record a
+    head's ident names.  -> ``columns`` lists of dict(kind, target_id | target_region, start, frames, mutual_frames, reason)."""
+    out = [[] for _ in range(columns)]
+
+    def episode(kind, ident, start, frames, mutual, reason):
+        target = dict(target_id=id_of(int(ident))) if kind == KIND_HEAD else dict(target_region=int(ident)) if kind == KIND_REGION else {}
+        return dict(kind=int(kind), **target, start=int(start), frames=int(frames), mutual_frames=int(mutual), reason=int(reason))
+
+    for row in np.asarray(events).reshape(-1, 10):
+        out[int(row[1])].append(episode(*row[4:10]))
+    cols, rows = open_episodes(state)
+    for c, row in zip(cols, rows):
+        out[int(c)].append(episode(*row[2:7], END_VIDEO_ENDED))
+    return out
+
+
+def _dwell_tables(records, num_frames):
+    """run_head_video(dwell=...): the [T, R] tables of pipeline.gaze_dwell from records that hold their targets -- a column per record, whose
+    person is its index + 1 in the frames it has; a head's ident is the looked-at record's index + 1, a region's its index."""
+    R = len(records)
+    person, kind, ident, mutual = (np.zeros((num_frames, R), np.int32) for _ in range(4))
+    index = {rec['id']: r for r, rec in enumerate(records)}
+    for r, rec in enumerate(records):
+        t = np.asarray(rec['frame_id'], dtype=np.int64)
+        person[t, r], kind[t, r], mutual[t, r] = r + 1, rec['target_kind'], rec['mutual']
+        ident[t, r] = [index[tid] + 1 if k == KIND_HEAD else reg for k, tid, reg in zip(rec['target_kind'], rec['target_id'], rec['target_region'])]
+    return person, kind, ident, mutual
+
+
+def _add_dwell(records, pipeline, device, num_frames, options):
+    """run_head_video(dwell=...): how long every record looks at what, MAX_ROWS // R frames at most per pipeline.gaze_dwell call with the
+    state carried from call to call (host tables up through the staging ring, dwell and the ended episodes read back), written into the
+    records; the episodes still open at the last frame are taken from the state, with reason END_VIDEO_ENDED."""
+    R = len(records)
+    if R > MAX_COLUMNS:
+        raise ValueError(f'run_head_video(dwell=...): at most {MAX_COLUMNS} records (got {R})')
+    for rec in records:
+        rec.update(dwell_kind=np.zeros(len(rec['frame_id']), np.int32), dwell_frames=np.zeros(len(rec['frame_id']), np.int32), episodes=[])
+    if R == 0 or num_frames == 0:
+        return
+    tables = _dwell_tables(records, num_frames)
+    state, events, dwell = None, [], []
+    for t0 in range(0, num_frames, MAX_ROWS // R):
+        got = pipeline.gaze_dwell(*(t[t0:t0 + MAX_ROWS // R] for t in tables), state=state, frame0=t0, device=device, **options)
+        state = got[4]
+        dwell.append(_host(got[0]))
+        events.append(_host(got[2])[:int(_host(got[3])[0])])
+    dwell = np.concatenate(dwell)
+    episodes = _dwell_episodes(np.concatenate(events), _host(state), R, lambda ident: records[ident - 1]['id'])
+    for r, rec in enumerate(records):
+        t = np.asarray(rec['frame_id'], dtype=np.int64)
+        rec['dwell_kind'], rec['dwell_frames'], rec['episodes'] = dwell[t, r, 0], dwell[t, r, 3], episodes[r]
+
+
 def run_head_video(engine, pipeline, frames, boxes_per_frame=None, max_len=100, batch_frames=448, expand=0.8, rgb=False, smooth=None, pixel_format='bgr',
-                   matrix='bt601', detections=None, track=None, attention=None, draw=None):
+                   matrix='bt601', detections=None, track=None, attention=None, dwell=None, draw=None):
     """Steps 3-4 of the demo from what its users hold -- the video's frames and one head box per person per frame -- to per-person gaze:
     segment_tracks (cell 1), the head windows cut, resized and normalised on the device (pipeline.head_crops: cell 4's crop arithmetic and
     ``cfg.data.test.pipeline[1:]``), run_tracks (cell 4's loop, batched), head_arrows (cell 5's end points).
@@ -846,9 +902,18 @@ def run_head_video(engine, pipeline, frames, boxes_per_frame=None, max_len=100, 
     KIND_REGION / KIND_CAMERA), target_id (a list: the ``id`` of the record of the person looked at, else None), target_region int32 [L] (the
     index into regions, else -1), target_hit f32 [L,2] (where the ray from the head's centre enters the target, in frame pixels) and mutual
     int32 [L] (the two look at each other).  The regions apply to every frame.  Decided in the image plane; expand and camera_angle are
-    conventions, not tuned on data."""
+    conventions, not tuned on data.
+    dwell: None (everything above), True, or dict(enter=3, exit=2); it needs ``attention`` (ValueError without): how LONG every person looks at
+    what (pipeline.gaze_dwell, mcg_gaze_dwell; include/mcgaze_hip.h, "gaze dwell").  The columns are the records; the frames go in chunks of
+    at most 65536 // records with the state carried between them.  Every record gains, per frame, dwell_kind and dwell_frames int32 [L] (the
+    current target after that frame and its frames so far: a look becomes current after ``enter`` consecutive frames and ends after
+    ``exit`` consecutive frames without it -- conventions, not tuned on data) and ``episodes``: a list of dict(kind, target_id (a head: the
+    ``id`` of that person's record) or target_region, start, frames, mutual_frames, reason (attention.END_LOOKED_AWAY / END_OWNER_LEFT /
+    END_REPLACED; END_VIDEO_ENDED for the episode still open at the last frame, which is appended from the state on the host)), in the order
+    they began."""
     smooth = check_smooth('run_head_video', smooth)
     attention = _attention_options('run_head_video', attention)
+    dwell = _dwell_options('run_head_video', dwell, attention)
     if (boxes_per_frame is None) == (detections is None):
         raise ValueError('run_head_video: give exactly one of boxes_per_frame and detections')
     tracker = None if track is None else _HeadTracker(pipeline, track, engine.device)
@@ -922,6 +987,8 @@ def run_head_video(engine, pipeline, frames, boxes_per_frame=None, max_len=100, 
                             arrow=head_arrows(person, rec['fused' if smooth is None else 'fused_smooth'])))
     if attention is not None:
         _add_targets(out, pipeline, engine.device, len(boxes_per_frame), 'fused' if smooth is None else 'fused_smooth', *attention)
+    if dwell is not None:
+        _add_dwell(out, pipeline, engine.device, len(boxes_per_frame), dwell)
     if draw is None:
         return out
     opts = {'copy': True, **({} if draw is True else dict(draw))}

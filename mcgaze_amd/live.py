@@ -30,7 +30,7 @@ import numpy as np
 import torch
 
 from . import lib as L
-from .attention import KIND_HEAD, _attention_options
+from .attention import KIND_HEAD, _attention_options, _dwell_options
 from .engine import _upload_table
 from .harness import _host, check_smooth
 from .head_detect import TRACK_HEADER_WORDS, TRACK_MAX_SLOTS, TRACK_SLOT_WORDS, _track_motion, _track_params, track_state_words
@@ -330,11 +330,23 @@ class LiveGaze:
     mutual (the two look at each other), shaped like track_id.  regions: a list of Q tables [m_q, 4] of rectangles x1 y1 x2 y2 in frame
     pixels, one per camera (None: none there), uploaded once; a region's index counts through the cameras' tables in order.  Targets are
     decided in the image plane, and expand / camera_angle are conventions, not tuned on data.  Still no wait for the device, no copy to the
-    host."""
+    host.
+
+    DWELL.  ``dwell=None`` is everything above.  ``dwell=True`` or ``dict(enter=3, exit=2)`` (it needs ``attention``; ValueError without) adds how
+    LONG every row has looked at its target (pipeline.gaze_dwell, mcg_gaze_dwell: one call per tick that returns frames, over the k frames
+    handed out, frame0 = first).  A column is a slot or a lane; its owner is person = track_id where valid, else 0, with lanes tagged by the
+    ring column camera * S + slot (ids are per camera); the target's identity is target_id for a head and the region's index for a region.
+    An observation becomes the current target after ``enter`` consecutive frames and its episode ends after ``exit`` consecutive frames
+    without it (conventions, not tuned on data).  The result gains dwell_kind, dwell_id, dwell_start, dwell_frames, shaped like track_id
+    (the current target after each frame: its kind, its identity, the frame it began in, its frames so far), ``episodes`` [k * columns, 10]
+    int32 (attention.EVENT_FIELDS: the episodes that ENDED in these frames, in ascending (frame, column); rows behind the count are zero) and
+    ``num_episodes`` int32 [1].  ``LiveGaze.region_frames`` holds the person-frames every region has collected so far, int32 [m] on the
+    device, and ``LiveGaze.dwell_state`` the state [columns, 16] (attention.STATE_WORDS): episodes still open -- after finish() too, which
+    adds nothing beyond its frames -- are read there.  Still no wait for the device, no copy to the host."""
 
     def __init__(self, engine_or_model, pipeline, cameras, slots=16, clip_len=7, stride=4, expand=0.8, match_iou=0.3, max_age=5, smooth=None,
                  pixel_format='bgr', draw=False, matrix='bt601', rgb=False, person_threshold=0.5, max_decode_windows=None, lanes=None, motion=None,
-                 attention=None):
+                 attention=None, dwell=None):
         self.S, self.match_iou, self.max_age = _track_params(slots, match_iou, max_age)
         _track_motion(motion, 'LiveGaze')
         self.motion = motion
@@ -345,6 +357,7 @@ class LiveGaze:
         self.Q, self.T, self.s = int(cameras), int(clip_len), int(stride)
         self.smooth = check_smooth('LiveGaze', smooth)
         attention = _attention_options('LiveGaze', attention, self.Q)
+        self.dwell = _dwell_options('LiveGaze', dwell, attention)
         self.pipe, self.expand, self.draw = pipeline, float(expand), bool(draw)
         self.frame_options = dict(pixel_format=pixel_format, matrix=matrix)
         self.rgb = bool(rgb)
@@ -372,6 +385,8 @@ class LiveGaze:
         if attention is not None:                                # the regions go up once: region_image = camera, matched through region_period = Q
             regions, region_image, options = attention
             self.attention = dict(options, regions=torch.from_numpy(regions).to(self.dev), region_image=torch.from_numpy(region_image).to(self.dev))
+        if self.dwell is not None:
+            self.dwell_state, self.region_frames = pipeline.dwell_state(n, device=self.dev), new(len(attention[0]))
 
     def _call(self, name, *args):
         """One entry of the library on the current stream: a tensor goes as its address, None as a null pointer, an int as it is."""
@@ -419,6 +434,20 @@ class LiveGaze:
             kind, target, target_id, mutual, t, hit = new(0), new(0), new(0), new(0), new(0, dtype=torch.float32), new(0, 2, dtype=torch.float32)
         return dict(target_kind=kind.view(k, *lead), target=target.view(k, *lead), target_id=target_id.view(k, *lead), target_t=t.view(k, *lead),
                     target_hit=hit.view(k, *lead, 2), mutual=mutual.view(k, *lead))
+
+    def _dwell(self, out, k):
+        """dwell=: the targets of the k frames handed out, accumulated into dwell_state and region_frames -> the tables _emit adds."""
+        lead = self.lead
+        rows = lambda t: t.reshape(k, len(self.sids))             # (k may be 0)
+        person = torch.where(out['valid'] != 0, out['track_id'], torch.zeros_like(out['track_id']))
+        tag = None if self.P is None else rows(out['camera'] * self.S + out['slot'])
+        ident = torch.where(out['target_kind'] == KIND_HEAD, out['target_id'], out['target'])
+        dwell, _, events, num, _, _ = self.pipe.gaze_dwell(rows(person), rows(out['target_kind']), rows(ident), rows(out['mutual']), tag=tag,
+                                                           state=self.dwell_state, frame0=self.emitted, region_frames=self.region_frames,
+                                                           device=self.dev, **self.dwell)
+        dwell = dwell.view(k, *lead, 4)
+        return dict(dwell_kind=dwell[..., 0], dwell_id=dwell[..., 1], dwell_start=dwell[..., 2], dwell_frames=dwell[..., 3], episodes=events,
+                    num_episodes=num)
 
     def tick(self, frames, boxes, counts):
         """One frame per camera and its detections -> the frames that became final (see the class)."""
@@ -481,6 +510,8 @@ class LiveGaze:
             self.windows = [w for w in self.windows if w[1] > self.emitted + k - 1]     # the next call's first neighbour is the last frame of this
         if self.attention is not None:
             out.update(self._targets(out, k))
+        if self.dwell is not None:
+            out.update(self._dwell(out, k))
         if self.draw:
             images = [f for t in range(self.emitted, self.emitted + k) for f in self.kept.pop(t)]
             if k:

@@ -37,6 +37,7 @@ from .arrows import (ARROW_COLOR, ARROW_COORD, ARROW_SIDE, _arrow_colors, _arrow
                      arrow_segments, draw_arrows_host, segment_coverage)
 from .attention import _check_counts, _region_tables, _target_params, gaze_targets_host  # noqa: F401
 from .attention import _row_tables as _target_rows
+from .attention import DWELL_ENTER, DWELL_EXIT, _dwell_counts, _dwell_params, _dwell_tables, gaze_dwell_host  # noqa: F401
 from .frame_cache import FrameCache, _DecodeProcs, decode_image  # noqa: F401
 from .head_detect import (DETECT_MAX_DET, LETTERBOX_PAD, LetterboxGeometry, _detect_params, _detect_shapes, _letterbox_dtype,  # noqa: F401
                           _letterbox_plan, _track_motion, _track_params, _track_shapes, detect_heads_host, letterbox_geometry, letterbox_host, track_heads_host,
@@ -788,6 +789,82 @@ class DevicePipeline:
                 if st is not None:
                     st.read_by(main)
         return out
+
+    def dwell_state(self, columns, device='cuda:0'):
+        """The empty state of ``gaze_dwell`` for that many columns: int32 [columns, 16] zeros on the device (attention.STATE_WORDS)."""
+        _dwell_counts('dwell_state', 0, int(columns), 0, 0)
+        return torch.zeros(int(columns), 16, dtype=torch.int32, device=_device(device, 'mcg_gaze_dwell'))
+
+    def gaze_dwell(self, person, kind, ident, mutual, tag=None, state=None, frame0=0, enter=DWELL_ENTER, exit=DWELL_EXIT, region_frames=None,
+                   max_events=None, device='cuda:0', stream=None):
+        """How long each person looks at what, on the device (mcg_gaze_dwell: one launch that walks the frames, one thread per column, and one
+        that compacts the ended episodes) -- ``gaze_dwell_host`` bit for bit, whose arguments and six results these are: the per-frame targets
+        of F frames of R columns become debounced episodes (``enter`` frames to become the current target, ``exit`` frames of grace; the
+        defaults are conventions, not tuned on data), and every region collects its raw person-frames.
+
+        person, kind, ident, mutual, tag [F, R] integers: CUDA tensors are read where they are (anything but contiguous int32 is converted on the
+        device); numpy tables go up through the staging ring (a host table next to a device one is moved with torch).  state: an int32
+        [R, 16] tensor on the device, which the call UPDATES IN PLACE and hands back; None allocates the empty one (``dwell_state``).
+        region_frames: an int32 [M] tensor on the device, ACCUMULATED IN PLACE and handed back; None: no regions.  max_events: the rows of
+        the event table (None: F * R, which always suffices).  Options and shapes are checked on the host before anything is launched
+        (TypeError / ValueError); the tables are never read back.  With device tables, a given state and given region_frames the call touches
+        the host nowhere and can be captured in a graph.
+        -> (dwell [F, R, 4], ended [F, R, 8], events [max_events, 10] (rows behind the count zero), num_events [1], state [R, 16],
+        region_frames [M]), int32 on the device."""
+        lib = L.load()
+        who = 'gaze_dwell'
+        enter, exit, frame0 = _dwell_params(enter, exit, frame0, who)
+        dev = _device(device, 'mcg_gaze_dwell')
+        tables = (person, kind, ident, mutual, tag)
+        there = any(isinstance(t, torch.Tensor) and t.is_cuda for t in tables)
+        if not there:
+            tables = _dwell_tables(who, *tables)
+            F, R = tables[0].shape
+            if tag is None:
+                tables[4] = None                                  # a null pointer: all zero
+        for name, t, shape in (('state', state, (None, 16)), ('region_frames', region_frames, (None,))):
+            if t is not None and not (isinstance(t, torch.Tensor) and t.device == dev and t.dtype == torch.int32 and t.is_contiguous() and
+                                      t.ndim == len(shape) and tuple(t.shape[1:]) == shape[1:]):
+                raise TypeError(f'{who}: {name} is a contiguous int32 {list(shape)} tensor on {dev} (it is updated in place)')
+        with torch.cuda.device(dev):
+            main = _caller_stream(stream, dev)
+            with torch.cuda.stream(main):
+                if there:
+                    moved = []
+                    for name, t in zip(('person', 'kind', 'ident', 'mutual', 'tag'), tables):
+                        if t is not None:
+                            t = t if isinstance(t, torch.Tensor) else torch.as_tensor(np.asarray(t))
+                            if t.dtype.is_floating_point or t.dtype.is_complex:
+                                raise TypeError(f'{who}: {name} must hold integers, got {t.dtype}')
+                            t = t.to(dev, torch.int32).contiguous()
+                            if t.ndim != 2 or (moved and tuple(t.shape) != tuple(moved[0].shape)):
+                                raise ValueError(f'{who}: person, kind, ident, mutual and tag are [F, R] tables of one shape; {name} is {tuple(t.shape)}')
+                        moved.append(t)
+                    tables = moved
+                    F, R = (int(v) for v in tables[0].shape)
+                M = 0 if region_frames is None else int(region_frames.shape[0])
+                E = _dwell_counts(who, F, R, M, max_events)
+                if state is not None and int(state.shape[0]) != R:
+                    raise ValueError(f'{who}: the state of {R} columns is [{R}, 16], got {tuple(state.shape)}')
+                if state is None:
+                    state = torch.zeros(R, 16, dtype=torch.int32, device=dev)
+                if region_frames is None:
+                    region_frames = torch.zeros(0, dtype=torch.int32, device=dev)
+                new = lambda *shape: torch.empty(*shape, dtype=torch.int32, device=dev)
+                dwell, ended, events, num = new(F, R, 4), new(F, R, 8), torch.zeros(E, 10, dtype=torch.int32, device=dev), \
+                    torch.zeros(1, dtype=torch.int32, device=dev)
+                if F == 0:
+                    return dwell, ended, events, num, state, region_frames
+                st, _, ptrs = self._ring.upload([], tuple(tables), dev, main)
+                ptrs = [ptrs[k] for k in (0, 4, 1, 2, 3)]         # the entry takes the tag behind the person
+                vp = C.c_void_p
+                # max_events = 0 still counts: the launch needs a table address and writes no row of it
+                L.check(lib.mcg_gaze_dwell(vp(main.cuda_stream), *(vp(p) for p in ptrs), F, R, frame0, enter, exit, vp(state.data_ptr()),
+                                           vp(region_frames.data_ptr() if M else None), M, vp(dwell.data_ptr()), vp(ended.data_ptr()),
+                                           vp(events.data_ptr() if E else num.data_ptr()), E, vp(num.data_ptr())), 'mcg_gaze_dwell')
+                if st is not None:
+                    st.read_by(main)
+        return dwell, ended, events, num, state, region_frames
 
     def letterbox(self, frames, new_shape=640, stride=32, auto=True, scaleup=True, dtype=torch.float16, rgb=False, pixel_format='bgr', matrix='bt601',
                   device='cuda:0', stream=None):

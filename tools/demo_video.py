@@ -6,7 +6,7 @@ usage: demo_video.py FRAMES_DIR LABELS_DIR CONFIG CHECKPOINT --out gaze.json [--
                      [--batch-frames 448] [--head-class 1] [--ext jpg] [--smooth ALPHA] [--nv12 WxH FILE] [--matrix bt601] [--draw OUT]
                      [--track [--slots 16] [--match-iou 0.3] [--max-age 5]] [--track-motion [GAIN[,DECAY]]]
                      [--color B,G,R] [--predictions DIR --in-shape HxW [--conf-thres 0.25] [--iou-thres 0.45]]
-                     [--detector MODULE:FACTORY [--img-size 640] [--half]] [--attention [--regions FILE.json]]
+                     [--detector MODULE:FACTORY [--img-size 640] [--half]] [--attention [--regions FILE.json] [--dwell [ENTER,EXIT]]]
 
 FRAMES_DIR holds 0.<ext>, 1.<ext>, ... (the demo's `frames/`), LABELS_DIR holds 0.txt, 1.txt, ... with lines `class x1 y1 x2 y2` in pixels
 (the demo's `result/labels/`); a frame without a label file shows no head.  CONFIG is the L2CS config, whose test pipeline the demo runs
@@ -36,7 +36,12 @@ pipeline.letterbox and pipeline.detect_heads); the network is the caller's.
 entry gains per frame `target_kind` (0 none, 1 another person, 2 a region, 3 the camera), `target_id` (the [segment, person] looked at, or
 null), `target_region`, `target_hit` (where the gaze ray enters the target, in frame pixels) and `mutual`.  --regions FILE.json: a JSON list
 of rectangles [[x1, y1, x2, y2], ...] in frame pixels -- a screen, a shelf, a door.  Decided in the image plane, with conventional,
-untuned defaults (a looked-at head box grown by 0.25 of its longer side, a 10 degree cone for the camera)."""
+untuned defaults (a looked-at head box grown by 0.25 of its longer side, a 10 degree cone for the camera).
+--dwell [ENTER,EXIT], with --attention: how LONG they look (harness.run_head_video(dwell=...), pipeline.gaze_dwell on the device): each entry
+gains per frame `dwell_kind` and `dwell_frames` (the current target and its frames so far) and `episodes`, a list of {kind, target_id or
+target_region, start, frames, mutual_frames, reason (1 looked away, 2 the person left, 3 replaced by another target, 4 the video ended)}.  A
+look becomes current after ENTER consecutive frames and ends after EXIT consecutive frames without it (default 3,2: conventions, not tuned
+on data)."""
 import argparse
 import importlib
 import json
@@ -128,6 +133,17 @@ def load_detector(spec):
     return getattr(importlib.import_module(module), factory)()
 
 
+def dwell_option(text):
+    """--dwell's value -> harness.run_head_video's dwell: '' is True (the defaults), 'ENTER,EXIT' a dict."""
+    if not text:
+        return True
+    try:
+        enter, exit = (int(v) for v in text.split(','))
+    except ValueError:
+        raise SystemExit(f'--dwell takes ENTER,EXIT (two integers), got {text!r}') from None
+    return dict(enter=enter, exit=exit)
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
     ap.add_argument('frames_dir')
@@ -162,9 +178,15 @@ def main(argv=None):
                          '(default 0.5,1.0: conventional alpha-beta values, not tuned on data)')
     ap.add_argument('--attention', action='store_true', help='add what every person looks at: another person, a region of --regions, the camera')
     ap.add_argument('--regions', default=None, metavar='FILE.json', help='rectangles [[x1, y1, x2, y2], ...] in frame pixels, of --attention')
+    ap.add_argument('--dwell', nargs='?', const='', default=None, metavar='ENTER,EXIT',
+                    help='--attention with how long every look lasts: episodes with a start, a length and an end (default 3,2: conventions, not '
+                         'tuned on data)')
     a = ap.parse_args(argv)
     if a.regions is not None and not a.attention:
         raise SystemExit('--regions belongs to --attention')
+    if a.dwell is not None and not a.attention:
+        raise SystemExit('--dwell belongs to --attention')
+    dwell = None if a.dwell is None else dwell_option(a.dwell)
     attention = None
     if a.attention:
         attention = {}
@@ -212,7 +234,8 @@ def main(argv=None):
     pipe = DevicePipeline(model.cfg.data.test.pipeline)
     res = harness.run_head_video(model.engine(), pipe, frames, per_frame, max_len=a.max_len, batch_frames=a.batch_frames, rgb=True,
                                  smooth=a.smooth, pixel_format='bgr' if a.nv12 is None else 'nv12', matrix=a.matrix, detections=detections, draw=draw,
-                                 track=track, attention=attention)
+                                 track=track, attention=attention, dwell=dwell)
+    as_json = lambda v: list(v) if isinstance(v, tuple) else v
     if draw is not None:
         res, annotated = res
         write_annotated(a.draw, annotated, a.nv12 is not None)
@@ -221,7 +244,9 @@ def main(argv=None):
                 **({} if a.smooth is None else dict(gaze_smooth=r['fused_smooth'].tolist())),
                 **({} if attention is None else dict(target_kind=r['target_kind'].tolist(), target_id=[None if v is None else list(v) for v in r['target_id']],
                                                      target_region=r['target_region'].tolist(), target_hit=r['target_hit'].tolist(),
-                                                     mutual=r['mutual'].tolist()))) for r in res]
+                                                     mutual=r['mutual'].tolist())),
+                **({} if dwell is None else dict(dwell_kind=r['dwell_kind'].tolist(), dwell_frames=r['dwell_frames'].tolist(),
+                                                 episodes=[{k: as_json(v) for k, v in e.items()} for e in r['episodes']]))) for r in res]
     with open(a.out, 'w') as f:
         json.dump(dict(frames=n, tracks=out), f)
     print(f'{n} frames, {len(out)} (segment, person) tracks, {sum(len(r["frame_id"]) for r in out)} head crops -> {a.out}')
