@@ -1030,8 +1030,8 @@ int mcg_live_gate_lanes(mcg_stream s, const int32_t* ring_id_dev, const float* r
  * whatever they hold nothing outside the given arrays is read or written.  Heads are searched in tiles of 256 rows and a tile whose
  * image_of range holds no picture a workgroup asks about is skipped: tables whose pictures come in ascending row order (LiveGaze's
  * [k, Q, S]) cost one picture per row.  mcgaze_amd/attention.py::gaze_targets_host is the same on the host, bit for bit.
- * Out of scope: camera intrinsics or depth, polygonal regions, arrows coloured or cut at the hit point.  (How long a target is looked at: "gaze
- * dwell" below.) */
+ * Out of scope: camera intrinsics or depth, arrows coloured or cut at the hit point.  (How long a target is looked at: "gaze dwell" below;
+ * regions that are polygons: "gaze targets, polygonal regions" below.) */
 int mcg_gaze_targets(mcg_stream s, const float* boxes_dev, const float* gaze_dev, int gaze_stride, const int32_t* image_of_dev, int n,
                      const float* regions_dev, const int32_t* region_image_dev, int m, int region_period, double expand, double camera_cos2,
                      int32_t* kind_dev, int32_t* target_dev, float* t_dev, float* hit_dev, int32_t* mutual_dev, int32_t* flags_dev);
@@ -1091,12 +1091,52 @@ int mcg_gaze_targets(mcg_stream s, const float* boxes_dev, const float* gaze_dev
  * 0 <= E <= 65536, frame0 >= 0, 1 <= enter <= 65536, 0 <= exit <= 65536.  A wrong count or parameter, a null pointer or a misaligned
  * table returns MCG_ERR_ARG before any launch; the CONTENTS of the tables and of the state never are an error.
  * mcgaze_amd/attention.py::gaze_dwell_host is the same on the host, bit for bit.
- * Out of scope: dwell per polygonal region, camera intrinsics or depth, re-identifying a person who comes back after the tracker's
- * max_age (a new id is a new owner). */
+ * (A polygonal region of mcg_gaze_targets_poly is a region index like any other.)
+ * Out of scope: camera intrinsics or depth, re-identifying a person who comes back after the tracker's max_age (a new id is a new
+ * owner). */
 int mcg_gaze_dwell(mcg_stream s, const int32_t* person_dev, const int32_t* tag_dev, const int32_t* kind_dev, const int32_t* ident_dev,
                    const int32_t* mutual_dev, int num_frames, int columns, int frame0, int enter, int exit_frames, int32_t* state_dev,
                    int32_t* region_frames_dev, int num_regions, int32_t* dwell_dev, int32_t* ended_dev, int32_t* events_dev, int max_events,
                    int32_t* num_events_dev);
+
+/* ---------------------------------------------------------------- gaze targets, polygonal regions (additions to ABI 19; nothing above changes)
+ * A marked region is rarely a rectangle in the picture: a screen seen off-axis is a quadrilateral, a shelf beside a pillar an L.
+ * mcg_gaze_targets_poly is mcg_gaze_targets with regions that are rectangles OR polygons.  Rows, UNUSABLE, CAMERA, RAY, the head
+ * candidates, CHOICE and OUTPUTS are word for word those of "gaze targets" above; only the regions differ.  Two launches, no allocation,
+ * no host sync, graph-capturable, no atomics in global memory.
+ * TABLES.  region_xy f32 [V][2] vertices (x, y), region_start int32 [m + 1], region_image int32 [m] (as above, with region_period).  Region
+ * j owns the vertices region_start[j] .. region_start[j + 1] - 1; c is their number.
+ * USABLE REGION.  Region j is usable iff 0 <= region_start[j] <= region_start[j + 1] <= V, and c == 2 or 3 <= c <= 32
+ * (MCG_ATTEND_POLY_VERTS), and every coordinate it owns is finite, and for c == 2 neither x2 < x1 nor y2 < y1.  Any other region is never
+ * hit and flags nothing, as a bad rectangle above.  The tables are device contents and their contents never are an error: whatever
+ * region_start holds, nothing outside region_xy[0 .. V) is read -- the offsets are checked before the first vertex load.
+ * c == 2.  The two vertices are (x1, y1) and (x2, y2) of a rectangle, tested by the SLAB TEST above unchanged: a table of only such regions
+ * gives the bits of mcg_gaze_targets.
+ * c >= 3.  Edge k runs from a = v_k to b = v_((k + 1) mod c), k ascending.  Everything is double and uncontracted; every product, quotient
+ * and sum is rounded on its own.
+ *   INSIDE (even-odd rule).  Edge k toggles iff (a_y > o_y) != (b_y > o_y) and o_x < a_x + ((o_y - a_y) * (b_x - a_x)) / (b_y - a_y).  An
+ *   odd number of toggles is a hit with t = +0.
+ *   CROSSINGS, otherwise.  e = b - a, w = a - o;  den = d_x * e_y - d_y * e_x,  tn = w_x * e_y - w_y * e_x,  sn = w_x * d_y - w_y * d_x.  The
+ *   edge is crossed iff (den > 0 and tn >= 0 and sn >= 0 and sn <= den) or (den < 0 and tn <= 0 and sn <= 0 and sn >= den): no division
+ *   in the decision.  With q = tn / den its t is q if q > 0, else +0; a t that is not finite is no crossing.  The region's t is the smallest
+ *   over its crossed edges; with no crossed edge it is a miss.
+ *   A parallel edge (den == 0) gives nothing by itself: its end points belong to its neighbours.  Self-intersecting and zero-area polygons
+ *   are whatever these rules give.  Winding does not matter.
+ * CHOICE is unchanged: the smallest t wins; on equal t a head comes before a region, then the lower index.  Rectangles and polygons share
+ * one index space, in the caller's order.
+ *   region_xy_dev      DEVICE f32 [V][2]; NULL iff V == 0
+ *   region_start_dev, region_image_dev   DEVICE int32 [m + 1] and int32 [m]; NULL iff m == 0
+ *   every other argument as mcg_gaze_targets takes it
+ * 0 <= n <= 65536, 0 <= m <= 4096, 0 <= V = num_vertices <= 65536; n == 0 returns MCG_OK without a launch.  A count outside these or a
+ * null table returns MCG_ERR_ARG before any launch.  The regions are searched in tiles of 256 with the picture-range skip of the heads; a
+ * polygon's vertices are read through an address that is the same in every thread of the workgroup.  No bounding-box reject: every edge
+ * is tested.  mcgaze_amd/attention.py::gaze_targets_host(region_start=...) is the same on the host, bit for bit.
+ * Out of scope: region outlines drawn on the device, arrows cut at the hit point, camera intrinsics or depth. */
+#define MCG_ATTEND_POLY_VERTS 32
+int mcg_gaze_targets_poly(mcg_stream s, const float* boxes_dev, const float* gaze_dev, int gaze_stride, const int32_t* image_of_dev, int n,
+                          const float* region_xy_dev, int num_vertices, const int32_t* region_start_dev, const int32_t* region_image_dev, int m,
+                          int region_period, double expand, double camera_cos2, int32_t* kind_dev, int32_t* target_dev, float* t_dev,
+                          float* hit_dev, int32_t* mutual_dev, int32_t* flags_dev);
 
 /* ---------------------------------------------------------------- measurement aids (bench.py)
  * While armed, every launch of the contraction kernel made by THIS engine is bracketed by a hipEvent pair on its launch stream.

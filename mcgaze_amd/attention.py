@@ -2,12 +2,14 @@
 rectangle, the lens or nothing.  ``gaze_targets_host`` is in numpy what ``DevicePipeline.gaze_targets`` (mcg_gaze_targets) writes on the
 device, bit for bit; it serves checks and users without a GPU.  The ray is the demo's arrow (MCGaze_demo/demo.ipynb, cell 5) followed until
 it meets something, in the image plane: no camera intrinsics, no depth.  The defaults (expand 0.25, a 10 degree cone for "the camera") are
-conventions, not tuned on data.
+conventions, not tuned on data.  A region may also be a polygon of 3 .. 32 vertices ("gaze targets, polygonal regions", mcg_gaze_targets_poly):
+``region_polygons`` turns the mixed list of rectangles and polygons into the vertex tables ``PolyRegions`` that both sides take.
 
 Gaze dwell (include/mcgaze_hip.h, "gaze dwell"): how LONG each person looks at what.  ``gaze_dwell_host`` is in numpy what
 ``DevicePipeline.gaze_dwell`` (mcg_gaze_dwell) writes on the device, bit for bit: the per-frame targets of the columns (tracker slots or
 lanes) become debounced episodes with a start, a length, an end and a reason, and every region collects its person-frames.  The defaults
 (enter 3, exit 2) are conventions, not tuned on data."""
+import collections
 import math
 
 import numpy as np
@@ -17,6 +19,7 @@ from .staging import _host_array
 KIND_NONE, KIND_HEAD, KIND_REGION, KIND_CAMERA = 0, 1, 2, 3
 KIND_NAMES = ('none', 'head', 'region', 'camera')
 MAX_ROWS, MAX_REGIONS = 65536, 4096                              # the bounds of mcg_gaze_targets
+MAX_VERTICES, POLY_VERTS = 65536, 32                             # ... and of mcg_gaze_targets_poly: vertices a call, vertices a polygon
 EXPAND, CAMERA_ANGLE = 0.25, 10.0                                # conventions, not tuned on data
 FIELDS = ('kind', 'target', 't', 'hit', 'mutual', 'flags')       # the order of the six tables
 
@@ -35,11 +38,13 @@ def _target_params(expand=EXPAND, camera_angle=CAMERA_ANGLE, region_period=0, wh
     return float(expand), cos2, int(region_period)
 
 
-def _check_counts(who, n, m):
+def _check_counts(who, n, m, vertices=0):
     if n > MAX_ROWS:
         raise ValueError(f'{who}: at most {MAX_ROWS} rows per call (got {n})')
     if m > MAX_REGIONS:
         raise ValueError(f'{who}: at most {MAX_REGIONS} regions per call (got {m})')
+    if vertices > MAX_VERTICES:
+        raise ValueError(f'{who}: at most {MAX_VERTICES} vertices per call (got {vertices})')
 
 
 def _region_tables(who, regions, region_image):
@@ -66,11 +71,85 @@ def _region_tables(who, regions, region_image):
     return r, ri
 
 
+def _holds_polygon(regions):
+    """A nested list with an item that is itself a list of lists: the mixed form of ``region_polygons`` ([m, 4] arrays and lists of 4-number
+    items keep meaning rectangles)."""
+    return isinstance(regions, (list, tuple)) and not isinstance(regions, PolyRegions) and any(isinstance(r, (list, tuple, np.ndarray)) and len(r) and np.ndim(r[0]) > 0 for r in regions)
+
+
+class PolyRegions(collections.namedtuple('PolyRegions', 'xy start')):
+    """The region tables of mcg_gaze_targets_poly, (xy f32 [V, 2], start int32 [m + 1]): region j owns the vertices start[j] ..
+    start[j + 1] - 1 -- 2 of them are the corners (x1, y1), (x2, y2) of a rectangle, 3 .. 32 a polygon.  ``regions=PolyRegions(xy, start)``
+    is how gaze_targets_host and DevicePipeline.gaze_targets take the vertex form (the tables may be device tensors there); what ``start``
+    HOLDS is contents, never an error."""
+    __slots__ = ()
+
+
+def _as_vertices(rectangles):
+    """Rectangles f32 [m, 4] in the vertex form: two vertices each."""
+    return PolyRegions(rectangles.reshape(-1, 2), 2 * np.arange(len(rectangles) + 1, dtype=np.int32))
+
+
+def region_polygons(regions):
+    """The mixed list of regions -> PolyRegions(xy f32 [V, 2], start int32 [m + 1]), the tables of mcg_gaze_targets_poly.  An item is 4
+    numbers x1 y1 x2 y2 (a rectangle: the 2 vertices (x1, y1), (x2, y2)) or 3 .. 32 pairs [x, y] (a polygon, either winding, closed by
+    itself).  TypeError for what is no list of such items or holds no numbers, ValueError for an item of another shape; the VALUES are
+    contents (a vertex that is not finite makes its region unusable, as on the device)."""
+    who = 'region_polygons'
+    if not isinstance(regions, (list, tuple, np.ndarray)):
+        raise TypeError(f'{who}: regions is a list of rectangles [x1, y1, x2, y2] and polygons [[x, y], ...]; got {type(regions).__name__}')
+    parts = []
+    for j, item in enumerate(regions):
+        if not isinstance(item, (list, tuple, np.ndarray)):
+            raise TypeError(f'{who}: region {j} is 4 numbers or a list of [x, y] pairs, got {type(item).__name__}')
+        try:
+            a = np.asarray(item)
+        except ValueError:
+            raise ValueError(f'{who}: region {j} is 4 numbers or 3 .. {POLY_VERTS} pairs [x, y], got a ragged list') from None
+        if a.dtype.kind not in 'fiu':
+            raise TypeError(f'{who}: region {j} must hold numbers, got {a.dtype}')
+        if a.shape == (4,):
+            a = a.reshape(2, 2)
+        elif not (a.ndim == 2 and a.shape[1] == 2 and 3 <= a.shape[0] <= POLY_VERTS):
+            raise ValueError(f'{who}: region {j} is 4 numbers or 3 .. {POLY_VERTS} pairs [x, y], got shape {a.shape}')
+        parts.append(a.astype(np.float32))
+    start = np.zeros(len(parts) + 1, np.int64)
+    np.cumsum([len(p) for p in parts], out=start[1:])
+    _check_counts(who, 0, len(parts), int(start[-1]))
+    return PolyRegions(np.concatenate(parts) if parts else np.zeros((0, 2), np.float32), start.astype(np.int32))
+
+
+def _poly_tables(who, regions, region_image):
+    """Host PolyRegions -> (f32 [V,2], int32 [m+1], int32 [m]), checked (TypeError / ValueError): the shapes, dtypes and counts only -- what
+    start HOLDS is contents, as on the device.  region_image None: every picture (-1)."""
+    v = np.asarray(_host_array(regions.xy))
+    if v.size == 0:
+        v = v.reshape(0, 2)
+    if v.ndim != 2 or v.shape[1] != 2 or v.dtype.kind not in 'fiu':
+        raise ValueError(f'{who}: PolyRegions.xy is the [V, 2] vertex table x y; got {v.dtype} {v.shape}')
+    s = np.asarray(_host_array(regions.start))
+    if s.size and s.dtype.kind not in 'iu':
+        raise TypeError(f'{who}: PolyRegions.start must hold integers, got {s.dtype}')
+    if s.ndim != 1 or len(s) < 1:
+        raise ValueError(f'{who}: PolyRegions.start must be [m + 1], got {s.shape}')
+    m = len(s) - 1
+    if region_image is None:
+        ri = np.full(m, -1, np.int32)
+    else:
+        ri = np.asarray(_host_array(region_image)).reshape(-1)
+        if ri.size and ri.dtype.kind not in 'iu':
+            raise TypeError(f'{who}: region_image must hold integers, got {ri.dtype}')
+        if ri.shape != (m,):
+            raise ValueError(f'{who}: region_image must be [{m}], one per region; got {ri.shape}')
+    return np.ascontiguousarray(v, dtype=np.float32), np.ascontiguousarray(s.astype(np.int32)), np.ascontiguousarray(ri, dtype=np.int32)
+
+
 def _attention_options(who, attention, cameras=None):
     """The ``attention=`` option of LiveGaze and run_head_video, validated (ValueError) -> None (off), or (regions f32 [m,4], region_image
     int32 [m], dict(expand=, camera_angle=)).  attention: None, True or dict(regions=, expand=, camera_angle=).  regions: [[x1, y1, x2, y2],
     ...], which apply to every picture (region_image -1); with ``cameras`` a list of that many such tables (or None), one per camera, whose
-    region_image is the camera."""
+    region_image is the camera.  A table may also be the mixed list of ``region_polygons``; where one holds a polygon, regions is the
+    PolyRegions of all tables -- ``regions=`` of gaze_targets either way."""
     if attention is None:
         return None
     if attention is not True and not isinstance(attention, dict):
@@ -80,18 +159,28 @@ def _attention_options(who, attention, cameras=None):
         raise ValueError(f'{who}: attention takes regions, expand and camera_angle; got {sorted(opts)}')
     regions = opts.pop('regions', None)
     _target_params(opts.get('expand', EXPAND), opts.get('camera_angle', CAMERA_ANGLE), 0, f'{who}(attention=...)')
+    one = lambda r: region_polygons(r) if _holds_polygon(r) else _region_tables(who, r, None)[0]      # (xy, start), or [m, 4]
     try:
         if cameras is None:
-            tables = [_region_tables(who, regions, None)[0]]
+            tables = [one(regions)]
         else:
             if regions is not None and (isinstance(regions, np.ndarray) or len(regions) != cameras):
                 raise ValueError(f'{who}: attention regions are a list of {cameras} tables, one per camera (None: no regions there)')
-            tables = [_region_tables(who, r, None)[0] for r in (regions if regions is not None else [None] * cameras)]
+            tables = [one(r) for r in (regions if regions is not None else [None] * cameras)]
     except TypeError as e:
         raise ValueError(f'{who}: attention regions: {e}') from None
-    table = np.concatenate(tables) if tables else np.zeros((0, 4), np.float32)
-    _check_counts(who, 0, len(table))
-    image = np.full(len(table), -1, np.int32) if cameras is None else np.repeat(np.arange(len(tables), dtype=np.int32), [len(t) for t in tables])
+    if any(isinstance(t, PolyRegions) for t in tables):          # a polygon somewhere: every table as vertices, the offsets counted through
+        tables = [t if isinstance(t, PolyRegions) else _as_vertices(t) for t in tables]
+        counts = [len(t.start) - 1 for t in tables]
+        first = np.cumsum([0] + [len(t.xy) for t in tables])
+        table = PolyRegions(np.concatenate([t.xy for t in tables]),
+                            np.concatenate([t.start[:-1] + f for t, f in zip(tables, first)] + [first[-1:]]).astype(np.int32))
+        _check_counts(who, 0, sum(counts), len(table.xy))
+    else:
+        counts = [len(t) for t in tables]
+        table = np.concatenate(tables) if tables else np.zeros((0, 4), np.float32)
+        _check_counts(who, 0, len(table))
+    image = np.full(sum(counts), -1, np.int32) if cameras is None else np.repeat(np.arange(len(tables), dtype=np.int32), counts)
     return table, image.astype(np.int32), opts
 
 
@@ -132,12 +221,54 @@ def _entries(o, d, lo, hi):
         return np.where(ok & (near <= far) & (far >= 0.0) & np.isfinite(t), t, np.inf)
 
 
+def _usable_regions(xy, start):
+    """The header's USABLE REGION for every region of the vertex tables (xy float64 [V,2]) -> (ok bool [m], first int64 [m], count int64 [m])."""
+    s, e = start[:-1].astype(np.int64), start[1:].astype(np.int64)
+    c = e - s
+    ok = (0 <= s) & (s <= e) & (e <= len(xy)) & (c >= 2) & (c <= POLY_VERTS)
+    for j in np.flatnonzero(ok):                                  # nothing outside xy is looked at: the offsets were checked first
+        v = xy[s[j]:e[j]]
+        ok[j] = np.isfinite(v).all() and not (c[j] == 2 and (v[1, 0] < v[0, 0] or v[1, 1] < v[0, 1]))
+    return ok, s, c
+
+
+def _polygon_entries(o, d, v):
+    """INSIDE and CROSSINGS of the header for rays (o, d: [s, 2]) against ONE polygon (v: [c, 2], c >= 3) -> t [s], +inf for a miss."""
+    ox, oy, dx, dy = o[:, 0], o[:, 1], d[:, 0], d[:, 1]
+    inside, best = np.zeros(len(o), bool), np.full(len(o), np.inf)
+    with np.errstate(divide='ignore', invalid='ignore', over='ignore'):
+        for k in range(len(v)):
+            (ax, ay), (bx, by) = v[k], v[(k + 1) % len(v)]
+            ex, ey, wx, wy = bx - ax, by - ay, ax - ox, ay - oy
+            inside ^= ((ay > oy) != (by > oy)) & (ox < ax + ((oy - ay) * ex) / ey)
+            den, tn, sn = dx * ey - dy * ex, wx * ey - wy * ex, wx * dy - wy * dx
+            crossed = ((den > 0.0) & (tn >= 0.0) & (sn >= 0.0) & (sn <= den)) | ((den < 0.0) & (tn <= 0.0) & (sn <= 0.0) & (sn >= den))
+            q = tn / den
+            t = np.where(q > 0.0, q, 0.0)
+            best = np.where(crossed & np.isfinite(t) & (t < best), t, best)
+    return np.where(inside, 0.0, best)
+
+
+def _region_entries(o, d, xy, first, count, regs):
+    """Rays (o, d: [s, 2]) against the usable regions ``regs`` of the vertex tables -> t [s, len(regs)], +inf for a miss: the slab test for
+    2 vertices, the polygon rules for more."""
+    t = np.full((len(o), len(regs)), np.inf)
+    rect = count[regs] == 2
+    f = first[regs[rect]]
+    t[:, rect] = _entries(o, d, xy[f], xy[f + 1])
+    for col in np.flatnonzero(~rect):
+        j = regs[col]
+        t[:, col] = _polygon_entries(o, d, xy[first[j]:first[j] + count[j]])
+    return t
+
+
 def gaze_targets_host(boxes, gaze, image_of=None, regions=None, region_image=None, region_period=0, expand=EXPAND, camera_angle=CAMERA_ANGLE):
-    """``mcg_gaze_targets`` in numpy float64, bit for bit (include/mcgaze_hip.h, "gaze targets").
+    """``mcg_gaze_targets`` and ``mcg_gaze_targets_poly`` in numpy float64, bit for bit (include/mcgaze_hip.h, "gaze targets" and "gaze
+    targets, polygonal regions").
 
     boxes [n,4] x1 y1 x2 y2 and gaze [n,>=3] (gx, gy, gz; -z towards the lens), read as f32 and widened; image_of [n] integers, rows with equal
-    image_of being in one picture (None: all in picture 0; negative: an unusable row).  regions [m,4] rectangles with region_image [m] (None:
-    -1): a region applies to a row iff region_image < 0, or equals image_of (region_period 0), or equals image_of % region_period.  expand: a
+    image_of being in one picture (None: all in picture 0; negative: an unusable row).  regions [m,4] rectangles -- or the mixed list of
+    ``region_polygons``, or a ``PolyRegions`` (the vertex tables as the device takes them) -- with region_image [m] (None: -1): a region applies to a row iff region_image < 0, or equals image_of (region_period 0), or equals image_of % region_period.  expand: a
     looked-at head's box is grown by expand * its longer side on each side.  camera_angle: half angle in degrees of the cone around the lens
     axis inside which a gaze is "at the camera" (None: never).  Both defaults are conventions, not tuned on data.
     -> (kind int32 [n]: KIND_NONE / KIND_HEAD / KIND_REGION / KIND_CAMERA; target int32 [n]: the row or region index, else -1; t float32 [n];
@@ -145,10 +276,16 @@ def gaze_targets_host(boxes, gaze, image_of=None, regions=None, region_image=Non
     who = 'gaze_targets_host'
     expand, cos2, period = _target_params(expand, camera_angle, region_period, who)
     b32, g32, io = _row_tables(who, boxes, gaze, image_of)
-    r32, ri = _region_tables(who, regions, region_image)
-    n, m = len(b32), len(r32)
-    _check_counts(who, n, m)
-    b, g, r = b32.astype(np.float64), g32.astype(np.float64), r32.astype(np.float64)
+    if _holds_polygon(regions):
+        regions = region_polygons(regions)
+    if isinstance(regions, PolyRegions):
+        xy32, start, ri = _poly_tables(who, regions, region_image)
+    else:                                                         # rectangles: two vertices each, one statement of the rest
+        r32, ri = _region_tables(who, regions, region_image)
+        xy32, start = _as_vertices(r32)
+    n, m = len(b32), len(ri)
+    _check_counts(who, n, m, len(xy32))
+    b, g, xy = b32.astype(np.float64), g32.astype(np.float64), xy32.astype(np.float64)
     kind, target = np.zeros(n, np.int32), np.full(n, -1, np.int32)
     t_out, hit = np.zeros(n, np.float64), np.zeros((n, 2), np.float64)
     usable = np.isfinite(b).all(axis=1) & np.isfinite(g).all(axis=1) & ~(b[:, 2] < b[:, 0]) & ~(b[:, 3] < b[:, 1]) & (io >= 0)
@@ -165,7 +302,7 @@ def gaze_targets_host(boxes, gaze, image_of=None, regions=None, region_image=Non
     with np.errstate(over='ignore'):
         e = expand * side
     lo, hi = np.stack([b[:, 0] - e, b[:, 1] - e], axis=1), np.stack([b[:, 2] + e, b[:, 3] + e], axis=1)
-    r_ok = np.isfinite(r).all(axis=1) & ~(r[:, 2] < r[:, 0]) & ~(r[:, 3] < r[:, 1])
+    r_ok, r_first, r_count = _usable_regions(xy, start)
     for picture in np.unique(io[searching]):
         rows = np.flatnonzero(usable & (io == picture))           # the candidates, ascending; the sources are among them
         src = rows[searching[rows]]
@@ -173,7 +310,7 @@ def gaze_targets_host(boxes, gaze, image_of=None, regions=None, region_image=Non
         heads[src[:, None] == rows[None, :]] = np.inf              # every OTHER row
         applies = r_ok & ((ri < 0) | (ri == (int(picture) % period if period > 0 else int(picture))))
         regs = np.flatnonzero(applies)
-        t = np.concatenate([heads, _entries(o[src], d[src], r[regs, :2], r[regs, 2:])], axis=1)
+        t = np.concatenate([heads, _region_entries(o[src], d[src], xy, r_first, r_count, regs)], axis=1)
         if t.shape[1] == 0:
             continue
         best = np.argmin(t, axis=1)                               # the FIRST smallest: heads before regions, then the lower index

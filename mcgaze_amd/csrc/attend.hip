@@ -10,6 +10,15 @@
 // candidates in ASCENDING index, heads before regions, and replaces its best only on a strictly smaller t: the winner is a function of the
 // inputs alone -- a skipped tile holds no candidate of the workgroup, so the launch geometry cannot show.  gaze_mutual_kernel needs every
 // target and is a second launch.  No atomics in global memory, no scratch; LDS: 256 x (4 doubles + 1 int) and a few words.
+//
+// Polygonal regions ("gaze targets, polygonal regions" in the header; mcg_gaze_targets_poly -> gaze_targets_poly_kernel).  Rows, head phase,
+// choice and outputs are those above -- gaze_targets_body<POLY> states them once and both kernels are that body.  A region is a run of
+// vertices of region_xy named by region_start.  The staging thread of a region checks its two offsets BEFORE its first vertex load, walks its
+// vertices once for finiteness and puts key, start and count into LDS (a 2-vertex region also its rectangle, for the slab test as it is); a
+// region that is not usable is "no candidate" and none of its vertices is read again.  The searching threads walk the tile's regions in
+// ascending order and a polygon's vertices through a UNIFORM ADDRESS: start and count come out of LDS at an index every thread shares, so
+// every lane of a wave loads the same region_xy word at the same time (one cache line, broadcast) -- no LDS staging of vertices.  The
+// previous vertex is carried in registers; there is no local array.  No bounding-box reject: every edge is tested.  LDS: + 2 x 256 ints.
 #include <climits>
 
 #include "common.hpp"
@@ -17,6 +26,7 @@
 #define MCG_ATTEND_ROWS 65536
 #define MCG_ATTEND_REGIONS 4096
 #define MCG_ATTEND_THREADS 256   // the tile of candidates is one per thread
+#define MCG_ATTEND_VERTICES 65536 // (at most MCG_ATTEND_POLY_VERTS a polygon: the header)
 
 // The slab test of one candidate rectangle against the ray o + t d, t >= 0 (d not both zero).  -> the entry t, or -1 for a miss.
 __device__ __forceinline__ double slab_entry(double ox, double oy, double dx, double dy, double lox, double loy, double hix, double hiy) {
@@ -42,16 +52,42 @@ __device__ __forceinline__ double slab_entry(double ox, double oy, double dx, do
   return (pass && near <= far && far >= 0.0 && isfinite(t)) ? t : -1.0;
 }
 
-__global__ __launch_bounds__(MCG_ATTEND_THREADS) void gaze_targets_kernel(const float* __restrict__ boxes, const float* __restrict__ gaze,
-                                                                          int gaze_stride, const int32_t* __restrict__ image_of, int n,
-                                                                          const float* __restrict__ regions,
-                                                                          const int32_t* __restrict__ region_image, int m, int region_period,
-                                                                          double expand, double camera_cos2, int32_t* __restrict__ kind,
-                                                                          int32_t* __restrict__ target, float* __restrict__ t_out,
-                                                                          float* __restrict__ hit, int32_t* __restrict__ flags) {
+// One polygon (c >= 3 finite vertices at xy, checked by the staging thread) against the ray: even-odd INSIDE -> +0, else the smallest t of
+// the CROSSED edges.  -> the entry t, or -1 for a miss.  xy is the same address in every lane.
+__device__ __forceinline__ double poly_entry(double ox, double oy, double dx, double dy, const float* __restrict__ xy, int c) {
+#pragma clang fp contract(off)
+  const double fx = xy[0], fy = xy[1];
+  double ax = fx, ay = fy, best = HUGE_VAL;
+  bool inside = false;
+  for (int k = 1; k <= c; ++k) {                                 // edge k - 1: a = v[k - 1] -> b = v[k mod c]
+    const double bx = k < c ? (double)xy[2 * k] : fx, by = k < c ? (double)xy[2 * k + 1] : fy;
+    const double ex = bx - ax, ey = by - ay, wx = ax - ox, wy = ay - oy;
+    if ((ay > oy) != (by > oy) && ox < ax + ((oy - ay) * ex) / ey) inside = !inside;
+    const double den = dx * ey - dy * ex, tn = wx * ey - wy * ex, sn = wx * dy - wy * dx;
+    if ((den > 0.0 && tn >= 0.0 && sn >= 0.0 && sn <= den) || (den < 0.0 && tn <= 0.0 && sn <= 0.0 && sn >= den)) {
+      const double q = tn / den;
+      const double t = q > 0.0 ? q : 0.0;
+      if (isfinite(t) && t < best) best = t;
+    }
+    ax = bx;
+    ay = by;
+  }
+  return inside ? 0.0 : best < HUGE_VAL ? best : -1.0;
+}
+
+// Both kernels.  POLY false: regions is f32 [m][4] rectangles (region_start and num_vertices are not read).  POLY true: regions is region_xy
+// f32 [num_vertices][2] and region j owns the vertices region_start[j] .. region_start[j + 1] - 1.
+template <bool POLY>
+__device__ __forceinline__ void gaze_targets_body(const float* __restrict__ boxes, const float* __restrict__ gaze, int gaze_stride,
+                                                  const int32_t* __restrict__ image_of, int n, const float* __restrict__ regions, int num_vertices,
+                                                  const int32_t* __restrict__ region_start, const int32_t* __restrict__ region_image, int m,
+                                                  int region_period, double expand, double camera_cos2, int32_t* __restrict__ kind,
+                                                  int32_t* __restrict__ target, float* __restrict__ t_out, float* __restrict__ hit,
+                                                  int32_t* __restrict__ flags) {
 #pragma clang fp contract(off)
   __shared__ double c_lox[MCG_ATTEND_THREADS], c_loy[MCG_ATTEND_THREADS], c_hix[MCG_ATTEND_THREADS], c_hiy[MCG_ATTEND_THREADS];
   __shared__ int c_key[MCG_ATTEND_THREADS];                      // a head's image_of / a region's region_image; INT_MIN: no candidate
+  __shared__ int c_start[POLY ? MCG_ATTEND_THREADS : 1], c_count[POLY ? MCG_ATTEND_THREADS : 1];      // a region's first vertex and their number
   __shared__ int src_lo, src_hi, srk_lo, srk_hi, tile_lo, tile_hi, tile_any;
   const int tid = threadIdx.x;
   const int i = blockIdx.x * MCG_ATTEND_THREADS + tid;
@@ -155,14 +191,28 @@ __global__ __launch_bounds__(MCG_ATTEND_THREADS) void gaze_targets_kernel(const 
       const int j = base + tid;
       int key = INT_MIN;
       if (j < m) {
-        const double x1 = regions[4 * (size_t)j], y1 = regions[4 * (size_t)j + 1], x2 = regions[4 * (size_t)j + 2], y2 = regions[4 * (size_t)j + 3];
-        if (isfinite(x1) && isfinite(y1) && isfinite(x2) && isfinite(y2) && !(x2 < x1) && !(y2 < y1)) {
+        size_t first = 4 * (size_t)j;                            // the rectangle's four floats: x1 y1 x2 y2
+        bool ok = true;
+        if constexpr (POLY) {
+          const int s = region_start[j], e = region_start[j + 1];     // (j + 1 <= m: the table has m + 1 words)
+          const int c = 0 <= s && s <= e && e <= num_vertices ? e - s : 0;      // (whatever the words hold, the difference cannot overflow)
+          ok = c >= 2 && c <= MCG_ATTEND_POLY_VERTS;
+          if (ok) {                                              // every vertex below lies inside region_xy[0 .. num_vertices)
+            first = 2 * (size_t)s;
+            for (int k = 0; k < 2 * c; ++k) ok = ok && isfinite(regions[first + k]);
+            c_start[tid] = s;
+            c_count[tid] = c;
+          }
+        }
+        if (ok && (!POLY || c_count[tid] == 2)) {
+          const double x1 = regions[first], y1 = regions[first + 1], x2 = regions[first + 2], y2 = regions[first + 3];
+          ok = isfinite(x1) && isfinite(y1) && isfinite(x2) && isfinite(y2) && !(x2 < x1) && !(y2 < y1);
           c_lox[tid] = x1;
           c_loy[tid] = y1;
           c_hix[tid] = x2;
           c_hiy[tid] = y2;
-          key = region_image[j] < 0 ? -1 : region_image[j];
         }
+        if (ok) key = region_image[j] < 0 ? -1 : region_image[j];
       }
       c_key[tid] = key;
       __syncthreads();
@@ -179,7 +229,12 @@ __global__ __launch_bounds__(MCG_ATTEND_THREADS) void gaze_targets_kernel(const 
         for (int c = 0; c < count; ++c) {
           const int rk = c_key[c];
           if (rk == INT_MIN || (rk != -1 && rk != my_rkey)) continue;
-          const double t = slab_entry(ox, oy, dx, dy, c_lox[c], c_loy[c], c_hix[c], c_hiy[c]);
+          double t;
+          if (POLY && c_count[POLY ? c : 0] != 2) {              // (c_start, c_count: one LDS word for the whole workgroup -> a uniform address)
+            t = poly_entry(ox, oy, dx, dy, regions + 2 * (size_t)c_start[POLY ? c : 0], c_count[POLY ? c : 0]);
+          } else {
+            t = slab_entry(ox, oy, dx, dy, c_lox[c], c_loy[c], c_hix[c], c_hiy[c]);
+          }
           if (t >= 0.0 && t < best) {
             best = t;
             best_target = base + c;
@@ -199,6 +254,29 @@ __global__ __launch_bounds__(MCG_ATTEND_THREADS) void gaze_targets_kernel(const 
   flags[i] = my_flag;
 }
 
+__global__ __launch_bounds__(MCG_ATTEND_THREADS) void gaze_targets_kernel(const float* __restrict__ boxes, const float* __restrict__ gaze,
+                                                                          int gaze_stride, const int32_t* __restrict__ image_of, int n,
+                                                                          const float* __restrict__ regions,
+                                                                          const int32_t* __restrict__ region_image, int m, int region_period,
+                                                                          double expand, double camera_cos2, int32_t* __restrict__ kind,
+                                                                          int32_t* __restrict__ target, float* __restrict__ t_out,
+                                                                          float* __restrict__ hit, int32_t* __restrict__ flags) {
+  gaze_targets_body<false>(boxes, gaze, gaze_stride, image_of, n, regions, 0, nullptr, region_image, m, region_period, expand, camera_cos2, kind, target,
+                           t_out, hit, flags);
+}
+
+__global__ __launch_bounds__(MCG_ATTEND_THREADS) void gaze_targets_poly_kernel(const float* __restrict__ boxes, const float* __restrict__ gaze,
+                                                                               int gaze_stride, const int32_t* __restrict__ image_of, int n,
+                                                                               const float* __restrict__ region_xy, int num_vertices,
+                                                                               const int32_t* __restrict__ region_start,
+                                                                               const int32_t* __restrict__ region_image, int m, int region_period,
+                                                                               double expand, double camera_cos2, int32_t* __restrict__ kind,
+                                                                               int32_t* __restrict__ target, float* __restrict__ t_out,
+                                                                               float* __restrict__ hit, int32_t* __restrict__ flags) {
+  gaze_targets_body<true>(boxes, gaze, gaze_stride, image_of, n, region_xy, num_vertices, region_start, region_image, m, region_period, expand,
+                          camera_cos2, kind, target, t_out, hit, flags);
+}
+
 __global__ __launch_bounds__(MCG_ATTEND_THREADS) void gaze_mutual_kernel(const int32_t* __restrict__ kind, const int32_t* __restrict__ target, int n,
                                                                          int32_t* __restrict__ mutual) {
   const int i = blockIdx.x * MCG_ATTEND_THREADS + threadIdx.x;
@@ -211,10 +289,11 @@ __global__ __launch_bounds__(MCG_ATTEND_THREADS) void gaze_mutual_kernel(const i
   mutual[i] = v;
 }
 
-extern "C" int mcg_gaze_targets(mcg_stream stream, const float* boxes_dev, const float* gaze_dev, int gaze_stride, const int32_t* image_of_dev, int n,
-                                const float* regions_dev, const int32_t* region_image_dev, int m, int region_period, double expand, double camera_cos2,
-                                int32_t* kind_dev, int32_t* target_dev, float* t_dev, float* hit_dev, int32_t* mutual_dev, int32_t* flags_dev) {
-  const char* what = "mcg_gaze_targets";
+// Both entries: their checks, then the two launches.  poly false: regions_dev is [m][4] rectangles; true: region_xy [num_vertices][2].
+static int gaze_targets_launch(const char* what, bool poly, mcg_stream stream, const float* boxes_dev, const float* gaze_dev, int gaze_stride,
+                               const int32_t* image_of_dev, int n, const float* regions_dev, int num_vertices, const int32_t* region_start_dev,
+                               const int32_t* region_image_dev, int m, int region_period, double expand, double camera_cos2, int32_t* kind_dev,
+                               int32_t* target_dev, float* t_dev, float* hit_dev, int32_t* mutual_dev, int32_t* flags_dev) {
   MCG_CHECK_ARG(n >= 0 && n <= MCG_ATTEND_ROWS, "%s: 0 .. %d rows per call (got %d)", what, MCG_ATTEND_ROWS, n);
   MCG_CHECK_ARG(m >= 0 && m <= MCG_ATTEND_REGIONS, "%s: 0 .. %d regions per call (got %d)", what, MCG_ATTEND_REGIONS, m);
   MCG_CHECK_ARG(gaze_stride >= 3 && region_period >= 0, "%s: bad sizes gaze_stride=%d region_period=%d", what, gaze_stride, region_period);
@@ -222,13 +301,42 @@ extern "C" int mcg_gaze_targets(mcg_stream stream, const float* boxes_dev, const
                 what);
   MCG_CHECK_ARG(n == 0 || (boxes_dev && gaze_dev && image_of_dev && kind_dev && target_dev && t_dev && hit_dev && mutual_dev && flags_dev),
                 "%s: null pointer", what);
-  MCG_CHECK_ARG(m == 0 || (regions_dev && region_image_dev), "%s: null region table with m=%d", what, m);
+  if (poly) {
+    MCG_CHECK_ARG(num_vertices >= 0 && num_vertices <= MCG_ATTEND_VERTICES, "%s: 0 .. %d vertices per call (got %d)", what, MCG_ATTEND_VERTICES,
+                  num_vertices);
+    MCG_CHECK_ARG(m == 0 || (region_start_dev && region_image_dev), "%s: null region table with m=%d", what, m);
+    MCG_CHECK_ARG(num_vertices == 0 || regions_dev, "%s: null vertex table with num_vertices=%d", what, num_vertices);
+  } else {
+    MCG_CHECK_ARG(m == 0 || (regions_dev && region_image_dev), "%s: null region table with m=%d", what, m);
+  }
   if (n == 0) return MCG_OK;
   const dim3 grid((n + MCG_ATTEND_THREADS - 1) / MCG_ATTEND_THREADS), block(MCG_ATTEND_THREADS);
-  hipLaunchKernelGGL(gaze_targets_kernel, grid, block, 0, (hipStream_t)stream, boxes_dev, gaze_dev, gaze_stride, image_of_dev, n, regions_dev,
-                     region_image_dev, m, region_period, expand, camera_cos2, kind_dev, target_dev, t_dev, hit_dev, flags_dev);
+  if (poly) {
+    hipLaunchKernelGGL(gaze_targets_poly_kernel, grid, block, 0, (hipStream_t)stream, boxes_dev, gaze_dev, gaze_stride, image_of_dev, n, regions_dev,
+                       num_vertices, region_start_dev, region_image_dev, m, region_period, expand, camera_cos2, kind_dev, target_dev, t_dev, hit_dev,
+                       flags_dev);
+  } else {
+    hipLaunchKernelGGL(gaze_targets_kernel, grid, block, 0, (hipStream_t)stream, boxes_dev, gaze_dev, gaze_stride, image_of_dev, n, regions_dev,
+                       region_image_dev, m, region_period, expand, camera_cos2, kind_dev, target_dev, t_dev, hit_dev, flags_dev);
+  }
   MCG_CHECK_LAUNCH(what);
   hipLaunchKernelGGL(gaze_mutual_kernel, grid, block, 0, (hipStream_t)stream, kind_dev, target_dev, n, mutual_dev);
-  MCG_CHECK_LAUNCH("mcg_gaze_targets (mutual)");
+  MCG_CHECK_LAUNCH(poly ? "mcg_gaze_targets_poly (mutual)" : "mcg_gaze_targets (mutual)");
   return MCG_OK;
+}
+
+extern "C" int mcg_gaze_targets(mcg_stream stream, const float* boxes_dev, const float* gaze_dev, int gaze_stride, const int32_t* image_of_dev, int n,
+                                const float* regions_dev, const int32_t* region_image_dev, int m, int region_period, double expand, double camera_cos2,
+                                int32_t* kind_dev, int32_t* target_dev, float* t_dev, float* hit_dev, int32_t* mutual_dev, int32_t* flags_dev) {
+  return gaze_targets_launch("mcg_gaze_targets", false, stream, boxes_dev, gaze_dev, gaze_stride, image_of_dev, n, regions_dev, 0, nullptr,
+                             region_image_dev, m, region_period, expand, camera_cos2, kind_dev, target_dev, t_dev, hit_dev, mutual_dev, flags_dev);
+}
+
+extern "C" int mcg_gaze_targets_poly(mcg_stream stream, const float* boxes_dev, const float* gaze_dev, int gaze_stride, const int32_t* image_of_dev,
+                                     int n, const float* region_xy_dev, int num_vertices, const int32_t* region_start_dev,
+                                     const int32_t* region_image_dev, int m, int region_period, double expand, double camera_cos2, int32_t* kind_dev,
+                                     int32_t* target_dev, float* t_dev, float* hit_dev, int32_t* mutual_dev, int32_t* flags_dev) {
+  return gaze_targets_launch("mcg_gaze_targets_poly", true, stream, boxes_dev, gaze_dev, gaze_stride, image_of_dev, n, region_xy_dev, num_vertices,
+                             region_start_dev, region_image_dev, m, region_period, expand, camera_cos2, kind_dev, target_dev, t_dev, hit_dev, mutual_dev,
+                             flags_dev);
 }

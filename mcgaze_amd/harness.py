@@ -901,8 +901,9 @@ def run_head_video(engine, pipeline, frames, boxes_per_frame=None, max_len=100, 
     the boxes and the gaze ``arrow`` comes from.  Every record gains, per frame: target_kind int32 [L] (attention.KIND_NONE / KIND_HEAD /
     KIND_REGION / KIND_CAMERA), target_id (a list: the ``id`` of the record of the person looked at, else None), target_region int32 [L] (the
     index into regions, else -1), target_hit f32 [L,2] (where the ray from the head's centre enters the target, in frame pixels) and mutual
-    int32 [L] (the two look at each other).  The regions apply to every frame.  Decided in the image plane; expand and camera_angle are
-    conventions, not tuned on data.
+    int32 [L] (the two look at each other).  The regions apply to every frame.  regions may be the mixed list of attention.region_polygons:
+    an item is a rectangle [x1, y1, x2, y2] or a polygon [[x, y], ...] of 3 .. 32 vertices (mcg_gaze_targets_poly); target_region indexes
+    that list.  Decided in the image plane; expand and camera_angle are conventions, not tuned on data.
     dwell: None (everything above), True, or dict(enter=3, exit=2); it needs ``attention`` (ValueError without): how LONG every person looks at
     what (pipeline.gaze_dwell, mcg_gaze_dwell; include/mcgaze_hip.h, "gaze dwell").  The columns are the records; the frames go in chunks of
     at most 65536 // records with the state carried between them.  Every record gains, per frame, dwell_kind and dwell_frames int32 [L] (the

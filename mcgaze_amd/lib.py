@@ -38,7 +38,7 @@ EXPORTS = ['mcg_abi_version', 'mcg_build_id', 'mcg_last_error', 'mcg_device_info
            'mcg_preprocess_head_crops_nv12', 'mcg_draw_gaze_arrows', 'mcg_draw_gaze_arrows_nv12',
            'mcg_detect_heads_workspace_bytes', 'mcg_detect_heads', 'mcg_letterbox_frames', 'mcg_letterbox_frames_nv12',
            'mcg_track_state_bytes', 'mcg_track_heads', 'mcg_track_heads_motion', 'mcg_live_slots', 'mcg_live_gate', 'mcg_live_lanes', 'mcg_live_gate_lanes',
-           'mcg_deferred_pyramid_state', 'mcg_inner_block_neighbours', 'mcg_gaze_targets', 'mcg_gaze_dwell',
+           'mcg_deferred_pyramid_state', 'mcg_inner_block_neighbours', 'mcg_gaze_targets', 'mcg_gaze_dwell', 'mcg_gaze_targets_poly',
            'mcg_pointwise_stream', 'mcg_pointwise_dyn', 'mcg_pointwise_pair']
 LETTERBOX_U8, LETTERBOX_F16, LETTERBOX_F32 = 0, 1, 2             # enum order of include/mcgaze_hip.h
 
@@ -186,7 +186,8 @@ def load():
     lib.mcg_live_lanes.argtypes = [vp, vp, i, i, i, i, i, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.mcg_live_gate_lanes.argtypes = [vp, vp, vp, vp, i, i, i, i, i, vp, i, i, i, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.mcg_gaze_targets.argtypes = [vp, vp, vp, i, vp, i, vp, vp, i, i, C.c_double, C.c_double, vp, vp, vp, vp, vp, vp]
-    lib.mcg_gaze_dwell.argtypes = [vp, vp, vp, vp, vp, vp, i, i, i, i, i, vp, vp, i, vp, vp, vp, i, vp]
+    lib.mcg_gaze_targets_poly.argtypes = [vp, vp, vp, i, vp, i, vp, i, vp, vp, i, i, C.c_double, C.c_double, vp, vp, vp, vp, vp, vp]
+    lib.mcg_gaze_dwell.argtypes =[vp, vp, vp, vp, vp, vp, i, i, i, i, i, vp, vp, i, vp, vp, vp, i, vp]
     lib.mcg_engine_set_option.argtypes = [vp, C.c_char_p, i]
     lib.mcg_engine_profile_start.argtypes = [vp, i]
     lib.mcg_engine_profile_stop.argtypes = [vp, C.POINTER(i), C.POINTER(C.c_float), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(i), C.POINTER(i), i]

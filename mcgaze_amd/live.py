@@ -30,7 +30,7 @@ import numpy as np
 import torch
 
 from . import lib as L
-from .attention import KIND_HEAD, _attention_options, _dwell_options
+from .attention import KIND_HEAD, PolyRegions, _attention_options, _dwell_options
 from .engine import _upload_table
 from .harness import _host, check_smooth
 from .head_detect import TRACK_HEADER_WORDS, TRACK_MAX_SLOTS, TRACK_SLOT_WORDS, _track_motion, _track_params, track_state_words
@@ -328,7 +328,9 @@ class LiveGaze:
     2 region, 3 camera), target (the slot of the person looked at -- with lanes their lane --, or the region's index, else -1), target_id (that
     person's track_id, else 0), target_t, target_hit [.., 2] (where the ray from the head's centre enters the target, in frame pixels) and
     mutual (the two look at each other), shaped like track_id.  regions: a list of Q tables [m_q, 4] of rectangles x1 y1 x2 y2 in frame
-    pixels, one per camera (None: none there), uploaded once; a region's index counts through the cameras' tables in order.  Targets are
+    pixels, one per camera (None: none there), uploaded once; a region's index counts through the cameras' tables in order.  A camera's
+    table may also be the mixed list of attention.region_polygons -- rectangles and polygons [[x, y], ...] of 3 .. 32 vertices, a screen seen
+    off-axis, an L-shaped shelf --: then the call is mcg_gaze_targets_poly, and a polygon is a region index like any other.  Targets are
     decided in the image plane, and expand / camera_angle are conventions, not tuned on data.  Still no wait for the device, no copy to the
     host.
 
@@ -384,9 +386,11 @@ class LiveGaze:
         self.attention = None
         if attention is not None:                                # the regions go up once: region_image = camera, matched through region_period = Q
             regions, region_image, options = attention
-            self.attention = dict(options, regions=torch.from_numpy(regions).to(self.dev), region_image=torch.from_numpy(region_image).to(self.dev))
+            up = lambda t: torch.from_numpy(t).to(self.dev)
+            regions = PolyRegions(*map(up, regions)) if isinstance(regions, PolyRegions) else up(regions)      # (a polygon somewhere: the vertex form)
+            self.attention = dict(options, regions=regions, region_image=up(region_image))
         if self.dwell is not None:
-            self.dwell_state, self.region_frames = pipeline.dwell_state(n, device=self.dev), new(len(attention[0]))
+            self.dwell_state, self.region_frames = pipeline.dwell_state(n, device=self.dev), new(len(attention[1]))
 
     def _call(self, name, *args):
         """One entry of the library on the current stream: a tensor goes as its address, None as a null pointer, an int as it is."""

@@ -35,7 +35,7 @@ import torch
 from . import lib as L
 from .arrows import (ARROW_COLOR, ARROW_COORD, ARROW_SIDE, _arrow_colors, _arrow_params, _arrow_rows,  # noqa: F401
                      arrow_segments, draw_arrows_host, segment_coverage)
-from .attention import _check_counts, _region_tables, _target_params, gaze_targets_host  # noqa: F401
+from .attention import PolyRegions, _check_counts, _holds_polygon, _poly_tables, _region_tables, _target_params, gaze_targets_host, region_polygons  # noqa: F401
 from .attention import _row_tables as _target_rows
 from .attention import DWELL_ENTER, DWELL_EXIT, _dwell_counts, _dwell_params, _dwell_tables, gaze_dwell_host  # noqa: F401
 from .frame_cache import FrameCache, _DecodeProcs, decode_image  # noqa: F401
@@ -732,7 +732,10 @@ class DevicePipeline:
         boxes [n,4], gaze [n,>=3], image_of [n] (None: one picture): CUDA tensors are read where they are -- an f32 gaze with packed rows, the
         [n,3] ``fused`` of a results='device' stream or a wider table, has its row stride taken from the tensor; other views are made contiguous
         -- and numpy tables go up through the staging ring (a host table next to a device one is moved with torch).  regions [m,4] and
-        region_image [m] (None: -1, every picture) likewise; region_period as in the header.  Options and shapes are checked on the host
+        region_image [m] (None: -1, every picture) likewise; region_period as in the header.  regions may also be the mixed list of
+        ``attention.region_polygons`` (rectangles and polygons of 3 .. 32 vertices) or an ``attention.PolyRegions(xy [V,2], start [m+1])`` of
+        host or device tables: then the call is mcg_gaze_targets_poly ("gaze targets, polygonal regions"), and what ``start`` holds is
+        contents, never an error.  An [m,4] table or a list of 4-number items means rectangles, as ever.  Options and shapes are checked on the host
         before anything is launched (TypeError / ValueError); device tables are not read back: a row that cannot be used comes back with
         flag 2.  With device tables the call touches the host nowhere and can be captured in a graph.
         -> (kind, target [n] int32, t [n] f32, hit [n,2] f32, mutual, flags [n] int32) on the device."""
@@ -742,11 +745,18 @@ class DevicePipeline:
         dev = _device(device, 'mcg_gaze_targets')
         on_device = lambda t: isinstance(t, torch.Tensor) and t.is_cuda
         rows_there = any(on_device(t) for t in (boxes, gaze, image_of))
-        regions_there = any(on_device(t) for t in (regions, region_image))
+        if _holds_polygon(regions):
+            regions = region_polygons(regions)
+        poly = isinstance(regions, PolyRegions)                   # the vertex form: mcg_gaze_targets_poly; anything else is today's rectangles
+        xy, start = regions if poly else (None, None)
+        regions_there = any(on_device(t) for t in ((xy, start, region_image) if poly else (regions, region_image)))
         if not rows_there:
             boxes, gaze, image_of = _target_rows(who, boxes, gaze, image_of)
         if not regions_there:
-            regions, region_image = _region_tables(who, regions, region_image)
+            if poly:
+                xy, start, region_image = _poly_tables(who, regions, region_image)
+            else:
+                regions, region_image = _region_tables(who, regions, region_image)
         with torch.cuda.device(dev):
             main = _caller_stream(stream, dev)
             with torch.cuda.stream(main):
@@ -765,27 +775,41 @@ class DevicePipeline:
                         raise ValueError(f'{who}: image_of must be [{n}], one per row; got {tuple(image_of.shape)}')
                 n = int(boxes.shape[0])
                 if regions_there:
-                    if regions is None:
-                        raise ValueError(f'{who}: region_image without regions')
-                    regions = there(regions, torch.float32).contiguous()
-                    if regions.ndim != 2 or regions.shape[1] != 4:
-                        raise ValueError(f'{who}: regions must be [m, 4] x1 y1 x2 y2, got {tuple(regions.shape)}')
-                    m = int(regions.shape[0])
+                    if poly:
+                        xy, start = there(xy, torch.float32).contiguous(), there(start, torch.int32).contiguous()
+                        if xy.ndim != 2 or xy.shape[1] != 2 or start.ndim != 1 or start.shape[0] < 1:
+                            raise ValueError(f'{who}: PolyRegions is xy [V, 2] and start [m + 1], got {tuple(xy.shape)} and {tuple(start.shape)}')
+                        m = int(start.shape[0]) - 1
+                    else:
+                        if regions is None:
+                            raise ValueError(f'{who}: region_image without regions')
+                        regions = there(regions, torch.float32).contiguous()
+                        if regions.ndim != 2 or regions.shape[1] != 4:
+                            raise ValueError(f'{who}: regions must be [m, 4] x1 y1 x2 y2, got {tuple(regions.shape)}')
+                        m = int(regions.shape[0])
                     region_image = torch.full((m,), -1, dtype=torch.int32, device=dev) if region_image is None else \
                         there(region_image, torch.int32).contiguous()
                     if tuple(region_image.shape) != (m,):
                         raise ValueError(f'{who}: region_image must be [{m}], one per region; got {tuple(region_image.shape)}')
-                m = int(regions.shape[0])
-                _check_counts(who, n, m)
+                m = int(region_image.shape[0])
+                V = int(xy.shape[0]) if poly else 0
+                _check_counts(who, n, m, V)
                 new = lambda *shape, dtype=torch.int32: torch.empty(*shape, dtype=dtype, device=dev)
                 out = (new(n), new(n), new(n, dtype=torch.float32), new(n, 2, dtype=torch.float32), new(n), new(n))
                 if n == 0:
                     return out
-                st, _, (boxes_ptr, gaze_ptr, image_of_ptr, regions_ptr, region_image_ptr) = self._ring.upload(
-                    [], (boxes, gaze, image_of, regions if m else None, region_image if m else None), dev, main)
                 vp = C.c_void_p
-                L.check(lib.mcg_gaze_targets(vp(main.cuda_stream), vp(boxes_ptr), vp(gaze_ptr), gaze_stride, vp(image_of_ptr), n, vp(regions_ptr),
-                                             vp(region_image_ptr), m, period, expand, cos2, *(vp(t.data_ptr()) for t in out)), 'mcg_gaze_targets')
+                if poly:
+                    st, _, (boxes_ptr, gaze_ptr, image_of_ptr, xy_ptr, start_ptr, region_image_ptr) = self._ring.upload(
+                        [], (boxes, gaze, image_of, xy if V else None, start if m else None, region_image if m else None), dev, main)
+                    L.check(lib.mcg_gaze_targets_poly(vp(main.cuda_stream), vp(boxes_ptr), vp(gaze_ptr), gaze_stride, vp(image_of_ptr), n, vp(xy_ptr), V,
+                                                      vp(start_ptr), vp(region_image_ptr), m, period, expand, cos2, *(vp(t.data_ptr()) for t in out)),
+                            'mcg_gaze_targets_poly')
+                else:
+                    st, _, (boxes_ptr, gaze_ptr, image_of_ptr, regions_ptr, region_image_ptr) = self._ring.upload(
+                        [], (boxes, gaze, image_of, regions if m else None, region_image if m else None), dev, main)
+                    L.check(lib.mcg_gaze_targets(vp(main.cuda_stream), vp(boxes_ptr), vp(gaze_ptr), gaze_stride, vp(image_of_ptr), n, vp(regions_ptr),
+                                                 vp(region_image_ptr), m, period, expand, cos2, *(vp(t.data_ptr()) for t in out)), 'mcg_gaze_targets')
                 if st is not None:
                     st.read_by(main)
         return out

@@ -9,6 +9,8 @@ usage: attention_bench.py [--shapes 8x1,64x8,1024x64] [--regions 16] [--calls 20
    boxes in 1280 x 720 pictures, random unit gaze, --regions rectangles that apply to every picture; every table in device memory.
      device:    DevicePipeline.gaze_targets on the device tables (mcg_gaze_targets: two launches, nothing read back).
      readback:  the route before: boxes, gaze and image_of copied to the host, attention.gaze_targets_host, the six tables uploaded.
+     quads, octagons:  the same rows and the same number of regions as polygons (mcg_gaze_targets_poly): every rectangle sheared into a
+                quadrilateral, and with its corners cut into an 8-gon; vertex tables in device memory.
    --runs times: --rounds rounds alternated, each --calls calls bracketed by synchronize; the median round of each run, us per call.
 2. The tick.  tools/live_bench.py's shapes and walkers (Q x S x people, 720 x 1280 frames, 448 x 448 crops, clip 7 / stride 4, synthetic
    weights, f16x3, smooth 0.6): LiveGaze.tick without and with attention=True in ONE process, two passes of each alternated, each --warmup
@@ -30,7 +32,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from live_bench import CHAIN, CLIP, DEV, FRAME_H, FRAME_W, STRIDE, timed, walkers  # noqa: E402
 from mcgaze_amd import lib, synth  # noqa: E402
 from mcgaze_amd import pipeline as P  # noqa: E402
-from mcgaze_amd.attention import gaze_targets_host  # noqa: E402
+from mcgaze_amd.attention import PolyRegions, gaze_targets_host, region_polygons  # noqa: E402
 from mcgaze_amd.engine import HipEngine  # noqa: E402
 from mcgaze_amd.live import LiveGaze  # noqa: E402
 
@@ -48,10 +50,25 @@ def tables(rs, n, pictures, m):
     return boxes, gaze, image_of, regions
 
 
+def polygons(regions, corners):
+    """The rectangles as quadrilaterals (sheared by a fifth of the width) or as 8-gons (a quarter of each side cut off every corner)."""
+    out = []
+    for x1, y1, x2, y2 in regions.tolist():
+        w, h = x2 - x1, y2 - y1
+        if corners == 4:
+            out.append([[x1 + w // 5, y1], [x2, y1], [x2 - w // 5, y2], [x1, y2]])
+        else:
+            a, b = w // 4, h // 4
+            out.append([[x1 + a, y1], [x2 - a, y1], [x2, y1 + b], [x2, y2 - b], [x2 - a, y2], [x1 + a, y2], [x1, y2 - b], [x1, y1 + b]])
+    return region_polygons(out)
+
+
 def bench_call(pipe, shape, m, calls, rounds, runs, rs):
     n, pictures = shape
-    boxes, gaze, image_of, regions = (torch.from_numpy(t).to(DEV) for t in tables(rs, n, pictures, m))
+    host = tables(rs, n, pictures, m)
+    boxes, gaze, image_of, regions = (torch.from_numpy(t).to(DEV) for t in host)
     region_image = torch.full((m,), -1, dtype=torch.int32, device=DEV)
+    poly = {name: PolyRegions(*(torch.from_numpy(t).to(DEV) for t in polygons(host[3], c))) for name, c in (('quads', 4), ('octagons', 8))}
 
     def device():
         return pipe.gaze_targets(boxes, gaze, image_of, regions=regions, region_image=region_image, device=DEV)
@@ -61,12 +78,19 @@ def bench_call(pipe, shape, m, calls, rounds, runs, rs):
                                  region_image=region_image.cpu().numpy())
         return tuple(torch.from_numpy(t).to(DEV) for t in host)
 
+    def polygon_route(name):
+        return lambda: pipe.gaze_targets(boxes, gaze, image_of, regions=poly[name], region_image=region_image, device=DEV)
+
     same = all(torch.equal(a, b) for a, b in zip(device(), readback()))
-    out = dict(rows=n, pictures=pictures, regions=m, equal=bool(same), us=dict(device=[], readback=[]))
+    for name in poly:                                             # the polygon legs against the twin over the same vertex tables
+        twin = gaze_targets_host(host[0], host[1], host[2], regions=PolyRegions(*(t.cpu().numpy() for t in poly[name])))
+        same = same and all(torch.equal(a.cpu(), torch.from_numpy(b)) for a, b in zip(polygon_route(name)(), twin))
+    routes = (('device', device), ('readback', readback), ('quads', polygon_route('quads')), ('octagons', polygon_route('octagons')))
+    out = dict(rows=n, pictures=pictures, regions=m, equal=bool(same), us={name: [] for name, _ in routes})
     for _ in range(runs):
-        us = dict(device=[], readback=[])
+        us = {name: [] for name, _ in routes}
         for _ in range(rounds):
-            for name, fn in (('device', device), ('readback', readback)):
+            for name, fn in routes:
                 us[name].append(timed(fn, calls) * 1e3)
         for name in us:
             out['us'][name].append(round(float(np.median(us[name])), 2))
@@ -124,9 +148,11 @@ def main():
                 calls_per_round=a.calls, rounds=a.rounds, runs=a.runs, steps=a.steps, warmup=a.warmup, call=calls, tick=ticks)
     print(json.dumps(line))
     if a.out:
-        rows = ['| rows x pictures, regions | device us / call (runs) | read-back us / call (runs) | read-back / device | equal |', '|---|---|---|---|---|']
+        rows = ['| rows x pictures, regions | device us / call (runs) | read-back us / call (runs) | read-back / device | quadrilaterals us / call (runs) | '
+                '8-gons us / call (runs) | equal |', '|---|---|---|---|---|---|---|']
         for c in calls:
-            rows.append(f"| {c['rows']} x {c['pictures']}, {c['regions']} | {c['us']['device']} | {c['us']['readback']} | {c['readback_over_device']} | {c['equal']} |")
+            rows.append(f"| {c['rows']} x {c['pictures']}, {c['regions']} | {c['us']['device']} | {c['us']['readback']} | {c['readback_over_device']} | "
+                        f"{c['us']['quads']} | {c['us']['octagons']} | {c['equal']} |")
         more = ['| Q x S, people | rows a call | plain ms / tick (passes) | attention=True ms / tick (passes) | added ms | plain: spread between its passes |',
                 '|---|---|---|---|---|---|']
         for t in ticks:

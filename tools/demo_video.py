@@ -35,7 +35,9 @@ pipeline.letterbox and pipeline.detect_heads); the network is the caller's.
 --attention: what every person looks at in every frame (harness.run_head_video(attention=...), pipeline.gaze_targets on the device): each
 entry gains per frame `target_kind` (0 none, 1 another person, 2 a region, 3 the camera), `target_id` (the [segment, person] looked at, or
 null), `target_region`, `target_hit` (where the gaze ray enters the target, in frame pixels) and `mutual`.  --regions FILE.json: a JSON list
-of rectangles [[x1, y1, x2, y2], ...] in frame pixels -- a screen, a shelf, a door.  Decided in the image plane, with conventional,
+of regions in frame pixels -- a screen, a shelf, a door --, each a rectangle [x1, y1, x2, y2] or a polygon [[x, y], [x, y], ...] of 3 .. 32
+vertices in either winding (a screen seen off-axis is a quadrilateral, a shelf beside a pillar an L: even-odd rule, so a notch is outside);
+`target_region` is the index into that list.  Decided in the image plane, with conventional,
 untuned defaults (a looked-at head box grown by 0.25 of its longer side, a 10 degree cone for the camera).
 --dwell [ENTER,EXIT], with --attention: how LONG they look (harness.run_head_video(dwell=...), pipeline.gaze_dwell on the device): each entry
 gains per frame `dwell_kind` and `dwell_frames` (the current target and its frames so far) and `episodes`, a list of {kind, target_id or
@@ -177,7 +179,7 @@ def main(argv=None):
                     help='--track with the constant-velocity motion model: a head missed for a few frames is looked for where it was going '
                          '(default 0.5,1.0: conventional alpha-beta values, not tuned on data)')
     ap.add_argument('--attention', action='store_true', help='add what every person looks at: another person, a region of --regions, the camera')
-    ap.add_argument('--regions', default=None, metavar='FILE.json', help='rectangles [[x1, y1, x2, y2], ...] in frame pixels, of --attention')
+    ap.add_argument('--regions', default=None, metavar='FILE.json', help='regions of --attention in frame pixels: a JSON list of rectangles [x1, y1, x2, y2] and polygons [[x, y], ...] of 3 .. 32 vertices')
     ap.add_argument('--dwell', nargs='?', const='', default=None, metavar='ENTER,EXIT',
                     help='--attention with how long every look lasts: episodes with a start, a length and an end (default 3,2: conventions, not '
                          'tuned on data)')
