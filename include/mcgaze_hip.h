@@ -1030,7 +1030,7 @@ int mcg_live_gate_lanes(mcg_stream s, const int32_t* ring_id_dev, const float* r
  * whatever they hold nothing outside the given arrays is read or written.  Heads are searched in tiles of 256 rows and a tile whose
  * image_of range holds no picture a workgroup asks about is skipped: tables whose pictures come in ascending row order (LiveGaze's
  * [k, Q, S]) cost one picture per row.  mcgaze_amd/attention.py::gaze_targets_host is the same on the host, bit for bit.
- * Out of scope: camera intrinsics or depth, arrows coloured or cut at the hit point.  (How long a target is looked at: "gaze dwell" below;
+ * Out of scope: camera intrinsics or depth, arrows cut at the hit point.  (Coloured arrows: "attention overlay" below.  How long a target is looked at: "gaze dwell" below;
  * regions that are polygons: "gaze targets, polygonal regions" below.) */
 int mcg_gaze_targets(mcg_stream s, const float* boxes_dev, const float* gaze_dev, int gaze_stride, const int32_t* image_of_dev, int n,
                      const float* regions_dev, const int32_t* region_image_dev, int m, int region_period, double expand, double camera_cos2,
@@ -1131,12 +1131,80 @@ int mcg_gaze_dwell(mcg_stream s, const int32_t* person_dev, const int32_t* tag_d
  * null table returns MCG_ERR_ARG before any launch.  The regions are searched in tiles of 256 with the picture-range skip of the heads; a
  * polygon's vertices are read through an address that is the same in every thread of the workgroup.  No bounding-box reject: every edge
  * is tested.  mcgaze_amd/attention.py::gaze_targets_host(region_start=...) is the same on the host, bit for bit.
- * Out of scope: region outlines drawn on the device, arrows cut at the hit point, camera intrinsics or depth. */
+ * Out of scope: arrows cut at the hit point, camera intrinsics or depth.  (Region outlines and coloured arrows: "attention overlay" below.) */
 #define MCG_ATTEND_POLY_VERTS 32
 int mcg_gaze_targets_poly(mcg_stream s, const float* boxes_dev, const float* gaze_dev, int gaze_stride, const int32_t* image_of_dev, int n,
                           const float* region_xy_dev, int num_vertices, const int32_t* region_start_dev, const int32_t* region_image_dev, int m,
                           int region_period, double expand, double camera_cos2, int32_t* kind_dev, int32_t* target_dev, float* t_dev,
                           float* hit_dev, int32_t* mutual_dev, int32_t* flags_dev);
+
+/* ---------------------------------------------------------------- attention overlay (additions to ABI 19; nothing above changes)
+ * What "gaze targets" found, drawn where it was found: the outlines of the marked regions (lit where somebody looks at them), a sight line
+ * from every head to the point its look landed on, and the arrows of "annotated frames out" coloured by what they point at -- IN PLACE into
+ * packed BGR frames (mcg_draw_attention) or NV12 surfaces (mcg_draw_attention_nv12), from tables that are all in device memory: the frame
+ * table and rows of mcg_draw_gaze_arrows, kind / target / hit / mutual as mcg_gaze_targets(_poly) writes them, and the region tables of
+ * mcg_gaze_targets_poly (a rectangle is a 2-vertex region).  Three launches (region_active cleared; a plan kernel, double and uncontracted;
+ * a gather kernel over (image, pixel tile)), no allocation, no host sync, graph-capturable, no atomics.
+ * STROKES.  Every stroke is a set of segments of one thickness t under COVERAGE of "annotated frames out" (the capsule test in 64-bit
+ * integers; every end point within [-8191, 8191], frames of at most 8192 a side, t <= 255).  The strokes of a call are numbered: region j
+ * is stroke j, the sight line of row k stroke m + k, the arrow of row k stroke m + n + k -- three LAYERS, low to high, ascending index in
+ * each.  A pixel takes the colour of the HIGHEST-numbered stroke that covers it, whatever the launch geometry; a pixel no stroke covers is
+ * not written.  Each layer may be empty, and a thickness of 0 switches its layer off (nothing of it is drawn; flags, region_flags and
+ * region_active are written as ever).
+ * 1. REGION OUTLINES.  Region j is usable iff it is a USABLE REGION of "gaze targets, polygonal regions" (offsets checked before the first
+ * vertex load; c == 2 or 3 <= c <= 32; every coordinate finite; a rectangle not inverted) AND every rounded coordinate rint((double)x)
+ * (half to even) lies in [-8191, 8191].  Otherwise region_flags[j] = 2, nothing is drawn for it and nothing outside region_xy[0 .. V) is
+ * read: what the tables hold is never an error.  The corners of a rectangle are (x1, y1) (x2, y1) (x2, y2) (x1, y2), those of a polygon
+ * its vertices, all rounded; the outline is the c edges v[k] -> v[(k + 1) % c] (4 for a rectangle) with t = region_thickness.  It is drawn
+ * into picture p iff region_image[j] < 0, or == p, or region_period > 0 and == p % region_period.  Its pixels are bounded by the h, w of
+ * the picture drawn into (one region may apply to pictures of different sizes).
+ * region_active[p][j] = 1 iff some row k has image_of[k] == p, kind[k] == 2 and target[k] == j (whatever the row's flag), else 0; it is
+ * written for every (p, j), drawable or not.  The outline's colour in picture p is palette[6] where region_active[p][j], else palette[5].
+ * 2. SIGHT LINES.  Row k gets one iff its arrow is drawable (flags[k] == 0), kind[k] is 1 or 2, and hx = rint((double)hit[k][0]),
+ * hy = rint((double)hit[k][1]) are finite and in [-8191, 8191]: one segment from the arrow plan's centre (cx, cy) to (hx, hy) with
+ * t = line_thickness, in the row's colour.  A row that fails only the hit test keeps its arrow.  target[k] is read only where kind[k] == 2.
+ * 3. ARROWS.  The ARROW PLAN, HEAD STROKES and FLAGS of "annotated frames out", term for term; flags[k] is that flag.  min_thickness == 0
+ * switches the layer off: the plan is then made with a minimum of 0 and serves the flags and the sight lines only.
+ * The row's colour is palette[mutual[k] != 0 ? 4 : (1 <= kind[k] <= 3 ? kind[k] : 0)]: any other kind word is "none".
+ * NV12 follows "annotated frames out": every covered luma pixel gets the Y of ITS highest stroke; a chroma pair is written iff any of its
+ * four luma pixels is covered, with the (U, V) of the highest stroke among the four.
+ * ANCHOR.  With m == 0, kind all zero and palette[0] = color the call writes the bytes and flags of mcg_draw_gaze_arrows(_nv12).
+ *   images_dev, num_images, max_h, max_w, boxes_dev, gaze_dev, gaze_stride, image_of_dev, n, length, thickness_ratio, tip_length: as
+ *                mcg_draw_gaze_arrows takes them; an image that is not writable or larger than (max_h, max_w) gets no stroke at all
+ *   kind_dev, target_dev, mutual_dev DEVICE int32 [n];  hit_dev DEVICE f32 [n][2]
+ *   region_xy_dev DEVICE f32 [V][2] (NULL iff V == 0);  region_start_dev int32 [m + 1], region_image_dev int32 [m] (NULL iff m == 0)
+ *   palette      HOST uint8 [7][3]: B, G, R (NV12: Y, U, V) of none, head, region, camera, mutual, region outline, region outline looked at
+ *   min_thickness, line_thickness, region_thickness: each 0 .. 255
+ *   workspace_dev DEVICE, written: the plan -- (m + 2 n) mcg_stroke_desc in stroke order, then the rounded vertices int32 [m][32][2];
+ *                workspace_bytes >= 96 * (m + 2 n) + 256 * m
+ *   flags_dev DEVICE int32 [n];  region_flags_dev DEVICE int32 [m];  region_active_dev DEVICE int32 [num_images][m]  (all written)
+ * n <= 65535, m <= 4096, V <= 65536, num_images * m <= 2^20, frames of at most 8192 a side: anything else, a null table or a workspace too
+ * small returns MCG_ERR_ARG before any launch; n == 0 and m == 0 returns MCG_OK without one.  No byte outside [0, h) x [0, w) of any plane
+ * is touched, padding included, for ANY table contents.  Every wave of the gather grid reads the plan in (m + 2 n) / 64 slices, and a large
+ * region's box covers many tiles that each test up to 32 capsules per pixel: made for the tens of heads and regions of a video frame.
+ * mcgaze_amd/arrows.py::draw_attention_host is the same on the host, bit for bit.  Out of scope: arrows cut at the hit point, filled
+ * regions, text. */
+typedef struct mcg_stroke_desc {
+  int seg[3][2][2];         /* a sight line: seg[0]; an arrow: shaft, stroke, stroke -- (from, to) x (x, y); a region: unused (its vertices follow the plan) */
+  int thickness;
+  int x0, y0, x1, y1;       /* bounding box of the covered pixels, half open; a row's is clipped to its frame, a region's only at 0 */
+  int image, flag;          /* a row: image_of; a region: region_image.  flag 0: drawn; 2: not */
+  int layer, count;         /* 0 region outline, 1 sight line, 2 arrow; the number of corners (layer 0) or segments */
+  unsigned color, color_active;   /* c0 | c1 << 8 | c2 << 16; color_active: a region outline that is looked at */
+  int reserved;
+} mcg_stroke_desc;
+int mcg_draw_attention(mcg_stream s, const mcg_image_desc* images_dev, int num_images, int max_h, int max_w, const float* boxes_dev,
+                       const float* gaze_dev, int gaze_stride, const int32_t* image_of_dev, int n, const int32_t* kind_dev, const int32_t* target_dev,
+                       const float* hit_dev, const int32_t* mutual_dev, const float* region_xy_dev, int num_vertices,
+                       const int32_t* region_start_dev, const int32_t* region_image_dev, int m, int region_period, const unsigned char* palette,
+                       double length, int min_thickness, double thickness_ratio, double tip_length, int line_thickness, int region_thickness,
+                       void* workspace_dev, size_t workspace_bytes, int32_t* flags_dev, int32_t* region_flags_dev, int32_t* region_active_dev);
+int mcg_draw_attention_nv12(mcg_stream s, const mcg_nv12_image_desc* images_dev, int num_images, int max_h, int max_w, const float* boxes_dev,
+                            const float* gaze_dev, int gaze_stride, const int32_t* image_of_dev, int n, const int32_t* kind_dev,
+                            const int32_t* target_dev, const float* hit_dev, const int32_t* mutual_dev, const float* region_xy_dev, int num_vertices,
+                            const int32_t* region_start_dev, const int32_t* region_image_dev, int m, int region_period, const unsigned char* palette,
+                            double length, int min_thickness, double thickness_ratio, double tip_length, int line_thickness, int region_thickness,
+                            void* workspace_dev, size_t workspace_bytes, int32_t* flags_dev, int32_t* region_flags_dev, int32_t* region_active_dev);
 
 /* ---------------------------------------------------------------- measurement aids (bench.py)
  * While armed, every launch of the contraction kernel made by THIS engine is bracketed by a hipEvent pair on its launch stream.

@@ -1,21 +1,29 @@
 """Gaze arrows on the host (include/mcgaze_hip.h, "annotated frames out"): the plan (``arrow_segments``), the capsule coverage
-(``segment_coverage``) and ``draw_arrows_host``, which draws in numpy what ``DevicePipeline.draw_arrows`` writes on the device, bit for bit."""
+(``segment_coverage``) and ``draw_arrows_host``, which draws in numpy what ``DevicePipeline.draw_arrows`` writes on the device, bit for bit.
+``draw_attention_host`` is the same for the attention overlay ("attention overlay": region outlines, sight lines, arrows coloured by their
+target), what ``DevicePipeline.draw_attention`` writes."""
 import numpy as np
 
+from . import attention as A
 from .nv12 import _nv12_planes, _pixel_format, bgr_to_yuv
 from .staging import _bgr_frame, _host_array
 
 ARROW_COLOR = (230, 253, 11)                                     # the demo's, BGR (MCGaze_demo/demo.ipynb, cell 5)
 ARROW_COORD, ARROW_SIDE = 8191, 8192                             # the bound under which the coverage test is exact in 64-bit integers
+# The overlay's default colours, B, G, R: none (the demo's arrow), head, region, camera, mutual, a region's outline, the outline of a region
+# that is looked at.  A convention, not tuned: seven colours that differ.
+OVERLAY_PALETTE = (ARROW_COLOR, (0, 165, 255), (0, 255, 0), (255, 0, 255), (0, 0, 255), (160, 160, 160), (0, 255, 255))
+OVERLAY_ACTIVE = 1 << 20                                         # num_images * m of mcg_draw_attention
 
 
-def _arrow_params(length=1.0, min_thickness=5, thickness_ratio=0.01, tip_length=0.1):
-    """The arrow parameters, validated (ValueError) -> (length, min_thickness, thickness_ratio, tip_length); the defaults are the demo's."""
+def _arrow_params(length=1.0, min_thickness=5, thickness_ratio=0.01, tip_length=0.1, lowest=1):
+    """The arrow parameters, validated (ValueError) -> (length, min_thickness, thickness_ratio, tip_length); the defaults are the demo's.
+    lowest: the least min_thickness (the overlay takes 0, "no arrows")."""
     length, thickness_ratio, tip_length = float(length), float(thickness_ratio), float(tip_length)
     if not all(np.isfinite(v) for v in (length, thickness_ratio, tip_length)):
         raise ValueError('length, thickness_ratio and tip_length must be finite')
-    if int(min_thickness) != min_thickness or not 1 <= int(min_thickness) <= 255:
-        raise ValueError(f'min_thickness must be an integer in 1 .. 255, got {min_thickness!r}')
+    if int(min_thickness) != min_thickness or not lowest <= int(min_thickness) <= 255:
+        raise ValueError(f'min_thickness must be an integer in {lowest} .. 255, got {min_thickness!r}')
     return length, int(min_thickness), thickness_ratio, tip_length
 
 
@@ -141,3 +149,172 @@ def draw_arrows_host(frames, boxes, gaze, image_of=None, color=None, pixel_forma
         else:
             out[int(image_of[k])][mask] = c
     return (out[0] if single else out), flags
+
+
+# ---------------------------------------------------------------- attention overlay (include/mcgaze_hip.h, "attention overlay")
+def _overlay_thickness(who, **values):
+    """line_thickness / region_thickness, validated (ValueError) -> ints in 0 .. 255; 0 switches the layer off."""
+    for name, v in values.items():
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= v <= 255:
+            raise ValueError(f'{who}: {name} must be an integer in 0 .. 255 (0: the layer is off), got {v!r}')
+    return [int(v) for v in values.values()]
+
+
+def _overlay_palette(who, palette, nv12, matrix):
+    """-> uint8 [7,3] as the entries take it: B, G, R, or with nv12 each entry converted once by bgr_to_yuv.  None: OVERLAY_PALETTE."""
+    c = np.asarray(OVERLAY_PALETTE if palette is None else _host_array(palette))
+    if c.dtype.kind not in 'iu' or c.shape != (7, 3) or c.min() < 0 or c.max() > 255:
+        raise ValueError(f'{who}: palette must be [7, 3] (B, G, R) integers in [0, 255] -- none, head, region, camera, mutual, outline, outline '
+                         f'looked at; got {c.dtype} {c.shape}')
+    c = c.astype(np.uint8)
+    return np.ascontiguousarray(np.stack([bgr_to_yuv(v, matrix) for v in c]).reshape(7, 3).astype(np.uint8) if nv12 else c)
+
+
+def _overlay_options(who, overlay, draw, attention):
+    """The ``overlay=`` option of LiveGaze and of run_head_video's draw dict, validated (ValueError) -> None (off) or the dict of
+    draw_attention's palette, line_thickness and region_thickness that were given.  It needs both ``draw`` and ``attention``."""
+    if overlay is None or overlay is False:
+        return None
+    if overlay is not True and not isinstance(overlay, dict):
+        raise ValueError(f'{who}: overlay is None, True or a dict of palette, line_thickness and region_thickness; got {overlay!r}')
+    opts = {} if overlay is True else dict(overlay)
+    if set(opts) - {'palette', 'line_thickness', 'region_thickness'}:
+        raise ValueError(f'{who}: overlay takes palette, line_thickness and region_thickness; got {sorted(opts)}')
+    if not draw or attention is None:
+        raise ValueError(f'{who}: overlay draws what attention found into the frames draw hands out: it needs both draw and attention')
+    _overlay_thickness(who, **{k: v for k, v in opts.items() if k != 'palette'})
+    _overlay_palette(who, opts.get('palette'), False, 'bt601')
+    return opts
+
+
+def _overlay_regions(who, regions, region_image):
+    """The three forms gaze_targets_host takes -- [m,4] rectangles, the mixed list of region_polygons, a PolyRegions -- as HOST vertex tables
+    -> (xy f32 [V,2], start int32 [m+1], region_image int32 [m]), checked as there."""
+    if A._holds_polygon(regions):
+        regions = A.region_polygons(regions)
+    if isinstance(regions, A.PolyRegions):
+        return A._poly_tables(who, regions, region_image)
+    r32, ri = A._region_tables(who, regions, region_image)
+    xy, start = A._as_vertices(r32)
+    return np.ascontiguousarray(xy), start, ri
+
+
+def _overlay_counts(who, n, m, vertices, images):
+    if n > 65535:
+        raise ValueError(f'{who}: at most 65535 rows per call (got {n})')
+    A._check_counts(who, 0, m, vertices)
+    if images * m > OVERLAY_ACTIVE:
+        raise ValueError(f'{who}: frames x regions must not exceed {OVERLAY_ACTIVE} (got {images} x {m})')
+
+
+def _overlay_targets(who, n, kind, target, hit, mutual):
+    """Host kind / target / mutual [n] integers and hit [n,2] -> (int32, int32, f32 [n,2], int32), checked (TypeError / ValueError)."""
+    out = []
+    for name, t in (('kind', kind), ('target', target), ('mutual', mutual)):
+        a = np.asarray(_host_array(t)).reshape(-1)
+        if a.size and a.dtype.kind not in 'iub':
+            raise TypeError(f'{who}: {name} must hold integers, got {a.dtype}')
+        if a.shape != (n,):
+            raise ValueError(f'{who}: {name} must be [{n}], one per row; got {a.shape}')
+        out.append(np.ascontiguousarray(a, dtype=np.int32))
+    h = np.asarray(_host_array(hit))
+    h = h.reshape(0, 2) if h.size == 0 else h
+    if h.shape != (n, 2) or h.dtype.kind not in 'fiu':
+        raise ValueError(f'{who}: hit must be [{n}, 2] numbers, got {h.dtype} {h.shape}')
+    return out[0], out[1], np.ascontiguousarray(h, dtype=np.float32), out[2]
+
+
+def region_outlines(xy, start):
+    """The outlines of the vertex tables (xy f32 [V,2], start [m+1]) as "attention overlay" draws them -> (corners: a list of m int64 [c,2]
+    arrays, None for an unusable region; region_flags int32 [m]).  Usable: the rule of gaze_targets' regions, and every coordinate rounded
+    (half to even, in double) within +-8191.  A rectangle's corners are (x1, y1) (x2, y1) (x2, y2) (x1, y2)."""
+    xy64 = np.asarray(xy, dtype=np.float32).astype(np.float64).reshape(-1, 2)
+    ok, first, count = A._usable_regions(xy64, np.asarray(start))
+    corners = []
+    for j in range(len(ok)):
+        v = np.rint(xy64[first[j]:first[j] + count[j]]) if ok[j] else None
+        if v is not None and (np.abs(v) <= ARROW_COORD).all():
+            v = v.astype(np.int64)
+            corners.append(np.array([v[0], (v[1, 0], v[0, 1]), v[1], (v[0, 0], v[1, 1])]) if len(v) == 2 else v)
+        else:
+            corners.append(None)
+    return corners, np.array([0 if c is not None else 2 for c in corners], dtype=np.int32)
+
+
+def draw_attention_host(frames, boxes, gaze, image_of, kind, target, hit, mutual, regions=None, region_image=None, region_period=0, palette=None,
+                        line_thickness=2, region_thickness=2, pixel_format='bgr', matrix='bt601', strict=False, **params):
+    """The attention overlay drawn with numpy: what DevicePipeline.draw_attention (mcg_draw_attention / mcg_draw_attention_nv12) writes on the
+    device, bit for bit (include/mcgaze_hip.h, "attention overlay").  Three layers, low to high, the higher index winning inside a layer: the
+    outlines of the regions (palette[6] in a picture where a row looks at the region, else palette[5]), a sight line from every head that
+    looks at a head or a region to its hit point, and draw_arrows_host's arrows in palette[4 if mutual else kind] (a kind outside 1 .. 3: 0).
+
+    frames, boxes, gaze, image_of, pixel_format, matrix, strict and params (length, min_thickness, thickness_ratio, tip_length): as for
+    draw_arrows_host; kind, target, mutual [n] integers and hit [n,2] as gaze_targets_host returns them; regions, region_image,
+    region_period as gaze_targets_host takes them ([m,4] rectangles, the mixed list of region_polygons, or a PolyRegions).  palette: [7,3]
+    B, G, R (None: OVERLAY_PALETTE, a convention); for NV12 each entry is converted once by bgr_to_yuv.  A thickness of 0 (line_thickness,
+    region_thickness, min_thickness) switches its layer off.
+    -> (annotated COPIES in the form given, flags int32 [n], region_flags int32 [m], region_active int32 [frames, m]).  A region that cannot be
+    used (region_flags 2) and a row flagged 2 change no byte; a hit that is not finite or beyond +-8191 drops the sight line only."""
+    who = 'draw_attention_host'
+    nv12, _ = _pixel_format(pixel_format, matrix)
+    line_thickness, region_thickness = _overlay_thickness(who, line_thickness=line_thickness, region_thickness=region_thickness)
+    _, _, period = A._target_params(region_period=region_period, who=who)
+    pal = _overlay_palette(who, palette, nv12, matrix)
+    single = not isinstance(frames, list)
+    frames = [frames] if single else frames
+    if nv12:
+        out = [tuple(np.array(p) for p in _nv12_planes(k, f)[:2]) for k, f in enumerate(frames)]
+        sizes = [y.shape for y, _ in out]
+    else:
+        out = [_bgr_frame(k, np.array(f)) for k, f in enumerate(frames)]
+        sizes = [a.shape[:2] for a in out]
+    n = len(np.asarray(_host_array(boxes)).reshape(-1, 4))
+    image_of = np.zeros(n, dtype=np.int32) if image_of is None or not np.size(_host_array(image_of)) else np.asarray(_host_array(image_of)).reshape(-1)
+    kind, target, hit, mutual = _overlay_targets(who, n, kind, target, hit, mutual)
+    xy, start, ri = _overlay_regions(who, regions, region_image)
+    m = len(ri)
+    _overlay_counts(who, n, m, len(xy), len(frames))
+    seg, t, flags = _arrow_rows(_host_array(boxes), _host_array(gaze), image_of, sizes, strict, lowest=0, **params)
+    min_thickness = _arrow_params(lowest=0, **params)[1]
+    corners, region_flags = region_outlines(xy, start)
+    region_active = np.zeros((len(frames), m), dtype=np.int32)
+    looks = (kind == 2) & (target >= 0) & (target < m) & (image_of >= 0) & (image_of < len(frames))
+    region_active[image_of[looks], target[looks]] = 1
+    row_color = np.where(mutual != 0, 4, np.where((kind >= 1) & (kind <= 3), kind, 0))
+    with np.errstate(invalid='ignore'):
+        h64 = np.rint(hit.astype(np.float64))
+        line_ok = (flags == 0) & ((kind == 1) | (kind == 2)) & (np.abs(h64) <= ARROW_COORD).all(axis=1)     # (a NaN fails the comparison)
+    for p, (h, w) in enumerate(sizes):
+        if h > ARROW_SIDE or w > ARROW_SIDE or h <= 0 or w <= 0:
+            continue
+        winner = np.full((h, w), -1, dtype=np.int64)              # the highest stroke that covers each pixel
+        color = np.zeros((m + 2 * n, 3), dtype=np.uint8)
+
+        def stroke(index, segments, thickness, c):
+            pts = np.asarray([q for s in segments for q in s])
+            r = (thickness + 1) // 2
+            x0, y0 = max(int(pts[:, 0].min()) - r, 0), max(int(pts[:, 1].min()) - r, 0)
+            x1, y1 = min(int(pts[:, 0].max()) + r + 1, w), min(int(pts[:, 1].max()) + r + 1, h)
+            color[index] = c
+            if x1 <= x0 or y1 <= y0:
+                return
+            cover = np.logical_or.reduce([segment_coverage(y1 - y0, x1 - x0, a, b, thickness, y0, x0) for a, b in segments])
+            winner[y0:y1, x0:x1][cover] = index                   # ascending: a later stroke overwrites an earlier one
+
+        for j in range(m if region_thickness else 0):
+            if corners[j] is not None and (ri[j] < 0 or ri[j] == p or (period > 0 and ri[j] == p % period)):
+                v = corners[j]
+                stroke(j, [(v[k], v[(k + 1) % len(v)]) for k in range(len(v))], region_thickness, pal[6 if region_active[p, j] else 5])
+        rows = np.flatnonzero((flags == 0) & (image_of == p))
+        for k in rows[line_ok[rows]] if line_thickness else ():
+            stroke(m + k, [(seg[k, 0, 0], h64[k].astype(np.int64))], line_thickness, pal[row_color[k]])
+        for k in rows if min_thickness else ():
+            stroke(m + n + k, list(seg[k]), int(t[k]), pal[row_color[k]])
+        if nv12:
+            y, uv = out[p]
+            y[winner >= 0] = color[winner[winner >= 0], 0]
+            top = winner.reshape(h // 2, 2, w // 2, 2).max(axis=(1, 3))   # the highest stroke among the four luma pixels of a chroma pair
+            uv.reshape(h // 2, w // 2, 2)[top >= 0] = color[top[top >= 0], 1:]
+        else:
+            out[p][winner >= 0] = color[winner[winner >= 0]]
+    return (out[0] if single else out), flags, region_flags, region_active

@@ -22,6 +22,7 @@ import torch
 
 from .attention import END_VIDEO_ENDED, KIND_HEAD, KIND_REGION, MAX_COLUMNS, MAX_ROWS, _attention_options, _dwell_options, open_episodes
 from .engine import _upload_table
+from .arrows import OVERLAY_PALETTE, _overlay_options
 from .pipeline import ARROW_COLOR, _track_motion, _track_params, letterbox_geometry
 
 CLUES = ('face', 'eyes', 'head')
@@ -879,6 +880,9 @@ def run_head_video(engine, pipeline, frames, boxes_per_frame=None, max_len=100, 
     (records, annotated): annotated[t] is frame t on the device in draw_arrows' form, for every t of boxes_per_frame, a frame without a head
     unchanged.  Device frames are drawn into clones (copy=False in the dict: in place).  ``color`` is B, G, R whatever rgb= says.  In a
     frame the people of a segment are drawn left to right: where two arrows overlap, the person further right wins.
+    ``overlay=True`` or ``dict(palette=, line_thickness=, region_thickness=)`` in the dict (it needs attention=; ValueError without, and with
+    color): the frames are drawn with pipeline.draw_attention from the records' target tables -- region outlines, sight lines, arrows
+    coloured by their target -- instead of draw_arrows.
     detections: in place of boxes_per_frame (exactly one of the two is given) a dict(pred=..., in_shape=..., **options): the head detector's
     raw prediction [T, N, 5 + nc] for the T frames, on the host or the device, the (h, w) of its letterboxed input, and options of
     pipeline.detect_heads (conf_thres, iou_thres, only_class, agnostic, max_nms, max_det).  The boxes come from DETECT_FRAMES frames per
@@ -993,23 +997,34 @@ def run_head_video(engine, pipeline, frames, boxes_per_frame=None, max_len=100, 
     if draw is None:
         return out
     opts = {'copy': True, **({} if draw is True else dict(draw))}
-    if rgb and pixel_format == 'bgr':                  # the frames hold R, G, B: the colour goes in in their order
+    overlay = _overlay_options('run_head_video(draw=...)', opts.pop('overlay', None), True, attention)
+    if overlay is not None and opts.get('color') is not None:
+        raise ValueError('run_head_video(draw=...): with overlay the colours are the palette\'s, not color')
+    if overlay is not None and rgb and pixel_format == 'bgr':
+        overlay['palette'] = np.asarray(OVERLAY_PALETTE if overlay.get('palette') is None else overlay['palette'])[..., ::-1]
+    elif rgb and pixel_format == 'bgr':                # the frames hold R, G, B: the colour goes in in their order
         opts['color'] = np.asarray(ARROW_COLOR if opts.get('color') is None else opts['color'])[..., ::-1]
     rows = [[] for _ in boxes_per_frame]               # frame -> (box, gaze) of its heads, in record order
     for r in out:
         g = r['fused' if smooth is None else 'fused_smooth']
         for j, t in enumerate(r['frame_id']):
-            rows[t].append((r['head_box'][j], g[j, :2]))
+            rows[t].append((r['head_box'][j], g[j, :2]) + (() if overlay is None else (r['target_kind'][j], r['target_region'][j], r['target_hit'][j], r['mutual'][j])))
     if opts.get('color') is not None and np.ndim(opts['color']) == 2:
         raise ValueError('run_head_video(draw=...): color is one (B, G, R) triple')
     annotated = []
     for t0 in range(0, len(rows), DRAW_FRAMES):
         part = rows[t0:t0 + DRAW_FRAMES]
         image_of = np.asarray([k for k, heads in enumerate(part) for _ in heads], dtype=np.int32)
-        boxes = np.asarray([b for heads in part for b, _ in heads], dtype=np.float32).reshape(-1, 4)
-        gaze = np.asarray([g for heads in part for _, g in heads], dtype=np.float32).reshape(-1, 2)
-        imgs, _ = pipeline.draw_arrows([frames[t] for t in range(t0, t0 + len(part))], boxes, gaze, image_of, pixel_format=pixel_format,
-                                       matrix=matrix, device=engine.device, **opts)
+        boxes = np.asarray([h[0] for heads in part for h in heads], dtype=np.float32).reshape(-1, 4)
+        gaze = np.asarray([h[1] for heads in part for h in heads], dtype=np.float32).reshape(-1, 2)
+        images = [frames[t] for t in range(t0, t0 + len(part))]
+        if overlay is None:
+            imgs, _ = pipeline.draw_arrows(images, boxes, gaze, image_of, pixel_format=pixel_format, matrix=matrix, device=engine.device, **opts)
+        else:                                          # the records' own tables: a head's target is not read by the overlay, a region's is target_region
+            kind, target, hit, mutual = ([h[i] for heads in part for h in heads] for i in (2, 3, 4, 5))
+            imgs = pipeline.draw_attention(images, boxes, gaze, image_of, np.asarray(kind, np.int32), np.asarray(target, np.int32),
+                                           np.asarray(hit, np.float32).reshape(-1, 2), np.asarray(mutual, np.int32), regions=attention[0],
+                                           region_image=attention[1], pixel_format=pixel_format, matrix=matrix, device=engine.device, **opts, **overlay)[0]
         annotated += imgs
     return out, annotated
 

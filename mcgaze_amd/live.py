@@ -30,6 +30,7 @@ import numpy as np
 import torch
 
 from . import lib as L
+from .arrows import _overlay_options
 from .attention import KIND_HEAD, PolyRegions, _attention_options, _dwell_options
 from .engine import _upload_table
 from .harness import _host, check_smooth
@@ -334,6 +335,10 @@ class LiveGaze:
     decided in the image plane, and expand / camera_angle are conventions, not tuned on data.  Still no wait for the device, no copy to the
     host.
 
+    OVERLAY.  ``overlay=True`` or ``dict(palette=, line_thickness=, region_thickness=)`` (it needs ``draw`` and ``attention``; ValueError
+    without) draws the frames with pipeline.draw_attention instead of draw_arrows, from the gated tables and the per-camera regions: region
+    outlines (lit where somebody looks at them), sight lines to the hit points, arrows coloured by their target.  Every table comes back as
+    without it, and the tick still never waits for the device.
     DWELL.  ``dwell=None`` is everything above.  ``dwell=True`` or ``dict(enter=3, exit=2)`` (it needs ``attention``; ValueError without) adds how
     LONG every row has looked at its target (pipeline.gaze_dwell, mcg_gaze_dwell: one call per tick that returns frames, over the k frames
     handed out, frame0 = first).  A column is a slot or a lane; its owner is person = track_id where valid, else 0, with lanes tagged by the
@@ -348,7 +353,7 @@ class LiveGaze:
 
     def __init__(self, engine_or_model, pipeline, cameras, slots=16, clip_len=7, stride=4, expand=0.8, match_iou=0.3, max_age=5, smooth=None,
                  pixel_format='bgr', draw=False, matrix='bt601', rgb=False, person_threshold=0.5, max_decode_windows=None, lanes=None, motion=None,
-                 attention=None, dwell=None):
+                 attention=None, dwell=None, overlay=None):
         self.S, self.match_iou, self.max_age = _track_params(slots, match_iou, max_age)
         _track_motion(motion, 'LiveGaze')
         self.motion = motion
@@ -360,6 +365,7 @@ class LiveGaze:
         self.smooth = check_smooth('LiveGaze', smooth)
         attention = _attention_options('LiveGaze', attention, self.Q)
         self.dwell = _dwell_options('LiveGaze', dwell, attention)
+        self.overlay = _overlay_options('LiveGaze', overlay, draw, attention)
         self.pipe, self.expand, self.draw = pipeline, float(expand), bool(draw)
         self.frame_options = dict(pixel_format=pixel_format, matrix=matrix)
         self.rgb = bool(rgb)
@@ -521,8 +527,13 @@ class LiveGaze:
             if k:
                 gaze = out['fused_smooth' if smoothing else 'fused']
                 # copy=True: the frame table of fresh tensors then travels pinned through the staging ring, not as a pageable upload
-                drawn, _ = self.pipe.draw_arrows(images, out['head_box'].view(-1, 4), gaze.view(-1, 3), out['image_of'].view(-1), copy=True,
-                                                 device=self.dev, **self.frame_options)
+                rows = (out['head_box'].view(-1, 4), gaze.view(-1, 3), out['image_of'].view(-1))
+                if self.overlay is None:
+                    drawn, _ = self.pipe.draw_arrows(images, *rows, copy=True, device=self.dev, **self.frame_options)
+                else:                                             # (a head's target is a slot or lane by now: the overlay reads target only where kind is "region")
+                    drawn = self.pipe.draw_attention(images, *rows, out['target_kind'].view(-1), out['target'].view(-1), out['target_hit'].view(-1, 2),
+                                                     out['mutual'].view(-1), regions=self.attention['regions'], region_image=self.attention['region_image'],
+                                                     region_period=self.Q, copy=True, device=self.dev, **self.frame_options, **self.overlay)[0]
                 images = list(drawn)
             out['frames'] = [images[i * Q:(i + 1) * Q] for i in range(k)]
         self.emitted += k

@@ -33,6 +33,8 @@ import numpy as np
 import torch
 
 from . import lib as L
+from .arrows import (OVERLAY_PALETTE, _overlay_counts, _overlay_palette, _overlay_regions, _overlay_targets, _overlay_thickness,  # noqa: F401
+                     draw_attention_host)
 from .arrows import (ARROW_COLOR, ARROW_COORD, ARROW_SIDE, _arrow_colors, _arrow_params, _arrow_rows,  # noqa: F401
                      arrow_segments, draw_arrows_host, segment_coverage)
 from .attention import PolyRegions, _check_counts, _holds_polygon, _poly_tables, _region_tables, _target_params, gaze_targets_host, region_polygons  # noqa: F401
@@ -721,6 +723,123 @@ class DevicePipeline:
                 if st is not None:
                     st.read_by(main)
         return out, flags
+
+    def draw_attention(self, images, boxes, gaze, image_of, kind, target, hit, mutual, regions=None, region_image=None, region_period=0,
+                       palette=None, line_thickness=2, region_thickness=2, pixel_format='bgr', matrix='bt601', copy=False, device='cuda:0',
+                       stream=None, **params):
+        """What ``gaze_targets`` found, drawn into the frames on the device (mcg_draw_attention / mcg_draw_attention_nv12: region_active
+        cleared, a plan launch, a gather launch) -- ``arrows.draw_attention_host`` bit for bit: the outlines of the regions (palette[6] in a
+        picture where a row looks at the region, else palette[5]), a sight line from every head that looks at a head or a region to its hit
+        point, and ``draw_arrows``' arrows in palette[4 if mutual else kind].  Higher layers and, inside a layer, higher indices win.
+
+        images, boxes, gaze, image_of, pixel_format, matrix, copy and params (length, min_thickness, thickness_ratio, tip_length) are
+        ``draw_arrows``': a CUDA frame is drawn IN PLACE (copy=True: into a packed clone), a numpy frame goes up through the staging ring.
+        kind, target, mutual [n] and hit [n,2] are gaze_targets' results; regions, region_image and region_period are what gaze_targets took
+        -- [m,4] rectangles, the mixed list of ``attention.region_polygons`` or a ``PolyRegions(xy, start)`` -- on the host or the device.
+        palette: [7,3] B, G, R on the host (None: ``arrows.OVERLAY_PALETTE``, a convention), converted once per entry for NV12.  A thickness
+        of 0 (line_thickness, region_thickness, min_thickness) switches its layer off.  Host tables are checked before anything is launched
+        (TypeError / ValueError as in draw_arrows); device tables are never read back: a row or region that cannot be drawn comes back with
+        flag 2 and writes nothing.  With device frames drawn in place, device tables and the frame table cached by a first call, the call
+        touches the host nowhere and can be captured in a graph.
+        -> (images on the device, in order; flags [n], region_flags [m], region_active [len(images), m]: int32 on the device)."""
+        lib = L.load()
+        who = 'draw_attention'
+        nv12, _ = _pixel_format(pixel_format, matrix)
+        length, min_thickness, ratio, tip_length = _arrow_params(lowest=0, **params)
+        line_thickness, region_thickness = _overlay_thickness(who, line_thickness=line_thickness, region_thickness=region_thickness)
+        _, _, period = _target_params(region_period=region_period, who=who)
+        pal = _overlay_palette(who, palette, nv12, matrix)
+        entry = lib.mcg_draw_attention_nv12 if nv12 else lib.mcg_draw_attention
+        dev = _device(device)
+        images = list(images)
+        planes = [_nv12_planes(k, im, dev) for k, im in enumerate(images)] if nv12 else None
+        dev = _device(dev, entry.__name__)
+        if not len(images):
+            raise ValueError(f'{who}: no frames')
+        table, _ = _image_table(images, dev, planes)              # every frame is checked before the first clone or upload
+        boxes, image_of, gaze, n = _row_tables(who, 'rows', len(images), boxes, image_of, gaze)
+        for name, t in (('box', boxes), ('gaze', gaze)):
+            if isinstance(t, np.ndarray) and not np.isfinite(t).all():
+                raise ValueError(f'{who}: {name} {int(np.flatnonzero(~np.isfinite(t).all(axis=1))[0])} is not finite')
+        on_device = lambda t: isinstance(t, torch.Tensor) and t.is_cuda
+        found = (kind, target, hit, mutual)
+        if not any(on_device(t) for t in found):
+            found = _overlay_targets(who, n, *found)
+        if _holds_polygon(regions):
+            regions = region_polygons(regions)
+        poly = isinstance(regions, PolyRegions)
+        regions_there = any(on_device(t) for t in ((*regions, region_image) if poly else (regions, region_image)))
+        if not regions_there:
+            xy, start, region_image = _overlay_regions(who, regions, region_image)
+        with torch.cuda.device(dev):
+            main = _caller_stream(stream, dev)
+            with torch.cuda.stream(main):
+                out, pixels, in_place = _arrow_targets(images, planes, copy, dev)
+                if not in_place:                                  # the table of the tensors that are drawn into
+                    table, _ = _image_table(out, dev, [_nv12_planes(k, o, dev) for k, o in enumerate(out)] if nv12 else None)
+                h_max, w_max = int(table['h'].max()), int(table['w'].max())
+                if h_max > ARROW_SIDE or w_max > ARROW_SIDE:
+                    raise ValueError(f'{who}: frames of at most {ARROW_SIDE} pixels a side, got {h_max} x {w_max}')
+                if isinstance(boxes, np.ndarray) and isinstance(gaze, np.ndarray) and n:
+                    _arrow_rows(boxes, gaze, image_of if isinstance(image_of, np.ndarray) else np.zeros(n, np.int32),
+                                [(int(r['h']), int(r['w'])) for r in table], True, length=length, min_thickness=min_thickness,
+                                thickness_ratio=ratio, tip_length=tip_length, lowest=0)
+                there = lambda t, dtype: (t if isinstance(t, torch.Tensor) else torch.as_tensor(np.asarray(t))).to(dev, dtype).contiguous()
+                boxes = boxes if isinstance(boxes, np.ndarray) else boxes.to(dev, torch.float32).contiguous()
+                image_of = image_of if isinstance(image_of, np.ndarray) else image_of.to(dev, torch.int32).contiguous()
+                gaze_stride = 2
+                if isinstance(gaze, torch.Tensor):
+                    if not (gaze.device == dev and gaze.dtype == torch.float32 and gaze.stride(1) == 1 and (n <= 1 or gaze.stride(0) >= 2)):
+                        gaze = gaze.to(dev, torch.float32).contiguous()
+                    gaze_stride = int(gaze.stride(0)) if n > 1 else int(gaze.shape[1])
+                if not isinstance(found[0], np.ndarray):          # one of them is on the device: the others are moved with torch
+                    found = tuple(there(t, torch.float32 if k == 2 else torch.int32) for k, t in enumerate(found))
+                    for name, t, shape in zip(('kind', 'target', 'hit', 'mutual'), found, ((n,), (n,), (n, 2), (n,))):
+                        if tuple(t.shape) != shape:
+                            raise ValueError(f'{who}: {name} must be {list(shape)}, got {tuple(t.shape)}')
+                if regions_there:
+                    if poly:
+                        xy, start = there(regions.xy, torch.float32), there(regions.start, torch.int32)
+                        if xy.ndim != 2 or xy.shape[1] != 2 or start.ndim != 1 or start.shape[0] < 1:
+                            raise ValueError(f'{who}: PolyRegions is xy [V, 2] and start [m + 1], got {tuple(xy.shape)} and {tuple(start.shape)}')
+                    else:
+                        if regions is None:
+                            raise ValueError(f'{who}: region_image without regions')
+                        xy = there(regions, torch.float32)
+                        if xy.ndim != 2 or xy.shape[1] != 4:
+                            raise ValueError(f'{who}: regions must be [m, 4] x1 y1 x2 y2, got {tuple(xy.shape)}')
+                        xy = xy.view(-1, 2)                       # a rectangle is a 2-vertex region
+                        start = torch.arange(0, xy.shape[0] + 1, 2, dtype=torch.int32, device=dev)
+                    m = int(start.shape[0]) - 1
+                    region_image = torch.full((m,), -1, dtype=torch.int32, device=dev) if region_image is None else there(region_image, torch.int32)
+                    if tuple(region_image.shape) != (m,):
+                        raise ValueError(f'{who}: region_image must be [{m}], one per region; got {tuple(region_image.shape)}')
+                m, V = int(region_image.shape[0]), int(xy.shape[0])
+                _overlay_counts(who, n, m, V, len(out))
+                tables = (boxes, gaze, image_of, *found, xy, start, region_image)
+                frame_table = table
+                if in_place and not any(isinstance(t, np.ndarray) for t in tables):
+                    # device frames drawn in place and device tables: only the frame table, and only the first time the frames are seen
+                    frame_table = self._device_image_table(table, dev, nv12)
+                operands = [t if (t.size if isinstance(t, np.ndarray) else t.numel()) else None for t in tables]
+                # everything that comes from the host travels in ONE pinned staging buffer and one copy: pixels, frame table, host tables
+                st, staged, ptrs = self._ring.upload([a for _, a in pixels], (frame_table, *operands), dev, main)
+                for (dst, _), src in zip(pixels, staged):         # out of the stage (the next calls reuse it) into the tensor handed back
+                    dst.copy_(src.view(dst.shape))
+                new = lambda *shape: torch.empty(*shape, dtype=torch.int32, device=dev)
+                flags, region_flags, region_active = new(n), new(m), new(len(out), m)
+                if n or m:
+                    work = new(24 * (m + 2 * n) + 64 * m)         # the header's formula: (m + 2 n) stroke records, then [m][32][2] vertices
+                    vp = C.c_void_p
+                    images_ptr, boxes_ptr, gaze_ptr, image_of_ptr, kind_ptr, target_ptr, hit_ptr, mutual_ptr, xy_ptr, start_ptr, ri_ptr = ptrs
+                    L.check(entry(vp(main.cuda_stream), vp(images_ptr), len(out), h_max, w_max, vp(boxes_ptr), vp(gaze_ptr), gaze_stride,
+                                  vp(image_of_ptr), n, vp(kind_ptr), vp(target_ptr), vp(hit_ptr), vp(mutual_ptr), vp(xy_ptr), V, vp(start_ptr),
+                                  vp(ri_ptr), m, period, (C.c_ubyte * 21)(*[int(v) for v in pal.reshape(-1)]), length, min_thickness, ratio,
+                                  tip_length, line_thickness, region_thickness, vp(work.data_ptr()), 4 * work.numel(), vp(flags.data_ptr()),
+                                  vp(region_flags.data_ptr()), vp(region_active.data_ptr())), entry.__name__)
+                if st is not None:
+                    st.read_by(main)
+        return out, flags, region_flags, region_active
 
     def gaze_targets(self, boxes, gaze, image_of, regions=None, region_image=None, region_period=0, expand=0.25, camera_angle=10.0, device='cuda:0',
                      stream=None):

@@ -3,7 +3,7 @@
 label files in, per-person per-frame gaze out -- and, with --draw, the frames with cell 5's arrows drawn on the device.
 
 usage: demo_video.py FRAMES_DIR LABELS_DIR CONFIG CHECKPOINT --out gaze.json [--precision f16x3] [--device cuda:0] [--max-len 100]
-                     [--batch-frames 448] [--head-class 1] [--ext jpg] [--smooth ALPHA] [--nv12 WxH FILE] [--matrix bt601] [--draw OUT]
+                     [--batch-frames 448] [--head-class 1] [--ext jpg] [--smooth ALPHA] [--nv12 WxH FILE] [--matrix bt601] [--draw OUT] [--overlay]
                      [--track [--slots 16] [--match-iou 0.3] [--max-age 5]] [--track-motion [GAIN[,DECAY]]]
                      [--color B,G,R] [--predictions DIR --in-shape HxW [--conf-thres 0.25] [--iou-thres 0.45]]
                      [--detector MODULE:FACTORY [--img-size 640] [--half]] [--attention [--regions FILE.json] [--dwell [ENTER,EXIT]]]
@@ -164,6 +164,8 @@ def main(argv=None):
     ap.add_argument('--matrix', default='bt601', choices=['bt601', 'bt709'], help='YUV -> RGB coefficients of --nv12')
     ap.add_argument('--draw', default=None, metavar='OUT', help='write the frames with the gaze arrows drawn into this directory')
     ap.add_argument('--color', default=None, metavar='B,G,R', help='colour of the arrows of --draw')
+    ap.add_argument('--overlay', action='store_true', help='--draw with --attention: region outlines, sight lines and arrows coloured by their target '
+                                                             '(pipeline.draw_attention) instead of the plain arrows')
     ap.add_argument('--predictions', default=None, metavar='DIR', help='raw detector output, <t>.npy per frame, instead of LABELS_DIR (then -)')
     ap.add_argument('--in-shape', default=None, metavar='HxW', help='the letterboxed input of the detector behind --predictions')
     ap.add_argument('--conf-thres', type=float, default=0.25)
@@ -211,6 +213,10 @@ def main(argv=None):
     draw = None
     if a.draw is not None:
         draw = {} if a.color is None else dict(color=parse_color(a.color))
+    if a.overlay:
+        if a.draw is None or not a.attention or a.color is not None:
+            raise SystemExit('--overlay belongs to --draw and --attention, and its colours are the palette\'s (no --color)')
+        draw['overlay'] = True
     if a.nv12 is not None:
         frames = Nv12File(a.nv12[1], *parse_size(a.nv12[0]))
         n = len(frames)
