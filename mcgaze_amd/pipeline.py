@@ -20,6 +20,13 @@ boxes that may both live in device memory already.  ``head_crop_window`` is the 
 ``track_heads`` one identity per person from the boxes of consecutive frames.
 Re-exported from beside this module: decoded frames (frame_cache.py), NV12 (nv12.py), arrows (arrows.py), gaze targets (attention.py), the detector's two sides (head_detect.py), upload (staging.py).
 
+What the device calls of ``DevicePipeline`` share is stated once, and a further call is written from these pieces: every call runs in a
+``_call_scope`` (staging.py: the device, the caller's stream, the one upload, the mark on the stage it took); ``_row_tables`` checks the rows
+of head_crops and the two drawing calls; ``_on_device`` / ``_there`` decide where a table lives and move a host table that stands next to a
+device one; ``_gaze_operand`` is the gaze table with its row stride; ``_region_operands`` decides the region tables of gaze_targets and
+draw_attention as a group; ``_drawing_checked``, ``_drawing_placed`` and ``_drawing_upload`` are, in the order of a call, what draw_arrows
+and draw_attention do to frames and rows; and ``_device_table`` keeps the record tables of device frames on the device.
+
 Randomness: the reference's ``CenterCrop(crop_type='relative_range')`` draws the crop size from the global numpy RNG at TEST
 time too (transforms.py:1126-1130), and ``RandomFlip(flip_ratio=0.0)`` consumes one more uniform
 (np.random.choice, transforms.py:463-497).  ``rng`` (default: the global ``np.random``) is drawn from in that order per frame,
@@ -46,7 +53,7 @@ from .head_detect import (DETECT_MAX_DET, LETTERBOX_PAD, LetterboxGeometry, _det
                           track_state_words)
 from .nv12 import YUV_COEF, _nv12_planes, _pixel_format, _yuv_coef, _yuv_to_bgr, bgr_to_yuv, nv12_to_bgr  # noqa: F401
 from .registry import Registry
-from .staging import _Stage, _StagingRing, _bgr_frame, _host_array, _layout  # noqa: F401
+from .staging import _Stage, _StagingRing, _bgr_frame, _call_scope, _host_array, _layout  # noqa: F401
 
 PIPELINES = Registry('pipeline')
 
@@ -334,8 +341,79 @@ def _device(device, entry=None):
     return torch.device('cuda', torch.cuda.current_device()) if dev.type == 'cuda' and dev.index is None else dev
 
 
-def _caller_stream(stream, dev):
-    return torch.cuda.current_stream(dev) if stream is None else torch.cuda.ExternalStream(stream, device=dev)
+def _on_device(t):
+    return isinstance(t, torch.Tensor) and t.is_cuda
+
+
+def _tensor(t):
+    return t if isinstance(t, torch.Tensor) else torch.as_tensor(np.asarray(t))
+
+
+def _there(t, dev, dtype):
+    """A table of any kind as a contiguous ``dtype`` tensor on ``dev``: how a host table next to a device one is moved (with torch, not
+    through the staging ring), and how a device table of another type or layout becomes what the kernels read."""
+    return (t if isinstance(t, torch.Tensor) else _tensor(t)).to(dev, dtype).contiguous()
+
+
+def _gaze_operand(gaze, n, columns, dev):
+    """The gaze table [n, >= columns] as the kernels take it -> (gaze, its row stride in floats).  A host array comes back as it is, its rows
+    ``columns`` apart.  A tensor that is f32 on ``dev`` with packed rows -- the [n,3] ``fused`` of a results='device' stream, or the first
+    columns of a wider table -- is read where it is; any other is converted and made contiguous.  Up to one row there is no row stride to
+    take from the tensor: it is the row's width."""
+    if not isinstance(gaze, torch.Tensor):
+        return gaze, columns
+    stride = gaze.stride(0) if n > 1 else gaze.shape[1]
+    if not (gaze.device == dev and gaze.dtype == torch.float32 and gaze.stride(1) == 1 and stride >= columns):
+        gaze, stride = gaze.to(dev, torch.float32).contiguous(), gaze.shape[1]
+    return gaze, int(stride)
+
+
+def _device_regions(who, regions, region_image, dev, as_vertices):
+    """The region tables of ``who`` where one of them is a device tensor -> (poly, table, start, region_image) on ``dev``, the others moved
+    with torch; nothing is read back, so only the shapes are checked (ValueError).  regions: a PolyRegions (table: xy [V,2]) or [m,4]
+    rectangles, which stay [m,4] with no ``start`` unless ``as_vertices`` asks for them as 2-vertex regions."""
+    poly = isinstance(regions, PolyRegions)
+    if poly:
+        table, start = _there(regions.xy, dev, torch.float32), _there(regions.start, dev, torch.int32)
+        if table.ndim != 2 or table.shape[1] != 2 or start.ndim != 1 or start.shape[0] < 1:
+            raise ValueError(f'{who}: PolyRegions is xy [V, 2] and start [m + 1], got {tuple(table.shape)} and {tuple(start.shape)}')
+        m = int(start.shape[0]) - 1
+    else:
+        if regions is None:
+            raise ValueError(f'{who}: region_image without regions')
+        table, start = _there(regions, dev, torch.float32), None
+        if table.ndim != 2 or table.shape[1] != 4:
+            raise ValueError(f'{who}: regions must be [m, 4] x1 y1 x2 y2, got {tuple(table.shape)}')
+        m = int(table.shape[0])
+        if as_vertices:                                           # a rectangle is a 2-vertex region
+            poly, table, start = True, table.view(-1, 2), torch.arange(0, 2 * m + 1, 2, dtype=torch.int32, device=dev)
+    region_image = torch.full((m,), -1, dtype=torch.int32, device=dev) if region_image is None else _there(region_image, dev, torch.int32)
+    if tuple(region_image.shape) != (m,):
+        raise ValueError(f'{who}: region_image must be [{m}], one per region; got {tuple(region_image.shape)}')
+    return poly, table, start, region_image
+
+
+def _region_operands(who, regions, region_image, dev, as_vertices=False):
+    """``regions`` / ``region_image`` as the user of ``who`` gave them -- [m,4] rectangles, the mixed list of ``region_polygons`` or a
+    PolyRegions; region_image None: -1, every picture -- -> (poly, table, start, region_image, m, V).  Decided as a group: tables that are
+    all on the host come back checked as numpy arrays, which go up through the staging ring; with one of them on the device all are tensors
+    on ``dev`` (``_device_regions``).  poly: table is xy [V,2] with start [m+1]; else table is the rectangles [m,4], start None and V 0 --
+    what mcg_gaze_targets takes.  as_vertices (the overlay): always the vertex form.
+    Where to call it: inside the call's scope (the device branch allocates and copies on the caller's stream) and FIRST there, before
+    anything is cloned or moved -- the host branch is a host check, and host checks come before the first clone, upload or launch.  The
+    device branch's shape errors therefore come before the shape errors of the other device tables."""
+    if _holds_polygon(regions):
+        regions = region_polygons(regions)
+    poly = isinstance(regions, PolyRegions)
+    if any(_on_device(t) for t in ((*regions, region_image) if poly else (regions, region_image))):
+        poly, table, start, region_image = _device_regions(who, regions, region_image, dev, as_vertices)
+    elif as_vertices:
+        poly, (table, start, region_image) = True, _overlay_regions(who, regions, region_image)
+    elif poly:
+        table, start, region_image = _poly_tables(who, regions, region_image)
+    else:
+        (table, region_image), start = _region_tables(who, regions, region_image), None
+    return poly, table, start, region_image, int(region_image.shape[0]), int(table.shape[0]) if poly else 0
 
 
 def _kernel_norm(norm, rgb, nv12=False):
@@ -374,22 +452,23 @@ def _arrow_targets(images, planes, copy, dev):
     """Where draw_arrows draws each frame -> (tensors, pixels, in_place): a device frame itself (copy: its packed clone), a fresh device tensor
     for a host frame (NV12: one [3H/2, W] surface as its (y, uv) views).  pixels: (the tensor they belong in, bytes) of the host frames, in image
     order; in_place: every frame is its own target."""
-    out, pixels = [], []
+    out, pixels, in_place = [], [], not copy
     for k, im in enumerate(images):
         if planes is not None and not planes[k][2]:
-            y, uv, _ = planes[k]
+            y, uv, in_place = planes[k][0], planes[k][1], False
             s = torch.empty(y.shape[0] * 3 // 2, y.shape[1], dtype=torch.uint8, device=dev)
             out.append((s[:y.shape[0]], s[y.shape[0]:]))
             pixels += [(out[-1][0], y.reshape(-1)), (out[-1][1], uv.reshape(-1))]
         elif planes is None and not isinstance(im, torch.Tensor):
             out.append(torch.empty(np.shape(im), dtype=torch.uint8, device=dev))
+            in_place = False
             pixels.append((out[-1], np.ascontiguousarray(im).reshape(-1)))
         elif copy:
             clone = lambda t: t.clone(memory_format=torch.contiguous_format)
             out.append(tuple(clone(t) for t in im) if isinstance(im, (tuple, list)) else clone(im))
         else:
             out.append(im)
-    return out, pixels, all(o is im for o, im in zip(out, images))
+    return out, pixels, in_place
 
 
 def _row_tables(caller, rows, frames, boxes, image_of, gaze=None):
@@ -398,14 +477,13 @@ def _row_tables(caller, rows, frames, boxes, image_of, gaze=None):
     back as it is and is not read back, or lives on the host and comes back CHECKED as a contiguous array: boxes f32 [n,4]; image_of int32
     [n] (TypeError unless it holds integers, ValueError outside [0, frames)); gaze f32, cut to its first two columns.  ValueError where the shapes
     do not belong together or n exceeds 65535."""
-    on_device = lambda t: isinstance(t, torch.Tensor) and t.is_cuda
-    if not on_device(boxes):
+    if not _on_device(boxes):
         boxes = np.ascontiguousarray(_host_array(boxes), dtype=np.float32).reshape(-1, 4)     # f32 is what the device reads: the checks see the same boxes
     n = int(boxes.shape[0])
-    if gaze is not None and not on_device(gaze):
+    if gaze is not None and not _on_device(gaze):
         gaze = np.ascontiguousarray(_host_array(gaze), dtype=np.float32)
         gaze = np.zeros((0, 2), np.float32) if n == 0 and gaze.size == 0 else np.ascontiguousarray(gaze[:, :2]) if gaze.ndim == 2 else gaze
-    if not on_device(image_of):
+    if not _on_device(image_of):
         image_of = np.ascontiguousarray(_host_array(image_of)).reshape(-1)
         if image_of.dtype.kind not in 'iu':
             raise TypeError(f'image_of must hold integers, got {image_of.dtype}')
@@ -419,6 +497,46 @@ def _row_tables(caller, rows, frames, boxes, image_of, gaze=None):
     if n > 65535:
         raise ValueError(f'{caller}: at most 65535 {rows} per call (got {n})')
     return boxes, image_of, gaze, n
+
+
+def _drawing_checked(who, rows, entry, images, boxes, gaze, image_of, nv12, device):
+    """The first of the three steps draw_arrows and draw_attention (``who``; they draw ``rows`` = 'arrows' / 'rows') share: the frames and the
+    row tables checked on the host, before anything is cloned, uploaded or launched -> (dev, images, planes, table, boxes, image_of, gaze, n),
+    which ``_drawing_placed`` takes inside the call's scope; ``DevicePipeline._drawing_upload`` is the third."""
+    dev = _device(device)                                         # the surfaces are checked whatever the device: a bad one is the caller's first error
+    images = list(images)
+    planes = [_nv12_planes(k, im, dev) for k, im in enumerate(images)] if nv12 else None
+    dev = _device(dev, entry.__name__)
+    if not len(images):
+        raise ValueError(f'{who}: no frames')
+    table, _ = _image_table(images, dev, planes)                  # every frame is checked before the first clone or upload
+    boxes, image_of, gaze, n = _row_tables(who, rows, len(images), boxes, image_of, gaze)
+    for name, t in (('box', boxes), ('gaze', gaze)):
+        if isinstance(t, np.ndarray) and not np.isfinite(t).all():
+            raise ValueError(f'{who}: {name} {int(np.flatnonzero(~np.isfinite(t).all(axis=1))[0])} is not finite')
+    return dev, images, planes, table, boxes, image_of, gaze, n
+
+
+def _drawing_placed(who, checked, nv12, copy, arrow, lowest):
+    """Inside the scope: the tensors that are drawn into and the rows as the kernels read them -> (out, pixels, in_place, table, h_max, w_max,
+    boxes, gaze, gaze_stride, image_of).  arrow: ``_arrow_params``' four, with ``lowest`` the least min_thickness they were checked against;
+    host rows that cannot be drawn are a ValueError here."""
+    dev, images, planes, table, boxes, image_of, gaze, n = checked
+    out, pixels, in_place = _arrow_targets(images, planes, copy, dev)
+    if not in_place:                                              # the table of the tensors that are drawn into
+        table, _ = _image_table(out, dev, [_nv12_planes(k, o, dev) for k, o in enumerate(out)] if nv12 else None)
+    h_max, w_max = int(table['h'].max()), int(table['w'].max())
+    if h_max > ARROW_SIDE or w_max > ARROW_SIDE:
+        raise ValueError(f'{who}: frames of at most {ARROW_SIDE} pixels a side, got {h_max} x {w_max}')
+    if isinstance(boxes, np.ndarray) and isinstance(gaze, np.ndarray) and n:
+        length, min_thickness, ratio, tip_length = arrow
+        _arrow_rows(boxes, gaze, image_of if isinstance(image_of, np.ndarray) else np.zeros(n, np.int32),
+                    [(int(r['h']), int(r['w'])) for r in table], True, length=length, min_thickness=min_thickness,
+                    thickness_ratio=ratio, tip_length=tip_length, lowest=lowest)
+    boxes = boxes if isinstance(boxes, np.ndarray) else boxes.to(dev, torch.float32).contiguous()
+    image_of = image_of if isinstance(image_of, np.ndarray) else image_of.to(dev, torch.int32).contiguous()
+    gaze, gaze_stride = _gaze_operand(gaze, n, 2, dev)
+    return out, pixels, in_place, table, h_max, w_max, boxes, gaze, gaze_stride, image_of
 
 
 class DevicePipeline:
@@ -452,11 +570,29 @@ class DevicePipeline:
             cache.move_to_end(key)
         return t
 
+    def _device_table(self, table, dev, *kind):
+        """The record table ``table`` on the device: uploaded the first time this content (of this ``kind``) is seen, then found again."""
+        return self._kept(self._image_tables, (dev.index, table.tobytes(), *kind), lambda: torch.from_numpy(table.view(np.uint8).reshape(-1).copy()).to(dev))
+
     def _device_image_table(self, table, dev, nv12):
-        """The frame table ``table`` on the device: uploaded the first time these frames are seen, then found again -- what lets head_crops
-        and draw_arrows on device frames and tables touch the host nowhere."""
-        return self._kept(self._image_tables, (dev.index, table.tobytes()) + (('nv12',) if nv12 else ()),
-                          lambda: torch.from_numpy(table.view(np.uint8).reshape(-1).copy()).to(dev))
+        """The frame table ``table`` on the device -- what lets head_crops and draw_arrows on device frames and tables touch the host nowhere."""
+        return self._device_table(table, dev, *(('nv12',) if nv12 else ()))
+
+    def _drawing_upload(self, call, nv12, table, pixels, in_place, tables, empty_is_null=False):
+        """The third step of the drawing calls: everything that comes from the host in ONE pinned staging buffer and one copy -- pixels, frame
+        table, host tables -- -> the addresses of the frame table and of ``tables`` (None for None; with ``empty_is_null`` for an empty
+        table too: the overlay's entry runs without rows or without regions).  The pixels of host frames are copied out of the stage, which
+        the next calls reuse, into the tensors handed back."""
+        frame_table = table
+        if in_place and np.ndarray not in map(type, tables):
+            # device frames drawn in place and device tables: only the frame table, and only the first time the frames are seen
+            frame_table = self._device_image_table(table, call.dev, nv12)
+        if empty_is_null:
+            tables = [t if (t.size if isinstance(t, np.ndarray) else t.numel()) else None for t in tables]
+        staged, ptrs = call.upload([a for _, a in pixels], (frame_table, *tables))
+        for (dst, _), src in zip(pixels, staged):
+            dst.copy_(src.view(dst.shape))
+        return ptrs
 
     def plan(self, shape, rng=np.random, filename=None, ori_filename=None):
         p = FramePlan(shape, filename, ori_filename)
@@ -546,19 +682,17 @@ class DevicePipeline:
                     for j, f in enumerate(('crop_y', 'crop_x', 'crop_h', 'crop_w', 'out_h', 'out_w')):
                         desc[f] = geo[idx, j]
 
-            with torch.cuda.device(dev):
-                main = _caller_stream(stream, dev)
-                st, _, desc_at = self._ring.upload([a.reshape(-1) for a in arrays], list(descs.values()), dev, main, describe)
+            with _call_scope(self._ring, dev, stream) as call:
+                _, desc_at = call.upload([a.reshape(-1) for a in arrays], list(descs.values()), describe)
                 desc_at = dict(zip(descs, desc_at))
-            mean, stdinv, swap = _kernel_norm(plans[0].img_norm_cfg, rgb_source)
-            for (pad_h, pad_w), wis in groups.items():
-                n = len(rows[pad_h, pad_w])
-                img = torch.empty(n, 3, pad_h, pad_w, dtype=torch.float32, device=dev)
-                L.check(lib.mcg_preprocess_frames(C.c_void_p(main.cuda_stream), C.c_void_p(desc_at[pad_h, pad_w]), n, C.c_void_p(img.data_ptr()),
-                                                  pad_h, pad_w, mean, stdinv, swap), 'mcg_preprocess_frames')
-                for wi, part in zip(wis, img.split([bounds[wi + 1] - bounds[wi] for wi in wis])):
-                    out[wi] = (part, [self.collect.meta(p) for p in plans[bounds[wi]:bounds[wi + 1]]])
-            st.read_by(main)
+                mean, stdinv, swap = _kernel_norm(plans[0].img_norm_cfg, rgb_source)
+                for (pad_h, pad_w), wis in groups.items():
+                    n = len(rows[pad_h, pad_w])
+                    img = torch.empty(n, 3, pad_h, pad_w, dtype=torch.float32, device=dev)
+                    L.check(lib.mcg_preprocess_frames(C.c_void_p(call.main.cuda_stream), C.c_void_p(desc_at[pad_h, pad_w]), n, C.c_void_p(img.data_ptr()),
+                                                      pad_h, pad_w, mean, stdinv, swap), 'mcg_preprocess_frames')
+                    for wi, part in zip(wis, img.split([bounds[wi + 1] - bounds[wi] for wi in wis])):
+                        out[wi] = (part, [self.collect.meta(p) for p in plans[bounds[wi]:bounds[wi + 1]]])
             return out
         except BaseException:
             # a TypeError for a non-uint8 frame, a decode error, a staging failure: the ring views handed out so far are not read any more --
@@ -620,34 +754,30 @@ class DevicePipeline:
                 k = int(np.flatnonzero(empty)[0])
                 raise ValueError(f'head box {k} {boxes[k].tolist()} leaves an empty window in frame {int(image_of[k])} '
                                  f'({int(table["h"][image_of[k]])} x {int(table["w"][image_of[k]])})')
-        with torch.cuda.device(dev):
-            main = _caller_stream(stream, dev)
-            with torch.cuda.stream(main):
-                boxes = boxes if isinstance(boxes, np.ndarray) else boxes.to(dev, torch.float32).contiguous()
-                image_of = image_of if isinstance(image_of, np.ndarray) else image_of.to(dev, torch.int32).contiguous()
-                new = lambda *shape, dtype=torch.int32: torch.empty(*shape, dtype=dtype, device=dev)
-                if n == 0:
-                    return new(0, 3, pad_h, pad_w, dtype=torch.float32), new(0, 2), new(0, 4, dtype=torch.float32), new(0, 4), new(0)
-                frame_table = table
-                if not parts and isinstance(boxes, torch.Tensor) and isinstance(image_of, torch.Tensor):
-                    # nothing comes from the host but the frame table, and that only the first time these frames are seen: no stage is taken
-                    frame_table = self._device_image_table(table, dev, nv12)
+        with _call_scope(self._ring, dev, stream) as call:
+            boxes = boxes if isinstance(boxes, np.ndarray) else boxes.to(dev, torch.float32).contiguous()
+            image_of = image_of if isinstance(image_of, np.ndarray) else image_of.to(dev, torch.int32).contiguous()
+            new = lambda *shape, dtype=torch.int32: torch.empty(*shape, dtype=dtype, device=dev)
+            if n == 0:
+                return new(0, 3, pad_h, pad_w, dtype=torch.float32), new(0, 2), new(0, 4, dtype=torch.float32), new(0, 4), new(0)
+            frame_table = table
+            if not parts and isinstance(boxes, torch.Tensor) and isinstance(image_of, torch.Tensor):
+                # nothing comes from the host but the frame table, and that only the first time these frames are seen: no stage is taken
+                frame_table = self._device_image_table(table, dev, nv12)
 
-                def name_frames(at):                              # a host frame's address: where its bytes land in the device twin
-                    for (k, f, _), a in zip(parts, at):
-                        table[f][k] = a
+            def name_frames(at):                                  # a host frame's address: where its bytes land in the device twin
+                for (k, f, _), a in zip(parts, at):
+                    table[f][k] = a
 
-                # everything that comes from the host travels in ONE pinned staging buffer and one copy: pixels, frame table, host tables
-                st, _, (images_ptr, boxes_ptr, image_of_ptr) = self._ring.upload([a for _, _, a in parts], (frame_table, boxes, image_of), dev, main, name_frames)
-                img, scale_factor = new(n, 3, pad_h, pad_w, dtype=torch.float32), new(n, 4, dtype=torch.float32)
-                desc, img_hw, flags = new(n, _NV12_DESC_WORDS if nv12 else _DESC_WORDS), new(n, 2), new(n)
-                vp = C.c_void_p
-                entry, more = (lib.mcg_preprocess_head_crops_nv12, (C.byref(L.YuvCoef(**coef)),)) if nv12 else (lib.mcg_preprocess_head_crops, ())
-                L.check(entry(vp(main.cuda_stream), vp(images_ptr), len(images), vp(boxes_ptr), vp(image_of_ptr), n, float(expand),
-                              scale_w, scale_h, vp(desc.data_ptr()), vp(img_hw.data_ptr()), vp(scale_factor.data_ptr()),
-                              vp(flags.data_ptr()), vp(img.data_ptr()), pad_h, pad_w, *_kernel_norm(norm, rgb, nv12), *more), entry.__name__)
-                if st is not None:
-                    st.read_by(main)
+            # everything that comes from the host travels in ONE pinned staging buffer and one copy: pixels, frame table, host tables
+            _, (images_ptr, boxes_ptr, image_of_ptr) = call.upload([a for _, _, a in parts], (frame_table, boxes, image_of), name_frames)
+            img, scale_factor = new(n, 3, pad_h, pad_w, dtype=torch.float32), new(n, 4, dtype=torch.float32)
+            desc, img_hw, flags = new(n, _NV12_DESC_WORDS if nv12 else _DESC_WORDS), new(n, 2), new(n)
+            vp = C.c_void_p
+            entry, more = (lib.mcg_preprocess_head_crops_nv12, (C.byref(L.YuvCoef(**coef)),)) if nv12 else (lib.mcg_preprocess_head_crops, ())
+            L.check(entry(vp(call.main.cuda_stream), vp(images_ptr), len(images), vp(boxes_ptr), vp(image_of_ptr), n, float(expand),
+                          scale_w, scale_h, vp(desc.data_ptr()), vp(img_hw.data_ptr()), vp(scale_factor.data_ptr()),
+                          vp(flags.data_ptr()), vp(img.data_ptr()), pad_h, pad_w, *_kernel_norm(norm, rgb, nv12), *more), entry.__name__)
         return img, img_hw, scale_factor, desc[:, _CROP_WORD:_CROP_WORD + 4], flags
 
     def draw_arrows(self, images, boxes, gaze, image_of, color=None, pixel_format='bgr', matrix='bt601', copy=False, device='cuda:0', stream=None,
@@ -670,58 +800,23 @@ class DevicePipeline:
         -> (images on the device, in order; flags [n] int32 on the device: 0 drawn -- possibly no pixel --, 2 unusable)."""
         lib = L.load()
         nv12, _ = _pixel_format(pixel_format, matrix)
-        length, min_thickness, ratio, tip_length = _arrow_params(**params)
+        arrow = _arrow_params(**params)
         entry = lib.mcg_draw_gaze_arrows_nv12 if nv12 else lib.mcg_draw_gaze_arrows
-        dev = _device(device)
-        images = list(images)
-        planes = [_nv12_planes(k, im, dev) for k, im in enumerate(images)] if nv12 else None
-        dev = _device(dev, entry.__name__)
-        if not len(images):
-            raise ValueError('draw_arrows: no frames')
-        table, _ = _image_table(images, dev, planes)              # every frame is checked before the first clone or upload
-        boxes, image_of, gaze, n = _row_tables('draw_arrows', 'arrows', len(images), boxes, image_of, gaze)
-        for name, t in (('box', boxes), ('gaze', gaze)):
-            if isinstance(t, np.ndarray) and not np.isfinite(t).all():
-                raise ValueError(f'draw_arrows: {name} {int(np.flatnonzero(~np.isfinite(t).all(axis=1))[0])} is not finite')
+        checked = _drawing_checked('draw_arrows', 'arrows', entry, images, boxes, gaze, image_of, nv12, device)
+        dev, n = checked[0], checked[-1]
         one, per_row = _arrow_colors(color, n, nv12, matrix)
-        with torch.cuda.device(dev):
-            main = _caller_stream(stream, dev)
-            with torch.cuda.stream(main):
-                out, pixels, in_place = _arrow_targets(images, planes, copy, dev)
-                if not in_place:                                  # the table of the tensors that are drawn into
-                    table, _ = _image_table(out, dev, [_nv12_planes(k, o, dev) for k, o in enumerate(out)] if nv12 else None)
-                h_max, w_max = int(table['h'].max()), int(table['w'].max())
-                if h_max > ARROW_SIDE or w_max > ARROW_SIDE:
-                    raise ValueError(f'draw_arrows: frames of at most {ARROW_SIDE} pixels a side, got {h_max} x {w_max}')
-                if isinstance(boxes, np.ndarray) and isinstance(gaze, np.ndarray) and n:
-                    _arrow_rows(boxes, gaze, image_of if isinstance(image_of, np.ndarray) else np.zeros(n, np.int32),
-                                [(int(r['h']), int(r['w'])) for r in table], True, length=length, min_thickness=min_thickness,
-                                thickness_ratio=ratio, tip_length=tip_length)
-                boxes = boxes if isinstance(boxes, np.ndarray) else boxes.to(dev, torch.float32).contiguous()
-                image_of = image_of if isinstance(image_of, np.ndarray) else image_of.to(dev, torch.int32).contiguous()
-                gaze_stride = 2
-                if isinstance(gaze, torch.Tensor):
-                    if not (gaze.device == dev and gaze.dtype == torch.float32 and gaze.stride(1) == 1 and (n <= 1 or gaze.stride(0) >= 2)):
-                        gaze = gaze.to(dev, torch.float32).contiguous()
-                    gaze_stride = int(gaze.stride(0)) if n > 1 else int(gaze.shape[1])
-                frame_table = table
-                if in_place and per_row is None and not (isinstance(boxes, np.ndarray) or isinstance(gaze, np.ndarray) or isinstance(image_of, np.ndarray)):
-                    # device frames drawn in place, device tables, one colour: only the frame table, and only the first time the frames are seen
-                    frame_table = self._device_image_table(table, dev, nv12)
-                # everything that comes from the host travels in ONE pinned staging buffer and one copy: pixels, frame table, host tables
-                st, staged, (images_ptr, boxes_ptr, gaze_ptr, image_of_ptr, colors_ptr) = self._ring.upload([a for _, a in pixels], (frame_table, boxes, gaze, image_of, per_row), dev, main)
-                for (dst, _), src in zip(pixels, staged):         # out of the stage (the next calls reuse it) into the tensor handed back
-                    dst.copy_(src.view(dst.shape))
-                flags = torch.empty(n, dtype=torch.int32, device=dev)
-                if n:
-                    plan = torch.empty(n, _ARROW_WORDS, dtype=torch.int32, device=dev)
-                    vp = C.c_void_p
-                    L.check(entry(vp(main.cuda_stream), vp(images_ptr), len(out), h_max, w_max, vp(boxes_ptr), vp(gaze_ptr),
-                                  gaze_stride, vp(image_of_ptr), n, length, min_thickness, ratio, tip_length,
-                                  None if one is None else (C.c_ubyte * 3)(*[int(v) for v in one]), vp(colors_ptr), vp(plan.data_ptr()),
-                                  vp(flags.data_ptr())), entry.__name__)
-                if st is not None:
-                    st.read_by(main)
+        with _call_scope(self._ring, dev, stream) as call:
+            out, pixels, in_place, table, h_max, w_max, boxes, gaze, gaze_stride, image_of = _drawing_placed('draw_arrows', checked, nv12, copy, arrow, 1)
+            images_ptr, boxes_ptr, gaze_ptr, image_of_ptr, colors_ptr = self._drawing_upload(call, nv12, table, pixels, in_place,
+                                                                                              (boxes, gaze, image_of, per_row))
+            flags = torch.empty(n, dtype=torch.int32, device=dev)
+            if n:
+                plan = torch.empty(n, _ARROW_WORDS, dtype=torch.int32, device=dev)
+                vp = C.c_void_p
+                L.check(entry(vp(call.main.cuda_stream), vp(images_ptr), len(out), h_max, w_max, vp(boxes_ptr), vp(gaze_ptr),
+                              gaze_stride, vp(image_of_ptr), n, *arrow,
+                              None if one is None else (C.c_ubyte * 3)(*[int(v) for v in one]), vp(colors_ptr), vp(plan.data_ptr()),
+                              vp(flags.data_ptr())), entry.__name__)
         return out, flags
 
     def draw_attention(self, images, boxes, gaze, image_of, kind, target, hit, mutual, regions=None, region_image=None, region_period=0,
@@ -745,100 +840,37 @@ class DevicePipeline:
         lib = L.load()
         who = 'draw_attention'
         nv12, _ = _pixel_format(pixel_format, matrix)
-        length, min_thickness, ratio, tip_length = _arrow_params(lowest=0, **params)
+        arrow = _arrow_params(lowest=0, **params)
         line_thickness, region_thickness = _overlay_thickness(who, line_thickness=line_thickness, region_thickness=region_thickness)
         _, _, period = _target_params(region_period=region_period, who=who)
         pal = _overlay_palette(who, palette, nv12, matrix)
         entry = lib.mcg_draw_attention_nv12 if nv12 else lib.mcg_draw_attention
-        dev = _device(device)
-        images = list(images)
-        planes = [_nv12_planes(k, im, dev) for k, im in enumerate(images)] if nv12 else None
-        dev = _device(dev, entry.__name__)
-        if not len(images):
-            raise ValueError(f'{who}: no frames')
-        table, _ = _image_table(images, dev, planes)              # every frame is checked before the first clone or upload
-        boxes, image_of, gaze, n = _row_tables(who, 'rows', len(images), boxes, image_of, gaze)
-        for name, t in (('box', boxes), ('gaze', gaze)):
-            if isinstance(t, np.ndarray) and not np.isfinite(t).all():
-                raise ValueError(f'{who}: {name} {int(np.flatnonzero(~np.isfinite(t).all(axis=1))[0])} is not finite')
-        on_device = lambda t: isinstance(t, torch.Tensor) and t.is_cuda
+        checked = _drawing_checked(who, 'rows', entry, images, boxes, gaze, image_of, nv12, device)
+        dev, n = checked[0], checked[-1]
         found = (kind, target, hit, mutual)
-        if not any(on_device(t) for t in found):
+        if not any(_on_device(t) for t in found):
             found = _overlay_targets(who, n, *found)
-        if _holds_polygon(regions):
-            regions = region_polygons(regions)
-        poly = isinstance(regions, PolyRegions)
-        regions_there = any(on_device(t) for t in ((*regions, region_image) if poly else (regions, region_image)))
-        if not regions_there:
-            xy, start, region_image = _overlay_regions(who, regions, region_image)
-        with torch.cuda.device(dev):
-            main = _caller_stream(stream, dev)
-            with torch.cuda.stream(main):
-                out, pixels, in_place = _arrow_targets(images, planes, copy, dev)
-                if not in_place:                                  # the table of the tensors that are drawn into
-                    table, _ = _image_table(out, dev, [_nv12_planes(k, o, dev) for k, o in enumerate(out)] if nv12 else None)
-                h_max, w_max = int(table['h'].max()), int(table['w'].max())
-                if h_max > ARROW_SIDE or w_max > ARROW_SIDE:
-                    raise ValueError(f'{who}: frames of at most {ARROW_SIDE} pixels a side, got {h_max} x {w_max}')
-                if isinstance(boxes, np.ndarray) and isinstance(gaze, np.ndarray) and n:
-                    _arrow_rows(boxes, gaze, image_of if isinstance(image_of, np.ndarray) else np.zeros(n, np.int32),
-                                [(int(r['h']), int(r['w'])) for r in table], True, length=length, min_thickness=min_thickness,
-                                thickness_ratio=ratio, tip_length=tip_length, lowest=0)
-                there = lambda t, dtype: (t if isinstance(t, torch.Tensor) else torch.as_tensor(np.asarray(t))).to(dev, dtype).contiguous()
-                boxes = boxes if isinstance(boxes, np.ndarray) else boxes.to(dev, torch.float32).contiguous()
-                image_of = image_of if isinstance(image_of, np.ndarray) else image_of.to(dev, torch.int32).contiguous()
-                gaze_stride = 2
-                if isinstance(gaze, torch.Tensor):
-                    if not (gaze.device == dev and gaze.dtype == torch.float32 and gaze.stride(1) == 1 and (n <= 1 or gaze.stride(0) >= 2)):
-                        gaze = gaze.to(dev, torch.float32).contiguous()
-                    gaze_stride = int(gaze.stride(0)) if n > 1 else int(gaze.shape[1])
-                if not isinstance(found[0], np.ndarray):          # one of them is on the device: the others are moved with torch
-                    found = tuple(there(t, torch.float32 if k == 2 else torch.int32) for k, t in enumerate(found))
-                    for name, t, shape in zip(('kind', 'target', 'hit', 'mutual'), found, ((n,), (n,), (n, 2), (n,))):
-                        if tuple(t.shape) != shape:
-                            raise ValueError(f'{who}: {name} must be {list(shape)}, got {tuple(t.shape)}')
-                if regions_there:
-                    if poly:
-                        xy, start = there(regions.xy, torch.float32), there(regions.start, torch.int32)
-                        if xy.ndim != 2 or xy.shape[1] != 2 or start.ndim != 1 or start.shape[0] < 1:
-                            raise ValueError(f'{who}: PolyRegions is xy [V, 2] and start [m + 1], got {tuple(xy.shape)} and {tuple(start.shape)}')
-                    else:
-                        if regions is None:
-                            raise ValueError(f'{who}: region_image without regions')
-                        xy = there(regions, torch.float32)
-                        if xy.ndim != 2 or xy.shape[1] != 4:
-                            raise ValueError(f'{who}: regions must be [m, 4] x1 y1 x2 y2, got {tuple(xy.shape)}')
-                        xy = xy.view(-1, 2)                       # a rectangle is a 2-vertex region
-                        start = torch.arange(0, xy.shape[0] + 1, 2, dtype=torch.int32, device=dev)
-                    m = int(start.shape[0]) - 1
-                    region_image = torch.full((m,), -1, dtype=torch.int32, device=dev) if region_image is None else there(region_image, torch.int32)
-                    if tuple(region_image.shape) != (m,):
-                        raise ValueError(f'{who}: region_image must be [{m}], one per region; got {tuple(region_image.shape)}')
-                m, V = int(region_image.shape[0]), int(xy.shape[0])
-                _overlay_counts(who, n, m, V, len(out))
-                tables = (boxes, gaze, image_of, *found, xy, start, region_image)
-                frame_table = table
-                if in_place and not any(isinstance(t, np.ndarray) for t in tables):
-                    # device frames drawn in place and device tables: only the frame table, and only the first time the frames are seen
-                    frame_table = self._device_image_table(table, dev, nv12)
-                operands = [t if (t.size if isinstance(t, np.ndarray) else t.numel()) else None for t in tables]
-                # everything that comes from the host travels in ONE pinned staging buffer and one copy: pixels, frame table, host tables
-                st, staged, ptrs = self._ring.upload([a for _, a in pixels], (frame_table, *operands), dev, main)
-                for (dst, _), src in zip(pixels, staged):         # out of the stage (the next calls reuse it) into the tensor handed back
-                    dst.copy_(src.view(dst.shape))
-                new = lambda *shape: torch.empty(*shape, dtype=torch.int32, device=dev)
-                flags, region_flags, region_active = new(n), new(m), new(len(out), m)
-                if n or m:
-                    work = new(24 * (m + 2 * n) + 64 * m)         # the header's formula: (m + 2 n) stroke records, then [m][32][2] vertices
-                    vp = C.c_void_p
-                    images_ptr, boxes_ptr, gaze_ptr, image_of_ptr, kind_ptr, target_ptr, hit_ptr, mutual_ptr, xy_ptr, start_ptr, ri_ptr = ptrs
-                    L.check(entry(vp(main.cuda_stream), vp(images_ptr), len(out), h_max, w_max, vp(boxes_ptr), vp(gaze_ptr), gaze_stride,
-                                  vp(image_of_ptr), n, vp(kind_ptr), vp(target_ptr), vp(hit_ptr), vp(mutual_ptr), vp(xy_ptr), V, vp(start_ptr),
-                                  vp(ri_ptr), m, period, (C.c_ubyte * 21)(*[int(v) for v in pal.reshape(-1)]), length, min_thickness, ratio,
-                                  tip_length, line_thickness, region_thickness, vp(work.data_ptr()), 4 * work.numel(), vp(flags.data_ptr()),
-                                  vp(region_flags.data_ptr()), vp(region_active.data_ptr())), entry.__name__)
-                if st is not None:
-                    st.read_by(main)
+        with _call_scope(self._ring, dev, stream) as call:
+            _, xy, start, region_image, m, V = _region_operands(who, regions, region_image, dev, as_vertices=True)
+            out, pixels, in_place, table, h_max, w_max, boxes, gaze, gaze_stride, image_of = _drawing_placed(who, checked, nv12, copy, arrow, 0)
+            if not isinstance(found[0], np.ndarray):              # one of them is on the device: the others are moved with torch
+                found = tuple(_there(t, dev, torch.float32 if k == 2 else torch.int32) for k, t in enumerate(found))
+                for name, t, shape in zip(('kind', 'target', 'hit', 'mutual'), found, ((n,), (n,), (n, 2), (n,))):
+                    if tuple(t.shape) != shape:
+                        raise ValueError(f'{who}: {name} must be {list(shape)}, got {tuple(t.shape)}')
+            _overlay_counts(who, n, m, V, len(out))
+            ptrs = self._drawing_upload(call, nv12, table, pixels, in_place, (boxes, gaze, image_of, *found, xy, start, region_image), empty_is_null=True)
+            new = lambda *shape: torch.empty(*shape, dtype=torch.int32, device=dev)
+            flags, region_flags, region_active = new(n), new(m), new(len(out), m)
+            if n or m:
+                work = new(24 * (m + 2 * n) + 64 * m)             # the header's formula: (m + 2 n) stroke records, then [m][32][2] vertices
+                vp = C.c_void_p
+                images_ptr, boxes_ptr, gaze_ptr, image_of_ptr, kind_ptr, target_ptr, hit_ptr, mutual_ptr, xy_ptr, start_ptr, ri_ptr = ptrs
+                L.check(entry(vp(call.main.cuda_stream), vp(images_ptr), len(out), h_max, w_max, vp(boxes_ptr), vp(gaze_ptr), gaze_stride,
+                              vp(image_of_ptr), n, vp(kind_ptr), vp(target_ptr), vp(hit_ptr), vp(mutual_ptr), vp(xy_ptr), V, vp(start_ptr),
+                              vp(ri_ptr), m, period, (C.c_ubyte * 21)(*[int(v) for v in pal.reshape(-1)]), *arrow,
+                              line_thickness, region_thickness, vp(work.data_ptr()), 4 * work.numel(), vp(flags.data_ptr()),
+                              vp(region_flags.data_ptr()), vp(region_active.data_ptr())), entry.__name__)
         return out, flags, region_flags, region_active
 
     def gaze_targets(self, boxes, gaze, image_of, regions=None, region_image=None, region_period=0, expand=0.25, camera_angle=10.0, device='cuda:0',
@@ -862,75 +894,34 @@ class DevicePipeline:
         who = 'gaze_targets'
         expand, cos2, period = _target_params(expand, camera_angle, region_period, who)
         dev = _device(device, 'mcg_gaze_targets')
-        on_device = lambda t: isinstance(t, torch.Tensor) and t.is_cuda
-        rows_there = any(on_device(t) for t in (boxes, gaze, image_of))
-        if _holds_polygon(regions):
-            regions = region_polygons(regions)
-        poly = isinstance(regions, PolyRegions)                   # the vertex form: mcg_gaze_targets_poly; anything else is today's rectangles
-        xy, start = regions if poly else (None, None)
-        regions_there = any(on_device(t) for t in ((xy, start, region_image) if poly else (regions, region_image)))
+        rows_there = any(_on_device(t) for t in (boxes, gaze, image_of))
         if not rows_there:
             boxes, gaze, image_of = _target_rows(who, boxes, gaze, image_of)
-        if not regions_there:
-            if poly:
-                xy, start, region_image = _poly_tables(who, regions, region_image)
-            else:
-                regions, region_image = _region_tables(who, regions, region_image)
-        with torch.cuda.device(dev):
-            main = _caller_stream(stream, dev)
-            with torch.cuda.stream(main):
-                there = lambda t, dtype: (t if isinstance(t, torch.Tensor) else torch.as_tensor(np.asarray(t))).to(dev, dtype)
-                gaze_stride = 3
-                if rows_there:
-                    boxes, gaze = there(boxes, torch.float32).contiguous(), there(gaze, torch.float32)
-                    n = int(boxes.shape[0])
-                    if boxes.ndim != 2 or boxes.shape[1] != 4 or gaze.ndim != 2 or gaze.shape[0] != n or gaze.shape[1] < 3:
-                        raise ValueError(f'{who}: boxes {tuple(boxes.shape)} and gaze {tuple(gaze.shape)} must be [n,4] and [n,>=3]')
-                    if not (gaze.stride(1) == 1 and (n <= 1 or gaze.stride(0) >= 3)):
-                        gaze = gaze.contiguous()
-                    gaze_stride = int(gaze.stride(0)) if n > 1 else int(gaze.shape[1])
-                    image_of = torch.zeros(n, dtype=torch.int32, device=dev) if image_of is None else there(image_of, torch.int32).contiguous()
-                    if tuple(image_of.shape) != (n,):
-                        raise ValueError(f'{who}: image_of must be [{n}], one per row; got {tuple(image_of.shape)}')
+        with _call_scope(self._ring, dev, stream) as call:
+            # the vertex form is mcg_gaze_targets_poly; anything else is the rectangles [m,4] of mcg_gaze_targets
+            poly, table, start, region_image, m, V = _region_operands(who, regions, region_image, dev)
+            if rows_there:
+                boxes, gaze = _there(boxes, dev, torch.float32), _tensor(gaze)
                 n = int(boxes.shape[0])
-                if regions_there:
-                    if poly:
-                        xy, start = there(xy, torch.float32).contiguous(), there(start, torch.int32).contiguous()
-                        if xy.ndim != 2 or xy.shape[1] != 2 or start.ndim != 1 or start.shape[0] < 1:
-                            raise ValueError(f'{who}: PolyRegions is xy [V, 2] and start [m + 1], got {tuple(xy.shape)} and {tuple(start.shape)}')
-                        m = int(start.shape[0]) - 1
-                    else:
-                        if regions is None:
-                            raise ValueError(f'{who}: region_image without regions')
-                        regions = there(regions, torch.float32).contiguous()
-                        if regions.ndim != 2 or regions.shape[1] != 4:
-                            raise ValueError(f'{who}: regions must be [m, 4] x1 y1 x2 y2, got {tuple(regions.shape)}')
-                        m = int(regions.shape[0])
-                    region_image = torch.full((m,), -1, dtype=torch.int32, device=dev) if region_image is None else \
-                        there(region_image, torch.int32).contiguous()
-                    if tuple(region_image.shape) != (m,):
-                        raise ValueError(f'{who}: region_image must be [{m}], one per region; got {tuple(region_image.shape)}')
-                m = int(region_image.shape[0])
-                V = int(xy.shape[0]) if poly else 0
-                _check_counts(who, n, m, V)
-                new = lambda *shape, dtype=torch.int32: torch.empty(*shape, dtype=dtype, device=dev)
-                out = (new(n), new(n), new(n, dtype=torch.float32), new(n, 2, dtype=torch.float32), new(n), new(n))
-                if n == 0:
-                    return out
-                vp = C.c_void_p
-                if poly:
-                    st, _, (boxes_ptr, gaze_ptr, image_of_ptr, xy_ptr, start_ptr, region_image_ptr) = self._ring.upload(
-                        [], (boxes, gaze, image_of, xy if V else None, start if m else None, region_image if m else None), dev, main)
-                    L.check(lib.mcg_gaze_targets_poly(vp(main.cuda_stream), vp(boxes_ptr), vp(gaze_ptr), gaze_stride, vp(image_of_ptr), n, vp(xy_ptr), V,
-                                                      vp(start_ptr), vp(region_image_ptr), m, period, expand, cos2, *(vp(t.data_ptr()) for t in out)),
-                            'mcg_gaze_targets_poly')
-                else:
-                    st, _, (boxes_ptr, gaze_ptr, image_of_ptr, regions_ptr, region_image_ptr) = self._ring.upload(
-                        [], (boxes, gaze, image_of, regions if m else None, region_image if m else None), dev, main)
-                    L.check(lib.mcg_gaze_targets(vp(main.cuda_stream), vp(boxes_ptr), vp(gaze_ptr), gaze_stride, vp(image_of_ptr), n, vp(regions_ptr),
-                                                 vp(region_image_ptr), m, period, expand, cos2, *(vp(t.data_ptr()) for t in out)), 'mcg_gaze_targets')
-                if st is not None:
-                    st.read_by(main)
+                if boxes.ndim != 2 or boxes.shape[1] != 4 or gaze.ndim != 2 or gaze.shape[0] != n or gaze.shape[1] < 3:
+                    raise ValueError(f'{who}: boxes {tuple(boxes.shape)} and gaze {tuple(gaze.shape)} must be [n,4] and [n,>=3]')
+                image_of = torch.zeros(n, dtype=torch.int32, device=dev) if image_of is None else _there(image_of, dev, torch.int32)
+                if tuple(image_of.shape) != (n,):
+                    raise ValueError(f'{who}: image_of must be [{n}], one per row; got {tuple(image_of.shape)}')
+            n = int(boxes.shape[0])
+            gaze, gaze_stride = _gaze_operand(gaze, n, 3, dev)
+            _check_counts(who, n, m, V)
+            new = lambda *shape, dtype=torch.int32: torch.empty(*shape, dtype=dtype, device=dev)
+            out = (new(n), new(n), new(n, dtype=torch.float32), new(n, 2, dtype=torch.float32), new(n), new(n))
+            if n == 0:
+                return out
+            _, (boxes_ptr, gaze_ptr, image_of_ptr, table_ptr, start_ptr, region_image_ptr) = call.upload(
+                [], (boxes, gaze, image_of, table if (V if poly else m) else None, start if m else None, region_image if m else None))
+            vp = C.c_void_p
+            entry, regions_at = (lib.mcg_gaze_targets_poly, (vp(table_ptr), V, vp(start_ptr), vp(region_image_ptr))) if poly else \
+                (lib.mcg_gaze_targets, (vp(table_ptr), vp(region_image_ptr)))
+            L.check(entry(vp(call.main.cuda_stream), vp(boxes_ptr), vp(gaze_ptr), gaze_stride, vp(image_of_ptr), n, *regions_at, m, period, expand, cos2,
+                          *(vp(t.data_ptr()) for t in out)), entry.__name__)
         return out
 
     def dwell_state(self, columns, device='cuda:0'):
@@ -969,44 +960,40 @@ class DevicePipeline:
             if t is not None and not (isinstance(t, torch.Tensor) and t.device == dev and t.dtype == torch.int32 and t.is_contiguous() and
                                       t.ndim == len(shape) and tuple(t.shape[1:]) == shape[1:]):
                 raise TypeError(f'{who}: {name} is a contiguous int32 {list(shape)} tensor on {dev} (it is updated in place)')
-        with torch.cuda.device(dev):
-            main = _caller_stream(stream, dev)
-            with torch.cuda.stream(main):
-                if there:
-                    moved = []
-                    for name, t in zip(('person', 'kind', 'ident', 'mutual', 'tag'), tables):
-                        if t is not None:
-                            t = t if isinstance(t, torch.Tensor) else torch.as_tensor(np.asarray(t))
-                            if t.dtype.is_floating_point or t.dtype.is_complex:
-                                raise TypeError(f'{who}: {name} must hold integers, got {t.dtype}')
-                            t = t.to(dev, torch.int32).contiguous()
-                            if t.ndim != 2 or (moved and tuple(t.shape) != tuple(moved[0].shape)):
-                                raise ValueError(f'{who}: person, kind, ident, mutual and tag are [F, R] tables of one shape; {name} is {tuple(t.shape)}')
-                        moved.append(t)
-                    tables = moved
-                    F, R = (int(v) for v in tables[0].shape)
-                M = 0 if region_frames is None else int(region_frames.shape[0])
-                E = _dwell_counts(who, F, R, M, max_events)
-                if state is not None and int(state.shape[0]) != R:
-                    raise ValueError(f'{who}: the state of {R} columns is [{R}, 16], got {tuple(state.shape)}')
-                if state is None:
-                    state = torch.zeros(R, 16, dtype=torch.int32, device=dev)
-                if region_frames is None:
-                    region_frames = torch.zeros(0, dtype=torch.int32, device=dev)
-                new = lambda *shape: torch.empty(*shape, dtype=torch.int32, device=dev)
-                dwell, ended, events, num = new(F, R, 4), new(F, R, 8), torch.zeros(E, 10, dtype=torch.int32, device=dev), \
-                    torch.zeros(1, dtype=torch.int32, device=dev)
-                if F == 0:
-                    return dwell, ended, events, num, state, region_frames
-                st, _, ptrs = self._ring.upload([], tuple(tables), dev, main)
-                ptrs = [ptrs[k] for k in (0, 4, 1, 2, 3)]         # the entry takes the tag behind the person
-                vp = C.c_void_p
-                # max_events = 0 still counts: the launch needs a table address and writes no row of it
-                L.check(lib.mcg_gaze_dwell(vp(main.cuda_stream), *(vp(p) for p in ptrs), F, R, frame0, enter, exit, vp(state.data_ptr()),
-                                           vp(region_frames.data_ptr() if M else None), M, vp(dwell.data_ptr()), vp(ended.data_ptr()),
-                                           vp(events.data_ptr() if E else num.data_ptr()), E, vp(num.data_ptr())), 'mcg_gaze_dwell')
-                if st is not None:
-                    st.read_by(main)
+        with _call_scope(self._ring, dev, stream) as call:
+            if there:
+                moved = []
+                for name, t in zip(('person', 'kind', 'ident', 'mutual', 'tag'), tables):
+                    if t is not None:
+                        t = t if isinstance(t, torch.Tensor) else _tensor(t)
+                        if t.dtype.is_floating_point or t.dtype.is_complex:
+                            raise TypeError(f'{who}: {name} must hold integers, got {t.dtype}')
+                        t = t.to(dev, torch.int32).contiguous()
+                        if t.ndim != 2 or (moved and tuple(t.shape) != tuple(moved[0].shape)):
+                            raise ValueError(f'{who}: person, kind, ident, mutual and tag are [F, R] tables of one shape; {name} is {tuple(t.shape)}')
+                    moved.append(t)
+                tables = moved
+                F, R = (int(v) for v in tables[0].shape)
+            M = 0 if region_frames is None else int(region_frames.shape[0])
+            E = _dwell_counts(who, F, R, M, max_events)
+            if state is not None and int(state.shape[0]) != R:
+                raise ValueError(f'{who}: the state of {R} columns is [{R}, 16], got {tuple(state.shape)}')
+            if state is None:
+                state = torch.zeros(R, 16, dtype=torch.int32, device=dev)
+            if region_frames is None:
+                region_frames = torch.zeros(0, dtype=torch.int32, device=dev)
+            new = lambda *shape: torch.empty(*shape, dtype=torch.int32, device=dev)
+            dwell, ended, events, num = new(F, R, 4), new(F, R, 8), torch.zeros(E, 10, dtype=torch.int32, device=dev), \
+                torch.zeros(1, dtype=torch.int32, device=dev)
+            if F == 0:
+                return dwell, ended, events, num, state, region_frames
+            _, ptrs = call.upload([], tuple(tables))
+            ptrs = [ptrs[k] for k in (0, 4, 1, 2, 3)]             # the entry takes the tag behind the person
+            vp = C.c_void_p
+            # max_events = 0 still counts: the launch needs a table address and writes no row of it
+            L.check(lib.mcg_gaze_dwell(vp(call.main.cuda_stream), *(vp(p) for p in ptrs), F, R, frame0, enter, exit, vp(state.data_ptr()),
+                                       vp(region_frames.data_ptr() if M else None), M, vp(dwell.data_ptr()), vp(ended.data_ptr()),
+                                       vp(events.data_ptr() if E else num.data_ptr()), E, vp(num.data_ptr())), 'mcg_gaze_dwell')
         return dwell, ended, events, num, state, region_frames
 
     def letterbox(self, frames, new_shape=640, stride=32, auto=True, scaleup=True, dtype=torch.float16, rgb=False, pixel_format='bgr', matrix='bt601',
@@ -1043,24 +1030,19 @@ class DevicePipeline:
         fd['src_w'] = fd['crop_w'] = table['w']
         fd['out_h'], fd['out_w'] = [g.unpad_h for g in geoms], [g.unpad_w for g in geoms]
         desc['top'], desc['left'] = [g.top for g in geoms], [g.left for g in geoms]
-        with torch.cuda.device(dev):
-            main = _caller_stream(stream, dev)
-            with torch.cuda.stream(main):
-                # device frames: only the descriptor table comes from the host, and only the first time these frames and sizes are seen
-                frame_table = desc if parts else self._kept(self._image_tables, (dev.index, desc.tobytes(), 'letterbox', nv12),
-                                                            lambda: torch.from_numpy(desc.view(np.uint8).reshape(-1).copy()).to(dev))
+        with _call_scope(self._ring, dev, stream) as call:
+            # device frames: only the descriptor table comes from the host, and only the first time these frames and sizes are seen
+            frame_table = desc if parts else self._device_table(desc, dev, 'letterbox', nv12)
 
-                def name_frames(at):                              # a host frame's address: where its bytes land in the device twin
-                    for (k, f, _), a in zip(parts, at):
-                        fd['uv' if f == 'uv' else 'src'][k] = a
+            def name_frames(at):                                  # a host frame's address: where its bytes land in the device twin
+                for (k, f, _), a in zip(parts, at):
+                    fd['uv' if f == 'uv' else 'src'][k] = a
 
-                st, _, (desc_ptr,) = self._ring.upload([a for _, _, a in parts], (frame_table,), dev, main, name_frames)
-                img = torch.empty(len(frames), 3, out_h, out_w, dtype=out_dtype, device=dev)
-                vp = C.c_void_p
-                L.check(entry(vp(main.cuda_stream), vp(desc_ptr), len(frames), vp(img.data_ptr()), out_h, out_w, _LETTERBOX_TYPES[out_dtype],
-                              int(not (rgb and not nv12)), *more), entry.__name__)
-                if st is not None:
-                    st.read_by(main)
+            _, (desc_ptr,) = call.upload([a for _, _, a in parts], (frame_table,), name_frames)
+            img = torch.empty(len(frames), 3, out_h, out_w, dtype=out_dtype, device=dev)
+            vp = C.c_void_p
+            L.check(entry(vp(call.main.cuda_stream), vp(desc_ptr), len(frames), vp(img.data_ptr()), out_h, out_w, _LETTERBOX_TYPES[out_dtype],
+                          int(not (rgb and not nv12)), *more), entry.__name__)
         return img, geoms
 
     def detect_heads(self, pred, in_shape, frame_hw, conf_thres=0.25, iou_thres=0.45, only_class=1, agnostic=False, max_nms=30000, max_det=300,
@@ -1082,40 +1064,36 @@ class DevicePipeline:
         lib = L.load()
         params = _detect_params(conf_thres, iou_thres, only_class, agnostic, max_nms, max_det)
         conf_thres, iou_thres, only_class, agnostic, max_nms, max_det = params
-        on_device = isinstance(pred, torch.Tensor) and pred.is_cuda
-        if not on_device:
+        pred_there = isinstance(pred, torch.Tensor) and pred.is_cuda
+        if not pred_there:
             pred = _host_array(pred)
-        if pred.dtype not in ((torch.float32, torch.float16) if on_device else (np.float32, np.float16)):
+        if pred.dtype not in ((torch.float32, torch.float16) if pred_there else (np.float32, np.float16)):
             raise TypeError(f'detect_heads: pred must be float32 or float16, got {pred.dtype}')
         B, N, nc, in_h, in_w, hw = _detect_shapes(tuple(pred.shape), in_shape, frame_hw)
-        dev = _device(pred.device if on_device else device, 'mcg_detect_heads')
-        with torch.cuda.device(dev):
-            main = _caller_stream(stream, dev)
-            with torch.cuda.stream(main):
-                new = lambda *shape, dtype=torch.int32: torch.empty(*shape, dtype=dtype, device=dev)
-                out = (new(B, max_det, 4, dtype=torch.float32), new(B, max_det, dtype=torch.float32), new(B, max_det), new(B, max_det), new(B), new(B))
-                if B == 0:
-                    return out
-                if on_device:
-                    pred = pred.float()
-                    if pred.stride(2) != 1 or pred.stride(1) < 5 + nc or pred.stride(0) < 0:
-                        pred = pred.contiguous()
-                    image_stride, row_stride = int(pred.stride(0)), int(pred.stride(1))
-                else:
-                    pred, image_stride, row_stride = np.ascontiguousarray(pred, dtype=np.float32), N * (5 + nc), 5 + nc
-                st, _, (pred_ptr,) = self._ring.upload([], (pred,), dev, main)
-                if hw is None:
-                    frame_hw = frame_hw.to(torch.int32).contiguous()
-                else:
-                    frame_hw = self._kept(self._frame_hw_tables, (dev.index, hw.tobytes()), lambda: torch.from_numpy(hw.copy()).to(dev))
-                ws = self._kept(self._detect_workspaces, (dev.index, B, N),
-                                lambda: torch.empty(int(lib.mcg_detect_heads_workspace_bytes(B, N)), dtype=torch.uint8, device=dev))
-                vp = C.c_void_p
-                L.check(lib.mcg_detect_heads(vp(main.cuda_stream), vp(pred_ptr), B, N, nc, image_stride, row_stride, in_h, in_w, vp(frame_hw.data_ptr()),
-                                             conf_thres, iou_thres, only_class, int(agnostic), min(max_nms, N), max_det, *(vp(t.data_ptr()) for t in out),
-                                             vp(ws.data_ptr()), ws.numel()), 'mcg_detect_heads')
-                if st is not None:
-                    st.read_by(main)
+        dev = _device(pred.device if pred_there else device, 'mcg_detect_heads')
+        with _call_scope(self._ring, dev, stream) as call:
+            new = lambda *shape, dtype=torch.int32: torch.empty(*shape, dtype=dtype, device=dev)
+            out = (new(B, max_det, 4, dtype=torch.float32), new(B, max_det, dtype=torch.float32), new(B, max_det), new(B, max_det), new(B), new(B))
+            if B == 0:
+                return out
+            if pred_there:
+                pred = pred.float()
+                if pred.stride(2) != 1 or pred.stride(1) < 5 + nc or pred.stride(0) < 0:
+                    pred = pred.contiguous()
+                image_stride, row_stride = int(pred.stride(0)), int(pred.stride(1))
+            else:
+                pred, image_stride, row_stride = np.ascontiguousarray(pred, dtype=np.float32), N * (5 + nc), 5 + nc
+            _, (pred_ptr,) = call.upload([], (pred,))
+            if hw is None:
+                frame_hw = frame_hw.to(torch.int32).contiguous()
+            else:
+                frame_hw = self._kept(self._frame_hw_tables, (dev.index, hw.tobytes()), lambda: torch.from_numpy(hw.copy()).to(dev))
+            ws = self._kept(self._detect_workspaces, (dev.index, B, N),
+                            lambda: torch.empty(int(lib.mcg_detect_heads_workspace_bytes(B, N)), dtype=torch.uint8, device=dev))
+            vp = C.c_void_p
+            L.check(lib.mcg_detect_heads(vp(call.main.cuda_stream), vp(pred_ptr), B, N, nc, image_stride, row_stride, in_h, in_w, vp(frame_hw.data_ptr()),
+                                         conf_thres, iou_thres, only_class, int(agnostic), min(max_nms, N), max_det, *(vp(t.data_ptr()) for t in out),
+                                         vp(ws.data_ptr()), ws.numel()), 'mcg_detect_heads')
         return out
 
     def track_heads(self, boxes, counts, state=None, slots=16, match_iou=0.3, max_age=5, device='cuda:0', stream=None, motion=None):
@@ -1137,10 +1115,10 @@ class DevicePipeline:
         lib = L.load()
         slots, match_iou, max_age = _track_params(slots, match_iou, max_age)
         motion = _track_motion(motion)
-        on_device = isinstance(boxes, torch.Tensor) and boxes.is_cuda
-        if not on_device:
+        boxes_there = isinstance(boxes, torch.Tensor) and boxes.is_cuda
+        if not boxes_there:
             boxes = _host_array(boxes)
-        if boxes.dtype != (torch.float32 if on_device else np.float32):
+        if boxes.dtype != (torch.float32 if boxes_there else np.float32):
             raise TypeError(f'track_heads: boxes must be float32, got {boxes.dtype}')
         counts_there = isinstance(counts, torch.Tensor) and counts.is_cuda
         if not counts_there:
@@ -1150,40 +1128,36 @@ class DevicePipeline:
         elif counts.dtype not in (torch.int32, torch.int64):
             raise TypeError(f'track_heads: counts must hold integers, got {counts.dtype}')
         Q, T, D, given_q = _track_shapes(tuple(boxes.shape), tuple(counts.shape), None if state is None else tuple(state.shape), slots)
-        dev = _device(boxes.device if on_device else device, 'mcg_track_heads')
+        dev = _device(boxes.device if boxes_there else device, 'mcg_track_heads')
         if state is not None and not (isinstance(state, torch.Tensor) and state.device == dev and state.dtype == torch.int32 and state.is_contiguous()):
             raise TypeError(f'track_heads: the state is a contiguous int32 tensor on {dev} (it is updated in place)')
-        with torch.cuda.device(dev):
-            main = _caller_stream(stream, dev)
-            with torch.cuda.stream(main):
-                new = lambda *shape, dtype=torch.int32: torch.empty(*shape, dtype=dtype, device=dev)
-                lead = (Q, T) if given_q else (T,)
-                out = (new(*lead, slots, 4, dtype=torch.float32), new(*lead, slots), new(*lead, slots), new(*lead, slots), new(*lead, slots), new(*lead))
-                more = () if motion is None else (new(*lead, slots, 4, dtype=torch.float32),)     # state_boxes
-                if state is None:
-                    state = torch.zeros(Q, track_state_words(slots), dtype=torch.int32, device=dev)
-                if Q == 0:
-                    return out + (state,) + more
-                frame_stride = 4 * D
-                if on_device:
-                    b = boxes if given_q else boxes[None]
-                    stride = b.stride(1) if T > 1 else b.stride(0) if Q > 1 else 4 * D
-                    if not (b.stride(3) == 1 and b.stride(2) == 4 and stride >= 4 * D and (Q == 1 or T == 1 or b.stride(0) == T * stride)):
-                        b, stride = b.contiguous(), 4 * D
-                    boxes, frame_stride = b, int(stride)
-                else:
-                    boxes = np.ascontiguousarray(boxes, dtype=np.float32)
-                counts = counts.to(dev, torch.int32).contiguous() if counts_there else np.ascontiguousarray(counts, dtype=np.int32)
-                st, _, (boxes_ptr, counts_ptr) = self._ring.upload([], (boxes, counts), dev, main)
-                vp = C.c_void_p
-                head = (vp(main.cuda_stream), vp(boxes_ptr), frame_stride, vp(counts_ptr), Q, T, D, slots, match_iou, max_age)
-                tail = (vp(state.data_ptr()), *(vp(t.data_ptr()) for t in out + more))
-                if motion is None:
-                    L.check(lib.mcg_track_heads(*head, *tail), 'mcg_track_heads')
-                else:
-                    L.check(lib.mcg_track_heads_motion(*head, *motion, *tail), 'mcg_track_heads_motion')
-                if st is not None:
-                    st.read_by(main)
+        with _call_scope(self._ring, dev, stream) as call:
+            new = lambda *shape, dtype=torch.int32: torch.empty(*shape, dtype=dtype, device=dev)
+            lead = (Q, T) if given_q else (T,)
+            out = (new(*lead, slots, 4, dtype=torch.float32), new(*lead, slots), new(*lead, slots), new(*lead, slots), new(*lead, slots), new(*lead))
+            more = () if motion is None else (new(*lead, slots, 4, dtype=torch.float32),)         # state_boxes
+            if state is None:
+                state = torch.zeros(Q, track_state_words(slots), dtype=torch.int32, device=dev)
+            if Q == 0:
+                return out + (state,) + more
+            frame_stride = 4 * D
+            if boxes_there:
+                b = boxes if given_q else boxes[None]
+                stride = b.stride(1) if T > 1 else b.stride(0) if Q > 1 else 4 * D
+                if not (b.stride(3) == 1 and b.stride(2) == 4 and stride >= 4 * D and (Q == 1 or T == 1 or b.stride(0) == T * stride)):
+                    b, stride = b.contiguous(), 4 * D
+                boxes, frame_stride = b, int(stride)
+            else:
+                boxes = np.ascontiguousarray(boxes, dtype=np.float32)
+            counts = counts.to(dev, torch.int32).contiguous() if counts_there else np.ascontiguousarray(counts, dtype=np.int32)
+            _, (boxes_ptr, counts_ptr) = call.upload([], (boxes, counts))
+            vp = C.c_void_p
+            head = (vp(call.main.cuda_stream), vp(boxes_ptr), frame_stride, vp(counts_ptr), Q, T, D, slots, match_iou, max_age)
+            tail = (vp(state.data_ptr()), *(vp(t.data_ptr()) for t in out + more))
+            if motion is None:
+                L.check(lib.mcg_track_heads(*head, *tail), 'mcg_track_heads')
+            else:
+                L.check(lib.mcg_track_heads_motion(*head, *motion, *tail), 'mcg_track_heads_motion')
         return out + (state,) + more
 
 

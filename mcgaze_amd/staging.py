@@ -1,6 +1,9 @@
 """Between host and device memory for a DevicePipeline: the upload stages its entry points share -- pinned host buffers with device twins, used
-in turn, ONE copy per call on a stream of its own --, the way back for a table the host has to read (``_host_array``) and the check of a host
-frame that goes up (``_bgr_frame``)."""
+in turn, ONE copy per call on a stream of its own --, the scope every device call of the pipeline runs in (``_call_scope``: the device, the
+caller's stream, the one upload, and the mark that keeps the stage from being overwritten while the call's kernels read it), the way back for
+a table the host has to read (``_host_array``) and the check of a host frame that goes up (``_bgr_frame``)."""
+import sys
+
 import numpy as np
 import torch
 
@@ -41,8 +44,8 @@ class _Stage:
 
 
 class _StagingRing:
-    """The upload stages of a DevicePipeline, used in turn, and the copy stream of each device.  What the bytes are is the caller's business:
-    ``st, pixels_at, operands_at = upload(pixels, operands, dev, main)``, launch, ``st.read_by(main)`` if a stage was taken."""
+    """The upload stages of a DevicePipeline, used in turn, and the copy stream of each device.  ``_call_scope.upload`` takes a stage, fills it and sends
+    it; the scope marks it as read by the caller's stream when the call leaves."""
 
     def __init__(self, stages):
         self.stages, self.i, self.copy_stream = [_Stage() for _ in range(stages)], 0, {}
@@ -70,18 +73,49 @@ class _StagingRing:
         st.cs, st.main = cs, main
         return st
 
-    def upload(self, pixels, operands, dev, main, pixels_staged=None):
-        """Everything a call brings from the host, in ONE stage and one copy.  pixels: flat uint8 host arrays; operands: what the kernels
-        read, each a device tensor, a host array (staged behind the pixels, in order) or None.  A device operand is read at its own address, a
-        host operand at its staged one: -> (the stage, or None when nothing comes from the host and no stage is taken; every pixel part
-        in the device twin, as a view of it; the address of every operand, None for None).  ``pixels_staged(addresses)`` runs once the pixels are in the pinned buffer
-        and before the host operands are copied there, so it may still write into them (a frame table takes its frames' addresses, run_many
-        its descriptors) and let go of the pixels' sources."""
+
+class _call_scope:
+    """One device call of a DevicePipeline, ``with _call_scope(ring, dev, stream) as call:``.  The body runs on ``dev`` and on the caller's
+    stream (``stream``: its handle, None: the current one), brings what it has on the host up with ONE ``call.upload`` and launches on
+    ``call.main``.  When the body leaves -- at its end or by an early ``return`` -- the stage the upload took is marked as read by what was
+    launched, so that a later call does not overwrite the staging buffer under those kernels; a body that took no stage marks none, and
+    one that raises marks none either.
+    Every call pays for the scope and host-bound calls are 30 - 60 us long (profiles/pipeline_calls_*.md), hence a class and not a
+    generator, the upload written here and not forwarded to the ring, and no stream context where there is nothing to switch: once
+    ``dev`` is the current device its current stream IS the caller's stream when no handle is given."""
+    __slots__ = ('ring', 'dev', 'stream', 'main', 'stage', 'on_device', 'on_stream')
+
+    def __init__(self, ring, dev, stream=None):
+        self.ring, self.dev, self.stream, self.stage = ring, dev, stream, None
+
+    def __enter__(self):
+        self.on_device = torch.cuda.device(self.dev)
+        self.on_device.__enter__()
+        try:
+            if self.stream is None:
+                self.main, self.on_stream = torch.cuda.current_stream(self.dev), None
+            else:
+                self.main = torch.cuda.ExternalStream(self.stream, device=self.dev)
+                self.on_stream = torch.cuda.stream(self.main)
+                self.on_stream.__enter__()
+        except BaseException:
+            self.on_device.__exit__(*sys.exc_info())
+            raise
+        return self
+
+    def upload(self, pixels, operands, pixels_staged=None):
+        """Everything the call brings from the host, in ONE stage and one copy.  pixels: flat uint8 host arrays; operands: what the kernels
+        read, each a device tensor, a host array (staged behind the pixels, in order) or None.  A device operand is read at its own
+        address, a host operand at its staged one: -> (every pixel part in the device twin, as a view of it; the address of every operand,
+        None for None).  When nothing comes from the host no stage is taken.  ``pixels_staged(addresses)`` runs once the pixels are in the
+        pinned buffer and before the host operands are copied there, so it may still write into them (a frame table takes its frames'
+        addresses, run_many its descriptors) and let go of the pixels' sources."""
         tables = [t.view(np.uint8).reshape(-1) for t in operands if isinstance(t, np.ndarray)]
         if not pixels and not tables:
-            return None, [], [None if t is None else t.data_ptr() for t in operands]
+            return [], [None if t is None else t.data_ptr() for t in operands]
+        assert self.stage is None, 'one upload per call: the scope marks one stage'
         offs, total = _layout([b.size for b in pixels] + [b.size for b in tables])
-        st = self.take(total, dev, main)
+        st = self.stage = self.ring.take(total, self.dev, self.main)
         at = [st.base + o for o in offs]
         for b, o in zip(pixels, offs):
             st.host[o:o + b.size] = b
@@ -91,4 +125,15 @@ class _StagingRing:
             st.host[o:o + b.size] = b
         st.send(total)
         staged = iter(at[len(pixels):])
-        return st, [st.dev[o:o + b.size] for b, o in zip(pixels, offs)], [None if t is None else t.data_ptr() if isinstance(t, torch.Tensor) else next(staged) for t in operands]
+        return [st.dev[o:o + b.size] for b, o in zip(pixels, offs)], [None if t is None else t.data_ptr() if isinstance(t, torch.Tensor) else next(staged) for t in operands]
+
+    def __exit__(self, kind, value, trace):
+        try:
+            if kind is None and self.stage is not None:
+                self.stage.read_by(self.main)
+        finally:
+            try:
+                if self.on_stream is not None:
+                    self.on_stream.__exit__(kind, value, trace)
+            finally:
+                self.on_device.__exit__(kind, value, trace)

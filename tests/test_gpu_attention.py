@@ -56,6 +56,21 @@ def test_tile_edges_and_the_skip_branch(pipe, n, pictures, m, shuffle):
     AC.same_tables(on_device(pipe, AC.args(case)), want, case['name'])
 
 
+def test_rows_and_regions_are_each_decided_as_a_group(pipe):
+    """Rows on the device beside regions on the host, and the reverse: the host group goes up through one stage, the device group is read
+    where it is.  One table of a group on the device moves the rest of that group with torch, and no stage is taken."""
+    a = AC.args(next(c for c in AC.hand_cases() if c['name'] == 'a region of every picture, of one picture, of a camera'))
+    want = AT.gaze_targets_host(**a)
+    rows, regions = ('boxes', 'gaze', 'image_of'), ('regions', 'region_image')
+    for there, stages in ((rows, 1), (regions, 1), (('gaze', 'regions'), 0)):
+        b = {k: dev(v) if k in there else v for k, v in a.items()}
+        before = pipe._ring.i
+        got = pipe.gaze_targets(b.pop('boxes'), b.pop('gaze'), b.pop('image_of'), device=DEV, **b)
+        assert pipe._ring.i == (before + stages) % pipe.STAGES
+        torch.cuda.synchronize()
+        AC.same_tables(tuple(g.cpu().numpy() for g in got), want, f'{there} on the device')
+
+
 def test_strided_gaze_tables(pipe):
     case = AC.random_case(11, 70, 2, 4)
     a = AC.args(case)

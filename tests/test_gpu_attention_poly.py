@@ -88,6 +88,23 @@ def test_rectangles_only_give_the_bits_of_mcg_gaze_targets(pipe, name, old, new)
     AC.same_tables(on_device(pipe, new), on_device(pipe, old, tables=False), name)
 
 
+def test_rows_and_regions_are_each_decided_as_a_group(pipe):
+    """Rows on the device beside vertex tables on the host, and the reverse: the host group goes up through one stage; one table of a group
+    on the device (here ``start`` alone) moves the rest of that group with torch."""
+    a = PC.tables(next(c for c in PC.hand_cases() if c['name'] == 'regions of every picture, of one picture, of a camera'))
+    want = AT.gaze_targets_host(**a)
+    xy, start = a['regions']
+    rows = {k: dev(a[k]) for k in ('boxes', 'gaze', 'image_of')}
+    for what, b, stages in (('rows on the device', dict(a, **rows), 1),
+                            ('regions on the device', dict(a, regions=AT.PolyRegions(dev(xy), dev(start)), region_image=dev(a['region_image'])), 1),
+                            ('boxes and start on the device', dict(a, boxes=rows['boxes'], regions=AT.PolyRegions(xy, dev(start))), 0)):
+        before = pipe._ring.i
+        got = pipe.gaze_targets(b.pop('boxes'), b.pop('gaze'), b.pop('image_of'), device=DEV, **b)
+        assert pipe._ring.i == (before + stages) % pipe.STAGES
+        torch.cuda.synchronize()
+        AC.same_tables(tuple(g.cpu().numpy() for g in got), want, what)
+
+
 def test_strided_gaze_tables(pipe):
     case = PC.random_case(11, 70, 2, 9)
     a = PC.tables(case)

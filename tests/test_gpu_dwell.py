@@ -153,6 +153,21 @@ def test_the_state_carried_over_three_calls_and_tag_none(pipe):
     DC.same(on_device(pipe, zero), AT.gaze_dwell_host(**dict(a, tag=None)), 'zeros against tag None')
 
 
+def test_a_host_table_next_to_device_tables_is_moved_with_torch(pipe):
+    """The five tables are decided as a group: with one of them on the device none goes through the staging ring."""
+    a = DC.args(next(c for c in DC.hand_cases() if c['name'] == 'an owner change, a tag change and person <= 0'))
+    assert a['tag'].any()                                         # the tag decides two of the three events
+    want = AT.gaze_dwell_host(**a)
+    for host in (('tag',), ('person', 'kind', 'ident', 'mutual')):
+        b = {k: v if k in host or k not in TABLES + ('region_frames',) else dev(v) for k, v in a.items()}
+        assert all(isinstance(b[k], np.ndarray) for k in host) and sum(isinstance(b[k], torch.Tensor) for k in TABLES) == 5 - len(host)
+        before = pipe._ring.i
+        got = pipe.gaze_dwell(b.pop('person'), b.pop('kind'), b.pop('ident'), b.pop('mutual'), device=DEV, **b)
+        assert pipe._ring.i == before
+        torch.cuda.synchronize()
+        DC.same(tuple(g.cpu().numpy() for g in got), want, f'{host} on the host')
+
+
 def test_option_and_shape_checks_raise_before_any_launch(pipe):
     a = DC.args(DC.hand_cases()[0])
     t = [dev(a[k]) for k in ('person', 'kind', 'ident', 'mutual')]

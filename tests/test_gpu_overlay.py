@@ -78,6 +78,34 @@ def test_the_scene_on_frames_with_their_own_pitches_and_junk_in_the_padding(pipe
     assert all(torch.equal(b, c) for bs, cs in zip(bufs, keep) for b, c in zip(bs, cs))
 
 
+@pytest.mark.parametrize('host_table,stages', [('gaze', 1), ('hit', 0), ('start', 0), ('region_image', 0)])
+@pytest.mark.parametrize('fmt,matrix', FORMATS[:2], ids=IDS[:2])
+def test_one_table_of_each_group_on_the_host_and_the_rest_on_the_device(fmt, matrix, host_table, stages):
+    """Every operand must be read where it really is.  A host row table beside device ones goes up through the staging ring (one stage); a
+    host table among gaze_targets' results or among the region tables, which are each decided as a group, is moved with torch (no stage:
+    the frame table of device frames drawn in place does not go through the ring)."""
+    pipe = P.DevicePipeline(chain(32))
+    args = O.scene()
+    want = AR.draw_attention_host(O.frames(fmt), pixel_format=fmt, matrix=matrix, **args)
+    tables = on_device(args)
+    if host_table == 'start':
+        xy, start = AT.region_polygons(args['regions'])
+        tables['regions'] = AT.PolyRegions(tables['regions'].xy, start)
+    else:
+        tables[host_table] = np.asarray(args[host_table])
+    views, bufs = device_frames(fmt, 255)
+    before = pipe._ring.i
+    got = pipe.draw_attention(views, pixel_format=fmt, matrix=matrix, device=DEV, **tables)
+    assert pipe._ring.i == (before + stages) % pipe.STAGES
+    torch.cuda.synchronize()
+    assert all(g is v for g, v in zip(got[0], views))
+    for g, w, name in zip(got[1:], want[1:], ('flags', 'region_flags', 'region_active')):
+        assert g.dtype == torch.int32 and np.array_equal(g.cpu().numpy(), w), (host_table, name)
+    for k, (bs, es) in enumerate(zip(bufs, expected_buffers(fmt, want[0], 255))):
+        for b, e in zip(bs, es):
+            assert np.array_equal(b.cpu().numpy(), e), (host_table, k)
+
+
 @pytest.mark.parametrize('n,m', [(63, 65), (64, 64), (65, 63), (0, 64), (64, 0), (1, 1)])
 @pytest.mark.parametrize('fmt,matrix', FORMATS[:2], ids=IDS[:2])
 def test_the_ballot_slice_edge(pipe, fmt, matrix, n, m):
