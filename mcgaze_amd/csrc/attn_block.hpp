@@ -9,14 +9,14 @@
 //   s_a / s_b   token rows, bf16, 16-byte K-chunks XOR-swizzled by the row (A operand; ping-pong between the passes)
 //   s_qkv       [32][768] bf16 row-major (q | k | v), aliased by the f32 slab of the out-projection
 //   s_att       attention output rows (A operand)
-// Linears follow chain.hpp: wave w owns 64 output columns (two 32x32 tiles), K = 256 in 16 MFMA steps, B fragments straight from
-// a fragment-major copy of the weights (1 KiB contiguous per wave load), the next sub-step's fragments in flight while this one's
-// results are written.  Rounding points and orders are those of the launches it replaces (qkv, attention output and the
+// Linears are the row-block linear of rowblock.hpp (Ops16<T>, as in chain.hpp): wave w owns 64 output columns (two 32x32 tiles), K = 256
+// in 16 MFMA steps, B fragments straight from a fragment-major copy of the weights, the next sub-step's fragments in flight while this
+// one's results are written.  Rounding points and orders are those of the launches it replaces (qkv, attention output and the
 // projection's output are rounded to bf16 where the unfused path stores them; K order of the igemm kernel; the attention core
-// is the same device function; LayerNorm with ln_kernel's lane -> column ownership), so the fused block is BIT-IDENTICAL to the
-// unfused sequence (tests/test_gpu_kernels.py::test_attn_block_matches_unfused_bitwise).
+// is the same device function; LayerNorm is ln256_row, with ln_kernel's lane -> column ownership), so the fused block reproduces the
+// unfused sequence (tests/test_gpu_kernels.py::test_mlp_chain_matches_unfused_bitwise).
 #pragma once
-#include "common.hpp"
+#include "rowblock.hpp"
 
 // One (query row, head) of the 8-head / 32-dim attention: scores over the L keys of the row's group, softmax, weighted sum of the
 // values.  One THREAD does the whole thing -- 32-term dot products as sequential fma chains, maximum first, then exp / sum /
@@ -114,7 +114,8 @@ struct AttnBlockParams {
 
 template <typename T>   // bf16_t or f16_t
 __global__ __launch_bounds__(256, 1) void attn_block_kernel(const AttnBlockParams p) {
-  constexpr int D = 256, ROWS = 32, ROWB = D * 2, QKV_LD = 3 * D;
+  typedef Ops16<T> Ops;
+  constexpr int D = RB_D, ROWS = RB_ROWS, ROWB = Ops::ROWB, QKV_LD = 3 * D;
   __shared__ __attribute__((aligned(16))) char s_a[ROWS * ROWB];
   __shared__ __attribute__((aligned(16))) char s_b[ROWS * ROWB];
   __shared__ __attribute__((aligned(16))) char s_att[ROWS * ROWB];
@@ -130,36 +131,10 @@ __global__ __launch_bounds__(256, 1) void attn_block_kernel(const AttnBlockParam
     T_b = cs.len; m0 = (size_t)cs.first * 3; bad = cs.bad;
   }
   const int rows = 3 * T_b;                                   // <= 32 (checked by the launcher; clip_span clamps)
-  auto swz = [](int row, int chunk) { return row * ROWB + ((chunk ^ (row & 31)) << 4); };
-  for (int idx = tid; idx < ROWS * 32; idx += 256) {          // token rows -> LDS (padding rows are zero; never stored)
-    const int r = idx >> 5, c = idx & 31;
-    uint4 v = make_uint4(0, 0, 0, 0);
-    if (r < rows) v = *(const uint4*)((const char*)p.x + (m0 + r) * ROWB + c * 16);
-    *(uint4*)(s_a + swz(r, c)) = v;
-  }
-  const int arow = lane & 31, half = lane >> 5;
-  uint4 bfr[2][16];
-  auto load_b = [&](const void* W, int tile0) {               // fragments of column tiles tile0, tile0 + 1: 32 x 1 KiB wave loads
-    const char* wb = (const char*)W + ((size_t)tile0 * 16 * 64 + lane) * 16;
-#pragma unroll
-    for (int ks = 0; ks < 16; ++ks) {
-      bfr[0][ks] = *(const uint4*)(wb + ks * 1024);
-      bfr[1][ks] = *(const uint4*)(wb + 16 * 1024 + ks * 1024);
-    }
-  };
-  auto mma2 = [&](const char* A, f32x16 (&acc)[2]) {
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
-#pragma unroll
-    for (int ks = 0; ks < 16; ++ks) {
-      const uint4 a = *(const uint4*)(A + swz(arow, 2 * ks + half));
-      Mma<T>::run(acc[0], a, bfr[0][ks]);
-      Mma<T>::run(acc[1], a, bfr[1][ks]);
-    }
-  };
-  load_b(p.w_in, wave * 2);
+  Ops::stage_rows(s_a, (const char*)p.x + m0 * ROWB, rows, tid);   // token rows -> LDS (padding rows are zero; never stored)
+  const int arow = lane & 31;
+  typename Ops::Bfr bfr;
+  Ops::load_b(bfr, p.w_in, wave * 2, lane);
   __syncthreads();
   char* xin = s_a;
   char* xout = s_b;
@@ -168,9 +143,9 @@ __global__ __launch_bounds__(256, 1) void attn_block_kernel(const AttnBlockParam
 #pragma unroll 1
     for (int u = 0; u < 3; ++u) {
       f32x16 acc[2];
-      mma2(xin, acc);
-      if (u < 2) load_b(p.w_in, (u + 1) * 8 + wave * 2);
-      else load_b(p.w_out, wave * 2);
+      Ops::mma2(xin, bfr, acc, lane);
+      if (u < 2) Ops::load_b(bfr, p.w_in, (u + 1) * 8 + wave * 2, lane);
+      else Ops::load_b(bfr, p.w_out, wave * 2, lane);
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
         const int col = u * D + wave * 64 + j * 32 + arow;
@@ -191,25 +166,19 @@ __global__ __launch_bounds__(256, 1) void attn_block_kernel(const AttnBlockParam
                            [&](int j) { return (const T*)(s_qkv + (kbase + j * kstep) * QKV_LD + D + h * 32); },
                            [&](int j) { return (const T*)(s_qkv + (kbase + j * kstep) * QKV_LD + 2 * D + h * 32); }, L, p.scale, o);
 #pragma unroll
-        for (int c = 0; c < 4; ++c) *(uint4*)(s_att + swz(i, h * 4 + c)) = *(const uint4*)(o + c * 8);
+        for (int c = 0; c < 4; ++c) *(uint4*)(s_att + Ops::swz(i, h * 4 + c)) = *(const uint4*)(o + c * 8);
       } else {
 #pragma unroll
-        for (int c = 0; c < 4; ++c) *(uint4*)(s_att + swz(i, h * 4 + c)) = make_uint4(0, 0, 0, 0);
+        for (int c = 0; c < 4; ++c) *(uint4*)(s_att + Ops::swz(i, h * 4 + c)) = make_uint4(0, 0, 0, 0);
       }
     }
     __syncthreads();   // s_att complete, s_qkv consumed (s_t aliases it)
     // ---- out-projection + bias (f32 slab), then + residual -> bf16 -> LayerNorm (chain.hpp's step)
     {
       f32x16 acc[2];
-      mma2(s_att, acc);
-      if (pass == 0) load_b(p.w_in, wave * 2);
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        const int col = wave * 64 + j * 32 + arow;
-        const float bb = p.b_out[col];
-#pragma unroll
-        for (int r = 0; r < 16; ++r) s_t[mfma32_row(r, lane) * D + col] = acc[j][r] + bb;
-      }
+      Ops::mma2(s_att, bfr, acc, lane);
+      if (pass == 0) Ops::load_b(bfr, p.w_in, wave * 2, lane);
+      rb_slab(s_t, acc, p.b_out, wave, lane);
     }
     __syncthreads();
     const int c0 = lane * 4;
@@ -220,26 +189,16 @@ __global__ __launch_bounds__(256, 1) void attn_block_kernel(const AttnBlockParam
       const float4 t4 = *(const float4*)(s_t + r * D + c0);
       float v[4] = {t4.x, t4.y, t4.z, t4.w};
       {  // residual = this pass's input row (the mmcv wrapper adds the identity, transformer.py MultiheadAttention)
-        const uint2 rr = *(const uint2*)(xin + swz(r, c0 >> 3) + (c0 & 7) * 2);
-        v[0] += H16<T>::lo(rr.x); v[1] += H16<T>::hi(rr.x);
-        v[2] += H16<T>::lo(rr.y); v[3] += H16<T>::hi(rr.y);
-      }
-      {  // the unfused path stores the projection's output as bf16 before the LayerNorm kernel reads it
-        const uint32_t lo = H16<T>::pack2(v[0], v[1]), hi = H16<T>::pack2(v[2], v[3]);
-        v[0] = H16<T>::lo(lo); v[1] = H16<T>::hi(lo);
-        v[2] = H16<T>::lo(hi); v[3] = H16<T>::hi(hi);
-      }
-      const float mean = wave_sum(v[0] + v[1] + v[2] + v[3]) * (1.0f / D);
-      float q = 0.f;
+        float rr[4];
+        Ops::unquad(*(const uint2*)(xin + Ops::quad_off(r, c0)), rr);
 #pragma unroll
-      for (int e = 0; e < 4; ++e) { const float d = v[e] - mean; q += d * d; }
-      const float rstd = 1.0f / sqrtf(wave_sum(q) * (1.0f / D) + 1e-5f);
-      const float gg[4] = {g4.x, g4.y, g4.z, g4.w}, bbv[4] = {b4.x, b4.y, b4.z, b4.w};
-#pragma unroll
-      for (int e = 0; e < 4; ++e) v[e] = (v[e] - mean) * rstd * gg[e] + bbv[e];
-      uint2 o = make_uint2(H16<T>::pack2(v[0], v[1]), H16<T>::pack2(v[2], v[3]));
+        for (int e = 0; e < 4; ++e) v[e] += rr[e];
+      }
+      Ops::round_stored(v);   // the unfused path stores the projection's output as bf16 before the LayerNorm kernel reads it
+      ln256_row<Ops::kLnSq>(v, g4, b4, false);
+      uint2 o = Ops::quad(v);
       if (r >= rows) o = make_uint2(0, 0);   // padding rows stay zero
-      *(uint2*)(xout + swz(r, c0 >> 3) + (c0 & 7) * 2) = o;
+      Ops::park(xout, r, c0, o);
       if (bad) o = make_uint2(0xffffffffu, 0xffffffffu);   // a clip the table guard clamped: NaN (bf16 and fp16 alike)
       if (pass == 1 && r < rows) *(uint2*)((char*)p.y + (m0 + r) * ROWB + c0 * 2) = o;
     }
@@ -249,7 +208,3 @@ __global__ __launch_bounds__(256, 1) void attn_block_kernel(const AttnBlockParam
 }
 
 static inline bool attn_block_applicable(int T) { return T >= 1 && 3 * T <= 32; }   // T: the longest clip of the call
-static inline int launch_attn_block(hipStream_t s, const AttnBlockParams& p, mcg_dtype dt) {
-  dispatch_elem16(dt, [&](auto e) { hipLaunchKernelGGL(attn_block_kernel<decltype(e)>, dim3(p.num_clips), dim3(256), 0, s, p); });
-  return hipGetLastError() == hipSuccess ? 0 : 1;
-}

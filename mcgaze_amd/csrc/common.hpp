@@ -166,14 +166,17 @@ template <int CTRL, int ROW_MASK = 0xF>
 __device__ __forceinline__ float dpp_mov(float v, float fill) {
   return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, fill), __builtin_bit_cast(int, v), CTRL, ROW_MASK, 0xF, false));
 }
-__device__ __forceinline__ float wave_sum(float v) {
-  v += dpp_mov<0xB1>(v, 0.f);        // quad_perm [1,0,3,2]
+// (wave_sum_rest: everything after the first step, for the one caller that states that step itself -- rowblock.hpp: ln64_relu)
+__device__ __forceinline__ float wave_sum_rest(float v) {
   v += dpp_mov<0x4E>(v, 0.f);        // quad_perm [2,3,0,1]
   v += dpp_mov<0x141>(v, 0.f);       // row_half_mirror
   v += dpp_mov<0x140>(v, 0.f);       // row_mirror: every lane holds its row's sum
   v += dpp_mov<0x142, 0xA>(v, 0.f);  // row_bcast15 into rows 1, 3
   v += dpp_mov<0x143, 0xC>(v, 0.f);  // row_bcast31 into rows 2, 3
   return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
+}
+__device__ __forceinline__ float wave_sum(float v) {
+  return wave_sum_rest(v + dpp_mov<0xB1>(v, 0.f));   // quad_perm [1,0,3,2]
 }
 __device__ __forceinline__ float wave_max(float v) {
   v = fmaxf(v, dpp_mov<0xB1>(v, v));

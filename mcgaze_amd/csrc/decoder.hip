@@ -6,7 +6,6 @@
 #include "attn_block.hpp"
 #include "pw_single.hpp"
 #include "igemm_dma.hpp"
-#include "chain_x3.hpp"
 #include "attn_block_x3.hpp"
 #include "pw_single_x3.hpp"
 
@@ -91,18 +90,18 @@ __global__ __launch_bounds__(256) void ln_kernel(const LnParams p) {
     v[e] = t;
   }
   const float invD = 1.0f / (float)p.D;
-  auto norm = [&](const float* g, const float* b, int relu) {
+  auto norm = [&](const float* g, const float* b, int relu) {   // rowblock.hpp's pinned expressions on this lane's `per` values (LN_SQ_FMA)
     float s = 0.f;
 #pragma unroll
     for (int e = 0; e < 4; ++e) if (e < per) s += v[e];
-    const float mean = wave_sum(s) * invD;
-    float q = 0.f;
+    const float sum = wave_sum(s);
+    float d[4], q = 0.f;
 #pragma unroll
-    for (int e = 0; e < 4; ++e) if (e < per) { const float d = v[e] - mean; q += d * d; }
-    const float rstd = 1.0f / sqrtf(wave_sum(q) * invD + 1e-5f);
+    for (int e = 0; e < 4; ++e) if (e < per) { d[e] = ln_dev(v[e], sum, invD); q = e ? __builtin_fmaf(d[e], d[e], q) : d[0] * d[0]; }
+    const float rstd = ln_rstd(wave_sum(q), invD);
 #pragma unroll
     for (int e = 0; e < 4; ++e) if (e < per) {
-      float t = (v[e] - mean) * rstd * g[grp * p.param_stride + c0 + e] + b[grp * p.param_stride + c0 + e];
+      const float t = ln_affine(d[e], rstd, g[grp * p.param_stride + c0 + e], b[grp * p.param_stride + c0 + e]);
       v[e] = relu ? fmaxf(t, 0.f) : t;
     }
   };
@@ -146,22 +145,58 @@ static LnParams ln_splitk(const float* partial, int slabs, const float* bias, co
 // The 49 positions are padded to 64 rows (2 MFMA row tiles).  MFMA operand fragments for F and
 // the generated weights are read straight from global/L2 (each is used by one token only);
 // F1 goes through LDS (f32 for the LayerNorm, then dtype, chunk-swizzled, as the next A operand).
+// What the two kernels below share: the geometry and LDS budget, the D1 / D2 tile stores, the 64-wide LayerNorm (rowblock.hpp: ln64_relu)
+// and the tail.  The contraction loops and the layout of A2 (F1 as the next A operand) are each kernel's own.
+namespace dyn {
+constexpr int P = 49, DI = 256, DF = 64;
+constexpr int D1_LD = DF + 4, D2_LD = DI + 4;
+constexpr int D1_BYTES = 64 * D1_LD * 4;
+constexpr int D2_BYTES = P * D2_LD * 4;                    // D2 aliases D1 and A2 (barrier in between)
+constexpr int lds_bytes(int a2_bytes) { return D2_BYTES > D1_BYTES + a2_bytes ? D2_BYTES : D1_BYTES + a2_bytes; }
+// stage 1: the wave's 32x32 tile (tm, tn) of D1[64][64]
+__device__ __forceinline__ void store_d1(float* D1, const f32x16& acc, int tm, int tn, int lane) {
+#pragma unroll
+  for (int i = 0; i < 16; ++i) D1[(tm * 32 + mfma32_row(i, lane)) * D1_LD + tn * 32 + (lane & 31)] = acc[i];
+}
+// stage 2: the wave's 2x2 tiles, columns [wave*64, +64) of D2[49][256] (the padding rows are not stored)
+__device__ __forceinline__ void store_d2(float* D2, const f32x16 (&acc)[2][2], int wave, int lane) {
+#pragma unroll
+  for (int a = 0; a < 2; ++a)
+#pragma unroll
+    for (int b = 0; b < 2; ++b)
+#pragma unroll
+      for (int i = 0; i < 16; ++i) {
+        const int row = a * 32 + mfma32_row(i, lane);
+        if (row < P) D2[row * D2_LD + wave * 64 + b * 32 + (lane & 31)] = acc[a][b][i];
+      }
+}
+// LN over 256 channels + ReLU, one wave per position, lane owns 4 consecutive channels -> out_tok[49][256].  LN_SQ_FMA_FROM_D1: these tails
+// sum the squares from d1 on, not ln_kernel's order (rowblock.hpp); nothing compares them with ln_kernel bit for bit, and their bits stay.
+template <typename T>
+__device__ __forceinline__ void tail(const float* D2, const float* __restrict__ g_out, const float* __restrict__ b_out, T* __restrict__ out_tok,
+                                     int wave, int lane) {
+  for (int row = wave; row < P; row += 4) {
+    const float4 t = *(const float4*)(D2 + row * D2_LD + lane * 4);
+    float v[4] = {t.x, t.y, t.z, t.w};
+    ln256_row<LN_SQ_FMA_FROM_D1>(v, *(const float4*)(g_out + lane * 4), *(const float4*)(b_out + lane * 4), true);
+    T* dst = out_tok + row * DI + lane * 4;
+    if constexpr (sizeof(T) == 4) *(float4*)dst = make_float4(v[0], v[1], v[2], v[3]);
+    else *(uint2*)dst = make_uint2(H16<T>::pack2(v[0], v[1]), H16<T>::pack2(v[2], v[3]));
+  }
+}
+}  // namespace dyn
+
 template <typename T>
 __global__ __launch_bounds__(256) void dynconv_kernel(const T* __restrict__ roi, const T* __restrict__ params,
                                                       const float* __restrict__ g_in, const float* __restrict__ b_in,
                                                       const float* __restrict__ g_out, const float* __restrict__ b_out,
                                                       T* __restrict__ out) {
+  using namespace dyn;
   constexpr int EPC = Elem<T>::kPerChunk;
-  constexpr int P = 49, DI = 256, DF = 64;
-  constexpr int D1_LD = DF + 4, D2_LD = DI + 4;
   constexpr int A2_ROWB = DF * (int)sizeof(T);            // bytes per F1 row as next A operand
   constexpr int A2_CPR = A2_ROWB / 16;
   constexpr int A2_RPB = (256 / A2_ROWB) > 0 ? (256 / A2_ROWB) : 1;
-  constexpr int A2_BYTES = 64 * A2_ROWB;
-  constexpr int D1_BYTES = 64 * D1_LD * 4;
-  constexpr int D2_BYTES = P * D2_LD * 4;                  // D2 aliases D1 and A2 (barrier in between)
-  constexpr int LDS_BYTES = D2_BYTES > D1_BYTES + A2_BYTES ? D2_BYTES : D1_BYTES + A2_BYTES;
-  __shared__ __attribute__((aligned(16))) char smem[LDS_BYTES];
+  __shared__ __attribute__((aligned(16))) char smem[lds_bytes(64 * A2_ROWB)];
   float* D1 = (float*)smem;
   float* D2 = (float*)smem;
   char* A2 = smem + D1_BYTES;
@@ -197,8 +232,7 @@ __global__ __launch_bounds__(256) void dynconv_kernel(const T* __restrict__ roi,
 #pragma unroll
       for (int j = 0; j < GRP; ++j) Mma<T>::run(acc, a[j], b[j]);
     }
-#pragma unroll
-    for (int i = 0; i < 16; ++i) D1[(tm * 32 + mfma32_row(i, lane)) * D1_LD + tn * 32 + (lane & 31)] = acc[i];
+    store_d1(D1, acc, tm, tn, lane);
   }
   // stage 2's weight fragments (wave -> columns [wave*64, +64) of Wout^T, K = 64): issued now, consumed after the LayerNorm below
   constexpr int PAIRS2 = DF / (2 * EPC);
@@ -210,11 +244,7 @@ __global__ __launch_bounds__(256) void dynconv_kernel(const T* __restrict__ roi,
   __syncthreads();
   // ---- LN over 64 features + ReLU, one wave per row, lane = feature; write F1 as dtype A operand
   for (int row = wave; row < 64; row += 4) {
-    float v = D1[row * D1_LD + lane];
-    const float mean = wave_sum(v) * (1.0f / DF);
-    const float d = v - mean;
-    const float rstd = 1.0f / sqrtf(wave_sum(d * d) * (1.0f / DF) + 1e-5f);
-    v = fmaxf(d * rstd * g_in[lane] + b_in[lane], 0.f);
+    const float v = ln64_relu(D1[row * D1_LD + lane], g_in[lane], b_in[lane]);
     const int chunk = lane / EPC, within = lane % EPC;
     T* dst = (T*)(A2 + row * A2_ROWB + ((chunk ^ ((row / A2_RPB) % A2_CPR)) << 4)) + within;
     Elem<T>::st(dst, v);
@@ -247,30 +277,10 @@ __global__ __launch_bounds__(256) void dynconv_kernel(const T* __restrict__ roi,
         for (int b = 0; b < 2; ++b) Mma<T>::run(acc[a][b], af[a], bf[b]);
     }
     __syncthreads();  // every wave is done reading A2 before D2 (which aliases it) is written
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-      for (int b = 0; b < 2; ++b)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-          const int row = a * 32 + mfma32_row(i, lane);
-          if (row < P) D2[row * D2_LD + wave * 64 + b * 32 + (lane & 31)] = acc[a][b][i];
-        }
+    store_d2(D2, acc, wave, lane);
   }
   __syncthreads();
-  // ---- LN over 256 channels + ReLU, one wave per position, lane owns 4 consecutive channels
-  for (int row = wave; row < P; row += 4) {
-    const float4 t = *(const float4*)(D2 + row * D2_LD + lane * 4);
-    float v[4] = {t.x, t.y, t.z, t.w};
-    const float mean = wave_sum(v[0] + v[1] + v[2] + v[3]) * (1.0f / DI);
-    float q = 0.f;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { v[e] -= mean; q += v[e] * v[e]; }
-    const float rstd = 1.0f / sqrtf(wave_sum(q) * (1.0f / DI) + 1e-5f);
-    T* dst = out + ((long long)r * P + row) * DI + lane * 4;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) Elem<T>::st(dst + e, fmaxf(v[e] * rstd * g_out[lane * 4 + e] + b_out[lane * 4 + e], 0.f));
-  }
+  tail(D2, g_out, b_out, out + (long long)r * P * DI, wave, lane);
 }
 
 // The same in the f16x3 arithmetic (MCG_F16X3 engine; round 5): f32 storage, both operands of both contractions split into fp16 high / low
@@ -283,14 +293,10 @@ __global__ __launch_bounds__(256) void dynconv_x3_kernel(const float* __restrict
                                                          const float* __restrict__ g_in, const float* __restrict__ b_in,
                                                          const float* __restrict__ g_out, const float* __restrict__ b_out,
                                                          float* __restrict__ out) {
-  constexpr int P = 49, DI = 256, DF = 64;
-  constexpr int D1_LD = DF + 4, D2_LD = DI + 4;
+  using namespace dyn;
   constexpr int A2_ROWB = DF * 2;                          // bytes per F1 row of one fp16 plane
   constexpr int A2_PLANE = 64 * A2_ROWB;                   // 8 KiB
-  constexpr int D1_BYTES = 64 * D1_LD * 4;
-  constexpr int D2_BYTES = P * D2_LD * 4;                  // D2 aliases D1 and the planes (barrier in between)
-  constexpr int LDS_BYTES = D2_BYTES > D1_BYTES + 2 * A2_PLANE ? D2_BYTES : D1_BYTES + 2 * A2_PLANE;
-  __shared__ __attribute__((aligned(16))) char smem[LDS_BYTES];
+  __shared__ __attribute__((aligned(16))) char smem[lds_bytes(2 * A2_PLANE)];
   float* D1 = (float*)smem;
   float* D2 = (float*)smem;
   char* A2h = smem + D1_BYTES;
@@ -332,8 +338,7 @@ __global__ __launch_bounds__(256) void dynconv_x3_kernel(const float* __restrict
         acc = x3_mfma(ah, bh, acc);
       }
     }
-#pragma unroll
-    for (int i = 0; i < 16; ++i) D1[(tm * 32 + mfma32_row(i, lane)) * D1_LD + tn * 32 + (lane & 31)] = acc[i];
+    store_d1(D1, acc, tm, tn, lane);
   }
   // stage 2's weight fragments (wave -> columns [wave*64, +64) of Wout^T, K = 64 = 4 steps): issued now, consumed after the LayerNorm
   uint4 bf2[4][2][2];
@@ -349,11 +354,7 @@ __global__ __launch_bounds__(256) void dynconv_x3_kernel(const float* __restrict
   // ---- LN over 64 features + ReLU, one wave per row, lane = feature; F1 split once into the fp16 planes (16-byte chunks XOR-swizzled
   // by row pair: a fragment read's 16 lanes hit 16 distinct bank groups)
   for (int row = wave; row < 64; row += 4) {
-    float v = D1[row * D1_LD + lane];
-    const float mean = wave_sum(v) * (1.0f / DF);
-    const float d = v - mean;
-    const float rstd = 1.0f / sqrtf(wave_sum(d * d) * (1.0f / DF) + 1e-5f);
-    v = fmaxf(d * rstd * g_in[lane] + b_in[lane], 0.f);
+    const float v = ln64_relu(D1[row * D1_LD + lane], g_in[lane], b_in[lane]);
     uint32_t hh, ll;
     split_pair(v, 0.f, hh, ll);                            // (the packed pair's second half is not stored)
     const int chunk = lane >> 3, within = lane & 7;
@@ -398,32 +399,10 @@ __global__ __launch_bounds__(256) void dynconv_x3_kernel(const float* __restrict
         for (int b = 0; b < 2; ++b) acc[a][b] = x3_mfma(ah[a], bh[b], acc[a][b]);
     }
     __syncthreads();  // every wave is done reading the planes before D2 (which aliases them) is written
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-      for (int b = 0; b < 2; ++b)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-          const int row = a * 32 + mfma32_row(i, lane);
-          if (row < P) D2[row * D2_LD + wave * 64 + b * 32 + (lane & 31)] = acc[a][b][i];
-        }
+    store_d2(D2, acc, wave, lane);
   }
   __syncthreads();
-  // ---- LN over 256 channels + ReLU, one wave per position, lane owns 4 consecutive channels
-  for (int row = wave; row < P; row += 4) {
-    const float4 t = *(const float4*)(D2 + row * D2_LD + lane * 4);
-    float v[4] = {t.x, t.y, t.z, t.w};
-    const float mean = wave_sum(v[0] + v[1] + v[2] + v[3]) * (1.0f / DI);
-    float q = 0.f;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { v[e] -= mean; q += v[e] * v[e]; }
-    const float rstd = 1.0f / sqrtf(wave_sum(q) * (1.0f / DI) + 1e-5f);
-    const float4 g = *(const float4*)(g_out + lane * 4), bb = *(const float4*)(b_out + lane * 4);
-    float4 o;
-    o.x = fmaxf(v[0] * rstd * g.x + bb.x, 0.f); o.y = fmaxf(v[1] * rstd * g.y + bb.y, 0.f);
-    o.z = fmaxf(v[2] * rstd * g.z + bb.z, 0.f); o.w = fmaxf(v[3] * rstd * g.w + bb.w, 0.f);
-    *(float4*)(out + ((long long)r * P + row) * DI + lane * 4) = o;
-  }
+  tail(D2, g_out, b_out, out + (long long)r * P * DI, wave, lane);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -555,6 +534,30 @@ __global__ void init_queries_kernel(const float* __restrict__ init_boxes, const 
 // ================================================================================================
 // Host orchestration of one decoder stage and of the gaze head.
 static inline size_t al256(size_t b) { return (b + 255) / 256 * 256; }
+static inline size_t elem_bytes(mcg_dtype dt) { return MCG_ELEM_BYTES(dt); }   // activation storage (MCG_F16X3: f32)
+
+// `dynamic_layer` (256 -> 32768 on M token rows, no residual) through the streaming kernels: pw_single.hpp's launch_pw_dyn (bf16 / fp16) or
+// pw_single_x3.hpp's launch_pw_dyn_x3 (f16x3, whose weights carry wscale)
+static PwSingleParams pw_dyn_params(const void* a, const void* wf, const float* bias, void* y, int M, float wscale) {
+  PwSingleParams pp;
+  memset(&pp, 0, sizeof(pp));
+  pp.a = a; pp.wf = wf; pp.bias = bias; pp.y = y; pp.M = M; pp.Ho = 1; pp.Wo = 1; pp.wscale = wscale;
+  return pp;
+}
+static int launch_dyn_layer(hipStream_t s, const PwSingleParams& pp, mcg_dtype dt, int grid_cap) {
+  const bool x3 = dt == MCG_F16X3;
+  int failed;
+  if (x3) failed = launch_pw_dyn_x3(s, pp, grid_cap);
+  else failed = launch_pw_dyn(s, pp, dt, grid_cap);
+  if (failed) { mcg_set_error("dynamic_layer (%s) launch failed", x3 ? "pw_single_x3" : "pw_single"); return MCG_ERR_HIP; }
+  return MCG_OK;
+}
+// One chain step: dst = [ReLU] LN(src . W^T [+ bias] [+ res]) (chain.hpp)
+static ChainStep chain_step(const void* W, const float* bias, const void* res, const float* g, const float* b, void* dst, int from_input, int relu) {
+  ChainStep st;
+  st.W = W; st.bias = bias; st.res = res; st.g = g; st.b = b; st.dst = dst; st.from_input = from_input; st.relu = relu;
+  return st;
+}
 
 struct StageWs {
   char *qkv, *att, *t, *x1, *x2, *x3, *params, *feat2, *h, *c1, *clsf, *r1, *r2;
@@ -563,7 +566,7 @@ struct StageWs {
 };
 static const int kFcSlices = 16;
 static StageWs stage_layout(mcg_dtype dt, int N, char* base) {
-  const size_t es = mcg_is16(dt) ? 2 : 4, R = (size_t)N * 3;
+  const size_t es = elem_bytes(dt), R = (size_t)N * 3;
   StageWs w;
   size_t off = 0;
   auto take = [&](size_t bytes) { char* p = base ? base + off : nullptr; off += al256(bytes); return p; };
@@ -612,24 +615,17 @@ extern "C" int mcg_stage_forward_ragged(mcg_stream s, mcg_dtype dt, const void* 
   return stage_forward_ctx((hipStream_t)s, dt, W, roi_feat, obj_in, boxes_in, N, ClipTable{clip_start, num_clips, max_clip_length}, obj_out, boxes_out,
                            cls_out, stds, ws, ws_bytes, McgCtx::from_flags(0, flags));
 }
-// `dynamic_layer`'s streaming kernels as a stand-alone operator, through this unit's own launchers (launch_pw_dyn / launch_pw_dyn_x3) at any M >= 1
+// `dynamic_layer`'s streaming kernels as a stand-alone operator, through this unit's own launcher (launch_dyn_layer) at any M >= 1
 extern "C" int mcg_pointwise_dyn(mcg_stream s, mcg_dtype dt, const void* a, const void* wf, const float* bias, void* y, int M, float wscale,
                                  int grid_cap) {
   MCG_CHECK_ARG(a && wf && bias && y, "mcg_pointwise_dyn: null pointer");
   MCG_CHECK_ARG(M > 0 && grid_cap >= 0, "mcg_pointwise_dyn: M must be positive and grid_cap >= 0 (M=%d grid_cap=%d)", M, grid_cap);
   const bool x3 = dt == MCG_F16X3;
-  if (!(x3 || mcg_is16(dt)) || (long long)M * MCG_ELEM_BYTES(dt) * 256 >= MCG_DMA_MAX_BYTES) {   // the A rows travel through a DMA descriptor
+  if (!(x3 || mcg_is16(dt)) || (long long)M * elem_bytes(dt) * 256 >= MCG_DMA_MAX_BYTES) {   // the A rows travel through a DMA descriptor
     mcg_set_error("mcg_pointwise_dyn: unsupported (dtype %d, M=%d): bf16 / fp16 / f16x3, M rows of 256 inputs below 2 GiB", (int)dt, M);
     return MCG_ERR_UNSUPPORTED;
   }
-  PwSingleParams pp;
-  memset(&pp, 0, sizeof(pp));
-  pp.a = a; pp.wf = wf; pp.bias = bias; pp.y = y; pp.M = M; pp.Ho = 1; pp.Wo = 1; pp.wscale = x3 ? wscale : 0.f;
-  if (x3 ? launch_pw_dyn_x3((hipStream_t)s, pp, grid_cap) : launch_pw_dyn((hipStream_t)s, pp, dt, grid_cap)) {
-    mcg_set_error("mcg_pointwise_dyn: launch failed");
-    return MCG_ERR_HIP;
-  }
-  return MCG_OK;
+  return launch_dyn_layer((hipStream_t)s, pw_dyn_params(a, wf, bias, y, M, x3 ? wscale : 0.f), dt, grid_cap);
 }
 
 int stage_forward_ctx(hipStream_t s, mcg_dtype dt, const void* const W[MCG_SW_COUNT], const void* roi_feat, const void* obj_in,
@@ -645,13 +641,13 @@ int stage_forward_ctx(hipStream_t s, mcg_dtype dt, const void* const W[MCG_SW_CO
   const float* f32w[MCG_SW_COUNT];
   for (int i = 0; i < MCG_SW_COUNT; ++i) f32w[i] = (const float*)W[i];
   const bool bf = mcg_is16(dt);   // 2-byte storage (MCG_BF16 or MCG_F16: the same launch sequence, instantiated per number format)
-  const size_t es = bf ? 2 : 4;
+  const size_t es = elem_bytes(dt);
 
   // --- spatial then temporal self-attention with SHARED weights and LayerNorm (gaze_stqi_head.py:148-166)
   const void* xin = obj_in;
   char* xout[2] = {w.x1, w.x2};
   const bool chain_attn = bf && ctx.chain;
-  const bool chain_x3 = dt == MCG_F16X3 && ctx.chain;   // f16x3: the row-block chains in the split arithmetic (chain_x3.hpp)
+  const bool chain_x3 = dt == MCG_F16X3 && ctx.chain;   // f16x3: the row-block chains in the split arithmetic (chain.hpp over OpsX3)
   // both passes as ONE launch, one clip per workgroup (bf16: attn_block.hpp; f16x3: attn_block_x3.hpp, round 6); bit-identical to the loop below
   const bool block_attn = (chain_attn || (chain_x3 && ctx.attn_block)) && attn_block_applicable(clip_length);
   if (block_attn) {
@@ -660,7 +656,7 @@ int stage_forward_ctx(hipStream_t s, mcg_dtype dt, const void* const W[MCG_SW_CO
     ap.x = obj_in; ap.y = w.x2; ap.w_in = W[MCG_SW_IN_PROJ_WF]; ap.b_in = f32w[MCG_SW_IN_PROJ_B];
     ap.w_out = W[MCG_SW_OUT_PROJ_WF]; ap.b_out = f32w[MCG_SW_OUT_PROJ_B]; ap.g = f32w[MCG_SW_ATTN_LN_G]; ap.b = f32w[MCG_SW_ATTN_LN_B];
     ap.num_clips = B; ap.T = clip_length; ap.scale = 1.0f / sqrtf(32.f); ap.clip_start = ct.start; ap.num_frames = N;
-    if (chain_x3 ? launch_attn_block_x3(s, ap) : launch_attn_block(s, ap, dt)) { mcg_set_error("attn_block launch failed"); return MCG_ERR_HIP; }
+    MCG_TRY(launch_attn_block(s, ap, dt));
   }
   for (int pass = 0; pass < 2 && !block_attn; ++pass) {
     MCG_TRY(launch_linear(s, dt, xin, 256, W[MCG_SW_IN_PROJ_W], f32w[MCG_SW_IN_PROJ_B], nullptr, 0, w.qkv, 768, R, 256, 768, 0, ctx));
@@ -674,9 +670,8 @@ int stage_forward_ctx(hipStream_t s, mcg_dtype dt, const void* const W[MCG_SW_CO
       ChainParams cp;
       memset(&cp, 0, sizeof(cp));
       cp.x = w.att; cp.M = R; cp.steps = 1;
-      cp.st[0].W = W[MCG_SW_OUT_PROJ_WF]; cp.st[0].bias = f32w[MCG_SW_OUT_PROJ_B]; cp.st[0].res = xin;
-      cp.st[0].g = f32w[MCG_SW_ATTN_LN_G]; cp.st[0].b = f32w[MCG_SW_ATTN_LN_B]; cp.st[0].dst = xout[pass]; cp.st[0].from_input = 1;
-      if (chain_x3 ? launch_mlp_chain_x3(s, cp) : launch_mlp_chain(s, cp, dt)) { mcg_set_error("mlp_chain launch failed"); return MCG_ERR_HIP; }
+      cp.st[0] = chain_step(W[MCG_SW_OUT_PROJ_WF], f32w[MCG_SW_OUT_PROJ_B], xin, f32w[MCG_SW_ATTN_LN_G], f32w[MCG_SW_ATTN_LN_B], xout[pass], 1, 0);
+      MCG_TRY(launch_mlp_chain(s, cp, dt));
     } else {
       MCG_TRY(launch_linear(s, dt, w.att, 256, W[MCG_SW_OUT_PROJ_W], f32w[MCG_SW_OUT_PROJ_B], xin, 256, w.t, 256, R, 256, 256, 0, ctx));
       MCG_TRY(launch_ln(s, dt, ln_simple(w.t, f32w[MCG_SW_ATTN_LN_G], f32w[MCG_SW_ATTN_LN_B], 0, xout[pass], R, 256)));
@@ -687,13 +682,10 @@ int stage_forward_ctx(hipStream_t s, mcg_dtype dt, const void* const W[MCG_SW_CO
   // few rows, 32768 columns: 256-column weight slices resident in registers, tokens streamed (16-bit: pw_single.hpp; f16x3: split weights,
   // 256 slices of 128 columns, pw_single_x3.hpp); bit-identical to the generic kernel
   if (ctx.chain && ctx.tile < 0 && pw_dyn_applicable(R) && (chain_x3 ? (long long)R * 1024 < MCG_DMA_MAX_BYTES : bf && !ctx.staged)) {
-    PwSingleParams pp;
-    memset(&pp, 0, sizeof(pp));
-    pp.a = w.x2; pp.wf = W[MCG_SW_DYN_WF]; pp.bias = f32w[MCG_SW_DYN_B]; pp.y = w.params; pp.M = R; pp.Ho = 1; pp.Wo = 1;
     ProfRec* rec = prof_begin(ctx, s, chain_x3 ? 72 : 62, R, 32768, 256, 2.0 * R * 32768 * 256, (double)es * ((double)R * (256 + 32768) + 32768.0 * 256));
-    const int rc = chain_x3 ? launch_pw_dyn_x3(s, pp) : launch_pw_dyn(s, pp, dt);
+    const int rc = launch_dyn_layer(s, pw_dyn_params(w.x2, W[MCG_SW_DYN_WF], f32w[MCG_SW_DYN_B], w.params, R, 0.f), dt, 0);
     prof_end(rec, s);
-    if (rc) { mcg_set_error("%s (dynamic_layer) launch failed", chain_x3 ? "pw_single_x3" : "pw_single"); return MCG_ERR_HIP; }
+    MCG_TRY(rc);
   } else {
     MCG_TRY(launch_linear(s, dt, w.x2, 256, W[MCG_SW_DYN_W], f32w[MCG_SW_DYN_B], nullptr, 0, w.params, 32768, R, 256, 32768, 0, ctx));
   }
@@ -719,19 +711,15 @@ int stage_forward_ctx(hipStream_t s, mcg_dtype dt, const void* const W[MCG_SW_CO
   // --- towers (gaze_stqi_head.py:185-188)
   const void* rin = obj_out;
   const bool chain = (bf || dt == MCG_F16X3) && ctx.chain;
-  if (chain) {  // cls tower + 3-layer reg tower: eight launches as one (chain.hpp: bit-identical; f16x3: chain_x3.hpp)
+  if (chain) {  // cls tower + 3-layer reg tower: eight launches as one (chain.hpp: bit-identical)
     ChainParams cp;
     memset(&cp, 0, sizeof(cp));
     cp.x = obj_out; cp.M = R; cp.steps = 4;
-    cp.st[0].W = W[MCG_SW_CLS_FC_WF]; cp.st[0].g = f32w[MCG_SW_CLS_LN_G]; cp.st[0].b = f32w[MCG_SW_CLS_LN_B]; cp.st[0].dst = w.clsf;
-    cp.st[0].from_input = 1; cp.st[0].relu = 1;
-    for (int j = 0; j < 3; ++j) {
-      ChainStep& st = cp.st[1 + j];
-      st.W = (const char*)W[MCG_SW_REG_FC_WF] + (size_t)j * 65536 * es;
-      st.g = f32w[MCG_SW_REG_LN_G] + j * 256; st.b = f32w[MCG_SW_REG_LN_B] + j * 256;
-      st.from_input = j == 0; st.relu = 1; st.dst = j == 2 ? w.r1 : nullptr;
-    }
-    if (bf ? launch_mlp_chain(s, cp, dt) : launch_mlp_chain_x3(s, cp)) { mcg_set_error("mlp_chain launch failed"); return MCG_ERR_HIP; }
+    cp.st[0] = chain_step(W[MCG_SW_CLS_FC_WF], nullptr, nullptr, f32w[MCG_SW_CLS_LN_G], f32w[MCG_SW_CLS_LN_B], w.clsf, 1, 1);
+    for (int j = 0; j < 3; ++j)
+      cp.st[1 + j] = chain_step((const char*)W[MCG_SW_REG_FC_WF] + (size_t)j * 65536 * es, nullptr, nullptr, f32w[MCG_SW_REG_LN_G] + j * 256,
+                                f32w[MCG_SW_REG_LN_B] + j * 256, j == 2 ? w.r1 : nullptr, j == 0, 1);
+    MCG_TRY(launch_mlp_chain(s, cp, dt));
     rin = w.r1;
   } else {
     MCG_TRY(launch_linear(s, dt, obj_out, 256, W[MCG_SW_CLS_FC_W], nullptr, nullptr, 0, w.c1, 256, R, 256, 256, 0, ctx));
@@ -754,8 +742,7 @@ int stage_forward_ctx(hipStream_t s, mcg_dtype dt, const void* const W[MCG_SW_CO
 }
 
 extern "C" size_t mcg_gaze_head_workspace_bytes(mcg_dtype dt, int num_frames) {
-  const size_t es = mcg_is16(dt) ? 2 : 4;
-  return 3 * al256((size_t)6 * num_frames * 256 * es);
+  return 3 * al256((size_t)6 * num_frames * 256 * elem_bytes(dt));
 }
 
 extern "C" int mcg_gaze_head(mcg_stream s, mcg_dtype dt, const void* const W[MCG_GW_COUNT], const void* obj, int N,
@@ -767,7 +754,7 @@ int gaze_head_ctx(hipStream_t s, mcg_dtype dt, const void* const W[MCG_GW_COUNT]
   MCG_CHECK_ARG(W && obj && gaze_out && ws && N > 0, "mcg_gaze_head: bad argument");
   for (int i = 0; i < MCG_GW_COUNT; ++i) MCG_CHECK_ARG(W[i], "mcg_gaze_head: weight table entry %d is null", i);
   if (ws_bytes < mcg_gaze_head_workspace_bytes(dt, N)) { mcg_set_error("mcg_gaze_head: workspace too small"); return MCG_ERR_WORKSPACE; }
-  const size_t es = mcg_is16(dt) ? 2 : 4;
+  const size_t es = elem_bytes(dt);
   const size_t buf = al256((size_t)6 * N * 256 * es);
   char* raw = (char*)ws; char* h1 = raw + buf; char* h2 = h1 + buf;
   const char* fcw = (const char*)W[MCG_GW_FC_W];  // [6 branches = k*3+clue][2 layers][256][256]

@@ -767,7 +767,7 @@ def test_mlp_chain_matches_unfused_bitwise(eng, sd, B, T, dtype):
 def test_attn_block_x3_matches_unfused_bitwise(eng, sd, B, T):
     """f16x3 (round 6): attn_block_x3.hpp -- both attention passes of a stage (in_proj, attention core, out_proj + residual + LayerNorm, twice) as
     ONE launch, one clip per workgroup, for 3 T <= 32 (T = 11 keeps the launch sequence) -- against the sequence it replaces
-    (MCG_FLAG_NO_ATTN_BLOCK: igemm_dma in_proj, attn_core_kernel, mlp_chain_x3 per pass) and against the generic launch sequence
+    (MCG_FLAG_NO_ATTN_BLOCK: igemm_dma in_proj, attn_core_kernel, mlp_chain_kernel<OpsX3> per pass) and against the generic launch sequence
     (MCG_FLAG_NO_SPECIALISED: no chains at all): same K order, same order of the three split terms, the same f32 rounding points, the
     same attention device function, ln_kernel's reduction order -- every output of the stage must be bit-identical in all three."""
     from mcgaze_amd.packing import PackedWeights

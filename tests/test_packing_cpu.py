@@ -1,4 +1,4 @@
-"""CPU: the weight layouts the round-3 kernels read (bneck_x3.hpp's slab stream, chain_x3.hpp's split fragment-major matrices) against
+"""CPU: the weight layouts the round-3 kernels read (bneck_x3.hpp's slab stream, the split fragment-major matrices of rowblock.hpp's OpsX3, which chain.hpp and attn_block_x3.hpp read) against
 their index formulas restated element by element, the fused-tail table PackedWeights builds, and bench.py's roofline bookkeeping."""
 import os
 import sys
