@@ -1183,7 +1183,7 @@ int mcg_gaze_targets_poly(mcg_stream s, const float* boxes_dev, const float* gaz
  * is touched, padding included, for ANY table contents.  Every wave of the gather grid reads the plan in (m + 2 n) / 64 slices, and a large
  * region's box covers many tiles that each test up to 32 capsules per pixel: made for the tens of heads and regions of a video frame.
  * mcgaze_amd/arrows.py::draw_attention_host is the same on the host, bit for bit.  Out of scope: arrows cut at the hit point, filled
- * regions, text. */
+ * regions.  (Text: "text labels" below.) */
 typedef struct mcg_stroke_desc {
   int seg[3][2][2];         /* a sight line: seg[0]; an arrow: shaft, stroke, stroke -- (from, to) x (x, y); a region: unused (its vertices follow the plan) */
   int thickness;
@@ -1205,6 +1205,66 @@ int mcg_draw_attention_nv12(mcg_stream s, const mcg_nv12_image_desc* images_dev,
                             const int32_t* region_start_dev, const int32_t* region_image_dev, int m, int region_period, const unsigned char* palette,
                             double length, int min_thickness, double thickness_ratio, double tip_length, int line_thickness, int region_thickness,
                             void* workspace_dev, size_t workspace_bytes, int32_t* flags_dev, int32_t* region_flags_dev, int32_t* region_active_dev);
+
+/* ---------------------------------------------------------------- text labels (additions to ABI 19; nothing above changes)
+ * Words on the frame: '#12 3.4s' next to a head, 'SHELF A' in a region -- drawn IN PLACE into packed BGR frames (mcg_draw_labels) or NV12
+ * surfaces (mcg_draw_labels_nv12) from tables that are all in device memory.  The library holds NO font: font_dev is a DEVICE uint8 [96][8]
+ * table for the codes 32 .. 126 and one spare entry, one byte per glyph row, bit c (from the least significant) the glyph's column c from
+ * the left -- any 8-row bitmap font (mcgaze_amd/arrows.py::LABEL_FONT is a 5 x 7 one drawn for this project).
+ * TEXT.  A row's text is MCG_LABEL_CHARS = 24 bytes; its length len is the index of its first zero byte, 24 if there is none.
+ * mcg_format_labels writes such rows, one launch, one thread per row, 24 bytes each: id <= 0 gives all zeros; otherwise '#' decimal(id), and
+ * where value_dev is given and value > 0, with q = (int64)value * 10 * den / num (a floor), ' ' decimal(q / 10) '.' ('0' + q % 10) 's' --
+ * the seconds of `value` frames at num / den frames per second, in tenths, never rounded up; the rest of the row is zero.
+ * 1 <= den <= num <= 2^20 is required: then q / 10 <= value, and every text of at most 24 characters is written whole.  The one longer
+ * text has 25: an id of ten digits with a seconds part of ten digits (value >= 10^9 frames at a rate below 2.15 frames per second); it is
+ * cut after 24 bytes, losing its 's'.  Nothing is ever written outside the row.
+ * PLAN, per row k (one thread per row; coordinates f32 widened to double, then integers).  USABLE: image_of in [0, num_images); the image
+ * writable (pixels; NV12: even sizes) and no larger than (max_h, max_w); the four box coordinates finite; bx1 = trunc(x1), by1, bx2, by2
+ * all in [-8191, 8191].  Anything else: flag 2, nothing written.  A usable row with len == 0: flag 1, an EMPTY LABEL, nothing written --
+ * how a row with nobody in it stays silent.  The descriptor of a flagged row is zero but for image = -1 and the flag.
+ * With s = scale, a = advance, P = pad * s:  TW = len * a * s, TH = 8 * s, PW = TW + 2 P, PH = TH + 2 P.
+ * PLACEMENT (the place word is 0 where place_dev is NULL).  place == 1: X = bx1, Y = by1 -- inside the top-left corner, for regions.  Any
+ * other word: X = bx1, Y = by1 - PH, and if Y < 0 then Y = by2 + 1 -- above the box, else below it.  Then X = max(0, min(X, w - PW)) and
+ * Y = max(0, min(Y, h - PH)): a plate wider than the frame starts at 0 and is clipped.  The PLATE is [X, X + PW) x [Y, Y + PH) clipped to
+ * the frame, the TEXT ORIGIN (X + P, Y + P).
+ * COVERAGE.  Pixel (px, py) is a glyph pixel of row k iff fx = px - (X + P) lies in [0, TW), fy = py - (Y + P) in [0, TH), and with
+ * ci = fx / (a s), col = (fx % (a s)) / s, r = fy / s, c = text[k][ci], g = c - 32 if 32 <= c <= 126 else 31 (the '?' glyph):
+ * (font[g][r] >> col) & 1.  (A glyph pixel lies inside the plate.)
+ * STROKES.  With a background the plate of row k is stroke 2 k, in the call's one background colour; the glyph pixels of row k are stroke
+ * 2 k + 1, in colors_dev[k], else color.  A pixel takes the colour of the HIGHEST-numbered stroke that covers it, whatever the launch
+ * geometry; a pixel no stroke covers is not written.  Without a background only the glyph strokes exist.  NV12 follows "annotated frames
+ * out": every covered luma pixel gets the Y of ITS highest stroke; a chroma pair is written iff any of its four luma pixels is covered,
+ * with the (U, V) of the highest stroke among the four; colours are (Y, U, V).
+ *   images_dev, num_images, max_h, max_w, boxes_dev, image_of_dev: as mcg_draw_gaze_arrows takes them
+ *   text_dev     DEVICE uint8 [n][24];  place_dev DEVICE int32 [n] or NULL;  font_dev DEVICE uint8 [96][8]
+ *   scale 1 .. 16 (pixels per font bit), advance 1 .. 8 (font columns per character), pad 0 .. 8 (font bits around the text)
+ *   color        HOST uint8[3], used for every row when colors_dev is NULL;  colors_dev DEVICE uint8 [n][3] or NULL
+ *   background   HOST uint8[3] or NULL (no plates)
+ *   plan_out_dev DEVICE [n] descriptors (written);  flags_dev DEVICE int32 [n] or NULL
+ * Two launches (plan; a gather kernel over (image, pixel tile) that ballots 64 plan records at a time against a wave's strip, walks the
+ * hits in ascending order and stores each covered pixel once), no allocation, no host sync, no atomics, graph-capturable.  n <= 65535 and
+ * the ranges above: anything else, or a null required table, returns MCG_ERR_ARG before any launch; n == 0 returns MCG_OK without one.  No
+ * byte outside [0, h) x [0, w) of any plane is touched, padding included, for ANY table contents.  Every wave of the gather grid reads the
+ * plan in n / 64 slices: made for the tens of labels of a video frame.  mcgaze_amd/arrows.py::format_labels_host and draw_labels_host are
+ * the same on the host, bit for bit.  Out of scope: scalable or anti-aliased fonts, glyphs beyond the '?' fallback, a scale per row. */
+#define MCG_LABEL_CHARS 24
+typedef struct mcg_label_desc {
+  int x, y;                 /* the text origin (X + P, Y + P) */
+  int x0, y0, x1, y1;       /* the plate clipped to the frame, half open */
+  int image, flag;          /* flag 0: drawn; 1: an empty label; 2: unusable */
+  int len;
+  unsigned color;           /* the glyphs' colour, c0 | c1 << 8 | c2 << 16 */
+  unsigned char text[MCG_LABEL_CHARS];   /* the first len codes, then zeros */
+} mcg_label_desc;
+int mcg_format_labels(mcg_stream s, const int32_t* id_dev, const int32_t* value_dev, int n, int num, int den, unsigned char* text_out_dev);
+int mcg_draw_labels(mcg_stream s, const mcg_image_desc* images_dev, int num_images, int max_h, int max_w, const float* boxes_dev,
+                    const int32_t* image_of_dev, const unsigned char* text_dev, const int32_t* place_dev, int n, const unsigned char* font_dev,
+                    int scale, int advance, int pad, const unsigned char* color, const unsigned char* colors_dev, const unsigned char* background,
+                    mcg_label_desc* plan_out_dev, int32_t* flags_dev);
+int mcg_draw_labels_nv12(mcg_stream s, const mcg_nv12_image_desc* images_dev, int num_images, int max_h, int max_w, const float* boxes_dev,
+                         const int32_t* image_of_dev, const unsigned char* text_dev, const int32_t* place_dev, int n, const unsigned char* font_dev,
+                         int scale, int advance, int pad, const unsigned char* yuv, const unsigned char* yuvs_dev, const unsigned char* background,
+                         mcg_label_desc* plan_out_dev, int32_t* flags_dev);
 
 /* ---------------------------------------------------------------- measurement aids (bench.py)
  * While armed, every launch of the contraction kernel made by THIS engine is bracketed by a hipEvent pair on its launch stream.

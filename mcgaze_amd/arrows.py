@@ -318,3 +318,349 @@ def draw_attention_host(frames, boxes, gaze, image_of, kind, target, hit, mutual
         else:
             out[p][winner >= 0] = color[winner[winner >= 0]]
     return (out[0] if single else out), flags, region_flags, region_active
+
+
+# ---------------------------------------------------------------- text labels (include/mcgaze_hip.h, "text labels")
+LABEL_CHARS = 24                                                 # MCG_LABEL_CHARS
+# The glyphs of LABEL_FONT, drawn by hand for this project: codes 32 .. 126 in order, seven rows of five columns each, '#' set.  The eighth
+# row and the columns 5 .. 7 of the 8 x 8 cell stay empty (the gap between lines and characters).
+_GLYPHS = (
+    '...../...../...../...../...../...../.....',   # space
+    '..#../..#../..#../..#../..#../...../..#..',   # !
+    '.#.#./.#.#./.#.#./...../...../...../.....',   # "
+    '.#.#./.#.#./#####/.#.#./#####/.#.#./.#.#.',   # #
+    '..#../.####/#.#../.###./..#.#/####./..#..',   # $
+    '##..#/##..#/...#./..#../.#.../#..##/#..##',   # %
+    '.##../#..#./#.#../.#.../#.#.#/#..#./.##.#',   # &
+    '..#../..#../..#../...../...../...../.....',   # '
+    '...#./..#../.#.../.#.../.#.../..#../...#.',   # (
+    '.#.../..#../...#./...#./...#./..#../.#...',   # )
+    '...../..#../#.#.#/.###./#.#.#/..#../.....',   # *
+    '...../..#../..#../#####/..#../..#../.....',   # +
+    '...../...../...../...../.##../..#../.#...',   # ,
+    '...../...../...../#####/...../...../.....',   # -
+    '...../...../...../...../...../.##../.##..',   # .
+    '....#/....#/...#./..#../.#.../#..../#....',   # /
+    '.###./#...#/#..##/#.#.#/##..#/#...#/.###.',   # 0
+    '..#../.##../..#../..#../..#../..#../.###.',   # 1
+    '.###./#...#/....#/...#./..#../.#.../#####',   # 2
+    '#####/...#./..#../...#./....#/#...#/.###.',   # 3
+    '...#./..##./.#.#./#..#./#####/...#./...#.',   # 4
+    '#####/#..../####./....#/....#/#...#/.###.',   # 5
+    '..##./.#.../#..../####./#...#/#...#/.###.',   # 6
+    '#####/....#/...#./..#../.#.../.#.../.#...',   # 7
+    '.###./#...#/#...#/.###./#...#/#...#/.###.',   # 8
+    '.###./#...#/#...#/.####/....#/...#./.##..',   # 9
+    '...../.##../.##../...../.##../.##../.....',   # :
+    '...../.##../.##../...../.##../..#../.#...',   # ;
+    '...#./..#../.#.../#..../.#.../..#../...#.',   # <
+    '...../...../#####/...../#####/...../.....',   # =
+    '.#.../..#../...#./....#/...#./..#../.#...',   # >
+    '.###./#...#/....#/...#./..#../...../..#..',   # ?
+    '.###./#...#/#.###/#.#.#/#.###/#..../.####',   # @
+    '.###./#...#/#...#/#####/#...#/#...#/#...#',   # A
+    '####./#...#/#...#/####./#...#/#...#/####.',   # B
+    '.###./#...#/#..../#..../#..../#...#/.###.',   # C
+    '###../#..#./#...#/#...#/#...#/#..#./###..',   # D
+    '#####/#..../#..../####./#..../#..../#####',   # E
+    '#####/#..../#..../####./#..../#..../#....',   # F
+    '.###./#...#/#..../#.###/#...#/#...#/.####',   # G
+    '#...#/#...#/#...#/#####/#...#/#...#/#...#',   # H
+    '.###./..#../..#../..#../..#../..#../.###.',   # I
+    '..###/...#./...#./...#./...#./#..#./.##..',   # J
+    '#...#/#..#./#.#../##.../#.#../#..#./#...#',   # K
+    '#..../#..../#..../#..../#..../#..../#####',   # L
+    '#...#/##.##/#.#.#/#.#.#/#...#/#...#/#...#',   # M
+    '#...#/##..#/#.#.#/#..##/#...#/#...#/#...#',   # N
+    '.###./#...#/#...#/#...#/#...#/#...#/.###.',   # O
+    '####./#...#/#...#/####./#..../#..../#....',   # P
+    '.###./#...#/#...#/#...#/#.#.#/#..#./.##.#',   # Q
+    '####./#...#/#...#/####./#.#../#..#./#...#',   # R
+    '.####/#..../#..../.###./....#/....#/####.',   # S
+    '#####/..#../..#../..#../..#../..#../..#..',   # T
+    '#...#/#...#/#...#/#...#/#...#/#...#/.###.',   # U
+    '#...#/#...#/#...#/#...#/#...#/.#.#./..#..',   # V
+    '#...#/#...#/#...#/#.#.#/#.#.#/##.##/#...#',   # W
+    '#...#/#...#/.#.#./..#../.#.#./#...#/#...#',   # X
+    '#...#/#...#/.#.#./..#../..#../..#../..#..',   # Y
+    '#####/....#/...#./..#../.#.../#..../#####',   # Z
+    '.###./.#.../.#.../.#.../.#.../.#.../.###.',   # [
+    '#..../#..../.#.../..#../...#./....#/....#',   # backslash
+    '.###./...#./...#./...#./...#./...#./.###.',   # ]
+    '..#../.#.#./#...#/...../...../...../.....',   # ^
+    '...../...../...../...../...../...../#####',   # _
+    '.#.../..#../...#./...../...../...../.....',   # `
+    '...../...../.###./....#/.####/#...#/.####',   # a
+    '#..../#..../#.##./##..#/#...#/#...#/####.',   # b
+    '...../...../.###./#..../#..../#...#/.###.',   # c
+    '....#/....#/.##.#/#..##/#...#/#...#/.####',   # d
+    '...../...../.###./#...#/#####/#..../.###.',   # e
+    '..##./.#..#/.#.../###../.#.../.#.../.#...',   # f
+    '...../.####/#...#/#...#/.####/....#/.###.',   # g
+    '#..../#..../#.##./##..#/#...#/#...#/#...#',   # h
+    '..#../...../.##../..#../..#../..#../.###.',   # i
+    '...#./...../..##./...#./...#./#..#./.##..',   # j
+    '#..../#..../#..#./#.#../##.../#.#../#..#.',   # k
+    '.##../..#../..#../..#../..#../..#../.###.',   # l
+    '...../...../##.#./#.#.#/#.#.#/#...#/#...#',   # m
+    '...../...../#.##./##..#/#...#/#...#/#...#',   # n
+    '...../...../.###./#...#/#...#/#...#/.###.',   # o
+    '...../####./#...#/#...#/####./#..../#....',   # p
+    '...../.####/#...#/#...#/.####/....#/....#',   # q
+    '...../...../#.##./##..#/#..../#..../#....',   # r
+    '...../...../.####/#..../.###./....#/####.',   # s
+    '.#.../.#.../###../.#.../.#.../.#..#/..##.',   # t
+    '...../...../#...#/#...#/#...#/#..##/.##.#',   # u
+    '...../...../#...#/#...#/#...#/.#.#./..#..',   # v
+    '...../...../#...#/#...#/#.#.#/#.#.#/.#.#.',   # w
+    '...../...../#...#/.#.#./..#../.#.#./#...#',   # x
+    '...../#...#/#...#/#...#/.####/....#/.###.',   # y
+    '...../...../#####/...#./..#../.#.../#####',   # z
+    '...#./..#../..#../.#.../..#../..#../...#.',   # {
+    '..#../..#../..#../..#../..#../..#../..#..',   # |
+    '.#.../..#../..#../...#./..#../..#../.#...',   # }
+    '...../...../.#.../#.#.#/...#./...../.....',   # ~
+)
+
+
+def _label_font():
+    font = np.zeros((96, 8), dtype=np.uint8)                     # entry 95 is spare: the codes end at 126
+    for g, rows in enumerate(_GLYPHS):
+        for r, bits in enumerate(rows.split('/')):
+            font[g, r] = sum(1 << c for c, b in enumerate(bits) if b == '#')
+    return font
+
+
+LABEL_FONT = _label_font()                                       # uint8 [96][8]: one byte per glyph row, bit c (from the least significant) is column c from the left
+LABEL_FONT.setflags(write=False)
+
+
+def glyph_sheet(font=LABEL_FONT, per_line=16):
+    """The font as text art, ``per_line`` glyphs side by side: what INTEGRATION.md shows."""
+    lines = []
+    for first in range(0, 95, per_line):
+        lines += [' '.join(''.join('#' if font[g, r] >> c & 1 else '.' for c in range(5)) for g in range(first, min(first + per_line, 95))) for r in range(7)]
+        lines.append('')
+    return '\n'.join(lines[:-1])
+
+
+def encode_labels(strings):
+    """Strings -> the text table uint8 [n][24] of the label entries: Latin-1 codes, zero behind the end.  ValueError for a string longer than
+    24 characters or with a character outside Latin-1.  (A code outside 32 .. 126 is drawn as '?'.)"""
+    out = np.zeros((len(strings), LABEL_CHARS), dtype=np.uint8)
+    for k, s in enumerate(strings):
+        try:
+            codes = str(s).encode('latin-1')
+        except UnicodeEncodeError:
+            raise ValueError(f'label {k} {s!r} holds a character outside Latin-1') from None
+        if len(codes) > LABEL_CHARS:
+            raise ValueError(f'label {k} {s!r} is longer than {LABEL_CHARS} characters')
+        out[k, :len(codes)] = np.frombuffer(codes, dtype=np.uint8)
+    return out
+
+
+def _label_rate(rate):
+    """rate = (num, den) frames per second, validated (ValueError) -> (num, den): integers with 1 <= den <= num <= 2^20."""
+    try:
+        num, den = rate
+        ok = all(isinstance(v, (int, np.integer)) and not isinstance(v, bool) for v in (num, den)) and 1 <= den <= num <= 1 << 20
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError(f'rate must be (num, den), integers with 1 <= den <= num <= 2^20 frames per second; got {rate!r}')
+    return int(num), int(den)
+
+
+def _label_params(scale=2, advance=6, pad=1):
+    """scale, advance and pad of the label entries, validated (ValueError) -> ints."""
+    for name, v, lo, hi in (('scale', scale, 1, 16), ('advance', advance, 1, 8), ('pad', pad, 0, 8)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= v <= hi:
+            raise ValueError(f'{name} must be an integer in {lo} .. {hi}, got {v!r}')
+    return int(scale), int(advance), int(pad)
+
+
+def _label_options(who, labels, draw):
+    """The ``labels=`` option of LiveGaze and of run_head_video's draw dict, validated (ValueError) -> None (off) or dict(scale, advance, pad,
+    background, fps, region_names), the defaults filled in.  It needs ``draw``."""
+    if labels is None or labels is False:
+        return None
+    if labels is not True and not isinstance(labels, dict):
+        raise ValueError(f'{who}: labels is None, True or a dict of scale, advance, pad, background, fps and region_names; got {labels!r}')
+    opts = dict(scale=2, advance=6, pad=1, background=(0, 0, 0), fps=(30, 1), region_names=None)
+    given = {} if labels is True else dict(labels)
+    if set(given) - set(opts):
+        raise ValueError(f'{who}: labels takes {sorted(opts)}; got {sorted(given)}')
+    if not draw:
+        raise ValueError(f'{who}: labels writes into the frames draw hands out: it needs draw')
+    opts.update(given)
+    opts['scale'], opts['advance'], opts['pad'] = _label_params(opts['scale'], opts['advance'], opts['pad'])
+    opts['fps'] = _label_rate(opts['fps'])
+    _label_background(opts['background'], False, 'bt601')
+    return opts
+
+
+def _label_ints(name, t, n=None):
+    a = np.asarray(_host_array(t)).reshape(-1)
+    if a.size and a.dtype.kind not in 'iu':
+        raise TypeError(f'{name} must hold integers, got {a.dtype}')
+    if n is not None and a.shape != (n,):
+        raise ValueError(f'{name} must be [{n}], one per row; got {a.shape}')
+    if a.size and (a.min() < -2 ** 31 or a.max() >= 2 ** 31):
+        raise ValueError(f'{name} must fit int32')
+    return np.ascontiguousarray(a, dtype=np.int32)
+
+
+def format_labels_host(ids, values=None, rate=(30, 1)):
+    """mcg_format_labels on the host, bit for bit (include/mcgaze_hip.h, "text labels") -> uint8 [n][24].  ids [n] int32: id <= 0 gives an
+    empty row, else '#' + decimal(id); with values [n] int32 (frames) and a value > 0, ' ' + seconds in tenths + 's' at rate = (num, den)
+    frames per second, floored.  A text of 25 characters -- ten digits on both sides -- loses its 's'."""
+    num, den = _label_rate(rate)
+    ids = _label_ints('ids', ids)
+    values = None if values is None else _label_ints('values', values, len(ids))
+    out = np.zeros((len(ids), LABEL_CHARS), dtype=np.uint8)
+    for k, v in enumerate(ids.tolist()):
+        if v <= 0:
+            continue
+        s = '#' + str(v)
+        f = 0 if values is None else int(values[k])
+        if f > 0:
+            q = f * 10 * den // num
+            s += f' {q // 10}.{q % 10}s'
+        codes = s.encode('ascii')[:LABEL_CHARS]
+        out[k, :len(codes)] = np.frombuffer(codes, dtype=np.uint8)
+    return out
+
+
+def _label_text(text, n):
+    t = np.asarray(_host_array(text))
+    t = t.reshape(0, LABEL_CHARS) if t.size == 0 else t
+    if t.dtype != np.uint8 or t.shape != (n, LABEL_CHARS):
+        raise ValueError(f'text must be uint8 [{n}, {LABEL_CHARS}] (encode_labels, format_labels), got {t.dtype} {t.shape}')
+    return np.ascontiguousarray(t)
+
+
+def _label_font_table(font):
+    f = np.asarray(LABEL_FONT if font is None else _host_array(font))
+    if f.dtype != np.uint8 or f.shape != (96, 8):
+        raise ValueError(f'font must be uint8 [96, 8], got {f.dtype} {f.shape}')
+    return np.ascontiguousarray(f)
+
+
+def _label_background(background, nv12, matrix):
+    """-> uint8 [3] as the entries take it (NV12: converted once by bgr_to_yuv), or None: no plates."""
+    if background is None:
+        return None
+    c = np.asarray(_host_array(background))
+    if c.dtype.kind not in 'iu' or c.shape != (3,) or c.min() < 0 or c.max() > 255:
+        raise ValueError(f'background must be one (B, G, R) triple of integers in [0, 255] or None, got {background!r}')
+    c = c.astype(np.uint8)
+    return np.asarray(bgr_to_yuv(c, matrix), dtype=np.uint8).reshape(3) if nv12 else c
+
+
+def label_plan(boxes, image_of, text, sizes, place=None, scale=2, advance=6, pad=1, nv12=False):
+    """The label plan on the host (include/mcgaze_hip.h, "text labels"; label_plan_kernel line for line): boxes [n,4] read as f32, image_of
+    [n], text uint8 [n,24], place [n] or None, sizes [(h, w), ...] of the frames -> a dict of int64 [n] arrays x, y (the text origin), x0,
+    y0, x1, y1 (the plate clipped to the frame), image, flag, len.  Flag 2: image_of outside the table, an image without pixels, larger than
+    8192 a side or (nv12) of odd size, a box that is not finite or beyond +-8191 once truncated; flag 1: an empty text.  A flagged row is
+    zero but for image = -1."""
+    scale, advance, pad = _label_params(scale, advance, pad)
+    b = np.asarray(boxes, dtype=np.float32).astype(np.float64).reshape(-1, 4)
+    n = len(b)
+    image_of = _label_ints('image_of', image_of, n).astype(np.int64)
+    text = _label_text(text, n)
+    place = np.zeros(n, dtype=np.int64) if place is None else _label_ints('place', place, n).astype(np.int64)
+    hw = np.asarray(sizes, dtype=np.int64).reshape(-1, 2)
+    ok = (image_of >= 0) & (image_of < len(hw)) & np.isfinite(b).all(axis=1)
+    h, w = (np.where(ok, hw[np.where(ok, image_of, 0), c] if len(hw) else 0, 0) for c in (0, 1))
+    ok &= (h > 0) & (w > 0) & (h <= ARROW_SIDE) & (w <= ARROW_SIDE)
+    if nv12:
+        ok &= ((h | w) & 1) == 0
+    bt = np.trunc(np.where(np.isfinite(b), b, 0.0))
+    ok &= (np.abs(bt) <= ARROW_COORD).all(axis=1)
+    bt = np.where(ok[:, None], bt, 0.0).astype(np.int64)
+    zero = text == 0
+    length = np.where(zero.any(axis=1), zero.argmax(axis=1), LABEL_CHARS).astype(np.int64)
+    flag = np.where(~ok, 2, np.where(length == 0, 1, 0))
+    live = flag == 0
+    P = pad * scale
+    PW, PH = length * advance * scale + 2 * P, 8 * scale + 2 * P
+    X, Y = bt[:, 0], np.where(place == 1, bt[:, 1], np.where(bt[:, 1] - PH < 0, bt[:, 3] + 1, bt[:, 1] - PH))
+    X, Y = np.maximum(0, np.minimum(X, w - PW)), np.maximum(0, np.minimum(Y, h - PH))
+    plan = dict(x=X + P, y=Y + P, x0=X, y0=Y, x1=np.minimum(X + PW, w), y1=np.minimum(Y + PH, h), image=image_of, len=length)
+    plan = {k: np.where(live, v, -1 if k == 'image' else 0).astype(np.int64) for k, v in plan.items()}
+    plan['flag'] = flag.astype(np.int64)
+    return plan
+
+
+def label_coverage(plan, k, text, font=None, scale=2, advance=6):
+    """(plate's y0, x0, bool [y1 - y0, x1 - x0]): which pixels of the clipped plate of row k are glyph pixels -- COVERAGE of "text labels"."""
+    font = _label_font_table(font)
+    x0, y0, x1, y1 = (int(plan[f][k]) for f in ('x0', 'y0', 'x1', 'y1'))
+    py, px = np.mgrid[y0:y1, x0:x1]
+    fx, fy = px - int(plan['x'][k]), py - int(plan['y'][k])
+    cell, n = advance * scale, int(plan['len'][k])
+    inside = (fx >= 0) & (fx < n * cell) & (fy >= 0) & (fy < 8 * scale)
+    fx, fy = np.where(inside, fx, 0), np.where(inside, fy, 0)
+    codes = np.asarray(text[k], dtype=np.int64)[fx // cell]
+    glyph = np.where((codes >= 32) & (codes <= 126), codes - 32, 31)
+    return y0, x0, inside & ((font[glyph, fy // scale] >> ((fx % cell) // scale).astype(np.uint8)) & 1).astype(bool)
+
+
+def draw_labels_host(frames, boxes, image_of, text, colors=None, color=None, background=(0, 0, 0), scale=2, advance=6, pad=1, place=None, font=None,
+                     pixel_format='bgr', matrix='bt601', strict=False):
+    """Text labels drawn with numpy: what DevicePipeline.draw_labels (mcg_draw_labels / mcg_draw_labels_nv12) writes on the device, bit for
+    bit (include/mcgaze_hip.h, "text labels": the plan, the coverage, the plate of row k as stroke 2 k under its glyphs as stroke 2 k + 1,
+    the highest stroke winning, the NV12 chroma rule).
+
+    frames, pixel_format, matrix: as for draw_arrows_host.  boxes [n,4], image_of [n] (None: frame 0), text uint8 [n,24] (encode_labels,
+    format_labels_host), place [n] or None (1: inside the box's top-left corner; else above the box, below it where there is no room).
+    color: one (B, G, R) triple (None: the arrows' (230, 253, 11)); colors: one per row, [n,3], instead.  background: one triple, or None
+    for no plates.  font: uint8 [96,8] (None: LABEL_FONT).
+    -> (annotated COPIES in the form given, flags int32 [n]: 0 drawn, 1 an empty label, 2 unusable).  strict=True raises ValueError for a
+    flag 2 row instead (what draw_labels does for host tables)."""
+    nv12, _ = _pixel_format(pixel_format, matrix)
+    scale, advance, pad = _label_params(scale, advance, pad)
+    font = _label_font_table(font)
+    single = not isinstance(frames, list)
+    frames = [frames] if single else frames
+    if nv12:
+        out = [tuple(np.array(p) for p in _nv12_planes(k, f)[:2]) for k, f in enumerate(frames)]
+        sizes = [y.shape for y, _ in out]
+    else:
+        out = [_bgr_frame(k, np.array(f)) for k, f in enumerate(frames)]
+        sizes = [a.shape[:2] for a in out]
+    n = len(np.asarray(_host_array(boxes)).reshape(-1, 4))
+    image_of = np.zeros(n, dtype=np.int32) if image_of is None else _host_array(image_of)
+    text = _label_text(text, n)
+    plan = label_plan(_host_array(boxes), image_of, text, sizes, place, scale, advance, pad, nv12)
+    flags = plan['flag'].astype(np.int32)
+    if strict and (flags == 2).any():
+        k = int(np.flatnonzero(flags == 2)[0])
+        raise ValueError(f'label {k} cannot be drawn: box {np.asarray(_host_array(boxes)).reshape(-1, 4)[k].tolist()}, image_of {int(np.asarray(image_of).reshape(-1)[k])} of '
+                         f'{len(sizes)} -- not finite, outside the image table, or a coordinate beyond +-{ARROW_COORD}')
+    one, per_row = _arrow_colors(color if colors is None else colors, n, nv12, matrix)
+    if colors is not None and per_row is None:
+        raise ValueError(f'colors must be one (B, G, R) triple per row, [{n}, 3]')
+    bg = _label_background(background, nv12, matrix)
+    for p, (h, w) in enumerate(sizes):
+        rows = np.flatnonzero((flags == 0) & (plan['image'] == p))
+        if not len(rows):
+            continue
+        winner = np.full((h, w), -1, dtype=np.int64)             # the highest stroke that covers each pixel
+        stroke_color = np.zeros((2 * n, 3), dtype=np.uint8)
+        for k in rows:                                           # ascending: a later stroke overwrites an earlier one
+            y0, x0, glyphs = label_coverage(plan, k, text, font, scale, advance)
+            area = winner[y0:y0 + glyphs.shape[0], x0:x0 + glyphs.shape[1]]
+            if bg is not None:
+                area[:] = 2 * k
+                stroke_color[2 * k] = bg
+            area[glyphs] = 2 * k + 1
+            stroke_color[2 * k + 1] = one if per_row is None else per_row[k]
+        if nv12:
+            y, uv = out[p]
+            y[winner >= 0] = stroke_color[winner[winner >= 0], 0]
+            top = winner.reshape(h // 2, 2, w // 2, 2).max(axis=(1, 3))   # the highest stroke among the four luma pixels of a chroma pair
+            uv.reshape(h // 2, w // 2, 2)[top >= 0] = stroke_color[top[top >= 0], 1:]
+        else:
+            out[p][winner >= 0] = stroke_color[winner[winner >= 0]]
+    return (out[0] if single else out), flags

@@ -503,3 +503,31 @@ def open_episodes(state):
     s = np.asarray(_host_array(state)).reshape(-1, 16)
     cols = np.flatnonzero((s[:, 0] != 0) & (s[:, 2] != 0))
     return cols, s[cols, :7]
+
+
+def region_label_rows(regions, region_image, names, num_images, region_period=0):
+    """The rows that name the regions in the pictures, for ``DevicePipeline.draw_labels`` / ``arrows.draw_labels_host``: one row per (picture,
+    named region) that draw_attention would draw the region's outline into -- the region usable, and region_image < 0, == p, or with a
+    region_period == p % region_period.  regions, region_image, region_period: as gaze_targets_host takes them, on the HOST (TypeError for a
+    device table: nothing is read back); names: one string per region, None or '' for a region without a name; num_images pictures.
+    -> (boxes f32 [r,4]: the bounding box of the region's vertices; image_of int32 [r]; text uint8 [r,24] (``encode_labels``); place int32 [r],
+    all 1: inside the box's top-left corner), pictures ascending and regions ascending inside a picture."""
+    from . import arrows as R                                     # (arrows imports this module)
+    who = 'region_label_rows'
+    parts = (*regions, region_image) if isinstance(regions, PolyRegions) else (regions, region_image)
+    if any(type(t).__module__.startswith('torch') and getattr(t, 'is_cuda', False) for t in parts):
+        raise TypeError(f'{who}: regions on the host only; device tables are not read back')
+    _, _, period = _target_params(region_period=region_period, who=who)
+    xy, start, ri = R._overlay_regions(who, regions, region_image)
+    if names is None or len(names) != len(ri):
+        raise ValueError(f'{who}: names must hold one entry per region ({len(ri)}), got {None if names is None else len(names)}')
+    text = R.encode_labels(['' if s is None else s for s in names])
+    corners, _ = R.region_outlines(xy, start)
+    rows = [(p, j) for p in range(int(num_images)) for j in range(len(ri))
+            if text[j, 0] and corners[j] is not None and (ri[j] < 0 or ri[j] == p or (period > 0 and ri[j] == p % period))]
+    boxes = np.zeros((len(rows), 4), dtype=np.float32)
+    for k, (_, j) in enumerate(rows):
+        v = xy[start[j]:start[j + 1]]
+        boxes[k] = (v[:, 0].min(), v[:, 1].min(), v[:, 0].max(), v[:, 1].max())
+    regs = np.array([j for _, j in rows], dtype=np.int64)
+    return boxes, np.array([p for p, _ in rows], dtype=np.int32), text[regs].reshape(-1, R.LABEL_CHARS), np.ones(len(rows), dtype=np.int32)

@@ -24,6 +24,8 @@ RULES = {
     # the 16 state words of a column are meant to stay in registers across the frame loop
     'gaze_dwell_kernel': dict(scratch=0, vgpr_spill=0, unit='dwell'),
     'gaze_dwell_events_kernel': dict(scratch=0, vgpr_spill=0, unit='dwell'),
+    # the winning stroke of a lane's pixels is meant to stay in registers across the plan walk, as in the arrows' gather kernel
+    'label_raster_kernel': dict(scratch=0, vgpr_spill=0, unit='labels'),
 }
 
 

@@ -22,7 +22,7 @@ import torch
 
 from .attention import END_VIDEO_ENDED, KIND_HEAD, KIND_REGION, MAX_COLUMNS, MAX_ROWS, _attention_options, _dwell_options, open_episodes
 from .engine import _upload_table
-from .arrows import OVERLAY_PALETTE, _overlay_options
+from .arrows import OVERLAY_PALETTE, _label_options, _overlay_options, format_labels_host
 from .pipeline import ARROW_COLOR, _track_motion, _track_params, letterbox_geometry
 
 CLUES = ('face', 'eyes', 'head')
@@ -883,6 +883,9 @@ def run_head_video(engine, pipeline, frames, boxes_per_frame=None, max_len=100, 
     ``overlay=True`` or ``dict(palette=, line_thickness=, region_thickness=)`` in the dict (it needs attention=; ValueError without, and with
     color): the frames are drawn with pipeline.draw_attention from the records' target tables -- region outlines, sight lines, arrows
     coloured by their target -- instead of draw_arrows.
+    ``labels=True`` or ``dict(scale=, advance=, pad=, background=, fps=(num, den))`` in the dict: every head gets '#<id>' above its box --
+    the record's id (its number where no tracker gave one), with dwell= followed by the seconds of its per-frame dwell_frames at fps --
+    through pipeline.draw_labels, after the arrows, in their colour.
     detections: in place of boxes_per_frame (exactly one of the two is given) a dict(pred=..., in_shape=..., **options): the head detector's
     raw prediction [T, N, 5 + nc] for the T frames, on the host or the device, the (h, w) of its letterboxed input, and options of
     pipeline.detect_heads (conf_thres, iou_thres, only_class, agnostic, max_nms, max_det).  The boxes come from DETECT_FRAMES frames per
@@ -998,6 +1001,9 @@ def run_head_video(engine, pipeline, frames, boxes_per_frame=None, max_len=100, 
         return out
     opts = {'copy': True, **({} if draw is True else dict(draw))}
     overlay = _overlay_options('run_head_video(draw=...)', opts.pop('overlay', None), True, attention)
+    labels = _label_options('run_head_video(draw=...)', opts.pop('labels', None), True)
+    if labels is not None and labels.pop('region_names') is not None:
+        raise ValueError('run_head_video(draw=...): labels takes no region_names here; draw them with attention.region_label_rows and draw_labels')
     if overlay is not None and opts.get('color') is not None:
         raise ValueError('run_head_video(draw=...): with overlay the colours are the palette\'s, not color')
     if overlay is not None and rgb and pixel_format == 'bgr':
@@ -1005,10 +1011,13 @@ def run_head_video(engine, pipeline, frames, boxes_per_frame=None, max_len=100, 
     elif rgb and pixel_format == 'bgr':                # the frames hold R, G, B: the colour goes in in their order
         opts['color'] = np.asarray(ARROW_COLOR if opts.get('color') is None else opts['color'])[..., ::-1]
     rows = [[] for _ in boxes_per_frame]               # frame -> (box, gaze) of its heads, in record order
-    for r in out:
+    named = [[] for _ in boxes_per_frame]              # frame -> (id, dwell_frames) of its heads, for labels
+    for number, r in enumerate(out):
         g = r['fused' if smooth is None else 'fused_smooth']
+        ident = r['id'] if isinstance(r['id'], (int, np.integer)) else number + 1      # (without a tracker a record's id is a pair: its number)
         for j, t in enumerate(r['frame_id']):
             rows[t].append((r['head_box'][j], g[j, :2]) + (() if overlay is None else (r['target_kind'][j], r['target_region'][j], r['target_hit'][j], r['mutual'][j])))
+            named[t].append((int(ident), int(r['dwell_frames'][j]) if dwell is not None else 0))
     if opts.get('color') is not None and np.ndim(opts['color']) == 2:
         raise ValueError('run_head_video(draw=...): color is one (B, G, R) triple')
     annotated = []
@@ -1025,6 +1034,16 @@ def run_head_video(engine, pipeline, frames, boxes_per_frame=None, max_len=100, 
             imgs = pipeline.draw_attention(images, boxes, gaze, image_of, np.asarray(kind, np.int32), np.asarray(target, np.int32),
                                            np.asarray(hit, np.float32).reshape(-1, 2), np.asarray(mutual, np.int32), regions=attention[0],
                                            region_image=attention[1], pixel_format=pixel_format, matrix=matrix, device=engine.device, **opts, **overlay)[0]
+        if labels is not None and len(boxes):           # into the frames just drawn, in place: the id, with dwell the seconds of dwell_frames
+            ids, values = (np.asarray([h[i] for heads in named[t0:t0 + len(part)] for h in heads], dtype=np.int32) for i in (0, 1))
+            text = format_labels_host(ids, values if dwell is not None else None, labels['fps'])
+            if overlay is None:
+                colors = dict(color=opts.get('color'))
+            else:
+                pal = np.asarray(OVERLAY_PALETTE if overlay.get('palette') is None else overlay['palette'])
+                colors = dict(colors=pal[[4 if m else k if 1 <= k <= 3 else 0 for k, m in zip(kind, mutual)]].astype(np.uint8))
+            imgs, _ = pipeline.draw_labels(imgs, boxes, image_of, text, pixel_format=pixel_format, matrix=matrix, device=engine.device, **colors,
+                                           **{k: v for k, v in labels.items() if k != 'fps'})
         annotated += imgs
     return out, annotated
 

@@ -39,7 +39,9 @@ EXPORTS = ['mcg_abi_version', 'mcg_build_id', 'mcg_last_error', 'mcg_device_info
            'mcg_detect_heads_workspace_bytes', 'mcg_detect_heads', 'mcg_letterbox_frames', 'mcg_letterbox_frames_nv12',
            'mcg_track_state_bytes', 'mcg_track_heads', 'mcg_track_heads_motion', 'mcg_live_slots', 'mcg_live_gate', 'mcg_live_lanes', 'mcg_live_gate_lanes',
            'mcg_deferred_pyramid_state', 'mcg_inner_block_neighbours', 'mcg_gaze_targets', 'mcg_gaze_dwell', 'mcg_gaze_targets_poly',
-           'mcg_pointwise_stream', 'mcg_pointwise_dyn', 'mcg_pointwise_pair', 'mcg_draw_attention', 'mcg_draw_attention_nv12']
+           'mcg_pointwise_stream', 'mcg_pointwise_dyn', 'mcg_pointwise_pair', 'mcg_draw_attention', 'mcg_draw_attention_nv12',
+           'mcg_format_labels', 'mcg_draw_labels', 'mcg_draw_labels_nv12']
+LABEL_CHARS = 24                                                 # MCG_LABEL_CHARS
 LETTERBOX_U8, LETTERBOX_F16, LETTERBOX_F32 = 0, 1, 2             # enum order of include/mcgaze_hip.h
 
 
@@ -106,6 +108,10 @@ class StrokeDesc(C.Structure):
     _fields_ = [('seg', C.c_int * 2 * 2 * 3), ('thickness', C.c_int), ('x0', C.c_int), ('y0', C.c_int), ('x1', C.c_int), ('y1', C.c_int),
                 ('image', C.c_int), ('flag', C.c_int), ('layer', C.c_int), ('count', C.c_int), ('color', C.c_uint), ('color_active', C.c_uint),
                 ('reserved', C.c_int)]
+
+
+class LabelDesc(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ('x', 'y', 'x0', 'y0', 'x1', 'y1', 'image', 'flag', 'len')] + [('color', C.c_uint), ('text', C.c_ubyte * LABEL_CHARS)]
 
 
 class McgError(RuntimeError):
@@ -196,6 +202,9 @@ def load():
     lib.mcg_draw_attention.argtypes = [vp, vp, i, i, i, vp, vp, i, vp, i, vp, vp, vp, vp, vp, i, vp, vp, i, i, u8p, C.c_double, i, C.c_double, C.c_double,
                                        i, i, vp, sz, vp, vp, vp]
     lib.mcg_draw_attention_nv12.argtypes = lib.mcg_draw_attention.argtypes
+    lib.mcg_format_labels.argtypes = [vp, vp, vp, i, i, i, vp]
+    lib.mcg_draw_labels.argtypes = [vp, vp, i, i, i, vp, vp, vp, vp, i, vp, i, i, i, u8p, vp, u8p, vp, vp]
+    lib.mcg_draw_labels_nv12.argtypes = lib.mcg_draw_labels.argtypes
     lib.mcg_gaze_dwell.argtypes =[vp, vp, vp, vp, vp, vp, i, i, i, i, i, vp, vp, i, vp, vp, vp, i, vp]
     lib.mcg_engine_set_option.argtypes = [vp, C.c_char_p, i]
     lib.mcg_engine_profile_start.argtypes = [vp, i]

@@ -30,8 +30,8 @@ import numpy as np
 import torch
 
 from . import lib as L
-from .arrows import _overlay_options
-from .attention import KIND_HEAD, PolyRegions, _attention_options, _dwell_options
+from .arrows import LABEL_CHARS, _label_background, _label_options, _overlay_options, _overlay_palette
+from .attention import KIND_HEAD, PolyRegions, _attention_options, _dwell_options, region_label_rows
 from .engine import _upload_table
 from .harness import _host, check_smooth
 from .head_detect import TRACK_HEADER_WORDS, TRACK_MAX_SLOTS, TRACK_SLOT_WORDS, _track_motion, _track_params, track_state_words
@@ -339,6 +339,13 @@ class LiveGaze:
     without) draws the frames with pipeline.draw_attention instead of draw_arrows, from the gated tables and the per-camera regions: region
     outlines (lit where somebody looks at them), sight lines to the hit points, arrows coloured by their target.  Every table comes back as
     without it, and the tick still never waits for the device.
+    LABELS.  ``labels=True`` or ``dict(scale=2, advance=6, pad=1, background=(0, 0, 0), fps=(30, 1), region_names=None)`` (it needs ``draw``;
+    ValueError without) writes words into the returned frames after the arrows or the overlay: per returned frame one pipeline.format_labels
+    call makes '#<track_id>' for every valid row -- with ``dwell`` followed by the seconds of dwell_frames at fps = (num, den) -- into the tail
+    of one preallocated text table, and one pipeline.draw_labels call draws it above the head boxes, in the arrow's colour (with ``overlay``
+    in palette[4 if mutual else kind], gathered on the device).  region_names: one list of names per camera, a name (or None) per region of
+    that camera's ``attention`` regions (ValueError without them); they are drawn inside the regions' top-left corners in palette[5], in front
+    of the row labels in the tables, so head labels win.  Every other table comes back as without it; still no wait for the device.
     DWELL.  ``dwell=None`` is everything above.  ``dwell=True`` or ``dict(enter=3, exit=2)`` (it needs ``attention``; ValueError without) adds how
     LONG every row has looked at its target (pipeline.gaze_dwell, mcg_gaze_dwell: one call per tick that returns frames, over the k frames
     handed out, frame0 = first).  A column is a slot or a lane; its owner is person = track_id where valid, else 0, with lanes tagged by the
@@ -353,7 +360,7 @@ class LiveGaze:
 
     def __init__(self, engine_or_model, pipeline, cameras, slots=16, clip_len=7, stride=4, expand=0.8, match_iou=0.3, max_age=5, smooth=None,
                  pixel_format='bgr', draw=False, matrix='bt601', rgb=False, person_threshold=0.5, max_decode_windows=None, lanes=None, motion=None,
-                 attention=None, dwell=None, overlay=None):
+                 attention=None, dwell=None, overlay=None, labels=None):
         self.S, self.match_iou, self.max_age = _track_params(slots, match_iou, max_age)
         _track_motion(motion, 'LiveGaze')
         self.motion = motion
@@ -366,6 +373,7 @@ class LiveGaze:
         attention = _attention_options('LiveGaze', attention, self.Q)
         self.dwell = _dwell_options('LiveGaze', dwell, attention)
         self.overlay = _overlay_options('LiveGaze', overlay, draw, attention)
+        self.labels = _label_options('LiveGaze', labels, draw)
         self.pipe, self.expand, self.draw = pipeline, float(expand), bool(draw)
         self.frame_options = dict(pixel_format=pixel_format, matrix=matrix)
         self.rgb = bool(rgb)
@@ -397,6 +405,51 @@ class LiveGaze:
             self.attention = dict(options, regions=regions, region_image=up(region_image))
         if self.dwell is not None:
             self.dwell_state, self.region_frames = pipeline.dwell_state(n, device=self.dev), new(len(attention[1]))
+        if self.labels is not None:
+            self._label_tables(attention, n, matrix)
+
+    def _label_tables(self, attention, n, matrix):
+        """labels=: the tables of the one draw_labels call per returned frame, allocated once -- the rows of the named regions of the Q
+        pictures of a frame in front (built here, on the host, once), the n row labels behind them, so that head labels win an overlap."""
+        names = self.labels.pop('region_names')
+        boxes, image_of, text = np.zeros((0, 4), np.float32), np.zeros(0, np.int32), np.zeros((0, LABEL_CHARS), np.uint8)
+        if names is not None:
+            if attention is None:
+                raise ValueError('LiveGaze: region_names names the regions of attention: it needs attention with regions')
+            if len(names) != self.Q or any(not isinstance(c, (list, tuple, type(None))) for c in names):
+                raise ValueError(f'LiveGaze: region_names is one list of names per camera ({self.Q}), a name per region of that camera; got {names!r}')
+            boxes, image_of, text, _ = region_label_rows(attention[0], attention[1], [s for c in names for s in (c or ())], self.Q, region_period=self.Q)
+        r = self.label_regions = len(boxes)
+        nv12 = self.frame_options['pixel_format'] == 'nv12'
+        up = lambda t: torch.from_numpy(np.ascontiguousarray(t)).to(self.dev)
+        palette = _overlay_palette('LiveGaze', None if self.overlay is None else self.overlay.get('palette'), nv12, matrix)
+        self.label_palette = up(palette)                          # in the frames' own format: a device colour table is read as it is
+        self.label_boxes = up(np.concatenate([boxes, np.zeros((n, 4), np.float32)]))
+        self.label_image_of = up(np.concatenate([image_of, np.full(n, -1, np.int32)]))
+        self.label_text = up(np.concatenate([text, np.zeros((n, LABEL_CHARS), np.uint8)]))
+        # region names in the outline's colour, row labels in the arrow's (with overlay: gathered per row, every frame)
+        self.label_colors = up(np.concatenate([np.tile(palette[5], (r, 1)), np.tile(palette[0], (n, 1))]).astype(np.uint8))
+        # a HOST table: with it the frame table of the fresh frames travels pinned through the staging ring, not as a pageable upload
+        self.label_place = np.concatenate([np.ones(r, np.int32), np.zeros(n, np.int32)])
+        _label_background(self.labels['background'], nv12, matrix)
+
+    def _draw_labels(self, out, images, i):
+        """labels=: the words of returned frame i into its Q drawn frames -- one format_labels call into the tail of the text buffer, one
+        draw_labels call."""
+        r, Q = self.label_regions, self.Q
+        fps, options = self.labels['fps'], {k: v for k, v in self.labels.items() if k != 'fps'}
+        ids = torch.where(out['valid'][i] != 0, out['track_id'][i], torch.zeros_like(out['track_id'][i])).reshape(-1)
+        values = out['dwell_frames'][i].reshape(-1) if self.dwell is not None else None
+        self.pipe.format_labels(ids, values, rate=fps, out=self.label_text[r:], device=self.dev)
+        self.label_boxes[r:].copy_(out['head_box'][i].reshape(-1, 4))
+        image_of = out['image_of'][i].reshape(-1)
+        self.label_image_of[r:].copy_(torch.where(image_of >= 0, image_of - i * Q, image_of))
+        if self.overlay is not None:
+            kind, mutual = out['target_kind'][i].reshape(-1), out['mutual'][i].reshape(-1)
+            index = torch.where(mutual != 0, torch.full_like(kind, 4), torch.where((kind >= 1) & (kind <= 3), kind, torch.zeros_like(kind)))
+            self.label_colors[r:].copy_(self.label_palette[index.long()])
+        self.pipe.draw_labels(images[i * Q:(i + 1) * Q], self.label_boxes, self.label_image_of, self.label_text, colors=self.label_colors,
+                              place=self.label_place, device=self.dev, **self.frame_options, **options)
 
     def _call(self, name, *args):
         """One entry of the library on the current stream: a tensor goes as its address, None as a null pointer, an int as it is."""
@@ -535,6 +588,8 @@ class LiveGaze:
                                                      out['mutual'].view(-1), regions=self.attention['regions'], region_image=self.attention['region_image'],
                                                      region_period=self.Q, copy=True, device=self.dev, **self.frame_options, **self.overlay)[0]
                 images = list(drawn)
+                for i in range(k if self.labels is not None else 0):
+                    self._draw_labels(out, images, i)             # in place, into the copies just drawn
             out['frames'] = [images[i * Q:(i + 1) * Q] for i in range(k)]
         self.emitted += k
         return out

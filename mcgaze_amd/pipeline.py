@@ -24,8 +24,8 @@ What the device calls of ``DevicePipeline`` share is stated once, and a further 
 ``_call_scope`` (staging.py: the device, the caller's stream, the one upload, the mark on the stage it took); ``_row_tables`` checks the rows
 of head_crops and the two drawing calls; ``_on_device`` / ``_there`` decide where a table lives and move a host table that stands next to a
 device one; ``_gaze_operand`` is the gaze table with its row stride; ``_region_operands`` decides the region tables of gaze_targets and
-draw_attention as a group; ``_drawing_checked``, ``_drawing_placed`` and ``_drawing_upload`` are, in the order of a call, what draw_arrows
-and draw_attention do to frames and rows; and ``_device_table`` keeps the record tables of device frames on the device.
+draw_attention as a group; ``_drawing_checked``, ``_drawing_placed`` and ``_drawing_upload`` are, in the order of a call, what draw_arrows,
+draw_attention and draw_labels do to frames and rows; and ``_device_table`` keeps the record tables of device frames on the device.
 
 Randomness: the reference's ``CenterCrop(crop_type='relative_range')`` draws the crop size from the global numpy RNG at TEST
 time too (transforms.py:1126-1130), and ``RandomFlip(flip_ratio=0.0)`` consumes one more uniform
@@ -44,6 +44,8 @@ from .arrows import (OVERLAY_PALETTE, _overlay_counts, _overlay_palette, _overla
                      draw_attention_host)
 from .arrows import (ARROW_COLOR, ARROW_COORD, ARROW_SIDE, _arrow_colors, _arrow_params, _arrow_rows,  # noqa: F401
                      arrow_segments, draw_arrows_host, segment_coverage)
+from .arrows import LABEL_CHARS, LABEL_FONT, _label_background, _label_ints, _label_params, _label_rate, _label_text, label_plan
+from .arrows import draw_labels_host, encode_labels, format_labels_host  # noqa: F401  (re-exported beside draw_arrows_host, for users of pipeline.*)
 from .attention import PolyRegions, _check_counts, _holds_polygon, _poly_tables, _region_tables, _target_params, gaze_targets_host, region_polygons  # noqa: F401
 from .attention import _row_tables as _target_rows
 from .attention import DWELL_ENTER, DWELL_EXIT, _dwell_counts, _dwell_params, _dwell_tables, gaze_dwell_host  # noqa: F401
@@ -283,6 +285,9 @@ _CROP_WORD = _DESC.fields['crop_y'][1] // 4         # crop_y, crop_x, crop_h, cr
 _ARROW = np.dtype([('seg', np.int32, (3, 2, 2)), ('thickness', np.int32)] + [(f, np.int32) for f in ('x0', 'y0', 'x1', 'y1', 'image', 'flag', 'reserved')])
 assert _ARROW.itemsize == C.sizeof(L.ArrowDesc) and all(_ARROW.fields[n][1] == getattr(L.ArrowDesc, n).offset for n in _ARROW.names)
 _ARROW_WORDS = _ARROW.itemsize // 4
+_LABEL = np.dtype([(f, np.int32) for f in ('x', 'y', 'x0', 'y0', 'x1', 'y1', 'image', 'flag', 'len')] + [('color', np.uint32), ('text', np.uint8, (LABEL_CHARS,))])
+assert _LABEL.itemsize == C.sizeof(L.LabelDesc) == 64 and all(_LABEL.fields[n][1] == getattr(L.LabelDesc, n).offset for n in _LABEL.names)
+_LABEL_WORDS = _LABEL.itemsize // 4
 
 
 class _NoDraw:
@@ -558,6 +563,7 @@ class DevicePipeline:
         self._image_tables = collections.OrderedDict()            # head_crops, draw_arrows, letterbox: (device, table bytes) -> that table on the device
         self._frame_hw_tables = collections.OrderedDict()         # detect_heads: (device, host frame_hw bytes) -> that table on the device
         self._detect_workspaces = collections.OrderedDict()       # detect_heads: (device, B, N) -> scratch of mcg_detect_heads
+        self._label_fonts = {}                                    # draw_labels: device -> LABEL_FONT on it
 
     def _kept(self, cache, key, make):
         """cache[key], made the first time it is asked for; the least recently used of IMAGE_TABLES entries goes."""
@@ -872,6 +878,97 @@ class DevicePipeline:
                               line_thickness, region_thickness, vp(work.data_ptr()), 4 * work.numel(), vp(flags.data_ptr()),
                               vp(region_flags.data_ptr()), vp(region_active.data_ptr())), entry.__name__)
         return out, flags, region_flags, region_active
+
+    def format_labels(self, ids, values=None, rate=(30, 1), out=None, device='cuda:0', stream=None):
+        """The text of one label per row, made on the device (mcg_format_labels, one launch) -- ``format_labels_host`` bit for bit: '#' and the
+        id, and with ``values`` (frames, e.g. gaze_dwell's dwell_frames) the seconds they last at rate = (num, den) frames per second, in
+        tenths: '#12 3.4s'.  A row whose id is <= 0 is empty, and draw_labels draws nothing for it.
+        ids, values [n] integers: numpy arrays (checked: TypeError / ValueError) or device tensors, which are never read back.  out: a device
+        uint8 [n, 24] tensor to write into (a slice of a larger text table), else a new one.  -> the text table uint8 [n, 24] on the device."""
+        lib = L.load()
+        num, den = _label_rate(rate)
+        dev = _device(device, 'mcg_format_labels')
+        tables = [None if t is None else t if _on_device(t) else _label_ints(name, t) for name, t in (('ids', ids), ('values', values))]
+        n = int(tables[0].shape[0])
+        if tables[0].ndim != 1 or (tables[1] is not None and tuple(tables[1].shape) != (n,)) or n > 65535:
+            raise ValueError(f'format_labels: ids and values must be [n], n <= 65535; got {tuple(tables[0].shape)} and {None if tables[1] is None else tuple(tables[1].shape)}')
+        if out is not None and not (_on_device(out) and out.device == dev and out.dtype == torch.uint8 and tuple(out.shape) == (n, LABEL_CHARS) and out.is_contiguous()):
+            raise ValueError(f'format_labels: out must be a contiguous uint8 [{n}, {LABEL_CHARS}] tensor on {dev}')
+        with _call_scope(self._ring, dev, stream) as call:
+            tables = [t if t is None or isinstance(t, np.ndarray) else t.to(dev, torch.int32).contiguous() for t in tables]
+            _, (ids_ptr, values_ptr) = call.upload([], tables)
+            text = torch.empty(n, LABEL_CHARS, dtype=torch.uint8, device=dev) if out is None else out
+            if n:
+                vp = C.c_void_p
+                L.check(lib.mcg_format_labels(vp(call.main.cuda_stream), vp(ids_ptr), vp(values_ptr), n, num, den, vp(text.data_ptr())), 'mcg_format_labels')
+        return text
+
+    def draw_labels(self, images, boxes, image_of, text, colors=None, color=None, background=(0, 0, 0), scale=2, advance=6, pad=1, place=None,
+                    pixel_format='bgr', matrix='bt601', copy=False, device='cuda:0', stream=None):
+        """Words in the frames, on the device (mcg_draw_labels / mcg_draw_labels_nv12: a plan launch and a gather launch) --
+        ``arrows.draw_labels_host`` bit for bit: the text of row k (``encode_labels``, ``format_labels``) on a plate of ``background`` above
+        the row's box -- below it where there is no room above, inside its top-left corner with place[k] == 1 -- moved inside the frame.
+
+        images, pixel_format, matrix, copy: ``draw_arrows``' -- a CUDA frame is drawn IN PLACE (copy=True: into a packed clone), a numpy frame
+        goes up through the staging ring.  boxes [n,4], image_of [n], text uint8 [n,24], place [n] or None, colors [n,3] or None: numpy arrays
+        or device tensors.  color: one (B, G, R) triple on the host (None: the arrows' (230, 253, 11)), used where ``colors`` is None; host
+        colours are converted once by ``bgr_to_yuv`` for NV12, DEVICE colours are read as they are: (Y, U, V) for NV12.  background: one
+        triple, or None for no plates.  scale 1 .. 16 pixels per font bit, advance 1 .. 8 font columns per character, pad 0 .. 8 font bits
+        around the text.  The font is ``arrows.LABEL_FONT``, uploaded once per device and kept.  Later rows cover earlier ones.
+        Host tables are checked before anything is launched (TypeError / ValueError: an image_of out of range, a box that is not finite or
+        beyond +-8191); device tables are never read back -- such rows come back with flag 2 and write nothing.  With device frames drawn in
+        place, device tables and the frame table cached by a first call, the call touches the host nowhere and can be captured in a graph.
+        -> (images on the device, in order; flags [n] int32 on the device: 0 drawn, 1 an empty label, 2 unusable)."""
+        lib = L.load()
+        who = 'draw_labels'
+        nv12, _ = _pixel_format(pixel_format, matrix)
+        scale, advance, pad = _label_params(scale, advance, pad)
+        bg = _label_background(background, nv12, matrix)
+        entry = lib.mcg_draw_labels_nv12 if nv12 else lib.mcg_draw_labels
+        checked = _drawing_checked(who, 'labels', entry, images, boxes, None, image_of, nv12, device)
+        dev, n = checked[0], checked[-1]
+        one = _arrow_colors(color, 0, nv12, matrix)[0]
+        if one is None:
+            raise ValueError(f'{who}: color must be one (B, G, R) triple; one per row goes in colors')
+        if not _on_device(text):
+            text = _label_text(text, n)
+        if place is not None and not _on_device(place):
+            place = _label_ints('place', place, n)
+        if colors is not None and not _on_device(colors):
+            colors = _arrow_colors(colors, n, nv12, matrix)[1]
+            if colors is None:
+                raise ValueError(f'{who}: colors must be one (B, G, R) triple per row, [{n}, 3]')
+        with _call_scope(self._ring, dev, stream) as call:
+            out, pixels, in_place, table, h_max, w_max, boxes, _, _, image_of = _drawing_placed(who, checked, nv12, copy, None, 0)
+            if isinstance(boxes, np.ndarray) and n:
+                if isinstance(image_of, np.ndarray):              # the whole plan, against each row's own frame
+                    bad = label_plan(boxes, image_of, np.ones((n, LABEL_CHARS), np.uint8), [(int(r['h']), int(r['w'])) for r in table], None, scale,
+                                     advance, pad, nv12)['flag'] == 2
+                else:                                             # image_of is on the device and is not read back: what does not depend on the frame
+                    bad = (np.abs(np.trunc(boxes.astype(np.float64))) > ARROW_COORD).any(axis=1)
+                if bad.any():
+                    k = int(np.flatnonzero(bad)[0])
+                    raise ValueError(f'{who}: label {k} cannot be drawn: box {boxes[k].tolist()} -- a coordinate beyond +-{ARROW_COORD}, or a frame without pixels')
+            moved = []
+            for name, t, dtype, shape in (('text', text, torch.uint8, (n, LABEL_CHARS)), ('place', place, torch.int32, (n,)), ('colors', colors, torch.uint8, (n, 3))):
+                if isinstance(t, torch.Tensor):
+                    t = t.to(dev, dtype).contiguous()
+                    if tuple(t.shape) != shape:
+                        raise ValueError(f'{who}: {name} must be {list(shape)}, got {tuple(t.shape)}')
+                moved.append(t)
+            images_ptr, boxes_ptr, image_of_ptr, text_ptr, place_ptr, colors_ptr = self._drawing_upload(call, nv12, table, pixels, in_place,
+                                                                                                         (boxes, image_of, *moved))
+            font = self._label_fonts.get(dev.index)
+            if font is None:                                      # the font is data the pipeline brings: uploaded once per device and kept
+                font = self._label_fonts[dev.index] = torch.from_numpy(LABEL_FONT.reshape(-1).copy()).to(dev)
+            flags = torch.empty(n, dtype=torch.int32, device=dev)
+            if n:
+                plan = torch.empty(n, _LABEL_WORDS, dtype=torch.int32, device=dev)
+                vp, u8 = C.c_void_p, lambda c: None if c is None else (C.c_ubyte * 3)(*[int(v) for v in c])
+                L.check(entry(vp(call.main.cuda_stream), vp(images_ptr), len(out), h_max, w_max, vp(boxes_ptr), vp(image_of_ptr), vp(text_ptr),
+                              vp(place_ptr), n, vp(font.data_ptr()), scale, advance, pad, u8(one), vp(colors_ptr), u8(bg), vp(plan.data_ptr()),
+                              vp(flags.data_ptr())), entry.__name__)
+        return out, flags
 
     def gaze_targets(self, boxes, gaze, image_of, regions=None, region_image=None, region_period=0, expand=0.25, camera_angle=10.0, device='cuda:0',
                      stream=None):

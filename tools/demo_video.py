@@ -3,7 +3,7 @@
 label files in, per-person per-frame gaze out -- and, with --draw, the frames with cell 5's arrows drawn on the device.
 
 usage: demo_video.py FRAMES_DIR LABELS_DIR CONFIG CHECKPOINT --out gaze.json [--precision f16x3] [--device cuda:0] [--max-len 100]
-                     [--batch-frames 448] [--head-class 1] [--ext jpg] [--smooth ALPHA] [--nv12 WxH FILE] [--matrix bt601] [--draw OUT] [--overlay]
+                     [--batch-frames 448] [--head-class 1] [--ext jpg] [--smooth ALPHA] [--nv12 WxH FILE] [--matrix bt601] [--draw OUT] [--overlay] [--labels [SCALE]] [--fps NUM[/DEN]]
                      [--track [--slots 16] [--match-iou 0.3] [--max-age 5]] [--track-motion [GAIN[,DECAY]]]
                      [--color B,G,R] [--predictions DIR --in-shape HxW [--conf-thres 0.25] [--iou-thres 0.45]]
                      [--detector MODULE:FACTORY [--img-size 640] [--half]] [--attention [--regions FILE.json] [--dwell [ENTER,EXIT]]]
@@ -166,6 +166,9 @@ def main(argv=None):
     ap.add_argument('--color', default=None, metavar='B,G,R', help='colour of the arrows of --draw')
     ap.add_argument('--overlay', action='store_true', help='--draw with --attention: region outlines, sight lines and arrows coloured by their target '
                                                              '(pipeline.draw_attention) instead of the plain arrows')
+    ap.add_argument('--labels', nargs='?', const=2, type=int, default=None, metavar='SCALE',
+                    help='--draw: write every person\'s id -- with --dwell the seconds they have looked at their target -- next to the head, SCALE pixels per font bit')
+    ap.add_argument('--fps', default=None, metavar='NUM[/DEN]', help='frames per second of the video, for the seconds of --labels (30)')
     ap.add_argument('--predictions', default=None, metavar='DIR', help='raw detector output, <t>.npy per frame, instead of LABELS_DIR (then -)')
     ap.add_argument('--in-shape', default=None, metavar='HxW', help='the letterboxed input of the detector behind --predictions')
     ap.add_argument('--conf-thres', type=float, default=0.25)
@@ -217,6 +220,17 @@ def main(argv=None):
         if a.draw is None or not a.attention or a.color is not None:
             raise SystemExit('--overlay belongs to --draw and --attention, and its colours are the palette\'s (no --color)')
         draw['overlay'] = True
+    if a.labels is not None or a.fps is not None:
+        if a.draw is None:
+            raise SystemExit('--labels and --fps belong to --draw')
+        labels = {} if a.labels is None else dict(scale=a.labels)
+        if a.fps is not None:
+            try:
+                num, _, den = a.fps.partition('/')
+                labels['fps'] = (int(num), int(den or 1))
+            except ValueError:
+                raise SystemExit(f'--fps takes NUM or NUM/DEN, got {a.fps!r}')
+        draw['labels'] = labels or True
     if a.nv12 is not None:
         frames = Nv12File(a.nv12[1], *parse_size(a.nv12[0]))
         n = len(frames)
