@@ -1266,6 +1266,70 @@ int mcg_draw_labels_nv12(mcg_stream s, const mcg_nv12_image_desc* images_dev, in
                          int scale, int advance, int pad, const unsigned char* yuv, const unsigned char* yuvs_dev, const unsigned char* background,
                          mcg_label_desc* plan_out_dev, int32_t* flags_dev);
 
+/* ---------------------------------------------------------------- gaze heat map (additions to ABI 19; nothing above changes)
+ * Where in the picture looks have landed, over the calls so far: `hit` of "gaze targets" accumulated into a grid of cells per camera
+ * (mcg_gaze_heat_add) and that grid blended, colour-mapped, into packed BGR frames (mcg_draw_heat) or NV12 surfaces (mcg_draw_heat_nv12)
+ * IN PLACE.  Every table is in device memory.  Behind the first rounding of `hit` everything is integer arithmetic; >> is an arithmetic
+ * shift (a floor), / a floor of non-negative integers.
+ * GRID.  heat is int32 [C][GH][GW], one grid per camera, a cell 2^cell_shift pixels square (cell_shift 0 .. 6); the caller keeps it between
+ * calls.  A negative value found in it is read as 0, by both entries.
+ * 1. ACCUMULATE, mcg_gaze_heat_add.  THE ROW RULE: row k counts iff ALL of
+ *   flags_dev is NULL or flags[k] == 0;  mask_dev is NULL or mask[k] != 0;
+ *   0 <= kind[k] <= 3 and bit kind[k] of `kinds` is set;
+ *   image_of[k] >= 0, and with c = image_of[k] where period == 0, else image_of[k] % period:  c < C;
+ *   hx = rint((double)hit[k][0]), hy = rint((double)hit[k][1]) (half to even) are finite and in [-8191, 8191] -- the sight line's test of
+ *   "attention overlay".
+ * Any other row is skipped: what the tables hold is never an error.
+ * THE SPLAT.  The row's cell is (ix, iy) = (hx >> cell_shift, hy >> cell_shift).  For every |dx| <= radius, |dy| <= radius it adds
+ * w = (radius + 1 - |dx|) * (radius + 1 - |dy|) to cell (ix + dx, iy + dy) of camera c; a tap outside [0, GW) x [0, GH) is dropped, so a
+ * hit outside the picture still lights the edge cells within its radius.
+ * THE UPDATE, per cell, once per CALL:  h = max(heat, 0);  if decay_shift > 0, h -= h >> decay_shift (before anything is added);
+ * heat = min((int64)h + the sum of the cell's taps, 2^31 - 1).  peak[c] = the maximum of camera c's updated cells (0 for a grid of zeros).
+ * SHAPE.  Three launches: the workspace and peak cleared; a SCATTER, one thread per (row, tap row), with integer vector atomics into the
+ * workspace; a per-cell pass that decays, adds, saturates and takes the camera's maximum with an integer atomic max.  Integer sums and
+ * maxima commute, so the result is a function of the inputs alone, whatever the launch geometry.  (A gather per cell tile would read all n
+ * rows in every tile of up to 2^24 cells for splats that touch at most 289 cells each: the scatter's work is n * (2 radius + 1)^2.)  One
+ * call's taps sum to at most 65536 * 81 < 2^23 per cell: the workspace cannot overflow.
+ *   hit_dev DEVICE f32 [n][2];  kind_dev, image_of_dev DEVICE int32 [n] (the three may be NULL iff n == 0);  flags_dev, mask_dev DEVICE int32 [n] or NULL
+ *   heat_dev DEVICE int32 [C][GH][GW], read and written;  peak_dev DEVICE int32 [C], written
+ *   radius 0 .. 8 (cells);  kinds: bits 0 .. 3 are read;  period >= 0;  decay_shift 0 .. 30, 0: off
+ *   workspace_dev DEVICE, workspace_bytes >= 4 * C * GH * GW; what it holds on entry does not matter
+ * n <= 65536, 1 <= C <= 4096, 1 <= GH, GW <= 8192, C * GH * GW <= 2^24: anything else, a null required table or a workspace too small
+ * returns MCG_ERR_ARG before any launch.  With n == 0 the call still decays and writes peak.  A fixed number of launches, no allocation, no
+ * host sync, graph-capturable.  mcgaze_amd/attention.py::gaze_heat_host is the same on the host, bit for bit.
+ * 2. RENDER, mcg_draw_heat / mcg_draw_heat_nv12, over the image table of mcg_draw_gaze_arrows.  Picture p shows camera c = p where
+ * period == 0, else p % period.  A picture is left untouched, byte for byte, if c >= C, if it is not writable (no pixels; NV12: an odd
+ * size), or if it is larger than (max_h, max_w).
+ * LEVEL of pixel (px, py), with S = 2^cell_shift -- an interpolation between cell centres:
+ *   u = 2 px + 1 - S;  i0 = u >> (cell_shift + 1);  fx = u - i0 * 2 S (in [0, 2 S));  i1 = i0 + 1;  both clamped to [0, GW - 1]
+ *   the same in y: j0, fy, j1, clamped to [0, GH - 1];  hab = max(heat[c][ja][ib], 0)
+ *   v = (2 S - fx) (2 S - fy) h00 + fx (2 S - fy) h01 + (2 S - fx) fy h10 + fx fy h11      (int64; v < 2^45)
+ *   full = max(full_dev[c], 1);  L = min(255, (v * 255) / (4 S S full))                    (int64; the product is below 2^53)
+ * At cell_shift == 0 this is the cell's own value; a grid smaller than the picture repeats its edge cells, so every pixel has a level.
+ * full_dev is the peak table of mcg_gaze_heat_add, or the caller's own fixed scale.
+ * COLOUR.  lut_dev is a DEVICE uint8 [256][4] table, 4-byte aligned, the ramp as DATA: entry L is (B, G, R, alpha), for NV12 (Y, U, V,
+ * alpha).  A BGR pixel with L >= min_level becomes (src * (255 - a) + col * a + 127) / 255 per channel with a = lut[L][3]; a pixel with
+ * L < min_level keeps its bytes.  NV12: every luma pixel is blended like that with the Y of ITS level; a chroma pair takes Lc, the maximum
+ * of its four luma pixels' levels, and is blended with the (U, V, alpha) of lut[Lc] iff Lc >= min_level, that is, iff any of the four is
+ * -- the rule of "annotated frames out".
+ *   images_dev, num_images, max_h, max_w: as mcg_draw_gaze_arrows takes them
+ *   heat_dev DEVICE int32 [C][GH][GW], full_dev DEVICE int32 [C] (both read);  min_level 1 .. 255
+ * ONE launch over (image, tile of 256 x 16 pixels; NV12: 256 x 32): a block keeps its tile's cells and one cell of apron, edge cells
+ * repeated, and the 256 colours in LDS; a thread owns 16 pixels of a row (NV12: 16 x 2 and their 8 chroma pairs), and reads and writes
+ * them in 16-byte accesses where the plane's address and pitch are multiples of 16, in 4-byte accesses where they are multiples of 4, byte
+ * by byte at the right edge and for any other pitch.  A tile over nothing but zero cells reads no pixel.  No allocation, no host sync, no
+ * atomics, graph-capturable.  The limits of the grid above, num_images in 1 .. 65535, frames of at most 8192 a side: anything else or a
+ * null table returns MCG_ERR_ARG before the launch.  No byte outside [0, h) x [0, w) of any plane is touched, padding included, for ANY
+ * table contents.  mcgaze_amd/arrows.py::draw_heat_host is the same on the host, bit for bit.  Out of scope: per-person maps, perspective
+ * or depth, a decay per frame inside a multi-frame call, Gaussian kernels. */
+int mcg_gaze_heat_add(mcg_stream s, const float* hit_dev, const int32_t* kind_dev, const int32_t* image_of_dev, const int32_t* flags_dev,
+                      const int32_t* mask_dev, int n, int32_t* heat_dev, int32_t* peak_dev, int C, int GH, int GW, int cell_shift, int radius,
+                      int kinds, int period, int decay_shift, void* workspace_dev, size_t workspace_bytes);
+int mcg_draw_heat(mcg_stream s, const mcg_image_desc* images_dev, int num_images, int max_h, int max_w, const int32_t* heat_dev,
+                  const int32_t* full_dev, int C, int GH, int GW, int cell_shift, int period, const unsigned char* lut_dev, int min_level);
+int mcg_draw_heat_nv12(mcg_stream s, const mcg_nv12_image_desc* images_dev, int num_images, int max_h, int max_w, const int32_t* heat_dev,
+                       const int32_t* full_dev, int C, int GH, int GW, int cell_shift, int period, const unsigned char* lut_dev, int min_level);
+
 /* ---------------------------------------------------------------- measurement aids (bench.py)
  * While armed, every launch of the contraction kernel made by THIS engine is bracketed by a hipEvent pair on its launch stream.
  * mcg_engine_profile_stop synchronises, returns per-launch duration (ms), algorithmic FLOPs, algorithmic HBM bytes (inputs and

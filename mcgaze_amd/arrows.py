@@ -664,3 +664,110 @@ def draw_labels_host(frames, boxes, image_of, text, colors=None, color=None, bac
         else:
             out[p][winner >= 0] = stroke_color[winner[winner >= 0]]
     return (out[0] if single else out), flags
+
+
+# ---------------------------------------------------------------- gaze heat map (include/mcgaze_hip.h, "gaze heat map")
+def _heat_ramp():
+    """HEAT_LUT, made here by an integer formula: four stretches of 64 levels -- blue to cyan, to green, to yellow, to red -- with
+    f = (level % 64) * 255 // 63 the way along a stretch, and an alpha of (level * 160 + 127) // 255: 0 at level 0, 160 at level 255."""
+    lut = np.zeros((256, 4), dtype=np.uint8)
+    for level in range(256):
+        f = (level & 63) * 255 // 63
+        lut[level, :3] = ((255, f, 0), (255 - f, 255, 0), (0, 255, f), (0, 255 - f, 255))[level >> 6]      # B, G, R
+        lut[level, 3] = (level * 160 + 127) // 255
+    return lut
+
+
+HEAT_LUT = _heat_ramp()
+HEAT_LUT.flags.writeable = False                                 # uint8 [256][4]: (B, G, R, alpha) per level; a convention, not tuned
+_HEAT_LUTS = {}
+
+
+def heat_lut(lut=None, nv12=False, matrix='bt601'):
+    """The colour table as the entries take it -> uint8 [256, 4], contiguous.  lut: [256, 4] integers in [0, 255], (B, G, R, alpha) per
+    level (None: HEAT_LUT); ValueError for anything else.  With nv12 each entry's colour is converted once by bgr_to_yuv(., matrix), as
+    _overlay_palette does; the default ramp's conversion is kept per matrix and handed out READ-ONLY (as HEAT_LUT is): it is everybody's."""
+    if lut is None and (nv12, matrix) in _HEAT_LUTS:
+        return _HEAT_LUTS[nv12, matrix]
+    c = np.asarray(HEAT_LUT if lut is None else _host_array(lut))
+    if c.dtype.kind not in 'iu' or c.shape != (256, 4) or c.min() < 0 or c.max() > 255:
+        raise ValueError(f'the heat colour table must be [256, 4] (B, G, R, alpha) integers in [0, 255]; got {c.dtype} {c.shape}')
+    c = np.ascontiguousarray(c.astype(np.uint8))
+    if nv12:
+        uniq, inverse = np.unique(c[:, :3], axis=0, return_inverse=True)
+        c[:, :3] = np.stack([bgr_to_yuv(v, matrix) for v in uniq]).reshape(-1, 3)[inverse.reshape(-1)]
+    if lut is None:
+        c.flags.writeable = False
+        _HEAT_LUTS[nv12, matrix] = c
+    return c
+
+
+def heat_levels(grid, full, h, w, cell_shift):
+    """The LEVEL of every pixel of an h x w picture over one camera's grid int32 [GH, GW] ("gaze heat map"): the interpolation between cell
+    centres in 64-bit integers, edge cells repeated -> int64 [h, w] in 0 .. 255.  full: the scale; below 1 it is 1."""
+    grid = np.maximum(np.asarray(grid, dtype=np.int64), 0)
+    GH, GW = grid.shape
+    S = 1 << cell_shift
+
+    def axis(size, cells):
+        u = 2 * np.arange(size, dtype=np.int64) + 1 - S
+        i0 = u >> (cell_shift + 1)                                # arithmetic: floors
+        return np.clip(i0, 0, cells - 1), np.clip(i0 + 1, 0, cells - 1), u - i0 * 2 * S
+
+    y0, y1, fy = axis(h, GH)
+    x0, x1, fx = axis(w, GW)
+    fy, fx = fy[:, None], fx[None, :]
+    v = (2 * S - fx) * (2 * S - fy) * grid[y0][:, x0] + fx * (2 * S - fy) * grid[y0][:, x1] + (2 * S - fx) * fy * grid[y1][:, x0] + \
+        fx * fy * grid[y1][:, x1]
+    return np.minimum(255, (v * 255) // (4 * S * S * max(int(full), 1)))
+
+
+def _heat_blend(src, col, a):
+    """(src (255 - a) + col a + 127) / 255 in integers, elementwise -> uint8."""
+    return ((src.astype(np.int64) * (255 - a) + col * a + 127) // 255).astype(np.uint8)
+
+
+def draw_heat_host(frames, heat, full, cell_shift, period=0, lut=None, min_level=1, pixel_format='bgr', matrix='bt601'):
+    """The heat map blended into frames with numpy: what DevicePipeline.draw_heat (mcg_draw_heat / mcg_draw_heat_nv12) writes on the device,
+    bit for bit (include/mcgaze_hip.h, "gaze heat map": the level of a pixel, the blend, the NV12 chroma rule).
+
+    frames, pixel_format, matrix: as for draw_arrows_host.  heat: int32 [C, GH, GW] (gaze_heat_host); full: int [C], the scale of each
+    camera -- gaze_heat_host's peak -- or one int for all; cell_shift 0 .. 6; picture p shows camera p, with a period p % period, and is
+    left as it is where that camera is not below C.  lut: [256, 4] (B, G, R, alpha) per level (None: HEAT_LUT), converted once per entry for
+    NV12.  A pixel whose level is below min_level (1 .. 255) keeps its bytes.
+    -> annotated COPIES in the form given (NV12 frames as (y [H,W], uv [H/2,W]) pairs)."""
+    who = 'draw_heat_host'
+    nv12, _ = _pixel_format(pixel_format, matrix)
+    cell_shift, _, _, period, _ = A._heat_params(who, cell_shift, 0, 0, period, 0)
+    _, min_level = A._heat_scale(who, None, min_level)
+    table = heat_lut(lut, nv12, matrix).astype(np.int64)
+    heat = np.asarray(_host_array(heat))
+    C, GH, GW = A._heat_grid(who, heat.shape)
+    full = np.broadcast_to(np.asarray(_host_array(full), dtype=np.int64).reshape(-1), (C,)) if np.size(full) in (1, C) else None
+    if full is None:
+        raise ValueError(f'{who}: full is one int or one per camera, [{C}]')
+    single = not isinstance(frames, list)
+    frames = [frames] if single else frames
+    if nv12:
+        out = [tuple(np.array(p) for p in _nv12_planes(k, f)[:2]) for k, f in enumerate(frames)]
+        sizes = [y.shape for y, _ in out]
+    else:
+        out = [_bgr_frame(k, np.array(f)) for k, f in enumerate(frames)]
+        sizes = [a.shape[:2] for a in out]
+    for p, (h, w) in enumerate(sizes):
+        c = p % period if period else p
+        if c >= C or h > ARROW_SIDE or w > ARROW_SIDE:
+            continue
+        level = heat_levels(heat[c], full[c], h, w, cell_shift)
+        if nv12:
+            y, uv = out[p]
+            on = level >= min_level
+            y[on] = _heat_blend(y[on], table[level[on], 0], table[level[on], 3])
+            top = level.reshape(h // 2, 2, w // 2, 2).max(axis=(1, 3))    # the pair's level: the highest of its four luma pixels
+            on = top >= min_level
+            pairs = uv.reshape(h // 2, w // 2, 2)
+            pairs[on] = _heat_blend(pairs[on], table[top[on], 1:3], table[top[on], 3:4])
+        else:
+            on = level >= min_level
+            out[p][on] = _heat_blend(out[p][on], table[level[on], :3], table[level[on], 3:4])
+    return out[0] if single else out

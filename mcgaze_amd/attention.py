@@ -531,3 +531,156 @@ def region_label_rows(regions, region_image, names, num_images, region_period=0)
         boxes[k] = (v[:, 0].min(), v[:, 1].min(), v[:, 0].max(), v[:, 1].max())
     regs = np.array([j for _, j in rows], dtype=np.int64)
     return boxes, np.array([p for p, _ in rows], dtype=np.int32), text[regs].reshape(-1, R.LABEL_CHARS), np.ones(len(rows), dtype=np.int32)
+
+
+# ---------------------------------------------------------------- gaze heat map (include/mcgaze_hip.h, "gaze heat map")
+HeatState = collections.namedtuple('HeatState', 'heat peak cell_shift')   # heat int32 [C, GH, GW], peak int32 [C]; a cell is 2^cell_shift pixels square
+HEAT_KINDS = ('head', 'region')                                  # the rows that count by default: a look that lands on something in the picture
+HEAT_MAX_CAMERAS, HEAT_MAX_SIDE, HEAT_MAX_CELLS, HEAT_COORD = 4096, 8192, 1 << 24, 8191
+HEAT_MAX = 2 ** 31 - 1
+
+
+def _heat_cell(who, cell):
+    """``cell``, the side of a cell in pixels: a power of two in 1 .. 64 (ValueError) -> cell_shift."""
+    if isinstance(cell, bool) or not isinstance(cell, (int, np.integer)) or not 1 <= cell <= 64 or cell & (cell - 1):
+        raise ValueError(f'{who}: cell must be a power of two in 1 .. 64 (pixels a side), got {cell!r}')
+    return int(cell).bit_length() - 1
+
+
+def _heat_kinds(who, kinds):
+    """``kinds``: the bit mask the entry takes, or names out of KIND_NAMES (ValueError) -> the bit mask."""
+    if isinstance(kinds, (int, np.integer)) and not isinstance(kinds, bool):
+        if not 0 <= kinds <= 15:
+            raise ValueError(f'{who}: kinds as a bit mask is 0 .. 15, got {kinds!r}')
+        return int(kinds)
+    names = [kinds] if isinstance(kinds, str) else list(kinds)
+    if any(k not in KIND_NAMES for k in names):
+        raise ValueError(f'{who}: kinds holds names out of {KIND_NAMES}, got {kinds!r}')
+    return sum({1 << KIND_NAMES.index(k) for k in names})
+
+
+def _heat_params(who, cell_shift, radius, kinds, period, decay):
+    """The options of one accumulation, validated (ValueError) -> (cell_shift, radius, kinds as a bit mask, period, decay_shift)."""
+    for name, v, lo, hi in (('cell_shift', cell_shift, 0, 6), ('radius', radius, 0, 8), ('period', period, 0, 2 ** 31 - 1), ('decay', decay, 0, 30)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= v <= hi:
+            raise ValueError(f'{who}: {name} must be an int in {lo} .. {hi}, got {v!r}')
+    return int(cell_shift), int(radius), _heat_kinds(who, kinds), int(period), int(decay)
+
+
+def _heat_grid(who, shape):
+    """The shape of a heat grid, checked against the entry's limits (ValueError) -> (C, GH, GW)."""
+    if len(shape) != 3 or not (1 <= shape[0] <= HEAT_MAX_CAMERAS and 1 <= shape[1] <= HEAT_MAX_SIDE and 1 <= shape[2] <= HEAT_MAX_SIDE) or \
+            shape[0] * shape[1] * shape[2] > HEAT_MAX_CELLS:
+        raise ValueError(f'{who}: heat is [C, GH, GW] with C in 1 .. {HEAT_MAX_CAMERAS}, GH and GW in 1 .. {HEAT_MAX_SIDE} and at most 2^24 cells; '
+                         f'got {tuple(shape)}')
+    return tuple(int(v) for v in shape)
+
+
+def _heat_options(who, heat, attention, draw):
+    """The ``heat=`` option of LiveGaze and run_head_video, validated (ValueError) -> None (off) or dict(cell, radius, decay, kinds, draw,
+    full_scale, min_level).  heat: None / False, True or a dict of those; it needs ``attention`` (whose hit points it accumulates), and with
+    draw=True it needs ``draw`` (the frames it is blended into)."""
+    if heat is None or heat is False:
+        return None
+    if heat is not True and not isinstance(heat, dict):
+        raise ValueError(f'{who}: heat is None, True or a dict of cell, radius, decay, kinds, draw, full_scale and min_level; got {heat!r}')
+    opts = dict(cell=8, radius=2, decay=0, kinds=HEAT_KINDS, draw=True, full_scale=None, min_level=1)
+    given = {} if heat is True else dict(heat)
+    if set(given) - set(opts):
+        raise ValueError(f'{who}: heat takes {sorted(opts)}; got {sorted(given)}')
+    if attention is None:
+        raise ValueError(f'{who}: heat accumulates the hit points of attention=...; give attention as well')
+    if heat is True:
+        opts['draw'] = bool(draw)                                 # heat=True: drawn where frames are drawn at all
+    opts.update(given)
+    if not isinstance(opts['draw'], (bool, np.bool_)):
+        raise ValueError(f"{who}: heat's draw is True or False, got {opts['draw']!r}")
+    if opts['draw'] and not draw:
+        raise ValueError(f'{who}: heat with draw=True is blended into the frames draw hands out: it needs draw')
+    _heat_cell(f'{who}(heat=...)', opts['cell'])
+    _heat_params(f'{who}(heat=...)', 0, opts['radius'], opts['kinds'], 0, opts['decay'])
+    _heat_scale(f'{who}(heat=...)', opts['full_scale'], opts['min_level'])
+    return opts
+
+
+def _heat_scale(who, full_scale, min_level):
+    """full_scale (None: the peak; else an int in 1 .. 2^31 - 1) and min_level (1 .. 255), validated (ValueError)."""
+    if full_scale is not None and (isinstance(full_scale, bool) or not isinstance(full_scale, (int, np.integer)) or not 1 <= full_scale <= HEAT_MAX):
+        raise ValueError(f'{who}: full_scale is None (the peak) or an int in 1 .. 2^31 - 1, got {full_scale!r}')
+    if isinstance(min_level, bool) or not isinstance(min_level, (int, np.integer)) or not 1 <= min_level <= 255:
+        raise ValueError(f'{who}: min_level must be an int in 1 .. 255, got {min_level!r}')
+    return None if full_scale is None else int(full_scale), int(min_level)
+
+
+def heat_grid_shape(frame_hw, cell=8):
+    """(GH, GW) of the grid that covers an h x w frame with cells of ``cell`` pixels a side: ceil(h / cell), ceil(w / cell)."""
+    _heat_cell('heat_grid_shape', cell)
+    h, w = (int(v) for v in frame_hw)
+    if h < 1 or w < 1:
+        raise ValueError(f'heat_grid_shape: a frame of at least one pixel, got {h} x {w}')
+    return -(-h // cell), -(-w // cell)
+
+
+def gaze_heat_host(hit, kind, image_of, heat, flags=None, mask=None, cell_shift=3, radius=2, kinds=HEAT_KINDS, period=0, decay=0):
+    """``mcg_gaze_heat_add`` in numpy, bit for bit (include/mcgaze_hip.h, "gaze heat map"): the hit points of the rows that count, splatted
+    into the grid of their camera.  hit [n,2] (read as f32), kind, image_of [n] integers, flags / mask [n] integers or None; heat: int32
+    [C, GH, GW], the grid as it stood (not changed); cell_shift 0 .. 6, radius 0 .. 8 cells, kinds: names out of KIND_NAMES or the bit
+    mask, period as in the header, decay: the decay shift, 0 .. 30, 0 off.
+    A row counts iff flags is None or 0, mask is None or not 0, kind in 0 .. 3 with its bit in ``kinds``, image_of >= 0, its camera
+    (image_of, or image_of % period) below C, and both rounded hit coordinates finite and within +-8191.  It adds
+    (radius + 1 - |dx|) (radius + 1 - |dy|) to every cell within ``radius`` of its own; taps off the grid are dropped.  Each cell: a negative
+    value counts as 0, then h -= h >> decay (once per call), then the taps, saturated at 2^31 - 1.
+    -> (heat int32 [C, GH, GW], peak int32 [C]: each camera's maximum)."""
+    who = 'gaze_heat_host'
+    cell_shift, radius, kinds, period, decay = _heat_params(who, cell_shift, radius, kinds, period, decay)
+    heat = np.asarray(_host_array(heat))
+    if heat.dtype != np.int32:
+        raise TypeError(f'{who}: heat must be int32, got {heat.dtype}')
+    C, GH, GW = _heat_grid(who, heat.shape)
+    hit = np.asarray(_host_array(hit), dtype=np.float32)
+    hit = hit.reshape(0, 2) if hit.size == 0 else hit
+    n = len(hit)
+    if hit.ndim != 2 or hit.shape[1] != 2 or n > MAX_ROWS:
+        raise ValueError(f'{who}: hit must be [n, 2] with n <= {MAX_ROWS}, got {hit.shape}')
+    ints = {}
+    for name, t in (('kind', kind), ('image_of', image_of), ('flags', flags), ('mask', mask)):
+        if t is None:
+            if name in ('kind', 'image_of'):
+                raise ValueError(f'{who}: {name} is required')
+            continue
+        a = np.asarray(_host_array(t)).reshape(-1)
+        if a.size and a.dtype.kind not in 'iub':
+            raise TypeError(f'{who}: {name} must hold integers, got {a.dtype}')
+        if a.shape != (n,):
+            raise ValueError(f'{who}: {name} must be [{n}], one per row; got {a.shape}')
+        ints[name] = a.astype(np.int64)
+    kd, io = ints['kind'], ints['image_of']
+    ok = np.ones(n, dtype=bool)
+    if 'flags' in ints:
+        ok &= ints['flags'] == 0
+    if 'mask' in ints:
+        ok &= ints['mask'] != 0
+    ok &= (kd >= 0) & (kd <= 3) & (((kinds >> np.clip(kd, 0, 3)) & 1) != 0)
+    ok &= io >= 0
+    cam = np.where(io >= 0, io % period if period else io, 0)
+    ok &= cam < C
+    with np.errstate(invalid='ignore'):
+        h64 = np.rint(hit.astype(np.float64))                     # half to even
+        ok &= (np.abs(h64) <= HEAT_COORD).all(axis=1)             # (a NaN fails the comparison)
+    rows = np.flatnonzero(ok)
+    taps = np.zeros((C, GH, GW), dtype=np.int64)
+    if len(rows):
+        cell = h64[rows].astype(np.int64) >> cell_shift           # arithmetic: floors
+        d = np.arange(-radius, radius + 1, dtype=np.int64)
+        wgt = radius + 1 - np.abs(d)
+        x, y = cell[:, 0, None, None] + d[None, None, :], cell[:, 1, None, None] + d[None, :, None]      # [rows, dy, dx]
+        x, y = np.broadcast_arrays(x, y)
+        w = np.broadcast_to(wgt[None, :, None] * wgt[None, None, :], x.shape)
+        c = np.broadcast_to(cam[rows][:, None, None], x.shape)
+        inside = (x >= 0) & (x < GW) & (y >= 0) & (y < GH)
+        np.add.at(taps, (c[inside], y[inside], x[inside]), w[inside])
+    h = np.maximum(heat.astype(np.int64), 0)
+    if decay:
+        h -= h >> decay
+    out = np.minimum(h + taps, HEAT_MAX).astype(np.int32)
+    return out, out.reshape(C, -1).max(axis=1).astype(np.int32)

@@ -26,6 +26,8 @@ RULES = {
     'gaze_dwell_events_kernel': dict(scratch=0, vgpr_spill=0, unit='dwell'),
     # the winning stroke of a lane's pixels is meant to stay in registers across the plan walk, as in the arrows' gather kernel
     'label_raster_kernel': dict(scratch=0, vgpr_spill=0, unit='labels'),
+    # the levels and the 48 bytes of a thread's 16 pixels are meant to stay in registers between the LDS reads and the one store
+    'heat_render_kernel': dict(scratch=0, vgpr_spill=0, unit='heat'),
 }
 
 

@@ -20,7 +20,7 @@ import os
 import numpy as np
 import torch
 
-from .attention import END_VIDEO_ENDED, KIND_HEAD, KIND_REGION, MAX_COLUMNS, MAX_ROWS, _attention_options, _dwell_options, open_episodes
+from .attention import END_VIDEO_ENDED, KIND_HEAD, KIND_REGION, MAX_COLUMNS, MAX_ROWS, _attention_options, _dwell_options, _heat_options, open_episodes
 from .engine import _upload_table
 from .arrows import OVERLAY_PALETTE, _label_options, _overlay_options, format_labels_host
 from .pipeline import ARROW_COLOR, _track_motion, _track_params, letterbox_geometry
@@ -855,8 +855,22 @@ def _add_dwell(records, pipeline, device, num_frames, options):
         rec['dwell_kind'], rec['dwell_frames'], rec['episodes'] = dwell[t, r, 0], dwell[t, r, 3], episodes[r]
 
 
+def _add_heat(records, pipeline, device, num_frames, frame_hw, options):
+    """run_head_video(heat=...): the hit points of records that hold their targets into one camera's grid, a pipeline.gaze_heat call per frame
+    (the grid decays once per frame) -> the HeatState on the device."""
+    state = pipeline.heat_state(1, frame_hw, cell=options['cell'], device=device)
+    rows = [[] for _ in range(num_frames)]
+    for r in records:
+        for j, t in enumerate(r['frame_id']):
+            rows[t].append((r['target_hit'][j], r['target_kind'][j]))
+    for heads in rows:
+        pipeline.gaze_heat(np.asarray([h[0] for h in heads], np.float32).reshape(-1, 2), np.asarray([h[1] for h in heads], np.int32),
+                           np.zeros(len(heads), np.int32), state, radius=options['radius'], kinds=options['kinds'], decay=options['decay'], device=device)
+    return state
+
+
 def run_head_video(engine, pipeline, frames, boxes_per_frame=None, max_len=100, batch_frames=448, expand=0.8, rgb=False, smooth=None, pixel_format='bgr',
-                   matrix='bt601', detections=None, track=None, attention=None, dwell=None, draw=None):
+                   matrix='bt601', detections=None, track=None, attention=None, dwell=None, heat=None, draw=None):
     """Steps 3-4 of the demo from what its users hold -- the video's frames and one head box per person per frame -- to per-person gaze:
     segment_tracks (cell 1), the head windows cut, resized and normalised on the device (pipeline.head_crops: cell 4's crop arithmetic and
     ``cfg.data.test.pipeline[1:]``), run_tracks (cell 4's loop, batched), head_arrows (cell 5's end points).
@@ -918,10 +932,17 @@ def run_head_video(engine, pipeline, frames, boxes_per_frame=None, max_len=100, 
     ``exit`` consecutive frames without it -- conventions, not tuned on data) and ``episodes``: a list of dict(kind, target_id (a head: the
     ``id`` of that person's record) or target_region, start, frames, mutual_frames, reason (attention.END_LOOKED_AWAY / END_OWNER_LEFT /
     END_REPLACED; END_VIDEO_ENDED for the episode still open at the last frame, which is appended from the state on the host)), in the order
-    they began."""
+    they began.
+    heat: None (everything above), True, or dict(cell=8, radius=2, decay=0, kinds=('head', 'region'), draw=True, full_scale=None, min_level=1);
+    it needs ``attention`` (ValueError without), and with draw=True it needs ``draw``: WHERE in the picture the looks landed
+    (pipeline.gaze_heat, mcg_gaze_heat_add; include/mcgaze_hip.h, "gaze heat map"), one call per frame over the records' target_hit, so the
+    grid decays once per frame; one camera, cells of ``cell`` pixels over the size of frame 0.  The return value gains, as its LAST item, the
+    final grid as a numpy array int32 [1, GH, GW] -- (records, heat), or (records, annotated, heat) with draw --, and with draw=True in the
+    dict that final grid is blended into every annotated frame first (pipeline.draw_heat), under the arrows, the overlay and the labels."""
     smooth = check_smooth('run_head_video', smooth)
     attention = _attention_options('run_head_video', attention)
     dwell = _dwell_options('run_head_video', dwell, attention)
+    heat = _heat_options('run_head_video', heat, attention, draw is not None)
     if (boxes_per_frame is None) == (detections is None):
         raise ValueError('run_head_video: give exactly one of boxes_per_frame and detections')
     tracker = None if track is None else _HeadTracker(pipeline, track, engine.device)
@@ -997,8 +1018,9 @@ def run_head_video(engine, pipeline, frames, boxes_per_frame=None, max_len=100, 
         _add_targets(out, pipeline, engine.device, len(boxes_per_frame), 'fused' if smooth is None else 'fused_smooth', *attention)
     if dwell is not None:
         _add_dwell(out, pipeline, engine.device, len(boxes_per_frame), dwell)
+    heat_state = None if heat is None else _add_heat(out, pipeline, engine.device, len(boxes_per_frame), _frame_hw(frames[0], pixel_format), heat)
     if draw is None:
-        return out
+        return out if heat is None else (out, _host(heat_state.heat))
     opts = {'copy': True, **({} if draw is True else dict(draw))}
     overlay = _overlay_options('run_head_video(draw=...)', opts.pop('overlay', None), True, attention)
     labels = _label_options('run_head_video(draw=...)', opts.pop('labels', None), True)
@@ -1020,13 +1042,18 @@ def run_head_video(engine, pipeline, frames, boxes_per_frame=None, max_len=100, 
             named[t].append((int(ident), int(r['dwell_frames'][j]) if dwell is not None else 0))
     if opts.get('color') is not None and np.ndim(opts['color']) == 2:
         raise ValueError('run_head_video(draw=...): color is one (B, G, R) triple')
-    annotated = []
+    annotated, drawing = [], opts                     # drawing: the caller's options, copy among them, the same for every batch
     for t0 in range(0, len(rows), DRAW_FRAMES):
         part = rows[t0:t0 + DRAW_FRAMES]
         image_of = np.asarray([k for k, heads in enumerate(part) for _ in heads], dtype=np.int32)
         boxes = np.asarray([h[0] for heads in part for h in heads], dtype=np.float32).reshape(-1, 4)
         gaze = np.asarray([h[1] for heads in part for h in heads], dtype=np.float32).reshape(-1, 2)
         images = [frames[t] for t in range(t0, t0 + len(part))]
+        opts = drawing
+        if heat is not None and heat['draw']:          # first, under everything else (period 1: every picture shows the one camera); what follows draws into THESE frames, in place
+            images = pipeline.draw_heat(images, heat_state, period=1, full_scale=heat['full_scale'], min_level=heat['min_level'], pixel_format=pixel_format,
+                                        matrix=matrix, copy=drawing['copy'], device=engine.device)
+            opts = dict(drawing, copy=False)
         if overlay is None:
             imgs, _ = pipeline.draw_arrows(images, boxes, gaze, image_of, pixel_format=pixel_format, matrix=matrix, device=engine.device, **opts)
         else:                                          # the records' own tables: a head's target is not read by the overlay, a region's is target_region
@@ -1045,7 +1072,7 @@ def run_head_video(engine, pipeline, frames, boxes_per_frame=None, max_len=100, 
             imgs, _ = pipeline.draw_labels(imgs, boxes, image_of, text, pixel_format=pixel_format, matrix=matrix, device=engine.device, **colors,
                                            **{k: v for k, v in labels.items() if k != 'fps'})
         annotated += imgs
-    return out, annotated
+    return (out, annotated) if heat is None else (out, annotated, _host(heat_state.heat))
 
 
 def dump_results(records, config_path, json_path, out_dir='results'):

@@ -40,7 +40,7 @@ EXPORTS = ['mcg_abi_version', 'mcg_build_id', 'mcg_last_error', 'mcg_device_info
            'mcg_track_state_bytes', 'mcg_track_heads', 'mcg_track_heads_motion', 'mcg_live_slots', 'mcg_live_gate', 'mcg_live_lanes', 'mcg_live_gate_lanes',
            'mcg_deferred_pyramid_state', 'mcg_inner_block_neighbours', 'mcg_gaze_targets', 'mcg_gaze_dwell', 'mcg_gaze_targets_poly',
            'mcg_pointwise_stream', 'mcg_pointwise_dyn', 'mcg_pointwise_pair', 'mcg_draw_attention', 'mcg_draw_attention_nv12',
-           'mcg_format_labels', 'mcg_draw_labels', 'mcg_draw_labels_nv12']
+           'mcg_format_labels', 'mcg_draw_labels', 'mcg_draw_labels_nv12', 'mcg_gaze_heat_add', 'mcg_draw_heat', 'mcg_draw_heat_nv12']
 LABEL_CHARS = 24                                                 # MCG_LABEL_CHARS
 LETTERBOX_U8, LETTERBOX_F16, LETTERBOX_F32 = 0, 1, 2             # enum order of include/mcgaze_hip.h
 
@@ -205,6 +205,9 @@ def load():
     lib.mcg_format_labels.argtypes = [vp, vp, vp, i, i, i, vp]
     lib.mcg_draw_labels.argtypes = [vp, vp, i, i, i, vp, vp, vp, vp, i, vp, i, i, i, u8p, vp, u8p, vp, vp]
     lib.mcg_draw_labels_nv12.argtypes = lib.mcg_draw_labels.argtypes
+    lib.mcg_gaze_heat_add.argtypes = [vp, vp, vp, vp, vp, vp, i, vp, vp, i, i, i, i, i, i, i, i, vp, sz]
+    lib.mcg_draw_heat.argtypes = [vp, vp, i, i, i, vp, vp, i, i, i, i, i, vp, i]
+    lib.mcg_draw_heat_nv12.argtypes = lib.mcg_draw_heat.argtypes
     lib.mcg_gaze_dwell.argtypes =[vp, vp, vp, vp, vp, vp, i, i, i, i, i, vp, vp, i, vp, vp, vp, i, vp]
     lib.mcg_engine_set_option.argtypes = [vp, C.c_char_p, i]
     lib.mcg_engine_profile_start.argtypes = [vp, i]

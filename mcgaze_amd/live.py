@@ -30,8 +30,8 @@ import numpy as np
 import torch
 
 from . import lib as L
-from .arrows import LABEL_CHARS, _label_background, _label_options, _overlay_options, _overlay_palette
-from .attention import KIND_HEAD, PolyRegions, _attention_options, _dwell_options, region_label_rows
+from .arrows import LABEL_CHARS, _label_background, _label_options, _overlay_options, _overlay_palette, heat_lut
+from .attention import KIND_HEAD, PolyRegions, _attention_options, _dwell_options, _heat_options, region_label_rows
 from .engine import _upload_table
 from .harness import _host, check_smooth
 from .head_detect import TRACK_HEADER_WORDS, TRACK_MAX_SLOTS, TRACK_SLOT_WORDS, _track_motion, _track_params, track_state_words
@@ -356,11 +356,20 @@ class LiveGaze:
     int32 (attention.EVENT_FIELDS: the episodes that ENDED in these frames, in ascending (frame, column); rows behind the count are zero) and
     ``num_episodes`` int32 [1].  ``LiveGaze.region_frames`` holds the person-frames every region has collected so far, int32 [m] on the
     device, and ``LiveGaze.dwell_state`` the state [columns, 16] (attention.STATE_WORDS): episodes still open -- after finish() too, which
-    adds nothing beyond its frames -- are read there.  Still no wait for the device, no copy to the host."""
+    adds nothing beyond its frames -- are read there.  Still no wait for the device, no copy to the host.
+    HEAT.  ``heat=None`` is everything above.  ``heat=True`` or ``dict(cell=8, radius=2, decay=0, kinds=('head', 'region'), draw=True,
+    full_scale=None, min_level=1)`` (it needs ``attention``; ValueError without) accumulates WHERE in the picture looks land
+    (pipeline.gaze_heat, mcg_gaze_heat_add; include/mcgaze_hip.h, "gaze heat map"): per returned frame one call over that frame's rows --
+    target_hit, target_kind, image_of, mask = valid, period = Q, so every camera has its own grid of ``cell``-pixel cells, made at the first
+    tick from the size of its frames (one size for all cameras) -- whose grid decays by h >> decay before the frame's looks are added.  Every
+    tick gains ``heat`` int32 [Q, GH, GW] and ``heat_peak`` int32 [Q]: the LIVE device tensors (``LiveGaze.heat_state``), which later ticks
+    go on updating; None before the first tick.  With draw=True (it needs ``draw``; ValueError without; heat=True draws where draw does) the
+    grid as it stands after a frame's looks is blended into that frame's pictures FIRST (pipeline.draw_heat with full_scale and min_level),
+    under the arrows, the overlay and the labels.  Still no wait for the device, no copy to the host."""
 
     def __init__(self, engine_or_model, pipeline, cameras, slots=16, clip_len=7, stride=4, expand=0.8, match_iou=0.3, max_age=5, smooth=None,
                  pixel_format='bgr', draw=False, matrix='bt601', rgb=False, person_threshold=0.5, max_decode_windows=None, lanes=None, motion=None,
-                 attention=None, dwell=None, overlay=None, labels=None):
+                 attention=None, dwell=None, overlay=None, labels=None, heat=None):
         self.S, self.match_iou, self.max_age = _track_params(slots, match_iou, max_age)
         _track_motion(motion, 'LiveGaze')
         self.motion = motion
@@ -374,6 +383,7 @@ class LiveGaze:
         self.dwell = _dwell_options('LiveGaze', dwell, attention)
         self.overlay = _overlay_options('LiveGaze', overlay, draw, attention)
         self.labels = _label_options('LiveGaze', labels, draw)
+        self.heat, self.heat_state = _heat_options('LiveGaze', heat, attention, draw), None
         self.pipe, self.expand, self.draw = pipeline, float(expand), bool(draw)
         self.frame_options = dict(pixel_format=pixel_format, matrix=matrix)
         self.rgb = bool(rgb)
@@ -512,6 +522,19 @@ class LiveGaze:
         return dict(dwell_kind=dwell[..., 0], dwell_id=dwell[..., 1], dwell_start=dwell[..., 2], dwell_frames=dwell[..., 3], episodes=events,
                     num_episodes=num)
 
+    def _heat(self, out, k, images):
+        """heat=: the hit points of each of the k frames handed out into the grids, and with draw the grids as they then stand into that
+        frame's Q pictures (``images``: the kept copies, drawn in place) -> the tables _emit adds."""
+        state, o, Q = self.heat_state, self.heat, self.Q
+        for i in range(k):
+            self.pipe.gaze_heat(out['target_hit'][i].reshape(-1, 2), out['target_kind'][i].reshape(-1), out['image_of'][i].reshape(-1), state,
+                                mask=out['valid'][i].reshape(-1), radius=o['radius'], kinds=o['kinds'], period=Q, decay=o['decay'], device=self.dev)
+            if o['draw']:
+                # the ramp as a HOST table: with it the frame table of the fresh frames travels pinned through the staging ring
+                self.pipe.draw_heat(images[i * Q:(i + 1) * Q], state, lut=heat_lut(None, self.frame_options['pixel_format'] == 'nv12', self.frame_options['matrix']),
+                                    full_scale=o['full_scale'], min_level=o['min_level'], device=self.dev, **self.frame_options)
+        return dict(heat=None if state is None else state.heat, heat_peak=None if state is None else state.peak)
+
     def tick(self, frames, boxes, counts):
         """One frame per camera and its detections -> the frames that became final (see the class)."""
         if self.finished:
@@ -521,6 +544,10 @@ class LiveGaze:
             raise ValueError(f'LiveGaze.tick: {self.Q} frames, boxes [{self.Q}, D, 4] and counts [{self.Q}] (got {len(frames)} frames, '
                              f'{tuple(boxes.shape)}, {tuple(counts.shape)})')
         with torch.cuda.device(self.dev):
+            if self.heat is not None and self.heat_state is None:  # the grids, from the size of the first frames
+                f = frames[0][0] if isinstance(frames[0], (tuple, list)) else frames[0]
+                hw = (f.shape[0] * 2 // 3, f.shape[1]) if self.frame_options['pixel_format'] == 'nv12' and not isinstance(frames[0], (tuple, list)) else f.shape[:2]
+                self.heat_state = self.pipe.heat_state(self.Q, hw, cell=self.heat['cell'], device=self.dev)
             out = self.pipe.track_heads(boxes[:, None], counts[:, None], state=self.state, slots=self.S, match_iou=self.match_iou, max_age=self.max_age,
                                         device=self.dev, motion=self.motion)
             more = dict(flags=out[5].reshape(self.Q), **self._assign())
@@ -575,8 +602,10 @@ class LiveGaze:
             out.update(self._targets(out, k))
         if self.dwell is not None:
             out.update(self._dwell(out, k))
+        images = [f for t in range(self.emitted, self.emitted + k) for f in self.kept.pop(t)] if self.draw else None
+        if self.heat is not None:
+            out.update(self._heat(out, k, images))
         if self.draw:
-            images = [f for t in range(self.emitted, self.emitted + k) for f in self.kept.pop(t)]
             if k:
                 gaze = out['fused_smooth' if smoothing else 'fused']
                 # copy=True: the frame table of fresh tensors then travels pinned through the staging ring, not as a pageable upload

@@ -46,6 +46,9 @@ from .arrows import (ARROW_COLOR, ARROW_COORD, ARROW_SIDE, _arrow_colors, _arrow
                      arrow_segments, draw_arrows_host, segment_coverage)
 from .arrows import LABEL_CHARS, LABEL_FONT, _label_background, _label_ints, _label_params, _label_rate, _label_text, label_plan
 from .arrows import draw_labels_host, encode_labels, format_labels_host  # noqa: F401  (re-exported beside draw_arrows_host, for users of pipeline.*)
+from .arrows import HEAT_LUT, draw_heat_host, heat_lut  # noqa: F401
+from .attention import (HEAT_KINDS, HeatState, _heat_cell, _heat_grid, _heat_params, _heat_scale, gaze_heat_host,  # noqa: F401
+                        heat_grid_shape)
 from .attention import PolyRegions, _check_counts, _holds_polygon, _poly_tables, _region_tables, _target_params, gaze_targets_host, region_polygons  # noqa: F401
 from .attention import _row_tables as _target_rows
 from .attention import DWELL_ENTER, DWELL_EXIT, _dwell_counts, _dwell_params, _dwell_tables, gaze_dwell_host  # noqa: F401
@@ -564,6 +567,8 @@ class DevicePipeline:
         self._frame_hw_tables = collections.OrderedDict()         # detect_heads: (device, host frame_hw bytes) -> that table on the device
         self._detect_workspaces = collections.OrderedDict()       # detect_heads: (device, B, N) -> scratch of mcg_detect_heads
         self._label_fonts = {}                                    # draw_labels: device -> LABEL_FONT on it
+        self._heat_workspaces = collections.OrderedDict()         # gaze_heat: (device, cells) -> scratch of mcg_gaze_heat_add
+        self._heat_tables = collections.OrderedDict()             # draw_heat: the ramp per (device, format, matrix), a fixed scale per (device, C, value)
 
     def _kept(self, cache, key, make):
         """cache[key], made the first time it is asked for; the least recently used of IMAGE_TABLES entries goes."""
@@ -1092,6 +1097,124 @@ class DevicePipeline:
                                        vp(region_frames.data_ptr() if M else None), M, vp(dwell.data_ptr()), vp(ended.data_ptr()),
                                        vp(events.data_ptr() if E else num.data_ptr()), E, vp(num.data_ptr())), 'mcg_gaze_dwell')
         return dwell, ended, events, num, state, region_frames
+
+    def heat_state(self, cameras, frame_hw, cell=8, device='cuda:0'):
+        """The empty state of ``gaze_heat`` for ``cameras`` cameras of h x w frames: HeatState(heat int32 [cameras, ceil(h / cell),
+        ceil(w / cell)] zeros, peak int32 [cameras] zeros, cell_shift) on the device.  cell: the side of a cell in pixels, a power of two in
+        1 .. 64 (ValueError)."""
+        shift = _heat_cell('heat_state', cell)
+        cams, GH, GW = _heat_grid('heat_state', (int(cameras), *heat_grid_shape(frame_hw, cell)))
+        dev = _device(device, 'mcg_gaze_heat_add')
+        return HeatState(torch.zeros(cams, GH, GW, dtype=torch.int32, device=dev), torch.zeros(cams, dtype=torch.int32, device=dev), shift)
+
+    def _heat_state(self, who, state, dev):
+        """``state`` as gaze_heat and draw_heat take it, checked (TypeError / ValueError) -> (cams, GH, GW)."""
+        if not (isinstance(state, HeatState) and all(isinstance(t, torch.Tensor) and t.device == dev and t.dtype == torch.int32 and t.is_contiguous()
+                                                     for t in state[:2])):
+            raise TypeError(f'{who}: state is a HeatState of contiguous int32 tensors on {dev} (heat_state makes it; it is updated in place)')
+        cams, GH, GW = _heat_grid(who, tuple(state.heat.shape))
+        if tuple(state.peak.shape) != (cams,):
+            raise ValueError(f'{who}: the peak of {cams} cameras is [{cams}], got {tuple(state.peak.shape)}')
+        _heat_params(who, state.cell_shift, 0, 0, 0, 0)
+        return cams, GH, GW
+
+    def gaze_heat(self, hit, kind, image_of, state, flags=None, mask=None, radius=2, kinds=HEAT_KINDS, period=0, decay=0, device='cuda:0', stream=None):
+        """Where looks land, accumulated on the device (mcg_gaze_heat_add: the workspace cleared, a scatter with integer atomics, a per-cell
+        pass) -- ``attention.gaze_heat_host`` bit for bit: every row that counts adds a pyramid of (radius + 1 - |dx|) (radius + 1 - |dy|)
+        around the cell of its hit point to the grid of its camera (image_of, or image_of % period).
+
+        hit [n,2], kind, image_of [n] -- gaze_targets' results and its image_of --, flags / mask [n] or None (a row counts where its flag is
+        0 and its mask is not): CUDA tensors are read where they are, numpy tables go up through the staging ring (a host table next to a
+        device one is moved with torch).  state: ``heat_state``'s, UPDATED IN PLACE: heat decays by h >> decay once per call (0: off), gains
+        the taps and saturates at 2^31 - 1; peak becomes each camera's maximum.  kinds: the kinds of target that count, names out of
+        ('none', 'head', 'region', 'camera') or the bit mask.  Options and shapes are checked on the host before anything is launched
+        (TypeError / ValueError); what the tables hold is never an error and is never read back.  With device tables the call touches the
+        host nowhere once a first call has allocated the workspace, and can be captured in a graph.
+        -> state."""
+        lib = L.load()
+        who = 'gaze_heat'
+        dev = _device(device, 'mcg_gaze_heat_add')
+        cams, GH, GW = self._heat_state(who, state, dev)
+        shift, radius, kinds, period, decay = _heat_params(who, state.cell_shift, radius, kinds, period, decay)
+        tables = [('hit', hit, torch.float32), ('kind', kind, torch.int32), ('image_of', image_of, torch.int32), ('flags', flags, torch.int32),
+                  ('mask', mask, torch.int32)]
+        there = any(_on_device(t) for _, t, _ in tables)
+        if not there:                                             # all on the host: checked here, staged below
+            host = []
+            for name, t, dtype in tables:
+                if t is None:
+                    host.append(None)
+                    continue
+                a = np.asarray(_host_array(t))
+                if name != 'hit' and a.size and a.dtype.kind not in 'iub':
+                    raise TypeError(f'{who}: {name} must hold integers, got {a.dtype}')
+                host.append(np.ascontiguousarray(a.reshape(-1, 2) if name == 'hit' else a.reshape(-1), dtype=np.float32 if name == 'hit' else np.int32))
+        with _call_scope(self._ring, dev, stream) as call:
+            moved = [None if t is None else _there(t, dev, dtype) for _, t, dtype in tables] if there else host
+            if moved[0] is None or moved[1] is None or moved[2] is None:
+                raise ValueError(f'{who}: hit, kind and image_of are required')
+            n = int(moved[0].shape[0])
+            for (name, _, _), t in zip(tables, moved):
+                if t is not None and tuple(t.shape) != ((n, 2) if name == 'hit' else (n,)):
+                    raise ValueError(f'{who}: {name} must be {[n, 2] if name == "hit" else [n]}, got {tuple(t.shape)}')
+            if n > 65536:
+                raise ValueError(f'{who}: at most 65536 rows per call (got {n})')
+            work = self._kept(self._heat_workspaces, (dev.index, cams * GH * GW), lambda: torch.empty(cams * GH * GW, dtype=torch.int32, device=dev))
+            _, ptrs = call.upload([], [t if t is None or (t.size if isinstance(t, np.ndarray) else t.numel()) else None for t in moved])
+            vp = C.c_void_p
+            L.check(lib.mcg_gaze_heat_add(vp(call.main.cuda_stream), *(vp(p) for p in ptrs), n, vp(state.heat.data_ptr()), vp(state.peak.data_ptr()), cams, GH,
+                                          GW, shift, radius, kinds, period, decay, vp(work.data_ptr()), 4 * work.numel()), 'mcg_gaze_heat_add')
+        return state
+
+    def draw_heat(self, images, state, period=0, lut=None, full_scale=None, min_level=1, pixel_format='bgr', matrix='bt601', copy=False, device='cuda:0',
+                  stream=None):
+        """The heat map blended into the frames on the device (mcg_draw_heat / mcg_draw_heat_nv12: one launch over every pixel) --
+        ``arrows.draw_heat_host`` bit for bit: picture p shows the grid of camera p (with a period: p % period), every pixel's level
+        interpolated between cell centres and scaled so that ``full_scale`` is level 255, coloured by ``lut`` and blended with its alpha.
+
+        images, pixel_format, matrix, copy: ``draw_arrows``' -- a CUDA frame is drawn IN PLACE (copy=True: into a packed clone), a numpy frame
+        goes up through the staging ring.  state: gaze_heat's.  full_scale: None -- ``state.peak``, each camera's own maximum, read on the
+        device -- or an int, the same fixed scale for every camera (a device table filled with it is kept).  lut: [256, 4] (B, G, R, alpha)
+        per level on the host (None: ``arrows.HEAT_LUT``, kept on the device), converted once by ``bgr_to_yuv`` for NV12; a uint8 [256, 4]
+        DEVICE tensor is read as it is, (Y, U, V, alpha) for NV12.  A pixel below min_level (1 .. 255) keeps its bytes.  A picture whose
+        camera has no grid is handed back untouched.  With device frames drawn in place and the frame table cached by a first call, the
+        call touches the host nowhere and can be captured in a graph.
+        -> the images on the device, in order."""
+        lib = L.load()
+        who = 'draw_heat'
+        nv12, _ = _pixel_format(pixel_format, matrix)
+        full_scale, min_level = _heat_scale(who, full_scale, min_level)
+        _heat_params(who, 0, 0, 0, period, 0)
+        entry = lib.mcg_draw_heat_nv12 if nv12 else lib.mcg_draw_heat
+        dev = _device(device)                                     # the surfaces are checked whatever the device: a bad one is the caller's first error
+        images = list(images)
+        planes = [_nv12_planes(k, im, dev) for k, im in enumerate(images)] if nv12 else None
+        dev = _device(dev, entry.__name__)
+        if not len(images):
+            raise ValueError(f'{who}: no frames')
+        table, _ = _image_table(images, dev, planes)              # every frame is checked before the first clone or upload
+        cams, GH, GW = self._heat_state(who, state, dev)
+        if _on_device(lut):
+            if not (lut.device == dev and lut.dtype == torch.uint8 and tuple(lut.shape) == (256, 4) and lut.is_contiguous()):
+                raise TypeError(f'{who}: a device lut is a contiguous uint8 [256, 4] tensor on {dev}')
+        elif lut is not None:
+            lut = heat_lut(lut, nv12, matrix)                     # a host table: checked, converted, staged with the call
+        with _call_scope(self._ring, dev, stream) as call:
+            out, pixels, in_place = _arrow_targets(images, planes, copy, dev)
+            if not in_place:                                      # the table of the tensors that are drawn into
+                table, _ = _image_table(out, dev, [_nv12_planes(k, o, dev) for k, o in enumerate(out)] if nv12 else None)
+            h_max, w_max = int(table['h'].max()), int(table['w'].max())
+            if h_max > ARROW_SIDE or w_max > ARROW_SIDE:
+                raise ValueError(f'{who}: frames of at most {ARROW_SIDE} pixels a side, got {h_max} x {w_max}')
+            if lut is None:                                       # the ramp is data the pipeline brings: uploaded once per device and format, and kept
+                lut = self._kept(self._heat_tables, (dev.index, 'lut', nv12, matrix), lambda: torch.from_numpy(heat_lut(None, nv12, matrix).copy()).to(dev))
+            full = state.peak if full_scale is None else self._kept(self._heat_tables, (dev.index, 'full', cams, full_scale),
+                                                                     lambda: torch.full((cams,), full_scale, dtype=torch.int32, device=dev))
+            images_ptr, lut_ptr = self._drawing_upload(call, nv12, table, pixels, in_place, (lut,))
+            vp = C.c_void_p
+            L.check(entry(vp(call.main.cuda_stream), vp(images_ptr), len(out), h_max, w_max, vp(state.heat.data_ptr()), vp(full.data_ptr()), cams, GH, GW,
+                          state.cell_shift, int(period), vp(lut_ptr), min_level), entry.__name__)
+        return out
 
     def letterbox(self, frames, new_shape=640, stride=32, auto=True, scaleup=True, dtype=torch.float16, rgb=False, pixel_format='bgr', matrix='bt601',
                   device='cuda:0', stream=None):

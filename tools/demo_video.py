@@ -6,7 +6,7 @@ usage: demo_video.py FRAMES_DIR LABELS_DIR CONFIG CHECKPOINT --out gaze.json [--
                      [--batch-frames 448] [--head-class 1] [--ext jpg] [--smooth ALPHA] [--nv12 WxH FILE] [--matrix bt601] [--draw OUT] [--overlay] [--labels [SCALE]] [--fps NUM[/DEN]]
                      [--track [--slots 16] [--match-iou 0.3] [--max-age 5]] [--track-motion [GAIN[,DECAY]]]
                      [--color B,G,R] [--predictions DIR --in-shape HxW [--conf-thres 0.25] [--iou-thres 0.45]]
-                     [--detector MODULE:FACTORY [--img-size 640] [--half]] [--attention [--regions FILE.json] [--dwell [ENTER,EXIT]]]
+                     [--detector MODULE:FACTORY [--img-size 640] [--half]] [--attention [--regions FILE.json] [--dwell [ENTER,EXIT]] [--heat [CELL,RADIUS]] [--heat-out FILE.npy]]
 
 FRAMES_DIR holds 0.<ext>, 1.<ext>, ... (the demo's `frames/`), LABELS_DIR holds 0.txt, 1.txt, ... with lines `class x1 y1 x2 y2` in pixels
 (the demo's `result/labels/`); a frame without a label file shows no head.  CONFIG is the L2CS config, whose test pipeline the demo runs
@@ -43,7 +43,11 @@ untuned defaults (a looked-at head box grown by 0.25 of its longer side, a 10 de
 gains per frame `dwell_kind` and `dwell_frames` (the current target and its frames so far) and `episodes`, a list of {kind, target_id or
 target_region, start, frames, mutual_frames, reason (1 looked away, 2 the person left, 3 replaced by another target, 4 the video ended)}.  A
 look becomes current after ENTER consecutive frames and ends after EXIT consecutive frames without it (default 3,2: conventions, not tuned
-on data)."""
+on data).
+--heat [CELL,RADIUS], with --attention: WHERE in the picture the looks land (harness.run_head_video(heat=...), pipeline.gaze_heat on the
+device): the hit points of every frame splatted into a grid of CELL-pixel cells (a power of two, default 8) with a radius of RADIUS cells
+(default 2).  With --draw the final grid is blended into every annotated frame, under the arrows (pipeline.draw_heat); --heat-out FILE.npy
+writes the grid, int32 [1, GH, GW]."""
 import argparse
 import importlib
 import json
@@ -188,7 +192,23 @@ def main(argv=None):
     ap.add_argument('--dwell', nargs='?', const='', default=None, metavar='ENTER,EXIT',
                     help='--attention with how long every look lasts: episodes with a start, a length and an end (default 3,2: conventions, not '
                          'tuned on data)')
+    ap.add_argument('--heat', nargs='?', const='', default=None, metavar='CELL,RADIUS',
+                    help='--attention with where the looks land: a heat map of CELL-pixel cells (8) and a splat of RADIUS cells (2), drawn under --draw')
+    ap.add_argument('--heat-out', default=None, metavar='FILE.npy', help='write the final grid of --heat, int32 [1, GH, GW]')
     a = ap.parse_args(argv)
+    if (a.heat is not None or a.heat_out is not None) and not a.attention:
+        raise SystemExit('--heat and --heat-out belong to --attention')
+    if a.heat_out is not None and a.heat is None:
+        a.heat = ''
+    heat = None
+    if a.heat is not None:
+        try:
+            values = [int(v) for v in a.heat.split(',')] if a.heat else []
+        except ValueError:
+            values = None
+        if values is None or len(values) > 2:
+            raise SystemExit(f'--heat takes CELL or CELL,RADIUS, got {a.heat!r}')
+        heat = dict(zip(('cell', 'radius'), values), draw=a.draw is not None)
     if a.regions is not None and not a.attention:
         raise SystemExit('--regions belongs to --attention')
     if a.dwell is not None and not a.attention:
@@ -256,8 +276,13 @@ def main(argv=None):
     pipe = DevicePipeline(model.cfg.data.test.pipeline)
     res = harness.run_head_video(model.engine(), pipe, frames, per_frame, max_len=a.max_len, batch_frames=a.batch_frames, rgb=True,
                                  smooth=a.smooth, pixel_format='bgr' if a.nv12 is None else 'nv12', matrix=a.matrix, detections=detections, draw=draw,
-                                 track=track, attention=attention, dwell=dwell)
+                                 track=track, attention=attention, dwell=dwell, heat=heat)
     as_json = lambda v: list(v) if isinstance(v, tuple) else v
+    if heat is not None:
+        res, grid = res[:-1], res[-1]
+        res = res[0] if draw is None else res
+        if a.heat_out is not None:
+            np.save(a.heat_out, grid)
     if draw is not None:
         res, annotated = res
         write_annotated(a.draw, annotated, a.nv12 is not None)
