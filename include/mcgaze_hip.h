@@ -1330,6 +1330,67 @@ int mcg_draw_heat(mcg_stream s, const mcg_image_desc* images_dev, int num_images
 int mcg_draw_heat_nv12(mcg_stream s, const mcg_nv12_image_desc* images_dev, int num_images, int max_h, int max_w, const int32_t* heat_dev,
                        const int32_t* full_dev, int C, int GH, int GW, int cell_shift, int period, const unsigned char* lut_dev, int min_level);
 
+/* ---------------------------------------------------------------- anonymised heads (additions to ABI 19; nothing above changes)
+ * The faces under the head boxes removed IN PLACE from packed BGR frames (mcg_anonymize_heads) or NV12 surfaces (mcg_anonymize_heads_nv12),
+ * after the network has read them and before anything is drawn on top: every covered pixel becomes the mean of a coarse cell of the frame
+ * (mosaic) or one colour (fill).  The image table and the rows are those of mcg_draw_gaze_arrows.  Two launches: a plan kernel (one thread
+ * per row, double, uncontracted) writes one mcg_anon_desc per row, then a render kernel over (tile of 64 x 64 pixels, image).  The call
+ * hides the heads it is GIVEN: a head the detector missed stays visible.
+ * 1. PLAN, per row, from a box x1 y1 x2 y2 (f32, widened to double) and image_of.  A row is USABLE iff image_of is in [0, num_images), the
+ * four coordinates are finite with x2 > x1 and y2 > y1, its picture is writable (it has pixels; NV12: of even size) and no larger than
+ * (max_h, max_w), and, with
+ *   ex = expand * (x2 - x1);  ey = expand * (y2 - y1);  X0 = floor(x1 - ex);  X1 = ceil(x2 + ex);  Y0 = floor(y1 - ey);  Y1 = ceil(y2 + ey)
+ * (every product and difference rounded on its own), |X0|, |X1|, |Y0|, |Y1| <= 8191.  The integer rectangle always contains the float
+ * box: rounding never uncovers a face.  W = X1 - X0 and H = Y1 - Y0 are at least 1 and below 2^14.
+ * The SHIFT s of the row is cell_shift where that is not 0; otherwise the smallest s in 1 .. 6 with (blocks << s) >= max(W, H), and 6 if
+ * there is none -- a far head gets small cells and a near head large ones, about `blocks` cells across either.
+ * The descriptor holds the rectangle clipped to the picture, half open, [max(X0, 0), min(X1, w)) x [max(Y0, 0), min(Y1, h)) -- it may be
+ * empty: the row then writes nothing and its flag is still 0 --, cx2 = X0 + X1, cy2 = Y0 + Y1, W, H, the shift and the shape.
+ * FLAGS.  0: usable.  2: unusable; NOTHING is written for the row, and its descriptor is zero but for image = -1 and flag = 2.
+ * 2. COVERAGE, exact, in 64-bit integers.  Pixel (px, py) is covered by a row iff it lies in the row's clipped rectangle and, with shape 1,
+ *   (2 px + 1 - cx2)^2 H^2 + (2 py + 1 - cy2)^2 W^2 <= W^2 H^2
+ * -- the ellipse inscribed in the integer rectangle, tested at pixel centres.  |2 px + 1 - cx2| and |2 py + 1 - cy2| are below 2^15 and
+ * W, H below 2^14: each product is below 2^58 and the sum below 2^59.
+ * 3. VALUE, mode 0 (mosaic).  For every s the frame carries a grid of cells of 2^s x 2^s pixels aligned to the frame's origin; the cells at
+ * the right and bottom edges are cut to the frame.  A covered pixel takes s(p), the LARGEST shift among the rows that cover it, and becomes
+ * the mean of its cell at that shift, per channel, (sum + (count >> 1)) / count in integers, over ALL of the cell's pixels inside the
+ * frame, covered or not, AS THEY WERE BEFORE THE CALL.  A cell has one value, so overlapping boxes cannot disagree.  A second call reads
+ * what the first one wrote: where the coverage cuts through cells the call is NOT idempotent.
+ * Mode 1 (fill): a covered pixel becomes `color`; the result does not depend on what the frame held.
+ * A pixel that no row covers keeps its bytes, pitch padding included (the kernel writes whole spans of 16 pixels that hold a covered
+ * pixel, the others with the bytes it read, and touches no span without one).
+ * NV12 follows "annotated frames out": a luma pixel is treated as above, over the Y plane.  A chroma pair is written iff ANY of its four
+ * luma pixels is covered; its shift is the largest s(p) of those four, and U and V each become the rounded mean of the chroma samples of
+ * the pair's cell at that shift -- 2^(s-1) x 2^(s-1) pairs (s >= 1), aligned to the origin, cut to the frame.  Fill: (Y, U, V) of `color`.
+ * No claim is made that the NV12 result equals the BGR result converted.
+ * THE RENDER KERNEL.  A tile is a frame-aligned block of 64 x 64 pixels, so every cell of every shift lies inside exactly one tile: a
+ * workgroup reads only its own tile, all of its reads come before its writes with a barrier between, and no other workgroup touches those
+ * bytes -- in place needs neither a second buffer nor atomics on the image.  A workgroup walks the descriptors in chunks of 256 and keeps
+ * those of its image whose rectangle meets the tile (no cap on their number); a tile under no head is never read.  A thread owns 16 pixels
+ * of a row (NV12: 16 x 2 and their 8 chroma pairs), read and written as mcg_draw_heat does.  Cell sums are integers: their order does not
+ * matter.
+ *   images_dev, num_images, max_h, max_w, boxes_dev, image_of_dev: as mcg_draw_gaze_arrows takes them;  n in 0 .. 65536
+ *   expand 0 .. 4;  shape 0 box, 1 ellipse;  cell_shift 0 (automatic) or 1 .. 6;  blocks 1 .. 64, read only where cell_shift == 0
+ *   mode 0 mosaic, 1 fill;  color HOST uint8[3] (B, G, R; NV12: Y, U, V), read only with mode 1
+ *   plan_out_dev DEVICE [n] descriptors (written);  flags_dev DEVICE int32 [n] or NULL
+ * Anything else or a null required pointer returns MCG_ERR_ARG before any launch; n == 0 returns MCG_OK without one.  No byte outside
+ * [0, h) x [0, w) of any plane is touched for ANY table contents.  No allocation, no host sync, graph-capturable.
+ * mcgaze_amd/arrows.py::anonymize_plan_host and anonymize_heads_host are the same on the host, bit for bit.  The defaults of the python
+ * layer (expand 0.125, ellipse, 8 blocks) are CONVENTIONS, not tuned on data. */
+typedef struct mcg_anon_desc {
+  int image, flag;
+  int x0, y0, x1, y1;       /* the covered rectangle clipped to the frame, half open; may be empty */
+  int cx2, cy2;             /* X0 + X1, Y0 + Y1 of the unclipped rectangle: twice its centre */
+  int W, H;                 /* its unclipped size */
+  int shift, shape;
+} mcg_anon_desc;
+int mcg_anonymize_heads(mcg_stream s, const mcg_image_desc* images_dev, int num_images, int max_h, int max_w, const float* boxes_dev,
+                        const int32_t* image_of_dev, int n, double expand, int shape, int cell_shift, int blocks, int mode,
+                        const unsigned char* color, mcg_anon_desc* plan_out_dev, int32_t* flags_dev);
+int mcg_anonymize_heads_nv12(mcg_stream s, const mcg_nv12_image_desc* images_dev, int num_images, int max_h, int max_w, const float* boxes_dev,
+                             const int32_t* image_of_dev, int n, double expand, int shape, int cell_shift, int blocks, int mode,
+                             const unsigned char* yuv, mcg_anon_desc* plan_out_dev, int32_t* flags_dev);
+
 /* ---------------------------------------------------------------- measurement aids (bench.py)
  * While armed, every launch of the contraction kernel made by THIS engine is bracketed by a hipEvent pair on its launch stream.
  * mcg_engine_profile_stop synchronises, returns per-launch duration (ms), algorithmic FLOPs, algorithmic HBM bytes (inputs and

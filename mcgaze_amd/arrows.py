@@ -771,3 +771,150 @@ def draw_heat_host(frames, heat, full, cell_shift, period=0, lut=None, min_level
             on = level >= min_level
             out[p][on] = _heat_blend(out[p][on], table[level[on], :3], table[level[on], 3:4])
     return out[0] if single else out
+
+
+# ---------------------------------------------------------------- anonymised heads (include/mcgaze_hip.h, "anonymised heads")
+ANON_SHAPES, ANON_MODES = ('box', 'ellipse'), ('mosaic', 'fill')
+
+
+def _anon_params(who, expand=0.125, shape='ellipse', cell=None, blocks=8, mode='mosaic'):
+    """The options of the anonymising calls, validated (ValueError) -> (expand, shape, cell_shift, blocks, mode) as the entries take them:
+    shape 0 box / 1 ellipse, cell_shift 0 (automatic, from ``blocks``) or log2 of ``cell``, mode 0 mosaic / 1 fill.  The defaults are
+    conventions, not tuned on data."""
+    expand = float(expand)
+    if not 0.0 <= expand <= 4.0:
+        raise ValueError(f'{who}: expand must lie in 0 .. 4, got {expand!r}')
+    if shape not in ANON_SHAPES or mode not in ANON_MODES:
+        raise ValueError(f'{who}: shape is one of {ANON_SHAPES} and mode one of {ANON_MODES}, got {shape!r}, {mode!r}')
+    if cell is not None and (int(cell) != cell or int(cell) not in (2, 4, 8, 16, 32, 64)):
+        raise ValueError(f'{who}: cell must be None or a power of two in 2 .. 64, got {cell!r}')
+    if int(blocks) != blocks or not 1 <= int(blocks) <= 64:
+        raise ValueError(f'{who}: blocks must be an integer in 1 .. 64, got {blocks!r}')
+    return expand, ANON_SHAPES.index(shape), 0 if cell is None else int(cell).bit_length() - 1, int(blocks), ANON_MODES.index(mode)
+
+
+_ANON_COLORS = {}
+
+
+def _anon_color(who, color, nv12, matrix):
+    """One (B, G, R) triple -> uint8 [3] as the entries take it: with nv12 the (Y, U, V) of bgr_to_yuv, worked out once per colour and
+    matrix and kept -- the live path hands in the same colour every tick."""
+    one = _arrow_colors(color, 0, False, matrix)[0]
+    if color is None or one is None:
+        raise ValueError(f'{who}: color must be one (B, G, R) triple')
+    if not nv12:
+        return np.asarray(one, dtype=np.uint8).reshape(3)
+    key = (int(one[0]), int(one[1]), int(one[2]), matrix)
+    if key not in _ANON_COLORS:
+        _ANON_COLORS[key] = np.asarray(bgr_to_yuv(one, matrix), dtype=np.uint8).reshape(3)
+    return _ANON_COLORS[key]
+
+
+def anonymize_plan_host(boxes, image_of, sizes, expand=0.125, shape='ellipse', cell=None, blocks=8, nv12=False):
+    """The plan of "anonymised heads" on the host (anonymize_plan_kernel line for line): boxes [n,4] read as f32 and widened to double,
+    image_of [n], sizes [(h, w), ...] of the frames -> a dict of int64 [n] arrays image, flag, x0, y0, x1, y1 (the integer rectangle
+    clipped to the frame, half open, possibly empty), cx2, cy2, W, H, shift, shape -- the fields of mcg_anon_desc.  Flag 2: image_of
+    outside the table, a coordinate that is not finite, x2 <= x1 or y2 <= y1, an image without pixels, larger than 8192 a side or (nv12)
+    of odd size, a rectangle beyond +-8191.  A flagged row is zero but for image = -1."""
+    expand, shape, cell_shift, blocks, _ = _anon_params('anonymize_plan_host', expand, shape, cell, blocks)
+    b = np.asarray(_host_array(boxes), dtype=np.float32).astype(np.float64).reshape(-1, 4)
+    n = len(b)
+    image_of = _label_ints('image_of', image_of, n).astype(np.int64)
+    hw = np.asarray(sizes, dtype=np.int64).reshape(-1, 2)
+    ok = (image_of >= 0) & (image_of < len(hw)) & np.isfinite(b).all(axis=1)
+    b = np.where(ok[:, None], b, 0.0)
+    ok &= (b[:, 2] > b[:, 0]) & (b[:, 3] > b[:, 1])
+    h, w = (np.where(ok, hw[np.where(ok, image_of, 0), c] if len(hw) else 0, 0) for c in (0, 1))
+    ok &= (h > 0) & (w > 0) & (h <= ARROW_SIDE) & (w <= ARROW_SIDE)
+    if nv12:
+        ok &= ((h | w) & 1) == 0
+    # numpy rounds every elementwise product and difference on its own: nothing is contracted, as in the kernel
+    ex, ey = expand * (b[:, 2] - b[:, 0]), expand * (b[:, 3] - b[:, 1])
+    X0, X1, Y0, Y1 = np.floor(b[:, 0] - ex), np.ceil(b[:, 2] + ex), np.floor(b[:, 1] - ey), np.ceil(b[:, 3] + ey)
+    ok &= np.logical_and.reduce([np.abs(v) <= ARROW_COORD for v in (X0, X1, Y0, Y1)])
+    X0, X1, Y0, Y1 = (np.where(ok, v, 0.0).astype(np.int64) for v in (X0, X1, Y0, Y1))
+    W, H = X1 - X0, Y1 - Y0
+    if cell_shift:
+        shift = np.full(n, cell_shift, dtype=np.int64)
+    else:
+        shift = np.full(n, 6, dtype=np.int64)
+        for c in range(5, 0, -1):
+            shift = np.where((blocks << c) >= np.maximum(W, H), c, shift)
+    plan = dict(image=image_of, x0=np.maximum(X0, 0), y0=np.maximum(Y0, 0), x1=np.minimum(X1, w), y1=np.minimum(Y1, h), cx2=X0 + X1, cy2=Y0 + Y1,
+                W=W, H=H, shift=shift, shape=np.full(n, shape, dtype=np.int64))
+    plan = {k: np.where(ok, v, -1 if k == 'image' else 0).astype(np.int64) for k, v in plan.items()}
+    plan['flag'] = np.where(ok, 0, 2).astype(np.int64)
+    return plan
+
+
+def anonymize_coverage(plan, k):
+    """(y0, x0, bool [y1 - y0, x1 - x0]): which pixels of the clipped rectangle of row k are covered -- COVERAGE of "anonymised heads", the
+    inscribed ellipse tested at pixel centres in 64-bit integers (every pixel of the rectangle for a box)."""
+    x0, y0, x1, y1, W, H = (int(plan[f][k]) for f in ('x0', 'y0', 'x1', 'y1', 'W', 'H'))
+    py, px = np.mgrid[y0:max(y1, y0), x0:max(x1, x0)].astype(np.int64)
+    if not int(plan['shape'][k]):
+        return y0, x0, np.ones(py.shape, dtype=bool)
+    dx, dy = 2 * px + 1 - int(plan['cx2'][k]), 2 * py + 1 - int(plan['cy2'][k])
+    return y0, x0, dx * dx * (H * H) + dy * dy * (W * W) <= W * W * H * H
+
+
+def _anon_cell_means(plane, s):
+    """The mean of every cell of 2^s x 2^s samples of plane [h, w, c], cells aligned to the origin and cut at the right and bottom edges,
+    (sum + (count >> 1)) / count in integers -> int64 [h, w, c], each sample's own cell's mean."""
+    S = 1 << s
+    h, w = plane.shape[:2]
+    edges_y, edges_x = np.arange(0, h, S), np.arange(0, w, S)
+    sums = np.add.reduceat(np.add.reduceat(plane.astype(np.int64), edges_y, axis=0), edges_x, axis=1)
+    count = (np.minimum(edges_y + S, h) - edges_y)[:, None, None] * (np.minimum(edges_x + S, w) - edges_x)[None, :, None]
+    mean = (sums + (count >> 1)) // count
+    return np.repeat(np.repeat(mean, S, axis=0), S, axis=1)[:h, :w]
+
+
+def anonymize_heads_host(frames, boxes, image_of=None, expand=0.125, shape='ellipse', cell=None, blocks=8, mode='mosaic', color=(0, 0, 0),
+                         pixel_format='bgr', matrix='bt601'):
+    """Heads anonymised with numpy: what DevicePipeline.anonymize_heads (mcg_anonymize_heads / mcg_anonymize_heads_nv12) writes on the
+    device, bit for bit (include/mcgaze_hip.h, "anonymised heads": the plan, the coverage, the largest shift winning, the cell means of
+    the frame as it was, the NV12 chroma rule).  It hides the heads it is given: a head the detector missed stays visible.
+
+    frames, pixel_format, matrix: as for draw_arrows_host.  boxes [n,4] x1 y1 x2 y2, image_of [n] (None: frame 0).  expand: the box grows
+    by this share of its size on every side, 0 .. 4; shape 'ellipse' (inscribed in the grown box) or 'box'; cell: None -- about ``blocks``
+    (1 .. 64) cells across each head, a power of two of 2 .. 64 pixels -- or that power of two for every head; mode 'mosaic' or 'fill'
+    with ``color``, one (B, G, R) triple.  The defaults are conventions, not tuned on data.
+    -> (anonymised COPIES in the form given -- NV12 frames as (y [H,W], uv [H/2,W]) pairs --, flags int32 [n]: 0 usable, 2 unusable; a row
+    flagged 2 changes no byte)."""
+    who = 'anonymize_heads_host'
+    nv12, _ = _pixel_format(pixel_format, matrix)
+    fill = _anon_params(who, expand, shape, cell, blocks, mode)[4]
+    c = _anon_color(who, color, nv12, matrix)
+    single = not isinstance(frames, list)
+    frames = [frames] if single else frames
+    if nv12:
+        out = [tuple(np.array(p) for p in _nv12_planes(k, f)[:2]) for k, f in enumerate(frames)]
+        sizes = [y.shape for y, _ in out]
+    else:
+        out = [_bgr_frame(k, np.array(f)) for k, f in enumerate(frames)]
+        sizes = [a.shape[:2] for a in out]
+    n = len(np.asarray(_host_array(boxes)).reshape(-1, 4))
+    image_of = np.zeros(n, dtype=np.int32) if image_of is None else _host_array(image_of)
+    plan = anonymize_plan_host(boxes, image_of, sizes, expand, shape, cell, blocks, nv12)
+    for p, (h, w) in enumerate(sizes):
+        rows = np.flatnonzero((plan['flag'] == 0) & (plan['image'] == p))
+        top = np.zeros((h, w), dtype=np.int64)                    # s(p): the largest shift that covers each pixel, 0 for none
+        for k in rows:
+            y0, x0, covered = anonymize_coverage(plan, k)
+            area = top[y0:y0 + covered.shape[0], x0:x0 + covered.shape[1]]
+            area[covered] = np.maximum(area[covered], plan['shift'][k])
+        if not top.any():
+            continue
+        if nv12:
+            y, uv = out[p]
+            pairs, pair_top = uv.reshape(h // 2, w // 2, 2), top.reshape(h // 2, 2, w // 2, 2).max(axis=(1, 3))
+            planes = [(y.reshape(h, w, 1), top, 0, c[:1]), (pairs, pair_top, 1, c[1:])]
+        else:
+            planes = [(out[p], top, 0, c)]
+        for plane, level, finer, col in planes:                   # a chroma cell of shift s is 2^(s-1) pairs a side
+            before = plane.copy()
+            for s in np.unique(level[level > 0]):
+                on = level == s
+                plane[on] = col if fill else _anon_cell_means(before, int(s) - finer)[on]
+    return (out[0] if single else out), plan['flag'].astype(np.int32)

@@ -28,6 +28,8 @@ RULES = {
     'label_raster_kernel': dict(scratch=0, vgpr_spill=0, unit='labels'),
     # the levels and the 48 bytes of a thread's 16 pixels are meant to stay in registers between the LDS reads and the one store
     'heat_render_kernel': dict(scratch=0, vgpr_spill=0, unit='heat'),
+    # the shifts and the bytes of a thread's 16 pixels (NV12: 16 x 2 and their pairs) are meant to stay in registers across the plan walk and the fold
+    'anonymize_render_kernel': dict(scratch=0, vgpr_spill=0, unit='anonymize'),
 }
 
 

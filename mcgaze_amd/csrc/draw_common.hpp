@@ -1,5 +1,6 @@
 // What draw.hip (gaze arrows) and overlay.hip (attention overlay) share: the bounds under which the coverage test is exact, the tile of the
-// gather kernels, the two kinds of frame a stroke is drawn into, and the capsule test itself.  The arithmetic is stated once, in
+// gather kernels, the two kinds of frame a stroke is drawn into, and the capsule test itself; and what the whole-frame kernels (heat.hip,
+// anonymize.hip) share: how a thread reads and writes the 16 pixels of a row it owns.  The arithmetic is stated once, in
 // include/mcgaze_hip.h ("annotated frames out").
 #pragma once
 #include "common.hpp"
@@ -97,4 +98,57 @@ __device__ __forceinline__ mcg_arrow_desc arrow_plan_row(const typename Target::
     }
   }
   return d;
+}
+
+// ---------------------------------------------------------------- a thread's span of a pixel row (heat.hip, anonymize.hip)
+// W 32-bit words at p, which holds `bytes` bytes this thread may touch.  mode 2: 16-byte accesses, 1: 4-byte accesses (both: bytes == 4 W and
+// p aligned to the access), 0: byte by byte, nothing read or written at or behind p + bytes.
+template <int W>
+__device__ __forceinline__ void span_load(const unsigned char* __restrict__ p, unsigned (&w)[W], int mode, int bytes) {
+  if (mode == 2) {
+#pragma unroll
+    for (int i = 0; i < W / 4; ++i) {
+      const uint4 v = ((const uint4*)p)[i];
+      w[4 * i] = v.x; w[4 * i + 1] = v.y; w[4 * i + 2] = v.z; w[4 * i + 3] = v.w;
+    }
+  } else if (mode == 1) {
+#pragma unroll
+    for (int i = 0; i < W; ++i) w[i] = ((const unsigned*)p)[i];
+  } else {
+#pragma unroll
+    for (int i = 0; i < W; ++i) {
+      unsigned v = 0;
+#pragma unroll
+      for (int b = 0; b < 4; ++b)
+        if (4 * i + b < bytes) v |= (unsigned)p[4 * i + b] << (8 * b);
+      w[i] = v;
+    }
+  }
+}
+
+template <int W>
+__device__ __forceinline__ void span_store(unsigned char* __restrict__ p, const unsigned (&w)[W], int mode, int bytes) {
+  if (mode == 2) {
+#pragma unroll
+    for (int i = 0; i < W / 4; ++i) ((uint4*)p)[i] = make_uint4(w[4 * i], w[4 * i + 1], w[4 * i + 2], w[4 * i + 3]);
+  } else if (mode == 1) {
+#pragma unroll
+    for (int i = 0; i < W; ++i) ((unsigned*)p)[i] = w[i];
+  } else {
+#pragma unroll
+    for (int i = 0; i < W; ++i)
+#pragma unroll
+      for (int b = 0; b < 4; ++b)
+        if (4 * i + b < bytes) p[4 * i + b] = (unsigned char)(w[i] >> (8 * b));
+  }
+}
+
+__device__ __forceinline__ int span_mode(const void* base, int pitch, bool whole) {
+  const unsigned long long a = (unsigned long long)base | (unsigned long long)(unsigned)pitch;
+  return !whole ? 0 : !(a & 15) ? 2 : !(a & 3) ? 1 : 0;
+}
+
+__device__ __forceinline__ unsigned span_byte(const unsigned* w, int i) { return (w[i >> 2] >> (8 * (i & 3))) & 255u; }
+__device__ __forceinline__ void span_set_byte(unsigned* w, int i, unsigned v) {
+  w[i >> 2] = (w[i >> 2] & ~(255u << (8 * (i & 3)))) | (v << (8 * (i & 3)));
 }

@@ -13,7 +13,7 @@
 // leaves if none reaches min_level, and otherwise reads, blends and writes its 48 bytes (NV12: 16 + 16 + 16) in 16-byte accesses where the
 // plane's address and pitch allow, in 4-byte accesses where only those are aligned, byte by byte at the right edge and for any other
 // pitch.  A tile whose cells are all zero leaves before any pixel is read.  No atomics, no scratch.
-#include "draw_common.hpp"   // the bounds, PackedTarget / Nv12Target
+#include "draw_common.hpp"   // the bounds, PackedTarget / Nv12Target, the span accesses
 
 #define MCG_HEAT_MAX_CELLS (1 << 24)
 #define MCG_HEAT_SPAN 16                    // pixels of a row a thread owns
@@ -111,57 +111,6 @@ extern "C" int mcg_gaze_heat_add(mcg_stream s, const float* hit_dev, const int32
 }
 
 // ---------------------------------------------------------------- render
-// W 32-bit words at p, which holds `bytes` bytes this thread may touch.  mode 2: 16-byte accesses, 1: 4-byte accesses (both: bytes == 4 W and
-// p aligned to the access), 0: byte by byte, nothing read or written at or behind p + bytes.
-template <int W>
-__device__ __forceinline__ void heat_load(const unsigned char* __restrict__ p, unsigned (&w)[W], int mode, int bytes) {
-  if (mode == 2) {
-#pragma unroll
-    for (int i = 0; i < W / 4; ++i) {
-      const uint4 v = ((const uint4*)p)[i];
-      w[4 * i] = v.x; w[4 * i + 1] = v.y; w[4 * i + 2] = v.z; w[4 * i + 3] = v.w;
-    }
-  } else if (mode == 1) {
-#pragma unroll
-    for (int i = 0; i < W; ++i) w[i] = ((const unsigned*)p)[i];
-  } else {
-#pragma unroll
-    for (int i = 0; i < W; ++i) {
-      unsigned v = 0;
-#pragma unroll
-      for (int b = 0; b < 4; ++b)
-        if (4 * i + b < bytes) v |= (unsigned)p[4 * i + b] << (8 * b);
-      w[i] = v;
-    }
-  }
-}
-
-template <int W>
-__device__ __forceinline__ void heat_store(unsigned char* __restrict__ p, const unsigned (&w)[W], int mode, int bytes) {
-  if (mode == 2) {
-#pragma unroll
-    for (int i = 0; i < W / 4; ++i) ((uint4*)p)[i] = make_uint4(w[4 * i], w[4 * i + 1], w[4 * i + 2], w[4 * i + 3]);
-  } else if (mode == 1) {
-#pragma unroll
-    for (int i = 0; i < W; ++i) ((unsigned*)p)[i] = w[i];
-  } else {
-#pragma unroll
-    for (int i = 0; i < W; ++i)
-#pragma unroll
-      for (int b = 0; b < 4; ++b)
-        if (4 * i + b < bytes) p[4 * i + b] = (unsigned char)(w[i] >> (8 * b));
-  }
-}
-
-__device__ __forceinline__ int heat_mode(const void* base, int pitch, bool whole) {
-  const unsigned long long a = (unsigned long long)base | (unsigned long long)(unsigned)pitch;
-  return !whole ? 0 : !(a & 15) ? 2 : !(a & 3) ? 1 : 0;
-}
-
-__device__ __forceinline__ unsigned heat_byte(const unsigned* w, int i) { return (w[i >> 2] >> (8 * (i & 3))) & 255u; }
-__device__ __forceinline__ void heat_set_byte(unsigned* w, int i, unsigned v) {
-  w[i >> 2] = (w[i >> 2] & ~(255u << (8 * (i & 3)))) | (v << (8 * (i & 3)));
-}
 // (src (255 - a) + col a + 127) / 255: at most 255 * 255 + 127, the division a multiply and a shift
 __device__ __forceinline__ unsigned heat_blend(unsigned src, unsigned col, unsigned a) { return (src * (255u - a) + col * a + 127u) / 255u; }
 
@@ -229,51 +178,51 @@ __global__ __launch_bounds__(256) void heat_render_kernel(const typename Target:
   const int span = min(MCG_HEAT_SPAN, im.w - px0);                // pixels of the thread inside the picture
   const bool whole = span == MCG_HEAT_SPAN;
   if constexpr (R == 1) {
-    const int mode = heat_mode(im.src, im.pitch, whole);
+    const int mode = span_mode(im.src, im.pitch, whole);
     unsigned char* p = (unsigned char*)im.src + (size_t)py0 * im.pitch + (size_t)px0 * 3;
     unsigned w[12];
-    heat_load<12>(p, w, mode, 3 * span);
+    span_load<12>(p, w, mode, 3 * span);
 #pragma unroll
     for (int j = 0; j < MCG_HEAT_SPAN; ++j) {
       const int L = level[0][j];
       if (L >= min_level) {
         const unsigned c = colour[L], a = c >> 24;
 #pragma unroll
-        for (int ch = 0; ch < 3; ++ch) heat_set_byte(w, 3 * j + ch, heat_blend(heat_byte(w, 3 * j + ch), (c >> (8 * ch)) & 255u, a));
+        for (int ch = 0; ch < 3; ++ch) span_set_byte(w, 3 * j + ch, heat_blend(span_byte(w, 3 * j + ch), (c >> (8 * ch)) & 255u, a));
       }
     }
-    heat_store<12>(p, w, mode, 3 * span);
+    span_store<12>(p, w, mode, 3 * span);
   } else {
-    const int mode_y = heat_mode(im.y, im.pitch_y, whole), mode_uv = heat_mode(im.uv, im.pitch_uv, whole);
+    const int mode_y = span_mode(im.y, im.pitch_y, whole), mode_uv = span_mode(im.uv, im.pitch_uv, whole);
     // py0 even and < h, h even: both rows are inside; px0 even, w even: span is even and the pairs are whole
 #pragma unroll
     for (int r = 0; r < 2; ++r) {
       unsigned char* p = (unsigned char*)im.y + (size_t)(py0 + r) * im.pitch_y + px0;
       unsigned w[4];
-      heat_load<4>(p, w, mode_y, span);
+      span_load<4>(p, w, mode_y, span);
 #pragma unroll
       for (int j = 0; j < MCG_HEAT_SPAN; ++j) {
         const int L = level[r][j];
         if (L >= min_level) {
           const unsigned c = colour[L];
-          heat_set_byte(w, j, heat_blend(heat_byte(w, j), c & 255u, c >> 24));
+          span_set_byte(w, j, heat_blend(span_byte(w, j), c & 255u, c >> 24));
         }
       }
-      heat_store<4>(p, w, mode_y, span);
+      span_store<4>(p, w, mode_y, span);
     }
     unsigned char* q = (unsigned char*)im.uv + (size_t)(py0 >> 1) * im.pitch_uv + px0;
     unsigned w[4];
-    heat_load<4>(q, w, mode_uv, span);
+    span_load<4>(q, w, mode_uv, span);
 #pragma unroll
     for (int j = 0; j < MCG_HEAT_SPAN; j += 2) {
       const int L = max(max(level[0][j], level[0][j + 1]), max(level[1][j], level[1][j + 1]));   // the pair's level: the highest of its four
       if (L >= min_level) {
         const unsigned c = colour[L], a = c >> 24;
-        heat_set_byte(w, j, heat_blend(heat_byte(w, j), (c >> 8) & 255u, a));
-        heat_set_byte(w, j + 1, heat_blend(heat_byte(w, j + 1), (c >> 16) & 255u, a));
+        span_set_byte(w, j, heat_blend(span_byte(w, j), (c >> 8) & 255u, a));
+        span_set_byte(w, j + 1, heat_blend(span_byte(w, j + 1), (c >> 16) & 255u, a));
       }
     }
-    heat_store<4>(q, w, mode_uv, span);
+    span_store<4>(q, w, mode_uv, span);
   }
 }
 

@@ -22,7 +22,7 @@ import torch
 
 from .attention import END_VIDEO_ENDED, KIND_HEAD, KIND_REGION, MAX_COLUMNS, MAX_ROWS, _attention_options, _dwell_options, _heat_options, open_episodes
 from .engine import _upload_table
-from .arrows import OVERLAY_PALETTE, _label_options, _overlay_options, format_labels_host
+from .arrows import OVERLAY_PALETTE, _anon_params, _label_options, _overlay_options, format_labels_host
 from .pipeline import ARROW_COLOR, _track_motion, _track_params, letterbox_geometry
 
 CLUES = ('face', 'eyes', 'head')
@@ -870,7 +870,7 @@ def _add_heat(records, pipeline, device, num_frames, frame_hw, options):
 
 
 def run_head_video(engine, pipeline, frames, boxes_per_frame=None, max_len=100, batch_frames=448, expand=0.8, rgb=False, smooth=None, pixel_format='bgr',
-                   matrix='bt601', detections=None, track=None, attention=None, dwell=None, heat=None, draw=None):
+                   matrix='bt601', detections=None, track=None, attention=None, dwell=None, heat=None, anonymize=None, draw=None):
     """Steps 3-4 of the demo from what its users hold -- the video's frames and one head box per person per frame -- to per-person gaze:
     segment_tracks (cell 1), the head windows cut, resized and normalised on the device (pipeline.head_crops: cell 4's crop arithmetic and
     ``cfg.data.test.pipeline[1:]``), run_tracks (cell 4's loop, batched), head_arrows (cell 5's end points).
@@ -938,11 +938,25 @@ def run_head_video(engine, pipeline, frames, boxes_per_frame=None, max_len=100, 
     (pipeline.gaze_heat, mcg_gaze_heat_add; include/mcgaze_hip.h, "gaze heat map"), one call per frame over the records' target_hit, so the
     grid decays once per frame; one camera, cells of ``cell`` pixels over the size of frame 0.  The return value gains, as its LAST item, the
     final grid as a numpy array int32 [1, GH, GW] -- (records, heat), or (records, annotated, heat) with draw --, and with draw=True in the
-    dict that final grid is blended into every annotated frame first (pipeline.draw_heat), under the arrows, the overlay and the labels."""
+    dict that final grid is blended into every annotated frame first (pipeline.draw_heat), under the arrows, the overlay and the labels.
+    anonymize: None (everything above), True, or a dict of pipeline.anonymize_heads' options (expand, shape, cell, blocks, mode, color); it
+    needs ``draw`` (ValueError without): the faces under the records' head boxes are removed from the annotated frames
+    (include/mcgaze_hip.h, "anonymised heads"), FIRST in every drawing batch -- before the heat map, the arrows, the overlay and the labels
+    -- and on the copies: the crops were cut from the untouched frames, so ``frames`` and the records are exactly those of a run without
+    it.  It hides the heads the records hold: a head the detector missed stays visible."""
     smooth = check_smooth('run_head_video', smooth)
     attention = _attention_options('run_head_video', attention)
     dwell = _dwell_options('run_head_video', dwell, attention)
     heat = _heat_options('run_head_video', heat, attention, draw is not None)
+    if anonymize is not None and draw is None:
+        raise ValueError('run_head_video: anonymize changes the annotated frames; it needs draw')
+    if anonymize is not None:
+        anonymize = {} if anonymize is True else dict(anonymize)
+        if set(anonymize) - {'expand', 'shape', 'cell', 'blocks', 'mode', 'color'}:
+            raise ValueError(f"run_head_video(anonymize=...): True or a dict of expand, shape, cell, blocks, mode, color; got {sorted(anonymize)}")
+        _anon_params('run_head_video(anonymize=...)', **{k: v for k, v in anonymize.items() if k != 'color'})
+        if rgb and pixel_format == 'bgr' and anonymize.get('color') is not None:      # the frames hold R, G, B: the colour goes in in their order
+            anonymize['color'] = np.asarray(anonymize['color'])[..., ::-1]
     if (boxes_per_frame is None) == (detections is None):
         raise ValueError('run_head_video: give exactly one of boxes_per_frame and detections')
     tracker = None if track is None else _HeadTracker(pipeline, track, engine.device)
@@ -1049,10 +1063,14 @@ def run_head_video(engine, pipeline, frames, boxes_per_frame=None, max_len=100, 
         boxes = np.asarray([h[0] for heads in part for h in heads], dtype=np.float32).reshape(-1, 4)
         gaze = np.asarray([h[1] for heads in part for h in heads], dtype=np.float32).reshape(-1, 2)
         images = [frames[t] for t in range(t0, t0 + len(part))]
-        opts = drawing
+        opts, copy = drawing, drawing['copy']
+        if anonymize is not None:                      # first of all: the faces go before anything is drawn over them; what follows draws into THESE frames, in place
+            images, _ = pipeline.anonymize_heads(images, boxes, image_of, pixel_format=pixel_format, matrix=matrix, copy=copy, device=engine.device,
+                                                 **anonymize)
+            opts, copy = dict(drawing, copy=False), False
         if heat is not None and heat['draw']:          # first, under everything else (period 1: every picture shows the one camera); what follows draws into THESE frames, in place
             images = pipeline.draw_heat(images, heat_state, period=1, full_scale=heat['full_scale'], min_level=heat['min_level'], pixel_format=pixel_format,
-                                        matrix=matrix, copy=drawing['copy'], device=engine.device)
+                                        matrix=matrix, copy=copy, device=engine.device)
             opts = dict(drawing, copy=False)
         if overlay is None:
             imgs, _ = pipeline.draw_arrows(images, boxes, gaze, image_of, pixel_format=pixel_format, matrix=matrix, device=engine.device, **opts)

@@ -40,7 +40,8 @@ EXPORTS = ['mcg_abi_version', 'mcg_build_id', 'mcg_last_error', 'mcg_device_info
            'mcg_track_state_bytes', 'mcg_track_heads', 'mcg_track_heads_motion', 'mcg_live_slots', 'mcg_live_gate', 'mcg_live_lanes', 'mcg_live_gate_lanes',
            'mcg_deferred_pyramid_state', 'mcg_inner_block_neighbours', 'mcg_gaze_targets', 'mcg_gaze_dwell', 'mcg_gaze_targets_poly',
            'mcg_pointwise_stream', 'mcg_pointwise_dyn', 'mcg_pointwise_pair', 'mcg_draw_attention', 'mcg_draw_attention_nv12',
-           'mcg_format_labels', 'mcg_draw_labels', 'mcg_draw_labels_nv12', 'mcg_gaze_heat_add', 'mcg_draw_heat', 'mcg_draw_heat_nv12']
+           'mcg_format_labels', 'mcg_draw_labels', 'mcg_draw_labels_nv12', 'mcg_gaze_heat_add', 'mcg_draw_heat', 'mcg_draw_heat_nv12',
+           'mcg_anonymize_heads', 'mcg_anonymize_heads_nv12']
 LABEL_CHARS = 24                                                 # MCG_LABEL_CHARS
 LETTERBOX_U8, LETTERBOX_F16, LETTERBOX_F32 = 0, 1, 2             # enum order of include/mcgaze_hip.h
 
@@ -112,6 +113,10 @@ class StrokeDesc(C.Structure):
 
 class LabelDesc(C.Structure):
     _fields_ = [(n, C.c_int) for n in ('x', 'y', 'x0', 'y0', 'x1', 'y1', 'image', 'flag', 'len')] + [('color', C.c_uint), ('text', C.c_ubyte * LABEL_CHARS)]
+
+
+class AnonDesc(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ('image', 'flag', 'x0', 'y0', 'x1', 'y1', 'cx2', 'cy2', 'W', 'H', 'shift', 'shape')]
 
 
 class McgError(RuntimeError):
@@ -208,6 +213,8 @@ def load():
     lib.mcg_gaze_heat_add.argtypes = [vp, vp, vp, vp, vp, vp, i, vp, vp, i, i, i, i, i, i, i, i, vp, sz]
     lib.mcg_draw_heat.argtypes = [vp, vp, i, i, i, vp, vp, i, i, i, i, i, vp, i]
     lib.mcg_draw_heat_nv12.argtypes = lib.mcg_draw_heat.argtypes
+    lib.mcg_anonymize_heads.argtypes = [vp, vp, i, i, i, vp, vp, i, C.c_double, i, i, i, i, u8p, vp, vp]
+    lib.mcg_anonymize_heads_nv12.argtypes = lib.mcg_anonymize_heads.argtypes
     lib.mcg_gaze_dwell.argtypes =[vp, vp, vp, vp, vp, vp, i, i, i, i, i, vp, vp, i, vp, vp, vp, i, vp]
     lib.mcg_engine_set_option.argtypes = [vp, C.c_char_p, i]
     lib.mcg_engine_profile_start.argtypes = [vp, i]

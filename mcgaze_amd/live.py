@@ -30,7 +30,7 @@ import numpy as np
 import torch
 
 from . import lib as L
-from .arrows import LABEL_CHARS, _label_background, _label_options, _overlay_options, _overlay_palette, heat_lut
+from .arrows import LABEL_CHARS, _anon_params, _label_background, _label_options, _overlay_options, _overlay_palette, heat_lut
 from .attention import KIND_HEAD, PolyRegions, _attention_options, _dwell_options, _heat_options, region_label_rows
 from .engine import _upload_table
 from .harness import _host, check_smooth
@@ -365,11 +365,17 @@ class LiveGaze:
     tick gains ``heat`` int32 [Q, GH, GW] and ``heat_peak`` int32 [Q]: the LIVE device tensors (``LiveGaze.heat_state``), which later ticks
     go on updating; None before the first tick.  With draw=True (it needs ``draw``; ValueError without; heat=True draws where draw does) the
     grid as it stands after a frame's looks is blended into that frame's pictures FIRST (pipeline.draw_heat with full_scale and min_level),
-    under the arrows, the overlay and the labels.  Still no wait for the device, no copy to the host."""
+    under the arrows, the overlay and the labels.  Still no wait for the device, no copy to the host.
+    ANONYMIZE.  ``anonymize=None`` is everything above.  ``anonymize=True`` or a dict of pipeline.anonymize_heads' options (expand, shape,
+    cell, blocks, mode, color; it needs ``draw``; ValueError without) removes the faces from the returned frames (include/mcgaze_hip.h,
+    "anonymised heads"): one call per tick that returns frames, over the kept copies, from head_box and image_of of the gated rows -- a row
+    that is not valid has image_of -1 and hides nothing -- BEFORE the heat map is blended and anything is drawn.  The network has read the
+    frames by then: every table comes back as without it.  It hides the heads the tracker holds: a head the detector missed stays visible.
+    Still no wait for the device, no copy to the host."""
 
     def __init__(self, engine_or_model, pipeline, cameras, slots=16, clip_len=7, stride=4, expand=0.8, match_iou=0.3, max_age=5, smooth=None,
                  pixel_format='bgr', draw=False, matrix='bt601', rgb=False, person_threshold=0.5, max_decode_windows=None, lanes=None, motion=None,
-                 attention=None, dwell=None, overlay=None, labels=None, heat=None):
+                 attention=None, dwell=None, overlay=None, labels=None, heat=None, anonymize=None):
         self.S, self.match_iou, self.max_age = _track_params(slots, match_iou, max_age)
         _track_motion(motion, 'LiveGaze')
         self.motion = motion
@@ -384,6 +390,13 @@ class LiveGaze:
         self.overlay = _overlay_options('LiveGaze', overlay, draw, attention)
         self.labels = _label_options('LiveGaze', labels, draw)
         self.heat, self.heat_state = _heat_options('LiveGaze', heat, attention, draw), None
+        if anonymize is not None and not draw:
+            raise ValueError('LiveGaze: anonymize changes the returned frames; it needs draw')
+        self.anonymize = None if anonymize is None else {} if anonymize is True else dict(anonymize)
+        if self.anonymize is not None:
+            if set(self.anonymize) - {'expand', 'shape', 'cell', 'blocks', 'mode', 'color'}:
+                raise ValueError(f'LiveGaze: anonymize is True or a dict of expand, shape, cell, blocks, mode, color; got {sorted(self.anonymize)}')
+            _anon_params('LiveGaze(anonymize=...)', **{k: v for k, v in self.anonymize.items() if k != 'color'})
         self.pipe, self.expand, self.draw = pipeline, float(expand), bool(draw)
         self.frame_options = dict(pixel_format=pixel_format, matrix=matrix)
         self.rgb = bool(rgb)
@@ -603,6 +616,8 @@ class LiveGaze:
         if self.dwell is not None:
             out.update(self._dwell(out, k))
         images = [f for t in range(self.emitted, self.emitted + k) for f in self.kept.pop(t)] if self.draw else None
+        if self.anonymize is not None and k:                     # first: into the kept copies, in place, before anything is blended or drawn over the faces
+            self.pipe.anonymize_heads(images, out['head_box'].view(-1, 4), out['image_of'].view(-1), device=self.dev, **self.frame_options, **self.anonymize)
         if self.heat is not None:
             out.update(self._heat(out, k, images))
         if self.draw:

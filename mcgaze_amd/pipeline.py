@@ -25,7 +25,7 @@ What the device calls of ``DevicePipeline`` share is stated once, and a further 
 of head_crops and the two drawing calls; ``_on_device`` / ``_there`` decide where a table lives and move a host table that stands next to a
 device one; ``_gaze_operand`` is the gaze table with its row stride; ``_region_operands`` decides the region tables of gaze_targets and
 draw_attention as a group; ``_drawing_checked``, ``_drawing_placed`` and ``_drawing_upload`` are, in the order of a call, what draw_arrows,
-draw_attention and draw_labels do to frames and rows; and ``_device_table`` keeps the record tables of device frames on the device.
+draw_attention, draw_labels and anonymize_heads do to frames and rows; and ``_device_table`` keeps the record tables of device frames on the device.
 
 Randomness: the reference's ``CenterCrop(crop_type='relative_range')`` draws the crop size from the global numpy RNG at TEST
 time too (transforms.py:1126-1130), and ``RandomFlip(flip_ratio=0.0)`` consumes one more uniform
@@ -47,6 +47,7 @@ from .arrows import (ARROW_COLOR, ARROW_COORD, ARROW_SIDE, _arrow_colors, _arrow
 from .arrows import LABEL_CHARS, LABEL_FONT, _label_background, _label_ints, _label_params, _label_rate, _label_text, label_plan
 from .arrows import draw_labels_host, encode_labels, format_labels_host  # noqa: F401  (re-exported beside draw_arrows_host, for users of pipeline.*)
 from .arrows import HEAT_LUT, draw_heat_host, heat_lut  # noqa: F401
+from .arrows import _anon_color, _anon_params, anonymize_heads_host, anonymize_plan_host  # noqa: F401
 from .attention import (HEAT_KINDS, HeatState, _heat_cell, _heat_grid, _heat_params, _heat_scale, gaze_heat_host,  # noqa: F401
                         heat_grid_shape)
 from .attention import PolyRegions, _check_counts, _holds_polygon, _poly_tables, _region_tables, _target_params, gaze_targets_host, region_polygons  # noqa: F401
@@ -291,6 +292,7 @@ _ARROW_WORDS = _ARROW.itemsize // 4
 _LABEL = np.dtype([(f, np.int32) for f in ('x', 'y', 'x0', 'y0', 'x1', 'y1', 'image', 'flag', 'len')] + [('color', np.uint32), ('text', np.uint8, (LABEL_CHARS,))])
 assert _LABEL.itemsize == C.sizeof(L.LabelDesc) == 64 and all(_LABEL.fields[n][1] == getattr(L.LabelDesc, n).offset for n in _LABEL.names)
 _LABEL_WORDS = _LABEL.itemsize // 4
+_ANON_WORDS = C.sizeof(L.AnonDesc) // 4
 
 
 class _NoDraw:
@@ -1215,6 +1217,54 @@ class DevicePipeline:
             L.check(entry(vp(call.main.cuda_stream), vp(images_ptr), len(out), h_max, w_max, vp(state.heat.data_ptr()), vp(full.data_ptr()), cams, GH, GW,
                           state.cell_shift, int(period), vp(lut_ptr), min_level), entry.__name__)
         return out
+
+    def anonymize_heads(self, images, boxes, image_of, expand=0.125, shape='ellipse', cell=None, blocks=8, mode='mosaic', color=(0, 0, 0),
+                        pixel_format='bgr', matrix='bt601', copy=False, device='cuda:0', stream=None):
+        """The faces under the head boxes removed from the frames on the device (mcg_anonymize_heads / mcg_anonymize_heads_nv12: a plan launch
+        and a render launch over the tiles under heads) -- ``arrows.anonymize_heads_host`` bit for bit: every pixel of the ellipse inscribed in
+        the grown box (shape='box': of the box) becomes the mean of a coarse cell of the frame, or ``color`` with mode='fill'.  Call it after
+        ``head_crops`` has read the frames and before anything is drawn on top.  It hides the heads it is GIVEN: a head the detector missed
+        stays visible.
+
+        images, pixel_format, matrix, copy: ``draw_arrows``' -- a CUDA frame is changed IN PLACE (copy=True: a packed clone is), a numpy frame
+        goes up through the staging ring.  boxes [n,4] x1 y1 x2 y2, image_of [n]: numpy arrays or device tensors, read where they are.
+        expand: the box grows by this share of its size on every side (0 .. 4).  cell: None -- every head gets about ``blocks`` (1 .. 64) cells
+        across, a power of two of 2 .. 64 pixels each, so a far head is as unreadable as a near one -- or one power of two in 2 .. 64 for all.
+        color: one (B, G, R) triple on the host, converted once by ``bgr_to_yuv`` for NV12; read only with mode='fill'.  The defaults are
+        CONVENTIONS, not tuned on data.  Where boxes overlap the coarser cell wins.  Calling twice is not idempotent: the second call
+        averages what the first one wrote.
+        Host tables are checked before anything is launched (ValueError: an image_of out of range, a box that is not finite, empty, or
+        beyond +-8191 once grown); device tables are never read back -- such rows come back with flag 2 and change no byte.  With device
+        frames in place, device tables and the frame table cached by a first call, the call touches the host nowhere and can be captured
+        in a graph.
+        -> (images on the device, in order; flags [n] int32 on the device: 0 usable -- possibly no pixel --, 2 unusable)."""
+        lib = L.load()
+        who = 'anonymize_heads'
+        nv12, _ = _pixel_format(pixel_format, matrix)
+        expand, shape_id, cell_shift, blocks, mode_id = _anon_params(who, expand, shape, cell, blocks, mode)
+        one = _anon_color(who, color, nv12, matrix)
+        entry = lib.mcg_anonymize_heads_nv12 if nv12 else lib.mcg_anonymize_heads
+        checked = _drawing_checked(who, 'heads', entry, images, boxes, None, image_of, nv12, device)
+        dev, n = checked[0], checked[-1]
+        with _call_scope(self._ring, dev, stream) as call:
+            out, pixels, in_place, table, h_max, w_max, boxes, _, _, image_of = _drawing_placed(who, checked, nv12, copy, None, 0)
+            if isinstance(boxes, np.ndarray) and n:                # image_of on the device is not read back: every frame's size then passes
+                sizes = [(int(r['h']), int(r['w'])) for r in table] if isinstance(image_of, np.ndarray) else [(2, 2)]
+                bad = anonymize_plan_host(boxes, image_of if isinstance(image_of, np.ndarray) else np.zeros(n, np.int32), sizes, expand, shape, cell,
+                                          blocks, nv12)['flag'] == 2
+                if bad.any():
+                    k = int(np.flatnonzero(bad)[0])
+                    raise ValueError(f'{who}: head {k} cannot be hidden: box {boxes[k].tolist()} -- x2 <= x1 or y2 <= y1, beyond +-{ARROW_COORD} once grown, '
+                                     f'or a frame without pixels')
+            images_ptr, boxes_ptr, image_of_ptr = self._drawing_upload(call, nv12, table, pixels, in_place, (boxes, image_of))
+            flags = torch.empty(n, dtype=torch.int32, device=dev)
+            if n:
+                plan = torch.empty(n, _ANON_WORDS, dtype=torch.int32, device=dev)
+                vp = C.c_void_p
+                L.check(entry(vp(call.main.cuda_stream), vp(images_ptr), len(out), h_max, w_max, vp(boxes_ptr), vp(image_of_ptr), n, expand, shape_id,
+                              cell_shift, blocks, mode_id, (C.c_ubyte * 3)(*[int(v) for v in one]), vp(plan.data_ptr()), vp(flags.data_ptr())),
+                        entry.__name__)
+        return out, flags
 
     def letterbox(self, frames, new_shape=640, stride=32, auto=True, scaleup=True, dtype=torch.float16, rgb=False, pixel_format='bgr', matrix='bt601',
                   device='cuda:0', stream=None):

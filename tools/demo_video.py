@@ -47,7 +47,11 @@ on data).
 --heat [CELL,RADIUS], with --attention: WHERE in the picture the looks land (harness.run_head_video(heat=...), pipeline.gaze_heat on the
 device): the hit points of every frame splatted into a grid of CELL-pixel cells (a power of two, default 8) with a radius of RADIUS cells
 (default 2).  With --draw the final grid is blended into every annotated frame, under the arrows (pipeline.draw_heat); --heat-out FILE.npy
-writes the grid, int32 [1, GH, GW]."""
+writes the grid, int32 [1, GH, GW].
+--anonymize [BLOCKS], with --draw: the faces under the head boxes are removed from the written frames on the device
+(harness.run_head_video(anonymize=...), pipeline.anonymize_heads), before anything is drawn over them -- a mosaic of about BLOCKS cells
+across every head (default 8) under the ellipse inscribed in the grown box; --anonymize-shape box covers the whole box.  It hides the heads
+that were detected: a head the detector missed stays visible."""
 import argparse
 import importlib
 import json
@@ -195,7 +199,15 @@ def main(argv=None):
     ap.add_argument('--heat', nargs='?', const='', default=None, metavar='CELL,RADIUS',
                     help='--attention with where the looks land: a heat map of CELL-pixel cells (8) and a splat of RADIUS cells (2), drawn under --draw')
     ap.add_argument('--heat-out', default=None, metavar='FILE.npy', help='write the final grid of --heat, int32 [1, GH, GW]')
+    ap.add_argument('--anonymize', nargs='?', const=8, type=int, default=None, metavar='BLOCKS',
+                    help='--draw with the faces removed first: a mosaic of about BLOCKS cells across every head (8)')
+    ap.add_argument('--anonymize-shape', default='ellipse', choices=['ellipse', 'box'], help='what of the grown head box --anonymize covers')
     a = ap.parse_args(argv)
+    if a.anonymize is not None and a.draw is None:
+        raise SystemExit('--anonymize changes the frames --draw writes: it needs --draw')
+    if a.anonymize is not None and not 1 <= a.anonymize <= 64:
+        raise SystemExit(f'--anonymize takes BLOCKS in 1 .. 64, got {a.anonymize}')
+    anonymize = None if a.anonymize is None else dict(blocks=a.anonymize, shape=a.anonymize_shape)
     if (a.heat is not None or a.heat_out is not None) and not a.attention:
         raise SystemExit('--heat and --heat-out belong to --attention')
     if a.heat_out is not None and a.heat is None:
@@ -276,7 +288,7 @@ def main(argv=None):
     pipe = DevicePipeline(model.cfg.data.test.pipeline)
     res = harness.run_head_video(model.engine(), pipe, frames, per_frame, max_len=a.max_len, batch_frames=a.batch_frames, rgb=True,
                                  smooth=a.smooth, pixel_format='bgr' if a.nv12 is None else 'nv12', matrix=a.matrix, detections=detections, draw=draw,
-                                 track=track, attention=attention, dwell=dwell, heat=heat)
+                                 track=track, attention=attention, dwell=dwell, heat=heat, anonymize=anonymize)
     as_json = lambda v: list(v) if isinstance(v, tuple) else v
     if heat is not None:
         res, grid = res[:-1], res[-1]
