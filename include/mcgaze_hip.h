@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define MCG_ABI_VERSION 19
+#define MCG_ABI_VERSION 20
 
 enum { MCG_OK = 0, MCG_ERR_ARG = 1, MCG_ERR_HIP = 2, MCG_ERR_UNSUPPORTED = 3, MCG_ERR_WORKSPACE = 4 };
 /* MCG_F16X3: the parity-grade fast mode.  Activations, biases and every non-GEMM kernel are exactly those of MCG_F32 (4-byte
@@ -136,6 +136,20 @@ int mcg_bottleneck_x3(mcg_stream s, const float* x, const float* src2, const voi
 size_t mcg_conv3x3_wino_x3_weight_bytes(int Cin, int Cout, int g);
 int mcg_conv3x3_wino_x3(mcg_stream s, const float* x, const void* u, const float* bias, float* y, int frames, int H, int W,
                         int Cin, int Cout, int relu, int tile, float wscale, int g);
+/* ABI 20: the BLOCK tile of the same conv as a stand-alone operator (wino_x3w_blocks_kernel through launch_wino_x3_blocks, the deferred FPN
+ * P2 conv of mcg_decoder_forward_deferred), for tests and measurements.  x, u (g = 2), bias, y, relu, wscale as above.  block_list (device)
+ * holds *block_count (device) ids of 8 x 8-pixel output blocks, id = (frame * (H / 8) + block row) * (W / 8) + block column, in any order;
+ * the pixels of the listed blocks are written with the bits mcg_conv3x3_wino_x3 writes there, every other pixel of y is left alone;
+ * *block_count == 0 writes nothing.  max_blocks: the capacity of block_list (>= *block_count, >= 1); it sizes the persistent grid and is
+ * not compared with the count on the device.  THE IDS MUST BE DISTINCT AND INSIDE [0, frames * (H / 8) * (W / 8)): the kernel does not guard
+ * them (an id outside addresses outside x and y; a repeated id is two workgroups storing the same pixels), and the marking kernels below
+ * produce no others.  H and W must be multiples of 8, Cin % 32 == 0, Cout % 128 == 0 and the operands within 2 GiB, W is not limited to 62:
+ * MCG_ERR_UNSUPPORTED otherwise (the engine reaches multiples of 8 only: frames are multiples of 32).  grid_cap: 0 = the product's
+ * persistent grid (one workgroup per unit of four blocks x 128 channels up to the compute units); else a host-side limit on the number of
+ * workgroups, so that a short list walks several units per workgroup.  No kernel reads it. */
+int mcg_conv3x3_wino_x3_blocks(mcg_stream s, const float* x, const void* u, const float* bias, float* y, int frames, int H, int W,
+                               int Cin, int Cout, int relu, float wscale, const int* block_list, const int* block_count, int max_blocks,
+                               int grid_cap);
 
 /* The streaming 1x1 kernels as stand-alone operators (ABI 19; pw_single.hpp, pw_single_x3.hpp, pw_pair.hpp): the engine takes them from
  * 64 Ki rows on and the decoder from 256 tokens on; these entries run the same launchers at ANY M >= 1, for tests and measurements.  They
@@ -194,6 +208,18 @@ int mcg_roi_align(mcg_stream s, mcg_dtype dt, const void* const feats[4], const 
 int mcg_roi_align_indexed(mcg_stream s, mcg_dtype dt, const void* const feats[4], const int feat_h[4], const int feat_w[4],
                           const int strides[4], int C, const float* boxes, int num_boxes, int boxes_per_frame,
                           const int32_t* frame_of, int pyramid_frames, void* out, int32_t* levels_out);
+/* ABI 20: roi_mark_kernel as a stand-alone operator (launch_roi_mark, the first step of a deferred decoder stage), for tests and
+ * measurements: which 8 x 8-pixel blocks of ONE pyramid level mcg_roi_align reads for these boxes.  boxes as above; level, H, W, stride: the
+ * deferred level (the engine: 0, P2's size, 4), at most 64 blocks per axis.  state [frames * by_n * bx_n] (by_n = ceil(H / 8), bx_n =
+ * ceil(W / 8), frames = ceil(num_boxes / boxes_per_frame)), list of the same capacity and count (one int) are DEVICE buffers of the caller.
+ * A box that map_roi_levels routes to another level does nothing.  Otherwise the box's blocks are {lo >> 3, hi >> 3 of every valid y sample}
+ * x {the same of every valid x sample} of frame = box row / boxes_per_frame, with lo, hi and valid as mcg_roi_align computes them
+ * (roi_sample.hpp: a tap of weight zero counts, a box without a valid sample on either axis has none); block id = (frame * by_n + block row)
+ * * bx_n + block column.  A block whose state is 0 gets state 1 and is appended, list[(*count)++] = id; a block whose state is already
+ * non-zero is not listed again -- so no id appears twice, within a call or over calls that share state.  The order of the list is
+ * unspecified.  *count is added to, not reset: the caller zeroes state and count. */
+int mcg_roi_mark_blocks(mcg_stream s, const float* boxes, int num_boxes, int boxes_per_frame, int level, int H, int W, int stride,
+                        int* state, int* list, int* count);
 
 /* ---------------------------------------------------------------- decoder stage / gaze head / whole path
  * Weight tables are arrays of device pointers indexed by the enums below.  Matrices are
@@ -451,12 +477,17 @@ int mcg_decoder_forward_ragged(mcg_engine* e, mcg_stream s, const void* const py
  * mcg_deferred_pyramid_state (test / measurement aid): where the slot's P2 inner map [N][H/4][W/4][256] lies (NULL: P2 not deferred) and,
  * where *lateral_deferred is 1, the inner-block flags [*blocks], counts [stages] and lists [stages][*blocks] (else NULL); any output
  * pointer may be NULL.  mcg_inner_block_neighbours: the host twin of the inner-block rule -- the blocks (id itself included, at most nine)
- * whose inner pixels output block id of a [.][H][W] map reads; returns how many were written to out. */
+ * whose inner pixels output block id of a [.][H][W] map reads; returns how many were written to out.
+ * mcg_inner_mark_blocks (ABI 20; tests and measurements): inner_mark_kernel as a stand-alone operator (launch_inner_mark).  out_list holds
+ * min(*out_count, nblk) output block ids (device; an id outside [0, nblk) is skipped); every block mcg_inner_block_neighbours names for one
+ * of them whose state is 0 gets state 1 and is appended, list[(*count)++] = id, in unspecified order; a block whose state is non-zero is not
+ * listed.  nblk = frames * ceil(H / 8) * ceil(W / 8): the length of state and the capacity of out_list and list.  *count is added to. */
 size_t mcg_deferred_pyramid_bytes(const mcg_engine* e, int num_frames, int H, int W);
 int mcg_deferred_pyramid_levels(const mcg_engine* e, void* slot, int num_frames, int H, int W, void* levels[4], int* deferred);
 int mcg_deferred_pyramid_state(const mcg_engine* e, void* slot, int num_frames, int H, int W, void** inner, int** flags, int** counts,
                                int** lists, int* blocks, int* lateral_deferred);
 int mcg_inner_block_neighbours(int id, int H, int W, int out[9]);
+int mcg_inner_mark_blocks(mcg_stream s, const int* out_list, const int* out_count, int H, int W, int nblk, int* state, int* list, int* count);
 int mcg_backbone_fpn_forward_deferred(mcg_engine* e, mcg_stream s, const float* img, int num_frames, int H, int W, int chunk_frames,
                                       void* slot, size_t slot_bytes, void* ws, size_t ws_bytes);
 int mcg_decoder_forward_deferred(mcg_engine* e, mcg_stream s, void* slot, size_t slot_bytes, int num_frames, int clip_length, int H, int W,

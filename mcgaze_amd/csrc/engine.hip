@@ -805,6 +805,28 @@ extern "C" int mcg_conv3x3_wino_x3(mcg_stream s, const float* x, const void* u, 
   if (launch_wino_x3((hipStream_t)s, wp, tile - 1, g)) { mcg_set_error("mcg_conv3x3_wino_x3: launch failed"); return MCG_ERR_HIP; }
   return MCG_OK;
 }
+// The block tile as a stand-alone operator (tests and measurements): launch_wino_x3_blocks over the caller's list, never another kernel
+extern "C" int mcg_conv3x3_wino_x3_blocks(mcg_stream s, const float* x, const void* u, const float* bias, float* y, int frames, int H, int W,
+                                          int Cin, int Cout, int relu, float wscale, const int* block_list, const int* block_count,
+                                          int max_blocks, int grid_cap) {
+  MCG_CHECK_ARG(x && u && y && block_list && block_count, "mcg_conv3x3_wino_x3_blocks: null pointer");
+  MCG_CHECK_ARG(max_blocks > 0 && grid_cap >= 0, "mcg_conv3x3_wino_x3_blocks: max_blocks must be positive and grid_cap >= 0 (max_blocks=%d grid_cap=%d)",
+                max_blocks, grid_cap);
+  if (H <= 0 || W <= 0 || H % 8 != 0 || W % 8 != 0 || !wino_x3_blocks_applicable(frames, H, W, Cin, Cout)) {
+    mcg_set_error("mcg_conv3x3_wino_x3_blocks: unsupported shape (frames=%d %dx%d, %d -> %d channels): H %% 8, W %% 8, Cin %% 32, Cout %% 128, operands within 2 GiB",
+                  frames, H, W, Cin, Cout);
+    return MCG_ERR_UNSUPPORTED;
+  }
+  WinoParams wp;
+  memset(&wp, 0, sizeof(wp));
+  wp.x = x; wp.u = u; wp.bias = bias; wp.y = y; wp.H = H; wp.W = W; wp.frames = frames; wp.Cin = Cin; wp.Cout = Cout; wp.relu = relu;
+  wp.wscale = wscale;
+  if (launch_wino_x3_blocks((hipStream_t)s, wp, block_list, block_count, max_blocks, grid_cap)) {
+    mcg_set_error("mcg_conv3x3_wino_x3_blocks: launch failed");
+    return MCG_ERR_HIP;
+  }
+  return MCG_OK;
+}
 
 // The streaming 1x1 kernels as stand-alone operators: the launchers' own dispatch tables at any M >= 1, never another kernel
 extern "C" int mcg_pointwise_stream(mcg_stream s, mcg_dtype dt, const void* a, const void* wf, const float* bias, const void* res, void* y,

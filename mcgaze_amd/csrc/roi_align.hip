@@ -186,6 +186,21 @@ int launch_roi_mark(hipStream_t s, const float* boxes, int num_boxes, int boxes_
   MCG_CHECK_LAUNCH("roi_mark");
   return MCG_OK;
 }
+// The two marking kernels as stand-alone operators (tests and measurements): the launchers above over the caller's device buffers
+extern "C" int mcg_roi_mark_blocks(mcg_stream s, const float* boxes, int num_boxes, int boxes_per_frame, int level, int H, int W, int stride,
+                                   int* state, int* list, int* count) {
+  MCG_CHECK_ARG(boxes && state && list && count, "mcg_roi_mark_blocks: null pointer");
+  MCG_CHECK_ARG(num_boxes > 0 && boxes_per_frame > 0, "mcg_roi_mark_blocks: empty box set");
+  MCG_CHECK_ARG(level >= 0 && level <= 3 && H > 0 && W > 0 && stride > 0, "mcg_roi_mark_blocks: bad level (level=%d %dx%d stride=%d)", level, H, W, stride);
+  return launch_roi_mark((hipStream_t)s, boxes, num_boxes, boxes_per_frame, level, H, W, stride, state, list, count);
+}
+extern "C" int mcg_inner_mark_blocks(mcg_stream s, const int* out_list, const int* out_count, int H, int W, int nblk, int* state, int* list,
+                                     int* count) {
+  MCG_CHECK_ARG(out_list && out_count && state && list && count, "mcg_inner_mark_blocks: null pointer");
+  MCG_CHECK_ARG(H > 0 && W > 0 && nblk > 0 && nblk % (((H + 7) / 8) * ((W + 7) / 8)) == 0,
+                "mcg_inner_mark_blocks: nblk = frames * blocks per frame (nblk=%d, %dx%d pixels)", nblk, H, W);
+  return launch_inner_mark((hipStream_t)s, out_list, out_count, H, W, nblk, state, list, count);
+}
 
 int launch_roi_align(hipStream_t s, mcg_dtype dt, const void* const feats[4], const int feat_h[4], const int feat_w[4],
                      const int strides[4], int C, const float* boxes, int num_boxes, int boxes_per_frame, const int32_t* frame_of,

@@ -1,6 +1,8 @@
 // The sample arithmetic of roi_align_kernel (roi_align.hip), shared with roi_mark_kernel, which flags the blocks of a deferred pyramid
 // level that RoIAlign will read: both take level and coordinates from these functions, so the flagged footprint is by construction the
-// set of pixels read -- boxes outside the image, degenerate and NaN boxes included.
+// set of pixels read -- boxes outside the image, degenerate and NaN boxes included.  Checked against roi_align_kernel itself by
+// tests/test_gpu_defer_blocks.py: a map that is NaN outside the flagged blocks gives the same RoIAlign bits, and the flagged set equals
+// a host statement of the footprint (tests/defer_cases.py), so it is neither short of a block nor larger than the 8 x 8 cover.
 #pragma once
 
 // map_roi_levels (single_level_roi_extractor.py:51-54), with the NaN guard: a NaN box reads level 0

@@ -463,7 +463,8 @@ __device__ __forceinline__ void buf_load16(u32x4v& dst, uint32_t voffset, const 
 // BLOCKS (8 rows x 4 pairs = 32 pairs each) taken from a device list, so that a conv can compute only the blocks somebody reads.  The
 // window holds, per block, its 10 rows (one halo row above and below) of ONE 1 KiB piece (16 pixels from the block's first column - 1:
 // the block's 10 input columns), 40 pieces in all; only where a row and a pair lie differs from the raster tile, so a block's bits are
-// those of the same pixels in wino_x3w_kernel (tests/test_gpu_fpn_deferred.py).
+// those of the same pixels in wino_x3w_kernel (tests/test_gpu_fpn_deferred.py through the engine; tests/test_gpu_defer_blocks.py on the
+// kernel alone, through mcg_conv3x3_wino_x3_blocks).
 template <int NB, bool BLK>
 __device__ __forceinline__ void wino_x3w_tile(const WinoParams& p, const int logical) {
   using namespace wnx;
@@ -810,9 +811,10 @@ static inline int launch_wino_x3_nb(hipStream_t s, const WinoParams& p, int g, i
 }
 // Block tile (8 x 8-pixel blocks, F(2,3)): the shapes whose window fits (any W a block's 16-pixel piece serves) and whose operands fit the
 // buffer descriptors -- the same arithmetic as launch_wino_x3 on them.  blk_grid: workgroups of the persistent launch.
+// cap: 0 = that grid; else a host-side limit on it (tests: several units per workgroup on a small list); no kernel reads it.
 static inline bool wino_x3_blocks_applicable(int frames, int H, int W, int Cin, int Cout) { return wino_x3_operands_ok(frames, H, W, Cin, Cout); }
 static inline int wino_x3_blocks_per_frame(int H, int W) { return ((H + 7) / 8) * ((W + 7) / 8); }
-static inline int launch_wino_x3_blocks(hipStream_t s, WinoParams p, const int* list, const int* count, int max_blocks) {
+static inline int launch_wino_x3_blocks(hipStream_t s, WinoParams p, const int* list, const int* count, int max_blocks, int cap = 0) {
   int cus;
   if (kernel_ready<wino_x3w_blocks_kernel>(wnx::W_LDS, &cus)) return 1;
   p.PW = (p.W + 1) / 2;
@@ -821,7 +823,8 @@ static inline int launch_wino_x3_blocks(hipStream_t s, WinoParams p, const int* 
   p.bpf = wino_x3_blocks_per_frame(p.H, p.W);
   p.blk_list = list; p.blk_count = count;
   const int units = (max_blocks + 3) / 4 * p.n_tiles;
-  const int grid = units < cus ? units : cus / 16 * 16;
+  int grid = units < cus ? units : cus / 16 * 16;
+  if (cap > 0 && grid > cap) grid = cap;
   hipLaunchKernelGGL(wino_x3w_blocks_kernel, dim3(grid > 0 ? grid : 1), dim3(256), wnx::W_LDS, s, p);
   return hipGetLastError() == hipSuccess ? 0 : 1;
 }

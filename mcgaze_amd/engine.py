@@ -114,8 +114,9 @@ def pointwise_stream(a, wf, bias, N, relu=False, residual=None, residual_mode=L.
                      many_slices=False, blocks=None, grid_cap=0, out=None):
     """The streaming 1x1 kernels at any M (mcg_pointwise_stream; many_slices=True: dynamic_layer's forms, mcg_pointwise_dyn, N = 32768):
     a [M, K] (16-bit, or f32 with split=True), wf / wscale from pointwise_weights, bias f32 [N] -> y [M, N].  residual [M, N] (RES_ADD) or
-    [frames, Hr, Wr, N] with out_hw = (Ho, Wo) and M = frames * Ho * Wo (RES_UPSAMPLE_ADD).  blocks: a sequence of 8 x 8 block ids -- the
-    list form, which writes the listed blocks only (give ``out``).  grid_cap: include/mcgaze_hip.h.  out: a buffer of at least M rows."""
+    [frames, Hr, Wr, N] with out_hw = (Ho, Wo) and M = frames * Ho * Wo (RES_UPSAMPLE_ADD).  blocks: a sequence of 8 x 8 block ids, or a
+    (list, count) pair of device int32 tensors as inner_mark_blocks returns -- the list form, which writes the listed blocks only (give
+    ``out``).  grid_cap: include/mcgaze_hip.h.  out: a buffer of at least M rows."""
     _require_gpu()
     lib = L.load()
     M, K = a.shape
@@ -131,10 +132,7 @@ def pointwise_stream(a, wf, bias, N, relu=False, residual=None, residual_mode=L.
     Hr, Wr = (residual.shape[1], residual.shape[2]) if mode == L.RES_UPSAMPLE_ADD else (Ho, Wo)
     blist = bcount = None
     if blocks is not None:
-        ids = _flat_ints(blocks, 'blocks must be a flat sequence', 'blocks must be integers', False)
-        blist = torch.zeros(max(len(ids), 1), dtype=torch.int32, device=a.device)
-        blist[:len(ids)] = torch.from_numpy(ids.astype(np.int32)).to(a.device)
-        bcount = torch.tensor([len(ids)], dtype=torch.int32, device=a.device)
+        blist, bcount = _block_list(blocks, a.device)
     L.check(lib.mcg_pointwise_stream(_stream(), code, _ptr(a), _ptr(wf), _ptr(bias), _ptr(residual.contiguous() if residual is not None else None),
                                      _ptr(y), M, K, N, int(relu), mode, Ho, Wo, Hr, Wr, wscale, _ptr(blist), _ptr(bcount), grid_cap),
             'mcg_pointwise_stream')
@@ -162,15 +160,54 @@ def conv3x3_wino(x, w, bias=None, relu=False, tile=0, g=2):
     g = 4: the F(4,3) form of the same kernel (maps whose width is a multiple of 4, at least 16)."""
     _require_gpu()
     lib = L.load()
-    from .packing import pow2_prescale, wino_pack
     N, H, W, Cin = x.shape
     Cout = w.shape[0]
-    ws, wscale = pow2_prescale(w.cpu())
-    u = wino_pack(ws, g=g).to(x.device)
+    u, wscale = wino_weights(w, g, x.device)
     assert u.numel() * 2 == lib.mcg_conv3x3_wino_x3_weight_bytes(Cin, Cout, g), (u.numel(), Cin, Cout)
     y = torch.empty(N, H, W, Cout, dtype=torch.float32, device=x.device)
     L.check(lib.mcg_conv3x3_wino_x3(_stream(), _ptr(x.contiguous()), _ptr(u), _ptr(bias), _ptr(y), N, H, W, Cin, Cout, int(relu), tile, wscale, g), 'mcg_conv3x3_wino_x3')
     return y
+
+
+def _block_list(blocks, device):
+    """A host sequence of block ids, or a (list, count) pair of device int32 tensors (count: one element; the kernels read *count entries
+    of list) -> that pair on ``device``."""
+    if isinstance(blocks, tuple) and len(blocks) == 2 and all(isinstance(t, torch.Tensor) for t in blocks):
+        blist, bcount = blocks
+        for t in (blist, bcount):
+            assert t.dtype == torch.int32 and t.is_contiguous() and t.device == torch.device(device), (t.dtype, t.device)
+        assert blist.dim() == 1 and blist.numel() >= 1 and bcount.numel() == 1
+        return blist, bcount
+    ids = _flat_ints(blocks, 'blocks must be a flat sequence', 'blocks must be integers', False)
+    blist = torch.zeros(max(len(ids), 1), dtype=torch.int32, device=device)
+    blist[:len(ids)] = torch.from_numpy(ids.astype(np.int32)).to(device)
+    return blist, torch.tensor([len(ids)], dtype=torch.int32, device=device)
+
+
+def wino_weights(w, g=2, device='cuda'):
+    """w OHWI f32 [Cout,3,3,Cin] -> (u, wscale): the weight operand of conv3x3_wino / conv3x3_wino_blocks (packing.wino_pack of the
+    pow2_prescale'd tensor) and the descale factor."""
+    from .packing import pow2_prescale, wino_pack
+    ws, wscale = pow2_prescale(w.cpu())
+    return wino_pack(ws, g=g).to(device), wscale
+
+
+def conv3x3_wino_blocks(x, packed, blocks, out, bias=None, relu=False, grid_cap=0):
+    """The block tile of conv3x3_wino (mcg_conv3x3_wino_x3_blocks; wino_x3w_blocks_kernel): x NHWC f32 with H and W multiples of 8, packed =
+    wino_weights(w) (g = 2), out NHWC f32 [N,H,W,Cout] -- the listed 8 x 8 blocks of it are written, the rest is left alone.  blocks: a
+    sequence of block ids or a (list, count) pair of device int32 tensors (roi_mark_blocks); the capacity of list sizes the grid.  THE IDS
+    MUST BE DISTINCT AND INSIDE [0, N * (H / 8) * (W / 8)) and count at most the capacity: the kernel does not guard them."""
+    _require_gpu()
+    lib = L.load()
+    N, H, W, Cin = x.shape
+    u, wscale = packed
+    Cout = out.shape[-1]
+    assert x.dtype == torch.float32 and x.is_contiguous() and out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (N, H, W, Cout)
+    assert u.numel() * 2 == lib.mcg_conv3x3_wino_x3_weight_bytes(Cin, Cout, 2), (u.numel(), Cin, Cout)
+    blist, bcount = _block_list(blocks, x.device)
+    L.check(lib.mcg_conv3x3_wino_x3_blocks(_stream(), _ptr(x), _ptr(u), _ptr(bias), _ptr(out), N, H, W, Cin, Cout, int(relu), wscale,
+                                           _ptr(blist), _ptr(bcount), blist.numel(), grid_cap), 'mcg_conv3x3_wino_x3_blocks')
+    return out
 
 
 def bottleneck_x3(x, src2, wstream, bias, cn, nsrc, trace=None):
@@ -203,6 +240,45 @@ def stem(img, w_stem, bias, dtype, flags=0, split=False):
 def roi_align(feats, boxes, strides=(4, 8, 16, 32)):
     """feats: 4 NHWC levels; boxes [N,P,4] f32 -> ([N*P,49,C], levels int32 [N*P]).  mcg_roi_align."""
     return roi_align_indexed(feats, boxes, None, strides)
+
+
+def _mark_buffers(nblk, state, blist, count, device):
+    """The caller's (state, list, count) of a marking call, or fresh zeroed ones: int32 device tensors, state and list nblk long."""
+    z = lambda n: torch.zeros(n, dtype=torch.int32, device=device)
+    state, blist, count = (z(nblk) if state is None else state), (z(nblk) if blist is None else blist), (z(1) if count is None else count)
+    for t in (state, blist, count):
+        assert t.dtype == torch.int32 and t.is_contiguous() and t.device == torch.device(device), (t.dtype, t.device)
+    assert state.numel() == nblk and blist.numel() >= nblk and count.numel() == 1, (state.numel(), blist.numel(), nblk)
+    return state, blist, count
+
+
+def roi_mark_blocks(boxes, hw, level=0, stride=4, state=None, blist=None, count=None):
+    """Which 8 x 8 blocks of ONE pyramid level roi_align reads for these boxes (mcg_roi_mark_blocks; roi_mark_kernel): boxes [N,P,4] f32,
+    hw = (H, W) of the level -> (state, list, count), int32 device tensors: state [N * by_n * bx_n] flags, list the ids newly flagged in
+    unspecified order, count [1] how many.  Given buffers are added to (a block whose state is set is not listed again; count is not
+    reset; list must have room for count + the new ids); None: fresh zeroed ones."""
+    _require_gpu()
+    lib = L.load()
+    N, P = boxes.shape[:2]
+    H, W = hw
+    b = boxes.contiguous().float()
+    state, blist, count = _mark_buffers(N * ((H + 7) // 8) * ((W + 7) // 8), state, blist, count, b.device)
+    L.check(lib.mcg_roi_mark_blocks(_stream(), _ptr(b), N * P, P, level, H, W, stride, _ptr(state), _ptr(blist), _ptr(count)), 'mcg_roi_mark_blocks')
+    return state, blist, count
+
+
+def inner_mark_blocks(out_list, out_count, hw, frames, state=None, blist=None, count=None):
+    """The inner blocks the listed output blocks' 3 x 3 convs read (mcg_inner_mark_blocks; inner_mark_kernel): out_list / out_count as
+    roi_mark_blocks returns them (out_list at least frames * by_n * bx_n long), hw = (H, W) of the map -> (state, list, count) as there:
+    the listed blocks and their in-frame neighbours that ``state`` did not hold."""
+    _require_gpu()
+    lib = L.load()
+    H, W = hw
+    nblk = frames * ((H + 7) // 8) * ((W + 7) // 8)
+    state, blist, count = _mark_buffers(nblk, state, blist, count, out_list.device)
+    _mark_buffers(nblk, state, out_list, out_count, out_list.device)
+    L.check(lib.mcg_inner_mark_blocks(_stream(), _ptr(out_list), _ptr(out_count), H, W, nblk, _ptr(state), _ptr(blist), _ptr(count)), 'mcg_inner_mark_blocks')
+    return state, blist, count
 
 
 def roi_align_indexed(feats, boxes, frame_of, strides=(4, 8, 16, 32)):

@@ -11,7 +11,7 @@ LIB_PATH = os.environ.get('MCGAZE_LIB') or os.path.join(_HERE, 'libmcgaze_hip.so
 
 MCG_OK = 0
 MCG_F32, MCG_BF16, MCG_F16X3, MCG_F16 = 0, 1, 2, 3
-ABI_VERSION = 19
+ABI_VERSION = 20
 RES_NONE, RES_ADD, RES_UPSAMPLE_ADD = 0, 1, 2
 FLAG_STAGED_GEMM, FLAG_NO_SPECIALISED, FLAG_NO_ATTN_BLOCK = 1, 2, 4
 
@@ -41,7 +41,7 @@ EXPORTS = ['mcg_abi_version', 'mcg_build_id', 'mcg_last_error', 'mcg_device_info
            'mcg_deferred_pyramid_state', 'mcg_inner_block_neighbours', 'mcg_gaze_targets', 'mcg_gaze_dwell', 'mcg_gaze_targets_poly',
            'mcg_pointwise_stream', 'mcg_pointwise_dyn', 'mcg_pointwise_pair', 'mcg_draw_attention', 'mcg_draw_attention_nv12',
            'mcg_format_labels', 'mcg_draw_labels', 'mcg_draw_labels_nv12', 'mcg_gaze_heat_add', 'mcg_draw_heat', 'mcg_draw_heat_nv12',
-           'mcg_anonymize_heads', 'mcg_anonymize_heads_nv12']
+           'mcg_anonymize_heads', 'mcg_anonymize_heads_nv12', 'mcg_roi_mark_blocks', 'mcg_inner_mark_blocks', 'mcg_conv3x3_wino_x3_blocks']
 LABEL_CHARS = 24                                                 # MCG_LABEL_CHARS
 LETTERBOX_U8, LETTERBOX_F16, LETTERBOX_F32 = 0, 1, 2             # enum order of include/mcgaze_hip.h
 
@@ -223,6 +223,9 @@ def load():
     lib.mcg_bench_backbone_levels.argtypes = [vp, vp, i, i, i, C.POINTER(vp)]
     lib.mcg_bottleneck_x3.argtypes = [vp, vp, vp, vp, vp, vp, vp, i, i, i, i, i, i, vp]
     lib.mcg_conv3x3_wino_x3.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, i, i, i, C.c_float, i]
+    lib.mcg_conv3x3_wino_x3_blocks.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, i, i, C.c_float, vp, vp, i, i]
+    lib.mcg_roi_mark_blocks.argtypes = [vp, vp, i, i, i, i, i, i, vp, vp, vp]
+    lib.mcg_inner_mark_blocks.argtypes = [vp, vp, vp, i, i, i, vp, vp, vp]
     lib.mcg_conv3x3_wino_x3_weight_bytes.restype = sz
     lib.mcg_pointwise_stream.argtypes = [vp, i, vp, vp, vp, vp, vp, i, i, i, i, i, i, i, i, i, C.c_float, vp, vp, i]
     lib.mcg_pointwise_dyn.argtypes = [vp, i, vp, vp, vp, vp, i, C.c_float, i]

@@ -99,7 +99,7 @@ def test_header_binding_and_library_agree_on_the_new_entry():
     assert len(lib.mcg_gaze_targets.argtypes) == 18
     declared = re.search(r'\bint mcg_gaze_targets\(([^;]*)\);', hdr).group(1)
     assert len(declared.split(',')) == 18
-    assert lib.mcg_abi_version() == L.ABI_VERSION == 19 and '#define MCG_ABI_VERSION 19' in hdr
+    assert lib.mcg_abi_version() == L.ABI_VERSION == 20 and '#define MCG_ABI_VERSION 20' in hdr
     assert 'attend.hip' in open(os.path.join(ROOT, 'mcgaze_amd', 'csrc', 'Makefile')).read()
     for phrase in ('gaze targets', 'not tuned on data', 'Out of scope', 'REAL centre'):
         assert phrase in hdr, phrase

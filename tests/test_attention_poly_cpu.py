@@ -178,7 +178,7 @@ def test_header_binding_and_library_agree_on_the_new_entry():
     assert len(lib.mcg_gaze_targets_poly.argtypes) == 20
     declared = re.search(r'\bint mcg_gaze_targets_poly\(([^;]*)\);', hdr).group(1)
     assert len(declared.split(',')) == 20
-    assert lib.mcg_abi_version() == L.ABI_VERSION == 19 and '#define MCG_ABI_VERSION 19' in hdr
+    assert lib.mcg_abi_version() == L.ABI_VERSION == 20 and '#define MCG_ABI_VERSION 20' in hdr
     assert '#define MCG_ATTEND_POLY_VERTS 32' in hdr
     for phrase in ('gaze targets, polygonal regions', 'USABLE REGION', 'INSIDE (even-odd rule)', 'CROSSINGS', 'Winding does not matter'):
         assert phrase in hdr, phrase

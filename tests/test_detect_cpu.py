@@ -196,7 +196,7 @@ def test_header_binding_and_library_agree_on_the_new_entries():
     assert re.search(r'\bint mcg_detect_heads\(mcg_stream s, const float\* pred_dev,', hdr)
     for name, nargs in (('mcg_detect_heads_workspace_bytes', 2), ('mcg_detect_heads', 24)):
         assert name in L.EXPORTS and hasattr(lib, name) and len(getattr(lib, name).argtypes) == nargs
-    assert lib.mcg_abi_version() == L.ABI_VERSION == 19 and '#define MCG_ABI_VERSION 19' in hdr
+    assert lib.mcg_abi_version() == L.ABI_VERSION == 20 and '#define MCG_ABI_VERSION 20' in hdr
     assert 'detect.hip' in open(os.path.join(ROOT, 'mcgaze_amd', 'csrc', 'Makefile')).read()
     # 32 bytes per anchor (rounded up to 64 anchors) per image; sizes the entry refuses give 0
     assert lib.mcg_detect_heads_workspace_bytes(3, 1025) == 3 * 1088 * 32 and lib.mcg_detect_heads_workspace_bytes(0, 5) == 0

@@ -112,8 +112,8 @@ def test_surface():
     hdr = open(os.path.join(ROOT, 'include', 'mcgaze_hip.h')).read()
     assert re.search(r'\bint mcg_merge_windows\(mcg_stream s, const float\* gaze, const float\* boxes, const float\* scores, int num_frames', hdr)
     assert 'tools/test_gaze360_gaze.py:129-206' in hdr and 'multiclue_gaze_roi_head.py:360-363' in hdr
-    assert 'mcg_merge_windows' in L.EXPORTS and L.ABI_VERSION == 19
-    assert int(re.search(r'#define MCG_ABI_VERSION (\d+)', hdr).group(1)) == 19
+    assert 'mcg_merge_windows' in L.EXPORTS and L.ABI_VERSION == 20
+    assert int(re.search(r'#define MCG_ABI_VERSION (\d+)', hdr).group(1)) == 20
     lib = L.load()
     assert hasattr(lib, 'mcg_merge_windows') and len(lib.mcg_merge_windows.argtypes) == 13
     assert 'merge.hip' in open(os.path.join(ROOT, 'mcgaze_amd', 'csrc', 'Makefile')).read()

@@ -202,7 +202,7 @@ def test_header_binding_and_library_agree_on_the_new_entries():
     for name in ('mcg_draw_gaze_arrows', 'mcg_draw_gaze_arrows_nv12'):
         assert re.search(r'\bint ' + name + r'\(', hdr) and name in L.EXPORTS and hasattr(lib, name)
         assert len(getattr(lib, name).argtypes) == 18
-    assert lib.mcg_abi_version() == L.ABI_VERSION == 19 and '#define MCG_ABI_VERSION 19' in hdr
+    assert lib.mcg_abi_version() == L.ABI_VERSION == 20 and '#define MCG_ABI_VERSION 20' in hdr
     assert P._ARROW.itemsize == 80 and 'draw.hip' in open(os.path.join(ROOT, 'mcgaze_amd', 'csrc', 'Makefile')).read()
     assert P.DevicePipeline.draw_arrows is not None
 

@@ -164,7 +164,7 @@ def test_header_binding_and_library_agree_on_the_new_entry():
     assert 'mcg_gaze_dwell' in L.EXPORTS and re.search(r'\bint mcg_gaze_dwell\(', hdr) and hasattr(lib, 'mcg_gaze_dwell')
     declared = re.search(r'\bint mcg_gaze_dwell\(([^;]*)\);', hdr).group(1)
     assert len(lib.mcg_gaze_dwell.argtypes) == len(declared.split(',')) == 19
-    assert lib.mcg_abi_version() == L.ABI_VERSION == 19 and '#define MCG_ABI_VERSION 19' in hdr
+    assert lib.mcg_abi_version() == L.ABI_VERSION == 20 and '#define MCG_ABI_VERSION 20' in hdr
     assert 'dwell.hip' in open(os.path.join(ROOT, 'mcgaze_amd', 'csrc', 'Makefile')).read()
     assert hdr.index('gaze dwell (additions') > hdr.index('gaze targets (additions')
     for phrase in ('AT MOST ONE END', 'not tuned on data', 'modulo 2^32', 'ascending (frame, column)'):

@@ -136,10 +136,10 @@ def test_arrow_end_points_worked_by_hand():
 
 def test_abi_18_registers_the_head_crop_entry():
     hdr = open(os.path.join(ROOT, 'include', 'mcgaze_hip.h')).read()
-    assert int(re.search(r'#define MCG_ABI_VERSION (\d+)', hdr).group(1)) == L.ABI_VERSION == 19
+    assert int(re.search(r'#define MCG_ABI_VERSION (\d+)', hdr).group(1)) == L.ABI_VERSION == 20
     assert 'mcg_preprocess_head_crops' in L.EXPORTS and re.search(r'\bint mcg_preprocess_head_crops\s*\(', hdr)
     lib = L.load()
-    assert lib.mcg_abi_version() == 19 and hasattr(lib, 'mcg_preprocess_head_crops')
+    assert lib.mcg_abi_version() == 20 and hasattr(lib, 'mcg_preprocess_head_crops')
     # the ctypes and numpy records are the header's struct: pointer, three ints
     fields = re.search(r'typedef struct mcg_image_desc \{(.*?)\} mcg_image_desc;', hdr, re.S).group(1)
     assert re.findall(r'\b(src|h|w|pitch)\b(?=[,;])', fields) == [n for n, _ in L.ImageDesc._fields_]

@@ -214,7 +214,7 @@ def test_live_gaze_and_run_head_video_check_heat_before_anything_else():
 # ---------------------------------------------------------------- the library
 def test_abi_line_exports_and_header():
     hdr = open(os.path.join(ROOT, 'include', 'mcgaze_hip.h')).read()
-    assert int(re.search(r'#define MCG_ABI_VERSION (\d+)', hdr).group(1)) == L.ABI_VERSION == 19
+    assert int(re.search(r'#define MCG_ABI_VERSION (\d+)', hdr).group(1)) == L.ABI_VERSION == 20
     lib = L.load()
     for name in ('mcg_gaze_heat_add', 'mcg_draw_heat', 'mcg_draw_heat_nv12'):
         assert name in L.EXPORTS and re.search(r'\bint %s\(' % name, hdr) and hasattr(lib, name)

@@ -235,7 +235,7 @@ def test_region_label_rows_follow_the_pictures_draw_attention_draws_into():
 # ---------------------------------------------------------------- the library entries
 def test_header_exports_and_abi():
     hdr = open(os.path.join(ROOT, 'include', 'mcgaze_hip.h')).read()
-    assert int(re.search(r'#define MCG_ABI_VERSION (\d+)', hdr).group(1)) == L.ABI_VERSION == 19
+    assert int(re.search(r'#define MCG_ABI_VERSION (\d+)', hdr).group(1)) == L.ABI_VERSION == 20
     assert int(re.search(r'#define MCG_LABEL_CHARS (\d+)', hdr).group(1)) == L.LABEL_CHARS == R.LABEL_CHARS == 24
     lib = L.load()
     for name in ('mcg_format_labels', 'mcg_draw_labels', 'mcg_draw_labels_nv12'):

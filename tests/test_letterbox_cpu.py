@@ -152,7 +152,7 @@ def test_header_binding_and_library_agree_on_the_new_entries():
     assert re.search(r'\bint mcg_letterbox_frames_nv12\(mcg_stream stream, const mcg_nv12_letterbox_desc\* frames_dev,', hdr)
     for name, nargs in (('mcg_letterbox_frames', 8), ('mcg_letterbox_frames_nv12', 9)):
         assert name in L.EXPORTS and hasattr(lib, name) and len(getattr(lib, name).argtypes) == nargs
-    assert lib.mcg_abi_version() == L.ABI_VERSION == 19 and '#define MCG_ABI_VERSION 19' in hdr
+    assert lib.mcg_abi_version() == L.ABI_VERSION == 20 and '#define MCG_ABI_VERSION 20' in hdr
     assert re.search(r'enum \{ MCG_LETTERBOX_U8 = 0, MCG_LETTERBOX_F16 = 1, MCG_LETTERBOX_F32 = 2 \};', hdr)
     assert (L.LETTERBOX_U8, L.LETTERBOX_F16, L.LETTERBOX_F32) == (0, 1, 2)
     # the records the pipeline writes are the header's structs: a frame descriptor, then top and left

@@ -302,6 +302,6 @@ def test_livegaze_validates_lanes_before_it_builds_anything():
 
 
 def test_the_abi_is_unchanged_and_the_entries_are_exported():
-    assert L.ABI_VERSION == 19 and L.load().mcg_abi_version() == 19
+    assert L.ABI_VERSION == 20 and L.load().mcg_abi_version() == 20
     assert 'mcg_live_lanes' in L.EXPORTS and 'mcg_live_gate_lanes' in L.EXPORTS
     assert hasattr(L.load(), 'mcg_live_lanes') and hasattr(L.load(), 'mcg_live_gate_lanes')

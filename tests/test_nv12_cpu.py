@@ -79,9 +79,9 @@ def test_coefficient_tables_are_pinned():
 
 def test_abi_18_registers_the_nv12_entries_and_structs():
     hdr = open(os.path.join(ROOT, 'include', 'mcgaze_hip.h')).read()
-    assert int(re.search(r'#define MCG_ABI_VERSION (\d+)', hdr).group(1)) == L.ABI_VERSION == 19
+    assert int(re.search(r'#define MCG_ABI_VERSION (\d+)', hdr).group(1)) == L.ABI_VERSION == 20
     lib = L.load()
-    assert lib.mcg_abi_version() == 19
+    assert lib.mcg_abi_version() == 20
     for name in ('mcg_preprocess_frames_nv12', 'mcg_preprocess_head_crops_nv12'):
         assert name in L.EXPORTS and re.search(r'\bint %s\s*\(' % name, hdr) and hasattr(lib, name)
     # the ctypes structs are the header's: same fields in the same order, and the sizes a C compiler gives them (LP64: 8-byte pointers, 4-byte ints)

@@ -281,7 +281,7 @@ def test_header_binding_makefile_and_library_agree_on_the_new_entries():
     for name in ('mcg_draw_attention', 'mcg_draw_attention_nv12'):
         assert re.search(r'\bint ' + name + r'\(', hdr) and name in L.EXPORTS and hasattr(lib, name)
         assert len(getattr(lib, name).argtypes) == 32
-    assert lib.mcg_abi_version() == L.ABI_VERSION == 19 and '#define MCG_ABI_VERSION 19' in hdr
+    assert lib.mcg_abi_version() == L.ABI_VERSION == 20 and '#define MCG_ABI_VERSION 20' in hdr
     for phrase in ('attention overlay (additions to ABI 19; nothing above changes)', 'workspace_bytes >= 96 * (m + 2 n) + 256 * m', 'ANCHOR', 'region_active[p][j]'):
         assert phrase in hdr, phrase
     assert C.sizeof(L.StrokeDesc) == 96 and 'overlay.hip' in open(os.path.join(ROOT, 'mcgaze_amd', 'csrc', 'Makefile')).read()

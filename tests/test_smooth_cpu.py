@@ -171,7 +171,7 @@ def test_boundary():
                      r'double alpha, float\* out\);', hdr)
     assert 'tools/calculate_mae_gaze360.py:16-29' in hdr      # the reference citation
     assert 'mcg_smooth_gaze' in L.EXPORTS
-    assert L.ABI_VERSION == 19 and int(re.search(r'#define MCG_ABI_VERSION (\d+)', hdr).group(1)) == 19
+    assert L.ABI_VERSION == 20 and int(re.search(r'#define MCG_ABI_VERSION (\d+)', hdr).group(1)) == 20
     assert 'smooth.hip' in open(os.path.join(ROOT, 'mcgaze_amd', 'csrc', 'Makefile')).read()
     lib = L.load()
     assert hasattr(lib, 'mcg_smooth_gaze') and len(lib.mcg_smooth_gaze.argtypes) == 7

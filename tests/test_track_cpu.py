@@ -323,7 +323,7 @@ def test_header_binding_and_library_agree_on_the_new_entries():
     assert re.search(r'\bsize_t mcg_track_state_bytes\(int num_sequences, int slots\);', hdr)
     for name, nargs in (('mcg_track_heads', 17), ('mcg_track_state_bytes', 2)):
         assert name in L.EXPORTS and hasattr(lib, name) and len(getattr(lib, name).argtypes) == nargs
-    assert lib.mcg_abi_version() == L.ABI_VERSION == 19
+    assert lib.mcg_abi_version() == L.ABI_VERSION == 20
     for slots in (1, 16, 64):                                     # the published layout: a 16-byte header, 32 bytes per slot
         assert lib.mcg_track_state_bytes(3, slots) == 3 * 4 * P.track_state_words(slots) == 3 * (16 + 32 * slots)
     assert lib.mcg_track_state_bytes(1, 0) == 0 and lib.mcg_track_state_bytes(1, 65) == 0 and lib.mcg_track_state_bytes(-1, 4) == 0

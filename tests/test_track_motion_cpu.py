@@ -208,7 +208,7 @@ def test_header_binding_and_library_agree_on_the_motion_entry():
     assert re.search(r'\bint mcg_track_heads_motion\(mcg_stream s, const float\* boxes_dev, long long frame_stride, const int32_t\* counts_dev,', hdr)
     assert re.search(r'int max_age, double velocity_gain, double coast_decay,\s+void\* state_dev,', hdr) and 'float* state_boxes_dev' in hdr
     assert 'mcg_track_heads_motion' in L.EXPORTS and hasattr(lib, 'mcg_track_heads_motion') and len(lib.mcg_track_heads_motion.argtypes) == 20
-    assert lib.mcg_abi_version() == L.ABI_VERSION == 19
+    assert lib.mcg_abi_version() == L.ABI_VERSION == 20
     assert 'The reserved words are neither read nor\n * written.' in hdr                         # the plain entry's contract stands
 
 
