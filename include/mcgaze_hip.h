@@ -150,6 +150,16 @@ int mcg_conv3x3_wino_x3(mcg_stream s, const float* x, const void* u, const float
 int mcg_conv3x3_wino_x3_blocks(mcg_stream s, const float* x, const void* u, const float* bias, float* y, int frames, int H, int W,
                                int Cin, int Cout, int relu, float wscale, const int* block_list, const int* block_count, int max_blocks,
                                int grid_cap);
+/* Addition to ABI 20 (nothing that existed changes): the FRAME-LIST tile of the same conv as a stand-alone operator (wino_x3w_frames_kernel through launch_wino_x3_frames, the deferred
+ * FPN P3 .. P5 convs of mcg_decoder_forward_deferred), for tests and measurements.  x, u (g = 2), bias, y as above; no ReLU, wscale = 1.
+ * frame_list (device, capacity `frames`) holds *frame_count (device) frame indices in any order: every pixel of a listed frame is written
+ * with the bits mcg_conv3x3_wino_x3 writes there, every other frame of y is left alone; *frame_count == 0 writes nothing.  The count is
+ * clamped to `frames` and an index outside [0, frames) is skipped on the device; THE INDICES MUST BE DISTINCT (a repeated one is two
+ * workgroups storing the same pixels; the marking kernel below produces no others).  Maps of 2 <= W <= 30 whose rows of one 128-pair tile
+ * fit the window buffer, Cin % 32 == 0, Cout % 128 == 0, operands within 2 GiB: MCG_ERR_UNSUPPORTED otherwise.  grid_cap as above (units
+ * are (list entry, 128-pair tile of the frame, 128 channels)). */
+int mcg_conv3x3_wino_x3_frames(mcg_stream s, const float* x, const void* u, const float* bias, float* y, int frames, int H, int W,
+                               int Cin, int Cout, const int* frame_list, const int* frame_count, int grid_cap);
 
 /* The streaming 1x1 kernels as stand-alone operators (ABI 19; pw_single.hpp, pw_single_x3.hpp, pw_pair.hpp): the engine takes them from
  * 64 Ki rows on and the decoder from 256 tokens on; these entries run the same launchers at ANY M >= 1, for tests and measurements.  They
@@ -220,6 +230,12 @@ int mcg_roi_align_indexed(mcg_stream s, mcg_dtype dt, const void* const feats[4]
  * unspecified.  *count is added to, not reset: the caller zeroes state and count. */
 int mcg_roi_mark_blocks(mcg_stream s, const float* boxes, int num_boxes, int boxes_per_frame, int level, int H, int W, int stride,
                         int* state, int* list, int* count);
+/* Addition to ABI 20: the frame marking of the same kernel alone (levels deferred by whole frames, engine option fpn_levels_deferred), for tests and
+ * measurements.  num_boxes is a multiple of boxes_per_frame; state [frames], list [frames] and count (one int) are DEVICE buffers of the
+ * caller.  A box that map_roi_levels routes to `level` (0 .. 3) lists its frame = box row / boxes_per_frame: a frame whose state is 0 gets
+ * state 1 and is appended, list[(*count)++] = frame; a frame whose state is non-zero is not listed again.  Order unspecified; *count is
+ * added to, not reset. */
+int mcg_roi_mark_frames(mcg_stream s, const float* boxes, int num_boxes, int boxes_per_frame, int level, int* state, int* list, int* count);
 
 /* ---------------------------------------------------------------- decoder stage / gaze head / whole path
  * Weight tables are arrays of device pointers indexed by the enums below.  Matrices are
@@ -417,7 +433,11 @@ void mcg_engine_destroy(mcg_engine* e);
  *                     decoder as well and computed only for the 8 x 8 blocks the deferred output conv reads -- the listed blocks and their
  *                     neighbours inside the frame.  The trunk then writes C2 and the P3 inner map into the slot.  Bit-identical; 0 = the dense
  *                     lateral in the trunk, launch for launch.  Not to be changed between the two calls of a pair
- *   range_audit       0/1 DEBUG (MCG_F32 / MCG_F16X3; default 0): after every activation tensor the trunk writes, a counting kernel tallies the
+ *   fpn_levels_deferred 0 / 1 / mask (default 1), honoured only where fpn_deferred holds: the output convs of P3 .. P5 are left to the decoder and
+ *                     computed per FRAME, for the frames in which a box of some stage reads the level.  1 = the default set (P5 alone: the only level
+ *                     a 224-pixel frame's boxes leave unread, profiles/fpn_levels_deferred_*.md); a mask of 2 (P3) | 4 (P4) | 8 (P5) names the
+ *                     levels; 0 = dense in the trunk, launch for launch.  Bit-identical.  Not to be changed between the two calls of a pair
+ *   range_audit      0/1 DEBUG (MCG_F32 / MCG_F16X3; default 0): after every activation tensor the trunk writes, a counting kernel tallies the
  *                     values beyond the fp16 range (|x| > 65504: an f16x3 operand half would saturate there) and the non-finite ones;
  *                     read and reset with mcg_engine_range_audit.  Turning it on allocates the counters (the library's only allocation,
  *                     at option time); it costs a pass over every activation, so it is off in the product path. */
@@ -481,11 +501,19 @@ int mcg_decoder_forward_ragged(mcg_engine* e, mcg_stream s, const void* const py
  * mcg_inner_mark_blocks (ABI 20; tests and measurements): inner_mark_kernel as a stand-alone operator (launch_inner_mark).  out_list holds
  * min(*out_count, nblk) output block ids (device; an id outside [0, nblk) is skipped); every block mcg_inner_block_neighbours names for one
  * of them whose state is 0 gets state 1 and is appended, list[(*count)++] = id, in unspecified order; a block whose state is non-zero is not
- * listed.  nblk = frames * ceil(H / 8) * ceil(W / 8): the length of state and the capacity of out_list and list.  *count is added to. */
+ * listed.  nblk = frames * ceil(H / 8) * ceil(W / 8): the length of state and the capacity of out_list and list.  *count is added to.
+ * Addition to ABI 20, option fpn_levels_deferred (0 = off, 1 = the engine's default set -- P5 --, else a mask of 2 = P3 | 4 = P4 | 8 = P5; only where P2
+ * is deferred): the output conv of each such level is left to the decoder as well, by whole FRAMES.  The slot then holds that level's inner
+ * map (written there by the trunk), a flag per frame and one frame list per stage; before a stage's RoIAlign the mark launch lists the frames
+ * one of the stage's boxes reads on the level that no earlier stage listed, and the conv runs over that list.  Frames of a level nobody reads
+ * are never written.  mcg_deferred_pyramid_frame_state (test / measurement aid): level 1 .. 3's flags [N], counts [stages] and lists
+ * [stages][N] where *frame_deferred is 1 (else NULL). */
 size_t mcg_deferred_pyramid_bytes(const mcg_engine* e, int num_frames, int H, int W);
 int mcg_deferred_pyramid_levels(const mcg_engine* e, void* slot, int num_frames, int H, int W, void* levels[4], int* deferred);
 int mcg_deferred_pyramid_state(const mcg_engine* e, void* slot, int num_frames, int H, int W, void** inner, int** flags, int** counts,
                                int** lists, int* blocks, int* lateral_deferred);
+int mcg_deferred_pyramid_frame_state(const mcg_engine* e, void* slot, int num_frames, int H, int W, int level, int** flags, int** counts,
+                                     int** lists, int* frame_deferred);
 int mcg_inner_block_neighbours(int id, int H, int W, int out[9]);
 int mcg_inner_mark_blocks(mcg_stream s, const int* out_list, const int* out_count, int H, int W, int nblk, int* state, int* list, int* count);
 int mcg_backbone_fpn_forward_deferred(mcg_engine* e, mcg_stream s, const float* img, int num_frames, int H, int W, int chunk_frames,

@@ -17,6 +17,7 @@ import sys
 RULES = {
     'wino_x3w_kernel': dict(scratch=0, vgpr_spill=0, unit='engine'),   # unit: the translation unit that instantiates it -- the gate must SEE it there
     'wino_x3w_blocks_kernel': dict(scratch=0, vgpr_spill=0, unit='engine'),   # the same loads, block-list tile (deferred FPN P2)
+    'wino_x3w_frames_kernel': dict(scratch=0, vgpr_spill=0, unit='engine'),   # the same loads, frame-list tile (deferred FPN P3 .. P5)
     # no hand-issued loads, but a double-precision row walk that is meant to live in registers: scratch would be a cost nobody looks for
     'gaze_targets_kernel': dict(scratch=0, vgpr_spill=0, unit='attend'),
     'gaze_targets_poly_kernel': dict(scratch=0, vgpr_spill=0, unit='attend'),   # the previous vertex is carried in registers: no local array

@@ -31,7 +31,7 @@ int launch_init_queries(hipStream_t s, mcg_dtype dt, const float* init_boxes, co
 bool roi_mark_supported(int H, int W);
 int launch_defer_clear(hipStream_t s, int* p, int n);
 int launch_roi_mark(hipStream_t s, const float* boxes, int num_boxes, int boxes_per_frame, int level, int H, int W, int stride, int* state,
-                    int* list, int* count);
+                    int* list, int* count, int* const* frame_state, int* const* frame_list, int* const* frame_count);
 int launch_inner_mark(hipStream_t s, const int* out_list, const int* out_count, int H, int W, int nblk, int* state, int* list, int* count);
 
 struct mcg_engine {
@@ -53,6 +53,10 @@ struct mcg_engine {
                                // (mcg_*_deferred, mcg_clip_forward); 0 = every level dense in the trunk.  Same bits either way
   int fpn_lateral_deferred = 1; // with fpn_deferred: the P2 lateral (+ top-down add) is left to the decoder too and computed for the listed blocks
                                // and their neighbours only (pw_single_x3_blocks_kernel); 0 = the dense lateral in the trunk.  Same bits either way
+  int fpn_levels_deferred = 1; // with fpn_deferred: output convs of P3 .. P5 left to the decoder and computed per FRAME, for the frames some box of a stage
+                               // reads on that level (wino_x3w_frames_kernel).  0 = dense in the trunk, 1 = the default set kDeferLevelsDefault,
+                               // >= 2 = a mask of levels (2 = P3, 4 = P4, 8 = P5).  Same bits either way
+  static constexpr int kDeferLevelsDefault = 8;   // P5: the only level a 224-pixel frame's boxes leave unread (profiles/fpn_levels_deferred_*.md)
   // range audit (debug option, f32-storage engines): per activation tensor the trunk writes, how many values lie beyond the fp16 range
   // (|x| > 65504: an f16x3 operand half would saturate) and how many are not finite.  Counters live on the device; read by mcg_engine_range_audit.
   static constexpr int kAuditCap = 256;
@@ -222,6 +226,10 @@ extern "C" int mcg_engine_set_option(mcg_engine* e, const char* name, int value)
   else if (!strcmp(name, "winograd")) { MCG_CHECK_ARG(value >= 0 && value <= 2, "winograd must be 0, 1 or 2"); e->winograd = value; }
   else if (!strcmp(name, "fpn_deferred")) e->fpn_deferred = value != 0;
   else if (!strcmp(name, "fpn_lateral_deferred")) e->fpn_lateral_deferred = value != 0;
+  else if (!strcmp(name, "fpn_levels_deferred")) {
+    MCG_CHECK_ARG(value >= 0 && value <= 15 && !(value & 1 && value > 1), "fpn_levels_deferred: 0, 1 or a mask of 2 (P3) | 4 (P4) | 8 (P5) (got %d)", value);
+    e->fpn_levels_deferred = value;
+  }
   else if (!strcmp(name, "wino_tile")) { MCG_CHECK_ARG(value >= -1 && value <= 3, "wino_tile must be -1 (by grid size) .. 3"); e->wino_tile = value; }
   else if (!strcmp(name, "range_audit")) {
     MCG_CHECK_ARG(!mcg_is16(e->dt) || !value, "range_audit: f32-storage engines only (MCG_F32, MCG_F16X3)");
@@ -544,9 +552,12 @@ static int conv3_step(const mcg_engine* e, hipStream_t s, const TrunkWs& t, Audi
 // tk.inner != NULL (deferred P2): the P2 top-down inner map goes to tk.inner (frame offset f0) and the P2 output conv is left to the decoder.
 // tk.c2 != NULL (deferred P2 lateral): C2 and the P3 inner map are written straight to tk.c2 / tk.l1 (frame offset f0) -- in place of the
 // workspace, no copy -- and the P2 lateral is left to the decoder as well; every reader follows t.c[0] / t.l[1]
-struct TrunkKeep { char *inner, *c2, *l1; };
+// tk.lin[i] != NULL, i = 1 .. 3 (level i deferred by frames): the inner map of level i is written straight to tk.lin[i] in the same way and
+// its output conv is left to the decoder
+struct TrunkKeep { char *inner, *c2, *l1, *lin[4]; };
+static const TrunkKeep kNoKeep = {nullptr, nullptr, nullptr, {nullptr, nullptr, nullptr, nullptr}};
 static int trunk_chunk(mcg_engine* e, hipStream_t s, const float* img, int f0, int n, int H, int W, void* const pyr[4], char* wsbase,
-                       bool backbone_only = false, const TrunkKeep tk = TrunkKeep{nullptr, nullptr, nullptr}) {
+                       bool backbone_only = false, const TrunkKeep tk = kNoKeep) {
   const mcg_dtype dt = e->dt;
   const size_t es = esize(dt);
   TrunkWs t = trunk_layout(dt, n, H, W, wsbase);
@@ -557,6 +568,8 @@ static int trunk_chunk(mcg_engine* e, hipStream_t s, const float* img, int f0, i
     t.c[0] = tk.c2 + (size_t)f0 * (H / 4) * (W / 4) * 256 * es;
     t.l[1] = tk.l1 + (size_t)f0 * (H / 8) * (W / 8) * 256 * es;
   }
+  for (int i = 1; i < 4; ++i)
+    if (tk.lin[i]) t.l[i] = tk.lin[i] + (size_t)f0 * ((H / 4) >> i) * ((W / 4) >> i) * 256 * es;
   MCG_TRY(stem_forward_ctx(s, dt, img + (size_t)f0 * 3 * H * W, e->stem.w, e->stem.bias, t.x0, n, H, W, t.stem_ws, t.stem_bytes, e->ctx));
   AuditCursor au{e, s, 0, e->audit_dev != nullptr && e->audit_names.empty()};
   audit_tensor(au, t.x0, (long long)n * (H / 4) * (W / 4) * 64, "stem");
@@ -596,6 +609,7 @@ static int trunk_chunk(mcg_engine* e, hipStream_t s, const float* img, int f0, i
     audit_tensor(au, t.l[i], (long long)n * hs[i] * wsz[i] * 256, "fpn.lateral%d (+ top-down)", i);
   }
   for (int i = inner0 ? 1 : 0; i < 4; ++i) {
+    if (tk.lin[i]) continue;
     char* dst = (char*)pyr[i] + (size_t)f0 * hs[i] * wsz[i] * 256 * es;
     MCG_TRY(conv_call(e, s, dt, e->fpn_out[i], t.l[i], n, hs[i], wsz[i], dst, 0, nullptr, MCG_RES_NONE, 0, 0));
     audit_tensor(au, dst, (long long)n * hs[i] * wsz[i] * 256, "fpn.P%d", i + 2);
@@ -663,6 +677,13 @@ struct DeferSlot {
   bool lateral;                      // the P2 lateral is deferred too
   char *c2, *l1;                     // C2 [N, H/4, W/4, 256], P3 inner map [N, H/8, W/8, 256]
   int *istate, *icount, *ilist;      // inner blocks: flag per block, count per stage, list per stage
+  // levels deferred by frames (option fpn_levels_deferred), i = 1 .. 3 where bit i of level_mask is set: the level's inner map, written there by
+  // the trunk (lin[1] is l1 where the P2 lateral is deferred too), a flag per frame + a count per stage (behind the block flags and counts: the
+  // slot's one clear covers all clear_n ints) and a frame list per stage
+  int level_mask;
+  char* lin[4];
+  int *fstate[4], *fcount[4], *flist[4];
+  int clear_n;
   size_t total;
 };
 static bool fpn_deferred_on(const mcg_engine* e, int N, int H, int W) {
@@ -679,6 +700,19 @@ static bool fpn_lateral_deferred_on(const mcg_engine* e, int N, int H, int W) {
          cw.pad == 0 && h % 2 == 0 && w % 2 == 0 &&
          pw_single_x3_blocks_applicable(cw.cin, cw.cout, h, w, (long long)N * h * w, (long long)N * (h / 2) * (w / 2));
 }
+// P3 .. P5 by frames: only where P2 is deferred, for the levels the option names whose dense conv is the F(2,3) Winograd kernel and whose map the
+// frame-list tile serves -> mask of levels (bit i = level i)
+static int fpn_levels_deferred_mask(const mcg_engine* e, int N, int H, int W) {
+  if (!e->fpn_levels_deferred || !fpn_deferred_on(e, N, H, W)) return 0;
+  const int want = e->fpn_levels_deferred == 1 ? mcg_engine::kDeferLevelsDefault : e->fpn_levels_deferred;
+  int mask = 0;
+  for (int i = 1; i < 4; ++i) {
+    const mcg_conv_weights& cw = e->fpn_out[i];
+    const int h = (H / 4) >> i, w = (W / 4) >> i;
+    if (((want >> i) & 1) && wino_kind(e, e->dt, cw, N, h, w, MCG_RES_NONE) == 2 && wino_x3_frames_applicable(N, h, w, cw.cin, cw.cout)) mask |= 1 << i;
+  }
+  return mask;
+}
 static DeferSlot defer_layout(const mcg_engine* e, int N, int H, int W, char* base) {
   DeferSlot d;
   memset(&d, 0, sizeof(d));
@@ -690,9 +724,21 @@ static DeferSlot defer_layout(const mcg_engine* e, int N, int H, int W, char* ba
     d.inner = take((size_t)N * (H / 4) * (W / 4) * 256 * esize(e->dt));
     d.nblk = N * wino_x3_blocks_per_frame(H / 4, W / 4);
     d.lateral = fpn_lateral_deferred_on(e, N, H, W);
-    const size_t per = (size_t)d.nblk + e->num_stages;
-    d.state = (int*)take(sizeof(int) * per * (d.lateral ? 2 : 1));
+    d.level_mask = fpn_levels_deferred_mask(e, N, H, W);
+    const size_t per = (size_t)d.nblk + e->num_stages, fper = (size_t)N + e->num_stages;
+    size_t ints = per * (d.lateral ? 2 : 1);
+    const size_t fints0 = ints;
+    for (int i = 1; i < 4; ++i) ints += ((d.level_mask >> i) & 1) ? fper : 0;
+    d.clear_n = (int)ints;
+    d.state = (int*)take(sizeof(int) * ints);
     d.count = d.state ? d.state + d.nblk : nullptr;
+    for (int i = 1, k = 0; i < 4; ++i) {
+      if (!((d.level_mask >> i) & 1)) continue;
+      d.fstate[i] = d.state ? d.state + fints0 + fper * k : nullptr;
+      d.fcount[i] = d.fstate[i] ? d.fstate[i] + N : nullptr;
+      d.flist[i] = (int*)take(sizeof(int) * (size_t)N * e->num_stages);
+      ++k;
+    }
     d.list = (int*)take(sizeof(int) * (size_t)d.nblk * e->num_stages);
     if (d.lateral) {
       d.istate = d.state ? d.state + per : nullptr;
@@ -701,6 +747,8 @@ static DeferSlot defer_layout(const mcg_engine* e, int N, int H, int W, char* ba
       d.c2 = take((size_t)N * (H / 4) * (W / 4) * 256 * esize(e->dt));
       d.l1 = take((size_t)N * (H / 8) * (W / 8) * 256 * esize(e->dt));
     }
+    for (int i = 1; i < 4; ++i)
+      if ((d.level_mask >> i) & 1) d.lin[i] = (i == 1 && d.lateral) ? d.l1 : take((size_t)N * ((H / 4) >> i) * ((W / 4) >> i) * 256 * esize(e->dt));
   }
   d.total = off;
   return d;
@@ -740,7 +788,7 @@ static int check_shape(int N, int H, int W) {
 }
 
 static int trunk_forward(mcg_engine* e, mcg_stream s_, const float* img, int N, int H, int W, int chunk,
-                         void* const pyramid[4], void* ws, size_t ws_bytes, bool backbone_only, const TrunkKeep tk = TrunkKeep{nullptr, nullptr, nullptr}) {
+                         void* const pyramid[4], void* ws, size_t ws_bytes, bool backbone_only, const TrunkKeep tk = kNoKeep) {
   MCG_CHECK_ARG(e && img && (pyramid || backbone_only) && ws, "mcg_backbone_fpn_forward: null pointer");
   MCG_TRY(check_shape(N, H, W));
   std::lock_guard<std::mutex> lock(e->mu);
@@ -828,6 +876,26 @@ extern "C" int mcg_conv3x3_wino_x3_blocks(mcg_stream s, const float* x, const vo
   return MCG_OK;
 }
 
+// The frame-list tile as a stand-alone operator (tests and measurements): launch_wino_x3_frames over the caller's list, never another kernel
+extern "C" int mcg_conv3x3_wino_x3_frames(mcg_stream s, const float* x, const void* u, const float* bias, float* y, int frames, int H, int W,
+                                          int Cin, int Cout, const int* frame_list, const int* frame_count, int grid_cap) {
+  MCG_CHECK_ARG(x && u && y && frame_list && frame_count, "mcg_conv3x3_wino_x3_frames: null pointer");
+  MCG_CHECK_ARG(grid_cap >= 0, "mcg_conv3x3_wino_x3_frames: grid_cap >= 0 (got %d)", grid_cap);
+  if (H <= 0 || W <= 0 || !wino_x3_frames_applicable(frames, H, W, Cin, Cout)) {
+    mcg_set_error("mcg_conv3x3_wino_x3_frames: unsupported shape (frames=%d %dx%d, %d -> %d channels): Cin %% 32, Cout %% 128, 2 <= W <= 30, a frame's rows of a tile within the window buffer, operands within 2 GiB",
+                  frames, H, W, Cin, Cout);
+    return MCG_ERR_UNSUPPORTED;
+  }
+  WinoParams wp;
+  memset(&wp, 0, sizeof(wp));
+  wp.x = x; wp.u = u; wp.bias = bias; wp.y = y; wp.H = H; wp.W = W; wp.frames = frames; wp.Cin = Cin; wp.Cout = Cout;
+  if (launch_wino_x3_frames((hipStream_t)s, wp, frame_list, frame_count, grid_cap)) {
+    mcg_set_error("mcg_conv3x3_wino_x3_frames: launch failed");
+    return MCG_ERR_HIP;
+  }
+  return MCG_OK;
+}
+
 // The streaming 1x1 kernels as stand-alone operators: the launchers' own dispatch tables at any M >= 1, never another kernel
 extern "C" int mcg_pointwise_stream(mcg_stream s, mcg_dtype dt, const void* a, const void* wf, const float* bias, const void* res, void* y,
                                     int M, int K, int N, int relu, int res_mode, int Ho, int Wo, int Hr, int Wr, float wscale,
@@ -905,10 +973,23 @@ extern "C" int mcg_bench_backbone_levels(const mcg_engine* e, void* ws, int N, i
 // (roi_mark_kernel), then compute them from the inner map (wino_x3w_blocks_kernel: same bits as the dense conv).  Booked once, at stage 0.
 // d.lateral: the inner map is computed here as well, between the two -- the listed blocks and their in-frame neighbours that no earlier
 // stage computed (inner_mark_kernel), by the streaming lateral's per-pixel code over that list (pw_single_x3_blocks_kernel)
-static int defer_stage_forward(const mcg_engine* e, hipStream_t s, const DeferSlot& d, int st, const float* boxes, int N, int h, int w) {
+// d.level_mask: the same mark launch lists, per level deferred by frames, the frames one of the stage's boxes reads there and no earlier stage
+// listed; each such level's output conv then runs over its list (wino_x3w_frames_kernel: the dense conv's bits), booked once, at stage 0.
+static int defer_stage_forward(const mcg_engine* e, hipStream_t s, const DeferSlot& d, int st, const float* boxes, int N, const int fh[4],
+                               const int fw[4]) {
   const mcg_conv_weights& cw = e->fpn_out[0];
+  const int h = fh[0], w = fw[0];
   int* list = d.list + (size_t)st * d.nblk;
-  MCG_TRY(launch_roi_mark(s, boxes, N * 3, 3, 0, h, w, 4, d.state, list, d.count + st));
+  int *fstate[4] = {nullptr, nullptr, nullptr, nullptr}, *flist[4] = {nullptr, nullptr, nullptr, nullptr}, *fcount[4] = {nullptr, nullptr, nullptr, nullptr};
+  for (int i = 1; i < 4; ++i)
+    if ((d.level_mask >> i) & 1) { fstate[i] = d.fstate[i]; flist[i] = d.flist[i] + (size_t)st * N; fcount[i] = d.fcount[i] + st; }
+  MCG_TRY(launch_roi_mark(s, boxes, N * 3, 3, 0, h, w, 4, d.state, list, d.count + st, fstate, flist, fcount));
+  for (int i = 1; i < 4; ++i) {
+    if (!fstate[i]) continue;
+    const mcg_conv_weights& fc = e->fpn_out[i];
+    ProfRec* frec = prof_begin_wino(e->ctx, s, fc, (long long)N * fh[i] * fw[i], st == 0);
+    MCG_TRY(launch_done(frec, s, launch_wino_x3_frames(s, wino_params(fc, 2, d.lin[i], N, fh[i], fw[i], d.p[i], 0), flist[i], fcount[i]), "wino_x3 frames"));
+  }
   if (d.lateral) {
     const mcg_conv_weights& lw = e->lateral[0];
     int* ilist = d.ilist + (size_t)st * d.nblk;
@@ -948,9 +1029,9 @@ static int decoder_forward(mcg_engine* e, hipStream_t s, const void* const pyram
   char* obj_in = c.obj_a; char* obj_out = c.obj_b;
   float* b_in = c.boxes_a; float* b_out = c.boxes_b;
   const bool defer = d && d->deferred;
-  if (defer) MCG_TRY(launch_defer_clear(s, d->state, (d->nblk + e->num_stages) * (d->lateral ? 2 : 1)));
+  if (defer) MCG_TRY(launch_defer_clear(s, d->state, d->clear_n));
   for (int st = 0; st < e->num_stages; ++st) {
-    if (defer) MCG_TRY(defer_stage_forward(e, s, *d, st, b_in, N, fh[0], fw[0]));
+    if (defer) MCG_TRY(defer_stage_forward(e, s, *d, st, b_in, N, fh, fw));
     MCG_TRY(launch_roi_align(s, e->dt, pyramid, fh, fw, strides, 256, b_in, N * 3, 3, frame_of, pyramid_frames, c.roi, nullptr));
     float* bdst = (st == e->num_stages - 1) ? boxes_out : b_out;
     MCG_TRY(stage_forward_ctx(s, e->dt, &e->stage_w[(size_t)st * MCG_SW_COUNT], c.roi, obj_in, b_in, N, ct, obj_out, bdst,
@@ -1004,7 +1085,7 @@ extern "C" int mcg_backbone_fpn_forward_deferred(mcg_engine* e, mcg_stream s, co
   const DeferSlot d = defer_layout(e, N, H, W, (char*)slot);
   if (slot_bytes < d.total) { mcg_set_error("mcg_backbone_fpn_forward_deferred: slot too small (%zu < %zu)", slot_bytes, d.total); return MCG_ERR_WORKSPACE; }
   return trunk_forward(e, s, img, N, H, W, chunk, d.p, ws, ws_bytes, false,
-                       TrunkKeep{d.deferred ? d.inner : nullptr, d.lateral ? d.c2 : nullptr, d.lateral ? d.l1 : nullptr});
+                       TrunkKeep{d.deferred ? d.inner : nullptr, d.lateral ? d.c2 : nullptr, d.lateral ? d.l1 : nullptr, {nullptr, d.lin[1], d.lin[2], d.lin[3]}});
 }
 
 // Test / measurement aid: where a deferred slot keeps the P2 inner map and the inner-block bookkeeping of the deferred lateral
@@ -1021,6 +1102,20 @@ extern "C" int mcg_deferred_pyramid_state(const mcg_engine* e, void* slot, int N
   if (lists) *lists = d.ilist;
   if (blocks) *blocks = d.nblk;
   if (lateral_deferred) *lateral_deferred = d.lateral ? 1 : 0;
+  return MCG_OK;
+}
+
+// Test / measurement aid: the frame bookkeeping of level (1 .. 3 = P3 .. P5) in a deferred slot (flags [N], counts [stages], lists [stages][N]);
+// *frame_deferred = whether the engine defers that level by frames for this shape (else the pointers are NULL)
+extern "C" int mcg_deferred_pyramid_frame_state(const mcg_engine* e, void* slot, int N, int H, int W, int level, int** flags, int** counts,
+                                                int** lists, int* frame_deferred) {
+  MCG_CHECK_ARG(e && slot && level >= 1 && level <= 3, "mcg_deferred_pyramid_frame_state: null pointer or level outside 1 .. 3");
+  MCG_TRY(check_shape(N, H, W));
+  const DeferSlot d = defer_layout(e, N, H, W, (char*)slot);
+  if (flags) *flags = d.fstate[level];
+  if (counts) *counts = d.fcount[level];
+  if (lists) *lists = d.flist[level];
+  if (frame_deferred) *frame_deferred = (d.level_mask >> level) & 1;
   return MCG_OK;
 }
 

@@ -103,15 +103,26 @@ __global__ __launch_bounds__(256) void roi_align_kernel(RoiLevels lv, int C, con
 // pixels a box reads are {lo, hi of every valid y sample} x {lo, hi of every valid x sample} (a sample pair is read iff both samples are
 // valid): the blocks are that product of block rows and columns.  state[b]: 0 = not listed, 1 = listed (by this or an earlier stage;
 // stream order computes a listed block before the RoIAlign that follows).  Vector atomics only.
+//
+// Levels deferred by whole FRAMES (engine option fpn_levels_deferred: P3 .. P5, whose maps are too small for blocks): fm.state[l] != NULL
+// names level l's flag per frame, fm.list[l] / fm.count[l] this stage's frame list.  A box routed to such a level lists its frame unless an
+// earlier box or stage did -- the flag flip is the only way onto a list, so a frame is listed once over all stages and a list never holds
+// more than one entry per frame.  Same launch, same rule (roi_level), no second kernel.
 constexpr int kMarkMaxBlocks = 64;   // block rows / columns of the deferred level (512 pixels)
+struct FrameMark { int *state[4], *list[4], *count[4]; };
 __global__ __launch_bounds__(256) void roi_mark_kernel(const float* __restrict__ boxes, int boxes_per_frame, int level_deferred, int H, int W,
                                                        float ss, int* __restrict__ state, int* __restrict__ list, int* __restrict__ count,
-                                                       float finest_scale) {
+                                                       float finest_scale, const FrameMark fm) {
   constexpr int P = 7, S = 2, NS = P * S;
   __shared__ int s_hit[2][kMarkMaxBlocks];
   const int box = blockIdx.x, tid = threadIdx.x;
   const float x1 = boxes[box * 4 + 0], y1 = boxes[box * 4 + 1], x2 = boxes[box * 4 + 2], y2 = boxes[box * 4 + 3];
-  if (roi_level(x1, y1, x2, y2, finest_scale) != level_deferred) return;   // uniform per workgroup
+  const int level = roi_level(x1, y1, x2, y2, finest_scale);               // 0 .. 3, uniform per workgroup
+  if (tid == 0 && fm.state[level]) {
+    const int f = box / boxes_per_frame;
+    if (atomicCAS(&fm.state[level][f], 0, 1) == 0) fm.list[level][atomicAdd(fm.count[level], 1)] = f;
+  }
+  if (level != level_deferred) return;
   const int by_n = (H + 7) / 8, bx_n = (W + 7) / 8;
   if (tid < 2 * kMarkMaxBlocks) s_hit[tid / kMarkMaxBlocks][tid % kMarkMaxBlocks] = 0;
   __syncthreads();
@@ -178,11 +189,18 @@ int launch_defer_clear(hipStream_t s, int* p, int n) {
   MCG_CHECK_LAUNCH("defer_clear");
   return MCG_OK;
 }
+// level < 0: no level is deferred by blocks (state / list / count unused); frame_state etc. [4], NULL entries (or NULL arrays) = that level
+// is not deferred by frames
 int launch_roi_mark(hipStream_t s, const float* boxes, int num_boxes, int boxes_per_frame, int level, int H, int W, int stride, int* state,
-                    int* list, int* count) {
+                    int* list, int* count, int* const* frame_state, int* const* frame_list, int* const* frame_count) {
   MCG_CHECK_ARG(roi_mark_supported(H, W), "roi_mark: deferred level of %dx%d pixels exceeds %d blocks per axis", H, W, kMarkMaxBlocks);
+  FrameMark fm;
+  for (int l = 0; l < 4; ++l) {
+    const bool on = frame_state && frame_list && frame_count && frame_state[l] && frame_list[l] && frame_count[l];
+    fm.state[l] = on ? frame_state[l] : nullptr; fm.list[l] = on ? frame_list[l] : nullptr; fm.count[l] = on ? frame_count[l] : nullptr;
+  }
   hipLaunchKernelGGL(roi_mark_kernel, dim3(num_boxes), dim3(256), 0, s, boxes, boxes_per_frame, level, H, W, 1.0f / (float)stride, state, list,
-                     count, 56.f);
+                     count, 56.f, fm);
   MCG_CHECK_LAUNCH("roi_mark");
   return MCG_OK;
 }
@@ -192,7 +210,18 @@ extern "C" int mcg_roi_mark_blocks(mcg_stream s, const float* boxes, int num_box
   MCG_CHECK_ARG(boxes && state && list && count, "mcg_roi_mark_blocks: null pointer");
   MCG_CHECK_ARG(num_boxes > 0 && boxes_per_frame > 0, "mcg_roi_mark_blocks: empty box set");
   MCG_CHECK_ARG(level >= 0 && level <= 3 && H > 0 && W > 0 && stride > 0, "mcg_roi_mark_blocks: bad level (level=%d %dx%d stride=%d)", level, H, W, stride);
-  return launch_roi_mark((hipStream_t)s, boxes, num_boxes, boxes_per_frame, level, H, W, stride, state, list, count);
+  return launch_roi_mark((hipStream_t)s, boxes, num_boxes, boxes_per_frame, level, H, W, stride, state, list, count, nullptr, nullptr, nullptr);
+}
+// The frame marking alone: boxes routed to `level` list their frames (state [frames], list [frames], count [1]); no block level
+extern "C" int mcg_roi_mark_frames(mcg_stream s, const float* boxes, int num_boxes, int boxes_per_frame, int level, int* state, int* list,
+                                   int* count) {
+  MCG_CHECK_ARG(boxes && state && list && count, "mcg_roi_mark_frames: null pointer");
+  MCG_CHECK_ARG(num_boxes > 0 && boxes_per_frame > 0 && num_boxes % boxes_per_frame == 0,
+                "mcg_roi_mark_frames: whole frames of boxes (num_boxes=%d boxes_per_frame=%d)", num_boxes, boxes_per_frame);
+  MCG_CHECK_ARG(level >= 0 && level <= 3, "mcg_roi_mark_frames: bad level %d", level);
+  int *fs[4] = {nullptr, nullptr, nullptr, nullptr}, *fl[4] = {nullptr, nullptr, nullptr, nullptr}, *fc[4] = {nullptr, nullptr, nullptr, nullptr};
+  fs[level] = state; fl[level] = list; fc[level] = count;
+  return launch_roi_mark((hipStream_t)s, boxes, num_boxes, boxes_per_frame, -1, 8, 8, 1, nullptr, nullptr, nullptr, fs, fl, fc);
 }
 extern "C" int mcg_inner_mark_blocks(mcg_stream s, const int* out_list, const int* out_count, int H, int W, int nblk, int* state, int* list,
                                      int* count) {

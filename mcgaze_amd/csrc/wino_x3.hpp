@@ -748,6 +748,21 @@ __global__ __launch_bounds__(256, 1) void wino_x3w_blocks_kernel(const WinoParam
     if (logical < units) wino_x3w_tile<1, true>(p, logical);
   }
 }
+// The raster tile over a device list of FRAMES (the deferred FPN P3 .. P5 output convs -- DESIGN.md 3.1i): tiles cut at frame boundaries
+// (p.tpf tiles per frame), and a fixed grid walks units (list entry, tile in frame, channel tile) until *blk_count entries are done.  A unit
+// is wino_x3w_tile<NB, false> on the listed frame's own tile index, so a frame's bits are the dense conv's (a pair's arithmetic does not
+// depend on its tile) whatever the list's order or length.  An entry outside [0, frames) is skipped; the count is clamped to the list's
+// capacity, one entry per frame.
+template <int NB>
+__global__ __launch_bounds__(256, 1) void wino_x3w_frames_kernel(const WinoParams p) {
+  const int per = p.tpf * p.n_tiles;
+  const int units = __builtin_amdgcn_readfirstlane(min(max(*p.blk_count, 0), p.frames)) * per;
+  for (int u = blockIdx.x; u < units; u += gridDim.x) {
+    const int e = u / per;
+    const int f = __builtin_amdgcn_readfirstlane(p.blk_list[e]);
+    if ((unsigned)f < (unsigned)p.frames) wino_x3w_tile<NB, false>(p, f * per + (u - e * per));
+  }
+}
 
 // Tile shapes.  G = 2: 0 = 128 pairs x 128 channels (8 waves), 1 = 64 x 64 (8 waves), 2 = 32 x 64 (4 waves), 3 = 128 x 128 with one wave per
 // SIMD (wino_x3w_kernel).  G = 4: 0 = 64 groups x 128
@@ -826,6 +841,31 @@ static inline int launch_wino_x3_blocks(hipStream_t s, WinoParams p, const int* 
   int grid = units < cus ? units : cus / 16 * 16;
   if (cap > 0 && grid > cap) grid = cap;
   hipLaunchKernelGGL(wino_x3w_blocks_kernel, dim3(grid > 0 ? grid : 1), dim3(256), wnx::W_LDS, s, p);
+  return hipGetLastError() == hipSuccess ? 0 : 1;
+}
+// Frame-list tile (whole frames named by a device list, F(2,3), 128 pairs x 128 channels): maps of at most two window pieces per row (W <= 30)
+// whose frame-cut window fits its buffer.  list holds at most p.frames entries; cap as in launch_wino_x3_blocks.
+static inline bool wino_x3_frames_applicable(int frames, int H, int W, int Cin, int Cout) {
+  if (!wino_x3_operands_ok(frames, H, W, Cin, Cout)) return false;
+  const int pcs = wino_x3_pieces(W, 2);
+  return pcs <= 2 && wino_x3_max_rows(H, W, wino_x3_tile_groups(2, 3), 2, false) * wino_x3_nb_template(pcs) * 1024 <= wnx::wcap(2, 4);
+}
+static inline int launch_wino_x3_frames(hipStream_t s, WinoParams p, const int* list, const int* count, int cap = 0) {
+  if (!wino_x3_frames_applicable(p.frames, p.H, p.W, p.Cin, p.Cout)) return 1;
+  const int nb = wino_x3_nb_template(wino_x3_pieces(p.W, 2));
+  int cus;
+  if (nb == 1 ? kernel_ready<wino_x3w_frames_kernel<1>>(wnx::W_LDS, &cus) : kernel_ready<wino_x3w_frames_kernel<2>>(wnx::W_LDS, &cus)) return 1;
+  p.PW = (p.W + 1) / 2;
+  p.gpf = p.H * p.PW;
+  p.total_pairs = p.frames * p.gpf;
+  p.n_tiles = p.Cout / 128;
+  p.tpf = (p.gpf + 127) / 128;
+  p.blk_list = list; p.blk_count = count;
+  const long long units = (long long)p.frames * p.tpf * p.n_tiles;
+  int grid = units < cus ? (int)units : cus;
+  if (cap > 0 && grid > cap) grid = cap;
+  if (nb == 1) hipLaunchKernelGGL(wino_x3w_frames_kernel<1>, dim3(grid > 0 ? grid : 1), dim3(256), wnx::W_LDS, s, p);
+  else hipLaunchKernelGGL(wino_x3w_frames_kernel<2>, dim3(grid > 0 ? grid : 1), dim3(256), wnx::W_LDS, s, p);
   return hipGetLastError() == hipSuccess ? 0 : 1;
 }
 // returns 0 on success; the caller has checked wino_x3_applicable(.., g).  shape: -1 = by grid size (the largest tile that still makes ~half

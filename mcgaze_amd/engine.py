@@ -210,6 +210,40 @@ def conv3x3_wino_blocks(x, packed, blocks, out, bias=None, relu=False, grid_cap=
     return out
 
 
+def conv3x3_wino_frames(x, u, frames, out, bias=None, grid_cap=0):
+    """The frame-list tile of conv3x3_wino (mcg_conv3x3_wino_x3_frames; wino_x3w_frames_kernel): x NHWC f32, u = packing.wino_pack(w) of the
+    UNSCALED weight (the entry takes no descale factor), out NHWC f32 [N,H,W,Cout] -- the listed frames of it are written, the rest is left
+    alone.  frames: a sequence of frame indices or a (list, count) pair of device int32 tensors (roi_mark_frames), list N long.  THE
+    INDICES MUST BE DISTINCT; one outside [0, N) is skipped and a count above N is clamped on the device."""
+    _require_gpu()
+    lib = L.load()
+    N, H, W, Cin = x.shape
+    Cout = out.shape[-1]
+    assert x.dtype == torch.float32 and x.is_contiguous() and out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (N, H, W, Cout)
+    assert u.numel() * 2 == lib.mcg_conv3x3_wino_x3_weight_bytes(Cin, Cout, 2), (u.numel(), Cin, Cout)
+    flist, fcount = _block_list(frames, x.device)
+    if flist.numel() < N:
+        flist = torch.cat([flist, torch.zeros(N - flist.numel(), dtype=torch.int32, device=x.device)])
+    L.check(lib.mcg_conv3x3_wino_x3_frames(_stream(), _ptr(x), _ptr(u), _ptr(bias), _ptr(out), N, H, W, Cin, Cout, _ptr(flist), _ptr(fcount),
+                                           grid_cap), 'mcg_conv3x3_wino_x3_frames')
+    return out
+
+
+def roi_mark_frames(boxes, level, state=None, flist=None, count=None):
+    """Which frames read pyramid level ``level`` (0 .. 3) for these boxes (mcg_roi_mark_frames; roi_mark_kernel's frame marking): boxes
+    [N,P,4] f32 -> (state, list, count), int32 device tensors: state [N] flags, list the frames newly flagged in unspecified order, count
+    [1] how many.  Given buffers are added to (a frame whose state is set is not listed again; count is not reset); None: fresh zeroed
+    ones."""
+    _require_gpu()
+    lib = L.load()
+    N, P, _ = boxes.shape
+    assert boxes.dtype == torch.float32
+    state, flist, count = _mark_buffers(N, state, flist, count, boxes.device)
+    L.check(lib.mcg_roi_mark_frames(_stream(), _ptr(boxes.contiguous()), N * P, P, int(level), _ptr(state), _ptr(flist), _ptr(count)),
+            'mcg_roi_mark_frames')
+    return state, flist, count
+
+
 def bottleneck_x3(x, src2, wstream, bias, cn, nsrc, trace=None):
     """The fused bottleneck tail (mcg_bottleneck_x3): x [N,H,W,cm] f32 = conv2's input (cm = 64 / 128), src2 = residual [N,H,W,4 cm]
     (nsrc 1) or the downsample conv's input [N,H,W,64] (nsrc 2); wstream / bias from packing.bneck_stream.
@@ -496,7 +530,7 @@ class HipEngine:
     def set_option(self, name, value):
         """mcg_engine_set_option: 'trunk_streams', 'max_range_frames', 'tile', 'staged_gemm', 'conv3x3_c64', 'stem_fused',
         'decoder_chain', 'decoder_attn_block', 'pointwise_pair', 'pointwise_stream', 'bottleneck_fused', 'bottleneck_blocked', 'winograd',
-        'wino_tile', 'fpn_deferred', 'fpn_lateral_deferred', 'range_audit'; values and defaults in include/mcgaze_hip.h."""
+        'wino_tile', 'fpn_deferred', 'fpn_lateral_deferred', 'fpn_levels_deferred', 'range_audit'; values and defaults in include/mcgaze_hip.h."""
         L.check(self.lib.mcg_engine_set_option(self._handle, name.encode(), int(value)), f'mcg_engine_set_option({name})')
 
     def range_audit(self, capacity=256):

@@ -41,7 +41,8 @@ EXPORTS = ['mcg_abi_version', 'mcg_build_id', 'mcg_last_error', 'mcg_device_info
            'mcg_deferred_pyramid_state', 'mcg_inner_block_neighbours', 'mcg_gaze_targets', 'mcg_gaze_dwell', 'mcg_gaze_targets_poly',
            'mcg_pointwise_stream', 'mcg_pointwise_dyn', 'mcg_pointwise_pair', 'mcg_draw_attention', 'mcg_draw_attention_nv12',
            'mcg_format_labels', 'mcg_draw_labels', 'mcg_draw_labels_nv12', 'mcg_gaze_heat_add', 'mcg_draw_heat', 'mcg_draw_heat_nv12',
-           'mcg_anonymize_heads', 'mcg_anonymize_heads_nv12', 'mcg_roi_mark_blocks', 'mcg_inner_mark_blocks', 'mcg_conv3x3_wino_x3_blocks']
+           'mcg_anonymize_heads', 'mcg_anonymize_heads_nv12', 'mcg_roi_mark_blocks', 'mcg_inner_mark_blocks', 'mcg_conv3x3_wino_x3_blocks',
+           'mcg_conv3x3_wino_x3_frames', 'mcg_roi_mark_frames', 'mcg_deferred_pyramid_frame_state']
 LABEL_CHARS = 24                                                 # MCG_LABEL_CHARS
 LETTERBOX_U8, LETTERBOX_F16, LETTERBOX_F32 = 0, 1, 2             # enum order of include/mcgaze_hip.h
 
@@ -225,6 +226,9 @@ def load():
     lib.mcg_conv3x3_wino_x3.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, i, i, i, C.c_float, i]
     lib.mcg_conv3x3_wino_x3_blocks.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, i, i, C.c_float, vp, vp, i, i]
     lib.mcg_roi_mark_blocks.argtypes = [vp, vp, i, i, i, i, i, i, vp, vp, vp]
+    lib.mcg_roi_mark_frames.argtypes = [vp, vp, i, i, i, vp, vp, vp]
+    lib.mcg_conv3x3_wino_x3_frames.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, i, vp, vp, i]
+    lib.mcg_deferred_pyramid_frame_state.argtypes = [vp, vp, i, i, i, i, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(i)]
     lib.mcg_inner_mark_blocks.argtypes = [vp, vp, vp, i, i, i, vp, vp, vp]
     lib.mcg_conv3x3_wino_x3_weight_bytes.restype = sz
     lib.mcg_pointwise_stream.argtypes = [vp, i, vp, vp, vp, vp, vp, i, i, i, i, i, i, i, i, i, C.c_float, vp, vp, i]
