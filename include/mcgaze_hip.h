@@ -1450,6 +1450,78 @@ int mcg_anonymize_heads_nv12(mcg_stream s, const mcg_nv12_image_desc* images_dev
                              const int32_t* image_of_dev, int n, double expand, int shape, int cell_shift, int blocks, int mode,
                              const unsigned char* yuv, mcg_anon_desc* plan_out_dev, int32_t* flags_dev);
 
+/* ---------------------------------------------------------------- gaze targets, 3-D (additions to ABI 20; nothing above changes)
+ * "gaze targets" decides in the image plane and reads only (gx, gy): a head behind another along the image ray is the farther one in
+ * pixels whatever its depth, and a look at a region lands on the region's rim.  mcg_gaze_targets_3d decides in CAMERA SPACE (x right, y
+ * down, z away from the lens, metres): every row is lifted to a point with the intrinsics of its camera and a depth, its gaze becomes a
+ * direction there, heads are boxes around those points and regions are planar polygons.  The output tables keep the names, shapes and
+ * meanings of "gaze targets", so dwell, heat, overlay and labels run on them unchanged; hit3d is added.  Two launches (the second is the
+ * `mutual` launch of "gaze targets"), no allocation, no host sync, graph-capturable, no atomics in global memory.
+ * Everything is double and uncontracted (no FMA): every product, quotient, sum and difference below is rounded on its own, in the order
+ * the parentheses give; f32 tables are widened exactly.  The only square roots are two sqrtf of a value rounded to f32 (correctly rounded
+ * on host and device).  Comparisons with a NaN are false, and every min / max below is written as the comparison it stands for.
+ * CAMERA TABLE.  cam f32 [C][4] = fx, fy, cx, cy (pixels).  Row k belongs to camera c = image_of[k] if cam_period == 0, else image_of[k] %
+ * cam_period.
+ * UNUSABLE (flag 2).  A row is unusable iff it is unusable under "gaze targets", or c >= C, or one of the camera's four numbers is not
+ * finite, or not (fx > 0 and fy > 0), or its Z or its origin below is not finite and positive / finite.  cam is read only at a c < C.
+ * DEPTH.  If depth is given and depth[k] is finite and > 0:  Z = depth[k].  Otherwise  Z = (fx * head_size) / max(x2 - x1, y2 - y1),
+ * (max: w > h ? w : h).  head_size is the size of a head in metres (Python default 0.24: a CONVENTION, not tuned on data).  Not (Z finite
+ * and Z > 0): flag 2.
+ * ORIGIN.  u = (x1 + x2) * 0.5, v = (y1 + y2) * 0.5 as in "gaze targets";  X = ((u - cx) * Z) / fx,  Y = ((v - cy) * Z) / fy,  O = (X, Y, Z).
+ * X or Y not finite (only a head_size beyond the f32 range can do that): flag 2.
+ * DIRECTION.  frame 0 ('camera'):  D = (-gx, -gy, gz) -- the arrow's (-gx, -gy), and gz < 0 towards the lens.
+ * frame 1 ('eye', the Python default): the gaze is relative to the line from the lens to the head, as Gaze360 states it and as the CAMERA
+ * rule of "gaze targets" assumes.  With the basis  right = (Z, 0, -X) / a,  down = (-X Y, a2, -Y Z) / (a r),  forward = (X, Y, Z) / r,
+ * scaled by a r > 0:
+ *   a2 = X * X + Z * Z;   a = (double)sqrtf((float)a2);   r = (double)sqrtf((float)(a2 + Y * Y));   p = gx * r;   q = gz * a;
+ *   Dx = ((q * X) - (p * Z)) + (gy * (X * Y));   Dy = (q * Y) - (gy * a2);   Dz = ((q * Z) + (p * X)) + (gy * (Y * Z))
+ * i.e. D = -gx r (Z, 0, -X) - gy (-X Y, a2, -Y Z) + gz a (X, Y, Z).  D is NOT normalised: t below is its ray parameter, and distances in
+ * metres come from hit3d.
+ * AT THE CAMERA (kind 3), before everything below.  frame 1: the CAMERA rule of "gaze targets" on (gx, gy, gz), unchanged.  frame 0:
+ *   s = -((Dx * X + Dy * Y) + Dz * Z);   s > 0  and  s * s >= camera_cos2 * (((Dx * Dx + Dy * Dy) + Dz * Dz) * ((X * X + Y * Y) + Z * Z)).
+ * Otherwise, if a component of D is not finite or all three compare equal to zero, the kind is 0.
+ * HEADS.  Every OTHER usable row j of the same picture, as the box [O_j - (hw, hh, hd), O_j + (hw, hh, hd)] with w = x2 - x1, h = y2 - y1,
+ * e = expand * max(w, h):   hw = (((w * 0.5) + e) * Z_j) / fx_j;   hh = (((h * 0.5) + e) * Z_j) / fy_j;   hd = hw > hh ? hw : hh.
+ * The SLAB TEST of "gaze targets" with a third axis: near starts at -inf and far at +inf; an axis with D_a == 0 passes iff lo_a <= O_a <=
+ * hi_a; any other gives t1 = (lo_a - O_a) / D_a, t2 = (hi_a - O_a) / D_a, l = t1 < t2 ? t1 : t2, h = the other, near = l > near ? l :
+ * near, far = h < far ? h : far, axes in the order x, y, z.  A hit iff every axis passes, near <= far, far >= 0 and t = (near > 0 ? near :
+ * +0) is finite.
+ * REGIONS.  region_xyz f32 [V][3] vertices in camera coordinates, region_start int32 [m + 1], region_image / region_period as in "gaze
+ * targets".  Region j is USABLE iff 0 <= region_start[j] <= region_start[j + 1] <= V, its vertex count c is 3 .. 32, every coordinate it
+ * owns is finite, and N is not all zero:  e1 = v1 - v0,  e2 = v2 - v0,
+ *   Nx = e1y * e2z - e1z * e2y;   Ny = e1z * e2x - e1x * e2z;   Nz = e1x * e2y - e1y * e2x.
+ * The offsets are checked before the first vertex load: whatever the tables hold, nothing outside them is read.  An unusable region is
+ * never hit and flags nothing.
+ *   den = (Nx * Dx + Ny * Dy) + Nz * Dz;   tn = (Nx * (v0x - X) + Ny * (v0y - Y)) + Nz * (v0z - Z);   q = tn / den.
+ * The plane is met iff den != 0, q is finite and q >= 0;  t = q > 0 ? q : +0;  P = (X + t * Dx, Y + t * Dy, Z + t * Dz).  The region is
+ * hit iff P is INSIDE by the even-odd rule of "gaze targets, polygonal regions" (its toggle test, edges in ascending order) applied to the
+ * two coordinates (pu, pv) left, in the order x y z, after the axis of the largest |N| component is dropped (|Nx| >= |Ny| and |Nx| >=
+ * |Nz|: x; else |Ny| >= |Nz|: y; else z).  There is no "inside means t = 0" case in 3-D, and a region is two-sided.
+ * CHOICE.  The smallest t wins; on equal t a head comes before a region, then the lower index -- the rule of "gaze targets".
+ * OUTPUTS.  kind, target, t, mutual and flags as in "gaze targets".  For kind 1 or 2, P = O + t * D per component as above;
+ * hit3d [n][3] = P rounded once to f32;  hit [n][2] = (fx * (Px / Pz) + cx, fy * (Py / Pz) + cy) rounded once to f32 where Pz > 0 and the
+ * value is a number, else the quiet NaN 0x7fc00000 (per component) -- the row rules of the overlay and of the heat map skip a hit that is
+ * not finite.  Every other row writes what "gaze targets" writes (zeros, target -1) and zeros to hit3d.
+ *   boxes_dev, gaze_dev, gaze_stride, image_of_dev, n, region_image_dev, m, region_period, expand, camera_cos2, kind_dev .. flags_dev
+ *                  as mcg_gaze_targets takes them
+ *   cam_dev        DEVICE f32 [num_cameras][4], 1 <= num_cameras <= 4096;  cam_period >= 0
+ *   depth_dev      DEVICE f32 [n] or NULL
+ *   head_size      finite, > 0;   frame 0 or 1
+ *   region_xyz_dev DEVICE f32 [num_vertices][3], NULL iff num_vertices == 0;  region_start_dev int32 [m + 1], NULL iff m == 0
+ *   hit3d_dev      DEVICE f32 [n][3], written
+ * 0 <= n <= 65536, 0 <= m <= 4096, 0 <= num_vertices <= 65536; n == 0 returns MCG_OK without a launch.  Anything else, or a null required
+ * table, returns MCG_ERR_ARG before any launch; the CONTENTS of the device tables never are an error and are never read back.  Heads and
+ * regions are searched in tiles of 256 with the picture-range skip of "gaze targets".
+ * mcgaze_amd/attention.py::gaze_targets_3d_host is the same on the host, bit for bit.  head_size, frame, expand and camera_cos2 are
+ * CONVENTIONS, not tuned on data.
+ * Out of scope: lens distortion, a region's pose from four image corners, one-sided regions, depth from anything but the size of the head
+ * or the caller's table. */
+int mcg_gaze_targets_3d(mcg_stream s, const float* boxes_dev, const float* gaze_dev, int gaze_stride, const int32_t* image_of_dev, int n,
+                        const float* cam_dev, int num_cameras, int cam_period, const float* depth_dev, double head_size, int frame,
+                        const float* region_xyz_dev, int num_vertices, const int32_t* region_start_dev, const int32_t* region_image_dev, int m,
+                        int region_period, double expand, double camera_cos2, int32_t* kind_dev, int32_t* target_dev, float* t_dev,
+                        float* hit_dev, int32_t* mutual_dev, int32_t* flags_dev, float* hit3d_dev);
+
 /* ---------------------------------------------------------------- measurement aids (bench.py)
  * While armed, every launch of the contraction kernel made by THIS engine is bracketed by a hipEvent pair on its launch stream.
  * mcg_engine_profile_stop synchronises, returns per-launch duration (ms), algorithmic FLOPs, algorithmic HBM bytes (inputs and

@@ -149,16 +149,20 @@ def _attention_options(who, attention, cameras=None):
     int32 [m], dict(expand=, camera_angle=)).  attention: None, True or dict(regions=, expand=, camera_angle=).  regions: [[x1, y1, x2, y2],
     ...], which apply to every picture (region_image -1); with ``cameras`` a list of that many such tables (or None), one per camera, whose
     region_image is the camera.  A table may also be the mixed list of ``region_polygons``; where one holds a polygon, regions is the
-    PolyRegions of all tables -- ``regions=`` of gaze_targets either way."""
+    PolyRegions of all tables -- ``regions=`` of gaze_targets either way.  With camera= (and regions3d=, head_size=, frame=) the dict carries
+    'three_d': the tables of ``_attention_3d_options``, by which gaze_targets_3d decides; ``regions`` are then only drawn and named."""
     if attention is None:
         return None
     if attention is not True and not isinstance(attention, dict):
         raise ValueError(f'{who}: attention is None, True or a dict of regions, expand and camera_angle; got {attention!r}')
     opts = {} if attention is True else dict(attention)
-    if set(opts) - {'regions', 'expand', 'camera_angle'}:
-        raise ValueError(f'{who}: attention takes regions, expand and camera_angle; got {sorted(opts)}')
+    if set(opts) - {'regions', 'expand', 'camera_angle'} - set(ATTENTION_3D_OPTIONS):
+        raise ValueError(f'{who}: attention takes regions, expand and camera_angle, and for targets in 3-D camera, regions3d, head_size and frame; '
+                         f'got {sorted(opts)}')
     regions = opts.pop('regions', None)
     _target_params(opts.get('expand', EXPAND), opts.get('camera_angle', CAMERA_ANGLE), 0, f'{who}(attention=...)')
+    if set(opts) & set(ATTENTION_3D_OPTIONS):                     # camera=: the 3-D entry decides; ``regions`` are then only what is drawn
+        opts['three_d'] = _attention_3d_options(who, {k: opts.pop(k) for k in ATTENTION_3D_OPTIONS if k in opts}, cameras)
     one = lambda r: region_polygons(r) if _holds_polygon(r) else _region_tables(who, r, None)[0]      # (xy, start), or [m, 4]
     try:
         if cameras is None:
@@ -182,6 +186,41 @@ def _attention_options(who, attention, cameras=None):
         _check_counts(who, 0, len(table))
     image = np.full(sum(counts), -1, np.int32) if cameras is None else np.repeat(np.arange(len(tables), dtype=np.int32), counts)
     return table, image.astype(np.int32), opts
+
+
+ATTENTION_3D_OPTIONS = ('camera', 'regions3d', 'head_size', 'frame')
+
+
+def _attention_3d_options(who, given, cameras=None):
+    """The 3-D part of the ``attention=`` option, validated (ValueError) -> dict(cam f32 [C,4], regions PolyRegions3D, region_image int32
+    [m], head_size, frame) as gaze_targets_3d takes them.  camera: [fx, fy, cx, cy] -- of every camera -- or with ``cameras`` one such row
+    per camera.  regions3d: a list of planar polygons [[x, y, z], ...] in camera coordinates, which apply to every picture; with ``cameras``
+    a list of that many such lists (or None), one per camera, in that camera's coordinates."""
+    if given.get('camera') is None:
+        raise ValueError(f'{who}: attention regions3d, head_size and frame belong to camera=[fx, fy, cx, cy]: targets in 3-D need the intrinsics')
+    try:
+        cam = _camera_table(who, given['camera'])
+        if cam.shape[0] != (cameras or 1):
+            if cam.shape[0] != 1:
+                raise ValueError(f'{who}: attention camera is [fx, fy, cx, cy] or one such row per camera ({cameras or 1}), got {cam.shape}')
+            cam = np.ascontiguousarray(np.repeat(cam, cameras, axis=0))
+        regions = given.get('regions3d')
+        if cameras is None:
+            tables = [regions_3d(regions if regions is not None else [])]
+        else:
+            if regions is not None and (isinstance(regions, np.ndarray) or len(regions) != cameras):
+                raise ValueError(f'{who}: attention regions3d are a list of {cameras} lists of polygons, one per camera (None: no regions there)')
+            tables = [regions_3d(r if r is not None else []) for r in (regions if regions is not None else [None] * cameras)]
+    except TypeError as e:
+        raise ValueError(f'{who}: attention camera / regions3d: {e}') from None
+    head_size, _, _ = _target3d_params(given.get('head_size', HEAD_SIZE), given.get('frame', 'eye'), 0, f'{who}(attention=...)')
+    counts = [len(t.start) - 1 for t in tables]
+    first = np.cumsum([0] + [len(t.xyz) for t in tables])
+    table = PolyRegions3D(np.concatenate([t.xyz for t in tables]),
+                          np.concatenate([t.start[:-1] + f for t, f in zip(tables, first)] + [first[-1:]]).astype(np.int32))
+    _check_counts(who, 0, sum(counts), len(table.xyz))
+    image = np.full(sum(counts), -1, np.int32) if cameras is None else np.repeat(np.arange(len(tables), dtype=np.int32), counts)
+    return dict(cam=cam, regions=table, region_image=image.astype(np.int32), head_size=head_size, frame=given.get('frame', 'eye'))
 
 
 def _row_tables(who, boxes, gaze, image_of):
@@ -328,6 +367,279 @@ def gaze_targets_host(boxes, gaze, image_of=None, regions=None, region_image=Non
     mutual[heads] = (kind[back] == KIND_HEAD) & (target[back] == heads)
     with np.errstate(over='ignore'):
         return kind, target, t_out.astype(np.float32), hit.astype(np.float32), mutual, flags
+
+
+# ---------------------------------------------------------------- gaze targets, 3-D (include/mcgaze_hip.h, "gaze targets, 3-D")
+HEAD_SIZE, GAZE_FRAMES, MAX_CAMERAS = 0.24, ('camera', 'eye'), 4096       # head_size in metres and frame 'eye': conventions, not tuned on data
+FIELDS_3D = FIELDS + ('hit3d',)                                  # the order of the seven tables
+NAN32 = np.array([0x7fc00000], np.uint32).view(np.float32)[0]    # the one NaN ``hit`` holds
+
+
+class PolyRegions3D(collections.namedtuple('PolyRegions3D', 'xyz start')):
+    """The region tables of mcg_gaze_targets_3d, (xyz f32 [V, 3], start int32 [m + 1]): region j is the planar polygon of the 3 .. 32
+    vertices start[j] .. start[j + 1] - 1, in camera coordinates (x right, y down, z away from the lens, metres).  The tables may be
+    device tensors for DevicePipeline.gaze_targets_3d; what ``start`` HOLDS is contents, never an error."""
+    __slots__ = ()
+
+
+def regions_3d(regions):
+    """A list of planar polygons [[x, y, z], ...] of 3 .. 32 vertices each, in camera coordinates -> PolyRegions3D(xyz f32 [V, 3], start
+    int32 [m + 1]).  TypeError for what is no list of such items or holds no numbers, ValueError for an item of another shape; the VALUES
+    are contents (a vertex that is not finite, or three first vertices on one line, make the region unusable, as on the device)."""
+    who = 'regions_3d'
+    if not isinstance(regions, (list, tuple, np.ndarray)):
+        raise TypeError(f'{who}: regions is a list of polygons [[x, y, z], ...]; got {type(regions).__name__}')
+    parts = []
+    for j, item in enumerate(regions):
+        if not isinstance(item, (list, tuple, np.ndarray)):
+            raise TypeError(f'{who}: region {j} is a list of [x, y, z] vertices, got {type(item).__name__}')
+        try:
+            a = np.asarray(item)
+        except ValueError:
+            raise ValueError(f'{who}: region {j} is 3 .. {POLY_VERTS} vertices [x, y, z], got a ragged list') from None
+        if a.dtype.kind not in 'fiu':
+            raise TypeError(f'{who}: region {j} must hold numbers, got {a.dtype}')
+        if not (a.ndim == 2 and a.shape[1] == 3 and 3 <= a.shape[0] <= POLY_VERTS):
+            raise ValueError(f'{who}: region {j} is 3 .. {POLY_VERTS} vertices [x, y, z], got shape {a.shape}')
+        parts.append(a.astype(np.float32))
+    start = np.zeros(len(parts) + 1, np.int64)
+    np.cumsum([len(p) for p in parts], out=start[1:])
+    _check_counts(who, 0, len(parts), int(start[-1]))
+    return PolyRegions3D(np.concatenate(parts) if parts else np.zeros((0, 3), np.float32), start.astype(np.int32))
+
+
+def _camera_table(who, cam):
+    """``cam``: [fx, fy, cx, cy] or one such row per camera -> f32 [C, 4], 1 <= C <= MAX_CAMERAS (TypeError / ValueError).  The VALUES are
+    contents: a camera that is not finite or has fx, fy <= 0 flags its rows."""
+    c = np.asarray(_host_array(cam))
+    if c.dtype.kind not in 'fiu':
+        raise TypeError(f'{who}: the camera table must hold numbers fx fy cx cy, got {c.dtype}')
+    c = c.reshape(1, 4) if c.shape == (4,) else c
+    if c.ndim != 2 or c.shape[1] != 4 or not 1 <= c.shape[0] <= MAX_CAMERAS:
+        raise ValueError(f'{who}: the camera table is [fx, fy, cx, cy] or [C, 4] with C in 1 .. {MAX_CAMERAS}, got {c.shape}')
+    return np.ascontiguousarray(c, dtype=np.float32)
+
+
+def _target3d_params(head_size=HEAD_SIZE, frame='eye', cam_period=0, who='gaze_targets_3d'):
+    """The options of the 3-D entry, validated (ValueError) -> (head_size, frame as the entry's int, cam_period)."""
+    if isinstance(head_size, bool) or not isinstance(head_size, (int, float, np.integer, np.floating)) or not (math.isfinite(head_size) and head_size > 0):
+        raise ValueError(f'{who}: head_size must be a finite number of metres > 0, got {head_size!r}')
+    if not isinstance(frame, str) or frame not in GAZE_FRAMES:
+        raise ValueError(f"{who}: frame is 'eye' or 'camera', got {frame!r}")
+    if isinstance(cam_period, bool) or not isinstance(cam_period, (int, np.integer)) or cam_period < 0:
+        raise ValueError(f'{who}: cam_period must be an int >= 0, got {cam_period!r}')
+    return float(head_size), GAZE_FRAMES.index(frame), int(cam_period)
+
+
+def _depth_table(who, depth, n):
+    """``depth``: None or [n] numbers -> None or f32 [n] (TypeError / ValueError)."""
+    if depth is None:
+        return None
+    d = np.asarray(_host_array(depth)).reshape(-1)
+    if d.size and d.dtype.kind not in 'fiu':
+        raise TypeError(f'{who}: depth must hold numbers, got {d.dtype}')
+    if d.shape != (n,):
+        raise ValueError(f'{who}: depth must be [{n}], one per row; got {d.shape}')
+    return np.ascontiguousarray(d, dtype=np.float32)
+
+
+def _poly3d_tables(who, regions, region_image):
+    """Host regions of the 3-D entry -- None, the list of ``regions_3d`` or a PolyRegions3D -> (f32 [V,3], int32 [m+1], int32 [m]), checked
+    (TypeError / ValueError): shapes, dtypes and counts only.  region_image None: every picture (-1)."""
+    if regions is None:
+        if region_image is not None and np.size(_host_array(region_image)):
+            raise ValueError(f'{who}: region_image without regions')
+        return np.zeros((0, 3), np.float32), np.zeros(1, np.int32), np.zeros(0, np.int32)
+    if not isinstance(regions, PolyRegions3D):
+        regions = regions_3d(regions)
+    v = np.asarray(_host_array(regions.xyz))
+    if v.size == 0:
+        v = v.reshape(0, 3)
+    if v.ndim != 2 or v.shape[1] != 3 or v.dtype.kind not in 'fiu':
+        raise ValueError(f'{who}: PolyRegions3D.xyz is the [V, 3] vertex table x y z; got {v.dtype} {v.shape}')
+    s = np.asarray(_host_array(regions.start))
+    if s.size and s.dtype.kind not in 'iu':
+        raise TypeError(f'{who}: PolyRegions3D.start must hold integers, got {s.dtype}')
+    if s.ndim != 1 or len(s) < 1:
+        raise ValueError(f'{who}: PolyRegions3D.start must be [m + 1], got {s.shape}')
+    m = len(s) - 1
+    if region_image is None:
+        ri = np.full(m, -1, np.int32)
+    else:
+        ri = np.asarray(_host_array(region_image)).reshape(-1)
+        if ri.size and ri.dtype.kind not in 'iu':
+            raise TypeError(f'{who}: region_image must hold integers, got {ri.dtype}')
+        if ri.shape != (m,):
+            raise ValueError(f'{who}: region_image must be [{m}], one per region; got {ri.shape}')
+    return np.ascontiguousarray(v, dtype=np.float32), np.ascontiguousarray(s.astype(np.int32)), np.ascontiguousarray(ri, dtype=np.int32)
+
+
+def unproject(points_px, depth, cam):
+    """Image points at a depth -> camera space, the header's ORIGIN rule: points_px [..., 2] pixels (u, v), depth a number or [...] metres
+    along z, cam [fx, fy, cx, cy] -> float64 [..., 3] = (((u - cx) * Z) / fx, ((v - cy) * Z) / fy, Z).  How the corners of a screen marked
+    in a picture, with their measured distances, become a region of ``regions_3d``."""
+    p = np.asarray(points_px, dtype=np.float64)
+    c = np.asarray(cam, dtype=np.float64)
+    if p.ndim < 1 or p.shape[-1] != 2 or c.shape != (4,):
+        raise ValueError(f'unproject: points_px is [..., 2] and cam [fx, fy, cx, cy]; got {p.shape} and {c.shape}')
+    z = np.broadcast_to(np.asarray(depth, dtype=np.float64), p.shape[:-1])
+    return np.stack([((p[..., 0] - c[2]) * z) / c[0], ((p[..., 1] - c[3]) * z) / c[1], z], axis=-1)
+
+
+def _sqrtf(x):
+    """(double)sqrtf((float)x)."""
+    return np.sqrt(x.astype(np.float32)).astype(np.float64)
+
+
+def _usable_regions_3d(xyz, start):
+    """The header's USABLE region of the 3-D entry (xyz float64 [V,3]) -> (ok bool [m], first int64 [m], count int64 [m], N float64 [m,3],
+    axis int64 [m]: the dropped one)."""
+    s, e = start[:-1].astype(np.int64), start[1:].astype(np.int64)
+    c = e - s
+    ok = (0 <= s) & (s <= e) & (e <= len(xyz)) & (c >= 3) & (c <= POLY_VERTS)
+    N, axis = np.zeros((len(s), 3)), np.zeros(len(s), np.int64)
+    for j in np.flatnonzero(ok):                                  # nothing outside xyz is looked at: the offsets were checked first
+        v = xyz[s[j]:e[j]]
+        if not np.isfinite(v).all():
+            ok[j] = False
+            continue
+        e1, e2 = v[1] - v[0], v[2] - v[0]
+        N[j] = (e1[1] * e2[2] - e1[2] * e2[1], e1[2] * e2[0] - e1[0] * e2[2], e1[0] * e2[1] - e1[1] * e2[0])
+        ax, ay, az = np.abs(N[j])
+        axis[j] = 0 if ax >= ay and ax >= az else 1 if ay >= az else 2
+        ok[j] = not (N[j, 0] == 0.0 and N[j, 1] == 0.0 and N[j, 2] == 0.0)
+    return ok, s, c, N, axis
+
+
+def gaze_targets_3d_host(boxes, gaze, image_of, cam, depth=None, regions=None, region_image=None, region_period=0, cam_period=0,
+                         head_size=HEAD_SIZE, frame='eye', expand=EXPAND, camera_angle=CAMERA_ANGLE):
+    """``mcg_gaze_targets_3d`` in numpy float64, bit for bit (include/mcgaze_hip.h, "gaze targets, 3-D"): gaze_targets_host decided in
+    camera space, so that depth orders the heads along a ray and a look at a region lands inside it.
+
+    boxes, gaze, image_of, region_image, region_period, expand, camera_angle: as gaze_targets_host takes them.  cam: [fx, fy, cx, cy] or
+    [C, 4], one row per camera; row k's camera is image_of[k] (cam_period 0) or image_of[k] % cam_period.  depth: None or [n] metres along
+    z; where it is not finite and positive the depth comes from the head's size: (fx * head_size) / the box's longer side.  regions: None,
+    the list of ``regions_3d`` (planar polygons [[x, y, z], ...] in camera coordinates) or a PolyRegions3D.  frame: 'eye' -- the gaze is
+    relative to the line from the lens to the head, as Gaze360 states it -- or 'camera': D = (-gx, -gy, gz).  head_size 0.24 m, frame,
+    expand and camera_angle are conventions, not tuned on data.
+    -> (kind, target, t, hit, mutual, flags as gaze_targets_host returns them -- hit is the 3-D point projected to pixels, NaN where it is
+    not in front of the lens --, hit3d float32 [n,3]: the point in camera coordinates)."""
+    who = 'gaze_targets_3d_host'
+    expand, cos2, period = _target_params(expand, camera_angle, region_period, who)
+    head_size, frame, cam_period = _target3d_params(head_size, frame, cam_period, who)
+    b32, g32, io = _row_tables(who, boxes, gaze, image_of)
+    cam32 = _camera_table(who, cam)
+    n = len(b32)
+    d32 = _depth_table(who, depth, n)
+    xyz32, start, ri = _poly3d_tables(who, regions, region_image)
+    _check_counts(who, n, len(ri), len(xyz32))
+    b, g, xyz = b32.astype(np.float64), g32.astype(np.float64), xyz32.astype(np.float64)
+    kind, target = np.zeros(n, np.int32), np.full(n, -1, np.int32)
+    t_out, hit, hit3d = np.zeros(n, np.float32), np.zeros((n, 2), np.float32), np.zeros((n, 3), np.float32)
+    with np.errstate(all='ignore'):
+        # ---- every row in camera space.  numpy rounds every elementwise product and sum on its own: nothing is contracted, as in the kernel
+        usable = np.isfinite(b).all(axis=1) & np.isfinite(g).all(axis=1) & ~(b[:, 2] < b[:, 0]) & ~(b[:, 3] < b[:, 1]) & (io >= 0)
+        c = np.where(usable, io % cam_period if cam_period > 0 else io, 0)
+        usable &= c < len(cam32)
+        k = cam32[np.where(usable, c, 0)].astype(np.float64)
+        fx, fy, cx, cy = k[:, 0], k[:, 1], k[:, 2], k[:, 3]
+        usable &= np.isfinite(k).all(axis=1) & (fx > 0.0) & (fy > 0.0)
+        w, h = b[:, 2] - b[:, 0], b[:, 3] - b[:, 1]
+        side = np.where(w > h, w, h)
+        Z = (fx * head_size) / side
+        if d32 is not None:
+            dz = d32.astype(np.float64)
+            Z = np.where(np.isfinite(dz) & (dz > 0.0), dz, Z)
+        usable &= np.isfinite(Z) & (Z > 0.0)
+        X = ((((b[:, 0] + b[:, 2]) * 0.5) - cx) * Z) / fx
+        Y = ((((b[:, 1] + b[:, 3]) * 0.5) - cy) * Z) / fy
+        usable &= np.isfinite(X) & np.isfinite(Y)
+        flags = np.where(usable, 0, 2).astype(np.int32)
+        gx, gy, gz = g[:, 0], g[:, 1], g[:, 2]
+        if frame == 0:
+            Dx, Dy, Dz = -gx, -gy, gz
+            s = -((Dx * X + Dy * Y) + Dz * Z)
+            camera = (s > 0.0) & (s * s >= cos2 * (((Dx * Dx + Dy * Dy) + Dz * Dz) * ((X * X + Y * Y) + Z * Z)))
+        else:
+            a2 = X * X + Z * Z
+            a, r = _sqrtf(a2), _sqrtf(a2 + Y * Y)
+            p, q = gx * r, gz * a
+            Dx = ((q * X) - (p * Z)) + (gy * (X * Y))
+            Dy = (q * Y) - (gy * a2)
+            Dz = ((q * Z) + (p * X)) + (gy * (Y * Z))
+            camera = (gz < 0.0) & (gz * gz >= cos2 * ((gx * gx + gy * gy) + gz * gz))
+        camera &= usable
+        kind[camera] = KIND_CAMERA
+        searching = usable & ~camera & np.isfinite(Dx) & np.isfinite(Dy) & np.isfinite(Dz) & ~((Dx == 0.0) & (Dy == 0.0) & (Dz == 0.0))
+        O, D = np.stack([X, Y, Z], axis=1), np.stack([Dx, Dy, Dz], axis=1)
+        e = expand * side
+        hw, hh = (((w * 0.5) + e) * Z) / fx, (((h * 0.5) + e) * Z) / fy
+        half = np.stack([hw, hh, np.where(hw > hh, hw, hh)], axis=1)
+        lo, hi = O - half, O + half
+        r_ok, r_first, r_count, r_N, r_axis = _usable_regions_3d(xyz, start)
+        best_t = np.full(n, np.inf)
+        for picture in np.unique(io[searching]):
+            rows = np.flatnonzero(usable & (io == picture))       # the candidates, ascending; the sources are among them
+            src = rows[searching[rows]]
+            o, d = O[src], D[src]
+            # heads: the slab test, axes x y z
+            near, far = np.full((len(src), len(rows)), -np.inf), np.full((len(src), len(rows)), np.inf)
+            ok = np.ones((len(src), len(rows)), bool)
+            for ax in (0, 1, 2):
+                oa, da, la, ha = o[:, ax, None], d[:, ax, None], lo[None, rows, ax], hi[None, rows, ax]
+                zero = np.broadcast_to(da == 0.0, ok.shape)
+                t1, t2 = (la - oa) / da, (ha - oa) / da
+                l, u = np.where(t1 < t2, t1, t2), np.where(t1 < t2, t2, t1)
+                ok &= np.where(zero, (la <= oa) & (oa <= ha), True)
+                near = np.where(zero, near, np.where(l > near, l, near))
+                far = np.where(zero, far, np.where(u < far, u, far))
+            t = np.where(near > 0.0, near, 0.0)
+            heads = np.where(ok & (near <= far) & (far >= 0.0) & np.isfinite(t), t, np.inf)
+            heads[src[:, None] == rows[None, :]] = np.inf          # every OTHER row
+            # regions: the plane, then the even-odd rule in the two kept coordinates
+            applies = r_ok & ((ri < 0) | (ri == (int(picture) % period if period > 0 else int(picture))))
+            regs = np.flatnonzero(applies)
+            planes = np.full((len(src), len(regs)), np.inf)
+            for col, j in enumerate(regs):
+                N, v = r_N[j], xyz[r_first[j]:r_first[j] + r_count[j]]
+                den = (N[0] * d[:, 0] + N[1] * d[:, 1]) + N[2] * d[:, 2]
+                tn = (N[0] * (v[0, 0] - o[:, 0]) + N[1] * (v[0, 1] - o[:, 1])) + N[2] * (v[0, 2] - o[:, 2])
+                q = tn / den
+                met = (den != 0.0) & np.isfinite(q) & (q >= 0.0)
+                t = np.where(q > 0.0, q, 0.0)
+                P = o + t[:, None] * d
+                iu, iv = (1 if r_axis[j] == 0 else 0), (1 if r_axis[j] == 2 else 2)
+                pu, pv = P[:, iu], P[:, iv]
+                inside = np.zeros(len(src), bool)
+                for e_ in range(len(v)):
+                    (au, av), (bu, bv) = v[e_, [iu, iv]], v[(e_ + 1) % len(v), [iu, iv]]
+                    inside ^= ((av > pv) != (bv > pv)) & (pu < au + ((pv - av) * (bu - au)) / (bv - av))
+                planes[:, col] = np.where(met & inside, t, np.inf)
+            t = np.concatenate([heads, planes], axis=1)
+            if t.shape[1] == 0:
+                continue
+            best = np.argmin(t, axis=1)                           # the FIRST smallest: heads before regions, then the lower index
+            tb = t[np.arange(len(src)), best]
+            found = tb < np.inf
+            s_, best, tb = src[found], best[found], tb[found]
+            is_head = best < len(rows)
+            kind[s_] = np.where(is_head, KIND_HEAD, KIND_REGION)
+            target[s_] = np.where(is_head, rows[np.minimum(best, len(rows) - 1)], regs[np.maximum(best - len(rows), 0)] if len(regs) else -1)
+            best_t[s_] = tb
+        found = np.flatnonzero((kind == KIND_HEAD) | (kind == KIND_REGION))
+        tb = best_t[found]
+        P = O[found] + tb[:, None] * D[found]
+        t_out[found] = tb.astype(np.float32)
+        hit3d[found] = P.astype(np.float32)
+        u, v = fx[found] * (P[:, 0] / P[:, 2]) + cx[found], fy[found] * (P[:, 1] / P[:, 2]) + cy[found]
+        front = P[:, 2] > 0.0
+        hit[found, 0] = np.where(front & (u == u), u.astype(np.float32), NAN32)
+        hit[found, 1] = np.where(front & (v == v), v.astype(np.float32), NAN32)
+    mutual = np.zeros(n, np.int32)
+    heads = np.flatnonzero(kind == KIND_HEAD)
+    back = target[heads]
+    mutual[heads] = (kind[back] == KIND_HEAD) & (target[back] == heads)
+    return kind, target, t_out, hit, mutual, flags, hit3d
 
 
 # ---------------------------------------------------------------- gaze dwell (include/mcgaze_hip.h, "gaze dwell")

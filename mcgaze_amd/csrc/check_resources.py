@@ -21,6 +21,7 @@ RULES = {
     # no hand-issued loads, but a double-precision row walk that is meant to live in registers: scratch would be a cost nobody looks for
     'gaze_targets_kernel': dict(scratch=0, vgpr_spill=0, unit='attend'),
     'gaze_targets_poly_kernel': dict(scratch=0, vgpr_spill=0, unit='attend'),   # the previous vertex is carried in registers: no local array
+    'gaze_targets_3d_kernel': dict(scratch=0, vgpr_spill=0, unit='attend'),   # the lifted row (origin, direction, intrinsics) lives in registers
     'gaze_mutual_kernel': dict(scratch=0, vgpr_spill=0, unit='attend'),
     # the 16 state words of a column are meant to stay in registers across the frame loop
     'gaze_dwell_kernel': dict(scratch=0, vgpr_spill=0, unit='dwell'),

@@ -775,10 +775,14 @@ def _add_targets(records, pipeline, device, num_frames, gaze_key, regions, regio
     """run_head_video(attention=...): the gaze targets of every record and frame, ATTENTION_FRAMES frames per pipeline.gaze_targets call (host
     tables up through the staging ring, the result tables read back), written into the records."""
     rows = [[] for _ in range(num_frames)]                        # frame -> (record, index in it) of its heads, in record order
+    options = dict(options)
+    three_d = options.pop('three_d', None)
     for r, rec in enumerate(records):
         L_ = len(rec['frame_id'])
         rec.update(target_kind=np.zeros(L_, np.int32), target_id=[None] * L_, target_region=np.full(L_, -1, np.int32),
                    target_hit=np.zeros((L_, 2), np.float32), mutual=np.zeros(L_, np.int32))
+        if three_d is not None:
+            rec['target_hit3d'] = np.zeros((L_, 3), np.float32)
         for j, t in enumerate(rec['frame_id']):
             rows[t].append((r, j))
     for t0 in range(0, num_frames, ATTENTION_FRAMES):
@@ -787,12 +791,18 @@ def _add_targets(records, pipeline, device, num_frames, gaze_key, regions, regio
             continue
         boxes = np.asarray([records[r]['head_box'][j] for _, r, j in part], dtype=np.float32).reshape(-1, 4)
         gaze = np.asarray([records[r][gaze_key][j, :3] for _, r, j in part], dtype=np.float32).reshape(-1, 3)
-        got = pipeline.gaze_targets(boxes, gaze, np.asarray([k for k, _, _ in part], dtype=np.int32), regions=regions, region_image=region_image,
-                                    device=device, **options)
-        kind, target, _, hit, mutual, _ = (np.asarray(_host(g)) for g in got)
+        image_of = np.asarray([k for k, _, _ in part], dtype=np.int32)
+        if three_d is None:
+            got = pipeline.gaze_targets(boxes, gaze, image_of, regions=regions, region_image=region_image, device=device, **options)
+        else:                                                     # camera=: one camera for every frame (cam_period 1), decided in camera space
+            got = pipeline.gaze_targets_3d(boxes, gaze, image_of, three_d['cam'], regions=three_d['regions'], region_image=three_d['region_image'],
+                                           cam_period=1, head_size=three_d['head_size'], frame=three_d['frame'], device=device, **options)
+        kind, target, _, hit, mutual, _ = (np.asarray(_host(g)) for g in got[:6])
         for i, (_, r, j) in enumerate(part):
             rec, k = records[r], int(kind[i])
             rec['target_kind'][j], rec['mutual'][j], rec['target_hit'][j] = k, mutual[i], hit[i]
+            if three_d is not None:
+                rec['target_hit3d'][j] = np.asarray(_host(got[6]))[i]
             if k == 1:
                 rec['target_id'][j] = records[part[int(target[i])][1]]['id']
             elif k == 2:

@@ -42,7 +42,7 @@ EXPORTS = ['mcg_abi_version', 'mcg_build_id', 'mcg_last_error', 'mcg_device_info
            'mcg_pointwise_stream', 'mcg_pointwise_dyn', 'mcg_pointwise_pair', 'mcg_draw_attention', 'mcg_draw_attention_nv12',
            'mcg_format_labels', 'mcg_draw_labels', 'mcg_draw_labels_nv12', 'mcg_gaze_heat_add', 'mcg_draw_heat', 'mcg_draw_heat_nv12',
            'mcg_anonymize_heads', 'mcg_anonymize_heads_nv12', 'mcg_roi_mark_blocks', 'mcg_inner_mark_blocks', 'mcg_conv3x3_wino_x3_blocks',
-           'mcg_conv3x3_wino_x3_frames', 'mcg_roi_mark_frames', 'mcg_deferred_pyramid_frame_state']
+           'mcg_conv3x3_wino_x3_frames', 'mcg_roi_mark_frames', 'mcg_deferred_pyramid_frame_state', 'mcg_gaze_targets_3d']
 LABEL_CHARS = 24                                                 # MCG_LABEL_CHARS
 LETTERBOX_U8, LETTERBOX_F16, LETTERBOX_F32 = 0, 1, 2             # enum order of include/mcgaze_hip.h
 
@@ -205,6 +205,8 @@ def load():
     lib.mcg_live_gate_lanes.argtypes = [vp, vp, vp, vp, i, i, i, i, i, vp, i, i, i, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.mcg_gaze_targets.argtypes = [vp, vp, vp, i, vp, i, vp, vp, i, i, C.c_double, C.c_double, vp, vp, vp, vp, vp, vp]
     lib.mcg_gaze_targets_poly.argtypes = [vp, vp, vp, i, vp, i, vp, i, vp, vp, i, i, C.c_double, C.c_double, vp, vp, vp, vp, vp, vp]
+    lib.mcg_gaze_targets_3d.argtypes = [vp, vp, vp, i, vp, i, vp, i, i, vp, C.c_double, i, vp, i, vp, vp, i, i, C.c_double, C.c_double, vp, vp, vp, vp,
+                                        vp, vp, vp]
     lib.mcg_draw_attention.argtypes = [vp, vp, i, i, i, vp, vp, i, vp, i, vp, vp, vp, vp, vp, i, vp, vp, i, i, u8p, C.c_double, i, C.c_double, C.c_double,
                                        i, i, vp, sz, vp, vp, vp]
     lib.mcg_draw_attention_nv12.argtypes = lib.mcg_draw_attention.argtypes

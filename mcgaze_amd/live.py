@@ -31,7 +31,7 @@ import torch
 
 from . import lib as L
 from .arrows import LABEL_CHARS, _anon_params, _label_background, _label_options, _overlay_options, _overlay_palette, heat_lut
-from .attention import KIND_HEAD, PolyRegions, _attention_options, _dwell_options, _heat_options, region_label_rows
+from .attention import KIND_HEAD, PolyRegions, PolyRegions3D, _attention_options, _dwell_options, _heat_options, region_label_rows
 from .engine import _upload_table
 from .harness import _host, check_smooth
 from .head_detect import TRACK_HEADER_WORDS, TRACK_MAX_SLOTS, TRACK_SLOT_WORDS, _track_motion, _track_params, track_state_words
@@ -334,6 +334,12 @@ class LiveGaze:
     off-axis, an L-shaped shelf --: then the call is mcg_gaze_targets_poly, and a polygon is a region index like any other.  Targets are
     decided in the image plane, and expand / camera_angle are conventions, not tuned on data.  Still no wait for the device, no copy to the
     host.
+    With ``camera=[fx, fy, cx, cy]`` (or one such row per camera) in the dict the tick's call is pipeline.gaze_targets_3d instead
+    (mcg_gaze_targets_3d: targets decided in camera space, depth from the size of the head): ``regions3d=`` a list of Q lists of planar
+    polygons [[x, y, z], ...] in that camera's coordinates (None: none there), ``head_size=0.24`` metres and ``frame='eye'`` (conventions,
+    not tuned on data).  Every table above keeps its name -- target_hit is the 3-D point projected to frame pixels, NaN where it is not in
+    front of the lens, and a region's index counts through regions3d --, target_hit3d [.., 3] is added, and dwell, heat, overlay and labels
+    run on top unchanged; ``regions=`` are then only what the overlay draws and the labels name.
 
     OVERLAY.  ``overlay=True`` or ``dict(palette=, line_thickness=, region_thickness=)`` (it needs ``draw`` and ``attention``; ValueError
     without) draws the frames with pipeline.draw_attention instead of draw_arrows, from the gated tables and the per-camera regions: region
@@ -420,14 +426,19 @@ class LiveGaze:
         self.windows, self.kept = [], {}
         self.ticks = self.emitted = 0
         self.finished = False
-        self.attention = None
+        self.attention = self.attention3d = None
         if attention is not None:                                # the regions go up once: region_image = camera, matched through region_period = Q
             regions, region_image, options = attention
             up = lambda t: torch.from_numpy(t).to(self.dev)
+            three_d = options.pop('three_d', None)               # camera=: mcg_gaze_targets_3d decides, its tables go up once as well
+            if three_d is not None:
+                self.attention3d = dict(options, cam=up(three_d['cam']), regions=PolyRegions3D(*map(up, three_d['regions'])),
+                                        region_image=up(three_d['region_image']), head_size=three_d['head_size'], frame=three_d['frame'])
             regions = PolyRegions(*map(up, regions)) if isinstance(regions, PolyRegions) else up(regions)      # (a polygon somewhere: the vertex form)
             self.attention = dict(options, regions=regions, region_image=up(region_image))
         if self.dwell is not None:
-            self.dwell_state, self.region_frames = pipeline.dwell_state(n, device=self.dev), new(len(attention[1]))
+            counted = attention[1] if self.attention3d is None else self.attention3d['region_image']
+            self.dwell_state, self.region_frames = pipeline.dwell_state(n, device=self.dev), new(len(counted))
         if self.labels is not None:
             self._label_tables(attention, n, matrix)
 
@@ -508,8 +519,13 @@ class LiveGaze:
         lead = self.lead
         if k:
             gaze = out['fused_smooth' if self.smooth is not None else 'fused']
-            kind, target, t, hit, mutual, _ = self.pipe.gaze_targets(out['head_box'].view(-1, 4), gaze.view(-1, 3), out['image_of'].view(-1),
-                                                                     region_period=self.Q, device=self.dev, **self.attention)
+            if self.attention3d is not None:                     # (pictures are numbered i * Q + camera: both periods are Q)
+                kind, target, t, hit, mutual, _, hit3d = self.pipe.gaze_targets_3d(out['head_box'].view(-1, 4), gaze.view(-1, 3), out['image_of'].view(-1),
+                                                                                   region_period=self.Q, cam_period=self.Q, device=self.dev,
+                                                                                   **self.attention3d)
+            else:
+                kind, target, t, hit, mutual, _ = self.pipe.gaze_targets(out['head_box'].view(-1, 4), gaze.view(-1, 3), out['image_of'].view(-1),
+                                                                         region_period=self.Q, device=self.dev, **self.attention)
             head = kind == KIND_HEAD
             # a head's target is a flat row of [k, Q, S] / [k, P]: its id is gathered there, and what is handed back is the index within
             # the picture's rows -- the slot (the same camera, since the same picture) or the lane
@@ -518,8 +534,12 @@ class LiveGaze:
         else:
             new = lambda *shape, dtype=torch.int32: torch.empty(*shape, dtype=dtype, device=self.dev)
             kind, target, target_id, mutual, t, hit = new(0), new(0), new(0), new(0), new(0, dtype=torch.float32), new(0, 2, dtype=torch.float32)
-        return dict(target_kind=kind.view(k, *lead), target=target.view(k, *lead), target_id=target_id.view(k, *lead), target_t=t.view(k, *lead),
-                    target_hit=hit.view(k, *lead, 2), mutual=mutual.view(k, *lead))
+            hit3d = new(0, 3, dtype=torch.float32)
+        tables = dict(target_kind=kind.view(k, *lead), target=target.view(k, *lead), target_id=target_id.view(k, *lead), target_t=t.view(k, *lead),
+                      target_hit=hit.view(k, *lead, 2), mutual=mutual.view(k, *lead))
+        if self.attention3d is not None:
+            tables['target_hit3d'] = hit3d.view(k, *lead, 3)
+        return tables
 
     def _dwell(self, out, k):
         """dwell=: the targets of the k frames handed out, accumulated into dwell_state and region_frames -> the tables _emit adds."""

@@ -52,6 +52,7 @@ from .attention import (HEAT_KINDS, HeatState, _heat_cell, _heat_grid, _heat_par
                         heat_grid_shape)
 from .attention import PolyRegions, _check_counts, _holds_polygon, _poly_tables, _region_tables, _target_params, gaze_targets_host, region_polygons  # noqa: F401
 from .attention import _row_tables as _target_rows
+from .attention import MAX_CAMERAS, PolyRegions3D, _camera_table, _depth_table, _poly3d_tables, _target3d_params, gaze_targets_3d_host, regions_3d  # noqa: F401
 from .attention import DWELL_ENTER, DWELL_EXIT, _dwell_counts, _dwell_params, _dwell_tables, gaze_dwell_host  # noqa: F401
 from .frame_cache import FrameCache, _DecodeProcs, decode_image  # noqa: F401
 from .head_detect import (DETECT_MAX_DET, LETTERBOX_PAD, LetterboxGeometry, _detect_params, _detect_shapes, _letterbox_dtype,  # noqa: F401
@@ -1026,6 +1027,82 @@ class DevicePipeline:
                 (lib.mcg_gaze_targets, (vp(table_ptr), vp(region_image_ptr)))
             L.check(entry(vp(call.main.cuda_stream), vp(boxes_ptr), vp(gaze_ptr), gaze_stride, vp(image_of_ptr), n, *regions_at, m, period, expand, cos2,
                           *(vp(t.data_ptr()) for t in out)), entry.__name__)
+        return out
+
+    def gaze_targets_3d(self, boxes, gaze, image_of, cam, depth=None, regions=None, region_image=None, region_period=0, cam_period=0, head_size=0.24,
+                        frame='eye', expand=0.25, camera_angle=10.0, device='cuda:0', stream=None):
+        """What every head looks at, decided in CAMERA SPACE on the device (mcg_gaze_targets_3d: one launch over the rows, one for
+        ``mutual``) -- ``gaze_targets_3d_host`` bit for bit, whose arguments and seven results these are: every row is lifted to a point
+        with the intrinsics ``cam`` ([fx, fy, cx, cy], or [C,4] with row image_of or image_of % cam_period) and a depth (``depth`` [n] in
+        metres where it is finite and positive, else (fx * head_size) / the box's longer side), its gaze becomes a direction there
+        (``frame`` 'eye': relative to the line from the lens to the head; 'camera': (-gx, -gy, gz)), heads are boxes around those points
+        and regions planar polygons in camera coordinates (``attention.regions_3d`` or a ``PolyRegions3D(xyz [V,3], start [m+1])``).
+        head_size 0.24 m, frame, expand and camera_angle are conventions, not tuned on data.
+
+        Host or device tables, as ``gaze_targets`` takes them: CUDA tensors are read where they are, numpy tables go up through the staging
+        ring, a host table next to a device one of its group (rows and depth; cam; the region tables) is moved with torch.  Options and
+        shapes are checked on the host before anything is launched (TypeError / ValueError); device tables are not read back.  With device
+        tables the call touches the host nowhere and can be captured in a graph.
+        -> (kind, target [n] int32, t [n] f32, hit [n,2] f32 -- the 3-D point projected to pixels, NaN where it is not in front of the lens
+        --, mutual, flags [n] int32, hit3d [n,3] f32) on the device."""
+        lib = L.load()
+        who = 'gaze_targets_3d'
+        expand, cos2, period = _target_params(expand, camera_angle, region_period, who)
+        head_size, frame, cam_period = _target3d_params(head_size, frame, cam_period, who)
+        dev = _device(device, 'mcg_gaze_targets_3d')
+        rows_there = any(_on_device(t) for t in (boxes, gaze, image_of, depth))
+        if not rows_there:
+            boxes, gaze, image_of = _target_rows(who, boxes, gaze, image_of)
+            depth = _depth_table(who, depth, len(boxes))
+        if not _on_device(cam):
+            cam = _camera_table(who, cam)
+        regions_there = any(_on_device(t) for t in ((*regions, region_image) if isinstance(regions, PolyRegions3D) else (region_image,)))
+        if not regions_there:
+            xyz, start, region_image = _poly3d_tables(who, regions, region_image)
+        elif regions is None:
+            raise ValueError(f'{who}: region_image without regions')
+        elif not isinstance(regions, PolyRegions3D):
+            regions = regions_3d(regions)
+        with _call_scope(self._ring, dev, stream) as call:
+            if _on_device(cam):
+                cam = _there(cam, dev, torch.float32)
+                cam = cam.view(1, 4) if tuple(cam.shape) == (4,) else cam
+                if cam.ndim != 2 or cam.shape[1] != 4 or not 1 <= cam.shape[0] <= MAX_CAMERAS:
+                    raise ValueError(f'{who}: the camera table is [fx, fy, cx, cy] or [C, 4] with C in 1 .. {MAX_CAMERAS}, got {tuple(cam.shape)}')
+            if regions_there:
+                xyz, start = _there(regions.xyz, dev, torch.float32), _there(regions.start, dev, torch.int32)
+                if xyz.ndim != 2 or xyz.shape[1] != 3 or start.ndim != 1 or start.shape[0] < 1:
+                    raise ValueError(f'{who}: PolyRegions3D is xyz [V, 3] and start [m + 1], got {tuple(xyz.shape)} and {tuple(start.shape)}')
+                m = int(start.shape[0]) - 1
+                region_image = torch.full((m,), -1, dtype=torch.int32, device=dev) if region_image is None else _there(region_image, dev, torch.int32)
+                if tuple(region_image.shape) != (m,):
+                    raise ValueError(f'{who}: region_image must be [{m}], one per region; got {tuple(region_image.shape)}')
+            m, V = int(region_image.shape[0]), int(xyz.shape[0])
+            if rows_there:
+                boxes, gaze = _there(boxes, dev, torch.float32), _tensor(gaze)
+                n = int(boxes.shape[0])
+                if boxes.ndim != 2 or boxes.shape[1] != 4 or gaze.ndim != 2 or gaze.shape[0] != n or gaze.shape[1] < 3:
+                    raise ValueError(f'{who}: boxes {tuple(boxes.shape)} and gaze {tuple(gaze.shape)} must be [n,4] and [n,>=3]')
+                image_of = torch.zeros(n, dtype=torch.int32, device=dev) if image_of is None else _there(image_of, dev, torch.int32)
+                if tuple(image_of.shape) != (n,):
+                    raise ValueError(f'{who}: image_of must be [{n}], one per row; got {tuple(image_of.shape)}')
+                if depth is not None:
+                    depth = _there(depth, dev, torch.float32)
+                    if tuple(depth.shape) != (n,):
+                        raise ValueError(f'{who}: depth must be [{n}], one per row; got {tuple(depth.shape)}')
+            n = int(boxes.shape[0])
+            gaze, gaze_stride = _gaze_operand(gaze, n, 3, dev)
+            _check_counts(who, n, m, V)
+            new = lambda *shape, dtype=torch.int32: torch.empty(*shape, dtype=dtype, device=dev)
+            out = (new(n), new(n), new(n, dtype=torch.float32), new(n, 2, dtype=torch.float32), new(n), new(n), new(n, 3, dtype=torch.float32))
+            if n == 0:
+                return out
+            _, (boxes_ptr, gaze_ptr, image_of_ptr, depth_ptr, cam_ptr, xyz_ptr, start_ptr, region_image_ptr) = call.upload(
+                [], (boxes, gaze, image_of, depth, cam, xyz if V else None, start if m else None, region_image if m else None))
+            vp = C.c_void_p
+            L.check(lib.mcg_gaze_targets_3d(vp(call.main.cuda_stream), vp(boxes_ptr), vp(gaze_ptr), gaze_stride, vp(image_of_ptr), n, vp(cam_ptr),
+                                            int(cam.shape[0]), cam_period, vp(depth_ptr), head_size, frame, vp(xyz_ptr), V, vp(start_ptr),
+                                            vp(region_image_ptr), m, period, expand, cos2, *(vp(t.data_ptr()) for t in out)), 'mcg_gaze_targets_3d')
         return out
 
     def dwell_state(self, columns, device='cuda:0'):

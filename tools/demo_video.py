@@ -6,7 +6,7 @@ usage: demo_video.py FRAMES_DIR LABELS_DIR CONFIG CHECKPOINT --out gaze.json [--
                      [--batch-frames 448] [--head-class 1] [--ext jpg] [--smooth ALPHA] [--nv12 WxH FILE] [--matrix bt601] [--draw OUT] [--overlay] [--labels [SCALE]] [--fps NUM[/DEN]]
                      [--track [--slots 16] [--match-iou 0.3] [--max-age 5]] [--track-motion [GAIN[,DECAY]]]
                      [--color B,G,R] [--predictions DIR --in-shape HxW [--conf-thres 0.25] [--iou-thres 0.45]]
-                     [--detector MODULE:FACTORY [--img-size 640] [--half]] [--attention [--regions FILE.json] [--dwell [ENTER,EXIT]] [--heat [CELL,RADIUS]] [--heat-out FILE.npy]]
+                     [--detector MODULE:FACTORY [--img-size 640] [--half]] [--attention [--regions FILE.json] [--camera FX,FY,CX,CY [--regions3d FILE.json] [--head-size M] [--gaze-frame eye|camera]] [--dwell [ENTER,EXIT]] [--heat [CELL,RADIUS]] [--heat-out FILE.npy]]
 
 FRAMES_DIR holds 0.<ext>, 1.<ext>, ... (the demo's `frames/`), LABELS_DIR holds 0.txt, 1.txt, ... with lines `class x1 y1 x2 y2` in pixels
 (the demo's `result/labels/`); a frame without a label file shows no head.  CONFIG is the L2CS config, whose test pipeline the demo runs
@@ -39,6 +39,10 @@ of regions in frame pixels -- a screen, a shelf, a door --, each a rectangle [x1
 vertices in either winding (a screen seen off-axis is a quadrilateral, a shelf beside a pillar an L: even-odd rule, so a notch is outside);
 `target_region` is the index into that list.  Decided in the image plane, with conventional,
 untuned defaults (a looked-at head box grown by 0.25 of its longer side, a 10 degree cone for the camera).
+--camera FX,FY,CX,CY, with --attention: the targets are decided in camera space (pipeline.gaze_targets_3d): depth from --head-size M (0.24) over the
+head's size in pixels, the gaze relative to the line from the lens to the head (--gaze-frame eye, the default) or to the optical axis (camera),
+--regions3d FILE.json a JSON list of planar polygons [[x, y, z], ...] in camera coordinates (metres).  `target_hit` is then the 3-D point projected
+to pixels and `target_hit3d` the point; --regions are only what --overlay draws.
 --dwell [ENTER,EXIT], with --attention: how LONG they look (harness.run_head_video(dwell=...), pipeline.gaze_dwell on the device): each entry
 gains per frame `dwell_kind` and `dwell_frames` (the current target and its frames so far) and `episodes`, a list of {kind, target_id or
 target_region, start, frames, mutual_frames, reason (1 looked away, 2 the person left, 3 replaced by another target, 4 the video ended)}.  A
@@ -192,6 +196,10 @@ def main(argv=None):
                     help='--track with the constant-velocity motion model: a head missed for a few frames is looked for where it was going '
                          '(default 0.5,1.0: conventional alpha-beta values, not tuned on data)')
     ap.add_argument('--attention', action='store_true', help='add what every person looks at: another person, a region of --regions, the camera')
+    ap.add_argument('--camera', default=None, metavar='FX,FY,CX,CY', help='--attention decided in 3-D (pipeline.gaze_targets_3d): the intrinsics of the camera, in pixels')
+    ap.add_argument('--regions3d', default=None, metavar='FILE.json', help='regions of --camera: a JSON list of planar polygons [[x, y, z], ...] of 3 .. 32 vertices in camera coordinates (metres)')
+    ap.add_argument('--head-size', type=float, default=0.24, metavar='M', help='with --camera: the size of a head in metres, from which its depth follows (a convention, not tuned on data)')
+    ap.add_argument('--gaze-frame', choices=('eye', 'camera'), default='eye', help='with --camera: the gaze is relative to the line from the lens to the head (eye) or to the optical axis (camera)')
     ap.add_argument('--regions', default=None, metavar='FILE.json', help='regions of --attention in frame pixels: a JSON list of rectangles [x1, y1, x2, y2] and polygons [[x, y], ...] of 3 .. 32 vertices')
     ap.add_argument('--dwell', nargs='?', const='', default=None, metavar='ENTER,EXIT',
                     help='--attention with how long every look lasts: episodes with a start, a length and an end (default 3,2: conventions, not '
@@ -225,6 +233,10 @@ def main(argv=None):
         raise SystemExit('--regions belongs to --attention')
     if a.dwell is not None and not a.attention:
         raise SystemExit('--dwell belongs to --attention')
+    if a.camera is not None and not a.attention:
+        raise SystemExit('--camera belongs to --attention')
+    if a.camera is None and (a.regions3d is not None or a.head_size != 0.24 or a.gaze_frame != 'eye'):
+        raise SystemExit('--regions3d, --head-size and --gaze-frame belong to --camera')
     dwell = None if a.dwell is None else dwell_option(a.dwell)
     attention = None
     if a.attention:
@@ -232,6 +244,17 @@ def main(argv=None):
         if a.regions is not None:
             with open(a.regions) as f:
                 attention['regions'] = json.load(f)
+        if a.camera is not None:                              # targets in 3-D: camera space instead of the image plane
+            try:
+                attention['camera'] = [float(v) for v in a.camera.split(',')]
+            except ValueError:
+                attention['camera'] = []
+            if len(attention['camera']) != 4:
+                raise SystemExit(f'--camera takes FX,FY,CX,CY, got {a.camera!r}')
+            attention.update(head_size=a.head_size, frame=a.gaze_frame)
+            if a.regions3d is not None:
+                with open(a.regions3d) as f:
+                    attention['regions3d'] = json.load(f)
     track = dict(slots=a.slots, match_iou=a.match_iou, max_age=a.max_age) if a.track or a.track_motion is not None else None
     if a.track_motion is not None:
         try:
@@ -304,6 +327,7 @@ def main(argv=None):
                 **({} if attention is None else dict(target_kind=r['target_kind'].tolist(), target_id=[None if v is None else list(v) for v in r['target_id']],
                                                      target_region=r['target_region'].tolist(), target_hit=r['target_hit'].tolist(),
                                                      mutual=r['mutual'].tolist())),
+                **({} if attention is None or 'camera' not in attention else dict(target_hit3d=r['target_hit3d'].tolist())),
                 **({} if dwell is None else dict(dwell_kind=r['dwell_kind'].tolist(), dwell_frames=r['dwell_frames'].tolist(),
                                                  episodes=[{k: as_json(v) for k, v in e.items()} for e in r['episodes']]))) for r in res]
     with open(a.out, 'w') as f:
