@@ -1380,7 +1380,8 @@ int mcg_draw_labels_nv12(mcg_stream s, const mcg_nv12_image_desc* images_dev, in
  * atomics, graph-capturable.  The limits of the grid above, num_images in 1 .. 65535, frames of at most 8192 a side: anything else or a
  * null table returns MCG_ERR_ARG before the launch.  No byte outside [0, h) x [0, w) of any plane is touched, padding included, for ANY
  * table contents.  mcgaze_amd/arrows.py::draw_heat_host is the same on the host, bit for bit.  Out of scope: per-person maps, perspective
- * or depth, a decay per frame inside a multi-frame call, Gaussian kernels. */
+ * or depth (the grid is the image plane; "surface heat map" below keeps a grid ON a planar region), a decay per frame inside a multi-frame
+ * call, Gaussian kernels. */
 int mcg_gaze_heat_add(mcg_stream s, const float* hit_dev, const int32_t* kind_dev, const int32_t* image_of_dev, const int32_t* flags_dev,
                       const int32_t* mask_dev, int n, int32_t* heat_dev, int32_t* peak_dev, int C, int GH, int GW, int cell_shift, int radius,
                       int kinds, int period, int decay_shift, void* workspace_dev, size_t workspace_bytes);
@@ -1521,6 +1522,99 @@ int mcg_gaze_targets_3d(mcg_stream s, const float* boxes_dev, const float* gaze_
                         const float* region_xyz_dev, int num_vertices, const int32_t* region_start_dev, const int32_t* region_image_dev, int m,
                         int region_period, double expand, double camera_cos2, int32_t* kind_dev, int32_t* target_dev, float* t_dev,
                         float* hit_dev, int32_t* mutual_dev, int32_t* flags_dev, float* hit3d_dev);
+
+/* ---------------------------------------------------------------- surface heat map (additions to ABI 20; nothing above changes)
+ * Where ON a planar region -- a screen, a shelf, a poster -- looks have landed, over the calls so far, as a grid in the region's OWN
+ * coordinates: hit3d of "gaze targets, 3-D" is taken into the region's chart and accumulated into one grid per region
+ * (mcg_surface_heat_add); the grids are drawn back onto their regions, with the right perspective, into packed BGR frames
+ * (mcg_draw_surface_heat) or NV12 surfaces (mcg_draw_surface_heat_nv12) IN PLACE.  The grid does not move when the camera does: a caller
+ * whose camera moves hands in the region's vertices in the new camera coordinates and keeps the grid.  Every table is in device memory.
+ * Everything up to the first floor is double and uncontracted (no FMA): every product, quotient, sum and difference below is rounded on
+ * its own, in the order the parentheses give; f32 tables are widened exactly; there is no square root.  Comparisons with a NaN are false,
+ * and every min / max is written as the comparison it stands for.  Behind the first floor everything is integer arithmetic; >> is an
+ * arithmetic shift (a floor), / a floor of non-negative integers.
+ * REGIONS are the PolyRegions3D tables of "gaze targets, 3-D" (region_xyz f32 [V][3], region_start int32 [M + 1]) under its USABLE rule,
+ * unchanged: the offsets checked before any vertex load, 3 .. 32 vertices, every coordinate finite, N = e1 x e2 not all zero.
+ * CHART of region j.  a = v1 - v0;  N as in "gaze targets, 3-D";  b = N x a, written as N is:
+ *   bx = Ny * az - Nz * ay;   by = Nz * ax - Nx * az;   bz = Nx * ay - Ny * ax;
+ *   aa = (ax * ax + ay * ay) + az * az;   bb = (bx * bx + by * by) + bz * bz.
+ * For a point Q, with w = Q - v0:   s(Q) = ((wx * ax + wy * ay) + wz * az) / aa;   r(Q) = ((wx * bx + wy * by) + wz * bz) / bb.
+ * smin, smax, rmin, rmax over the region's OWN vertices k = 0, 1, ... in ascending order: the first vertex gives the start value, every
+ * later one replaces it on  s < smin  (s > smax; r likewise).  ws = smax - smin;  hr = rmax - rmin.
+ * The chart is USABLE iff the region is usable and aa, bb, ws, hr are finite and > 0.  The grid coordinates of Q in a GW x GH grid:
+ *   fu = ((s - smin) / ws) * GW;   fv = ((r - rmin) / hr) * GH.
+ * The chart is the bounding rectangle of the polygon in the (a, N x a) frame stretched over GW x GH cells: the aspect ratio is the
+ * caller's choice of grid (mcgaze_amd/attention.py::surface_extent gives the rectangle's sides in metres).  WINDING: for a screen listed
+ * CLOCKWISE from its top-left corner as the camera sees it (x right, y down), fu runs right and fv runs down, so grid row 0 is the top;
+ * the other winding flips the map vertically.
+ * 1. ACCUMULATE, mcg_surface_heat_add.  The state is heat int32 [M][GH][GW] and peak int32 [M].  THE ROW RULE: row k counts iff ALL of
+ *   flags_dev is NULL or flags[k] == 0;  mask_dev is NULL or mask[k] != 0;  kind[k] == 2;  0 <= target[k] < M;
+ *   region target[k] has a usable chart;  the three values of hit3d[k] are finite;
+ *   with Q = hit3d[k]:  fu and fv are finite and |fu|, |fv| <= 16384.
+ * Any other row is skipped: what the tables hold is never an error.  The row's cell is (ix, iy) = (floor(fu), floor(fv)) -- a hit on the
+ * far edge (fu == GW) has its cell just off the grid and still lights the edge cells within its radius.  THE SPLAT (radius 0 .. 8,
+ * weights (radius + 1 - |dx|) (radius + 1 - |dy|), taps off the grid dropped), THE UPDATE once per call (max(h, 0), decay_shift,
+ * saturation at 2^31 - 1) and peak[j] are those of "gaze heat map" with the region index in the camera's place; the clear and the update
+ * launches ARE that section's kernels.
+ *   hit3d_dev DEVICE f32 [n][3];  kind_dev, target_dev DEVICE int32 [n] (the three may be NULL iff n == 0);  flags_dev, mask_dev DEVICE int32 [n] or NULL
+ *   region_xyz_dev DEVICE f32 [num_vertices][3], NULL iff num_vertices == 0;  region_start_dev DEVICE int32 [M + 1]
+ *   heat_dev DEVICE int32 [M][GH][GW], read and written;  peak_dev DEVICE int32 [M], written
+ *   radius 0 .. 8 (cells);  decay_shift 0 .. 30, 0: off
+ *   workspace_dev DEVICE, aligned to 8 bytes, workspace_bytes >= MCG_SURFACE_CHART_BYTES * M + 4 * M * GH * GW; what it holds on entry
+ *   does not matter
+ * Four launches: a PLAN launch, one thread per region, writes each region's chart (v0, a, b, N, aa, bb, smin, ws, rmin, hr, a usable
+ * word, the dropped axis: 20 doubles, all zero for a chart that is not usable) into the workspace -- the scatter and the render read that
+ * table, so the chart is worked out once, by one piece of code --; the rest of the workspace and peak cleared; a SCATTER, one thread per
+ * (row, tap row), with integer vector atomics; the per-cell update over M regions.  Integer sums and maxima commute, so the result is a
+ * function of the inputs alone.  With n == 0 the call still decays and writes peak.
+ * 2. RENDER, mcg_draw_surface_heat / mcg_draw_surface_heat_nv12, over the image table of mcg_draw_gaze_arrows.  Picture p has camera
+ * c = p where cam_period == 0, else p % cam_period; cam f32 [C][4] as in "gaze targets, 3-D".  A picture is left untouched, byte for byte,
+ * if c >= C, if one of its camera's four numbers is not finite or not (fx > 0 and fy > 0), if it is not writable (no pixels; NV12: an odd
+ * size), or if it is larger than (max_h, max_w).  Region j APPLIES to picture p by the region_image / region_period rule of "gaze
+ * targets" with p in place of image_of[i]: region_image[j] < 0, or region_image[j] == p (region_period == 0), == p % region_period.
+ * For pixel (px, py):   d = ((px - cx) / fx, (py - cy) / fy, 1).  For every applying region with a usable chart:
+ *   den = (Nx * dx + Ny * dy) + Nz * dz;   tn = (Nx * v0x + Ny * v0y) + Nz * v0z;   t = tn / den.
+ * The plane is met iff den != 0, t is finite and t > 0;  then P = (t * dx, t * dy, t).  The region COVERS the pixel iff P is inside by the
+ * even-odd rule of "gaze targets, 3-D" (the axis of the largest |N| dropped).  The smallest t wins; on equal t the lower index.
+ * LEVEL, for the winner j, from fu, fv of P in j's chart; a pixel that no region covers, or whose fu or fv is not finite, keeps its bytes:
+ *   U = (int64)floor(fu * 256) - 128  (the floor is first held to [-2^30, 2^30]: both cells are then the same edge cell, no level changes);
+ *   i0 = U >> 8;  fx = U - i0 * 256;  i1 = i0 + 1;  both clamped to [0, GW - 1];  the same in v: j0, fy, j1, clamped to [0, GH - 1]
+ *   hab = max(heat[j][ja][ib], 0)
+ *   val = (256 - fx) (256 - fy) h00 + fx (256 - fy) h01 + (256 - fx) fy h10 + fx fy h11      (int64; val < 2^47)
+ *   full = max(full_dev[j], 1);  L = min(255, (val * 255) / (65536 * full))                  (int64)
+ * -- an interpolation between cell centres, edge cells repeated.  COLOUR, alpha, min_level, the BGR blend and the NV12 luma / chroma-pair
+ * rule are those of mcg_draw_heat, word for word; lut_dev is the same [256][4] table; full_dev is peak or the caller's own scale, int32 [M].
+ *   images_dev, num_images, max_h, max_w: as mcg_draw_gaze_arrows takes them
+ *   cam_dev DEVICE f32 [C][4], 1 <= C <= 4096;  cam_period, region_period >= 0;  region_image_dev DEVICE int32 [M]
+ *   heat_dev DEVICE int32 [M][GH][GW], full_dev DEVICE int32 [M] (both read);  min_level 1 .. 255
+ *   workspace_dev DEVICE, aligned to 8 bytes, workspace_bytes >= MCG_SURFACE_CHART_BYTES * M
+ * Two launches: the PLAN launch above, then ONE launch over (image, tile of 256 x 16 pixels; NV12: 256 x 32).  A workgroup first lists in
+ * LDS the applying regions with a usable chart whose projected bounding box, grown by one pixel, touches its tile.  The box is that of
+ * the vertices MOVED ALONG THE DROPPED AXIS ONTO THE PLANE through v0 -- a region's vertices need not be coplanar, and those are the
+ * points between which the exact test decides --; a region with such a point at z <= 0 counts as touching every tile.  The list is a cull: the exact
+ * test per pixel decides, and the result is that of the test made for every applying region.  A thread owns 16 pixels of a row (NV12:
+ * 16 x 2 and their 8 chroma pairs); a tile with an empty list, and a thread whose pixels are all uncovered or below min_level, read no
+ * pixel; the others read and write as mcg_draw_heat does (16-byte, 4-byte or byte accesses by the plane's address and pitch).  No atomics
+ * in global memory.  No byte outside [0, h) x [0, w) of any plane is touched, padding included, for ANY table contents.
+ * LIMITS.  n <= 65536, 1 <= M <= 4096, num_vertices <= 65536, 1 <= GH, GW <= 1024, M * GH * GW <= 2^24, num_images in 1 .. 65535, frames
+ * of at most 8192 a side: anything else, a null required table, a workspace that is too small or not aligned returns MCG_ERR_ARG before
+ * any launch, with nothing written.  A fixed number of launches, no allocation, no host sync, graph-capturable.
+ * mcgaze_amd/attention.py::surface_charts_host and surface_heat_host and mcgaze_amd/arrows.py::draw_surface_heat_host are the same on the
+ * host, bit for bit.  The python defaults (a grid of 32 x 32, radius 1) are CONVENTIONS, not tuned on data.
+ * Out of scope: curved surfaces, one-sided regions, lens distortion, a chart other than the bounding rectangle, per-person maps. */
+#define MCG_SURFACE_CHART_BYTES 160
+int mcg_surface_heat_add(mcg_stream s, const float* hit3d_dev, const int32_t* kind_dev, const int32_t* target_dev, const int32_t* flags_dev,
+                         const int32_t* mask_dev, int n, const float* region_xyz_dev, int num_vertices, const int32_t* region_start_dev, int M,
+                         int32_t* heat_dev, int32_t* peak_dev, int GH, int GW, int radius, int decay_shift, void* workspace_dev,
+                         size_t workspace_bytes);
+int mcg_draw_surface_heat(mcg_stream s, const mcg_image_desc* images_dev, int num_images, int max_h, int max_w, const float* cam_dev, int C,
+                          int cam_period, const float* region_xyz_dev, int num_vertices, const int32_t* region_start_dev,
+                          const int32_t* region_image_dev, int M, int region_period, const int32_t* heat_dev, const int32_t* full_dev, int GH, int GW,
+                          const unsigned char* lut_dev, int min_level, void* workspace_dev, size_t workspace_bytes);
+int mcg_draw_surface_heat_nv12(mcg_stream s, const mcg_nv12_image_desc* images_dev, int num_images, int max_h, int max_w, const float* cam_dev,
+                               int C, int cam_period, const float* region_xyz_dev, int num_vertices, const int32_t* region_start_dev,
+                               const int32_t* region_image_dev, int M, int region_period, const int32_t* heat_dev, const int32_t* full_dev, int GH,
+                               int GW, const unsigned char* lut_dev, int min_level, void* workspace_dev, size_t workspace_bytes);
 
 /* ---------------------------------------------------------------- measurement aids (bench.py)
  * While armed, every launch of the contraction kernel made by THIS engine is bracketed by a hipEvent pair on its launch stream.

@@ -773,6 +773,139 @@ def draw_heat_host(frames, heat, full, cell_shift, period=0, lut=None, min_level
     return out[0] if single else out
 
 
+# ---------------------------------------------------------------- surface heat map (include/mcgaze_hip.h, "surface heat map")
+def surface_cover(h, w, cam, charts, xyz, start, applies):
+    """Which region every pixel of an h x w picture shows, by the header's RENDER rule -> (region int64 [h, w], -1: none; t float64 [h, w],
+    the depth of its point).  cam: float64 fx fy cx cy; charts: surface_charts_host's; xyz float64 [V,3]; applies: the regions of this
+    picture, ascending."""
+    with np.errstate(all='ignore'):
+        return _surface_cover(h, w, cam, charts, xyz, start, applies)
+
+
+def _surface_cover(h, w, cam, charts, xyz, start, applies):
+    fx, fy, cx, cy = cam
+    dx, dy = ((np.arange(w, dtype=np.float64) - cx) / fx)[None, :], ((np.arange(h, dtype=np.float64) - cy) / fy)[:, None]
+    best, region = np.full((h, w), np.inf), np.full((h, w), -1, dtype=np.int64)
+    for j in applies:
+        c = charts[j]
+        if c[A.CHART_INDEX['usable']] == 0.0:
+            continue
+        v0, N, axis = c[0:3], c[9:12], int(c[A.CHART_INDEX['axis']])
+        den = (N[0] * dx + N[1] * dy) + N[2] * 1.0
+        tn = (N[0] * v0[0] + N[1] * v0[1]) + N[2] * v0[2]
+        t = tn / den
+        met = (den != 0.0) & np.isfinite(t) & (t > 0.0)
+        P = (t * dx, t * dy, t * 1.0)
+        iu, iv = (1 if axis == 0 else 0), (1 if axis == 2 else 2)
+        pu, pv = P[iu], P[iv]
+        v = xyz[start[j]:start[j + 1]]
+        inside = np.zeros((h, w), dtype=bool)
+        for e in range(len(v)):
+            (au, av), (bu, bv) = v[e, [iu, iv]], v[(e + 1) % len(v), [iu, iv]]
+            inside ^= ((av > pv) != (bv > pv)) & (pu < au + ((pv - av) * (bu - au)) / (bv - av))
+        won = met & inside & (t < best)                           # ascending j and a strict <: the lower index keeps an equal t
+        best, region = np.where(won, t, best), np.where(won, j, region)
+    return region, best
+
+
+def surface_levels(h, w, cam, charts, region, t, heat, full):
+    """The LEVEL of every pixel from ``surface_cover``'s (region, t): the winner's grid interpolated between cell centres in 64-bit
+    integers -> int64 [h, w] in 0 .. 255, 0 where no region covers the pixel or a grid coordinate is not finite."""
+    with np.errstate(all='ignore'):
+        return _surface_levels(h, w, cam, charts, region, t, heat, full)
+
+
+def _surface_levels(h, w, cam, charts, region, t, heat, full):
+    fx, fy, cx, cy = cam
+    M, GH, GW = heat.shape
+    dx, dy = np.broadcast_to(((np.arange(w, dtype=np.float64) - cx) / fx)[None, :], (h, w)), \
+        np.broadcast_to(((np.arange(h, dtype=np.float64) - cy) / fy)[:, None], (h, w))
+    level = np.zeros((h, w), dtype=np.int64)
+    on = region >= 0
+    if not on.any():
+        return level
+    j, tt = region[on], t[on]
+    P = np.stack([tt * dx[on], tt * dy[on], tt * 1.0], axis=-1)
+    fu, fv = A.surface_coords(charts, j, P, GW, GH)
+    ok = np.isfinite(fu) & np.isfinite(fv)
+
+    def axis(f, cells):
+        g = np.clip(np.floor(np.where(ok, f, 0.0) * 256.0), -2.0 ** 30, 2.0 ** 30)
+        U = g.astype(np.int64) - 128
+        i0 = U >> 8                                               # arithmetic: floors
+        return np.clip(i0, 0, cells - 1), np.clip(i0 + 1, 0, cells - 1), U - i0 * 256
+
+    x0, x1, wx = axis(fu, GW)
+    y0, y1, wy = axis(fv, GH)
+    grid = np.maximum(heat.astype(np.int64), 0)
+    val = (256 - wx) * (256 - wy) * grid[j, y0, x0] + wx * (256 - wy) * grid[j, y0, x1] + (256 - wx) * wy * grid[j, y1, x0] + wx * wy * grid[j, y1, x1]
+    L = np.minimum(255, (val * 255) // (65536 * np.maximum(full[j], 1)))
+    level[on] = np.where(ok, L, 0)
+    return level
+
+
+def draw_surface_heat_host(frames, heat, full, cam, regions, region_image=None, region_period=0, cam_period=0, lut=None, min_level=1,
+                           pixel_format='bgr', matrix='bt601'):
+    """The surface heat maps drawn back onto their regions with numpy: what DevicePipeline.draw_surface_heat (mcg_draw_surface_heat /
+    mcg_draw_surface_heat_nv12) writes on the device, bit for bit (include/mcgaze_hip.h, "surface heat map": the ray of a pixel, the
+    nearest region that covers it, the level from that region's grid; the blend and the NV12 chroma rule are draw_heat_host's).
+
+    frames, pixel_format, matrix, lut, min_level: as for draw_heat_host.  heat: int32 [M, GH, GW] (surface_heat_host); full: int [M], the
+    scale of each region -- surface_heat_host's peak -- or one int for all.  cam: [fx, fy, cx, cy] or [C, 4]; picture p has camera p, with
+    cam_period p % cam_period, and is left as it is where that camera is not below C, is not finite or has fx, fy <= 0.  regions: the list
+    of ``regions_3d`` or a PolyRegions3D, in camera coordinates; region_image [M] (None: -1, every picture) and region_period as
+    gaze_targets takes them, with the picture's index in image_of's place.
+    -> annotated COPIES in the form given (NV12 frames as (y [H,W], uv [H/2,W]) pairs)."""
+    who = 'draw_surface_heat_host'
+    nv12, _ = _pixel_format(pixel_format, matrix)
+    _, _, region_period = A._target_params(0.0, None, region_period, who)
+    _, _, cam_period = A._target3d_params(A.HEAD_SIZE, 'eye', cam_period, who)
+    _, min_level = A._heat_scale(who, None, min_level)
+    table = heat_lut(lut, nv12, matrix).astype(np.int64)
+    xyz32, start = A._surface_regions(who, regions)
+    _, _, ri = A._poly3d_tables(who, A.PolyRegions3D(xyz32, start), region_image)
+    heat = np.asarray(_host_array(heat))
+    M, GH, GW = A._surface_grid(who, heat.shape)
+    if M != len(start) - 1:
+        raise ValueError(f'{who}: heat holds {M} grids for {len(start) - 1} regions')
+    full = np.broadcast_to(np.asarray(_host_array(full), dtype=np.int64).reshape(-1), (M,)) if np.size(full) in (1, M) else None
+    if full is None:
+        raise ValueError(f'{who}: full is one int or one per region, [{M}]')
+    cam64 = A._camera_table(who, cam).astype(np.float64)
+    charts, xyz = A.surface_charts_host(A.PolyRegions3D(xyz32, start)), xyz32.astype(np.float64)
+    single = not isinstance(frames, list)
+    frames = [frames] if single else frames
+    if nv12:
+        out = [tuple(np.array(p) for p in _nv12_planes(k, f)[:2]) for k, f in enumerate(frames)]
+        sizes = [y.shape for y, _ in out]
+    else:
+        out = [_bgr_frame(k, np.array(f)) for k, f in enumerate(frames)]
+        sizes = [a.shape[:2] for a in out]
+    for p, (h, w) in enumerate(sizes):
+        c = p % cam_period if cam_period else p
+        if c >= len(cam64) or h > ARROW_SIDE or w > ARROW_SIDE:
+            continue
+        k = cam64[c]
+        if not (np.isfinite(k).all() and k[0] > 0.0 and k[1] > 0.0):
+            continue
+        key = p % region_period if region_period else p
+        applies = np.flatnonzero((ri < 0) | (ri == key))
+        region, t = surface_cover(h, w, k, charts, xyz, start, applies)
+        level = surface_levels(h, w, k, charts, region, t, heat, full)
+        if nv12:
+            y, uv = out[p]
+            on = level >= min_level
+            y[on] = _heat_blend(y[on], table[level[on], 0], table[level[on], 3])
+            top = level.reshape(h // 2, 2, w // 2, 2).max(axis=(1, 3))    # the pair's level: the highest of its four luma pixels
+            on = top >= min_level
+            pairs = uv.reshape(h // 2, w // 2, 2)
+            pairs[on] = _heat_blend(pairs[on], table[top[on], 1:3], table[top[on], 3:4])
+        else:
+            on = level >= min_level
+            out[p][on] = _heat_blend(out[p][on], table[level[on], :3], table[level[on], 3:4])
+    return out[0] if single else out
+
+
 # ---------------------------------------------------------------- anonymised heads (include/mcgaze_hip.h, "anonymised heads")
 ANON_SHAPES, ANON_MODES = ('box', 'ellipse'), ('mosaic', 'fill')
 

@@ -996,3 +996,194 @@ def gaze_heat_host(hit, kind, image_of, heat, flags=None, mask=None, cell_shift=
         h -= h >> decay
     out = np.minimum(h + taps, HEAT_MAX).astype(np.int32)
     return out, out.reshape(C, -1).max(axis=1).astype(np.int32)
+
+
+# ---------------------------------------------------------------- surface heat map (include/mcgaze_hip.h, "surface heat map")
+SurfaceHeatState = collections.namedtuple('SurfaceHeatState', 'heat peak')     # heat int32 [M, GH, GW], peak int32 [M]: one grid per region
+SURFACE_GRID, SURFACE_RADIUS = (32, 32), 1                       # (GW, GH) and the splat's radius in cells: conventions, not tuned on data
+SURFACE_MAX_SIDE, SURFACE_COORD = 1024, 16384
+CHART_FIELDS = ('v0x', 'v0y', 'v0z', 'ax', 'ay', 'az', 'bx', 'by', 'bz', 'Nx', 'Ny', 'Nz', 'aa', 'bb', 'smin', 'ws', 'rmin', 'hr', 'usable', 'axis')
+CHART_INDEX = {name: k for k, name in enumerate(CHART_FIELDS)}   # the 20 doubles of a chart, MCG_SURFACE_CHART_BYTES = 160
+
+
+def _surface_regions(who, regions):
+    """``regions`` of the surface entries -- the list of ``regions_3d`` or a PolyRegions3D, at least one region -> (xyz f32 [V,3], start
+    int32 [M+1]), checked (TypeError / ValueError): shapes, dtypes and counts only."""
+    if regions is None:
+        raise ValueError(f'{who}: regions are required: the list of regions_3d or a PolyRegions3D')
+    xyz, start, _ = _poly3d_tables(who, regions, None)
+    if len(start) < 2:
+        raise ValueError(f'{who}: at least one region')
+    _check_counts(who, 0, len(start) - 1, len(xyz))
+    return xyz, start
+
+
+def _surface_grid(who, shape):
+    """The shape of the grids, checked against the entries' limits (ValueError) -> (M, GH, GW)."""
+    if len(shape) != 3 or not (1 <= shape[0] <= MAX_REGIONS and 1 <= shape[1] <= SURFACE_MAX_SIDE and 1 <= shape[2] <= SURFACE_MAX_SIDE) or \
+            shape[0] * shape[1] * shape[2] > HEAT_MAX_CELLS:
+        raise ValueError(f'{who}: heat is [M, GH, GW] with M in 1 .. {MAX_REGIONS}, GH and GW in 1 .. {SURFACE_MAX_SIDE} and at most 2^24 cells; '
+                         f'got {tuple(shape)}')
+    return tuple(int(v) for v in shape)
+
+
+def _surface_params(who, radius, decay):
+    """radius 0 .. 8 and decay 0 .. 30, validated (ValueError)."""
+    for name, v, lo, hi in (('radius', radius, 0, 8), ('decay', decay, 0, 30)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= v <= hi:
+            raise ValueError(f'{who}: {name} must be an int in {lo} .. {hi}, got {v!r}')
+    return int(radius), int(decay)
+
+
+def _surface_grid_option(who, grid):
+    """``grid`` = (GW, GH), two ints in 1 .. 1024 (ValueError) -> (GW, GH)."""
+    ok = isinstance(grid, (tuple, list)) and len(grid) == 2 and all(isinstance(v, (int, np.integer)) and not isinstance(v, bool) and
+                                                                   1 <= v <= SURFACE_MAX_SIDE for v in grid)
+    if not ok:
+        raise ValueError(f'{who}: grid is (GW, GH), two ints in 1 .. {SURFACE_MAX_SIDE}; got {grid!r}')
+    return int(grid[0]), int(grid[1])
+
+
+def _surface_options(who, surface_heat, attention, draw):
+    """The ``surface_heat=`` option of LiveGaze and run_head_video, validated (ValueError) -> None (off) or dict(grid, radius, decay, draw,
+    full_scale, min_level).  surface_heat: None / False, True or a dict of those.  It accumulates hit3d of attention=dict(camera=...,
+    regions3d=...) on those regions and needs both; with draw=True it needs ``draw`` (the frames it is blended into).  surface_heat=True
+    draws where frames are drawn at all.  grid (32, 32) and radius 1 are conventions, not tuned on data."""
+    if surface_heat is None or surface_heat is False:
+        return None
+    if surface_heat is not True and not isinstance(surface_heat, dict):
+        raise ValueError(f'{who}: surface_heat is None, True or a dict of grid, radius, decay, draw, full_scale and min_level; got {surface_heat!r}')
+    opts = dict(grid=SURFACE_GRID, radius=SURFACE_RADIUS, decay=0, draw=True, full_scale=None, min_level=1)
+    given = {} if surface_heat is True else dict(surface_heat)
+    if set(given) - set(opts):
+        raise ValueError(f'{who}: surface_heat takes {sorted(opts)}; got {sorted(given)}')
+    three_d = None if attention is None else attention[2].get('three_d')
+    if three_d is None or len(three_d['regions'].start) < 2:
+        raise ValueError(f'{who}: surface_heat accumulates hit3d on planar regions: give attention=dict(camera=..., regions3d=...) as well')
+    if surface_heat is True:
+        opts['draw'] = bool(draw)
+    opts.update(given)
+    if not isinstance(opts['draw'], (bool, np.bool_)):
+        raise ValueError(f"{who}: surface_heat's draw is True or False, got {opts['draw']!r}")
+    if opts['draw'] and not draw:
+        raise ValueError(f'{who}: surface_heat with draw=True is blended into the frames draw hands out: it needs draw')
+    opts['grid'] = _surface_grid_option(f'{who}(surface_heat=...)', opts['grid'])
+    _surface_grid(f'{who}(surface_heat=...)', (len(three_d['regions'].start) - 1, opts['grid'][1], opts['grid'][0]))
+    _surface_params(f'{who}(surface_heat=...)', opts['radius'], opts['decay'])
+    _heat_scale(f'{who}(surface_heat=...)', opts['full_scale'], opts['min_level'])
+    return opts
+
+
+def surface_charts_host(regions):
+    """The CHART of every region ("surface heat map"), what the plan launch of mcg_surface_heat_add and mcg_draw_surface_heat writes, bit
+    for bit -> float64 [M, 20], the columns CHART_FIELDS: v0, a = v1 - v0, b = N x a, N, aa, bb, smin, ws, rmin, hr, usable (1 / 0) and the
+    dropped axis.  A region that is not usable, or whose aa, bb, ws or hr is not finite and positive, has a row of zeros.  regions: the
+    list of ``regions_3d`` or a PolyRegions3D."""
+    xyz32, start = _surface_regions('surface_charts_host', regions)
+    xyz = xyz32.astype(np.float64)
+    ok, first, count, N, axis = _usable_regions_3d(xyz, start)
+    out = np.zeros((len(first), len(CHART_FIELDS)))
+    with np.errstate(all='ignore'):
+        for j in np.flatnonzero(ok):
+            v = xyz[first[j]:first[j] + count[j]]
+            v0, a, n = v[0], v[1] - v[0], N[j]
+            b = np.array([n[1] * a[2] - n[2] * a[1], n[2] * a[0] - n[0] * a[2], n[0] * a[1] - n[1] * a[0]])
+            aa, bb = (a[0] * a[0] + a[1] * a[1]) + a[2] * a[2], (b[0] * b[0] + b[1] * b[1]) + b[2] * b[2]
+            w = v - v0
+            s = ((w[:, 0] * a[0] + w[:, 1] * a[1]) + w[:, 2] * a[2]) / aa
+            r = ((w[:, 0] * b[0] + w[:, 1] * b[1]) + w[:, 2] * b[2]) / bb
+            smin = smax = s[0]
+            rmin = rmax = r[0]
+            for k in range(1, len(v)):                           # each written as the comparison it stands for: a NaN replaces nothing
+                smin, smax = (s[k] if s[k] < smin else smin), (s[k] if s[k] > smax else smax)
+                rmin, rmax = (r[k] if r[k] < rmin else rmin), (r[k] if r[k] > rmax else rmax)
+            ws, hr = smax - smin, rmax - rmin
+            if all(np.isfinite(x) and x > 0.0 for x in (aa, bb, ws, hr)):
+                out[j] = (*v0, *a, *b, *n, aa, bb, smin, ws, rmin, hr, 1.0, float(axis[j]))
+    return out
+
+
+def surface_extent(regions):
+    """The sides of every chart's rectangle in METRES -> float64 [M, 2] = (ws * |a|, hr * |b|), width along a = v1 - v0 and height along
+    N x a; zeros for a chart that is not usable.  Host only (the one square root of this section): for showing an exported grid at the
+    right aspect."""
+    c = surface_charts_host(regions)
+    return np.stack([c[:, CHART_INDEX['ws']] * np.sqrt(c[:, CHART_INDEX['aa']]), c[:, CHART_INDEX['hr']] * np.sqrt(c[:, CHART_INDEX['bb']])], axis=1)
+
+
+def surface_coords(charts, j, Q, GW, GH):
+    """fu, fv of the points Q float64 [..., 3] in the charts of the regions j [...] (usable ones) -> (fu, fv) float64 [...], as the header
+    writes them; the caller silences the floating-point warnings."""
+    c = charts[j]
+    wx, wy, wz = Q[..., 0] - c[..., 0], Q[..., 1] - c[..., 1], Q[..., 2] - c[..., 2]
+    s = ((wx * c[..., 3] + wy * c[..., 4]) + wz * c[..., 5]) / c[..., 12]
+    r = ((wx * c[..., 6] + wy * c[..., 7]) + wz * c[..., 8]) / c[..., 13]
+    return ((s - c[..., 14]) / c[..., 15]) * float(GW), ((r - c[..., 16]) / c[..., 17]) * float(GH)
+
+
+def surface_heat_host(hit3d, kind, target, regions, heat, flags=None, mask=None, radius=SURFACE_RADIUS, decay=0):
+    """``mcg_surface_heat_add`` in numpy, bit for bit (include/mcgaze_hip.h, "surface heat map"): the 3-D hit points of the rows that look
+    at a region, taken into that region's chart and splatted into its grid.  hit3d [n,3] (read as f32), kind, target [n] integers --
+    gaze_targets_3d's results --, flags / mask [n] integers or None; regions: the list of ``regions_3d`` or a PolyRegions3D; heat: int32
+    [M, GH, GW], the grids as they stood (not changed); radius 0 .. 8 cells, decay: the decay shift, 0 .. 30, 0 off.
+    A row counts iff flags is None or 0, mask is None or not 0, kind == 2, 0 <= target < M, that region's chart is usable, hit3d is finite
+    and both grid coordinates are finite and within +-16384.  The splat, the update and the peak are gaze_heat_host's.
+    -> (heat int32 [M, GH, GW], peak int32 [M]: each region's maximum)."""
+    who = 'surface_heat_host'
+    radius, decay = _surface_params(who, radius, decay)
+    xyz32, start = _surface_regions(who, regions)
+    heat = np.asarray(_host_array(heat))
+    if heat.dtype != np.int32:
+        raise TypeError(f'{who}: heat must be int32, got {heat.dtype}')
+    M, GH, GW = _surface_grid(who, heat.shape)
+    if M != len(start) - 1:
+        raise ValueError(f'{who}: heat holds {M} grids for {len(start) - 1} regions')
+    hit = np.asarray(_host_array(hit3d), dtype=np.float32)
+    hit = hit.reshape(0, 3) if hit.size == 0 else hit
+    n = len(hit)
+    if hit.ndim != 2 or hit.shape[1] != 3 or n > MAX_ROWS:
+        raise ValueError(f'{who}: hit3d must be [n, 3] with n <= {MAX_ROWS}, got {hit.shape}')
+    ints = {}
+    for name, t in (('kind', kind), ('target', target), ('flags', flags), ('mask', mask)):
+        if t is None:
+            if name in ('kind', 'target'):
+                raise ValueError(f'{who}: {name} is required')
+            continue
+        a = np.asarray(_host_array(t)).reshape(-1)
+        if a.size and a.dtype.kind not in 'iub':
+            raise TypeError(f'{who}: {name} must hold integers, got {a.dtype}')
+        if a.shape != (n,):
+            raise ValueError(f'{who}: {name} must be [{n}], one per row; got {a.shape}')
+        ints[name] = a.astype(np.int64)
+    charts = surface_charts_host(PolyRegions3D(xyz32, start))
+    ok = np.ones(n, dtype=bool)
+    if 'flags' in ints:
+        ok &= ints['flags'] == 0
+    if 'mask' in ints:
+        ok &= ints['mask'] != 0
+    tg = ints['target']
+    ok &= (ints['kind'] == KIND_REGION) & (tg >= 0) & (tg < M)
+    j = np.where(ok, tg, 0)
+    ok &= charts[j, CHART_INDEX['usable']] != 0.0
+    Q = hit.astype(np.float64)
+    ok &= np.isfinite(Q).all(axis=1)
+    with np.errstate(all='ignore'):
+        fu, fv = surface_coords(charts, j, Q, GW, GH)
+        ok &= (np.abs(fu) <= SURFACE_COORD) & (np.abs(fv) <= SURFACE_COORD)      # (a NaN fails the comparison)
+    rows = np.flatnonzero(ok)
+    taps = np.zeros((M, GH, GW), dtype=np.int64)
+    if len(rows):
+        cell = np.stack([np.floor(fu[rows]), np.floor(fv[rows])], axis=1).astype(np.int64)
+        d = np.arange(-radius, radius + 1, dtype=np.int64)
+        wgt = radius + 1 - np.abs(d)
+        x, y = cell[:, 0, None, None] + d[None, None, :], cell[:, 1, None, None] + d[None, :, None]      # [rows, dy, dx]
+        x, y = np.broadcast_arrays(x, y)
+        w = np.broadcast_to(wgt[None, :, None] * wgt[None, None, :], x.shape)
+        c = np.broadcast_to(j[rows][:, None, None], x.shape)
+        inside = (x >= 0) & (x < GW) & (y >= 0) & (y < GH)
+        np.add.at(taps, (c[inside], y[inside], x[inside]), w[inside])
+    h = np.maximum(heat.astype(np.int64), 0)
+    if decay:
+        h -= h >> decay
+    out = np.minimum(h + taps, HEAT_MAX).astype(np.int32)
+    return out, out.reshape(M, -1).max(axis=1).astype(np.int32)

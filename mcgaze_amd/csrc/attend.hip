@@ -22,6 +22,7 @@
 #include <climits>
 
 #include "common.hpp"
+#include "region3d.hpp"   // a 3-D region: usable, normal, dropped axis, the even-odd test (shared with surface.hip)
 
 #define MCG_ATTEND_ROWS 65536
 #define MCG_ATTEND_REGIONS 4096
@@ -526,29 +527,18 @@ __global__ __launch_bounds__(MCG_ATTEND_THREADS) void gaze_targets_3d_kernel(
       const int j = base + tid;
       int key = INT_MIN;
       if (j < m) {
-        const int s = region_start[j], e = region_start[j + 1];  // (j + 1 <= m: the table has m + 1 words)
-        const int c = 0 <= s && s <= e && e <= num_vertices ? e - s : 0;        // (whatever the words hold, the difference cannot overflow)
-        bool ok = c >= 3 && c <= MCG_ATTEND_POLY_VERTS;
-        if (ok) {                                                // every vertex below lies inside xyz[0 .. num_vertices)
-          const float* v = xyz + 3 * (size_t)s;
-          for (int k = 0; k < 3 * c; ++k) ok = ok && isfinite(v[k]);
-          if (ok) {
-            const double v0x = v[0], v0y = v[1], v0z = v[2];
-            const double e1x = (double)v[3] - v0x, e1y = (double)v[4] - v0y, e1z = (double)v[5] - v0z;
-            const double e2x = (double)v[6] - v0x, e2y = (double)v[7] - v0y, e2z = (double)v[8] - v0z;
-            const double Nx = e1y * e2z - e1z * e2y, Ny = e1z * e2x - e1x * e2z, Nz = e1x * e2y - e1y * e2x;
-            const double ax = fabs(Nx), ay = fabs(Ny), az = fabs(Nz);
-            ok = !(Nx == 0.0 && Ny == 0.0 && Nz == 0.0);
-            c_a[tid] = Nx;
-            c_b[tid] = Ny;
-            c_c[tid] = Nz;
-            c_d[tid] = v0x;
-            c_e[tid] = v0y;
-            c_f[tid] = v0z;
-            c_start[tid] = s;
-            c_count[tid] = c;
-            c_axis[tid] = ax >= ay && ax >= az ? 0 : ay >= az ? 1 : 2;     // the dropped axis: the largest |N|, the first on ties
-          }
+        const region3d r = region3d_load(xyz, num_vertices, region_start, j);    // (the offsets are checked before the first vertex load)
+        const bool ok = r.usable;
+        if (ok) {
+          c_a[tid] = r.Nx;
+          c_b[tid] = r.Ny;
+          c_c[tid] = r.Nz;
+          c_d[tid] = r.v0x;
+          c_e[tid] = r.v0y;
+          c_f[tid] = r.v0z;
+          c_start[tid] = r.start;
+          c_count[tid] = r.count;
+          c_axis[tid] = r.axis;
         }
         if (ok) key = region_image[j] < 0 ? -1 : region_image[j];
       }
@@ -576,19 +566,8 @@ __global__ __launch_bounds__(MCG_ATTEND_THREADS) void gaze_targets_3d_kernel(
           const double t = q > 0.0 ? q : 0.0;
           if (!(t < best)) continue;                             // (it could not win: its polygon need not be walked)
           const double Px = X + t * Dx, Py = Y + t * Dy, Pz = Z + t * Dz;
-          const int axis = c_axis[c], cnt = c_count[c];          // (one LDS word for the whole workgroup -> uniform addresses below)
-          const int iu = axis == 0 ? 1 : 0, iv = axis == 2 ? 1 : 2;
-          const double pu = axis == 0 ? Py : Px, pv = axis == 2 ? Py : Pz;
-          const float* v = xyz + 3 * (size_t)c_start[c];
-          const double fu = v[iu], fv = v[iv];
-          double au = fu, av = fv;
-          bool inside = false;
-          for (int k = 1; k <= cnt; ++k) {                       // edge k - 1: a = v[k - 1] -> b = v[k mod cnt]
-            const double bu = k < cnt ? (double)v[3 * k + iu] : fu, bv = k < cnt ? (double)v[3 * k + iv] : fv;
-            if ((av > pv) != (bv > pv) && pu < au + ((pv - av) * (bu - au)) / (bv - av)) inside = !inside;
-            au = bu;
-            av = bv;
-          }
+          // (c_axis, c_count, c_start: one LDS word for the whole workgroup -> uniform addresses in the walk)
+          const bool inside = region3d_inside(xyz + 3 * (size_t)c_start[c], c_count[c], c_axis[c], Px, Py, Pz);
           if (inside) {
             best = t;
             best_target = base + c;

@@ -13,20 +13,12 @@
 // leaves if none reaches min_level, and otherwise reads, blends and writes its 48 bytes (NV12: 16 + 16 + 16) in 16-byte accesses where the
 // plane's address and pitch allow, in 4-byte accesses where only those are aligned, byte by byte at the right edge and for any other
 // pitch.  A tile whose cells are all zero leaves before any pixel is read.  No atomics, no scratch.
-#include "draw_common.hpp"   // the bounds, PackedTarget / Nv12Target, the span accesses
+#include "heat_common.hpp"   // the clear and update launches, the blend, a thread's span of pixels (shared with surface.hip)
 
-#define MCG_HEAT_MAX_CELLS (1 << 24)
-#define MCG_HEAT_SPAN 16                    // pixels of a row a thread owns
 #define MCG_HEAT_TILE_W (16 * MCG_HEAT_SPAN) // 16 threads side by side
 #define MCG_HEAT_LDS_W (MCG_HEAT_TILE_W + 2) // cell_shift 0: the tile's 256 columns and the one to their right; one spare
 
-// ---------------------------------------------------------------- accumulate
-__global__ __launch_bounds__(256) void heat_clear_kernel(int32_t* __restrict__ work, int cells, int32_t* __restrict__ peak, int C) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i < cells) work[i] = 0;
-  if (i < C) peak[i] = 0;
-}
-
+// ---------------------------------------------------------------- accumulate (heat_clear_kernel and heat_update_kernel: heat_common.hpp)
 __global__ __launch_bounds__(256) void heat_scatter_kernel(const float* __restrict__ hit, const int32_t* __restrict__ kind,
                                                            const int32_t* __restrict__ image_of, const int32_t* __restrict__ flags,
                                                            const int32_t* __restrict__ mask, int n, int32_t* __restrict__ work, int C, int GH, int GW,
@@ -55,28 +47,6 @@ __global__ __launch_bounds__(256) void heat_scatter_kernel(const float* __restri
   for (int dx = -radius; dx <= radius; ++dx) {
     const int x = ix + dx;
     if (x >= 0 && x < GW) atomicAdd(row + x, wy * (radius + 1 - abs(dx)));   // at most 65536 rows of 81: the sum stays below 2^23
-  }
-}
-
-__global__ __launch_bounds__(256) void heat_update_kernel(int32_t* __restrict__ heat, const int32_t* __restrict__ work, int32_t* __restrict__ peak,
-                                                          int cells, int decay_shift) {
-  const int c = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
-  int v = 0;
-  if (i < cells) {
-    const size_t at = (size_t)c * cells + i;
-    int h = max(heat[at], 0);                                     // a negative value is taken as 0
-    if (decay_shift > 0) h -= h >> decay_shift;
-    v = (int)min((long long)h + work[at], 2147483647LL);
-    heat[at] = v;
-  }
-  // the block's maximum: an xor-shuffle reduction inside each wave of 64, the four waves' maxima through four LDS words
-  __shared__ int top[4];
-  for (int o = 32; o; o >>= 1) v = max(v, __shfl_xor(v, o));
-  if ((threadIdx.x & 63) == 0) top[threadIdx.x >> 6] = v;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const int m = max(max(top[0], top[1]), max(top[2], top[3]));
-    if (m > 0) atomicMax(peak + c, m);                            // peak was cleared by the first launch; a maximum commutes
   }
 }
 
@@ -111,9 +81,6 @@ extern "C" int mcg_gaze_heat_add(mcg_stream s, const float* hit_dev, const int32
 }
 
 // ---------------------------------------------------------------- render
-// (src (255 - a) + col a + 127) / 255: at most 255 * 255 + 127, the division a multiply and a shift
-__device__ __forceinline__ unsigned heat_blend(unsigned src, unsigned col, unsigned a) { return (src * (255u - a) + col * a + 127u) / 255u; }
-
 template <class Target>
 __global__ __launch_bounds__(256) void heat_render_kernel(const typename Target::Image* __restrict__ images, int tiles_x, int max_h, int max_w,
                                                           const int32_t* __restrict__ heat, const int32_t* __restrict__ full_dev, int C, int GH, int GW,
@@ -162,68 +129,14 @@ __global__ __launch_bounds__(256) void heat_render_kernel(const typename Target:
                           (long long)(fx * fy) * h11;                                   // below 2^45
       // L = min(255, floor(v 255 / (4 S S full))): 4 S S is a power of two, and the quotient by full is found bit by bit -- eight
       // multiplications in place of a 64-bit division
-      const long long a = (v * 255) >> (2 * cell_shift + 2);
-      int L = 0;
-      if (a >= full) {
-#pragma unroll
-        for (int b = 128; b; b >>= 1)
-          if ((long long)(L | b) * full <= a) L |= b;
-      }
+      const int L = heat_level((v * 255) >> (2 * cell_shift + 2), full);
       level[r][j] = L;
       most = max(most, L);
     }
   }
   if (most < min_level) return;                                   // none of this thread's pixels is written: none is read either
 
-  const int span = min(MCG_HEAT_SPAN, im.w - px0);                // pixels of the thread inside the picture
-  const bool whole = span == MCG_HEAT_SPAN;
-  if constexpr (R == 1) {
-    const int mode = span_mode(im.src, im.pitch, whole);
-    unsigned char* p = (unsigned char*)im.src + (size_t)py0 * im.pitch + (size_t)px0 * 3;
-    unsigned w[12];
-    span_load<12>(p, w, mode, 3 * span);
-#pragma unroll
-    for (int j = 0; j < MCG_HEAT_SPAN; ++j) {
-      const int L = level[0][j];
-      if (L >= min_level) {
-        const unsigned c = colour[L], a = c >> 24;
-#pragma unroll
-        for (int ch = 0; ch < 3; ++ch) span_set_byte(w, 3 * j + ch, heat_blend(span_byte(w, 3 * j + ch), (c >> (8 * ch)) & 255u, a));
-      }
-    }
-    span_store<12>(p, w, mode, 3 * span);
-  } else {
-    const int mode_y = span_mode(im.y, im.pitch_y, whole), mode_uv = span_mode(im.uv, im.pitch_uv, whole);
-    // py0 even and < h, h even: both rows are inside; px0 even, w even: span is even and the pairs are whole
-#pragma unroll
-    for (int r = 0; r < 2; ++r) {
-      unsigned char* p = (unsigned char*)im.y + (size_t)(py0 + r) * im.pitch_y + px0;
-      unsigned w[4];
-      span_load<4>(p, w, mode_y, span);
-#pragma unroll
-      for (int j = 0; j < MCG_HEAT_SPAN; ++j) {
-        const int L = level[r][j];
-        if (L >= min_level) {
-          const unsigned c = colour[L];
-          span_set_byte(w, j, heat_blend(span_byte(w, j), c & 255u, c >> 24));
-        }
-      }
-      span_store<4>(p, w, mode_y, span);
-    }
-    unsigned char* q = (unsigned char*)im.uv + (size_t)(py0 >> 1) * im.pitch_uv + px0;
-    unsigned w[4];
-    span_load<4>(q, w, mode_uv, span);
-#pragma unroll
-    for (int j = 0; j < MCG_HEAT_SPAN; j += 2) {
-      const int L = max(max(level[0][j], level[0][j + 1]), max(level[1][j], level[1][j + 1]));   // the pair's level: the highest of its four
-      if (L >= min_level) {
-        const unsigned c = colour[L], a = c >> 24;
-        span_set_byte(w, j, heat_blend(span_byte(w, j), (c >> 8) & 255u, a));
-        span_set_byte(w, j + 1, heat_blend(span_byte(w, j + 1), (c >> 16) & 255u, a));
-      }
-    }
-    span_store<4>(q, w, mode_uv, span);
-  }
+  heat_blend_span<Target>(im, px0, py0, level, colour, min_level);
 }
 
 template <class Target>

@@ -20,7 +20,7 @@ import os
 import numpy as np
 import torch
 
-from .attention import END_VIDEO_ENDED, KIND_HEAD, KIND_REGION, MAX_COLUMNS, MAX_ROWS, _attention_options, _dwell_options, _heat_options, open_episodes
+from .attention import END_VIDEO_ENDED, KIND_HEAD, KIND_REGION, MAX_COLUMNS, MAX_ROWS, _attention_options, _dwell_options, _heat_options, _surface_options, open_episodes
 from .engine import _upload_table
 from .arrows import OVERLAY_PALETTE, _anon_params, _label_options, _overlay_options, format_labels_host
 from .pipeline import ARROW_COLOR, _track_motion, _track_params, letterbox_geometry
@@ -879,8 +879,24 @@ def _add_heat(records, pipeline, device, num_frames, frame_hw, options):
     return state
 
 
+def _add_surface_heat(records, pipeline, device, num_frames, three_d, options):
+    """run_head_video(surface_heat=...): the 3-D hit points of records that hold their targets into the grids of regions3d, a
+    pipeline.surface_heat call per frame (the grids decay once per frame) -> the SurfaceHeatState on the device."""
+    state = pipeline.surface_heat_state(len(three_d['region_image']), grid=options['grid'], device=device)
+    regions = type(three_d['regions'])(*(torch.from_numpy(t).to(device) for t in three_d['regions']))      # up once, read where they are by every call
+    rows = [[] for _ in range(num_frames)]
+    for r in records:
+        for j, t in enumerate(r['frame_id']):
+            rows[t].append((r['target_hit3d'][j], r['target_kind'][j], r['target_region'][j]))
+    for heads in rows:
+        pipeline.surface_heat(np.asarray([h[0] for h in heads], np.float32).reshape(-1, 3), np.asarray([h[1] for h in heads], np.int32),
+                              np.asarray([h[2] for h in heads], np.int32), regions, state, radius=options['radius'], decay=options['decay'],
+                              device=device)
+    return state
+
+
 def run_head_video(engine, pipeline, frames, boxes_per_frame=None, max_len=100, batch_frames=448, expand=0.8, rgb=False, smooth=None, pixel_format='bgr',
-                   matrix='bt601', detections=None, track=None, attention=None, dwell=None, heat=None, anonymize=None, draw=None):
+                   matrix='bt601', detections=None, track=None, attention=None, dwell=None, heat=None, anonymize=None, surface_heat=None, draw=None):
     """Steps 3-4 of the demo from what its users hold -- the video's frames and one head box per person per frame -- to per-person gaze:
     segment_tracks (cell 1), the head windows cut, resized and normalised on the device (pipeline.head_crops: cell 4's crop arithmetic and
     ``cfg.data.test.pipeline[1:]``), run_tracks (cell 4's loop, batched), head_arrows (cell 5's end points).
@@ -953,11 +969,19 @@ def run_head_video(engine, pipeline, frames, boxes_per_frame=None, max_len=100, 
     needs ``draw`` (ValueError without): the faces under the records' head boxes are removed from the annotated frames
     (include/mcgaze_hip.h, "anonymised heads"), FIRST in every drawing batch -- before the heat map, the arrows, the overlay and the labels
     -- and on the copies: the crops were cut from the untouched frames, so ``frames`` and the records are exactly those of a run without
-    it.  It hides the heads the records hold: a head the detector missed stays visible."""
+    it.  It hides the heads the records hold: a head the detector missed stays visible.
+    surface_heat: None (everything above), True, or dict(grid=(32, 32), radius=1, decay=0, draw=True, full_scale=None, min_level=1); it
+    needs attention=dict(camera=..., regions3d=...) (ValueError without), and with draw=True it needs ``draw``: WHERE ON each planar region
+    the looks landed, as a grid of GW x GH cells in the region's own coordinates (pipeline.surface_heat, mcg_surface_heat_add;
+    include/mcgaze_hip.h, "surface heat map"), one call per frame over the records' target_hit3d.  The final grids, a numpy array int32
+    [M, GH, GW], are appended after everything returned above, and with draw=True in the dict they are drawn back onto their regions in
+    every annotated frame with the right perspective (pipeline.draw_surface_heat), after the image-plane heat map and under the arrows,
+    the overlay and the labels.  The grid and the radius are conventions, not tuned on data."""
     smooth = check_smooth('run_head_video', smooth)
     attention = _attention_options('run_head_video', attention)
     dwell = _dwell_options('run_head_video', dwell, attention)
     heat = _heat_options('run_head_video', heat, attention, draw is not None)
+    surface = _surface_options('run_head_video', surface_heat, attention, draw is not None)
     if anonymize is not None and draw is None:
         raise ValueError('run_head_video: anonymize changes the annotated frames; it needs draw')
     if anonymize is not None:
@@ -1043,8 +1067,12 @@ def run_head_video(engine, pipeline, frames, boxes_per_frame=None, max_len=100, 
     if dwell is not None:
         _add_dwell(out, pipeline, engine.device, len(boxes_per_frame), dwell)
     heat_state = None if heat is None else _add_heat(out, pipeline, engine.device, len(boxes_per_frame), _frame_hw(frames[0], pixel_format), heat)
+    three_d = None if surface is None else attention[2]['three_d']
+    surface_state = None if surface is None else _add_surface_heat(out, pipeline, engine.device, len(boxes_per_frame), three_d, surface)
+    last = () if surface is None else (_host(surface_state.heat),)      # appended after everything returned without the option
     if draw is None:
-        return out if heat is None else (out, _host(heat_state.heat))
+        got = out if heat is None else (out, _host(heat_state.heat))
+        return got if surface is None else ((got,) if heat is None else got) + last
     opts = {'copy': True, **({} if draw is True else dict(draw))}
     overlay = _overlay_options('run_head_video(draw=...)', opts.pop('overlay', None), True, attention)
     labels = _label_options('run_head_video(draw=...)', opts.pop('labels', None), True)
@@ -1082,6 +1110,11 @@ def run_head_video(engine, pipeline, frames, boxes_per_frame=None, max_len=100, 
             images = pipeline.draw_heat(images, heat_state, period=1, full_scale=heat['full_scale'], min_level=heat['min_level'], pixel_format=pixel_format,
                                         matrix=matrix, copy=copy, device=engine.device)
             opts = dict(drawing, copy=False)
+        if surface is not None and surface['draw']:   # after the image-plane map, under everything else (one camera: cam_period 1, the regions on every picture)
+            images = pipeline.draw_surface_heat(images, surface_state, three_d['cam'], three_d['regions'], three_d['region_image'], cam_period=1,
+                                                full_scale=surface['full_scale'], min_level=surface['min_level'], pixel_format=pixel_format, matrix=matrix,
+                                                copy=copy if opts is drawing else False, device=engine.device)
+            opts = dict(drawing, copy=False)
         if overlay is None:
             imgs, _ = pipeline.draw_arrows(images, boxes, gaze, image_of, pixel_format=pixel_format, matrix=matrix, device=engine.device, **opts)
         else:                                          # the records' own tables: a head's target is not read by the overlay, a region's is target_region
@@ -1100,7 +1133,7 @@ def run_head_video(engine, pipeline, frames, boxes_per_frame=None, max_len=100, 
             imgs, _ = pipeline.draw_labels(imgs, boxes, image_of, text, pixel_format=pixel_format, matrix=matrix, device=engine.device, **colors,
                                            **{k: v for k, v in labels.items() if k != 'fps'})
         annotated += imgs
-    return (out, annotated) if heat is None else (out, annotated, _host(heat_state.heat))
+    return ((out, annotated) if heat is None else (out, annotated, _host(heat_state.heat))) + last
 
 
 def dump_results(records, config_path, json_path, out_dir='results'):

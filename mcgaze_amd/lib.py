@@ -42,8 +42,10 @@ EXPORTS = ['mcg_abi_version', 'mcg_build_id', 'mcg_last_error', 'mcg_device_info
            'mcg_pointwise_stream', 'mcg_pointwise_dyn', 'mcg_pointwise_pair', 'mcg_draw_attention', 'mcg_draw_attention_nv12',
            'mcg_format_labels', 'mcg_draw_labels', 'mcg_draw_labels_nv12', 'mcg_gaze_heat_add', 'mcg_draw_heat', 'mcg_draw_heat_nv12',
            'mcg_anonymize_heads', 'mcg_anonymize_heads_nv12', 'mcg_roi_mark_blocks', 'mcg_inner_mark_blocks', 'mcg_conv3x3_wino_x3_blocks',
-           'mcg_conv3x3_wino_x3_frames', 'mcg_roi_mark_frames', 'mcg_deferred_pyramid_frame_state', 'mcg_gaze_targets_3d']
+           'mcg_conv3x3_wino_x3_frames', 'mcg_roi_mark_frames', 'mcg_deferred_pyramid_frame_state', 'mcg_gaze_targets_3d', 'mcg_surface_heat_add',
+           'mcg_draw_surface_heat', 'mcg_draw_surface_heat_nv12']
 LABEL_CHARS = 24                                                 # MCG_LABEL_CHARS
+SURFACE_CHART_BYTES = 160                                        # MCG_SURFACE_CHART_BYTES: a region's chart in the workspace of the surface entries
 LETTERBOX_U8, LETTERBOX_F16, LETTERBOX_F32 = 0, 1, 2             # enum order of include/mcgaze_hip.h
 
 
@@ -216,6 +218,9 @@ def load():
     lib.mcg_gaze_heat_add.argtypes = [vp, vp, vp, vp, vp, vp, i, vp, vp, i, i, i, i, i, i, i, i, vp, sz]
     lib.mcg_draw_heat.argtypes = [vp, vp, i, i, i, vp, vp, i, i, i, i, i, vp, i]
     lib.mcg_draw_heat_nv12.argtypes = lib.mcg_draw_heat.argtypes
+    lib.mcg_surface_heat_add.argtypes = [vp, vp, vp, vp, vp, vp, i, vp, i, vp, i, vp, vp, i, i, i, i, vp, sz]
+    lib.mcg_draw_surface_heat.argtypes = [vp, vp, i, i, i, vp, i, i, vp, i, vp, vp, i, i, vp, vp, i, i, vp, i, vp, sz]
+    lib.mcg_draw_surface_heat_nv12.argtypes = lib.mcg_draw_surface_heat.argtypes
     lib.mcg_anonymize_heads.argtypes = [vp, vp, i, i, i, vp, vp, i, C.c_double, i, i, i, i, u8p, vp, vp]
     lib.mcg_anonymize_heads_nv12.argtypes = lib.mcg_anonymize_heads.argtypes
     lib.mcg_gaze_dwell.argtypes =[vp, vp, vp, vp, vp, vp, i, i, i, i, i, vp, vp, i, vp, vp, vp, i, vp]

@@ -31,7 +31,7 @@ import torch
 
 from . import lib as L
 from .arrows import LABEL_CHARS, _anon_params, _label_background, _label_options, _overlay_options, _overlay_palette, heat_lut
-from .attention import KIND_HEAD, PolyRegions, PolyRegions3D, _attention_options, _dwell_options, _heat_options, region_label_rows
+from .attention import KIND_HEAD, PolyRegions, PolyRegions3D, _attention_options, _dwell_options, _heat_options, _surface_options, region_label_rows
 from .engine import _upload_table
 from .harness import _host, check_smooth
 from .head_detect import TRACK_HEADER_WORDS, TRACK_MAX_SLOTS, TRACK_SLOT_WORDS, _track_motion, _track_params, track_state_words
@@ -372,6 +372,16 @@ class LiveGaze:
     go on updating; None before the first tick.  With draw=True (it needs ``draw``; ValueError without; heat=True draws where draw does) the
     grid as it stands after a frame's looks is blended into that frame's pictures FIRST (pipeline.draw_heat with full_scale and min_level),
     under the arrows, the overlay and the labels.  Still no wait for the device, no copy to the host.
+    SURFACE HEAT.  ``surface_heat=None`` is everything above.  ``surface_heat=True`` or ``dict(grid=(32, 32), radius=1, decay=0, draw=True,
+    full_scale=None, min_level=1)`` (it needs attention=dict(camera=..., regions3d=...); ValueError without) accumulates WHERE ON each
+    planar region looks land, in the region's own coordinates (pipeline.surface_heat, mcg_surface_heat_add; include/mcgaze_hip.h, "surface
+    heat map"): per returned frame one call over that frame's rows -- target_hit3d, target_kind, target, mask = valid -- into one grid of
+    GW x GH cells per region of regions3d, counted through the cameras as ``target`` counts them; the grid and the radius are
+    conventions, not tuned on data.  Every tick gains ``surface_heat`` int32 [M, GH, GW] and ``surface_heat_peak`` int32 [M]: the LIVE
+    device tensors (``LiveGaze.surface_heat_state``, made with the object; the caller may set them).  With draw=True (it needs ``draw``;
+    ValueError without; surface_heat=True draws where draw does) the grids as they stand after a frame's looks are drawn back onto their
+    regions in that frame's pictures with the right perspective (pipeline.draw_surface_heat), AFTER the image-plane heat map and before
+    the arrows, the overlay and the labels.  Still no wait for the device, no copy to the host.
     ANONYMIZE.  ``anonymize=None`` is everything above.  ``anonymize=True`` or a dict of pipeline.anonymize_heads' options (expand, shape,
     cell, blocks, mode, color; it needs ``draw``; ValueError without) removes the faces from the returned frames (include/mcgaze_hip.h,
     "anonymised heads"): one call per tick that returns frames, over the kept copies, from head_box and image_of of the gated rows -- a row
@@ -381,7 +391,7 @@ class LiveGaze:
 
     def __init__(self, engine_or_model, pipeline, cameras, slots=16, clip_len=7, stride=4, expand=0.8, match_iou=0.3, max_age=5, smooth=None,
                  pixel_format='bgr', draw=False, matrix='bt601', rgb=False, person_threshold=0.5, max_decode_windows=None, lanes=None, motion=None,
-                 attention=None, dwell=None, overlay=None, labels=None, heat=None, anonymize=None):
+                 attention=None, dwell=None, overlay=None, labels=None, heat=None, anonymize=None, surface_heat=None):
         self.S, self.match_iou, self.max_age = _track_params(slots, match_iou, max_age)
         _track_motion(motion, 'LiveGaze')
         self.motion = motion
@@ -396,6 +406,7 @@ class LiveGaze:
         self.overlay = _overlay_options('LiveGaze', overlay, draw, attention)
         self.labels = _label_options('LiveGaze', labels, draw)
         self.heat, self.heat_state = _heat_options('LiveGaze', heat, attention, draw), None
+        self.surface_heat, self.surface_heat_state = _surface_options('LiveGaze', surface_heat, attention, draw), None
         if anonymize is not None and not draw:
             raise ValueError('LiveGaze: anonymize changes the returned frames; it needs draw')
         self.anonymize = None if anonymize is None else {} if anonymize is True else dict(anonymize)
@@ -436,6 +447,8 @@ class LiveGaze:
                                         region_image=up(three_d['region_image']), head_size=three_d['head_size'], frame=three_d['frame'])
             regions = PolyRegions(*map(up, regions)) if isinstance(regions, PolyRegions) else up(regions)      # (a polygon somewhere: the vertex form)
             self.attention = dict(options, regions=regions, region_image=up(region_image))
+        if self.surface_heat is not None:                        # one grid per region of regions3d, in the region's own coordinates
+            self.surface_heat_state = pipeline.surface_heat_state(len(three_d['region_image']), grid=self.surface_heat['grid'], device=self.dev)
         if self.dwell is not None:
             counted = attention[1] if self.attention3d is None else self.attention3d['region_image']
             self.dwell_state, self.region_frames = pipeline.dwell_state(n, device=self.dev), new(len(counted))
@@ -568,6 +581,20 @@ class LiveGaze:
                                     full_scale=o['full_scale'], min_level=o['min_level'], device=self.dev, **self.frame_options)
         return dict(heat=None if state is None else state.heat, heat_peak=None if state is None else state.peak)
 
+    def _surface_heat(self, out, k, images):
+        """surface_heat=: the 3-D hit points of each of the k frames handed out into the grids of their regions, and with draw the grids as
+        they then stand drawn back onto the regions in that frame's Q pictures (``images``: the kept copies, drawn in place) -> the tables
+        _emit adds."""
+        state, o, Q, a = self.surface_heat_state, self.surface_heat, self.Q, self.attention3d
+        for i in range(k):
+            self.pipe.surface_heat(out['target_hit3d'][i].reshape(-1, 3), out['target_kind'][i].reshape(-1), out['target'][i].reshape(-1), a['regions'],
+                                   state, mask=out['valid'][i].reshape(-1), radius=o['radius'], decay=o['decay'], device=self.dev)
+            if o['draw']:                                         # (picture p of a frame is camera p: no periods; the ramp as a HOST table, as _heat has it)
+                self.pipe.draw_surface_heat(images[i * Q:(i + 1) * Q], state, a['cam'], a['regions'], a['region_image'],
+                                            lut=heat_lut(None, self.frame_options['pixel_format'] == 'nv12', self.frame_options['matrix']),
+                                            full_scale=o['full_scale'], min_level=o['min_level'], device=self.dev, **self.frame_options)
+        return dict(surface_heat=state.heat, surface_heat_peak=state.peak)
+
     def tick(self, frames, boxes, counts):
         """One frame per camera and its detections -> the frames that became final (see the class)."""
         if self.finished:
@@ -640,6 +667,8 @@ class LiveGaze:
             self.pipe.anonymize_heads(images, out['head_box'].view(-1, 4), out['image_of'].view(-1), device=self.dev, **self.frame_options, **self.anonymize)
         if self.heat is not None:
             out.update(self._heat(out, k, images))
+        if self.surface_heat is not None:                        # after the image-plane heat map, before arrows, overlay and labels
+            out.update(self._surface_heat(out, k, images))
         if self.draw:
             if k:
                 gaze = out['fused_smooth' if smoothing else 'fused']

@@ -46,13 +46,15 @@ from .arrows import (ARROW_COLOR, ARROW_COORD, ARROW_SIDE, _arrow_colors, _arrow
                      arrow_segments, draw_arrows_host, segment_coverage)
 from .arrows import LABEL_CHARS, LABEL_FONT, _label_background, _label_ints, _label_params, _label_rate, _label_text, label_plan
 from .arrows import draw_labels_host, encode_labels, format_labels_host  # noqa: F401  (re-exported beside draw_arrows_host, for users of pipeline.*)
-from .arrows import HEAT_LUT, draw_heat_host, heat_lut  # noqa: F401
+from .arrows import HEAT_LUT, draw_heat_host, draw_surface_heat_host, heat_lut  # noqa: F401
 from .arrows import _anon_color, _anon_params, anonymize_heads_host, anonymize_plan_host  # noqa: F401
 from .attention import (HEAT_KINDS, HeatState, _heat_cell, _heat_grid, _heat_params, _heat_scale, gaze_heat_host,  # noqa: F401
                         heat_grid_shape)
 from .attention import PolyRegions, _check_counts, _holds_polygon, _poly_tables, _region_tables, _target_params, gaze_targets_host, region_polygons  # noqa: F401
 from .attention import _row_tables as _target_rows
 from .attention import MAX_CAMERAS, PolyRegions3D, _camera_table, _depth_table, _poly3d_tables, _target3d_params, gaze_targets_3d_host, regions_3d  # noqa: F401
+from .attention import (SURFACE_GRID, SURFACE_RADIUS, SurfaceHeatState, _surface_grid, _surface_grid_option, _surface_params,  # noqa: F401
+                        _surface_regions, surface_charts_host, surface_extent, surface_heat_host)
 from .attention import DWELL_ENTER, DWELL_EXIT, _dwell_counts, _dwell_params, _dwell_tables, gaze_dwell_host  # noqa: F401
 from .frame_cache import FrameCache, _DecodeProcs, decode_image  # noqa: F401
 from .head_detect import (DETECT_MAX_DET, LETTERBOX_PAD, LetterboxGeometry, _detect_params, _detect_shapes, _letterbox_dtype,  # noqa: F401
@@ -572,6 +574,7 @@ class DevicePipeline:
         self._label_fonts = {}                                    # draw_labels: device -> LABEL_FONT on it
         self._heat_workspaces = collections.OrderedDict()         # gaze_heat: (device, cells) -> scratch of mcg_gaze_heat_add
         self._heat_tables = collections.OrderedDict()             # draw_heat: the ramp per (device, format, matrix), a fixed scale per (device, C, value)
+        self._surface_workspaces = collections.OrderedDict()      # surface_heat, draw_surface_heat: (device, bytes) -> the charts and the scratch
 
     def _kept(self, cache, key, make):
         """cache[key], made the first time it is asked for; the least recently used of IMAGE_TABLES entries goes."""
@@ -1293,6 +1296,173 @@ class DevicePipeline:
             vp = C.c_void_p
             L.check(entry(vp(call.main.cuda_stream), vp(images_ptr), len(out), h_max, w_max, vp(state.heat.data_ptr()), vp(full.data_ptr()), cams, GH, GW,
                           state.cell_shift, int(period), vp(lut_ptr), min_level), entry.__name__)
+        return out
+
+    def surface_heat_state(self, num_regions, grid=SURFACE_GRID, device='cuda:0'):
+        """The empty state of ``surface_heat`` for ``num_regions`` planar regions: SurfaceHeatState(heat int32 [num_regions, GH, GW] zeros,
+        peak int32 [num_regions] zeros) on the device.  grid: (GW, GH) cells over each region's chart, 1 .. 1024 a side (ValueError); the
+        default of 32 x 32 is a convention, not tuned on data."""
+        GW, GH = _surface_grid_option('surface_heat_state', grid)
+        M, GH, GW = _surface_grid('surface_heat_state', (int(num_regions), GH, GW))
+        dev = _device(device, 'mcg_surface_heat_add')
+        return SurfaceHeatState(torch.zeros(M, GH, GW, dtype=torch.int32, device=dev), torch.zeros(M, dtype=torch.int32, device=dev))
+
+    def _surface_state(self, who, state, dev):
+        """``state`` as surface_heat and draw_surface_heat take it, checked (TypeError / ValueError) -> (M, GH, GW)."""
+        if not (isinstance(state, SurfaceHeatState) and all(isinstance(t, torch.Tensor) and t.device == dev and t.dtype == torch.int32 and t.is_contiguous()
+                                                            for t in state)):
+            raise TypeError(f'{who}: state is a SurfaceHeatState of contiguous int32 tensors on {dev} (surface_heat_state makes it; it is updated in place)')
+        M, GH, GW = _surface_grid(who, tuple(state.heat.shape))
+        if tuple(state.peak.shape) != (M,):
+            raise ValueError(f'{who}: the peak of {M} regions is [{M}], got {tuple(state.peak.shape)}')
+        return M, GH, GW
+
+    @staticmethod
+    def _surface_region_tables(who, regions, region_image, M, dev, with_image):
+        """The region tables of the surface entries -> (xyz, start, region_image or None, V): all on the host (checked numpy arrays, which
+        go up through the staging ring) or, with one of them on the device, tensors on ``dev`` (only their shapes are checked).  The call
+        is made inside the call's scope and first there."""
+        if regions is None:
+            raise ValueError(f'{who}: regions are required: the list of regions_3d or a PolyRegions3D')
+        there = any(_on_device(t) for t in ((*regions, region_image) if isinstance(regions, PolyRegions3D) else (region_image,)))
+        if not there:
+            xyz, start, region_image = _poly3d_tables(who, regions, region_image)
+        else:
+            if not isinstance(regions, PolyRegions3D):
+                regions = regions_3d(regions)
+            xyz, start = _there(regions.xyz, dev, torch.float32), _there(regions.start, dev, torch.int32)
+            if xyz.ndim != 2 or xyz.shape[1] != 3 or start.ndim != 1 or start.shape[0] < 1:
+                raise ValueError(f'{who}: PolyRegions3D is xyz [V, 3] and start [m + 1], got {tuple(xyz.shape)} and {tuple(start.shape)}')
+            m = int(start.shape[0]) - 1
+            if with_image:
+                region_image = torch.full((m,), -1, dtype=torch.int32, device=dev) if region_image is None else _there(region_image, dev, torch.int32)
+                if tuple(region_image.shape) != (m,):
+                    raise ValueError(f'{who}: region_image must be [{m}], one per region; got {tuple(region_image.shape)}')
+        if int(start.shape[0]) - 1 != M:
+            raise ValueError(f'{who}: the state holds {M} grids for {int(start.shape[0]) - 1} regions')
+        _check_counts(who, 0, M, int(xyz.shape[0]))
+        return xyz, start, (region_image if with_image else None), int(xyz.shape[0])
+
+    def _surface_workspace(self, dev, nbytes):
+        """The workspace of the surface entries: the charts and, for surface_heat, the scratch grid -- kept per device and size."""
+        return self._kept(self._surface_workspaces, (dev.index, nbytes), lambda: torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=dev))
+
+    def surface_heat(self, hit3d, kind, target, regions, state, flags=None, mask=None, radius=SURFACE_RADIUS, decay=0, device='cuda:0', stream=None):
+        """Where ON a planar region looks land, accumulated on the device (mcg_surface_heat_add: the charts planned, the workspace cleared,
+        a scatter with integer atomics, a per-cell pass) -- ``attention.surface_heat_host`` bit for bit: every row that looks at a region
+        (kind 2) has its 3-D hit point taken into that region's chart -- the bounding rectangle of the polygon in the frame of its first
+        edge and the normal, stretched over the grid -- and adds a pyramid of (radius + 1 - |dx|) (radius + 1 - |dy|) around its cell to
+        the region's grid.  The grid is in the surface's own coordinates: it does not move when the camera does.
+
+        hit3d [n,3], kind, target [n] -- gaze_targets_3d's results --, flags / mask [n] or None (a row counts where its flag is 0 and its
+        mask is not): CUDA tensors are read where they are, numpy tables go up through the staging ring (a host table next to a device one
+        is moved with torch).  regions: the list of ``regions_3d`` or a PolyRegions3D, host or device, in camera coordinates -- the
+        regions gaze_targets_3d searched.  state: ``surface_heat_state``'s, UPDATED IN PLACE: heat decays by h >> decay once per call (0:
+        off), gains the taps and saturates at 2^31 - 1; peak becomes each region's maximum.  radius 1 is a convention, not tuned on data.
+        Options and shapes are checked on the host before anything is launched (TypeError / ValueError); what the tables hold is never an
+        error and is never read back.  With device tables the call touches the host nowhere once a first call has allocated the workspace,
+        and can be captured in a graph.
+        -> state."""
+        lib = L.load()
+        who = 'surface_heat'
+        dev = _device(device, 'mcg_surface_heat_add')
+        M, GH, GW = self._surface_state(who, state, dev)
+        radius, decay = _surface_params(who, radius, decay)
+        tables = [('hit3d', hit3d, torch.float32), ('kind', kind, torch.int32), ('target', target, torch.int32), ('flags', flags, torch.int32),
+                  ('mask', mask, torch.int32)]
+        there = any(_on_device(t) for _, t, _ in tables)
+        if not there:                                             # all on the host: checked here, staged below
+            host = []
+            for name, t, dtype in tables:
+                if t is None:
+                    host.append(None)
+                    continue
+                a = np.asarray(_host_array(t))
+                if name != 'hit3d' and a.size and a.dtype.kind not in 'iub':
+                    raise TypeError(f'{who}: {name} must hold integers, got {a.dtype}')
+                host.append(np.ascontiguousarray(a.reshape(-1, 3) if name == 'hit3d' else a.reshape(-1), dtype=np.float32 if name == 'hit3d' else np.int32))
+        with _call_scope(self._ring, dev, stream) as call:
+            xyz, start, _, V = self._surface_region_tables(who, regions, None, M, dev, False)
+            moved = [None if t is None else _there(t, dev, dtype) for _, t, dtype in tables] if there else host
+            if moved[0] is None or moved[1] is None or moved[2] is None:
+                raise ValueError(f'{who}: hit3d, kind and target are required')
+            n = int(moved[0].shape[0])
+            for (name, _, _), t in zip(tables, moved):
+                if t is not None and tuple(t.shape) != ((n, 3) if name == 'hit3d' else (n,)):
+                    raise ValueError(f'{who}: {name} must be {[n, 3] if name == "hit3d" else [n]}, got {tuple(t.shape)}')
+            if n > 65536:
+                raise ValueError(f'{who}: at most 65536 rows per call (got {n})')
+            work = self._surface_workspace(dev, L.SURFACE_CHART_BYTES * M + 4 * M * GH * GW)
+            empty = lambda t: t is None or not (t.size if isinstance(t, np.ndarray) else t.numel())
+            _, ptrs = call.upload([], [None if empty(t) else t for t in moved] + [None if empty(xyz) else xyz, start])
+            vp = C.c_void_p
+            L.check(lib.mcg_surface_heat_add(vp(call.main.cuda_stream), *(vp(p) for p in ptrs[:5]), n, vp(ptrs[5]), V, vp(ptrs[6]), M,
+                                             vp(state.heat.data_ptr()), vp(state.peak.data_ptr()), GH, GW, radius, decay, vp(work.data_ptr()),
+                                             8 * work.numel()), 'mcg_surface_heat_add')
+        return state
+
+    def draw_surface_heat(self, images, state, cam, regions, region_image=None, region_period=0, cam_period=0, lut=None, full_scale=None, min_level=1,
+                          pixel_format='bgr', matrix='bt601', copy=False, device='cuda:0', stream=None):
+        """The surface heat maps drawn back onto their regions on the device, with the right perspective (mcg_draw_surface_heat /
+        mcg_draw_surface_heat_nv12: the charts planned, then one launch over every pixel) -- ``arrows.draw_surface_heat_host`` bit for
+        bit: every pixel's ray through the lens (``cam`` [fx, fy, cx, cy], or [C,4] with row p or p % cam_period for picture p) meets the
+        nearest region that covers it, the pixel's level is interpolated between the cell centres of that region's grid and scaled so that
+        ``full_scale`` is level 255, coloured by ``lut`` and blended with its alpha.
+
+        images, pixel_format, matrix, copy, lut, full_scale, min_level: ``draw_heat``'s, staging and in-place rule included; full_scale
+        None is ``state.peak``, each region's own maximum, read on the device.  state: surface_heat's.  regions: the list of
+        ``regions_3d`` or a PolyRegions3D in camera coordinates; region_image [M] (None: every picture) and region_period as gaze_targets
+        takes them, with the picture's index in image_of's place.  cam, regions and region_image may be host or device tables; device
+        tables are read where they are.  A picture whose camera is missing or not finite is handed back untouched.  With device frames drawn
+        in place, device tables and the frame table cached by a first call, the call touches the host nowhere and can be captured in a graph.
+        -> the images on the device, in order."""
+        lib = L.load()
+        who = 'draw_surface_heat'
+        nv12, _ = _pixel_format(pixel_format, matrix)
+        full_scale, min_level = _heat_scale(who, full_scale, min_level)
+        _, _, region_period = _target_params(0.0, None, region_period, who)
+        _, _, cam_period = _target3d_params(0.24, 'eye', cam_period, who)
+        entry = lib.mcg_draw_surface_heat_nv12 if nv12 else lib.mcg_draw_surface_heat
+        dev = _device(device)                                     # the surfaces are checked whatever the device: a bad one is the caller's first error
+        images = list(images)
+        planes = [_nv12_planes(k, im, dev) for k, im in enumerate(images)] if nv12 else None
+        dev = _device(dev, entry.__name__)
+        if not len(images):
+            raise ValueError(f'{who}: no frames')
+        table, _ = _image_table(images, dev, planes)              # every frame is checked before the first clone or upload
+        M, GH, GW = self._surface_state(who, state, dev)
+        if not _on_device(cam):
+            cam = _camera_table(who, cam)
+        if _on_device(lut):
+            if not (lut.device == dev and lut.dtype == torch.uint8 and tuple(lut.shape) == (256, 4) and lut.is_contiguous()):
+                raise TypeError(f'{who}: a device lut is a contiguous uint8 [256, 4] tensor on {dev}')
+        elif lut is not None:
+            lut = heat_lut(lut, nv12, matrix)                     # a host table: checked, converted, staged with the call
+        with _call_scope(self._ring, dev, stream) as call:
+            xyz, start, region_image, V = self._surface_region_tables(who, regions, region_image, M, dev, True)
+            if _on_device(cam):
+                cam = _there(cam, dev, torch.float32)
+                cam = cam.view(1, 4) if tuple(cam.shape) == (4,) else cam
+                if cam.ndim != 2 or cam.shape[1] != 4 or not 1 <= cam.shape[0] <= MAX_CAMERAS:
+                    raise ValueError(f'{who}: the camera table is [fx, fy, cx, cy] or [C, 4] with C in 1 .. {MAX_CAMERAS}, got {tuple(cam.shape)}')
+            out, pixels, in_place = _arrow_targets(images, planes, copy, dev)
+            if not in_place:                                      # the table of the tensors that are drawn into
+                table, _ = _image_table(out, dev, [_nv12_planes(k, o, dev) for k, o in enumerate(out)] if nv12 else None)
+            h_max, w_max = int(table['h'].max()), int(table['w'].max())
+            if h_max > ARROW_SIDE or w_max > ARROW_SIDE:
+                raise ValueError(f'{who}: frames of at most {ARROW_SIDE} pixels a side, got {h_max} x {w_max}')
+            if lut is None:                                       # the ramp is data the pipeline brings: uploaded once per device and format, and kept
+                lut = self._kept(self._heat_tables, (dev.index, 'lut', nv12, matrix), lambda: torch.from_numpy(heat_lut(None, nv12, matrix).copy()).to(dev))
+            full = state.peak if full_scale is None else self._kept(self._heat_tables, (dev.index, 'full', M, full_scale),
+                                                                     lambda: torch.full((M,), full_scale, dtype=torch.int32, device=dev))
+            work = self._surface_workspace(dev, L.SURFACE_CHART_BYTES * M)
+            empty = lambda t: not (t.size if isinstance(t, np.ndarray) else t.numel())
+            images_ptr, lut_ptr, cam_ptr, xyz_ptr, start_ptr, ri_ptr = self._drawing_upload(
+                call, nv12, table, pixels, in_place, (lut, cam, None if empty(xyz) else xyz, start, region_image))
+            vp = C.c_void_p
+            L.check(entry(vp(call.main.cuda_stream), vp(images_ptr), len(out), h_max, w_max, vp(cam_ptr), int(cam.shape[0]), cam_period, vp(xyz_ptr), V,
+                          vp(start_ptr), vp(ri_ptr), M, region_period, vp(state.heat.data_ptr()), vp(full.data_ptr()), GH, GW, vp(lut_ptr), min_level,
+                          vp(work.data_ptr()), 8 * work.numel()), entry.__name__)
         return out
 
     def anonymize_heads(self, images, boxes, image_of, expand=0.125, shape='ellipse', cell=None, blocks=8, mode='mosaic', color=(0, 0, 0),

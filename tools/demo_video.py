@@ -6,7 +6,7 @@ usage: demo_video.py FRAMES_DIR LABELS_DIR CONFIG CHECKPOINT --out gaze.json [--
                      [--batch-frames 448] [--head-class 1] [--ext jpg] [--smooth ALPHA] [--nv12 WxH FILE] [--matrix bt601] [--draw OUT] [--overlay] [--labels [SCALE]] [--fps NUM[/DEN]]
                      [--track [--slots 16] [--match-iou 0.3] [--max-age 5]] [--track-motion [GAIN[,DECAY]]]
                      [--color B,G,R] [--predictions DIR --in-shape HxW [--conf-thres 0.25] [--iou-thres 0.45]]
-                     [--detector MODULE:FACTORY [--img-size 640] [--half]] [--attention [--regions FILE.json] [--camera FX,FY,CX,CY [--regions3d FILE.json] [--head-size M] [--gaze-frame eye|camera]] [--dwell [ENTER,EXIT]] [--heat [CELL,RADIUS]] [--heat-out FILE.npy]]
+                     [--detector MODULE:FACTORY [--img-size 640] [--half]] [--attention [--regions FILE.json] [--camera FX,FY,CX,CY [--regions3d FILE.json] [--head-size M] [--gaze-frame eye|camera]] [--dwell [ENTER,EXIT]] [--heat [CELL,RADIUS]] [--heat-out FILE.npy] [--surface-heat [GW,GH,RADIUS]] [--surface-heat-out FILE.npy]]
 
 FRAMES_DIR holds 0.<ext>, 1.<ext>, ... (the demo's `frames/`), LABELS_DIR holds 0.txt, 1.txt, ... with lines `class x1 y1 x2 y2` in pixels
 (the demo's `result/labels/`); a frame without a label file shows no head.  CONFIG is the L2CS config, whose test pipeline the demo runs
@@ -52,6 +52,12 @@ on data).
 device): the hit points of every frame splatted into a grid of CELL-pixel cells (a power of two, default 8) with a radius of RADIUS cells
 (default 2).  With --draw the final grid is blended into every annotated frame, under the arrows (pipeline.draw_heat); --heat-out FILE.npy
 writes the grid, int32 [1, GH, GW].
+--surface-heat [GW,GH,RADIUS], with --camera and --regions3d: WHERE ON each planar region the looks land
+(harness.run_head_video(surface_heat=...), pipeline.surface_heat on the device): the 3-D hit points of every frame taken into the region's
+own coordinates and splatted into a grid of GW x GH cells per region (default 32,32; radius 1 -- conventions, not tuned on data).  With
+--draw the final grids are drawn back onto the regions in every annotated frame with the right perspective
+(pipeline.draw_surface_heat); --surface-heat-out FILE.npy writes the grids, int32 [M, GH, GW] (attention.surface_extent gives each
+region's width and height in metres, for showing a grid at the right aspect).
 --anonymize [BLOCKS], with --draw: the faces under the head boxes are removed from the written frames on the device
 (harness.run_head_video(anonymize=...), pipeline.anonymize_heads), before anything is drawn over them -- a mosaic of about BLOCKS cells
 across every head (default 8) under the ellipse inscribed in the grown box; --anonymize-shape box covers the whole box.  It hides the heads
@@ -207,6 +213,10 @@ def main(argv=None):
     ap.add_argument('--heat', nargs='?', const='', default=None, metavar='CELL,RADIUS',
                     help='--attention with where the looks land: a heat map of CELL-pixel cells (8) and a splat of RADIUS cells (2), drawn under --draw')
     ap.add_argument('--heat-out', default=None, metavar='FILE.npy', help='write the final grid of --heat, int32 [1, GH, GW]')
+    ap.add_argument('--surface-heat', nargs='?', const='', default=None, metavar='GW,GH,RADIUS',
+                    help='--camera and --regions3d with where ON each region the looks land: a grid of GW x GH cells (32,32) over every region and a '
+                         'splat of RADIUS cells (1) -- conventions, not tuned on data --, drawn back onto the regions under --draw')
+    ap.add_argument('--surface-heat-out', default=None, metavar='FILE.npy', help='write the final grids of --surface-heat, int32 [M, GH, GW]')
     ap.add_argument('--anonymize', nargs='?', const=8, type=int, default=None, metavar='BLOCKS',
                     help='--draw with the faces removed first: a mosaic of about BLOCKS cells across every head (8)')
     ap.add_argument('--anonymize-shape', default='ellipse', choices=['ellipse', 'box'], help='what of the grown head box --anonymize covers')
@@ -229,6 +239,19 @@ def main(argv=None):
         if values is None or len(values) > 2:
             raise SystemExit(f'--heat takes CELL or CELL,RADIUS, got {a.heat!r}')
         heat = dict(zip(('cell', 'radius'), values), draw=a.draw is not None)
+    if (a.surface_heat is not None or a.surface_heat_out is not None) and (a.camera is None or a.regions3d is None):
+        raise SystemExit('--surface-heat and --surface-heat-out belong to --attention --camera --regions3d')
+    if a.surface_heat_out is not None and a.surface_heat is None:
+        a.surface_heat = ''
+    surface = None
+    if a.surface_heat is not None:
+        try:
+            values = [int(v) for v in a.surface_heat.split(',')] if a.surface_heat else []
+        except ValueError:
+            values = None
+        if values is None or len(values) not in (0, 2, 3):
+            raise SystemExit(f'--surface-heat takes GW,GH or GW,GH,RADIUS, got {a.surface_heat!r}')
+        surface = dict(draw=a.draw is not None, **(dict(grid=tuple(values[:2])) if values else {}), **(dict(radius=values[2]) if len(values) == 3 else {}))
     if a.regions is not None and not a.attention:
         raise SystemExit('--regions belongs to --attention')
     if a.dwell is not None and not a.attention:
@@ -311,8 +334,13 @@ def main(argv=None):
     pipe = DevicePipeline(model.cfg.data.test.pipeline)
     res = harness.run_head_video(model.engine(), pipe, frames, per_frame, max_len=a.max_len, batch_frames=a.batch_frames, rgb=True,
                                  smooth=a.smooth, pixel_format='bgr' if a.nv12 is None else 'nv12', matrix=a.matrix, detections=detections, draw=draw,
-                                 track=track, attention=attention, dwell=dwell, heat=heat, anonymize=anonymize)
+                                 track=track, attention=attention, dwell=dwell, heat=heat, anonymize=anonymize, surface_heat=surface)
     as_json = lambda v: list(v) if isinstance(v, tuple) else v
+    if surface is not None:                               # the grids come last, after everything a run without the option returns
+        res, grids = res[:-1], res[-1]
+        res = res[0] if len(res) == 1 else res
+        if a.surface_heat_out is not None:
+            np.save(a.surface_heat_out, grids)
     if heat is not None:
         res, grid = res[:-1], res[-1]
         res = res[0] if draw is None else res
